@@ -8,7 +8,9 @@ dt 0.1, maccormackOurs with strength 0.6, ConvNet projection (3-D `default` topo
 the reference ships no 3-D model), plus a procedural voxel obstacle standing in for the bunny binvox
 (not in the reference tree). One "step" = one tfluids.simulate() call on the whole grid; fp32.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]      (N>1: launched by torch.distributed.run)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]      (N>1: launched by torch.distributed.run)
+
+K is the number of timed steps in all; --dump-outputs DIR writes what the last of them computed (see dump_outputs).
 
 N = 1: the whole 128^3 grid on one GPU through ONE C-ABI call per step (tfl_simulate_step).
 N > 1: STRONG scaling of the same 128^3 grid -- the metric's 1/2/4/8 series: z-slabs of 128/N planes (+4 halo planes per
@@ -77,6 +79,12 @@ ALG_BYTES_PER_CELL = {
     # round 6, z-slab step only (advect_pair3.hip): the passes A / the passes B of advectScalar AND advectVel as one launch each
     "k_adv_fwd_pair": 24 + 28, "k_adv_bwd_pair": 28 + 40,
 }
+
+
+MIN_BLOCK_STEPS = 20          # a timed block shorter than this measures its two barriers as much as the steps
+DUMP_FIELDS = ("pDiv", "UDiv", "density")     # what simulate() leaves in the caller's batch
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 20240229
 
 
 def build_scene(res_xy, z_total, layout, device):
@@ -283,6 +291,26 @@ def make_stepper(res, world, rank, dev, model, scene):
     return batch, mconf, step, None
 
 
+def dump_outputs(out_dir, batch, layout, rank, world):
+    """--dump-outputs: pDiv, UDiv and density as float32 .npy files under out_dir (one rank: <name>.npy; z-slabs: each rank its
+    owned planes as <name>_rank<r>.npy). A field that would take the files past DUMP_BUDGET_BYTES is replaced by a fixed
+    sample of its flat indices (torch.Generator seeded with DUMP_SAMPLE_SEED, drawn on the host, the same for every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    fields = [(k, batch[k] if layout is None else layout.owned(batch[k])) for k in DUMP_FIELDS]
+    total = sum(t.numel() * 4 for _, t in fields)
+    budget = DUMP_BUDGET_BYTES // world
+    for k, t in fields:
+        flat = t.detach().reshape(-1).to(torch.float32)
+        if total > budget:
+            m = max(1, flat.numel() * budget // total)
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randint(flat.numel(), (m,), generator=g).sort().values
+            arr = flat[idx.to(flat.device)].cpu().numpy()
+        else:
+            arr = flat.reshape(t.shape).cpu().numpy()
+        np.save(os.path.join(out_dir, (k if world == 1 else "%s_rank%d" % (k, rank)) + ".npy"), np.ascontiguousarray(arr))
+
+
 def measured_hbm_GBps(dev, mib=1024, reps=10):
     """read + write rate of a 1 GiB device copy by the library's own float4 kernel (k_stream_copy, stencil.hip), timed
     per launch with the built-in HIP-event profiler: what this box's HBM delivers to a streaming kernel."""
@@ -433,11 +461,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--res", type=int, default=128)
     ap.add_argument("--preroll", type=int, default=16, help="untimed steps that develop the plume before warm-up")
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps each; ms_per_step = their median")
+    ap.add_argument("--blocks", type=int, default=5, help="the --steps timed steps run as at most this many blocks of at least "
+                    "%d steps each; ms_per_step = the median block's time per step" % MIN_BLOCK_STEPS)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-config5", action="store_true", help="skip the extra 256^3 (BASELINE config 5) measurement")
     ap.add_argument("--no-configs", action="store_true", help="skip BASELINE configs 1-3")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (pDiv, UDiv, density) "
+                    "as DIR/<name>.npy, float32, at most %d MB in all" % (DUMP_BUDGET_BYTES // 10 ** 6))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher around it: become the launcher (one rank per GPU, this node only)
@@ -506,10 +539,13 @@ def main():
 
     for _ in range(args.preroll + args.warmup):
         step()
-    # EXACTLY --steps steps per timed block, barrier + synchronize on both sides; --blocks blocks back to back. The line
-    # reports the MEDIAN block (box-to-box and run-to-run noise on this pool is +-5 %, a round's gains are of that order)
-    # with the fastest and slowest beside it.
-    block_s = sorted(timed(step, args.steps) for _ in range(max(1, args.blocks)))
+    # EXACTLY --steps timed steps in all, cut into at most --blocks blocks of at least MIN_BLOCK_STEPS steps, barrier +
+    # synchronize on both sides of each block. The line reports the MEDIAN block's time per step (box-to-box and run-to-run
+    # noise on this pool is +-5 %, a round's gains are of that order) with the fastest and slowest beside it; block_s and
+    # elapsed are block times scaled to --steps steps.
+    nblocks = max(1, min(args.blocks, args.steps // MIN_BLOCK_STEPS))
+    block_steps = [args.steps // nblocks + (1 if i < args.steps % nblocks else 0) for i in range(nblocks)]
+    block_s = sorted(timed(step, n) * args.steps / n for n in block_steps)
     elapsed = block_s[len(block_s) // 2] if len(block_s) % 2 else 0.5 * (block_s[len(block_s) // 2 - 1] + block_s[len(block_s) // 2])
     assert bool(torch.isfinite(batch["UDiv"]).all()), "simulation blew up"
     # the two silent-failure counters of the path, read AFTER the timed region (both synchronise): activations the fp16-split
@@ -519,6 +555,9 @@ def main():
     trace_errors = int(tfluids.traceErrors(batch["UDiv"]))
     assert range_errors == 0, "fp16 range errors in the timed region: %d blocks clamped an activation" % range_errors
     assert trace_errors == 0, "line-trace invariant errors in the timed region: %d" % trace_errors
+    if args.dump_outputs:
+        # what the caller of the timed path holds after the last timed step, before anything below steps the state again
+        dump_outputs(args.dump_outputs, sim.batch if sim is not None else batch, sim.lay if sim is not None else None, rank, world)
 
     total_cells = res ** 3
     owned_planes = res // world
@@ -750,7 +789,7 @@ def main():
         "metric": "simulate_mcells_per_s", "value": total_cells * args.steps / elapsed / 1e6, "unit": "Mcells/s",
         "steps_per_s": args.steps / elapsed, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": ms, "ms_per_step_min": block_s[0] / args.steps * 1e3, "ms_per_step_max": block_s[-1] / args.steps * 1e3,
-        "timed_blocks": len(block_s), "sum_kernel_ms": sum_kernel_ms, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+        "timed_blocks": len(block_s), "timed_block_steps": block_steps, "sum_kernel_ms": sum_kernel_ms, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
         "dtype_note": "every operator computes in fp32; the 3-D conv stack multiplies fp32 values held as fp16 hi/lo pairs on the "
                       "matrix cores with fp32 accumulation (conv_mfma16.hip); evidence in this line: conv_witness_ratio (error vs an "
                       "fp64 convolution / PyTorch-fp32's, cpu_baseline.conv_witness), range_errors = 0, and conv_exact_fp32 = the same "

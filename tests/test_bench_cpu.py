@@ -110,3 +110,76 @@ def test_bench_gpus_2_over_real_rccl_with_ranks_sharing_the_gpu(graph):
     assert "native RCCL send/recv" in line["config"]["decomposition"], line["config"]["decomposition"]
     issued = line["config"]["rank_step"]["issued_as"]
     assert ("HIP graph" in issued) == (graph == "1"), issued
+
+
+def test_dump_outputs_writes_the_callers_fields_whole_or_as_a_fixed_sample(tmp_path):
+    """--dump-outputs: float32 <name>.npy per field of simulate()'s batch; past the byte budget every field becomes the same
+    seeded sample of its flat indices (two runs, two identical files), and the files stay inside the budget."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(3)
+    batch = {k: torch.randn(1, c, 8, 8, 8, generator=g) for k, c in (("pDiv", 1), ("UDiv", 3), ("density", 1))}
+    batch["flags"] = torch.ones(1, 1, 8, 8, 8)
+    bench.dump_outputs(str(tmp_path / "whole"), batch, None, 0, 1)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["UDiv.npy", "density.npy", "pDiv.npy"]
+    for k in bench.DUMP_FIELDS:
+        a = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, batch[k].numpy())
+
+    old = bench.DUMP_BUDGET_BYTES
+    bench.DUMP_BUDGET_BYTES = 5 * 512 * 4 // 2          # half of the 5 * 8^3 floats
+    try:
+        for d in ("s1", "s2"):
+            bench.dump_outputs(str(tmp_path / d), batch, None, 0, 1)
+    finally:
+        bench.DUMP_BUDGET_BYTES = old
+    nbytes = 0
+    for k in bench.DUMP_FIELDS:
+        a, b = np.load(tmp_path / "s1" / (k + ".npy")), np.load(tmp_path / "s2" / (k + ".npy"))
+        assert a.dtype == np.float32 and a.ndim == 1 and np.array_equal(a, b)
+        assert np.isin(a, batch[k].numpy().reshape(-1)).all()
+        nbytes += a.nbytes
+    assert 0 < nbytes <= 5 * 512 * 4 // 2
+
+
+def test_dump_outputs_of_a_slab_holds_the_owned_planes_per_rank(tmp_path):
+    import numpy as np
+    import torch
+    import bench
+    from fluidnet_amd.dist import SlabLayout
+    lay = SlabLayout(16, 2, 1)
+    batch = {k: torch.arange(c * (lay.hi - lay.lo) * 16, dtype=torch.float32).view(1, c, lay.hi - lay.lo, 4, 4)
+             for k, c in (("pDiv", 1), ("UDiv", 3), ("density", 1))}
+    bench.dump_outputs(str(tmp_path), batch, lay, 1, 2)
+    assert sorted(os.listdir(tmp_path)) == ["UDiv_rank1.npy", "density_rank1.npy", "pDiv_rank1.npy"]
+    assert np.array_equal(np.load(tmp_path / "UDiv_rank1.npy"), lay.owned(batch["UDiv"]).numpy())
+
+
+def test_bench_refuses_zero_steps():
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--steps" in p.stderr
+
+
+@pytest.mark.gpu
+def test_bench_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    """--steps K is the number of timed steps in all (here two blocks, 21 + 20); --dump-outputs writes the whole 64^3 state
+    the last of them left in the batch."""
+    import sys
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "41", "--warmup", "1", "--preroll", "2",
+                        "--res", "64", "--no-config5", "--no-configs", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 41 and line["timed_block_steps"] == [21, 20] and line["ms_per_step"] > 0
+    shapes = {"pDiv": (1, 1, 64, 64, 64), "UDiv": (1, 3, 64, 64, 64), "density": (1, 1, 64, 64, 64)}
+    assert sorted(os.listdir(tmp_path)) == sorted(k + ".npy" for k in shapes)
+    for k, shape in shapes.items():
+        a = np.load(tmp_path / (k + ".npy"))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), k
+    assert np.abs(np.load(tmp_path / "UDiv.npy")).max() > 0
