@@ -59,6 +59,54 @@ __global__ __launch_bounds__(256) void k_jacobi(Dom d, const float* __restrict__
   }
 }
 
+// ---- one sweep on a z-slab (tfl_simulate_step_slab, simMethod = 'jacobi') ----------------------------------------------------
+// The planes [w0, w0 + n0) of the LOCAL array only: a slab rank sweeps exactly the planes whose inputs are valid since the last
+// exchange (the window schedule: csrc/simulate.cpp). Domain walls are tested in GLOBAL z (Dom::zg / Zg, tfl_set_z_origin);
+// the local test beside it only decides at the array ends of a cut, planes that no window of the step contains (they lie
+// >= one halo depth below the owned range) -- it keeps every tap inside the array whatever window a caller passes.
+// Per cell: k_jacobi<true, false> character for character (obstacle substitution, p1 + ... + p6 + dv, a true / 6.0f; the
+// library is built with -ffp-contract=off), so the cut solve equals the un-cut one bit for bit.
+__global__ __launch_bounds__(256) void k_jacobi_slab(Dom d, const float* __restrict__ pp, const float* __restrict__ flags,
+                                                     const float* __restrict__ div, float* __restrict__ p) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int j = blockIdx.y * blockDim.y + threadIdx.y;
+  int b, k; dom_bk(d, b, k);
+  const long long cells = d.sc;
+  if (i < d.X && j < d.Y) {
+    pp += b * cells; flags += b * cells; div += b * cells; p += b * cells;
+    const int o = TFL_AT(d, i, j, k);
+    const int kg = k + d.zg;
+    const bool inner = i >= 1 && i <= d.X - 2 && j >= 1 && j <= d.Y - 2 && kg >= 1 && kg <= d.Zg - 2 && k >= 1 && k <= d.Z - 2;
+    const int sx = inner ? 1 : 0, sy = inner ? d.sy : 0, sz = inner ? d.sz : 0;
+    const int fc = (int)flags[o];
+    const float c = pp[o], dv = div[o];
+    float p1 = pp[o - sx], p2 = pp[o + sx], p3 = pp[o - sy], p4 = pp[o + sy];
+    float p5 = pp[o - sz], p6 = pp[o + sz];
+    const int f1 = (int)flags[o - sx], f2 = (int)flags[o + sx], f3 = (int)flags[o - sy], f4 = (int)flags[o + sy];
+    const int f5 = (int)flags[o - sz], f6 = (int)flags[o + sz];
+    p1 = (f1 & kObstacle) ? c : p1;
+    p2 = (f2 & kObstacle) ? c : p2;
+    p3 = (f3 & kObstacle) ? c : p3;
+    p4 = (f4 & kObstacle) ? c : p4;
+    p5 = (f5 & kObstacle) ? c : p5;
+    p6 = (f6 & kObstacle) ? c : p6;
+    const float upd = (p1 + p2 + p3 + p4 + p5 + p6 + dv) / 6.0f;
+    p[o] = (inner && !(fc & kObstacle)) ? upd : 0.0f;
+  }
+}
+
+// planes [k0, k1) of a Z-deep local array that holds global planes [zg, zg + Z) of a Zg-deep grid; nothing when k1 <= k0
+void jacobi_sweep_slab(hipStream_t st, int B, int Z, int Y, int X, int zg, int Zg, int k0, int k1, const float* p_prev,
+                       const float* flags, const float* div, float* p) {
+  k0 = k0 < 0 ? 0 : k0; k1 = k1 > Z ? Z : k1;
+  if (k1 <= k0 || B < 1) return;
+  Dom d = make_dom(Z, Y, X);
+  d.w0 = k0; d.n0 = k1 - k0; d.w1 = 0; d.nw = d.n0; d.zg = zg; d.Zg = Zg;
+  const dim3 blk(64, 4, 1), grd((X + 63) / 64, (Y + 3) / 4, (unsigned)(d.nw * B));
+  TFL_TIMED("k_jacobi_slab", st);
+  k_jacobi_slab<<<grd, blk, 0, st>>>(d, p_prev, flags, div, p);
+}
+
 // ---- small 2-D grids: the WHOLE solve in one launch (round 4, late) -------------------------------------------------------
 // BASELINE config 1 (64 x 64, 20 iterations) spent its step in 20 dependent launches of a kernel that moves 64 KB. Up to
 // 16 K cells the two pressure buffers fit the LDS of one CU (2 x 64 KB): one block of 1024 threads per batch item keeps the

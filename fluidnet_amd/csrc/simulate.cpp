@@ -384,6 +384,15 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
 //                                                                                             valid from T2]
 // Local array ends are treated by the kernels as the domain's border shell (zeros); with halo >= max(4, 2R+1) no window
 // above ever evaluates a tap there except through data that is exchanged instead (div, p).
+//
+// Jacobi projection (simMethod = 'jacobi', state->model = NULL), the un-cut branch's order: setWallBcs on (0,1), setConstVals,
+// divergence (0,0) -> div halos (J-1, J-1) [T3], then maxIter sweeps from p = 0, then velocity update (0,0) <- p (1,0).
+// J = the stored halo depth (own_lo; the smaller of the two sides on a middle rank -- every rank must store the same depth).
+// A sweep turns p valid on (d,d) into p valid on (d-1,d-1); p = 0 is valid on (J,J) at the start, so the first round needs no
+// exchange. Rounds of J sweeps each end at (0,0) and refill (J,J) by a p exchange [T1]; the last round, r < J sweeps, ends at
+// (1,0) or wider. Sweep n of a round of r (n = 1..r) computes the window (min(d-1, r-n+f), min(d-1, r-n)), f = 1 in the last
+// round (the velocity update's plane below), 0 otherwise -- so a window never reaches the array end of a cut (d-1 < J). Per
+// step: maxIter sweep launches and floor(maxIter / J) p exchanges of J planes a side, plus the div exchange.
 namespace {
 
 struct Halo { const tfl_tensor* t; int below, above; };   // planes of `t` refreshed below / above the owned range
@@ -397,6 +406,7 @@ struct Msg {                 // one neighbour exchange: buffers inside the works
 
 struct SlabGeom {
   int Zl, o0, o1, R, H;
+  int J;                     // the stored halo depth: planes between two p exchanges of the Jacobi projection
   bool lower, upper;
   long long yx, N;           // Y*X, B*Zl*Y*X
   int B;
@@ -412,6 +422,7 @@ int slab_geom(tfl_ctx* c, const tfl_sim_state* s, const tfl_slab* sl, SlabGeom* 
   g->N = (long long)g->B * g->Zl * g->yx;
   g->lower = sl->z_first + sl->own_lo > 0;
   g->upper = sl->z_first + sl->own_hi < sl->z_total;
+  g->J = g->lower ? (g->upper ? std::min(g->o0, g->Zl - g->o1) : g->o0) : (g->upper ? g->Zl - g->o1 : 0);
   const bool ok = g->o0 >= 0 && g->o1 > g->o0 && g->o1 <= g->Zl && sl->z_first >= 0 && sl->z_first + g->Zl <= sl->z_total &&
                   (g->lower ? g->o0 >= g->H : (g->o0 == 0 && sl->z_first == 0)) &&
                   (g->upper ? g->Zl - g->o1 >= g->H : (g->o1 == g->Zl && sl->z_first + g->Zl == sl->z_total)) &&
@@ -530,9 +541,11 @@ void slab_messages(const SlabGeom& g, const tfl_sim_state* s, const tfl_tensor* 
   // next one: nothing writes either field's halo planes in between (p is only read by the first conv layer)
   m[0].tag = 0; m[0].n = 2; m[0].f[0] = Halo{s->U, ur, ur}; m[0].f[1] = Halo{s->p, 4, 3};
   m[1].tag = 1; m[1].n = 0;
+  if (!s->model) { m[1].n = 1; m[1].f[0] = Halo{s->p, g.J, g.J}; }       // Jacobi: p between two rounds of sweeps (either buffer)
   m[2].tag = 2; m[2].n = s->n_density > 0 ? 2 : 1; m[2].f[0] = Halo{Uadv, 3, 4};
   if (s->n_density > 0) m[2].f[1] = Halo{s->density[0], rr > 4 ? rr : 4, rr > 4 ? rr : 4};
   m[3].tag = 3; m[3].n = 1; m[3].f[0] = Halo{div, 4, 3};
+  if (!s->model) m[3].f[0] = Halo{div, g.J > 1 ? g.J - 1 : 0, g.J > 1 ? g.J - 1 : 0};     // what the first round of sweeps reads
 }
 
 constexpr int kReachPrimed = 0x100;  // tfl_slab::in_flight, beside the message bits: this run has reset the context's sticky reach word
@@ -665,7 +678,14 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   if (!z.is3d) return bad("2-D grids have no z to cut (run replicas)");
   const char* method = (prm->advectionMethod && prm->advectionMethod[0]) ? prm->advectionMethod : "maccormackOurs";
   if (std::strcmp(method, "maccormackOurs") != 0) return bad("only advectionMethod maccormackOurs");
-  if (method_of(prm) != "convnet" || !s->model) return bad("only the ConvNet projection");
+  const std::string sm = method_of(prm);
+  if (sm == "pcg")
+    return bad("the PCG projection cannot be cut along z: its dot products need an all-reduce per iteration and its IC(0) "
+               "preconditioner is a lexicographic wavefront over the whole grid (use simMethod 'jacobi' or 'convnet')");
+  const bool jac = sm == "jacobi";
+  if (jac && s->model) return bad("the Jacobi projection takes no model (state->model = NULL: the workspace layout follows it)");
+  if (!jac && (sm != "convnet" || !s->model)) return bad("only the ConvNet projection (with a model) or 'jacobi' (without one)");
+  if (jac && multi && g.o1 - g.o0 < g.J) return bad("Jacobi: the owned range is thinner than the halo depth it sends");
   if (s->n_density < 0 || s->n_density > 1) return bad("at most one density channel");
   if (!ws || ((uintptr_t)ws & 15) != 0 || ws_floats < slab_ws(g, s, nullptr, nullptr)) { c->err = "simulate_step_slab: workspace too small or misaligned"; return TFL_EINVAL; }
   SlabWs W;
@@ -680,7 +700,7 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   tfl_tensor fwd = view(cw, 1), fwdPos = view(cw + N, 3), bwdPos = view(cw + 4 * N, 3);
   tfl_tensor vfwd = view(cw + 7 * N, 3), Uadv = view(cw + 10 * N, 3);
   tfl_tensor curl = view(cw, 3), cnorm = view(cw + 3 * N, 1);
-  tfl_tensor div = view(tfl_model_div(s->model, g.B, g.Zl, s->flags->Y, s->flags->X, cw), 1);
+  tfl_tensor div = view(jac ? cw : tfl_model_div(s->model, g.B, g.Zl, s->flags->Y, s->flags->X, cw), 1);
   Msg m[4];
   slab_messages(g, s, &Uadv, &div, m);
   msg_layout(g, m, 4, W.msg);
@@ -735,7 +755,8 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
     }
     double* d_flags = W.stats + 2 * g.B;
     tfl::reach_flags(c->stream, c->d_reach, prm->dt, kReachFlags, d_flags, tfl::model_range_counter(s->model));
-    if (multi && comm->allreduce_sum(comm->user, d_flags, kReachFlags + 1) != 0) { c->err = "simulate_step_slab: comm callback failed (allreduce_sum, reach)"; return TFL_EINVAL; }
+    // (without a model there is no range word: the Jacobi step all-reduces the reach flags alone)
+    if (multi && comm->allreduce_sum(comm->user, d_flags, kReachFlags + (s->model ? 1 : 0)) != 0) { c->err = "simulate_step_slab: comm callback failed (allreduce_sum, reach)"; return TFL_EINVAL; }
     if (hipMemcpyAsync(c->h_reach_flags, d_flags, sizeof(double) * (kReachFlags + 1), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "simulate_step_slab: reading the reach flags failed"; (void)hipGetLastError(); return TFL_EHIP; }
     if (c->h_reach_flags[kReachFlags] > 0.0) {      // some rank's conv stack left the fp16 range: EVERY rank refuses this step
@@ -752,6 +773,10 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
       c->err = buf; c->needed_reach = need;
       return TFL_EREACH;
     }
+  } else if (sl->check_reach && jac) {
+    // no projection kernel to ride on: the word k_absmax has just folded goes to the pinned mirror by a launch of its own
+    tfl::reach_publish(c->stream, c->d_reach, c->d_reach_host, c->d_reach_tick);
+    c->reach_issued++;
   } else if (sl->check_reach) {
     c->reach_sink = true;                  // the projection kernel of THIS step publishes the word (cleared by the guard below)
   }
@@ -835,8 +860,9 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   const double dx = tfl_getDx(c, s->flags);
   WIN(set_win(c, ext(g, 3, 4)));
   // as tfl_simulate_step: the last force's kernel applies the U pair of the setConstVals that follows, on the planes it writes
-  // (they include every plane the projection reads: (0, 1)); the launch below then skips U
-  const bool fold_forces = !prm->outputDiv;
+  // (they include every plane the projection reads: (0, 1)); the launch below then skips U. Not before the Jacobi projection:
+  // its setWallBcs comes between the last force and the pair (as in tfl_simulate_step)
+  const bool fold_forces = !prm->outputDiv && !jac;
   const bool gravity_on = prm->gravityScale > 0.0;
   bool U_folded = false;
   if (buoyant) {
@@ -876,8 +902,69 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   }
   (void)tfl_set_stages(c, 0); (void)tfl_set_z_window(c, 0, 0, 0, 0);
   if (prm->outputDiv) return TFL_OK;
+  const int Y = s->flags->Y, X = s->flags->X;
+  if (jac) {
+    const Win w = ext(g, 0, 1);            // what the divergence reads
+    tfl::set_wall_bcs_planes(c->stream, g.B, g.Zl, Y, X, w.a, w.b, s->U->data, s->flags->data);
+  }
   rc = set_const_vals(c, s, s->U, !U_folded, Unchanged{true, false, true});
   if (rc) return rc;
+
+  // the end of every step: the next step's U and p halos leave now; they are consumed at its start / before its first conv layer
+  auto end_step = [&]() -> int {
+    if (sl->check_reach == 1 && !c->capturing) reach_mark(c);      // behind the kernel that published this step's reach word
+    if (multi) {
+      int r = msg_start(c, g, comm, m[0]); if (r) return r;
+      if (c->capturing) {
+        // a captured step must end with every stream joined: the message is finished here instead of by the next call (nothing
+        // of the next step could have run beside it anyway -- its first kernels read these halos)
+        r = msg_finish(c, g, comm, m[0]); if (r) return r;
+      } else {
+        sl->in_flight |= 1;
+      }
+    }
+    return TFL_OK;
+  };
+
+  if (jac) {
+    // ---- Jacobi projection (window schedule: the bookkeeping comment above) ---------------------------------------------
+    tfl::velocity_divergence_planes(c->stream, g.B, g.Zl, Y, X, g.o0, g.o1, s->U->data, s->flags->data, div.data);
+    rc = msg_start(c, g, comm, m[3]); if (rc) return rc;
+    rc = msg_finish(c, g, comm, m[3]); if (rc) return rc;
+    const int M = prm->maxIter > 0 ? prm->maxIter : 100;
+    tfl_tensor pPrev = view(cw + N, 1);
+    const tfl_tensor* buf[2] = {s->p, &pPrev};
+    int cur = M & 1;                       // p^0's buffer, so that p^M lands in s->p
+    if (hipMemsetAsync(buf[cur]->data, 0, sizeof(float) * (size_t)N, c->stream) != hipSuccess) {
+      (void)hipGetLastError(); c->err = "simulate_step_slab: hipMemsetAsync failed"; return TFL_EHIP;
+    }
+    auto exchange_p = [&]() -> int {
+      Msg q = m[1];
+      q.f[0].t = buf[cur];
+      int r = msg_start(c, g, comm, q); if (r) return r;
+      return msg_finish(c, g, comm, q);
+    };
+    const int J = multi ? g.J : M + 1;     // (no neighbour: one round, windows clipped to the array)
+    int d = J;                             // p is valid on (d, d)
+    for (int n = 0; n < M; n++) {
+      if (d == 0) { rc = exchange_p(); if (rc) return rc; d = J; }
+      const int left = M - n;              // sweeps still to run, this one included
+      const bool last_round = left < d;    // no exchange follows: end at (1, 0)
+      const int r = std::min(d, left) - 1; // sweeps of this round after this one
+      const Win w = ext(g, std::min(d - 1, r + (last_round ? 1 : 0)), std::min(d - 1, r));
+      tfl::jacobi_sweep_slab(c->stream, g.B, g.Zl, Y, X, sl->z_first, sl->z_total, w.a, w.b, buf[cur]->data, s->flags->data,
+                             div.data, buf[cur ^ 1]->data);
+      cur ^= 1; d--;
+    }
+    if (d == 0) { rc = exchange_p(); if (rc) return rc; }
+    tfl::velocity_update_planes(c->stream, g.B, g.Zl, Y, X, g.o0, g.o1, s->U->data, s->flags->data, s->p->data);
+    if (hipPeekAtLastError() != hipSuccess) { c->err = std::string("simulate_step_slab: ") + hipGetErrorString(hipGetLastError()); return TFL_EHIP; }
+    rc = set_const_vals(c, s, s->U, true, Unchanged{false, false, true});
+    if (rc) return rc;
+    rc = tfl_applyBCs(c, s->U, nullptr, nullptr, 1, -1e6f, 1e6f);
+    if (rc) return rc;
+    return end_step();
+  }
 
   // ---- projection ----------------------------------------------------------------------------------------------------
   const long long mws = ws_floats - (cw - ws);
@@ -926,19 +1013,7 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   (void)tfl_set_stages(c, 0); (void)tfl_set_z_window(c, 0, 0, 0, 0);
   rc = set_const_vals(c, s, s->U, late_ubc && !U_late_folded, Unchanged{false, false, true});
   if (rc) return rc;
-  if (sl->check_reach == 1 && !c->capturing) reach_mark(c);      // behind the kernel that published this step's reach word
-  // the next step's U and p halos leave now; they are consumed at its start / before its first conv layer
-  if (multi) {
-    rc = msg_start(c, g, comm, m[0]); if (rc) return rc;
-    if (c->capturing) {
-      // a captured step must end with every stream joined: the message is finished here instead of by the next call (nothing
-      // of the next step could have run beside it anyway -- its first kernels read these halos)
-      rc = msg_finish(c, g, comm, m[0]); if (rc) return rc;
-    } else {
-      sl->in_flight |= 1;
-    }
-  }
-  return TFL_OK;
+  return end_step();
 }
 
 int32_t tfl_slab_needed_reach(const tfl_ctx* c) { return c ? c->needed_reach : 0; }

@@ -249,6 +249,20 @@ void reach_flags(hipStream_t st, const float* maxu, float dt, int n, double* fla
   k_reach_flags<<<1, 64, 0, st>>>(maxu, dt, n, flags, range_count);
 }
 
+// check_reach = 1 without a projection kernel to ride on (the Jacobi slab step): the sticky maximum and its publication count
+// into the mapped pinned mirror, as k_project's publish_reach does (model.hip)
+__global__ void k_reach_publish(const float* __restrict__ src, float* dst, unsigned* __restrict__ tick) {
+  const unsigned v = atomicOr(reinterpret_cast<unsigned*>(const_cast<float*>(src)), 0u);
+  *reinterpret_cast<unsigned*>(dst) = v;
+  const unsigned t = atomicAdd(tick, 1u) + 1u;
+  __threadfence_system();                       // the maximum is visible to the host before the count that announces it
+  reinterpret_cast<volatile unsigned*>(dst)[1] = t;
+}
+void reach_publish(hipStream_t st, const float* src, float* dst, unsigned* tick) {
+  TFL_TIMED("k_reach_publish", st);
+  k_reach_publish<<<1, 1, 0, st>>>(src, dst, tick);
+}
+
 void absmax(hipStream_t st, long long n, const float* x, float* out, bool reset) {
   if (reset) (void)hipMemsetAsync(out, 0, sizeof(float), st);
   const long long want = (n / 4 + 255) / 256;
@@ -296,6 +310,35 @@ void velocity_divergence(hipStream_t st, bool is3d, int B, int Z, int Y, int X, 
 void velocity_update(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags,
                      const float* p) {
   TFL_LAUNCH(k_velocity_update, U, flags, p);
+}
+// The z-slab step's Jacobi projection (csrc/simulate.cpp) runs three of these on the planes [k0, k1) of the local array only
+// (what tfl_set_z_window does for the operators that honour it; the public operators keep ignoring the window). Their border
+// test stays the local one: inside any window the step passes it is the global one -- a domain end is an array end, and the
+// array ends of a cut lie a halo depth or more beyond the owned planes, outside every window.
+static inline Dom planes_dom(int Z, int Y, int X, int k0, int k1) {
+  Dom d = make_dom(Z, Y, X);
+  d.w0 = k0; d.n0 = k1 - k0; d.w1 = 0; d.nw = d.n0;
+  return d;
+}
+#define TFL_LAUNCH_PLANES(kern, ...)                                 \
+  do {                                                               \
+    k0 = k0 < 0 ? 0 : k0; k1 = k1 > Z ? Z : k1;                     \
+    if (k1 <= k0 || B < 1) return;                                   \
+    const Dom d = planes_dom(Z, Y, X, k0, k1);                       \
+    const dim3 blk(64, 4, 1), grd = cgrid(d, B, blk);                \
+    TFL_TIMED(#kern, st);                                            \
+    kern<true><<<grd, blk, 0, st>>>(d, __VA_ARGS__);                 \
+  } while (0)
+void set_wall_bcs_planes(hipStream_t st, int B, int Z, int Y, int X, int k0, int k1, float* U, const float* flags) {
+  TFL_LAUNCH_PLANES(k_set_wall_bcs, U, flags);
+}
+void velocity_divergence_planes(hipStream_t st, int B, int Z, int Y, int X, int k0, int k1, const float* U, const float* flags,
+                                float* div) {
+  TFL_LAUNCH_PLANES(k_divergence, U, flags, div);
+}
+void velocity_update_planes(hipStream_t st, int B, int Z, int Y, int X, int k0, int k1, float* U, const float* flags,
+                            const float* p) {
+  TFL_LAUNCH_PLANES(k_velocity_update, U, flags, p);
 }
 void add_buoyancy(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* Usrc, float* U, const float* flags,
                   const float* density, float sx, float sy, float sz) {

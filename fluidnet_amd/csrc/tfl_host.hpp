@@ -135,6 +135,12 @@ void velocity_divergence(hipStream_t st, bool is3d, int B, int Z, int Y, int X, 
                          float* div);
 void velocity_update(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags,
                      const float* p);
+// the same three on the 3-D planes [k0, k1) of the local array only (the z-slab step's Jacobi projection)
+void set_wall_bcs_planes(hipStream_t st, int B, int Z, int Y, int X, int k0, int k1, float* U, const float* flags);
+void velocity_divergence_planes(hipStream_t st, int B, int Z, int Y, int X, int k0, int k1, const float* U, const float* flags,
+                                float* div);
+void velocity_update_planes(hipStream_t st, int B, int Z, int Y, int X, int k0, int k1, float* U, const float* flags,
+                            const float* p);
 void add_buoyancy(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* Usrc, float* U, const float* flags,
                   const float* density, float sx, float sy, float sz);
 void add_gravity(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags, float fx,
@@ -147,6 +153,7 @@ void signed_distance_field(hipStream_t st, int B, int Z, int Y, int X, int rad, 
 void stream_copy(hipStream_t st, long long n4, const float* src, float* dst);   // n4 float4s, 16-byte aligned
 void absmax(hipStream_t st, long long n, const float* x, float* out, bool reset);   // *out = max(*out, max |x|)
 void reach_flags(hipStream_t st, const float* maxu, float dt, int n, double* flags, const unsigned long long* range_count = nullptr);   // flags[r-1] = (*maxu * dt >= r), r = 1..n (n <= 62); flags[n] = (*range_count != 0) when given
+void reach_publish(hipStream_t st, const float* src, float* dst, unsigned* tick);   // dst[0] = *src, dst[1] = ++*tick (mapped pinned mirror)
 
 // vorticity.hip
 // stages: bit 0 = pass A (U -> curl, |curl|), bit 1 = pass B (curl, |curl|, flags, U -> U); a z-slab rank runs the two
@@ -164,6 +171,10 @@ bool vorticity_confinement_fused(hipStream_t st, int B, int Z, int Y, int X, con
 // jacobi.hip
 void jacobi_iteration(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* p_prev, const float* flags,
                       const float* div, float* p, double* resid_sq /* [B] or nullptr */);
+
+// one 3-D sweep on the planes [k0, k1) of a z-slab's local array (global planes [zg, zg + Z) of a Zg-deep grid; walls in global z)
+void jacobi_sweep_slab(hipStream_t st, int B, int Z, int Y, int X, int zg, int Zg, int k0, int k1, const float* p_prev,
+                       const float* flags, const float* div, float* p);
 
 // a 2-D grid of up to 16 K cells: the whole Jacobi solve in one launch, p ping-pongs in LDS (false = not taken)
 bool jacobi_solve_lds(hipStream_t st, int B, int Y, int X, const float* flags, const float* div, float* p, float* p_prev,

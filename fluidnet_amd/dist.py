@@ -243,19 +243,26 @@ class ThreadComm(_CommBase):
 
 
 class SlabSimulation:
-    """tfluids.simulate() (lib/simulate.lua:175-327, ConvNet projection) on one z-slab through ONE native call per
+    """tfluids.simulate() (lib/simulate.lua:175-327, ConvNet or Jacobi projection) on one z-slab through ONE native call per
     step (tfl_simulate_step_slab). `batch` holds the EXTENDED local tensors (SlabLayout.extract of the global pDiv,
-    UDiv, flags, density and BC tensors). With world == 1 the result is exactly simulate_native()'s."""
+    UDiv, flags, density and BC tensors). With world == 1 the result is exactly simulate_native()'s; with
+    simMethod='jacobi' (model=None) it is so at any world size."""
 
     def __init__(self, batch, mconf, model, layout, comm=None, check_reach=True, overlap=None, own_context=False, graph=None):
         """graph: True = replay the rank-step as ONE HIP-graph launch (tfl_slab_graph_create, recorded after `graph_after`
         eager steps; raises if it cannot be recorded), False = always step eagerly, None (default) = try when the transport's
         calls are stream operations (tfl_comm.capturable: the native RCCL transport, or a slab without neighbours) and fall
         back to the eager step, with the reason in `graph_error`, when recording fails. mconf is frozen by the recording."""
+        method = mconf.get("simMethod") or "convnet"
+        if method == "pcg":
+            raise TfluidsError("the z-slab path cannot cut the PCG projection (an all-reduce per iteration; its IC(0) "
+                               "preconditioner is a wavefront over the whole grid): use simMethod 'jacobi' or 'convnet'")
+        if method not in ("convnet", "jacobi"):
+            raise TfluidsError("the z-slab path implements the ConvNet and the Jacobi projections, not %r" % (method,))
+        if method == "jacobi":
+            model = None      # (as in simulate(): the Jacobi projection reads no model; the slab step takes state->model = NULL)
         self.batch, self.mconf, self.model, self.lay, self.comm = batch, mconf, model, layout, comm
         U = batch["UDiv"]
-        if (mconf.get("simMethod") or "convnet") != "convnet":
-            raise TfluidsError("the z-slab path implements the ConvNet projection")
         if layout.world > 1 and comm is None:
             raise TfluidsError("a slab with neighbours needs a transport (RcclComm / DistComm / ThreadComm)")
         self.lib = _lib.load()

@@ -516,6 +516,7 @@ end
 --   local slab = M.Slab{zTotal = 256, zFirst = lo, ownLo = c0, ownHi = c1, id = idString, rank = r, world = n}
 -- on its LOCAL extended tensors (owned planes + tfl_slab_halo(reach) planes next to each neighbour) and steps with
 --   slab:simulate(conf, mconf, batch, model)       -- tfluids.simulate on the slab, bit-equal on the owned planes
+--                                                     (mconf.simMethod = 'jacobi': no model, bit-equal at any world size)
 --   slab:drain()                                   -- before reading halo planes / at the end
 function M.rcclUniqueId()
   local id = ffi.new('char[128]')
@@ -558,6 +559,7 @@ function Slab:record()
 end
 function Slab:simulate(conf, mconf, batch, model)
   if self.graph ~= nil then check(lib.tfl_slab_graph_step(ctx, self.graph)); return end
+  if mconf.simMethod == 'jacobi' then model = nil end   -- the Jacobi slab step takes state->model = NULL (it reads none)
   local prm, st, keep = sim_args(mconf, batch, model, false)
   if self.ws == nil then   -- the SAME buffer on every call: messages started by one step are consumed by the next
     self.n = tonumber(lib.tfl_simulate_slab_workspace_floats(ctx, prm, st, self.desc))

@@ -541,8 +541,11 @@ int64_t tfl_simulate_slab_workspace_floats(tfl_ctx* ctx, const tfl_sim_params* p
 /* tfl_simulate_step on one z-slab: the owned planes of p, U and density come out as the single-GPU step would compute
  * them (bit for bit, except for the summation order of the std normaliser's all-reduce). State tensors are the LOCAL
  * extended arrays; BC plans are made on the local BC tensors; flags halos are static (filled by the caller once).
- * Preconditions: 3-D, maccormackOurs, ConvNet projection with the 3-D default topology, at most one density channel,
- * B*C layout as in tfl_simulate_step; on the first call every halo plane holds valid data (the caller cut its arrays
+ * Preconditions: 3-D, maccormackOurs, at most one density channel, B*C layout as in tfl_simulate_step, and one of two
+ * projections: the ConvNet (simMethod "convnet", state->model with the 3-D default topology) or Jacobi (simMethod "jacobi",
+ * state->model = NULL, maxIter sweeps from p = 0 as in tfl_simulate_step; the workspace size follows state->model, so ask
+ * for it with the state the step will get). PCG is refused (TFL_EUNSUPPORTED): its dot products need an all-reduce per
+ * iteration and its IC(0) preconditioner is a lexicographic wavefront over the whole grid, which does not cut along z; on the first call every halo plane holds valid data (the caller cut its arrays
  * out of a global initial state); `workspace` must be the SAME buffer on every call (halo messages of p and U started
  * at the end of one step are consumed by the next).
  * Per step: three neighbour exchanges + one 2*B-double all-reduce --
@@ -550,7 +553,12 @@ int64_t tfl_simulate_slab_workspace_floats(tfl_ctx* ctx, const tfl_sim_params* p
  *   advected U(3 below, 4 above) + density(max(4, 2R+1)) after MacCormack pass B, overlapped with its interior
  *   divergence(4 below, 3 above)          overlapped with the interior of the first conv layer
  * and every phase runs under the narrowest z-window that keeps the owned planes exact, so the redundant compute is a
- * few planes per phase instead of a fixed wide halo. */
+ * few planes per phase instead of a fixed wide halo.
+ * Jacobi instead: the same U + p message and T2, then divergence(J-1 planes a side) once, and p(J planes a side) after every
+ * J sweeps -- floor(maxIter / J) exchanges, none before the first sweep (p starts at zero) -- where J = the stored halo depth
+ * (own_lo, or z_local - own_hi on the lowest rank; every rank must store the same depth). No all-reduce (check_reach = 2
+ * all-reduces its 8 reach flags only), so the owned planes equal tfl_simulate_step's bit for bit at any world size. A host that
+ * stores deeper halos gets fewer, longer exchanges. maxIter = 34 with 4-plane halos: 34 sweep launches, 8 p exchanges + div. */
 int tfl_simulate_step_slab(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state, tfl_slab* slab,
                            const tfl_comm* comm, float* workspace, int64_t workspace_floats);
 

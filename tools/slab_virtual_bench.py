@@ -1,6 +1,10 @@
 """Per-rank compute of the z-slab step estimated on ONE GPU: W virtual ranks (threads, ThreadComm: halos move by device
 copies) advance the bench scene; all ranks share one stream, so wall time / W ~ the kernel time one real rank spends per
-step (no RCCL, no overlap). Also prints rank 0's per-kernel table. usage: slab_virtual_bench.py [res] [world] [steps]"""
+step (no RCCL, no overlap). Also prints rank 0's per-kernel table.
+usage: slab_virtual_bench.py [res] [world] [steps] [--sim jacobi [--iters N]]
+--sim jacobi: the Jacobi projection (no model, N sweeps per step, default 34 -- the 3-D driver's count), with the un-cut
+single-GPU Jacobi step at the same size printed beside it."""
+import argparse
 import os
 import sys
 import time
@@ -13,16 +17,42 @@ import bench  # noqa: E402
 from fluidnet_amd import FluidNetModel, tfluids  # noqa: E402
 from fluidnet_amd.dist import SlabLayout, SlabSimulation, ThreadComm, run_virtual_ranks  # noqa: E402
 
-res = int(sys.argv[1]) if len(sys.argv) > 1 else 128
-world = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-steps = int(sys.argv[3]) if len(sys.argv) > 3 else 20
+ap = argparse.ArgumentParser()
+ap.add_argument("res", nargs="?", type=int, default=128)
+ap.add_argument("world", nargs="?", type=int, default=8)
+ap.add_argument("steps", nargs="?", type=int, default=20)
+ap.add_argument("--sim", default="convnet", choices=("convnet", "jacobi"))
+ap.add_argument("--iters", type=int, default=34)
+args = ap.parse_args()
+res, world, steps = args.res, args.world, args.steps
 dev = torch.device("cuda:0")
-model = FluidNetModel.default_3d(seed=1)
+model = FluidNetModel.default_3d(seed=1) if args.sim == "convnet" else None
+
+
+def scene(lay):
+    batch, mconf = bench.build_scene(res, res, lay, dev)
+    if args.sim == "jacobi":
+        mconf = dict(mconf, simMethod="jacobi", maxIter=args.iters)
+    return batch, mconf
+
+
+if args.sim == "jacobi":       # the un-cut single-GPU step on the same scene, for comparison
+    from fluidnet_amd.simulate import simulate_native
+    batch, mconf = scene(None)
+    for _ in range(3):
+        simulate_native(None, mconf, batch, None)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    for _ in range(steps):
+        simulate_native(None, mconf, batch, None)
+    torch.cuda.synchronize()
+    print("res %d un-cut jacobi (%d sweeps): %.3f ms per step" % (res, args.iters, (time.time() - t0) / steps * 1e3))
+    del batch
 hub = ThreadComm.Hub(world)
 sims = []
 for r in range(world):
     lay = SlabLayout(res, world, r)
-    batch, mconf = bench.build_scene(res, res, lay, dev)
+    batch, mconf = scene(lay)
     sims.append(SlabSimulation(batch, mconf, model, lay, ThreadComm(hub, r), own_context=True))
 run_virtual_ranks(sims, 6)
 torch.cuda.synchronize()
@@ -30,8 +60,8 @@ t0 = time.time()
 run_virtual_ranks(sims, steps)
 torch.cuda.synchronize()
 dt = (time.time() - t0) / steps
-print("res %d, %d virtual ranks: %.3f ms per step for all ranks = %.3f ms per rank-step (single GPU un-split: see bench.py)"
-      % (res, world, dt * 1e3, dt * 1e3 / world))
+print("[%s] res %d, %d virtual ranks: %.3f ms per step for all ranks = %.3f ms per rank-step (single GPU un-split: see bench.py)"
+      % (args.sim, res, world, dt * 1e3, dt * 1e3 / world))
 with tfluids.profile(sims[0].batch["UDiv"]) as prof:
     run_virtual_ranks(sims, 5)
 tot = 0.0
