@@ -23,6 +23,15 @@ class tfl_model_opts(ctypes.Structure):
                                               "nonlin", "pressure_skip")]
 
 
+class tfl_model_graph(ctypes.Structure):
+    """include/tfluids_hip.h tfl_model_graph"""
+    _PP = ctypes.POINTER(ctypes.POINTER(ctypes.c_float))
+    _fields_ = [(n, ctypes.c_int32) for n in ("banks_num", "bank_type", "aggregate", "split_stage", "join_stage",
+                                              "pool_type", "batch_norm")] + \
+               [("bn_mean", _PP), ("bn_var", _PP), ("bn_weight", _PP), ("bn_bias", _PP),
+                ("bn_eps", ctypes.POINTER(ctypes.c_double))]
+
+
 class tfl_tensor(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("B", ctypes.c_int32), ("C", ctypes.c_int32),
                 ("Z", ctypes.c_int32), ("Y", ctypes.c_int32), ("X", ctypes.c_int32)]
@@ -118,6 +127,10 @@ SIGNATURES = {
                                             _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32),
                                             _c.POINTER(_c.c_int32), _c.POINTER(_c.POINTER(_c.c_float)),
                                             _c.POINTER(_c.POINTER(_c.c_float)), _c.c_void_p]),
+    "tfl_model_create_graph": (_c.c_void_p, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int32),
+                                             _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32),
+                                             _c.POINTER(_c.c_int32), _c.POINTER(_c.POINTER(_c.c_float)),
+                                             _c.POINTER(_c.POINTER(_c.c_float)), _c.c_void_p, _c.c_void_p]),
     "tfl_model_destroy": (None, [_c.c_void_p, _c.c_void_p]),
     "tfl_model_range_errors": (_c.c_int64, [_c.c_void_p, _c.c_void_p]),
     "tfl_model_range_flag": (_c.c_int64, [_c.c_void_p, _c.c_void_p]),

@@ -25,6 +25,11 @@ struct tfl_layer {
   int up = 1;          // 2: {Spatial,Volumetric}ConvolutionUpsample -- up^dim sub-position convolutions, pixel-shuffled
   float* w = nullptr;  // device, [sub][tap][cin][cout]
   float* b = nullptr;  // device, [sub][cout]
+  // tfl_model_create_graph only
+  int dil = 1;         // dilation (banksType 'dilate': 2^(bank - 1))
+  int stage = 0;       // 1-based stage of lib/model.lua's layer tables
+  int bank = 0;        // 0-based bank (0 outside [banksSplitStage, banksJoinStage))
+  float* bn = nullptr; // device, the folded batch norm after this module: scale[cout] then shift[cout]
 };
 struct tfl_model {
   bool is3d = false;
@@ -58,6 +63,14 @@ struct tfl_model {
   tfl_model_opts opts = {1, 0, 1, 1, TFL_NORM_UDIV, TFL_NORMFUNC_STD, TFL_NONLIN_RELU, 0};
   bool custom = false;
   int in_c = 3;               // net input channels
+  // tfl_model_create_graph: banks / batch norm / max pooling (shape-generic kernels, un-sharded)
+  bool graph = false;
+  int banks = 1, bank_type = TFL_BANKS_MRES, aggregate = TFL_AGG_CONCAT, split = 0, join = 0, nstages = 0;
+  bool pool_max = false;
+  int bank_c = 0;             // channel planes of each bank's two scratch buffers
+  int bank_down = 1;          // bank 1's finest resolution inside [split, join) = grid / bank_down (bank i: / 2^(i-1) more, mres)
+  int split_c = 0;            // channels entering the split (the mres pyramid's planes)
+  int split_down = 1;         // resolution at the split = grid / split_down
 };
 
 #include "tfl_ctx.hpp"
@@ -90,6 +103,8 @@ KernelTimer::~KernelTimer() {
 }
 hipEvent_t KernelTimer::start() const { return (slot_ >= 0 && g_prof) ? g_prof->recs[slot_].e0 : nullptr; }
 hipEvent_t KernelTimer::stop() const { return (slot_ >= 0 && g_prof) ? g_prof->recs[slot_].e1 : nullptr; }
+bool model_is_graph(const tfl_model* m) { return m && m->graph; }
+int model_grid_factor(const tfl_model* m) { return m ? m->max_down : 1; }
 }  // namespace tfl
 
 namespace {
@@ -722,12 +737,10 @@ tfl_model* tfl_model_create_ex(tfl_ctx* c, int is3D, int nlayers, const int32_t*
   return tfl_model_create_opts(c, is3D, nlayers, cin, cout, ksize, pool, up, weights, biases, nullptr);
 }
 
-tfl_model* tfl_model_create_opts(tfl_ctx* c, int is3D, int nlayers, const int32_t* cin, const int32_t* cout,
-                                 const int32_t* ksize, const int32_t* pool, const int32_t* up,
-                                 const float* const* weights, const float* const* biases, const tfl_model_opts* opts) {
-  if (!c) return nullptr;
-  auto bad = [&](const char* m) -> tfl_model* { fail(c, TFL_EINVAL, "model_create: %s", m); return nullptr; };
-  if (nlayers < 1 || !cin || !cout || !ksize || !weights || !biases) return bad("null or empty layer description");
+// the tfl_model_opts of a new model (NULL = default_conf.lua's), checked against the layer table; false on error
+static bool model_opts_of(tfl_ctx* c, int nlayers, const int32_t* pool, const int32_t* up, const tfl_model_opts* opts,
+                          tfl_model_opts* out) {
+  auto bad = [&](const char* m) { fail(c, TFL_EINVAL, "model_create: %s", m); return false; };
   tfl_model_opts o = {1, 0, 1, 1, TFL_NORM_UDIV, TFL_NORMFUNC_STD, TFL_NONLIN_RELU, 0};
   if (opts) {
     o = *opts;
@@ -746,10 +759,22 @@ tfl_model* tfl_model_create_opts(tfl_ctx* c, int is3D, int nlayers, const int32_
       const bool tail = (pool && (pool[nlayers - 1] > 1 || pool[nlayers - 2] > 1)) || (up && (up[nlayers - 1] > 1 || up[nlayers - 2] > 1));
       if (tail || (nlayers > 2 && multires)) {
         fail(c, TFL_EUNSUPPORTED, "model_create: addPressureSkip with pooling / upsampling layers");
-        return nullptr;
+        return false;
       }
     }
   }
+  *out = o;
+  return true;
+}
+
+tfl_model* tfl_model_create_opts(tfl_ctx* c, int is3D, int nlayers, const int32_t* cin, const int32_t* cout,
+                                 const int32_t* ksize, const int32_t* pool, const int32_t* up,
+                                 const float* const* weights, const float* const* biases, const tfl_model_opts* opts) {
+  if (!c) return nullptr;
+  auto bad = [&](const char* m) -> tfl_model* { fail(c, TFL_EINVAL, "model_create: %s", m); return nullptr; };
+  if (nlayers < 1 || !cin || !cout || !ksize || !weights || !biases) return bad("null or empty layer description");
+  tfl_model_opts o;
+  if (!model_opts_of(c, nlayers, pool, up, opts, &o)) return nullptr;
   const int in_c = o.in_pDiv + o.in_UDiv * (is3D ? 3 : 2) + o.in_div + 1;
   if (cin[0] != in_c) {
     fail(c, TFL_EINVAL, "model_create: the first layer must take %d input channels {pDiv, UDiv, div, occupancy as selected}", in_c);
@@ -923,10 +948,163 @@ tfl_model* tfl_model_create_opts(tfl_ctx* c, int is3D, int nlayers, const int32_
   return m;
 }
 
+// Every defineModelGraph configuration (include/tfluids_hip.h tfl_model_create_graph; lib/model.lua:253-392). The trivial
+// graph is tfl_model_create_opts; everything else is laid out here for the shape-generic kernels (graph_forward below).
+tfl_model* tfl_model_create_graph(tfl_ctx* c, int is3D, int nconv, const int32_t* cin, const int32_t* cout,
+                                  const int32_t* ksize, const int32_t* pool, const int32_t* up,
+                                  const float* const* weights, const float* const* biases, const tfl_model_opts* opts,
+                                  const tfl_model_graph* g) {
+  if (!c) return nullptr;
+  auto bad = [&](const char* m) -> tfl_model* { fail(c, TFL_EINVAL, "model_create: %s", m); return nullptr; };
+  auto unsupported = [&](const char* m) -> tfl_model* { fail(c, TFL_EUNSUPPORTED, "model_create: %s", m); return nullptr; };
+  if (g) {
+    if (g->banks_num < 1 || g->banks_num > tfl::kMaxJoinBanks) return bad("banksNum must be 1 .. 8");
+    if (g->pool_type != TFL_POOL_AVG && g->pool_type != TFL_POOL_MAX) return bad("Bad pool type.  Must be 'avg' or 'max'");
+  }
+  if (!g || (g->banks_num == 1 && !g->batch_norm && g->pool_type == TFL_POOL_AVG))
+    return tfl_model_create_opts(c, is3D, nconv, cin, cout, ksize, pool, up, weights, biases, opts);
+  if (nconv < 2 || !cin || !cout || !ksize || !weights || !biases) return bad("null or empty layer description");
+  const int N = g->banks_num;
+  const bool mres = g->bank_type == TFL_BANKS_MRES, concat = g->aggregate == TFL_AGG_CONCAT;
+  int nst = nconv;
+  if (N > 1) {
+    if (g->bank_type != TFL_BANKS_MRES && g->bank_type != TFL_BANKS_DILATE) return bad("banksType must be 'mres' or 'dilate'");
+    if (g->aggregate != TFL_AGG_CONCAT && g->aggregate != TFL_AGG_ADD) return bad("ERROR: unsupported mconf.banksAggregateMethod");
+    if (!(g->split_stage < g->join_stage)) return bad("banksSplitStage must come before banksJoinStage");
+    nst = nconv - (N - 1) * (g->join_stage - g->split_stage);
+    if (g->split_stage < 1 || g->join_stage >= nst) return bad("banksSplitStage / banksJoinStage must lie before the last stage (model.lua:257-258)");
+  }
+  if (g->batch_norm && (!g->bn_mean || !g->bn_var || !g->bn_eps)) return bad("addBatchNorm needs running_mean, running_var and eps per module");
+  // module m -> (stage, bank), creation order
+  std::vector<int> stage_of, bank_of, first_of(nst + 2, -1);
+  for (int st = 1; st <= nst; st++) {
+    const int nb = (N > 1 && st >= g->split_stage && st < g->join_stage) ? N : 1;
+    first_of[st] = (int)stage_of.size();
+    for (int b = 0; b < nb; b++) { stage_of.push_back(st); bank_of.push_back(b); }
+  }
+  auto P = [&](const int32_t* a, int i) { return a ? a[i] : 1; };
+  for (int i = 0; i < nconv; i++) {
+    const int f = first_of[stage_of[i]];
+    if (cin[i] != cin[f] || cout[i] != cout[f] || ksize[i] != ksize[f] || P(pool, i) != P(pool, f) || P(up, i) != P(up, f))
+      return bad("the banks of a stage must have the same shape");
+    if (N > 1 && !mres && bank_of[i] > 0 && P(up, i) > 1) return bad("upsampling not supported for dilated convolutions.");
+  }
+  // the stage table the options are checked against (one entry per stage)
+  std::vector<int32_t> spool(nst), sup(nst);
+  for (int st = 1; st <= nst; st++) { spool[st - 1] = P(pool, first_of[st]); sup[st - 1] = P(up, first_of[st]); }
+  tfl_model_opts o;
+  if (!model_opts_of(c, nst, spool.data(), sup.data(), opts, &o)) return nullptr;
+  if (o.pressure_skip && N > 1 && mres) return unsupported("addPressureSkip with pooling / upsampling layers");
+  const int in_c = o.in_pDiv + o.in_UDiv * (is3D ? 3 : 2) + o.in_div + 1;
+  if (cin[0] != in_c) {
+    fail(c, TFL_EINVAL, "model_create: the first layer must take %d input channels {pDiv, UDiv, div, occupancy as selected}", in_c);
+    return nullptr;
+  }
+  if (cout[nconv - 1] != 1) return bad("the last layer must output 1 channel (pressure)");
+  tfl_model* m = new tfl_model();
+  m->is3d = is3D != 0;
+  m->opts = o; m->in_c = in_c;
+  m->custom = !(o.in_pDiv && !o.in_UDiv && o.in_div && o.normalize && o.norm_chan == TFL_NORM_UDIV &&
+                o.norm_func == TFL_NORMFUNC_STD && o.nonlin == TFL_NONLIN_RELU && !o.pressure_skip);
+  m->graph = true; m->banks = N; m->bank_type = g->bank_type; m->aggregate = g->aggregate;
+  m->split = N > 1 ? g->split_stage : 0; m->join = N > 1 ? g->join_stage : 0; m->nstages = nst;
+  m->pool_max = g->pool_type == TFL_POOL_MAX;
+  auto cleanup = [&](const char* msg) -> tfl_model* { tfl_model_destroy(c, m); return bad(msg); };
+  if (hipMalloc((void**)&m->d_stats, sizeof(double) * 2 * kMaxBatch) != hipSuccess) return cleanup("hipMalloc failed");
+  auto padded = [](int cch) { for (int w : {1, 2, 4, 8, 16, 32, 64}) if (cch <= w) return w; return -1; };
+  std::vector<int> cout_p(nst + 1, 0);     // padded output channels of each stage
+  int down = 1;                            // resolution of the current activations = grid / down
+  for (int i = 0; i < nconv; i++) {
+    const int st = stage_of[i], bk = bank_of[i];
+    const bool last = i + 1 == nconv;
+    const bool skip_in = o.pressure_skip && last;
+    const bool joined = N > 1 && st == g->join_stage && concat;         // input = the concat of the banks
+    if (cin[i] < 1 || cout[i] < 1 || ksize[i] < 1 || (ksize[i] % 2) != 1) return cleanup("convolution size must be odd and positive");
+    if (st > 1 && cin[i] != cout[first_of[st - 1]] * (joined ? N : 1) + (skip_in ? 1 : 0)) return cleanup("layer channel counts do not chain");
+    tfl_layer L;
+    L.stage = st; L.bank = bk;
+    L.pool = P(pool, i); L.up = P(up, i);
+    L.dil = (N > 1 && !mres && bk > 0) ? (1 << bk) : 1;
+    if ((L.pool != 1 && L.pool != 2) || (L.up != 1 && L.up != 2)) return cleanup("pooling / upsampling factors must be 1 or 2");
+    if (L.pool > 1 && L.up > 1) return cleanup("Pooling and upsampling in the same layer!");               // model.lua:322-324
+    if (L.pool > 1 && last) return cleanup("Pooling is not allowed in the last layer");                    // model.lua:247
+    const int cp = last ? cout[i] : padded(cout[i]);
+    if (cp < 0) return cleanup("unsupported output channel count (at most 64)");
+    const int prev_p = st == 1 ? in_c : cout_p[st - 1];
+    const int cin_p = st == 1 ? in_c : prev_p * (joined ? N : 1) + (skip_in ? 1 : 0);
+    if (bk == 0) {
+      cout_p[st] = cp;
+      if (N > 1 && st == g->split_stage) {
+        m->split_c = cin_p; m->split_down = down; m->bank_down = down;
+        // the pyramid's coarsest level, whatever the banked stages do after it
+        if (mres && (down << (N - 1)) > m->max_down) m->max_down = down << (N - 1);
+      }
+      if (down % L.up) return cleanup("a layer upsamples beyond the grid resolution");
+      down = down / L.up;
+      if (N > 1 && st >= g->split_stage && st < g->join_stage) {
+        if (down < m->bank_down) m->bank_down = down;
+        if (cp > m->bank_c) m->bank_c = cp;
+      }
+      down *= L.pool;
+      const int bank_max = (N > 1 && mres && st >= g->split_stage && st < g->join_stage) ? down << (N - 1) : down;
+      if (bank_max > m->max_down) m->max_down = bank_max;
+      if (L.pool > 1 || L.up > 1 || down != 1) m->multires = true;
+    }
+    // input channel ci of the reference -> its plane in the padded layout (banks' slices Cp apart; the skip channel last)
+    const int C = st == 1 ? in_c : cout[first_of[st - 1]];
+    auto cmap = [&](int ci) {
+      if (skip_in && ci == cin[i] - 1) return cin_p - 1;
+      return joined ? (ci / C) * prev_p + ci % C : ci;
+    };
+    L.cin = cin_p; L.cout = cp; L.k = ksize[i];
+    const int taps = is3D ? L.k * L.k * L.k : L.k * L.k;
+    const int S = is3D ? L.up * L.up * L.up : L.up * L.up;
+    std::vector<float> relaid((size_t)S * taps * L.cin * L.cout, 0.0f);
+    for (int sub = 0; sub < S; sub++)
+      for (int co = 0; co < cout[i]; co++)
+        for (int ci = 0; ci < cin[i]; ci++)
+          for (int t = 0; t < taps; t++)
+            relaid[(((size_t)sub * taps + t) * L.cin + cmap(ci)) * L.cout + co] = weights[i][(((size_t)co * S + sub) * cin[i] + ci) * taps + t];
+    std::vector<float> bias_p((size_t)S * L.cout, 0.0f);
+    for (int sub = 0; sub < S; sub++)
+      for (int co = 0; co < cout[i]; co++) bias_p[(size_t)sub * L.cout + co] = biases[i][(size_t)co * S + sub];
+    // batch norm after every hidden module, folded in double: scale = w / sqrt(var + eps), shift = b - mean * scale, each
+    // rounded once to fp32 (padded channels: 0, 0 -- they stay exact zeros)
+    std::vector<float> bn;
+    if (g->batch_norm && !last) {
+      if (!g->bn_mean[i] || !g->bn_var[i]) { m->layers.push_back(L); return cleanup("addBatchNorm: a module lacks running_mean / running_var"); }
+      bn.assign((size_t)2 * L.cout, 0.0f);
+      for (int co = 0; co < cout[i]; co++) {
+        const double wt = (g->bn_weight && g->bn_weight[i]) ? (double)g->bn_weight[i][co] : 1.0;
+        const double bi = (g->bn_bias && g->bn_bias[i]) ? (double)g->bn_bias[i][co] : 0.0;
+        const double sc = wt / std::sqrt((double)g->bn_var[i][co] + g->bn_eps[i]);
+        bn[co] = (float)sc;
+        bn[L.cout + co] = (float)(bi - (double)g->bn_mean[i][co] * sc);
+      }
+    }
+    if (hipMalloc((void**)&L.w, relaid.size() * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&L.b, bias_p.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(L.w, relaid.data(), relaid.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(L.b, bias_p.data(), bias_p.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        (!bn.empty() && (hipMalloc((void**)&L.bn, bn.size() * sizeof(float)) != hipSuccess ||
+                         hipMemcpy(L.bn, bn.data(), bn.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))) {
+      m->layers.push_back(L);
+      return cleanup("uploading weights failed");
+    }
+    m->layers.push_back(L);
+    const int width = (N > 1 && st == g->join_stage - 1 && concat) ? cp * N : cp + (o.pressure_skip ? 1 : 0);
+    if (!last && width > m->max_c) m->max_c = width;
+  }
+  if (down != 1) return cleanup("the layers do not return to the grid resolution (pool / up factors)");
+  if (N > 1 && mres) m->multires = true;
+  if (m->max_c < 1) m->max_c = 1;
+  return m;
+}
+
 void tfl_model_destroy(tfl_ctx* c, tfl_model* m) {
   (void)c;
   if (!m) return;
-  for (auto& L : m->layers) { if (L.w) (void)hipFree(L.w); if (L.b) (void)hipFree(L.b); }
+  for (auto& L : m->layers) { if (L.w) (void)hipFree(L.w); if (L.b) (void)hipFree(L.b); if (L.bn) (void)hipFree(L.bn); }
   for (int l = 0; l < 3; l++) if (m->bfrag[l]) (void)hipFree(m->bfrag[l]);
   for (int l = 0; l < 3; l++) if (m->wino[l]) (void)hipFree(m->wino[l]);
   for (int l = 0; l < 3; l++) if (m->wfrag16[l]) (void)hipFree(m->wfrag16[l]);
@@ -973,17 +1151,37 @@ static int range_gate(tfl_ctx* c, tfl_model* m, const char* who) {
   return TFL_OK;
 }
 
+// floats of a graph model's bank buffers behind pPred: per bank two scratch buffers of bank_c planes at its finest
+// resolution, and (mres) the pyramid level it starts from; with `base`, their addresses (layout in this order)
+static int64_t graph_ws_floats(const tfl_model* m, int B, int Z, int Y, int X, float* base, float* (*bank)[2], float** pyr = nullptr) {
+  if (!m->graph || m->banks < 2) return 0;
+  auto cells = [&](int f) { return (int64_t)B * (m->is3d ? (Z + f - 1) / f : Z) * ((Y + f - 1) / f) * ((X + f - 1) / f); };
+  const bool mres = m->bank_type == TFL_BANKS_MRES;
+  int64_t off = 0;
+  for (int i = 0; i < m->banks; i++) {
+    const int64_t n = (int64_t)m->bank_c * cells(mres ? m->bank_down << i : m->bank_down);
+    if (base) { bank[i][0] = base + off; bank[i][1] = base + off + n; }
+    off += 2 * n;
+    if (mres && i > 0) {
+      if (base) pyr[i] = base + off;
+      off += (int64_t)m->split_c * cells(m->split_down << i);
+    }
+  }
+  return off;
+}
+
 int64_t tfl_model_workspace_floats(const tfl_model* m, int B, int Z, int Y, int X) {
   if (!m) return -1;
   const int64_t n = (int64_t)B * Z * Y * X;
   // per-block fp64 stat partials (2 doubles = 4 floats per block, kept first for 8-byte alignment)
   // + div[1] + net input[in_c] + two ping-pong activation buffers[max_c] + pPred[1]
   // (+4: the fp16 MFMA path aligns its activation buffers to 16 bytes)
-  return 4 * tfl::model_stat_blocks(B, Z, Y, X) + n * (1 + (int64_t)m->in_c + 2 * (int64_t)m->max_c + 1) + (m->m16 ? 4 : 0);
+  return 4 * tfl::model_stat_blocks(B, Z, Y, X) + n * (1 + (int64_t)m->in_c + 2 * (int64_t)m->max_c + 1) + (m->m16 ? 4 : 0) +
+         graph_ws_floats(m, B, Z, Y, X, nullptr, nullptr);
 }
 
 namespace {
-struct ModelWs { double* partials; float* div; float* x3; float* act[2]; float* pPred; };
+struct ModelWs { double* partials; float* div; float* x3; float* act[2]; float* pPred; float* bank[tfl::kMaxJoinBanks][2]; float* pyr[tfl::kMaxJoinBanks]; };
 int model_ws(tfl_ctx* c, const tfl_model* m, const tfl_tensor* flags, float* workspace, int64_t workspace_floats,
              ModelWs* w) {
   const int B = flags->B, Z = flags->Z, Y = flags->Y, X = flags->X;
@@ -1000,6 +1198,7 @@ int model_ws(tfl_ctx* c, const tfl_model* m, const tfl_tensor* flags, float* wor
   if (m->m16) w->act[0] = (float*)(((uintptr_t)w->act[0] + 15) & ~(uintptr_t)15);
   w->act[1] = w->act[0] + (int64_t)m->max_c * n;
   w->pPred = w->act[1] + (int64_t)m->max_c * n;
+  graph_ws_floats(m, B, Z, Y, X, w->pPred + n, w->bank, w->pyr);
   return TFL_OK;
 }
 }  // namespace
@@ -1017,6 +1216,17 @@ static const unsigned short* wall_code_of(tfl_ctx* c, const tfl_model* m, const 
   return nullptr;
 }
 
+// a graph model's grid must be divisible by its largest downsampling factor (the mres pyramid times the pooling): refused
+// before anything is launched (the reference fails at the join)
+static int graph_gate(tfl_ctx* c, const tfl_model* m, const tfl_tensor* flags, const char* who) {
+  if (!m->graph) return TFL_OK;
+  const int f = m->max_down;
+  if ((m->is3d && flags->Z % f) || flags->Y % f || flags->X % f)
+    return fail(c, TFL_EINVAL, "%s: grid %dx%dx%d is not divisible by the model's downsampling factor %d (banks x pooling)", who,
+                flags->Z, flags->Y, flags->X, f);
+  return TFL_OK;
+}
+
 int tfl_model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tensor* flags, const tfl_tensor* UOut,
                     float* workspace, int64_t workspace_floats, int zlo, int zhi, double* stats) {
   TRY(check_flags(c, "model_begin", flags));
@@ -1026,6 +1236,7 @@ int tfl_model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_
   TRY(check_vel(c, "model_begin", "UDiv", UDiv, flags, is3D));
   TRY(check_vel(c, "model_begin", "UOut", UOut, flags, is3D));
   if (zlo < 0 || zhi > flags->Z || zlo >= zhi) return fail(c, TFL_EINVAL, "model_begin: bad z range [%d, %d)", zlo, zhi);
+  TRY(graph_gate(c, m, flags, "model_begin"));
   ModelWs w;
   TRY(model_ws(c, m, flags, workspace, workspace_floats, &w));
   // SetWallBcs(UDiv) lands in UOut. UOut may alias UDiv: a thread rewrites only the cell it read, and
@@ -1081,6 +1292,100 @@ void tfl_wall_plan_destroy(tfl_ctx* c, tfl_wall_plan* p) {
   delete p;
 }
 
+namespace {
+// One conv module of a graph model at [Zc][Yc][Xc] (updated to its output's): its conv(s) -- one per ConvolutionUpsample
+// sub-position -- then the pooling; the module's batch norm rides on whichever launch writes last. P / Q are two scratch
+// buffers (`in` may be one of them); the result goes to planes [c0, c0 + cout) of the och-plane `dst`, or (dst = null)
+// into P or Q. Returns where the result is, null when no kernel exists for the width.
+float* graph_layer(hipStream_t st, const tfl_model* m, const tfl_layer& L, int B, int& Zc, int& Yc, int& Xc, const float* in,
+                   float* P, float* Q, float* dst, int och, int c0, int act) {
+  float* conv_out = in == P ? Q : P;
+  const bool pools = L.pool > 1;
+  float* cdst = (pools || !dst) ? conv_out : dst;
+  const float* bs = L.bn ? L.bn : nullptr;
+  const float* bt = L.bn ? L.bn + L.cout : nullptr;
+  const int taps = m->is3d ? L.k * L.k * L.k : L.k * L.k;
+  const int S = m->is3d ? L.up * L.up * L.up : L.up * L.up;
+  for (int sub = 0; sub < S; sub++)
+    if (!tfl::conv_direct_graph(st, m->is3d, B, Zc, Yc, Xc, L.cin, L.cout, L.k, act, in, L.w + (size_t)sub * taps * L.cin * L.cout,
+                                L.b + (size_t)sub * L.cout, cdst, L.up, sub, cdst == dst ? och : 0, cdst == dst ? c0 : 0, L.dil,
+                                pools ? nullptr : bs, pools ? nullptr : bt))
+      return nullptr;
+  if (m->is3d) Zc *= L.up;
+  Yc *= L.up; Xc *= L.up;
+  if (!pools) return cdst;
+  float* pdst = dst ? dst : (conv_out == P ? Q : P);
+  tfl::pool2_graph(st, m->is3d, m->pool_max, B, L.cout, Zc, Yc, Xc, conv_out, pdst, dst ? och : L.cout, dst ? c0 : 0, bs, bt);
+  if (m->is3d) Zc /= 2;
+  Yc /= 2; Xc /= 2;
+  return pdst;
+}
+
+// The conv stack of a graph model (lib/model.lua:262-362): trunk stages in the act[] ping-pong, the banks in their own
+// buffers, one k_bank_join launch at the join (none when every bank wrote its own concat slice: dilate + concat).
+int graph_forward(tfl_ctx* c, const tfl_model* m, hipStream_t st, const ModelWs& w, int B, int Z, int Y, int X,
+                  const float* pDiv, const double* st_in, double count) {
+  const int act = 1 + m->opts.nonlin;
+  const int nl = (int)m->layers.size();
+  const bool mres = m->bank_type == TFL_BANKS_MRES, concat = m->aggregate == TFL_AGG_CONCAT;
+  const float* in = w.x3;
+  int Zc = Z, Yc = Y, Xc = X;
+  auto none = [&](const tfl_layer& L) { return fail(c, TFL_EUNSUPPORTED, "model_finish: no kernel for %d output channels", L.cout); };
+  for (int l = 0; l < nl;) {
+    const tfl_layer& L0 = m->layers[l];
+    if (m->banks > 1 && L0.stage == m->split) {
+      float* join = in == w.act[0] ? w.act[1] : w.act[0];     // (`in` is read by every bank: the join goes elsewhere)
+      const int N = m->banks, Cp = m->layers[l + (m->join - m->split - 1) * N].cout, och = concat ? Cp * N : Cp;
+      // mres: the average-pooling pyramid, one launch per level (model.lua:266-276)
+      const float* bin[tfl::kMaxJoinBanks];
+      int bZ[tfl::kMaxJoinBanks], bY[tfl::kMaxJoinBanks], bX[tfl::kMaxJoinBanks];
+      bin[0] = in; bZ[0] = Zc; bY[0] = Yc; bX[0] = Xc;
+      for (int i = 1; i < N; i++) {
+        bin[i] = in; bZ[i] = bZ[i - 1]; bY[i] = bY[i - 1]; bX[i] = bX[i - 1];
+        if (!mres) continue;
+        tfl::avg_pool2(st, m->is3d, B * m->split_c, bZ[i - 1], bY[i - 1], bX[i - 1], bin[i - 1], w.pyr[i]);
+        bin[i] = w.pyr[i];
+        if (m->is3d) bZ[i] /= 2;
+        bY[i] /= 2; bX[i] /= 2;
+      }
+      int slot[tfl::kMaxJoinBanks], sh[tfl::kMaxJoinBanks], n = 0;
+      const float* src[tfl::kMaxJoinBanks];
+      int jZ = 0, jY = 0, jX = 0;
+      for (int i = 0; i < N; i++) {
+        const float* x = bin[i];
+        int z = bZ[i], y = bY[i], xx = bX[i];
+        const bool direct = i == 0 || (concat && !mres);            // this bank writes its slice of the join itself
+        for (int s = m->split; s < m->join; s++) {
+          const tfl_layer& L = m->layers[l + (s - m->split) * N + i];
+          const bool last = s + 1 == m->join;
+          x = graph_layer(st, m, L, B, z, y, xx, x, w.bank[i][0], w.bank[i][1], (last && direct) ? join : nullptr, och,
+                          concat ? i * Cp : 0, act);
+          if (!x) return none(L);
+        }
+        if (i == 0) { jZ = z; jY = y; jX = xx; }
+        if (!direct) { slot[n] = i; sh[n] = mres ? i : 0; src[n] = x; n++; }
+      }
+      if (n > 0 && !tfl::bank_join(st, m->is3d, !concat, B, Cp, jZ, jY, jX, n, slot, sh, src, join, och))
+        return fail(c, TFL_EINVAL, "model_finish: bad bank join");
+      in = join; Zc = jZ; Yc = jY; Xc = jX;
+      l += (m->join - m->split) * N;
+      continue;
+    }
+    const bool last = l + 1 == nl;
+    const bool joins_skip = m->opts.pressure_skip && l + 2 == nl;
+    float* dst = last ? w.pPred : (joins_skip ? (in == w.act[0] ? w.act[1] : w.act[0]) : nullptr);
+    float* out = graph_layer(st, m, L0, B, Zc, Yc, Xc, in, w.act[0], w.act[1], dst, joins_skip ? L0.cout + 1 : L0.cout, 0,
+                             last ? 0 : act);
+    if (!out) return none(L0);
+    // addPressureSkip: pDiv/scale becomes the last input channel of the last layer (model.lua:356-360)
+    if (joins_skip) tfl::model_skip_channel(st, B, (long long)Z * Y * X, pDiv, st_in, count, out, L0.cout + 1, L0.cout);
+    in = out;
+    l++;
+  }
+  return TFL_OK;
+}
+}  // namespace
+
 int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* flags,
                      const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace, int64_t workspace_floats,
                      const double* stats, double count, const tfl_tensor* UBC, const tfl_tensor* UBCInvMask,
@@ -1102,6 +1407,9 @@ int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl
   const int B = flags->B, Z = flags->Z, Y = flags->Y, X = flags->X;
   const double* st_in = stats ? stats : m->d_stats;
   hipStream_t st = c->stream;
+  TRY(graph_gate(c, m, flags, "model_finish"));
+  if (m->graph && (stats || c->stages || c->zwin.a1 > c->zwin.a0 || c->zwin.b1 > c->zwin.b0))
+    return fail(c, TFL_EUNSUPPORTED, "model_finish: banked, batch-norm and max-pool models run un-sharded only");
   if (m->custom) {
     // tfl_model_opts: the input scale comes from another field / function / not at all. All three reach the kernels
     // through the (stats, count) pair scale_from_stats reads -- sqrt((n s2 - s1^2) / (n (n - 1))): the l2 norm is
@@ -1165,6 +1473,13 @@ int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl
     tfl::conv2_mfma_mid(st, B, Y, X, w.act[0], m->bfrag2[1], m->layers[1].b, w.act[1]);
     tfl::conv2_mfma_mid(st, B, Y, X, w.act[1], m->bfrag2[2], m->layers[2].b, w.act[0]);
     tfl::conv2_mfma_tail(st, B, Y, X, w.act[0], m->bfrag2[3], m->layers[3].b, m->tail_w5, m->layers[4].b, w.pPred);
+  } else if (m->graph) {
+    if (m->custom)
+      tfl::model_net_input_gen(st, m->is3d, B, Z, Y, X, m->opts.in_pDiv, m->opts.in_UDiv, m->opts.in_div, pDiv->data,
+                               UOut->data, w.div, flags->data, st_in, count, w.x3);
+    else
+      tfl::model_net_input(st, m->is3d, B, Z, Y, X, pDiv->data, w.div, flags->data, st_in, count, w.x3);
+    TRY(graph_forward(c, m, st, w, B, Z, Y, X, pDiv->data, st_in, count));
   } else {
     if (m->multires && ((m->is3d && Z % m->max_down) || Y % m->max_down || X % m->max_down))
       return fail(c, TFL_EINVAL, "model_finish: grid %dx%dx%d is not divisible by the model's pooling factor %d", Z, Y, X, m->max_down);

@@ -204,6 +204,15 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
              "read the count with tfl_model_range_errors, or create the model under TFL_CONV_PATH=winograd (strict fp32)";
     return TFL_ERANGE;
   }
+  // a banked / batch-norm / max-pool model refuses a grid its pyramid and pooling cannot halve evenly: here, before the
+  // advection writes anything (tfl_model_begin would refuse the same grid half-way through the step)
+  if (s->model && method_of(prm) == "convnet" && tfl::model_is_graph(s->model)) {
+    const int f = tfl::model_grid_factor(s->model);
+    if ((z.is3d && z.Z % f) || z.Y % f || z.X % f) {
+      c->err = "simulate_step: the grid is not divisible by the model's downsampling factor " + std::to_string(f) + " (banks x pooling)";
+      return TFL_EINVAL;
+    }
+  }
   InStep in_step(c);      // the gate above is the step's only one: nothing below refuses half-way through
 
   // ---- advection (simulate.lua:183-200): every density channel with the pre-advection U, then U ----------------
@@ -665,6 +674,7 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
                            float* ws, int64_t ws_floats) {
   if (!c || !prm || !s || !s->p || !s->U || !s->flags || !sl) return TFL_EINVAL;
   auto bad = [&](const char* m) { c->err = std::string("simulate_step_slab: ") + m; return TFL_EUNSUPPORTED; };
+  if (tfl::model_is_graph(s->model)) return bad("banked, batch-norm and max-pool models run un-sharded only (tfl_simulate_step)");
   SlabGeom g;
   int rc = slab_geom(c, s, sl, &g);
   if (rc) return rc;

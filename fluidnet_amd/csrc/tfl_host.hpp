@@ -7,6 +7,8 @@
 
 #include "tfl_device.hpp"
 
+struct tfl_model;
+
 namespace tfl {
 
 // A switch that only the EXPERIMENTS flavour of the library reads (-DTFL_EXPERIMENTS, `make exp`: the earlier and the
@@ -229,6 +231,11 @@ void apply_bcs_indexed(hipStream_t st, long long n, const int* idx, float* x, co
 long long pack_planes(hipStream_t st, int n, float* const* ptrs, const int* rows, const int* zlo, const int* nplanes,
                       long long zstride, long long yx, float* buf, int unpack, float* const* bufs = nullptr);
 
+// abi.cpp: a model built by tfl_model_create_graph with banks, batch norm or max pooling (runs un-sharded only)
+bool model_is_graph(const tfl_model* m);
+// the factor its grid must be divisible by (the mres pyramid times the pooling; 1 = any grid)
+int model_grid_factor(const tfl_model* m);
+
 // conv.hip
 // upf > 1: the result goes to sub-position `sub` (= (c*upf + b)*upf + a) of an upf-times finer output grid (pixel shuffle)
 // act: 0 none | 1 ReLU | 2 ReLU6 | 3 sigmoid; out_ch: channel planes per batch item of `out` (0 = cout)
@@ -236,6 +243,20 @@ bool conv_direct(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int cin,
                  const float* in, const float* w, const float* bias, float* out, int upf = 1, int sub = 0, int out_ch = 0);
 // 2x average pooling of `rows` = B*C planes-stacks [Z][Y][X] -> [Z/2 (3-D)][Y/2][X/2]
 void avg_pool2(hipStream_t st, bool is3d, int rows, int Z, int Y, int X, const float* in, float* out);
+// the model-graph form (tfl_model_create_graph): the same conv with tap spacing `dil`, the output at channel planes
+// [c0, c0 + cout) of `out`, and the folded batch norm y = fmaf(act(x), bn_s[c], bn_t[c]) when bn_s is non-null
+bool conv_direct_graph(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int cin, int cout, int ksz, int act,
+                       const float* in, const float* w, const float* bias, float* out, int upf, int sub, int out_ch, int c0,
+                       int dil, const float* bn_s, const float* bn_t);
+// 2x average (max = false) or max pooling of [B][C][Z][Y][X] into planes [c0, c0 + C) of an och-plane output, with the
+// folded batch norm applied to the result when bn_s is non-null
+void pool2_graph(hipStream_t st, bool is3d, bool max, int B, int C, int Z, int Y, int X, const float* in, float* out, int och,
+                 int c0, const float* bn_s, const float* bn_t);
+// the join of a banked model in one launch (conv.hip k_bank_join): n banks src[q] (C channels, upsampled nearest by
+// 2^sh[q]) go into channel slice slot[q] of the och-plane output (concat), or are added onto it in order (add)
+constexpr int kMaxJoinBanks = 8;
+bool bank_join(hipStream_t st, bool is3d, bool add, int B, int C, int Z, int Y, int X, int n, const int* slot, const int* sh,
+               const float* const* src, float* out, int och);
 
 // conv_mfma.hip (3-D default topology: k=3, 8 output channels; x-phase-packed fp32 MFMA)
 void conv3_mfma_first(hipStream_t st, int B, int Z, int Y, int X, const float* in_planar3, const float* bfrag,

@@ -124,6 +124,26 @@ typedef struct tfl_model_opts {
 tfl_model* tfl_model_create_opts(tfl_ctx* ctx, int is3D, int nlayers, const int32_t* cin, const int32_t* cout,
                                  const int32_t* ksize, const int32_t* pool, const int32_t* up,
                                  const float* const* weights, const float* const* biases, const tfl_model_opts* opts);
+enum { TFL_BANKS_MRES = 0, TFL_BANKS_DILATE = 1 };
+enum { TFL_AGG_CONCAT = 0, TFL_AGG_ADD = 1 };
+enum { TFL_POOL_AVG = 0, TFL_POOL_MAX = 1 };
+typedef struct tfl_model_graph {
+  int32_t banks_num;
+  int32_t bank_type;
+  int32_t aggregate;
+  int32_t split_stage, join_stage;
+  int32_t pool_type;
+  int32_t batch_norm;
+  const float* const* bn_mean;
+  const float* const* bn_var;
+  const float* const* bn_weight;
+  const float* const* bn_bias;
+  const double* bn_eps;
+} tfl_model_graph;
+tfl_model* tfl_model_create_graph(tfl_ctx* ctx, int is3D, int nconv, const int32_t* cin, const int32_t* cout,
+                                  const int32_t* ksize, const int32_t* pool, const int32_t* up,
+                                  const float* const* weights, const float* const* biases, const tfl_model_opts* opts,
+                                  const tfl_model_graph* graph);
 void tfl_model_destroy(tfl_ctx* ctx, tfl_model* model);
 int64_t tfl_model_range_errors(tfl_ctx* ctx, tfl_model* model);
 int64_t tfl_model_range_flag(tfl_ctx* ctx, tfl_model* model);
@@ -363,20 +383,108 @@ end
 local Model = {}
 Model.__index = Model
 
--- mconf (optional): the model's configuration table (torch.loadModel returns it next to the graph); its fields
--- inputChannels / normalizeInput* / nonlinType / addPressureSkip select the forward graph as lib/model.lua:27-160 does.
-function M.Model(gmodule, mconf)
-  local cin, cout, ks, ws, bs, keep = {}, {}, {}, {}, {}, {}
-  local is3D = false
+-- The gModule walk of fluidnet_amd/torch7.py model_graph (lib/model.lua:253-392): the conv modules by their
+-- `Bank i: conv stage N` annotation in the reference's creation order (stage, then bank; the unannotated output conv last),
+-- and along each one's single consumer chain the pooling and batch norm that follow its non-linearity. Refuses by name
+-- what the library does not build: gated (CMulTable) and low-rank (Sequential of convs) convolutions, a batch norm in
+-- training mode, weight sharing. Returns {convs = {{module, stage, bank, pool, bn}}, poolType}.
+local function is_conv(m) return m ~= nil and torch.type(m):find('Convolution') ~= nil end
+local function graph_walk(gmodule, mconf)
+  local nodes, users = {}, {}
   for _, node in ipairs(gmodule.forwardnodes) do
-    local m = node.data.module
-    local tn = m and torch.type(m) or ''
-    if tn:find('Convolution') then
-      is3D = tn:find('Volumetric') ~= nil
-      local w, b = m.weight:float():contiguous(), m.bias:float():contiguous()   -- [nOut][nIn][k(z)][k(y)][k(x)]
-      keep[#keep + 1] = w; keep[#keep + 1] = b
-      cin[#cin + 1] = m.nInputPlane; cout[#cout + 1] = m.nOutputPlane; ks[#ks + 1] = m.kW
-      ws[#ws + 1] = ffi.cast('const float*', torch.data(w)); bs[#bs + 1] = ffi.cast('const float*', torch.data(b))
+    local d = node.data
+    local ins = {}
+    for i, v in ipairs(d.mapindex or {}) do ins[i] = v.forwardNodeId end
+    nodes[d.forwardNodeId] = {m = d.module, name = d.annotations and d.annotations.name, ins = ins}
+  end
+  for id, nd in pairs(nodes) do
+    for _, i in ipairs(nd.ins) do users[i] = users[i] or {}; users[i][#users[i] + 1] = id end
+  end
+  if mconf.banksWeightShare then error('banksWeightShare: weight sharing is not supported (model.lua:326-328)', 3) end
+  local convs, last = {}, nil
+  for id, nd in pairs(nodes) do
+    local tn = nd.m and torch.type(nd.m) or ''
+    local what = tostring(nd.name or id)
+    if tn == 'nn.CMulTable' then error('node ' .. what .. ': gated convolutions (CMulTable) are not supported', 3) end
+    if tn == 'nn.Sequential' then
+      for _, sm in ipairs(nd.m.modules) do
+        if is_conv(sm) then error('node ' .. what .. ': low-rank convolutions (Sequential of convolutions) are not supported', 3) end
+      end
+    end
+    if is_conv(nd.m) then
+      local bank, stage = (nd.name or ''):match('^Bank (%d+): conv stage (%d+)$')
+      if bank then convs[#convs + 1] = {m = nd.m, stage = tonumber(stage), bank = tonumber(bank) - 1, id = id}
+      elseif last == nil then last = id
+      else error('node ' .. what .. ': a convolution outside the layer stages', 3) end
+    end
+  end
+  assert(last ~= nil and #convs > 0, 'no convolution stages found in the model')
+  table.sort(convs, function(x, y) return x.stage < y.stage or (x.stage == y.stage and x.bank < y.bank) end)
+  convs[#convs + 1] = {m = nodes[last].m, stage = convs[#convs].stage + 1, bank = 0, id = last, last = true}
+  local pool_type = nil
+  for _, c in ipairs(convs) do
+    c.pool = 1
+    local cur = c.id
+    while not c.last and users[cur] ~= nil and #users[cur] == 1 do
+      cur = users[cur][1]
+      local m, name = nodes[cur].m, nodes[cur].name or ''
+      local tn = m and torch.type(m) or ''
+      if m == nil or is_conv(m) or tn:find('Table') or tn:find('UpSampling') or tn:find('Unsqueeze') or name:find('downsample') then break end
+      if tn:find('MaxPooling') or tn:find('AveragePooling') then
+        c.pool = m.kW
+        local pt = tn:find('MaxPooling') and 'max' or 'avg'
+        assert(pool_type == nil or pool_type == pt, 'both average and max pooling layers')
+        pool_type = pt
+      elseif tn:find('BatchNormalization') then
+        if m.train then error('node ' .. tostring(nodes[cur].name or cur) .. ': batch norm in training mode (call model:evaluate() before saving)', 3) end
+        c.bn = m
+      end
+    end
+  end
+  return {convs = convs, poolType = pool_type or mconf.poolType or 'avg'}
+end
+
+-- mconf (optional): the model's configuration table (torch.loadModel returns it next to the graph); its fields
+-- inputChannels / normalizeInput* / nonlinType / addPressureSkip select the forward graph as lib/model.lua:27-160 does, and
+-- with it the graph is walked as a whole (graph_walk: banks, dilation, pooling, batch norm; tfl_model_create_graph).
+-- Without it, a graph holding batch-norm, dilated, pooling, upsampling or bank-join nodes is refused: the flat walk below
+-- would drop them.
+function M.Model(gmodule, mconf)
+  if mconf == nil then
+    for _, node in ipairs(gmodule.forwardnodes) do
+      local tn = node.data.module and torch.type(node.data.module) or ''
+      for _, h in ipairs({'BatchNormalization', 'Dilated', 'Pooling', 'UpSampling', 'ConvolutionUpsample', 'CAddTable', 'CMulTable'}) do
+        if tn:find(h) then error('the model holds ' .. tn .. ' nodes: pass its mconf (torch.loadModel) to build it', 2) end
+      end
+    end
+  end
+  local cin, cout, ks, ws, bs, keep = {}, {}, {}, {}, {}, {}
+  local pool, up = {}, {}
+  local is3D = false
+  local walk = mconf ~= nil and graph_walk(gmodule, mconf) or nil
+  local function add_conv(m)
+    local u = 1
+    if torch.type(m):find('ConvolutionUpsample') then u = m.scaleW; m = m.modules[1] end
+    is3D = torch.type(m):find('Volumetric') ~= nil
+    local w, b = m.weight:float():contiguous(), m.bias:float():contiguous()   -- [nOut][nIn][k(z)][k(y)][k(x)]
+    keep[#keep + 1] = w; keep[#keep + 1] = b
+    cin[#cin + 1] = m.nInputPlane; cout[#cout + 1] = m.nOutputPlane / (u ^ (is3D and 3 or 2)); ks[#ks + 1] = m.kW
+    ws[#ws + 1] = ffi.cast('const float*', torch.data(w)); bs[#bs + 1] = ffi.cast('const float*', torch.data(b))
+    up[#up + 1] = u
+    return m
+  end
+  if walk then
+    for _, c in ipairs(walk.convs) do
+      local m = add_conv(c.m)
+      local dil = m.dilationW or 1
+      local want = (mconf.banksNum or 1) > 1 and mconf.banksType == 'dilate' and 2 ^ c.bank or 1
+      if dil ~= want then error('stage ' .. c.stage .. ' bank ' .. (c.bank + 1) .. ': dilation ' .. dil .. ' is not what banksType builds', 2) end
+      pool[#pool + 1] = c.pool
+    end
+  else
+    for _, node in ipairs(gmodule.forwardnodes) do
+      local m = node.data.module
+      if m and torch.type(m):find('Convolution') then add_conv(m); pool[#pool + 1] = 1 end
     end
   end
   local n = #cin
@@ -395,7 +503,34 @@ function M.Model(gmodule, mconf)
   end
   local c_cin, c_cout, c_ks = ffi.new('int32_t[?]', n, cin), ffi.new('int32_t[?]', n, cout), ffi.new('int32_t[?]', n, ks)
   local c_ws, c_bs = ffi.new('const float*[?]', n, ws), ffi.new('const float*[?]', n, bs)
-  if opts == nil then
+  if walk then
+    local g = ffi.new('tfl_model_graph')
+    g.banks_num = mconf.banksNum or 1
+    g.bank_type = (mconf.banksType == 'dilate') and lib.TFL_BANKS_DILATE or lib.TFL_BANKS_MRES
+    g.aggregate = (mconf.banksAggregateMethod == 'add') and lib.TFL_AGG_ADD or lib.TFL_AGG_CONCAT
+    g.split_stage, g.join_stage = mconf.banksSplitStage or 1, mconf.banksJoinStage or 3
+    g.pool_type = walk.poolType == 'max' and lib.TFL_POOL_MAX or lib.TFL_POOL_AVG
+    local nbn = 0
+    for i = 1, n - 1 do if walk.convs[i].bn then nbn = nbn + 1 end end
+    if nbn ~= 0 and nbn ~= n - 1 then error('batch norm after some hidden stages only', 2) end
+    if (nbn > 0) ~= (mconf.addBatchNorm == true) then error('mconf.addBatchNorm does not match the graph\'s batch-norm nodes', 2) end
+    if nbn > 0 then
+      g.batch_norm = 1
+      local mean, var = ffi.new('const float*[?]', n - 1), ffi.new('const float*[?]', n - 1)
+      local wt, bi = ffi.new('const float*[?]', n - 1), ffi.new('const float*[?]', n - 1)
+      local eps = ffi.new('double[?]', n - 1)
+      local function ptr(t) if t == nil then return nil end; t = t:float():contiguous(); keep[#keep + 1] = t; return ffi.cast('const float*', torch.data(t)) end
+      for i = 1, n - 1 do
+        local bn = walk.convs[i].bn
+        mean[i - 1], var[i - 1] = ptr(bn.running_mean), ptr(bn.running_var)
+        wt[i - 1], bi[i - 1], eps[i - 1] = ptr(bn.weight), ptr(bn.bias), bn.eps
+      end
+      keep[#keep + 1] = {mean, var, wt, bi, eps}
+      g.bn_mean, g.bn_var, g.bn_weight, g.bn_bias, g.bn_eps = mean, var, wt, bi, eps
+    end
+    self.handle = lib.tfl_model_create_graph(ctx, b2i(is3D), n, c_cin, c_cout, c_ks, ffi.new('int32_t[?]', n, pool),
+                                             ffi.new('int32_t[?]', n, up), c_ws, c_bs, opts, g)
+  elseif opts == nil then
     self.handle = lib.tfl_model_create(ctx, b2i(is3D), n, c_cin, c_cout, c_ks, c_ws, c_bs)
   else
     self.handle = lib.tfl_model_create_opts(ctx, b2i(is3D), n, c_cin, c_cout, c_ks, nil, nil, c_ws, c_bs, opts)

@@ -8,6 +8,7 @@ host copy, the device handle and the scratch tensor.
 """
 import ctypes
 import math
+import os
 
 import numpy as np
 import torch
@@ -39,16 +40,64 @@ def _resolve_opts(opts):
     return o
 
 
+# the mconf switches of lib/model.lua:253-392 that add banks, batch norm or max pooling, with default_conf.lua:40-120's defaults
+DEFAULT_GRAPH = dict(banksNum=1, banksType="mres", banksAggregateMethod="concat", banksSplitStage=1, banksJoinStage=3,
+                     banksWeightShare=False, poolType="avg", addBatchNorm=False, batchNormAffine=True, batchNormEps=1e-4,
+                     bn=None)
+
+# lib/model.lua:163-236: (osize, ksize, psize, usize) of each modelType, 2-D / 3-D
+_LAYER_TABLES = {
+    ("default", False): ([16, 16, 16, 16, 1], [3, 3, 3, 3, 1], [1] * 5, [1] * 5),
+    ("default", True): ([8, 8, 8, 8, 1], [3, 3, 3, 1, 1], [1] * 5, [1] * 5),
+    ("yang", False): ([6, 6, 6, 1], [3, 1, 1, 1], [1] * 4, [1] * 4),
+    ("yang", True): ([6, 6, 6, 1], [3, 1, 1, 1], [1] * 4, [1] * 4),
+    ("tog", False): ([16, 32, 32, 64, 64, 32, 1], [5, 5, 5, 5, 1, 1, 3], [2, 1, 1, 1, 1, 1, 1], [1, 1, 1, 1, 1, 1, 2]),
+    ("tog", True): ([16, 16, 16, 16, 32, 32, 1], [3, 3, 3, 3, 1, 1, 3], [2, 2, 1, 1, 1, 1, 1], [1, 1, 1, 1, 1, 2, 2]),
+}
+
+
+def _resolve_graph(graph):
+    g = dict(DEFAULT_GRAPH)
+    for k, v in (graph or {}).items():
+        if k not in g:
+            raise TfluidsError("unknown model graph field %r" % (k,))
+        g[k] = v
+    if g["banksWeightShare"]:
+        raise TfluidsError("weight sharing not supported for dilated conv networks.")      # model.lua:326-328
+    for key, allowed in (("banksType", ("mres", "dilate")), ("banksAggregateMethod", ("concat", "add")),
+                         ("poolType", ("avg", "max"))):
+        if g[key] not in allowed:
+            raise TfluidsError("bad %s %r (one of %s)" % (key, g[key], ", ".join(allowed)))
+    g["banksNum"] = int(g["banksNum"])
+    return g
+
+
+def conv_modules(nstages, graph):
+    """(stage, bank) of every conv module in lib/model.lua's creation order (1-based stage, 0-based bank)."""
+    n = graph["banksNum"]
+    out = []
+    for st in range(1, nstages + 1):
+        nb = n if n > 1 and graph["banksSplitStage"] <= st < graph["banksJoinStage"] else 1
+        out.extend((st, b) for b in range(nb))
+    return out
+
+
 class FluidNetModel:
-    def __init__(self, layers, is3D, pool=None, up=None, opts=None):
+    def __init__(self, layers, is3D, pool=None, up=None, opts=None, graph=None):
         """layers: [(weight[nOut, nIn, k(,k),k], bias[nOut])] in forward order (numpy float32),
         weight layout as cudnn.{Spatial,Volumetric}Convolution.weight. pool / up: per-layer psize / usize of
         lib/model.lua's layer tables (1 or 2; None = all 1): 2x average pooling after a layer, or the layer is an
         nn.{Spatial,Volumetric}ConvolutionUpsample (its weight then has nOut * 2^dim output channels).
         opts: mconf fields that change the forward graph (lib/model.lua:27-160, 356-387), defaults as
         default_conf.lua: inputChannels={pDiv,UDiv,div,flags}, normalizeInput, normalizeInputChan ('UDiv'|'pDiv'|'div'),
-        normalizeInputFunc ('std'|'norm'), nonlinType ('relu'|'relu6'|'sigmoid'), addPressureSkip."""
+        normalizeInputFunc ('std'|'norm'), nonlinType ('relu'|'relu6'|'sigmoid'), addPressureSkip.
+        graph: mconf's own fields for banks, batch norm and pooling (lib/model.lua:253-392): banksNum, banksType
+        ('mres'|'dilate'), banksAggregateMethod ('concat'|'add'), banksSplitStage, banksJoinStage, poolType ('avg'|'max'),
+        addBatchNorm, plus `bn`: one dict {running_mean, running_var, weight, bias, eps} per hidden conv module (weight /
+        bias None when not affine). `layers`, `pool` and `up` then list the conv modules in the reference's creation order:
+        the stages before the split, bank 1..banksNum of every banked stage, the rest (tfl_model_create_graph)."""
         self.opts = _resolve_opts(opts)
+        self.graph = None if graph is None else _resolve_graph(graph)
         self.is3D = bool(is3D)
         self.layers = [(np.ascontiguousarray(w, np.float32), np.ascontiguousarray(b, np.float32))
                        for w, b in layers]
@@ -66,11 +115,66 @@ class FluidNetModel:
     # -- constructors ------------------------------------------------------------------------
     @classmethod
     def from_torch7(cls, path):
-        """Load a model saved by torch.saveModel (lib/model.lua:463-478), e.g. data/models/myModel2D."""
-        layers = torch7.conv_layers(torch7.load(path))
+        """Load a model saved by torch.saveModel (lib/model.lua:463-478), e.g. data/models/myModel2D. With the
+        `path + "_mconf.bin"` that torch.saveModel writes beside it, this is load_model(path)[1]: the whole graph and the
+        forward options. Without it, a graph holding batch norm, dilated, pooling, upsampling or banked nodes is refused
+        (the bank layout is in the mconf); any other graph is its convolutions in node order."""
+        if os.path.exists(path + "_mconf.bin"):
+            return load_model(path)[1]
+        gm = torch7.load(path)
+        if torch7.needs_graph(gm):
+            raise TfluidsError("%s holds batch-norm / dilated / pooling / banked nodes: its %s_mconf.bin is needed to "
+                               "build it (fluidnet_amd.load_model)" % (path, os.path.basename(path)))
+        layers = torch7.conv_layers(gm)
         if not layers:
             raise TfluidsError("no convolution layers found in " + path)
         return cls(layers, is3D=layers[0][0].ndim == 5)
+
+    @classmethod
+    def from_mconf(cls, mconf, is3D, seed=1):
+        """Seeded stand-in for any defineModelGraph configuration (lib/model.lua:27-392): modelType 'default' | 'yang' |
+        'tog' with any of the graph knobs (DEFAULT_GRAPH) and forward options (DEFAULT_OPTS) read from `mconf`. With one
+        bank and no batch norm the weights are those of default_3d(seed) / tog(is3D, seed); the BN statistics are drawn
+        after all convolutions."""
+        mt = mconf.get("modelType", "default")
+        if (mt, bool(is3D)) not in _LAYER_TABLES:
+            raise TfluidsError("Incorrect modelType for %dD model." % (3 if is3D else 2))
+        osize, ksize, psize, usize = _LAYER_TABLES[(mt, bool(is3D))]
+        opts = {k: mconf[k] for k in DEFAULT_OPTS if k in mconf}
+        graph = _resolve_graph({k: mconf[k] for k in DEFAULT_GRAPH if k in mconf})
+        ic = _resolve_opts(opts)["inputChannels"]
+        dim = 3 if is3D else 2
+        in_c = int(ic["pDiv"]) + int(ic["UDiv"]) * dim + int(ic["div"]) + 1
+        scale = 0.5 if mt == "tog" else 0.35
+        rng = np.random.RandomState(seed)
+        mods = conv_modules(len(osize), graph)
+        layers, pool, up = [], [], []
+        for st, _ in mods:
+            i = st - 1
+            if st == 1:
+                ci = in_c
+            else:
+                ci = osize[i - 1] * (graph["banksNum"] if graph["banksNum"] > 1 and st == graph["banksJoinStage"]
+                                     and graph["banksAggregateMethod"] == "concat" else 1)
+                ci += 1 if (_resolve_opts(opts)["addPressureSkip"] and st == len(osize)) else 0
+            co, k, u = osize[i], ksize[i], usize[i]
+            fan = ci * k ** dim
+            w = (rng.randn(co * u ** dim, ci, *([k] * dim)) * scale * math.sqrt(2.0 / fan)).astype(np.float32)
+            b = (rng.randn(co * u ** dim) * 0.01).astype(np.float32)
+            layers.append((w, b))
+            pool.append(psize[i])
+            up.append(usize[i])
+        if graph["addBatchNorm"] and graph["bn"] is None:
+            bn = []
+            for st, _ in mods[:-1]:
+                co = osize[st - 1]
+                bn.append(dict(running_mean=(rng.randn(co) * 0.1).astype(np.float32),
+                               running_var=rng.uniform(0.5, 1.5, co).astype(np.float32),
+                               weight=(1.0 + rng.randn(co) * 0.1).astype(np.float32) if graph["batchNormAffine"] else None,
+                               bias=(rng.randn(co) * 0.1).astype(np.float32) if graph["batchNormAffine"] else None,
+                               eps=float(graph["batchNormEps"])))
+            graph["bn"] = bn
+        return cls(layers, is3D, pool=pool, up=up, opts=opts, graph=graph)
 
     @classmethod
     def from_npz(cls, path):
@@ -131,8 +235,28 @@ class FluidNetModel:
                                         ("UDiv", "pDiv", "div").index(o["normalizeInputChan"]),
                                         ("std", "norm").index(o["normalizeInputFunc"]),
                                         ("relu", "relu6", "sigmoid").index(o["nonlinType"]), int(o["addPressureSkip"]))
-            h = lib.tfl_model_create_opts(ctx, int(self.is3D), n, cin, cout, ks, I32(*self.pool), I32(*self.up), ws, bs,
-                                          ctypes.byref(copts))
+            if self.graph is None:
+                h = lib.tfl_model_create_opts(ctx, int(self.is3D), n, cin, cout, ks, I32(*self.pool), I32(*self.up), ws, bs,
+                                              ctypes.byref(copts))
+            else:
+                g, keep = self.graph, []
+                cg = _lib.tfl_model_graph(g["banksNum"], ("mres", "dilate").index(g["banksType"]),
+                                          ("concat", "add").index(g["banksAggregateMethod"]), int(g["banksSplitStage"]),
+                                          int(g["banksJoinStage"]), ("avg", "max").index(g["poolType"]), int(g["addBatchNorm"]))
+                if g["addBatchNorm"]:
+                    bn = g["bn"] or []
+                    if len(bn) != n - 1:
+                        raise TfluidsError("addBatchNorm: %d BN modules for %d hidden conv modules" % (len(bn), n - 1))
+
+                    def arr(key):
+                        a = [None if d.get(key) is None else np.ascontiguousarray(d[key], np.float32) for d in bn]
+                        keep.append(a)
+                        return (FP * len(a))(*[None if x is None else x.ctypes.data_as(FP) for x in a])
+                    cg.bn_mean, cg.bn_var, cg.bn_weight, cg.bn_bias = arr("running_mean"), arr("running_var"), arr("weight"), arr("bias")
+                    cg.bn_eps = (ctypes.c_double * len(bn))(*[float(d.get("eps", 1e-5)) for d in bn])
+                    keep.append((cg.bn_mean, cg.bn_var, cg.bn_weight, cg.bn_bias, cg.bn_eps))
+                h = lib.tfl_model_create_graph(ctx, int(self.is3D), n, cin, cout, ks, I32(*self.pool), I32(*self.up), ws, bs,
+                                               ctypes.byref(copts), ctypes.byref(cg))
             if not h:
                 raise TfluidsError(lib.tfl_last_error(ctx).decode())
             self._handles[dev] = h
@@ -224,3 +348,45 @@ class FluidNetModel:
             ctypes.c_void_p(work.data_ptr()), work.numel(), ctypes.c_void_p(stats.data_ptr()), float(count),
             tfluids._tt(UBC) if UBC is not None else None,
             tfluids._tt(UBCInvMask) if UBCInvMask is not None else None, int(clamp is not None), lo, hi))
+
+
+def load_model(path):
+    """(mconf, model) = torch.loadModel(path) (lib/model.lua:480-494): the gModule at `path` and the mconf table at
+    `path + "_mconf.bin"`, walked by the nodes' annotations (torch7.model_graph) into a FluidNetModel with the graph's
+    banks, dilation, pooling, batch norm and forward options. Unsupported nodes are refused by name."""
+    gm = torch7.load(path)
+    mconf = torch7.load(path + "_mconf.bin")
+    if not isinstance(mconf, dict):
+        raise TfluidsError("%s_mconf.bin is not an mconf table" % path)
+    try:
+        g = torch7.model_graph(gm, mconf)
+    except torch7.GraphError as e:
+        raise TfluidsError("%s: %s" % (path, e)) from None
+    is3D = g["layers"][0][0].ndim == 5
+    if bool(mconf.get("is3D", is3D)) != is3D:
+        raise TfluidsError("%s: mconf.is3D does not match the convolutions" % path)
+    graph = {k: mconf[k] for k in DEFAULT_GRAPH if k in mconf and k != "bn"}
+    graph["poolType"] = g["poolType"] if any(p > 1 for p in g["pool"]) else graph.get("poolType", "avg")
+    n = int(graph.get("banksNum", 1))
+    split, join = int(graph.get("banksSplitStage", 1)), int(graph.get("banksJoinStage", 3))
+    mods = conv_modules(g["stages"], dict(banksNum=n, banksSplitStage=split, banksJoinStage=join))
+    if len(mods) != len(g["layers"]):
+        raise TfluidsError("%s: %d convolution modules, the mconf's banks need %d" % (path, len(g["layers"]), len(mods)))
+    dilate = n > 1 and graph.get("banksType", "mres") == "dilate"
+    for (st, bank), d in zip(mods, g["dilation"]):
+        if d != (2 ** bank if dilate else 1):
+            raise TfluidsError("%s: stage %d bank %d has dilation %d, not what banksType %r builds"
+                               % (path, st, bank + 1, d, graph.get("banksType")))
+    has_bn = [b is not None for b in g["bn"]]
+    if any(has_bn) and not all(has_bn):
+        raise TfluidsError("%s: batch norm after some hidden stages only" % path)
+    if bool(mconf.get("addBatchNorm")) != all(has_bn):
+        raise TfluidsError("%s: mconf.addBatchNorm does not match the graph's batch-norm nodes" % path)
+    graph["addBatchNorm"] = all(has_bn)
+    graph["bn"] = g["bn"] if all(has_bn) else None
+    opts = {k: mconf[k] for k in DEFAULT_OPTS if k in mconf}
+    if "inputChannels" in opts:
+        opts["inputChannels"] = {k: bool(v) for k, v in opts["inputChannels"].items()}
+    plain = n == 1 and not graph["addBatchNorm"] and graph["poolType"] == "avg"
+    model = FluidNetModel(g["layers"], is3D, pool=g["pool"], up=g["up"], opts=opts, graph=None if plain else graph)
+    return mconf, model

@@ -291,6 +291,46 @@ typedef struct tfl_model_opts {
 tfl_model* tfl_model_create_opts(tfl_ctx* ctx, int is3D, int nlayers, const int32_t* cin, const int32_t* cout,
                                  const int32_t* ksize, const int32_t* pool, const int32_t* up,
                                  const float* const* weights, const float* const* biases, const tfl_model_opts* opts);
+/* Every projection net lib/model.lua's defineModelGraph builds from mconf (model.lua:253-392): the knobs above plus
+ * resolution or dilated banks, their join, batch norm and max pooling.
+ *   Conv modules are listed in the reference's creation order: the stages before banksSplitStage, then for every banked
+ *   stage lid in [split, join) bank 1..banks_num, then the remaining stages. pool / up are per conv module (NULL = all 1);
+ *   every bank of a stage must have bank 1's shape.
+ *   banks_num > 1 splits before stage `split_stage` and joins before `join_stage` (1-based, 1 <= split < join < #stages):
+ *     TFL_BANKS_MRES: bank i starts from 2x average pooling of bank i-1 (a cascade), and is upsampled nearest by 2^(i-1)
+ *                     at the join; TFL_BANKS_DILATE: every bank starts from the same tensor and bank i's convolutions
+ *                     have dilation 2^(i-1), zero padding 2^(i-1)*(k-1)/2 (their up must be 1).
+ *     TFL_AGG_CONCAT: nn.JoinTable -- bank 1's channels first, the join stage takes cout * banks_num inputs;
+ *     TFL_AGG_ADD:    nn.CAddTable -- ((b1 + b2) + b3) ... in fp32, bank order.
+ *   pool_type: the psize > 1 pooling is average (TFL_POOL_AVG) or max (TFL_POOL_MAX); the mres pyramid is average always.
+ *   batch_norm (addBatchNorm): one inference-form BN module per hidden conv module (after its non-linearity and pooling),
+ *     in the same order: y = (x - mean[c]) / sqrt(var[c] + eps) * weight[c] + bias[c]. bn_weight / bn_bias NULL (or a NULL
+ *     entry) = not affine (weight 1, bias 0). The library folds each module on the host, in double, into one scale and
+ *     one shift per channel, each rounded once to fp32, and applies y = fmaf(x, scale, shift) in the launch that writes
+ *     the stage's output (the conv, or the pooling when the stage pools): no launch of its own.
+ * graph = NULL, or one bank without BN and with average pooling, builds exactly what tfl_model_create_opts builds. Other
+ * graphs run through the shape-generic kernels, un-sharded: tfl_simulate_step_slab refuses them (TFL_EUNSUPPORTED), and
+ * the grid must be divisible by the model's largest downsampling factor (the mres pyramid times the pooling). */
+enum { TFL_BANKS_MRES = 0, TFL_BANKS_DILATE = 1 };
+enum { TFL_AGG_CONCAT = 0, TFL_AGG_ADD = 1 };
+enum { TFL_POOL_AVG = 0, TFL_POOL_MAX = 1 };
+typedef struct tfl_model_graph {
+  int32_t banks_num;                 /* banksNum (1 = no banks; at most 8) */
+  int32_t bank_type;                 /* banksType: TFL_BANKS_* */
+  int32_t aggregate;                 /* banksAggregateMethod: TFL_AGG_* */
+  int32_t split_stage, join_stage;   /* banksSplitStage / banksJoinStage (1-based) */
+  int32_t pool_type;                 /* poolType: TFL_POOL_* */
+  int32_t batch_norm;                /* addBatchNorm: 1 = the bn_* arrays hold one entry per hidden conv module */
+  const float* const* bn_mean;       /* running_mean[cout] */
+  const float* const* bn_var;        /* running_var[cout] */
+  const float* const* bn_weight;     /* weight[cout], or NULL (batchNormAffine = false) */
+  const float* const* bn_bias;       /* bias[cout], or NULL */
+  const double* bn_eps;              /* eps of each module */
+} tfl_model_graph;
+tfl_model* tfl_model_create_graph(tfl_ctx* ctx, int is3D, int nconv, const int32_t* cin, const int32_t* cout,
+                                  const int32_t* ksize, const int32_t* pool, const int32_t* up,
+                                  const float* const* weights, const float* const* biases, const tfl_model_opts* opts,
+                                  const tfl_model_graph* graph);
 void tfl_model_destroy(tfl_ctx* ctx, tfl_model* model);
 /* The 3-D default topology's convolution stack runs as a split-operand fp16 MFMA implicit GEMM (csrc/conv_mfma16.hip):
  * every fp32 operand travels as two fp16 halves, which ends at |x| = 65504. An activation above that is clamped and the
