@@ -393,6 +393,10 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
 //                                                                                             valid from T2]
 // Local array ends are treated by the kernels as the domain's border shell (zeros); with halo >= max(4, 2R+1) no window
 // above ever evaluates a tap there except through data that is exchanged instead (div, p).
+// The other advection methods (one dependency cone per method) need no more: single-pass methods write (0,0)
+// from s +-R and U (R,R); Manta maccormack pass A (R,R) reads s (2R,2R) and U (R,R+1), its velocity pass A U (2R,2R); their
+// passes B (0,0) read fwd, s / U and flags +-R. Their density goes through the workspace (no in-place kernels) and its owned
+// planes are copied back before T2, which carries every density channel.
 //
 // Jacobi projection (simMethod = 'jacobi', state->model = NULL), the un-cut branch's order: setWallBcs on (0,1), setConstVals,
 // divergence (0,0) -> div halos (J-1, J-1) [T3], then maxIter sweeps from p = 0, then velocity update (0,0) <- p (1,0).
@@ -408,7 +412,7 @@ struct Halo { const tfl_tensor* t; int below, above; };   // planes of `t` refre
 
 struct Msg {                 // one neighbour exchange: buffers inside the workspace
   int tag, n;
-  Halo f[8];
+  Halo f[10];                // T2: the advected U + up to 8 density channels
   float *send_lo, *recv_lo, *send_hi, *recv_hi;
   long long n_send_lo, n_recv_lo, n_send_hi, n_recv_hi;   // floats
 };
@@ -423,6 +427,7 @@ struct SlabGeom {
 
 int slab_geom(tfl_ctx* c, const tfl_sim_state* s, const tfl_slab* sl, SlabGeom* g) {
   if (!s || !s->flags || !s->U || !sl) return TFL_EINVAL;
+  if (s->n_density < 0 || s->n_density > 8) { if (c) c->err = "simulate_step_slab: 0 to 8 density channels"; return TFL_EINVAL; }
   g->Zl = s->flags->Z; g->B = s->flags->B;
   g->o0 = sl->own_lo; g->o1 = sl->own_hi;
   g->R = sl->reach > 0 ? sl->reach : 1;
@@ -468,7 +473,7 @@ long long msg_layout(const SlabGeom& g, Msg* m, int count, float* base) {
 // the planes of one message that leave (unpack = false: owned planes -> send buffers) or arrive (unpack = true: receive
 // buffers -> halo planes), BOTH neighbours in one launch
 void pack_msg(tfl_ctx* c, const SlabGeom& g, const Msg& q, bool unpack) {
-  float* ptrs[8]; float* bufs[8]; int rows[8], zlo[8], np[8];
+  float* ptrs[20]; float* bufs[20]; int rows[20], zlo[20], np[20];
   int n = 0;
   for (int side = 0; side < 2; side++) {
     const bool lower = side == 0;
@@ -484,7 +489,8 @@ void pack_msg(tfl_ctx* c, const SlabGeom& g, const Msg& q, bool unpack) {
       n++;
     }
   }
-  if (n) tfl::pack_planes(c->stream, n, ptrs, rows, zlo, np, g.yx * g.Zl, g.yx, nullptr, unpack ? 1 : 0, bufs);
+  for (int i = 0; i < n; i += 8)        // (a launch takes 8 fields: more only with several density channels)
+    tfl::pack_planes(c->stream, std::min(8, n - i), ptrs + i, rows + i, zlo + i, np + i, g.yx * g.Zl, g.yx, nullptr, unpack ? 1 : 0, bufs + i);
 }
 
 // the same planes as contiguous runs of the fields themselves, one per (batch item, channel): what exchange_start_v moves
@@ -551,8 +557,8 @@ void slab_messages(const SlabGeom& g, const tfl_sim_state* s, const tfl_tensor* 
   m[0].tag = 0; m[0].n = 2; m[0].f[0] = Halo{s->U, ur, ur}; m[0].f[1] = Halo{s->p, 4, 3};
   m[1].tag = 1; m[1].n = 0;
   if (!s->model) { m[1].n = 1; m[1].f[0] = Halo{s->p, g.J, g.J}; }       // Jacobi: p between two rounds of sweeps (either buffer)
-  m[2].tag = 2; m[2].n = s->n_density > 0 ? 2 : 1; m[2].f[0] = Halo{Uadv, 3, 4};
-  if (s->n_density > 0) m[2].f[1] = Halo{s->density[0], rr > 4 ? rr : 4, rr > 4 ? rr : 4};
+  m[2].tag = 2; m[2].n = 1 + s->n_density; m[2].f[0] = Halo{Uadv, 3, 4};
+  for (int i = 0; i < s->n_density; i++) m[2].f[1 + i] = Halo{s->density[i], rr > 4 ? rr : 4, rr > 4 ? rr : 4};
   m[3].tag = 3; m[3].n = 1; m[3].f[0] = Halo{div, 4, 3};
   if (!s->model) m[3].f[0] = Halo{div, g.J > 1 ? g.J - 1 : 0, g.J > 1 ? g.J - 1 : 0};     // what the first round of sweeps reads
 }
@@ -575,6 +581,30 @@ long long slab_ws(const SlabGeom& g, const tfl_sim_state* s, float* ws, SlabWs* 
   const long long comp = std::max<long long>(13 * g.N, model) + 4;
   if (out) { out->msg = ws; out->stats = ws ? (double*)(ws + stats_off) : nullptr; out->compute = ws ? ws + off : nullptr; out->compute_floats = comp; }
   return off + comp;
+}
+
+// How the rank-step runs an advection method (the dependency cones). maccormackOurs advects in place
+// through the pair kernels; every other method goes through tfl_advectScalar / tfl_advectVel, the density into the workspace
+// first. Two-pass: a pass A on (R, R) before the pass that writes the owned planes. rk2Ours / rk3Ours advect the velocity
+// with maccormackOurs (tfluids.cc:799-802), so only their scalar advection is single-pass.
+struct AdvPlan { bool known, ours, scalar2, vel2; };
+AdvPlan adv_plan(const char* m) {
+  static const char* names[] = {"euler", "maccormack", "eulerOurs", "rk2Ours", "rk3Ours", "maccormackOurs"};
+  int k = -1;
+  for (int i = 0; i < 6; i++) if (std::strcmp(m, names[i]) == 0) k = i;
+  return AdvPlan{k >= 0, k == 5, k == 1 || k == 5, k == 1 || k >= 3};
+}
+
+// owned planes [o0, o1) of `src` into `dst` (two [B][1][Zl][Y][X] fields): the advected density out of the workspace
+int copy_owned(tfl_ctx* c, const SlabGeom& g, const tfl_tensor* dst, const tfl_tensor* src) {
+  const long long off = (long long)g.o0 * g.yx, n = (long long)(g.o1 - g.o0) * g.yx;
+  for (int b = 0; b < g.B; b++) {
+    const long long row = (long long)b * g.Zl * g.yx + off;
+    if (hipMemcpyAsync(dst->data + row, src->data + row, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) {
+      (void)hipGetLastError(); c->err = "simulate_step_slab: hipMemcpyAsync failed"; return TFL_EHIP;
+    }
+  }
+  return TFL_OK;
 }
 
 struct Win { int a, b; };
@@ -687,7 +717,8 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   const Sizes z = sizes_of(s);
   if (!z.is3d) return bad("2-D grids have no z to cut (run replicas)");
   const char* method = (prm->advectionMethod && prm->advectionMethod[0]) ? prm->advectionMethod : "maccormackOurs";
-  if (std::strcmp(method, "maccormackOurs") != 0) return bad("only advectionMethod maccormackOurs");
+  const AdvPlan ap = adv_plan(method);
+  if (!ap.known) { c->err = std::string("simulate_step_slab: unknown advection method '") + method + "'"; return TFL_EINVAL; }
   const std::string sm = method_of(prm);
   if (sm == "pcg")
     return bad("the PCG projection cannot be cut along z: its dot products need an all-reduce per iteration and its IC(0) "
@@ -696,7 +727,6 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   if (jac && s->model) return bad("the Jacobi projection takes no model (state->model = NULL: the workspace layout follows it)");
   if (!jac && (sm != "convnet" || !s->model)) return bad("only the ConvNet projection (with a model) or 'jacobi' (without one)");
   if (jac && multi && g.o1 - g.o0 < g.J) return bad("Jacobi: the owned range is thinner than the halo depth it sends");
-  if (s->n_density < 0 || s->n_density > 1) return bad("at most one density channel");
   if (!ws || ((uintptr_t)ws & 15) != 0 || ws_floats < slab_ws(g, s, nullptr, nullptr)) { c->err = "simulate_step_slab: workspace too small or misaligned"; return TFL_EINVAL; }
   SlabWs W;
   slab_ws(g, s, ws, &W);
@@ -802,6 +832,7 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   // pass B (the launches that write the advected fields) applies the pairs of the setConstVals that follows on the planes
   // it writes -- the owned ones, which is what message T2 carries to the neighbours' halos (fold_ask / fold_took)
   bool rho_done = true, Uadv_done = true;
+  unsigned extra_done = 0;            // density channels 1.. whose pair their pass B has applied
   auto adv_scalar_b = [&]() { fold_ask(c, s->densityBC[0]); const int r = adv_scalar(); rho_done = fold_took(c) && rho_done; return r; };
   auto adv_vel_b = [&]() { fold_ask(c, s->UBC); const int r = adv_vel(); Uadv_done = fold_took(c) && Uadv_done; return r; };
   // (Round 6 measured the scalar advection on a second stream beside the velocity's -- they are independent, simulate.lua:183-200
@@ -810,36 +841,70 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   // Round 6: the two advections' passes as PAIRS -- passes A in one launch, passes B in one launch (advect_pair3.hip; they are
   // independent here: the slab step does not fold the buoyancy force into pass B). false once = the shape is not the pair
   // kernels': the four launches as before.
-  bool paired = rho != nullptr;
+  bool paired = ap.ours && rho != nullptr;
   auto adv_pair = [&](bool with_folds) {
     const tfl::BcFoldArg fs = with_folds ? fold_arg(s->densityBC[0]) : tfl::no_fold(), fv = with_folds ? fold_arg(s->UBC) : tfl::no_fold();
     const int r = tfl::advect_pair(c, prm->dt, prm->maccormackStrength, rho, s->U, s->flags, &fwd, &fwdPos, rho, &vfwd, &Uadv, fs, fv);
     if (r == TFL_OK && with_folds) { rho_done = rho_done && fs.dev != nullptr; Uadv_done = Uadv_done && fv.dev != nullptr; }
     return r;
   };
-  if (rho && !paired) {
-    (void)tfl_set_stages(c, 1); WIN(set_win(c, ext(g, 2 * g.R, 2 * g.R)));
-    rc = adv_scalar(); if (rc) return rc;
-  }
-  (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, g.R, g.R)));
-  if (paired) {
-    rc = adv_pair(false);
-    if (rc == TFL_EUNSUPPORTED) {
-      paired = false;
+  if (ap.ours) {
+    // density channels 1.. (RGB): each one complete -- min/max (2R, 2R), pass A (R, R), pass B (0, 0) in place -- before channel 0
+    // and the velocity, so that the pair kernels below run as with one channel and T2 finds every channel's owned planes written
+    for (int i = 1; i < s->n_density; i++) {
+      const tfl_tensor* di = s->density[i];
+      auto adv_i = [&]() { return tfl_advectScalar(c, prm->dt, di, s->U, s->flags, &fwd, &fwd, is3D, method, &fwdPos, &bwdPos, 1, 0,
+                                                   prm->maccormackStrength, di); };
+      (void)tfl_set_stages(c, 1); WIN(set_win(c, ext(g, 2 * g.R, 2 * g.R))); rc = adv_i(); if (rc) return rc;
+      (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, g.R, g.R))); rc = adv_i(); if (rc) return rc;
+      (void)tfl_set_stages(c, 4); WIN(set_win(c, ext(g, 0, 0)));
+      fold_ask(c, s->densityBC[i]);
+      rc = adv_i();
+      if (fold_took(c)) extra_done |= 1u << i;
+      if (rc) return rc;
+    }
+    if (rho && !paired) {
       (void)tfl_set_stages(c, 1); WIN(set_win(c, ext(g, 2 * g.R, 2 * g.R)));
       rc = adv_scalar(); if (rc) return rc;
-      (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, g.R, g.R)));
-    } else if (rc) return rc;
+    }
+    (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, g.R, g.R)));
+    if (paired) {
+      rc = adv_pair(false);
+      if (rc == TFL_EUNSUPPORTED) {
+        paired = false;
+        (void)tfl_set_stages(c, 1); WIN(set_win(c, ext(g, 2 * g.R, 2 * g.R)));
+        rc = adv_scalar(); if (rc) return rc;
+        (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, g.R, g.R)));
+      } else if (rc) return rc;
+    }
+    if (!paired) {
+      if (rho) { rc = adv_scalar(); if (rc) return rc; }
+      rc = adv_vel(); if (rc) return rc;
+    }
+  } else {
+    // every other method: the generic gather kernels (and the LDS-tiled single pass of eulerOurs) under the windows of the
+    // cones -- a two-pass method's pass A on (R, R), the pass that writes on (0, 0). Those kernels cannot advect in place:
+    // each density channel goes to `sout` (the fwdPos planes, which only maccormackOurs uses) and its owned planes are copied
+    // back before T2 leaves. Its setConstVals pair is left to the launch after T2 (on every plane: halos arrive unpaired).
+    tfl_tensor sout = view(cw + N, 1);
+    for (int i = 0; i < s->n_density; i++) {
+      const tfl_tensor* di = s->density[i];
+      auto adv_i = [&]() { return tfl_advectScalar(c, prm->dt, di, s->U, s->flags, &fwd, &fwd, is3D, method, &fwdPos, &bwdPos, 1, 0,
+                                                   prm->maccormackStrength, &sout); };
+      if (ap.scalar2) { (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, g.R, g.R))); rc = adv_i(); if (rc) return rc; }
+      (void)tfl_set_stages(c, ap.scalar2 ? 4 : 2); WIN(set_win(c, ext(g, 0, 0)));
+      rc = adv_i(); if (rc) return rc;
+      rc = copy_owned(c, g, di, &sout); if (rc) return rc;
+    }
+    rho_done = false;
+    if (ap.vel2) { (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, g.R, g.R))); rc = adv_vel(); if (rc) return rc; }
   }
-  if (!paired) {
-    if (rho) { rc = adv_scalar(); if (rc) return rc; }
-    rc = adv_vel(); if (rc) return rc;
-  }
-  (void)tfl_set_stages(c, 4);
+  (void)tfl_set_stages(c, ap.vel2 ? 4 : 2);    // the velocity's pass that writes the owned planes (single-pass methods: stage 2)
   const int strip = 4 > 2 * g.R + 1 ? 4 : 2 * g.R + 1;        // deepest plane count message T2 sends
   const Split spB = split_owned(g, strip);
   const bool ovl = sl->overlap && multi;
-  auto pass_b = [&]() -> int {      // the passes B of both operators on the current window
+  auto pass_b = [&]() -> int {      // the passes B of both operators on the current window (other methods: the velocity's)
+    if (!ap.ours) return adv_vel_b();
     if (paired) { const int r = adv_pair(true); if (r != TFL_EUNSUPPORTED) return r; paired = false; }
     if (rho) { const int r = adv_scalar_b(); if (r) return r; }
     return adv_vel_b();
@@ -863,7 +928,7 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   tfl_tensor Utmp = view(cw + 4 * N, 3);                   // the scalar advection's bwdPos planes, dead by now
   const tfl_tensor* cur = &Uadv;
   if (!buoyant && !vfused) { rc = tfl_copy(c, s->U, &Uadv); if (rc) return rc; cur = s->U; }
-  rc = set_const_vals(c, s, cur, !Uadv_done, Unchanged{false, false, false}, (rho && rho_done) ? 1u : 0u);
+  rc = set_const_vals(c, s, cur, !Uadv_done, Unchanged{false, false, false}, ((rho && rho_done) ? 1u : 0u) | extra_done);
   if (rc) return rc;
 
   // ---- forces --------------------------------------------------------------------------------------------------------

@@ -246,7 +246,8 @@ class SlabSimulation:
     """tfluids.simulate() (lib/simulate.lua:175-327, ConvNet or Jacobi projection) on one z-slab through ONE native call per
     step (tfl_simulate_step_slab). `batch` holds the EXTENDED local tensors (SlabLayout.extract of the global pDiv,
     UDiv, flags, density and BC tensors). With world == 1 the result is exactly simulate_native()'s; with
-    simMethod='jacobi' (model=None) it is so at any world size."""
+    simMethod='jacobi' (model=None) it is so at any world size. Every advectionMethod and density channel count (a list of
+    up to 8 tensors, with a matching densityBC list) that simulate_native() takes is taken here too."""
 
     def __init__(self, batch, mconf, model, layout, comm=None, check_reach=True, overlap=None, own_context=False, graph=None):
         """graph: True = replay the rank-step as ONE HIP-graph launch (tfl_slab_graph_create, recorded after `graph_after`

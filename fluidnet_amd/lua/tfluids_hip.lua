@@ -651,7 +651,8 @@ end
 --   local slab = M.Slab{zTotal = 256, zFirst = lo, ownLo = c0, ownHi = c1, id = idString, rank = r, world = n}
 -- on its LOCAL extended tensors (owned planes + tfl_slab_halo(reach) planes next to each neighbour) and steps with
 --   slab:simulate(conf, mconf, batch, model)       -- tfluids.simulate on the slab, bit-equal on the owned planes
---                                                     (mconf.simMethod = 'jacobi': no model, bit-equal at any world size)
+--                                                     (mconf.simMethod = 'jacobi': no model, bit-equal at any world size;
+--                                                      any mconf.advectionMethod, batch.density a table of up to 8 channels)
 --   slab:drain()                                   -- before reading halo planes / at the end
 function M.rcclUniqueId()
   local id = ffi.new('char[128]')

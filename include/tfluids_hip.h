@@ -581,7 +581,9 @@ int64_t tfl_simulate_slab_workspace_floats(tfl_ctx* ctx, const tfl_sim_params* p
 /* tfl_simulate_step on one z-slab: the owned planes of p, U and density come out as the single-GPU step would compute
  * them (bit for bit, except for the summation order of the std normaliser's all-reduce). State tensors are the LOCAL
  * extended arrays; BC plans are made on the local BC tensors; flags halos are static (filled by the caller once).
- * Preconditions: 3-D, maccormackOurs, at most one density channel, B*C layout as in tfl_simulate_step, and one of two
+ * Preconditions: 3-D, any advectionMethod tfl_simulate_step takes (an unknown name: TFL_EINVAL before anything is written),
+ * 0..8 density channels as in tfl_simulate_step (every channel travels in the advected-field message; buoyancy reads
+ * channel 0), B*C layout as in tfl_simulate_step, and one of two
  * projections: the ConvNet (simMethod "convnet", state->model with the 3-D default topology) or Jacobi (simMethod "jacobi",
  * state->model = NULL, maxIter sweeps from p = 0 as in tfl_simulate_step; the workspace size follows state->model, so ask
  * for it with the state the step will get). PCG is refused (TFL_EUNSUPPORTED): its dot products need an all-reduce per
@@ -590,7 +592,9 @@ int64_t tfl_simulate_slab_workspace_floats(tfl_ctx* ctx, const tfl_sim_params* p
  * at the end of one step are consumed by the next).
  * Per step: three neighbour exchanges + one 2*B-double all-reduce --
  *   U(max(R+1, 2R) planes) + p(4 below, 3 above)   ONE message started at the end of the previous step, consumed at the start
- *   advected U(3 below, 4 above) + density(max(4, 2R+1)) after MacCormack pass B, overlapped with its interior
+ *   advected U(3 below, 4 above) + every density channel(max(4, 2R+1)) after the advection's last pass, overlapped with
+ *                                         the interior of the velocity's last pass
+ * (the same halos serve every advection method: DESIGN.md section 6c derives each method's dependency cone)
  *   divergence(4 below, 3 above)          overlapped with the interior of the first conv layer
  * and every phase runs under the narrowest z-window that keeps the owned planes exact, so the redundant compute is a
  * few planes per phase instead of a fixed wide halo.

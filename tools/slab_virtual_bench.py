@@ -1,9 +1,11 @@
 """Per-rank compute of the z-slab step estimated on ONE GPU: W virtual ranks (threads, ThreadComm: halos move by device
 copies) advance the bench scene; all ranks share one stream, so wall time / W ~ the kernel time one real rank spends per
 step (no RCCL, no overlap). Also prints rank 0's per-kernel table.
-usage: slab_virtual_bench.py [res] [world] [steps] [--sim jacobi [--iters N]]
+usage: slab_virtual_bench.py [res] [world] [steps] [--sim jacobi [--iters N]] [--advection METHOD] [--density-channels N]
 --sim jacobi: the Jacobi projection (no model, N sweeps per step, default 34 -- the 3-D driver's count), with the un-cut
-single-GPU Jacobi step at the same size printed beside it."""
+single-GPU Jacobi step at the same size printed beside it.
+--advection: any method of tfl_simulate_step (default maccormackOurs, the bench's); --density-channels: the plume's density
+carried in N channels (default 1). Either option also prints the un-cut single-GPU step of the same configuration."""
 import argparse
 import os
 import sys
@@ -23,6 +25,10 @@ ap.add_argument("world", nargs="?", type=int, default=8)
 ap.add_argument("steps", nargs="?", type=int, default=20)
 ap.add_argument("--sim", default="convnet", choices=("convnet", "jacobi"))
 ap.add_argument("--iters", type=int, default=34)
+ap.add_argument("--advection", default="maccormackOurs",
+                choices=("euler", "maccormack", "eulerOurs", "rk2Ours", "rk3Ours", "maccormackOurs"))
+ap.add_argument("--density-channels", type=int, default=1)
+ap.add_argument("--no-uncut", action="store_true", help="skip the un-cut comparison (a kernel trace of the rank-steps alone)")
 args = ap.parse_args()
 res, world, steps = args.res, args.world, args.steps
 dev = torch.device("cuda:0")
@@ -33,20 +39,30 @@ def scene(lay):
     batch, mconf = bench.build_scene(res, res, lay, dev)
     if args.sim == "jacobi":
         mconf = dict(mconf, simMethod="jacobi", maxIter=args.iters)
+    mconf = dict(mconf, advectionMethod=args.advection)
+    if args.density_channels > 1:
+        n = args.density_channels
+        batch["density"] = [batch["density"].clone() for _ in range(n)]
+        for k in ("densityBC", "densityBCInvMask"):
+            if batch.get(k) is not None:
+                batch[k] = [batch[k].clone() for _ in range(n)]
     return batch, mconf
 
 
-if args.sim == "jacobi":       # the un-cut single-GPU step on the same scene, for comparison
+if not args.no_uncut and (args.sim == "jacobi" or args.advection != "maccormackOurs" or args.density_channels > 1):
+    # the un-cut single-GPU step on the same scene, for comparison
     from fluidnet_amd.simulate import simulate_native
     batch, mconf = scene(None)
     for _ in range(3):
-        simulate_native(None, mconf, batch, None)
+        simulate_native(None, mconf, batch, model)
     torch.cuda.synchronize()
     t0 = time.time()
     for _ in range(steps):
-        simulate_native(None, mconf, batch, None)
+        simulate_native(None, mconf, batch, model)
     torch.cuda.synchronize()
-    print("res %d un-cut jacobi (%d sweeps): %.3f ms per step" % (res, args.iters, (time.time() - t0) / steps * 1e3))
+    print("res %d un-cut %s, %s, %d density channel(s)%s: %.3f ms per step"
+          % (res, args.sim, args.advection, args.density_channels, " (%d sweeps)" % args.iters if args.sim == "jacobi" else "",
+             (time.time() - t0) / steps * 1e3))
     del batch
 hub = ThreadComm.Hub(world)
 sims = []
@@ -60,8 +76,8 @@ t0 = time.time()
 run_virtual_ranks(sims, steps)
 torch.cuda.synchronize()
 dt = (time.time() - t0) / steps
-print("[%s] res %d, %d virtual ranks: %.3f ms per step for all ranks = %.3f ms per rank-step (single GPU un-split: see bench.py)"
-      % (args.sim, res, world, dt * 1e3, dt * 1e3 / world))
+print("[%s, %s, %d ch] res %d, %d virtual ranks: %.3f ms per step for all ranks = %.3f ms per rank-step (single GPU un-split: see bench.py)"
+      % (args.sim, args.advection, args.density_channels, res, world, dt * 1e3, dt * 1e3 / world))
 with tfluids.profile(sims[0].batch["UDiv"]) as prof:
     run_virtual_ranks(sims, 5)
 tot = 0.0
