@@ -105,6 +105,58 @@ hipEvent_t KernelTimer::start() const { return (slot_ >= 0 && g_prof) ? g_prof->
 hipEvent_t KernelTimer::stop() const { return (slot_ >= 0 && g_prof) ? g_prof->recs[slot_].e1 : nullptr; }
 bool model_is_graph(const tfl_model* m) { return m && m->graph; }
 int model_grid_factor(const tfl_model* m) { return m ? m->max_down : 1; }
+
+// The z-slab cone of a model: ONE backward walk over the layer table gives both the window of every launch and
+// the halo depth, so the two cannot disagree. Start: pPred on the owned planes widened by (1, 0) -- what the velocity update
+// reads. Per layer, from its output back to its input:
+//   2x pooling       pooled planes (lo, hi) at grid / 2d  <-  pre-pool planes (2 lo, 2 hi) at grid / d (owned ranges are
+//                    multiples of F, so a pooling window never straddles the owned boundary: outward alignment is exact)
+//   ConvolutionUpsample  fine planes (lo, hi) at grid / d  <-  coarse conv planes (ceil(lo / 2), ceil(hi / 2)) at grid / 2d
+//                    (fine plane 2 kc + c comes from coarse plane kc: the floor mapping)
+//   conv k           conv planes (lo, hi)  <-  input planes (lo + k/2, hi + k/2) at the same resolution
+// The stored halo must hold every plane any level reads: depth = max over the layers of d x (input extent).
+bool model_cone(const tfl_model* m, ModelCone* out, const char** why) {
+  auto no = [&](const char* w) { if (why) *why = w; return false; };
+  if (!m) return no("no model");
+  if (m->graph) return no("banked, batch-norm and max-pool models run un-sharded only (tfl_simulate_step)");
+  if (!m->is3d) return no("2-D grids have no z to cut (run replicas)");
+  const int n = (int)m->layers.size();
+  if (n > (int)(sizeof(out->layer) / sizeof(out->layer[0]))) return no("more than 32 layers");
+  ModelCone c{};
+  c.fused = m->mfma3d;
+  c.windowed = !m->mfma3d;
+  c.F = m->max_down;
+  c.nlayers = n;
+  c.reads_U = m->opts.in_UDiv != 0;
+  c.norm = !m->opts.normalize ? 2 : ((m->opts.norm_chan == TFL_NORM_UDIV && m->opts.norm_func == TFL_NORMFUNC_STD) ? 0 : 1);
+  int lo = 1, hi = 0, d = 1, depth = 1;
+  for (int l = n - 1; l >= 0; l--) {
+    const tfl_layer& L = m->layers[l];
+    LayerCone& w = c.layer[l];
+    w.pool_lo = w.pool_hi = 0;
+    if (L.pool > 1) { w.pool_lo = lo; w.pool_hi = hi; lo *= 2; hi *= 2; d /= 2; }
+    if (L.up > 1) { lo = (lo + 1) / 2; hi = (hi + 1) / 2; d *= 2; }
+    w.conv_lo = lo; w.conv_hi = hi; w.conv_d = d;
+    lo += L.k / 2; hi += L.k / 2;
+    w.in_lo = lo; w.in_hi = hi;
+    depth = std::max(depth, d * std::max(lo, hi));
+  }
+  c.in_lo = lo; c.in_hi = hi;
+  c.depth = depth;
+  *out = c;
+  return true;
+}
+
+void model_slab_stats(hipStream_t st, const tfl_model* m, int B, int Z, long long yx, int zlo, int zhi, int z_total,
+                      const float* pDiv, const float* U, const float* div, double* stats, double* count) {
+  const tfl_model_opts& o = m->opts;
+  const bool udiv = o.norm_chan == TFL_NORM_UDIV;
+  const float* field = o.norm_chan == TFL_NORM_PDIV ? pDiv : (o.norm_chan == TFL_NORM_DIV ? div : U);
+  const int mode = !o.normalize ? 2 : (o.norm_func == TFL_NORMFUNC_L2 ? 1 : 0);
+  model_field_stats_planes(st, B, udiv ? 3 : 1, Z, yx, zlo, zhi, field, mode, stats);
+  // as tfl_model_finish's un-cut forms: std over the whole grid's n values, l2 and none through n = 2
+  *count = mode == 0 ? (double)z_total * (double)yx * (udiv ? 3.0 : 1.0) : 2.0;
+}
 }  // namespace tfl
 
 namespace {
@@ -1410,12 +1462,15 @@ int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl
   TRY(graph_gate(c, m, flags, "model_finish"));
   if (m->graph && (stats || c->stages || c->zwin.a1 > c->zwin.a0 || c->zwin.b1 > c->zwin.b0))
     return fail(c, TFL_EUNSUPPORTED, "model_finish: banked, batch-norm and max-pool models run un-sharded only");
-  if (m->custom) {
+  const bool windowed = c->zwin.a1 > c->zwin.a0 || c->zwin.b1 > c->zwin.b0;
+  if (m->custom && !stats && (c->stages || windowed))
+    return fail(c, TFL_EUNSUPPORTED, "model_finish: a windowed forward of a model with non-default tfl_model_opts takes the caller's "
+                                     "input-scale stats over the owned planes (tfl_simulate_step_slab forms them)");
+  if (m->custom && !stats) {
     // tfl_model_opts: the input scale comes from another field / function / not at all. All three reach the kernels
     // through the (stats, count) pair scale_from_stats reads -- sqrt((n s2 - s1^2) / (n (n - 1))): the l2 norm is
-    // (s1, s2, n) = (0, sum x^2, 2), "no scaling" is (0, 1, 2).
-    if (stats || c->stages || c->zwin.a1 > c->zwin.a0 || c->zwin.b1 > c->zwin.b0)
-      return fail(c, TFL_EUNSUPPORTED, "model_finish: models with non-default tfl_model_opts run un-sharded only");
+    // (s1, s2, n) = (0, sum x^2, 2), "no scaling" is (0, 1, 2). A caller that passes stats has formed that pair itself
+    // (a z-slab rank: over its owned planes, all-reduced -- model_slab_stats).
     const tfl_model_opts& o = m->opts;
     const long long cells = (long long)Z * Y * X;
     const float* field = o.norm_chan == TFL_NORM_PDIV ? pDiv->data : (o.norm_chan == TFL_NORM_DIV ? w.div : UOut->data);
@@ -1429,9 +1484,13 @@ int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl
   }
   WindowScope win(c);
   // tfl_set_stages (z-slab ranks run each layer under its own z-window): 1 = first conv layer, 2 = second, 4 = third
-  // + the two 1x1x1 layers, 8 = velocity update / un-scale / wall BCs. Only the 3-D MFMA path is staged.
+  // + the two 1x1x1 layers, 8 = velocity update / un-scale / wall BCs on the 3-D default topology's fused kernels. The other
+  // 3-D models (the shape-generic forward): 1 = the whole net, each launch on its layer's cone of the z-window's planes
+  // (DESIGN.md 6d), 8 = velocity update / un-scale / wall BCs on the window.
   const int stg = stages_of(c);
-  if (c->stages && !m->mfma3d) return fail(c, TFL_EUNSUPPORTED, "model_finish: stage masks need the 3-D default topology");
+  const bool generic3 = m->is3d && !m->mfma3d && !m->graph;
+  if (c->stages && !m->mfma3d && !generic3)
+    return fail(c, TFL_EUNSUPPORTED, "model_finish: stage masks need a 3-D model that is not a graph model");
   if (m->mfma3d && m->m16) {
     // split-operand fp16 MFMA (conv_mfma16.hip); the two activation buffers hold the "h2" form (32 B per voxel, as 8 fp32)
     // layers 1 + 2 in one launch where the whole array is computed (round 5); a z-slab rank runs them under separate windows
@@ -1480,19 +1539,38 @@ int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl
     else
       tfl::model_net_input(st, m->is3d, B, Z, Y, X, pDiv->data, w.div, flags->data, st_in, count, w.x3);
     TRY(graph_forward(c, m, st, w, B, Z, Y, X, pDiv->data, st_in, count));
-  } else {
+  } else if (stg & 1) {
     if (m->multires && ((m->is3d && Z % m->max_down) || Y % m->max_down || X % m->max_down))
       return fail(c, TFL_EINVAL, "model_finish: grid %dx%dx%d is not divisible by the model's pooling factor %d", Z, Y, X, m->max_down);
-    if (m->custom)
-      tfl::model_net_input_gen(st, m->is3d, B, Z, Y, X, m->opts.in_pDiv, m->opts.in_UDiv, m->opts.in_div, pDiv->data,
-                               UOut->data, w.div, flags->data, st_in, count, w.x3);
-    else
-      tfl::model_net_input(st, m->is3d, B, Z, Y, X, pDiv->data, w.div, flags->data, st_in, count, w.x3);
-    const int act = 1 + m->opts.nonlin;            // conv_direct: 1 ReLU, 2 ReLU6, 3 sigmoid
     const size_t nl = m->layers.size();
     if (m->opts.pressure_skip && (m->layers[nl - 1].pool > 1 || m->layers[nl - 1].up > 1 || m->layers[nl - 2].pool > 1 ||
                                   m->layers[nl - 2].up > 1 || (nl > 2 && m->multires)))
       return fail(c, TFL_EUNSUPPORTED, "model_finish: addPressureSkip with pooling / upsampling layers");
+    // the planes of every launch: the whole grid, or (a z-window [za, zb) on a 3-D model: a z-slab rank's owned planes) the
+    // cone of the planes the velocity update reads, layer by layer (model_cone)
+    tfl::ModelCone cone;
+    int za = 0, zb = Z;
+    if (windowed) {
+      const char* why = nullptr;
+      if (!tfl::model_cone(m, &cone, &why)) return fail(c, TFL_EUNSUPPORTED, "model_finish: %s", why);
+      if (c->zwin.b1 > c->zwin.b0) return fail(c, TFL_EINVAL, "model_finish: the shape-generic forward takes one z-window run");
+      za = std::max(c->zwin.a0, 0); zb = std::min(c->zwin.a1, Z);
+      if (za % cone.F || zb % cone.F)
+        return fail(c, TFL_EINVAL, "model_finish: z-window [%d, %d) is not aligned to the model's downsampling factor %d", za, zb, cone.F);
+    }
+    auto span = [&](int lo, int hi, int dd, int Zd, int& z0, int& nz) {     // planes [za/dd - lo, zb/dd + hi) of a Zd-deep level
+      if (!windowed) { z0 = 0; nz = Zd; return; }
+      const int a = std::max(za / dd - lo, 0), b = std::min(zb / dd + hi, Zd);
+      z0 = a; nz = b > a ? b - a : 0;
+    };
+    int z0, nz;
+    if (windowed) span(cone.in_lo, cone.in_hi, 1, Z, z0, nz); else { z0 = 0; nz = -1; }
+    if (m->custom)
+      tfl::model_net_input_gen(st, m->is3d, B, Z, Y, X, m->opts.in_pDiv, m->opts.in_UDiv, m->opts.in_div, pDiv->data,
+                               UOut->data, w.div, flags->data, st_in, count, w.x3, z0, nz);
+    else
+      tfl::model_net_input(st, m->is3d, B, Z, Y, X, pDiv->data, w.div, flags->data, st_in, count, w.x3, z0, nz);
+    const int act = 1 + m->opts.nonlin;            // conv_direct: 1 ReLU, 2 ReLU6, 3 sigmoid
     const float* in = w.x3;
     int Zc = Z, Yc = Y, Xc = X;     // resolution of `in`
     for (size_t l = 0; l < m->layers.size(); l++) {
@@ -1502,19 +1580,27 @@ int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl
       float* out = last ? w.pPred : (in == w.act[0] ? w.act[1] : w.act[0]);
       const int taps = m->is3d ? L.k * L.k * L.k : L.k * L.k;
       const int S = m->is3d ? L.up * L.up * L.up : L.up * L.up;
+      if (windowed) span(cone.layer[l].conv_lo, cone.layer[l].conv_hi, cone.layer[l].conv_d, Zc, z0, nz);
       for (int sub = 0; sub < S; sub++)      // ConvolutionUpsample: one strided-store convolution per sub-position
         if (!tfl::conv_direct(st, m->is3d, B, Zc, Yc, Xc, L.cin, L.cout, L.k, last ? 0 : act, in,
                               L.w + (size_t)sub * taps * L.cin * L.cout, L.b + (size_t)sub * L.cout, out, L.up, sub,
-                              joins_skip ? L.cout + 1 : 0))
+                              joins_skip ? L.cout + 1 : 0, z0, nz))
           return fail(c, TFL_EUNSUPPORTED, "model_finish: no kernel for %d output channels", L.cout);
-      // addPressureSkip: pDiv/scale becomes the last input channel of the last layer (model.lua:356-360)
-      if (joins_skip) tfl::model_skip_channel(st, B, (long long)Z * Y * X, pDiv->data, st_in, count, out, L.cout + 1, L.cout);
+      // addPressureSkip: pDiv/scale becomes the last input channel of the last layer (model.lua:356-360); windowed: on the
+      // planes the last layer reads (the skip needs a full-resolution net, so they are at the grid's resolution)
+      if (joins_skip) {
+        long long t0 = 0, nt = -1;
+        if (windowed) { span(cone.layer[nl - 1].in_lo, cone.layer[nl - 1].in_hi, 1, Z, z0, nz); t0 = (long long)z0 * Y * X; nt = (long long)nz * Y * X; }
+        tfl::model_skip_channel(st, B, (long long)Z * Y * X, pDiv->data, st_in, count, out, L.cout + 1, L.cout, t0, nt);
+      }
       if (m->is3d) Zc *= L.up;
       Yc *= L.up; Xc *= L.up;
       in = out;
       if (L.pool > 1) {
         float* pooled = in == w.act[0] ? w.act[1] : w.act[0];
-        tfl::avg_pool2(st, m->is3d, B * L.cout, Zc, Yc, Xc, in, pooled);
+        if (windowed) span(cone.layer[l].pool_lo, cone.layer[l].pool_hi, 2 * cone.layer[l].conv_d, Zc / 2, z0, nz);
+        else { z0 = 0; nz = -1; }
+        tfl::avg_pool2(st, m->is3d, B * L.cout, Zc, Yc, Xc, in, pooled, z0, nz);
         if (m->is3d) Zc /= 2;
         Yc /= 2; Xc /= 2;
         in = pooled;

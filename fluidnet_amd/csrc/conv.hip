@@ -18,6 +18,8 @@
 //
 // The model-graph form (tfl_model_create_graph: banks, dilation, batch norm, max pooling) has kernels of
 // its own -- k_conv_direct_ex, k_pool2_ex, k_bank_join -- so k_conv_direct and k_avg_pool2 compile exactly as before.
+// A z-slab rank launches k_conv_direct and k_avg_pool2 on the planes of each layer's cone only: the grid covers
+// the window's planes, every voxel computes what it computes on the whole grid.
 #include "tfl_device.hpp"
 #include "tfl_host.hpp"
 
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(256) void k_conv_direct(Dom d, int cin, int ksz, co
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int j = blockIdx.y * blockDim.y + threadIdx.y;
   const int zg = blockIdx.z / G, co0 = (blockIdx.z - zg * G) * CPT;
-  const int b = zg / d.Z, k = zg - b * d.Z;
+  const int b = zg / d.nw, k = d.w0 + (zg - b * d.nw);        // planes [w0, w0 + nw) of the conv grid
   if (i >= d.X || j >= d.Y) return;
   const long long cells = d.sc;
   const long long ocells = (long long)up.oX * up.oY * up.oZ;
@@ -157,12 +159,13 @@ __global__ __launch_bounds__(256) void k_conv_direct_ex(Dom d, int cin, int ksz,
 }
 
 // cudnn average pooling, window = stride = 2, no padding: out size floor(n / 2) per pooled axis (z only in 3-D)
+// (output planes [k0, k0 + nk) only: a z-slab rank pools the planes of its cone)
 template <bool IS3D>
-__global__ __launch_bounds__(256) void k_avg_pool2(int rows, int Zo, int Yo, int Xo, int Z, int Y, int X,
+__global__ __launch_bounds__(256) void k_avg_pool2(int rows, int Zo, int Yo, int Xo, int Z, int Y, int X, int k0, int nk,
                                                    const float* __restrict__ in, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  const int r = blockIdx.z / Zo, k = blockIdx.z - r * Zo;      // r = b*C + c
+  const int r = blockIdx.z / nk, k = k0 + (blockIdx.z - r * nk);      // r = b*C + c
   if (i >= Xo || j >= Yo) return;
   const float* p = in + ((long long)r * Z + (IS3D ? 2 * k : 0)) * Y * X + (long long)(2 * j) * X + 2 * i;
   float s = (p[0] + p[1]) + (p[X] + p[X + 1]);
@@ -261,20 +264,25 @@ static void launch_direct(hipStream_t st, const Dom& d, int B, int cin, int ksz,
     return;
   }
   TFL_TIMED("k_conv_direct", st);
-  if (split) {
-    const dim3 grd((d.X + 63) / 64, (d.Y + 3) / 4, (unsigned)(d.Z * B * (COUT / CPT_SMALL)));
+  const bool split_w = COUT >= 4 && (long long)nxy * d.nw * B < 1024;      // (the plain kernel covers the window's planes)
+  if (split_w) {
+    const dim3 grd((d.X + 63) / 64, (d.Y + 3) / 4, (unsigned)(d.nw * B * (COUT / CPT_SMALL)));
     k_conv_direct<IS3D, COUT, CPT_SMALL><<<grd, blk, 0, st>>>(d, cin, ksz, in, w, bias, out, up);
   } else {
-    const dim3 grd((d.X + 63) / 64, (d.Y + 3) / 4, (unsigned)(d.Z * B));
+    const dim3 grd((d.X + 63) / 64, (d.Y + 3) / 4, (unsigned)(d.nw * B));
     k_conv_direct<IS3D, COUT, COUT><<<grd, blk, 0, st>>>(d, cin, ksz, in, w, bias, out, up);
   }
 }
 
 static bool conv_direct_any(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int cin, int cout, int ksz, int act,
                             const float* in, const float* w, const float* bias, float* out, int upf, int sub, int out_ch,
-                            const ConvEx* ex) {
+                            const ConvEx* ex, int z0 = 0, int nz = -1) {
   Dom d = make_dom(Z, Y, X);
-  d.w0 = 0; d.n0 = Z; d.w1 = 0; d.nw = Z;       // the shape-generic path always covers the whole grid
+  // the shape-generic path covers the planes it is given, not the thread's z-window: the whole grid, or (z-slab rank) the
+  // planes [z0, z0 + nz) of this layer's cone (the model-graph form: always the whole grid)
+  if (ex || nz < 0) { z0 = 0; nz = Z; }
+  d.w0 = z0; d.n0 = nz; d.w1 = 0; d.nw = nz;
+  if (nz == 0) return true;
   ConvUp up;
   up.u = upf; up.uz = is3d ? upf : 1;
   up.a = sub % upf; up.b = (sub / upf) % upf; up.c = is3d ? sub / (upf * upf) : 0;
@@ -301,8 +309,9 @@ static bool conv_direct_any(hipStream_t st, bool is3d, int B, int Z, int Y, int 
 // w: device, [tap][cin][cout]. act: 0 none | 1 ReLU | 2 ReLU6 | 3 sigmoid. out_ch: channel planes per batch item of
 // `out` (0 = cout). Returns false when cout has no instantiation.
 bool conv_direct(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int cin, int cout, int ksz, int act,
-                 const float* in, const float* w, const float* bias, float* out, int upf, int sub, int out_ch) {
-  return conv_direct_any(st, is3d, B, Z, Y, X, cin, cout, ksz, act, in, w, bias, out, upf, sub, out_ch, nullptr);
+                 const float* in, const float* w, const float* bias, float* out, int upf, int sub, int out_ch, int z0, int nz) {
+  if (nz >= 0 && (z0 < 0 || z0 + nz > Z)) return false;
+  return conv_direct_any(st, is3d, B, Z, Y, X, cin, cout, ksz, act, in, w, bias, out, upf, sub, out_ch, nullptr, z0, nz);
 }
 
 bool conv_direct_graph(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int cin, int cout, int ksz, int act,
@@ -344,12 +353,14 @@ bool bank_join(hipStream_t st, bool is3d, bool add, int B, int C, int Z, int Y, 
   return true;
 }
 
-void avg_pool2(hipStream_t st, bool is3d, int rows, int Z, int Y, int X, const float* in, float* out) {
+void avg_pool2(hipStream_t st, bool is3d, int rows, int Z, int Y, int X, const float* in, float* out, int k0, int nk) {
   const int Zo = is3d ? Z / 2 : Z, Yo = Y / 2, Xo = X / 2;
-  const dim3 blk(64, 4, 1), grd((Xo + 63) / 64, (Yo + 3) / 4, (unsigned)(rows * Zo));
+  if (nk < 0 || k0 < 0 || k0 + nk > Zo) { k0 = 0; nk = Zo; }
+  if (nk == 0) return;
+  const dim3 blk(64, 4, 1), grd((Xo + 63) / 64, (Yo + 3) / 4, (unsigned)(rows * nk));
   TFL_TIMED("k_avg_pool2", st);
-  if (is3d) k_avg_pool2<true><<<grd, blk, 0, st>>>(rows, Zo, Yo, Xo, Z, Y, X, in, out);
-  else k_avg_pool2<false><<<grd, blk, 0, st>>>(rows, Zo, Yo, Xo, Z, Y, X, in, out);
+  if (is3d) k_avg_pool2<true><<<grd, blk, 0, st>>>(rows, Zo, Yo, Xo, Z, Y, X, k0, nk, in, out);
+  else k_avg_pool2<false><<<grd, blk, 0, st>>>(rows, Zo, Yo, Xo, Z, Y, X, k0, nk, in, out);
 }
 
 }  // namespace tfl

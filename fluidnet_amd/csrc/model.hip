@@ -487,12 +487,37 @@ __global__ __launch_bounds__(1024) void k_field_stats(long long n, const float* 
   }
 }
 
-__global__ __launch_bounds__(256) void k_skip_channel(long long cells, const float* __restrict__ pDiv,
+// the planes of a [B][C][Z][yx] field from [zlo, zhi) only, every channel: k_field_stats' sums over a z-slab rank's owned planes
+// (its partial sums go through the slab's all-reduce like k_bcs_div_stats')
+__global__ __launch_bounds__(1024) void k_field_stats_planes(int C, long long zstride, long long off, long long n,
+                                                             const float* __restrict__ field, int mode, double* __restrict__ stats) {
+  const int b = blockIdx.x;
+  double s1 = 0.0, s2 = 0.0;
+  if (mode != 2)
+    for (int c = 0; c < C; c++) {
+      const float* p = field + ((long long)b * C + c) * zstride + off;
+      for (long long t = threadIdx.x; t < n; t += 1024) { const double v = (double)p[t]; s1 += v; s2 += v * v; }
+    }
+  __shared__ double sh1[1024], sh2[1024];
+  sh1[threadIdx.x] = s1; sh2[threadIdx.x] = s2;
+  __syncthreads();
+  for (int w = 512; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) { sh1[threadIdx.x] += sh1[threadIdx.x + w]; sh2[threadIdx.x] += sh2[threadIdx.x + w]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    stats[b * 2] = mode == 0 ? sh1[0] : 0.0;
+    stats[b * 2 + 1] = mode == 2 ? 1.0 : sh2[0];
+  }
+}
+
+// (cells [t0, t1) of every batch item: a z-slab rank joins the channel on the planes of the last layer's input cone only)
+__global__ __launch_bounds__(256) void k_skip_channel(long long cells, long long t0, long long t1, const float* __restrict__ pDiv,
                                                       const double* __restrict__ stats, double count,
                                                       float* __restrict__ dst, int och, int ch) {
   const int b = blockIdx.y;
-  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= cells) return;
+  const long long t = t0 + (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= t1) return;
   dst[((long long)b * och + ch) * cells + t] = pDiv[(long long)b * cells + t] / scale_from_stats(stats, b, count);
 }
 
@@ -893,9 +918,17 @@ void model_pre(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const floa
   if ((stages & 2) && !fused) { TFL_TIMED_EXT("k_reduce_stats", st); TFL_LAUNCH_EXT(k_reduce_stats, B, 256, 0, st, (const double*)partials, per_plane * Z, per_plane * zlo, per_plane * (zhi - zlo), stats); }
 }
 
+// planes [z0, z0 + nz) in place of the thread's z-window (nz >= 0)
+static Dom dom_planes(int Z, int Y, int X, int z0, int nz) {
+  Dom d = make_dom(Z, Y, X);
+  if (nz >= 0) { d.w0 = z0; d.n0 = nz; d.w1 = 0; d.nw = nz; }
+  return d;
+}
+
 void model_net_input(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* pDiv, const float* div,
-                     const float* flags, const double* stats, double count, float* x3) {
-  const Dom d = make_dom(Z, Y, X);
+                     const float* flags, const double* stats, double count, float* x3, int z0, int nz) {
+  const Dom d = dom_planes(Z, Y, X, z0, nz);
+  if (d.nw == 0) return;
   const dim3 blk(64, 4, 1), grd = TFL_GRID3(d, B);
   if (is3d) { TFL_TIMED("k_net_input", st); k_net_input<true><<<grd, blk, 0, st>>>(d, pDiv, div, flags, stats, count, x3); }
   else { TFL_TIMED("k_net_input", st); k_net_input<false><<<grd, blk, 0, st>>>(d, pDiv, div, flags, stats, count, x3); }
@@ -903,8 +936,9 @@ void model_net_input(hipStream_t st, bool is3d, int B, int Z, int Y, int X, cons
 
 void model_net_input_gen(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int in_pDiv, int in_UDiv, int in_div,
                          const float* pDiv, const float* Ubc, const float* div, const float* flags, const double* stats,
-                         double count, float* x) {
-  const Dom d = make_dom(Z, Y, X);
+                         double count, float* x, int z0, int nz) {
+  const Dom d = dom_planes(Z, Y, X, z0, nz);
+  if (d.nw == 0) return;
   const dim3 blk(64, 4, 1), grd = TFL_GRID3(d, B);
   TFL_TIMED("k_net_input", st);
   if (is3d) k_net_input_gen<true><<<grd, blk, 0, st>>>(d, in_pDiv, in_UDiv, in_div, pDiv, Ubc, div, flags, stats, count, x);
@@ -916,10 +950,21 @@ void model_field_stats(hipStream_t st, int B, long long n, const float* field, i
   k_field_stats<<<B, 1024, 0, st>>>(n, field, mode, stats);
 }
 
+void model_field_stats_planes(hipStream_t st, int B, int C, int Z, long long yx, int zlo, int zhi, const float* field, int mode,
+                              double* stats) {
+  TFL_TIMED("k_field_stats", st);
+  if (zlo == 0 && zhi == Z)      // the whole array (a slab without neighbours): k_field_stats' one run per item, its order, its bits
+    k_field_stats_planes<<<B, 1024, 0, st>>>(1, (long long)C * Z * yx, 0, (long long)C * Z * yx, field, mode, stats);
+  else
+    k_field_stats_planes<<<B, 1024, 0, st>>>(C, (long long)Z * yx, (long long)zlo * yx, (long long)(zhi - zlo) * yx, field, mode, stats);
+}
+
 void model_skip_channel(hipStream_t st, int B, long long cells, const float* pDiv, const double* stats, double count,
-                        float* dst, int och, int ch) {
+                        float* dst, int och, int ch, long long t0, long long nt) {
+  if (nt < 0 || t0 < 0 || t0 + nt > cells) { t0 = 0; nt = cells; }
+  if (nt == 0) return;
   TFL_TIMED("k_skip_channel", st);
-  k_skip_channel<<<dim3((unsigned)((cells + 255) / 256), (unsigned)B), 256, 0, st>>>(cells, pDiv, stats, count, dst, och, ch);
+  k_skip_channel<<<dim3((unsigned)((nt + 255) / 256), (unsigned)B), 256, 0, st>>>(cells, t0, t0 + nt, pDiv, stats, count, dst, och, ch);
 }
 
 bool model_project(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* pPred, const float* flags,

@@ -398,6 +398,10 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
 // passes B (0,0) read fwd, s / U and flags +-R. Their density goes through the workspace (no in-place kernels) and its owned
 // planes are copied back before T2, which carries every density channel.
 //
+// Every other projection net that is not a graph model (tog, yang, tfl_model_opts, the default topology on the
+// shape-generic kernels): its cone (model_cone) replaces the conv rows above -- p and div travel with the net input's (lo, hi)
+// planes, the halo is tfl_slab_halo_model, and the whole net runs as one stage under per-layer windows.
+//
 // Jacobi projection (simMethod = 'jacobi', state->model = NULL), the un-cut branch's order: setWallBcs on (0,1), setConstVals,
 // divergence (0,0) -> div halos (J-1, J-1) [T3], then maxIter sweeps from p = 0, then velocity update (0,0) <- p (1,0).
 // J = the stored halo depth (own_lo; the smaller of the two sides on a middle rank -- every rank must store the same depth).
@@ -423,6 +427,8 @@ struct SlabGeom {
   bool lower, upper;
   long long yx, N;           // Y*X, B*Zl*Y*X
   int B;
+  bool gen;                  // the model runs the shape-generic forward under per-layer windows
+  tfl::ModelCone cone;       // its cone (s->model != NULL)
 };
 
 int slab_geom(tfl_ctx* c, const tfl_sim_state* s, const tfl_slab* sl, SlabGeom* g) {
@@ -432,6 +438,26 @@ int slab_geom(tfl_ctx* c, const tfl_sim_state* s, const tfl_slab* sl, SlabGeom* 
   g->o0 = sl->own_lo; g->o1 = sl->own_hi;
   g->R = sl->reach > 0 ? sl->reach : 1;
   g->H = tfl_slab_halo(g->R);
+  g->gen = false;
+  g->cone = tfl::ModelCone{};
+  g->cone.F = 1;
+  // (a model without a cone -- graph models, 2-D -- keeps the plain halo here: the step's entry gate refuses it with its reason)
+  if (s->model && tfl::model_cone(s->model, &g->cone)) {
+    g->gen = g->cone.windowed;
+    g->H = tfl_slab_halo_model(s->model, g->R);
+    // pooling windows of the cut grid must be those of the un-cut grid: every cut, owned boundary and local depth on the
+    // model's downsampling factor
+    const int F = g->cone.F;
+    if (F > 1 && (sl->z_first % F || g->o0 % F || g->o1 % F || g->Zl % F || sl->z_total % F)) {
+      if (c) {
+        char buf[240];
+        snprintf(buf, sizeof(buf), "simulate_step_slab: the model pools by %d along z: z_first %d, owned planes [%d, %d), local depth %d "
+                                   "and z_total %d must be multiples of %d", F, sl->z_first, g->o0, g->o1, g->Zl, sl->z_total, F);
+        c->err = buf;
+      }
+      return TFL_EINVAL;
+    }
+  }
   g->yx = (long long)s->flags->Y * s->flags->X;
   g->N = (long long)g->B * g->Zl * g->yx;
   g->lower = sl->z_first + sl->own_lo > 0;
@@ -441,7 +467,15 @@ int slab_geom(tfl_ctx* c, const tfl_sim_state* s, const tfl_slab* sl, SlabGeom* 
                   (g->lower ? g->o0 >= g->H : (g->o0 == 0 && sl->z_first == 0)) &&
                   (g->upper ? g->Zl - g->o1 >= g->H : (g->o1 == g->Zl && sl->z_first + g->Zl == sl->z_total)) &&
                   ((!g->lower && !g->upper) || g->o1 - g->o0 >= g->H);
-  if (!ok) { if (c) c->err = "simulate_step_slab: inconsistent slab description (halo too thin, or owned range thinner than the halo)"; return TFL_EINVAL; }
+  if (!ok) {
+    if (c) {
+      char buf[240];
+      snprintf(buf, sizeof(buf), "simulate_step_slab: inconsistent slab description (halo too thin, or owned range thinner than the halo: "
+                                 "%d planes needed next to each neighbour, tfl_slab_halo_model)", g->H);
+      c->err = buf;
+    }
+    return TFL_EINVAL;
+  }
   return TFL_OK;
 }
 
@@ -554,12 +588,17 @@ void slab_messages(const SlabGeom& g, const tfl_sim_state* s, const tfl_tensor* 
   const int ur = std::max(g.R + 1, 2 * g.R);
   // U and p leave together at the end of a step (ONE message, one packing launch) and are consumed at the start of the
   // next one: nothing writes either field's halo planes in between (p is only read by the first conv layer)
-  m[0].tag = 0; m[0].n = 2; m[0].f[0] = Halo{s->U, ur, ur}; m[0].f[1] = Halo{s->p, 4, 3};
+  // (the net reads its input on the cone of the owned planes: (4, 3) for the default topology, (in_lo, in_hi) of the model_cone
+  // walk for every other net)
+  const int nlo = g.gen ? g.cone.in_lo : 4, nhi = g.gen ? g.cone.in_hi : 3;
+  m[0].tag = 0; m[0].n = 2; m[0].f[0] = Halo{s->U, ur, ur}; m[0].f[1] = Halo{s->p, nlo, nhi};
   m[1].tag = 1; m[1].n = 0;
   if (!s->model) { m[1].n = 1; m[1].f[0] = Halo{s->p, g.J, g.J}; }       // Jacobi: p between two rounds of sweeps (either buffer)
   m[2].tag = 2; m[2].n = 1 + s->n_density; m[2].f[0] = Halo{Uadv, 3, 4};
   for (int i = 0; i < s->n_density; i++) m[2].f[1 + i] = Halo{s->density[i], rr > 4 ? rr : 4, rr > 4 ? rr : 4};
-  m[3].tag = 3; m[3].n = 1; m[3].f[0] = Halo{div, 4, 3};
+  m[3].tag = 3; m[3].n = 1; m[3].f[0] = Halo{div, nlo, nhi};
+  // a net whose input holds UDiv also reads SetWallBcs(U) there: tfl_model_begin has left it in U's owned planes
+  if (g.gen && g.cone.reads_U) { m[3].n = 2; m[3].f[1] = Halo{s->U, nlo, nhi}; }
   if (!s->model) m[3].f[0] = Halo{div, g.J > 1 ? g.J - 1 : 0, g.J > 1 ? g.J - 1 : 0};     // what the first round of sweeps reads
 }
 
@@ -676,6 +715,15 @@ void reach_quiesce(tfl_ctx* c) {   // every publication enqueued so far has land
 int32_t tfl_slab_halo(int32_t reach) {
   const int r = reach > 0 ? reach : 1;
   return 2 * r + 1 > 4 ? 2 * r + 1 : 4;
+}
+
+int32_t tfl_slab_halo_model(const tfl_model* model, int32_t reach) {
+  const int h = tfl_slab_halo(reach);
+  if (!model) return h;
+  tfl::ModelCone cone;
+  if (!tfl::model_cone(model, &cone)) return TFL_EUNSUPPORTED;
+  const int need = cone.fused ? h : std::max(h, cone.depth);      // (the fused default topology: its (4, 3) cone, always <= h)
+  return (need + cone.F - 1) / cone.F * cone.F;
 }
 
 int64_t tfl_simulate_slab_workspace_floats(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state* s, const tfl_slab* sl) {
@@ -1044,7 +1092,7 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   // ---- projection ----------------------------------------------------------------------------------------------------
   const long long mws = ws_floats - (cw - ws);
   (void)tfl_set_stages(c, 2);
-  const Split spD = split_owned(g, 4);
+  const Split spD = split_owned(g, g.gen ? std::max(g.cone.in_lo, g.cone.in_hi) : 4);     // (the planes message T3 sends)
   if (ovl && spD.has_strips && spD.has_interior) {
     WIN(tfl_set_z_window(c, spD.a0, spD.a1, spD.b0, spD.b1));
     rc = tfl_model_begin(c, s->model, s->U, s->flags, s->U, cw, mws, g.o0, g.o1, W.stats); if (rc) return rc;
@@ -1056,17 +1104,28 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
     rc = tfl_model_begin(c, s->model, s->U, s->flags, s->U, cw, mws, g.o0, g.o1, W.stats); if (rc) return rc;
     rc = msg_start(c, g, comm, m[3]); if (rc) return rc;
   }
-  (void)tfl_set_stages(c, 4);
-  rc = tfl_model_begin(c, s->model, s->U, s->flags, s->U, cw, mws, g.o0, g.o1, W.stats); if (rc) return rc;
-  if (multi && comm->allreduce_sum(comm->user, W.stats, 2ll * g.B) != 0) { c->err = "simulate_step_slab: comm callback failed (allreduce_sum)"; return TFL_EINVAL; }
-  const double count = 3.0 * (double)sl->z_total * (double)g.yx;
+  double count = 3.0 * (double)sl->z_total * (double)g.yx;
+  if (g.cone.norm == 0) {        // std(UDiv): tfl_model_begin's partial sums over the owned planes
+    (void)tfl_set_stages(c, 4);
+    rc = tfl_model_begin(c, s->model, s->U, s->flags, s->U, cw, mws, g.o0, g.o1, W.stats); if (rc) return rc;
+  } else {                       // another field / the l2 norm / none: the same over the owned planes
+    tfl::model_slab_stats(c->stream, s->model, g.B, g.Zl, g.yx, g.o0, g.o1, sl->z_total, s->p->data, s->U->data, div.data, W.stats, &count);
+  }
+  // (no input scale: every rank holds (0, 1) already -- a sum would make it (0, world))
+  if (multi && g.cone.norm != 2 && comm->allreduce_sum(comm->user, W.stats, 2ll * g.B) != 0) { c->err = "simulate_step_slab: comm callback failed (allreduce_sum)"; return TFL_EINVAL; }
   const bool late_ubc = s->UBC && s->UBC->sparse && s->UBC->idem;
   const tfl_tensor* ubc = (s->UBC && !late_ubc) ? &s->UBC->bc : nullptr;
   const tfl_tensor* umask = (s->UBC && !late_ubc) ? &s->UBC->inv : nullptr;
   auto finish = [&]() { return tfl_model_finish(c, s->model, s->p, s->flags, s->p, s->U, cw, mws, W.stats, count, ubc, umask, 1, -1e6f, 1e6f); };
   (void)tfl_set_stages(c, 1);
   const Win w1 = ext(g, 3, 2);
-  if (ovl && g.o1 - 1 > g.o0 + 1) {
+  if (g.gen) {
+    // every other net: the whole shape-generic forward as stage 1, each launch on its layer's cone of the owned planes (the
+    // window names the owned planes; tfl_model_finish widens it layer by layer)
+    rc = msg_finish(c, g, comm, m[3]); if (rc) return rc;
+    WIN(set_win(c, ext(g, 0, 0)));
+    rc = finish(); if (rc) return rc;
+  } else if (ovl && g.o1 - 1 > g.o0 + 1) {
     // interior of conv 1 needs only owned planes of div / p: it runs while the div halos travel
     WIN(tfl_set_z_window(c, g.lower ? g.o0 + 1 : w1.a, g.upper ? g.o1 - 1 : w1.b, 0, 0));
     rc = finish(); if (rc) return rc;
@@ -1078,8 +1137,10 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
     WIN(set_win(c, w1));
     rc = finish(); if (rc) return rc;
   }
-  (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, 2, 1))); rc = finish(); if (rc) return rc;
-  (void)tfl_set_stages(c, 4); WIN(set_win(c, ext(g, 1, 0))); rc = finish(); if (rc) return rc;
+  if (!g.gen) {
+    (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, 2, 1))); rc = finish(); if (rc) return rc;
+    (void)tfl_set_stages(c, 4); WIN(set_win(c, ext(g, 1, 0))); rc = finish(); if (rc) return rc;
+  }
   (void)tfl_set_stages(c, 8); WIN(set_win(c, ext(g, 0, 0)));
   if (late_ubc) fold_ask(c, s->UBC);          // the projection kernel applies the sparse U pair itself (owned planes: what T0 sends)
   rc = finish();

@@ -199,19 +199,23 @@ void model_pre(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const floa
                float* div, double* partials, double* stats, int zlo, int zhi, int stages = 3, unsigned* ticket = nullptr,
                const unsigned short* wall_code = nullptr);      // wall_code: the flags' tfl_wall_plan (round 6), or null
 void wall_code(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* flags, unsigned short* code);
+// (z0 / nz, here and in the two below: the planes [z0, z0 + nz) only; nz < 0 = the thread's z-window, as make_dom reads it)
 void model_net_input(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* pDiv, const float* div,
-                     const float* flags, const double* stats, double count, float* x3);
+                     const float* flags, const double* stats, double count, float* x3, int z0 = 0, int nz = -1);
 // the general net input of lib/model.lua:130-148: channels {pDiv/scale?, SetWallBcs(U)/scale (C)?, div/scale?, occupancy} in
 // this order into x [B][in_c][Z][Y][X]; Ubc = the wall-BC'd velocity tfl_model_begin left in UOut
 void model_net_input_gen(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int in_pDiv, int in_UDiv, int in_div,
                          const float* pDiv, const float* Ubc, const float* div, const float* flags, const double* stats,
-                         double count, float* x);
+                         double count, float* x, int z0 = 0, int nz = -1);
 // stats[b] = {mode 0: sum x, sum x^2 | mode 1: 0, sum x^2 | mode 2: 0, 1} over the n floats of sample b of `field`
 // (the three ways tfl_model_opts sets the input scale through scale_from_stats: std, l2 norm with count = 2, none)
 void model_field_stats(hipStream_t st, int B, long long n, const float* field, int mode, double* stats);
+// the same over the planes [zlo, zhi) of every channel of a [B][C][Z][yx] field only (a z-slab rank's owned planes)
+void model_field_stats_planes(hipStream_t st, int B, int C, int Z, long long yx, int zlo, int zhi, const float* field, int mode,
+                              double* stats);
 // dst[b][ch][cell] = pDiv[b][cell] / scale_b: the joined pressure-skip channel (model.lua:356-360); dst has `och` planes per item
 void model_skip_channel(hipStream_t st, int B, long long cells, const float* pDiv, const double* stats, double count,
-                        float* dst, int och, int ch);
+                        float* dst, int och, int ch, long long t0 = 0, long long nt = -1);     // cells [t0, t0 + nt) only
 // returns true when the launch also folded max |u_z| of what it wrote into *reach_acc (round 6: k_project_v4 on full blocks)
 bool model_project(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* pPred, const float* flags,
                    const double* stats, double count, float* Uio, float* pOut, const float* UBC, const float* UInvMask,
@@ -235,14 +239,42 @@ long long pack_planes(hipStream_t st, int n, float* const* ptrs, const int* rows
 bool model_is_graph(const tfl_model* m);
 // the factor its grid must be divisible by (the mres pyramid times the pooling; 1 = any grid)
 int model_grid_factor(const tfl_model* m);
+// The z-slab cone of a 3-D model that is not a graph model, walked backwards from what the velocity update reads
+// (pPred on the owned planes widened by (1, 0)). Extents are planes below / above the owned range in the resolution named.
+struct LayerCone {
+  int conv_lo, conv_hi, conv_d;   // the planes each conv launch computes, at its own resolution grid / conv_d (the coarse grid
+                                  // of a ConvolutionUpsample)
+  int pool_lo, pool_hi;           // the pooled planes (pool > 1), at grid / (2 * conv_d)
+  int in_lo, in_hi;               // the planes of the layer's input it reads, at grid / conv_d
+};
+struct ModelCone {
+  bool fused;                     // the 3-D default topology on its fused kernels: staged launches of their own, halo (4, 3)
+  bool windowed;                  // the shape-generic forward under per-layer windows (everything else the slab step takes)
+  int F;                          // downsampling factor (the pooling product): cuts, owned ranges and local depths align to it
+  int in_lo, in_hi;               // planes of net input (pDiv, div, flags, UDiv) the owned planes need below / above
+  int depth;                      // the stored halo the cone needs (max over the layers of resolution x extent), before rounding
+  bool reads_U;                   // the net input holds UDiv: the divergence message also carries SetWallBcs(U)
+  int norm;                       // what sets the input scale on a slab: 0 = UDiv std (tfl_model_begin's sums), 1 = the
+                                  // owned planes of another field / function (model_slab_stats), 2 = none (no all-reduce)
+  int nlayers;
+  LayerCone layer[32];
+};
+// false (and why in `why`) for graph models, 2-D models and null
+bool model_cone(const tfl_model* m, ModelCone* out, const char** why = nullptr);
+// A windowed model's input scale over the owned planes [zlo, zhi) of a slab (norm = 1 / 2), into stats[2 * B]; *count = what
+// tfl_model_finish then takes with them (z_total: planes of the whole grid)
+void model_slab_stats(hipStream_t st, const tfl_model* m, int B, int Z, long long yx, int zlo, int zhi, int z_total,
+                      const float* pDiv, const float* U, const float* div, double* stats, double* count);
 
 // conv.hip
 // upf > 1: the result goes to sub-position `sub` (= (c*upf + b)*upf + a) of an upf-times finer output grid (pixel shuffle)
 // act: 0 none | 1 ReLU | 2 ReLU6 | 3 sigmoid; out_ch: channel planes per batch item of `out` (0 = cout)
+// z0 / nz: compute the conv-grid planes [z0, z0 + nz) only (nz < 0: all Z; the thread's z-window is not read)
 bool conv_direct(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int cin, int cout, int ksz, int act,
-                 const float* in, const float* w, const float* bias, float* out, int upf = 1, int sub = 0, int out_ch = 0);
-// 2x average pooling of `rows` = B*C planes-stacks [Z][Y][X] -> [Z/2 (3-D)][Y/2][X/2]
-void avg_pool2(hipStream_t st, bool is3d, int rows, int Z, int Y, int X, const float* in, float* out);
+                 const float* in, const float* w, const float* bias, float* out, int upf = 1, int sub = 0, int out_ch = 0,
+                 int z0 = 0, int nz = -1);
+// 2x average pooling of `rows` = B*C planes-stacks [Z][Y][X] -> [Z/2 (3-D)][Y/2][X/2]; output planes [k0, k0 + nk) (nk < 0: all)
+void avg_pool2(hipStream_t st, bool is3d, int rows, int Z, int Y, int X, const float* in, float* out, int k0 = 0, int nk = -1);
 // the model-graph form (tfl_model_create_graph): the same conv with tap spacing `dil`, the output at channel planes
 // [c0, c0 + cout) of `out`, and the folded batch norm y = fmaf(act(x), bn_s[c], bn_t[c]) when bn_s is non-null
 bool conv_direct_graph(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int cin, int cout, int ksz, int act,

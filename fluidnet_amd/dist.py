@@ -12,6 +12,7 @@ halo), packs the halo messages, and calls back into THIS module only to move the
     U (max(R+1, 2R) planes) and p (4 / 3 planes)  leave at the end of a step, are consumed by the next one
     advected U (3 / 4) + density (max(4, 2R+1))  after MacCormack pass B, overlapped with the interior of pass B
     divergence (4 / 3)                        overlapped with the interior of the first conv layer
+(other projection nets: p and the divergence with the planes their cone reads; slab_halo(reach, model))
 plus one 2-double all-reduce for the ConvNet's global std(U) normaliser (lib/model.lua:93-117). xGMI is point-to-point:
 a slab only ever talks to ranks r-1 and r+1, each over its own link, so every exchange is one grouped send/recv pair
 per neighbour -- no ring, no all-to-all.
@@ -27,22 +28,76 @@ from ._lib import COMM_ALLREDUCE, COMM_START, COMM_WAIT, TfluidsError, tfl_comm,
 TFL_EREACH = -5     # include/tfluids_hip.h: check_reach = 2 refused the step, nothing written
 
 
-def slab_halo(reach=1):
-    """Planes a slab stores next to each neighbour (tfl_slab_halo): max(4, 2*reach + 1)."""
+def slab_halo(reach=1, model=None):
+    """Planes a slab stores next to each neighbour: tfl_slab_halo = max(4, 2*reach + 1), or with the FluidNetModel the step
+    projects with, tfl_slab_halo_model -- that, widened to the depth of net input the model's cone reads and rounded up to its
+    downsampling factor (the default topology: unchanged, 3-D `tog`: 16). Graph and 2-D models are refused."""
     r = max(int(reach), 1)
-    return max(4, 2 * r + 1)
+    if model is None:
+        return max(4, 2 * r + 1)
+    lib, ctx = tfluids._context(torch.empty(0, device="cuda"))
+    h = int(lib.tfl_slab_halo_model(model._handle(lib, ctx, torch.cuda.current_device()), r))
+    if h < 0:
+        raise TfluidsError("the z-slab step cannot run this model: %s" % (model_cone_refusal(model) or "refused"))
+    return h
+
+
+def model_cone_refusal(model):
+    """why the z-slab step refuses `model` (None: it takes it)"""
+    g = model.graph
+    if g is not None and (g["banksNum"] > 1 or g["addBatchNorm"] or g["poolType"] != "avg"):     # (else: tfl_model_create_opts)
+        return "banked, batch-norm and max-pool models run un-sharded only"
+    if not model.is3D:
+        return "2-D grids have no z to cut"
+    return None
+
+
+def model_cone(model):
+    """The z-slab cone of a (3-D, non-graph) FluidNetModel, as tfl_slab_halo_model's walk forms it (csrc/abi.cpp model_cone):
+    backwards from pPred on the owned planes widened by (1, 0), through each layer's pooling (extents x 2), ConvolutionUpsample
+    (ceil(extent / 2) at the coarse grid) and conv (+ k // 2). Returns a dict: `layers` = per layer {conv: (lo, hi), d, pool:
+    (lo, hi) or None, input: (lo, hi)} (planes below / above the owned range at grid / d), `input` = the net input's (lo, hi),
+    `depth` = max over the layers of d x input extent, `F` = the downsampling factor, `halo` = depth rounded up to F (before
+    the max with tfl_slab_halo(reach))."""
+    why = model_cone_refusal(model)
+    if why:
+        raise TfluidsError(why)
+    lo, hi, d, depth, num, den, F = 1, 0, 1, 1, 1, 1, 1
+    for p, u in zip(model.pool, model.up):      # the coarsest resolution the net reaches (tfl_model::max_down)
+        num, den = num * u, den * p
+        F = max(F, den // num)
+    out = []
+    for (w, _), p, u in reversed(list(zip(model.layers, model.pool, model.up))):
+        k = w.shape[-1]
+        pool = None
+        if p > 1:
+            pool = (lo, hi)
+            lo, hi, d = 2 * lo, 2 * hi, d // 2
+        if u > 1:
+            lo, hi, d = (lo + 1) // 2, (hi + 1) // 2, d * 2
+        conv = (lo, hi)
+        lo, hi = lo + k // 2, hi + k // 2
+        depth = max(depth, d * max(lo, hi))
+        out.append(dict(conv=conv, d=d, pool=pool, input=(lo, hi)))
+    out.reverse()
+    return dict(layers=out, input=(lo, hi), depth=depth, F=F, halo=-(-depth // F) * F)
 
 
 class SlabLayout:
-    """Owned planes [z0, z1) of a z_total grid and the extended local range [lo, hi)."""
+    """Owned planes [z0, z1) of a z_total grid and the extended local range [lo, hi). model: the FluidNetModel the step
+    projects with -- the halo becomes slab_halo(reach, model), and a pooling model needs slabs on its downsampling factor."""
 
-    def __init__(self, z_total, world, rank, reach=1):
+    def __init__(self, z_total, world, rank, reach=1, model=None):
         if z_total % world != 0:
             raise ValueError("z extent %d is not divisible by %d ranks" % (z_total, world))
         per = z_total // world
-        halo = slab_halo(reach) if world > 1 else 0
+        halo = slab_halo(reach, model) if world > 1 else 0
+        F = model_cone(model)["F"] if model is not None else 1
+        if per % F:
+            raise ValueError("slab thickness %d is not a multiple of the model's downsampling factor %d" % (per, F))
         if world > 1 and per < halo:
             raise ValueError("slab thickness %d is smaller than the halo %d" % (per, halo))
+        self.model = model
         self.z_total, self.world, self.rank, self.reach, self.halo = z_total, world, rank, max(int(reach), 1), halo
         self.z0, self.z1 = rank * per, (rank + 1) * per
         self.lo, self.hi = max(self.z0 - halo, 0), min(self.z1 + halo, z_total)
@@ -314,7 +369,8 @@ class SlabSimulation:
         identity, its tensors are replaced. Collective: every rank arrives here at the same step with the same reach."""
         old = self.lay
         try:
-            new = SlabLayout(old.z_total, old.world, old.rank, reach)
+            # (the model halo and its alignment stay: an explicit layout's model, else the one the step projects with)
+            new = SlabLayout(old.z_total, old.world, old.rank, reach, model=getattr(old, "model", None) or self.model)
         except ValueError as e:
             raise TfluidsError("the flow needs a back-trace reach of %d planes: %s" % (reach, e))
         if self.graph is not None:

@@ -234,6 +234,7 @@ typedef struct tfl_comm {
   int32_t capturable;
 } tfl_comm;
 int32_t tfl_slab_halo(int32_t reach);
+int32_t tfl_slab_halo_model(const tfl_model* model, int32_t reach);
 int64_t tfl_simulate_slab_workspace_floats(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state,
                                            const tfl_slab* slab);
 int tfl_simulate_step_slab(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state, tfl_slab* slab,
@@ -649,11 +650,21 @@ end
 -- (no counterpart in the reference, which is single-GPU; BASELINE config 5). Rank 0 calls M.rcclUniqueId() and hands
 -- the 128-byte string to the other ranks (a file, the launcher's environment, a socket); every rank then builds
 --   local slab = M.Slab{zTotal = 256, zFirst = lo, ownLo = c0, ownHi = c1, id = idString, rank = r, world = n}
--- on its LOCAL extended tensors (owned planes + tfl_slab_halo(reach) planes next to each neighbour) and steps with
+-- on its LOCAL extended tensors (owned planes + M.slabHalo(reach, model) planes next to each neighbour) and steps with
 --   slab:simulate(conf, mconf, batch, model)       -- tfluids.simulate on the slab, bit-equal on the owned planes
 --                                                     (mconf.simMethod = 'jacobi': no model, bit-equal at any world size;
 --                                                      any mconf.advectionMethod, batch.density a table of up to 8 channels)
 --   slab:drain()                                   -- before reading halo planes / at the end
+-- The halo planes a slab stores next to each neighbour for reach R when the step projects with `model` (an M.Model, or nil for
+-- the Jacobi projection): tfl_slab_halo_model -- max(4, 2R + 1), widened to the depth the net's cone reads and rounded up to
+-- its downsampling factor (16 for the 3-D tog table; DESIGN.md 6d). With a pooling net, zFirst / ownLo / ownHi and the local
+-- depth go on that factor too. Graph and 2-D models: an error (the slab step refuses them).
+function M.slabHalo(reach, model)
+  local h = lib.tfl_slab_halo_model(model and model.handle or nil, reach or 1)
+  if h < 0 then error('tfluids_hip: the z-slab step cannot run this model (graph or 2-D models run un-sharded only)', 2) end
+  return h
+end
+
 function M.rcclUniqueId()
   local id = ffi.new('char[128]')
   check(lib.tfl_rccl_get_unique_id(ctx, id))
@@ -705,9 +716,10 @@ function Slab:simulate(conf, mconf, batch, model)
   self.prm, self.st, self.keep = prm, st, keep
   local rc = lib.tfl_simulate_step_slab(ctx, prm, st, self.desc, self.callbacks, self.ws, self.n)
   if rc == -5 then      -- TFL_EREACH (checkReach = 'exact'): every rank is here, nothing has been written
-    error(string.format('tfluids_hip: the flow needs a back-trace reach of %d planes: re-cut the local tensors with tfl_slab_halo(%d) halo planes ' ..
-                        '(tfl_slab_exchange fetches them) and create the Slab again with reach = %d', lib.tfl_slab_needed_reach(ctx),
-                        lib.tfl_slab_needed_reach(ctx), lib.tfl_slab_needed_reach(ctx)))
+    local need = lib.tfl_slab_needed_reach(ctx)
+    error(string.format('tfluids_hip: the flow needs a back-trace reach of %d planes: re-cut the local tensors with M.slabHalo(%d, model) = %d ' ..
+                        'halo planes (tfl_slab_exchange fetches them) and create the Slab again with reach = %d', need, need,
+                        lib.tfl_slab_halo_model(st.model, need), need))
   end
   check(rc)
 end

@@ -362,8 +362,10 @@ int tfl_model_forward(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* pDiv, co
  * all-reduces stats across ranks; `finish` runs the rest with `count` = the GLOBAL number of velocity
  * samples per batch item (C*Z*Y*X of the whole grid). tfl_model_forward == begin(0, Z) + finish.
  * Models created with non-default tfl_model_opts (another normaliser channel / function, normalisation off) form their
- * scale from statistics the model computes itself inside `finish`: pass stats = NULL there (a caller-supplied `stats`
- * is refused with TFL_EUNSUPPORTED rather than silently ignored), and `count` is not used. */
+ * scale from statistics the model computes itself inside `finish` over the whole array when stats = NULL (`count` is then
+ * not used). A caller that passes `stats` has formed the (sum, sum of squares | 0, sum of squares | 0, 1) pair and its
+ * `count` itself (std | l2 norm with count 2 | none with count 2): a z-slab rank does so over its owned planes, and a
+ * windowed / staged `finish` of such a model requires it. */
 int tfl_model_begin(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* UDiv, const tfl_tensor* flags,
                     const tfl_tensor* UOut, float* workspace, int64_t workspace_floats, int zlo, int zhi,
                     double* stats);
@@ -493,8 +495,11 @@ int tfl_set_z_origin(tfl_ctx* ctx, int z_first, int z_total);
 /* Pass selection for the multi-pass operators (0 = all passes, the default), so that each pass can get its own
  * window: advectScalar 1 = 3^dim min/max grid, 2 = pass A (forward), 4 = pass B (backward + correct + clamp);
  * advectVel 2 / 4 likewise; vorticityConfinement 2 = curl, 4 = confinement force; tfl_model_begin 2 = wall BCs +
- * divergence + partial sums, 4 = reduction over [zlo, zhi); tfl_model_finish (3-D default topology only) 1 / 2 / 4 =
- * first / second / third(+1x1x1) conv layer, 8 = velocity update + un-scale + wall BCs. */
+ * divergence + partial sums, 4 = reduction over [zlo, zhi); tfl_model_finish on the 3-D default topology's fused kernels
+ * 1 / 2 / 4 = first / second / third(+1x1x1) conv layer, 8 = velocity update + un-scale + wall BCs; on any other 3-D model
+ * that is not a graph model 1 = the whole net, every launch on its layer's cone of the window's planes (the window names the
+ * planes whose pressure must come out exact and is aligned to the model's downsampling factor), 8 = as above. Such a windowed
+ * forward of a model with non-default tfl_model_opts takes its input-scale stats from the caller. */
 int tfl_set_stages(tfl_ctx* ctx, int mask);
 
 /* The divergence plane tfl_model_begin wrote inside `workspace` (a [B][1][Z][Y][X] field): a slab rank exchanges its
@@ -575,6 +580,13 @@ typedef struct tfl_comm {
 
 /* Halo depth a slab must store next to each neighbour for reach R (>= 4). */
 int32_t tfl_slab_halo(int32_t reach);
+/* The same for a step that projects with `model` (NULL: the Jacobi projection, = tfl_slab_halo(reach)): max(tfl_slab_halo(reach),
+ * the depth of net input the model's cone reads below / above the owned planes), rounded up to the model's downsampling factor F
+ * (the pooling product along z). The 3-D default topology returns exactly tfl_slab_halo(reach); the 3-D `tog` table needs 16
+ * (F = 4). With F > 1 the slab's z_first, owned boundaries and local depth must be multiples of F as well (the pooling windows of
+ * the cut grid are then the un-cut grid's). TFL_EUNSUPPORTED (< 0) for the models the slab step refuses: graph models (banks,
+ * batch norm, max pooling) and 2-D models. DESIGN.md 6d. */
+int32_t tfl_slab_halo_model(const tfl_model* model, int32_t reach);
 int64_t tfl_simulate_slab_workspace_floats(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state,
                                            const tfl_slab* slab);
 
