@@ -1,7 +1,8 @@
 // simulate.cpp -- tfluids.simulate() (torch/lib/simulate.lua:175-327) as one native call, for hosts that are not
-// Python. Pure orchestration of the operators behind include/tfluids_hip.h (nothing here launches a kernel of its
-// own except the one-time BC scan): the same sequence, temp layout and launch-saving rules as
-// fluidnet_amd/simulate.py, which it is tested against bit for bit (tests/test_hip_simulate.py).
+// Python. Orchestration of the operators behind include/tfluids_hip.h: the same sequence, temp layout and launch-saving
+// rules as fluidnet_amd/simulate.py, which it is tested against bit for bit (tests/test_hip_simulate.py). The un-cut step
+// launches no kernel of its own except the one-time BC scan; the z-slab rank-step (tfl_simulate_step_slab) also launches
+// the plane kernels of its Jacobi projection and its halo bookkeeping (reach absmax / publication, message packing).
 #include "../../include/tfluids_hip.h"
 #include "tfl_ctx.hpp"
 #include "tfl_host.hpp"
@@ -83,21 +84,18 @@ int set_const_vals(tfl_ctx* c, const tfl_sim_state* s, const tfl_tensor* U_now, 
   return apply_bcs(c, todo, n);
 }
 
-// Folding a sparse pair into the kernel that produces the field (tfl_host.hpp BcFold): fold_ask before the operator, fold_took
-// after it. TFL_BC_FOLD=0 keeps every pair in its own launch (A/B switch).
-bool fold_ask(tfl_ctx* c, const tfl_bc_plan* p) {
-  const char* e = getenv("TFL_BC_FOLD");       // (read per call: the A/B parity test switches it inside one process)
-  const bool off = e && atoi(e) == 0;
-  c->fold_done = false;
-  if (off || !p || !p->sparse || !p->boxed || !p->d_fold || p->n_idx == 0) { c->fold = tfl::no_fold(); return false; }
-  c->fold = tfl::BcFoldArg{p->d_fold, (unsigned)p->box[2] | ((unsigned)p->box[4] << 16), (unsigned)p->box[3] | ((unsigned)p->box[5] << 16)};
-  return true;
-}
-// the same request as a value (the pair kernels of advect_pair3.hip take two of them as arguments)
+// Folding a sparse pair into the kernel that produces the field (tfl_host.hpp BcFold): fold_arg is the request as a value
+// (the pair kernels of advect_pair3.hip take two of them as arguments), fold_ask hands it to the next operator through the
+// context, fold_took reads the acknowledgement after it. TFL_BC_FOLD=0 keeps every pair in its own launch (A/B switch).
 tfl::BcFoldArg fold_arg(const tfl_bc_plan* p) {
-  const char* e = getenv("TFL_BC_FOLD");
+  const char* e = getenv("TFL_BC_FOLD");       // (read per call: the A/B parity test switches it inside one process)
   if ((e && atoi(e) == 0) || !p || !p->sparse || !p->boxed || !p->d_fold || p->n_idx == 0) return tfl::no_fold();
   return tfl::BcFoldArg{p->d_fold, (unsigned)p->box[2] | ((unsigned)p->box[4] << 16), (unsigned)p->box[3] | ((unsigned)p->box[5] << 16)};
+}
+bool fold_ask(tfl_ctx* c, const tfl_bc_plan* p) {
+  c->fold_done = false;
+  c->fold = fold_arg(p);
+  return c->fold.dev != nullptr;
 }
 bool fold_took(tfl_ctx* c) {
   const bool d = c->fold_done;
@@ -120,6 +118,30 @@ Sizes sizes_of(const tfl_sim_state* s) {
   return z;
 }
 std::string method_of(const tfl_sim_params* p) { return p->simMethod && p->simMethod[0] ? p->simMethod : "convnet"; }
+
+// an earlier ConvNet projection left the fp16 range; `who` = the entry point, `some_rank` = the z-slab step's collective gate
+int range_refusal(tfl_ctx* c, const char* who, bool some_rank = false) {
+  c->err = std::string(who) + ": an earlier step's ConvNet projection clamped activations at the fp16 range" + (some_rank ? " on some rank" : "") +
+           " (a blown-up simulation); read the count" + (some_rank ? "s" : "") +
+           " with tfl_model_range_errors, or create the model under TFL_CONV_PATH=winograd (strict fp32)";
+  return TFL_ERANGE;
+}
+
+// gravity * (-dx / 4) * scale (formed in double, rounded once): the force of addBuoyancy (buoyancyScale) / addGravity (gravityScale)
+void scaled_gravity(const tfl_sim_params* prm, double dx, double scale, float out[3]) {
+  const float sc = (float)(-(dx / 4.0) * scale);
+  for (int i = 0; i < 3; i++) out[i] = prm->gravity[i] * sc;
+}
+
+// sparse idempotent U BCs go after the projection by index list instead of as two dense fields inside it (round 4: the
+// projection kernel applies them itself on the rows inside their box -- fold_ask -- and the launch goes too)
+struct LateUbc { bool late; const tfl_tensor *bc, *mask; };
+LateUbc late_ubc_of(const tfl_sim_state* s) {
+  const bool late = s->UBC && s->UBC->sparse && s->UBC->idem;
+  return LateUbc{late, (s->UBC && !late) ? &s->UBC->bc : nullptr, (s->UBC && !late) ? &s->UBC->inv : nullptr};
+}
+
+#define TRY(x) do { int rc_ = (x); if (rc_ != TFL_OK) return rc_; } while (0)
 
 }  // namespace
 
@@ -199,11 +221,7 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
   int rc;
   // an earlier step's projection left the fp16 range of the default 3-D conv path (no sync: the word the projection kernel
   // wrote to pinned memory): refuse to step on from a clamped pressure, before anything of this step has been written
-  if (s->model && method_of(prm) == "convnet" && tfl_model_range_flag(c, s->model) > 0) {
-    c->err = "simulate_step: an earlier step's ConvNet projection clamped activations at the fp16 range (a blown-up simulation); "
-             "read the count with tfl_model_range_errors, or create the model under TFL_CONV_PATH=winograd (strict fp32)";
-    return TFL_ERANGE;
-  }
+  if (s->model && method_of(prm) == "convnet" && tfl_model_range_flag(c, s->model) > 0) return range_refusal(c, "simulate_step");
   // a banked / batch-norm / max-pool model refuses a grid its pyramid and pooling cannot halve evenly: here, before the
   // advection writes anything (tfl_model_begin would refuse the same grid half-way through the step)
   if (s->model && method_of(prm) == "convnet" && tfl::model_is_graph(s->model)) {
@@ -233,8 +251,8 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
   tfl_tensor vfwd = view(ws, (int)z.C), vbwd = view(ws + z.C * z.N, (int)z.C), Uadv = view(ws + 2 * z.C * z.N, (int)z.C);
   const bool buoyant = s->n_density > 0 && prm->buoyancyScale > 0.0;
   const double dx = tfl_getDx(c, s->flags);
-  const float bsc = (float)(-(dx / 4.0) * prm->buoyancyScale);
-  const float bg[3] = {prm->gravity[0] * bsc, prm->gravity[1] * bsc, prm->gravity[2] * bsc};
+  float bg[3];
+  scaled_gravity(prm, dx, prm->buoyancyScale, bg);
   const bool U_pair_asked = fold_ask(c, s->UBC);
   // addBuoyancy follows advectVel and the first setConstVals directly and needs nothing but the advected density, which is
   // final by now: pass B of advectVel may add the force itself behind the folded U pair (tfl_host.hpp BuoyFold; round 5).
@@ -297,8 +315,8 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
     cur = dst;
   }
   if (gravity_on) {
-    const float sc = (float)((-dx / 4.0) * prm->gravityScale);
-    const float g[3] = {prm->gravity[0] * sc, prm->gravity[1] * sc, prm->gravity[2] * sc};
+    float g[3];
+    scaled_gravity(prm, dx, prm->gravityScale, g);
     rc = tfl_addGravity(c, cur, s->flags, g, prm->dt, is3D, nullptr);
     if (rc) return rc;
   }
@@ -336,17 +354,13 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
   const int max_iter = prm->maxIter > 0 ? prm->maxIter : 100;
   if (sm == "convnet") {
     if (!s->model) return TFL_EINVAL;
-    // sparse idempotent U BCs go after the projection by index list instead of as two dense fields inside it
-    // (round 4: the projection kernel applies them itself on the rows inside their box -- fold_ask -- and the launch goes too)
-    const bool late_ubc = s->UBC && s->UBC->sparse && s->UBC->idem;
-    const tfl_tensor* ubc = (s->UBC && !late_ubc) ? &s->UBC->bc : nullptr;
-    const tfl_tensor* umask = (s->UBC && !late_ubc) ? &s->UBC->inv : nullptr;
-    if (late_ubc) fold_ask(c, s->UBC);
-    rc = tfl_model_forward(c, s->model, s->p, cur, s->flags, s->p, s->U, ws, ws_floats, ubc, umask, 1, -1e6f, 1e6f);
+    const LateUbc lu = late_ubc_of(s);
+    if (lu.late) fold_ask(c, s->UBC);
+    rc = tfl_model_forward(c, s->model, s->p, cur, s->flags, s->p, s->U, ws, ws_floats, lu.bc, lu.mask, 1, -1e6f, 1e6f);
     const bool folded = fold_took(c);
     if (rc) return rc;
     // p was rewritten by the model, density has not changed since the second setConstVals
-    return set_const_vals(c, s, s->U, late_ubc && !folded, Unchanged{false, false, true});
+    return set_const_vals(c, s, s->U, lu.late && !folded, Unchanged{false, false, true});
   }
   tfl_tensor div = view(ws, 1);
   rc = tfl_velocityDivergenceForward(c, s->U, s->flags, &div, is3D);
@@ -579,7 +593,7 @@ int msg_finish(tfl_ctx* c, const SlabGeom& g, const tfl_comm* comm, const Msg& q
   return TFL_OK;
 }
 
-// the three messages of a step (slot 1 is empty); `div` / `Uadv` may be null tensors when only the layout of T0 is wanted
+// the messages of a step (slot 1: Jacobi only); for the layout alone any tensors with the B and C of `Uadv` / `div` will do
 void slab_messages(const SlabGeom& g, const tfl_sim_state* s, const tfl_tensor* Uadv, const tfl_tensor* div, Msg m[4]) {
   const int rr = 2 * g.R + 1;
   // U feeds pass A twice: as the trace velocity (window (R,R) reads it out to +-(R+1)) and as the ADVECTED field of the
@@ -608,9 +622,8 @@ struct SlabWs { float* msg; double* stats; float* compute; long long compute_flo
 
 // workspace = [message buffers][stats: 2*B doubles][compute region]
 long long slab_ws(const SlabGeom& g, const tfl_sim_state* s, float* ws, SlabWs* out) {
-  tfl_tensor u3 = *s->U, s1 = *s->flags;
   Msg m[4];
-  slab_messages(g, s, &u3, &s1, m);
+  slab_messages(g, s, s->U, s->flags, m);
   long long off = msg_layout(g, m, 4, nullptr);
   off = (off + 3) & ~3ll;
   const long long stats_off = off;
@@ -652,20 +665,6 @@ Win ext(const SlabGeom& g, int below, int above) {
   static const int widen = tfl::exp_env("TFL_SLAB_WIDEN") ? atoi(tfl::exp_env("TFL_SLAB_WIDEN")) : 0;   // development aid
   below += widen; above += widen; w.a = g.o0 - below < 0 ? 0 : g.o0 - below; w.b = g.o1 + above > g.Zl ? g.Zl : g.o1 + above; return w;
 }
-int set_win(tfl_ctx* c, Win w) { return tfl_set_z_window(c, w.a, w.b, 0, 0); }
-#define WIN(call) do { int wrc_ = (call); if (wrc_) return wrc_; } while (0)
-
-// boundary strips of the owned range (k planes next to each existing neighbour) and what is left between them
-struct Split { int a0, a1, b0, b1, i0, i1; bool has_strips, has_interior; };
-Split split_owned(const SlabGeom& g, int k) {
-  Split sp;
-  sp.a0 = g.o0; sp.a1 = g.lower ? std::min(g.o0 + k, g.o1) : g.o0;
-  sp.b1 = g.o1; sp.b0 = g.upper ? std::max(g.o1 - k, sp.a1) : g.o1;
-  sp.i0 = sp.a1; sp.i1 = sp.b0;
-  sp.has_strips = sp.a1 > sp.a0 || sp.b1 > sp.b0;
-  sp.has_interior = sp.i1 > sp.i0;
-  return sp;
-}
 
 struct StageGuard {          // whatever happens, leave the context with no window / stage mask / dx override
   tfl_ctx* c;
@@ -706,8 +705,22 @@ bool reach_violated(tfl_ctx* c, float dt, int R, char* msg, size_t msg_len) {
 void reach_mark(tfl_ctx* c) {      // at the end of a step whose projection published (eager, or behind the launch of a recorded step)
   c->reach_hist[0] = c->reach_hist[1]; c->reach_hist[1] = c->reach_issued;
 }
+// the first step of a run on this context (the host initialised in_flight to 0): the sticky maximum of whatever ran on the
+// context before must not speak for this run
+void reach_prime(tfl_ctx* c, tfl_slab* sl) {
+  c->h_reach[0] = 0.0f;
+  (void)hipMemsetAsync(c->d_reach, 0, sizeof(float), c->stream);
+  sl->in_flight |= kReachPrimed;
+}
 void reach_quiesce(tfl_ctx* c) {   // every publication enqueued so far has landed
   if (c->reach_issued) reach_wait(c, c->reach_issued);
+}
+
+// the U / p messages (T0, T1) an earlier eager step left in flight are finished (a failed one is not waited for again)
+int finish_in_flight(tfl_ctx* c, const SlabGeom& g, const tfl_comm* comm, const Msg* m, tfl_slab* sl) {
+  for (int t = 0; t < 2; t++)
+    if (sl->in_flight & (1 << t)) { const int rc = msg_finish(c, g, comm, m[t]); sl->in_flight &= ~(1 << t); if (rc) return rc; }
+  return TFL_OK;
 }
 
 }  // namespace
@@ -740,66 +753,122 @@ int tfl_slab_drain(tfl_ctx* c, const tfl_sim_state* s, tfl_slab* sl, const tfl_c
   if (rc) return rc;
   if (ws_floats < slab_ws(g, s, nullptr, nullptr)) return TFL_EINVAL;
   Msg m[4];
-  tfl_tensor u3 = *s->U, s1 = *s->flags;
-  slab_messages(g, s, &u3, &s1, m);
+  slab_messages(g, s, s->U, s->flags, m);
   msg_layout(g, m, 4, ws);
-  for (int t = 0; t < 2; t++)
-    if (sl->in_flight & (1 << t)) { rc = msg_finish(c, g, comm, m[t]); if (rc) return rc; sl->in_flight &= ~(1 << t); }
-  return TFL_OK;
+  return finish_in_flight(c, g, comm, m, sl);
 }
 
-int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state* s, tfl_slab* sl, const tfl_comm* comm,
-                           float* ws, int64_t ws_floats) {
-  if (!c || !prm || !s || !s->p || !s->U || !s->flags || !sl) return TFL_EINVAL;
-  auto bad = [&](const char* m) { c->err = std::string("simulate_step_slab: ") + m; return TFL_EUNSUPPORTED; };
+namespace {
+
+// One rank-step, phase by phase. The phases share the call's arguments, the slab's geometry, the workspace views and messages,
+// and what one phase hands to the next (which pairs pass B applied, where the velocity lives).
+struct SlabStep {
+  tfl_ctx* c; const tfl_sim_params* prm; const tfl_sim_state* s; tfl_slab* sl; const tfl_comm* comm;
+  float* ws; int64_t ws_floats;
+  SlabGeom g; SlabWs W; Msg m[4];
+  const char* method; AdvPlan ap;
+  bool multi, jac, ovl;                // a slab with neighbours; the Jacobi projection; boundary strips first (tfl_slab::overlap)
+  bool buoyant, vort, vfused;
+  const tfl_tensor* rho;               // density channel 0 (null without density)
+  // compute region: scalar temps [fwd N][fwdPos 3N][bwdPos 3N] | velocity temps [vfwd 3N][Uadv 3N]; the vorticity temps
+  // and the model workspace re-use the region once the advection is done (Uadv lives until addBuoyancy)
+  tfl_tensor fwd, fwdPos, bwdPos, vfwd, Uadv, curl, cnorm, div, Utmp;
+  bool rho_done = true, Uadv_done = true;  // pass B applied the setConstVals pair of density channel 0 / of the advected U
+  unsigned extra_done = 0;                 // ... of density channels 1.. (bit i)
+  bool paired = false;                 // both advections' passes run as pairs (advect_pair3.hip)
+  bool U_folded = false;               // the last force applied the U pair of the second setConstVals
+  const tfl_tensor* cur = nullptr;     // where the velocity of the step currently lives
+
+  int validate();                      // the refusals that come before anything is enqueued, then the views and messages
+  int gates();                         // reach checks (check_reach 1 / 2), the fp16 range gate, the previous step's U / p halos
+  int advect();                        // passes A, passes B under message T2, the first setConstVals
+  int forces();                        // buoyancy, gravity, confinement; Jacobi's setWallBcs, the second setConstVals
+  int project_jacobi();                // divergence under T3, the rounds of sweeps and p exchanges, velocity update
+  int project_net();                   // tfl_model_begin under T3, input statistics, the conv stages, the projection
+  int end_step();                      // the next step's U / p halos leave (message T0)
+
+  tfl_tensor view(float* base, int C) const { tfl_tensor t = *s->flags; t.data = base; t.C = C; return t; }
+  int stage(int mask, int below, int above) {      // stage mask `mask` on the planes (below, above) around the owned ones
+    (void)tfl_set_stages(c, mask);
+    const Win w = ext(g, below, above);
+    return tfl_set_z_window(c, w.a, w.b, 0, 0);
+  }
+  void no_stage() { (void)tfl_set_stages(c, 0); (void)tfl_set_z_window(c, 0, 0, 0, 0); }
+  int run_then_send(int mask, int k, const Msg& q, int (SlabStep::*op)());
+  int adv_scalar(const tfl_tensor* d, const tfl_tensor* dst) {
+    return tfl_advectScalar(c, prm->dt, d, s->U, s->flags, &fwd, &fwd, 1, method, &fwdPos, &bwdPos, 1, 0, prm->maccormackStrength, dst);
+  }
+  int adv_vel() { return tfl_advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vfwd, 1, method, 1, prm->maccormackStrength, &Uadv); }
+  int adv_pair(bool with_folds);
+  int pass_b();
+  int model_begin() { return tfl_model_begin(c, s->model, s->U, s->flags, s->U, W.compute, ws_floats - (W.compute - ws), g.o0, g.o1, W.stats); }
+};
+
+// `op` on the owned planes under stage mask `mask`, then message `q` starts. Overlapped: `op` on the boundary strips (k planes
+// next to each neighbour) first, then the message starts and `op` runs on the interior while it travels.
+int SlabStep::run_then_send(int mask, int k, const Msg& q, int (SlabStep::*op)()) {
+  const int a1 = g.lower ? std::min(g.o0 + k, g.o1) : g.o0, b0 = g.upper ? std::max(g.o1 - k, a1) : g.o1;   // strips [o0, a1), [b0, o1)
+  if (!ovl || (a1 == g.o0 && b0 == g.o1) || b0 == a1) {
+    TRY(stage(mask, 0, 0));
+    TRY((this->*op)());
+    return msg_start(c, g, comm, q);
+  }
+  (void)tfl_set_stages(c, mask);
+  TRY(tfl_set_z_window(c, g.o0, a1, b0, g.o1));
+  TRY((this->*op)());
+  TRY(msg_start(c, g, comm, q));
+  TRY(tfl_set_z_window(c, a1, b0, 0, 0));
+  return (this->*op)();
+}
+
+int SlabStep::validate() {
+  auto bad = [&](const char* why) { c->err = std::string("simulate_step_slab: ") + why; return TFL_EUNSUPPORTED; };
   if (tfl::model_is_graph(s->model)) return bad("banked, batch-norm and max-pool models run un-sharded only (tfl_simulate_step)");
-  SlabGeom g;
-  int rc = slab_geom(c, s, sl, &g);
-  if (rc) return rc;
-  const bool multi = g.lower || g.upper;
+  TRY(slab_geom(c, s, sl, &g));
+  multi = g.lower || g.upper;
   if (multi && (!comm || comm->size < (int32_t)(offsetof(tfl_comm, allreduce_sum) + sizeof(comm->allreduce_sum)) ||
                 !comm->exchange_start || !comm->exchange_wait || !comm->allreduce_sum)) {
     c->err = "simulate_step_slab: tfl_comm is null, has no size (ABI 3: size = sizeof(tfl_comm)) or lacks a required callback";
     return TFL_EINVAL;
   }
-  const Sizes z = sizes_of(s);
-  if (!z.is3d) return bad("2-D grids have no z to cut (run replicas)");
-  const char* method = (prm->advectionMethod && prm->advectionMethod[0]) ? prm->advectionMethod : "maccormackOurs";
-  const AdvPlan ap = adv_plan(method);
+  if (!sizes_of(s).is3d) return bad("2-D grids have no z to cut (run replicas)");
+  method = (prm->advectionMethod && prm->advectionMethod[0]) ? prm->advectionMethod : "maccormackOurs";
+  ap = adv_plan(method);
   if (!ap.known) { c->err = std::string("simulate_step_slab: unknown advection method '") + method + "'"; return TFL_EINVAL; }
   const std::string sm = method_of(prm);
   if (sm == "pcg")
     return bad("the PCG projection cannot be cut along z: its dot products need an all-reduce per iteration and its IC(0) "
                "preconditioner is a lexicographic wavefront over the whole grid (use simMethod 'jacobi' or 'convnet')");
-  const bool jac = sm == "jacobi";
+  jac = sm == "jacobi";
   if (jac && s->model) return bad("the Jacobi projection takes no model (state->model = NULL: the workspace layout follows it)");
   if (!jac && (sm != "convnet" || !s->model)) return bad("only the ConvNet projection (with a model) or 'jacobi' (without one)");
   if (jac && multi && g.o1 - g.o0 < g.J) return bad("Jacobi: the owned range is thinner than the halo depth it sends");
   if (!ws || ((uintptr_t)ws & 15) != 0 || ws_floats < slab_ws(g, s, nullptr, nullptr)) { c->err = "simulate_step_slab: workspace too small or misaligned"; return TFL_EINVAL; }
-  SlabWs W;
-  slab_ws(g, s, ws, &W);
-  StageGuard guard(c);
-  const int is3D = 1;
   const long long N = g.N;
+  slab_ws(g, s, ws, &W);
   float* cw = W.compute;
-  auto view = [&](float* base, int C) { tfl_tensor t = *s->flags; t.data = base; t.C = C; return t; };
-  // compute region: scalar temps [fwd N][fwdPos 3N][bwdPos 3N] | velocity temps [vfwd 3N][Uadv 3N]; the vorticity temps
-  // and the model workspace re-use the region once the advection is done (Uadv lives until addBuoyancy)
-  tfl_tensor fwd = view(cw, 1), fwdPos = view(cw + N, 3), bwdPos = view(cw + 4 * N, 3);
-  tfl_tensor vfwd = view(cw + 7 * N, 3), Uadv = view(cw + 10 * N, 3);
-  tfl_tensor curl = view(cw, 3), cnorm = view(cw + 3 * N, 1);
-  tfl_tensor div = view(jac ? cw : tfl_model_div(s->model, g.B, g.Zl, s->flags->Y, s->flags->X, cw), 1);
-  Msg m[4];
+  fwd = view(cw, 1); fwdPos = view(cw + N, 3); bwdPos = view(cw + 4 * N, 3); vfwd = view(cw + 7 * N, 3); Uadv = view(cw + 10 * N, 3);
+  curl = view(cw, 3); cnorm = view(cw + 3 * N, 1);
+  div = view(jac ? cw : tfl_model_div(s->model, g.B, g.Zl, s->flags->Y, s->flags->X, cw), 1);
+  Utmp = view(cw + 4 * N, 3);          // the scalar advection's bwdPos planes, dead once the advection is done
   slab_messages(g, s, &Uadv, &div, m);
   msg_layout(g, m, 4, W.msg);
+  ovl = sl->overlap && multi;
+  rho = s->n_density > 0 ? s->density[0] : nullptr;
+  buoyant = s->n_density > 0 && prm->buoyancyScale > 0.0;
+  // as tfl_simulate_step: the fused vorticity confinement delivers into U, so buoyancy / gravity work on a scratch velocity
+  vort = prm->vorticityConfinementAmp > 0.0;
+  vfused = vort && tfl::vorticity_confinement_fused_ok(true, g.Zl, s->flags->Y, s->flags->X);
+  return TFL_OK;
+}
 
+int SlabStep::gates() {
   // ---- reach check of the PREVIOUS step's velocity (no host sync: the word was copied back behind that step) ---------
   if (sl->check_reach == 1 && !c->capturing) {  // (a captured step: tfl_slab_graph_step makes both checks before it launches)
     char buf[256];
     if (reach_violated(c, prm->dt, g.R, buf, sizeof(buf))) {
       // the neighbours' matching receives of the U / p messages are already posted: finish ours before giving up
-      for (int t = 0; t < 2; t++)
-        if (multi && (sl->in_flight & (1 << t))) { (void)msg_finish(c, g, comm, m[t]); sl->in_flight &= ~(1 << t); }
+      if (multi) (void)finish_in_flight(c, g, comm, m, sl);
       c->err = buf;
       return TFL_EINVAL;
     }
@@ -807,23 +876,10 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   // The fp16 range gate of tfl_simulate_step -- only where refusing cannot strand a neighbour: a slab WITHOUT
   // neighbours, or (below) collectively under check_reach = 2. A rank that refused on its own word would leave the others
   // waiting for its halos; the host of a cut run polls tfl_model_range_flag / tfl_model_range_errors and stops every rank.
-  if (!c->capturing && !multi && s->model && tfl_model_range_flag(c, s->model) > 0) {
-    for (int t = 0; t < 2; t++)
-      if (multi && (sl->in_flight & (1 << t))) { (void)msg_finish(c, g, comm, m[t]); sl->in_flight &= ~(1 << t); }
-    c->err = "simulate_step_slab: an earlier step's ConvNet projection clamped activations at the fp16 range (a blown-up simulation); "
-             "read the count with tfl_model_range_errors, or create the model under TFL_CONV_PATH=winograd (strict fp32)";
-    return TFL_ERANGE;
-  }
-  InStep in_step(c);      // the range gate above is the step's only one
-  if (sl->in_flight & 1) { rc = msg_finish(c, g, comm, m[0]); if (rc) return rc; sl->in_flight &= ~1; }     // U and p halos
-  if (sl->check_reach == 1 && !(sl->in_flight & kReachPrimed)) {
-    // the first step of a run on this context (the host initialised in_flight to 0): the sticky maximum of whatever ran on the
-    // context before must not speak for this run
-    c->h_reach[0] = 0.0f;
-    (void)hipMemsetAsync(c->d_reach, 0, sizeof(float), c->stream);
-    sl->in_flight |= kReachPrimed;
-    c->reach_folded = false;               // the state this run starts from has been through no projection of ours
-  }
+  if (!c->capturing && !multi && s->model && tfl_model_range_flag(c, s->model) > 0) return range_refusal(c, "simulate_step_slab");
+  TRY(finish_in_flight(c, g, comm, m, sl));      // U and p halos
+  // (the state a run starts from has been through no projection of ours)
+  if (sl->check_reach == 1 && !(sl->in_flight & kReachPrimed)) { reach_prime(c, sl); c->reach_folded = false; }
   // mode 1, from the second step on: the projection kernel of the step before has folded max |u_z| of the planes it wrote -- this
   // rank's OWNED planes; the halo planes are their owners' to report -- into the sticky word (k_project_v4, reach_acc): no launch
   // of our own (round 6: k_absmax was 5-6 us of a 0.1 ms rank-step). Mode 2 needs THIS step's exact maximum and keeps it.
@@ -847,11 +903,8 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
     if (multi && comm->allreduce_sum(comm->user, d_flags, kReachFlags + (s->model ? 1 : 0)) != 0) { c->err = "simulate_step_slab: comm callback failed (allreduce_sum, reach)"; return TFL_EINVAL; }
     if (hipMemcpyAsync(c->h_reach_flags, d_flags, sizeof(double) * (kReachFlags + 1), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "simulate_step_slab: reading the reach flags failed"; (void)hipGetLastError(); return TFL_EHIP; }
-    if (c->h_reach_flags[kReachFlags] > 0.0) {      // some rank's conv stack left the fp16 range: EVERY rank refuses this step
-      c->err = "simulate_step_slab: an earlier step's ConvNet projection clamped activations at the fp16 range on some rank (a blown-up "
-               "simulation); read the counts with tfl_model_range_errors, or create the model under TFL_CONV_PATH=winograd (strict fp32)";
-      return TFL_ERANGE;
-    }
+    // some rank's conv stack left the fp16 range: EVERY rank refuses this step
+    if (c->h_reach_flags[kReachFlags] > 0.0) return range_refusal(c, "simulate_step_slab", true);
     int need = 1;
     for (int r = 0; r < kReachFlags; r++) if (c->h_reach_flags[r] > 0.0) need = r + 2;
     if (need > g.R) {
@@ -866,290 +919,238 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
     tfl::reach_publish(c->stream, c->d_reach, c->d_reach_host, c->d_reach_tick);
     c->reach_issued++;
   } else if (sl->check_reach) {
-    c->reach_sink = true;                  // the projection kernel of THIS step publishes the word (cleared by the guard below)
+    c->reach_sink = true;                  // the projection kernel of THIS step publishes the word (cleared by StageGuard)
   }
-  c->dx_dim = std::max(std::max(s->flags->X, s->flags->Y), sl->z_total);   // tfluids.getDx of the WHOLE grid
-  (void)tfl_set_z_origin(c, sl->z_first, sl->z_total);
-  const bool buoyant = s->n_density > 0 && prm->buoyancyScale > 0.0;
-  const tfl_tensor* rho = s->n_density > 0 ? s->density[0] : nullptr;
+  return TFL_OK;
+}
 
-  // ---- advection -------------------------------------------------------------------------------------------------
-  auto adv_scalar = [&]() { return tfl_advectScalar(c, prm->dt, rho, s->U, s->flags, &fwd, &fwd, is3D, method, &fwdPos, &bwdPos, 1, 0,
-                                                    prm->maccormackStrength, rho); };
-  auto adv_vel = [&]() { return tfl_advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vfwd, is3D, method, 1, prm->maccormackStrength, &Uadv); };
-  // pass B (the launches that write the advected fields) applies the pairs of the setConstVals that follows on the planes
-  // it writes -- the owned ones, which is what message T2 carries to the neighbours' halos (fold_ask / fold_took)
-  bool rho_done = true, Uadv_done = true;
-  unsigned extra_done = 0;            // density channels 1.. whose pair their pass B has applied
-  auto adv_scalar_b = [&]() { fold_ask(c, s->densityBC[0]); const int r = adv_scalar(); rho_done = fold_took(c) && rho_done; return r; };
-  auto adv_vel_b = [&]() { fold_ask(c, s->UBC); const int r = adv_vel(); Uadv_done = fold_took(c) && Uadv_done; return r; };
+// Round 6: the two advections' passes as PAIRS -- passes A in one launch, passes B in one launch (advect_pair3.hip; they are
+// independent here: the slab step does not fold the buoyancy force into pass B). TFL_EUNSUPPORTED = the shape is not the pair
+// kernels': the four launches as before.
+int SlabStep::adv_pair(bool with_folds) {
+  const tfl::BcFoldArg fs = with_folds ? fold_arg(s->densityBC[0]) : tfl::no_fold(), fv = with_folds ? fold_arg(s->UBC) : tfl::no_fold();
+  const int r = tfl::advect_pair(c, prm->dt, prm->maccormackStrength, rho, s->U, s->flags, &fwd, &fwdPos, rho, &vfwd, &Uadv, fs, fv);
+  if (r == TFL_OK && with_folds) { rho_done = rho_done && fs.dev != nullptr; Uadv_done = Uadv_done && fv.dev != nullptr; }
+  return r;
+}
+
+// the passes B of both operators on the current window (other methods: the velocity's). They apply the pairs of the
+// setConstVals that follows on the planes they write -- the owned ones, which is what message T2 carries to the neighbours'
+// halos (fold_ask / fold_took)
+int SlabStep::pass_b() {
+  if (ap.ours && paired) { const int r = adv_pair(true); if (r != TFL_EUNSUPPORTED) return r; paired = false; }
+  if (ap.ours && rho) {
+    fold_ask(c, s->densityBC[0]);
+    const int r = adv_scalar(rho, rho);
+    rho_done = fold_took(c) && rho_done;
+    if (r) return r;
+  }
+  fold_ask(c, s->UBC);
+  const int r = adv_vel();
+  Uadv_done = fold_took(c) && Uadv_done;
+  return r;
+}
+
+int SlabStep::advect() {
+  const int R = g.R;
   // (Round 6 measured the scalar advection on a second stream beside the velocity's -- they are independent, simulate.lua:183-200
   // -- and dropped it: an event hop between two streams costs 12-15 us of GPU-side latency on this stack
   // (tools/ubench/host_costs.hip), more than the overlap of two 8 us kernels returns; profiles/r06_slab_host_cost.txt.)
-  // Round 6: the two advections' passes as PAIRS -- passes A in one launch, passes B in one launch (advect_pair3.hip; they are
-  // independent here: the slab step does not fold the buoyancy force into pass B). false once = the shape is not the pair
-  // kernels': the four launches as before.
-  bool paired = ap.ours && rho != nullptr;
-  auto adv_pair = [&](bool with_folds) {
-    const tfl::BcFoldArg fs = with_folds ? fold_arg(s->densityBC[0]) : tfl::no_fold(), fv = with_folds ? fold_arg(s->UBC) : tfl::no_fold();
-    const int r = tfl::advect_pair(c, prm->dt, prm->maccormackStrength, rho, s->U, s->flags, &fwd, &fwdPos, rho, &vfwd, &Uadv, fs, fv);
-    if (r == TFL_OK && with_folds) { rho_done = rho_done && fs.dev != nullptr; Uadv_done = Uadv_done && fv.dev != nullptr; }
-    return r;
-  };
+  paired = ap.ours && rho != nullptr;
   if (ap.ours) {
     // density channels 1.. (RGB): each one complete -- min/max (2R, 2R), pass A (R, R), pass B (0, 0) in place -- before channel 0
     // and the velocity, so that the pair kernels below run as with one channel and T2 finds every channel's owned planes written
     for (int i = 1; i < s->n_density; i++) {
       const tfl_tensor* di = s->density[i];
-      auto adv_i = [&]() { return tfl_advectScalar(c, prm->dt, di, s->U, s->flags, &fwd, &fwd, is3D, method, &fwdPos, &bwdPos, 1, 0,
-                                                   prm->maccormackStrength, di); };
-      (void)tfl_set_stages(c, 1); WIN(set_win(c, ext(g, 2 * g.R, 2 * g.R))); rc = adv_i(); if (rc) return rc;
-      (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, g.R, g.R))); rc = adv_i(); if (rc) return rc;
-      (void)tfl_set_stages(c, 4); WIN(set_win(c, ext(g, 0, 0)));
+      TRY(stage(1, 2 * R, 2 * R)); TRY(adv_scalar(di, di));
+      TRY(stage(2, R, R)); TRY(adv_scalar(di, di));
+      TRY(stage(4, 0, 0));
       fold_ask(c, s->densityBC[i]);
-      rc = adv_i();
+      const int rc = adv_scalar(di, di);
       if (fold_took(c)) extra_done |= 1u << i;
       if (rc) return rc;
     }
-    if (rho && !paired) {
-      (void)tfl_set_stages(c, 1); WIN(set_win(c, ext(g, 2 * g.R, 2 * g.R)));
-      rc = adv_scalar(); if (rc) return rc;
-    }
-    (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, g.R, g.R)));
-    if (paired) {
-      rc = adv_pair(false);
-      if (rc == TFL_EUNSUPPORTED) {
-        paired = false;
-        (void)tfl_set_stages(c, 1); WIN(set_win(c, ext(g, 2 * g.R, 2 * g.R)));
-        rc = adv_scalar(); if (rc) return rc;
-        (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, g.R, g.R)));
-      } else if (rc) return rc;
-    }
+    TRY(stage(2, R, R));
+    const int rc = paired ? adv_pair(false) : TFL_OK;
+    if (rc == TFL_EUNSUPPORTED) {
+      paired = false;
+      TRY(stage(1, 2 * R, 2 * R)); TRY(adv_scalar(rho, rho));
+      TRY(stage(2, R, R));
+    } else if (rc) return rc;
     if (!paired) {
-      if (rho) { rc = adv_scalar(); if (rc) return rc; }
-      rc = adv_vel(); if (rc) return rc;
+      if (rho) TRY(adv_scalar(rho, rho));
+      TRY(adv_vel());
     }
   } else {
     // every other method: the generic gather kernels (and the LDS-tiled single pass of eulerOurs) under the windows of the
     // cones -- a two-pass method's pass A on (R, R), the pass that writes on (0, 0). Those kernels cannot advect in place:
     // each density channel goes to `sout` (the fwdPos planes, which only maccormackOurs uses) and its owned planes are copied
     // back before T2 leaves. Its setConstVals pair is left to the launch after T2 (on every plane: halos arrive unpaired).
-    tfl_tensor sout = view(cw + N, 1);
+    tfl_tensor sout = view(W.compute + g.N, 1);
     for (int i = 0; i < s->n_density; i++) {
       const tfl_tensor* di = s->density[i];
-      auto adv_i = [&]() { return tfl_advectScalar(c, prm->dt, di, s->U, s->flags, &fwd, &fwd, is3D, method, &fwdPos, &bwdPos, 1, 0,
-                                                   prm->maccormackStrength, &sout); };
-      if (ap.scalar2) { (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, g.R, g.R))); rc = adv_i(); if (rc) return rc; }
-      (void)tfl_set_stages(c, ap.scalar2 ? 4 : 2); WIN(set_win(c, ext(g, 0, 0)));
-      rc = adv_i(); if (rc) return rc;
-      rc = copy_owned(c, g, di, &sout); if (rc) return rc;
+      if (ap.scalar2) { TRY(stage(2, R, R)); TRY(adv_scalar(di, &sout)); }
+      TRY(stage(ap.scalar2 ? 4 : 2, 0, 0)); TRY(adv_scalar(di, &sout));
+      TRY(copy_owned(c, g, di, &sout));
     }
     rho_done = false;
-    if (ap.vel2) { (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, g.R, g.R))); rc = adv_vel(); if (rc) return rc; }
+    if (ap.vel2) { TRY(stage(2, R, R)); TRY(adv_vel()); }
   }
-  (void)tfl_set_stages(c, ap.vel2 ? 4 : 2);    // the velocity's pass that writes the owned planes (single-pass methods: stage 2)
-  const int strip = 4 > 2 * g.R + 1 ? 4 : 2 * g.R + 1;        // deepest plane count message T2 sends
-  const Split spB = split_owned(g, strip);
-  const bool ovl = sl->overlap && multi;
-  auto pass_b = [&]() -> int {      // the passes B of both operators on the current window (other methods: the velocity's)
-    if (!ap.ours) return adv_vel_b();
-    if (paired) { const int r = adv_pair(true); if (r != TFL_EUNSUPPORTED) return r; paired = false; }
-    if (rho) { const int r = adv_scalar_b(); if (r) return r; }
-    return adv_vel_b();
-  };
-  if (ovl && spB.has_strips && spB.has_interior) {
-    WIN(tfl_set_z_window(c, spB.a0, spB.a1, spB.b0, spB.b1));
-    rc = pass_b(); if (rc) return rc;
-    rc = msg_start(c, g, comm, m[2]); if (rc) return rc;
-    WIN(tfl_set_z_window(c, spB.i0, spB.i1, 0, 0));
-    rc = pass_b(); if (rc) return rc;
-  } else {
-    WIN(set_win(c, ext(g, 0, 0)));
-    rc = pass_b(); if (rc) return rc;
-    rc = msg_start(c, g, comm, m[2]); if (rc) return rc;
-  }
-  rc = msg_finish(c, g, comm, m[2]); if (rc) return rc;
-  (void)tfl_set_stages(c, 0); (void)tfl_set_z_window(c, 0, 0, 0, 0);
-  // as tfl_simulate_step: the fused vorticity confinement delivers into U, so buoyancy / gravity work on a scratch velocity
-  const bool vort = prm->vorticityConfinementAmp > 0.0;
-  const bool vfused = vort && tfl::vorticity_confinement_fused_ok(true, g.Zl, s->flags->Y, s->flags->X);
-  tfl_tensor Utmp = view(cw + 4 * N, 3);                   // the scalar advection's bwdPos planes, dead by now
-  const tfl_tensor* cur = &Uadv;
-  if (!buoyant && !vfused) { rc = tfl_copy(c, s->U, &Uadv); if (rc) return rc; cur = s->U; }
-  rc = set_const_vals(c, s, cur, !Uadv_done, Unchanged{false, false, false}, ((rho && rho_done) ? 1u : 0u) | extra_done);
-  if (rc) return rc;
+  // the velocity's pass that writes the owned planes (single-pass methods: stage 2); strips as deep as message T2 sends
+  TRY(run_then_send(ap.vel2 ? 4 : 2, std::max(4, 2 * R + 1), m[2], &SlabStep::pass_b));
+  TRY(msg_finish(c, g, comm, m[2]));
+  no_stage();
+  cur = &Uadv;
+  if (!buoyant && !vfused) { TRY(tfl_copy(c, s->U, &Uadv)); cur = s->U; }
+  return set_const_vals(c, s, cur, !Uadv_done, Unchanged{false, false, false}, ((rho && rho_done) ? 1u : 0u) | extra_done);
+}
 
-  // ---- forces --------------------------------------------------------------------------------------------------------
+int SlabStep::forces() {
   const double dx = tfl_getDx(c, s->flags);
-  WIN(set_win(c, ext(g, 3, 4)));
+  TRY(stage(0, 3, 4));
   // as tfl_simulate_step: the last force's kernel applies the U pair of the setConstVals that follows, on the planes it writes
   // (they include every plane the projection reads: (0, 1)); the launch below then skips U. Not before the Jacobi projection:
   // its setWallBcs comes between the last force and the pair (as in tfl_simulate_step)
   const bool fold_forces = !prm->outputDiv && !jac;
   const bool gravity_on = prm->gravityScale > 0.0;
-  bool U_folded = false;
+  float gv[3];
   if (buoyant) {
-    const float sc = (float)(-(dx / 4.0) * prm->buoyancyScale);
-    const float gv[3] = {prm->gravity[0] * sc, prm->gravity[1] * sc, prm->gravity[2] * sc};
+    scaled_gravity(prm, dx, prm->buoyancyScale, gv);
     const tfl_tensor* dst = vfused ? &Utmp : s->U;
     const bool last = fold_forces && !gravity_on && !vort;
     if (last) fold_ask(c, s->UBC);
-    rc = tfl_addBuoyancyFrom(c, cur, dst, s->flags, rho, gv, prm->dt, is3D);
+    const int rc = tfl_addBuoyancyFrom(c, cur, dst, s->flags, rho, gv, prm->dt, 1);
     if (last) U_folded = fold_took(c);
     if (rc) return rc;
     cur = dst;
   }
   if (gravity_on) {
-    const float sc = (float)((-dx / 4.0) * prm->gravityScale);
-    const float gv[3] = {prm->gravity[0] * sc, prm->gravity[1] * sc, prm->gravity[2] * sc};
-    rc = tfl_addGravity(c, cur, s->flags, gv, prm->dt, is3D, nullptr); if (rc) return rc;
+    scaled_gravity(prm, dx, prm->gravityScale, gv);
+    TRY(tfl_addGravity(c, cur, s->flags, gv, prm->dt, 1, nullptr));
   }
   if (vort) {
+    // fused: one launch, curl (2,2) and |curl| live in LDS, the planes (0,1) of U are written (inputs: planes (3,3) of `cur`);
+    // otherwise curl on (2, 2), then the force on (0, 1)
     const float strength = (float)(dx * prm->vorticityConfinementAmp);
-    if (vfused) {
-      // one launch: curl (2,2) and |curl| live in LDS, the planes (0,1) of U are written (inputs: planes (3,3) of `cur`)
-      (void)tfl_set_stages(c, 0); WIN(set_win(c, ext(g, 0, 1)));
-      if (fold_forces) fold_ask(c, s->UBC);
-      rc = tfl_vorticityConfinementFrom(c, cur, s->U, s->flags, strength, &curl, &cnorm, is3D);
-      if (fold_forces) U_folded = fold_took(c);
-      if (rc) return rc;
-    } else {
-      (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, 2, 2)));
-      rc = tfl_vorticityConfinement(c, s->U, s->flags, strength, &curl, &curl, &cnorm, &curl, is3D); if (rc) return rc;
-      (void)tfl_set_stages(c, 4); WIN(set_win(c, ext(g, 0, 1)));
-      if (fold_forces) fold_ask(c, s->UBC);
-      rc = tfl_vorticityConfinement(c, s->U, s->flags, strength, &curl, &curl, &cnorm, &curl, is3D);
-      if (fold_forces) U_folded = fold_took(c);
-      if (rc) return rc;
-    }
+    if (!vfused) { TRY(stage(2, 2, 2)); TRY(tfl_vorticityConfinement(c, s->U, s->flags, strength, &curl, &curl, &cnorm, &curl, 1)); }
+    TRY(stage(vfused ? 0 : 4, 0, 1));
+    if (fold_forces) fold_ask(c, s->UBC);
+    const int rc = vfused ? tfl_vorticityConfinementFrom(c, cur, s->U, s->flags, strength, &curl, &cnorm, 1)
+                          : tfl_vorticityConfinement(c, s->U, s->flags, strength, &curl, &curl, &cnorm, &curl, 1);
+    if (fold_forces) U_folded = fold_took(c);
+    if (rc) return rc;
   }
-  (void)tfl_set_stages(c, 0); (void)tfl_set_z_window(c, 0, 0, 0, 0);
+  no_stage();
   if (prm->outputDiv) return TFL_OK;
-  const int Y = s->flags->Y, X = s->flags->X;
   if (jac) {
     const Win w = ext(g, 0, 1);            // what the divergence reads
-    tfl::set_wall_bcs_planes(c->stream, g.B, g.Zl, Y, X, w.a, w.b, s->U->data, s->flags->data);
+    tfl::set_wall_bcs_planes(c->stream, g.B, g.Zl, s->flags->Y, s->flags->X, w.a, w.b, s->U->data, s->flags->data);
   }
-  rc = set_const_vals(c, s, s->U, !U_folded, Unchanged{true, false, true});
-  if (rc) return rc;
+  return set_const_vals(c, s, s->U, !U_folded, Unchanged{true, false, true});
+}
 
-  // the end of every step: the next step's U and p halos leave now; they are consumed at its start / before its first conv layer
-  auto end_step = [&]() -> int {
-    if (sl->check_reach == 1 && !c->capturing) reach_mark(c);      // behind the kernel that published this step's reach word
-    if (multi) {
-      int r = msg_start(c, g, comm, m[0]); if (r) return r;
-      if (c->capturing) {
-        // a captured step must end with every stream joined: the message is finished here instead of by the next call (nothing
-        // of the next step could have run beside it anyway -- its first kernels read these halos)
-        r = msg_finish(c, g, comm, m[0]); if (r) return r;
-      } else {
-        sl->in_flight |= 1;
-      }
-    }
-    return TFL_OK;
-  };
-
-  if (jac) {
-    // ---- Jacobi projection (window schedule: the bookkeeping comment above) ---------------------------------------------
-    tfl::velocity_divergence_planes(c->stream, g.B, g.Zl, Y, X, g.o0, g.o1, s->U->data, s->flags->data, div.data);
-    rc = msg_start(c, g, comm, m[3]); if (rc) return rc;
-    rc = msg_finish(c, g, comm, m[3]); if (rc) return rc;
-    const int M = prm->maxIter > 0 ? prm->maxIter : 100;
-    tfl_tensor pPrev = view(cw + N, 1);
-    const tfl_tensor* buf[2] = {s->p, &pPrev};
-    int cur = M & 1;                       // p^0's buffer, so that p^M lands in s->p
-    if (hipMemsetAsync(buf[cur]->data, 0, sizeof(float) * (size_t)N, c->stream) != hipSuccess) {
-      (void)hipGetLastError(); c->err = "simulate_step_slab: hipMemsetAsync failed"; return TFL_EHIP;
-    }
-    auto exchange_p = [&]() -> int {
-      Msg q = m[1];
-      q.f[0].t = buf[cur];
-      int r = msg_start(c, g, comm, q); if (r) return r;
-      return msg_finish(c, g, comm, q);
-    };
-    const int J = multi ? g.J : M + 1;     // (no neighbour: one round, windows clipped to the array)
-    int d = J;                             // p is valid on (d, d)
-    for (int n = 0; n < M; n++) {
-      if (d == 0) { rc = exchange_p(); if (rc) return rc; d = J; }
-      const int left = M - n;              // sweeps still to run, this one included
-      const bool last_round = left < d;    // no exchange follows: end at (1, 0)
-      const int r = std::min(d, left) - 1; // sweeps of this round after this one
-      const Win w = ext(g, std::min(d - 1, r + (last_round ? 1 : 0)), std::min(d - 1, r));
-      tfl::jacobi_sweep_slab(c->stream, g.B, g.Zl, Y, X, sl->z_first, sl->z_total, w.a, w.b, buf[cur]->data, s->flags->data,
-                             div.data, buf[cur ^ 1]->data);
-      cur ^= 1; d--;
-    }
-    if (d == 0) { rc = exchange_p(); if (rc) return rc; }
-    tfl::velocity_update_planes(c->stream, g.B, g.Zl, Y, X, g.o0, g.o1, s->U->data, s->flags->data, s->p->data);
-    if (hipPeekAtLastError() != hipSuccess) { c->err = std::string("simulate_step_slab: ") + hipGetErrorString(hipGetLastError()); return TFL_EHIP; }
-    rc = set_const_vals(c, s, s->U, true, Unchanged{false, false, true});
-    if (rc) return rc;
-    rc = tfl_applyBCs(c, s->U, nullptr, nullptr, 1, -1e6f, 1e6f);
-    if (rc) return rc;
-    return end_step();
+// (window schedule: the bookkeeping comment above)
+int SlabStep::project_jacobi() {
+  const int Y = s->flags->Y, X = s->flags->X;
+  tfl::velocity_divergence_planes(c->stream, g.B, g.Zl, Y, X, g.o0, g.o1, s->U->data, s->flags->data, div.data);
+  TRY(msg_start(c, g, comm, m[3]));
+  TRY(msg_finish(c, g, comm, m[3]));
+  const int M = prm->maxIter > 0 ? prm->maxIter : 100;
+  tfl_tensor pPrev = view(W.compute + g.N, 1);
+  const tfl_tensor* buf[2] = {s->p, &pPrev};
+  int in = M & 1;                        // p^0's buffer, so that p^M lands in s->p
+  if (hipMemsetAsync(buf[in]->data, 0, sizeof(float) * (size_t)g.N, c->stream) != hipSuccess) {
+    (void)hipGetLastError(); c->err = "simulate_step_slab: hipMemsetAsync failed"; return TFL_EHIP;
   }
-
-  // ---- projection ----------------------------------------------------------------------------------------------------
-  const long long mws = ws_floats - (cw - ws);
-  (void)tfl_set_stages(c, 2);
-  const Split spD = split_owned(g, g.gen ? std::max(g.cone.in_lo, g.cone.in_hi) : 4);     // (the planes message T3 sends)
-  if (ovl && spD.has_strips && spD.has_interior) {
-    WIN(tfl_set_z_window(c, spD.a0, spD.a1, spD.b0, spD.b1));
-    rc = tfl_model_begin(c, s->model, s->U, s->flags, s->U, cw, mws, g.o0, g.o1, W.stats); if (rc) return rc;
-    rc = msg_start(c, g, comm, m[3]); if (rc) return rc;
-    WIN(tfl_set_z_window(c, spD.i0, spD.i1, 0, 0));
-    rc = tfl_model_begin(c, s->model, s->U, s->flags, s->U, cw, mws, g.o0, g.o1, W.stats); if (rc) return rc;
-  } else {
-    WIN(set_win(c, ext(g, 0, 0)));
-    rc = tfl_model_begin(c, s->model, s->U, s->flags, s->U, cw, mws, g.o0, g.o1, W.stats); if (rc) return rc;
-    rc = msg_start(c, g, comm, m[3]); if (rc) return rc;
+  auto exchange_p = [&]() -> int { Msg q = m[1]; q.f[0].t = buf[in]; TRY(msg_start(c, g, comm, q)); return msg_finish(c, g, comm, q); };
+  const int J = multi ? g.J : M + 1;     // (no neighbour: one round, windows clipped to the array)
+  int d = J;                             // p is valid on (d, d)
+  for (int n = 0; n < M; n++) {
+    if (d == 0) { TRY(exchange_p()); d = J; }
+    const int left = M - n;              // sweeps still to run, this one included
+    const bool last_round = left < d;    // no exchange follows: end at (1, 0)
+    const int r = std::min(d, left) - 1; // sweeps of this round after this one
+    const Win w = ext(g, std::min(d - 1, r + (last_round ? 1 : 0)), std::min(d - 1, r));
+    tfl::jacobi_sweep_slab(c->stream, g.B, g.Zl, Y, X, sl->z_first, sl->z_total, w.a, w.b, buf[in]->data, s->flags->data,
+                           div.data, buf[in ^ 1]->data);
+    in ^= 1; d--;
   }
+  if (d == 0) TRY(exchange_p());
+  tfl::velocity_update_planes(c->stream, g.B, g.Zl, Y, X, g.o0, g.o1, s->U->data, s->flags->data, s->p->data);
+  if (hipPeekAtLastError() != hipSuccess) { c->err = std::string("simulate_step_slab: ") + hipGetErrorString(hipGetLastError()); return TFL_EHIP; }
+  TRY(set_const_vals(c, s, s->U, true, Unchanged{false, false, true}));
+  return tfl_applyBCs(c, s->U, nullptr, nullptr, 1, -1e6f, 1e6f);
+}
+
+int SlabStep::project_net() {
+  TRY(run_then_send(2, g.gen ? std::max(g.cone.in_lo, g.cone.in_hi) : 4, m[3], &SlabStep::model_begin));  // (strips: what T3 sends)
   double count = 3.0 * (double)sl->z_total * (double)g.yx;
   if (g.cone.norm == 0) {        // std(UDiv): tfl_model_begin's partial sums over the owned planes
     (void)tfl_set_stages(c, 4);
-    rc = tfl_model_begin(c, s->model, s->U, s->flags, s->U, cw, mws, g.o0, g.o1, W.stats); if (rc) return rc;
+    TRY(model_begin());
   } else {                       // another field / the l2 norm / none: the same over the owned planes
     tfl::model_slab_stats(c->stream, s->model, g.B, g.Zl, g.yx, g.o0, g.o1, sl->z_total, s->p->data, s->U->data, div.data, W.stats, &count);
   }
   // (no input scale: every rank holds (0, 1) already -- a sum would make it (0, world))
   if (multi && g.cone.norm != 2 && comm->allreduce_sum(comm->user, W.stats, 2ll * g.B) != 0) { c->err = "simulate_step_slab: comm callback failed (allreduce_sum)"; return TFL_EINVAL; }
-  const bool late_ubc = s->UBC && s->UBC->sparse && s->UBC->idem;
-  const tfl_tensor* ubc = (s->UBC && !late_ubc) ? &s->UBC->bc : nullptr;
-  const tfl_tensor* umask = (s->UBC && !late_ubc) ? &s->UBC->inv : nullptr;
-  auto finish = [&]() { return tfl_model_finish(c, s->model, s->p, s->flags, s->p, s->U, cw, mws, W.stats, count, ubc, umask, 1, -1e6f, 1e6f); };
+  const LateUbc lu = late_ubc_of(s);
+  auto finish = [&]() { return tfl_model_finish(c, s->model, s->p, s->flags, s->p, s->U, W.compute, ws_floats - (W.compute - ws), W.stats, count,
+                                                lu.bc, lu.mask, 1, -1e6f, 1e6f); };
   (void)tfl_set_stages(c, 1);
   const Win w1 = ext(g, 3, 2);
   if (g.gen) {
     // every other net: the whole shape-generic forward as stage 1, each launch on its layer's cone of the owned planes (the
     // window names the owned planes; tfl_model_finish widens it layer by layer)
-    rc = msg_finish(c, g, comm, m[3]); if (rc) return rc;
-    WIN(set_win(c, ext(g, 0, 0)));
-    rc = finish(); if (rc) return rc;
+    TRY(msg_finish(c, g, comm, m[3])); TRY(stage(1, 0, 0)); TRY(finish());
   } else if (ovl && g.o1 - 1 > g.o0 + 1) {
     // interior of conv 1 needs only owned planes of div / p: it runs while the div halos travel
-    WIN(tfl_set_z_window(c, g.lower ? g.o0 + 1 : w1.a, g.upper ? g.o1 - 1 : w1.b, 0, 0));
-    rc = finish(); if (rc) return rc;
-    rc = msg_finish(c, g, comm, m[3]); if (rc) return rc;
-    WIN(tfl_set_z_window(c, g.lower ? w1.a : 0, g.lower ? g.o0 + 1 : 0, g.upper ? g.o1 - 1 : 0, g.upper ? w1.b : 0));
-    rc = finish(); if (rc) return rc;
+    TRY(tfl_set_z_window(c, g.lower ? g.o0 + 1 : w1.a, g.upper ? g.o1 - 1 : w1.b, 0, 0));
+    TRY(finish());
+    TRY(msg_finish(c, g, comm, m[3]));
+    TRY(tfl_set_z_window(c, g.lower ? w1.a : 0, g.lower ? g.o0 + 1 : 0, g.upper ? g.o1 - 1 : 0, g.upper ? w1.b : 0));
+    TRY(finish());
   } else {
-    rc = msg_finish(c, g, comm, m[3]); if (rc) return rc;
-    WIN(set_win(c, w1));
-    rc = finish(); if (rc) return rc;
+    TRY(msg_finish(c, g, comm, m[3])); TRY(stage(1, 3, 2)); TRY(finish());
   }
-  if (!g.gen) {
-    (void)tfl_set_stages(c, 2); WIN(set_win(c, ext(g, 2, 1))); rc = finish(); if (rc) return rc;
-    (void)tfl_set_stages(c, 4); WIN(set_win(c, ext(g, 1, 0))); rc = finish(); if (rc) return rc;
-  }
-  (void)tfl_set_stages(c, 8); WIN(set_win(c, ext(g, 0, 0)));
-  if (late_ubc) fold_ask(c, s->UBC);          // the projection kernel applies the sparse U pair itself (owned planes: what T0 sends)
-  rc = finish();
+  if (!g.gen) { TRY(stage(2, 2, 1)); TRY(finish()); TRY(stage(4, 1, 0)); TRY(finish()); }
+  TRY(stage(8, 0, 0));
+  if (lu.late) fold_ask(c, s->UBC);          // the projection kernel applies the sparse U pair itself (owned planes: what T0 sends)
+  const int rc = finish();
   const bool U_late_folded = fold_took(c);
   if (rc) return rc;
-  (void)tfl_set_stages(c, 0); (void)tfl_set_z_window(c, 0, 0, 0, 0);
-  rc = set_const_vals(c, s, s->U, late_ubc && !U_late_folded, Unchanged{false, false, true});
-  if (rc) return rc;
-  return end_step();
+  no_stage();
+  return set_const_vals(c, s, s->U, lu.late && !U_late_folded, Unchanged{false, false, true});
+}
+
+// the end of every step: the next step's U and p halos leave now; they are consumed at its start / before its first conv layer
+int SlabStep::end_step() {
+  if (sl->check_reach == 1 && !c->capturing) reach_mark(c);      // behind the kernel that published this step's reach word
+  if (!multi) return TFL_OK;
+  TRY(msg_start(c, g, comm, m[0]));
+  // a captured step must end with every stream joined: the message is finished here instead of by the next call (nothing
+  // of the next step could have run beside it anyway -- its first kernels read these halos)
+  if (c->capturing) return msg_finish(c, g, comm, m[0]);
+  sl->in_flight |= 1;
+  return TFL_OK;
+}
+
+}  // namespace
+
+int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state* s, tfl_slab* sl, const tfl_comm* comm,
+                           float* ws, int64_t ws_floats) {
+  if (!c || !prm || !s || !s->p || !s->U || !s->flags || !sl) return TFL_EINVAL;
+  SlabStep S{c, prm, s, sl, comm, ws, ws_floats};
+  TRY(S.validate());
+  StageGuard guard(c);
+  TRY(S.gates());
+  InStep in_step(c);      // the gates above are the step's only refusals: nothing below refuses half-way through
+  c->dx_dim = std::max(std::max(s->flags->X, s->flags->Y), sl->z_total);   // tfluids.getDx of the WHOLE grid
+  (void)tfl_set_z_origin(c, sl->z_first, sl->z_total);
+  TRY(S.advect());
+  TRY(S.forces());
+  if (prm->outputDiv) return TFL_OK;
+  TRY(S.jac ? S.project_jacobi() : S.project_net());
+  return S.end_step();
 }
 
 int32_t tfl_slab_needed_reach(const tfl_ctx* c) { return c ? c->needed_reach : 0; }
@@ -1232,12 +1233,8 @@ tfl_slab_graph* tfl_slab_graph_create(tfl_ctx* c, const tfl_sim_params* prm, con
   if (sl->check_reach == 2) { c->err = "slab_graph_create: check_reach = 2 synchronises with the host every step: step eagerly"; return nullptr; }
   // the U / p message the last eager step left in flight is consumed now: a captured step starts and ends with none
   if ((sl->in_flight & 0xF) && tfl_slab_drain(c, s, sl, comm, ws, ws_floats) != TFL_OK) return nullptr;
-  if (sl->check_reach == 1 && !(sl->in_flight & kReachPrimed)) {
-    // (a host that records before its first eager step: the reset of the sticky reach word must not become a node of the graph)
-    c->h_reach[0] = 0.0f;
-    (void)hipMemsetAsync(c->d_reach, 0, sizeof(float), c->stream);
-    sl->in_flight |= kReachPrimed;
-  }
+  // (a host that records before its first eager step: the reset of the sticky reach word must not become a node of the graph)
+  if (sl->check_reach == 1 && !(sl->in_flight & kReachPrimed)) reach_prime(c, sl);
   tfl_slab_graph* G = new tfl_slab_graph();
   G->prm = prm; G->s = s; G->sl = sl; G->reach = g.R; G->multi = multi;
   if (hipStreamCreateWithFlags(&G->cap, hipStreamNonBlocking) != hipSuccess) { c->err = "slab_graph_create: hipStreamCreate failed"; delete G; return nullptr; }
@@ -1281,11 +1278,8 @@ int tfl_slab_graph_step(tfl_ctx* c, tfl_slab_graph* G) {
     char buf[256];
     if (reach_violated(c, G->prm->dt, G->reach, buf, sizeof(buf))) { c->err = buf; return TFL_EINVAL; }
   }
-  if (!G->multi && G->s->model && tfl_model_range_flag(c, G->s->model) > 0) {     // (a slab with neighbours never refuses on its own word: see the eager step)
-    c->err = "simulate_step_slab: an earlier step's ConvNet projection clamped activations at the fp16 range (a blown-up simulation); "
-             "read the count with tfl_model_range_errors, or create the model under TFL_CONV_PATH=winograd (strict fp32)";
-    return TFL_ERANGE;
-  }
+  // (a slab with neighbours never refuses on its own word: see the eager step)
+  if (!G->multi && G->s->model && tfl_model_range_flag(c, G->s->model) > 0) return range_refusal(c, "simulate_step_slab");
   if (hipGraphLaunch(G->exec, c->stream) != hipSuccess) { c->err = "slab_graph_step: hipGraphLaunch failed"; (void)hipGetLastError(); return TFL_EHIP; }
   if (G->sl->check_reach) { c->reach_issued += G->reach_pubs; reach_mark(c); }
   return TFL_OK;
