@@ -25,36 +25,44 @@ struct tfl_layer {
   int up = 1;          // 2: {Spatial,Volumetric}ConvolutionUpsample -- up^dim sub-position convolutions, pixel-shuffled
   float* w = nullptr;  // device, [sub][tap][cin][cout]
   float* b = nullptr;  // device, [sub][cout]
-  // tfl_model_create_graph only
-  int dil = 1;         // dilation (banksType 'dilate': 2^(bank - 1))
   int stage = 0;       // 1-based stage of lib/model.lua's layer tables
   int bank = 0;        // 0-based bank (0 outside [banksSplitStage, banksJoinStage))
+  // graph models only
+  int dil = 1;         // dilation (banksType 'dilate': 2^(bank - 1))
   float* bn = nullptr; // device, the folded batch norm after this module: scale[cout] then shift[cout]
 };
+// The forward a model runs (tfl_model_finish dispatches on it), named after its kernel file; TFL_CONV_PATH at creation picks
+// it for the 3-D `default` topology (3->8 k3, 8->8 k3, 8->8 k3, 8->8 k1, 8->1 k1), and "direct" = generic for both defaults.
+enum class ConvPath {
+  conv_mfma16,   // 3-D default: split-operand fp16 MFMA (conv_mfma16.hip), TFL_CONV_PATH unset or "mfma16"
+  conv_valu,     // 3-D default: fp32 Winograd on the vector ALUs (conv_valu.hip), "winograd" and any unrecognised value
+  conv_mfma,     // 3-D default: fp32-operand MFMA (conv_mfma.hip), "mfma"
+  conv2d_mfma,   // 2-D default topology (3->16, 16->16 x3 k3, 16->1 k1): conv2d_mfma.hip
+  generic,       // everything else that is not a graph model: the shape-generic kernels (conv.hip), layer by layer
+  graph,         // tfl_model_create_graph: banks / batch norm / max pooling (graph_forward)
+};
+static bool default3(ConvPath p) { return p == ConvPath::conv_mfma16 || p == ConvPath::conv_valu || p == ConvPath::conv_mfma; }
 struct tfl_model {
   bool is3d = false;
   int max_c = 0;
   bool multires = false;   // some layer pools / upsamples (the `tog` topologies)
   int max_down = 1;        // coarsest activation resolution = grid / max_down
   std::vector<tfl_layer> layers;
-  // 3-D `default` topology (3->8 k3, 8->8 k3, 8->8 k3, 8->8 k1, 8->1 k1): MFMA path (conv_mfma.hip)
-  bool mfma3d = false;
-  bool valu3d = false;                            // the same three layers on the vector ALUs (conv_valu.hip): the default
+  ConvPath path = ConvPath::generic;
+  // 3-D `default` topology: the weights of its three forms (pack_default3)
   float* bfrag[3] = {nullptr, nullptr, nullptr};  // per-lane B fragments of the three k=3 layers
   float* wino[3] = {nullptr, nullptr, nullptr};   // F(2,3)-in-x transformed weights of the same layers, [dz][dy][cin][4][8]
   float* tail_w4 = nullptr;                       // [8][8] (out, in) of the 8->8 k1 layer
   float* tail_w5 = nullptr;                       // [8] of the 8->1 k1 layer
   float* tail_pack = nullptr;                     // conv_valu.hip: {bias3[8], w4[8][8], b4[8], w5[8], b5[1]} in one buffer
-  // conv_mfma16.hip: split-operand fp16 MFMA (TFL_CONV_PATH=mfma16)
-  bool m16 = false;
+  // conv_mfma16.hip
   void* wfrag16[3] = {nullptr, nullptr, nullptr}; // A fragments of the three k=3 layers (conv3_m16_pack_weights)
   float post16[3] = {0.0f, 0.0f, 0.0f};           // 2^-(11 + e) of each layer
   float post16_tail = 0.0f;                       // the same for the tail's 8 -> 8 (k = 1) layer (conv3_m16_pack_tail)
   unsigned long long* d_range_err = nullptr;      // blocks that clamped an activation at the fp16 range
   unsigned long long* h_range = nullptr;          // pinned, device-mapped: the projection kernel copies a non-zero count here, so the
   unsigned long long* d_range_host = nullptr;     // NEXT call sees it without a stream sync (d_range_host = its device address)
-  // 2-D `default` topology (3->16, 16->16 x3 k3, 16->1 k1): MFMA path (conv2d_mfma.hip)
-  bool mfma2d = false;
+  // 2-D `default` topology (conv2d_mfma.hip)
   float* bfrag2[4] = {nullptr, nullptr, nullptr, nullptr};
   double* d_stats = nullptr;  // [2 * kMaxBatch]: sum(u), sum(u^2) per sample
   long long stat_pairs_per_plane = 0;   // partial pairs per z-plane the last tfl_model_begin wrote (model.hip model_pre's layout)
@@ -63,8 +71,7 @@ struct tfl_model {
   tfl_model_opts opts = {1, 0, 1, 1, TFL_NORM_UDIV, TFL_NORMFUNC_STD, TFL_NONLIN_RELU, 0};
   bool custom = false;
   int in_c = 3;               // net input channels
-  // tfl_model_create_graph: banks / batch norm / max pooling (shape-generic kernels, un-sharded)
-  bool graph = false;
+  // graph models: banks / batch norm / max pooling (shape-generic kernels, un-sharded)
   int banks = 1, bank_type = TFL_BANKS_MRES, aggregate = TFL_AGG_CONCAT, split = 0, join = 0, nstages = 0;
   bool pool_max = false;
   int bank_c = 0;             // channel planes of each bank's two scratch buffers
@@ -103,7 +110,7 @@ KernelTimer::~KernelTimer() {
 }
 hipEvent_t KernelTimer::start() const { return (slot_ >= 0 && g_prof) ? g_prof->recs[slot_].e0 : nullptr; }
 hipEvent_t KernelTimer::stop() const { return (slot_ >= 0 && g_prof) ? g_prof->recs[slot_].e1 : nullptr; }
-bool model_is_graph(const tfl_model* m) { return m && m->graph; }
+bool model_is_graph(const tfl_model* m) { return m && m->path == ConvPath::graph; }
 int model_grid_factor(const tfl_model* m) { return m ? m->max_down : 1; }
 
 // The z-slab cone of a model: ONE backward walk over the layer table gives both the window of every launch and
@@ -118,13 +125,13 @@ int model_grid_factor(const tfl_model* m) { return m ? m->max_down : 1; }
 bool model_cone(const tfl_model* m, ModelCone* out, const char** why) {
   auto no = [&](const char* w) { if (why) *why = w; return false; };
   if (!m) return no("no model");
-  if (m->graph) return no("banked, batch-norm and max-pool models run un-sharded only (tfl_simulate_step)");
+  if (m->path == ConvPath::graph) return no("banked, batch-norm and max-pool models run un-sharded only (tfl_simulate_step)");
   if (!m->is3d) return no("2-D grids have no z to cut (run replicas)");
   const int n = (int)m->layers.size();
   if (n > (int)(sizeof(out->layer) / sizeof(out->layer[0]))) return no("more than 32 layers");
   ModelCone c{};
-  c.fused = m->mfma3d;
-  c.windowed = !m->mfma3d;
+  c.fused = default3(m->path);
+  c.windowed = !c.fused;
   c.F = m->max_down;
   c.nlayers = n;
   c.reads_U = m->opts.in_UDiv != 0;
@@ -774,10 +781,6 @@ int tfl_solveLinearSystemJacobi(tfl_ctx* c, const tfl_tensor* p, const tfl_tenso
   return check_launch(c, "solveLinearSystemJacobi");
 }
 
-// TFL_CONV_PATH: unset / "mfma16" = split-operand fp16 MFMA (conv_mfma16.hip: the default), "winograd" = fp32 Winograd on
-// the vector ALUs (conv_valu.hip), "mfma" = fp32-operand MFMA (conv_mfma.hip), "direct" = the shape-generic kernels
-static bool conv3d_default_is_m16(const char* force) { return !force || !*force || strcmp(force, "mfma16") == 0; }
-
 tfl_model* tfl_model_create(tfl_ctx* c, int is3D, int nlayers, const int32_t* cin, const int32_t* cout,
                             const int32_t* ksize, const float* const* weights, const float* const* biases) {
   return tfl_model_create_ex(c, is3D, nlayers, cin, cout, ksize, nullptr, nullptr, weights, biases);
@@ -819,6 +822,241 @@ static bool model_opts_of(tfl_ctx* c, int nlayers, const int32_t* pool, const in
   return true;
 }
 
+}  // extern "C"
+// the layer table and weight packing of tfl_model_create_opts / _graph (C++ linkage: templates)
+namespace {
+// a new device buffer holding `bytes` host bytes; false on failure (what was allocated goes with the model)
+template <class T> bool upload(T*& dst, const void* src, size_t bytes) {
+  return hipMalloc((void**)&dst, bytes) == hipSuccess && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// Where the conv modules sit in lib/model.lua's stage table: module i is bank bank[i] of stage stage[i] (1-based), and stage s
+// starts at module first[s]. Stages [split, join) run `banks` banks side by side; a linear model has one bank per stage.
+struct StageTable {
+  std::vector<int> stage, bank, first;
+  int banks = 1, split = 0, join = 0;
+  bool mres = false, concat = false;
+  bool banked(int st) const { return banks > 1 && st >= split && st < join; }
+};
+
+StageTable stage_table(int nst, int banks = 1, int split = 0, int join = 0) {
+  StageTable t;
+  t.banks = banks; t.split = split; t.join = join;
+  t.first.assign(nst + 2, -1);
+  for (int st = 1; st <= nst; st++) {
+    t.first[st] = (int)t.stage.size();
+    for (int b = 0; b < (t.banked(st) ? banks : 1); b++) { t.stage.push_back(st); t.bank.push_back(b); }
+  }
+  return t;
+}
+
+// A module's cudnn weight [cout*S][cin][taps] (output channel index = o*S + sub) -> [sub][tap][cin_p][cout_p], reference input
+// channel ci on plane cmap(ci), and its bias [cout*S] -> [sub][cout_p], uploaded into L (the padding holds zeros)
+template <class Map>
+bool upload_layer(tfl_layer& L, bool is3d, int ci_n, int co_n, const float* w, const float* b, Map cmap) {
+  const int taps = is3d ? L.k * L.k * L.k : L.k * L.k;
+  const int S = is3d ? L.up * L.up * L.up : L.up * L.up;
+  std::vector<float> relaid((size_t)S * taps * L.cin * L.cout, 0.0f);
+  for (int sub = 0; sub < S; sub++)
+    for (int co = 0; co < co_n; co++)
+      for (int ci = 0; ci < ci_n; ci++)
+        for (int t = 0; t < taps; t++)
+          relaid[(((size_t)sub * taps + t) * L.cin + cmap(ci)) * L.cout + co] = w[(((size_t)co * S + sub) * ci_n + ci) * taps + t];
+  std::vector<float> bias_p((size_t)S * L.cout, 0.0f);
+  for (int sub = 0; sub < S; sub++)
+    for (int co = 0; co < co_n; co++) bias_p[(size_t)sub * L.cout + co] = b[(size_t)co * S + sub];
+  return upload(L.w, relaid.data(), relaid.size() * sizeof(float)) && upload(L.b, bias_p.data(), bias_p.size() * sizeof(float));
+}
+
+// batch norm after hidden module i, folded in double: scale = w / sqrt(var + eps), shift = b - mean * scale, each rounded once
+// to fp32, as [2][cout_p] (padded channels: 0, 0 -- they stay exact zeros)
+std::vector<float> bn_fold(const tfl_model_graph* g, int i, int co_n, int cout_p) {
+  std::vector<float> bn((size_t)2 * cout_p, 0.0f);
+  for (int co = 0; co < co_n; co++) {
+    const double wt = (g->bn_weight && g->bn_weight[i]) ? (double)g->bn_weight[i][co] : 1.0;
+    const double bi = (g->bn_bias && g->bn_bias[i]) ? (double)g->bn_bias[i][co] : 0.0;
+    const double sc = wt / std::sqrt((double)g->bn_var[i][co] + g->bn_eps[i]);
+    bn[co] = (float)sc;
+    bn[cout_p + co] = (float)(bi - (double)g->bn_mean[i][co] * sc);
+  }
+  return bn;
+}
+
+// The layer table of a new model, for both create functions: checks every module against the stage table, pads its channel
+// counts, lays out and uploads its weights (and, with g->batch_norm, its folded batch norm), and tracks the resolution, the
+// widest activation and the bank buffers' shapes. g = null for a linear model. Null on error (c->err says why).
+tfl_model* build_layers(tfl_ctx* c, bool is3d, int n, const int32_t* cin, const int32_t* cout, const int32_t* ksize,
+                        const int32_t* pool, const int32_t* up, const float* const* weights, const float* const* biases,
+                        const tfl_model_opts& o, const StageTable& t, const tfl_model_graph* g) {
+  auto bad = [&](const char* msg) -> tfl_model* { fail(c, TFL_EINVAL, "model_create: %s", msg); return nullptr; };
+  const int in_c = o.in_pDiv + o.in_UDiv * (is3d ? 3 : 2) + o.in_div + 1;
+  if (cin[0] != in_c) {
+    fail(c, TFL_EINVAL, "model_create: the first layer must take %d input channels {pDiv, UDiv, div, occupancy as selected}", in_c);
+    return nullptr;
+  }
+  if (cout[n - 1] != 1) return bad("the last layer must output 1 channel (pressure)");
+  tfl_model* m = new tfl_model();
+  m->is3d = is3d;
+  m->opts = o; m->in_c = in_c;
+  m->custom = !(o.in_pDiv && !o.in_UDiv && o.in_div && o.normalize && o.norm_chan == TFL_NORM_UDIV &&
+                o.norm_func == TFL_NORMFUNC_STD && o.nonlin == TFL_NONLIN_RELU && !o.pressure_skip);
+  auto cleanup = [&](const char* msg) -> tfl_model* { tfl_model_destroy(c, m); return bad(msg); };
+  if (hipMalloc((void**)&m->d_stats, sizeof(double) * 2 * kMaxBatch) != hipSuccess) return cleanup("hipMalloc failed");
+#ifdef TFL_EXPERIMENTS      // the ticket words of the producer-side stats fold (model.hip kStatTickets): EXPERIMENTS flavour and linear models only
+  if (!g && (hipMalloc((void**)&m->d_ticket, sizeof(unsigned) * (1 << 16)) != hipSuccess || hipMemset(m->d_ticket, 0, sizeof(unsigned) * (1 << 16)) != hipSuccess))
+    return cleanup("hipMalloc failed");
+#endif
+  // The shape-generic kernels are instantiated for 1, 2, 4, 8, 16, 32, 64 output channels. Any other width (the
+  // `yang` topology of model.lua:188-205 has 6) is zero-padded to the next one: the extra channels carry
+  // relu(0 + 0) = 0 into zero weights of the next layer, i.e. every sum gains exact `+ 0 * 0` terms only.
+  auto padded = [](int cch) { for (int w : {1, 2, 4, 8, 16, 32, 64}) if (cch <= w) return w; return -1; };
+  const int N = t.banks;
+  std::vector<int> cout_p(t.first.size(), 0);     // padded output channels of each stage
+  int down = 1;                                   // resolution of the current activations = grid / down
+  for (int i = 0; i < n; i++) {
+    const int st = t.stage[i], bk = t.bank[i];
+    const bool last = i + 1 == n, skip_in = o.pressure_skip && last;     // skip_in: also reads pDiv/scale (last channel)
+    const bool joined = N > 1 && st == t.join && t.concat;          // input = the concat of the banks
+    if (cin[i] < 1 || cout[i] < 1 || ksize[i] < 1 || (ksize[i] % 2) != 1) return cleanup("convolution size must be odd and positive");
+    if (st > 1 && cin[i] != cout[t.first[st - 1]] * (joined ? N : 1) + (skip_in ? 1 : 0)) return cleanup("layer channel counts do not chain");
+    tfl_layer L;
+    L.stage = st; L.bank = bk; L.pool = pool ? pool[i] : 1; L.up = up ? up[i] : 1;
+    L.dil = (N > 1 && !t.mres && bk > 0) ? (1 << bk) : 1;
+    if ((L.pool != 1 && L.pool != 2) || (L.up != 1 && L.up != 2)) return cleanup("pooling / upsampling factors must be 1 or 2");
+    if (L.pool > 1 && L.up > 1) return cleanup("Pooling and upsampling in the same layer!");               // model.lua:322-324
+    if (L.pool > 1 && last) return cleanup("Pooling is not allowed in the last layer");                    // model.lua:247
+    const int cp = last ? cout[i] : padded(cout[i]);
+    const int prev_p = st == 1 ? in_c : cout_p[st - 1];
+    const int cin_p = st == 1 ? in_c : prev_p * (joined ? N : 1) + (skip_in ? 1 : 0);     // the skip channel sits last
+    if (bk == 0) {     // (the banks of a stage have bank 0's shape)
+      cout_p[st] = cp;
+      if (N > 1 && st == t.split) {
+        m->split_c = cin_p; m->split_down = down; m->bank_down = down;
+        // the pyramid's coarsest level, whatever the banked stages do after it
+        if (t.mres && (down << (N - 1)) > m->max_down) m->max_down = down << (N - 1);
+      }
+      if (down % L.up) return cleanup("a layer upsamples beyond the grid resolution");
+      down /= L.up;
+      if (t.banked(st)) {
+        if (down < m->bank_down) m->bank_down = down;
+        if (cp > m->bank_c) m->bank_c = cp;
+      }
+      down *= L.pool;
+      const int coarsest = (t.mres && t.banked(st)) ? down << (N - 1) : down;
+      if (coarsest > m->max_down) m->max_down = coarsest;
+      if (L.pool > 1 || L.up > 1 || down != 1) m->multires = true;
+    }
+    if (cp < 0) return cleanup("unsupported output channel count (at most 64)");
+    L.cin = cin_p; L.cout = cp; L.k = ksize[i];
+    // reference input channel ci -> its plane in the padded layout (banks' slices prev_p apart; the skip channel last)
+    const int C = st == 1 ? in_c : cout[t.first[st - 1]];
+    auto cmap = [&](int ci) { return (skip_in && ci == cin[i] - 1) ? cin_p - 1 : joined ? (ci / C) * prev_p + ci % C : ci; };
+    const bool has_bn = g && g->batch_norm && !last;
+    if (has_bn && (!g->bn_mean[i] || !g->bn_var[i])) { m->layers.push_back(L); return cleanup("addBatchNorm: a module lacks running_mean / running_var"); }
+    const std::vector<float> bn = has_bn ? bn_fold(g, i, cout[i], cp) : std::vector<float>();
+    const bool ok = upload_layer(L, is3d, cin[i], cout[i], weights[i], biases[i], cmap) &&
+                    (bn.empty() || upload(L.bn, bn.data(), bn.size() * sizeof(float)));
+    m->layers.push_back(L);
+    if (!ok) return cleanup("uploading weights failed");
+    const int width = (N > 1 && st == t.join - 1 && t.concat) ? cp * N : cp + (o.pressure_skip ? 1 : 0);
+    if (!last && width > m->max_c) m->max_c = width;
+  }
+  if (down != 1) return cleanup("the layers do not return to the grid resolution (pool / up factors)");
+  if (N > 1 && t.mres) m->multires = true;
+  if (m->max_c < 1) m->max_c = 1;
+  return m;
+}
+
+// TFL_CONV_PATH -> the form of the 3-D default topology ("direct" never gets here: it keeps the generic kernels)
+ConvPath conv3d_path(const char* force) {
+  if (!force || !*force || strcmp(force, "mfma16") == 0) return ConvPath::conv_mfma16;
+  if (strcmp(force, "mfma") == 0) return ConvPath::conv_mfma;
+  return ConvPath::conv_valu;
+}
+
+// The 3-D default topology's own weights: the fp32 MFMA B fragments and tail weights (every form), the fp16 A fragments and
+// range words (conv_mfma16), the tail pack and the Winograd-transformed weights (conv_mfma16 and conv_valu). Sets the path;
+// returns what failed, or null.
+const char* pack_default3(tfl_model* m, const int32_t* cin, const float* const* weights, const float* const* biases, ConvPath path) {
+  m->path = path;
+  for (int l = 0; l < 3; l++) {
+    const int ci_n = cin[l];
+    std::vector<float> frag((size_t)ci_n * 9 * 64);
+    for (int c = 0; c < ci_n; c++)
+      for (int kz = 0; kz < 3; kz++)
+        for (int ky = 0; ky < 3; ky++)
+          for (int lane = 0; lane < 64; lane++) {
+            const int k = lane >> 4, n = lane & 15, ph = n >> 3, co = n & 7, kx = k - ph;
+            float v = 0.0f;
+            if (kx >= 0 && kx <= 2) v = weights[l][((((size_t)co * ci_n + c) * 3 + kz) * 3 + ky) * 3 + kx];
+            frag[(((size_t)c * 3 + kz) * 3 + ky) * 64 + lane] = v;
+          }
+    if (!upload(m->bfrag[l], frag.data(), frag.size() * sizeof(float))) return "uploading MFMA weight fragments failed";
+  }
+  if (!upload(m->tail_w4, weights[3], 64 * sizeof(float)) || !upload(m->tail_w5, weights[4], 8 * sizeof(float)))
+    return "uploading tail weights failed";
+  if (path == ConvPath::conv_mfma16) {
+    for (int l = 0; l < 3; l++) {
+      std::vector<uint16_t> fr(tfl::conv3_m16_frag_halves(cin[l]));
+      m->post16[l] = tfl::conv3_m16_pack_weights(weights[l], cin[l], fr.data());
+      if (l == 2) m->post16_tail = tfl::conv3_m16_pack_tail(weights[3], fr.data());     // the 8 -> 8 (k = 1) layer's A fragment
+      if (!upload(m->wfrag16[l], fr.data(), fr.size() * sizeof(uint16_t))) return "uploading fp16 MFMA weight fragments failed";
+    }
+    if (hipMalloc((void**)&m->d_range_err, sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(m->d_range_err, 0, sizeof(unsigned long long)) != hipSuccess)
+      return "hipMalloc failed";
+    // the word a later call reads without a sync; failing to get mapped memory only loses the early warning
+    if (hipHostMalloc((void**)&m->h_range, sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
+      *m->h_range = 0;
+      if (hipHostGetDevicePointer((void**)&m->d_range_host, m->h_range, 0) != hipSuccess) { (void)hipHostFree(m->h_range); m->h_range = nullptr; m->d_range_host = nullptr; }
+    } else m->h_range = nullptr;
+  }
+  if (path == ConvPath::conv_mfma) return nullptr;
+  std::vector<float> tp(8 + 64 + 8 + 8 + 1 + 1);
+  for (int i = 0; i < 8; i++) tp[i] = biases[2][i];
+  for (int i = 0; i < 64; i++) tp[8 + i] = weights[3][i];
+  for (int i = 0; i < 8; i++) { tp[72 + i] = biases[3][i]; tp[80 + i] = weights[4][i]; }
+  tp[88] = biases[4][0];
+  tp[89] = m->post16_tail;        // conv_mfma16.hip kTailPost4 (0 on the fp32 paths, which do not read it)
+  if (!upload(m->tail_pack, tp.data(), tp.size() * sizeof(float))) return "uploading tail weights failed";
+  // the three k = 3 layers' weights, Winograd-transformed along x: U = (g0, (g0 + g1 + g2)/2, (g0 - g1 + g2)/2, g2) over the
+  // three x-taps of every (dz, dy, c_in, c_out)
+  for (int l = 0; l < 3; l++) {
+    const int ci_n = cin[l];
+    std::vector<float> u((size_t)9 * 4 * ci_n * 8);
+    for (int co = 0; co < 8; co++)
+      for (int c = 0; c < ci_n; c++)
+        for (int zy = 0; zy < 9; zy++) {
+          const float* g = weights[l] + (((size_t)co * ci_n + c) * 9 + zy) * 3;
+          const float uu[4] = {g[0], 0.5f * ((g[0] + g[2]) + g[1]), 0.5f * ((g[0] + g[2]) - g[1]), g[2]};
+          for (int p = 0; p < 4; p++) u[(((size_t)zy * ci_n + c) * 4 + p) * 8 + co] = uu[p];
+        }
+    if (!upload(m->wino[l], u.data(), u.size() * sizeof(float))) return "uploading transformed weights failed";
+  }
+  return nullptr;
+}
+
+// The 2-D default topology's own weights (conv2d_mfma.hip); returns what failed, or null
+const char* pack_default2(tfl_model* m, const int32_t* cin, const float* const* weights) {
+  m->path = ConvPath::conv2d_mfma;
+  for (int l = 0; l < 4; l++) {
+    const int ci_n = cin[l], c4n = (ci_n + 3) / 4;
+    // B[k][n] of MFMA (tap, c4): lane = k*16 + n holds w[n][4*c4 + k][dy][dx] (0 for padded channels)
+    std::vector<float> frag((size_t)9 * c4n * 64);
+    for (int tap = 0; tap < 9; tap++)
+      for (int c4 = 0; c4 < c4n; c4++)
+        for (int lane = 0; lane < 64; lane++) {
+          const int k = lane >> 4, n = lane & 15, c = 4 * c4 + k;
+          frag[((size_t)tap * c4n + c4) * 64 + lane] = c < ci_n ? weights[l][((size_t)n * ci_n + c) * 9 + tap] : 0.0f;
+        }
+    if (!upload(m->bfrag2[l], frag.data(), frag.size() * sizeof(float))) return "uploading 2-D MFMA weight fragments failed";
+  }
+  if (!upload(m->tail_w5, weights[4], 16 * sizeof(float))) return "uploading tail weights failed";
+  return nullptr;
+}
+}  // namespace
+extern "C" {
+
 tfl_model* tfl_model_create_opts(tfl_ctx* c, int is3D, int nlayers, const int32_t* cin, const int32_t* cout,
                                  const int32_t* ksize, const int32_t* pool, const int32_t* up,
                                  const float* const* weights, const float* const* biases, const tfl_model_opts* opts) {
@@ -827,176 +1065,21 @@ tfl_model* tfl_model_create_opts(tfl_ctx* c, int is3D, int nlayers, const int32_
   if (nlayers < 1 || !cin || !cout || !ksize || !weights || !biases) return bad("null or empty layer description");
   tfl_model_opts o;
   if (!model_opts_of(c, nlayers, pool, up, opts, &o)) return nullptr;
-  const int in_c = o.in_pDiv + o.in_UDiv * (is3D ? 3 : 2) + o.in_div + 1;
-  if (cin[0] != in_c) {
-    fail(c, TFL_EINVAL, "model_create: the first layer must take %d input channels {pDiv, UDiv, div, occupancy as selected}", in_c);
-    return nullptr;
-  }
-  if (cout[nlayers - 1] != 1) return bad("the last layer must output 1 channel (pressure)");
-  tfl_model* m = new tfl_model();
-  m->is3d = is3D != 0;
-  m->opts = o; m->in_c = in_c;
-  m->custom = !(o.in_pDiv && !o.in_UDiv && o.in_div && o.normalize && o.norm_chan == TFL_NORM_UDIV &&
-                o.norm_func == TFL_NORMFUNC_STD && o.nonlin == TFL_NONLIN_RELU && !o.pressure_skip);
-  auto cleanup = [&](const char* msg) -> tfl_model* { tfl_model_destroy(c, m); return bad(msg); };
-  if (hipMalloc((void**)&m->d_stats, sizeof(double) * 2 * kMaxBatch) != hipSuccess) return cleanup("hipMalloc failed");
-#ifdef TFL_EXPERIMENTS      // the ticket words of the producer-side stats fold (model.hip kStatTickets): EXPERIMENTS flavour only
-  if (hipMalloc((void**)&m->d_ticket, sizeof(unsigned) * (1 << 16)) != hipSuccess || hipMemset(m->d_ticket, 0, sizeof(unsigned) * (1 << 16)) != hipSuccess)
-    return cleanup("hipMalloc failed");
-#endif
-  // The shape-generic kernels are instantiated for 1, 2, 4, 8, 16, 32, 64 output channels. Any other width (the
-  // `yang` topology of model.lua:188-205 has 6) is zero-padded to the next one: the extra channels carry
-  // relu(0 + 0) = 0 into zero weights of the next layer, i.e. every sum gains exact `+ 0 * 0` terms only.
-  auto padded = [](int cch) { for (int w : {1, 2, 4, 8, 16, 32, 64}) if (cch <= w) return w; return -1; };
-  int prev_cout_padded = in_c;
-  int res_num = 1, res_den = 1;   // resolution of the current activations relative to the grid = res_num / res_den
-  for (int l = 0; l < nlayers; l++) {
-    tfl_layer L;
-    if (cin[l] < 1 || cout[l] < 1 || ksize[l] < 1 || (ksize[l] % 2) != 1) return cleanup("convolution size must be odd and positive");
-    const bool skip_in = m->opts.pressure_skip && l + 1 == nlayers;     // this layer also reads pDiv/scale (last channel)
-    if (l > 0 && cin[l] != cout[l - 1] + (skip_in ? 1 : 0)) return cleanup("layer channel counts do not chain");
-    L.pool = pool ? pool[l] : 1; L.up = up ? up[l] : 1;
-    if ((L.pool != 1 && L.pool != 2) || (L.up != 1 && L.up != 2)) return cleanup("pooling / upsampling factors must be 1 or 2");
-    if (L.pool > 1 && L.up > 1) return cleanup("Pooling and upsampling in the same layer!");               // model.lua:322-324
-    if (L.pool > 1 && l + 1 == nlayers) return cleanup("Pooling is not allowed in the last layer");        // model.lua:247
-    res_num *= L.up; res_den *= L.pool;
-    if (res_num > res_den) return cleanup("a layer upsamples beyond the grid resolution");
-    if (L.pool > 1 || L.up > 1 || res_num != res_den) m->multires = true;
-    if (res_den / res_num > m->max_down) m->max_down = res_den / res_num;
-    const int cout_p = (l + 1 == nlayers) ? cout[l] : padded(cout[l]);
-    if (cout_p < 0) return cleanup("unsupported output channel count (at most 64)");
-    const int cin_p = prev_cout_padded + (skip_in ? 1 : 0);     // the skip channel sits after the (padded) hidden channels
-    L.cin = cin_p; L.cout = cout_p; L.k = ksize[l];
-    prev_cout_padded = cout_p;
-    const int taps = m->is3d ? L.k * L.k * L.k : L.k * L.k;
-    const int S = m->is3d ? L.up * L.up * L.up : L.up * L.up;
-    // cudnn weight [cout*S][cin][taps] (output channel index = o*S + sub) -> [sub][tap][cin_p][cout_p]
-    std::vector<float> relaid((size_t)S * taps * L.cin * L.cout, 0.0f);
-    for (int sub = 0; sub < S; sub++)
-      for (int co = 0; co < cout[l]; co++)
-        for (int ci = 0; ci < cin[l]; ci++)
-          for (int t = 0; t < taps; t++) {
-            const int cid = (skip_in && ci == cin[l] - 1) ? L.cin - 1 : ci;
-            relaid[(((size_t)sub * taps + t) * L.cin + cid) * L.cout + co] =
-                weights[l][(((size_t)co * S + sub) * cin[l] + ci) * taps + t];
-          }
-    std::vector<float> bias_p((size_t)S * L.cout, 0.0f);
-    for (int sub = 0; sub < S; sub++)
-      for (int co = 0; co < cout[l]; co++) bias_p[(size_t)sub * L.cout + co] = biases[l][(size_t)co * S + sub];
-    if (hipMalloc((void**)&L.w, relaid.size() * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&L.b, bias_p.size() * sizeof(float)) != hipSuccess ||
-        hipMemcpy(L.w, relaid.data(), relaid.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(L.b, bias_p.data(), bias_p.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-      m->layers.push_back(L);
-      return cleanup("uploading weights failed");
-    }
-    m->layers.push_back(L);
-    if (L.cout + (m->opts.pressure_skip ? 1 : 0) > m->max_c && l + 1 < nlayers) m->max_c = L.cout + (m->opts.pressure_skip ? 1 : 0);
-  }
-  if (res_num != res_den) return cleanup("the layers do not return to the grid resolution (pool / up factors)");
-  if (m->max_c < 1) m->max_c = 1;
-  // ---- MFMA path for the 3-D default topology (TFL_CONV_PATH=direct forces the generic kernels) ----
+  tfl_model* m = build_layers(c, is3D != 0, nlayers, cin, cout, ksize, pool, up, weights, biases, o, stage_table(nlayers), nullptr);
+  if (!m) return nullptr;
+  // the default topologies run on kernels of their own (TFL_CONV_PATH=direct forces the generic ones)
   const char* force = getenv("TFL_CONV_PATH");
-  const bool want_mfma = !(force && strcmp(force, "direct") == 0) && !m->custom;
-  const int dflt[5][3] = {{3, 8, 3}, {8, 8, 3}, {8, 8, 3}, {8, 8, 1}, {8, 1, 1}};
-  bool match = m->is3d && nlayers == 5 && !m->multires;
-  for (int l = 0; match && l < 5; l++) match = cin[l] == dflt[l][0] && cout[l] == dflt[l][1] && ksize[l] == dflt[l][2];
-  if (match && want_mfma) {
-    for (int l = 0; l < 3; l++) {
-      const int ci_n = cin[l];
-      std::vector<float> frag((size_t)ci_n * 9 * 64);
-      for (int c = 0; c < ci_n; c++)
-        for (int kz = 0; kz < 3; kz++)
-          for (int ky = 0; ky < 3; ky++)
-            for (int lane = 0; lane < 64; lane++) {
-              const int k = lane >> 4, n = lane & 15, ph = n >> 3, co = n & 7, kx = k - ph;
-              float v = 0.0f;
-              if (kx >= 0 && kx <= 2) v = weights[l][((((size_t)co * ci_n + c) * 3 + kz) * 3 + ky) * 3 + kx];
-              frag[(((size_t)c * 3 + kz) * 3 + ky) * 64 + lane] = v;
-            }
-      if (hipMalloc((void**)&m->bfrag[l], frag.size() * sizeof(float)) != hipSuccess ||
-          hipMemcpy(m->bfrag[l], frag.data(), frag.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup("uploading MFMA weight fragments failed");
-    }
-    if (hipMalloc((void**)&m->tail_w4, 64 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&m->tail_w5, 8 * sizeof(float)) != hipSuccess ||
-        hipMemcpy(m->tail_w4, weights[3], 64 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(m->tail_w5, weights[4], 8 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-      return cleanup("uploading tail weights failed");
-    m->mfma3d = true;
-    // default: the vector-ALU kernels (conv_valu.hip; faster than the fp32-MFMA form for 8 output channels, see there).
-    // TFL_CONV_PATH=mfma keeps the MFMA kernels.
-    m->valu3d = !(force && strcmp(force, "mfma") == 0);
-    m->m16 = conv3d_default_is_m16(force);
-    // their weights, Winograd-transformed along x: U = (g0, (g0 + g1 + g2)/2, (g0 - g1 + g2)/2, g2) over the three x-taps
-    // of every (dz, dy, c_in, c_out)
-    if (m->m16) {
-      for (int l = 0; l < 3; l++) {
-        std::vector<uint16_t> fr(tfl::conv3_m16_frag_halves(cin[l]));
-        m->post16[l] = tfl::conv3_m16_pack_weights(weights[l], cin[l], fr.data());
-        if (l == 2) m->post16_tail = tfl::conv3_m16_pack_tail(weights[3], fr.data());     // the 8 -> 8 (k = 1) layer's A fragment
-        if (hipMalloc(&m->wfrag16[l], fr.size() * sizeof(uint16_t)) != hipSuccess ||
-            hipMemcpy(m->wfrag16[l], fr.data(), fr.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess)
-          return cleanup("uploading fp16 MFMA weight fragments failed");
-      }
-      if (hipMalloc((void**)&m->d_range_err, sizeof(unsigned long long)) != hipSuccess ||
-          hipMemset(m->d_range_err, 0, sizeof(unsigned long long)) != hipSuccess)
-        return cleanup("hipMalloc failed");
-      // the word a later call reads without a sync; failing to get mapped memory only loses the early warning
-      if (hipHostMalloc((void**)&m->h_range, sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
-        *m->h_range = 0;
-        if (hipHostGetDevicePointer((void**)&m->d_range_host, m->h_range, 0) != hipSuccess) { (void)hipHostFree(m->h_range); m->h_range = nullptr; m->d_range_host = nullptr; }
-      } else m->h_range = nullptr;
-    }
-    if (m->valu3d) {
-      std::vector<float> tp(8 + 64 + 8 + 8 + 1 + 1);
-      for (int i = 0; i < 8; i++) tp[i] = biases[2][i];
-      for (int i = 0; i < 64; i++) tp[8 + i] = weights[3][i];
-      for (int i = 0; i < 8; i++) { tp[72 + i] = biases[3][i]; tp[80 + i] = weights[4][i]; }
-      tp[88] = biases[4][0];
-      tp[89] = m->post16_tail;        // conv_mfma16.hip kTailPost4 (0 on the fp32 paths, which do not read it)
-      if (hipMalloc((void**)&m->tail_pack, tp.size() * sizeof(float)) != hipSuccess ||
-          hipMemcpy(m->tail_pack, tp.data(), tp.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup("uploading tail weights failed");
-      for (int l = 0; l < 3; l++) {
-        const int ci_n = cin[l];
-        std::vector<float> u((size_t)9 * 4 * ci_n * 8);
-        for (int co = 0; co < 8; co++)
-          for (int c = 0; c < ci_n; c++)
-            for (int zy = 0; zy < 9; zy++) {
-              const float* g = weights[l] + (((size_t)co * ci_n + c) * 9 + zy) * 3;
-              const float uu[4] = {g[0], 0.5f * ((g[0] + g[2]) + g[1]), 0.5f * ((g[0] + g[2]) - g[1]), g[2]};
-              for (int p = 0; p < 4; p++) u[(((size_t)zy * ci_n + c) * 4 + p) * 8 + co] = uu[p];
-            }
-        if (hipMalloc((void**)&m->wino[l], u.size() * sizeof(float)) != hipSuccess ||
-            hipMemcpy(m->wino[l], u.data(), u.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-          return cleanup("uploading transformed weights failed");
-      }
-    }
-  }
+  if ((force && strcmp(force, "direct") == 0) || m->custom || m->multires || nlayers != 5) return m;
+  const int dflt3[5][3] = {{3, 8, 3}, {8, 8, 3}, {8, 8, 3}, {8, 8, 1}, {8, 1, 1}};
   const int dflt2[5][3] = {{3, 16, 3}, {16, 16, 3}, {16, 16, 3}, {16, 16, 3}, {16, 1, 1}};
-  bool match2 = !m->is3d && nlayers == 5 && !m->multires;
-  for (int l = 0; match2 && l < 5; l++) match2 = cin[l] == dflt2[l][0] && cout[l] == dflt2[l][1] && ksize[l] == dflt2[l][2];
-  if (match2 && want_mfma) {
-    for (int l = 0; l < 4; l++) {
-      const int ci_n = cin[l], c4n = (ci_n + 3) / 4;
-      // B[k][n] of MFMA (tap, c4): lane = k*16 + n holds w[n][4*c4 + k][dy][dx] (0 for padded channels)
-      std::vector<float> frag((size_t)9 * c4n * 64);
-      for (int tap = 0; tap < 9; tap++)
-        for (int c4 = 0; c4 < c4n; c4++)
-          for (int lane = 0; lane < 64; lane++) {
-            const int k = lane >> 4, n = lane & 15, c = 4 * c4 + k;
-            frag[((size_t)tap * c4n + c4) * 64 + lane] = c < ci_n ? weights[l][((size_t)n * ci_n + c) * 9 + tap] : 0.0f;
-          }
-      if (hipMalloc((void**)&m->bfrag2[l], frag.size() * sizeof(float)) != hipSuccess ||
-          hipMemcpy(m->bfrag2[l], frag.data(), frag.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup("uploading 2-D MFMA weight fragments failed");
-    }
-    if (hipMalloc((void**)&m->tail_w5, 16 * sizeof(float)) != hipSuccess ||
-        hipMemcpy(m->tail_w5, weights[4], 16 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-      return cleanup("uploading tail weights failed");
-    m->mfma2d = true;
-  }
+  auto is = [&](const int (&t)[5][3]) {
+    for (int l = 0; l < 5; l++) if (cin[l] != t[l][0] || cout[l] != t[l][1] || ksize[l] != t[l][2]) return false;
+    return true;
+  };
+  const char* err = nullptr;
+  if (m->is3d && is(dflt3)) err = pack_default3(m, cin, weights, biases, conv3d_path(force));
+  if (!m->is3d && is(dflt2)) err = pack_default2(m, cin, weights);
+  if (err) { tfl_model_destroy(c, m); return bad(err); }
   return m;
 }
 
@@ -1017,7 +1100,6 @@ tfl_model* tfl_model_create_graph(tfl_ctx* c, int is3D, int nconv, const int32_t
     return tfl_model_create_opts(c, is3D, nconv, cin, cout, ksize, pool, up, weights, biases, opts);
   if (nconv < 2 || !cin || !cout || !ksize || !weights || !biases) return bad("null or empty layer description");
   const int N = g->banks_num;
-  const bool mres = g->bank_type == TFL_BANKS_MRES, concat = g->aggregate == TFL_AGG_CONCAT;
   int nst = nconv;
   if (N > 1) {
     if (g->bank_type != TFL_BANKS_MRES && g->bank_type != TFL_BANKS_DILATE) return bad("banksType must be 'mres' or 'dilate'");
@@ -1027,129 +1109,26 @@ tfl_model* tfl_model_create_graph(tfl_ctx* c, int is3D, int nconv, const int32_t
     if (g->split_stage < 1 || g->join_stage >= nst) return bad("banksSplitStage / banksJoinStage must lie before the last stage (model.lua:257-258)");
   }
   if (g->batch_norm && (!g->bn_mean || !g->bn_var || !g->bn_eps)) return bad("addBatchNorm needs running_mean, running_var and eps per module");
-  // module m -> (stage, bank), creation order
-  std::vector<int> stage_of, bank_of, first_of(nst + 2, -1);
-  for (int st = 1; st <= nst; st++) {
-    const int nb = (N > 1 && st >= g->split_stage && st < g->join_stage) ? N : 1;
-    first_of[st] = (int)stage_of.size();
-    for (int b = 0; b < nb; b++) { stage_of.push_back(st); bank_of.push_back(b); }
-  }
+  StageTable t = N > 1 ? stage_table(nst, N, g->split_stage, g->join_stage) : stage_table(nst);
+  t.mres = g->bank_type == TFL_BANKS_MRES; t.concat = g->aggregate == TFL_AGG_CONCAT;
   auto P = [&](const int32_t* a, int i) { return a ? a[i] : 1; };
   for (int i = 0; i < nconv; i++) {
-    const int f = first_of[stage_of[i]];
+    const int f = t.first[t.stage[i]];
     if (cin[i] != cin[f] || cout[i] != cout[f] || ksize[i] != ksize[f] || P(pool, i) != P(pool, f) || P(up, i) != P(up, f))
       return bad("the banks of a stage must have the same shape");
-    if (N > 1 && !mres && bank_of[i] > 0 && P(up, i) > 1) return bad("upsampling not supported for dilated convolutions.");
+    if (N > 1 && !t.mres && t.bank[i] > 0 && P(up, i) > 1) return bad("upsampling not supported for dilated convolutions.");
   }
   // the stage table the options are checked against (one entry per stage)
   std::vector<int32_t> spool(nst), sup(nst);
-  for (int st = 1; st <= nst; st++) { spool[st - 1] = P(pool, first_of[st]); sup[st - 1] = P(up, first_of[st]); }
+  for (int st = 1; st <= nst; st++) { spool[st - 1] = P(pool, t.first[st]); sup[st - 1] = P(up, t.first[st]); }
   tfl_model_opts o;
   if (!model_opts_of(c, nst, spool.data(), sup.data(), opts, &o)) return nullptr;
-  if (o.pressure_skip && N > 1 && mres) return unsupported("addPressureSkip with pooling / upsampling layers");
-  const int in_c = o.in_pDiv + o.in_UDiv * (is3D ? 3 : 2) + o.in_div + 1;
-  if (cin[0] != in_c) {
-    fail(c, TFL_EINVAL, "model_create: the first layer must take %d input channels {pDiv, UDiv, div, occupancy as selected}", in_c);
-    return nullptr;
-  }
-  if (cout[nconv - 1] != 1) return bad("the last layer must output 1 channel (pressure)");
-  tfl_model* m = new tfl_model();
-  m->is3d = is3D != 0;
-  m->opts = o; m->in_c = in_c;
-  m->custom = !(o.in_pDiv && !o.in_UDiv && o.in_div && o.normalize && o.norm_chan == TFL_NORM_UDIV &&
-                o.norm_func == TFL_NORMFUNC_STD && o.nonlin == TFL_NONLIN_RELU && !o.pressure_skip);
-  m->graph = true; m->banks = N; m->bank_type = g->bank_type; m->aggregate = g->aggregate;
-  m->split = N > 1 ? g->split_stage : 0; m->join = N > 1 ? g->join_stage : 0; m->nstages = nst;
+  if (o.pressure_skip && N > 1 && t.mres) return unsupported("addPressureSkip with pooling / upsampling layers");
+  tfl_model* m = build_layers(c, is3D != 0, nconv, cin, cout, ksize, pool, up, weights, biases, o, t, g);
+  if (!m) return nullptr;
+  m->path = ConvPath::graph; m->banks = N; m->bank_type = g->bank_type; m->aggregate = g->aggregate;
+  m->split = t.split; m->join = t.join; m->nstages = nst;
   m->pool_max = g->pool_type == TFL_POOL_MAX;
-  auto cleanup = [&](const char* msg) -> tfl_model* { tfl_model_destroy(c, m); return bad(msg); };
-  if (hipMalloc((void**)&m->d_stats, sizeof(double) * 2 * kMaxBatch) != hipSuccess) return cleanup("hipMalloc failed");
-  auto padded = [](int cch) { for (int w : {1, 2, 4, 8, 16, 32, 64}) if (cch <= w) return w; return -1; };
-  std::vector<int> cout_p(nst + 1, 0);     // padded output channels of each stage
-  int down = 1;                            // resolution of the current activations = grid / down
-  for (int i = 0; i < nconv; i++) {
-    const int st = stage_of[i], bk = bank_of[i];
-    const bool last = i + 1 == nconv;
-    const bool skip_in = o.pressure_skip && last;
-    const bool joined = N > 1 && st == g->join_stage && concat;         // input = the concat of the banks
-    if (cin[i] < 1 || cout[i] < 1 || ksize[i] < 1 || (ksize[i] % 2) != 1) return cleanup("convolution size must be odd and positive");
-    if (st > 1 && cin[i] != cout[first_of[st - 1]] * (joined ? N : 1) + (skip_in ? 1 : 0)) return cleanup("layer channel counts do not chain");
-    tfl_layer L;
-    L.stage = st; L.bank = bk;
-    L.pool = P(pool, i); L.up = P(up, i);
-    L.dil = (N > 1 && !mres && bk > 0) ? (1 << bk) : 1;
-    if ((L.pool != 1 && L.pool != 2) || (L.up != 1 && L.up != 2)) return cleanup("pooling / upsampling factors must be 1 or 2");
-    if (L.pool > 1 && L.up > 1) return cleanup("Pooling and upsampling in the same layer!");               // model.lua:322-324
-    if (L.pool > 1 && last) return cleanup("Pooling is not allowed in the last layer");                    // model.lua:247
-    const int cp = last ? cout[i] : padded(cout[i]);
-    if (cp < 0) return cleanup("unsupported output channel count (at most 64)");
-    const int prev_p = st == 1 ? in_c : cout_p[st - 1];
-    const int cin_p = st == 1 ? in_c : prev_p * (joined ? N : 1) + (skip_in ? 1 : 0);
-    if (bk == 0) {
-      cout_p[st] = cp;
-      if (N > 1 && st == g->split_stage) {
-        m->split_c = cin_p; m->split_down = down; m->bank_down = down;
-        // the pyramid's coarsest level, whatever the banked stages do after it
-        if (mres && (down << (N - 1)) > m->max_down) m->max_down = down << (N - 1);
-      }
-      if (down % L.up) return cleanup("a layer upsamples beyond the grid resolution");
-      down = down / L.up;
-      if (N > 1 && st >= g->split_stage && st < g->join_stage) {
-        if (down < m->bank_down) m->bank_down = down;
-        if (cp > m->bank_c) m->bank_c = cp;
-      }
-      down *= L.pool;
-      const int bank_max = (N > 1 && mres && st >= g->split_stage && st < g->join_stage) ? down << (N - 1) : down;
-      if (bank_max > m->max_down) m->max_down = bank_max;
-      if (L.pool > 1 || L.up > 1 || down != 1) m->multires = true;
-    }
-    // input channel ci of the reference -> its plane in the padded layout (banks' slices Cp apart; the skip channel last)
-    const int C = st == 1 ? in_c : cout[first_of[st - 1]];
-    auto cmap = [&](int ci) {
-      if (skip_in && ci == cin[i] - 1) return cin_p - 1;
-      return joined ? (ci / C) * prev_p + ci % C : ci;
-    };
-    L.cin = cin_p; L.cout = cp; L.k = ksize[i];
-    const int taps = is3D ? L.k * L.k * L.k : L.k * L.k;
-    const int S = is3D ? L.up * L.up * L.up : L.up * L.up;
-    std::vector<float> relaid((size_t)S * taps * L.cin * L.cout, 0.0f);
-    for (int sub = 0; sub < S; sub++)
-      for (int co = 0; co < cout[i]; co++)
-        for (int ci = 0; ci < cin[i]; ci++)
-          for (int t = 0; t < taps; t++)
-            relaid[(((size_t)sub * taps + t) * L.cin + cmap(ci)) * L.cout + co] = weights[i][(((size_t)co * S + sub) * cin[i] + ci) * taps + t];
-    std::vector<float> bias_p((size_t)S * L.cout, 0.0f);
-    for (int sub = 0; sub < S; sub++)
-      for (int co = 0; co < cout[i]; co++) bias_p[(size_t)sub * L.cout + co] = biases[i][(size_t)co * S + sub];
-    // batch norm after every hidden module, folded in double: scale = w / sqrt(var + eps), shift = b - mean * scale, each
-    // rounded once to fp32 (padded channels: 0, 0 -- they stay exact zeros)
-    std::vector<float> bn;
-    if (g->batch_norm && !last) {
-      if (!g->bn_mean[i] || !g->bn_var[i]) { m->layers.push_back(L); return cleanup("addBatchNorm: a module lacks running_mean / running_var"); }
-      bn.assign((size_t)2 * L.cout, 0.0f);
-      for (int co = 0; co < cout[i]; co++) {
-        const double wt = (g->bn_weight && g->bn_weight[i]) ? (double)g->bn_weight[i][co] : 1.0;
-        const double bi = (g->bn_bias && g->bn_bias[i]) ? (double)g->bn_bias[i][co] : 0.0;
-        const double sc = wt / std::sqrt((double)g->bn_var[i][co] + g->bn_eps[i]);
-        bn[co] = (float)sc;
-        bn[L.cout + co] = (float)(bi - (double)g->bn_mean[i][co] * sc);
-      }
-    }
-    if (hipMalloc((void**)&L.w, relaid.size() * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&L.b, bias_p.size() * sizeof(float)) != hipSuccess ||
-        hipMemcpy(L.w, relaid.data(), relaid.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(L.b, bias_p.data(), bias_p.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        (!bn.empty() && (hipMalloc((void**)&L.bn, bn.size() * sizeof(float)) != hipSuccess ||
-                         hipMemcpy(L.bn, bn.data(), bn.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))) {
-      m->layers.push_back(L);
-      return cleanup("uploading weights failed");
-    }
-    m->layers.push_back(L);
-    const int width = (N > 1 && st == g->join_stage - 1 && concat) ? cp * N : cp + (o.pressure_skip ? 1 : 0);
-    if (!last && width > m->max_c) m->max_c = width;
-  }
-  if (down != 1) return cleanup("the layers do not return to the grid resolution (pool / up factors)");
-  if (N > 1 && mres) m->multires = true;
-  if (m->max_c < 1) m->max_c = 1;
   return m;
 }
 
@@ -1206,7 +1185,7 @@ static int range_gate(tfl_ctx* c, tfl_model* m, const char* who) {
 // floats of a graph model's bank buffers behind pPred: per bank two scratch buffers of bank_c planes at its finest
 // resolution, and (mres) the pyramid level it starts from; with `base`, their addresses (layout in this order)
 static int64_t graph_ws_floats(const tfl_model* m, int B, int Z, int Y, int X, float* base, float* (*bank)[2], float** pyr = nullptr) {
-  if (!m->graph || m->banks < 2) return 0;
+  if (m->path != ConvPath::graph || m->banks < 2) return 0;
   auto cells = [&](int f) { return (int64_t)B * (m->is3d ? (Z + f - 1) / f : Z) * ((Y + f - 1) / f) * ((X + f - 1) / f); };
   const bool mres = m->bank_type == TFL_BANKS_MRES;
   int64_t off = 0;
@@ -1228,7 +1207,7 @@ int64_t tfl_model_workspace_floats(const tfl_model* m, int B, int Z, int Y, int 
   // per-block fp64 stat partials (2 doubles = 4 floats per block, kept first for 8-byte alignment)
   // + div[1] + net input[in_c] + two ping-pong activation buffers[max_c] + pPred[1]
   // (+4: the fp16 MFMA path aligns its activation buffers to 16 bytes)
-  return 4 * tfl::model_stat_blocks(B, Z, Y, X) + n * (1 + (int64_t)m->in_c + 2 * (int64_t)m->max_c + 1) + (m->m16 ? 4 : 0) +
+  return 4 * tfl::model_stat_blocks(B, Z, Y, X) + n * (1 + (int64_t)m->in_c + 2 * (int64_t)m->max_c + 1) + (m->path == ConvPath::conv_mfma16 ? 4 : 0) +
          graph_ws_floats(m, B, Z, Y, X, nullptr, nullptr);
 }
 
@@ -1247,7 +1226,7 @@ int model_ws(tfl_ctx* c, const tfl_model* m, const tfl_tensor* flags, float* wor
   w->div = workspace + 4 * tfl::model_stat_blocks(B, Z, Y, X);
   w->x3 = w->div + n;
   w->act[0] = w->x3 + (int64_t)m->in_c * n;
-  if (m->m16) w->act[0] = (float*)(((uintptr_t)w->act[0] + 15) & ~(uintptr_t)15);
+  if (m->path == ConvPath::conv_mfma16) w->act[0] = (float*)(((uintptr_t)w->act[0] + 15) & ~(uintptr_t)15);
   w->act[1] = w->act[0] + (int64_t)m->max_c * n;
   w->pPred = w->act[1] + (int64_t)m->max_c * n;
   graph_ws_floats(m, B, Z, Y, X, w->pPred + n, w->bank, w->pyr);
@@ -1271,7 +1250,7 @@ static const unsigned short* wall_code_of(tfl_ctx* c, const tfl_model* m, const 
 // a graph model's grid must be divisible by its largest downsampling factor (the mres pyramid times the pooling): refused
 // before anything is launched (the reference fails at the join)
 static int graph_gate(tfl_ctx* c, const tfl_model* m, const tfl_tensor* flags, const char* who) {
-  if (!m->graph) return TFL_OK;
+  if (m->path != ConvPath::graph) return TFL_OK;
   const int f = m->max_down;
   if ((m->is3d && flags->Z % f) || flags->Y % f || flags->X % f)
     return fail(c, TFL_EINVAL, "%s: grid %dx%dx%d is not divisible by the model's downsampling factor %d (banks x pooling)", who,
@@ -1345,6 +1324,26 @@ void tfl_wall_plan_destroy(tfl_ctx* c, tfl_wall_plan* p) {
 }
 
 namespace {
+// What every forward of tfl_model_finish reads. U: the wall-BC'd velocity tfl_model_begin left in UOut; (st_in, count): the
+// input scale; stg: the tfl_set_stages mask.
+struct Fwd {
+  hipStream_t st;
+  int B, Z, Y, X;
+  const float *pDiv, *U, *flags;
+  const double* st_in; double count;
+  int stg; bool windowed;     // windowed: a z-window is set
+};
+
+// the net input {pDiv/scale, div/scale, occupancy}, or the channels tfl_model_opts selects, into w.x3 on the planes
+// [z0, z0 + nz) (nz < 0: the thread's z-window)
+void net_input(const tfl_model* m, const ModelWs& w, const Fwd& a, int z0, int nz) {
+  if (m->custom)
+    tfl::model_net_input_gen(a.st, m->is3d, a.B, a.Z, a.Y, a.X, m->opts.in_pDiv, m->opts.in_UDiv, m->opts.in_div, a.pDiv,
+                             a.U, w.div, a.flags, a.st_in, a.count, w.x3, z0, nz);
+  else
+    tfl::model_net_input(a.st, m->is3d, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, w.x3, z0, nz);
+}
+
 // One conv module of a graph model at [Zc][Yc][Xc] (updated to its output's): its conv(s) -- one per ConvolutionUpsample
 // sub-position -- then the pooling; the module's batch norm rides on whichever launch writes last. P / Q are two scratch
 // buffers (`in` may be one of them); the result goes to planes [c0, c0 + cout) of the och-plane `dst`, or (dst = null)
@@ -1375,13 +1374,15 @@ float* graph_layer(hipStream_t st, const tfl_model* m, const tfl_layer& L, int B
 
 // The conv stack of a graph model (lib/model.lua:262-362): trunk stages in the act[] ping-pong, the banks in their own
 // buffers, one k_bank_join launch at the join (none when every bank wrote its own concat slice: dilate + concat).
-int graph_forward(tfl_ctx* c, const tfl_model* m, hipStream_t st, const ModelWs& w, int B, int Z, int Y, int X,
-                  const float* pDiv, const double* st_in, double count) {
+int graph_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a) {
+  net_input(m, w, a, 0, -1);
+  hipStream_t st = a.st;
+  const int B = a.B;
   const int act = 1 + m->opts.nonlin;
   const int nl = (int)m->layers.size();
   const bool mres = m->bank_type == TFL_BANKS_MRES, concat = m->aggregate == TFL_AGG_CONCAT;
   const float* in = w.x3;
-  int Zc = Z, Yc = Y, Xc = X;
+  int Zc = a.Z, Yc = a.Y, Xc = a.X;
   auto none = [&](const tfl_layer& L) { return fail(c, TFL_EUNSUPPORTED, "model_finish: no kernel for %d output channels", L.cout); };
   for (int l = 0; l < nl;) {
     const tfl_layer& L0 = m->layers[l];
@@ -1430,9 +1431,143 @@ int graph_forward(tfl_ctx* c, const tfl_model* m, hipStream_t st, const ModelWs&
                              last ? 0 : act);
     if (!out) return none(L0);
     // addPressureSkip: pDiv/scale becomes the last input channel of the last layer (model.lua:356-360)
-    if (joins_skip) tfl::model_skip_channel(st, B, (long long)Z * Y * X, pDiv, st_in, count, out, L0.cout + 1, L0.cout);
+    if (joins_skip) tfl::model_skip_channel(st, B, (long long)a.Z * a.Y * a.X, a.pDiv, a.st_in, a.count, out, L0.cout + 1, L0.cout);
     in = out;
     l++;
+  }
+  return TFL_OK;
+}
+// tfl_model_opts: the input scale comes from another field / function / not at all. All three reach the kernels through the
+// (stats, count) pair scale_from_stats reads -- sqrt((n s2 - s1^2) / (n (n - 1))): the l2 norm is (s1, s2, n) = (0, sum x^2, 2),
+// "no scaling" is (0, 1, 2). Forms that pair in the model's stats buffer (a.st_in) and a.count. A caller that passes stats has
+// formed it itself (a z-slab rank: over its owned planes, all-reduced -- model_slab_stats).
+int opts_stats(tfl_ctx* c, const tfl_model* m, const ModelWs& w, Fwd& a) {
+  const tfl_model_opts& o = m->opts;
+  const long long cells = (long long)a.Z * a.Y * a.X;
+  const float* field = o.norm_chan == TFL_NORM_PDIV ? a.pDiv : (o.norm_chan == TFL_NORM_DIV ? w.div : a.U);
+  const long long nf = o.norm_chan == TFL_NORM_UDIV ? cells * (m->is3d ? 3 : 2) : cells;
+  if (!o.normalize) { tfl::model_field_stats(a.st, a.B, nf, field, 2, m->d_stats); a.count = 2.0; }
+  else if (o.norm_func == TFL_NORMFUNC_L2) { tfl::model_field_stats(a.st, a.B, nf, field, 1, m->d_stats); a.count = 2.0; }
+  else if (o.norm_chan != TFL_NORM_UDIV) {
+    if (nf < 2) return fail(c, TFL_EINVAL, "model_finish: Sample variance requires more than one sample.");
+    tfl::model_field_stats(a.st, a.B, nf, field, 0, m->d_stats); a.count = (double)nf;
+  }
+  return TFL_OK;
+}
+
+// The 3-D default topology's three forms. Stage bits: 1 = first conv layer, 2 = second, 4 = third + the two 1x1x1 layers.
+// Split-operand fp16 MFMA (conv_mfma16.hip); the two activation buffers hold the "h2" form (32 B per voxel, as 8 fp32).
+// Layers 1 + 2 in one launch where the whole array is computed (round 5); a z-slab rank runs them under separate windows.
+void forward_mfma16(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a) {
+  const bool fused12 = (a.stg & 3) == 3 &&
+                       tfl::conv3_m16_first2_fused(a.st, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0],
+                                                   m->layers[0].b, m->post16[0], m->wfrag16[1], m->layers[1].b, m->post16[1],
+                                                   w.act[1], m->d_range_err);
+  if ((a.stg & 1) && !fused12) {
+    if (c->defer_stats)      // (tfl_model_forward only: whole array, the model's own stats buffer)
+      tfl::conv3_m16_first_fused(a.st, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0], m->layers[0].b,
+                                 m->post16[0], w.act[0], m->d_range_err, w.partials, m->stat_pairs_per_plane * a.Z, m->d_stats);
+    else
+      tfl::conv3_m16_first_fused(a.st, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0], m->layers[0].b,
+                                 m->post16[0], w.act[0], m->d_range_err);
+  }
+  if ((a.stg & 2) && !fused12)
+    tfl::conv3_m16_mid(a.st, a.B, a.Z, a.Y, a.X, w.act[0], m->wfrag16[1], m->layers[1].b, m->post16[1], w.act[1], m->d_range_err);
+  if (a.stg & 4)
+    tfl::conv3_m16_tail(a.st, a.B, a.Z, a.Y, a.X, w.act[1], m->wfrag16[2], m->tail_pack, m->post16[2], w.pPred, m->d_range_err);
+}
+
+// fp32 Winograd on the vector ALUs (conv_valu.hip): the first layer builds {pDiv/scale, div/scale, occupancy} while staging
+// its LDS tile
+void forward_valu(const tfl_model* m, const ModelWs& w, const Fwd& a) {
+  if (a.stg & 1)
+    tfl::conv3_valu_first_fused(a.st, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wino[0], m->layers[0].b, w.act[0]);
+  if (a.stg & 2) tfl::conv3_valu_mid(a.st, a.B, a.Z, a.Y, a.X, w.act[0], m->wino[1], m->layers[1].b, w.act[1]);
+  if (a.stg & 4) tfl::conv3_valu_tail(a.st, a.B, a.Z, a.Y, a.X, w.act[1], m->wino[2], m->tail_pack, w.pPred);
+}
+
+// fp32-operand MFMA (conv_mfma.hip): the first layer builds {pDiv/scale, div/scale, occupancy} while staging its LDS tile
+void forward_mfma(const tfl_model* m, const ModelWs& w, const Fwd& a) {
+  if (a.stg & 1)
+    tfl::conv3_mfma_first_fused(a.st, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->bfrag[0],
+                                m->layers[0].b, w.act[0]);
+  if (a.stg & 2) tfl::conv3_mfma_mid(a.st, a.B, a.Z, a.Y, a.X, w.act[0], m->bfrag[1], m->layers[1].b, w.act[1]);
+  if (a.stg & 4)
+    tfl::conv3_mfma_tail(a.st, a.B, a.Z, a.Y, a.X, w.act[1], m->bfrag[2], m->layers[2].b, m->tail_w4, m->layers[3].b,
+                         m->tail_w5, m->layers[4].b, w.pPred);
+}
+
+// The 2-D default topology (conv2d_mfma.hip), whole grid only
+void forward_mfma2d(const tfl_model* m, const ModelWs& w, const Fwd& a) {
+  tfl::conv2_mfma_first_fused(a.st, a.B, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->bfrag2[0], m->layers[0].b, w.act[0]);
+  tfl::conv2_mfma_mid(a.st, a.B, a.Y, a.X, w.act[0], m->bfrag2[1], m->layers[1].b, w.act[1]);
+  tfl::conv2_mfma_mid(a.st, a.B, a.Y, a.X, w.act[1], m->bfrag2[2], m->layers[2].b, w.act[0]);
+  tfl::conv2_mfma_tail(a.st, a.B, a.Y, a.X, w.act[0], m->bfrag2[3], m->layers[3].b, m->tail_w5, m->layers[4].b, w.pPred);
+}
+
+// Every other linear model, layer by layer on the shape-generic kernels. The planes of every launch: the whole grid, or (a
+// z-window [za, zb) on a 3-D model: a z-slab rank's owned planes) the cone of the planes the velocity update reads, layer by
+// layer (model_cone).
+int generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a) {
+  hipStream_t st = a.st;
+  const int B = a.B, Z = a.Z, Y = a.Y, X = a.X;
+  const bool windowed = a.windowed;
+  if (m->multires && ((m->is3d && Z % m->max_down) || Y % m->max_down || X % m->max_down))
+    return fail(c, TFL_EINVAL, "model_finish: grid %dx%dx%d is not divisible by the model's pooling factor %d", Z, Y, X, m->max_down);
+  const size_t nl = m->layers.size();
+  tfl::ModelCone cone;
+  int za = 0, zb = Z;
+  if (windowed) {
+    const char* why = nullptr;
+    if (!tfl::model_cone(m, &cone, &why)) return fail(c, TFL_EUNSUPPORTED, "model_finish: %s", why);
+    if (c->zwin.b1 > c->zwin.b0) return fail(c, TFL_EINVAL, "model_finish: the shape-generic forward takes one z-window run");
+    za = std::max(c->zwin.a0, 0); zb = std::min(c->zwin.a1, Z);
+    if (za % cone.F || zb % cone.F)
+      return fail(c, TFL_EINVAL, "model_finish: z-window [%d, %d) is not aligned to the model's downsampling factor %d", za, zb, cone.F);
+  }
+  auto span = [&](int lo, int hi, int dd, int Zd, int& z0, int& nz) {     // planes [za/dd - lo, zb/dd + hi) of a Zd-deep level
+    if (!windowed) { z0 = 0; nz = Zd; return; }
+    const int a = std::max(za / dd - lo, 0), b = std::min(zb / dd + hi, Zd);
+    z0 = a; nz = b > a ? b - a : 0;
+  };
+  int z0, nz;
+  if (windowed) span(cone.in_lo, cone.in_hi, 1, Z, z0, nz); else { z0 = 0; nz = -1; }
+  net_input(m, w, a, z0, nz);
+  const int act = 1 + m->opts.nonlin;            // conv_direct: 1 ReLU, 2 ReLU6, 3 sigmoid
+  const float* in = w.x3;
+  int Zc = Z, Yc = Y, Xc = X;     // resolution of `in`
+  for (size_t l = 0; l < nl; l++) {
+    const tfl_layer& L = m->layers[l];
+    const bool last = l + 1 == nl;
+    const bool joins_skip = m->opts.pressure_skip && l + 2 == nl;
+    float* out = last ? w.pPred : (in == w.act[0] ? w.act[1] : w.act[0]);
+    const int taps = m->is3d ? L.k * L.k * L.k : L.k * L.k;
+    const int S = m->is3d ? L.up * L.up * L.up : L.up * L.up;
+    if (windowed) span(cone.layer[l].conv_lo, cone.layer[l].conv_hi, cone.layer[l].conv_d, Zc, z0, nz);
+    for (int sub = 0; sub < S; sub++)      // ConvolutionUpsample: one strided-store convolution per sub-position
+      if (!tfl::conv_direct(st, m->is3d, B, Zc, Yc, Xc, L.cin, L.cout, L.k, last ? 0 : act, in,
+                            L.w + (size_t)sub * taps * L.cin * L.cout, L.b + (size_t)sub * L.cout, out, L.up, sub,
+                            joins_skip ? L.cout + 1 : 0, z0, nz))
+        return fail(c, TFL_EUNSUPPORTED, "model_finish: no kernel for %d output channels", L.cout);
+    // addPressureSkip: pDiv/scale becomes the last input channel of the last layer (model.lua:356-360); windowed: on the
+    // planes the last layer reads (the skip needs a full-resolution net, so they are at the grid's resolution)
+    if (joins_skip) {
+      long long t0 = 0, nt = -1;
+      if (windowed) { span(cone.layer[nl - 1].in_lo, cone.layer[nl - 1].in_hi, 1, Z, z0, nz); t0 = (long long)z0 * Y * X; nt = (long long)nz * Y * X; }
+      tfl::model_skip_channel(st, B, (long long)Z * Y * X, a.pDiv, a.st_in, a.count, out, L.cout + 1, L.cout, t0, nt);
+    }
+    if (m->is3d) Zc *= L.up;
+    Yc *= L.up; Xc *= L.up;
+    in = out;
+    if (L.pool > 1) {
+      float* pooled = in == w.act[0] ? w.act[1] : w.act[0];
+      if (windowed) span(cone.layer[l].pool_lo, cone.layer[l].pool_hi, 2 * cone.layer[l].conv_d, Zc / 2, z0, nz);
+      else { z0 = 0; nz = -1; }
+      tfl::avg_pool2(st, m->is3d, B * L.cout, Zc, Yc, Xc, in, pooled, z0, nz);
+      if (m->is3d) Zc /= 2;
+      Yc /= 2; Xc /= 2;
+      in = pooled;
+    }
   }
   return TFL_OK;
 }
@@ -1456,160 +1591,34 @@ int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl
   if (!(count > 1.0)) return fail(c, TFL_EINVAL, "model_finish: Sample variance requires more than one sample.");
   ModelWs w;
   TRY(model_ws(c, m, flags, workspace, workspace_floats, &w));
-  const int B = flags->B, Z = flags->Z, Y = flags->Y, X = flags->X;
-  const double* st_in = stats ? stats : m->d_stats;
-  hipStream_t st = c->stream;
   TRY(graph_gate(c, m, flags, "model_finish"));
-  if (m->graph && (stats || c->stages || c->zwin.a1 > c->zwin.a0 || c->zwin.b1 > c->zwin.b0))
-    return fail(c, TFL_EUNSUPPORTED, "model_finish: banked, batch-norm and max-pool models run un-sharded only");
   const bool windowed = c->zwin.a1 > c->zwin.a0 || c->zwin.b1 > c->zwin.b0;
+  if (m->path == ConvPath::graph && (stats || c->stages || windowed))
+    return fail(c, TFL_EUNSUPPORTED, "model_finish: banked, batch-norm and max-pool models run un-sharded only");
   if (m->custom && !stats && (c->stages || windowed))
     return fail(c, TFL_EUNSUPPORTED, "model_finish: a windowed forward of a model with non-default tfl_model_opts takes the caller's "
                                      "input-scale stats over the owned planes (tfl_simulate_step_slab forms them)");
-  if (m->custom && !stats) {
-    // tfl_model_opts: the input scale comes from another field / function / not at all. All three reach the kernels
-    // through the (stats, count) pair scale_from_stats reads -- sqrt((n s2 - s1^2) / (n (n - 1))): the l2 norm is
-    // (s1, s2, n) = (0, sum x^2, 2), "no scaling" is (0, 1, 2). A caller that passes stats has formed that pair itself
-    // (a z-slab rank: over its owned planes, all-reduced -- model_slab_stats).
-    const tfl_model_opts& o = m->opts;
-    const long long cells = (long long)Z * Y * X;
-    const float* field = o.norm_chan == TFL_NORM_PDIV ? pDiv->data : (o.norm_chan == TFL_NORM_DIV ? w.div : UOut->data);
-    const long long nf = o.norm_chan == TFL_NORM_UDIV ? cells * (m->is3d ? 3 : 2) : cells;
-    if (!o.normalize) { tfl::model_field_stats(st, B, nf, field, 2, m->d_stats); count = 2.0; }
-    else if (o.norm_func == TFL_NORMFUNC_L2) { tfl::model_field_stats(st, B, nf, field, 1, m->d_stats); count = 2.0; }
-    else if (o.norm_chan != TFL_NORM_UDIV) {
-      if (nf < 2) return fail(c, TFL_EINVAL, "model_finish: Sample variance requires more than one sample.");
-      tfl::model_field_stats(st, B, nf, field, 0, m->d_stats); count = (double)nf;
-    }
-  }
+  Fwd a{c->stream, flags->B, flags->Z, flags->Y, flags->X, pDiv->data, UOut->data, flags->data, stats ? stats : m->d_stats,
+        count, 0, windowed};
+  if (m->custom && !stats) TRY(opts_stats(c, m, w, a));
   WindowScope win(c);
-  // tfl_set_stages (z-slab ranks run each layer under its own z-window): 1 = first conv layer, 2 = second, 4 = third
-  // + the two 1x1x1 layers, 8 = velocity update / un-scale / wall BCs on the 3-D default topology's fused kernels. The other
-  // 3-D models (the shape-generic forward): 1 = the whole net, each launch on its layer's cone of the z-window's planes
-  // (DESIGN.md 6d), 8 = velocity update / un-scale / wall BCs on the window.
-  const int stg = stages_of(c);
-  const bool generic3 = m->is3d && !m->mfma3d && !m->graph;
-  if (c->stages && !m->mfma3d && !generic3)
+  // tfl_set_stages (z-slab ranks run each layer under its own z-window): the 3-D default topology's forms take stage bits 1,
+  // 2 and 4 (see there); the other 3-D linear models take 1 = the whole net, each launch on its layer's cone of the
+  // z-window's planes. 8 = velocity update / un-scale / wall BCs on the window.
+  a.stg = stages_of(c);
+  if (c->stages && !default3(m->path) && !(m->path == ConvPath::generic && m->is3d))
     return fail(c, TFL_EUNSUPPORTED, "model_finish: stage masks need a 3-D model that is not a graph model");
-  if (m->mfma3d && m->m16) {
-    // split-operand fp16 MFMA (conv_mfma16.hip); the two activation buffers hold the "h2" form (32 B per voxel, as 8 fp32)
-    // layers 1 + 2 in one launch where the whole array is computed (round 5); a z-slab rank runs them under separate windows
-    const bool fused12 = (stg & 3) == 3 &&
-                         tfl::conv3_m16_first2_fused(st, B, Z, Y, X, pDiv->data, w.div, flags->data, st_in, count, m->wfrag16[0],
-                                                     m->layers[0].b, m->post16[0], m->wfrag16[1], m->layers[1].b, m->post16[1],
-                                                     w.act[1], m->d_range_err);
-    if ((stg & 1) && !fused12) {
-      if (c->defer_stats)      // (tfl_model_forward only: whole array, the model's own stats buffer)
-        tfl::conv3_m16_first_fused(st, B, Z, Y, X, pDiv->data, w.div, flags->data, st_in, count, m->wfrag16[0], m->layers[0].b,
-                                   m->post16[0], w.act[0], m->d_range_err, w.partials, m->stat_pairs_per_plane * Z, m->d_stats);
-      else
-        tfl::conv3_m16_first_fused(st, B, Z, Y, X, pDiv->data, w.div, flags->data, st_in, count, m->wfrag16[0], m->layers[0].b,
-                                   m->post16[0], w.act[0], m->d_range_err);
-    }
-    if ((stg & 2) && !fused12)
-      tfl::conv3_m16_mid(st, B, Z, Y, X, w.act[0], m->wfrag16[1], m->layers[1].b, m->post16[1], w.act[1], m->d_range_err);
-    if (stg & 4)
-      tfl::conv3_m16_tail(st, B, Z, Y, X, w.act[1], m->wfrag16[2], m->tail_pack, m->post16[2], w.pPred, m->d_range_err);
-  } else if (m->mfma3d && m->valu3d) {
-    // the first layer builds {pDiv/scale, div/scale, occupancy} while staging its LDS tile
-    if (stg & 1)
-      tfl::conv3_valu_first_fused(st, B, Z, Y, X, pDiv->data, w.div, flags->data, st_in, count, m->wino[0], m->layers[0].b, w.act[0]);
-    if (stg & 2) tfl::conv3_valu_mid(st, B, Z, Y, X, w.act[0], m->wino[1], m->layers[1].b, w.act[1]);
-    if (stg & 4)
-      tfl::conv3_valu_tail(st, B, Z, Y, X, w.act[1], m->wino[2], m->tail_pack, w.pPred);
-  } else if (m->mfma3d) {
-    // the first MFMA layer builds {pDiv/scale, div/scale, occupancy} while staging its LDS tile
-    if (stg & 1)
-      tfl::conv3_mfma_first_fused(st, B, Z, Y, X, pDiv->data, w.div, flags->data, st_in, count, m->bfrag[0],
-                                  m->layers[0].b, w.act[0]);
-    if (stg & 2) tfl::conv3_mfma_mid(st, B, Z, Y, X, w.act[0], m->bfrag[1], m->layers[1].b, w.act[1]);
-    if (stg & 4)
-      tfl::conv3_mfma_tail(st, B, Z, Y, X, w.act[1], m->bfrag[2], m->layers[2].b, m->tail_w4, m->layers[3].b,
-                           m->tail_w5, m->layers[4].b, w.pPred);
-  } else if (m->mfma2d) {
-    tfl::conv2_mfma_first_fused(st, B, Y, X, pDiv->data, w.div, flags->data, st_in, count, m->bfrag2[0],
-                                m->layers[0].b, w.act[0]);
-    tfl::conv2_mfma_mid(st, B, Y, X, w.act[0], m->bfrag2[1], m->layers[1].b, w.act[1]);
-    tfl::conv2_mfma_mid(st, B, Y, X, w.act[1], m->bfrag2[2], m->layers[2].b, w.act[0]);
-    tfl::conv2_mfma_tail(st, B, Y, X, w.act[0], m->bfrag2[3], m->layers[3].b, m->tail_w5, m->layers[4].b, w.pPred);
-  } else if (m->graph) {
-    if (m->custom)
-      tfl::model_net_input_gen(st, m->is3d, B, Z, Y, X, m->opts.in_pDiv, m->opts.in_UDiv, m->opts.in_div, pDiv->data,
-                               UOut->data, w.div, flags->data, st_in, count, w.x3);
-    else
-      tfl::model_net_input(st, m->is3d, B, Z, Y, X, pDiv->data, w.div, flags->data, st_in, count, w.x3);
-    TRY(graph_forward(c, m, st, w, B, Z, Y, X, pDiv->data, st_in, count));
-  } else if (stg & 1) {
-    if (m->multires && ((m->is3d && Z % m->max_down) || Y % m->max_down || X % m->max_down))
-      return fail(c, TFL_EINVAL, "model_finish: grid %dx%dx%d is not divisible by the model's pooling factor %d", Z, Y, X, m->max_down);
-    const size_t nl = m->layers.size();
-    if (m->opts.pressure_skip && (m->layers[nl - 1].pool > 1 || m->layers[nl - 1].up > 1 || m->layers[nl - 2].pool > 1 ||
-                                  m->layers[nl - 2].up > 1 || (nl > 2 && m->multires)))
-      return fail(c, TFL_EUNSUPPORTED, "model_finish: addPressureSkip with pooling / upsampling layers");
-    // the planes of every launch: the whole grid, or (a z-window [za, zb) on a 3-D model: a z-slab rank's owned planes) the
-    // cone of the planes the velocity update reads, layer by layer (model_cone)
-    tfl::ModelCone cone;
-    int za = 0, zb = Z;
-    if (windowed) {
-      const char* why = nullptr;
-      if (!tfl::model_cone(m, &cone, &why)) return fail(c, TFL_EUNSUPPORTED, "model_finish: %s", why);
-      if (c->zwin.b1 > c->zwin.b0) return fail(c, TFL_EINVAL, "model_finish: the shape-generic forward takes one z-window run");
-      za = std::max(c->zwin.a0, 0); zb = std::min(c->zwin.a1, Z);
-      if (za % cone.F || zb % cone.F)
-        return fail(c, TFL_EINVAL, "model_finish: z-window [%d, %d) is not aligned to the model's downsampling factor %d", za, zb, cone.F);
-    }
-    auto span = [&](int lo, int hi, int dd, int Zd, int& z0, int& nz) {     // planes [za/dd - lo, zb/dd + hi) of a Zd-deep level
-      if (!windowed) { z0 = 0; nz = Zd; return; }
-      const int a = std::max(za / dd - lo, 0), b = std::min(zb / dd + hi, Zd);
-      z0 = a; nz = b > a ? b - a : 0;
-    };
-    int z0, nz;
-    if (windowed) span(cone.in_lo, cone.in_hi, 1, Z, z0, nz); else { z0 = 0; nz = -1; }
-    if (m->custom)
-      tfl::model_net_input_gen(st, m->is3d, B, Z, Y, X, m->opts.in_pDiv, m->opts.in_UDiv, m->opts.in_div, pDiv->data,
-                               UOut->data, w.div, flags->data, st_in, count, w.x3, z0, nz);
-    else
-      tfl::model_net_input(st, m->is3d, B, Z, Y, X, pDiv->data, w.div, flags->data, st_in, count, w.x3, z0, nz);
-    const int act = 1 + m->opts.nonlin;            // conv_direct: 1 ReLU, 2 ReLU6, 3 sigmoid
-    const float* in = w.x3;
-    int Zc = Z, Yc = Y, Xc = X;     // resolution of `in`
-    for (size_t l = 0; l < m->layers.size(); l++) {
-      const tfl_layer& L = m->layers[l];
-      const bool last = l + 1 == m->layers.size();
-      const bool joins_skip = m->opts.pressure_skip && l + 2 == m->layers.size();
-      float* out = last ? w.pPred : (in == w.act[0] ? w.act[1] : w.act[0]);
-      const int taps = m->is3d ? L.k * L.k * L.k : L.k * L.k;
-      const int S = m->is3d ? L.up * L.up * L.up : L.up * L.up;
-      if (windowed) span(cone.layer[l].conv_lo, cone.layer[l].conv_hi, cone.layer[l].conv_d, Zc, z0, nz);
-      for (int sub = 0; sub < S; sub++)      // ConvolutionUpsample: one strided-store convolution per sub-position
-        if (!tfl::conv_direct(st, m->is3d, B, Zc, Yc, Xc, L.cin, L.cout, L.k, last ? 0 : act, in,
-                              L.w + (size_t)sub * taps * L.cin * L.cout, L.b + (size_t)sub * L.cout, out, L.up, sub,
-                              joins_skip ? L.cout + 1 : 0, z0, nz))
-          return fail(c, TFL_EUNSUPPORTED, "model_finish: no kernel for %d output channels", L.cout);
-      // addPressureSkip: pDiv/scale becomes the last input channel of the last layer (model.lua:356-360); windowed: on the
-      // planes the last layer reads (the skip needs a full-resolution net, so they are at the grid's resolution)
-      if (joins_skip) {
-        long long t0 = 0, nt = -1;
-        if (windowed) { span(cone.layer[nl - 1].in_lo, cone.layer[nl - 1].in_hi, 1, Z, z0, nz); t0 = (long long)z0 * Y * X; nt = (long long)nz * Y * X; }
-        tfl::model_skip_channel(st, B, (long long)Z * Y * X, pDiv->data, st_in, count, out, L.cout + 1, L.cout, t0, nt);
-      }
-      if (m->is3d) Zc *= L.up;
-      Yc *= L.up; Xc *= L.up;
-      in = out;
-      if (L.pool > 1) {
-        float* pooled = in == w.act[0] ? w.act[1] : w.act[0];
-        if (windowed) span(cone.layer[l].pool_lo, cone.layer[l].pool_hi, 2 * cone.layer[l].conv_d, Zc / 2, z0, nz);
-        else { z0 = 0; nz = -1; }
-        tfl::avg_pool2(st, m->is3d, B * L.cout, Zc, Yc, Xc, in, pooled, z0, nz);
-        if (m->is3d) Zc /= 2;
-        Yc /= 2; Xc /= 2;
-        in = pooled;
-      }
-    }
+  switch (m->path) {
+    case ConvPath::conv_mfma16: forward_mfma16(c, m, w, a); break;
+    case ConvPath::conv_valu: forward_valu(m, w, a); break;
+    case ConvPath::conv_mfma: forward_mfma(m, w, a); break;
+    case ConvPath::conv2d_mfma: forward_mfma2d(m, w, a); break;
+    case ConvPath::generic: if (a.stg & 1) TRY(generic_forward(c, m, w, a)); break;
+    case ConvPath::graph: TRY(graph_forward(c, m, w, a)); break;
   }
-  if (stg & 8) {
-    const bool folded = tfl::model_project(st, m->is3d, B, Z, Y, X, w.pPred, flags->data, st_in, count, UOut->data, pOut->data,
-                                           UBC ? UBC->data : nullptr, UBC ? UBCInvMask->data : nullptr, doClamp, lo, hi,
+  if (a.stg & 8) {
+    const bool folded = tfl::model_project(a.st, m->is3d, a.B, a.Z, a.Y, a.X, w.pPred, flags->data, a.st_in, a.count, UOut->data,
+                                           pOut->data, UBC ? UBC->data : nullptr, UBC ? UBCInvMask->data : nullptr, doClamp, lo, hi,
                                            m->d_range_host ? m->d_range_err : nullptr, m->d_range_host,
                                            c->reach_sink ? c->d_reach : nullptr, c->reach_sink ? c->d_reach_host : nullptr,
                                            c->reach_sink ? c->d_reach : nullptr, wall_code_of(c, m, flags),
@@ -1629,7 +1638,7 @@ int tfl_model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tf
   // round 6: with the default 3-D conv path the first layer's blocks sum k_bcs_div_stats' partial pairs themselves (the same
   // order, the same bits) -- no k_reduce_stats launch between the two kernels (4.3 us of pure latency at 128^3)
   struct Defer { tfl_ctx* c; ~Defer() { c->defer_stats = false; } } defer{c};
-  c->defer_stats = m && m->mfma3d && m->m16 && !m->custom && tfl::conv3_m16_first_sums_partials() &&
+  c->defer_stats = m && m->path == ConvPath::conv_mfma16 && tfl::conv3_m16_first_sums_partials() &&
                    !tfl::conv3_m16_fuse12_requested() && !tfl::model_stats_fold_requested();
   TRY(tfl_model_begin(c, m, UDiv, flags, UOut, workspace, workspace_floats, 0, flags->Z, nullptr));
   const double count = (double)flags->Z * flags->Y * flags->X * (m->is3d ? 3 : 2);
