@@ -81,6 +81,7 @@ struct tfl_model {
 };
 
 #include "tfl_ctx.hpp"
+#include "tfl_ops.hpp"
 static const int kMaxBatch = 1024;
 
 // ---- per-kernel event profiler (TFL_TIMED in the launchers) ---------------------------------------
@@ -88,10 +89,6 @@ namespace tfl {
 thread_local ZWin g_zwin = {0, 0, 0, 0};
 thread_local ZOrigin g_zorigin = {0, 0};
 thread_local int g_advect_fast = 0;
-thread_local BcFoldArg g_fold = {nullptr, 0u, 0u};
-thread_local bool g_fold_done = false;
-thread_local BuoyFold g_buoy = {nullptr, 0.0f, 0.0f, 0.0f};
-thread_local bool g_buoy_done = false;
 struct ProfRec { const char* name; hipEvent_t e0, e1; };
 struct Profiler { std::vector<ProfRec> recs; };
 static thread_local Profiler* g_prof = nullptr;
@@ -226,22 +223,9 @@ int check_scalar(tfl_ctx* ctx, const char* op, const char* name, const tfl_tenso
 // Operators that honour tfl_set_z_window open one of these before launching: the launchers read the window from the
 // calling thread (tfl_host.hpp make_dom); it is cleared again on the way out so that every other operator -- and every
 // other context used from this thread -- sees the whole array.
-// The same scope carries tfl_simulate_step's setConstVals request (tfl_host.hpp BcFold) to the launchers and the
-// acknowledgement back into the context.
 struct WindowScope {
-  explicit WindowScope(tfl_ctx* c) : c_(c) {
-    tfl::g_zwin = c->zwin; tfl::g_zorigin = c->zorigin; tfl::g_advect_fast = c->advect_fast;
-    tfl::g_fold = c->fold; tfl::g_fold_done = false;
-    tfl::g_buoy = c->buoy; tfl::g_buoy_done = false;
-  }
-  ~WindowScope() {
-    tfl::g_zwin = tfl::ZWin{0, 0, 0, 0}; tfl::g_zorigin = tfl::ZOrigin{0, 0}; tfl::g_advect_fast = 0;
-    c_->fold_done = c_->fold_done || tfl::g_fold_done;
-    tfl::g_fold = tfl::no_fold(); tfl::g_fold_done = false;
-    c_->buoy_done = c_->buoy_done || tfl::g_buoy_done;
-    tfl::g_buoy = tfl::no_buoy(); tfl::g_buoy_done = false;
-  }
-  tfl_ctx* c_;
+  explicit WindowScope(const tfl_ctx* c) { tfl::g_zwin = c->zwin; tfl::g_zorigin = c->zorigin; tfl::g_advect_fast = c->advect_fast; }
+  ~WindowScope() { tfl::g_zwin = tfl::ZWin{0, 0, 0, 0}; tfl::g_zorigin = tfl::ZOrigin{0, 0}; tfl::g_advect_fast = 0; }
 };
 int stages_of(const tfl_ctx* c) { return c->stages ? c->stages : 0xff; }
 
@@ -407,10 +391,12 @@ int64_t tfl_trace_errors(tfl_ctx* c) {
   return (int64_t)v;
 }
 
-int tfl_advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags,
-                     const tfl_tensor* fwd, const tfl_tensor* bwd, int is3D, const char* method,
-                     const tfl_tensor* fwdPos, const tfl_tensor* bwdPos, int boundaryWidth, int sampleOutsideFluid,
-                     float maccormackStrength, const tfl_tensor* sDst) {
+}  // extern "C"
+// The operators a native step calls with a request (tfl_ops.hpp); the public tfl_* forms pass an empty one.
+namespace tfl {
+int advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* fwd,
+                 const tfl_tensor* bwd, int is3D, const char* method, const tfl_tensor* fwdPos, const tfl_tensor* bwdPos,
+                 int boundaryWidth, int sampleOutsideFluid, float maccormackStrength, const tfl_tensor* sDst, Ask& ask) {
   (void)bwd; (void)boundaryWidth;  // bnd = 1 like the reference (tfluids.cc:436,467)
   TRY(check_flags(c, "advectScalar", flags));
   TRY(check_vel(c, "advectScalar", "U", U, flags, is3D));
@@ -438,13 +424,12 @@ int tfl_advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor
   WindowScope win(c);
   tfl::advect_scalar(c->stream, is3D != 0, m, flags->B, flags->Z, flags->Y, flags->X, dt, maccormackStrength,
                      sampleOutsideFluid != 0, c->d_trace_err, s->data, U->data, flags->data, fwd_p, bounds_p, mm_p,
-                     sDst->data, stages_of(c));
+                     sDst->data, stages_of(c), ask.fold);
   return check_launch(c, "advectScalar");
 }
 
-int tfl_advectVel(tfl_ctx* c, float dt, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* fwd,
-                  const tfl_tensor* bwd, int is3D, const char* method, int boundaryWidth, float maccormackStrength,
-                  const tfl_tensor* UDst) {
+int advectVel(tfl_ctx* c, float dt, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* fwd, const tfl_tensor* bwd,
+              int is3D, const char* method, int boundaryWidth, float maccormackStrength, const tfl_tensor* UDst, Ask& ask) {
   (void)bwd; (void)boundaryWidth;
   TRY(check_flags(c, "advectVel", flags));
   TRY(check_vel(c, "advectVel", "U", U, flags, is3D));
@@ -459,17 +444,12 @@ int tfl_advectVel(tfl_ctx* c, float dt, const tfl_tensor* U, const tfl_tensor* f
   }
   WindowScope win(c);
   tfl::advect_vel(c->stream, is3D != 0, m, flags->B, flags->Z, flags->Y, flags->X, dt, maccormackStrength,
-                  c->d_trace_err, U->data, flags->data, fwd_p, UDst->data, stages_of(c));
+                  c->d_trace_err, U->data, flags->data, fwd_p, UDst->data, stages_of(c), ask.fold);
   return check_launch(c, "advectVel");
 }
 
-}  // extern "C"
-// Library-internal (simulate.cpp's z-slab step; C++ linkage): the MacCormack(Ours) advection of one density channel AND of the
-// velocity on a 3-D grid, their passes A as one launch (stage bit 2) and their passes B as one launch (stage bit 4) --
-// advect_pair3.hip. Honours the z-window / z-origin / advect mode of the context like the two operators. fold_s / fold_v: the
-// setConstVals pairs the passes B apply (tfl_host.hpp BcFold; dev == nullptr: none). TFL_EUNSUPPORTED = not taken, nothing
-// launched: the caller runs tfl_advectScalar and tfl_advectVel.
-namespace tfl {
+// (the z-slab step: both advections' passes A / passes B as one launch each, tfl_ops.hpp) Honours the z-window / z-origin /
+// advect mode of the context like the two operators.
 int advect_pair(tfl_ctx* c, float dt, float strength, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags,
                 const tfl_tensor* sfwd, const tfl_tensor* sbounds, const tfl_tensor* sDst, const tfl_tensor* vfwd, const tfl_tensor* UDst,
                 const BcFoldArg& fold_s, const BcFoldArg& fold_v) {
@@ -492,6 +472,22 @@ int advect_pair(tfl_ctx* c, float dt, float strength, const tfl_tensor* s, const
 }
 }  // namespace tfl
 extern "C" {
+
+int tfl_advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags,
+                     const tfl_tensor* fwd, const tfl_tensor* bwd, int is3D, const char* method,
+                     const tfl_tensor* fwdPos, const tfl_tensor* bwdPos, int boundaryWidth, int sampleOutsideFluid,
+                     float maccormackStrength, const tfl_tensor* sDst) {
+  tfl::Ask none;
+  return tfl::advectScalar(c, dt, s, U, flags, fwd, bwd, is3D, method, fwdPos, bwdPos, boundaryWidth, sampleOutsideFluid,
+                           maccormackStrength, sDst, none);
+}
+
+int tfl_advectVel(tfl_ctx* c, float dt, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* fwd,
+                  const tfl_tensor* bwd, int is3D, const char* method, int boundaryWidth, float maccormackStrength,
+                  const tfl_tensor* UDst) {
+  tfl::Ask none;
+  return tfl::advectVel(c, dt, U, flags, fwd, bwd, is3D, method, boundaryWidth, maccormackStrength, UDst, none);
+}
 
 int tfl_setWallBcsForward(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, int is3D) {
   TRY(check_flags(c, "setWallBcsForward", flags));
@@ -519,9 +515,10 @@ int tfl_velocityUpdateForward(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor*
   return check_launch(c, "velocityUpdateForward");
 }
 
-int tfl_vorticityConfinement(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, float strength,
-                             const tfl_tensor* centered, const tfl_tensor* curl, const tfl_tensor* curlNorm,
-                             const tfl_tensor* force, int is3D) {
+}  // extern "C"
+namespace tfl {      // (tfl_ops.hpp)
+int vorticityConfinement(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, float strength, const tfl_tensor* centered,
+                         const tfl_tensor* curl, const tfl_tensor* curlNorm, const tfl_tensor* force, int is3D, Ask& ask) {
   (void)centered; (void)force;  // fused away (vorticity.hip)
   TRY(check_flags(c, "vorticityConfinement", flags));
   TRY(check_vel(c, "vorticityConfinement", "U", U, flags, is3D));
@@ -531,12 +528,12 @@ int tfl_vorticityConfinement(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* 
   WindowScope win(c);
   const int stg = stages_of(c);   // tfl_set_stages: 2 = pass A (curl), 4 = pass B (confinement force)
   tfl::vorticity_confinement(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data,
-                             strength, curl->data, curlNorm->data, ((stg & 2) ? 1 : 0) | ((stg & 4) ? 2 : 0));
+                             strength, curl->data, curlNorm->data, ((stg & 2) ? 1 : 0) | ((stg & 4) ? 2 : 0), nullptr, ask.fold);
   return check_launch(c, "vorticityConfinement");
 }
 
-int tfl_vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, float strength,
-                                 const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D) {
+int vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, float strength,
+                             const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D, Ask& ask) {
   TRY(check_flags(c, "vorticityConfinementFrom", flags));
   TRY(check_vel(c, "vorticityConfinementFrom", "U", U, flags, is3D));
   TRY(check_vel(c, "vorticityConfinementFrom", "USrc", USrc, flags, is3D));
@@ -545,8 +542,8 @@ int tfl_vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_t
     return fail(c, TFL_EINVAL, "vorticityConfinementFrom: curl must be a 3-channel grid of the flags size");
   TRY(check_scalar(c, "vorticityConfinementFrom", "curlNorm", curlNorm, flags));
   WindowScope win(c);
-  if (is3D && !c->vort_from_two_launch && tfl::vorticity_confinement_fused_ok(true, flags->Z, flags->Y, flags->X) &&
-      tfl::vorticity_confinement_fused(c->stream, flags->B, flags->Z, flags->Y, flags->X, USrc->data, U->data, flags->data, strength))
+  if (is3D && !ask.two_launch && tfl::vorticity_confinement_fused_ok(true, flags->Z, flags->Y, flags->X) &&
+      tfl::vorticity_confinement_fused(c->stream, flags->B, flags->Z, flags->Y, flags->X, USrc->data, U->data, flags->data, strength, ask.fold))
     return check_launch(c, "vorticityConfinementFrom");
   // 2-D, a grid below the fused kernel's size, or TFL_VORT_FUSED=0: the two launches read USrc and write U (round 5) ...
   // Under a z-window pass A must cover what pass B taps: |curl| two planes below / one above, curl one below -- the
@@ -560,14 +557,14 @@ int tfl_vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_t
     else if (wa.b1 > wa.b0 && wa.b0 <= wa.a1) { wa.a1 = wa.b1; wa.b0 = wa.b1 = 0; }
     tfl::g_zwin = wa;
     const bool a_ok = tfl::vorticity_confinement(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
-                                                 curl->data, curlNorm->data, 1, USrc->data);
+                                                 curl->data, curlNorm->data, 1, USrc->data, ask.fold);
     tfl::g_zwin = w0;
     if (a_ok && tfl::vorticity_confinement(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
-                                           curl->data, curlNorm->data, 2, USrc->data))
+                                           curl->data, curlNorm->data, 2, USrc->data, ask.fold))
       return check_launch(c, "vorticityConfinementFrom");
     if (a_ok) return fail(c, TFL_EUNSUPPORTED, "vorticityConfinementFrom: pass B could not read USrc on this grid under a z-window");
   } else if (tfl::vorticity_confinement(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
-                                        curl->data, curlNorm->data, 3, USrc->data))
+                                        curl->data, curlNorm->data, 3, USrc->data, ask.fold))
     return check_launch(c, "vorticityConfinementFrom");
   if (windowed)      // (the one-cell kernels below run in place on a copy: the same two windows are needed there -- not built)
     return fail(c, TFL_EUNSUPPORTED, "vorticityConfinementFrom: this grid takes the one-cell kernels, which do not run from USrc under a z-window; "
@@ -586,12 +583,12 @@ int tfl_vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_t
       }
   }
   tfl::vorticity_confinement(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
-                             curl->data, curlNorm->data, 3);
+                             curl->data, curlNorm->data, 3, nullptr, ask.fold);
   return check_launch(c, "vorticityConfinementFrom");
 }
 
-int tfl_addBuoyancyFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags,
-                        const tfl_tensor* density, const float gravity[3], float dt, int is3D) {
+int addBuoyancyFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* density,
+                    const float gravity[3], float dt, int is3D, Ask& ask) {
   TRY(check_flags(c, "addBuoyancy", flags));
   TRY(check_vel(c, "addBuoyancy", "U", U, flags, is3D));
   TRY(check_vel(c, "addBuoyancy", "USrc", USrc, flags, is3D));
@@ -600,8 +597,29 @@ int tfl_addBuoyancyFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U,
   const float sc = dt / get_dx(c, flags);  // strength = -gravity * (dt / dx), tfluids.cc:1190-1192
   WindowScope win(c);
   tfl::add_buoyancy(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, USrc->data, U->data, flags->data,
-                    density->data, -gravity[0] * sc, -gravity[1] * sc, -gravity[2] * sc);
+                    density->data, -gravity[0] * sc, -gravity[1] * sc, -gravity[2] * sc, ask.fold);
   return check_launch(c, "addBuoyancy");
+}
+}  // namespace tfl
+extern "C" {
+
+int tfl_vorticityConfinement(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, float strength,
+                             const tfl_tensor* centered, const tfl_tensor* curl, const tfl_tensor* curlNorm,
+                             const tfl_tensor* force, int is3D) {
+  tfl::Ask none;
+  return tfl::vorticityConfinement(c, U, flags, strength, centered, curl, curlNorm, force, is3D, none);
+}
+
+int tfl_vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, float strength,
+                                 const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D) {
+  tfl::Ask none;
+  return tfl::vorticityConfinementFrom(c, USrc, U, flags, strength, curl, curlNorm, is3D, none);
+}
+
+int tfl_addBuoyancyFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags,
+                        const tfl_tensor* density, const float gravity[3], float dt, int is3D) {
+  tfl::Ask none;
+  return tfl::addBuoyancyFrom(c, USrc, U, flags, density, gravity, dt, is3D, none);
 }
 
 int tfl_addBuoyancy(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* density,
@@ -1171,10 +1189,9 @@ int64_t tfl_model_range_flag(tfl_ctx* c, tfl_model* m) {
 // fp32 cuDNN carries on: refuse it until the host has acknowledged the count (tfl_model_range_errors).
 // The word is written by the device whenever the projection of an earlier pass gets there (no synchronisation), so WHICH later
 // call sees it first depends on how far the host runs ahead: the gate is best-effort in time, but it is taken at ONE defined
-// point per unit of work -- the entry of a forward pass, or the entry of tfl_simulate_step[_slab] (which then marks the
-// context `in_step`, so that the model calls inside the step do not refuse half-way through it).
+// point per unit of work -- the entry of a forward pass, or the entry of tfl_simulate_step[_slab] (whose model calls then ask
+// for no gate: tfl_ops.hpp Ask::gated, so that they do not refuse half-way through the step).
 static int range_gate(tfl_ctx* c, tfl_model* m, const char* who) {
-  if (c && c->in_step) return TFL_OK;
   if (m && m->h_range && *(volatile unsigned long long*)m->h_range != 0)
     return fail(c, TFL_ERANGE, "%s: an earlier forward pass of this model clamped activations at the fp16 range (|x| > 65504 after the "
                                "std normalisation: a blown-up simulation); its pressure is not the reference's. Read and reset the count with "
@@ -1258,11 +1275,13 @@ static int graph_gate(tfl_ctx* c, const tfl_model* m, const tfl_tensor* flags, c
   return TFL_OK;
 }
 
-int tfl_model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tensor* flags, const tfl_tensor* UOut,
-                    float* workspace, int64_t workspace_floats, int zlo, int zhi, double* stats) {
+}  // extern "C"
+namespace tfl {      // (tfl_ops.hpp)
+int model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tensor* flags, const tfl_tensor* UOut, float* workspace,
+                int64_t workspace_floats, int zlo, int zhi, double* stats, Ask& ask) {
   TRY(check_flags(c, "model_begin", flags));
   if (!m) return fail(c, TFL_EINVAL, "model_begin: null model");
-  TRY(range_gate(c, m, "model_begin"));
+  if (ask.gated) TRY(range_gate(c, m, "model_begin"));
   const int is3D = m->is3d ? 1 : 0;
   TRY(check_vel(c, "model_begin", "UDiv", UDiv, flags, is3D));
   TRY(check_vel(c, "model_begin", "UOut", UOut, flags, is3D));
@@ -1275,12 +1294,20 @@ int tfl_model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_
   // value gives the identical result (the BC is idempotent).
   WindowScope win(c);
   int stg = stages_of(c);   // tfl_set_stages: 2 = wall BCs + divergence + partial sums, 4 = reduce [zlo, zhi)
-  if (c->defer_stats) stg &= ~4;  // tfl_model_forward: the first conv layer reduces the partials itself (round 6)
+  if (ask.conv1_sums_stats) stg &= ~4;   // tfl_model_forward: the first conv layer reduces the partials itself (round 6)
   m->stat_pairs_per_plane = tfl::model_stat_pairs_per_plane(flags->B, flags->Z, flags->Y, flags->X, UDiv->data, flags->data, UOut->data, w.div);
   const unsigned short* code = wall_code_of(c, m, flags);
   tfl::model_pre(c->stream, m->is3d, flags->B, flags->Z, flags->Y, flags->X, UDiv->data, flags->data, UOut->data,
                  w.div, w.partials, stats ? stats : m->d_stats, zlo, zhi, ((stg & 2) ? 1 : 0) | ((stg & 4) ? 2 : 0), m->d_ticket, code);
   return check_launch(c, "model_begin");
+}
+}  // namespace tfl
+extern "C" {
+
+int tfl_model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tensor* flags, const tfl_tensor* UOut,
+                    float* workspace, int64_t workspace_floats, int zlo, int zhi, double* stats) {
+  tfl::Ask none;
+  return tfl::model_begin(c, m, UDiv, flags, UOut, workspace, workspace_floats, zlo, zhi, stats, none);
 }
 
 tfl_wall_plan* tfl_wall_plan_create(tfl_ctx* c, const tfl_tensor* flags) {
@@ -1332,6 +1359,7 @@ struct Fwd {
   const float *pDiv, *U, *flags;
   const double* st_in; double count;
   int stg; bool windowed;     // windowed: a z-window is set
+  bool conv1_sums_stats;      // tfl_model_forward (whole array, the model's own stats buffer): conv layer 1 sums the partials
 };
 
 // the net input {pDiv/scale, div/scale, occupancy}, or the channels tfl_model_opts selects, into w.x3 on the planes
@@ -1458,13 +1486,13 @@ int opts_stats(tfl_ctx* c, const tfl_model* m, const ModelWs& w, Fwd& a) {
 // The 3-D default topology's three forms. Stage bits: 1 = first conv layer, 2 = second, 4 = third + the two 1x1x1 layers.
 // Split-operand fp16 MFMA (conv_mfma16.hip); the two activation buffers hold the "h2" form (32 B per voxel, as 8 fp32).
 // Layers 1 + 2 in one launch where the whole array is computed (round 5); a z-slab rank runs them under separate windows.
-void forward_mfma16(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a) {
+void forward_mfma16(const tfl_model* m, const ModelWs& w, const Fwd& a) {
   const bool fused12 = (a.stg & 3) == 3 &&
                        tfl::conv3_m16_first2_fused(a.st, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0],
                                                    m->layers[0].b, m->post16[0], m->wfrag16[1], m->layers[1].b, m->post16[1],
                                                    w.act[1], m->d_range_err);
   if ((a.stg & 1) && !fused12) {
-    if (c->defer_stats)      // (tfl_model_forward only: whole array, the model's own stats buffer)
+    if (a.conv1_sums_stats)
       tfl::conv3_m16_first_fused(a.st, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0], m->layers[0].b,
                                  m->post16[0], w.act[0], m->d_range_err, w.partials, m->stat_pairs_per_plane * a.Z, m->d_stats);
     else
@@ -1572,11 +1600,12 @@ int generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd&
   return TFL_OK;
 }
 }  // namespace
+}  // extern "C"
 
-int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* flags,
-                     const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace, int64_t workspace_floats,
-                     const double* stats, double count, const tfl_tensor* UBC, const tfl_tensor* UBCInvMask,
-                     int doClamp, float lo, float hi) {
+namespace tfl {      // (tfl_ops.hpp)
+int model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* flags, const tfl_tensor* pOut,
+                 const tfl_tensor* UOut, float* workspace, int64_t workspace_floats, const double* stats, double count,
+                 const tfl_tensor* UBC, const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, Ask& ask) {
   TRY(check_flags(c, "model_finish", flags));
   if (!m) return fail(c, TFL_EINVAL, "model_finish: null model");
   const int is3D = m->is3d ? 1 : 0;
@@ -1599,7 +1628,7 @@ int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl
     return fail(c, TFL_EUNSUPPORTED, "model_finish: a windowed forward of a model with non-default tfl_model_opts takes the caller's "
                                      "input-scale stats over the owned planes (tfl_simulate_step_slab forms them)");
   Fwd a{c->stream, flags->B, flags->Z, flags->Y, flags->X, pDiv->data, UOut->data, flags->data, stats ? stats : m->d_stats,
-        count, 0, windowed};
+        count, 0, windowed, ask.conv1_sums_stats};
   if (m->custom && !stats) TRY(opts_stats(c, m, w, a));
   WindowScope win(c);
   // tfl_set_stages (z-slab ranks run each layer under its own z-window): the 3-D default topology's forms take stage bits 1,
@@ -1609,7 +1638,7 @@ int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl
   if (c->stages && !default3(m->path) && !(m->path == ConvPath::generic && m->is3d))
     return fail(c, TFL_EUNSUPPORTED, "model_finish: stage masks need a 3-D model that is not a graph model");
   switch (m->path) {
-    case ConvPath::conv_mfma16: forward_mfma16(c, m, w, a); break;
+    case ConvPath::conv_mfma16: forward_mfma16(m, w, a); break;
     case ConvPath::conv_valu: forward_valu(m, w, a); break;
     case ConvPath::conv_mfma: forward_mfma(m, w, a); break;
     case ConvPath::conv2d_mfma: forward_mfma2d(m, w, a); break;
@@ -1617,33 +1646,48 @@ int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl
     case ConvPath::graph: TRY(graph_forward(c, m, w, a)); break;
   }
   if (a.stg & 8) {
-    const bool folded = tfl::model_project(a.st, m->is3d, a.B, a.Z, a.Y, a.X, w.pPred, flags->data, a.st_in, a.count, UOut->data,
-                                           pOut->data, UBC ? UBC->data : nullptr, UBC ? UBCInvMask->data : nullptr, doClamp, lo, hi,
-                                           m->d_range_host ? m->d_range_err : nullptr, m->d_range_host,
-                                           c->reach_sink ? c->d_reach : nullptr, c->reach_sink ? c->d_reach_host : nullptr,
-                                           c->reach_sink ? c->d_reach : nullptr, wall_code_of(c, m, flags),
-                                           c->reach_sink ? c->d_reach_tick : nullptr);
-    if (c->reach_sink) { c->reach_folded = folded; c->reach_issued++; }
+    const bool pub = ask.reach_via_project;
+    ask.reach_folded = tfl::model_project(a.st, m->is3d, a.B, a.Z, a.Y, a.X, w.pPred, flags->data, a.st_in, a.count, UOut->data,
+                                          pOut->data, UBC ? UBC->data : nullptr, UBC ? UBCInvMask->data : nullptr, doClamp, lo, hi,
+                                          m->d_range_host ? m->d_range_err : nullptr, m->d_range_host, pub ? c->d_reach : nullptr,
+                                          pub ? c->d_reach_host : nullptr, pub ? c->d_reach : nullptr, wall_code_of(c, m, flags),
+                                          pub ? c->d_reach_tick : nullptr, ask.fold);
+    ask.reach_published = pub;
   }
   return check_launch(c, "model_finish");
+}
+
+int model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
+                  const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace, int64_t workspace_floats, const tfl_tensor* UBC,
+                  const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, Ask& ask) {
+  TRY(check_flags(c, "model_forward", flags));
+  if (c->stages || c->zwin.a1 > c->zwin.a0 || c->zwin.b1 > c->zwin.b0)
+    return fail(c, TFL_EINVAL, "model_forward: clear the z-window / stage mask first (use tfl_model_begin / _finish)");
+  // round 6: with the default 3-D conv path the first layer's blocks sum k_bcs_div_stats' partial pairs themselves (the same
+  // order, the same bits) -- no k_reduce_stats launch between the two kernels (4.3 us of pure latency at 128^3)
+  ask.conv1_sums_stats = m && m->path == ConvPath::conv_mfma16 && conv3_m16_first_sums_partials() && !conv3_m16_fuse12_requested() &&
+                         !model_stats_fold_requested();
+  TRY(model_begin(c, m, UDiv, flags, UOut, workspace, workspace_floats, 0, flags->Z, nullptr, ask));
+  const double count = (double)flags->Z * flags->Y * flags->X * (m->is3d ? 3 : 2);
+  return model_finish(c, m, pDiv, flags, pOut, UOut, workspace, workspace_floats, nullptr, count, UBC, UBCInvMask, doClamp, lo, hi, ask);
+}
+}  // namespace tfl
+extern "C" {
+
+int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* flags,
+                     const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace, int64_t workspace_floats,
+                     const double* stats, double count, const tfl_tensor* UBC, const tfl_tensor* UBCInvMask,
+                     int doClamp, float lo, float hi) {
+  tfl::Ask none;
+  return tfl::model_finish(c, m, pDiv, flags, pOut, UOut, workspace, workspace_floats, stats, count, UBC, UBCInvMask, doClamp, lo, hi, none);
 }
 
 int tfl_model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* UDiv,
                       const tfl_tensor* flags, const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace,
                       int64_t workspace_floats, const tfl_tensor* UBC, const tfl_tensor* UBCInvMask, int doClamp,
                       float lo, float hi) {
-  TRY(check_flags(c, "model_forward", flags));
-  if (c->stages || c->zwin.a1 > c->zwin.a0 || c->zwin.b1 > c->zwin.b0)
-    return fail(c, TFL_EINVAL, "model_forward: clear the z-window / stage mask first (use tfl_model_begin / _finish)");
-  // round 6: with the default 3-D conv path the first layer's blocks sum k_bcs_div_stats' partial pairs themselves (the same
-  // order, the same bits) -- no k_reduce_stats launch between the two kernels (4.3 us of pure latency at 128^3)
-  struct Defer { tfl_ctx* c; ~Defer() { c->defer_stats = false; } } defer{c};
-  c->defer_stats = m && m->path == ConvPath::conv_mfma16 && tfl::conv3_m16_first_sums_partials() &&
-                   !tfl::conv3_m16_fuse12_requested() && !tfl::model_stats_fold_requested();
-  TRY(tfl_model_begin(c, m, UDiv, flags, UOut, workspace, workspace_floats, 0, flags->Z, nullptr));
-  const double count = (double)flags->Z * flags->Y * flags->X * (m->is3d ? 3 : 2);
-  return tfl_model_finish(c, m, pDiv, flags, pOut, UOut, workspace, workspace_floats, nullptr, count, UBC, UBCInvMask,
-                          doClamp, lo, hi);
+  tfl::Ask none;
+  return tfl::model_forward(c, m, pDiv, UDiv, flags, pOut, UOut, workspace, workspace_floats, UBC, UBCInvMask, doClamp, lo, hi, none);
 }
 
 double tfl_getDx(tfl_ctx* c, const tfl_tensor* flags) {

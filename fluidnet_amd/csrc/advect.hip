@@ -363,14 +363,14 @@ __global__ __launch_bounds__(256) void k_vel_bwd(AdvArgs a, const float* __restr
 // ---- host launchers ----------------------------------------------------------------------------
 template <bool IS3D>
 static void launch_scalar(hipStream_t st, int method, const AdvArgs& a, int B, const float* s, const float* U,
-                          const float* flags, float* fwd, float* bounds, float* mm, float* dst, int stages) {
+                          const float* flags, float* fwd, float* bounds, float* mm, float* dst, int stages, Fold& f) {
   const dim3 blk(64, 4, 1), grd = cell_grid(a.d, B, blk);
   // stages (tfl_set_stages): 1 = the 3^dim min/max grid, 2 = pass A, 4 = pass B; single-pass methods are "pass A"
   const bool pm = stages & 1, pa = stages & 2, pb = stages & 4;
   if (method != kMacCormack && method != kMacCormackOurs && !pa) return;
   // the trace-based methods on a 3-D grid: LDS-tiled fast-path kernels without a min/max grid (advect_scalar3.hip)
   if (IS3D && (method == kEulerOurs || method == kMacCormackOurs) &&
-      advect_scalar3(st, method == kMacCormackOurs, a, B, s, U, flags, fwd, bounds, dst, stages))
+      advect_scalar3(st, method == kMacCormackOurs, a, B, s, U, flags, fwd, bounds, dst, stages, f))
     return;
   switch (method) {
     case kEuler: { TFL_TIMED("k_scalar_fwd", st); k_scalar_fwd<IS3D, kEuler><<<grd, blk, 0, st>>>(a, s, U, flags, dst, nullptr, nullptr, nullptr); break; }
@@ -407,21 +407,21 @@ void minmax3(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int outside,
 
 void advect_scalar(hipStream_t st, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
                    int outside, unsigned long long* err, const float* s, const float* U, const float* flags,
-                   float* fwd, float* bounds, float* mm, float* dst, int stages) {
+                   float* fwd, float* bounds, float* mm, float* dst, int stages, Fold& f) {
   AdvArgs a; a.d = make_dom(Z, Y, X); a.dt = dt; a.strength = strength; a.outside = outside; a.err = err; a.fast = g_advect_fast;
-  if (is3d) launch_scalar<true>(st, method, a, B, s, U, flags, fwd, bounds, mm, dst, stages);
-  else launch_scalar<false>(st, method, a, B, s, U, flags, fwd, bounds, mm, dst, stages);
+  if (is3d) launch_scalar<true>(st, method, a, B, s, U, flags, fwd, bounds, mm, dst, stages, f);
+  else launch_scalar<false>(st, method, a, B, s, U, flags, fwd, bounds, mm, dst, stages, f);
 }
 
 template <bool IS3D>
 static void launch_vel(hipStream_t st, int method, const AdvArgs& a, int B, const float* U, const float* flags,
-                       float* fwd, float* dst, int stages) {
+                       float* fwd, float* dst, int stages, Fold& f) {
   const dim3 blk(64, 4, 1), grd = cell_grid(a.d, B, blk);
   const bool pa = stages & 2, pb = stages & 4;   // as in launch_scalar
   if (method != kMacCormack && method != kMacCormackOurs && !pa) return;
   // the trace-based methods on a 3-D grid: LDS-tiled fast-path kernels (advect_vel3.hip)
   if (IS3D && (method == kEulerOurs || method == kMacCormackOurs) &&
-      advect_vel3(st, method == kMacCormackOurs, a, B, U, flags, fwd, dst, stages))
+      advect_vel3(st, method == kMacCormackOurs, a, B, U, flags, fwd, dst, stages, f))
     return;
   switch (method) {
     case kEuler: { TFL_TIMED("k_vel_fwd", st); k_vel_fwd<IS3D, false><<<grd, blk, 0, st>>>(a, U, flags, dst); break; }
@@ -438,11 +438,11 @@ static void launch_vel(hipStream_t st, int method, const AdvArgs& a, int B, cons
 }
 
 void advect_vel(hipStream_t st, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
-                unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, int stages) {
+                unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, int stages, Fold& f) {
   if (method == kRK2Ours || method == kRK3Ours) method = kMacCormackOurs;  // tfluids.cc:799-802
   AdvArgs a; a.d = make_dom(Z, Y, X); a.dt = dt; a.strength = strength; a.outside = 0; a.err = err; a.fast = g_advect_fast;
-  if (is3d) launch_vel<true>(st, method, a, B, U, flags, fwd, dst, stages);
-  else launch_vel<false>(st, method, a, B, U, flags, fwd, dst, stages);
+  if (is3d) launch_vel<true>(st, method, a, B, U, flags, fwd, dst, stages, f);
+  else launch_vel<false>(st, method, a, B, U, flags, fwd, dst, stages, f);
 }
 
 }  // namespace tfl

@@ -468,7 +468,7 @@ void launch_b(hipStream_t st, const AdvArgs& a, int B, const float* s, const flo
 
 template <bool FAST>
 void launch(hipStream_t st, int shape, bool two_pass, const AdvArgs& a, int B, const float* s, const float* U, const float* flags,
-            float* fwd, float* bounds, float* dst, int stages) {
+            float* fwd, float* bounds, float* dst, int stages, Fold& f) {
   const bool pa = stages & 2, pb = two_pass && (stages & 4);
   float* outA = two_pass ? fwd : dst;
   // Block shapes (threads in z x planes per thread), measured at 128^3 / 256^3 (profiles/r04_advect_experiments.txt 9):
@@ -482,7 +482,7 @@ void launch(hipStream_t st, int shape, bool two_pass, const AdvArgs& a, int B, c
     case 14: launch_a<1, 4, FAST>(st, two_pass, a, B, s, U, flags, outA, bounds); break;
     default: launch_a<2, 1, FAST>(st, two_pass, a, B, s, U, flags, outA, bounds); break;
   }
-  const BcFoldArg fold = pb ? take_fold() : no_fold();   // pass B writes the operator's result
+  const BcFoldArg fold = pb ? f.hand_bc() : no_fold();   // pass B writes the operator's result
   if (pb) switch (sb) {
     case 1:  launch_b<1, 1, FAST>(st, a, B, s, U, flags, fwd, bounds, dst, fold); break;
     case 2:  launch_b<2, 1, FAST>(st, a, B, s, U, flags, fwd, bounds, dst, fold); break;
@@ -495,7 +495,7 @@ void launch(hipStream_t st, int shape, bool two_pass, const AdvArgs& a, int B, c
 
 #ifndef TFL_SCAL3_NO_ENTRY      // (advect_pair3.hip includes this file for the kernels' bodies only)
 bool advect_scalar3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* s, const float* U, const float* flags,
-                    float* fwd, float* bounds, float* dst, int stages) {
+                    float* fwd, float* bounds, float* dst, int stages, Fold& f) {
   static const bool off = exp_env("TFL_ADVECT_GATHER") != nullptr || exp_env("TFL_SCALAR_GATHER") != nullptr;   // A/B switch: the round-2 gather kernels
   static const int tzsel = getenv("TFL_SCAL3_TZ") ? atoi(getenv("TFL_SCAL3_TZ")) : 0;   // 0 = per pass and grid size (launch)
   const Dom& d = a.d;
@@ -508,13 +508,13 @@ bool advect_scalar3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, cons
   // staging bookkeeping make the marched stream LONGER per cell (345 against 274 vector instructions in pass A)
   static const bool march = getenv("TFL_SCAL3_MARCH") && atoi(getenv("TFL_SCAL3_MARCH")) == 1;
   if (march && !tzsel) {
-    if (a.fast) zm::launch<true>(st, two_pass, a, B, s, U, flags, fwd, bounds, dst, stages);
-    else zm::launch<false>(st, two_pass, a, B, s, U, flags, fwd, bounds, dst, stages);
+    if (a.fast) zm::launch<true>(st, two_pass, a, B, s, U, flags, fwd, bounds, dst, stages, f);
+    else zm::launch<false>(st, two_pass, a, B, s, U, flags, fwd, bounds, dst, stages, f);
     return true;
   }
 #endif
-  if (a.fast) launch<true>(st, tzsel, two_pass, a, B, s, U, flags, fwd, bounds, dst, stages);
-  else launch<false>(st, tzsel, two_pass, a, B, s, U, flags, fwd, bounds, dst, stages);
+  if (a.fast) launch<true>(st, tzsel, two_pass, a, B, s, U, flags, fwd, bounds, dst, stages, f);
+  else launch<false>(st, tzsel, two_pass, a, B, s, U, flags, fwd, bounds, dst, stages, f);
   return true;
 }
 #endif

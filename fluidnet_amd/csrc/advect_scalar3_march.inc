@@ -361,7 +361,7 @@ static int pick_chunk(long long cols, int na, int nb, int slots, int fill, const
 
 template <bool FAST>
 void launch(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* s, const float* U, const float* flags, float* fwd,
-            float* bounds, float* dst, int stages) {
+            float* bounds, float* dst, int stages, Fold& f) {
   const Dom& d = a.d;
   const bool pa = stages & 2, pb = two_pass && (stages & 4);
   float* outA = two_pass ? fwd : dst;
@@ -376,7 +376,7 @@ void launch(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float*
     if (two_pass) TFL_LAUNCH_EXT((k_scal3m_fwd<true, FAST>), (unsigned)(cols * chunks), dim3(TX, TY, 1), 0, st, a, cxn, cyn, cz, chunks_a, chunks, s, U, flags, outA, bounds);
     else TFL_LAUNCH_EXT((k_scal3m_fwd<false, FAST>), (unsigned)(cols * chunks), dim3(TX, TY, 1), 0, st, a, cxn, cyn, cz, chunks_a, chunks, s, U, flags, outA, (float*)nullptr);
   }
-  const BcFoldArg fold = pb ? take_fold() : no_fold();   // pass B writes the operator's result
+  const BcFoldArg fold = pb ? f.hand_bc() : no_fold();   // pass B writes the operator's result
   if (pb) {
     const int cz = pick_chunk(cols, na, nb, device_cus() * blocks_per_cu((const void*)k_scal3m_bwd<FAST>), 3, "TFL_SCAL3M_CZ_B");
     const int chunks_a = (na + cz - 1) / cz, chunks = chunks_a + (nb + cz - 1) / cz;

@@ -371,7 +371,7 @@ __global__ __launch_bounds__(256) void k_vel3_bwd(AdvArgs a, double half_strengt
 
 
 static void launch(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* U, const float* flags, float* fwd, float* dst,
-                   int stages) {
+                   int stages, Fold& f) {
   const Dom& d = a.d;
   const dim3 blk(TX, TY, 1), grd = cell_grid(d, B, blk);
   const bool pa = stages & 2, pb = stages & 4;
@@ -383,8 +383,8 @@ static void launch(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const
   }
   if (two_pass && pb) {
     TFL_TIMED_EXT("k_vel_bwd", st);
-    const BcFoldArg fold = take_fold();    // pass B writes the operator's result
-    const BuoyFold by = take_buoy();       // ... and may add the buoyancy force that follows it in simulate()
+    const BcFoldArg fold = f.hand_bc();    // pass B writes the operator's result
+    const BuoyFold by = f.hand_buoy();     // ... and may add the buoyancy force that follows it in simulate()
     const bool y_only = by.rho && by.sx == 0.0f && by.sz == 0.0f && by.sy != 0.0f;
     if (y_only) {
       if (a.fast) TFL_LAUNCH_EXT((k_vel3_bwd<true, 2>), grd, blk, 0, st, a, (double)a.strength * 0.5, U, flags, (const float*)fwd, dst, fold, by);

@@ -970,15 +970,16 @@ void model_skip_channel(hipStream_t st, int B, long long cells, const float* pDi
 bool model_project(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* pPred, const float* flags,
                    const double* stats, double count, float* Uio, float* pOut, const float* UBC, const float* UInvMask,
                    int do_clamp, float lo, float hi, const unsigned long long* range_src, unsigned long long* range_dst,
-                   const float* reach_src, float* reach_dst, float* reach_acc, const unsigned short* wall_code, unsigned* reach_tick) {
+                   const float* reach_src, float* reach_dst, float* reach_acc, const unsigned short* wall_code, unsigned* reach_tick,
+                   Fold& f) {
   const Dom d = make_dom(Z, Y, X);
   const dim3 blk(64, 4, 1), grd = TFL_GRID3(d, B);
-  // a dense pair acts everywhere; without one, tfl_simulate_step's sparse pair (if it asked: tfl_host.hpp BcFold) in its box
+  // a dense pair acts everywhere; without one, tfl_simulate_step's sparse pair (if it asked: tfl_host.hpp Fold) in its box
   BcArgs bc; bc.enable_clamp = do_clamp; bc.lo = lo; bc.hi = hi;
   bc.range_src = range_dst ? range_src : nullptr; bc.range_dst = range_dst;
   bc.reach_src = reach_dst ? reach_src : nullptr; bc.reach_dst = reach_dst;
   bc.reach_acc = nullptr; bc.wall_code = nullptr; bc.reach_tick = bc.reach_src ? reach_tick : nullptr;
-  bc.UBC = UBC; bc.UInvMask = UInvMask; bc.fold = UBC ? no_fold() : take_fold();
+  bc.UBC = UBC; bc.UInvMask = UInvMask; bc.fold = UBC ? no_fold() : f.hand_bc();
   const uintptr_t al = (uintptr_t)pPred | (uintptr_t)flags | (uintptr_t)Uio | (uintptr_t)pOut | (uintptr_t)UBC |
                        (uintptr_t)UInvMask;
   if (X % 4 == 0 && (al & 15) == 0 && !exp_env("TFL_NO_VEC4")) {

@@ -6,6 +6,7 @@
 #include "../../include/tfluids_hip.h"
 #include "tfl_ctx.hpp"
 #include "tfl_host.hpp"
+#include "tfl_ops.hpp"
 
 #include <cstddef>
 #include <algorithm>
@@ -17,13 +18,6 @@
 #include <cstring>
 #include <thread>
 #include <string>
-
-namespace tfl { const unsigned long long* model_range_counter(const tfl_model* m); }      // abi.cpp (library-internal)
-namespace tfl {      // abi.cpp (library-internal): both advections' passes A / passes B as one launch each (advect_pair3.hip)
-int advect_pair(tfl_ctx* c, float dt, float strength, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags,
-                const tfl_tensor* sfwd, const tfl_tensor* sbounds, const tfl_tensor* sDst, const tfl_tensor* vfwd, const tfl_tensor* UDst,
-                const BcFoldArg& fold_s, const BcFoldArg& fold_v);
-}
 
 struct tfl_bc_plan {
   tfl_tensor bc, inv;      // the dense pair (pointers kept, not owned)
@@ -85,30 +79,21 @@ int set_const_vals(tfl_ctx* c, const tfl_sim_state* s, const tfl_tensor* U_now, 
 }
 
 // Folding a sparse pair into the kernel that produces the field (tfl_host.hpp BcFold): fold_arg is the request as a value
-// (the pair kernels of advect_pair3.hip take two of them as arguments), fold_ask hands it to the next operator through the
-// context, fold_took reads the acknowledgement after it. TFL_BC_FOLD=0 keeps every pair in its own launch (A/B switch).
+// (the pair kernels of advect_pair3.hip take two of them as arguments). TFL_BC_FOLD=0 keeps every pair in its own launch
+// (A/B switch).
 tfl::BcFoldArg fold_arg(const tfl_bc_plan* p) {
   const char* e = getenv("TFL_BC_FOLD");       // (read per call: the A/B parity test switches it inside one process)
   if ((e && atoi(e) == 0) || !p || !p->sparse || !p->boxed || !p->d_fold || p->n_idx == 0) return tfl::no_fold();
   return tfl::BcFoldArg{p->d_fold, (unsigned)p->box[2] | ((unsigned)p->box[4] << 16), (unsigned)p->box[3] | ((unsigned)p->box[5] << 16)};
 }
-bool fold_ask(tfl_ctx* c, const tfl_bc_plan* p) {
-  c->fold_done = false;
-  c->fold = fold_arg(p);
-  return c->fold.dev != nullptr;
+// What a step asks of an operator call (tfl_ops.hpp): the sparse pair of plan p (null: none) for the kernel that writes the
+// result, and no fp16 range gate -- the step has taken it at its entry, nothing refuses half-way through.
+tfl::Ask step_ask(const tfl_bc_plan* p) {
+  tfl::Ask a;
+  a.fold.bc = fold_arg(p);
+  a.gated = false;
+  return a;
 }
-bool fold_took(tfl_ctx* c) {
-  const bool d = c->fold_done;
-  c->fold = tfl::no_fold();
-  c->fold_done = false;
-  return d;
-}
-
-struct InStep {              // tfl_ctx::in_step for the length of a step, whatever way it ends
-  tfl_ctx* c;
-  explicit InStep(tfl_ctx* ctx) : c(ctx) { c->in_step = true; }
-  ~InStep() { c->in_step = false; }
-};
 
 struct Sizes { long long N, C; int B, Z, Y, X; bool is3d; };
 Sizes sizes_of(const tfl_sim_state* s) {
@@ -134,7 +119,7 @@ void scaled_gravity(const tfl_sim_params* prm, double dx, double scale, float ou
 }
 
 // sparse idempotent U BCs go after the projection by index list instead of as two dense fields inside it (round 4: the
-// projection kernel applies them itself on the rows inside their box -- fold_ask -- and the launch goes too)
+// projection kernel applies them itself on the rows inside their box -- step_ask -- and the launch goes too)
 struct LateUbc { bool late; const tfl_tensor *bc, *mask; };
 LateUbc late_ubc_of(const tfl_sim_state* s) {
   const bool late = s->UBC && s->UBC->sparse && s->UBC->idem;
@@ -231,7 +216,6 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
       return TFL_EINVAL;
     }
   }
-  InStep in_step(c);      // the gate above is the step's only one: nothing below refuses half-way through
 
   // ---- advection (simulate.lua:183-200): every density channel with the pre-advection U, then U ----------------
   unsigned density_done = 0;
@@ -240,11 +224,11 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
                bwdPos = view(ws + (2 + z.C) * z.N, (int)z.C), out = view(ws + (2 + 2 * z.C) * z.N, 1);
     const tfl_tensor* dst = ours ? s->density[i] : &out;       // maccormackOurs runs in place (no copy back)
     // the first setConstVals (below) follows the advection directly: the kernel that writes the advected field applies
-    // the field's pair itself where it can (fold_ask / fold_took; the sparse launch covers the rest)
-    fold_ask(c, s->densityBC[i]);
-    rc = tfl_advectScalar(c, prm->dt, s->density[i], s->U, s->flags, &fwd, &bwd, is3D, method, &fwdPos, &bwdPos, 1, 0,
-                          prm->maccormackStrength, dst);
-    if (fold_took(c)) density_done |= 1u << i;
+    // the field's pair itself where it can (step_ask; the sparse launch covers the rest)
+    tfl::Ask a = step_ask(s->densityBC[i]);
+    rc = tfl::advectScalar(c, prm->dt, s->density[i], s->U, s->flags, &fwd, &bwd, is3D, method, &fwdPos, &bwdPos, 1, 0,
+                           prm->maccormackStrength, dst, a);
+    if (a.fold.bc_took) density_done |= 1u << i;
     if (rc) return rc;
     if (!ours) { rc = tfl_copy(c, s->density[i], &out); if (rc) return rc; }
   }
@@ -253,30 +237,26 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
   const double dx = tfl_getDx(c, s->flags);
   float bg[3];
   scaled_gravity(prm, dx, prm->buoyancyScale, bg);
-  const bool U_pair_asked = fold_ask(c, s->UBC);
+  tfl::Ask adv = step_ask(s->UBC);
   // addBuoyancy follows advectVel and the first setConstVals directly and needs nothing but the advected density, which is
   // final by now: pass B of advectVel may add the force itself behind the folded U pair (tfl_host.hpp BuoyFold; round 5).
   // Asked for only when the density's own pair has been applied already (or there is none) and the U pair travels with the
   // same kernel (or there is none); TFL_BUOY_FOLD=0 keeps the force in its own launch (A/B switch).
-  bool buoy_folded = false;
   {
     const char* e = getenv("TFL_BUOY_FOLD");
     const bool rho_final = buoyant && (!s->densityBC[0] || (density_done & 1u));
-    if (rho_final && ours && is3D && !(e && atoi(e) == 0) && (!s->UBC || U_pair_asked)) {
+    if (rho_final && ours && is3D && !(e && atoi(e) == 0) && (!s->UBC || adv.fold.bc.dev)) {
       // strength = -gravity * (dt / dx) in float, exactly as tfl_addBuoyancyFrom forms it (abi.cpp get_dx; tfluids.cc:1190-1192)
       float dxf;
       if (c->dx_dim > 0) dxf = 1.0f / (float)c->dx_dim;
       else if (c->dx_override > 0.0f) dxf = c->dx_override;
       else dxf = 1.0f / (float)std::max(std::max(s->flags->X, s->flags->Y), s->flags->Z);
       const float bs = prm->dt / dxf;
-      c->buoy = tfl::BuoyFold{s->density[0]->data, -bg[0] * bs, -bg[1] * bs, -bg[2] * bs};
+      adv.fold.buoy = tfl::BuoyFold{s->density[0]->data, -bg[0] * bs, -bg[1] * bs, -bg[2] * bs};
     }
-    c->buoy_done = false;
   }
-  rc = tfl_advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vbwd, is3D, method, 1, prm->maccormackStrength, &Uadv);
-  const bool Uadv_done = fold_took(c);
-  buoy_folded = c->buoy_done;
-  c->buoy = tfl::no_buoy(); c->buoy_done = false;
+  rc = tfl::advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vbwd, is3D, method, 1, prm->maccormackStrength, &Uadv, adv);
+  const bool Uadv_done = adv.fold.bc_took, buoy_folded = adv.fold.buoy_took;
   if (rc) return rc;
   // U:copy(advected) (init.lua:216-218) costs nothing: the velocity stays in the advection's scratch array (`cur`) until an
   // operator that writes every cell of its output delivers it into U -- addBuoyancy (tfl_addBuoyancyFrom), the vorticity
@@ -297,7 +277,7 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
   // ---- forces (simulate.lua:204-239) -------------------------------------------------------------------------
   // The setConstVals that follows the forces (below) touches only U (nothing else has been written since the first one):
   // with the ConvNet projection nothing comes between the last force and it, so the LAST force's kernel applies the U pair
-  // itself where it can (fold_ask / fold_took; the other projections run setWallBcs first, outputDiv skips the call).
+  // itself where it can (step_ask; the other projections run setWallBcs first, outputDiv skips the call).
   const std::string sm = method_of(prm);
   const bool fold_forces = !prm->outputDiv && sm == "convnet";
   const bool gravity_on = prm->gravityScale > 0.0;
@@ -308,9 +288,9 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
     // SOMEONE, and addBuoyancyFrom does that for free, so it delivers into U unless the fused confinement reads next)
     const tfl_tensor* dst = vfused ? &Utmp : s->U;
     const bool last = fold_forces && !gravity_on && !vort;
-    if (last) fold_ask(c, s->UBC);
-    rc = tfl_addBuoyancyFrom(c, cur, dst, s->flags, s->density[0], bg, prm->dt, is3D);
-    if (last) U_folded = fold_took(c);
+    tfl::Ask a = step_ask(last ? s->UBC : nullptr);
+    rc = tfl::addBuoyancyFrom(c, cur, dst, s->flags, s->density[0], bg, prm->dt, is3D, a);
+    U_folded = a.fold.bc_took;
     if (rc) return rc;
     cur = dst;
   }
@@ -322,16 +302,15 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
   }
   if (vort) {
     const float strength = (float)(dx * prm->vorticityConfinementAmp);
-    if (fold_forces) fold_ask(c, s->UBC);
+    tfl::Ask a = step_ask(fold_forces ? s->UBC : nullptr);
     if (cur != s->U) {
-      c->vort_from_two_launch = !vfused;     // below the fused kernel's size the two launches read `cur` and write U
-      rc = tfl_vorticityConfinementFrom(c, cur, s->U, s->flags, strength, &curl, &cnorm, is3D);
-      c->vort_from_two_launch = false;
+      a.two_launch = !vfused;     // below the fused kernel's size the two launches read `cur` and write U
+      rc = tfl::vorticityConfinementFrom(c, cur, s->U, s->flags, strength, &curl, &cnorm, is3D, a);
     } else {
       tfl_tensor centered = view(ws + 4 * z.N, (int)z.C), force = view(ws + (4 + z.C) * z.N, (int)z.C);   // (unused by the kernels)
-      rc = tfl_vorticityConfinement(c, s->U, s->flags, strength, &centered, &curl, &cnorm, &force, is3D);
+      rc = tfl::vorticityConfinement(c, s->U, s->flags, strength, &centered, &curl, &cnorm, &force, is3D, a);
     }
-    if (fold_forces) U_folded = fold_took(c);
+    U_folded = a.fold.bc_took;
     if (rc) return rc;
     cur = s->U;
   }
@@ -355,12 +334,11 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
   if (sm == "convnet") {
     if (!s->model) return TFL_EINVAL;
     const LateUbc lu = late_ubc_of(s);
-    if (lu.late) fold_ask(c, s->UBC);
-    rc = tfl_model_forward(c, s->model, s->p, cur, s->flags, s->p, s->U, ws, ws_floats, lu.bc, lu.mask, 1, -1e6f, 1e6f);
-    const bool folded = fold_took(c);
+    tfl::Ask a = step_ask(lu.late ? s->UBC : nullptr);
+    rc = tfl::model_forward(c, s->model, s->p, cur, s->flags, s->p, s->U, ws, ws_floats, lu.bc, lu.mask, 1, -1e6f, 1e6f, a);
     if (rc) return rc;
     // p was rewritten by the model, density has not changed since the second setConstVals
-    return set_const_vals(c, s, s->U, lu.late && !folded, Unchanged{false, false, true});
+    return set_const_vals(c, s, s->U, lu.late && !a.fold.bc_took, Unchanged{false, false, true});
   }
   tfl_tensor div = view(ws, 1);
   rc = tfl_velocityDivergenceForward(c, s->U, s->flags, &div, is3D);
@@ -669,7 +647,7 @@ Win ext(const SlabGeom& g, int below, int above) {
 struct StageGuard {          // whatever happens, leave the context with no window / stage mask / dx override
   tfl_ctx* c;
   explicit StageGuard(tfl_ctx* ctx) : c(ctx) {}
-  ~StageGuard() { (void)tfl_set_z_window(c, 0, 0, 0, 0); (void)tfl_set_stages(c, 0); c->dx_dim = 0; (void)tfl_set_z_origin(c, 0, 0); c->reach_sink = false; }
+  ~StageGuard() { (void)tfl_set_z_window(c, 0, 0, 0, 0); (void)tfl_set_stages(c, 0); c->dx_dim = 0; (void)tfl_set_z_origin(c, 0, 0); }
 };
 
 // the pinned publication count has reached `target` (wrap-safe); spins without an API call, gives the core away after a while,
@@ -698,7 +676,7 @@ bool reach_violated(tfl_ctx* c, float dt, int R, char* msg, size_t msg_len) {
   return true;
 }
 // ... device side: the sticky word and the publication count reach the host through the step's LAST kernel (k_project writes
-// them into the mapped pinned mirror: tfl_ctx::reach_sink) -- not through hipMemcpyAsync (a 4-byte D2H copy on the stream makes
+// them into the mapped pinned mirror: Ask::reach_via_project) -- not through hipMemcpyAsync (a 4-byte D2H copy on the stream makes
 // the HOST wait until the stream has drained on this stack, tools/ubench/host_costs.hip) and not behind an event (4 us of
 // device time per hipEventRecord): the host counts the publishing launches it has enqueued (tfl_model_finish) and keeps the
 // count as it stood at the end of the last two steps
@@ -777,6 +755,7 @@ struct SlabStep {
   unsigned extra_done = 0;                 // ... of density channels 1.. (bit i)
   bool paired = false;                 // both advections' passes run as pairs (advect_pair3.hip)
   bool U_folded = false;               // the last force applied the U pair of the second setConstVals
+  bool reach_via_project = false;      // the projection kernel of this step publishes the reach word (check_reach = 1)
   const tfl_tensor* cur = nullptr;     // where the velocity of the step currently lives
 
   int validate();                      // the refusals that come before anything is enqueued, then the views and messages
@@ -795,13 +774,22 @@ struct SlabStep {
   }
   void no_stage() { (void)tfl_set_stages(c, 0); (void)tfl_set_z_window(c, 0, 0, 0, 0); }
   int run_then_send(int mask, int k, const Msg& q, int (SlabStep::*op)());
-  int adv_scalar(const tfl_tensor* d, const tfl_tensor* dst) {
-    return tfl_advectScalar(c, prm->dt, d, s->U, s->flags, &fwd, &fwd, 1, method, &fwdPos, &bwdPos, 1, 0, prm->maccormackStrength, dst);
+  // (a: what the call is asked, step_ask; null: nothing)
+  int adv_scalar(const tfl_tensor* d, const tfl_tensor* dst, tfl::Ask* a = nullptr) {
+    tfl::Ask none = step_ask(nullptr);
+    return tfl::advectScalar(c, prm->dt, d, s->U, s->flags, &fwd, &fwd, 1, method, &fwdPos, &bwdPos, 1, 0, prm->maccormackStrength, dst,
+                             a ? *a : none);
   }
-  int adv_vel() { return tfl_advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vfwd, 1, method, 1, prm->maccormackStrength, &Uadv); }
+  int adv_vel(tfl::Ask* a = nullptr) {
+    tfl::Ask none = step_ask(nullptr);
+    return tfl::advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vfwd, 1, method, 1, prm->maccormackStrength, &Uadv, a ? *a : none);
+  }
   int adv_pair(bool with_folds);
   int pass_b();
-  int model_begin() { return tfl_model_begin(c, s->model, s->U, s->flags, s->U, W.compute, ws_floats - (W.compute - ws), g.o0, g.o1, W.stats); }
+  int model_begin() {
+    tfl::Ask a = step_ask(nullptr);
+    return tfl::model_begin(c, s->model, s->U, s->flags, s->U, W.compute, ws_floats - (W.compute - ws), g.o0, g.o1, W.stats, a);
+  }
 };
 
 // `op` on the owned planes under stage mask `mask`, then message `q` starts. Overlapped: `op` on the boundary strips (k planes
@@ -919,7 +907,7 @@ int SlabStep::gates() {
     tfl::reach_publish(c->stream, c->d_reach, c->d_reach_host, c->d_reach_tick);
     c->reach_issued++;
   } else if (sl->check_reach) {
-    c->reach_sink = true;                  // the projection kernel of THIS step publishes the word (cleared by StageGuard)
+    reach_via_project = true;              // the projection kernel of THIS step publishes the word
   }
   return TFL_OK;
 }
@@ -936,18 +924,18 @@ int SlabStep::adv_pair(bool with_folds) {
 
 // the passes B of both operators on the current window (other methods: the velocity's). They apply the pairs of the
 // setConstVals that follows on the planes they write -- the owned ones, which is what message T2 carries to the neighbours'
-// halos (fold_ask / fold_took)
+// halos (step_ask)
 int SlabStep::pass_b() {
   if (ap.ours && paired) { const int r = adv_pair(true); if (r != TFL_EUNSUPPORTED) return r; paired = false; }
   if (ap.ours && rho) {
-    fold_ask(c, s->densityBC[0]);
-    const int r = adv_scalar(rho, rho);
-    rho_done = fold_took(c) && rho_done;
+    tfl::Ask a = step_ask(s->densityBC[0]);
+    const int r = adv_scalar(rho, rho, &a);
+    rho_done = a.fold.bc_took && rho_done;
     if (r) return r;
   }
-  fold_ask(c, s->UBC);
-  const int r = adv_vel();
-  Uadv_done = fold_took(c) && Uadv_done;
+  tfl::Ask a = step_ask(s->UBC);
+  const int r = adv_vel(&a);
+  Uadv_done = a.fold.bc_took && Uadv_done;
   return r;
 }
 
@@ -965,9 +953,9 @@ int SlabStep::advect() {
       TRY(stage(1, 2 * R, 2 * R)); TRY(adv_scalar(di, di));
       TRY(stage(2, R, R)); TRY(adv_scalar(di, di));
       TRY(stage(4, 0, 0));
-      fold_ask(c, s->densityBC[i]);
-      const int rc = adv_scalar(di, di);
-      if (fold_took(c)) extra_done |= 1u << i;
+      tfl::Ask a = step_ask(s->densityBC[i]);
+      const int rc = adv_scalar(di, di, &a);
+      if (a.fold.bc_took) extra_done |= 1u << i;
       if (rc) return rc;
     }
     TRY(stage(2, R, R));
@@ -1018,9 +1006,9 @@ int SlabStep::forces() {
     scaled_gravity(prm, dx, prm->buoyancyScale, gv);
     const tfl_tensor* dst = vfused ? &Utmp : s->U;
     const bool last = fold_forces && !gravity_on && !vort;
-    if (last) fold_ask(c, s->UBC);
-    const int rc = tfl_addBuoyancyFrom(c, cur, dst, s->flags, rho, gv, prm->dt, 1);
-    if (last) U_folded = fold_took(c);
+    tfl::Ask a = step_ask(last ? s->UBC : nullptr);
+    const int rc = tfl::addBuoyancyFrom(c, cur, dst, s->flags, rho, gv, prm->dt, 1, a);
+    U_folded = a.fold.bc_took;
     if (rc) return rc;
     cur = dst;
   }
@@ -1034,10 +1022,10 @@ int SlabStep::forces() {
     const float strength = (float)(dx * prm->vorticityConfinementAmp);
     if (!vfused) { TRY(stage(2, 2, 2)); TRY(tfl_vorticityConfinement(c, s->U, s->flags, strength, &curl, &curl, &cnorm, &curl, 1)); }
     TRY(stage(vfused ? 0 : 4, 0, 1));
-    if (fold_forces) fold_ask(c, s->UBC);
-    const int rc = vfused ? tfl_vorticityConfinementFrom(c, cur, s->U, s->flags, strength, &curl, &cnorm, 1)
-                          : tfl_vorticityConfinement(c, s->U, s->flags, strength, &curl, &curl, &cnorm, &curl, 1);
-    if (fold_forces) U_folded = fold_took(c);
+    tfl::Ask a = step_ask(fold_forces ? s->UBC : nullptr);
+    const int rc = vfused ? tfl::vorticityConfinementFrom(c, cur, s->U, s->flags, strength, &curl, &cnorm, 1, a)
+                          : tfl::vorticityConfinement(c, s->U, s->flags, strength, &curl, &curl, &cnorm, &curl, 1, a);
+    U_folded = a.fold.bc_took;
     if (rc) return rc;
   }
   no_stage();
@@ -1094,8 +1082,11 @@ int SlabStep::project_net() {
   // (no input scale: every rank holds (0, 1) already -- a sum would make it (0, world))
   if (multi && g.cone.norm != 2 && comm->allreduce_sum(comm->user, W.stats, 2ll * g.B) != 0) { c->err = "simulate_step_slab: comm callback failed (allreduce_sum)"; return TFL_EINVAL; }
   const LateUbc lu = late_ubc_of(s);
-  auto finish = [&]() { return tfl_model_finish(c, s->model, s->p, s->flags, s->p, s->U, W.compute, ws_floats - (W.compute - ws), W.stats, count,
-                                                lu.bc, lu.mask, 1, -1e6f, 1e6f); };
+  auto finish = [&](tfl::Ask* a = nullptr) {
+    tfl::Ask none = step_ask(nullptr);
+    return tfl::model_finish(c, s->model, s->p, s->flags, s->p, s->U, W.compute, ws_floats - (W.compute - ws), W.stats, count,
+                             lu.bc, lu.mask, 1, -1e6f, 1e6f, a ? *a : none);
+  };
   (void)tfl_set_stages(c, 1);
   const Win w1 = ext(g, 3, 2);
   if (g.gen) {
@@ -1114,12 +1105,13 @@ int SlabStep::project_net() {
   }
   if (!g.gen) { TRY(stage(2, 2, 1)); TRY(finish()); TRY(stage(4, 1, 0)); TRY(finish()); }
   TRY(stage(8, 0, 0));
-  if (lu.late) fold_ask(c, s->UBC);          // the projection kernel applies the sparse U pair itself (owned planes: what T0 sends)
-  const int rc = finish();
-  const bool U_late_folded = fold_took(c);
+  tfl::Ask a = step_ask(lu.late ? s->UBC : nullptr);   // the projection kernel applies the sparse U pair itself (owned planes: what T0 sends)
+  a.reach_via_project = reach_via_project;
+  const int rc = finish(&a);
+  if (a.reach_published) { c->reach_folded = a.reach_folded; c->reach_issued++; }   // (tfl_slab_graph_create counts these)
   if (rc) return rc;
   no_stage();
-  return set_const_vals(c, s, s->U, lu.late && !U_late_folded, Unchanged{false, false, true});
+  return set_const_vals(c, s, s->U, lu.late && !a.fold.bc_took, Unchanged{false, false, true});
 }
 
 // the end of every step: the next step's U and p halos leave now; they are consumed at its start / before its first conv layer
@@ -1143,7 +1135,6 @@ int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_
   TRY(S.validate());
   StageGuard guard(c);
   TRY(S.gates());
-  InStep in_step(c);      // the gates above are the step's only refusals: nothing below refuses half-way through
   c->dx_dim = std::max(std::max(s->flags->X, s->flags->Y), sl->z_total);   // tfluids.getDx of the WHOLE grid
   (void)tfl_set_z_origin(c, sl->z_first, sl->z_total);
   TRY(S.advect());

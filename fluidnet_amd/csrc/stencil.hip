@@ -341,14 +341,14 @@ void velocity_update_planes(hipStream_t st, int B, int Z, int Y, int X, int k0, 
   TFL_LAUNCH_PLANES(k_velocity_update, U, flags, p);
 }
 void add_buoyancy(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* Usrc, float* U, const float* flags,
-                  const float* density, float sx, float sy, float sz) {
+                  const float* density, float sx, float sy, float sz, Fold& f) {
   const bool vec = (X % 4 == 0) && ((((uintptr_t)U | (uintptr_t)Usrc | (uintptr_t)flags | (uintptr_t)density) & 15) == 0) &&
                    !exp_env("TFL_NO_VEC4");
   if (vec) {
     const Dom d = make_dom(Z, Y, X);
     const dim3 blk(32, 8, 1), grd((X / 4 + 31) / 32, (Y + 7) / 8, (unsigned)(d.nw * B));
     TFL_TIMED_EXT("k_add_buoyancy", st);
-    const BcFoldArg fold = Usrc != U ? take_fold() : no_fold();
+    const BcFoldArg fold = Usrc != U ? f.hand_bc() : no_fold();
     if (is3d) TFL_LAUNCH_EXT((k_add_buoyancy_v4<true>), grd, blk, 0, st, d, Usrc, U, flags, density, sx, sy, sz, fold);
     else TFL_LAUNCH_EXT((k_add_buoyancy_v4<false>), grd, blk, 0, st, d, Usrc, U, flags, density, sx, sy, sz, fold);
     return;

@@ -124,10 +124,10 @@ static inline dim3 cell_grid(const Dom& d, int B, dim3 blk) {
 
 // advect_vel3.hip: advectVel of the trace-based methods on a 3-D grid; false = shape not supported (caller falls back)
 bool advect_vel3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* U, const float* flags, float* fwd,
-                 float* dst, int stages);
+                 float* dst, int stages, Fold& f);
 // advect_scalar3.hip: advectScalar of the trace-based methods on a 3-D grid (no min/max grid: `bounds` = two planes)
 bool advect_scalar3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* s, const float* U, const float* flags,
-                    float* fwd, float* bounds, float* dst, int stages);
+                    float* fwd, float* bounds, float* dst, int stages, Fold& f);
 
 // advect_pair3.hip (round 6): the passes A (stages & 2) / the passes B (stages & 4) of advectScalar AND advectVel in one launch each
 bool advect_pair3(hipStream_t st, const AdvArgs& a, int B, const float* s, const float* U, const float* flags, float* sfwd, float* sbounds,

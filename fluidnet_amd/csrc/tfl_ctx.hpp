@@ -1,5 +1,6 @@
 // tfl_ctx.hpp -- the context object behind the opaque tfl_ctx* of include/tfluids_hip.h (private to the library:
-// abi.cpp owns it, simulate.cpp reads the stream and the z-slab reach-check words).
+// abi.cpp owns it, simulate.cpp reads the stream and keeps the z-slab reach-check words). What a native step asks of an
+// operator call is not kept here: it travels as an argument (tfl_ops.hpp Ask).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,22 +44,13 @@ struct tfl_ctx {
   // and no event on either side: the hipEventRecord per step of the first form cost the device 4 us of a 0.1 ms rank-step.
   float* d_reach_host = nullptr;              // the device address of h_reach
   unsigned* d_reach_tick = nullptr;           // device word: publications made so far
-  bool reach_sink = false;                    // the projection launches of THIS step publish (set by the slab step, cleared by its guard)
   bool reach_folded = false;                  // the last projection launch of a slab step folded max|u_z| of the planes it wrote into d_reach: the next step's k_absmax is not needed
   unsigned reach_issued = 0;                  // publishing launches enqueued so far (host side)
   unsigned reach_hist[2] = {0, 0};            // reach_issued as it stood at the end of the step before last / of the last step
   double* h_reach_flags = nullptr;            // pinned [kReachFlags]: the all-reduced "reach >= r" counts of check_reach = 2 (created on first use)
   int needed_reach = 0;                       // what the last TFL_EREACH asked for (tfl_slab_needed_reach)
-  tfl::BcFoldArg fold = {nullptr, 0u, 0u};    // tfl_simulate_step: a setConstVals pair (device descriptor + gate) the next operator may apply to its output
-  bool fold_done = false;                     // ... and whether a launcher did (tfl_host.hpp BcFold)
-  tfl::BuoyFold buoy = {nullptr, 0.0f, 0.0f, 0.0f};   // tfl_simulate_step: the buoyancy force the next advectVel may add itself (tfl_host.hpp BuoyFold)
-  bool buoy_done = false;
-  bool vort_from_two_launch = false;          // tfl_simulate_step: the next tfl_vorticityConfinementFrom skips the fused kernel (grid below its size)
   int wf_skip = 0;                            // > 0: a pipelined PCG sweep timed out on this context: the next wf_skip solves go straight to
                                               // hyperplane sweeps, then the pipelined form is tried again (a transient stall must not latch for good)
   int wf_timeouts = 0;                        // how often that happened (the back-off doubles, one warning per latch)
-  bool defer_stats = false;                   // tfl_model_forward: the first conv layer sums k_bcs_div_stats' partials itself (no k_reduce_stats launch)
-  bool in_step = false;                       // inside tfl_simulate_step[_slab]: the fp16 range gate was taken at the step's entry, tfl_model_begin /
-                                              // tfl_model_forward do not take it again mid-step (a half-stepped state otherwise)
   bool capturing = false;                     // tfl_slab_graph_create is recording the step on `stream`: no host waits, no host reads
 };

@@ -37,30 +37,33 @@ extern thread_local int g_advect_fast;
 // threads inside it load bc / invMask ([B][C][Z][Y][X] like the field) -- nothing per cell elsewhere. The descriptor lives in
 // DEVICE memory (the plan owns it) and a kernel gets its address: one pointer argument, read with scalar loads at the store
 // -- ten scalars by value stayed live through the whole kernel and cost the advection kernels 30 SGPR spills each. A launcher
-// that hands the pointer to its kernel sets g_fold_done; tfl_simulate_step launches the sparse kernel (k_apply_bcs_indexed)
-// when nobody did.
+// that hands the pointer to its kernel says so (Fold below); tfl_simulate_step launches the sparse kernel
+// (k_apply_bcs_indexed) when none did.
 struct BcFold { const float* bc; const float* inv; int x0, x1, y0, y1, z0, z1; };
 // What a kernel is handed: the descriptor's device address and, by value, the box's y / z range packed into two words
 // (lo = y0 | z0 << 16, hi = y1 | z1 << 16): the block-uniform gate at the top of the kernel needs no memory access.
 struct BcFoldArg { const BcFold* dev; unsigned lo, hi; };     // dev == nullptr: no request
-extern thread_local BcFoldArg g_fold;
-extern thread_local bool g_fold_done;
-// the request for a kernel launch (and the acknowledgement), or an empty one
-inline BcFoldArg take_fold() { if (g_fold.dev) g_fold_done = true; return g_fold; }
 inline BcFoldArg no_fold() { return BcFoldArg{nullptr, 0u, 0u}; }
 
 // addBuoyancy (third_party/tfluids.cc:1162-1233) folded into the kernel that writes the advected velocity (round 5). In
 // simulate() the buoyancy force follows advectVel and the first setConstVals directly (lib/simulate.lua:196-226), it is
 // pointwise in U and needs the ADVECTED density -- which advectScalar has delivered (pair applied) before advectVel runs. So
-// tfl_simulate_step hands pass B of advectVel a request {rho, (sx, sy, sz) = -gravity dt / dx}; a launcher that takes it
-// (g_buoy_done) adds 0.5 s_c (rho(i) + rho(i - e_c)) on the faces between two fluid cells behind the folded pair, from two
-// to four more loads per cell, and the 32 B/cell launch of k_add_buoyancy disappears. Only taken together with the U pair
-// (or when there is none): the force must see the boundary values.
+// tfl_simulate_step hands pass B of advectVel a request {rho, (sx, sy, sz) = -gravity dt / dx}; the kernel that takes it
+// adds 0.5 s_c (rho(i) + rho(i - e_c)) on the faces between two fluid cells behind the folded pair, from two to four more
+// loads per cell, and the 32 B/cell launch of k_add_buoyancy disappears. Asked for only together with the U pair (or when
+// there is none): the force must see the boundary values.
 struct BuoyFold { const float* rho; float sx, sy, sz; };      // rho == nullptr: no request
-extern thread_local BuoyFold g_buoy;
-extern thread_local bool g_buoy_done;
-inline BuoyFold no_buoy() { return BuoyFold{nullptr, 0.0f, 0.0f, 0.0f}; }
-inline BuoyFold take_buoy() { if (g_buoy.rho) g_buoy_done = true; return g_buoy; }
+
+// What a native step asks of the kernel that writes an operator's result -- the pair and the force above, each may be empty --
+// and what the operator's launchers took of it. A request counts as taken only where a launcher hands it to a kernel (take_*);
+// the step launches whatever was not taken itself.
+struct Fold {
+  BcFoldArg bc = {nullptr, 0u, 0u};
+  BuoyFold buoy = {nullptr, 0.0f, 0.0f, 0.0f};
+  bool bc_took = false, buoy_took = false;
+  BcFoldArg hand_bc() { bc_took = bc_took || bc.dev; return bc; }
+  BuoyFold hand_buoy() { buoy_took = buoy_took || buoy.rho; return buoy; }
+};
 
 // does row (j, k) / cell i of the field lie inside the pair's box
 __device__ __forceinline__ bool fold_row(const BcFold& f, int j, int k) {
@@ -124,9 +127,9 @@ struct KernelTimer {
 // advect.hip
 void advect_scalar(hipStream_t st, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
                    int outside, unsigned long long* err, const float* s, const float* U, const float* flags,
-                   float* fwd, float* bounds, float* mm, float* dst, int stages = 7);
+                   float* fwd, float* bounds, float* mm, float* dst, int stages, Fold& f);
 void advect_vel(hipStream_t st, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
-                unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, int stages = 7);
+                unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, int stages, Fold& f);
 
 void minmax3(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int outside, const float* s, const float* flags,
              float* lo3, float* hi3);
@@ -144,7 +147,7 @@ void velocity_divergence_planes(hipStream_t st, int B, int Z, int Y, int X, int 
 void velocity_update_planes(hipStream_t st, int B, int Z, int Y, int X, int k0, int k1, float* U, const float* flags,
                             const float* p);
 void add_buoyancy(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* Usrc, float* U, const float* flags,
-                  const float* density, float sx, float sy, float sz);
+                  const float* density, float sx, float sy, float sz, Fold& f);
 void add_gravity(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags, float fx,
                  float fy, float fz);
 void empty_domain(hipStream_t st, bool is3d, int bnd, int B, int Z, int Y, int X, float* flags);
@@ -163,12 +166,12 @@ void reach_publish(hipStream_t st, const float* src, float* dst, unsigned* tick)
 // Usrc (round 5): U = Usrc + force with every cell of the window written (the four-cells-per-thread kernels only: false =
 // not possible here, nothing launched, the caller copies Usrc into U and calls again without it)
 bool vorticity_confinement(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags,
-                           float strength, float* curl, float* curl_norm, int stages = 3, const float* Usrc = nullptr);
+                           float strength, float* curl, float* curl_norm, int stages, const float* Usrc, Fold& f);
 
 // U_out = U_in + confinement(U_in), 3-D, one fused launch without curl arrays (U_out != U_in); false = not supported here
 bool vorticity_confinement_fused_ok(bool is3d, int Z, int Y, int X);   // does the native step use the fused kernel for this grid
 bool vorticity_confinement_fused(hipStream_t st, int B, int Z, int Y, int X, const float* Uin, float* Uout, const float* flags,
-                                 float strength);
+                                 float strength, Fold& f);
 
 // jacobi.hip
 void jacobi_iteration(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* p_prev, const float* flags,
@@ -219,9 +222,9 @@ void model_skip_channel(hipStream_t st, int B, long long cells, const float* pDi
 // returns true when the launch also folded max |u_z| of what it wrote into *reach_acc (round 6: k_project_v4 on full blocks)
 bool model_project(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* pPred, const float* flags,
                    const double* stats, double count, float* Uio, float* pOut, const float* UBC, const float* UInvMask,
-                   int do_clamp, float lo, float hi, const unsigned long long* range_src = nullptr,
-                   unsigned long long* range_dst = nullptr, const float* reach_src = nullptr, float* reach_dst = nullptr,
-                   float* reach_acc = nullptr, const unsigned short* wall_code = nullptr, unsigned* reach_tick = nullptr);
+                   int do_clamp, float lo, float hi, const unsigned long long* range_src, unsigned long long* range_dst,
+                   const float* reach_src, float* reach_dst, float* reach_acc, const unsigned short* wall_code, unsigned* reach_tick,
+                   Fold& f);
 void apply_bcs(hipStream_t st, long long n, float* x, const float* bcv, const float* inv, int do_clamp, float lo,
                float hi);
 

@@ -1,0 +1,49 @@
+// tfl_ops.hpp -- library-internal (C++ linkage) forms of the operators that the native steps of simulate.cpp call with a
+// request: each takes the public tfl_* operator's arguments plus an Ask. The public operator (abi.cpp) passes an empty one.
+#pragma once
+#include "../../include/tfluids_hip.h"
+#include "tfl_host.hpp"
+
+namespace tfl {
+
+// What a step asks of the one operator call meant to take it, and what that call reports back (out). Empty = the public operator.
+struct Ask {
+  Fold fold;                       // the setConstVals pair / buoyancy force for the kernel that writes the result, and what was taken
+  bool two_launch = false;         // vorticityConfinementFrom: the two launches even where the fused kernel would run
+  bool gated = true;               // model_begin / model_forward: take the fp16 range gate (a step takes it once, at its entry)
+  bool conv1_sums_stats = false;   // model_begin / model_finish (model_forward sets it): the first conv layer sums the partials itself
+  bool reach_via_project = false;  // model_finish: the projection (stage 8) publishes the z-slab reach word (tfl_ctx.hpp d_reach) ...
+  bool reach_published = false;    // ... out: it was launched so,
+  bool reach_folded = false;       // ... out: and folded max|u_z| of the planes it wrote into the word
+};
+
+int advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* fwd,
+                 const tfl_tensor* bwd, int is3D, const char* method, const tfl_tensor* fwdPos, const tfl_tensor* bwdPos,
+                 int boundaryWidth, int sampleOutsideFluid, float maccormackStrength, const tfl_tensor* sDst, Ask& ask);
+int advectVel(tfl_ctx* c, float dt, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* fwd, const tfl_tensor* bwd,
+              int is3D, const char* method, int boundaryWidth, float maccormackStrength, const tfl_tensor* UDst, Ask& ask);
+int addBuoyancyFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* density,
+                    const float gravity[3], float dt, int is3D, Ask& ask);
+int vorticityConfinement(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, float strength, const tfl_tensor* centered,
+                         const tfl_tensor* curl, const tfl_tensor* curlNorm, const tfl_tensor* force, int is3D, Ask& ask);
+int vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, float strength,
+                             const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D, Ask& ask);
+int model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tensor* flags, const tfl_tensor* UOut, float* workspace,
+                int64_t workspace_floats, int zlo, int zhi, double* stats, Ask& ask);
+int model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* flags, const tfl_tensor* pOut,
+                 const tfl_tensor* UOut, float* workspace, int64_t workspace_floats, const double* stats, double count,
+                 const tfl_tensor* UBC, const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, Ask& ask);
+int model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
+                  const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace, int64_t workspace_floats, const tfl_tensor* UBC,
+                  const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, Ask& ask);
+
+// The MacCormack(Ours) advection of one density channel AND of the velocity on a 3-D grid (the z-slab step), their passes A as
+// one launch (stage bit 2) and their passes B as one launch (stage bit 4) -- advect_pair3.hip. fold_s / fold_v: the
+// setConstVals pairs the passes B apply (dev == nullptr: none). TFL_EUNSUPPORTED = not taken, nothing launched: the caller runs
+// advectScalar and advectVel.
+int advect_pair(tfl_ctx* c, float dt, float strength, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags,
+                const tfl_tensor* sfwd, const tfl_tensor* sbounds, const tfl_tensor* sDst, const tfl_tensor* vfwd, const tfl_tensor* UDst,
+                const BcFoldArg& fold_s, const BcFoldArg& fold_v);
+const unsigned long long* model_range_counter(const tfl_model* m);     // the model's fp16 range word (device)
+
+}  // namespace tfl

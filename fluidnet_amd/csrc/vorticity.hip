@@ -987,7 +987,7 @@ static int march_chunk(long long tiles, int na, int nb, int slots, int fill, int
 
 template <int BX, int BY>
 static bool launch_vort_pipe(hipStream_t st, const Dom& d, int B, int X, int Y, int na, int nb, const float* Uin, float* Uout,
-                             const float* flags, float strength, int xcd_order) {
+                             const float* flags, float strength, int xcd_order, Fold& f) {
   using G = PipeGeo<BX, BY>;
   const int pslots = vort_pipe_slots_of<BX, BY>();
   const int pcx = (X + BX - 1) / BX, pcy = (Y + BY - 1) / BY;
@@ -999,7 +999,7 @@ static bool launch_vort_pipe(hipStream_t st, const Dom& d, int B, int X, int Y, 
   const int chunks_a = (na + cz - 1) / cz, chunks = chunks_a + (nb + cz - 1) / cz;
   const int n_blocks = (int)(pcx * pcy * chunks * B);
   TFL_TIMED_EXT("k_vort_fused", st);
-  const BcFoldArg fold = take_fold();    // the kernel writes the operator's result: it applies the pair that follows
+  const BcFoldArg fold = f.hand_bc();    // the kernel writes the operator's result: it applies the pair that follows
   TFL_LAUNCH_EXT((k_vort_pipe<BX, BY>), n_blocks, G::NT, G::kLds, st, d, pcx, pcy, cz, chunks_a, chunks, n_blocks, Uin, Uout, flags, strength, xcd_order, fold);
   return true;
 }
@@ -1030,7 +1030,7 @@ bool vorticity_confinement_fused_ok(bool is3d, int Z, int Y, int X) {
 
 // false = shape not supported by the fused kernel (the caller copies and runs the two-launch form)
 bool vorticity_confinement_fused(hipStream_t st, int B, int Z, int Y, int X, const float* Uin, float* Uout, const float* flags,
-                                 float strength) {
+                                 float strength, Fold& f) {
   if (Z < 3 || Uin == Uout) return false;
   const Dom d = make_dom(Z, Y, X);
   const int na = d.n0, nb = d.nw - d.n0;
@@ -1044,9 +1044,9 @@ bool vorticity_confinement_fused(hipStream_t st, int B, int Z, int Y, int X, con
     // 32 x 16 tiles, two 512-thread blocks per CU (round 6): level with 64 x 16 at 128^3 (34.9 against 34.3 us) and at 256^3
     // (182.6 / 180.5) -- a CU issues the two blocks' steps no faster than the one big block's; kept for A/B only
     static const int tile = exp_env("TFL_VORT_TILE") ? atoi(exp_env("TFL_VORT_TILE")) : 64;
-    if (tile == 32 && launch_vort_pipe<32, 16>(st, d, B, X, Y, na, nb, Uin, Uout, flags, strength, xcd_order)) return true;
+    if (tile == 32 && launch_vort_pipe<32, 16>(st, d, B, X, Y, na, nb, Uin, Uout, flags, strength, xcd_order, f)) return true;
 #endif
-    if (launch_vort_pipe<64, 16>(st, d, B, X, Y, na, nb, Uin, Uout, flags, strength, xcd_order)) return true;
+    if (launch_vort_pipe<64, 16>(st, d, B, X, Y, na, nb, Uin, Uout, flags, strength, xcd_order, f)) return true;
   }
   const int cxn = (X + FBX - 1) / FBX, cyn = (Y + FBY - 1) / FBY;
   if ((long long)cxn * cyn * (na + nb) * B <= 0) return true;
@@ -1062,14 +1062,14 @@ bool vorticity_confinement_fused(hipStream_t st, int B, int Z, int Y, int X, con
 }
 
 bool vorticity_confinement(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags,
-                           float strength, float* curl, float* curl_norm, int stages, const float* Usrc) {
+                           float strength, float* curl, float* curl_norm, int stages, const float* Usrc, Fold& f) {
   const Dom d = make_dom(Z, Y, X);
   const dim3 blk(64, 4, 1), grd((X + 63) / 64, (Y + 3) / 4, (unsigned)(d.nw * B));
   const float* Uin = Usrc ? Usrc : U;
   const Vec4Launch v = vec4_launch(B, Z, Y, X, {U, flags, curl, curl_norm, Uin});
   const bool pa = stages & 1, pb = stages & 2;
   if (v.ok) {
-    const BcFoldArg fold = pb ? take_fold() : no_fold();   // pass B writes the operator's result
+    const BcFoldArg fold = pb ? f.hand_bc() : no_fold();   // pass B writes the operator's result
     const BlockOrder ord = make_block_order(v.grd.x, v.grd.y, v.grd.z, is3d && xcd_order_enabled(), xcd_run(v.grd.x, v.grd.y));
     if (is3d) {
       if (pa) { TFL_TIMED_EXT("k_curl", st); TFL_LAUNCH_EXT((k_curl_v4<true>), v.grd, v.blk, 0, st, d, Uin, curl, curl_norm, ord); }
