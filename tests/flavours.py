@@ -44,7 +44,8 @@ def experiments_flavour(fn):
             pytest.skip("fluidnet_amd/libtfluids_hip_exp.so is not built (make -C fluidnet_amd/csrc exp)")
         nodeid = os.environ["PYTEST_CURRENT_TEST"].rsplit(" ", 1)[0]
         env = dict(os.environ, TFL_LIBRARY=EXP_LIB)
-        out = subprocess.run([sys.executable, "-m", "pytest", nodeid, "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"], cwd=ROOT, env=env,
-                             capture_output=True, text=True, timeout=1800)
+        out = subprocess.run([sys.executable, "-m", "pytest", nodeid, "-q", "-s", "-x", "-m", "gpu", "-p", "no:cacheprovider"], cwd=ROOT,
+                             env=env, capture_output=True, text=True, timeout=1800)
         assert out.returncode == 0 and " passed" in out.stdout and "failed" not in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
+        print(out.stdout)       # what the child printed (shown under -s)
     return wrapper

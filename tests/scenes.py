@@ -82,6 +82,27 @@ def make_scene(dims, seed=0, B=1, vel_cells=2.5, dt=0.1, obstacles=True, empty_c
                 density=s.astype(np.float32), p=p.astype(np.float32), is3d=is3d, dt=dt)
 
 
+def rough_scene(dims, seed=0, B=1, obstacle_frac=0.1, empty_frac=0.0, dt=0.1):
+    """White-noise U and p, salt-and-pepper obstacles at about `obstacle_frac` of the cells inside the walls and, with
+    empty_frac > 0, empty cells: neighbouring voxels are uncorrelated, so a convolution tap that reads the wrong voxel is
+    off by O(1). (The projection net's FlagsToOccupancy refuses empty cells, generic/tfluids.cu:355-371, so scenes that
+    feed the net keep empty_frac = 0.)"""
+    Z, Y, X = dims
+    is3d = Z > 1
+    C = 3 if is3d else 2
+    rng = np.random.RandomState(seed)
+    flags = empty_domain(B, Z, Y, X, is3d)
+    inner = flags == FLUID
+    draw = rng.uniform(size=flags.shape)
+    flags[inner & (draw < obstacle_frac)] = OBSTACLE
+    flags[inner & (draw >= obstacle_frac) & (draw < obstacle_frac + empty_frac)] = EMPTY
+    U = rng.randn(B, C, Z, Y, X)
+    p = rng.randn(B, 1, Z, Y, X)
+    s = rng.uniform(0.1, 1.0, size=(B, 1, Z, Y, X))
+    return dict(flags=np.ascontiguousarray(flags, np.float32), U=U.astype(np.float32), density=s.astype(np.float32),
+                p=p.astype(np.float32), is3d=is3d, dt=dt)
+
+
 def rel_l2(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)
