@@ -86,9 +86,6 @@ static const int kMaxBatch = 1024;
 
 // ---- per-kernel event profiler (TFL_TIMED in the launchers) ---------------------------------------
 namespace tfl {
-thread_local ZWin g_zwin = {0, 0, 0, 0};
-thread_local ZOrigin g_zorigin = {0, 0};
-thread_local int g_advect_fast = 0;
 struct ProfRec { const char* name; hipEvent_t e0, e1; };
 struct Profiler { std::vector<ProfRec> recs; };
 static thread_local Profiler* g_prof = nullptr;
@@ -220,15 +217,6 @@ int check_scalar(tfl_ctx* ctx, const char* op, const char* name, const tfl_tenso
 }
 #define TRY(x) do { int rc_ = (x); if (rc_ != TFL_OK) return rc_; } while (0)
 
-// Operators that honour tfl_set_z_window open one of these before launching: the launchers read the window from the
-// calling thread (tfl_host.hpp make_dom); it is cleared again on the way out so that every other operator -- and every
-// other context used from this thread -- sees the whole array.
-struct WindowScope {
-  explicit WindowScope(const tfl_ctx* c) { tfl::g_zwin = c->zwin; tfl::g_zorigin = c->zorigin; tfl::g_advect_fast = c->advect_fast; }
-  ~WindowScope() { tfl::g_zwin = tfl::ZWin{0, 0, 0, 0}; tfl::g_zorigin = tfl::ZOrigin{0, 0}; tfl::g_advect_fast = 0; }
-};
-int stages_of(const tfl_ctx* c) { return c->stages ? c->stages : 0xff; }
-
 // generic/advect_type.cc:18-37
 int parse_method(const char* m) {
   if (!m) return -1;
@@ -237,15 +225,29 @@ int parse_method(const char* m) {
   return -1;
 }
 
-float get_dx(const tfl_ctx* c, const tfl_tensor* f) {  // grid.cc:37-40
-  if (c && c->dx_dim > 0) return 1.0f / (float)c->dx_dim;
-  if (c && c->dx_override > 0.0f) return c->dx_override;
-  int m = f->X > f->Y ? f->X : f->Y;
-  if (f->Z > m) m = f->Z;
-  return 1.0f / (float)m;
-}
-
 }  // namespace
+
+namespace tfl {
+// What the tfl_set_* calls left on the context, as the one value a public operator that honours them forms at its entry and
+// passes down (the operators that ignore them never call this). A null context gives the empty scope: the operator's own
+// checks refuse it.
+Scope scope_of(const tfl_ctx* c) {
+  Scope sc;
+  if (c) { sc.win = c->zwin; sc.origin = c->zorigin; sc.stages = c->stages; sc.advect_fast = c->advect_fast; }
+  return sc;
+}
+static int dx_cells(const Scope& sc, const tfl_tensor* f) {
+  return sc.dx_cells > 0 ? sc.dx_cells : std::max(std::max(f->X, f->Y), f->Z);
+}
+float get_dx(const tfl_ctx* c, const Scope& sc, const tfl_tensor* f) {  // grid.cc:37-40
+  if (sc.dx_cells <= 0 && c && c->dx_override > 0.0f) return c->dx_override;
+  return 1.0f / (float)dx_cells(sc, f);
+}
+double get_dx_double(const tfl_ctx* c, const Scope& sc, const tfl_tensor* f) {
+  if (sc.dx_cells <= 0 && c && c->dx_override > 0.0f) return (double)c->dx_override;
+  return 1.0 / (double)dx_cells(sc, f);
+}
+}  // namespace tfl
 
 // (library-internal, C++ linkage: the device word of a model's fp16 range counter, for the z-slab step's collective gate -- simulate.cpp)
 namespace tfl { const unsigned long long* model_range_counter(const tfl_model* m) { return m ? m->d_range_err : nullptr; } }
@@ -396,7 +398,7 @@ int64_t tfl_trace_errors(tfl_ctx* c) {
 namespace tfl {
 int advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* fwd,
                  const tfl_tensor* bwd, int is3D, const char* method, const tfl_tensor* fwdPos, const tfl_tensor* bwdPos,
-                 int boundaryWidth, int sampleOutsideFluid, float maccormackStrength, const tfl_tensor* sDst, Ask& ask) {
+                 int boundaryWidth, int sampleOutsideFluid, float maccormackStrength, const tfl_tensor* sDst, const Scope& sc, Ask& ask) {
   (void)bwd; (void)boundaryWidth;  // bnd = 1 like the reference (tfluids.cc:436,467)
   TRY(check_flags(c, "advectScalar", flags));
   TRY(check_vel(c, "advectScalar", "U", U, flags, is3D));
@@ -421,15 +423,14 @@ int advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor* U,
     bounds_p = fwdPos->data;   // two planes: clamp bounds of each cell's forward position
     mm_p = bwdPos->data;       // two planes: 3^dim fluid min / max grid of s
   }
-  WindowScope win(c);
-  tfl::advect_scalar(c->stream, is3D != 0, m, flags->B, flags->Z, flags->Y, flags->X, dt, maccormackStrength,
+  tfl::advect_scalar(c->stream, sc, is3D != 0, m, flags->B, flags->Z, flags->Y, flags->X, dt, maccormackStrength,
                      sampleOutsideFluid != 0, c->d_trace_err, s->data, U->data, flags->data, fwd_p, bounds_p, mm_p,
-                     sDst->data, stages_of(c), ask.fold);
+                     sDst->data, ask.fold);
   return check_launch(c, "advectScalar");
 }
 
 int advectVel(tfl_ctx* c, float dt, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* fwd, const tfl_tensor* bwd,
-              int is3D, const char* method, int boundaryWidth, float maccormackStrength, const tfl_tensor* UDst, Ask& ask) {
+              int is3D, const char* method, int boundaryWidth, float maccormackStrength, const tfl_tensor* UDst, const Scope& sc, Ask& ask) {
   (void)bwd; (void)boundaryWidth;
   TRY(check_flags(c, "advectVel", flags));
   TRY(check_vel(c, "advectVel", "U", U, flags, is3D));
@@ -442,17 +443,15 @@ int advectVel(tfl_ctx* c, float dt, const tfl_tensor* U, const tfl_tensor* flags
     TRY(check_vel(c, "advectVel", "fwd", fwd, flags, is3D));
     fwd_p = fwd->data;
   }
-  WindowScope win(c);
-  tfl::advect_vel(c->stream, is3D != 0, m, flags->B, flags->Z, flags->Y, flags->X, dt, maccormackStrength,
-                  c->d_trace_err, U->data, flags->data, fwd_p, UDst->data, stages_of(c), ask.fold);
+  tfl::advect_vel(c->stream, sc, is3D != 0, m, flags->B, flags->Z, flags->Y, flags->X, dt, maccormackStrength,
+                  c->d_trace_err, U->data, flags->data, fwd_p, UDst->data, ask.fold);
   return check_launch(c, "advectVel");
 }
 
-// (the z-slab step: both advections' passes A / passes B as one launch each, tfl_ops.hpp) Honours the z-window / z-origin /
-// advect mode of the context like the two operators.
+// (the z-slab step: both advections' passes A / passes B as one launch each, tfl_ops.hpp)
 int advect_pair(tfl_ctx* c, float dt, float strength, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags,
                 const tfl_tensor* sfwd, const tfl_tensor* sbounds, const tfl_tensor* sDst, const tfl_tensor* vfwd, const tfl_tensor* UDst,
-                const BcFoldArg& fold_s, const BcFoldArg& fold_v) {
+                const BcFoldArg& fold_s, const BcFoldArg& fold_v, const Scope& sc) {
   TRY(check_flags(c, "advectPair", flags));
   TRY(check_vel(c, "advectPair", "U", U, flags, 1));
   TRY(check_vel(c, "advectPair", "UDst", UDst, flags, 1));
@@ -462,11 +461,10 @@ int advect_pair(tfl_ctx* c, float dt, float strength, const tfl_tensor* s, const
   TRY(check_scalar(c, "advectPair", "sfwd", sfwd, flags));
   if (!sbounds || !sbounds->data || sbounds->C < 2 || !same_dims(sbounds, flags)) return fail(c, TFL_EINVAL, "advectPair: bounds needs two planes of the flags size");
   if (UDst->data == U->data) return fail(c, TFL_EINVAL, "advectPair: UDst must not alias U");
-  WindowScope win(c);
-  AdvArgs a; a.d = make_dom(flags->Z, flags->Y, flags->X); a.dt = dt; a.strength = strength; a.outside = 0; a.err = c->d_trace_err; a.fast = g_advect_fast;
+  AdvArgs a; a.d = make_dom(sc, flags->Z, flags->Y, flags->X); a.dt = dt; a.strength = strength; a.outside = 0; a.err = c->d_trace_err; a.fast = sc.advect_fast;
   a.ord = BlockOrder{};
   if (!advect_pair3(c->stream, a, flags->B, s->data, U->data, flags->data, sfwd->data, sbounds->data, sDst->data, vfwd->data, UDst->data,
-                    stages_of(c), fold_s, fold_v))
+                    sc.passes(), fold_s, fold_v))
     return TFL_EUNSUPPORTED;
   return check_launch(c, "advectPair");
 }
@@ -479,14 +477,14 @@ int tfl_advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor
                      float maccormackStrength, const tfl_tensor* sDst) {
   tfl::Ask none;
   return tfl::advectScalar(c, dt, s, U, flags, fwd, bwd, is3D, method, fwdPos, bwdPos, boundaryWidth, sampleOutsideFluid,
-                           maccormackStrength, sDst, none);
+                           maccormackStrength, sDst, tfl::scope_of(c), none);
 }
 
 int tfl_advectVel(tfl_ctx* c, float dt, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* fwd,
                   const tfl_tensor* bwd, int is3D, const char* method, int boundaryWidth, float maccormackStrength,
                   const tfl_tensor* UDst) {
   tfl::Ask none;
-  return tfl::advectVel(c, dt, U, flags, fwd, bwd, is3D, method, boundaryWidth, maccormackStrength, UDst, none);
+  return tfl::advectVel(c, dt, U, flags, fwd, bwd, is3D, method, boundaryWidth, maccormackStrength, UDst, tfl::scope_of(c), none);
 }
 
 int tfl_setWallBcsForward(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, int is3D) {
@@ -518,22 +516,21 @@ int tfl_velocityUpdateForward(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor*
 }  // extern "C"
 namespace tfl {      // (tfl_ops.hpp)
 int vorticityConfinement(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, float strength, const tfl_tensor* centered,
-                         const tfl_tensor* curl, const tfl_tensor* curlNorm, const tfl_tensor* force, int is3D, Ask& ask) {
+                         const tfl_tensor* curl, const tfl_tensor* curlNorm, const tfl_tensor* force, int is3D, const Scope& sc, Ask& ask) {
   (void)centered; (void)force;  // fused away (vorticity.hip)
   TRY(check_flags(c, "vorticityConfinement", flags));
   TRY(check_vel(c, "vorticityConfinement", "U", U, flags, is3D));
   if (!curl || !curl->data || curl->C != 3 || !same_dims(curl, flags))
     return fail(c, TFL_EINVAL, "vorticityConfinement: curl must be a 3-channel grid of the flags size");
   TRY(check_scalar(c, "vorticityConfinement", "curlNorm", curlNorm, flags));
-  WindowScope win(c);
-  const int stg = stages_of(c);   // tfl_set_stages: 2 = pass A (curl), 4 = pass B (confinement force)
-  tfl::vorticity_confinement(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data,
+  const int stg = sc.passes();   // tfl_set_stages: 2 = pass A (curl), 4 = pass B (confinement force)
+  tfl::vorticity_confinement(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data,
                              strength, curl->data, curlNorm->data, ((stg & 2) ? 1 : 0) | ((stg & 4) ? 2 : 0), nullptr, ask.fold);
   return check_launch(c, "vorticityConfinement");
 }
 
 int vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, float strength,
-                             const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D, Ask& ask) {
+                             const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D, const Scope& sc, Ask& ask) {
   TRY(check_flags(c, "vorticityConfinementFrom", flags));
   TRY(check_vel(c, "vorticityConfinementFrom", "U", U, flags, is3D));
   TRY(check_vel(c, "vorticityConfinementFrom", "USrc", USrc, flags, is3D));
@@ -541,29 +538,28 @@ int vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tenso
   if (!curl || !curl->data || curl->C != 3 || !same_dims(curl, flags))
     return fail(c, TFL_EINVAL, "vorticityConfinementFrom: curl must be a 3-channel grid of the flags size");
   TRY(check_scalar(c, "vorticityConfinementFrom", "curlNorm", curlNorm, flags));
-  WindowScope win(c);
   if (is3D && !ask.two_launch && tfl::vorticity_confinement_fused_ok(true, flags->Z, flags->Y, flags->X) &&
-      tfl::vorticity_confinement_fused(c->stream, flags->B, flags->Z, flags->Y, flags->X, USrc->data, U->data, flags->data, strength, ask.fold))
+      tfl::vorticity_confinement_fused(c->stream, sc, flags->B, flags->Z, flags->Y, flags->X, USrc->data, U->data, flags->data, strength, ask.fold))
     return check_launch(c, "vorticityConfinementFrom");
   // 2-D, a grid below the fused kernel's size, or TFL_VORT_FUSED=0: the two launches read USrc and write U (round 5) ...
   // Under a z-window pass A must cover what pass B taps: |curl| two planes below / one above, curl one below -- the
   // window widened by two planes either way, its two runs merged where they meet; pass B then runs on the window itself.
-  const tfl::ZWin w0 = tfl::g_zwin;
-  const bool windowed = w0.a1 > w0.a0 || w0.b1 > w0.b0;
+  const tfl::ZWin w0 = sc.win;
+  const bool windowed = sc.windowed();
   if (windowed) {
-    tfl::ZWin wa = {std::max(w0.a0 - 2, 0), std::min(w0.a1 + 2, (int)flags->Z), 0, 0};
+    tfl::Scope sa = sc;
+    tfl::ZWin& wa = sa.win;
+    wa = {std::max(w0.a0 - 2, 0), std::min(w0.a1 + 2, (int)flags->Z), 0, 0};
     if (w0.b1 > w0.b0) { wa.b0 = std::max(w0.b0 - 2, 0); wa.b1 = std::min(w0.b1 + 2, (int)flags->Z); }
     if (w0.a1 <= w0.a0) { wa.a0 = wa.b0; wa.a1 = wa.b1; wa.b0 = wa.b1 = 0; }
     else if (wa.b1 > wa.b0 && wa.b0 <= wa.a1) { wa.a1 = wa.b1; wa.b0 = wa.b1 = 0; }
-    tfl::g_zwin = wa;
-    const bool a_ok = tfl::vorticity_confinement(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
+    const bool a_ok = tfl::vorticity_confinement(c->stream, sa, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
                                                  curl->data, curlNorm->data, 1, USrc->data, ask.fold);
-    tfl::g_zwin = w0;
-    if (a_ok && tfl::vorticity_confinement(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
+    if (a_ok && tfl::vorticity_confinement(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
                                            curl->data, curlNorm->data, 2, USrc->data, ask.fold))
       return check_launch(c, "vorticityConfinementFrom");
     if (a_ok) return fail(c, TFL_EUNSUPPORTED, "vorticityConfinementFrom: pass B could not read USrc on this grid under a z-window");
-  } else if (tfl::vorticity_confinement(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
+  } else if (tfl::vorticity_confinement(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
                                         curl->data, curlNorm->data, 3, USrc->data, ask.fold))
     return check_launch(c, "vorticityConfinementFrom");
   if (windowed)      // (the one-cell kernels below run in place on a copy: the same two windows are needed there -- not built)
@@ -572,7 +568,7 @@ int vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tenso
   // ... or, where only the one-cell kernels apply (X % 4 != 0, misaligned views), the planes of the window are copied and the
   // two-launch form runs in place
   {
-    const tfl::Dom d = tfl::make_dom(flags->Z, flags->Y, flags->X);
+    const tfl::Dom d = tfl::make_dom(sc, flags->Z, flags->Y, flags->X);
     const size_t plane = sizeof(float) * (size_t)flags->Y * flags->X;
     const int C = is3D ? 3 : 2;
     for (int b = 0; b < flags->B; b++)
@@ -582,23 +578,32 @@ int vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tenso
         if (d.nw > d.n0) HIP_TRY(c, hipMemcpyAsync(U->data + (row + d.w1) * (plane / 4), USrc->data + (row + d.w1) * (plane / 4), plane * (d.nw - d.n0), hipMemcpyDeviceToDevice, c->stream));
       }
   }
-  tfl::vorticity_confinement(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
+  tfl::vorticity_confinement(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
                              curl->data, curlNorm->data, 3, nullptr, ask.fold);
   return check_launch(c, "vorticityConfinementFrom");
 }
 
 int addBuoyancyFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* density,
-                    const float gravity[3], float dt, int is3D, Ask& ask) {
+                    const float gravity[3], float dt, int is3D, const Scope& sc, Ask& ask) {
   TRY(check_flags(c, "addBuoyancy", flags));
   TRY(check_vel(c, "addBuoyancy", "U", U, flags, is3D));
   TRY(check_vel(c, "addBuoyancy", "USrc", USrc, flags, is3D));
   TRY(check_scalar(c, "addBuoyancy", "density", density, flags));
   if (!gravity) return fail(c, TFL_EINVAL, "addBuoyancy: gravity is null");
-  const float sc = dt / get_dx(c, flags);  // strength = -gravity * (dt / dx), tfluids.cc:1190-1192
-  WindowScope win(c);
-  tfl::add_buoyancy(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, USrc->data, U->data, flags->data,
-                    density->data, -gravity[0] * sc, -gravity[1] * sc, -gravity[2] * sc, ask.fold);
+  const float k = dt / get_dx(c, sc, flags);  // strength = -gravity * (dt / dx), tfluids.cc:1190-1192
+  tfl::add_buoyancy(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, USrc->data, U->data, flags->data,
+                    density->data, -gravity[0] * k, -gravity[1] * k, -gravity[2] * k, ask.fold);
   return check_launch(c, "addBuoyancy");
+}
+
+int addGravity(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const float gravity[3], float dt, int is3D, const Scope& sc) {
+  TRY(check_flags(c, "addGravity", flags));
+  TRY(check_vel(c, "addGravity", "U", U, flags, is3D));
+  if (!gravity) return fail(c, TFL_EINVAL, "addGravity: gravity is null");
+  const float k = dt / get_dx(c, sc, flags);  // force = gravity * (dt / dx), tfluids.cc:1265-1267
+  tfl::add_gravity(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data,
+                   gravity[0] * k, gravity[1] * k, gravity[2] * k);
+  return check_launch(c, "addGravity");
 }
 }  // namespace tfl
 extern "C" {
@@ -607,19 +612,19 @@ int tfl_vorticityConfinement(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* 
                              const tfl_tensor* centered, const tfl_tensor* curl, const tfl_tensor* curlNorm,
                              const tfl_tensor* force, int is3D) {
   tfl::Ask none;
-  return tfl::vorticityConfinement(c, U, flags, strength, centered, curl, curlNorm, force, is3D, none);
+  return tfl::vorticityConfinement(c, U, flags, strength, centered, curl, curlNorm, force, is3D, tfl::scope_of(c), none);
 }
 
 int tfl_vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, float strength,
                                  const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D) {
   tfl::Ask none;
-  return tfl::vorticityConfinementFrom(c, USrc, U, flags, strength, curl, curlNorm, is3D, none);
+  return tfl::vorticityConfinementFrom(c, USrc, U, flags, strength, curl, curlNorm, is3D, tfl::scope_of(c), none);
 }
 
 int tfl_addBuoyancyFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags,
                         const tfl_tensor* density, const float gravity[3], float dt, int is3D) {
   tfl::Ask none;
-  return tfl::addBuoyancyFrom(c, USrc, U, flags, density, gravity, dt, is3D, none);
+  return tfl::addBuoyancyFrom(c, USrc, U, flags, density, gravity, dt, is3D, tfl::scope_of(c), none);
 }
 
 int tfl_addBuoyancy(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* density,
@@ -631,14 +636,7 @@ int tfl_addBuoyancy(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, co
 int tfl_addGravity(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const float gravity[3], float dt,
                    int is3D, float* forceTmp) {
   (void)forceTmp;
-  TRY(check_flags(c, "addGravity", flags));
-  TRY(check_vel(c, "addGravity", "U", U, flags, is3D));
-  if (!gravity) return fail(c, TFL_EINVAL, "addGravity: gravity is null");
-  const float sc = dt / get_dx(c, flags);  // force = gravity * (dt / dx), tfluids.cc:1265-1267
-  WindowScope win(c);
-  tfl::add_gravity(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data,
-                   gravity[0] * sc, gravity[1] * sc, gravity[2] * sc);
-  return check_launch(c, "addGravity");
+  return tfl::addGravity(c, U, flags, gravity, dt, is3D, tfl::scope_of(c));
 }
 
 int tfl_emptyDomain(tfl_ctx* c, const tfl_tensor* flags, int is3D, int bnd) {
@@ -1278,7 +1276,7 @@ static int graph_gate(tfl_ctx* c, const tfl_model* m, const tfl_tensor* flags, c
 }  // extern "C"
 namespace tfl {      // (tfl_ops.hpp)
 int model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tensor* flags, const tfl_tensor* UOut, float* workspace,
-                int64_t workspace_floats, int zlo, int zhi, double* stats, Ask& ask) {
+                int64_t workspace_floats, int zlo, int zhi, double* stats, const Scope& sc, Ask& ask) {
   TRY(check_flags(c, "model_begin", flags));
   if (!m) return fail(c, TFL_EINVAL, "model_begin: null model");
   if (ask.gated) TRY(range_gate(c, m, "model_begin"));
@@ -1292,12 +1290,11 @@ int model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tens
   // SetWallBcs(UDiv) lands in UOut. UOut may alias UDiv: a thread rewrites only the cell it read, and
   // neighbour values are re-derived from the flags, so a neighbour already holding the BC-applied
   // value gives the identical result (the BC is idempotent).
-  WindowScope win(c);
-  int stg = stages_of(c);   // tfl_set_stages: 2 = wall BCs + divergence + partial sums, 4 = reduce [zlo, zhi)
+  int stg = sc.passes();   // tfl_set_stages: 2 = wall BCs + divergence + partial sums, 4 = reduce [zlo, zhi)
   if (ask.conv1_sums_stats) stg &= ~4;   // tfl_model_forward: the first conv layer reduces the partials itself (round 6)
   m->stat_pairs_per_plane = tfl::model_stat_pairs_per_plane(flags->B, flags->Z, flags->Y, flags->X, UDiv->data, flags->data, UOut->data, w.div);
   const unsigned short* code = wall_code_of(c, m, flags);
-  tfl::model_pre(c->stream, m->is3d, flags->B, flags->Z, flags->Y, flags->X, UDiv->data, flags->data, UOut->data,
+  tfl::model_pre(c->stream, sc, m->is3d, flags->B, flags->Z, flags->Y, flags->X, UDiv->data, flags->data, UOut->data,
                  w.div, w.partials, stats ? stats : m->d_stats, zlo, zhi, ((stg & 2) ? 1 : 0) | ((stg & 4) ? 2 : 0), m->d_ticket, code);
   return check_launch(c, "model_begin");
 }
@@ -1307,7 +1304,7 @@ extern "C" {
 int tfl_model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tensor* flags, const tfl_tensor* UOut,
                     float* workspace, int64_t workspace_floats, int zlo, int zhi, double* stats) {
   tfl::Ask none;
-  return tfl::model_begin(c, m, UDiv, flags, UOut, workspace, workspace_floats, zlo, zhi, stats, none);
+  return tfl::model_begin(c, m, UDiv, flags, UOut, workspace, workspace_floats, zlo, zhi, stats, tfl::scope_of(c), none);
 }
 
 tfl_wall_plan* tfl_wall_plan_create(tfl_ctx* c, const tfl_tensor* flags) {
@@ -1319,7 +1316,6 @@ tfl_wall_plan* tfl_wall_plan_create(tfl_ctx* c, const tfl_tensor* flags) {
   if (hipMalloc((void**)&p->code, (size_t)n * sizeof(unsigned short)) != hipSuccess) { (void)hipGetLastError(); c->err = "wall_plan_create: hipMalloc failed"; delete p; return nullptr; }
   (void)hipDeviceSynchronize();               // one-time set-up: whoever filled the flags (any stream) is done
   p->is3d = flags->Z > 1; p->owner = c;
-  // (outside a WindowScope the thread's z-window is empty: the launch covers every plane, whatever window the host has set)
   tfl::wall_code(c->stream, p->is3d, flags->B, flags->Z, flags->Y, flags->X, flags->data, p->code);
   if (hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p->code); c->err = "wall_plan_create: the code kernel failed"; delete p; return nullptr; }
   std::lock_guard<std::mutex> lock(c->wall_mu);
@@ -1352,18 +1348,18 @@ void tfl_wall_plan_destroy(tfl_ctx* c, tfl_wall_plan* p) {
 
 namespace {
 // What every forward of tfl_model_finish reads. U: the wall-BC'd velocity tfl_model_begin left in UOut; (st_in, count): the
-// input scale; stg: the tfl_set_stages mask.
+// input scale; sc: the window and stage mask of the call.
 struct Fwd {
   hipStream_t st;
   int B, Z, Y, X;
   const float *pDiv, *U, *flags;
   const double* st_in; double count;
-  int stg; bool windowed;     // windowed: a z-window is set
+  const tfl::Scope& sc;
   bool conv1_sums_stats;      // tfl_model_forward (whole array, the model's own stats buffer): conv layer 1 sums the partials
 };
 
 // the net input {pDiv/scale, div/scale, occupancy}, or the channels tfl_model_opts selects, into w.x3 on the planes
-// [z0, z0 + nz) (nz < 0: the thread's z-window)
+// [z0, z0 + nz) (nz < 0: every plane)
 void net_input(const tfl_model* m, const ModelWs& w, const Fwd& a, int z0, int nz) {
   if (m->custom)
     tfl::model_net_input_gen(a.st, m->is3d, a.B, a.Z, a.Y, a.X, m->opts.in_pDiv, m->opts.in_UDiv, m->opts.in_div, a.pDiv,
@@ -1487,41 +1483,41 @@ int opts_stats(tfl_ctx* c, const tfl_model* m, const ModelWs& w, Fwd& a) {
 // Split-operand fp16 MFMA (conv_mfma16.hip); the two activation buffers hold the "h2" form (32 B per voxel, as 8 fp32).
 // Layers 1 + 2 in one launch where the whole array is computed (round 5); a z-slab rank runs them under separate windows.
 void forward_mfma16(const tfl_model* m, const ModelWs& w, const Fwd& a) {
-  const bool fused12 = (a.stg & 3) == 3 &&
-                       tfl::conv3_m16_first2_fused(a.st, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0],
+  const bool fused12 = (a.sc.passes() & 3) == 3 &&
+                       tfl::conv3_m16_first2_fused(a.st, a.sc, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0],
                                                    m->layers[0].b, m->post16[0], m->wfrag16[1], m->layers[1].b, m->post16[1],
                                                    w.act[1], m->d_range_err);
-  if ((a.stg & 1) && !fused12) {
+  if ((a.sc.passes() & 1) && !fused12) {
     if (a.conv1_sums_stats)
-      tfl::conv3_m16_first_fused(a.st, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0], m->layers[0].b,
+      tfl::conv3_m16_first_fused(a.st, a.sc, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0], m->layers[0].b,
                                  m->post16[0], w.act[0], m->d_range_err, w.partials, m->stat_pairs_per_plane * a.Z, m->d_stats);
     else
-      tfl::conv3_m16_first_fused(a.st, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0], m->layers[0].b,
+      tfl::conv3_m16_first_fused(a.st, a.sc, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0], m->layers[0].b,
                                  m->post16[0], w.act[0], m->d_range_err);
   }
-  if ((a.stg & 2) && !fused12)
-    tfl::conv3_m16_mid(a.st, a.B, a.Z, a.Y, a.X, w.act[0], m->wfrag16[1], m->layers[1].b, m->post16[1], w.act[1], m->d_range_err);
-  if (a.stg & 4)
-    tfl::conv3_m16_tail(a.st, a.B, a.Z, a.Y, a.X, w.act[1], m->wfrag16[2], m->tail_pack, m->post16[2], w.pPred, m->d_range_err);
+  if ((a.sc.passes() & 2) && !fused12)
+    tfl::conv3_m16_mid(a.st, a.sc, a.B, a.Z, a.Y, a.X, w.act[0], m->wfrag16[1], m->layers[1].b, m->post16[1], w.act[1], m->d_range_err);
+  if (a.sc.passes() & 4)
+    tfl::conv3_m16_tail(a.st, a.sc, a.B, a.Z, a.Y, a.X, w.act[1], m->wfrag16[2], m->tail_pack, m->post16[2], w.pPred, m->d_range_err);
 }
 
 // fp32 Winograd on the vector ALUs (conv_valu.hip): the first layer builds {pDiv/scale, div/scale, occupancy} while staging
 // its LDS tile
 void forward_valu(const tfl_model* m, const ModelWs& w, const Fwd& a) {
-  if (a.stg & 1)
-    tfl::conv3_valu_first_fused(a.st, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wino[0], m->layers[0].b, w.act[0]);
-  if (a.stg & 2) tfl::conv3_valu_mid(a.st, a.B, a.Z, a.Y, a.X, w.act[0], m->wino[1], m->layers[1].b, w.act[1]);
-  if (a.stg & 4) tfl::conv3_valu_tail(a.st, a.B, a.Z, a.Y, a.X, w.act[1], m->wino[2], m->tail_pack, w.pPred);
+  if (a.sc.passes() & 1)
+    tfl::conv3_valu_first_fused(a.st, a.sc, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wino[0], m->layers[0].b, w.act[0]);
+  if (a.sc.passes() & 2) tfl::conv3_valu_mid(a.st, a.sc, a.B, a.Z, a.Y, a.X, w.act[0], m->wino[1], m->layers[1].b, w.act[1]);
+  if (a.sc.passes() & 4) tfl::conv3_valu_tail(a.st, a.sc, a.B, a.Z, a.Y, a.X, w.act[1], m->wino[2], m->tail_pack, w.pPred);
 }
 
 // fp32-operand MFMA (conv_mfma.hip): the first layer builds {pDiv/scale, div/scale, occupancy} while staging its LDS tile
 void forward_mfma(const tfl_model* m, const ModelWs& w, const Fwd& a) {
-  if (a.stg & 1)
-    tfl::conv3_mfma_first_fused(a.st, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->bfrag[0],
+  if (a.sc.passes() & 1)
+    tfl::conv3_mfma_first_fused(a.st, a.sc, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->bfrag[0],
                                 m->layers[0].b, w.act[0]);
-  if (a.stg & 2) tfl::conv3_mfma_mid(a.st, a.B, a.Z, a.Y, a.X, w.act[0], m->bfrag[1], m->layers[1].b, w.act[1]);
-  if (a.stg & 4)
-    tfl::conv3_mfma_tail(a.st, a.B, a.Z, a.Y, a.X, w.act[1], m->bfrag[2], m->layers[2].b, m->tail_w4, m->layers[3].b,
+  if (a.sc.passes() & 2) tfl::conv3_mfma_mid(a.st, a.sc, a.B, a.Z, a.Y, a.X, w.act[0], m->bfrag[1], m->layers[1].b, w.act[1]);
+  if (a.sc.passes() & 4)
+    tfl::conv3_mfma_tail(a.st, a.sc, a.B, a.Z, a.Y, a.X, w.act[1], m->bfrag[2], m->layers[2].b, m->tail_w4, m->layers[3].b,
                          m->tail_w5, m->layers[4].b, w.pPred);
 }
 
@@ -1539,7 +1535,8 @@ void forward_mfma2d(const tfl_model* m, const ModelWs& w, const Fwd& a) {
 int generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a) {
   hipStream_t st = a.st;
   const int B = a.B, Z = a.Z, Y = a.Y, X = a.X;
-  const bool windowed = a.windowed;
+  const bool windowed = a.sc.windowed();
+  const tfl::ZWin& win = a.sc.win;
   if (m->multires && ((m->is3d && Z % m->max_down) || Y % m->max_down || X % m->max_down))
     return fail(c, TFL_EINVAL, "model_finish: grid %dx%dx%d is not divisible by the model's pooling factor %d", Z, Y, X, m->max_down);
   const size_t nl = m->layers.size();
@@ -1548,8 +1545,8 @@ int generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd&
   if (windowed) {
     const char* why = nullptr;
     if (!tfl::model_cone(m, &cone, &why)) return fail(c, TFL_EUNSUPPORTED, "model_finish: %s", why);
-    if (c->zwin.b1 > c->zwin.b0) return fail(c, TFL_EINVAL, "model_finish: the shape-generic forward takes one z-window run");
-    za = std::max(c->zwin.a0, 0); zb = std::min(c->zwin.a1, Z);
+    if (win.b1 > win.b0) return fail(c, TFL_EINVAL, "model_finish: the shape-generic forward takes one z-window run");
+    za = std::max(win.a0, 0); zb = std::min(win.a1, Z);
     if (za % cone.F || zb % cone.F)
       return fail(c, TFL_EINVAL, "model_finish: z-window [%d, %d) is not aligned to the model's downsampling factor %d", za, zb, cone.F);
   }
@@ -1605,7 +1602,7 @@ int generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd&
 namespace tfl {      // (tfl_ops.hpp)
 int model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* flags, const tfl_tensor* pOut,
                  const tfl_tensor* UOut, float* workspace, int64_t workspace_floats, const double* stats, double count,
-                 const tfl_tensor* UBC, const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, Ask& ask) {
+                 const tfl_tensor* UBC, const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, const Scope& sc, Ask& ask) {
   TRY(check_flags(c, "model_finish", flags));
   if (!m) return fail(c, TFL_EINVAL, "model_finish: null model");
   const int is3D = m->is3d ? 1 : 0;
@@ -1621,33 +1618,32 @@ int model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_ten
   ModelWs w;
   TRY(model_ws(c, m, flags, workspace, workspace_floats, &w));
   TRY(graph_gate(c, m, flags, "model_finish"));
-  const bool windowed = c->zwin.a1 > c->zwin.a0 || c->zwin.b1 > c->zwin.b0;
-  if (m->path == ConvPath::graph && (stats || c->stages || windowed))
+  const bool windowed = sc.windowed();
+  if (m->path == ConvPath::graph && (stats || sc.stages || windowed))
     return fail(c, TFL_EUNSUPPORTED, "model_finish: banked, batch-norm and max-pool models run un-sharded only");
-  if (m->custom && !stats && (c->stages || windowed))
+  if (m->custom && !stats && (sc.stages || windowed))
     return fail(c, TFL_EUNSUPPORTED, "model_finish: a windowed forward of a model with non-default tfl_model_opts takes the caller's "
                                      "input-scale stats over the owned planes (tfl_simulate_step_slab forms them)");
   Fwd a{c->stream, flags->B, flags->Z, flags->Y, flags->X, pDiv->data, UOut->data, flags->data, stats ? stats : m->d_stats,
-        count, 0, windowed, ask.conv1_sums_stats};
+        count, sc, ask.conv1_sums_stats};
   if (m->custom && !stats) TRY(opts_stats(c, m, w, a));
-  WindowScope win(c);
   // tfl_set_stages (z-slab ranks run each layer under its own z-window): the 3-D default topology's forms take stage bits 1,
   // 2 and 4 (see there); the other 3-D linear models take 1 = the whole net, each launch on its layer's cone of the
   // z-window's planes. 8 = velocity update / un-scale / wall BCs on the window.
-  a.stg = stages_of(c);
-  if (c->stages && !default3(m->path) && !(m->path == ConvPath::generic && m->is3d))
+  const int stg = sc.passes();
+  if (sc.stages && !default3(m->path) && !(m->path == ConvPath::generic && m->is3d))
     return fail(c, TFL_EUNSUPPORTED, "model_finish: stage masks need a 3-D model that is not a graph model");
   switch (m->path) {
     case ConvPath::conv_mfma16: forward_mfma16(m, w, a); break;
     case ConvPath::conv_valu: forward_valu(m, w, a); break;
     case ConvPath::conv_mfma: forward_mfma(m, w, a); break;
     case ConvPath::conv2d_mfma: forward_mfma2d(m, w, a); break;
-    case ConvPath::generic: if (a.stg & 1) TRY(generic_forward(c, m, w, a)); break;
+    case ConvPath::generic: if (stg & 1) TRY(generic_forward(c, m, w, a)); break;
     case ConvPath::graph: TRY(graph_forward(c, m, w, a)); break;
   }
-  if (a.stg & 8) {
+  if (stg & 8) {
     const bool pub = ask.reach_via_project;
-    ask.reach_folded = tfl::model_project(a.st, m->is3d, a.B, a.Z, a.Y, a.X, w.pPred, flags->data, a.st_in, a.count, UOut->data,
+    ask.reach_folded = tfl::model_project(a.st, sc, m->is3d, a.B, a.Z, a.Y, a.X, w.pPred, flags->data, a.st_in, a.count, UOut->data,
                                           pOut->data, UBC ? UBC->data : nullptr, UBC ? UBCInvMask->data : nullptr, doClamp, lo, hi,
                                           m->d_range_host ? m->d_range_err : nullptr, m->d_range_host, pub ? c->d_reach : nullptr,
                                           pub ? c->d_reach_host : nullptr, pub ? c->d_reach : nullptr, wall_code_of(c, m, flags),
@@ -1659,17 +1655,17 @@ int model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_ten
 
 int model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
                   const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace, int64_t workspace_floats, const tfl_tensor* UBC,
-                  const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, Ask& ask) {
+                  const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, const Scope& sc, Ask& ask) {
   TRY(check_flags(c, "model_forward", flags));
-  if (c->stages || c->zwin.a1 > c->zwin.a0 || c->zwin.b1 > c->zwin.b0)
+  if (sc.stages || sc.windowed())
     return fail(c, TFL_EINVAL, "model_forward: clear the z-window / stage mask first (use tfl_model_begin / _finish)");
   // round 6: with the default 3-D conv path the first layer's blocks sum k_bcs_div_stats' partial pairs themselves (the same
   // order, the same bits) -- no k_reduce_stats launch between the two kernels (4.3 us of pure latency at 128^3)
   ask.conv1_sums_stats = m && m->path == ConvPath::conv_mfma16 && conv3_m16_first_sums_partials() && !conv3_m16_fuse12_requested() &&
                          !model_stats_fold_requested();
-  TRY(model_begin(c, m, UDiv, flags, UOut, workspace, workspace_floats, 0, flags->Z, nullptr, ask));
+  TRY(model_begin(c, m, UDiv, flags, UOut, workspace, workspace_floats, 0, flags->Z, nullptr, sc, ask));
   const double count = (double)flags->Z * flags->Y * flags->X * (m->is3d ? 3 : 2);
-  return model_finish(c, m, pDiv, flags, pOut, UOut, workspace, workspace_floats, nullptr, count, UBC, UBCInvMask, doClamp, lo, hi, ask);
+  return model_finish(c, m, pDiv, flags, pOut, UOut, workspace, workspace_floats, nullptr, count, UBC, UBCInvMask, doClamp, lo, hi, sc, ask);
 }
 }  // namespace tfl
 extern "C" {
@@ -1679,7 +1675,7 @@ int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl
                      const double* stats, double count, const tfl_tensor* UBC, const tfl_tensor* UBCInvMask,
                      int doClamp, float lo, float hi) {
   tfl::Ask none;
-  return tfl::model_finish(c, m, pDiv, flags, pOut, UOut, workspace, workspace_floats, stats, count, UBC, UBCInvMask, doClamp, lo, hi, none);
+  return tfl::model_finish(c, m, pDiv, flags, pOut, UOut, workspace, workspace_floats, stats, count, UBC, UBCInvMask, doClamp, lo, hi, tfl::scope_of(c), none);
 }
 
 int tfl_model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* UDiv,
@@ -1687,16 +1683,12 @@ int tfl_model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tf
                       int64_t workspace_floats, const tfl_tensor* UBC, const tfl_tensor* UBCInvMask, int doClamp,
                       float lo, float hi) {
   tfl::Ask none;
-  return tfl::model_forward(c, m, pDiv, UDiv, flags, pOut, UOut, workspace, workspace_floats, UBC, UBCInvMask, doClamp, lo, hi, none);
+  return tfl::model_forward(c, m, pDiv, UDiv, flags, pOut, UOut, workspace, workspace_floats, UBC, UBCInvMask, doClamp, lo, hi, tfl::scope_of(c), none);
 }
 
 double tfl_getDx(tfl_ctx* c, const tfl_tensor* flags) {
   if (!flags) return 0.0;
-  if (c && c->dx_dim > 0) return 1.0 / (double)c->dx_dim;
-  if (c && c->dx_override > 0.0f) return (double)c->dx_override;
-  int m = flags->X > flags->Y ? flags->X : flags->Y;
-  if (flags->Z > m) m = flags->Z;
-  return 1.0 / (double)m;
+  return tfl::get_dx_double(c, tfl::Scope{}, flags);
 }
 
 int tfl_copy(tfl_ctx* c, const tfl_tensor* dst, const tfl_tensor* src) {

@@ -382,18 +382,17 @@ static void launch_scalar(hipStream_t st, int method, const AdvArgs& a, int B, c
       if (pb) { TFL_TIMED("k_scalar_bwd", st); k_scalar_bwd<IS3D, kMacCormack><<<grd, blk, 0, st>>>(a, s, U, flags, fwd, nullptr, dst); }
       break;
     default:
-      if (pm) minmax3(st, IS3D, B, a.d.Z, a.d.Y, a.d.X, a.outside, s, flags, mm, mm + (long long)B * a.d.sc);
+      if (pm) minmax3(st, IS3D, B, a.d, a.outside, s, flags, mm, mm + (long long)B * a.d.sc);
       if (pa) { TFL_TIMED_EXT("k_scalar_fwd", st); TFL_LAUNCH_EXT((k_scalar_fwd<IS3D, kMacCormackOurs>), grd, blk, 0, st, a, s, U, flags, fwd, bounds, (const float*)mm, (const float*)(mm + (long long)B * a.d.sc)); }
       if (pb) { TFL_TIMED_EXT("k_scalar_bwd", st); TFL_LAUNCH_EXT((k_scalar_bwd<IS3D, kMacCormackOurs>), grd, blk, 0, st, a, s, U, flags, (const float*)fwd, (const float*)bounds, dst); }
       break;
   }
 }
 
-void minmax3(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int outside, const float* s, const float* flags,
-             float* lo3, float* hi3) {
-  const Dom d = make_dom(Z, Y, X);
+void minmax3(hipStream_t st, bool is3d, int B, const Dom& d, int outside, const float* s, const float* flags, float* lo3,
+             float* hi3) {
   const dim3 blk(64, 4, 1), grd = cell_grid(d, B, blk);
-  const Vec4Launch v = vec4_launch(B, Z, Y, X, {s, flags, lo3, hi3});
+  const Vec4Launch v = vec4_launch(B, d, {s, flags, lo3, hi3});
   if (v.ok) {
     TFL_TIMED_EXT("k_minmax3", st);
     if (is3d) TFL_LAUNCH_EXT((k_minmax3_v4<true>), v.grd, v.blk, 0, st, d, outside, s, flags, lo3, hi3);
@@ -405,10 +404,11 @@ void minmax3(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int outside,
   else k_minmax3<false><<<grd, blk, 0, st>>>(d, outside, s, flags, lo3, hi3);
 }
 
-void advect_scalar(hipStream_t st, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
+void advect_scalar(hipStream_t st, const Scope& sc, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
                    int outside, unsigned long long* err, const float* s, const float* U, const float* flags,
-                   float* fwd, float* bounds, float* mm, float* dst, int stages, Fold& f) {
-  AdvArgs a; a.d = make_dom(Z, Y, X); a.dt = dt; a.strength = strength; a.outside = outside; a.err = err; a.fast = g_advect_fast;
+                   float* fwd, float* bounds, float* mm, float* dst, Fold& f) {
+  AdvArgs a; a.d = make_dom(sc, Z, Y, X); a.dt = dt; a.strength = strength; a.outside = outside; a.err = err; a.fast = sc.advect_fast;
+  const int stages = sc.passes();
   if (is3d) launch_scalar<true>(st, method, a, B, s, U, flags, fwd, bounds, mm, dst, stages, f);
   else launch_scalar<false>(st, method, a, B, s, U, flags, fwd, bounds, mm, dst, stages, f);
 }
@@ -437,10 +437,11 @@ static void launch_vel(hipStream_t st, int method, const AdvArgs& a, int B, cons
   }
 }
 
-void advect_vel(hipStream_t st, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
-                unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, int stages, Fold& f) {
+void advect_vel(hipStream_t st, const Scope& sc, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
+                unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, Fold& f) {
   if (method == kRK2Ours || method == kRK3Ours) method = kMacCormackOurs;  // tfluids.cc:799-802
-  AdvArgs a; a.d = make_dom(Z, Y, X); a.dt = dt; a.strength = strength; a.outside = 0; a.err = err; a.fast = g_advect_fast;
+  AdvArgs a; a.d = make_dom(sc, Z, Y, X); a.dt = dt; a.strength = strength; a.outside = 0; a.err = err; a.fast = sc.advect_fast;
+  const int stages = sc.passes();
   if (is3d) launch_vel<true>(st, method, a, B, U, flags, fwd, dst, stages, f);
   else launch_vel<false>(st, method, a, B, U, flags, fwd, dst, stages, f);
 }

@@ -126,8 +126,8 @@ __global__ __launch_bounds__(256) void k_upsample_bwd(int ratio, long long rows,
 
 #define TFL_BWD_LAUNCH(kern, name, ...)                                             \
   do {                                                                              \
-    const Dom d = make_dom(Z, Y, X);                                                \
-    const dim3 blk(64, 4, 1), grd((X + 63) / 64, (Y + 3) / 4, (unsigned)(zwin_planes(Z) * B)); \
+    const Dom d = whole_dom(Z, Y, X);                                                \
+    const dim3 blk(64, 4, 1), grd((X + 63) / 64, (Y + 3) / 4, (unsigned)(d.nw * B)); \
     TFL_TIMED(name, st);                                                            \
     if (is3d) kern<true><<<grd, blk, 0, st>>>(d, __VA_ARGS__);                      \
     else kern<false><<<grd, blk, 0, st>>>(d, __VA_ARGS__);                          \

@@ -277,8 +277,8 @@ static void launch_direct(hipStream_t st, const Dom& d, int B, int cin, int ksz,
 static bool conv_direct_any(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int cin, int cout, int ksz, int act,
                             const float* in, const float* w, const float* bias, float* out, int upf, int sub, int out_ch,
                             const ConvEx* ex, int z0 = 0, int nz = -1) {
-  Dom d = make_dom(Z, Y, X);
-  // the shape-generic path covers the planes it is given, not the thread's z-window: the whole grid, or (z-slab rank) the
+  Dom d = whole_dom(Z, Y, X);
+  // the shape-generic path covers the planes it is given and takes no scope: the whole grid, or (z-slab rank) the
   // planes [z0, z0 + nz) of this layer's cone (the model-graph form: always the whole grid)
   if (ex || nz < 0) { z0 = 0; nz = Z; }
   d.w0 = z0; d.n0 = nz; d.w1 = 0; d.nw = nz;

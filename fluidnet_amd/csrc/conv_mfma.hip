@@ -326,33 +326,33 @@ static void launch_mfma(hipStream_t st, const Dom& d, int B, const float* in, co
 }
 
 // 3 -> 8 (planar in) / 8 -> 8 (channel-last in), k = 3, ReLU; channel-last [Z][Y][X][8] out.
-void conv3_mfma_first(hipStream_t st, int B, int Z, int Y, int X, const float* in_planar3, const float* bfrag,
+void conv3_mfma_first(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* in_planar3, const float* bfrag,
                       const float* bias, float* out_cl8) {
   ConvTail none = {nullptr, nullptr, nullptr, nullptr};
   ConvIn noin = {nullptr, nullptr, nullptr, nullptr, 0.0};
-  launch_mfma<3, true, false>(st, make_dom(Z, Y, X), B, in_planar3, bfrag, bias, out_cl8, none, noin);
+  launch_mfma<3, true, false>(st, make_dom(sc, Z, Y, X), B, in_planar3, bfrag, bias, out_cl8, none, noin);
 }
 // the same with the network input {pDiv/scale, div/scale, occupancy} built on the fly while staging
-void conv3_mfma_first_fused(hipStream_t st, int B, int Z, int Y, int X, const float* pDiv, const float* div,
+void conv3_mfma_first_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* pDiv, const float* div,
                             const float* flags, const double* stats, double count, const float* bfrag,
                             const float* bias, float* out_cl8) {
   ConvTail none = {nullptr, nullptr, nullptr, nullptr};
   ConvIn ci = {pDiv, div, flags, stats, count};
-  launch_mfma<3, true, false>(st, make_dom(Z, Y, X), B, pDiv, bfrag, bias, out_cl8, none, ci);
+  launch_mfma<3, true, false>(st, make_dom(sc, Z, Y, X), B, pDiv, bfrag, bias, out_cl8, none, ci);
 }
-void conv3_mfma_mid(hipStream_t st, int B, int Z, int Y, int X, const float* in_cl8, const float* bfrag,
+void conv3_mfma_mid(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* in_cl8, const float* bfrag,
                     const float* bias, float* out_cl8) {
   ConvTail none = {nullptr, nullptr, nullptr, nullptr};
   ConvIn noin = {nullptr, nullptr, nullptr, nullptr, 0.0};
-  launch_mfma<8, false, false>(st, make_dom(Z, Y, X), B, in_cl8, bfrag, bias, out_cl8, none, noin);
+  launch_mfma<8, false, false>(st, make_dom(sc, Z, Y, X), B, in_cl8, bfrag, bias, out_cl8, none, noin);
 }
 // 8 -> 8 k3 + ReLU, then 8 -> 8 k1 + ReLU, then 8 -> 1 k1; planar pressure out.
-void conv3_mfma_tail(hipStream_t st, int B, int Z, int Y, int X, const float* in_cl8, const float* bfrag,
+void conv3_mfma_tail(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* in_cl8, const float* bfrag,
                      const float* bias, const float* w4, const float* b4, const float* w5, const float* b5,
                      float* p_out) {
   ConvTail tail = {w4, b4, w5, b5};
   ConvIn noin = {nullptr, nullptr, nullptr, nullptr, 0.0};
-  launch_mfma<8, false, true>(st, make_dom(Z, Y, X), B, in_cl8, bfrag, bias, p_out, tail, noin);
+  launch_mfma<8, false, true>(st, make_dom(sc, Z, Y, X), B, in_cl8, bfrag, bias, p_out, tail, noin);
 }
 
 }  // namespace tfl

@@ -756,26 +756,26 @@ bool conv3_m16_first_sums_partials() {
   const char* e = getenv("TFL_STATS_CONSUMER");     // A/B switch (read per call: the parity test flips it inside one process): 0 = k_reduce_stats as its own launch
   return !(e && atoi(e) == 0);
 }
-void conv3_m16_first_fused(hipStream_t st, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
+void conv3_m16_first_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
                            const double* stats, double count, const void* wfrag, const float* bias, float post, void* out_h2,
                            unsigned long long* range_err, const double* partials, long long per_sample, double* stats_out) {
   MIn ci = {pDiv, div, flags, stats, count, partials, per_sample, stats_out};
 #ifdef TFL_EXPERIMENTS
-  if (exp_kpack() == 0 || exp_kpack() == 2) { launch_m16<kModeIn>(st, make_dom(Z, Y, X), B, nullptr, wfrag, bias, out_h2, post, ci, range_err); return; }
+  if (exp_kpack() == 0 || exp_kpack() == 2) { launch_m16<kModeIn>(st, make_dom(sc, Z, Y, X), B, nullptr, wfrag, bias, out_h2, post, ci, range_err); return; }
 #endif
-  launch_m16p_in(st, make_dom(Z, Y, X), B, ci, wfrag, bias, out_h2, post, range_err);
+  launch_m16p_in(st, make_dom(sc, Z, Y, X), B, ci, wfrag, bias, out_h2, post, range_err);
 }
 // layers 1 + 2 in ONE launch (k_conv3_m16p_f2, conv_mfma16_exp.inc): measured slower than the two launches (round 5), so only
 // the EXPERIMENTS flavour carries it (TFL_M16_FUSE12=1); false = not taken, the caller runs the two layers
-bool conv3_m16_first2_fused(hipStream_t st, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
+bool conv3_m16_first2_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
                             const double* stats, double count, const void* wfrag1, const float* bias1, float post1,
                             const void* wfrag2, const float* bias2, float post2, void* out_h2, unsigned long long* range_err) {
 #ifdef TFL_EXPERIMENTS
   if (exp_kpack() != 1 || exp_tiled() != 0) return false;
   MIn ci = {pDiv, div, flags, stats, count, nullptr, 0, nullptr};
-  return launch_m16p_f2(st, make_dom(Z, Y, X), B, ci, wfrag1, bias1, post1, wfrag2, bias2, post2, out_h2, range_err);
+  return launch_m16p_f2(st, make_dom(sc, Z, Y, X), B, ci, wfrag1, bias1, post1, wfrag2, bias2, post2, out_h2, range_err);
 #else
-  (void)st; (void)B; (void)Z; (void)Y; (void)X; (void)pDiv; (void)div; (void)flags; (void)stats; (void)count; (void)wfrag1; (void)bias1; (void)post1;
+  (void)st; (void)sc; (void)B; (void)Z; (void)Y; (void)X; (void)pDiv; (void)div; (void)flags; (void)stats; (void)count; (void)wfrag1; (void)bias1; (void)post1;
   (void)wfrag2; (void)bias2; (void)post2; (void)out_h2; (void)range_err;
   return false;
 #endif
@@ -788,21 +788,21 @@ bool conv3_m16_fuse12_requested() {
   return false;
 #endif
 }
-void conv3_m16_mid(hipStream_t st, int B, int Z, int Y, int X, const void* in_h2, const void* wfrag, const float* bias, float post,
+void conv3_m16_mid(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const void* in_h2, const void* wfrag, const float* bias, float post,
                    void* out_h2, unsigned long long* range_err) {
 #ifdef TFL_EXPERIMENTS
-  if (exp_tiled() & 1) { MIn noin = {nullptr, nullptr, nullptr, nullptr, 0.0, nullptr, 0, nullptr}; launch_m16<kModeMid>(st, make_dom(Z, Y, X), B, in_h2, wfrag, bias, out_h2, post, noin, range_err); return; }
-  if (exp_kpack() == 0) { launch_m16z<false>(st, make_dom(Z, Y, X), B, in_h2, wfrag, bias, out_h2, post, range_err); return; }
+  if (exp_tiled() & 1) { MIn noin = {nullptr, nullptr, nullptr, nullptr, 0.0, nullptr, 0, nullptr}; launch_m16<kModeMid>(st, make_dom(sc, Z, Y, X), B, in_h2, wfrag, bias, out_h2, post, noin, range_err); return; }
+  if (exp_kpack() == 0) { launch_m16z<false>(st, make_dom(sc, Z, Y, X), B, in_h2, wfrag, bias, out_h2, post, range_err); return; }
 #endif
-  launch_m16p<false>(st, make_dom(Z, Y, X), B, in_h2, wfrag, bias, out_h2, post, range_err);
+  launch_m16p<false>(st, make_dom(sc, Z, Y, X), B, in_h2, wfrag, bias, out_h2, post, range_err);
 }
-void conv3_m16_tail(hipStream_t st, int B, int Z, int Y, int X, const void* in_h2, const void* wfrag, const float* tail_pack,
+void conv3_m16_tail(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const void* in_h2, const void* wfrag, const float* tail_pack,
                     float post, float* p_out, unsigned long long* range_err) {
 #ifdef TFL_EXPERIMENTS
-  if (exp_tiled() & 2) { MIn noin = {nullptr, nullptr, nullptr, nullptr, 0.0, nullptr, 0, nullptr}; launch_m16<kModeTail>(st, make_dom(Z, Y, X), B, in_h2, wfrag, tail_pack, p_out, post, noin, range_err); return; }
-  if (exp_kpack() == 0) { launch_m16z<true>(st, make_dom(Z, Y, X), B, in_h2, wfrag, tail_pack, p_out, post, range_err); return; }
+  if (exp_tiled() & 2) { MIn noin = {nullptr, nullptr, nullptr, nullptr, 0.0, nullptr, 0, nullptr}; launch_m16<kModeTail>(st, make_dom(sc, Z, Y, X), B, in_h2, wfrag, tail_pack, p_out, post, noin, range_err); return; }
+  if (exp_kpack() == 0) { launch_m16z<true>(st, make_dom(sc, Z, Y, X), B, in_h2, wfrag, tail_pack, p_out, post, range_err); return; }
 #endif
-  launch_m16p<true>(st, make_dom(Z, Y, X), B, in_h2, wfrag, tail_pack, p_out, post, range_err);
+  launch_m16p<true>(st, make_dom(sc, Z, Y, X), B, in_h2, wfrag, tail_pack, p_out, post, range_err);
 }
 
 // ---- host: weights [8][cin][3][3][3] (cudnn order) -> A fragments ----------------------------------------------------

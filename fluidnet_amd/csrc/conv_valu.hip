@@ -272,21 +272,21 @@ static void launch_wino(hipStream_t st, const Dom& d, int B, const float* in, co
 }
 
 // first layer: {pDiv/scale, div/scale, occupancy} built while staging; activations out: channel-planar [B][8][Z][Y][X]
-void conv3_valu_first_fused(hipStream_t st, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
+void conv3_valu_first_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
                             const double* stats, double count, const float* wq, const float* bias, float* out_p8) {
   VIn ci = {pDiv, div, flags, stats, count};
-  launch_wino<3, false>(st, make_dom(Z, Y, X), B, pDiv, wq, bias, out_p8, ci);
+  launch_wino<3, false>(st, make_dom(sc, Z, Y, X), B, pDiv, wq, bias, out_p8, ci);
 }
-void conv3_valu_mid(hipStream_t st, int B, int Z, int Y, int X, const float* in_p8, const float* wq, const float* bias,
+void conv3_valu_mid(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* in_p8, const float* wq, const float* bias,
                     float* out_p8) {
   VIn noin = {nullptr, nullptr, nullptr, nullptr, 0.0};
-  launch_wino<8, false>(st, make_dom(Z, Y, X), B, in_p8, wq, bias, out_p8, noin);
+  launch_wino<8, false>(st, make_dom(sc, Z, Y, X), B, in_p8, wq, bias, out_p8, noin);
 }
 // 8 -> 8 k3 + ReLU, then 8 -> 8 k1 + ReLU, then 8 -> 1 k1; planar pressure out.
-void conv3_valu_tail(hipStream_t st, int B, int Z, int Y, int X, const float* in_p8, const float* wq, const float* tail_pack,
+void conv3_valu_tail(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* in_p8, const float* wq, const float* tail_pack,
                      float* p_out) {
   VIn noin = {nullptr, nullptr, nullptr, nullptr, 0.0};
-  launch_wino<8, true>(st, make_dom(Z, Y, X), B, in_p8, wq, tail_pack, p_out, noin);
+  launch_wino<8, true>(st, make_dom(sc, Z, Y, X), B, in_p8, wq, tail_pack, p_out, noin);
 }
 
 }  // namespace tfl

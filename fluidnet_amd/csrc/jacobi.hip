@@ -100,7 +100,7 @@ void jacobi_sweep_slab(hipStream_t st, int B, int Z, int Y, int X, int zg, int Z
                        const float* flags, const float* div, float* p) {
   k0 = k0 < 0 ? 0 : k0; k1 = k1 > Z ? Z : k1;
   if (k1 <= k0 || B < 1) return;
-  Dom d = make_dom(Z, Y, X);
+  Dom d = whole_dom(Z, Y, X);
   d.w0 = k0; d.n0 = k1 - k0; d.w1 = 0; d.nw = d.n0; d.zg = zg; d.Zg = Zg;
   const dim3 blk(64, 4, 1), grd((X + 63) / 64, (Y + 3) / 4, (unsigned)(d.nw * B));
   TFL_TIMED("k_jacobi_slab", st);
@@ -206,8 +206,8 @@ bool jacobi_solve_lds(hipStream_t st, int B, int Y, int X, const float* flags, c
 
 void jacobi_iteration(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* p_prev, const float* flags,
                       const float* div, float* p, double* resid_sq) {
-  const Dom d = make_dom(Z, Y, X);
-  const dim3 blk(64, 4, 1), grd((X + 63) / 64, (Y + 3) / 4, (unsigned)(zwin_planes(Z) * B));
+  const Dom d = whole_dom(Z, Y, X);
+  const dim3 blk(64, 4, 1), grd((X + 63) / 64, (Y + 3) / 4, (unsigned)(d.nw * B));
   if (is3d) {
     if (resid_sq) { TFL_TIMED("k_jacobi", st); k_jacobi<true, true><<<grd, blk, 0, st>>>(d, p_prev, flags, div, p, resid_sq); }
     else { TFL_TIMED("k_jacobi", st); k_jacobi<true, false><<<grd, blk, 0, st>>>(d, p_prev, flags, div, p, nullptr); }

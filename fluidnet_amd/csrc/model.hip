@@ -848,27 +848,27 @@ bool model_stats_fold_requested() {       // EXPERIMENTS flavour + TFL_STATS_FOL
 }
 
 long long model_stat_pairs_per_plane(int B, int Z, int Y, int X, const float* U, const float* flags, const float* Ubc, const float* div) {
-  const Dom d = make_dom(Z, Y, X);
+  const Dom d = whole_dom(Z, Y, X);      // (blocks per plane: whichever planes a launch covers)
   const dim3 grd = TFL_GRID3(d, B);
-  const Vec4Launch v = vec4_launch(B, Z, Y, X, {U, flags, Ubc, div});
+  const Vec4Launch v = vec4_launch(B, d, {U, flags, Ubc, div});
   return v.ok ? (long long)v.grd.x * v.grd.y : (long long)grd.x * grd.y;
 }
 
-// stages: bit 0 = k_bcs_div_stats on the current z-window (per-plane partial sums land in absolute slots, so the
+// stages: bit 0 = k_bcs_div_stats on the scope's z-window (per-plane partial sums land in absolute slots, so the
 // launch may be split into boundary / interior windows), bit 1 = reduce the partials of planes [zlo, zhi) into stats
-// the wall codes of a whole flags array (tfl_wall_plan_create; no z-window: the caller clears it)
+// the wall codes of a whole flags array (tfl_wall_plan_create)
 void wall_code(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* flags, unsigned short* code) {
-  const Dom d = make_dom(Z, Y, X);
+  const Dom d = whole_dom(Z, Y, X);
   const dim3 blk(64, 4, 1), grd = TFL_GRID3(d, B);
   if (is3d) k_wall_code<true><<<grd, blk, 0, st>>>(d, flags, code);
   else k_wall_code<false><<<grd, blk, 0, st>>>(d, flags, code);
 }
 
-void model_pre(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* U, const float* flags, float* Ubc,
+void model_pre(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* U, const float* flags, float* Ubc,
                float* div, double* partials, double* stats, int zlo, int zhi, int stages, unsigned* ticket, const unsigned short* code) {
-  const Dom d = make_dom(Z, Y, X);
+  const Dom d = make_dom(sc, Z, Y, X);
   const dim3 blk(64, 4, 1), grd = TFL_GRID3(d, B);
-  const Vec4Launch v = vec4_launch(B, Z, Y, X, {U, flags, Ubc, div});
+  const Vec4Launch v = vec4_launch(B, d, {U, flags, Ubc, div});
   const long long per_plane = v.ok ? (long long)v.grd.x * v.grd.y : (long long)grd.x * grd.y;   // <= model_stat_blocks / (Z*B)
   // both stages over the whole array in one call (tfl_model_forward): the launch CAN reduce its own partials
   // (publish_and_maybe_reduce) -- opt-in, TFL_STATS_FOLD=1: bit-identical, but measured slower than the 4-wave k_reduce_stats
@@ -918,9 +918,9 @@ void model_pre(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const floa
   if ((stages & 2) && !fused) { TFL_TIMED_EXT("k_reduce_stats", st); TFL_LAUNCH_EXT(k_reduce_stats, B, 256, 0, st, (const double*)partials, per_plane * Z, per_plane * zlo, per_plane * (zhi - zlo), stats); }
 }
 
-// planes [z0, z0 + nz) in place of the thread's z-window (nz >= 0)
+// planes [z0, z0 + nz) of the array (nz < 0: all of them)
 static Dom dom_planes(int Z, int Y, int X, int z0, int nz) {
-  Dom d = make_dom(Z, Y, X);
+  Dom d = whole_dom(Z, Y, X);
   if (nz >= 0) { d.w0 = z0; d.n0 = nz; d.w1 = 0; d.nw = nz; }
   return d;
 }
@@ -967,12 +967,12 @@ void model_skip_channel(hipStream_t st, int B, long long cells, const float* pDi
   k_skip_channel<<<dim3((unsigned)((nt + 255) / 256), (unsigned)B), 256, 0, st>>>(cells, t0, t0 + nt, pDiv, stats, count, dst, och, ch);
 }
 
-bool model_project(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* pPred, const float* flags,
+bool model_project(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* pPred, const float* flags,
                    const double* stats, double count, float* Uio, float* pOut, const float* UBC, const float* UInvMask,
                    int do_clamp, float lo, float hi, const unsigned long long* range_src, unsigned long long* range_dst,
                    const float* reach_src, float* reach_dst, float* reach_acc, const unsigned short* wall_code, unsigned* reach_tick,
                    Fold& f) {
-  const Dom d = make_dom(Z, Y, X);
+  const Dom d = make_dom(sc, Z, Y, X);
   const dim3 blk(64, 4, 1), grd = TFL_GRID3(d, B);
   // a dense pair acts everywhere; without one, tfl_simulate_step's sparse pair (if it asked: tfl_host.hpp Fold) in its box
   BcArgs bc; bc.enable_clamp = do_clamp; bc.lo = lo; bc.hi = hi;

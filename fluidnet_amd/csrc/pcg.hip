@@ -778,7 +778,7 @@ long long pcg_workspace_floats(int Z, int Y, int X) {
 int pcg_solve(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* p, const float* flags, const float* div,
               int precond /*0 none, 1 ilu0, 2 ic0*/, float tol, int max_iter, int verbose, float* workspace, float* residual,
               char* msg, size_t msg_len, bool allow_wavefronts) {
-  const Dom d = make_dom(Z, Y, X);
+  const Dom d = whole_dom(Z, Y, X);
   const long long n = d.sc;
   double* partials = reinterpret_cast<double*>(workspace);
   double* p_den = partials + kRedBlocks;      // s.w
@@ -990,7 +990,7 @@ long long npm_workspace_floats(int Z, int Y, int X) { return 4ll * Z * Y * X + 1
 // normalizePressureMean for every batch element. workspace: sum_at (fp64, first for alignment), label, size_at, counters.
 int normalize_pressure_mean(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* p, const float* flags,
                             float* workspace, char* msg, size_t msg_len) {
-  const Dom d = make_dom(Z, Y, X);
+  const Dom d = whole_dom(Z, Y, X);
   const long long n = d.sc;
   double* sum_at = reinterpret_cast<double*>(workspace);
   int* label = reinterpret_cast<int*>(workspace + 2 * n);

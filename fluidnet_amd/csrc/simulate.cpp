@@ -204,6 +204,9 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
   const bool ours = std::strcmp(method, "maccormackOurs") == 0;
   auto view = [&](float* base, int C) { tfl_tensor t = *s->flags; t.data = base; t.C = C; return t; };
   int rc;
+  // whatever window / stage mask / origin / advect mode the host left on the context: every windowed operator of the step runs
+  // under it (and the ConvNet projection refuses a set window or mask)
+  const tfl::Scope sc = tfl::scope_of(c);
   // an earlier step's projection left the fp16 range of the default 3-D conv path (no sync: the word the projection kernel
   // wrote to pinned memory): refuse to step on from a clamped pressure, before anything of this step has been written
   if (s->model && method_of(prm) == "convnet" && tfl_model_range_flag(c, s->model) > 0) return range_refusal(c, "simulate_step");
@@ -227,14 +230,14 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
     // the field's pair itself where it can (step_ask; the sparse launch covers the rest)
     tfl::Ask a = step_ask(s->densityBC[i]);
     rc = tfl::advectScalar(c, prm->dt, s->density[i], s->U, s->flags, &fwd, &bwd, is3D, method, &fwdPos, &bwdPos, 1, 0,
-                           prm->maccormackStrength, dst, a);
+                           prm->maccormackStrength, dst, sc, a);
     if (a.fold.bc_took) density_done |= 1u << i;
     if (rc) return rc;
     if (!ours) { rc = tfl_copy(c, s->density[i], &out); if (rc) return rc; }
   }
   tfl_tensor vfwd = view(ws, (int)z.C), vbwd = view(ws + z.C * z.N, (int)z.C), Uadv = view(ws + 2 * z.C * z.N, (int)z.C);
   const bool buoyant = s->n_density > 0 && prm->buoyancyScale > 0.0;
-  const double dx = tfl_getDx(c, s->flags);
+  const double dx = tfl::get_dx_double(c, sc, s->flags);
   float bg[3];
   scaled_gravity(prm, dx, prm->buoyancyScale, bg);
   tfl::Ask adv = step_ask(s->UBC);
@@ -246,16 +249,12 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
     const char* e = getenv("TFL_BUOY_FOLD");
     const bool rho_final = buoyant && (!s->densityBC[0] || (density_done & 1u));
     if (rho_final && ours && is3D && !(e && atoi(e) == 0) && (!s->UBC || adv.fold.bc.dev)) {
-      // strength = -gravity * (dt / dx) in float, exactly as tfl_addBuoyancyFrom forms it (abi.cpp get_dx; tfluids.cc:1190-1192)
-      float dxf;
-      if (c->dx_dim > 0) dxf = 1.0f / (float)c->dx_dim;
-      else if (c->dx_override > 0.0f) dxf = c->dx_override;
-      else dxf = 1.0f / (float)std::max(std::max(s->flags->X, s->flags->Y), s->flags->Z);
-      const float bs = prm->dt / dxf;
+      // strength = -gravity * (dt / dx) in float, exactly as tfl_addBuoyancyFrom forms it (tfluids.cc:1190-1192)
+      const float bs = prm->dt / tfl::get_dx(c, sc, s->flags);
       adv.fold.buoy = tfl::BuoyFold{s->density[0]->data, -bg[0] * bs, -bg[1] * bs, -bg[2] * bs};
     }
   }
-  rc = tfl::advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vbwd, is3D, method, 1, prm->maccormackStrength, &Uadv, adv);
+  rc = tfl::advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vbwd, is3D, method, 1, prm->maccormackStrength, &Uadv, sc, adv);
   const bool Uadv_done = adv.fold.bc_took, buoy_folded = adv.fold.buoy_took;
   if (rc) return rc;
   // U:copy(advected) (init.lua:216-218) costs nothing: the velocity stays in the advection's scratch array (`cur`) until an
@@ -289,7 +288,7 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
     const tfl_tensor* dst = vfused ? &Utmp : s->U;
     const bool last = fold_forces && !gravity_on && !vort;
     tfl::Ask a = step_ask(last ? s->UBC : nullptr);
-    rc = tfl::addBuoyancyFrom(c, cur, dst, s->flags, s->density[0], bg, prm->dt, is3D, a);
+    rc = tfl::addBuoyancyFrom(c, cur, dst, s->flags, s->density[0], bg, prm->dt, is3D, sc, a);
     U_folded = a.fold.bc_took;
     if (rc) return rc;
     cur = dst;
@@ -297,7 +296,7 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
   if (gravity_on) {
     float g[3];
     scaled_gravity(prm, dx, prm->gravityScale, g);
-    rc = tfl_addGravity(c, cur, s->flags, g, prm->dt, is3D, nullptr);
+    rc = tfl::addGravity(c, cur, s->flags, g, prm->dt, is3D, sc);
     if (rc) return rc;
   }
   if (vort) {
@@ -305,10 +304,10 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
     tfl::Ask a = step_ask(fold_forces ? s->UBC : nullptr);
     if (cur != s->U) {
       a.two_launch = !vfused;     // below the fused kernel's size the two launches read `cur` and write U
-      rc = tfl::vorticityConfinementFrom(c, cur, s->U, s->flags, strength, &curl, &cnorm, is3D, a);
+      rc = tfl::vorticityConfinementFrom(c, cur, s->U, s->flags, strength, &curl, &cnorm, is3D, sc, a);
     } else {
       tfl_tensor centered = view(ws + 4 * z.N, (int)z.C), force = view(ws + (4 + z.C) * z.N, (int)z.C);   // (unused by the kernels)
-      rc = tfl::vorticityConfinement(c, s->U, s->flags, strength, &centered, &curl, &cnorm, &force, is3D, a);
+      rc = tfl::vorticityConfinement(c, s->U, s->flags, strength, &centered, &curl, &cnorm, &force, is3D, sc, a);
     }
     U_folded = a.fold.bc_took;
     if (rc) return rc;
@@ -335,7 +334,7 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
     if (!s->model) return TFL_EINVAL;
     const LateUbc lu = late_ubc_of(s);
     tfl::Ask a = step_ask(lu.late ? s->UBC : nullptr);
-    rc = tfl::model_forward(c, s->model, s->p, cur, s->flags, s->p, s->U, ws, ws_floats, lu.bc, lu.mask, 1, -1e6f, 1e6f, a);
+    rc = tfl::model_forward(c, s->model, s->p, cur, s->flags, s->p, s->U, ws, ws_floats, lu.bc, lu.mask, 1, -1e6f, 1e6f, sc, a);
     if (rc) return rc;
     // p was rewritten by the model, density has not changed since the second setConstVals
     return set_const_vals(c, s, s->U, lu.late && !a.fold.bc_took, Unchanged{false, false, true});
@@ -644,12 +643,6 @@ Win ext(const SlabGeom& g, int below, int above) {
   below += widen; above += widen; w.a = g.o0 - below < 0 ? 0 : g.o0 - below; w.b = g.o1 + above > g.Zl ? g.Zl : g.o1 + above; return w;
 }
 
-struct StageGuard {          // whatever happens, leave the context with no window / stage mask / dx override
-  tfl_ctx* c;
-  explicit StageGuard(tfl_ctx* ctx) : c(ctx) {}
-  ~StageGuard() { (void)tfl_set_z_window(c, 0, 0, 0, 0); (void)tfl_set_stages(c, 0); c->dx_dim = 0; (void)tfl_set_z_origin(c, 0, 0); }
-};
-
 // the pinned publication count has reached `target` (wrap-safe); spins without an API call, gives the core away after a while,
 // and gives up after 30 s (a dead device must not hang the host here: the next HIP call reports it)
 void reach_wait(tfl_ctx* c, unsigned target) {
@@ -743,6 +736,7 @@ namespace {
 struct SlabStep {
   tfl_ctx* c; const tfl_sim_params* prm; const tfl_sim_state* s; tfl_slab* sl; const tfl_comm* comm;
   float* ws; int64_t ws_floats;
+  bool capturing;                      // tfl_slab_graph_create is recording the step on the context's stream: no host waits, no host reads
   SlabGeom g; SlabWs W; Msg m[4];
   const char* method; AdvPlan ap;
   bool multi, jac, ovl;                // a slab with neighbours; the Jacobi projection; boundary strips first (tfl_slab::overlap)
@@ -767,46 +761,48 @@ struct SlabStep {
   int end_step();                      // the next step's U / p halos leave (message T0)
 
   tfl_tensor view(float* base, int C) const { tfl_tensor t = *s->flags; t.data = base; t.C = C; return t; }
-  int stage(int mask, int below, int above) {      // stage mask `mask` on the planes (below, above) around the owned ones
-    (void)tfl_set_stages(c, mask);
-    const Win w = ext(g, below, above);
-    return tfl_set_z_window(c, w.a, w.b, 0, 0);
+  // The scope of one operator call: stage mask `mask` on the planes [a0, a1) and [b0, b1) of the local array, which sits at
+  // z_first of the whole grid; dx is the whole grid's, the advect mode the context's.
+  tfl::Scope planes(int mask, int a0, int a1, int b0, int b1) const {
+    tfl::Scope sc;
+    sc.win = tfl::ZWin{a0, a1, b0, b1}; sc.origin = tfl::ZOrigin{sl->z_first, sl->z_total}; sc.stages = mask;
+    sc.advect_fast = c->advect_fast;
+    sc.dx_cells = std::max(std::max(s->flags->X, s->flags->Y), sl->z_total);   // tfluids.getDx of the WHOLE grid
+    return sc;
   }
-  void no_stage() { (void)tfl_set_stages(c, 0); (void)tfl_set_z_window(c, 0, 0, 0, 0); }
-  int run_then_send(int mask, int k, const Msg& q, int (SlabStep::*op)());
+  // ... on the planes (below, above) around the owned ones
+  tfl::Scope stage(int mask, int below, int above) const { const Win w = ext(g, below, above); return planes(mask, w.a, w.b, 0, 0); }
+  using Op = int (SlabStep::*)(const tfl::Scope&);
+  int run_then_send(int mask, int k, const Msg& q, Op op);
   // (a: what the call is asked, step_ask; null: nothing)
-  int adv_scalar(const tfl_tensor* d, const tfl_tensor* dst, tfl::Ask* a = nullptr) {
+  int adv_scalar(const tfl::Scope& sc, const tfl_tensor* d, const tfl_tensor* dst, tfl::Ask* a = nullptr) {
     tfl::Ask none = step_ask(nullptr);
     return tfl::advectScalar(c, prm->dt, d, s->U, s->flags, &fwd, &fwd, 1, method, &fwdPos, &bwdPos, 1, 0, prm->maccormackStrength, dst,
-                             a ? *a : none);
+                             sc, a ? *a : none);
   }
-  int adv_vel(tfl::Ask* a = nullptr) {
+  int adv_vel(const tfl::Scope& sc, tfl::Ask* a = nullptr) {
     tfl::Ask none = step_ask(nullptr);
-    return tfl::advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vfwd, 1, method, 1, prm->maccormackStrength, &Uadv, a ? *a : none);
+    return tfl::advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vfwd, 1, method, 1, prm->maccormackStrength, &Uadv, sc, a ? *a : none);
   }
-  int adv_pair(bool with_folds);
-  int pass_b();
-  int model_begin() {
+  int adv_pair(const tfl::Scope& sc, bool with_folds);
+  int pass_b(const tfl::Scope& sc);
+  int model_begin(const tfl::Scope& sc) {
     tfl::Ask a = step_ask(nullptr);
-    return tfl::model_begin(c, s->model, s->U, s->flags, s->U, W.compute, ws_floats - (W.compute - ws), g.o0, g.o1, W.stats, a);
+    return tfl::model_begin(c, s->model, s->U, s->flags, s->U, W.compute, ws_floats - (W.compute - ws), g.o0, g.o1, W.stats, sc, a);
   }
 };
 
 // `op` on the owned planes under stage mask `mask`, then message `q` starts. Overlapped: `op` on the boundary strips (k planes
 // next to each neighbour) first, then the message starts and `op` runs on the interior while it travels.
-int SlabStep::run_then_send(int mask, int k, const Msg& q, int (SlabStep::*op)()) {
+int SlabStep::run_then_send(int mask, int k, const Msg& q, Op op) {
   const int a1 = g.lower ? std::min(g.o0 + k, g.o1) : g.o0, b0 = g.upper ? std::max(g.o1 - k, a1) : g.o1;   // strips [o0, a1), [b0, o1)
   if (!ovl || (a1 == g.o0 && b0 == g.o1) || b0 == a1) {
-    TRY(stage(mask, 0, 0));
-    TRY((this->*op)());
+    TRY((this->*op)(stage(mask, 0, 0)));
     return msg_start(c, g, comm, q);
   }
-  (void)tfl_set_stages(c, mask);
-  TRY(tfl_set_z_window(c, g.o0, a1, b0, g.o1));
-  TRY((this->*op)());
+  TRY((this->*op)(planes(mask, g.o0, a1, b0, g.o1)));
   TRY(msg_start(c, g, comm, q));
-  TRY(tfl_set_z_window(c, a1, b0, 0, 0));
-  return (this->*op)();
+  return (this->*op)(planes(mask, a1, b0, 0, 0));
 }
 
 int SlabStep::validate() {
@@ -852,7 +848,7 @@ int SlabStep::validate() {
 
 int SlabStep::gates() {
   // ---- reach check of the PREVIOUS step's velocity (no host sync: the word was copied back behind that step) ---------
-  if (sl->check_reach == 1 && !c->capturing) {  // (a captured step: tfl_slab_graph_step makes both checks before it launches)
+  if (sl->check_reach == 1 && !capturing) {  // (a captured step: tfl_slab_graph_step makes both checks before it launches)
     char buf[256];
     if (reach_violated(c, prm->dt, g.R, buf, sizeof(buf))) {
       // the neighbours' matching receives of the U / p messages are already posted: finish ours before giving up
@@ -864,7 +860,7 @@ int SlabStep::gates() {
   // The fp16 range gate of tfl_simulate_step -- only where refusing cannot strand a neighbour: a slab WITHOUT
   // neighbours, or (below) collectively under check_reach = 2. A rank that refused on its own word would leave the others
   // waiting for its halos; the host of a cut run polls tfl_model_range_flag / tfl_model_range_errors and stops every rank.
-  if (!c->capturing && !multi && s->model && tfl_model_range_flag(c, s->model) > 0) return range_refusal(c, "simulate_step_slab");
+  if (!capturing && !multi && s->model && tfl_model_range_flag(c, s->model) > 0) return range_refusal(c, "simulate_step_slab");
   TRY(finish_in_flight(c, g, comm, m, sl));      // U and p halos
   // (the state a run starts from has been through no projection of ours)
   if (sl->check_reach == 1 && !(sl->in_flight & kReachPrimed)) { reach_prime(c, sl); c->reach_folded = false; }
@@ -881,7 +877,7 @@ int SlabStep::gates() {
   if (sl->check_reach == 2) {
     // "exact" (round 6): the reach THIS step needs, agreed by all ranks, before anything is written. One-hot flags
     // (max|u_z| dt >= r, r = 1 .. 8) so that the transport's SUM all-reduce can combine them; one host synchronisation.
-    if (c->capturing) { c->err = "simulate_step_slab: check_reach = 2 synchronises with the host and cannot be recorded into a graph"; return TFL_EUNSUPPORTED; }
+    if (capturing) { c->err = "simulate_step_slab: check_reach = 2 synchronises with the host and cannot be recorded into a graph"; return TFL_EUNSUPPORTED; }
     if (!c->h_reach_flags && hipHostMalloc((void**)&c->h_reach_flags, sizeof(double) * (kReachFlags + 1), hipHostMallocDefault) != hipSuccess) {
       c->h_reach_flags = nullptr; c->err = "simulate_step_slab: hipHostMalloc failed"; return TFL_EHIP;
     }
@@ -915,26 +911,26 @@ int SlabStep::gates() {
 // Round 6: the two advections' passes as PAIRS -- passes A in one launch, passes B in one launch (advect_pair3.hip; they are
 // independent here: the slab step does not fold the buoyancy force into pass B). TFL_EUNSUPPORTED = the shape is not the pair
 // kernels': the four launches as before.
-int SlabStep::adv_pair(bool with_folds) {
+int SlabStep::adv_pair(const tfl::Scope& sc, bool with_folds) {
   const tfl::BcFoldArg fs = with_folds ? fold_arg(s->densityBC[0]) : tfl::no_fold(), fv = with_folds ? fold_arg(s->UBC) : tfl::no_fold();
-  const int r = tfl::advect_pair(c, prm->dt, prm->maccormackStrength, rho, s->U, s->flags, &fwd, &fwdPos, rho, &vfwd, &Uadv, fs, fv);
+  const int r = tfl::advect_pair(c, prm->dt, prm->maccormackStrength, rho, s->U, s->flags, &fwd, &fwdPos, rho, &vfwd, &Uadv, fs, fv, sc);
   if (r == TFL_OK && with_folds) { rho_done = rho_done && fs.dev != nullptr; Uadv_done = Uadv_done && fv.dev != nullptr; }
   return r;
 }
 
-// the passes B of both operators on the current window (other methods: the velocity's). They apply the pairs of the
+// the passes B of both operators on the window of `sc` (other methods: the velocity's). They apply the pairs of the
 // setConstVals that follows on the planes they write -- the owned ones, which is what message T2 carries to the neighbours'
 // halos (step_ask)
-int SlabStep::pass_b() {
-  if (ap.ours && paired) { const int r = adv_pair(true); if (r != TFL_EUNSUPPORTED) return r; paired = false; }
+int SlabStep::pass_b(const tfl::Scope& sc) {
+  if (ap.ours && paired) { const int r = adv_pair(sc, true); if (r != TFL_EUNSUPPORTED) return r; paired = false; }
   if (ap.ours && rho) {
     tfl::Ask a = step_ask(s->densityBC[0]);
-    const int r = adv_scalar(rho, rho, &a);
+    const int r = adv_scalar(sc, rho, rho, &a);
     rho_done = a.fold.bc_took && rho_done;
     if (r) return r;
   }
   tfl::Ask a = step_ask(s->UBC);
-  const int r = adv_vel(&a);
+  const int r = adv_vel(sc, &a);
   Uadv_done = a.fold.bc_took && Uadv_done;
   return r;
 }
@@ -950,24 +946,22 @@ int SlabStep::advect() {
     // and the velocity, so that the pair kernels below run as with one channel and T2 finds every channel's owned planes written
     for (int i = 1; i < s->n_density; i++) {
       const tfl_tensor* di = s->density[i];
-      TRY(stage(1, 2 * R, 2 * R)); TRY(adv_scalar(di, di));
-      TRY(stage(2, R, R)); TRY(adv_scalar(di, di));
-      TRY(stage(4, 0, 0));
+      TRY(adv_scalar(stage(1, 2 * R, 2 * R), di, di));
+      TRY(adv_scalar(stage(2, R, R), di, di));
       tfl::Ask a = step_ask(s->densityBC[i]);
-      const int rc = adv_scalar(di, di, &a);
+      const int rc = adv_scalar(stage(4, 0, 0), di, di, &a);
       if (a.fold.bc_took) extra_done |= 1u << i;
       if (rc) return rc;
     }
-    TRY(stage(2, R, R));
-    const int rc = paired ? adv_pair(false) : TFL_OK;
+    const tfl::Scope pass_a = stage(2, R, R);
+    const int rc = paired ? adv_pair(pass_a, false) : TFL_OK;
     if (rc == TFL_EUNSUPPORTED) {
       paired = false;
-      TRY(stage(1, 2 * R, 2 * R)); TRY(adv_scalar(rho, rho));
-      TRY(stage(2, R, R));
+      TRY(adv_scalar(stage(1, 2 * R, 2 * R), rho, rho));
     } else if (rc) return rc;
     if (!paired) {
-      if (rho) TRY(adv_scalar(rho, rho));
-      TRY(adv_vel());
+      if (rho) TRY(adv_scalar(pass_a, rho, rho));
+      TRY(adv_vel(pass_a));
     }
   } else {
     // every other method: the generic gather kernels (and the LDS-tiled single pass of eulerOurs) under the windows of the
@@ -977,25 +971,24 @@ int SlabStep::advect() {
     tfl_tensor sout = view(W.compute + g.N, 1);
     for (int i = 0; i < s->n_density; i++) {
       const tfl_tensor* di = s->density[i];
-      if (ap.scalar2) { TRY(stage(2, R, R)); TRY(adv_scalar(di, &sout)); }
-      TRY(stage(ap.scalar2 ? 4 : 2, 0, 0)); TRY(adv_scalar(di, &sout));
+      if (ap.scalar2) TRY(adv_scalar(stage(2, R, R), di, &sout));
+      TRY(adv_scalar(stage(ap.scalar2 ? 4 : 2, 0, 0), di, &sout));
       TRY(copy_owned(c, g, di, &sout));
     }
     rho_done = false;
-    if (ap.vel2) { TRY(stage(2, R, R)); TRY(adv_vel()); }
+    if (ap.vel2) TRY(adv_vel(stage(2, R, R)));
   }
   // the velocity's pass that writes the owned planes (single-pass methods: stage 2); strips as deep as message T2 sends
   TRY(run_then_send(ap.vel2 ? 4 : 2, std::max(4, 2 * R + 1), m[2], &SlabStep::pass_b));
   TRY(msg_finish(c, g, comm, m[2]));
-  no_stage();
   cur = &Uadv;
   if (!buoyant && !vfused) { TRY(tfl_copy(c, s->U, &Uadv)); cur = s->U; }
   return set_const_vals(c, s, cur, !Uadv_done, Unchanged{false, false, false}, ((rho && rho_done) ? 1u : 0u) | extra_done);
 }
 
 int SlabStep::forces() {
-  const double dx = tfl_getDx(c, s->flags);
-  TRY(stage(0, 3, 4));
+  const tfl::Scope force_sc = stage(0, 3, 4);
+  const double dx = tfl::get_dx_double(c, force_sc, s->flags);
   // as tfl_simulate_step: the last force's kernel applies the U pair of the setConstVals that follows, on the planes it writes
   // (they include every plane the projection reads: (0, 1)); the launch below then skips U. Not before the Jacobi projection:
   // its setWallBcs comes between the last force and the pair (as in tfl_simulate_step)
@@ -1007,28 +1000,30 @@ int SlabStep::forces() {
     const tfl_tensor* dst = vfused ? &Utmp : s->U;
     const bool last = fold_forces && !gravity_on && !vort;
     tfl::Ask a = step_ask(last ? s->UBC : nullptr);
-    const int rc = tfl::addBuoyancyFrom(c, cur, dst, s->flags, rho, gv, prm->dt, 1, a);
+    const int rc = tfl::addBuoyancyFrom(c, cur, dst, s->flags, rho, gv, prm->dt, 1, force_sc, a);
     U_folded = a.fold.bc_took;
     if (rc) return rc;
     cur = dst;
   }
   if (gravity_on) {
     scaled_gravity(prm, dx, prm->gravityScale, gv);
-    TRY(tfl_addGravity(c, cur, s->flags, gv, prm->dt, 1, nullptr));
+    TRY(tfl::addGravity(c, cur, s->flags, gv, prm->dt, 1, force_sc));
   }
   if (vort) {
     // fused: one launch, curl (2,2) and |curl| live in LDS, the planes (0,1) of U are written (inputs: planes (3,3) of `cur`);
     // otherwise curl on (2, 2), then the force on (0, 1)
     const float strength = (float)(dx * prm->vorticityConfinementAmp);
-    if (!vfused) { TRY(stage(2, 2, 2)); TRY(tfl_vorticityConfinement(c, s->U, s->flags, strength, &curl, &curl, &cnorm, &curl, 1)); }
-    TRY(stage(vfused ? 0 : 4, 0, 1));
+    if (!vfused) {
+      tfl::Ask none;
+      TRY(tfl::vorticityConfinement(c, s->U, s->flags, strength, &curl, &curl, &cnorm, &curl, 1, stage(2, 2, 2), none));
+    }
+    const tfl::Scope sc = stage(vfused ? 0 : 4, 0, 1);
     tfl::Ask a = step_ask(fold_forces ? s->UBC : nullptr);
-    const int rc = vfused ? tfl::vorticityConfinementFrom(c, cur, s->U, s->flags, strength, &curl, &cnorm, 1, a)
-                          : tfl::vorticityConfinement(c, s->U, s->flags, strength, &curl, &curl, &cnorm, &curl, 1, a);
+    const int rc = vfused ? tfl::vorticityConfinementFrom(c, cur, s->U, s->flags, strength, &curl, &cnorm, 1, sc, a)
+                          : tfl::vorticityConfinement(c, s->U, s->flags, strength, &curl, &curl, &cnorm, &curl, 1, sc, a);
     U_folded = a.fold.bc_took;
     if (rc) return rc;
   }
-  no_stage();
   if (prm->outputDiv) return TFL_OK;
   if (jac) {
     const Win w = ext(g, 0, 1);            // what the divergence reads
@@ -1074,74 +1069,74 @@ int SlabStep::project_net() {
   TRY(run_then_send(2, g.gen ? std::max(g.cone.in_lo, g.cone.in_hi) : 4, m[3], &SlabStep::model_begin));  // (strips: what T3 sends)
   double count = 3.0 * (double)sl->z_total * (double)g.yx;
   if (g.cone.norm == 0) {        // std(UDiv): tfl_model_begin's partial sums over the owned planes
-    (void)tfl_set_stages(c, 4);
-    TRY(model_begin());
+    TRY(model_begin(stage(4, 0, 0)));
   } else {                       // another field / the l2 norm / none: the same over the owned planes
     tfl::model_slab_stats(c->stream, s->model, g.B, g.Zl, g.yx, g.o0, g.o1, sl->z_total, s->p->data, s->U->data, div.data, W.stats, &count);
   }
   // (no input scale: every rank holds (0, 1) already -- a sum would make it (0, world))
   if (multi && g.cone.norm != 2 && comm->allreduce_sum(comm->user, W.stats, 2ll * g.B) != 0) { c->err = "simulate_step_slab: comm callback failed (allreduce_sum)"; return TFL_EINVAL; }
   const LateUbc lu = late_ubc_of(s);
-  auto finish = [&](tfl::Ask* a = nullptr) {
+  auto finish = [&](const tfl::Scope& sc, tfl::Ask* a = nullptr) {
     tfl::Ask none = step_ask(nullptr);
     return tfl::model_finish(c, s->model, s->p, s->flags, s->p, s->U, W.compute, ws_floats - (W.compute - ws), W.stats, count,
-                             lu.bc, lu.mask, 1, -1e6f, 1e6f, a ? *a : none);
+                             lu.bc, lu.mask, 1, -1e6f, 1e6f, sc, a ? *a : none);
   };
-  (void)tfl_set_stages(c, 1);
   const Win w1 = ext(g, 3, 2);
   if (g.gen) {
     // every other net: the whole shape-generic forward as stage 1, each launch on its layer's cone of the owned planes (the
     // window names the owned planes; tfl_model_finish widens it layer by layer)
-    TRY(msg_finish(c, g, comm, m[3])); TRY(stage(1, 0, 0)); TRY(finish());
+    TRY(msg_finish(c, g, comm, m[3])); TRY(finish(stage(1, 0, 0)));
   } else if (ovl && g.o1 - 1 > g.o0 + 1) {
     // interior of conv 1 needs only owned planes of div / p: it runs while the div halos travel
-    TRY(tfl_set_z_window(c, g.lower ? g.o0 + 1 : w1.a, g.upper ? g.o1 - 1 : w1.b, 0, 0));
-    TRY(finish());
+    TRY(finish(planes(1, g.lower ? g.o0 + 1 : w1.a, g.upper ? g.o1 - 1 : w1.b, 0, 0)));
     TRY(msg_finish(c, g, comm, m[3]));
-    TRY(tfl_set_z_window(c, g.lower ? w1.a : 0, g.lower ? g.o0 + 1 : 0, g.upper ? g.o1 - 1 : 0, g.upper ? w1.b : 0));
-    TRY(finish());
+    TRY(finish(planes(1, g.lower ? w1.a : 0, g.lower ? g.o0 + 1 : 0, g.upper ? g.o1 - 1 : 0, g.upper ? w1.b : 0)));
   } else {
-    TRY(msg_finish(c, g, comm, m[3])); TRY(stage(1, 3, 2)); TRY(finish());
+    TRY(msg_finish(c, g, comm, m[3])); TRY(finish(stage(1, 3, 2)));
   }
-  if (!g.gen) { TRY(stage(2, 2, 1)); TRY(finish()); TRY(stage(4, 1, 0)); TRY(finish()); }
-  TRY(stage(8, 0, 0));
+  if (!g.gen) { TRY(finish(stage(2, 2, 1))); TRY(finish(stage(4, 1, 0))); }
   tfl::Ask a = step_ask(lu.late ? s->UBC : nullptr);   // the projection kernel applies the sparse U pair itself (owned planes: what T0 sends)
   a.reach_via_project = reach_via_project;
-  const int rc = finish(&a);
+  const int rc = finish(stage(8, 0, 0), &a);
   if (a.reach_published) { c->reach_folded = a.reach_folded; c->reach_issued++; }   // (tfl_slab_graph_create counts these)
   if (rc) return rc;
-  no_stage();
   return set_const_vals(c, s, s->U, lu.late && !a.fold.bc_took, Unchanged{false, false, true});
 }
 
 // the end of every step: the next step's U and p halos leave now; they are consumed at its start / before its first conv layer
 int SlabStep::end_step() {
-  if (sl->check_reach == 1 && !c->capturing) reach_mark(c);      // behind the kernel that published this step's reach word
+  if (sl->check_reach == 1 && !capturing) reach_mark(c);      // behind the kernel that published this step's reach word
   if (!multi) return TFL_OK;
   TRY(msg_start(c, g, comm, m[0]));
   // a captured step must end with every stream joined: the message is finished here instead of by the next call (nothing
   // of the next step could have run beside it anyway -- its first kernels read these halos)
-  if (c->capturing) return msg_finish(c, g, comm, m[0]);
+  if (capturing) return msg_finish(c, g, comm, m[0]);
   sl->in_flight |= 1;
   return TFL_OK;
 }
 
-}  // namespace
-
-int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state* s, tfl_slab* sl, const tfl_comm* comm,
-                           float* ws, int64_t ws_floats) {
+// the rank-step, eager (tfl_simulate_step_slab) or while tfl_slab_graph_create records it (capturing)
+int slab_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state* s, tfl_slab* sl, const tfl_comm* comm, float* ws,
+              int64_t ws_floats, bool capturing) {
   if (!c || !prm || !s || !s->p || !s->U || !s->flags || !sl) return TFL_EINVAL;
-  SlabStep S{c, prm, s, sl, comm, ws, ws_floats};
+  SlabStep S{c, prm, s, sl, comm, ws, ws_floats, capturing};
   TRY(S.validate());
-  StageGuard guard(c);
   TRY(S.gates());
-  c->dx_dim = std::max(std::max(s->flags->X, s->flags->Y), sl->z_total);   // tfluids.getDx of the WHOLE grid
-  (void)tfl_set_z_origin(c, sl->z_first, sl->z_total);
   TRY(S.advect());
   TRY(S.forces());
   if (prm->outputDiv) return TFL_OK;
   TRY(S.jac ? S.project_jacobi() : S.project_net());
   return S.end_step();
+}
+
+}  // namespace
+
+// Every operator call of the step carries its own scope (planes, stage mask, the slab's origin in the whole grid, the whole
+// grid's dx): whatever tfl_set_z_window / tfl_set_stages / tfl_set_z_origin left on the context is neither read nor changed
+// (tfl_set_advect_mode is honoured).
+int tfl_simulate_step_slab(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state* s, tfl_slab* sl, const tfl_comm* comm,
+                           float* ws, int64_t ws_floats) {
+  return slab_step(c, prm, s, sl, comm, ws, ws_floats, false);
 }
 
 int32_t tfl_slab_needed_reach(const tfl_ctx* c) { return c ? c->needed_reach : 0; }
@@ -1238,11 +1233,11 @@ tfl_slab_graph* tfl_slab_graph_create(tfl_ctx* c, const tfl_sim_params* prm, con
   if (hipStreamBeginCapture(G->cap, hipStreamCaptureModeRelaxed) != hipSuccess) {
     c->err = "slab_graph_create: hipStreamBeginCapture failed"; (void)hipStreamDestroy(G->cap); delete G; return nullptr;
   }
-  c->stream = G->cap; c->capturing = true;
+  c->stream = G->cap;
   const unsigned issued0 = c->reach_issued;
-  const int rc = tfl_simulate_step_slab(c, prm, s, sl, comm, ws, ws_floats);
+  const int rc = slab_step(c, prm, s, sl, comm, ws, ws_floats, true);
   G->reach_pubs = c->reach_issued - issued0; c->reach_issued = issued0;      // recorded, not run: every REPLAY makes them
-  c->capturing = false; c->stream = user;
+  c->stream = user;
   const hipError_t ec = hipStreamEndCapture(G->cap, &graph);
   std::string why;
   if (rc != TFL_OK) why = "the step failed while being recorded: " + c->err;

@@ -291,9 +291,9 @@ void stream_copy(hipStream_t st, long long n4, const float* src, float* dst) {
 static inline dim3 cgrid(const Dom& d, int B, dim3 blk) {
   return dim3((d.X + blk.x - 1) / blk.x, (d.Y + blk.y - 1) / blk.y, (unsigned)(d.nw * B));
 }
-#define TFL_LAUNCH(kern, ...)                                        \
+#define TFL_LAUNCH(dom, kern, ...)                                   \
   do {                                                               \
-    const Dom d = make_dom(Z, Y, X);                                 \
+    const Dom d = dom;                                               \
     const dim3 blk(64, 4, 1), grd = cgrid(d, B, blk);                \
     TFL_TIMED(#kern, st);                                            \
     if (is3d) kern<true><<<grd, blk, 0, st>>>(d, __VA_ARGS__);       \
@@ -301,22 +301,22 @@ static inline dim3 cgrid(const Dom& d, int B, dim3 blk) {
   } while (0)
 
 void set_wall_bcs(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags) {
-  TFL_LAUNCH(k_set_wall_bcs, U, flags);
+  TFL_LAUNCH(whole_dom(Z, Y, X), k_set_wall_bcs, U, flags);
 }
 void velocity_divergence(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* U, const float* flags,
                          float* div) {
-  TFL_LAUNCH(k_divergence, U, flags, div);
+  TFL_LAUNCH(whole_dom(Z, Y, X), k_divergence, U, flags, div);
 }
 void velocity_update(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags,
                      const float* p) {
-  TFL_LAUNCH(k_velocity_update, U, flags, p);
+  TFL_LAUNCH(whole_dom(Z, Y, X), k_velocity_update, U, flags, p);
 }
 // The z-slab step's Jacobi projection (csrc/simulate.cpp) runs three of these on the planes [k0, k1) of the local array only
-// (what tfl_set_z_window does for the operators that honour it; the public operators keep ignoring the window). Their border
+// (what a Scope window does for the operators that take one; the public operators cover the whole array). Their border
 // test stays the local one: inside any window the step passes it is the global one -- a domain end is an array end, and the
 // array ends of a cut lie a halo depth or more beyond the owned planes, outside every window.
 static inline Dom planes_dom(int Z, int Y, int X, int k0, int k1) {
-  Dom d = make_dom(Z, Y, X);
+  Dom d = whole_dom(Z, Y, X);
   d.w0 = k0; d.n0 = k1 - k0; d.w1 = 0; d.nw = d.n0;
   return d;
 }
@@ -340,12 +340,12 @@ void velocity_update_planes(hipStream_t st, int B, int Z, int Y, int X, int k0, 
                             const float* p) {
   TFL_LAUNCH_PLANES(k_velocity_update, U, flags, p);
 }
-void add_buoyancy(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* Usrc, float* U, const float* flags,
+void add_buoyancy(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* Usrc, float* U, const float* flags,
                   const float* density, float sx, float sy, float sz, Fold& f) {
   const bool vec = (X % 4 == 0) && ((((uintptr_t)U | (uintptr_t)Usrc | (uintptr_t)flags | (uintptr_t)density) & 15) == 0) &&
                    !exp_env("TFL_NO_VEC4");
   if (vec) {
-    const Dom d = make_dom(Z, Y, X);
+    const Dom d = make_dom(sc, Z, Y, X);
     const dim3 blk(32, 8, 1), grd((X / 4 + 31) / 32, (Y + 7) / 8, (unsigned)(d.nw * B));
     TFL_TIMED_EXT("k_add_buoyancy", st);
     const BcFoldArg fold = Usrc != U ? f.hand_bc() : no_fold();
@@ -355,11 +355,11 @@ void add_buoyancy(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const f
   }
   if (Usrc != U)   // the one-cell-per-thread kernel skips the cells it does not change
     (void)hipMemcpyAsync(U, Usrc, sizeof(float) * (size_t)B * (is3d ? 3 : 2) * Z * Y * X, hipMemcpyDeviceToDevice, st);
-  TFL_LAUNCH(k_add_buoyancy, U, flags, density, sx, sy, sz);
+  TFL_LAUNCH(make_dom(sc, Z, Y, X), k_add_buoyancy, U, flags, density, sx, sy, sz);
 }
-void add_gravity(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags, float fx,
+void add_gravity(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags, float fx,
                  float fy, float fz) {
-  TFL_LAUNCH(k_add_gravity, U, flags, fx, fy, fz);
+  TFL_LAUNCH(make_dom(sc, Z, Y, X), k_add_gravity, U, flags, fx, fy, fz);
 }
 // ---- rectangularBlur / signedDistanceField (generic/tfluids.cc:642-821): criterion-side helpers, not on the step ----------
 // One thread per line; the running sum is sequential along the line in the reference's order (bit-exact). Lines of a pass:
@@ -428,7 +428,7 @@ void signed_distance_field(hipStream_t st, int B, int Z, int Y, int X, int rad, 
 }
 
 void empty_domain(hipStream_t st, bool is3d, int bnd, int B, int Z, int Y, int X, float* flags) {
-  TFL_LAUNCH(k_empty_domain, bnd, flags);
+  TFL_LAUNCH(whole_dom(Z, Y, X), k_empty_domain, bnd, flags);
 }
 void flags_to_occupancy(hipStream_t st, long long numel, const float* flags, float* occ) {
   const int blocks = (int)((numel + 255) / 256 < 2048 ? (numel + 255) / 256 : 2048);

@@ -1,6 +1,7 @@
 // tfl_ctx.hpp -- the context object behind the opaque tfl_ctx* of include/tfluids_hip.h (private to the library:
-// abi.cpp owns it, simulate.cpp reads the stream and keeps the z-slab reach-check words). What a native step asks of an
-// operator call is not kept here: it travels as an argument (tfl_ops.hpp Ask).
+// abi.cpp owns it, simulate.cpp reads the stream and keeps the z-slab reach-check words). It holds resources and what the
+// host's tfl_set_* calls stored. Nothing per call lives here: what a native step asks of an operator call (tfl_ops.hpp Ask)
+// and where that call computes (tfl_host.hpp Scope) travel as arguments.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,9 +30,10 @@ struct tfl_ctx {
   double* d_resid = nullptr;                  // Jacobi residual accumulators [kMaxBatch]
   double* h_resid = nullptr;                  // pinned mirror
   float dx_override = 0.0f;                   // > 0: use instead of 1/max(X,Y,Z) (z-slab ranks: global dx)
-  int dx_dim = 0;                             // > 0: dx = 1/dx_dim formed exactly like getDx does (tfl_simulate_step_slab)
+  // the next four: what scope_of (abi.cpp) copies into a Scope, for the public operators that honour them and for
+  // tfl_simulate_step; the z-slab step builds scopes of its own and takes the advect mode alone
   tfl::ZWin zwin = {0, 0, 0, 0};              // tfl_set_z_window: planes the next operators compute (all zero = all)
-  tfl::ZOrigin zorigin = {0, 0};              // tfl_set_z_origin: where the arrays sit in the whole grid (z-slab ranks)
+  tfl::ZOrigin zorigin = {0, 0};              // tfl_set_z_origin: where the arrays sit in the whole grid
   int advect_fast = 0;                        // tfl_set_advect_mode (initialised from TFL_ADVECT_MODE by tfl_create)
   int stages = 0;                             // tfl_set_stages: which passes of a multi-pass operator run (0 = all)
   float* d_reach = nullptr;                   // z-slab reach check: max|u_z| of the current step (device word)
@@ -52,5 +54,4 @@ struct tfl_ctx {
   int wf_skip = 0;                            // > 0: a pipelined PCG sweep timed out on this context: the next wf_skip solves go straight to
                                               // hyperplane sweeps, then the pipelined form is tried again (a transient stall must not latch for good)
   int wf_timeouts = 0;                        // how often that happened (the back-off doubles, one warning per latch)
-  bool capturing = false;                     // tfl_slab_graph_create is recording the step on `stream`: no host waits, no host reads
 };

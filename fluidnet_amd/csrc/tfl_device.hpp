@@ -35,10 +35,10 @@ struct Dom {
   int one;         // always 1, but opaque to the compiler (see TFL_P1)
   // Compute window: a launch covers the z-planes [w0, w0 + n0) and then [w1, w1 + (nw - n0)) of the array (nw planes
   // per batch item in all; default = all Z planes). Addressing always uses the full Z: a z-slab rank computes each
-  // phase only on the planes whose inputs are valid (tfl_set_z_window, csrc/simulate.cpp), in at most two runs
+  // phase only on the planes whose inputs are valid (tfl_host.hpp Scope::win, csrc/simulate.cpp), in at most two runs
   // (the two boundary strips of an interior/boundary split go out as ONE launch).
   int w0, n0, w1, nw;
-  // z-slab ranks: the array holds planes [zg, zg + Z) of a Zg-deep grid (tfl_set_z_origin; default zg = 0, Zg = Z).
+  // z-slab ranks: the array holds planes [zg, zg + Z) of a Zg-deep grid (Scope::origin; default zg = 0, Zg = Z).
   // Back-trace positions are formed in GLOBAL z -- (k + zg) + 0.5 - u*dt rounds exactly as the unsplit grid's
   // k_global + 0.5 - u*dt does, a position relative to the slab would round differently whenever the two indices
   // fall into different binades -- and are turned into local plane indices only to address memory.

@@ -22,16 +22,22 @@ inline const char* exp_env(const char* name) {
 #endif
 }
 
-// The z-window of the calling thread's current operator (set by abi.cpp from tfl_set_z_window, cleared after the
-// launch): planes [a0, a1) and [b0, b1) in array indices; all zero = the whole array.
-struct ZWin { int a0, a1, b0, b1; };
-extern thread_local ZWin g_zwin;
-// z origin of the array inside the whole grid (tfl_set_z_origin): {first global plane, planes of the whole grid}; {0, 0} = none
-struct ZOrigin { int first, total; };
-extern thread_local ZOrigin g_zorigin;
-// tfl_set_advect_mode of the calling thread's current operator: 1 = tolerance mode of the LDS-tiled 3-D advection kernels
-extern thread_local int g_advect_fast;
-// A setConstVals pair (lib/simulate.lua:130-160: x = x * invMask + bc) that the calling thread's current operator MAY apply
+// Where an operator computes and which of its passes run: a value that every windowed operator receives as an argument and
+// hands to its launchers. A public tfl_* operator that honours the tfl_set_* calls forms one from its context at entry
+// (abi.cpp scope_of); the z-slab step builds its own per call. All zero = the whole array, every pass, exact advection, dx of
+// the array itself.
+struct ZWin { int a0, a1, b0, b1; };       // planes [a0, a1) and [b0, b1) in array indices; all zero = the whole array
+struct ZOrigin { int first, total; };      // the array inside the whole grid: {first global plane, planes of the whole grid}; {0, 0} = none
+struct Scope {
+  ZWin win = {0, 0, 0, 0};                 // tfl_set_z_window
+  ZOrigin origin = {0, 0};                 // tfl_set_z_origin
+  int stages = 0;                          // tfl_set_stages: which passes of a multi-pass operator run (0 = all)
+  int advect_fast = 0;                     // tfl_set_advect_mode: 1 = tolerance mode of the LDS-tiled 3-D advection kernels
+  int dx_cells = 0;                        // > 0: dx = 1 / dx_cells, formed exactly like getDx does (a z-slab rank: the whole grid's)
+  bool windowed() const { return win.a1 > win.a0 || win.b1 > win.b0; }
+  int passes() const { return stages ? stages : 0xff; }
+};
+// A setConstVals pair (lib/simulate.lua:130-160: x = x * invMask + bc) that an operator MAY apply
 // to the field it writes (round 4): the pair is the identity outside the box [x0, x1] x [y0, y1] x [z0, z1] (inclusive, array
 // indices; the plume's pair covers four y rows), so a producing kernel compares its rows against the box and only the
 // threads inside it load bc / invMask ([B][C][Z][Y][X] like the field) -- nothing per cell elsewhere. The descriptor lives in
@@ -78,13 +84,20 @@ __device__ __forceinline__ bool fold_block(const BcFoldArg& a, int ya, int yb, i
          (zb >= (int)(a.lo >> 16));
 }
 
-inline Dom make_dom(int Z, int Y, int X) {
+// The launch domain of a launcher that covers the whole array whatever window a host has set (Jacobi, PCG, the public stencil
+// operators, the wall plan ...): it takes no scope.
+inline Dom whole_dom(int Z, int Y, int X) {
   Dom d; d.X = X; d.Y = Y; d.Z = Z; d.sy = X; d.sz = X * Y; d.sc = X * Y * Z; d.one = 1;
   d.w0 = 0; d.n0 = Z; d.w1 = 0; d.nw = Z;
   d.zg = 0; d.Zg = Z;
-  if (g_zorigin.total > 0) { d.zg = g_zorigin.first; d.Zg = g_zorigin.total; }
-  const ZWin w = g_zwin;
-  if (w.a1 > w.a0 || w.b1 > w.b0) {
+  return d;
+}
+// The launch domain of a windowed launcher: the planes of the scope's window, the array placed at the scope's origin.
+inline Dom make_dom(const Scope& sc, int Z, int Y, int X) {
+  Dom d = whole_dom(Z, Y, X);
+  if (sc.origin.total > 0) { d.zg = sc.origin.first; d.Zg = sc.origin.total; }
+  const ZWin w = sc.win;
+  if (sc.windowed()) {
     auto clip = [Z](int v) { return v < 0 ? 0 : (v > Z ? Z : v); };
     const int a0 = clip(w.a0), a1 = clip(w.a1) > a0 ? clip(w.a1) : a0;
     const int b0 = clip(w.b0), b1 = clip(w.b1) > b0 ? clip(w.b1) : b0;
@@ -92,8 +105,6 @@ inline Dom make_dom(int Z, int Y, int X) {
   }
   return d;
 }
-// number of planes a launch over a Z-deep array covers under the current window (grid.z = this * B)
-inline int zwin_planes(int Z) { return make_dom(Z, 1, 1).nw; }
 
 // Built-in per-kernel timing (the reference only has host timers around the projection,
 // lib/simulate.lua:254-260,306-318). When a profile is active on this thread every kernel launch is
@@ -125,14 +136,14 @@ struct KernelTimer {
   } while (0)
 
 // advect.hip
-void advect_scalar(hipStream_t st, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
+void advect_scalar(hipStream_t st, const Scope& sc, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
                    int outside, unsigned long long* err, const float* s, const float* U, const float* flags,
-                   float* fwd, float* bounds, float* mm, float* dst, int stages, Fold& f);
-void advect_vel(hipStream_t st, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
-                unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, int stages, Fold& f);
+                   float* fwd, float* bounds, float* mm, float* dst, Fold& f);
+void advect_vel(hipStream_t st, const Scope& sc, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
+                unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, Fold& f);
 
-void minmax3(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int outside, const float* s, const float* flags,
-             float* lo3, float* hi3);
+void minmax3(hipStream_t st, bool is3d, int B, const Dom& d, int outside, const float* s, const float* flags, float* lo3,
+             float* hi3);
 
 // stencil.hip
 void set_wall_bcs(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags);
@@ -146,9 +157,9 @@ void velocity_divergence_planes(hipStream_t st, int B, int Z, int Y, int X, int 
                                 float* div);
 void velocity_update_planes(hipStream_t st, int B, int Z, int Y, int X, int k0, int k1, float* U, const float* flags,
                             const float* p);
-void add_buoyancy(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* Usrc, float* U, const float* flags,
+void add_buoyancy(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* Usrc, float* U, const float* flags,
                   const float* density, float sx, float sy, float sz, Fold& f);
-void add_gravity(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags, float fx,
+void add_gravity(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags, float fx,
                  float fy, float fz);
 void empty_domain(hipStream_t st, bool is3d, int bnd, int B, int Z, int Y, int X, float* flags);
 void flags_to_occupancy(hipStream_t st, long long numel, const float* flags, float* occ);
@@ -162,15 +173,15 @@ void reach_publish(hipStream_t st, const float* src, float* dst, unsigned* tick)
 
 // vorticity.hip
 // stages: bit 0 = pass A (U -> curl, |curl|), bit 1 = pass B (curl, |curl|, flags, U -> U); a z-slab rank runs the two
-// passes under different z-windows
+// passes under different z-windows (sc: the window and origin only -- the caller has mapped sc.stages into `stages`)
 // Usrc (round 5): U = Usrc + force with every cell of the window written (the four-cells-per-thread kernels only: false =
 // not possible here, nothing launched, the caller copies Usrc into U and calls again without it)
-bool vorticity_confinement(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags,
+bool vorticity_confinement(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags,
                            float strength, float* curl, float* curl_norm, int stages, const float* Usrc, Fold& f);
 
 // U_out = U_in + confinement(U_in), 3-D, one fused launch without curl arrays (U_out != U_in); false = not supported here
 bool vorticity_confinement_fused_ok(bool is3d, int Z, int Y, int X);   // does the native step use the fused kernel for this grid
-bool vorticity_confinement_fused(hipStream_t st, int B, int Z, int Y, int X, const float* Uin, float* Uout, const float* flags,
+bool vorticity_confinement_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* Uin, float* Uout, const float* flags,
                                  float strength, Fold& f);
 
 // jacobi.hip
@@ -198,11 +209,11 @@ int normalize_pressure_mean(hipStream_t st, bool is3d, int B, int Z, int Y, int 
 long long model_stat_blocks(int B, int Z, int Y, int X);
 bool model_stats_fold_requested();
 long long model_stat_pairs_per_plane(int B, int Z, int Y, int X, const float* U, const float* flags, const float* Ubc, const float* div);   // as model_pre lays them out
-void model_pre(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* U, const float* flags, float* Ubc,
+void model_pre(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* U, const float* flags, float* Ubc,
                float* div, double* partials, double* stats, int zlo, int zhi, int stages = 3, unsigned* ticket = nullptr,
                const unsigned short* wall_code = nullptr);      // wall_code: the flags' tfl_wall_plan (round 6), or null
 void wall_code(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* flags, unsigned short* code);
-// (z0 / nz, here and in the two below: the planes [z0, z0 + nz) only; nz < 0 = the thread's z-window, as make_dom reads it)
+// (z0 / nz, here and in the two below: the planes [z0, z0 + nz) only; nz < 0 = every plane)
 void model_net_input(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* pDiv, const float* div,
                      const float* flags, const double* stats, double count, float* x3, int z0 = 0, int nz = -1);
 // the general net input of lib/model.lua:130-148: channels {pDiv/scale?, SetWallBcs(U)/scale (C)?, div/scale?, occupancy} in
@@ -220,7 +231,7 @@ void model_field_stats_planes(hipStream_t st, int B, int C, int Z, long long yx,
 void model_skip_channel(hipStream_t st, int B, long long cells, const float* pDiv, const double* stats, double count,
                         float* dst, int och, int ch, long long t0 = 0, long long nt = -1);     // cells [t0, t0 + nt) only
 // returns true when the launch also folded max |u_z| of what it wrote into *reach_acc (round 6: k_project_v4 on full blocks)
-bool model_project(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* pPred, const float* flags,
+bool model_project(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* pPred, const float* flags,
                    const double* stats, double count, float* Uio, float* pOut, const float* UBC, const float* UInvMask,
                    int do_clamp, float lo, float hi, const unsigned long long* range_src, unsigned long long* range_dst,
                    const float* reach_src, float* reach_dst, float* reach_acc, const unsigned short* wall_code, unsigned* reach_tick,
@@ -272,7 +283,7 @@ void model_slab_stats(hipStream_t st, const tfl_model* m, int B, int Z, long lon
 // conv.hip
 // upf > 1: the result goes to sub-position `sub` (= (c*upf + b)*upf + a) of an upf-times finer output grid (pixel shuffle)
 // act: 0 none | 1 ReLU | 2 ReLU6 | 3 sigmoid; out_ch: channel planes per batch item of `out` (0 = cout)
-// z0 / nz: compute the conv-grid planes [z0, z0 + nz) only (nz < 0: all Z; the thread's z-window is not read)
+// z0 / nz: compute the conv-grid planes [z0, z0 + nz) only (nz < 0: all Z)
 bool conv_direct(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int cin, int cout, int ksz, int act,
                  const float* in, const float* w, const float* bias, float* out, int upf = 1, int sub = 0, int out_ch = 0,
                  int z0 = 0, int nz = -1);
@@ -294,43 +305,43 @@ bool bank_join(hipStream_t st, bool is3d, bool add, int B, int C, int Z, int Y, 
                const float* const* src, float* out, int och);
 
 // conv_mfma.hip (3-D default topology: k=3, 8 output channels; x-phase-packed fp32 MFMA)
-void conv3_mfma_first(hipStream_t st, int B, int Z, int Y, int X, const float* in_planar3, const float* bfrag,
+void conv3_mfma_first(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* in_planar3, const float* bfrag,
                       const float* bias, float* out_cl8);
-void conv3_mfma_first_fused(hipStream_t st, int B, int Z, int Y, int X, const float* pDiv, const float* div,
+void conv3_mfma_first_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* pDiv, const float* div,
                             const float* flags, const double* stats, double count, const float* bfrag,
                             const float* bias, float* out_cl8);
-void conv3_mfma_mid(hipStream_t st, int B, int Z, int Y, int X, const float* in_cl8, const float* bfrag,
+void conv3_mfma_mid(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* in_cl8, const float* bfrag,
                     const float* bias, float* out_cl8);
-void conv3_mfma_tail(hipStream_t st, int B, int Z, int Y, int X, const float* in_cl8, const float* bfrag,
+void conv3_mfma_tail(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* in_cl8, const float* bfrag,
                      const float* bias, const float* w4, const float* b4, const float* w5, const float* b5,
                      float* p_out);
 
 // conv_valu.hip: the same three layers on the vector ALUs, x-taps as Winograd F(2,3) (wq = tfl_model::wino,
 // [dz][dy][cin][4][8]); activations between the layers are channel-planar [B][8][Z][Y][X]
-void conv3_valu_first_fused(hipStream_t st, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
+void conv3_valu_first_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
                             const double* stats, double count, const float* wq, const float* bias, float* out_p8);
-void conv3_valu_mid(hipStream_t st, int B, int Z, int Y, int X, const float* in_p8, const float* wq, const float* bias,
+void conv3_valu_mid(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* in_p8, const float* wq, const float* bias,
                     float* out_p8);
 // tail_pack: {bias of the k3 layer [8], w4 [8][8] (out, in), b4 [8], w5 [8], b5 [1]} (tfl_model::tail_pack)
-void conv3_valu_tail(hipStream_t st, int B, int Z, int Y, int X, const float* in_p8, const float* wq, const float* tail_pack,
+void conv3_valu_tail(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* in_p8, const float* wq, const float* tail_pack,
                      float* p_out);
 
 // conv_mfma16.hip: the same three layers as a split-operand fp16 MFMA implicit GEMM; activations between the layers are
 // "h2": per (b, z, y) two rows [x][8] of fp16 (hi, lo): 32 B per voxel. wfrag / post from conv3_m16_pack_weights.
-void conv3_m16_first_fused(hipStream_t st, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
+void conv3_m16_first_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
                            const double* stats, double count, const void* wfrag, const float* bias, float post, void* out_h2,
                            unsigned long long* range_err, const double* partials = nullptr, long long per_sample = 0,
                            double* stats_out = nullptr);
 // round 6: can the first layer sum k_bcs_div_stats' partial pairs itself (partials / per_sample / stats_out above)? Then
 // tfl_model_forward skips the launch of k_reduce_stats between the two kernels.
 bool conv3_m16_first_sums_partials();
-void conv3_m16_mid(hipStream_t st, int B, int Z, int Y, int X, const void* in_h2, const void* wfrag, const float* bias, float post,
+void conv3_m16_mid(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const void* in_h2, const void* wfrag, const float* bias, float post,
                    void* out_h2, unsigned long long* range_err);
-void conv3_m16_tail(hipStream_t st, int B, int Z, int Y, int X, const void* in_h2, const void* wfrag, const float* tail_pack,
+void conv3_m16_tail(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const void* in_h2, const void* wfrag, const float* tail_pack,
                     float post, float* p_out, unsigned long long* range_err);
 // layers 1 + 2 in ONE launch (round 5: the 64 B/voxel between them stay in LDS); false = not taken (z-window set, or switched
 // off): the caller runs conv3_m16_first_fused + conv3_m16_mid
-bool conv3_m16_first2_fused(hipStream_t st, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
+bool conv3_m16_first2_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
                             const double* stats, double count, const void* wfrag1, const float* bias1, float post1,
                             const void* wfrag2, const float* bias2, float post2, void* out_h2, unsigned long long* range_err);
 bool conv3_m16_fuse12_requested();      // EXPERIMENTS flavour + TFL_M16_FUSE12=1 (the default library: always false)

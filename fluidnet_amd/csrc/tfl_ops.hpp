@@ -1,5 +1,6 @@
-// tfl_ops.hpp -- library-internal (C++ linkage) forms of the operators that the native steps of simulate.cpp call with a
-// request: each takes the public tfl_* operator's arguments plus an Ask. The public operator (abi.cpp) passes an empty one.
+// tfl_ops.hpp -- library-internal (C++ linkage) forms of the operators that the native steps of simulate.cpp call: each takes
+// the public tfl_* operator's arguments plus where it computes and which passes run (tfl_host.hpp Scope) and a request (Ask).
+// The public operator (abi.cpp) passes scope_of(its context) and an empty Ask; a native step passes scopes of its own.
 #pragma once
 #include "../../include/tfluids_hip.h"
 #include "tfl_host.hpp"
@@ -17,25 +18,35 @@ struct Ask {
   bool reach_folded = false;       // ... out: and folded max|u_z| of the planes it wrote into the word
 };
 
+Scope scope_of(const tfl_ctx* c);     // what tfl_set_z_window / _z_origin / _stages / _advect_mode left on the context
+// tfluids.getDx (grid.cc:37-40) in float, as the operators form dt / dx, and in double: the scope's dx_cells, else
+// tfl_set_dx_override, else the array's own largest dimension
+float get_dx(const tfl_ctx* c, const Scope& sc, const tfl_tensor* flags);
+double get_dx_double(const tfl_ctx* c, const Scope& sc, const tfl_tensor* flags);
+
 int advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* fwd,
                  const tfl_tensor* bwd, int is3D, const char* method, const tfl_tensor* fwdPos, const tfl_tensor* bwdPos,
-                 int boundaryWidth, int sampleOutsideFluid, float maccormackStrength, const tfl_tensor* sDst, Ask& ask);
+                 int boundaryWidth, int sampleOutsideFluid, float maccormackStrength, const tfl_tensor* sDst, const Scope& sc,
+                 Ask& ask);
 int advectVel(tfl_ctx* c, float dt, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* fwd, const tfl_tensor* bwd,
-              int is3D, const char* method, int boundaryWidth, float maccormackStrength, const tfl_tensor* UDst, Ask& ask);
+              int is3D, const char* method, int boundaryWidth, float maccormackStrength, const tfl_tensor* UDst, const Scope& sc,
+              Ask& ask);
 int addBuoyancyFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* density,
-                    const float gravity[3], float dt, int is3D, Ask& ask);
+                    const float gravity[3], float dt, int is3D, const Scope& sc, Ask& ask);
+int addGravity(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const float gravity[3], float dt, int is3D, const Scope& sc);
 int vorticityConfinement(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, float strength, const tfl_tensor* centered,
-                         const tfl_tensor* curl, const tfl_tensor* curlNorm, const tfl_tensor* force, int is3D, Ask& ask);
+                         const tfl_tensor* curl, const tfl_tensor* curlNorm, const tfl_tensor* force, int is3D, const Scope& sc,
+                         Ask& ask);
 int vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, float strength,
-                             const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D, Ask& ask);
+                             const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D, const Scope& sc, Ask& ask);
 int model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tensor* flags, const tfl_tensor* UOut, float* workspace,
-                int64_t workspace_floats, int zlo, int zhi, double* stats, Ask& ask);
+                int64_t workspace_floats, int zlo, int zhi, double* stats, const Scope& sc, Ask& ask);
 int model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* flags, const tfl_tensor* pOut,
                  const tfl_tensor* UOut, float* workspace, int64_t workspace_floats, const double* stats, double count,
-                 const tfl_tensor* UBC, const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, Ask& ask);
+                 const tfl_tensor* UBC, const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, const Scope& sc, Ask& ask);
 int model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
                   const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace, int64_t workspace_floats, const tfl_tensor* UBC,
-                  const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, Ask& ask);
+                  const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, const Scope& sc, Ask& ask);
 
 // The MacCormack(Ours) advection of one density channel AND of the velocity on a 3-D grid (the z-slab step), their passes A as
 // one launch (stage bit 2) and their passes B as one launch (stage bit 4) -- advect_pair3.hip. fold_s / fold_v: the
@@ -43,7 +54,7 @@ int model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_te
 // advectScalar and advectVel.
 int advect_pair(tfl_ctx* c, float dt, float strength, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags,
                 const tfl_tensor* sfwd, const tfl_tensor* sbounds, const tfl_tensor* sDst, const tfl_tensor* vfwd, const tfl_tensor* UDst,
-                const BcFoldArg& fold_s, const BcFoldArg& fold_v);
+                const BcFoldArg& fold_s, const BcFoldArg& fold_v, const Scope& sc);
 const unsigned long long* model_range_counter(const tfl_model* m);     // the model's fp16 range word (device)
 
 }  // namespace tfl

@@ -92,7 +92,8 @@ __device__ __forceinline__ void v4_load6(const V4Ctx& c, const float* __restrict
 // Host side: launch geometry for a vec4 kernel, or ok=false when the contract does not hold (odd X, a
 // misaligned view, or TFL_NO_VEC4 set: callers then fall back to their one-cell-per-thread kernel).
 struct Vec4Launch { bool ok; dim3 blk, grd; };
-inline Vec4Launch vec4_launch(int B, int Z, int Y, int X, std::initializer_list<const void*> ptrs) {
+inline Vec4Launch vec4_launch(int B, const Dom& d, std::initializer_list<const void*> ptrs) {
+  const int Y = d.Y, X = d.X;
   Vec4Launch l; l.ok = false;
   static const bool disabled = exp_env("TFL_NO_VEC4") != nullptr;
   uintptr_t al = 0;
@@ -100,7 +101,7 @@ inline Vec4Launch vec4_launch(int B, int Z, int Y, int X, std::initializer_list<
   if (disabled || X % 4 != 0 || (al & 15) != 0) return l;
   const int nx = X / 4, bx = nx <= 8 ? 8 : (nx <= 16 ? 16 : 32), by = 256 / bx;
   l.blk = dim3(bx, by, 1);
-  l.grd = dim3((nx + bx - 1) / bx, (Y + by - 1) / by, (unsigned)(zwin_planes(Z) * B));
+  l.grd = dim3((nx + bx - 1) / bx, (Y + by - 1) / by, (unsigned)(d.nw * B));
   l.ok = true;
   return l;
 }

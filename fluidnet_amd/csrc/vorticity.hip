@@ -1029,10 +1029,10 @@ bool vorticity_confinement_fused_ok(bool is3d, int Z, int Y, int X) {
 }
 
 // false = shape not supported by the fused kernel (the caller copies and runs the two-launch form)
-bool vorticity_confinement_fused(hipStream_t st, int B, int Z, int Y, int X, const float* Uin, float* Uout, const float* flags,
+bool vorticity_confinement_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* Uin, float* Uout, const float* flags,
                                  float strength, Fold& f) {
   if (Z < 3 || Uin == Uout) return false;
-  const Dom d = make_dom(Z, Y, X);
+  const Dom d = make_dom(sc, Z, Y, X);
   const int na = d.n0, nb = d.nw - d.n0;
   const int xcd_order = xcd_order_enabled() ? 1 : 0;
   // the software-pipelined form (one barrier per step; 64 x 16 tiles, 9 steps of fill) wherever the device can hold its block:
@@ -1061,12 +1061,12 @@ bool vorticity_confinement_fused(hipStream_t st, int B, int Z, int Y, int X, con
   return true;
 }
 
-bool vorticity_confinement(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags,
+bool vorticity_confinement(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags,
                            float strength, float* curl, float* curl_norm, int stages, const float* Usrc, Fold& f) {
-  const Dom d = make_dom(Z, Y, X);
+  const Dom d = make_dom(sc, Z, Y, X);
   const dim3 blk(64, 4, 1), grd((X + 63) / 64, (Y + 3) / 4, (unsigned)(d.nw * B));
   const float* Uin = Usrc ? Usrc : U;
-  const Vec4Launch v = vec4_launch(B, Z, Y, X, {U, flags, curl, curl_norm, Uin});
+  const Vec4Launch v = vec4_launch(B, d, {U, flags, curl, curl_norm, Uin});
   const bool pa = stages & 1, pb = stages & 2;
   if (v.ok) {
     const BcFoldArg fold = pb ? f.hand_bc() : no_fold();   // pass B writes the operator's result

@@ -609,7 +609,9 @@ int64_t tfl_simulate_slab_workspace_floats(tfl_ctx* ctx, const tfl_sim_params* p
  * (the same halos serve every advection method: DESIGN.md section 6c derives each method's dependency cone)
  *   divergence(4 below, 3 above)          overlapped with the interior of the first conv layer
  * and every phase runs under the narrowest z-window that keeps the owned planes exact, so the redundant compute is a
- * few planes per phase instead of a fixed wide halo.
+ * few planes per phase instead of a fixed wide halo. Those windows, stage masks and the slab's
+ * origin are the step's own: it neither reads nor changes what tfl_set_z_window / tfl_set_stages / tfl_set_z_origin left
+ * on the context (tfl_set_advect_mode is honoured).
  * Jacobi instead: the same U + p message and T2, then divergence(J-1 planes a side) once, and p(J planes a side) after every
  * J sweeps -- floor(maxIter / J) exchanges, none before the first sweep (p starts at zero) -- where J = the stored halo depth
  * (own_lo, or z_local - own_hi on the lowest rank; every rank must store the same depth). No all-reduce (check_reach = 2

@@ -650,6 +650,40 @@ def test_zslab_decomposition_equals_single_gpu(world, overlap):
         s.close()
 
 
+def test_zslab_step_does_not_see_the_contexts_window():
+    """tfl_simulate_step_slab gives every operator call its own window, stage mask and origin: what a host left on the context
+    with tfl_set_z_window / tfl_set_stages / tfl_set_z_origin must not reach the step. One rank-step (world 1) on a context with
+    all three set equals, bit for bit and on every plane, the same step on a fresh context."""
+    import torch
+    from fluidnet_amd import FluidNetModel
+    from fluidnet_amd.simulate import simulate_native
+    dev = torch.device("cuda:0")
+    b = _plume_batch((12, 24, 32), 0.15, 0.6, obstacles_seed=11)
+    mconf = dict(dt=0.1, advectionMethod="maccormackOurs", maccormackStrength=0.6, buoyancyScale=1.0,
+                 gravityScale=0.2, vorticityConfinementAmp=2.0, simMethod="convnet")
+    layers = S.default_3d_layers(seed=2)
+    ref = _to_dev(b, dev)
+    for _ in range(2):                           # a state with a flow in it
+        simulate_native(None, mconf, ref, FluidNetModel(layers, True))
+    torch.cuda.synchronize()
+    assert float(ref["UDiv"].abs().max()) > 0
+    fresh, = _slab_sims(ref, mconf, 1, layers)
+    dirty, = _slab_sims(ref, mconf, 1, layers)
+    lib, ctx = dirty._context()
+    assert lib.tfl_set_z_window(ctx, 2, 5, 7, 9) == 0
+    assert lib.tfl_set_stages(ctx, 2) == 0
+    assert lib.tfl_set_z_origin(ctx, 3, 40) == 0
+    for s in (fresh, dirty):
+        s.step()
+        s.drain()
+    torch.cuda.synchronize()
+    for k in ("pDiv", "UDiv", "density"):
+        assert torch.equal(dirty.batch[k], fresh.batch[k]), k
+    assert not torch.equal(fresh.batch["UDiv"], ref["UDiv"])      # the step did something
+    for s in (fresh, dirty):
+        s.close()
+
+
 def test_zslab_reach_violation_is_reported():
     """A flow faster than the slab's back-trace reach (max|u_z|*dt >= R) breaks the halo contract: the step after the
     offending one must raise instead of silently returning wrong planes (unchecked precondition)."""
