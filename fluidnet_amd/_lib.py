@@ -100,6 +100,8 @@ SIGNATURES = {
                                  _c.c_int, _c.c_float, _T]),
     "tfl_setWallBcsForward": (_c.c_int, [_c.c_void_p, _T, _T, _c.c_int]),
     "tfl_velocityDivergenceForward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int]),
+    "tfl_divergence_norm_workspace_floats": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32]),
+    "tfl_velocityDivergenceNorm": (_c.c_int, [_c.c_void_p, _T, _T, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int64]),
     "tfl_velocityUpdateForward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int]),
     "tfl_vorticityConfinement": (_c.c_int, [_c.c_void_p, _T, _T, _c.c_float, _T, _T, _T, _T,
                                             _c.c_int]),
@@ -190,6 +192,8 @@ SIGNATURES = {
     "tfl_rccl_comm_set_inline": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "tfl_slab_drain": (_c.c_int, [_c.c_void_p, _c.POINTER(tfl_sim_state), _c.POINTER(tfl_slab), _c.POINTER(tfl_comm),
                                   _c.c_void_p, _c.c_int64]),
+    "tfl_slab_divergence_norm": (_c.c_int, [_c.c_void_p, _c.POINTER(tfl_sim_state), _c.POINTER(tfl_slab), _c.POINTER(tfl_comm),
+                                            _c.c_void_p, _c.c_int64, _c.c_void_p]),
     "tfl_slab_needed_reach": (_c.c_int32, [_c.c_void_p]),
     "tfl_slab_exchange_floats": (_c.c_int64, [_c.c_int, _c.POINTER(_c.POINTER(tfl_tensor)), _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32),
                                                _c.POINTER(tfl_slab)]),

@@ -504,6 +504,28 @@ int tfl_velocityDivergenceForward(tfl_ctx* c, const tfl_tensor* U, const tfl_ten
   return check_launch(c, "velocityDivergenceForward");
 }
 
+int64_t tfl_divergence_norm_workspace_floats(int32_t B, int32_t Z, int32_t Y, int32_t X) {
+  (void)Y; (void)X;
+  if (B < 1 || Z < 1) return 0;
+  return 2ll * B * Z;        // one double per (batch item, z-plane)
+}
+
+int tfl_velocityDivergenceNorm(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, int is3D, double* norm, float* workspace,
+                               int64_t workspace_floats) {
+  TRY(check_flags(c, "velocityDivergenceNorm", flags));
+  TRY(check_vel(c, "velocityDivergenceNorm", "U", U, flags, is3D));
+  if (!norm || ((uintptr_t)norm & 7) != 0) return fail(c, TFL_EINVAL, "velocityDivergenceNorm: norm is null or not 8-byte aligned");
+  if (!workspace || ((uintptr_t)workspace & 7) != 0 ||
+      workspace_floats < tfl_divergence_norm_workspace_floats(flags->B, flags->Z, flags->Y, flags->X))
+    return fail(c, TFL_EINVAL, "velocityDivergenceNorm: workspace too small or not 8-byte aligned (tfl_divergence_norm_workspace_floats)");
+  double* sums = reinterpret_cast<double*>(workspace);
+  // the whole array, like tfl_velocityDivergenceForward: the empty scope, whatever tfl_set_z_window / _z_origin left on the context
+  tfl::divergence_norm_planes(c->stream, tfl::Scope{}, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, sums,
+                              flags->Z, 0);
+  tfl::divergence_norm_finish(c->stream, flags->B, flags->Z, sums, norm);
+  return check_launch(c, "velocityDivergenceNorm");
+}
+
 int tfl_velocityUpdateForward(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* p,
                               int is3D) {
   TRY(check_flags(c, "velocityUpdateForward", flags));

@@ -729,6 +729,46 @@ int tfl_slab_drain(tfl_ctx* c, const tfl_sim_state* s, tfl_slab* sl, const tfl_c
   return finish_in_flight(c, g, comm, m, sl);
 }
 
+// The divergence norm of the whole grid from its slabs (include/tfluids_hip.h; divnorm.hip). Bit-equal to the un-cut
+// tfl_velocityDivergenceNorm: each plane's sum is formed by the rank that owns it, by the un-cut call's kernel in the un-cut
+// call's order (it depends on (Y, X) only), the all-reduce adds zeros to it, and stage 2 adds the planes as the un-cut call does.
+int tfl_slab_divergence_norm(tfl_ctx* c, const tfl_sim_state* s, tfl_slab* sl, const tfl_comm* comm, float* ws, int64_t ws_floats,
+                             double* norm) {
+  if (!c) return TFL_EINVAL;
+  if (!s || !sl || !ws || !norm || ((uintptr_t)norm & 7) != 0) { c->err = "slab_divergence_norm: null state, slab, workspace or norm"; return TFL_EINVAL; }
+  SlabGeom g;
+  TRY(slab_geom(c, s, sl, &g));
+  if (!sizes_of(s).is3d) { c->err = "slab_divergence_norm: 2-D grids have no z to cut (run replicas)"; return TFL_EUNSUPPORTED; }
+  const bool multi = g.lower || g.upper;
+  if (multi && (!comm || comm->size < (int32_t)(offsetof(tfl_comm, allreduce_sum) + sizeof(comm->allreduce_sum)) ||
+                !comm->exchange_wait || !comm->allreduce_sum)) {
+    c->err = "slab_divergence_norm: tfl_comm is null, has no size or lacks a required callback";
+    return TFL_EINVAL;
+  }
+  if (((uintptr_t)ws & 15) != 0 || ws_floats < slab_ws(g, s, nullptr, nullptr)) { c->err = "slab_divergence_norm: workspace too small or misaligned"; return TFL_EINVAL; }
+  SlabWs W;
+  slab_ws(g, s, ws, &W);
+  // the plane sums live in the compute region (13 fields of the local array or the model's workspace: dead between steps)
+  const long long n_sums = (long long)g.B * sl->z_total;
+  if (2 * n_sums > W.compute_floats) { c->err = "slab_divergence_norm: the plane sums (B * z_total doubles) do not fit the workspace's compute region"; return TFL_EINVAL; }
+  Msg m[4];
+  slab_messages(g, s, s->U, s->flags, m);
+  msg_layout(g, m, 4, W.msg);
+  TRY(finish_in_flight(c, g, comm, m, sl));          // U on the plane above the owned range
+  double* sums = reinterpret_cast<double*>(W.compute);
+  if (hipMemsetAsync(sums, 0, sizeof(double) * (size_t)n_sums, c->stream) != hipSuccess) {
+    (void)hipGetLastError(); c->err = "slab_divergence_norm: hipMemsetAsync failed"; return TFL_EHIP;
+  }
+  tfl::Scope sc;
+  sc.win = tfl::ZWin{g.o0, g.o1, 0, 0}; sc.origin = tfl::ZOrigin{sl->z_first, sl->z_total};
+  tfl::divergence_norm_planes(c->stream, sc, true, g.B, g.Zl, s->flags->Y, s->flags->X, s->U->data, s->flags->data, sums, sl->z_total,
+                              sl->z_first);
+  if (multi && comm->allreduce_sum(comm->user, sums, n_sums) != 0) { c->err = "slab_divergence_norm: comm callback failed (allreduce_sum)"; return TFL_EINVAL; }
+  tfl::divergence_norm_finish(c->stream, g.B, sl->z_total, sums, norm);
+  if (hipGetLastError() != hipSuccess) { c->err = "slab_divergence_norm: a launch failed"; return TFL_EHIP; }
+  return TFL_OK;
+}
+
 namespace {
 
 // One rank-step, phase by phase. The phases share the call's arguments, the slab's geometry, the workspace views and messages,

@@ -171,6 +171,14 @@ void absmax(hipStream_t st, long long n, const float* x, float* out, bool reset)
 void reach_flags(hipStream_t st, const float* maxu, float dt, int n, double* flags, const unsigned long long* range_count = nullptr);   // flags[r-1] = (*maxu * dt >= r), r = 1..n (n <= 62); flags[n] = (*range_count != 0) when given
 void reach_publish(hipStream_t st, const float* src, float* dst, unsigned* tick);   // dst[0] = *src, dst[1] = ++*tick (mapped pinned mirror)
 
+// divnorm.hip: ||velocityDivergence(U, flags)[b]||_2 in two launches, no divergence field, no atomics.
+// Stage 1: sums[b * zstride + zoff + k] = the fp64 sum of the squared fp32 divergence over plane k, for the planes k of the
+// scope's window (the scope's origin decides which planes are the domain's border). Stage 2: norm[b] = sqrt of the sum of
+// sums[b * nz + 0 .. nz - 1] in ascending order.
+void divergence_norm_planes(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* U, const float* flags,
+                            double* sums, int zstride, int zoff);
+void divergence_norm_finish(hipStream_t st, int B, int nz, const double* sums, double* norm);
+
 // vorticity.hip
 // stages: bit 0 = pass A (U -> curl, |curl|), bit 1 = pass B (curl, |curl|, flags, U -> U); a z-slab rank runs the two
 // passes under different z-windows (sc: the window and origin only -- the caller has mapped sc.stages into `stages`)

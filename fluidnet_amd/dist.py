@@ -497,6 +497,33 @@ class SlabSimulation:
         if self.slab.in_flight & 0xF:      # (bits 0-3: messages; bit 8 is the library's own)
             self._call(self.lib.tfl_slab_drain, ctypes.byref(self.st))
 
+    def divergence_norm(self, out=None):
+        """||velocityDivergence(U, flags)[b]||_2 of the WHOLE grid as a float64 device tensor [B], the same on every rank and
+        bit-equal to tfluids.velocityDivergenceNorm of the un-cut grid (tfl_slab_divergence_norm: the owned planes' sums, one
+        all-reduce of B * z_total doubles, the planes added in the un-cut order). Collective: every rank calls it at the same
+        step. It finishes the U / p messages the last step left in flight first; the next step is not disturbed."""
+        U = self.batch["UDiv"]
+        if out is None:
+            out = torch.empty(U.size(0), dtype=torch.float64, device=U.device)
+        if out.dtype != torch.float64 or out.dim() != 1 or out.size(0) != U.size(0) or not out.is_contiguous() or out.device != U.device:
+            raise TfluidsError("out must be a contiguous float64 tensor [B] on U's device")
+        lib, ctx = self._context()
+        if self.comm is not None and not hasattr(self.comm, "struct"):      # (a transport factory: see _call)
+            self.comm = self.comm(ctx)
+            self.comm.bind(self.ws)
+            if isinstance(self.comm, RcclComm):
+                self.comm.set_inline(not self.slab.overlap)
+        cptr = ctypes.byref(self.comm.struct) if self.comm is not None else None
+        if self.comm is not None:
+            self.comm.error = None
+        rc = lib.tfl_slab_divergence_norm(ctx, ctypes.byref(self.st), ctypes.byref(self.slab), cptr,
+                                          ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), ctypes.c_void_p(out.data_ptr()))
+        if rc != 0:
+            if self.comm is not None and self.comm.error is not None:
+                raise self.comm.error
+            raise TfluidsError(lib.tfl_last_error(ctx).decode())
+        return out
+
     def close(self):
         if self.graph is not None:
             lib, ctx = self._context()

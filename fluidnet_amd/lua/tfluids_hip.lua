@@ -63,6 +63,9 @@ int tfl_advectVel(tfl_ctx* ctx, float dt, const tfl_tensor* U, const tfl_tensor*
 int tfl_setWallBcsForward(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags, int is3D);
 int tfl_velocityDivergenceForward(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
                                   const tfl_tensor* UDiv, int is3D);
+int64_t tfl_divergence_norm_workspace_floats(int32_t B, int32_t Z, int32_t Y, int32_t X);
+int tfl_velocityDivergenceNorm(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags, int is3D,
+                               double* norm, float* workspace, int64_t workspace_floats);
 int tfl_velocityUpdateForward(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
                               const tfl_tensor* p, int is3D);
 int tfl_vorticityConfinement(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
@@ -245,6 +248,8 @@ int tfl_slab_exchange(tfl_ctx* ctx, int n, const tfl_tensor* const* fields, cons
                       const tfl_slab* slab, const tfl_comm* comm, float* scratch, int64_t scratch_floats);
 int tfl_slab_drain(tfl_ctx* ctx, const tfl_sim_state* state, tfl_slab* slab, const tfl_comm* comm, float* workspace,
                    int64_t workspace_floats);
+int tfl_slab_divergence_norm(tfl_ctx* ctx, const tfl_sim_state* state, tfl_slab* slab, const tfl_comm* comm, float* workspace,
+                             int64_t workspace_floats, double* norm);
 typedef struct tfl_slab_graph tfl_slab_graph;
 tfl_slab_graph* tfl_slab_graph_create(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state, tfl_slab* slab,
                                       const tfl_comm* comm, float* workspace, int64_t workspace_floats);
@@ -729,6 +734,25 @@ function Slab:drain()
   end
 end
 
+-- The divergence norm of the WHOLE grid from its slabs (tfl_slab_divergence_norm): a torch.CudaDoubleTensor [B], the same on
+-- every rank and bit-equal to M.velocityDivergenceNorm of the un-cut grid. Collective; call after slab:simulate().
+function Slab:divergenceNorm()
+  assert(self.st ~= nil, 'call slab:simulate() at least once first')
+  local out = torch.CudaDoubleTensor(self.st.flags.B)
+  check(lib.tfl_slab_divergence_norm(ctx, self.st, self.desc, self.callbacks, self.ws, self.n, ffi.cast('double*', torch.data(out))))
+  return out
+end
+
+--- || velocityDivergence(U, flags)[b] ||_2 per batch item as a torch.CudaDoubleTensor [B] (what lib/calc_stats.lua:98-118 takes
+--- with div[i]:norm(), one host synchronisation per sample): two launches, no divergence field, no host read.
+function M.velocityDivergenceNorm(U, flags)
+  local is3D = U:size(2) == 3
+  local out = torch.CudaDoubleTensor(flags:size(1))
+  local ws, n = workspace(flags, lib.tfl_divergence_norm_workspace_floats(flags:size(1), flags:size(3), flags:size(4), flags:size(5)))
+  check(lib.tfl_velocityDivergenceNorm(ctx, T(U), T(flags), b2i(is3D), ffi.cast('double*', torch.data(out)), ws, n))
+  return out
+end
+
 --- Arithmetic of the LDS-tiled 3-D advection kernels (include/tfluids_hip.h tfl_set_advect_mode): 'exact' (default; bit-equal
 --- to the reference CPU path) or 'fast' (the tolerance mode: rel-L2 ~2e-8 against the reference, bar 1e-5).
 function M.setAdvectMode(mode)
@@ -753,6 +777,7 @@ function M.install(tfluids, opts)
   mt.tfluids = mt.tfluids or {}
   for name, fn in pairs(ops) do mt.tfluids[name] = fn end
   rawset(tfluids, 'normalizePressureMean', M.normalizePressureMean)
+  rawset(tfluids, 'velocityDivergenceNorm', M.velocityDivergenceNorm)
   if not opts.keepLuaSimulate then rawset(tfluids, 'simulate', M.simulate) end
   tfluids.withHIP = true
   return M

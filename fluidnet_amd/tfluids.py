@@ -219,6 +219,23 @@ def velocityDivergenceForward(U, flags, UDiv):
                                                       int(is3D)))
 
 
+def velocityDivergenceNorm(U, flags, out=None):
+    """||velocityDivergence(U, flags)[b]||_2 per batch item as a float64 DEVICE tensor [B] (what lib/calc_stats.lua:98-118
+    records per step with div[i]:norm()), without the divergence field and without a host read: two launches on the
+    current stream (include/tfluids_hip.h tfl_velocityDivergenceNorm), so the call can be captured into a graph."""
+    bsz, d, h, w, is3D = _dims(U, flags)
+    lib, ctx = _context(U)
+    if out is None:
+        out = torch.empty(bsz, dtype=torch.float64, device=U.device)
+    _check(out.dtype == torch.float64 and out.dim() == 1 and out.size(0) == bsz and out.is_contiguous() and
+           out.device == U.device, "out must be a contiguous float64 tensor [B] on U's device")
+    n = int(lib.tfl_divergence_norm_workspace_floats(bsz, d, h, w))
+    ws, = getTempStorage(U, [(n,)])
+    _call(lib, ctx, lib.tfl_velocityDivergenceNorm(ctx, _tt(U), _tt(flags), int(is3D), ctypes.c_void_p(out.data_ptr()),
+                                                   ctypes.c_void_p(ws.data_ptr()), n))
+    return out
+
+
 def velocityUpdateForward(U, flags, p):
     """init.lua:322-347 (in place on U)."""
     _, _, _, _, is3D = _dims(U, flags)

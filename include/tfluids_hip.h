@@ -127,6 +127,18 @@ int tfl_setWallBcsForward(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* f
 int tfl_velocityDivergenceForward(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
                                   const tfl_tensor* UDiv, int is3D);
 
+/* norm[b] = || velocityDivergence(U, flags)[b] ||_2 for every batch item b, without the divergence field: what
+ * lib/calc_stats.lua:98-118 records after every step of a rollout (div[i]:norm(), one host synchronisation per sample there).
+ * Per cell the fp32 value is the bits tfl_velocityDivergenceForward writes; its square (exact in fp64) is accumulated in fp64
+ * in a fixed order -- one sum per z-plane, then the planes in ascending z, then the root -- with no atomics, so a call gives
+ * the same bits every time and batch item b's result does not depend on B. `norm` is DEVICE memory, B doubles; `workspace` is
+ * device memory, 8-byte aligned, tfl_divergence_norm_workspace_floats(B, Z, Y, X) floats. Two launches on the context's
+ * stream; no host read, no synchronisation, no allocation: the call can be captured into a HIP graph. Covers the whole array
+ * like tfl_velocityDivergenceForward (tfl_set_z_window / tfl_set_z_origin are not read). No reference counterpart. */
+int64_t tfl_divergence_norm_workspace_floats(int32_t B, int32_t Z, int32_t Y, int32_t X);
+int tfl_velocityDivergenceNorm(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags, int is3D,
+                               double* norm, float* workspace, int64_t workspace_floats);
+
 /* init.lua:346 -> third_party/tfluids.cc:1072-1156 | tfluids.cu:1111-1195 (in place on U). */
 int tfl_velocityUpdateForward(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
                               const tfl_tensor* p, int is3D);
@@ -636,6 +648,19 @@ int tfl_slab_exchange(tfl_ctx* ctx, int n, const tfl_tensor* const* fields, cons
  * valid too (call before reading halos on the host, or before freeing the workspace). */
 int tfl_slab_drain(tfl_ctx* ctx, const tfl_sim_state* state, tfl_slab* slab, const tfl_comm* comm, float* workspace,
                    int64_t workspace_floats);
+
+/* tfl_velocityDivergenceNorm of the WHOLE grid from its z-slabs: norm[b] (device, B doubles, the same on every rank) =
+ * || velocityDivergence(U, flags)[b] ||_2 over all z_total planes. `workspace` is the step's workspace. The call first finishes
+ * the U / p messages the last step left in flight (as tfl_slab_drain does: the plane above the owned range is valid then),
+ * sums each OWNED plane into a zeroed [B][z_total] array of doubles at the plane's global index (in the compute region of the
+ * workspace, which is dead between steps), makes ONE allreduce_sum of B * z_total doubles (none on a slab without neighbours)
+ * and adds the planes on every rank. A plane's sum is formed by its owner exactly as the un-cut call forms it, every other
+ * rank adds zeros to it, and the planes are added in the un-cut call's order: THE RESULT EQUALS tfl_velocityDivergenceNorm OF
+ * THE UN-CUT GRID BIT FOR BIT AT ANY WORLD SIZE. Collective; no host read or synchronisation of its own (a transport with
+ * `capturable` set only enqueues, so the call may be recorded; tfl_slab_graph_* does not record it). 2-D states are refused
+ * like the step ("no z to cut"). */
+int tfl_slab_divergence_norm(tfl_ctx* ctx, const tfl_sim_state* state, tfl_slab* slab, const tfl_comm* comm, float* workspace,
+                             int64_t workspace_floats, double* norm);
 
 /* ---- the rank-step as ONE host call (round 6). tfl_simulate_step_slab costs the host a dozen kernel launches plus the
  * transport's calls per step -- on a 16-plane slab about as long as the GPU needs to run them. tfl_slab_graph_create records
