@@ -47,7 +47,9 @@ ADVECT_EXACT, ADVECT_FAST = 0, 1
 
 def set_advect_mode(t, mode):
     """Arithmetic of the LDS-tiled 3-D advection kernels on t's device (include/tfluids_hip.h tfl_set_advect_mode):
-    "exact" (default; bit-equal to the reference CPU path) or "fast" (the tolerance mode, rel-L2 <= 1e-5).
+    "exact" (default; bit-equal to the reference CPU path) or "fast" (the tolerance mode, rel-L2 <= 1e-5; per voxel within
+    the derived fp64 bound of tests/advect_bound.py -- tens of 2^-24 of the local magnitude -- and the exact mode's bits
+    wherever the kernels take the generic path).
     Returns the previous mode's name."""
     lib, ctx = _context(t)
     names = {"exact": ADVECT_EXACT, "fast": ADVECT_FAST, ADVECT_EXACT: ADVECT_EXACT, ADVECT_FAST: ADVECT_FAST}

@@ -82,7 +82,10 @@ int tfl_abi_version(void);
  *                               trip), trilinear samples as contracted a + t (b - a), MacCormack correction in fp32.
  *                               Differs from the reference by a few ulp per cell; held to the north-star's rel-L2 <= 1e-5
  *                               by tests/test_hip_fullsize.py. Lanes off the fast path (obstacle neighbours, fast flow)
- *                               run the exact generic code in both modes.
+ *                               run the exact generic code in both modes. Per voxel: within the bound that
+ *                               tests/advect_bound.py derives from this arithmetic (tens of 2^-24 of the LOCAL magnitude)
+ *                               of the operator evaluated in fp64, and the exact mode's bits on the generic path
+ *                               (tests/test_hip_advect_bound.py).
  * A context starts in the mode named by the environment variable TFL_ADVECT_MODE ("fast" | "exact"; unset = exact). */
 enum { TFL_ADVECT_EXACT = 0, TFL_ADVECT_FAST = 1 };
 int tfl_set_advect_mode(tfl_ctx* ctx, int mode);
