@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void k_conv2_mfma(int B, int Y, int X, const f
         v0 = ci.pDiv[bo] / in_scale;   // ApplyScale(true) = CDivTable, apply_scale.lua:24-30
         v1 = ci.div[bo] / in_scale;
         const int f = (int)ci.flags[bo];   // FlagsToOccupancy, generic/tfluids.cu:355-371
-        v2 = (f == kFluid) ? 0.0f : ((f == kObstacle) ? 1.0f : -1.0f);
+        v2 = (f & kFluid) ? 0.0f : ((f & kObstacle) ? 1.0f : -1.0f);
       }
       lds[0 * k2Plane + idx] = v0; lds[1 * k2Plane + idx] = v1; lds[2 * k2Plane + idx] = v2;
       lds[3 * k2Plane + idx] = 0.0f;

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256, 4) void k_conv3_mfma(Dom d, int tiles_x, int t
             v[0] = ld[u][0].x / in_scale;
             v[1] = ld[u][1 % NLD].x / in_scale;
             const int f = (int)ld[u][2 % NLD].x;
-            v[CG - 1] = (f == kFluid) ? 0.0f : ((f == kObstacle) ? 1.0f : -1.0f);
+            v[CG - 1] = (f & kFluid) ? 0.0f : ((f & kObstacle) ? 1.0f : -1.0f);
           } else if (IN_PLANAR) {
 #pragma unroll
             for (int c = 0; c < CG; c++) v[c] = ld[u][c % NLD].x;

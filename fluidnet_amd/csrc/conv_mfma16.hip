@@ -519,7 +519,7 @@ __global__ __launch_bounds__(256, TFL_M16PI_LB) void k_conv3_m16p_in(Dom d, int 
       if (scale_in_range) { v0 = div_by<1>(raw[j][0], in_scale, inv_scale); v1 = div_by<1>(raw[j][1], in_scale, inv_scale); }
       else { v0 = raw[j][0] / in_scale; v1 = raw[j][1] / in_scale; }
       const int f = (int)raw[j][2];
-      const float occ = (f == kFluid) ? 0.0f : ((f == kObstacle) ? 1.0f : -1.0f);
+      const float occ = (f & kFluid) ? 0.0f : ((f & kObstacle) ? 1.0f : -1.0f);
       const float k0 = __builtin_fminf(__builtin_fmaxf(v0, -kHalfMax), kHalfMax), k1 = __builtin_fminf(__builtin_fmaxf(v1, -kHalfMax), kHalfMax);
       const bool ok = z_ok && st_in[j];
       clipped = clipped || (ok && (k0 != v0 || k1 != v1));

@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256, TFL_VALU_LB) void k_conv3_wino(Dom d, int tile
           if (scale_in_range) { v[0] = div_by<1>(ld[tt][0], in_scale, inv_scale); v[1] = div_by<1>(ld[tt][1], in_scale, inv_scale); }
           else { v[0] = ld[tt][0] / in_scale; v[1] = ld[tt][1] / in_scale; }
           const int f = (int)ld[tt][2];
-          v[2] = (f == kFluid) ? 0.0f : ((f == kObstacle) ? 1.0f : -1.0f);
+          v[2] = (f & kFluid) ? 0.0f : ((f & kObstacle) ? 1.0f : -1.0f);
         } else {
 #pragma unroll
           for (int c = 0; c < CG; c++) v[c] = ld[tt][c];

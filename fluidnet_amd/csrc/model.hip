@@ -439,7 +439,7 @@ __global__ __launch_bounds__(256) void k_net_input(Dom d, const float* __restric
   x3[o] = pDiv[bo + o] / scale;               // nn.ApplyScale(true) = CDivTable, apply_scale.lua:24-30
   x3[o + d.sc] = div[bo + o] / scale;
   const int f = (int)flags[bo + o];           // tfluids.FlagsToOccupancy, generic/tfluids.cu:355-371
-  x3[o + 2 * d.sc] = (f == kFluid) ? 0.0f : ((f == kObstacle) ? 1.0f : -1.0f);
+  x3[o + 2 * d.sc] = (f & kFluid) ? 0.0f : ((f & kObstacle) ? 1.0f : -1.0f);
 }
 
 // The general net input (tfl_model_opts): model.lua:130-148's JoinTable of the selected fields.
@@ -464,7 +464,7 @@ __global__ __launch_bounds__(256) void k_net_input_gen(Dom d, int in_pDiv, int i
     for (int c = 0; c < C; c++) x[o + (ch++) * cells] = Ubc[bo * C + o + c * cells] / scale;
   if (in_div) x[o + (ch++) * cells] = div[bo + o] / scale;
   const int f = (int)flags[bo + o];           // tfluids.FlagsToOccupancy, generic/tfluids.cu:355-371
-  x[o + ch * cells] = (f == kFluid) ? 0.0f : ((f == kObstacle) ? 1.0f : -1.0f);
+  x[o + ch * cells] = (f & kFluid) ? 0.0f : ((f & kObstacle) ? 1.0f : -1.0f);
 }
 
 __global__ __launch_bounds__(1024) void k_field_stats(long long n, const float* __restrict__ field, int mode,

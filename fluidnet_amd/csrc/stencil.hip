@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void k_flags_to_occupancy(long long n, const f
                                                             float* __restrict__ occ) {
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
     const int f = (int)flags[t];
-    occ[t] = (f == kFluid) ? 0.0f : ((f == kObstacle) ? 1.0f : -1.0f);
+    occ[t] = (f & kFluid) ? 0.0f : ((f & kObstacle) ? 1.0f : -1.0f);
   }
 }
 

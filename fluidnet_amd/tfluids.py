@@ -380,7 +380,11 @@ def getDx(flags):
 
 
 def flagsToOccupancy(flags, occupancy):
-    """init.lua:567-576."""
+    """init.lua:567-576, with the contract of the reference's CUDA build (generic/tfluids.cu:355-401): a word with the fluid bit
+    gives 0, otherwise one with the obstacle bit gives 1, anything else gives -1, and nothing raises (the reference leaves its
+    minimum check commented out: "this reduction is very expensive on GPU"). The reference's CPU function instead takes the two
+    plain words only and raises on every other (generic/tfluids.cc:175-210); callers that want that check read occupancy.min().
+    The projection net's fused occupancy reads decode the same way."""
     _check(flags.dim() == 5 and flags.size(1) == 1, "Flags should be 5D and scalar")
     _check(occupancy.shape == flags.shape, "Size mismatch")
     _check(flags.is_contiguous() and occupancy.is_contiguous(), "Input is not contiguous")

@@ -168,6 +168,16 @@ class OracleTfluids:
         b, d, h, w = self._dims(flags)
         self.lib.ora_normalizePressureMean(_p(p), _p(flags), int(bool(is3D)), b, d, h, w)
 
+    def findConnectedFluidComponents(self, flags, is3D):
+        """the labelling solveLinearSystemPCG solves on: (int32 [B, 1, Z, Y, X] component of each cell in the reference's
+        scan order, -1 without the fluid bit; number of components per sample)"""
+        b, d, h, w = self._dims(flags)
+        comp = np.empty(flags.shape, np.int32)
+        n = np.zeros(b, np.int32)
+        self.lib.ora_findConnectedFluidComponents(_p(flags), int(bool(is3D)), b, d, h, w, comp.ctypes.data_as(ctypes.c_void_p),
+                                                  n.ctypes.data_as(ctypes.c_void_p))
+        return comp, n
+
     def solveLinearSystemPCG(self, p, flags, div, is3D, tol=1e-6, maxIter=1000, precondType="ic0", verbose=False):
         """init.lua:645-677; restated from the CUDA-only generic/tfluids.cu:864-1759 (see tfluids_oracle.c)."""
         b, d, h, w = self._dims(flags)

@@ -1288,6 +1288,51 @@ static void csr_utsolve(long n, const int* row, const int* col, const float* val
   }
 }
 
+/* findConnectedFluidComponents (generic/find_connected_fluid_components.cc): scan order, depth-first stack. comp[n] = the
+ * component of cell n (-1: no fluid bit), sizes[c] = its cells; returns the number of components. */
+static int label_fluid_components(const dom_t* d, const float* fb, int is3d, int* comp, int* sizes, int* stack) {
+  const int X = d->X, Y = d->Y, Z = d->Z;
+  const long N = (long)X * Y * Z;
+  int ncomp = 0;
+  long n;
+  for (n = 0; n < N; n++) comp[n] = -1;
+  for (n = 0; n < N; n++) {
+    int sp = 0;
+    if (comp[n] != -1 || !(((int)fb[n]) & F_FLUID)) continue;
+    stack[sp++] = (int)n;
+    while (sp > 0) {
+      const int cur = stack[--sp];
+      const int ci = cur % X, cj = (cur / X) % Y, ck = cur / (X * Y);
+      const int nb[6][3] = {{ci - 1, cj, ck}, {ci + 1, cj, ck}, {ci, cj - 1, ck}, {ci, cj + 1, ck}, {ci, cj, ck - 1}, {ci, cj, ck + 1}};
+      int q;
+      comp[cur] = ncomp; sizes[ncomp]++;
+      for (q = 0; q < (is3d ? 6 : 4); q++) {
+        const int xi = nb[q][0], yj = nb[q][1], zk = nb[q][2];
+        long m;
+        if (xi < 0 || xi >= X || yj < 0 || yj >= Y || zk < 0 || zk >= Z) continue;
+        m = AT(d, xi, yj, zk);
+        if ((((int)fb[m]) & F_FLUID) && comp[m] == -1) { comp[m] = -2; stack[sp++] = (int)m; }
+      }
+    }
+    ncomp++;
+  }
+  return ncomp;
+}
+
+/* the labelling the PCG solver uses, for the tests: comp [B][Z][Y][X] ints (-1: no fluid bit), ncomp [B] */
+void ora_findConnectedFluidComponents(const float* flags, int is3d, int B, int Z, int Y, int X, int* comp, int* ncomp) {
+  dom_t dm = mkdom(Z, Y, X, is3d);
+  const long N = (long)X * Y * Z;
+  int* sizes = (int*)malloc(sizeof(int) * (N + 1));
+  int* stack = (int*)malloc(sizeof(int) * N);
+  int b;
+  for (b = 0; b < B; b++) {
+    memset(sizes, 0, sizeof(int) * (N + 1));
+    ncomp[b] = label_fluid_components(&dm, flags + b * N, is3d, comp + b * N, sizes, stack);
+  }
+  free(sizes); free(stack);
+}
+
 int ora_solveLinearSystemPCG(float* p, const float* flags, const float* div, int is3d, int precond, float tol,
                              int max_iter, int B, int Z, int Y, int X, float* out_residual) {
   dom_t dm = mkdom(Z, Y, X, is3d);
@@ -1311,29 +1356,8 @@ int ora_solveLinearSystemPCG(float* p, const float* flags, const float* div, int
     int ncomp = 0, c, i, j, k;
     long n;
     int* sizes;
-    /* findConnectedFluidComponents: scan order, depth-first stack */
-    for (n = 0; n < N; n++) comp[n] = -1;
     sizes = (int*)calloc((size_t)N + 1, sizeof(int));
-    for (n = 0; n < N; n++) {
-      int sp = 0;
-      if (comp[n] != -1 || !(((int)fb[n]) & F_FLUID)) continue;
-      stack[sp++] = (int)n;
-      while (sp > 0) {
-        const int cur = stack[--sp];
-        const int ci = cur % X, cj = (cur / X) % Y, ck = cur / (X * Y);
-        const int nb[6][3] = {{ci - 1, cj, ck}, {ci + 1, cj, ck}, {ci, cj - 1, ck}, {ci, cj + 1, ck}, {ci, cj, ck - 1}, {ci, cj, ck + 1}};
-        int q;
-        comp[cur] = ncomp; sizes[ncomp]++;
-        for (q = 0; q < (is3d ? 6 : 4); q++) {
-          const int xi = nb[q][0], yj = nb[q][1], zk = nb[q][2];
-          long m;
-          if (xi < 0 || xi >= X || yj < 0 || yj >= Y || zk < 0 || zk >= Z) continue;
-          m = AT(d, xi, yj, zk);
-          if ((((int)fb[m]) & F_FLUID) && comp[m] == -1) { comp[m] = -2; stack[sp++] = (int)m; }
-        }
-      }
-      ncomp++;
-    }
+    ncomp = label_fluid_components(d, fb, is3d, comp, sizes, stack);
     for (c = 0; c < ncomp && status == 0; c++) {
       long numel = 0, nz = 0, r;
       int pc = precond, iter = 0, upper;

@@ -6,7 +6,11 @@ import scenes
 
 
 def run_backward_ops(t, dims, seed, **kw):
-    sc = scenes.make_scene(dims, seed=seed, **kw)
+    return run_backward_ops_on(t, scenes.make_scene(dims, seed=seed, **kw), seed)
+
+
+def run_backward_ops_on(t, sc, seed):
+    """the same operators on a scene the caller made"""
     rng = np.random.RandomState(seed + 1000)
     f, U, p = sc["flags"], sc["U"], sc["p"]
     out = {}

@@ -469,3 +469,148 @@ def test_signed_distance_field(tracer, oracle, ref, is3d):
     oracle.signedDistanceField(flags, rad, is3d, d_o)
     ref.signedDistanceField(flags, rad, is3d, d_r)
     assert np.array_equal(d_o, d_r)
+
+
+# ---- the flag alphabet: every cell-type word next to every other, border included (tests/flag_alphabet.py) ---------------------
+import flag_alphabet as FA  # noqa: E402
+from backward_cases import run_backward_ops_on  # noqa: E402
+
+
+def test_neighbourhood_scene_holds_the_cover_it_claims():
+    """every ordered (centre word, face, neighbour word) triple and every pair of opposite-face words per axis, at the DESIGNED
+    stencil centres alone, on the two grids the GPU suite runs for the full cover; the alphabet is the issue's 16 words; the
+    generators are seeded (same call, same field) and leave the older generators' draws alone"""
+    assert len(set(scenes.ALPHABET)) == 16 and set(scenes.ALPHABET) >= {0, 1, 2, 4, 8, 16, 32, 128, 130, 20, 9, 36, 10, 17, 12, 129}
+    for dims in (FA.COVER3, (1, 66, 130)):
+        sc = FA.scene("neighbourhood", dims)
+        assert sc["stencils"] >= 256
+        cov = scenes.neighbourhood_cover(sc["flags"], sc["is3d"], centres=sc["centres"])
+        assert len(cov["face"]) == (6 if sc["is3d"] else 4) and len(cov["axis"]) == (3 if sc["is3d"] else 2)
+        assert all(v == cov["full"] == 256 for v in cov["face"].values()), cov
+        assert all(v == 256 for v in cov["axis"].values()), cov
+        assert np.array_equal(sc["flags"], FA.scene("neighbourhood", dims)["flags"])
+        assert not np.array_equal(sc["flags"][0], sc["flags"][1])
+        shell = scenes.border_mask(sc["flags"].shape, sc["is3d"])
+        assert np.all(sc["flags"][shell] == 2.0)
+    # a counting helper that cannot count would pass the above on anything: an all-fluid field holds one pair
+    cov = scenes.neighbourhood_cover(np.ones((1, 1, 4, 5, 6), np.float32), True)
+    assert set(cov["face"].values()) == {1} and set(cov["axis"].values()) == {1}
+    # alphabet_scene: every word present, the border overwritten only on request and then without the fluid bit
+    for border in (False, True):
+        sc = FA.scene("alphabet", (5, 9, 21), border)
+        shell = scenes.border_mask(sc["flags"].shape, True)
+        assert set(np.unique(sc["flags"][~shell]).astype(int)) == set(scenes.ALPHABET)
+        if border:
+            assert len(np.unique(sc["flags"][shell])) > 8 and not (sc["flags"][shell].astype(int) & 1).any()
+        else:
+            assert np.all(sc["flags"][shell] == 2.0)
+    sc = scenes.alphabet_scene((5, 9, 21), 3, B=2, border=True, fluid_border=True)
+    assert (sc["flags"][scenes.border_mask(sc["flags"].shape, True)].astype(int) & 1).any()
+
+
+@pytest.mark.parametrize("kind,dims,border", FA.CASES, ids=FA.CASE_IDS)
+def test_flag_alphabet_oracle_matches_reference_bitwise(oracle, ref, kind, dims, border):
+    """every operator of run_ops and the backward operators, oracle vs the compiled reference, bit for bit; an operator the
+    reference raises in must raise in the oracle too"""
+    sc = FA.scene(kind, dims, border)
+    words, _ = FA.compare_ops(FA.guarded_ops(oracle, sc), FA.guarded_ops(ref, sc), FA.case_id(kind, dims, border))
+    assert words > 0
+    seed = FA.seed_of(dims, kind, border)
+    a, b = run_backward_ops_on(oracle, sc, seed), run_backward_ops_on(ref, sc, seed)
+    for k in sorted(a):
+        assert np.array_equal(a[k], b[k]), k
+    occ_a, occ_b = np.full_like(sc["flags"], 5.0), np.full_like(sc["flags"], 5.0)
+    from oracle.oracle import OracleError
+    from oracle.ref import RefError
+    assert not np.isin(sc["flags"], FA.PLAIN_WORDS).all()
+    with pytest.raises(OracleError):            # words other than the two plain ones: the CPU function refuses
+        oracle.flagsToOccupancy(sc["flags"], occ_a)
+    with pytest.raises(RefError):
+        ref.flagsToOccupancy(sc["flags"], occ_b)
+    if kind == "alphabet":
+        so = scenes.alphabet_scene(dims, seed, B=FA.B, border=border, fluid_border=True, words=FA.PLAIN_WORDS)
+        oracle.flagsToOccupancy(so["flags"], occ_a)
+        ref.flagsToOccupancy(so["flags"], occ_b)
+        assert np.array_equal(occ_a, occ_b) and set(np.unique(occ_a)) <= {0.0, 1.0}
+        assert np.array_equal(occ_a, FA.occupancy_np(so["flags"]))       # where both builds are defined they agree
+
+
+@pytest.mark.parametrize("kind,dims,border", FA.CASES, ids=FA.CASE_IDS)
+def test_flag_alphabet_jacobi_and_pressure_mean_match_reference(oracle, ref, kind, dims, border):
+    import subprocess
+    from oracle import ref as refmod
+    if not refmod.jacobi_available():
+        if not os.path.isdir("/root/reference/torch/tfluids"):
+            pytest.skip("oracle/_ref/libtfluids_ref_jacobi.so not built and /root/reference absent")
+        subprocess.check_call(["make", "-s", "-C", os.path.join(os.path.dirname(HERE), "oracle"), "ref_jacobi"])
+    sc = FA.scene(kind, dims, border)
+    f, U = sc["flags"], sc["U"].copy()
+    oracle.setWallBcsForward(U, f)
+    div = np.zeros_like(sc["p"])
+    oracle.velocityDivergenceForward(U, f, div)
+    for iters in (1, 2, 7):
+        pa, pb = np.full_like(div, 3.0), np.full_like(div, -1.0)
+        ra = oracle.solveLinearSystemJacobi(pa, f, div, sc["is3d"], 0.0, iters)
+        rb = ref.solveLinearSystemJacobi(pb, f, div, sc["is3d"], 0.0, iters)
+        assert np.array_equal(pa, pb), iters
+        assert abs(ra - rb) <= 1e-5 * max(1.0, abs(rb)), (ra, rb)
+    p0 = (np.random.RandomState(3).randn(*div.shape) * 3 + 5).astype(np.float32)
+    a, b = p0.copy(), p0.copy()
+    oracle.normalizePressureMean(a, f, sc["is3d"])
+    ref.normalizePressureMean(b, f, sc["is3d"])
+    assert np.abs(a - b).max() < 1e-5 * np.abs(p0).max()          # (the bound of the test above: unordered float atomics)
+    nf = (f.astype(np.int64) & 1) == 0
+    assert np.array_equal(a[nf], p0[nf]) and np.array_equal(b[nf], p0[nf])
+
+
+PCG_CASES = [((1, 13, 21), False), ((5, 9, 21), False), ((1, 13, 21), True), ((5, 9, 21), True), ((4, 6, 68), True)]
+
+
+@pytest.mark.parametrize("dims,border", PCG_CASES)
+def test_flag_alphabet_pcg_matches_reference(oracle, ref_pcg, dims, border):
+    """all three preconditioners on an alphabet scene without fluid on the border: restatement == the reference's host
+    function, bit for bit, converged and cut off; the scene is well posed (every multi-cell fluid component touches a cell
+    that is neither fluid nor obstacle), which the test checks and does not assume"""
+    sc = FA.pcg_scene(dims, 77 + dims[2], border=border)
+    f = sc["flags"]
+    bad, multi, single = FA.singular_components(oracle, f, sc["is3d"])
+    assert multi >= 2 and not any(bad), (multi, bad)
+    U = sc["U"].copy()
+    oracle.setWallBcsForward(U, f)
+    div = np.zeros_like(sc["p"])
+    oracle.velocityDivergenceForward(U, f, div)
+    for pc in ("none", "ilu0", "ic0"):
+        for tol, max_iter in ((1e-5, 1000), (1e-12, 1), (1e-12, 6)):
+            pa = np.random.RandomState(1).rand(*div.shape).astype(np.float32)
+            pb = pa.copy()
+            ra = oracle.solveLinearSystemPCG(pa, f, div, sc["is3d"], tol, max_iter, pc)
+            rb = ref_pcg.solveLinearSystemPCG(pb, f, div, sc["is3d"], tol, max_iter, pc)
+            assert np.array_equal(pa, pb), (pc, tol, max_iter, np.abs(pa - pb).max())
+            assert np.all(pa[single] == 0.0)          # a one-cell component is skipped
+            assert ra == rb and (max_iter < 1000 or ra < 2 * tol), (pc, tol, max_iter, ra, rb)
+    # fluid on the border: both refuse (generic/tfluids.cu:1082-1090)
+    from oracle.oracle import OracleError
+    from oracle.ref import RefError
+    fb = scenes.alphabet_scene(dims, 77 + dims[2], B=FA.B, border=True, fluid_border=True)["flags"]
+    with pytest.raises(OracleError):
+        oracle.solveLinearSystemPCG(np.zeros_like(div), fb, div, sc["is3d"], 1e-5, 100, "none")
+    with pytest.raises(RefError):
+        ref_pcg.solveLinearSystemPCG(np.zeros_like(div), fb, div, sc["is3d"], 1e-5, 100, "none")
+
+
+@pytest.mark.parametrize("dims", [FA.COVER3, (1, 66, 130), (5, 9, 21), (1, 13, 21)])
+def test_neighbourhood_scene_catches_a_dropped_stick_test(oracle, dims):
+    """the power of the scene: the setWallBcs decision restated in numpy (FA.wall_mask_np) equals the oracle bit for bit on
+    the neighbourhood scene; with ONE term dropped (the stick test of the y axis) it does not. A scene on which the defect
+    passed would check nothing. (On make_scene's fields -- stick on whole spheres -- the same defect also shows; on a
+    scene without stick cells it cannot, which the last lines state.)"""
+    sc = FA.scene("neighbourhood", dims)
+    want = sc["U"].copy()
+    oracle.setWallBcsForward(want, sc["flags"])
+    good = FA.set_wall_bcs_np(sc["U"], sc["flags"], sc["is3d"])
+    assert np.array_equal(good, want)
+    broken = FA.set_wall_bcs_np(sc["U"], sc["flags"], sc["is3d"], defect="stick-y")
+    assert int((broken != want).sum()) > 0
+    plain = scenes.make_scene(dims, seed=1)
+    assert np.array_equal(FA.set_wall_bcs_np(plain["U"], plain["flags"], plain["is3d"], defect="stick-y"),
+                          FA.set_wall_bcs_np(plain["U"], plain["flags"], plain["is3d"]))
