@@ -13,6 +13,7 @@ KERNEL_SOURCE = {
     "k_curl": "vorticity.hip", "k_confine": "vorticity.hip", "k_vort_fused": "vorticity.hip", "k_stream_copy": "stencil.hip",
     "k_add_buoyancy": "stencil.hip", "k_add_gravity": "stencil.hip",
     "k_divnorm_planes": "divnorm.hip", "k_divnorm_finish": "divnorm.hip",
+    "k_criterion_weight": "criterion.hip", "k_criterion_planes": "criterion.hip", "k_criterion_finish": "criterion.hip",
     "k_bcs_div_stats": "model.hip", "k_reduce_stats": "model.hip", "k_project": "model.hip", "k_net_input": "model.hip",
     "k_apply_bcs_indexed": "model.hip", "k_bc_scan": "model.hip",
 }

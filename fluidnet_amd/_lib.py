@@ -102,6 +102,10 @@ SIGNATURES = {
     "tfl_velocityDivergenceForward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int]),
     "tfl_divergence_norm_workspace_floats": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32]),
     "tfl_velocityDivergenceNorm": (_c.c_int, [_c.c_void_p, _T, _T, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int64]),
+    "tfl_criterion_weight": (_c.c_int, [_c.c_void_p, _T, _c.c_double, _c.c_double, _c.c_int, _T]),
+    "tfl_fluid_criterion_workspace_floats": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32]),
+    "tfl_fluidCriterion": (_c.c_int, [_c.c_void_p, _T, _T, _T, _T, _T, _T, _c.c_double, _c.c_double, _c.c_double, _c.c_int, _c.c_int,
+                                      _c.c_void_p, _T, _T, _c.c_void_p, _c.c_int64]),
     "tfl_velocityUpdateForward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int]),
     "tfl_vorticityConfinement": (_c.c_int, [_c.c_void_p, _T, _T, _c.c_float, _T, _T, _T, _T,
                                             _c.c_int]),

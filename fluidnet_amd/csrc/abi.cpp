@@ -526,6 +526,81 @@ int tfl_velocityDivergenceNorm(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor
   return check_launch(c, "velocityDivergenceNorm");
 }
 
+int tfl_criterion_weight(tfl_ctx* c, const tfl_tensor* flags, double borderWidth, double borderWeight, int is3D,
+                         const tfl_tensor* weight) {
+  TRY(check_flags(c, "criterion_weight", flags));
+  TRY(check_scalar(c, "criterion_weight", "weight", weight, flags));
+  if (!(borderWidth > 1.0) || floor(borderWidth) != borderWidth)
+    return fail(c, TFL_EINVAL, "criterion_weight: borderWidth must a positive integer > 1");      // fluid_criterion.lua:46
+  if (borderWidth > 1024.0) return fail(c, TFL_EINVAL, "criterion_weight: borderWidth above 1024 is not supported");
+  if (!(borderWeight > 1.0)) return fail(c, TFL_EINVAL, "criterion_weight: borderWeight must be > 1");      // :63
+  if (!is3D && flags->Z != 1) return fail(c, TFL_EINVAL, "criterion_weight: 2D domain but zdepth > 1");
+  if (weight->data == flags->data) return fail(c, TFL_EINVAL, "criterion_weight: weight must not alias flags");
+  tfl::criterion_weight(c->stream, flags->B, flags->Z, flags->Y, flags->X, (int)borderWidth, (float)borderWidth,
+                        (float)(-1.0 / (borderWidth - 1.0)), (float)(borderWeight - 1.0), flags->data, weight->data);
+  return check_launch(c, "criterion_weight");
+}
+
+int64_t tfl_fluid_criterion_workspace_floats(int32_t B, int32_t Z, int32_t Y, int32_t X) {
+  (void)Y; (void)X;
+  if (B < 1 || Z < 1) return 0;
+  return 6ll * B * Z;        // three doubles per (batch item, z-plane)
+}
+
+int tfl_fluidCriterion(tfl_ctx* c, const tfl_tensor* pPred, const tfl_tensor* UPred, const tfl_tensor* pTarget,
+                       const tfl_tensor* UTarget, const tfl_tensor* flags, const tfl_tensor* weight, double pLambda,
+                       double uLambda, double divLambda, int sizeAverage, int is3D, double* loss, const tfl_tensor* gradP,
+                       const tfl_tensor* gradU, float* workspace, int64_t workspace_floats) {
+  const char* op = "fluidCriterion";
+  TRY(check_flags(c, op, flags));
+  TRY(check_scalar(c, op, "pPred", pPred, flags));
+  TRY(check_scalar(c, op, "pTarget", pTarget, flags));
+  TRY(check_vel(c, op, "UPred", UPred, flags, is3D));
+  TRY(check_vel(c, op, "UTarget", UTarget, flags, is3D));
+  if (weight) TRY(check_scalar(c, op, "weight", weight, flags));
+  if ((gradP != nullptr) != (gradU != nullptr)) return fail(c, TFL_EINVAL, "%s: gradP and gradU are given both or neither", op);
+  const size_t cells = (size_t)flags->B * flags->Z * flags->Y * flags->X;
+  if (gradP) {
+    TRY(check_scalar(c, op, "gradP", gradP, flags));
+    TRY(check_vel(c, op, "gradU", gradU, flags, is3D));
+    // the kernel reads neighbours of what it writes: a gradient must not overlap any input, nor the other gradient
+    auto overlap = [cells](const tfl_tensor* a, const tfl_tensor* b) {
+      if (!a || !b) return false;
+      const float *a0 = a->data, *a1 = a0 + cells * a->C, *b0 = b->data, *b1 = b0 + cells * b->C;
+      return a0 < b1 && b0 < a1;
+    };
+    const tfl_tensor* ins[6] = {pPred, UPred, pTarget, UTarget, flags, weight};
+    static const char* names[6] = {"pPred", "UPred", "pTarget", "UTarget", "flags", "weight"};
+    for (int i = 0; i < 6; i++) {
+      if (overlap(gradP, ins[i])) return fail(c, TFL_EINVAL, "%s: gradP must not alias %s", op, names[i]);
+      if (overlap(gradU, ins[i])) return fail(c, TFL_EINVAL, "%s: gradU must not alias %s", op, names[i]);
+    }
+    if (overlap(gradP, gradU)) return fail(c, TFL_EINVAL, "%s: gradP must not alias gradU", op);
+  }
+  if (!loss || ((uintptr_t)loss & 7) != 0) return fail(c, TFL_EINVAL, "%s: loss is null or not 8-byte aligned", op);
+  if (!workspace || ((uintptr_t)workspace & 7) != 0 ||
+      workspace_floats < tfl_fluid_criterion_workspace_floats(flags->B, flags->Z, flags->Y, flags->X))
+    return fail(c, TFL_EINVAL, "%s: workspace too small or not 8-byte aligned (tfl_fluid_criterion_workspace_floats)", op);
+  const double n_p = (double)cells, n_u = (double)cells * UPred->C;
+  tfl::CriterionArgs a{};
+  a.p = pPred->data; a.pt = pTarget->data; a.U = UPred->data; a.Ut = UTarget->data; a.flags = flags->data;
+  a.w = weight ? weight->data : nullptr;
+  a.gP = gradP ? gradP->data : nullptr; a.gU = gradU ? gradU->data : nullptr;
+  a.sums = reinterpret_cast<double*>(workspace);
+  a.BZ = (long long)flags->B * flags->Z;
+  a.normP = sizeAverage ? (float)(2.0 / n_p) : 2.0f;
+  a.normU = sizeAverage ? (float)(2.0 / n_u) : 2.0f;
+  a.lamP = (float)pLambda; a.lamU = (float)uLambda; a.lamD = (float)divLambda;
+  a.pOn = pLambda > 0.0; a.uOn = uLambda > 0.0; a.dOn = divLambda > 0.0;
+  tfl::CriterionFinish f{};
+  f.lambda[0] = pLambda; f.lambda[1] = uLambda; f.lambda[2] = divLambda;
+  f.n[0] = sizeAverage ? n_p : 1.0; f.n[1] = sizeAverage ? n_u : 1.0; f.n[2] = sizeAverage ? n_p : 1.0;
+  f.on[0] = a.pOn; f.on[1] = a.uOn; f.on[2] = a.dOn;
+  tfl::criterion_planes(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, a);
+  tfl::criterion_finish(c->stream, a.BZ, a.sums, f, loss);
+  return check_launch(c, op);
+}
+
 int tfl_velocityUpdateForward(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* p,
                               int is3D) {
   TRY(check_flags(c, "velocityUpdateForward", flags));

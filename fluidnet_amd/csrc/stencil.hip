@@ -390,18 +390,7 @@ __global__ __launch_bounds__(256) void k_signed_distance(int rad, int Z, int Y, 
   const int b = blockIdx.z / Z, z = blockIdx.z - b * Z;
   if (x >= X || y >= Y) return;
   const long long N = (long long)Z * Y * X;
-  const float* f = flags + b * N;
-  const long long o = (long long)z * Y * X + (long long)y * X + x;
-  if ((int)f[o] & kObstacle) { dst[b * N + o] = 0.0f; return; }
-  float dist_sq = (float)(rad * rad);
-  for (int zs = max(0, z - rad); zs <= min(Z - 1, z + rad); zs++)
-    for (int ys = max(0, y - rad); ys <= min(Y - 1, y + rad); ys++)
-      for (int xs = max(0, x - rad); xs <= min(X - 1, x + rad); xs++)
-        if ((int)f[(long long)zs * Y * X + (long long)ys * X + xs] & kObstacle) {
-          const float cur = (float)((z - zs) * (z - zs) + (y - ys) * (y - ys) + (x - xs) * (x - xs));
-          if (dist_sq > cur) dist_sq = cur;
-        }
-  dst[b * N + o] = sqrtf(dist_sq);
+  dst[b * N + (long long)z * Y * X + (long long)y * X + x] = signed_distance_at(rad, Z, Y, X, flags + b * N, x, y, z);
 }
 
 void rectangular_blur(hipStream_t st, bool is3d, int B, int C, int Z, int Y, int X, int rad, const float* src, float* dst,

@@ -193,6 +193,23 @@ __device__ __forceinline__ bool fluid_at(const Dom& d, const float* __restrict__
   return (flag_at(d, f, i, j, k) & kFluid) != 0;
 }
 
+// signedDistanceField of one cell (generic/tfluids.cc:735-821): the distance to the nearest obstacle cell within the search
+// cube of half-width rad, rad where there is none, 0 on an obstacle. f: one batch item's flags. Shared by k_signed_distance
+// (stencil.hip) and the criterion's border weight (criterion.hip), so the two write the same bits.
+__device__ __forceinline__ float signed_distance_at(int rad, int Z, int Y, int X, const float* __restrict__ f, int x, int y, int z) {
+  const long long o = (long long)z * Y * X + (long long)y * X + x;
+  if ((int)f[o] & kObstacle) return 0.0f;
+  float dist_sq = (float)(rad * rad);
+  for (int zs = max(0, z - rad); zs <= min(Z - 1, z + rad); zs++)
+    for (int ys = max(0, y - rad); ys <= min(Y - 1, y + rad); ys++)
+      for (int xs = max(0, x - rad); xs <= min(X - 1, x + rad); xs++)
+        if ((int)f[(long long)zs * Y * X + (long long)ys * X + xs] & kObstacle) {
+          const float cur = (float)((z - zs) * (z - zs) + (y - ys) * (y - ys) + (x - xs) * (x - xs));
+          if (dist_sq > cur) dist_sq = cur;
+        }
+  return sqrtf(dist_sq);
+}
+
 __device__ __forceinline__ int iclampi(int v, int lo, int hi) { return max(min(v, hi), lo); }
 // std::min<real>(hi, std::max<real>(lo, v)), third_party/tfluids.cc:246-248
 __device__ __forceinline__ float fclampf(float v, float lo, float hi) {

@@ -179,6 +179,23 @@ void divergence_norm_planes(hipStream_t st, const Scope& sc, bool is3d, int B, i
                             double* sums, int zstride, int zoff);
 void divergence_norm_finish(hipStream_t st, int B, int nz, const double* sums, double* norm);
 
+// criterion.hip: nn.FluidCriterion (lib/modules/fluid_criterion.lua) in two launches, plus its border weight.
+// What k_criterion_planes is handed by value. w == nullptr: unweighted; gP == gU == nullptr: no gradients. norm* = 2 / n of the
+// term's tensor (2 without sizeAverage), lam* = (float)lambda, *On = lambda > 0. sums: [3][BZ] doubles (p, U, div plane sums).
+struct CriterionArgs {
+  const float *p, *pt, *U, *Ut, *flags, *w;
+  float *gP, *gU;
+  double* sums;
+  long long BZ;
+  float normP, normU, lamP, lamU, lamD;
+  int pOn, uOn, dOn;
+};
+struct CriterionFinish { double lambda[3], n[3]; int on[3]; };      // term t = on ? lambda * (S / n) : 0 (n = 1 without sizeAverage)
+// w = ((clamp(sdf(flags, rad), 1, bw) - 1) * m + 1) * s + 1, one fp32 rounding per operation (fluid_criterion.lua:149-157)
+void criterion_weight(hipStream_t st, int B, int Z, int Y, int X, int rad, float bw, float m, float s, const float* flags, float* w);
+void criterion_planes(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const CriterionArgs& a);
+void criterion_finish(hipStream_t st, long long n, const double* sums, const CriterionFinish& f, double* loss);
+
 // vorticity.hip
 // stages: bit 0 = pass A (U -> curl, |curl|), bit 1 = pass B (curl, |curl|, flags, U -> U); a z-slab rank runs the two
 // passes under different z-windows (sc: the window and origin only -- the caller has mapped sc.stages into `stages`)

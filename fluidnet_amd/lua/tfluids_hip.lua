@@ -66,6 +66,13 @@ int tfl_velocityDivergenceForward(tfl_ctx* ctx, const tfl_tensor* U, const tfl_t
 int64_t tfl_divergence_norm_workspace_floats(int32_t B, int32_t Z, int32_t Y, int32_t X);
 int tfl_velocityDivergenceNorm(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags, int is3D,
                                double* norm, float* workspace, int64_t workspace_floats);
+int tfl_criterion_weight(tfl_ctx* ctx, const tfl_tensor* flags, double borderWidth, double borderWeight, int is3D,
+                         const tfl_tensor* weight);
+int64_t tfl_fluid_criterion_workspace_floats(int32_t B, int32_t Z, int32_t Y, int32_t X);
+int tfl_fluidCriterion(tfl_ctx* ctx, const tfl_tensor* pPred, const tfl_tensor* UPred, const tfl_tensor* pTarget,
+                       const tfl_tensor* UTarget, const tfl_tensor* flags, const tfl_tensor* weight, double pLambda,
+                       double uLambda, double divLambda, int sizeAverage, int is3D, double* loss, const tfl_tensor* gradP,
+                       const tfl_tensor* gradU, float* workspace, int64_t workspace_floats);
 int tfl_velocityUpdateForward(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
                               const tfl_tensor* p, int is3D);
 int tfl_vorticityConfinement(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
@@ -753,6 +760,25 @@ function M.velocityDivergenceNorm(U, flags)
   return out
 end
 
+--- The border weight of nn.FluidCriterion (lib/modules/fluid_criterion.lua:145-158) in one launch: a function of flags only.
+function M.criterionWeight(flags, borderWidth, borderWeight, out)
+  local is3D = flags:size(3) > 1
+  out = out or flags:clone()
+  check(lib.tfl_criterion_weight(ctx, T(flags), borderWidth, borderWeight, b2i(is3D), T(out)))
+  return out
+end
+
+--- nn.FluidCriterion's updateOutput and (with gradP / gradU, both or neither) updateGradInput in two launches: returns a
+--- torch.CudaDoubleTensor [4] = {pLoss, uLoss, divLoss, total} on the device (no host read). weight: M.criterionWeight(flags,
+--- ...) or nil (unweighted); a term whose lambda is <= 0 is 0 and adds nothing to the gradients.
+function M.FluidCriterion(pPred, UPred, pTarget, UTarget, flags, weight, pLambda, uLambda, divLambda, sizeAverage, gradP, gradU)
+  local is3D = UPred:size(2) == 3
+  local loss = torch.CudaDoubleTensor(4)
+  local ws, n = workspace(flags, lib.tfl_fluid_criterion_workspace_floats(flags:size(1), flags:size(3), flags:size(4), flags:size(5)))
+  check(lib.tfl_fluidCriterion(ctx, T(pPred), T(UPred), T(pTarget), T(UTarget), T(flags), weight and T(weight) or nil, pLambda, uLambda, divLambda, b2i(sizeAverage ~= false), b2i(is3D), ffi.cast('double*', torch.data(loss)), gradP and T(gradP) or nil, gradU and T(gradU) or nil, ws, n))
+  return loss
+end
+
 --- Arithmetic of the LDS-tiled 3-D advection kernels (include/tfluids_hip.h tfl_set_advect_mode): 'exact' (default; bit-equal
 --- to the reference CPU path) or 'fast' (the tolerance mode: rel-L2 ~2e-8 against the reference, bar 1e-5).
 function M.setAdvectMode(mode)
@@ -778,6 +804,8 @@ function M.install(tfluids, opts)
   for name, fn in pairs(ops) do mt.tfluids[name] = fn end
   rawset(tfluids, 'normalizePressureMean', M.normalizePressureMean)
   rawset(tfluids, 'velocityDivergenceNorm', M.velocityDivergenceNorm)
+  rawset(tfluids, 'criterionWeight', M.criterionWeight)
+  rawset(tfluids, 'fluidCriterion', M.FluidCriterion)
   if not opts.keepLuaSimulate then rawset(tfluids, 'simulate', M.simulate) end
   tfluids.withHIP = true
   return M

@@ -290,6 +290,35 @@ def simulate(conf, mconf, batch, model, outputDiv=False):
         _apply(U, None, None, clamp=(-1e6, 1e6))
 
 
+def calcPUTargets(conf, mconf, batch, model=None):
+    """tfluids.calcPUTargets, simulate.lua:332-372: the training targets (batch["pTarget"], batch["UTarget"], written in
+    place) by a Jacobi or PCG projection of batch["UDiv"] (which takes its wall BCs in place, as in the reference).
+    batch["div"] is created on the first call and kept between calls."""
+    source = mconf.get("trainTargetSource")
+    if source == "manta":
+        raise TfluidsError("target source is manta, this method should not be called!")
+    UDiv, flags = batch["UDiv"], batch["flags"]
+    pTarget, UTarget = batch["pTarget"], batch["UTarget"]
+    is3D = UDiv.size(1) == 3
+    tfluids.setWallBcsForward(UDiv, flags)
+    # the right-hand side of the linear system (divergence)
+    div = batch.get("div")
+    if div is None or div.shape != flags.shape or div.dtype != UDiv.dtype or div.device != UDiv.device:
+        div = torch.empty_like(flags)
+        batch["div"] = div
+    tfluids.velocityDivergenceForward(UDiv, flags, div)
+    if source == "pcg":
+        tfluids.solveLinearSystemPCG(pTarget, flags, div, is3D, 1e-4, mconf.get("maxIter") or 100, "ic0")
+    elif source == "jacobi":
+        tfluids.solveLinearSystemJacobi(pTarget, flags, div, is3D, 0, mconf.get("maxIter") or 50, residual=False)
+    else:
+        raise TfluidsError("mconf.trainTargetSource (%s) is not a valid option" % source)
+    # the velocity update with the pressure gradient
+    UTarget.copy_(UDiv)
+    tfluids.velocityUpdateForward(UTarget, flags, pTarget)
+    tfluids.setWallBcsForward(UTarget, flags)
+
+
 _dead_plans = []      # plans whose tensors have died, waiting for a safe moment
 _WALL_PLANS = os.environ.get("TFL_WALL_PLAN", "1") != "0"
 

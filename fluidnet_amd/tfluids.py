@@ -238,6 +238,48 @@ def velocityDivergenceNorm(U, flags, out=None):
     return out
 
 
+def criterionWeight(flags, borderWidth, borderWeight, out=None):
+    """The border weight of nn.FluidCriterion (lib/modules/fluid_criterion.lua:145-158) in one launch: signedDistanceField
+    (flags, borderWidth) clamped to [1, borderWidth], ramped to [1, 0] = [next to an obstacle, far] and rescaled to
+    [borderWeight, 1], each step rounded once in fp32 (include/tfluids_hip.h tfl_criterion_weight). A function of flags only."""
+    _check(flags.dim() == 5 and flags.size(1) == 1, "flags is not scalar")
+    _check(flags.is_contiguous(), "Input is not contiguous")
+    lib, ctx = _context(flags)
+    if out is None:
+        out = torch.empty_like(flags)
+    _check(out.shape == flags.shape and out.is_contiguous() and out.device == flags.device, "Size mismatch")
+    is3D = flags.size(2) > 1
+    _call(lib, ctx, lib.tfl_criterion_weight(ctx, _tt(flags), float(borderWidth), float(borderWeight), int(is3D), _tt(out)))
+    return out
+
+
+def fluidCriterion(pPred, UPred, pTarget, UTarget, flags, weight, pLambda, uLambda, divLambda, sizeAverage, loss,
+                   gradP=None, gradU=None):
+    """nn.FluidCriterion's updateOutput and (with gradP / gradU, both or neither) updateGradInput in two launches
+    (include/tfluids_hip.h tfl_fluidCriterion): loss (float64 DEVICE tensor [4]) = {pLoss, uLoss, divLoss, total}. weight:
+    criterionWeight(flags, ...) or None (unweighted). No host read: the call can be captured into a graph."""
+    bsz, d, h, w, is3D = _dims(UPred, flags)
+    lib, ctx = _context(UPred)
+    for name, t, like in (("flags", flags, flags), ("pPred", pPred, flags), ("pTarget", pTarget, flags), ("UTarget", UTarget, UPred),
+                          ("weight", weight, flags), ("gradP", gradP, flags), ("gradU", gradU, UPred)):
+        if t is None:
+            continue
+        _check(t.dim() == 5 and t.shape == like.shape, name + ": Size mismatch")
+        _check(t.is_contiguous(), "Input is not contiguous")
+        _check(t.is_cuda and t.device == UPred.device, name + " must be on UPred's device (there is no CPU fallback)")
+    _check((gradP is None) == (gradU is None), "gradP and gradU are given both or neither")
+    _check(loss.dtype == torch.float64 and loss.dim() == 1 and loss.size(0) == 4 and loss.is_contiguous() and
+           loss.device == UPred.device, "loss must be a contiguous float64 tensor [4] on UPred's device")
+    n = int(lib.tfl_fluid_criterion_workspace_floats(bsz, d, h, w))
+    ws, = getTempStorage(UPred, [(n,)])
+    opt = lambda t: _tt(t) if t is not None else None      # noqa: E731
+    _call(lib, ctx, lib.tfl_fluidCriterion(ctx, _tt(pPred), _tt(UPred), _tt(pTarget), _tt(UTarget), _tt(flags), opt(weight),
+                                           float(pLambda), float(uLambda), float(divLambda), int(bool(sizeAverage)), int(is3D),
+                                           ctypes.c_void_p(loss.data_ptr()), opt(gradP), opt(gradU),
+                                           ctypes.c_void_p(ws.data_ptr()), n))
+    return loss
+
+
 def velocityUpdateForward(U, flags, p):
     """init.lua:322-347 (in place on U)."""
     _, _, _, _, is3D = _dims(U, flags)

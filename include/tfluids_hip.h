@@ -142,6 +142,39 @@ int64_t tfl_divergence_norm_workspace_floats(int32_t B, int32_t Z, int32_t Y, in
 int tfl_velocityDivergenceNorm(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags, int is3D,
                                double* norm, float* workspace, int64_t workspace_floats);
 
+/* ---- nn.FluidCriterion (lib/modules/fluid_criterion.lua, lib/modules/weighted_flat_mse_criterion.lua) ------------------------
+ * tfl_criterion_weight: the border weight of fluid_criterion.lua:145-158 in one launch. Per cell it starts from the bits
+ * tfl_signedDistanceField(flags, borderWidth) writes and applies, in fp32 with one rounding each and no contraction,
+ *   c = min(max(sdf, 1), bw); c = c + (-1); c = c * (float)(-1.0 / (bw - 1)); c = c + 1; c = c * (float)(borderWeight - 1); w = c + 1.
+ * A function of flags only: a scene computes it once. borderWidth must be an integer > 1 and borderWeight > 1 (:46, :63);
+ * a borderWidth above 1024 is refused too (the search visits (2 borderWidth + 1)^3 cells per cell).
+ *
+ * tfl_fluidCriterion: loss[0..3] (DEVICE memory, 4 doubles) = {pLoss, uLoss, divLoss, (pLoss + uLoss) + divLoss} with
+ *   term = lambda * (S / n),  S = the fp64 sum of z * z over the term's tensor,  n = its element count (1 when !sizeAverage),
+ *   z = x - t (weight == NULL) or z = a - b, a = w * x, b = w * t in fp32 (the cell's weight for every channel of U); for the
+ *   divergence term z = dv resp. w * dv, dv being the bits tfl_velocityDivergenceForward writes for the cell.
+ * A term whose lambda is <= 0 is 0 and adds nothing to the gradients (fluid_criterion.lua:162-181, 199-235). The sums follow
+ * tfl_velocityDivergenceNorm's discipline: one sum per (batch item, z-plane) in a fixed order, the planes in ascending (b, z),
+ * no atomics -- the same bits every call, and batch item b's plane sums do not depend on B.
+ * With gradP / gradU (both or neither) the same launch writes the gradients to pPred and UPred, in fp32:
+ *   norm = sizeAverage ? (float)(2.0 / n) : 2.0f;  g = norm * z;  weighted: g = g * w;  g = g * (float)lambda;
+ *   gradP = g_p;  gradU_c = (0.0f + g_u,c) + d_c,  d_c = what tfl_velocityDivergenceBackward gathers from gradOutput = g_div
+ * (g_div is recomputed at the three -c neighbours from UPred, flags and weight: no divergence or gradOutput field is stored).
+ * `workspace`: device memory, 8-byte aligned, tfl_fluid_criterion_workspace_floats(B, Z, Y, X) floats. Two launches on the
+ * context's stream; no host read, no synchronisation, no allocation: the call can be captured into a HIP graph. Refused with
+ * TFL_EINVAL before anything is written: shape mismatches (fluid_criterion.lua:86-99, 117-129), a gradient that overlaps an
+ * input or the other gradient. Covers the whole array (tfl_set_z_window / tfl_set_z_origin are not read); there is no z-slab
+ * form: it would need one 3-double all-reduce and is out of scope.
+ * The MSE arithmetic of the reference lives in Torch7's nn / THNN, outside the reference tree: the element-wise order above is
+ * this library's, chosen to follow the Lua call order; the tfluids pieces (SDF, divergence forward / backward) are the reference's. */
+int tfl_criterion_weight(tfl_ctx* ctx, const tfl_tensor* flags, double borderWidth, double borderWeight, int is3D,
+                         const tfl_tensor* weight);
+int64_t tfl_fluid_criterion_workspace_floats(int32_t B, int32_t Z, int32_t Y, int32_t X);
+int tfl_fluidCriterion(tfl_ctx* ctx, const tfl_tensor* pPred, const tfl_tensor* UPred, const tfl_tensor* pTarget,
+                       const tfl_tensor* UTarget, const tfl_tensor* flags, const tfl_tensor* weight, double pLambda,
+                       double uLambda, double divLambda, int sizeAverage, int is3D, double* loss, const tfl_tensor* gradP,
+                       const tfl_tensor* gradU, float* workspace, int64_t workspace_floats);
+
 /* init.lua:346 -> third_party/tfluids.cc:1072-1156 | tfluids.cu:1111-1195 (in place on U). */
 int tfl_velocityUpdateForward(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
                               const tfl_tensor* p, int is3D);
