@@ -1,221 +1,20 @@
-// abi.cpp -- the C ABI of libtfluids_hip.so (include/tfluids_hip.h): argument validation that
-// mirrors torch/tfluids/init.lua's asserts, then kernel launches on the context's stream.
-// No torch / Lua / C++ types cross the boundary; errors come back as codes + tfl_last_error().
-#include "../../include/tfluids_hip.h"
-
-#include <hip/hip_runtime.h>
-
+// abi.cpp -- the fluid operators of the C ABI of libtfluids_hip.so (include/tfluids_hip.h): argument validation that
+// mirrors torch/tfluids/init.lua's asserts, then kernel launches on the context's stream. The operators a native step calls
+// come first in their tfl:: forms (tfl_ops.hpp), then every public tfl_* operator. The context is context.cpp's, the
+// projection ConvNet model_host.cpp's.
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 
-#include <vector>
-
-#include "tfl_device.hpp"
-#include "tfl_host.hpp"
+#include "tfl_abi.hpp"
 #include "tfl_advect.hpp"
-
-struct tfl_layer {
-  int cin = 0, cout = 0, k = 0;
-  int pool = 1;        // 2: 2x average pooling after the non-linearity (model_utils.lua:184-208)
-  int up = 1;          // 2: {Spatial,Volumetric}ConvolutionUpsample -- up^dim sub-position convolutions, pixel-shuffled
-  float* w = nullptr;  // device, [sub][tap][cin][cout]
-  float* b = nullptr;  // device, [sub][cout]
-  int stage = 0;       // 1-based stage of lib/model.lua's layer tables
-  int bank = 0;        // 0-based bank (0 outside [banksSplitStage, banksJoinStage))
-  // graph models only
-  int dil = 1;         // dilation (banksType 'dilate': 2^(bank - 1))
-  float* bn = nullptr; // device, the folded batch norm after this module: scale[cout] then shift[cout]
-};
-// The forward a model runs (tfl_model_finish dispatches on it), named after its kernel file; TFL_CONV_PATH at creation picks
-// it for the 3-D `default` topology (3->8 k3, 8->8 k3, 8->8 k3, 8->8 k1, 8->1 k1), and "direct" = generic for both defaults.
-enum class ConvPath {
-  conv_mfma16,   // 3-D default: split-operand fp16 MFMA (conv_mfma16.hip), TFL_CONV_PATH unset or "mfma16"
-  conv_valu,     // 3-D default: fp32 Winograd on the vector ALUs (conv_valu.hip), "winograd" and any unrecognised value
-  conv_mfma,     // 3-D default: fp32-operand MFMA (conv_mfma.hip), "mfma"
-  conv2d_mfma,   // 2-D default topology (3->16, 16->16 x3 k3, 16->1 k1): conv2d_mfma.hip
-  generic,       // everything else that is not a graph model: the shape-generic kernels (conv.hip), layer by layer
-  graph,         // tfl_model_create_graph: banks / batch norm / max pooling (graph_forward)
-};
-static bool default3(ConvPath p) { return p == ConvPath::conv_mfma16 || p == ConvPath::conv_valu || p == ConvPath::conv_mfma; }
-struct tfl_model {
-  bool is3d = false;
-  int max_c = 0;
-  bool multires = false;   // some layer pools / upsamples (the `tog` topologies)
-  int max_down = 1;        // coarsest activation resolution = grid / max_down
-  std::vector<tfl_layer> layers;
-  ConvPath path = ConvPath::generic;
-  // 3-D `default` topology: the weights of its three forms (pack_default3)
-  float* bfrag[3] = {nullptr, nullptr, nullptr};  // per-lane B fragments of the three k=3 layers
-  float* wino[3] = {nullptr, nullptr, nullptr};   // F(2,3)-in-x transformed weights of the same layers, [dz][dy][cin][4][8]
-  float* tail_w4 = nullptr;                       // [8][8] (out, in) of the 8->8 k1 layer
-  float* tail_w5 = nullptr;                       // [8] of the 8->1 k1 layer
-  float* tail_pack = nullptr;                     // conv_valu.hip: {bias3[8], w4[8][8], b4[8], w5[8], b5[1]} in one buffer
-  // conv_mfma16.hip
-  void* wfrag16[3] = {nullptr, nullptr, nullptr}; // A fragments of the three k=3 layers (conv3_m16_pack_weights)
-  float post16[3] = {0.0f, 0.0f, 0.0f};           // 2^-(11 + e) of each layer
-  float post16_tail = 0.0f;                       // the same for the tail's 8 -> 8 (k = 1) layer (conv3_m16_pack_tail)
-  unsigned long long* d_range_err = nullptr;      // blocks that clamped an activation at the fp16 range
-  unsigned long long* h_range = nullptr;          // pinned, device-mapped: the projection kernel copies a non-zero count here, so the
-  unsigned long long* d_range_host = nullptr;     // NEXT call sees it without a stream sync (d_range_host = its device address)
-  // 2-D `default` topology (conv2d_mfma.hip)
-  float* bfrag2[4] = {nullptr, nullptr, nullptr, nullptr};
-  double* d_stats = nullptr;  // [2 * kMaxBatch]: sum(u), sum(u^2) per sample
-  long long stat_pairs_per_plane = 0;   // partial pairs per z-plane the last tfl_model_begin wrote (model.hip model_pre's layout)
-  unsigned* d_ticket = nullptr;   // model.hip publish_and_maybe_reduce: blocks of the current k_bcs_div_stats launch that have published
-  // forward-graph switches (tfl_model_opts); `custom` = any of them differs from default_conf.lua -> generic kernels only
-  tfl_model_opts opts = {1, 0, 1, 1, TFL_NORM_UDIV, TFL_NORMFUNC_STD, TFL_NONLIN_RELU, 0};
-  bool custom = false;
-  int in_c = 3;               // net input channels
-  // graph models: banks / batch norm / max pooling (shape-generic kernels, un-sharded)
-  int banks = 1, bank_type = TFL_BANKS_MRES, aggregate = TFL_AGG_CONCAT, split = 0, join = 0, nstages = 0;
-  bool pool_max = false;
-  int bank_c = 0;             // channel planes of each bank's two scratch buffers
-  int bank_down = 1;          // bank 1's finest resolution inside [split, join) = grid / bank_down (bank i: / 2^(i-1) more, mres)
-  int split_c = 0;            // channels entering the split (the mres pyramid's planes)
-  int split_down = 1;         // resolution at the split = grid / split_down
-};
-
-#include "tfl_ctx.hpp"
 #include "tfl_ops.hpp"
-static const int kMaxBatch = 1024;
 
-// ---- per-kernel event profiler (TFL_TIMED in the launchers) ---------------------------------------
-namespace tfl {
-struct ProfRec { const char* name; hipEvent_t e0, e1; };
-struct Profiler { std::vector<ProfRec> recs; };
-static thread_local Profiler* g_prof = nullptr;
-
-KernelTimer::KernelTimer(const char* name, hipStream_t st, bool ext) : slot_(-1), st_(st), ext_(ext) {
-  if (!g_prof) return;
-  ProfRec r; r.name = name;
-  if (hipEventCreate(&r.e0) != hipSuccess) return;
-  if (hipEventCreate(&r.e1) != hipSuccess) { (void)hipEventDestroy(r.e0); return; }
-  if (!ext_) (void)hipEventRecord(r.e0, st);
-  g_prof->recs.push_back(r);
-  slot_ = (int)g_prof->recs.size() - 1;
-}
-KernelTimer::~KernelTimer() {
-  if (slot_ >= 0 && g_prof && !ext_) (void)hipEventRecord(g_prof->recs[slot_].e1, st_);
-}
-hipEvent_t KernelTimer::start() const { return (slot_ >= 0 && g_prof) ? g_prof->recs[slot_].e0 : nullptr; }
-hipEvent_t KernelTimer::stop() const { return (slot_ >= 0 && g_prof) ? g_prof->recs[slot_].e1 : nullptr; }
-bool model_is_graph(const tfl_model* m) { return m && m->path == ConvPath::graph; }
-int model_grid_factor(const tfl_model* m) { return m ? m->max_down : 1; }
-
-// The z-slab cone of a model: ONE backward walk over the layer table gives both the window of every launch and
-// the halo depth, so the two cannot disagree. Start: pPred on the owned planes widened by (1, 0) -- what the velocity update
-// reads. Per layer, from its output back to its input:
-//   2x pooling       pooled planes (lo, hi) at grid / 2d  <-  pre-pool planes (2 lo, 2 hi) at grid / d (owned ranges are
-//                    multiples of F, so a pooling window never straddles the owned boundary: outward alignment is exact)
-//   ConvolutionUpsample  fine planes (lo, hi) at grid / d  <-  coarse conv planes (ceil(lo / 2), ceil(hi / 2)) at grid / 2d
-//                    (fine plane 2 kc + c comes from coarse plane kc: the floor mapping)
-//   conv k           conv planes (lo, hi)  <-  input planes (lo + k/2, hi + k/2) at the same resolution
-// The stored halo must hold every plane any level reads: depth = max over the layers of d x (input extent).
-bool model_cone(const tfl_model* m, ModelCone* out, const char** why) {
-  auto no = [&](const char* w) { if (why) *why = w; return false; };
-  if (!m) return no("no model");
-  if (m->path == ConvPath::graph) return no("banked, batch-norm and max-pool models run un-sharded only (tfl_simulate_step)");
-  if (!m->is3d) return no("2-D grids have no z to cut (run replicas)");
-  const int n = (int)m->layers.size();
-  if (n > (int)(sizeof(out->layer) / sizeof(out->layer[0]))) return no("more than 32 layers");
-  ModelCone c{};
-  c.fused = default3(m->path);
-  c.windowed = !c.fused;
-  c.F = m->max_down;
-  c.nlayers = n;
-  c.reads_U = m->opts.in_UDiv != 0;
-  c.norm = !m->opts.normalize ? 2 : ((m->opts.norm_chan == TFL_NORM_UDIV && m->opts.norm_func == TFL_NORMFUNC_STD) ? 0 : 1);
-  int lo = 1, hi = 0, d = 1, depth = 1;
-  for (int l = n - 1; l >= 0; l--) {
-    const tfl_layer& L = m->layers[l];
-    LayerCone& w = c.layer[l];
-    w.pool_lo = w.pool_hi = 0;
-    if (L.pool > 1) { w.pool_lo = lo; w.pool_hi = hi; lo *= 2; hi *= 2; d /= 2; }
-    if (L.up > 1) { lo = (lo + 1) / 2; hi = (hi + 1) / 2; d *= 2; }
-    w.conv_lo = lo; w.conv_hi = hi; w.conv_d = d;
-    lo += L.k / 2; hi += L.k / 2;
-    w.in_lo = lo; w.in_hi = hi;
-    depth = std::max(depth, d * std::max(lo, hi));
-  }
-  c.in_lo = lo; c.in_hi = hi;
-  c.depth = depth;
-  *out = c;
-  return true;
-}
-
-void model_slab_stats(hipStream_t st, const tfl_model* m, int B, int Z, long long yx, int zlo, int zhi, int z_total,
-                      const float* pDiv, const float* U, const float* div, double* stats, double* count) {
-  const tfl_model_opts& o = m->opts;
-  const bool udiv = o.norm_chan == TFL_NORM_UDIV;
-  const float* field = o.norm_chan == TFL_NORM_PDIV ? pDiv : (o.norm_chan == TFL_NORM_DIV ? div : U);
-  const int mode = !o.normalize ? 2 : (o.norm_func == TFL_NORMFUNC_L2 ? 1 : 0);
-  model_field_stats_planes(st, B, udiv ? 3 : 1, Z, yx, zlo, zhi, field, mode, stats);
-  // as tfl_model_finish's un-cut forms: std over the whole grid's n values, l2 and none through n = 2
-  *count = mode == 0 ? (double)z_total * (double)yx * (udiv ? 3.0 : 1.0) : 2.0;
-}
-}  // namespace tfl
+using tfl::fail; using tfl::check_launch; using tfl::same_dims; using tfl::check_flags; using tfl::check_vel; using tfl::check_scalar;
 
 namespace {
-
-int fail(tfl_ctx* ctx, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  if (ctx) ctx->err = buf;
-  return code;
-}
-
-#define HIP_TRY(ctx, call)                                                                     \
-  do {                                                                                         \
-    hipError_t e_ = (call);                                                                    \
-    if (e_ != hipSuccess) return fail(ctx, TFL_EHIP, "%s: %s", #call, hipGetErrorString(e_)); \
-  } while (0)
-
-int check_launch(tfl_ctx* ctx, const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ctx, TFL_EHIP, "%s: %s", what, hipGetErrorString(e));
-  return TFL_OK;
-}
-
-bool same_dims(const tfl_tensor* a, const tfl_tensor* b) {
-  return a->B == b->B && a->Z == b->Z && a->Y == b->Y && a->X == b->X;
-}
-
-// init.lua's shape asserts (e.g. :99-120): flags scalar, U has 2 (2-D, Z==1) or 3 channels, all same B/Z/Y/X.
-int check_flags(tfl_ctx* ctx, const char* op, const tfl_tensor* flags) {
-  if (!ctx) return TFL_EINVAL;
-  if (!flags || !flags->data) return fail(ctx, TFL_EINVAL, "%s: flags is null", op);
-  if (flags->C != 1) return fail(ctx, TFL_EINVAL, "%s: flags is not scalar", op);
-  if (flags->B < 1 || flags->Z < 1 || flags->Y < 1 || flags->X < 1) return fail(ctx, TFL_EINVAL, "%s: empty grid", op);
-  if ((long long)flags->Z * flags->Y * flags->X * 3 >= (1ll << 31))
-    return fail(ctx, TFL_EINVAL, "%s: grid too large for 32-bit cell offsets", op);
-  if ((long long)flags->Z * flags->B > 65535) return fail(ctx, TFL_EINVAL, "%s: B*Z exceeds the launch grid limit", op);
-  return TFL_OK;
-}
-int check_vel(tfl_ctx* ctx, const char* op, const char* name, const tfl_tensor* U, const tfl_tensor* flags, int is3D) {
-  if (!U || !U->data) return fail(ctx, TFL_EINVAL, "%s: %s is null", op, name);
-  if (!same_dims(U, flags)) return fail(ctx, TFL_EINVAL, "%s: %s size mismatch", op, name);
-  if (is3D) {
-    if (U->C != 3) return fail(ctx, TFL_EINVAL, "%s: 3D velocity field must have 3 channels", op);
-  } else {
-    if (flags->Z != 1) return fail(ctx, TFL_EINVAL, "%s: 2D velocity field but zdepth > 1", op);
-    if (U->C != 2) return fail(ctx, TFL_EINVAL, "%s: 2D velocity field must have only 2 channels", op);
-  }
-  return TFL_OK;
-}
-int check_scalar(tfl_ctx* ctx, const char* op, const char* name, const tfl_tensor* s, const tfl_tensor* flags) {
-  if (!s || !s->data) return fail(ctx, TFL_EINVAL, "%s: %s is null", op, name);
-  if (s->C != 1 || !same_dims(s, flags)) return fail(ctx, TFL_EINVAL, "%s: %s size mismatch", op, name);
-  return TFL_OK;
-}
-#define TRY(x) do { int rc_ = (x); if (rc_ != TFL_OK) return rc_; } while (0)
 
 // generic/advect_type.cc:18-37
 int parse_method(const char* m) {
@@ -227,173 +26,6 @@ int parse_method(const char* m) {
 
 }  // namespace
 
-namespace tfl {
-// What the tfl_set_* calls left on the context, as the one value a public operator that honours them forms at its entry and
-// passes down (the operators that ignore them never call this). A null context gives the empty scope: the operator's own
-// checks refuse it.
-Scope scope_of(const tfl_ctx* c) {
-  Scope sc;
-  if (c) { sc.win = c->zwin; sc.origin = c->zorigin; sc.stages = c->stages; sc.advect_fast = c->advect_fast; }
-  return sc;
-}
-static int dx_cells(const Scope& sc, const tfl_tensor* f) {
-  return sc.dx_cells > 0 ? sc.dx_cells : std::max(std::max(f->X, f->Y), f->Z);
-}
-float get_dx(const tfl_ctx* c, const Scope& sc, const tfl_tensor* f) {  // grid.cc:37-40
-  if (sc.dx_cells <= 0 && c && c->dx_override > 0.0f) return c->dx_override;
-  return 1.0f / (float)dx_cells(sc, f);
-}
-double get_dx_double(const tfl_ctx* c, const Scope& sc, const tfl_tensor* f) {
-  if (sc.dx_cells <= 0 && c && c->dx_override > 0.0f) return (double)c->dx_override;
-  return 1.0 / (double)dx_cells(sc, f);
-}
-}  // namespace tfl
-
-// (library-internal, C++ linkage: the device word of a model's fp16 range counter, for the z-slab step's collective gate -- simulate.cpp)
-namespace tfl { const unsigned long long* model_range_counter(const tfl_model* m) { return m ? m->d_range_err : nullptr; } }
-
-extern "C" {
-
-int tfl_abi_version(void) { return TFL_ABI_VERSION; }
-
-tfl_ctx* tfl_create(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return nullptr;
-  if (hipSetDevice(device) != hipSuccess) return nullptr;
-  tfl_ctx* c = new tfl_ctx();
-  c->device = device;
-  if (hipMalloc((void**)&c->d_trace_err, sizeof(unsigned long long)) != hipSuccess ||
-      hipMemset(c->d_trace_err, 0, sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc((void**)&c->d_resid, sizeof(double) * kMaxBatch) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_resid, sizeof(double) * kMaxBatch, hipHostMallocDefault) != hipSuccess ||
-      hipMalloc((void**)&c->d_reach, sizeof(float)) != hipSuccess ||
-      hipMemset(c->d_reach, 0, sizeof(float)) != hipSuccess ||      // (a sticky maximum since round 6: nothing resets it per step)
-      hipHostMalloc((void**)&c->h_reach, 2 * sizeof(float), hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&c->d_reach_host, c->h_reach, 0) != hipSuccess ||
-      hipMalloc((void**)&c->d_reach_tick, sizeof(unsigned)) != hipSuccess ||
-      hipMemset(c->d_reach_tick, 0, sizeof(unsigned)) != hipSuccess) {
-    tfl_destroy(c);
-    return nullptr;
-  }
-  c->h_reach[0] = 0.0f; reinterpret_cast<unsigned*>(c->h_reach)[1] = 0u;
-  if (const char* m = getenv("TFL_ADVECT_MODE")) c->advect_fast = (strcmp(m, "fast") == 0 || strcmp(m, "1") == 0) ? 1 : 0;
-  return c;
-}
-
-int tfl_set_advect_mode(tfl_ctx* c, int mode) {
-  if (!c) return TFL_EINVAL;
-  if (mode != TFL_ADVECT_EXACT && mode != TFL_ADVECT_FAST) return fail(c, TFL_EINVAL, "set_advect_mode: unknown mode %d", mode);
-  c->advect_fast = mode == TFL_ADVECT_FAST ? 1 : 0;
-  return TFL_OK;
-}
-int tfl_get_advect_mode(const tfl_ctx* c) { return c ? (c->advect_fast ? TFL_ADVECT_FAST : TFL_ADVECT_EXACT) : TFL_EINVAL; }
-
-void tfl_destroy(tfl_ctx* c) {
-  if (!c) return;
-  { std::lock_guard<std::mutex> lock(c->wall_mu); for (tfl_wall_plan* p : c->wall_plans) p->owner = nullptr; c->wall_plans.clear(); }      // the host still owns (and frees) them
-  if (c->d_reach) (void)hipFree(c->d_reach);
-  if (c->h_reach) (void)hipHostFree(c->h_reach);
-  if (c->d_reach_tick) (void)hipFree(c->d_reach_tick);
-  if (c->h_reach_flags) (void)hipHostFree(c->h_reach_flags);
-  if (c->d_trace_err) (void)hipFree(c->d_trace_err);
-  if (c->d_resid) (void)hipFree(c->d_resid);
-  if (c->h_resid) (void)hipHostFree(c->h_resid);
-  delete c;
-}
-
-int tfl_set_stream(tfl_ctx* c, void* s) {
-  if (!c) return TFL_EINVAL;
-  c->stream = (hipStream_t)s;
-  return TFL_OK;
-}
-
-const char* tfl_last_error(const tfl_ctx* c) { return c ? c->err.c_str() : "null context"; }
-
-int tfl_set_dx_override(tfl_ctx* c, float dx) {
-  if (!c) return TFL_EINVAL;
-  c->dx_override = dx > 0.0f ? dx : 0.0f;
-  return TFL_OK;
-}
-
-int tfl_set_z_window(tfl_ctx* c, int a0, int a1, int b0, int b1) {
-  if (!c) return TFL_EINVAL;
-  if (a0 < 0 || a1 < a0 || b0 < 0 || b1 < b0 || (a1 > a0 && b1 > b0 && b0 < a1))
-    return fail(c, TFL_EINVAL, "set_z_window: [%d,%d) [%d,%d) is not an ordered pair of plane runs", a0, a1, b0, b1);
-  c->zwin = tfl::ZWin{a0, a1, b0, b1};
-  return TFL_OK;
-}
-
-int tfl_set_z_origin(tfl_ctx* c, int z_first, int z_total) {
-  if (!c || z_first < 0 || z_total < 0 || (z_total > 0 && z_first >= z_total)) return TFL_EINVAL;
-  c->zorigin = tfl::ZOrigin{z_total > 0 ? z_first : 0, z_total};
-  return TFL_OK;
-}
-
-int tfl_set_stages(tfl_ctx* c, int mask) {
-  if (!c || mask < 0) return TFL_EINVAL;
-  c->stages = mask;
-  return TFL_OK;
-}
-
-int tfl_synchronize(tfl_ctx* c) {
-  if (!c) return TFL_EINVAL;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return TFL_OK;
-}
-
-int tfl_profile_begin(tfl_ctx* c) {
-  if (!c) return TFL_EINVAL;
-  if (tfl::g_prof) return fail(c, TFL_EINVAL, "profile_begin: a profile is already active on this thread");
-  tfl::g_prof = new tfl::Profiler();
-  return TFL_OK;
-}
-
-int tfl_profile_end(tfl_ctx* c, char* buf, int64_t cap) {
-  if (!c) return TFL_EINVAL;
-  tfl::Profiler* p = tfl::g_prof;
-  if (!p) return fail(c, TFL_EINVAL, "profile_end: no active profile");
-  tfl::g_prof = nullptr;
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipDeviceSynchronize();
-  std::vector<std::string> names;
-  std::vector<double> ms;
-  std::vector<long long> calls;
-  for (auto& r : p->recs) {
-    float t = 0.0f;
-    if (hipEventElapsedTime(&t, r.e0, r.e1) != hipSuccess) t = 0.0f;
-    (void)hipEventDestroy(r.e0);
-    (void)hipEventDestroy(r.e1);
-    size_t i = 0;
-    for (; i < names.size(); i++) if (names[i] == r.name) break;
-    if (i == names.size()) { names.push_back(r.name); ms.push_back(0.0); calls.push_back(0); }
-    ms[i] += t; calls[i] += 1;
-  }
-  delete p;
-  std::string js = "{";
-  for (size_t i = 0; i < names.size(); i++) {
-    char tmp[256];
-    snprintf(tmp, sizeof(tmp), "%s\"%s\": {\"calls\": %lld, \"ms\": %.6f}", i ? ", " : "", names[i].c_str(), calls[i], ms[i]);
-    js += tmp;
-  }
-  js += "}";
-  if (buf && cap > 0) {
-    const size_t n = js.size() < (size_t)cap - 1 ? js.size() : (size_t)cap - 1;
-    memcpy(buf, js.data(), n);
-    buf[n] = 0;
-  }
-  return (int)names.size();
-}
-
-int64_t tfl_trace_errors(tfl_ctx* c) {
-  if (!c) return -1;
-  unsigned long long v = 0;
-  if (hipMemcpyAsync(&v, c->d_trace_err, sizeof(v), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return -1;
-  if (hipMemsetAsync(c->d_trace_err, 0, sizeof(v), c->stream) != hipSuccess) return -1;
-  if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
-  return (int64_t)v;
-}
-
-}  // extern "C"
 // The operators a native step calls with a request (tfl_ops.hpp); the public tfl_* forms pass an empty one.
 namespace tfl {
 int advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* fwd,
@@ -468,7 +100,99 @@ int advect_pair(tfl_ctx* c, float dt, float strength, const tfl_tensor* s, const
     return TFL_EUNSUPPORTED;
   return check_launch(c, "advectPair");
 }
+
+int vorticityConfinement(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, float strength, const tfl_tensor* centered,
+                         const tfl_tensor* curl, const tfl_tensor* curlNorm, const tfl_tensor* force, int is3D, const Scope& sc, Ask& ask) {
+  (void)centered; (void)force;  // fused away (vorticity.hip)
+  TRY(check_flags(c, "vorticityConfinement", flags));
+  TRY(check_vel(c, "vorticityConfinement", "U", U, flags, is3D));
+  if (!curl || !curl->data || curl->C != 3 || !same_dims(curl, flags))
+    return fail(c, TFL_EINVAL, "vorticityConfinement: curl must be a 3-channel grid of the flags size");
+  TRY(check_scalar(c, "vorticityConfinement", "curlNorm", curlNorm, flags));
+  const int stg = sc.passes();   // tfl_set_stages: 2 = pass A (curl), 4 = pass B (confinement force)
+  tfl::vorticity_confinement(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data,
+                             strength, curl->data, curlNorm->data, ((stg & 2) ? 1 : 0) | ((stg & 4) ? 2 : 0), nullptr, ask.fold);
+  return check_launch(c, "vorticityConfinement");
+}
+
+int vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, float strength,
+                             const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D, const Scope& sc, Ask& ask) {
+  TRY(check_flags(c, "vorticityConfinementFrom", flags));
+  TRY(check_vel(c, "vorticityConfinementFrom", "U", U, flags, is3D));
+  TRY(check_vel(c, "vorticityConfinementFrom", "USrc", USrc, flags, is3D));
+  if (USrc->data == U->data) return fail(c, TFL_EINVAL, "vorticityConfinementFrom: U must not alias USrc (use vorticityConfinement)");
+  if (!curl || !curl->data || curl->C != 3 || !same_dims(curl, flags))
+    return fail(c, TFL_EINVAL, "vorticityConfinementFrom: curl must be a 3-channel grid of the flags size");
+  TRY(check_scalar(c, "vorticityConfinementFrom", "curlNorm", curlNorm, flags));
+  if (is3D && !ask.two_launch && tfl::vorticity_confinement_fused_ok(true, flags->Z, flags->Y, flags->X) &&
+      tfl::vorticity_confinement_fused(c->stream, sc, flags->B, flags->Z, flags->Y, flags->X, USrc->data, U->data, flags->data, strength, ask.fold))
+    return check_launch(c, "vorticityConfinementFrom");
+  // 2-D, a grid below the fused kernel's size, or TFL_VORT_FUSED=0: the two launches read USrc and write U (round 5) ...
+  // Under a z-window (ADVICE r05) pass A must cover what pass B taps: |curl| two planes below / one above, curl one below -- the
+  // window widened by two planes either way, its two runs merged where they meet; pass B then runs on the window itself.
+  const tfl::ZWin w0 = sc.win;
+  const bool windowed = sc.windowed();
+  if (windowed) {
+    tfl::Scope sa = sc;
+    tfl::ZWin& wa = sa.win;
+    wa = {std::max(w0.a0 - 2, 0), std::min(w0.a1 + 2, (int)flags->Z), 0, 0};
+    if (w0.b1 > w0.b0) { wa.b0 = std::max(w0.b0 - 2, 0); wa.b1 = std::min(w0.b1 + 2, (int)flags->Z); }
+    if (w0.a1 <= w0.a0) { wa.a0 = wa.b0; wa.a1 = wa.b1; wa.b0 = wa.b1 = 0; }
+    else if (wa.b1 > wa.b0 && wa.b0 <= wa.a1) { wa.a1 = wa.b1; wa.b0 = wa.b1 = 0; }
+    const bool a_ok = tfl::vorticity_confinement(c->stream, sa, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
+                                                 curl->data, curlNorm->data, 1, USrc->data, ask.fold);
+    if (a_ok && tfl::vorticity_confinement(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
+                                           curl->data, curlNorm->data, 2, USrc->data, ask.fold))
+      return check_launch(c, "vorticityConfinementFrom");
+    if (a_ok) return fail(c, TFL_EUNSUPPORTED, "vorticityConfinementFrom: pass B could not read USrc on this grid under a z-window");
+  } else if (tfl::vorticity_confinement(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
+                                        curl->data, curlNorm->data, 3, USrc->data, ask.fold))
+    return check_launch(c, "vorticityConfinementFrom");
+  if (windowed)      // (the one-cell kernels below run in place on a copy: the same two windows are needed there -- not built)
+    return fail(c, TFL_EUNSUPPORTED, "vorticityConfinementFrom: this grid takes the one-cell kernels, which do not run from USrc under a z-window; "
+                                     "copy USrc into U and call tfl_vorticityConfinement per pass (tfl_set_stages) with the passes' own windows");
+  // ... or, where only the one-cell kernels apply (X % 4 != 0, misaligned views), the planes of the window are copied and the
+  // two-launch form runs in place
+  {
+    const tfl::Dom d = tfl::make_dom(sc, flags->Z, flags->Y, flags->X);
+    const size_t plane = sizeof(float) * (size_t)flags->Y * flags->X;
+    const int C = is3D ? 3 : 2;
+    for (int b = 0; b < flags->B; b++)
+      for (int ch = 0; ch < C; ch++) {
+        const size_t row = ((size_t)b * C + ch) * flags->Z;
+        if (d.n0 > 0) HIP_TRY(c, hipMemcpyAsync(U->data + (row + d.w0) * (plane / 4), USrc->data + (row + d.w0) * (plane / 4), plane * d.n0, hipMemcpyDeviceToDevice, c->stream));
+        if (d.nw > d.n0) HIP_TRY(c, hipMemcpyAsync(U->data + (row + d.w1) * (plane / 4), USrc->data + (row + d.w1) * (plane / 4), plane * (d.nw - d.n0), hipMemcpyDeviceToDevice, c->stream));
+      }
+  }
+  tfl::vorticity_confinement(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
+                             curl->data, curlNorm->data, 3, nullptr, ask.fold);
+  return check_launch(c, "vorticityConfinementFrom");
+}
+
+int addBuoyancyFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* density,
+                    const float gravity[3], float dt, int is3D, const Scope& sc, Ask& ask) {
+  TRY(check_flags(c, "addBuoyancy", flags));
+  TRY(check_vel(c, "addBuoyancy", "U", U, flags, is3D));
+  TRY(check_vel(c, "addBuoyancy", "USrc", USrc, flags, is3D));
+  TRY(check_scalar(c, "addBuoyancy", "density", density, flags));
+  if (!gravity) return fail(c, TFL_EINVAL, "addBuoyancy: gravity is null");
+  const float k = dt / get_dx(c, sc, flags);  // strength = -gravity * (dt / dx), tfluids.cc:1190-1192
+  tfl::add_buoyancy(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, USrc->data, U->data, flags->data,
+                    density->data, -gravity[0] * k, -gravity[1] * k, -gravity[2] * k, ask.fold);
+  return check_launch(c, "addBuoyancy");
+}
+
+int addGravity(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const float gravity[3], float dt, int is3D, const Scope& sc) {
+  TRY(check_flags(c, "addGravity", flags));
+  TRY(check_vel(c, "addGravity", "U", U, flags, is3D));
+  if (!gravity) return fail(c, TFL_EINVAL, "addGravity: gravity is null");
+  const float k = dt / get_dx(c, sc, flags);  // force = gravity * (dt / dx), tfluids.cc:1265-1267
+  tfl::add_gravity(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data,
+                   gravity[0] * k, gravity[1] * k, gravity[2] * k);
+  return check_launch(c, "addGravity");
+}
 }  // namespace tfl
+
 extern "C" {
 
 int tfl_advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags,
@@ -609,101 +333,6 @@ int tfl_velocityUpdateForward(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor*
   tfl::velocity_update(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, p->data);
   return check_launch(c, "velocityUpdateForward");
 }
-
-}  // extern "C"
-namespace tfl {      // (tfl_ops.hpp)
-int vorticityConfinement(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, float strength, const tfl_tensor* centered,
-                         const tfl_tensor* curl, const tfl_tensor* curlNorm, const tfl_tensor* force, int is3D, const Scope& sc, Ask& ask) {
-  (void)centered; (void)force;  // fused away (vorticity.hip)
-  TRY(check_flags(c, "vorticityConfinement", flags));
-  TRY(check_vel(c, "vorticityConfinement", "U", U, flags, is3D));
-  if (!curl || !curl->data || curl->C != 3 || !same_dims(curl, flags))
-    return fail(c, TFL_EINVAL, "vorticityConfinement: curl must be a 3-channel grid of the flags size");
-  TRY(check_scalar(c, "vorticityConfinement", "curlNorm", curlNorm, flags));
-  const int stg = sc.passes();   // tfl_set_stages: 2 = pass A (curl), 4 = pass B (confinement force)
-  tfl::vorticity_confinement(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data,
-                             strength, curl->data, curlNorm->data, ((stg & 2) ? 1 : 0) | ((stg & 4) ? 2 : 0), nullptr, ask.fold);
-  return check_launch(c, "vorticityConfinement");
-}
-
-int vorticityConfinementFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, float strength,
-                             const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D, const Scope& sc, Ask& ask) {
-  TRY(check_flags(c, "vorticityConfinementFrom", flags));
-  TRY(check_vel(c, "vorticityConfinementFrom", "U", U, flags, is3D));
-  TRY(check_vel(c, "vorticityConfinementFrom", "USrc", USrc, flags, is3D));
-  if (USrc->data == U->data) return fail(c, TFL_EINVAL, "vorticityConfinementFrom: U must not alias USrc (use vorticityConfinement)");
-  if (!curl || !curl->data || curl->C != 3 || !same_dims(curl, flags))
-    return fail(c, TFL_EINVAL, "vorticityConfinementFrom: curl must be a 3-channel grid of the flags size");
-  TRY(check_scalar(c, "vorticityConfinementFrom", "curlNorm", curlNorm, flags));
-  if (is3D && !ask.two_launch && tfl::vorticity_confinement_fused_ok(true, flags->Z, flags->Y, flags->X) &&
-      tfl::vorticity_confinement_fused(c->stream, sc, flags->B, flags->Z, flags->Y, flags->X, USrc->data, U->data, flags->data, strength, ask.fold))
-    return check_launch(c, "vorticityConfinementFrom");
-  // 2-D, a grid below the fused kernel's size, or TFL_VORT_FUSED=0: the two launches read USrc and write U (round 5) ...
-  // Under a z-window (ADVICE r05) pass A must cover what pass B taps: |curl| two planes below / one above, curl one below -- the
-  // window widened by two planes either way, its two runs merged where they meet; pass B then runs on the window itself.
-  const tfl::ZWin w0 = sc.win;
-  const bool windowed = sc.windowed();
-  if (windowed) {
-    tfl::Scope sa = sc;
-    tfl::ZWin& wa = sa.win;
-    wa = {std::max(w0.a0 - 2, 0), std::min(w0.a1 + 2, (int)flags->Z), 0, 0};
-    if (w0.b1 > w0.b0) { wa.b0 = std::max(w0.b0 - 2, 0); wa.b1 = std::min(w0.b1 + 2, (int)flags->Z); }
-    if (w0.a1 <= w0.a0) { wa.a0 = wa.b0; wa.a1 = wa.b1; wa.b0 = wa.b1 = 0; }
-    else if (wa.b1 > wa.b0 && wa.b0 <= wa.a1) { wa.a1 = wa.b1; wa.b0 = wa.b1 = 0; }
-    const bool a_ok = tfl::vorticity_confinement(c->stream, sa, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
-                                                 curl->data, curlNorm->data, 1, USrc->data, ask.fold);
-    if (a_ok && tfl::vorticity_confinement(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
-                                           curl->data, curlNorm->data, 2, USrc->data, ask.fold))
-      return check_launch(c, "vorticityConfinementFrom");
-    if (a_ok) return fail(c, TFL_EUNSUPPORTED, "vorticityConfinementFrom: pass B could not read USrc on this grid under a z-window");
-  } else if (tfl::vorticity_confinement(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
-                                        curl->data, curlNorm->data, 3, USrc->data, ask.fold))
-    return check_launch(c, "vorticityConfinementFrom");
-  if (windowed)      // (the one-cell kernels below run in place on a copy: the same two windows are needed there -- not built)
-    return fail(c, TFL_EUNSUPPORTED, "vorticityConfinementFrom: this grid takes the one-cell kernels, which do not run from USrc under a z-window; "
-                                     "copy USrc into U and call tfl_vorticityConfinement per pass (tfl_set_stages) with the passes' own windows");
-  // ... or, where only the one-cell kernels apply (X % 4 != 0, misaligned views), the planes of the window are copied and the
-  // two-launch form runs in place
-  {
-    const tfl::Dom d = tfl::make_dom(sc, flags->Z, flags->Y, flags->X);
-    const size_t plane = sizeof(float) * (size_t)flags->Y * flags->X;
-    const int C = is3D ? 3 : 2;
-    for (int b = 0; b < flags->B; b++)
-      for (int ch = 0; ch < C; ch++) {
-        const size_t row = ((size_t)b * C + ch) * flags->Z;
-        if (d.n0 > 0) HIP_TRY(c, hipMemcpyAsync(U->data + (row + d.w0) * (plane / 4), USrc->data + (row + d.w0) * (plane / 4), plane * d.n0, hipMemcpyDeviceToDevice, c->stream));
-        if (d.nw > d.n0) HIP_TRY(c, hipMemcpyAsync(U->data + (row + d.w1) * (plane / 4), USrc->data + (row + d.w1) * (plane / 4), plane * (d.nw - d.n0), hipMemcpyDeviceToDevice, c->stream));
-      }
-  }
-  tfl::vorticity_confinement(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, strength,
-                             curl->data, curlNorm->data, 3, nullptr, ask.fold);
-  return check_launch(c, "vorticityConfinementFrom");
-}
-
-int addBuoyancyFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* density,
-                    const float gravity[3], float dt, int is3D, const Scope& sc, Ask& ask) {
-  TRY(check_flags(c, "addBuoyancy", flags));
-  TRY(check_vel(c, "addBuoyancy", "U", U, flags, is3D));
-  TRY(check_vel(c, "addBuoyancy", "USrc", USrc, flags, is3D));
-  TRY(check_scalar(c, "addBuoyancy", "density", density, flags));
-  if (!gravity) return fail(c, TFL_EINVAL, "addBuoyancy: gravity is null");
-  const float k = dt / get_dx(c, sc, flags);  // strength = -gravity * (dt / dx), tfluids.cc:1190-1192
-  tfl::add_buoyancy(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, USrc->data, U->data, flags->data,
-                    density->data, -gravity[0] * k, -gravity[1] * k, -gravity[2] * k, ask.fold);
-  return check_launch(c, "addBuoyancy");
-}
-
-int addGravity(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const float gravity[3], float dt, int is3D, const Scope& sc) {
-  TRY(check_flags(c, "addGravity", flags));
-  TRY(check_vel(c, "addGravity", "U", U, flags, is3D));
-  if (!gravity) return fail(c, TFL_EINVAL, "addGravity: gravity is null");
-  const float k = dt / get_dx(c, sc, flags);  // force = gravity * (dt / dx), tfluids.cc:1265-1267
-  tfl::add_gravity(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data,
-                   gravity[0] * k, gravity[1] * k, gravity[2] * k);
-  return check_launch(c, "addGravity");
-}
-}  // namespace tfl
-extern "C" {
 
 int tfl_vorticityConfinement(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, float strength,
                              const tfl_tensor* centered, const tfl_tensor* curl, const tfl_tensor* curlNorm,
@@ -892,900 +521,6 @@ int tfl_solveLinearSystemJacobi(tfl_ctx* c, const tfl_tensor* p, const tfl_tenso
   if (cur != p->data) HIP_TRY(c, hipMemcpyAsync(p->data, cur, bytes, hipMemcpyDeviceToDevice, c->stream));
   if (residual) *residual = res;
   return check_launch(c, "solveLinearSystemJacobi");
-}
-
-tfl_model* tfl_model_create(tfl_ctx* c, int is3D, int nlayers, const int32_t* cin, const int32_t* cout,
-                            const int32_t* ksize, const float* const* weights, const float* const* biases) {
-  return tfl_model_create_ex(c, is3D, nlayers, cin, cout, ksize, nullptr, nullptr, weights, biases);
-}
-
-tfl_model* tfl_model_create_ex(tfl_ctx* c, int is3D, int nlayers, const int32_t* cin, const int32_t* cout,
-                               const int32_t* ksize, const int32_t* pool, const int32_t* up,
-                               const float* const* weights, const float* const* biases) {
-  return tfl_model_create_opts(c, is3D, nlayers, cin, cout, ksize, pool, up, weights, biases, nullptr);
-}
-
-// the tfl_model_opts of a new model (NULL = default_conf.lua's), checked against the layer table; false on error
-static bool model_opts_of(tfl_ctx* c, int nlayers, const int32_t* pool, const int32_t* up, const tfl_model_opts* opts,
-                          tfl_model_opts* out) {
-  auto bad = [&](const char* m) { fail(c, TFL_EINVAL, "model_create: %s", m); return false; };
-  tfl_model_opts o = {1, 0, 1, 1, TFL_NORM_UDIV, TFL_NORMFUNC_STD, TFL_NONLIN_RELU, 0};
-  if (opts) {
-    o = *opts;
-    o.in_pDiv = o.in_pDiv != 0; o.in_UDiv = o.in_UDiv != 0; o.in_div = o.in_div != 0; o.normalize = o.normalize != 0;
-    o.pressure_skip = o.pressure_skip != 0;
-    if (!o.in_pDiv && !o.in_UDiv && !o.in_div) return bad("Are you sure you dont want any (U, div or p) fields?");   // model.lua:50-52
-    if (o.norm_chan < TFL_NORM_UDIV || o.norm_chan > TFL_NORM_DIV) return bad("Incorrect normalize input channel.");
-    if (o.norm_func != TFL_NORMFUNC_STD && o.norm_func != TFL_NORMFUNC_L2) return bad("Incorrect normalize input function");
-    if (o.nonlin < TFL_NONLIN_RELU || o.nonlin > TFL_NONLIN_SIGMOID) return bad("Bad mconf.nonlinType");
-    if (o.pressure_skip && nlayers < 2) return bad("addPressureSkip needs a hidden layer to join pDiv to");
-    if (o.pressure_skip && (pool || up)) {
-      // the skip joins pDiv at full resolution in front of the last layer: with the layer table in hand, refuse the
-      // combinations tfl_model_finish cannot run (it used to report them on every forward instead: ADVICE r02)
-      bool multires = false;
-      for (int l = 0; l < nlayers; l++) multires = multires || (pool && pool[l] > 1) || (up && up[l] > 1);
-      const bool tail = (pool && (pool[nlayers - 1] > 1 || pool[nlayers - 2] > 1)) || (up && (up[nlayers - 1] > 1 || up[nlayers - 2] > 1));
-      if (tail || (nlayers > 2 && multires)) {
-        fail(c, TFL_EUNSUPPORTED, "model_create: addPressureSkip with pooling / upsampling layers");
-        return false;
-      }
-    }
-  }
-  *out = o;
-  return true;
-}
-
-}  // extern "C"
-// the layer table and weight packing of tfl_model_create_opts / _graph (C++ linkage: templates)
-namespace {
-// a new device buffer holding `bytes` host bytes; false on failure (what was allocated goes with the model)
-template <class T> bool upload(T*& dst, const void* src, size_t bytes) {
-  return hipMalloc((void**)&dst, bytes) == hipSuccess && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-}
-
-// Where the conv modules sit in lib/model.lua's stage table: module i is bank bank[i] of stage stage[i] (1-based), and stage s
-// starts at module first[s]. Stages [split, join) run `banks` banks side by side; a linear model has one bank per stage.
-struct StageTable {
-  std::vector<int> stage, bank, first;
-  int banks = 1, split = 0, join = 0;
-  bool mres = false, concat = false;
-  bool banked(int st) const { return banks > 1 && st >= split && st < join; }
-};
-
-StageTable stage_table(int nst, int banks = 1, int split = 0, int join = 0) {
-  StageTable t;
-  t.banks = banks; t.split = split; t.join = join;
-  t.first.assign(nst + 2, -1);
-  for (int st = 1; st <= nst; st++) {
-    t.first[st] = (int)t.stage.size();
-    for (int b = 0; b < (t.banked(st) ? banks : 1); b++) { t.stage.push_back(st); t.bank.push_back(b); }
-  }
-  return t;
-}
-
-// A module's cudnn weight [cout*S][cin][taps] (output channel index = o*S + sub) -> [sub][tap][cin_p][cout_p], reference input
-// channel ci on plane cmap(ci), and its bias [cout*S] -> [sub][cout_p], uploaded into L (the padding holds zeros)
-template <class Map>
-bool upload_layer(tfl_layer& L, bool is3d, int ci_n, int co_n, const float* w, const float* b, Map cmap) {
-  const int taps = is3d ? L.k * L.k * L.k : L.k * L.k;
-  const int S = is3d ? L.up * L.up * L.up : L.up * L.up;
-  std::vector<float> relaid((size_t)S * taps * L.cin * L.cout, 0.0f);
-  for (int sub = 0; sub < S; sub++)
-    for (int co = 0; co < co_n; co++)
-      for (int ci = 0; ci < ci_n; ci++)
-        for (int t = 0; t < taps; t++)
-          relaid[(((size_t)sub * taps + t) * L.cin + cmap(ci)) * L.cout + co] = w[(((size_t)co * S + sub) * ci_n + ci) * taps + t];
-  std::vector<float> bias_p((size_t)S * L.cout, 0.0f);
-  for (int sub = 0; sub < S; sub++)
-    for (int co = 0; co < co_n; co++) bias_p[(size_t)sub * L.cout + co] = b[(size_t)co * S + sub];
-  return upload(L.w, relaid.data(), relaid.size() * sizeof(float)) && upload(L.b, bias_p.data(), bias_p.size() * sizeof(float));
-}
-
-// batch norm after hidden module i, folded in double: scale = w / sqrt(var + eps), shift = b - mean * scale, each rounded once
-// to fp32, as [2][cout_p] (padded channels: 0, 0 -- they stay exact zeros)
-std::vector<float> bn_fold(const tfl_model_graph* g, int i, int co_n, int cout_p) {
-  std::vector<float> bn((size_t)2 * cout_p, 0.0f);
-  for (int co = 0; co < co_n; co++) {
-    const double wt = (g->bn_weight && g->bn_weight[i]) ? (double)g->bn_weight[i][co] : 1.0;
-    const double bi = (g->bn_bias && g->bn_bias[i]) ? (double)g->bn_bias[i][co] : 0.0;
-    const double sc = wt / std::sqrt((double)g->bn_var[i][co] + g->bn_eps[i]);
-    bn[co] = (float)sc;
-    bn[cout_p + co] = (float)(bi - (double)g->bn_mean[i][co] * sc);
-  }
-  return bn;
-}
-
-// The layer table of a new model, for both create functions: checks every module against the stage table, pads its channel
-// counts, lays out and uploads its weights (and, with g->batch_norm, its folded batch norm), and tracks the resolution, the
-// widest activation and the bank buffers' shapes. g = null for a linear model. Null on error (c->err says why).
-tfl_model* build_layers(tfl_ctx* c, bool is3d, int n, const int32_t* cin, const int32_t* cout, const int32_t* ksize,
-                        const int32_t* pool, const int32_t* up, const float* const* weights, const float* const* biases,
-                        const tfl_model_opts& o, const StageTable& t, const tfl_model_graph* g) {
-  auto bad = [&](const char* msg) -> tfl_model* { fail(c, TFL_EINVAL, "model_create: %s", msg); return nullptr; };
-  const int in_c = o.in_pDiv + o.in_UDiv * (is3d ? 3 : 2) + o.in_div + 1;
-  if (cin[0] != in_c) {
-    fail(c, TFL_EINVAL, "model_create: the first layer must take %d input channels {pDiv, UDiv, div, occupancy as selected}", in_c);
-    return nullptr;
-  }
-  if (cout[n - 1] != 1) return bad("the last layer must output 1 channel (pressure)");
-  tfl_model* m = new tfl_model();
-  m->is3d = is3d;
-  m->opts = o; m->in_c = in_c;
-  m->custom = !(o.in_pDiv && !o.in_UDiv && o.in_div && o.normalize && o.norm_chan == TFL_NORM_UDIV &&
-                o.norm_func == TFL_NORMFUNC_STD && o.nonlin == TFL_NONLIN_RELU && !o.pressure_skip);
-  auto cleanup = [&](const char* msg) -> tfl_model* { tfl_model_destroy(c, m); return bad(msg); };
-  if (hipMalloc((void**)&m->d_stats, sizeof(double) * 2 * kMaxBatch) != hipSuccess) return cleanup("hipMalloc failed");
-#ifdef TFL_EXPERIMENTS      // the ticket words of the producer-side stats fold (model.hip kStatTickets): EXPERIMENTS flavour and linear models only
-  if (!g && (hipMalloc((void**)&m->d_ticket, sizeof(unsigned) * (1 << 16)) != hipSuccess || hipMemset(m->d_ticket, 0, sizeof(unsigned) * (1 << 16)) != hipSuccess))
-    return cleanup("hipMalloc failed");
-#endif
-  // The shape-generic kernels are instantiated for 1, 2, 4, 8, 16, 32, 64 output channels. Any other width (the
-  // `yang` topology of model.lua:188-205 has 6) is zero-padded to the next one: the extra channels carry
-  // relu(0 + 0) = 0 into zero weights of the next layer, i.e. every sum gains exact `+ 0 * 0` terms only.
-  auto padded = [](int cch) { for (int w : {1, 2, 4, 8, 16, 32, 64}) if (cch <= w) return w; return -1; };
-  const int N = t.banks;
-  std::vector<int> cout_p(t.first.size(), 0);     // padded output channels of each stage
-  int down = 1;                                   // resolution of the current activations = grid / down
-  for (int i = 0; i < n; i++) {
-    const int st = t.stage[i], bk = t.bank[i];
-    const bool last = i + 1 == n, skip_in = o.pressure_skip && last;     // skip_in: also reads pDiv/scale (last channel)
-    const bool joined = N > 1 && st == t.join && t.concat;          // input = the concat of the banks
-    if (cin[i] < 1 || cout[i] < 1 || ksize[i] < 1 || (ksize[i] % 2) != 1) return cleanup("convolution size must be odd and positive");
-    if (st > 1 && cin[i] != cout[t.first[st - 1]] * (joined ? N : 1) + (skip_in ? 1 : 0)) return cleanup("layer channel counts do not chain");
-    tfl_layer L;
-    L.stage = st; L.bank = bk; L.pool = pool ? pool[i] : 1; L.up = up ? up[i] : 1;
-    L.dil = (N > 1 && !t.mres && bk > 0) ? (1 << bk) : 1;
-    if ((L.pool != 1 && L.pool != 2) || (L.up != 1 && L.up != 2)) return cleanup("pooling / upsampling factors must be 1 or 2");
-    if (L.pool > 1 && L.up > 1) return cleanup("Pooling and upsampling in the same layer!");               // model.lua:322-324
-    if (L.pool > 1 && last) return cleanup("Pooling is not allowed in the last layer");                    // model.lua:247
-    const int cp = last ? cout[i] : padded(cout[i]);
-    const int prev_p = st == 1 ? in_c : cout_p[st - 1];
-    const int cin_p = st == 1 ? in_c : prev_p * (joined ? N : 1) + (skip_in ? 1 : 0);     // the skip channel sits last
-    if (bk == 0) {     // (the banks of a stage have bank 0's shape)
-      cout_p[st] = cp;
-      if (N > 1 && st == t.split) {
-        m->split_c = cin_p; m->split_down = down; m->bank_down = down;
-        // the pyramid's coarsest level, whatever the banked stages do after it
-        if (t.mres && (down << (N - 1)) > m->max_down) m->max_down = down << (N - 1);
-      }
-      if (down % L.up) return cleanup("a layer upsamples beyond the grid resolution");
-      down /= L.up;
-      if (t.banked(st)) {
-        if (down < m->bank_down) m->bank_down = down;
-        if (cp > m->bank_c) m->bank_c = cp;
-      }
-      down *= L.pool;
-      const int coarsest = (t.mres && t.banked(st)) ? down << (N - 1) : down;
-      if (coarsest > m->max_down) m->max_down = coarsest;
-      if (L.pool > 1 || L.up > 1 || down != 1) m->multires = true;
-    }
-    if (cp < 0) return cleanup("unsupported output channel count (at most 64)");
-    L.cin = cin_p; L.cout = cp; L.k = ksize[i];
-    // reference input channel ci -> its plane in the padded layout (banks' slices prev_p apart; the skip channel last)
-    const int C = st == 1 ? in_c : cout[t.first[st - 1]];
-    auto cmap = [&](int ci) { return (skip_in && ci == cin[i] - 1) ? cin_p - 1 : joined ? (ci / C) * prev_p + ci % C : ci; };
-    const bool has_bn = g && g->batch_norm && !last;
-    if (has_bn && (!g->bn_mean[i] || !g->bn_var[i])) { m->layers.push_back(L); return cleanup("addBatchNorm: a module lacks running_mean / running_var"); }
-    const std::vector<float> bn = has_bn ? bn_fold(g, i, cout[i], cp) : std::vector<float>();
-    const bool ok = upload_layer(L, is3d, cin[i], cout[i], weights[i], biases[i], cmap) &&
-                    (bn.empty() || upload(L.bn, bn.data(), bn.size() * sizeof(float)));
-    m->layers.push_back(L);
-    if (!ok) return cleanup("uploading weights failed");
-    const int width = (N > 1 && st == t.join - 1 && t.concat) ? cp * N : cp + (o.pressure_skip ? 1 : 0);
-    if (!last && width > m->max_c) m->max_c = width;
-  }
-  if (down != 1) return cleanup("the layers do not return to the grid resolution (pool / up factors)");
-  if (N > 1 && t.mres) m->multires = true;
-  if (m->max_c < 1) m->max_c = 1;
-  return m;
-}
-
-// TFL_CONV_PATH -> the form of the 3-D default topology ("direct" never gets here: it keeps the generic kernels)
-ConvPath conv3d_path(const char* force) {
-  if (!force || !*force || strcmp(force, "mfma16") == 0) return ConvPath::conv_mfma16;
-  if (strcmp(force, "mfma") == 0) return ConvPath::conv_mfma;
-  return ConvPath::conv_valu;
-}
-
-// The 3-D default topology's own weights: the fp32 MFMA B fragments and tail weights (every form), the fp16 A fragments and
-// range words (conv_mfma16), the tail pack and the Winograd-transformed weights (conv_mfma16 and conv_valu). Sets the path;
-// returns what failed, or null.
-const char* pack_default3(tfl_model* m, const int32_t* cin, const float* const* weights, const float* const* biases, ConvPath path) {
-  m->path = path;
-  for (int l = 0; l < 3; l++) {
-    const int ci_n = cin[l];
-    std::vector<float> frag((size_t)ci_n * 9 * 64);
-    for (int c = 0; c < ci_n; c++)
-      for (int kz = 0; kz < 3; kz++)
-        for (int ky = 0; ky < 3; ky++)
-          for (int lane = 0; lane < 64; lane++) {
-            const int k = lane >> 4, n = lane & 15, ph = n >> 3, co = n & 7, kx = k - ph;
-            float v = 0.0f;
-            if (kx >= 0 && kx <= 2) v = weights[l][((((size_t)co * ci_n + c) * 3 + kz) * 3 + ky) * 3 + kx];
-            frag[(((size_t)c * 3 + kz) * 3 + ky) * 64 + lane] = v;
-          }
-    if (!upload(m->bfrag[l], frag.data(), frag.size() * sizeof(float))) return "uploading MFMA weight fragments failed";
-  }
-  if (!upload(m->tail_w4, weights[3], 64 * sizeof(float)) || !upload(m->tail_w5, weights[4], 8 * sizeof(float)))
-    return "uploading tail weights failed";
-  if (path == ConvPath::conv_mfma16) {
-    for (int l = 0; l < 3; l++) {
-      std::vector<uint16_t> fr(tfl::conv3_m16_frag_halves(cin[l]));
-      m->post16[l] = tfl::conv3_m16_pack_weights(weights[l], cin[l], fr.data());
-      if (l == 2) m->post16_tail = tfl::conv3_m16_pack_tail(weights[3], fr.data());     // the 8 -> 8 (k = 1) layer's A fragment
-      if (!upload(m->wfrag16[l], fr.data(), fr.size() * sizeof(uint16_t))) return "uploading fp16 MFMA weight fragments failed";
-    }
-    if (hipMalloc((void**)&m->d_range_err, sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(m->d_range_err, 0, sizeof(unsigned long long)) != hipSuccess)
-      return "hipMalloc failed";
-    // the word a later call reads without a sync; failing to get mapped memory only loses the early warning
-    if (hipHostMalloc((void**)&m->h_range, sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
-      *m->h_range = 0;
-      if (hipHostGetDevicePointer((void**)&m->d_range_host, m->h_range, 0) != hipSuccess) { (void)hipHostFree(m->h_range); m->h_range = nullptr; m->d_range_host = nullptr; }
-    } else m->h_range = nullptr;
-  }
-  if (path == ConvPath::conv_mfma) return nullptr;
-  std::vector<float> tp(8 + 64 + 8 + 8 + 1 + 1);
-  for (int i = 0; i < 8; i++) tp[i] = biases[2][i];
-  for (int i = 0; i < 64; i++) tp[8 + i] = weights[3][i];
-  for (int i = 0; i < 8; i++) { tp[72 + i] = biases[3][i]; tp[80 + i] = weights[4][i]; }
-  tp[88] = biases[4][0];
-  tp[89] = m->post16_tail;        // conv_mfma16.hip kTailPost4 (0 on the fp32 paths, which do not read it)
-  if (!upload(m->tail_pack, tp.data(), tp.size() * sizeof(float))) return "uploading tail weights failed";
-  // the three k = 3 layers' weights, Winograd-transformed along x: U = (g0, (g0 + g1 + g2)/2, (g0 - g1 + g2)/2, g2) over the
-  // three x-taps of every (dz, dy, c_in, c_out)
-  for (int l = 0; l < 3; l++) {
-    const int ci_n = cin[l];
-    std::vector<float> u((size_t)9 * 4 * ci_n * 8);
-    for (int co = 0; co < 8; co++)
-      for (int c = 0; c < ci_n; c++)
-        for (int zy = 0; zy < 9; zy++) {
-          const float* g = weights[l] + (((size_t)co * ci_n + c) * 9 + zy) * 3;
-          const float uu[4] = {g[0], 0.5f * ((g[0] + g[2]) + g[1]), 0.5f * ((g[0] + g[2]) - g[1]), g[2]};
-          for (int p = 0; p < 4; p++) u[(((size_t)zy * ci_n + c) * 4 + p) * 8 + co] = uu[p];
-        }
-    if (!upload(m->wino[l], u.data(), u.size() * sizeof(float))) return "uploading transformed weights failed";
-  }
-  return nullptr;
-}
-
-// The 2-D default topology's own weights (conv2d_mfma.hip); returns what failed, or null
-const char* pack_default2(tfl_model* m, const int32_t* cin, const float* const* weights) {
-  m->path = ConvPath::conv2d_mfma;
-  for (int l = 0; l < 4; l++) {
-    const int ci_n = cin[l], c4n = (ci_n + 3) / 4;
-    // B[k][n] of MFMA (tap, c4): lane = k*16 + n holds w[n][4*c4 + k][dy][dx] (0 for padded channels)
-    std::vector<float> frag((size_t)9 * c4n * 64);
-    for (int tap = 0; tap < 9; tap++)
-      for (int c4 = 0; c4 < c4n; c4++)
-        for (int lane = 0; lane < 64; lane++) {
-          const int k = lane >> 4, n = lane & 15, c = 4 * c4 + k;
-          frag[((size_t)tap * c4n + c4) * 64 + lane] = c < ci_n ? weights[l][((size_t)n * ci_n + c) * 9 + tap] : 0.0f;
-        }
-    if (!upload(m->bfrag2[l], frag.data(), frag.size() * sizeof(float))) return "uploading 2-D MFMA weight fragments failed";
-  }
-  if (!upload(m->tail_w5, weights[4], 16 * sizeof(float))) return "uploading tail weights failed";
-  return nullptr;
-}
-}  // namespace
-extern "C" {
-
-tfl_model* tfl_model_create_opts(tfl_ctx* c, int is3D, int nlayers, const int32_t* cin, const int32_t* cout,
-                                 const int32_t* ksize, const int32_t* pool, const int32_t* up,
-                                 const float* const* weights, const float* const* biases, const tfl_model_opts* opts) {
-  if (!c) return nullptr;
-  auto bad = [&](const char* m) -> tfl_model* { fail(c, TFL_EINVAL, "model_create: %s", m); return nullptr; };
-  if (nlayers < 1 || !cin || !cout || !ksize || !weights || !biases) return bad("null or empty layer description");
-  tfl_model_opts o;
-  if (!model_opts_of(c, nlayers, pool, up, opts, &o)) return nullptr;
-  tfl_model* m = build_layers(c, is3D != 0, nlayers, cin, cout, ksize, pool, up, weights, biases, o, stage_table(nlayers), nullptr);
-  if (!m) return nullptr;
-  // the default topologies run on kernels of their own (TFL_CONV_PATH=direct forces the generic ones)
-  const char* force = getenv("TFL_CONV_PATH");
-  if ((force && strcmp(force, "direct") == 0) || m->custom || m->multires || nlayers != 5) return m;
-  const int dflt3[5][3] = {{3, 8, 3}, {8, 8, 3}, {8, 8, 3}, {8, 8, 1}, {8, 1, 1}};
-  const int dflt2[5][3] = {{3, 16, 3}, {16, 16, 3}, {16, 16, 3}, {16, 16, 3}, {16, 1, 1}};
-  auto is = [&](const int (&t)[5][3]) {
-    for (int l = 0; l < 5; l++) if (cin[l] != t[l][0] || cout[l] != t[l][1] || ksize[l] != t[l][2]) return false;
-    return true;
-  };
-  const char* err = nullptr;
-  if (m->is3d && is(dflt3)) err = pack_default3(m, cin, weights, biases, conv3d_path(force));
-  if (!m->is3d && is(dflt2)) err = pack_default2(m, cin, weights);
-  if (err) { tfl_model_destroy(c, m); return bad(err); }
-  return m;
-}
-
-// Every defineModelGraph configuration (include/tfluids_hip.h tfl_model_create_graph; lib/model.lua:253-392). The trivial
-// graph is tfl_model_create_opts; everything else is laid out here for the shape-generic kernels (graph_forward below).
-tfl_model* tfl_model_create_graph(tfl_ctx* c, int is3D, int nconv, const int32_t* cin, const int32_t* cout,
-                                  const int32_t* ksize, const int32_t* pool, const int32_t* up,
-                                  const float* const* weights, const float* const* biases, const tfl_model_opts* opts,
-                                  const tfl_model_graph* g) {
-  if (!c) return nullptr;
-  auto bad = [&](const char* m) -> tfl_model* { fail(c, TFL_EINVAL, "model_create: %s", m); return nullptr; };
-  auto unsupported = [&](const char* m) -> tfl_model* { fail(c, TFL_EUNSUPPORTED, "model_create: %s", m); return nullptr; };
-  if (g) {
-    if (g->banks_num < 1 || g->banks_num > tfl::kMaxJoinBanks) return bad("banksNum must be 1 .. 8");
-    if (g->pool_type != TFL_POOL_AVG && g->pool_type != TFL_POOL_MAX) return bad("Bad pool type.  Must be 'avg' or 'max'");
-  }
-  if (!g || (g->banks_num == 1 && !g->batch_norm && g->pool_type == TFL_POOL_AVG))
-    return tfl_model_create_opts(c, is3D, nconv, cin, cout, ksize, pool, up, weights, biases, opts);
-  if (nconv < 2 || !cin || !cout || !ksize || !weights || !biases) return bad("null or empty layer description");
-  const int N = g->banks_num;
-  int nst = nconv;
-  if (N > 1) {
-    if (g->bank_type != TFL_BANKS_MRES && g->bank_type != TFL_BANKS_DILATE) return bad("banksType must be 'mres' or 'dilate'");
-    if (g->aggregate != TFL_AGG_CONCAT && g->aggregate != TFL_AGG_ADD) return bad("ERROR: unsupported mconf.banksAggregateMethod");
-    if (!(g->split_stage < g->join_stage)) return bad("banksSplitStage must come before banksJoinStage");
-    nst = nconv - (N - 1) * (g->join_stage - g->split_stage);
-    if (g->split_stage < 1 || g->join_stage >= nst) return bad("banksSplitStage / banksJoinStage must lie before the last stage (model.lua:257-258)");
-  }
-  if (g->batch_norm && (!g->bn_mean || !g->bn_var || !g->bn_eps)) return bad("addBatchNorm needs running_mean, running_var and eps per module");
-  StageTable t = N > 1 ? stage_table(nst, N, g->split_stage, g->join_stage) : stage_table(nst);
-  t.mres = g->bank_type == TFL_BANKS_MRES; t.concat = g->aggregate == TFL_AGG_CONCAT;
-  auto P = [&](const int32_t* a, int i) { return a ? a[i] : 1; };
-  for (int i = 0; i < nconv; i++) {
-    const int f = t.first[t.stage[i]];
-    if (cin[i] != cin[f] || cout[i] != cout[f] || ksize[i] != ksize[f] || P(pool, i) != P(pool, f) || P(up, i) != P(up, f))
-      return bad("the banks of a stage must have the same shape");
-    if (N > 1 && !t.mres && t.bank[i] > 0 && P(up, i) > 1) return bad("upsampling not supported for dilated convolutions.");
-  }
-  // the stage table the options are checked against (one entry per stage)
-  std::vector<int32_t> spool(nst), sup(nst);
-  for (int st = 1; st <= nst; st++) { spool[st - 1] = P(pool, t.first[st]); sup[st - 1] = P(up, t.first[st]); }
-  tfl_model_opts o;
-  if (!model_opts_of(c, nst, spool.data(), sup.data(), opts, &o)) return nullptr;
-  if (o.pressure_skip && N > 1 && t.mres) return unsupported("addPressureSkip with pooling / upsampling layers");
-  tfl_model* m = build_layers(c, is3D != 0, nconv, cin, cout, ksize, pool, up, weights, biases, o, t, g);
-  if (!m) return nullptr;
-  m->path = ConvPath::graph; m->banks = N; m->bank_type = g->bank_type; m->aggregate = g->aggregate;
-  m->split = t.split; m->join = t.join; m->nstages = nst;
-  m->pool_max = g->pool_type == TFL_POOL_MAX;
-  return m;
-}
-
-void tfl_model_destroy(tfl_ctx* c, tfl_model* m) {
-  (void)c;
-  if (!m) return;
-  for (auto& L : m->layers) { if (L.w) (void)hipFree(L.w); if (L.b) (void)hipFree(L.b); if (L.bn) (void)hipFree(L.bn); }
-  for (int l = 0; l < 3; l++) if (m->bfrag[l]) (void)hipFree(m->bfrag[l]);
-  for (int l = 0; l < 3; l++) if (m->wino[l]) (void)hipFree(m->wino[l]);
-  for (int l = 0; l < 3; l++) if (m->wfrag16[l]) (void)hipFree(m->wfrag16[l]);
-  if (m->d_range_err) (void)hipFree(m->d_range_err);
-  if (m->h_range) (void)hipHostFree(m->h_range);
-  for (int l = 0; l < 4; l++) if (m->bfrag2[l]) (void)hipFree(m->bfrag2[l]);
-  if (m->tail_w4) (void)hipFree(m->tail_w4);
-  if (m->tail_pack) (void)hipFree(m->tail_pack);
-  if (m->tail_w5) (void)hipFree(m->tail_w5);
-  if (m->d_stats) (void)hipFree(m->d_stats);
-  if (m->d_ticket) (void)hipFree(m->d_ticket);
-  delete m;
-}
-
-int64_t tfl_model_range_errors(tfl_ctx* c, tfl_model* m) {
-  if (!c || !m) return -1;
-  if (!m->d_range_err) return 0;
-  unsigned long long v = 0;
-  if (hipMemcpyAsync(&v, m->d_range_err, sizeof(v), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return -1;
-  if (hipMemsetAsync(m->d_range_err, 0, sizeof(v), c->stream) != hipSuccess) return -1;
-  if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
-  if (m->h_range) *(volatile unsigned long long*)m->h_range = 0;      // acknowledged: the next forward runs again
-  return (int64_t)v;
-}
-
-
-int64_t tfl_model_range_flag(tfl_ctx* c, tfl_model* m) {
-  if (!c || !m) return -1;
-  return m->h_range ? (int64_t)*(volatile unsigned long long*)m->h_range : 0;
-}
-
-// A forward pass after one that clamped activations at the fp16 range would build on wrong values where the reference's
-// fp32 cuDNN carries on: refuse it until the host has acknowledged the count (tfl_model_range_errors).
-// The word is written by the device whenever the projection of an earlier pass gets there (no synchronisation), so WHICH later
-// call sees it first depends on how far the host runs ahead: the gate is best-effort in time, but it is taken at ONE defined
-// point per unit of work -- the entry of a forward pass, or the entry of tfl_simulate_step[_slab] (whose model calls then ask
-// for no gate: tfl_ops.hpp Ask::gated, so that they do not refuse half-way through the step).
-static int range_gate(tfl_ctx* c, tfl_model* m, const char* who) {
-  if (m && m->h_range && *(volatile unsigned long long*)m->h_range != 0)
-    return fail(c, TFL_ERANGE, "%s: an earlier forward pass of this model clamped activations at the fp16 range (|x| > 65504 after the "
-                               "std normalisation: a blown-up simulation); its pressure is not the reference's. Read and reset the count with "
-                               "tfl_model_range_errors, or create the model under TFL_CONV_PATH=winograd (strict fp32, no range limit)", who);
-  return TFL_OK;
-}
-
-// floats of a graph model's bank buffers behind pPred: per bank two scratch buffers of bank_c planes at its finest
-// resolution, and (mres) the pyramid level it starts from; with `base`, their addresses (layout in this order)
-static int64_t graph_ws_floats(const tfl_model* m, int B, int Z, int Y, int X, float* base, float* (*bank)[2], float** pyr = nullptr) {
-  if (m->path != ConvPath::graph || m->banks < 2) return 0;
-  auto cells = [&](int f) { return (int64_t)B * (m->is3d ? (Z + f - 1) / f : Z) * ((Y + f - 1) / f) * ((X + f - 1) / f); };
-  const bool mres = m->bank_type == TFL_BANKS_MRES;
-  int64_t off = 0;
-  for (int i = 0; i < m->banks; i++) {
-    const int64_t n = (int64_t)m->bank_c * cells(mres ? m->bank_down << i : m->bank_down);
-    if (base) { bank[i][0] = base + off; bank[i][1] = base + off + n; }
-    off += 2 * n;
-    if (mres && i > 0) {
-      if (base) pyr[i] = base + off;
-      off += (int64_t)m->split_c * cells(m->split_down << i);
-    }
-  }
-  return off;
-}
-
-int64_t tfl_model_workspace_floats(const tfl_model* m, int B, int Z, int Y, int X) {
-  if (!m) return -1;
-  const int64_t n = (int64_t)B * Z * Y * X;
-  // per-block fp64 stat partials (2 doubles = 4 floats per block, kept first for 8-byte alignment)
-  // + div[1] + net input[in_c] + two ping-pong activation buffers[max_c] + pPred[1]
-  // (+4: the fp16 MFMA path aligns its activation buffers to 16 bytes)
-  return 4 * tfl::model_stat_blocks(B, Z, Y, X) + n * (1 + (int64_t)m->in_c + 2 * (int64_t)m->max_c + 1) + (m->path == ConvPath::conv_mfma16 ? 4 : 0) +
-         graph_ws_floats(m, B, Z, Y, X, nullptr, nullptr);
-}
-
-namespace {
-struct ModelWs { double* partials; float* div; float* x3; float* act[2]; float* pPred; float* bank[tfl::kMaxJoinBanks][2]; float* pyr[tfl::kMaxJoinBanks]; };
-int model_ws(tfl_ctx* c, const tfl_model* m, const tfl_tensor* flags, float* workspace, int64_t workspace_floats,
-             ModelWs* w) {
-  const int B = flags->B, Z = flags->Z, Y = flags->Y, X = flags->X;
-  if (B > kMaxBatch) return fail(c, TFL_EINVAL, "model: batch size above %d", kMaxBatch);
-  const int64_t n = (int64_t)B * Z * Y * X;
-  if (!workspace || workspace_floats < tfl_model_workspace_floats(m, B, Z, Y, X))
-    return fail(c, TFL_EINVAL, "model: workspace too small (%lld floats needed)",
-                (long long)tfl_model_workspace_floats(m, B, Z, Y, X));
-  if (((uintptr_t)workspace & 7) != 0) return fail(c, TFL_EINVAL, "model: workspace must be 8-byte aligned");
-  w->partials = (double*)workspace;
-  w->div = workspace + 4 * tfl::model_stat_blocks(B, Z, Y, X);
-  w->x3 = w->div + n;
-  w->act[0] = w->x3 + (int64_t)m->in_c * n;
-  if (m->path == ConvPath::conv_mfma16) w->act[0] = (float*)(((uintptr_t)w->act[0] + 15) & ~(uintptr_t)15);
-  w->act[1] = w->act[0] + (int64_t)m->max_c * n;
-  w->pPred = w->act[1] + (int64_t)m->max_c * n;
-  graph_ws_floats(m, B, Z, Y, X, w->pPred + n, w->bank, w->pyr);
-  return TFL_OK;
-}
-}  // namespace
-
-float* tfl_model_div(const tfl_model* m, int B, int Z, int Y, int X, float* workspace) {
-  if (!m || !workspace) return nullptr;
-  return workspace + 4 * tfl::model_stat_blocks(B, Z, Y, X);
-}
-
-// the wall codes of THESE flags, if the host registered them with this context (tfl_wall_plan_create), else null
-static const unsigned short* wall_code_of(tfl_ctx* c, const tfl_model* m, const tfl_tensor* flags) {
-  std::lock_guard<std::mutex> lock(c->wall_mu);
-  for (const tfl_wall_plan* wp : c->wall_plans)
-    if (wp->flags == flags->data && wp->is3d == m->is3d && wp->B == flags->B && wp->Z == flags->Z && wp->Y == flags->Y && wp->X == flags->X) return wp->code;
-  return nullptr;
-}
-
-// a graph model's grid must be divisible by its largest downsampling factor (the mres pyramid times the pooling): refused
-// before anything is launched (the reference fails at the join)
-static int graph_gate(tfl_ctx* c, const tfl_model* m, const tfl_tensor* flags, const char* who) {
-  if (m->path != ConvPath::graph) return TFL_OK;
-  const int f = m->max_down;
-  if ((m->is3d && flags->Z % f) || flags->Y % f || flags->X % f)
-    return fail(c, TFL_EINVAL, "%s: grid %dx%dx%d is not divisible by the model's downsampling factor %d (banks x pooling)", who,
-                flags->Z, flags->Y, flags->X, f);
-  return TFL_OK;
-}
-
-}  // extern "C"
-namespace tfl {      // (tfl_ops.hpp)
-int model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tensor* flags, const tfl_tensor* UOut, float* workspace,
-                int64_t workspace_floats, int zlo, int zhi, double* stats, const Scope& sc, Ask& ask) {
-  TRY(check_flags(c, "model_begin", flags));
-  if (!m) return fail(c, TFL_EINVAL, "model_begin: null model");
-  if (ask.gated) TRY(range_gate(c, m, "model_begin"));
-  const int is3D = m->is3d ? 1 : 0;
-  TRY(check_vel(c, "model_begin", "UDiv", UDiv, flags, is3D));
-  TRY(check_vel(c, "model_begin", "UOut", UOut, flags, is3D));
-  if (zlo < 0 || zhi > flags->Z || zlo >= zhi) return fail(c, TFL_EINVAL, "model_begin: bad z range [%d, %d)", zlo, zhi);
-  TRY(graph_gate(c, m, flags, "model_begin"));
-  ModelWs w;
-  TRY(model_ws(c, m, flags, workspace, workspace_floats, &w));
-  // SetWallBcs(UDiv) lands in UOut. UOut may alias UDiv: a thread rewrites only the cell it read, and
-  // neighbour values are re-derived from the flags, so a neighbour already holding the BC-applied
-  // value gives the identical result (the BC is idempotent).
-  int stg = sc.passes();   // tfl_set_stages: 2 = wall BCs + divergence + partial sums, 4 = reduce [zlo, zhi)
-  if (ask.conv1_sums_stats) stg &= ~4;   // tfl_model_forward: the first conv layer reduces the partials itself (round 6)
-  m->stat_pairs_per_plane = tfl::model_stat_pairs_per_plane(flags->B, flags->Z, flags->Y, flags->X, UDiv->data, flags->data, UOut->data, w.div);
-  const unsigned short* code = wall_code_of(c, m, flags);
-  tfl::model_pre(c->stream, sc, m->is3d, flags->B, flags->Z, flags->Y, flags->X, UDiv->data, flags->data, UOut->data,
-                 w.div, w.partials, stats ? stats : m->d_stats, zlo, zhi, ((stg & 2) ? 1 : 0) | ((stg & 4) ? 2 : 0), m->d_ticket, code);
-  return check_launch(c, "model_begin");
-}
-}  // namespace tfl
-extern "C" {
-
-int tfl_model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tensor* flags, const tfl_tensor* UOut,
-                    float* workspace, int64_t workspace_floats, int zlo, int zhi, double* stats) {
-  tfl::Ask none;
-  return tfl::model_begin(c, m, UDiv, flags, UOut, workspace, workspace_floats, zlo, zhi, stats, tfl::scope_of(c), none);
-}
-
-tfl_wall_plan* tfl_wall_plan_create(tfl_ctx* c, const tfl_tensor* flags) {
-  if (!c || !flags || !flags->data) return nullptr;
-  if (check_flags(c, "wall_plan_create", flags) != TFL_OK) return nullptr;
-  const long long n = (long long)flags->B * flags->Z * flags->Y * flags->X;
-  tfl_wall_plan* p = new tfl_wall_plan();
-  p->flags = flags->data; p->B = flags->B; p->Z = flags->Z; p->Y = flags->Y; p->X = flags->X;
-  if (hipMalloc((void**)&p->code, (size_t)n * sizeof(unsigned short)) != hipSuccess) { (void)hipGetLastError(); c->err = "wall_plan_create: hipMalloc failed"; delete p; return nullptr; }
-  (void)hipDeviceSynchronize();               // one-time set-up: whoever filled the flags (any stream) is done
-  p->is3d = flags->Z > 1; p->owner = c;
-  tfl::wall_code(c->stream, p->is3d, flags->B, flags->Z, flags->Y, flags->X, flags->data, p->code);
-  if (hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(p->code); c->err = "wall_plan_create: the code kernel failed"; delete p; return nullptr; }
-  std::lock_guard<std::mutex> lock(c->wall_mu);
-  for (tfl_wall_plan*& q : c->wall_plans)     // a new plan for the same array replaces the old registration (its owner still frees it)
-    if (q->flags == p->flags) { q->owner = nullptr; q = p; return p; }
-  c->wall_plans.push_back(p);
-  return p;
-}
-
-// Take the plan out of its context's registry WITHOUT freeing it: no HIP call, safe from a finalizer (where the hipFree of
-// tfl_wall_plan_destroy could invalidate a graph capture in progress). The step stops finding it at once -- which matters when the
-// flags array has died and its address may be handed out again before the host gets round to tfl_wall_plan_destroy.
-void tfl_wall_plan_retire(tfl_wall_plan* p) {
-  if (!p) return;
-  tfl_ctx* o = p->owner;
-  if (!o) return;
-  std::lock_guard<std::mutex> lock(o->wall_mu);
-  for (size_t i = 0; i < o->wall_plans.size(); i++)
-    if (o->wall_plans[i] == p) { o->wall_plans.erase(o->wall_plans.begin() + (long)i); break; }
-  p->owner = nullptr;
-}
-
-void tfl_wall_plan_destroy(tfl_ctx* c, tfl_wall_plan* p) {
-  if (!p) return;
-  (void)c;                                    // (the plan knows its context, and whether that context still exists)
-  tfl_wall_plan_retire(p);
-  if (p->code) (void)hipFree(p->code);
-  delete p;
-}
-
-namespace {
-// What every forward of tfl_model_finish reads. U: the wall-BC'd velocity tfl_model_begin left in UOut; (st_in, count): the
-// input scale; sc: the window and stage mask of the call.
-struct Fwd {
-  hipStream_t st;
-  int B, Z, Y, X;
-  const float *pDiv, *U, *flags;
-  const double* st_in; double count;
-  const tfl::Scope& sc;
-  bool conv1_sums_stats;      // tfl_model_forward (whole array, the model's own stats buffer): conv layer 1 sums the partials
-};
-
-// the net input {pDiv/scale, div/scale, occupancy}, or the channels tfl_model_opts selects, into w.x3 on the planes
-// [z0, z0 + nz) (nz < 0: every plane)
-void net_input(const tfl_model* m, const ModelWs& w, const Fwd& a, int z0, int nz) {
-  if (m->custom)
-    tfl::model_net_input_gen(a.st, m->is3d, a.B, a.Z, a.Y, a.X, m->opts.in_pDiv, m->opts.in_UDiv, m->opts.in_div, a.pDiv,
-                             a.U, w.div, a.flags, a.st_in, a.count, w.x3, z0, nz);
-  else
-    tfl::model_net_input(a.st, m->is3d, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, w.x3, z0, nz);
-}
-
-// One conv module of a graph model at [Zc][Yc][Xc] (updated to its output's): its conv(s) -- one per ConvolutionUpsample
-// sub-position -- then the pooling; the module's batch norm rides on whichever launch writes last. P / Q are two scratch
-// buffers (`in` may be one of them); the result goes to planes [c0, c0 + cout) of the och-plane `dst`, or (dst = null)
-// into P or Q. Returns where the result is, null when no kernel exists for the width.
-float* graph_layer(hipStream_t st, const tfl_model* m, const tfl_layer& L, int B, int& Zc, int& Yc, int& Xc, const float* in,
-                   float* P, float* Q, float* dst, int och, int c0, int act) {
-  float* conv_out = in == P ? Q : P;
-  const bool pools = L.pool > 1;
-  float* cdst = (pools || !dst) ? conv_out : dst;
-  const float* bs = L.bn ? L.bn : nullptr;
-  const float* bt = L.bn ? L.bn + L.cout : nullptr;
-  const int taps = m->is3d ? L.k * L.k * L.k : L.k * L.k;
-  const int S = m->is3d ? L.up * L.up * L.up : L.up * L.up;
-  for (int sub = 0; sub < S; sub++)
-    if (!tfl::conv_direct_graph(st, m->is3d, B, Zc, Yc, Xc, L.cin, L.cout, L.k, act, in, L.w + (size_t)sub * taps * L.cin * L.cout,
-                                L.b + (size_t)sub * L.cout, cdst, L.up, sub, cdst == dst ? och : 0, cdst == dst ? c0 : 0, L.dil,
-                                pools ? nullptr : bs, pools ? nullptr : bt))
-      return nullptr;
-  if (m->is3d) Zc *= L.up;
-  Yc *= L.up; Xc *= L.up;
-  if (!pools) return cdst;
-  float* pdst = dst ? dst : (conv_out == P ? Q : P);
-  tfl::pool2_graph(st, m->is3d, m->pool_max, B, L.cout, Zc, Yc, Xc, conv_out, pdst, dst ? och : L.cout, dst ? c0 : 0, bs, bt);
-  if (m->is3d) Zc /= 2;
-  Yc /= 2; Xc /= 2;
-  return pdst;
-}
-
-// The conv stack of a graph model (lib/model.lua:262-362): trunk stages in the act[] ping-pong, the banks in their own
-// buffers, one k_bank_join launch at the join (none when every bank wrote its own concat slice: dilate + concat).
-int graph_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a) {
-  net_input(m, w, a, 0, -1);
-  hipStream_t st = a.st;
-  const int B = a.B;
-  const int act = 1 + m->opts.nonlin;
-  const int nl = (int)m->layers.size();
-  const bool mres = m->bank_type == TFL_BANKS_MRES, concat = m->aggregate == TFL_AGG_CONCAT;
-  const float* in = w.x3;
-  int Zc = a.Z, Yc = a.Y, Xc = a.X;
-  auto none = [&](const tfl_layer& L) { return fail(c, TFL_EUNSUPPORTED, "model_finish: no kernel for %d output channels", L.cout); };
-  for (int l = 0; l < nl;) {
-    const tfl_layer& L0 = m->layers[l];
-    if (m->banks > 1 && L0.stage == m->split) {
-      float* join = in == w.act[0] ? w.act[1] : w.act[0];     // (`in` is read by every bank: the join goes elsewhere)
-      const int N = m->banks, Cp = m->layers[l + (m->join - m->split - 1) * N].cout, och = concat ? Cp * N : Cp;
-      // mres: the average-pooling pyramid, one launch per level (model.lua:266-276)
-      const float* bin[tfl::kMaxJoinBanks];
-      int bZ[tfl::kMaxJoinBanks], bY[tfl::kMaxJoinBanks], bX[tfl::kMaxJoinBanks];
-      bin[0] = in; bZ[0] = Zc; bY[0] = Yc; bX[0] = Xc;
-      for (int i = 1; i < N; i++) {
-        bin[i] = in; bZ[i] = bZ[i - 1]; bY[i] = bY[i - 1]; bX[i] = bX[i - 1];
-        if (!mres) continue;
-        tfl::avg_pool2(st, m->is3d, B * m->split_c, bZ[i - 1], bY[i - 1], bX[i - 1], bin[i - 1], w.pyr[i]);
-        bin[i] = w.pyr[i];
-        if (m->is3d) bZ[i] /= 2;
-        bY[i] /= 2; bX[i] /= 2;
-      }
-      int slot[tfl::kMaxJoinBanks], sh[tfl::kMaxJoinBanks], n = 0;
-      const float* src[tfl::kMaxJoinBanks];
-      int jZ = 0, jY = 0, jX = 0;
-      for (int i = 0; i < N; i++) {
-        const float* x = bin[i];
-        int z = bZ[i], y = bY[i], xx = bX[i];
-        const bool direct = i == 0 || (concat && !mres);            // this bank writes its slice of the join itself
-        for (int s = m->split; s < m->join; s++) {
-          const tfl_layer& L = m->layers[l + (s - m->split) * N + i];
-          const bool last = s + 1 == m->join;
-          x = graph_layer(st, m, L, B, z, y, xx, x, w.bank[i][0], w.bank[i][1], (last && direct) ? join : nullptr, och,
-                          concat ? i * Cp : 0, act);
-          if (!x) return none(L);
-        }
-        if (i == 0) { jZ = z; jY = y; jX = xx; }
-        if (!direct) { slot[n] = i; sh[n] = mres ? i : 0; src[n] = x; n++; }
-      }
-      if (n > 0 && !tfl::bank_join(st, m->is3d, !concat, B, Cp, jZ, jY, jX, n, slot, sh, src, join, och))
-        return fail(c, TFL_EINVAL, "model_finish: bad bank join");
-      in = join; Zc = jZ; Yc = jY; Xc = jX;
-      l += (m->join - m->split) * N;
-      continue;
-    }
-    const bool last = l + 1 == nl;
-    const bool joins_skip = m->opts.pressure_skip && l + 2 == nl;
-    float* dst = last ? w.pPred : (joins_skip ? (in == w.act[0] ? w.act[1] : w.act[0]) : nullptr);
-    float* out = graph_layer(st, m, L0, B, Zc, Yc, Xc, in, w.act[0], w.act[1], dst, joins_skip ? L0.cout + 1 : L0.cout, 0,
-                             last ? 0 : act);
-    if (!out) return none(L0);
-    // addPressureSkip: pDiv/scale becomes the last input channel of the last layer (model.lua:356-360)
-    if (joins_skip) tfl::model_skip_channel(st, B, (long long)a.Z * a.Y * a.X, a.pDiv, a.st_in, a.count, out, L0.cout + 1, L0.cout);
-    in = out;
-    l++;
-  }
-  return TFL_OK;
-}
-// tfl_model_opts: the input scale comes from another field / function / not at all. All three reach the kernels through the
-// (stats, count) pair scale_from_stats reads -- sqrt((n s2 - s1^2) / (n (n - 1))): the l2 norm is (s1, s2, n) = (0, sum x^2, 2),
-// "no scaling" is (0, 1, 2). Forms that pair in the model's stats buffer (a.st_in) and a.count. A caller that passes stats has
-// formed it itself (a z-slab rank: over its owned planes, all-reduced -- model_slab_stats).
-int opts_stats(tfl_ctx* c, const tfl_model* m, const ModelWs& w, Fwd& a) {
-  const tfl_model_opts& o = m->opts;
-  const long long cells = (long long)a.Z * a.Y * a.X;
-  const float* field = o.norm_chan == TFL_NORM_PDIV ? a.pDiv : (o.norm_chan == TFL_NORM_DIV ? w.div : a.U);
-  const long long nf = o.norm_chan == TFL_NORM_UDIV ? cells * (m->is3d ? 3 : 2) : cells;
-  if (!o.normalize) { tfl::model_field_stats(a.st, a.B, nf, field, 2, m->d_stats); a.count = 2.0; }
-  else if (o.norm_func == TFL_NORMFUNC_L2) { tfl::model_field_stats(a.st, a.B, nf, field, 1, m->d_stats); a.count = 2.0; }
-  else if (o.norm_chan != TFL_NORM_UDIV) {
-    if (nf < 2) return fail(c, TFL_EINVAL, "model_finish: Sample variance requires more than one sample.");
-    tfl::model_field_stats(a.st, a.B, nf, field, 0, m->d_stats); a.count = (double)nf;
-  }
-  return TFL_OK;
-}
-
-// The 3-D default topology's three forms. Stage bits: 1 = first conv layer, 2 = second, 4 = third + the two 1x1x1 layers.
-// Split-operand fp16 MFMA (conv_mfma16.hip); the two activation buffers hold the "h2" form (32 B per voxel, as 8 fp32).
-// Layers 1 + 2 in one launch where the whole array is computed (round 5); a z-slab rank runs them under separate windows.
-void forward_mfma16(const tfl_model* m, const ModelWs& w, const Fwd& a) {
-  const bool fused12 = (a.sc.passes() & 3) == 3 &&
-                       tfl::conv3_m16_first2_fused(a.st, a.sc, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0],
-                                                   m->layers[0].b, m->post16[0], m->wfrag16[1], m->layers[1].b, m->post16[1],
-                                                   w.act[1], m->d_range_err);
-  if ((a.sc.passes() & 1) && !fused12) {
-    if (a.conv1_sums_stats)
-      tfl::conv3_m16_first_fused(a.st, a.sc, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0], m->layers[0].b,
-                                 m->post16[0], w.act[0], m->d_range_err, w.partials, m->stat_pairs_per_plane * a.Z, m->d_stats);
-    else
-      tfl::conv3_m16_first_fused(a.st, a.sc, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wfrag16[0], m->layers[0].b,
-                                 m->post16[0], w.act[0], m->d_range_err);
-  }
-  if ((a.sc.passes() & 2) && !fused12)
-    tfl::conv3_m16_mid(a.st, a.sc, a.B, a.Z, a.Y, a.X, w.act[0], m->wfrag16[1], m->layers[1].b, m->post16[1], w.act[1], m->d_range_err);
-  if (a.sc.passes() & 4)
-    tfl::conv3_m16_tail(a.st, a.sc, a.B, a.Z, a.Y, a.X, w.act[1], m->wfrag16[2], m->tail_pack, m->post16[2], w.pPred, m->d_range_err);
-}
-
-// fp32 Winograd on the vector ALUs (conv_valu.hip): the first layer builds {pDiv/scale, div/scale, occupancy} while staging
-// its LDS tile
-void forward_valu(const tfl_model* m, const ModelWs& w, const Fwd& a) {
-  if (a.sc.passes() & 1)
-    tfl::conv3_valu_first_fused(a.st, a.sc, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->wino[0], m->layers[0].b, w.act[0]);
-  if (a.sc.passes() & 2) tfl::conv3_valu_mid(a.st, a.sc, a.B, a.Z, a.Y, a.X, w.act[0], m->wino[1], m->layers[1].b, w.act[1]);
-  if (a.sc.passes() & 4) tfl::conv3_valu_tail(a.st, a.sc, a.B, a.Z, a.Y, a.X, w.act[1], m->wino[2], m->tail_pack, w.pPred);
-}
-
-// fp32-operand MFMA (conv_mfma.hip): the first layer builds {pDiv/scale, div/scale, occupancy} while staging its LDS tile
-void forward_mfma(const tfl_model* m, const ModelWs& w, const Fwd& a) {
-  if (a.sc.passes() & 1)
-    tfl::conv3_mfma_first_fused(a.st, a.sc, a.B, a.Z, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->bfrag[0],
-                                m->layers[0].b, w.act[0]);
-  if (a.sc.passes() & 2) tfl::conv3_mfma_mid(a.st, a.sc, a.B, a.Z, a.Y, a.X, w.act[0], m->bfrag[1], m->layers[1].b, w.act[1]);
-  if (a.sc.passes() & 4)
-    tfl::conv3_mfma_tail(a.st, a.sc, a.B, a.Z, a.Y, a.X, w.act[1], m->bfrag[2], m->layers[2].b, m->tail_w4, m->layers[3].b,
-                         m->tail_w5, m->layers[4].b, w.pPred);
-}
-
-// The 2-D default topology (conv2d_mfma.hip), whole grid only
-void forward_mfma2d(const tfl_model* m, const ModelWs& w, const Fwd& a) {
-  tfl::conv2_mfma_first_fused(a.st, a.B, a.Y, a.X, a.pDiv, w.div, a.flags, a.st_in, a.count, m->bfrag2[0], m->layers[0].b, w.act[0]);
-  tfl::conv2_mfma_mid(a.st, a.B, a.Y, a.X, w.act[0], m->bfrag2[1], m->layers[1].b, w.act[1]);
-  tfl::conv2_mfma_mid(a.st, a.B, a.Y, a.X, w.act[1], m->bfrag2[2], m->layers[2].b, w.act[0]);
-  tfl::conv2_mfma_tail(a.st, a.B, a.Y, a.X, w.act[0], m->bfrag2[3], m->layers[3].b, m->tail_w5, m->layers[4].b, w.pPred);
-}
-
-// Every other linear model, layer by layer on the shape-generic kernels. The planes of every launch: the whole grid, or (a
-// z-window [za, zb) on a 3-D model: a z-slab rank's owned planes) the cone of the planes the velocity update reads, layer by
-// layer (model_cone).
-int generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a) {
-  hipStream_t st = a.st;
-  const int B = a.B, Z = a.Z, Y = a.Y, X = a.X;
-  const bool windowed = a.sc.windowed();
-  const tfl::ZWin& win = a.sc.win;
-  if (m->multires && ((m->is3d && Z % m->max_down) || Y % m->max_down || X % m->max_down))
-    return fail(c, TFL_EINVAL, "model_finish: grid %dx%dx%d is not divisible by the model's pooling factor %d", Z, Y, X, m->max_down);
-  const size_t nl = m->layers.size();
-  tfl::ModelCone cone;
-  int za = 0, zb = Z;
-  if (windowed) {
-    const char* why = nullptr;
-    if (!tfl::model_cone(m, &cone, &why)) return fail(c, TFL_EUNSUPPORTED, "model_finish: %s", why);
-    if (win.b1 > win.b0) return fail(c, TFL_EINVAL, "model_finish: the shape-generic forward takes one z-window run");
-    za = std::max(win.a0, 0); zb = std::min(win.a1, Z);
-    if (za % cone.F || zb % cone.F)
-      return fail(c, TFL_EINVAL, "model_finish: z-window [%d, %d) is not aligned to the model's downsampling factor %d", za, zb, cone.F);
-  }
-  auto span = [&](int lo, int hi, int dd, int Zd, int& z0, int& nz) {     // planes [za/dd - lo, zb/dd + hi) of a Zd-deep level
-    if (!windowed) { z0 = 0; nz = Zd; return; }
-    const int a = std::max(za / dd - lo, 0), b = std::min(zb / dd + hi, Zd);
-    z0 = a; nz = b > a ? b - a : 0;
-  };
-  int z0, nz;
-  if (windowed) span(cone.in_lo, cone.in_hi, 1, Z, z0, nz); else { z0 = 0; nz = -1; }
-  net_input(m, w, a, z0, nz);
-  const int act = 1 + m->opts.nonlin;            // conv_direct: 1 ReLU, 2 ReLU6, 3 sigmoid
-  const float* in = w.x3;
-  int Zc = Z, Yc = Y, Xc = X;     // resolution of `in`
-  for (size_t l = 0; l < nl; l++) {
-    const tfl_layer& L = m->layers[l];
-    const bool last = l + 1 == nl;
-    const bool joins_skip = m->opts.pressure_skip && l + 2 == nl;
-    float* out = last ? w.pPred : (in == w.act[0] ? w.act[1] : w.act[0]);
-    const int taps = m->is3d ? L.k * L.k * L.k : L.k * L.k;
-    const int S = m->is3d ? L.up * L.up * L.up : L.up * L.up;
-    if (windowed) span(cone.layer[l].conv_lo, cone.layer[l].conv_hi, cone.layer[l].conv_d, Zc, z0, nz);
-    for (int sub = 0; sub < S; sub++)      // ConvolutionUpsample: one strided-store convolution per sub-position
-      if (!tfl::conv_direct(st, m->is3d, B, Zc, Yc, Xc, L.cin, L.cout, L.k, last ? 0 : act, in,
-                            L.w + (size_t)sub * taps * L.cin * L.cout, L.b + (size_t)sub * L.cout, out, L.up, sub,
-                            joins_skip ? L.cout + 1 : 0, z0, nz))
-        return fail(c, TFL_EUNSUPPORTED, "model_finish: no kernel for %d output channels", L.cout);
-    // addPressureSkip: pDiv/scale becomes the last input channel of the last layer (model.lua:356-360); windowed: on the
-    // planes the last layer reads (the skip needs a full-resolution net, so they are at the grid's resolution)
-    if (joins_skip) {
-      long long t0 = 0, nt = -1;
-      if (windowed) { span(cone.layer[nl - 1].in_lo, cone.layer[nl - 1].in_hi, 1, Z, z0, nz); t0 = (long long)z0 * Y * X; nt = (long long)nz * Y * X; }
-      tfl::model_skip_channel(st, B, (long long)Z * Y * X, a.pDiv, a.st_in, a.count, out, L.cout + 1, L.cout, t0, nt);
-    }
-    if (m->is3d) Zc *= L.up;
-    Yc *= L.up; Xc *= L.up;
-    in = out;
-    if (L.pool > 1) {
-      float* pooled = in == w.act[0] ? w.act[1] : w.act[0];
-      if (windowed) span(cone.layer[l].pool_lo, cone.layer[l].pool_hi, 2 * cone.layer[l].conv_d, Zc / 2, z0, nz);
-      else { z0 = 0; nz = -1; }
-      tfl::avg_pool2(st, m->is3d, B * L.cout, Zc, Yc, Xc, in, pooled, z0, nz);
-      if (m->is3d) Zc /= 2;
-      Yc /= 2; Xc /= 2;
-      in = pooled;
-    }
-  }
-  return TFL_OK;
-}
-}  // namespace
-}  // extern "C"
-
-namespace tfl {      // (tfl_ops.hpp)
-int model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* flags, const tfl_tensor* pOut,
-                 const tfl_tensor* UOut, float* workspace, int64_t workspace_floats, const double* stats, double count,
-                 const tfl_tensor* UBC, const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, const Scope& sc, Ask& ask) {
-  TRY(check_flags(c, "model_finish", flags));
-  if (!m) return fail(c, TFL_EINVAL, "model_finish: null model");
-  const int is3D = m->is3d ? 1 : 0;
-  TRY(check_vel(c, "model_finish", "UOut", UOut, flags, is3D));
-  TRY(check_scalar(c, "model_finish", "pDiv", pDiv, flags));
-  TRY(check_scalar(c, "model_finish", "pOut", pOut, flags));
-  if ((UBC == nullptr) != (UBCInvMask == nullptr)) return fail(c, TFL_EINVAL, "model_finish: UBC and UBCInvMask go together");
-  if (UBC) {
-    TRY(check_vel(c, "model_finish", "UBC", UBC, flags, is3D));
-    TRY(check_vel(c, "model_finish", "UBCInvMask", UBCInvMask, flags, is3D));
-  }
-  if (!(count > 1.0)) return fail(c, TFL_EINVAL, "model_finish: Sample variance requires more than one sample.");
-  ModelWs w;
-  TRY(model_ws(c, m, flags, workspace, workspace_floats, &w));
-  TRY(graph_gate(c, m, flags, "model_finish"));
-  const bool windowed = sc.windowed();
-  if (m->path == ConvPath::graph && (stats || sc.stages || windowed))
-    return fail(c, TFL_EUNSUPPORTED, "model_finish: banked, batch-norm and max-pool models run un-sharded only");
-  if (m->custom && !stats && (sc.stages || windowed))
-    return fail(c, TFL_EUNSUPPORTED, "model_finish: a windowed forward of a model with non-default tfl_model_opts takes the caller's "
-                                     "input-scale stats over the owned planes (tfl_simulate_step_slab forms them)");
-  Fwd a{c->stream, flags->B, flags->Z, flags->Y, flags->X, pDiv->data, UOut->data, flags->data, stats ? stats : m->d_stats,
-        count, sc, ask.conv1_sums_stats};
-  if (m->custom && !stats) TRY(opts_stats(c, m, w, a));
-  // tfl_set_stages (z-slab ranks run each layer under its own z-window): the 3-D default topology's forms take stage bits 1,
-  // 2 and 4 (see there); the other 3-D linear models take 1 = the whole net, each launch on its layer's cone of the
-  // z-window's planes. 8 = velocity update / un-scale / wall BCs on the window.
-  const int stg = sc.passes();
-  if (sc.stages && !default3(m->path) && !(m->path == ConvPath::generic && m->is3d))
-    return fail(c, TFL_EUNSUPPORTED, "model_finish: stage masks need a 3-D model that is not a graph model");
-  switch (m->path) {
-    case ConvPath::conv_mfma16: forward_mfma16(m, w, a); break;
-    case ConvPath::conv_valu: forward_valu(m, w, a); break;
-    case ConvPath::conv_mfma: forward_mfma(m, w, a); break;
-    case ConvPath::conv2d_mfma: forward_mfma2d(m, w, a); break;
-    case ConvPath::generic: if (stg & 1) TRY(generic_forward(c, m, w, a)); break;
-    case ConvPath::graph: TRY(graph_forward(c, m, w, a)); break;
-  }
-  if (stg & 8) {
-    const bool pub = ask.reach_via_project;
-    ask.reach_folded = tfl::model_project(a.st, sc, m->is3d, a.B, a.Z, a.Y, a.X, w.pPred, flags->data, a.st_in, a.count, UOut->data,
-                                          pOut->data, UBC ? UBC->data : nullptr, UBC ? UBCInvMask->data : nullptr, doClamp, lo, hi,
-                                          m->d_range_host ? m->d_range_err : nullptr, m->d_range_host, pub ? c->d_reach : nullptr,
-                                          pub ? c->d_reach_host : nullptr, pub ? c->d_reach : nullptr, wall_code_of(c, m, flags),
-                                          pub ? c->d_reach_tick : nullptr, ask.fold);
-    ask.reach_published = pub;
-  }
-  return check_launch(c, "model_finish");
-}
-
-int model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
-                  const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace, int64_t workspace_floats, const tfl_tensor* UBC,
-                  const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi, const Scope& sc, Ask& ask) {
-  TRY(check_flags(c, "model_forward", flags));
-  if (sc.stages || sc.windowed())
-    return fail(c, TFL_EINVAL, "model_forward: clear the z-window / stage mask first (use tfl_model_begin / _finish)");
-  // round 6: with the default 3-D conv path the first layer's blocks sum k_bcs_div_stats' partial pairs themselves (the same
-  // order, the same bits) -- no k_reduce_stats launch between the two kernels (4.3 us of pure latency at 128^3)
-  ask.conv1_sums_stats = m && m->path == ConvPath::conv_mfma16 && conv3_m16_first_sums_partials() && !conv3_m16_fuse12_requested() &&
-                         !model_stats_fold_requested();
-  TRY(model_begin(c, m, UDiv, flags, UOut, workspace, workspace_floats, 0, flags->Z, nullptr, sc, ask));
-  const double count = (double)flags->Z * flags->Y * flags->X * (m->is3d ? 3 : 2);
-  return model_finish(c, m, pDiv, flags, pOut, UOut, workspace, workspace_floats, nullptr, count, UBC, UBCInvMask, doClamp, lo, hi, sc, ask);
-}
-}  // namespace tfl
-extern "C" {
-
-int tfl_model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* flags,
-                     const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace, int64_t workspace_floats,
-                     const double* stats, double count, const tfl_tensor* UBC, const tfl_tensor* UBCInvMask,
-                     int doClamp, float lo, float hi) {
-  tfl::Ask none;
-  return tfl::model_finish(c, m, pDiv, flags, pOut, UOut, workspace, workspace_floats, stats, count, UBC, UBCInvMask, doClamp, lo, hi, tfl::scope_of(c), none);
-}
-
-int tfl_model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* UDiv,
-                      const tfl_tensor* flags, const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace,
-                      int64_t workspace_floats, const tfl_tensor* UBC, const tfl_tensor* UBCInvMask, int doClamp,
-                      float lo, float hi) {
-  tfl::Ask none;
-  return tfl::model_forward(c, m, pDiv, UDiv, flags, pOut, UOut, workspace, workspace_floats, UBC, UBCInvMask, doClamp, lo, hi, tfl::scope_of(c), none);
-}
-
-double tfl_getDx(tfl_ctx* c, const tfl_tensor* flags) {
-  if (!flags) return 0.0;
-  return tfl::get_dx_double(c, tfl::Scope{}, flags);
 }
 
 int tfl_copy(tfl_ctx* c, const tfl_tensor* dst, const tfl_tensor* src) {

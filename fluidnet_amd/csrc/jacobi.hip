@@ -1,6 +1,6 @@
 // jacobi.hip -- one Jacobi sweep of the pressure Poisson problem (gfx950).
 // Replaces generic/tfluids.cu:1765-1821 (kernel) -- the reference has no CPU version
-// (generic/tfluids.cc:836-839). The iteration loop lives in abi.cpp (:1853-1921 semantics).
+// (generic/tfluids.cc:836-839). The iteration loop lives in abi.cpp (tfl_solveLinearSystemJacobi).
 // Algorithmic bytes: p_prev, flags, div -> p = 16 B/cell/iteration; HBM/L2-bound.
 #include <atomic>
 #include <cstdlib>

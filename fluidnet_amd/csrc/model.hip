@@ -113,7 +113,7 @@ __device__ __forceinline__ void reduce_partials(const double* __restrict__ p, lo
 // -- one counter for all blocks serialised 2048 same-address atomics at 128^3 (+16 us on a 19 us kernel, measured); with
 // one counter per plane the atomics of different planes proceed in parallel and only 128 meet on the last one.
 struct StatTail { unsigned* ticket; double* stats; long long per_sample; unsigned per_plane, planes; int B; };
-[[maybe_unused]] constexpr int kStatTickets = 1 << 16;       // ticket words a model owns (abi.cpp): B * Z + 1 of them are used
+[[maybe_unused]] constexpr int kStatTickets = 1 << 16;       // ticket words a model owns (model_host.cpp): B * Z + 1 of them are used
 // (FOLD is a template flag of the kernels: the default instantiation carries none of this -- its loads stay one batch,
 // tests/test_isa_cpu.py)
 template <bool FOLD>
@@ -526,7 +526,7 @@ struct BcArgs {  // optional fused tail of simulate(): setConstVals + clamp, sim
   BcFoldArg fold;                            // or tfl_simulate_step's sparse pair with its box (tfl_host.hpp)
   int enable_clamp; float lo, hi;
   // the fp16 conv path's range-error count (device word, final once the conv kernels are done) and the pinned host word a
-  // non-zero count is copied to, so that the host sees it at its next call without a stream sync (abi.cpp range_gate)
+  // non-zero count is copied to, so that the host sees it at its next call without a stream sync (model_host.cpp range_gate)
   const unsigned long long* range_src; unsigned long long* range_dst;
   // the z-slab step's reach word (sticky max|u_z|, device) and its mapped pinned mirror: the same thread copies it, every step
   // (round 6: an async 4-byte D2H copy on the stream blocks the host until the stream has drained on this stack)

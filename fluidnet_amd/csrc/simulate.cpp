@@ -4,7 +4,7 @@
 // launches no kernel of its own except the one-time BC scan; the z-slab rank-step (tfl_simulate_step_slab) also launches
 // the plane kernels of its Jacobi projection and its halo bookkeeping (reach absmax / publication, message packing).
 #include "../../include/tfluids_hip.h"
-#include "tfl_ctx.hpp"
+#include "tfl_abi.hpp"
 #include "tfl_host.hpp"
 #include "tfl_ops.hpp"
 
@@ -125,8 +125,6 @@ LateUbc late_ubc_of(const tfl_sim_state* s) {
   const bool late = s->UBC && s->UBC->sparse && s->UBC->idem;
   return LateUbc{late, (s->UBC && !late) ? &s->UBC->bc : nullptr, (s->UBC && !late) ? &s->UBC->inv : nullptr};
 }
-
-#define TRY(x) do { int rc_ = (x); if (rc_ != TFL_OK) return rc_; } while (0)
 
 }  // namespace
 

@@ -1,5 +1,5 @@
 // tfl_ctx.hpp -- the context object behind the opaque tfl_ctx* of include/tfluids_hip.h (private to the library:
-// abi.cpp owns it, simulate.cpp reads the stream and keeps the z-slab reach-check words). It holds resources and what the
+// context.cpp owns it, simulate.cpp reads the stream and keeps the z-slab reach-check words). It holds resources and what the
 // host's tfl_set_* calls stored. Nothing per call lives here: what a native step asks of an operator call (tfl_ops.hpp Ask)
 // and where that call computes (tfl_host.hpp Scope) travel as arguments.
 #pragma once
@@ -30,7 +30,7 @@ struct tfl_ctx {
   double* d_resid = nullptr;                  // Jacobi residual accumulators [kMaxBatch]
   double* h_resid = nullptr;                  // pinned mirror
   float dx_override = 0.0f;                   // > 0: use instead of 1/max(X,Y,Z) (z-slab ranks: global dx)
-  // the next four: what scope_of (abi.cpp) copies into a Scope, for the public operators that honour them and for
+  // the next four: what scope_of (context.cpp) copies into a Scope, for the public operators that honour them and for
   // tfl_simulate_step; the z-slab step builds scopes of its own and takes the advect mode alone
   tfl::ZWin zwin = {0, 0, 0, 0};              // tfl_set_z_window: planes the next operators compute (all zero = all)
   tfl::ZOrigin zorigin = {0, 0};              // tfl_set_z_origin: where the arrays sit in the whole grid

@@ -1,4 +1,4 @@
-// tfl_host.hpp -- host-side launcher prototypes shared by the .hip translation units and abi.cpp.
+// tfl_host.hpp -- host-side launcher prototypes shared by the .hip translation units and the .cpp files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -24,7 +24,7 @@ inline const char* exp_env(const char* name) {
 
 // Where an operator computes and which of its passes run: a value that every windowed operator receives as an argument and
 // hands to its launchers. A public tfl_* operator that honours the tfl_set_* calls forms one from its context at entry
-// (abi.cpp scope_of); the z-slab step builds its own per call. All zero = the whole array, every pass, exact advection, dx of
+// (context.cpp scope_of); the z-slab step builds its own per call. All zero = the whole array, every pass, exact advection, dx of
 // the array itself.
 struct ZWin { int a0, a1, b0, b1; };       // planes [a0, a1) and [b0, b1) in array indices; all zero = the whole array
 struct ZOrigin { int first, total; };      // the array inside the whole grid: {first global plane, planes of the whole grid}; {0, 0} = none
@@ -274,7 +274,7 @@ void apply_bcs_indexed(hipStream_t st, long long n, const int* idx, float* x, co
 long long pack_planes(hipStream_t st, int n, float* const* ptrs, const int* rows, const int* zlo, const int* nplanes,
                       long long zstride, long long yx, float* buf, int unpack, float* const* bufs = nullptr);
 
-// abi.cpp: a model built by tfl_model_create_graph with banks, batch norm or max pooling (runs un-sharded only)
+// model_host.cpp: a model built by tfl_model_create_graph with banks, batch norm or max pooling (runs un-sharded only)
 bool model_is_graph(const tfl_model* m);
 // the factor its grid must be divisible by (the mres pyramid times the pooling; 1 = any grid)
 int model_grid_factor(const tfl_model* m);

@@ -53,7 +53,7 @@ def model_cone_refusal(model):
 
 
 def model_cone(model):
-    """The z-slab cone of a (3-D, non-graph) FluidNetModel, as tfl_slab_halo_model's walk forms it (csrc/abi.cpp model_cone):
+    """The z-slab cone of a (3-D, non-graph) FluidNetModel, as tfl_slab_halo_model's walk forms it (csrc/model_host.cpp model_cone):
     backwards from pPred on the owned planes widened by (1, 0), through each layer's pooling (extents x 2), ConvolutionUpsample
     (ceil(extent / 2) at the coarse grid) and conv (+ k // 2). Returns a dict: `layers` = per layer {conv: (lo, hi), d, pool:
     (lo, hi) or None, input: (lo, hi)} (planes below / above the owned range at grid / d), `input` = the net input's (lo, hi),
