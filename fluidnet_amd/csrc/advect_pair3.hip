@@ -76,6 +76,7 @@ bool advect_pair3(hipStream_t st, const AdvArgs& a0, int B, const float* s, cons
   AdvArgs as = a0, av = a0;
   as.ord = make_block_order(g.sgx, g.sgy, g.sgz, xcd_order_enabled(), xcd_run(g.sgx, g.sgy));      // as the scalar launchers: runs of tiles per XCD
   av.outside = 0;
+  as.zskip = scal3_zskip(d);
   const unsigned grid = (unsigned)(g.ns + nv);
   if (stages & 2) {
     TFL_TIMED_EXT("k_adv_fwd_pair", st);

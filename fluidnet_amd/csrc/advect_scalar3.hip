@@ -24,6 +24,30 @@
 //    halo-2 tile of pass A 68 x 8 x 6 = 6.4 staged words per cell (10.6 for one plane), the halo-1 tile of pass B 3.1;
 //    the shape is chosen per pass and grid size (launch()).
 //
+//  * THE SHORT PATH OF AN ALL-ZERO TILE. The density of a plume in a large box is +0.0 almost everywhere, and
+//    there every lane of the fast path computes the same thing: a trace, an 8-tap lerp over zeros, a 27-tap search over zeros.
+//    - Block predicate Zt: every word stage_masked wrote is the mask word or has the bit pattern 0 (-0.0, denormals, NaNs, inf
+//      clear it). Each thread ORs the bits of the fluid words it stages (the select mask_word already makes, once more, and an
+//      OR per word); each wave leaves its verdict in an LDS word of its own before the block's ONE barrier, every thread reads
+//      the words after it. No load and no barrier is added. (A fluid word that carries the mask word's own bits counts as
+//      non-zero: the block then traces as before.)
+//    - Lane predicate `small`: |u * ndt| <= T = 0.45 on every axis, as three ordered compares (a NaN or inf is not small).
+//    - Pass A, lane with Zt && fluid && deep && small: fwd = +0, bounds = (+0, +0); pass B (Zt over the tile of fwd), lane with
+//      Zt && fluid && !border && deep && small: bwd = +0, then the unchanged correction, clamp, BC fold and store.
+//    Why this is exact. With |d| <= T per axis: l2 <= 3 T^2 (1 + 3 ulp), so len <= 0.78 <= kFastLen: one step, `shortd` holds.
+//    Exact mode: q = d / len and q * len are each rounded once, |q * len| <= |d| (1 + 2^-23)^2 < 0.4500002; tolerance mode: the
+//    step is d itself; a displacement below the norm threshold gives p = ctr. The grid's global extent is at most 2^16
+//    (scal3_zskip checks it next to the entry's other guards), so ctr = i + 0.5 is exact with ulp <= 2^-8 and p = fl(ctr + step)
+//    lies within 0.4500002 + 2^-9 < 0.5 of the centre: strictly inside (i, i + 1) on every axis, finite, (int)p = i. So
+//    trace_fast returns ok with e = the lane's own cell, which is fluid. lerp_tile's corners are int(p - 0.5) in {i - 1, i}
+//    and the next: the own cell is one of the eight, so the result is not the mask word; every unmasked corner is +0, and
+//    0 * t0 + 0 * t1 (exact) / fma(t1, 0 - 0, 0) (tolerance) is +0 for the weights in [0, 1] fract produces; the lerp1_fluid
+//    redo (a masked corner) picks among +0 values. The 27 taps around e are +0 or masked and e itself is +0: v_min3 / v_max3
+//    from (+inf, -inf) give (+0, +0). Nothing on this path counts a trace error. tests/test_scal3_zero_skip_cpu.py restates the
+//    trace in float32 and pins T and the extent; tests/test_hip_scal3_zero_skip.py holds the bits.
+//    TFL_SCAL3_ZSKIP=0 (EXPERIMENTS flavour) turns the short path off; that flavour also counts the blocks with Zt per pass
+//    (tfl_scal3_zero_blocks).
+//
 // Algorithmic HBM bytes per cell: pass A 24 (s, U3, flags -> fwd) + 8 (the clamp bounds of the forward position, two
 // planes of the fwdPos temp), pass B 28 (fwd, s, U3, flags -> dst) + 8. `sampleOutsideFluid`, 2-D grids and the Manta
 // methods stay on advect.hip.
@@ -73,19 +97,26 @@ __device__ __forceinline__ void stg(float* __restrict__ base, unsigned byte_off,
 __device__ __forceinline__ float mask_word(float v, float f, bool in) {
   return (in && ((((int)f) & kFluid) != 0)) ? v : __builtin_bit_cast(float, kMaskBits);
 }
+// the same word for the zero test of the tile: the value's bits where mask_word keeps the value, 0 where it writes the mask word
+// (the same condition: one select + one OR per staged word)
+__device__ __forceinline__ unsigned nonzero_bits(float v, float f, bool in) {
+  return (in && ((((int)f) & kFluid) != 0)) ? __builtin_bit_cast(unsigned, v) : 0u;
+}
 
 // tile <- (flags & fluid) ? g : mask word over the block's halo box; cells outside the array get the mask word.
 // A wave stages whole rows (one coalesced 256-B load of g and of flags per row, the row's offset is scalar), a thread one
 // word of the 2H halo columns. EDGE = false: the block's halo rows and planes all lie inside the array and its 64 columns
 // inside the row (only the halo COLUMNS can stick out): no clamps, no row tests.
+// Returns the OR of the bit patterns of the words this thread wrote for fluid cells inside the array (the mask word counts as 0):
+// 0 from every thread of the block <=> the tile holds nothing but +0.0 and mask words (the block predicate Zt, header).
 template <int TZ, int H, bool EDGE, int NW>       // TZ: planes of the tile; NW: waves of the block
-__device__ __forceinline__ void stage_masked(float* __restrict__ tile, const float* __restrict__ g,
+__device__ __forceinline__ unsigned stage_masked(float* __restrict__ tile, const float* __restrict__ g,
                                              const float* __restrict__ flags, const Dom& d, int x0, int y0, int k0, int tid) {
   using T = Tile<TZ, H>;
   constexpr int NT = 64 * NW, ROWS = T::LY * T::LZ;
   if (TFL_SCAL3_ABL & 1) {
     for (int it = tid; it < T::N; it += NT) tile[it] = 0.5f;
-    return;
+    return 1u;
   }
   const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int gx = x0 + lane;
@@ -109,6 +140,7 @@ __device__ __forceinline__ void stage_masked(float* __restrict__ tile, const flo
   float hs[HPER], hf[HPER];
   bool hok[HPER];
   int hdst[HPER];
+  unsigned nzw = 0u;
 #pragma unroll
   for (int q = 0; q < HPER; q++) {
     const int it = min(tid + q * NT, ITEMS - 1);
@@ -126,11 +158,50 @@ __device__ __forceinline__ void stage_masked(float* __restrict__ tile, const flo
   for (int q = 0; q < PER; q++) {
     const int r = w + q * NW;
     const int rz = r / T::LY, ry = r - rz * T::LY;
-    if ((ROWS % NW) == 0 || r < ROWS) tile[rz * T::LP + ry * T::LX + H + lane] = mask_word(sv[q], fv[q], okr[q] && xin);
+    if ((ROWS % NW) == 0 || r < ROWS) {
+      tile[rz * T::LP + ry * T::LX + H + lane] = mask_word(sv[q], fv[q], okr[q] && xin);
+      nzw |= nonzero_bits(sv[q], fv[q], okr[q] && xin);
+    }
   }
 #pragma unroll
   for (int q = 0; q < HPER; q++)
-    if (tid + q * NT < ITEMS) tile[hdst[q]] = mask_word(hs[q], hf[q], hok[q]);
+    if (tid + q * NT < ITEMS) {
+      tile[hdst[q]] = mask_word(hs[q], hf[q], hok[q]);
+      nzw |= nonzero_bits(hs[q], hf[q], hok[q]);
+    }
+  return nzw;
+}
+
+// The block's barrier between staging and use of the tile, and on it the block predicate Zt: every wave leaves "did any of my
+// lanes stage a word that is neither +0.0 nor the mask word" in its own LDS word BEFORE the barrier (no word to clear first, so
+// no second barrier), every thread reads the NW words after it. `on`: AdvArgs::zskip.
+template <int NW>
+__device__ __forceinline__ bool barrier_all_zero(unsigned nzw, int tid, int on) {
+  __shared__ unsigned wave_nz[NW];
+  const bool any = __builtin_amdgcn_ballot_w64(nzw != 0u) != 0ull;       // wave-uniform
+  wave_nz[__builtin_amdgcn_readfirstlane(tid >> 6)] = any ? 1u : 0u;
+  __syncthreads();
+  unsigned r = 0u;
+#pragma unroll
+  for (int w = 0; w < NW; w++) r |= wave_nz[w];
+  return (__builtin_amdgcn_readfirstlane((int)r) == 0) & (on != 0);
+}
+
+// the lane predicate `small` of the short path (header): every component of the displacement u * ndt, formed as trace_fast forms
+// it, is at most kSmallDisp in magnitude. Three ordered compares: a NaN makes it false (v_max3_f32 would drop the NaN).
+constexpr float kSmallDisp = 0.45f;
+constexpr int kSmallExtent = 1 << 16;      // the proof's bound on the grid's global extent (scal3_zskip)
+__device__ __forceinline__ bool small_disp(v3 u, float ndt) {
+  const float dx = u.x * ndt, dy = u.y * ndt, dz = u.z * ndt;
+  return (__builtin_fabsf(dx) <= kSmallDisp) & (__builtin_fabsf(dy) <= kSmallDisp) & (__builtin_fabsf(dz) <= kSmallDisp);
+}
+// EXPERIMENTS flavour: blocks that had Zt set, per pass (words 1 and 2 behind the trace-error word of the context)
+__device__ __forceinline__ void count_zero_block(const AdvArgs& a, bool zt, int tid, int pass) {
+#ifdef TFL_EXPERIMENTS
+  if (zt && tid == 0) atomicAdd(a.err + 1 + pass, 1ull);
+#else
+  (void)a; (void)zt; (void)tid; (void)pass;
+#endif
 }
 
 // getCentered (third_party/grid.cc:346-377) of a cell whose +1 neighbours exist (not a border cell); o4 = byte offset of the cell
@@ -276,9 +347,12 @@ __device__ __forceinline__ float max3r(float a, float b, float c) { float r; asm
   const unsigned oxy4 = (unsigned)(min(i, d.X - 1) + __mul24(min(j, d.Y - 1), d.sy)) * 4u;         \
   /* on_border (bnd = 1) without branches: c < 1 || c > N - 2  <=>  unsigned(c - 1) >= unsigned(N - 2) */ \
   const bool border_xy = ((unsigned)(i - 1) >= (unsigned)(d.X - 2)) | ((unsigned)(j - 1) >= (unsigned)(d.Y - 2))
+/* (STAGE ends with the block's barrier; Zt: the staged tile holds only +0.0 and mask words, and the short path is on) */
 #define TFL_SCAL3_STAGE(H, SRC)                                                                    \
-  if (inner) stage_masked<PZ, H, false, TY * TZ>(tile, SRC, flags, d, x0, y0, k0, tid);            \
-  else stage_masked<PZ, H, true, TY * TZ>(tile, SRC, flags, d, x0, y0, k0, tid)
+  unsigned nzw_;                                                                                   \
+  if (inner) nzw_ = stage_masked<PZ, H, false, TY * TZ>(tile, SRC, flags, d, x0, y0, k0, tid);     \
+  else nzw_ = stage_masked<PZ, H, true, TY * TZ>(tile, SRC, flags, d, x0, y0, k0, tid);            \
+  const bool Zt = barrier_all_zero<TY * TZ>(nzw_, tid, a.zskip)
 
 // Cell part (inside a loop over q): geometry of the thread's q-th cell
 #define TFL_SCAL3_CELL(H, q)                                                                       \
@@ -314,7 +388,7 @@ __device__ __forceinline__ void scal3_fwd_body(const SBlock sb, float* __restric
     uq[q] = centred_if(d, U, o4, deep);
   }
   TFL_SCAL3_STAGE(HH, s);
-  __syncthreads();
+  count_zero_block(a, Zt, tid, 0);
 #pragma unroll
   for (int q = 0; q < KZ; q++) {
     TFL_SCAL3_CELL(HH, q);
@@ -324,11 +398,12 @@ __device__ __forceinline__ void scal3_fwd_body(const SBlock sb, float* __restric
     const bool fl = !is_mask(tile[c0]);
     float v = svq[q];
     int e = c0;                     // cell of the forward position: the cell itself where nothing is advected (tfluids.cc:159-163)
-    bool slow = false;
+    bool slow = false, zshort = false;
     if (fl) {
       slow = true;
       if (deep) {
         if (TFL_SCAL3_ABL & 8) { v = tile[c0] + u.x; slow = false; }
+        else if (Zt && small_disp(u, -a.dt)) { v = 0.0f; slow = false; zshort = true; }      // the short path (header): e = c0
         else {
           v3 p;
           const bool ok = trace_fast<FAST>(tile, T::LX, T::LP, cbias, ctr, u, -a.dt, p, e);
@@ -339,7 +414,8 @@ __device__ __forceinline__ void scal3_fwd_body(const SBlock sb, float* __restric
     }
     float lo = __builtin_inff(), hi = -__builtin_inff();
     if (BOUNDS && !slow && (TFL_SCAL3_ABL & 2)) { lo = tile[e]; hi = lo; }
-    if (BOUNDS && !slow && !(TFL_SCAL3_ABL & 2)) {
+    if (BOUNDS && zshort) { lo = 0.0f; hi = 0.0f; }
+    if (BOUNDS && !slow && !zshort && !(TFL_SCAL3_ABL & 2)) {
       const float* qq = tile + (e - 1 - T::LX - T::LP);
       float t[27];
 #pragma unroll
@@ -387,7 +463,7 @@ __device__ __forceinline__ void scal3_bwd_body(const SBlock sb, float* __restric
     uq[q] = centred_if(d, U, o4, deep);
   }
   TFL_SCAL3_STAGE(1, fwd);
-  __syncthreads();
+  count_zero_block(a, Zt, tid, 1);
 #pragma unroll
   for (int q = 0; q < KZ; q++) {
     TFL_SCAL3_CELL(1, q);
@@ -402,6 +478,7 @@ __device__ __forceinline__ void scal3_bwd_body(const SBlock sb, float* __restric
       bool slow = true;
       if (deep) {
         if (TFL_SCAL3_ABL & 8) { bwd = tile[c0] + u.x; slow = false; }
+        else if (Zt && small_disp(u, a.dt)) { bwd = 0.0f; slow = false; }      // the short path (header)
         else {
           v3 p; int e;
           const bool ok = trace_fast<FAST>(tile, T::LX, T::LP, cbias, ctr, u, a.dt, p, e);
@@ -494,13 +571,21 @@ void launch(hipStream_t st, int shape, bool two_pass, const AdvArgs& a, int B, c
 }  // namespace
 
 #ifndef TFL_SCAL3_NO_ENTRY      // (advect_pair3.hip includes this file for the kernels' bodies only)
-bool advect_scalar3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* s, const float* U, const float* flags,
+int scal3_zskip(const Dom& d) {
+  // A/B and test switch, EXPERIMENTS flavour only (the product library is at its limit of switches): 0 = no short path
+  static const bool on = !(exp_env("TFL_SCAL3_ZSKIP") && atoi(exp_env("TFL_SCAL3_ZSKIP")) == 0);
+  // the proof that a `small` displacement ends in the lane's own cell needs ulp(cell centre) <= 2^-8 (header)
+  return on && d.X <= kSmallExtent && d.Y <= kSmallExtent && d.Zg <= kSmallExtent;
+}
+
+bool advect_scalar3(hipStream_t st, bool two_pass, const AdvArgs& a0, int B, const float* s, const float* U, const float* flags,
                     float* fwd, float* bounds, float* dst, int stages, Fold& f) {
   static const bool off = exp_env("TFL_ADVECT_GATHER") != nullptr || exp_env("TFL_SCALAR_GATHER") != nullptr;   // A/B switch: the round-2 gather kernels
   static const int tzsel = getenv("TFL_SCAL3_TZ") ? atoi(getenv("TFL_SCAL3_TZ")) : 0;   // 0 = per pass and grid size (launch)
-  const Dom& d = a.d;
+  const Dom& d = a0.d;
   // 24-bit multiplies address the tile and the planes; 32-bit BYTE offsets the cells of the three velocity channels
-  if (off || a.outside || d.Z < 3 || (long long)d.X * d.Y * 4 >= (1 << 24) || 12ll * d.sc >= (1ll << 32)) return false;
+  if (off || a0.outside || d.Z < 3 || (long long)d.X * d.Y * 4 >= (1 << 24) || 12ll * d.sc >= (1ll << 32)) return false;
+  AdvArgs a = a0; a.zskip = scal3_zskip(d);
 #ifdef TFL_EXPERIMENTS
   // the z-marched kernels (round 5): TFL_SCAL3_MARCH=1 -- bit-identical, one staging pass per plane, and SLOWER than the
   // tile kernels (profiles/r05_advect_experiments.txt: pass A 29.5 vs 25.3 us at 128^3, 176 vs 162 at 256^3; pass B 21.3 vs

@@ -77,8 +77,8 @@ tfl_ctx* tfl_create(int device) {
   if (hipSetDevice(device) != hipSuccess) return nullptr;
   tfl_ctx* c = new tfl_ctx();
   c->device = device;
-  if (hipMalloc((void**)&c->d_trace_err, sizeof(unsigned long long)) != hipSuccess ||
-      hipMemset(c->d_trace_err, 0, sizeof(unsigned long long)) != hipSuccess ||
+  if (hipMalloc((void**)&c->d_trace_err, 3 * sizeof(unsigned long long)) != hipSuccess ||      // [1], [2]: tfl_scal3_zero_blocks
+      hipMemset(c->d_trace_err, 0, 3 * sizeof(unsigned long long)) != hipSuccess ||
       hipMalloc((void**)&c->d_resid, sizeof(double) * kMaxBatch) != hipSuccess ||
       hipHostMalloc((void**)&c->h_resid, sizeof(double) * kMaxBatch, hipHostMallocDefault) != hipSuccess ||
       hipMalloc((void**)&c->d_reach, sizeof(float)) != hipSuccess ||
@@ -206,6 +206,16 @@ int64_t tfl_trace_errors(tfl_ctx* c) {
   if (hipMemsetAsync(c->d_trace_err, 0, sizeof(v), c->stream) != hipSuccess) return -1;
   if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
   return (int64_t)v;
+}
+
+int tfl_scal3_zero_blocks(tfl_ctx* c, int64_t* blocks) {
+  if (!c || !blocks) return TFL_EINVAL;
+  unsigned long long v[2] = {0, 0};
+  HIP_TRY(c, hipMemcpyAsync(v, c->d_trace_err + 1, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->d_trace_err + 1, 0, sizeof(v), c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  blocks[0] = (int64_t)v[0]; blocks[1] = (int64_t)v[1];
+  return TFL_OK;
 }
 
 double tfl_getDx(tfl_ctx* c, const tfl_tensor* flags) {

@@ -12,7 +12,8 @@ struct AdvArgs {
   float strength;
   int outside;  // sampleOutsideFluid
   int fast;     // tfl_set_advect_mode: 1 = the tolerance mode of the LDS-tiled 3-D kernels (advect_vel3.hip, advect_scalar3.hip)
-  unsigned long long* err;
+  unsigned long long* err;   // the context's counters: [0] trace errors (EXPERIMENTS flavour: [1], [2] all-zero blocks of the scalar passes A / B)
+  int zskip = 0;    // advect_scalar3.hip: 1 = an all-zero tile takes the short path (scal3_zskip; TFL_SCAL3_ZSKIP=0 turns it off)
   BlockOrder ord;   // block -> tile order of the LDS-tiled 3-D kernels (tfl_device.hpp; zero = blockIdx as it comes)
 };
 
@@ -128,6 +129,10 @@ bool advect_vel3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const f
 // advect_scalar3.hip: advectScalar of the trace-based methods on a 3-D grid (no min/max grid: `bounds` = two planes)
 bool advect_scalar3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* s, const float* U, const float* flags,
                     float* fwd, float* bounds, float* dst, int stages, Fold& f);
+
+// 1 = the scalar passes may take the short path of all-zero tiles on this grid (the switch is on and the grid's global extent is
+// inside the bound of the proof); what advect_scalar3 / advect_pair3 put into AdvArgs::zskip
+int scal3_zskip(const Dom& d);
 
 // advect_pair3.hip (round 6): the passes A (stages & 2) / the passes B (stages & 4) of advectScalar AND advectVel in one launch each
 bool advect_pair3(hipStream_t st, const AdvArgs& a, int B, const float* s, const float* U, const float* flags, float* sfwd, float* sbounds,

@@ -26,7 +26,7 @@ struct tfl_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   std::string err;
-  unsigned long long* d_trace_err = nullptr;  // device word: traces that hit an invariant path
+  unsigned long long* d_trace_err = nullptr;  // device words: [0] traces that hit an invariant path, [1], [2] tfl_scal3_zero_blocks
   double* d_resid = nullptr;                  // Jacobi residual accumulators [kMaxBatch]
   double* h_resid = nullptr;                  // pinned mirror
   float dx_override = 0.0f;                   // > 0: use instead of 1/max(X,Y,Z) (z-slab ranks: global dx)

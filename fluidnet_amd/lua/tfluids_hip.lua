@@ -50,6 +50,7 @@ int tfl_set_advect_mode(tfl_ctx* ctx, int mode);
 int tfl_get_advect_mode(const tfl_ctx* ctx);
 int tfl_synchronize(tfl_ctx* ctx);
 int64_t tfl_trace_errors(tfl_ctx* ctx);
+int tfl_scal3_zero_blocks(tfl_ctx* ctx, int64_t* blocks);
 int tfl_profile_begin(tfl_ctx* ctx);
 int tfl_profile_end(tfl_ctx* ctx, char* buf, int64_t cap);
 int tfl_advectScalar(tfl_ctx* ctx, float dt, const tfl_tensor* s, const tfl_tensor* U,

@@ -528,6 +528,15 @@ def traceErrors(like):
     return int(lib.tfl_trace_errors(ctx))
 
 
+def scal3ZeroBlocks(like):
+    """(pass A, pass B) thread blocks of the tiled 3-D advectScalar kernels that found their tile all +0.0 since the last call.
+    Counted by the EXPERIMENTS flavour of the library only; the product library reports (0, 0)."""
+    lib, ctx = _context(like)
+    out = (ctypes.c_int64 * 2)()
+    _call(lib, ctx, lib.tfl_scal3_zero_blocks(ctx, out))
+    return int(out[0]), int(out[1])
+
+
 class profile:
     """with tfluids.profile(tensor) as prof: ...; prof.kernels -> {name: {"calls": n, "ms": total}}.
     Per-kernel HIP-event timing inside the library (tfl_profile_begin/end)."""

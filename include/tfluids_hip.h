@@ -96,6 +96,10 @@ int tfl_synchronize(tfl_ctx* ctx);
  * call (the reference CPU build THErrors there, calc_line_trace.cc:325-330,410,421; its CUDA build
  * silently substitutes). Synchronises the stream. Diagnostic only. */
 int64_t tfl_trace_errors(tfl_ctx* ctx);
+/* EXPERIMENTS flavour of the library only (the product library counts nothing and reports 0, 0): blocks[0], blocks[1] = thread
+ * blocks of pass A / pass B of the tiled 3-D advectScalar kernels whose staged tile held nothing but +0.0 and non-fluid cells
+ * (they take the short path) since the last call. Synchronises the stream. Diagnostic only. */
+int tfl_scal3_zero_blocks(tfl_ctx* ctx, int64_t* blocks);
 
 /* Built-in per-kernel timing, the analogue of tfluids.profilePressure (lib/simulate.lua:254-260,
  * 306-318) at kernel granularity: between begin and end every kernel this library launches from the
