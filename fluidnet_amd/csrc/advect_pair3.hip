@@ -6,7 +6,7 @@
 // does not fill the chip for long); a pair costs about what its longer half does. (Two streams do not work for this on this
 // stack -- an event hop costs 12-15 us, tools/ubench/host_costs.hip -- and hipExtAnyOrderLaunch is ignored on gfx9.)
 // The kernels ARE the tile kernels of advect_scalar3.hip (block shape 64 x 4 threads, two planes per thread) and
-// advect_vel3_kz1.inc, called as device functions with the block's place in its launch passed in: same code, same bits
+// the one-plane bodies of advect_vel3_kernels.hpp, called as device functions with the block's place in its launch passed in: same code, same bits
 // (tests/test_hip_simulate.py: the z-slab runs against the un-cut step; tests/test_hip_parity.py against the oracle).
 #include "tfl_advect.hpp"
 #include "tfl_fastmath.hpp"
@@ -15,23 +15,33 @@
 
 #define TFL_SCAL3_NO_ENTRY
 #include "advect_scalar3.hip"      // namespace tfl { namespace { scal3_fwd_body, scal3_bwd_body, Tile, SBlock ... } }
-#ifndef TFL_VEL3_ABL
-#define TFL_VEL3_ABL 0
-#endif
+#include "advect_vel3_kernels.hpp" // namespace tfl { namespace { namespace vel3 { vel3_fwd_body, vel3_bwd_body, VTile, VBlock ... } } }
 
 namespace tfl {
 namespace {
-#include "advect_vel3_kz1.inc"     // namespace kz1 { vel3_fwd_body, vel3_bwd_body, VBlock ... }
+constexpr int kVelTile = 4 * vel3::VTile<1>::LN;                                  // the velocity halves run the one-plane bodies
+constexpr int kPairTileA = Tile<2, 2>::N > kVelTile ? Tile<2, 2>::N : kVelTile;      // floats of LDS: the larger of the two tiles
+constexpr int kPairTileB = Tile<2, 1>::N > kVelTile ? Tile<2, 1>::N : kVelTile;
 
-constexpr int kPairTileA = Tile<2, 2>::N > 4 * kz1::LN ? Tile<2, 2>::N : 4 * kz1::LN;      // floats of LDS: the larger of the two tiles
-constexpr int kPairTileB = Tile<2, 1>::N > 4 * kz1::LN ? Tile<2, 1>::N : 4 * kz1::LN;
+// The stand-alone one-plane kernels, never launched from here. This object has always carried them (their launcher used to be
+// part of the included kernel file), they share the generic slow-path functions of tfl_advect.hpp with the pair kernels, and
+// how the inliner treats those depends on how many callers the module has: without these the pair kernels compile to slightly
+// different code (profiles/advect_vel3_unify.md). Dropping them is a change of its own, to be timed on the slab benchmark.
+#define TFL_PAIR3_KEEP(FAST)                                                                                                      \
+  template __global__ void vel3::k_vel3_fwd<1, FAST>(AdvArgs, const float*, const float*, float*);                               \
+  template __global__ void vel3::k_vel3_bwd_fold<FAST, 0>(AdvArgs, double, const float*, const float*, const float*, float*, BcFoldArg, BuoyFold); \
+  template __global__ void vel3::k_vel3_bwd_fold<FAST, 2>(AdvArgs, double, const float*, const float*, const float*, float*, BcFoldArg, BuoyFold); \
+  template __global__ void vel3::k_vel3_bwd_fold<FAST, 7>(AdvArgs, double, const float*, const float*, const float*, float*, BcFoldArg, BuoyFold);
+TFL_PAIR3_KEEP(true)
+TFL_PAIR3_KEEP(false)
+#undef TFL_PAIR3_KEEP
 
 struct PairGrid { int ns, sgx, sgy, sgz, vgx, vgy, vgz; };      // blocks [0, ns): the scalar pass (sgx x sgy x sgz tiles), the rest: the velocity pass
 
-__device__ __forceinline__ kz1::VBlock vel_block(const PairGrid& g, int m) {
+__device__ __forceinline__ vel3::VBlock vel_block(const PairGrid& g, int m) {
   const int r = m / g.vgx;
   const int z = r / g.vgy;
-  return kz1::VBlock{m - r * g.vgx, r - z * g.vgy, z, g.vgz};
+  return vel3::VBlock{m - r * g.vgx, r - z * g.vgy, z, g.vgz};
 }
 
 template <bool FAST>
@@ -41,7 +51,7 @@ __global__ __launch_bounds__(256) void k_adv3_fwd_pair(PairGrid g, AdvArgs as, c
   __shared__ float tile[kPairTileA];
   const int L = (int)blockIdx.x;      // (block-uniform branch)
   if (L < g.ns) scal3_fwd_body<1, 2, true, FAST>(SBlock{L, g.sgx, g.sgy, g.sgz}, tile, as, s, U, flags, sfwd, bounds);
-  else kz1::vel3_fwd_body<FAST>(vel_block(g, L - g.ns), tile, av, U, flags, vfwd);
+  else vel3::vel3_fwd_body<1, FAST>(vel_block(g, L - g.ns), tile, av, U, flags, vfwd);
 }
 
 template <bool FAST>
@@ -53,7 +63,7 @@ __global__ __launch_bounds__(256) void k_adv3_bwd_pair(PairGrid g, AdvArgs as, d
   __shared__ float tile[kPairTileB];
   const int L = (int)blockIdx.x;
   if (L < g.ns) scal3_bwd_body<1, 2, FAST>(SBlock{L, g.sgx, g.sgy, g.sgz}, tile, as, half_strength, s, U, flags, sfwd, bounds, sdst, fold_s);
-  else kz1::vel3_bwd_body<FAST, 0>(vel_block(g, L - g.ns), tile, av, half_strength, U, flags, vfwd, vdst, fold_v, BuoyFold{nullptr, 0.0f, 0.0f, 0.0f});
+  else vel3::vel3_bwd_body<1, FAST, 0>(vel_block(g, L - g.ns), tile, av, half_strength, U, flags, vfwd, vdst, fold_v, BuoyFold{nullptr, 0.0f, 0.0f, 0.0f});
 }
 
 }  // namespace
@@ -70,7 +80,7 @@ bool advect_pair3(hipStream_t st, const AdvArgs& a0, int B, const float* s, cons
   const int G = (d.n0 + 1) / 2 + (d.nw - d.n0 + 1) / 2;      // scalar: groups of two planes over the window's two runs
   PairGrid g;
   g.sgx = (d.X + TX - 1) / TX; g.sgy = (d.Y + TY - 1) / TY; g.sgz = G * B; g.ns = g.sgx * g.sgy * g.sgz;
-  g.vgx = (d.X + kz1::TX - 1) / kz1::TX; g.vgy = (d.Y + kz1::TY - 1) / kz1::TY; g.vgz = d.nw * B;
+  g.vgx = (d.X + vel3::TX - 1) / vel3::TX; g.vgy = (d.Y + vel3::TY - 1) / vel3::TY; g.vgz = d.nw * B;
   const long long nv = (long long)g.vgx * g.vgy * g.vgz;
   if (g.ns <= 0 || nv <= 0 || g.ns + nv >= (1ll << 31)) return false;
   AdvArgs as = a0, av = a0;

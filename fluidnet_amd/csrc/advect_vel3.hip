@@ -26,29 +26,57 @@
 //    instructions per cell but lost more to block-count quantisation at 128^3 (2048 long blocks on 256 CUs).
 //
 // Algorithmic HBM bytes per cell are unchanged: pass A 28 B (U3, flags -> fwd3), pass B 40 B (fwd3, U3, flags -> dst3).
-#include "tfl_advect.hpp"
-#include "tfl_fastmath.hpp"
+//
+// The kernels themselves are in advect_vel3_kernels.hpp, one source templated on the block depth (planes per block); this file
+// picks the depth and launches them.
+#include "advect_vel3_kernels.hpp"
 
 #include <cstdlib>
 
-// timing ablations (tools/ab_build.sh -DTFL_VEL3_ABL=..): 1 = the tile is filled with constants instead of staged (no staging
-// loads; every lane on the fast path), 2 = pass B's 24 gathers of the forward field replaced by the cell's own value,
-// 4 = no stores
-#ifndef TFL_VEL3_ABL
-#define TFL_VEL3_ABL 0
-#endif
-
 namespace tfl {
 namespace {
-// block depth 1 (a block = 64 x 4 cells of one plane: the round-3 kernels, no loop, 54 / 72 VGPRs, no SGPR spills in pass A)
-#include "advect_vel3_kz1.inc"
-// block depth 2 (two planes per block on one staged tile: 3.1 instead of 4.6 staged words per cell and field, at the price of
-// registers -- 63 / 94 VGPRs, SGPR spills): the better one once the staging traffic leaves the caches
-#define TFL_VEL3_KZ 2
-#define TFL_VEL3_NS kz2
-#include "advect_vel3.inc"
-#undef TFL_VEL3_KZ
-#undef TFL_VEL3_NS
+using namespace vel3;
+
+// launches of block depth KZ (advect_vel3 picks the depth by grid size): 1 = a block is 64 x 4 cells of one plane (the round-3
+// kernels: 54 / 72 VGPRs, no SGPR spills in pass A), 2 = two planes per block on one staged tile (3.1 instead of 4.6 staged words
+// per cell and field, at the price of registers -- 63 / 94 VGPRs, SGPR spills): the better one once the staging traffic leaves
+// the caches. Only the one-plane pass B takes the folds' requests `f` (k_vel3_bwd_fold); a deeper launch leaves them untaken.
+template <int KZ>
+void launch(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* U, const float* flags, float* fwd, float* dst,
+            int stages, Fold& f) {
+  const Dom& d = a.d;
+  const int groups = (d.n0 + KZ - 1) / KZ + (d.nw - d.n0 + KZ - 1) / KZ;      // (KZ = 1: the window's planes, d.nw)
+  const dim3 blk(TX, TY, 1), grd((d.X + TX - 1) / TX, (d.Y + TY - 1) / TY, (unsigned)(groups * B));
+  const bool pa = stages & 2, pb = stages & 4;
+  float* outA = two_pass ? fwd : dst;
+  const double hs = (double)a.strength * 0.5;
+  if (pa) {
+    TFL_TIMED_EXT("k_vel_fwd", st);
+    if (a.fast) TFL_LAUNCH_EXT((k_vel3_fwd<KZ, true>), grd, blk, 0, st, a, U, flags, outA);
+    else TFL_LAUNCH_EXT((k_vel3_fwd<KZ, false>), grd, blk, 0, st, a, U, flags, outA);
+  }
+  if (two_pass && pb) {
+    TFL_TIMED_EXT("k_vel_bwd", st);
+    if constexpr (KZ == 1) {
+      const BcFoldArg fold = f.hand_bc();    // pass B writes the operator's result
+      const BuoyFold by = f.hand_buoy();     // ... and may add the buoyancy force that follows it in simulate()
+      const bool y_only = by.rho && by.sx == 0.0f && by.sz == 0.0f && by.sy != 0.0f;
+      if (y_only) {
+        if (a.fast) TFL_LAUNCH_EXT((k_vel3_bwd_fold<true, 2>), grd, blk, 0, st, a, hs, U, flags, (const float*)fwd, dst, fold, by);
+        else TFL_LAUNCH_EXT((k_vel3_bwd_fold<false, 2>), grd, blk, 0, st, a, hs, U, flags, (const float*)fwd, dst, fold, by);
+      } else if (by.rho) {
+        if (a.fast) TFL_LAUNCH_EXT((k_vel3_bwd_fold<true, 7>), grd, blk, 0, st, a, hs, U, flags, (const float*)fwd, dst, fold, by);
+        else TFL_LAUNCH_EXT((k_vel3_bwd_fold<false, 7>), grd, blk, 0, st, a, hs, U, flags, (const float*)fwd, dst, fold, by);
+      } else {
+        if (a.fast) TFL_LAUNCH_EXT((k_vel3_bwd_fold<true, 0>), grd, blk, 0, st, a, hs, U, flags, (const float*)fwd, dst, fold, by);
+        else TFL_LAUNCH_EXT((k_vel3_bwd_fold<false, 0>), grd, blk, 0, st, a, hs, U, flags, (const float*)fwd, dst, fold, by);
+      }
+    } else {
+      if (a.fast) TFL_LAUNCH_EXT((k_vel3_bwd<KZ, true>), grd, blk, 0, st, a, hs, U, flags, (const float*)fwd, dst);
+      else TFL_LAUNCH_EXT((k_vel3_bwd<KZ, false>), grd, blk, 0, st, a, hs, U, flags, (const float*)fwd, dst);
+    }
+  }
+}
 }  // namespace
 
 bool advect_vel3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* U, const float* flags, float* fwd,
@@ -69,10 +97,10 @@ bool advect_vel3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const f
   static const int kzb_env = exp_env("TFL_VEL3_KZ_B") ? atoi(exp_env("TFL_VEL3_KZ_B")) : 0;
   const bool b_shallow = deep && two_pass && (stages & 4) && f.buoy.rho && kzb_env != 2;
   if (deep && b_shallow) {
-    if (stages & 2) kz2::launch(st, two_pass, a, B, U, flags, fwd, dst, stages & ~4);
-    kz1::launch(st, two_pass, a, B, U, flags, fwd, dst, stages & ~2, f);
-  } else if (deep) kz2::launch(st, two_pass, a, B, U, flags, fwd, dst, stages);
-  else kz1::launch(st, two_pass, a, B, U, flags, fwd, dst, stages, f);
+    if (stages & 2) launch<2>(st, two_pass, a, B, U, flags, fwd, dst, stages & ~4, f);
+    launch<1>(st, two_pass, a, B, U, flags, fwd, dst, stages & ~2, f);
+  } else if (deep) launch<2>(st, two_pass, a, B, U, flags, fwd, dst, stages, f);
+  else launch<1>(st, two_pass, a, B, U, flags, fwd, dst, stages, f);
   return true;
 }
 

@@ -1,5 +1,5 @@
 """Per-voxel fp64 error bounds for the trace-based advection operators (advectVel, advectScalar; eulerOurs, maccormackOurs;
-3-D), in the exact and in the tolerance mode of the LDS-tiled kernels (advect_vel3*.inc, advect_scalar3.hip, advect_pair3.hip).
+3-D), in the exact and in the tolerance mode of the LDS-tiled kernels (advect_vel3_kernels.hpp, advect_scalar3.hip, advect_pair3.hip).
 
 advect_vel() / advect_scalar() evaluate the operator in float64 from its definition on the same fp32 inputs and give, beside
 every value, an upper bound on how far an fp32 evaluation in the named arithmetic (`mode`) may lie from it -- running-error

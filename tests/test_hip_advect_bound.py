@@ -12,10 +12,10 @@ reference alone. Here, per scene, operator and method:
   * the z-slab step's fused pair kernels: tests/advect_bound_run.py `slab`.
 
 Which test reaches which FAST = true instantiation:
-  test_both_modes_within_their_bounds       kz1 k_vel3_fwd<true> / k_vel3_bwd<true, ..> (advect_vel3_kz1.inc), launch_a<2, 1, true>,
+  test_both_modes_within_their_bounds       k_vel3_fwd<1, true> / k_vel3_bwd_fold<true, ..> (advect_vel3_kernels.hpp), launch_a<2, 1, true>,
                                             launch_b<1, 2, true> (advect_scalar3.hip): the default shapes of small grids
   test_forced_shapes_..[kz1-scal-1x1]       launch_a<1, 1, true>, launch_b<1, 1, true>
-  test_forced_shapes_..[kz2-scal-1x2]       kz2 k_vel3_fwd<true> / k_vel3_bwd<true> (advect_vel3.inc), launch_a<1, 2, true>
+  test_forced_shapes_..[kz2-scal-1x2]       k_vel3_fwd<2, true> / k_vel3_bwd<2, true> (advect_vel3_kernels.hpp), launch_a<1, 2, true>
   test_forced_shapes_..[kz2-scal-1x4]       launch_a<1, 4, true>, launch_b<1, 4, true> (the 256^3 shapes)
   test_forced_shapes_..[kz1-scal-2x1]       launch_b<2, 1, true>
   test_forced_shapes_..[marched]            zm::launch<true> (advect_scalar3_march.inc, experiments flavour)

@@ -459,7 +459,7 @@ print("ADV_VARIANTS_OK", done)
                               "marched-1-and-64", "marched-scalar-kernels"])
 def test_advection_kernel_variants_are_bit_exact(env):
     """The advection kernels pick their block shape from the grid size: from 6 M cells per batch item on (256^3, BASELINE
-    config 5) advectVel runs two planes per block (advect_vel3.inc, kz2) and advectScalar's pass A four planes per thread
+    config 5) advectVel runs two planes per block (advect_vel3_kernels.hpp, KZ = 2) and advectScalar's pass A four planes per thread
     (advect_scalar3.hip <1, 4>). The golden / oracle tests above run small grids and would never see those kernels, so
     the variants are FORCED here (TFL_VEL3_KZ, TFL_SCAL3_TZ; read once per process: child processes) onto small ragged
     grids -- partial 64 x 4 tiles, odd plane counts against the 2- and 4-plane blocks, B = 2, obstacles, stick and empty

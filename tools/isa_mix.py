@@ -11,7 +11,7 @@ if "--" in args:
 loops = "--loops" in args
 args = [a for a in args if a != "--loops"]
 src = args[0]; pat = args[1] if len(args) > 1 else "."
-flags = ["-fno-slp-vectorize"] if src in ("advect.hip", "advect_vel3.hip", "advect_scalar3.hip") else []
+flags = ["-fno-slp-vectorize"] if src in ("advect.hip", "advect_vel3.hip", "advect_scalar3.hip", "advect_pair3.hip") else []
 out = tempfile.mktemp(suffix=".s")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
                        "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only", "-x", "hip",

@@ -5,7 +5,7 @@ rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 names = [r["Kernel_Name"] for r in rows]
 # the steady part: from the first k_project after 200 kernels on
-k = [(r["Kernel_Name"].replace("(anonymous namespace)::", "").replace("void ", "").replace("tfl::", "").replace("kz1::", "").replace("kz2::", "").split("(")[0], int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows]
+k = [(r["Kernel_Name"].replace("(anonymous namespace)::", "").replace("void ", "").replace("tfl::", "").replace("vel3::", "").split("(")[0], int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows]
 k = [x for x in k if x[0].startswith("k_")]
 gaps = collections.defaultdict(list)
 busy = 0

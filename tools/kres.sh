@@ -3,7 +3,7 @@
 # usage: tools/kres.sh <file.hip> [grep pattern] [extra hipcc flags]
 f=$1; pat=${2:-.}; shift; shift
 cd "$(dirname "$0")/../fluidnet_amd/csrc"
-extra=""; case $f in advect.hip|advect_vel3.hip|advect_scalar3.hip) extra="-fno-slp-vectorize";; esac
+extra=""; case $f in advect.hip|advect_vel3.hip|advect_scalar3.hip|advect_pair3.hip) extra="-fno-slp-vectorize";; esac      # (as the Makefile)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Wno-unused-function $extra -I../../include "$@" \
   -Rpass-analysis=kernel-resource-usage -x hip -c -o /dev/null "$f" 2>&1 |
   python3 -c '

@@ -23,7 +23,7 @@ def short(name):
     if not m:
         return None
     k, targs = m.group(1), m.group(2) or ""
-    k = {"k_vel3_fwd": "k_vel_fwd", "k_vel3_bwd": "k_vel_bwd", "k_vort_pipe": "k_vort_fused", "k_bcs_div_stats_code": "k_bcs_div_stats"}.get(k, k)     # profiler names of advect_vel3.hip's launches; the pipelined fused confinement
+    k = {"k_vel3_fwd": "k_vel_fwd", "k_vel3_bwd": "k_vel_bwd", "k_vel3_bwd_fold": "k_vel_bwd", "k_vort_pipe": "k_vort_fused", "k_bcs_div_stats_code": "k_bcs_div_stats"}.get(k, k)     # profiler names of advect_vel3.hip's launches; the pipelined fused confinement
     if k == "k_conv3_mfma":
         a = [t.strip() for t in targs.strip("<>").split(",")]
         return "k_conv3_mfma_in" if a[1] == "true" else ("k_conv3_mfma_tail" if a[2] == "true" else "k_conv3_mfma")
