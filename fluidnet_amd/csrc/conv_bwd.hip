@@ -1,0 +1,212 @@
+// conv_bwd.hip -- parameter gradients of the projection ConvNet's convolution layers (gfx950): what
+// cudnn.{Spatial,Volumetric}Convolution:accGradParameters computes for the reference's model:backward
+// (torch/lib/run_epoch.lua:207-235), for the stride-1, zero-padded cross-correlation of conv.hip.
+//
+//   gradWeight[co][ci][tap] = sum over (b, pos) of x[ci][pos + tap] * g_pre[co][pos],   gradBias[co] = sum of g_pre[co][pos]
+//   g_pre = g_out (.) act'(y), y the layer's saved post-activation output
+//
+// i.e. a GEMM with M = cin * taps rows (plus one row of ones: the bias rides in the same launch), N = cout columns and the
+// reduction over every voxel of every batch item. gfx950's fp32 MFMA runs at the fp32 vector rate, so this is an LDS-tiled
+// vector-ALU kernel: k_conv_wgrad stages a 32 x 8 tile of x with its halo and the tile's (masked) g once per chunk, every
+// thread owns one row and a register block of output channels and runs an fp32 fmaf chain over the tile's voxels; after each
+// tile the chain goes into the thread's fp64 sums. A block walks its tiles in a fixed order, adds the threads that shared a
+// row in a fixed order and leaves its sums at a fixed place; k_conv_wgrad_finish adds the blocks' partials in a fixed order in
+// fp64, rounds once to fp32, accumulates (one fp32 add) or overwrites, and writes the cudnn layout. No atomics: the same
+// inputs give the same bits on every call.
+//
+// The activation mask is applied where g is read; with `wb` the masked value is also written back over g, so that the data
+// gradient that follows (conv_direct on the transposed, mirrored weights) reads g_pre without a launch of its own.
+#include "tfl_device.hpp"
+#include "tfl_host.hpp"
+#include "tfl_train.hpp"
+
+namespace tfl {
+
+struct WgArgs {
+  const float* x;       // the layer's input [B][cin][Z][Y][X]
+  float* g;             // the gradient at the layer's output [B][cout][Z][Y][X]
+  const float* y;       // the saved post-activation output [B][ych][Z][Y][X] (act != 0)
+  double* partials;     // [block][cin * taps + 1][cout]
+  int Z, Y, X, cin, cout, k, taps, ych, act, wb, is3d;
+  int ch, tt, S, ntx, nty;
+  long long tiles;
+};
+
+// act'(y) from the saved output: ReLU y > 0, ReLU6 0 < y < 6, sigmoid y (1 - y)
+__device__ __forceinline__ float act_grad(float g, float y, int act) {
+  if (act == 1) return y > 0.0f ? g : 0.0f;
+  if (act == 2) return (y > 0.0f && y < 6.0f) ? g : 0.0f;
+  return g * (y * (1.0f - y));
+}
+
+template <int CB>
+__global__ __launch_bounds__(kWgThreads) void k_conv_wgrad(WgArgs a) {
+  extern __shared__ float lds[];
+  const int tid = threadIdx.x;
+  const WgHalo h = wg_halo(a.is3d != 0, a.k);
+  float* xs = lds;                        // [ch][HZ][HY][HX]
+  float* gs = lds + a.ch * h.floats;      // [voxel][CB]
+  const long long cells = (long long)a.Z * a.Y * a.X;
+  const int M = a.cin * a.taps;
+  const int vx = tid % kWgTX, vy = tid / kWgTX;      // the voxel this thread stages g for
+  for (int co0 = 0; co0 < a.cout; co0 += CB)
+    for (int ci0 = 0; ci0 < a.cin; ci0 += a.ch)
+      for (int t0 = 0; t0 < a.taps; t0 += a.tt) {
+        const WgChunk ck = wg_chunk(a.ch, a.tt, a.cin, a.taps, ci0, t0);      // (its first chunk carries the bias row and masks g)
+        const WgThread t = wg_thread(tid, ck, h, a.S, ci0, t0, a.k, a.taps, a.is3d != 0, M);
+        const bool mask_now = a.act != 0 && (!a.wb || ck.first);
+        double acc64[CB];
+#pragma unroll
+        for (int c = 0; c < CB; c++) acc64[c] = 0.0;
+        for (long long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+          const int tx = (int)(tile % a.ntx);
+          long long q = tile / a.ntx;
+          const int ty = (int)(q % a.nty); q /= a.nty;
+          const int z = (int)(q % a.Z), b = (int)(q / a.Z);
+          const int x0 = tx * kWgTX, y0 = ty * kWgTY;
+          for (int e = tid; e < ck.nch * h.floats; e += kWgThreads) {
+            const int c = e / h.floats, hh = e - c * h.floats;
+            const int hx = hh % h.HX, hy = (hh / h.HX) % h.HY, hz = hh / (h.HX * h.HY);
+            const int gx = x0 + hx - h.r, gy = y0 + hy - h.r, gz = z + hz - h.rz;
+            const bool ok = gx >= 0 && gx < a.X && gy >= 0 && gy < a.Y && gz >= 0 && gz < a.Z;
+            xs[e] = ok ? a.x[((long long)b * a.cin + ci0 + c) * cells + ((long long)gz * a.Y + gy) * a.X + gx] : 0.0f;
+          }
+          {
+            const int gx = x0 + vx, gy = y0 + vy;
+            const bool ok = gx < a.X && gy < a.Y;
+            const long long o = ((long long)z * a.Y + gy) * a.X + gx;
+#pragma unroll
+            for (int c = 0; c < CB; c++) {
+              float v = 0.0f;
+              if (ok) {
+                float* gp = a.g + ((long long)b * a.cout + co0 + c) * cells + o;
+                v = *gp;
+                if (mask_now) {
+                  v = act_grad(v, a.y[((long long)b * a.ych + co0 + c) * cells + o], a.act);
+                  if (a.wb) *gp = v;
+                }
+              }
+              gs[wg_g_slot(tid, CB, c)] = v;
+            }
+          }
+          __syncthreads();
+          if (t.active) {
+            float acc[CB];
+#pragma unroll
+            for (int c = 0; c < CB; c++) acc[c] = 0.0f;
+            for (int v = t.s; v < kWgThreads; v += a.S) {
+              const float xv = t.is_bias ? 1.0f : xs[wg_x_slot(t, h, v)];
+#pragma unroll
+              for (int c = 0; c < CB; c++) acc[c] = fmaf(xv, gs[wg_g_slot(v, CB, c)], acc[c]);
+            }
+#pragma unroll
+            for (int c = 0; c < CB; c++) acc64[c] += (double)acc[c];
+          }
+          __syncthreads();
+        }
+        // the slices of a row, added in slice order (the tile loop ended on a barrier: the LDS is free)
+        if (a.S > 1) {
+          double* red = reinterpret_cast<double*>(lds);      // [slice][row of the chunk][CB]
+          if (t.active) {
+#pragma unroll
+            for (int c = 0; c < CB; c++) red[wg_red_slot(t, ck, t.s, CB, c)] = acc64[c];
+          }
+          __syncthreads();
+          if (t.active && t.s == 0) {
+            for (int q = 1; q < a.S; q++) {
+#pragma unroll
+              for (int c = 0; c < CB; c++) acc64[c] += red[wg_red_slot(t, ck, q, CB, c)];
+            }
+          }
+          __syncthreads();
+        }
+        if (t.active && t.s == 0) {
+#pragma unroll
+          for (int c = 0; c < CB; c++) a.partials[wg_partial_slot((int)blockIdx.x, M, t.row, a.cout, co0 + c)] = acc64[c];
+        }
+      }
+}
+
+// The blocks' partials of 32 (row, co) results per block of 32 x 8 threads, in fp64 and in a fixed order: lane y adds the
+// partials y, y + 8, ... in ascending order, lane 0 then adds the eight lanes in order; then the cudnn layout.
+__global__ __launch_bounds__(256) void k_conv_wgrad_finish(const double* __restrict__ partials, int P, int M, int cout, int taps, int cin,
+                                                           int cin_ref, int cout_ref, int skip_in, float* __restrict__ gw,
+                                                           float* __restrict__ gb, int accumulate) {
+  __shared__ double sh[8][33];
+  const int total = (M + 1) * cout;
+  const int o = blockIdx.x * 32 + threadIdx.x;
+  double s = 0.0;
+  if (o < total)
+    for (int p = threadIdx.y; p < P; p += 8) s += partials[wg_partial_slot(p, M, 0, cout, o)];      // (row * cout + co = o)
+  sh[threadIdx.y][threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.y != 0 || o >= total) return;
+  for (int q = 1; q < 8; q++) s += sh[q][threadIdx.x];
+  const int row = o / cout, co = o - row * cout;
+  const float f = (float)s;
+  float* dst;
+  if (row == M) {
+    if (co >= cout_ref) return;
+    dst = gb + co;
+  } else {
+    const long long i = wg_cudnn_index(row, co, taps, cin, cin_ref, cout_ref, skip_in);
+    if (i < 0) return;
+    dst = gw + i;
+  }
+  *dst = accumulate ? *dst + f : f;
+}
+
+// (model.hip scale_from_stats, restated: the input scale of batch item b from its (sum, sum of squares) pair)
+__device__ __forceinline__ float tape_scale(const double* __restrict__ stats, int b, double n) {
+  const double s1 = stats[b * 2], s2 = stats[b * 2 + 1];
+  return (float)sqrt(fmax(n * s2 - s1 * s1, 0.0) / (n * (n - 1.0)));
+}
+
+// dst[b][t] = scale_b * src[b][t] (+ add[b][t]); dst may be add
+__global__ __launch_bounds__(256) void k_scale_add(long long per, const double* __restrict__ stats, double count, const float* __restrict__ src,
+                                                   const float* add, float* dst) {
+  const int b = blockIdx.y;
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= per) return;
+  const long long o = (long long)b * per + t;
+  const float v = tape_scale(stats, b, count) * src[o];
+  dst[o] = add ? v + add[o] : v;
+}
+
+void scale_add(hipStream_t st, int B, long long per, const double* stats, double count, const float* src, const float* add, float* dst) {
+  TFL_TIMED("k_scale_add", st);
+  k_scale_add<<<dim3((unsigned)((per + 255) / 256), (unsigned)B), 256, 0, st>>>(per, stats, count, src, add, dst);
+}
+
+bool conv_wgrad_fits(const WgPlan& p) { return p.lds_floats <= 16384; }
+
+bool conv_wgrad(hipStream_t st, bool is3d, const WgPlan& p, int B, int Z, int Y, int X, int cin, int cout, int k, const float* x,
+                float* g, const float* y, int ych, int act, bool wb, double* partials) {
+  if (!conv_wgrad_fits(p)) return false;
+  (void)B;
+  WgArgs a;
+  a.x = x; a.g = g; a.y = y; a.partials = partials;
+  a.Z = Z; a.Y = Y; a.X = X; a.cin = cin; a.cout = cout; a.k = k; a.taps = p.taps; a.ych = ych; a.act = y ? act : 0; a.wb = wb ? 1 : 0;
+  a.is3d = is3d ? 1 : 0;
+  a.ch = p.ch; a.tt = p.tt; a.S = p.S; a.ntx = (X + kWgTX - 1) / kWgTX; a.nty = (Y + kWgTY - 1) / kWgTY; a.tiles = p.tiles;
+  const size_t shmem = sizeof(float) * (size_t)p.lds_floats;
+  TFL_TIMED("k_conv_wgrad", st);
+  switch (p.cb) {
+    case 1: k_conv_wgrad<1><<<p.nblocks, kWgThreads, shmem, st>>>(a); return true;
+    case 2: k_conv_wgrad<2><<<p.nblocks, kWgThreads, shmem, st>>>(a); return true;
+    case 4: k_conv_wgrad<4><<<p.nblocks, kWgThreads, shmem, st>>>(a); return true;
+    case 8: k_conv_wgrad<8><<<p.nblocks, kWgThreads, shmem, st>>>(a); return true;
+    case 16: k_conv_wgrad<16><<<p.nblocks, kWgThreads, shmem, st>>>(a); return true;
+    default: return false;
+  }
+}
+
+void conv_wgrad_finish(hipStream_t st, const WgPlan& p, int cin, int cout, int cin_ref, int cout_ref, int skip_in, const double* partials,
+                       float* gw, float* gb, int accumulate) {
+  const int M = cin * p.taps;
+  TFL_TIMED("k_conv_wgrad_finish", st);
+  k_conv_wgrad_finish<<<((M + 1) * cout + 31) / 32, dim3(32, 8), 0, st>>>(partials, p.nblocks, M, cout, p.taps, cin, cin_ref, cout_ref,
+                                                                        skip_in, gw, gb, accumulate);
+}
+
+}  // namespace tfl

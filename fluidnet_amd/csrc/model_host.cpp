@@ -10,8 +10,9 @@
 
 #include "tfl_abi.hpp"
 #include "tfl_ops.hpp"
+#include "tfl_train.hpp"
 
-using tfl::fail; using tfl::check_flags;
+using tfl::fail; using tfl::check_flags; using tfl::check_vel; using tfl::check_scalar; using tfl::check_launch;
 
 struct tfl_layer {
   int cin = 0, cout = 0, k = 0;
@@ -24,6 +25,12 @@ struct tfl_layer {
   // graph models only
   int dil = 1;         // dilation (banksType 'dilate': 2^(bank - 1))
   float* bn = nullptr; // device, the folded batch norm after this module: scale[cout] then shift[cout]
+  // what the module's cudnn weight looked like (tfl_model_set_weights lays a new one out the same way): its channel counts,
+  // whether its last input channel is the joined skip channel, and (join_c > 0) that input channel ci sits on plane
+  // (ci / join_c) * join_p + ci % join_c -- the concat of the banks
+  int cin_ref = 0, cout_ref = 0, join_c = 0, join_p = 0;
+  bool skip_in = false;
+  float* wt = nullptr; // device, trainable models, every layer but the first: the data-gradient form [tap][cout][cin] (tfl_train.hpp)
 };
 // The forward a model runs (tfl_model_finish dispatches on it), named after its kernel file; TFL_CONV_PATH at creation picks
 // it for the 3-D `default` topology (3->8 k3, 8->8 k3, 8->8 k3, 8->8 k1, 8->1 k1), and "direct" = generic for both defaults.
@@ -65,6 +72,7 @@ struct tfl_model {
   tfl_model_opts opts = {1, 0, 1, 1, TFL_NORM_UDIV, TFL_NORMFUNC_STD, TFL_NONLIN_RELU, 0};
   bool custom = false;
   int in_c = 3;               // net input channels
+  float* zero_bias = nullptr; // 64 zeros: the bias of the data-gradient convolutions (tfl_model_backward)
   // graph models: banks / batch norm / max pooling (shape-generic kernels, un-sharded)
   int banks = 1, bank_type = TFL_BANKS_MRES, aggregate = TFL_AGG_CONCAT, split = 0, join = 0, nstages = 0;
   bool pool_max = false;
@@ -106,9 +114,11 @@ static bool model_opts_of(tfl_ctx* c, int nlayers, const int32_t* pool, const in
 }
 
 // the layer table and weight packing of tfl_model_create_opts / _graph (C++ linkage: templates)
-// a new device buffer holding `bytes` host bytes; false on failure (what was allocated goes with the model)
+// `bytes` host bytes into the device buffer dst, allocated here when dst is null (creation; tfl_model_set_weights refills it
+// in place); false on failure (what was allocated goes with the model)
 template <class T> bool upload(T*& dst, const void* src, size_t bytes) {
-  return hipMalloc((void**)&dst, bytes) == hipSuccess && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+  if (!dst && hipMalloc((void**)&dst, bytes) != hipSuccess) return false;
+  return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
 }
 
 // Where the conv modules sit in lib/model.lua's stage table: module i is bank bank[i] of stage stage[i] (1-based), and stage s
@@ -131,22 +141,23 @@ StageTable stage_table(int nst, int banks = 1, int split = 0, int join = 0) {
   return t;
 }
 
-// A module's cudnn weight [cout*S][cin][taps] (output channel index = o*S + sub) -> [sub][tap][cin_p][cout_p], reference input
-// channel ci on plane cmap(ci), and its bias [cout*S] -> [sub][cout_p], uploaded into L (the padding holds zeros)
-template <class Map>
-bool upload_layer(tfl_layer& L, bool is3d, int ci_n, int co_n, const float* w, const float* b, Map cmap) {
+// A module's cudnn weight [cout*S][cin][taps] (output channel index = o*S + sub) -> [sub][tap][cin_p][cout_p] and its bias
+// [cout*S] -> [sub][cout_p] (tfl_train.hpp relay_layer; the padding holds zeros), uploaded into L -- at creation, and again by
+// tfl_model_set_weights into the same buffers. transposed: also the data-gradient form L.wt (every layer but the first of a
+// model tfl_model_backward takes).
+bool upload_layer(tfl_layer& L, bool is3d, const float* w, const float* b, bool transposed) {
   const int taps = is3d ? L.k * L.k * L.k : L.k * L.k;
   const int S = is3d ? L.up * L.up * L.up : L.up * L.up;
-  std::vector<float> relaid((size_t)S * taps * L.cin * L.cout, 0.0f);
-  for (int sub = 0; sub < S; sub++)
-    for (int co = 0; co < co_n; co++)
-      for (int ci = 0; ci < ci_n; ci++)
-        for (int t = 0; t < taps; t++)
-          relaid[(((size_t)sub * taps + t) * L.cin + cmap(ci)) * L.cout + co] = w[(((size_t)co * S + sub) * ci_n + ci) * taps + t];
-  std::vector<float> bias_p((size_t)S * L.cout, 0.0f);
-  for (int sub = 0; sub < S; sub++)
-    for (int co = 0; co < co_n; co++) bias_p[(size_t)sub * L.cout + co] = b[(size_t)co * S + sub];
-  return upload(L.w, relaid.data(), relaid.size() * sizeof(float)) && upload(L.b, bias_p.data(), bias_p.size() * sizeof(float));
+  auto cmap = [&](int ci) {
+    return (L.skip_in && ci == L.cin_ref - 1) ? L.cin - 1 : L.join_c > 0 ? (ci / L.join_c) * L.join_p + ci % L.join_c : ci;
+  };
+  std::vector<float> relaid, bias_p;
+  tfl::relay_layer(S, taps, L.cin, L.cout, L.cin_ref, L.cout_ref, w, b, cmap, relaid, bias_p);
+  if (!upload(L.w, relaid.data(), relaid.size() * sizeof(float)) || !upload(L.b, bias_p.data(), bias_p.size() * sizeof(float))) return false;
+  if (!transposed) return true;
+  std::vector<float> wt;
+  tfl::relay_transposed(taps, L.cin, L.cout, L.cin - (L.skip_in ? 1 : 0), relaid.data(), wt);
+  return upload(L.wt, wt.data(), wt.size() * sizeof(float));
 }
 
 // batch norm after hidden module i, folded in double: scale = w / sqrt(var + eps), shift = b - mean * scale, each rounded once
@@ -230,12 +241,12 @@ tfl_model* build_layers(tfl_ctx* c, bool is3d, int n, const int32_t* cin, const 
     if (cp < 0) return cleanup("unsupported output channel count (at most 64)");
     L.cin = cin_p; L.cout = cp; L.k = ksize[i];
     // reference input channel ci -> its plane in the padded layout (banks' slices prev_p apart; the skip channel last)
-    const int C = st == 1 ? in_c : cout[t.first[st - 1]];
-    auto cmap = [&](int ci) { return (skip_in && ci == cin[i] - 1) ? cin_p - 1 : joined ? (ci / C) * prev_p + ci % C : ci; };
+    L.cin_ref = cin[i]; L.cout_ref = cout[i]; L.skip_in = skip_in;
+    if (joined) { L.join_c = cout[t.first[st - 1]]; L.join_p = prev_p; }
     const bool has_bn = g && g->batch_norm && !last;
     if (has_bn && (!g->bn_mean[i] || !g->bn_var[i])) { m->layers.push_back(L); return cleanup("addBatchNorm: a module lacks running_mean / running_var"); }
     const std::vector<float> bn = has_bn ? bn_fold(g, i, cout[i], cp) : std::vector<float>();
-    const bool ok = upload_layer(L, is3d, cin[i], cout[i], weights[i], biases[i], cmap) &&
+    const bool ok = upload_layer(L, is3d, weights[i], biases[i], false) &&
                     (bn.empty() || upload(L.bn, bn.data(), bn.size() * sizeof(float)));
     m->layers.push_back(L);
     if (!ok) return cleanup("uploading weights failed");
@@ -245,6 +256,12 @@ tfl_model* build_layers(tfl_ctx* c, bool is3d, int n, const int32_t* cin, const 
   if (down != 1) return cleanup("the layers do not return to the grid resolution (pool / up factors)");
   if (N > 1 && t.mres) m->multires = true;
   if (m->max_c < 1) m->max_c = 1;
+  if (!g && !m->multires) {     // a model tfl_model_backward takes: the data-gradient weights and the zero bias of their convolutions
+    const std::vector<float> zeros(64, 0.0f);
+    bool ok = upload(m->zero_bias, zeros.data(), zeros.size() * sizeof(float));
+    for (int i = 1; i < n && ok; i++) ok = upload_layer(m->layers[i], is3d, weights[i], biases[i], true);
+    if (!ok) return cleanup("uploading weights failed");
+  }
   return m;
 }
 
@@ -283,14 +300,16 @@ const char* pack_default3(tfl_model* m, const int32_t* cin, const float* const* 
       if (l == 2) m->post16_tail = tfl::conv3_m16_pack_tail(weights[3], fr.data());     // the 8 -> 8 (k = 1) layer's A fragment
       if (!upload(m->wfrag16[l], fr.data(), fr.size() * sizeof(uint16_t))) return "uploading fp16 MFMA weight fragments failed";
     }
-    if (hipMalloc((void**)&m->d_range_err, sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(m->d_range_err, 0, sizeof(unsigned long long)) != hipSuccess)
-      return "hipMalloc failed";
-    // the word a later call reads without a sync; failing to get mapped memory only loses the early warning
-    if (hipHostMalloc((void**)&m->h_range, sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
-      *m->h_range = 0;
-      if (hipHostGetDevicePointer((void**)&m->d_range_host, m->h_range, 0) != hipSuccess) { (void)hipHostFree(m->h_range); m->h_range = nullptr; m->d_range_host = nullptr; }
-    } else m->h_range = nullptr;
+    if (!m->d_range_err) {      // (once: tfl_model_set_weights packs again and keeps the words)
+      if (hipMalloc((void**)&m->d_range_err, sizeof(unsigned long long)) != hipSuccess ||
+          hipMemset(m->d_range_err, 0, sizeof(unsigned long long)) != hipSuccess)
+        return "hipMalloc failed";
+      // the word a later call reads without a sync; failing to get mapped memory only loses the early warning
+      if (hipHostMalloc((void**)&m->h_range, sizeof(unsigned long long), hipHostMallocMapped) == hipSuccess) {
+        *m->h_range = 0;
+        if (hipHostGetDevicePointer((void**)&m->d_range_host, m->h_range, 0) != hipSuccess) { (void)hipHostFree(m->h_range); m->h_range = nullptr; m->d_range_host = nullptr; }
+      } else m->h_range = nullptr;
+    }
   }
   if (path == ConvPath::conv_mfma) return nullptr;
   std::vector<float> tp(8 + 64 + 8 + 8 + 1 + 1);
@@ -594,7 +613,8 @@ void forward_mfma2d(const tfl_model* m, const ModelWs& w, const Fwd& a) {
 // Every other linear model, layer by layer on the shape-generic kernels. The planes of every launch: the whole grid, or (a
 // z-window [za, zb) on a 3-D model: a z-slab rank's owned planes) the cone of the planes the velocity update reads, layer by
 // layer (model_cone).
-int generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a) {
+// outs (tfl_model_forward_train): where each layer's output goes instead of the act[] ping-pong -- the tape.
+int generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a, float* const* outs = nullptr) {
   hipStream_t st = a.st;
   const int B = a.B, Z = a.Z, Y = a.Y, X = a.X;
   const bool windowed = a.sc.windowed();
@@ -627,7 +647,7 @@ int generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd&
     const tfl_layer& L = m->layers[l];
     const bool last = l + 1 == nl;
     const bool joins_skip = m->opts.pressure_skip && l + 2 == nl;
-    float* out = last ? w.pPred : (in == w.act[0] ? w.act[1] : w.act[0]);
+    float* out = outs ? outs[l] : last ? w.pPred : (in == w.act[0] ? w.act[1] : w.act[0]);
     const int taps = m->is3d ? L.k * L.k * L.k : L.k * L.k;
     const int S = m->is3d ? L.up * L.up * L.up : L.up * L.up;
     if (windowed) span(cone.layer[l].conv_lo, cone.layer[l].conv_hi, cone.layer[l].conv_d, Zc, z0, nz);
@@ -903,7 +923,8 @@ tfl_model* tfl_model_create_graph(tfl_ctx* c, int is3D, int nconv, const int32_t
 void tfl_model_destroy(tfl_ctx* c, tfl_model* m) {
   (void)c;
   if (!m) return;
-  for (auto& L : m->layers) { if (L.w) (void)hipFree(L.w); if (L.b) (void)hipFree(L.b); if (L.bn) (void)hipFree(L.bn); }
+  for (auto& L : m->layers) { if (L.w) (void)hipFree(L.w); if (L.b) (void)hipFree(L.b); if (L.bn) (void)hipFree(L.bn); if (L.wt) (void)hipFree(L.wt); }
+  if (m->zero_bias) (void)hipFree(m->zero_bias);
   for (int l = 0; l < 3; l++) if (m->bfrag[l]) (void)hipFree(m->bfrag[l]);
   for (int l = 0; l < 3; l++) if (m->wino[l]) (void)hipFree(m->wino[l]);
   for (int l = 0; l < 3; l++) if (m->wfrag16[l]) (void)hipFree(m->wfrag16[l]);
@@ -1009,6 +1030,172 @@ int tfl_model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tf
                       float lo, float hi) {
   tfl::Ask none;
   return tfl::model_forward(c, m, pDiv, UDiv, flags, pOut, UOut, workspace, workspace_floats, UBC, UBCInvMask, doClamp, lo, hi, tfl::scope_of(c), none);
+}
+
+}  // extern "C"
+
+// ---- the training side: new weights in place, the forward that keeps a tape, the parameter gradients ----
+namespace {
+// Linear models without pooling / upsampling only (they hold the data-gradient weights: build_layers); the rest is refused by name
+int train_gate(tfl_ctx* c, const tfl_model* m, const char* who) {
+  if (m->path == ConvPath::graph)
+    return fail(c, TFL_EUNSUPPORTED, "%s: graph models (banks, batch norm, max pooling: tfl_model_create_graph) have no training pass", who);
+  if (m->multires || !m->zero_bias)
+    return fail(c, TFL_EUNSUPPORTED, "%s: models with pooling or ConvolutionUpsample layers (`tog`) have no training pass: the "
+                                     "backward of pooling and of the pixel shuffle is not built", who);
+  return TFL_OK;
+}
+std::vector<tfl::TrainLayer> train_layers(const tfl_model* m) {
+  std::vector<tfl::TrainLayer> v;
+  for (const tfl_layer& L : m->layers) v.push_back(tfl::TrainLayer{L.cin, L.cout, L.cin_ref, L.cout_ref, L.k, L.skip_in ? 1 : 0});
+  return v;
+}
+// the `count` that goes with the model's input-scale pair (opts_stats; tfl_model_forward's own for the default normaliser)
+double scale_count(const tfl_model* m, int Z, int Y, int X) {
+  const tfl_model_opts& o = m->opts;
+  const double cells = (double)Z * Y * X;
+  if (!o.normalize || o.norm_func == TFL_NORMFUNC_L2) return 2.0;
+  return o.norm_chan == TFL_NORM_UDIV ? cells * (m->is3d ? 3 : 2) : cells;
+}
+int check_tape(tfl_ctx* c, const char* who, const tfl::TapeLayout& t, const float* tape, int64_t tape_floats) {
+  if (!tape || tape_floats < t.total) return fail(c, TFL_EINVAL, "%s: tape too small (%lld floats needed)", who, (long long)t.total);
+  if (((uintptr_t)tape & 7) != 0) return fail(c, TFL_EINVAL, "%s: tape must be 8-byte aligned", who);
+  return TFL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tfl_model_set_weights(tfl_ctx* c, tfl_model* m, const float* const* weights, const float* const* biases) {
+  if (!c) return TFL_EINVAL;
+  if (!m || !weights || !biases) return fail(c, TFL_EINVAL, "model_set_weights: null model or weight table");
+  const int n = (int)m->layers.size();
+  for (int l = 0; l < n; l++)
+    if (!weights[l] || !biases[l]) return fail(c, TFL_EINVAL, "model_set_weights: layer %d has no weight or no bias", l);
+  // every launch that reads the old weights is done before they change; the copies below are synchronous
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int l = 0; l < n; l++)
+    if (!upload_layer(m->layers[l], m->is3d, weights[l], biases[l], m->layers[l].wt != nullptr))
+      return fail(c, TFL_EHIP, "model_set_weights: uploading layer %d failed", l);
+  std::vector<int32_t> cin;
+  for (const tfl_layer& L : m->layers) cin.push_back(L.cin_ref);
+  const char* err = nullptr;
+  if (default3(m->path)) err = pack_default3(m, cin.data(), weights, biases, m->path);
+  else if (m->path == ConvPath::conv2d_mfma) err = pack_default2(m, cin.data(), weights);
+  if (err) return fail(c, TFL_EHIP, "model_set_weights: %s", err);
+  return TFL_OK;
+}
+
+int64_t tfl_model_tape_floats(const tfl_model* m, int B, int Z, int Y, int X) {
+  if (!m || m->path == ConvPath::graph || !m->zero_bias || B < 1 || Z < 1 || Y < 1 || X < 1) return -1;
+  return tfl::tape_layout(train_layers(m), B, Z, Y, X).total;
+}
+
+int tfl_model_forward_train(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
+                            const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace, int64_t workspace_floats, float* tape,
+                            int64_t tape_floats) {
+  const char* who = "model_forward_train";
+  TRY(check_flags(c, who, flags));
+  if (!m) return fail(c, TFL_EINVAL, "%s: null model", who);
+  TRY(train_gate(c, m, who));
+  const int is3D = m->is3d ? 1 : 0;
+  TRY(check_vel(c, who, "UDiv", UDiv, flags, is3D));
+  TRY(check_vel(c, who, "UOut", UOut, flags, is3D));
+  TRY(check_scalar(c, who, "pDiv", pDiv, flags));
+  TRY(check_scalar(c, who, "pOut", pOut, flags));
+  const tfl::Scope sc = tfl::scope_of(c);
+  if (sc.stages || sc.windowed()) return fail(c, TFL_EINVAL, "%s: clear the z-window / stage mask first", who);
+  const int B = flags->B, Z = flags->Z, Y = flags->Y, X = flags->X;
+  const tfl::TapeLayout t = tfl::tape_layout(train_layers(m), B, Z, Y, X);
+  TRY(check_tape(c, who, t, tape, tape_floats));
+  ModelWs w;
+  TRY(model_ws(c, m, flags, workspace, workspace_floats, &w));
+  // the same calls as tfl_model_forward of a model on the shape-generic path, with the tape in place of the activation buffers
+  tfl::Ask ask;
+  ask.gated = false;       // (fp32 throughout: no fp16 range to guard)
+  TRY(tfl::model_begin(c, m, UDiv, flags, UOut, workspace, workspace_floats, 0, Z, nullptr, sc, ask));
+  Fwd a{c->stream, B, Z, Y, X, pDiv->data, UOut->data, flags->data, m->d_stats, (double)Z * Y * X * (m->is3d ? 3 : 2), sc, false};
+  if (m->custom) TRY(opts_stats(c, m, w, a));
+  w.x3 = tape + t.x; w.pPred = tape + t.pPred;
+  std::vector<float*> outs;
+  for (size_t l = 0; l < m->layers.size(); l++) outs.push_back(l + 1 < m->layers.size() ? tape + t.out[l] : w.pPred);
+  TRY(generic_forward(c, m, w, a, outs.data()));
+  tfl::model_project(a.st, sc, m->is3d, B, Z, Y, X, w.pPred, flags->data, a.st_in, a.count, UOut->data, pOut->data, nullptr, nullptr, 0,
+                     0.0f, 0.0f, nullptr, nullptr, nullptr, nullptr, nullptr, wall_code_of(c, m, flags), nullptr, ask.fold);
+  HIP_TRY(c, hipMemcpyAsync(tape + t.stats, m->d_stats, sizeof(double) * 2 * B, hipMemcpyDeviceToDevice, c->stream));
+  return check_launch(c, who);
+}
+
+int64_t tfl_model_backward_workspace_floats(const tfl_model* m, int B, int Z, int Y, int X) {
+  if (!m || m->path == ConvPath::graph || !m->zero_bias || B < 1 || Z < 1 || Y < 1 || X < 1) return -1;
+  return tfl::bwd_layout(m->is3d, train_layers(m), B, Z, Y, X).total;
+}
+
+int tfl_model_backward(tfl_ctx* c, tfl_model* m, const tfl_tensor* flags, const tfl_tensor* gradP, const tfl_tensor* gradU,
+                       const float* tape, int64_t tape_floats, float* workspace, int64_t workspace_floats, float* const* gradWeights,
+                       float* const* gradBiases, int accumulate) {
+  const char* who = "model_backward";
+  TRY(check_flags(c, who, flags));
+  if (!m) return fail(c, TFL_EINVAL, "%s: null model", who);
+  TRY(train_gate(c, m, who));
+  const int is3D = m->is3d ? 1 : 0;
+  if (gradP) TRY(check_scalar(c, who, "gradP", gradP, flags));
+  if (gradU) TRY(check_vel(c, who, "gradU", gradU, flags, is3D));
+  if (!is3D && flags->Z != 1) return fail(c, TFL_EINVAL, "%s: 2D model but zdepth > 1", who);
+  const int B = flags->B, Z = flags->Z, Y = flags->Y, X = flags->X;
+  if (B > kMaxBatch) return fail(c, TFL_EINVAL, "%s: batch size above %d", who, kMaxBatch);
+  const std::vector<tfl::TrainLayer> tl = train_layers(m);
+  const int nl = (int)tl.size();
+  const tfl::TapeLayout t = tfl::tape_layout(tl, B, Z, Y, X);
+  TRY(check_tape(c, who, t, tape, tape_floats));
+  const tfl::BwdLayout w = tfl::bwd_layout(m->is3d, tl, B, Z, Y, X);
+  if (!workspace || workspace_floats < w.total)
+    return fail(c, TFL_EINVAL, "%s: workspace too small (%lld floats needed)", who, (long long)w.total);
+  if (((uintptr_t)workspace & 7) != 0) return fail(c, TFL_EINVAL, "%s: workspace must be 8-byte aligned", who);
+  if (!gradWeights || !gradBiases) return fail(c, TFL_EINVAL, "%s: null gradient table", who);
+  for (int l = 0; l < nl; l++) {
+    if (!gradWeights[l] || !gradBiases[l]) return fail(c, TFL_EINVAL, "%s: layer %d has no gradient buffer", who, l);
+    if (!tfl::conv_wgrad_fits(tfl::wg_plan(m->is3d, tl[l], B, Z, Y, X)))
+      return fail(c, TFL_EUNSUPPORTED, "%s: layer %d (k = %d) does not fit the weight-gradient kernel's tile", who, l, tl[l].k);
+  }
+  hipStream_t st = c->stream;
+  const long long cells = (long long)Z * Y * X;
+  const int C = m->is3d ? 3 : 2;
+  const double* stats = (const double*)(tape + t.stats);
+  const double count = scale_count(m, Z, Y, X);
+  float* g = workspace + w.g0;
+  float* g2 = workspace + w.g1;
+  float* gu = workspace + w.gu;
+  double* partials = (double*)(workspace + w.partials);
+  // g_pPred = scale gradP + velocityUpdateBackward(setWallBcsBackward(scale gradU)): the wall mask only zeroes, so the
+  // scale goes in front of it
+  if (gradU) {
+    tfl::scale_add(st, B, cells * C, stats, count, gradU->data, nullptr, gu);
+    tfl::set_wall_bcs(st, m->is3d, B, Z, Y, X, gu, flags->data);
+    tfl::velocity_update_bwd(st, m->is3d, B, Z, Y, X, flags->data, gu, g);
+    if (gradP) tfl::scale_add(st, B, cells, stats, count, gradP->data, g, g);
+  } else if (gradP) {
+    tfl::scale_add(st, B, cells, stats, count, gradP->data, nullptr, g);
+  } else {
+    HIP_TRY(c, hipMemsetAsync(g, 0, sizeof(float) * (size_t)B * cells, st));
+  }
+  const int act = 1 + m->opts.nonlin;
+  for (int l = nl - 1; l >= 0; l--) {
+    const tfl_layer& L = m->layers[l];
+    const tfl::WgPlan p = tfl::wg_plan(m->is3d, tl[l], B, Z, Y, X);
+    const float* x = l == 0 ? tape + t.x : tape + t.out[l - 1];
+    const float* y = l + 1 < nl ? tape + t.out[l] : nullptr;
+    if (!tfl::conv_wgrad(st, m->is3d, p, B, Z, Y, X, L.cin, L.cout, L.k, x, g, y, y ? tfl::train_och(tl, l) : 0, act, l > 0 && y, partials))
+      return fail(c, TFL_EUNSUPPORTED, "%s: no weight-gradient kernel for layer %d (%d output channels)", who, l, L.cout);
+    tfl::conv_wgrad_finish(st, p, L.cin, L.cout, L.cin_ref, L.cout_ref, L.skip_in ? 1 : 0, partials, gradWeights[l], gradBiases[l],
+                           accumulate != 0);
+    if (l == 0) break;
+    // g_in = conv(g_pre, W transposed and mirrored); the joined skip channel gets none
+    if (!tfl::conv_direct(st, m->is3d, B, Z, Y, X, L.cout, L.cin - (L.skip_in ? 1 : 0), L.k, 0, g, L.wt, m->zero_bias, g2))
+      return fail(c, TFL_EUNSUPPORTED, "%s: no kernel for %d channels", who, L.cin - (L.skip_in ? 1 : 0));
+    std::swap(g, g2);
+  }
+  return check_launch(c, who);
 }
 
 }  // extern "C"

@@ -382,6 +382,20 @@ void velocity_update_bwd(hipStream_t st, bool is3d, int B, int Z, int Y, int X, 
 void upsample_nearest_fwd(hipStream_t st, int ratio, long long rows, int Zo, int Yo, int Xo, const float* in, float* out);
 void upsample_nearest_bwd(hipStream_t st, int ratio, long long rows, int Zi, int Yi, int Xi, const float* go, float* gi);
 
+// conv_bwd.hip: the parameter gradients of one convolution layer (tfl_model_backward), deterministic. `p`: the layer's chunking
+// (tfl_train.hpp wg_plan). conv_wgrad leaves fp64 partials of gradWeight and gradBias per block; g is masked by act'(y) where it
+// is read (y = null: no activation) and, with wb, rewritten masked for the data gradient that follows. conv_wgrad_finish adds
+// the partials in a fixed order and writes (accumulate = 0) or adds onto (1) the cudnn-layout gw [cout_ref][cin_ref][taps] and
+// gb [cout_ref]. false = the layer does not fit the kernel (nothing launched).
+struct WgPlan;
+bool conv_wgrad_fits(const WgPlan& p);
+bool conv_wgrad(hipStream_t st, bool is3d, const WgPlan& p, int B, int Z, int Y, int X, int cin, int cout, int k, const float* x,
+                float* g, const float* y, int ych, int act, bool wb, double* partials);
+void conv_wgrad_finish(hipStream_t st, const WgPlan& p, int cin, int cout, int cin_ref, int cout_ref, int skip_in, const double* partials,
+                       float* gw, float* gb, int accumulate);
+// dst[b][t] = scale_b * src[b][t] (+ add[b][t]) over `per` floats per batch item; scale_b from the (sum, sum of squares) pairs
+void scale_add(hipStream_t st, int B, long long per, const double* stats, double count, const float* src, const float* add, float* dst);
+
 // conv2d_mfma.hip (2-D default topology: 16 channels, k = 3; one MFMA = one tap x four input channels)
 void conv2_mfma_first_fused(hipStream_t st, int B, int Y, int X, const float* pDiv, const float* div, const float* flags,
                             const double* stats, double count, const float* bfrag, const float* bias, float* out16);

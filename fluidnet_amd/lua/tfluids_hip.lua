@@ -170,6 +170,15 @@ int tfl_model_finish(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* pDiv, con
                      const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace,
                      int64_t workspace_floats, const double* stats, double count, const tfl_tensor* UBC,
                      const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi);
+int tfl_model_set_weights(tfl_ctx* ctx, tfl_model* model, const float* const* weights, const float* const* biases);
+int64_t tfl_model_tape_floats(const tfl_model* model, int B, int Z, int Y, int X);
+int tfl_model_forward_train(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* pDiv, const tfl_tensor* UDiv,
+                            const tfl_tensor* flags, const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace,
+                            int64_t workspace_floats, float* tape, int64_t tape_floats);
+int64_t tfl_model_backward_workspace_floats(const tfl_model* model, int B, int Z, int Y, int X);
+int tfl_model_backward(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* flags, const tfl_tensor* gradP,
+                       const tfl_tensor* gradU, const float* tape, int64_t tape_floats, float* workspace,
+                       int64_t workspace_floats, float* const* gradWeights, float* const* gradBiases, int accumulate);
 int tfl_set_dx_override(tfl_ctx* ctx, float dx);
 int tfl_applyBCs(tfl_ctx* ctx, const tfl_tensor* x, const tfl_tensor* bc, const tfl_tensor* invMask,
                  int doClamp, float lo, float hi);
@@ -574,6 +583,53 @@ function Model:cuda() return self end
 -- so far (no synchronisation). TFL_CONV_PATH=winograd in the environment before hip.Model(...) is the strict-fp32 stack.
 function Model:rangeErrors() return tonumber(lib.tfl_model_range_errors(ctx, self.handle)) end
 function Model:rangeFlag() return tonumber(lib.tfl_model_range_flag(ctx, self.handle)) end
+
+-- The training side (linear models without pooling / upsampling; parameter gradients only -- include/tfluids_hip.h).
+-- model:setWeights(weights, biases): tables of FloatTensors laid out like the convolutions' weight / bias, copied into the
+-- model's own buffers (synchronous; re-record any slab graph built on the model).
+function Model:setWeights(weights, biases)
+  local n = #weights
+  local ws, bs, hold = ffi.new('const float*[?]', n), ffi.new('const float*[?]', n), {}
+  for i = 1, n do
+    local w, b = weights[i]:float():contiguous(), biases[i]:float():contiguous()
+    hold[#hold + 1] = w; hold[#hold + 1] = b
+    ws[i - 1], bs[i - 1] = ffi.cast('const float*', torch.data(w)), ffi.cast('const float*', torch.data(b))
+  end
+  check(lib.tfl_model_set_weights(ctx, self.handle, ws, bs))
+end
+-- model:forwardTrain({pDiv, UDiv, flags}) -> {p, U}: the forward on the exact fp32 kernels that keeps the tape for model:backward
+function Model:forwardTrain(input)
+  local pDiv, UDiv, flags = input[1], input[2], input[3]
+  self.p = self.p or pDiv.new(); self.U = self.U or UDiv.new()
+  self.p:resizeAs(pDiv); self.U:resizeAs(UDiv)
+  local B, Z, Y, X = flags:size(1), flags:size(3), flags:size(4), flags:size(5)
+  local ws, n = workspace(pDiv, lib.tfl_model_workspace_floats(self.handle, B, Z, Y, X))
+  local nt = tonumber(lib.tfl_model_tape_floats(self.handle, B, Z, Y, X))
+  if nt < 0 then error('this model has no training pass (graph model, pooling or upsampling layers)', 2) end
+  self.tape = self.tape or pDiv.new()
+  self.tape:resize(nt)
+  check(lib.tfl_model_forward_train(ctx, self.handle, T(pDiv), T(UDiv), T(flags), T(self.p), T(self.U), ws, n,
+                                    ffi.cast('float*', torch.data(self.tape)), nt))
+  self.output = {self.p, self.U}
+  return self.output
+end
+-- model:backward(flags, gradP, gradU, gradWeights, gradBiases, accumulate): gradWeights / gradBiases are tables of CudaTensors
+-- shaped like the convolutions' weight / bias; gradP or gradU may be nil; accumulate = true adds (accGradParameters)
+function Model:backward(flags, gradP, gradU, gradWeights, gradBiases, accumulate)
+  assert(self.tape, 'model:forwardTrain first')
+  local n = #gradWeights
+  local gw, gb = ffi.new('float*[?]', n), ffi.new('float*[?]', n)
+  for i = 1, n do
+    gw[i - 1], gb[i - 1] = ffi.cast('float*', torch.data(gradWeights[i])), ffi.cast('float*', torch.data(gradBiases[i]))
+  end
+  local B, Z, Y, X = flags:size(1), flags:size(3), flags:size(4), flags:size(5)
+  local need = tonumber(lib.tfl_model_backward_workspace_floats(self.handle, B, Z, Y, X))
+  self.bwdWork = self.bwdWork or flags.new()
+  if self.bwdWork:nElement() < need then self.bwdWork:resize(need) end
+  check(lib.tfl_model_backward(ctx, self.handle, T(flags), gradP and T(gradP) or nil, gradU and T(gradU) or nil,
+                               ffi.cast('const float*', torch.data(self.tape)), self.tape:nElement(),
+                               ffi.cast('float*', torch.data(self.bwdWork)), self.bwdWork:nElement(), gw, gb, b2i(accumulate == true)))
+end
 
 -- ---- tfluids.simulate as ONE native call (lib/simulate.lua:175-327 = fluidnet_amd/csrc/simulate.cpp) -----------------
 local plans = setmetatable({}, {__mode = 'k'})    -- BC tensor -> {mask tensor, tfl_bc_plan*}: created once per pair

@@ -426,6 +426,46 @@ int tfl_model_finish(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* pDiv, con
                      int64_t workspace_floats, const double* stats, double count, const tfl_tensor* UBC,
                      const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi);
 
+/* ---- the training side of the projection ConvNet: the reference's closure is model:forward, crit:forward / :backward,
+ * model:backward (lib/run_epoch.lua:207-235, 269-293); tfl_fluidCriterion is the middle, these are the two ends. For linear
+ * models (tfl_model_create[_ex|_opts]) whose layers neither pool nor upsample -- `default`, `yang`, custom layer tables, every
+ * tfl_model_opts switch. Graph models and models with pooling / ConvolutionUpsample layers (`tog`) are refused with
+ * TFL_EUNSUPPORTED before anything is written. Parameter gradients only: the gradients to pDiv, UDiv and flags are not built
+ * (the reference computes a gradInput and run_epoch.lua discards it). */
+
+/* New weights into an existing model: host pointers laid out as for tfl_model_create. Every re-layout the model's path holds
+ * (the [tap][cin][cout] form, the MFMA fragments, the Winograd transform, the tail packs, the data-gradient form) is redone into
+ * the buffers it already has, by the code that filled them at creation. Synchronous: waits for the context's stream, copies,
+ * and returns with the new weights in place -- what an optimiser step calls; legal between two tfl_simulate_step calls. A
+ * tfl_slab_graph recorded with this model holds per-layer constants of the OLD weights by value: the model does not know its
+ * graphs, so the caller destroys and re-records them after this call. */
+int tfl_model_set_weights(tfl_ctx* ctx, tfl_model* model, const float* const* weights, const float* const* biases);
+/* Floats of the tape tfl_model_forward_train fills for a [B][.][Z][Y][X] grid (-1: the model has no training pass). */
+int64_t tfl_model_tape_floats(const tfl_model* model, int B, int Z, int Y, int X);
+/* tfl_model_forward (without its fused UBC / clamp tail) that also keeps what the backward pass reads in `tape` (device,
+ * 8-byte aligned): the per-item input scale, the net input, every layer's post-activation output with the joined skip channel.
+ * Always evaluated on the shape-generic fp32 kernels -- the exact fmaf chain, no fp16 and hence no range gate -- whatever
+ * path the model was created on: the outputs are those of the same model created under TFL_CONV_PATH=direct, bit for bit.
+ * workspace: tfl_model_workspace_floats. A short tape or workspace is TFL_EINVAL with nothing written. */
+int tfl_model_forward_train(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* pDiv, const tfl_tensor* UDiv,
+                            const tfl_tensor* flags, const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace,
+                            int64_t workspace_floats, float* tape, int64_t tape_floats);
+/* Scratch floats tfl_model_backward needs (-1: the model has no training pass). */
+int64_t tfl_model_backward_workspace_floats(const tfl_model* model, int B, int Z, int Y, int X);
+/* model:backward for the parameters: from gradP / gradU at the model's outputs (either may be NULL = zero) and the tape of
+ * the forward pass, gradWeights[l] / gradBiases[l] (DEVICE arrays, laid out like the weights of tfl_model_create). At the
+ * last layer's output, per batch item with its input scale,
+ *   g = scale gradP + velocityUpdateBackward(scale setWallBcsBackward(gradU))
+ * then per layer from the last to the first g_pre = g (.) act'(y), gradBias = sum g_pre, gradWeight[co][ci][tap] =
+ * sum x[ci][pos + tap] g_pre[co][pos], and g = conv(g_pre, W transposed and mirrored) for the layer in front.
+ * accumulate = 0 overwrites; 1 adds the fresh gradient, rounded to fp32, onto what is there with one fp32 add per element
+ * (Torch's accGradParameters). Sums over voxels run in a fixed order (fp32 fmaf inside a 32 x 8 tile, fp64 across tiles and
+ * blocks, no atomics): the same inputs give the same bits on every call. No host read, no stream synchronisation; capturable.
+ * Sizes are checked before the first launch: a short tape or workspace is TFL_EINVAL with nothing written. */
+int tfl_model_backward(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* flags, const tfl_tensor* gradP,
+                       const tfl_tensor* gradU, const float* tape, int64_t tape_floats, float* workspace,
+                       int64_t workspace_floats, float* const* gradWeights, float* const* gradBiases, int accumulate);
+
 /* A z-slab rank holds only part of the grid, but tfluids.getDx = 1/max(X,Y,Z) (grid.cc:37-40) is a
  * property of the WHOLE grid: dx > 0 overrides the value addBuoyancy / addGravity derive from the
  * local tensor sizes; 0 restores the default. */
