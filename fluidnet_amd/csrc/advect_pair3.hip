@@ -73,8 +73,8 @@ __global__ __launch_bounds__(256) void k_adv3_bwd_pair(PairGrid g, AdvArgs as, d
 // runs the two operators one after the other. fold_s / fold_v: the setConstVals pairs pass B may apply (tfl_host.hpp BcFold).
 bool advect_pair3(hipStream_t st, const AdvArgs& a0, int B, const float* s, const float* U, const float* flags, float* sfwd, float* sbounds,
                   float* sdst, float* vfwd, float* vdst, int stages, const BcFoldArg& fold_s, const BcFoldArg& fold_v) {
-  static const bool off = (getenv("TFL_ADV_PAIR") && atoi(getenv("TFL_ADV_PAIR")) == 0) || exp_env("TFL_ADVECT_GATHER") || exp_env("TFL_SCALAR_GATHER") ||
-                          getenv("TFL_VEL3_KZ") || getenv("TFL_SCAL3_TZ");      // (a forced block shape means the caller wants THOSE kernels)
+  const bool off = sw::num(Sw::ADV_PAIR, 1) == 0 || sw::present(Sw::ADVECT_GATHER) || sw::present(Sw::SCALAR_GATHER) ||
+                   sw::present(Sw::VEL3_KZ) || sw::present(Sw::SCAL3_TZ);      // (a forced block shape means the caller wants THOSE kernels)
   const Dom& d = a0.d;
   if (off || a0.outside || d.Z < 3 || (long long)d.X * d.Y * 4 >= (1 << 24) || 12ll * d.sc >= (1ll << 32) || (long long)d.sc >= 6000000ll) return false;
   const int G = (d.n0 + 1) / 2 + (d.nw - d.n0 + 1) / 2;      // scalar: groups of two planes over the window's two runs

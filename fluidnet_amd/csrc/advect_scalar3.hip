@@ -573,15 +573,15 @@ void launch(hipStream_t st, int shape, bool two_pass, const AdvArgs& a, int B, c
 #ifndef TFL_SCAL3_NO_ENTRY      // (advect_pair3.hip includes this file for the kernels' bodies only)
 int scal3_zskip(const Dom& d) {
   // A/B and test switch, EXPERIMENTS flavour only (the product library is at its limit of switches): 0 = no short path
-  static const bool on = !(exp_env("TFL_SCAL3_ZSKIP") && atoi(exp_env("TFL_SCAL3_ZSKIP")) == 0);
+  const bool on = sw::num(Sw::SCAL3_ZSKIP, 1) != 0;
   // the proof that a `small` displacement ends in the lane's own cell needs ulp(cell centre) <= 2^-8 (header)
   return on && d.X <= kSmallExtent && d.Y <= kSmallExtent && d.Zg <= kSmallExtent;
 }
 
 bool advect_scalar3(hipStream_t st, bool two_pass, const AdvArgs& a0, int B, const float* s, const float* U, const float* flags,
                     float* fwd, float* bounds, float* dst, int stages, Fold& f) {
-  static const bool off = exp_env("TFL_ADVECT_GATHER") != nullptr || exp_env("TFL_SCALAR_GATHER") != nullptr;   // A/B switch: the round-2 gather kernels
-  static const int tzsel = getenv("TFL_SCAL3_TZ") ? atoi(getenv("TFL_SCAL3_TZ")) : 0;   // 0 = per pass and grid size (launch)
+  const bool off = sw::present(Sw::ADVECT_GATHER) || sw::present(Sw::SCALAR_GATHER);   // A/B switch: the round-2 gather kernels
+  const int tzsel = sw::num(Sw::SCAL3_TZ, 0);   // 0 = per pass and grid size (launch)
   const Dom& d = a0.d;
   // 24-bit multiplies address the tile and the planes; 32-bit BYTE offsets the cells of the three velocity channels
   if (off || a0.outside || d.Z < 3 || (long long)d.X * d.Y * 4 >= (1 << 24) || 12ll * d.sc >= (1ll << 32)) return false;
@@ -591,8 +591,7 @@ bool advect_scalar3(hipStream_t st, bool two_pass, const AdvArgs& a0, int B, con
   // tile kernels (profiles/r05_advect_experiments.txt: pass A 29.5 vs 25.3 us at 128^3, 176 vs 162 at 256^3; pass B 21.3 vs
   // 20.8, 143 vs 141): these passes run at the length of their instruction streams, and the ring addressing + the per-plane
   // staging bookkeeping make the marched stream LONGER per cell (345 against 274 vector instructions in pass A)
-  static const bool march = getenv("TFL_SCAL3_MARCH") && atoi(getenv("TFL_SCAL3_MARCH")) == 1;
-  if (march && !tzsel) {
+  if (sw::num(Sw::SCAL3_MARCH, 0) == 1 && !tzsel) {
     if (a.fast) zm::launch<true>(st, two_pass, a, B, s, U, flags, fwd, bounds, dst, stages, f);
     else zm::launch<false>(st, two_pass, a, B, s, U, flags, fwd, bounds, dst, stages, f);
     return true;

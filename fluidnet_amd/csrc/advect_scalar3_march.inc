@@ -348,8 +348,8 @@ static int device_cus() {
 }
 // chunk length: the blocks of a launch occupy the chip in rounds of `slots`; a block of c planes costs c plane steps + `fill`
 // staging-only planes (a sixth of a step each) + ~2 steps of prologue latency
-static int pick_chunk(long long cols, int na, int nb, int slots, int fill, const char* env) {
-  if (const char* e = getenv(env)) if (atoi(e) > 0) return atoi(e);
+static int pick_chunk(long long cols, int na, int nb, int slots, int fill, Sw override) {
+  if (const int e = sw::num(override, 0); e > 0) return e;
   int best_c = 8; double best = -1.0;
   for (int c = 2; c <= 128; c++) {
     const long long blocks = cols * ((na + c - 1) / c + (nb + c - 1) / c);
@@ -370,7 +370,7 @@ void launch(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float*
   const long long cols = (long long)cxn * cyn * B;
   if (pa) {
     const void* fn = two_pass ? (const void*)k_scal3m_fwd<true, FAST> : (const void*)k_scal3m_fwd<false, FAST>;
-    const int cz = pick_chunk(cols, na, nb, device_cus() * blocks_per_cu(fn), 5, "TFL_SCAL3M_CZ_A");
+    const int cz = pick_chunk(cols, na, nb, device_cus() * blocks_per_cu(fn), 5, Sw::SCAL3M_CZ_A);
     const int chunks_a = (na + cz - 1) / cz, chunks = chunks_a + (nb + cz - 1) / cz;
     TFL_TIMED_EXT("k_scalar_fwd", st);
     if (two_pass) TFL_LAUNCH_EXT((k_scal3m_fwd<true, FAST>), (unsigned)(cols * chunks), dim3(TX, TY, 1), 0, st, a, cxn, cyn, cz, chunks_a, chunks, s, U, flags, outA, bounds);
@@ -378,7 +378,7 @@ void launch(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float*
   }
   const BcFoldArg fold = pb ? f.hand_bc() : no_fold();   // pass B writes the operator's result
   if (pb) {
-    const int cz = pick_chunk(cols, na, nb, device_cus() * blocks_per_cu((const void*)k_scal3m_bwd<FAST>), 3, "TFL_SCAL3M_CZ_B");
+    const int cz = pick_chunk(cols, na, nb, device_cus() * blocks_per_cu((const void*)k_scal3m_bwd<FAST>), 3, Sw::SCAL3M_CZ_B);
     const int chunks_a = (na + cz - 1) / cz, chunks = chunks_a + (nb + cz - 1) / cz;
     TFL_TIMED_EXT("k_scalar_bwd", st);
     TFL_LAUNCH_EXT((k_scal3m_bwd<FAST>), (unsigned)(cols * chunks), dim3(TX, TY, 1), 0, st, a, cxn, cyn, cz, chunks_a, chunks, (double)a.strength * 0.5,

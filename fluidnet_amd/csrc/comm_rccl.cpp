@@ -27,6 +27,7 @@
 
 #include "../../include/tfluids_hip.h"
 #include "tfl_ctx.hpp"
+#include "tfl_switches.hpp"
 
 namespace {
 
@@ -55,7 +56,7 @@ std::once_flag g_once;
 
 void load_api() {
   RcclApi& a = g_api;
-  const char* env = getenv("TFL_RCCL_LIBRARY");
+  const char* env = tfl::sw::text(tfl::Sw::RCCL_LIBRARY);
   const char* names[] = {"librccl.so.1", "librccl.so"};
   if (env && env[0]) {
     a.handle = dlopen(env, RTLD_NOW | RTLD_LOCAL);
@@ -219,7 +220,7 @@ tfl_rccl_comm* make(tfl_ctx* c, const RcclApi* a, NcclComm comm, bool owns, int 
   q->callbacks.exchange_wait = cb_exchange_wait;
   q->callbacks.allreduce_sum = cb_allreduce_sum;
   // TFL_RCCL_PACKED=1: staged messages (one send + one receive per neighbour, pack / unpack kernels) for comparison
-  q->callbacks.exchange_start_v = getenv("TFL_RCCL_PACKED") ? nullptr : cb_exchange_start_v;
+  q->callbacks.exchange_start_v = tfl::sw::present(tfl::Sw::RCCL_PACKED) ? nullptr : cb_exchange_start_v;
   q->callbacks.capturable = 1;     // every callback above is event record / wait + nccl* calls on streams: a step records into a HIP graph
   return q;
 }

@@ -91,7 +91,7 @@ tfl_ctx* tfl_create(int device) {
     return nullptr;
   }
   c->h_reach[0] = 0.0f; reinterpret_cast<unsigned*>(c->h_reach)[1] = 0u;
-  if (const char* m = getenv("TFL_ADVECT_MODE")) c->advect_fast = (strcmp(m, "fast") == 0 || strcmp(m, "1") == 0) ? 1 : 0;
+  if (const char* m = tfl::sw::text(tfl::Sw::ADVECT_MODE)) c->advect_fast = (strcmp(m, "fast") == 0 || strcmp(m, "1") == 0) ? 1 : 0;
   return c;
 }
 

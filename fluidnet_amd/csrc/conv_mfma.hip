@@ -272,7 +272,7 @@ static void launch_mfma(hipStream_t st, const Dom& d, int B, const float* in, co
     (void)hipFuncSetAttribute((const void*)k_conv3_mfma<CIN, IN_PLANAR, TAIL>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     attr_dev = cur_dev;
-    if (getenv("TFL_DEBUG")) {
+    if (sw::present(Sw::DEBUG)) {
       int nb = -1;
       (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_conv3_mfma<CIN, IN_PLANAR, TAIL>, 256,
                                                          lds_bytes);
@@ -281,9 +281,8 @@ static void launch_mfma(hipStream_t st, const Dom& d, int B, const float* in, co
     }
   }
   TFL_TIMED_EXT(TAIL ? "k_conv3_mfma_tail" : (IN_PLANAR ? "k_conv3_mfma_in" : "k_conv3_mfma"), st);
-  static const int dbg = exp_env("TFL_CONV_DEBUG") ? atoi(exp_env("TFL_CONV_DEBUG")) : 0;
-  static const bool want_trace = exp_env("TFL_CONV_TRACE") != nullptr;
-  if (want_trace) {
+  const int dbg = sw::num(Sw::CONV_DEBUG, 0);
+  if (sw::present(Sw::CONV_TRACE)) {
     // development aid: per-block phase timestamps of this launch, summarised on stderr (synchronises!)
     unsigned long long* dev = nullptr;
     const size_t n = (size_t)grid * 8;

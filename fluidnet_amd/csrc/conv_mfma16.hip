@@ -137,12 +137,6 @@ __device__ __forceinline__ void stagger_start(int units, uint4* lds) {
   __syncthreads();
   for (int i = 0; i < n; i++) __builtin_amdgcn_s_sleep(1);
 }
-#ifdef TFL_EXPERIMENTS
-static int stagger_units(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-#endif
 
 // a + b after v_permlane32_swap / v_permlane16_swap of the pair: the sum over the two lane halves (32) or over the odd /
 // even 16-lane row pairs (16) of a in the lanes that keep their a, of b in the others (the tail's reduce-scatter).
@@ -663,17 +657,6 @@ static int pick_chunk(long long cols, int na, int nb, int slots, int cus, float 
 }
 
 
-
-// A development switch of the EXPERIMENTS flavour (chunk lengths, the de-phased block starts): the default library reads none
-static int exp_int(const char* name, int dflt) {
-#ifdef TFL_EXPERIMENTS
-  if (const char* e = getenv(name)) return atoi(e);
-#else
-  (void)name;
-#endif
-  return dflt;
-}
-
 template <bool TAIL>
 static void launch_m16p(hipStream_t st, const Dom& d, int B, const void* in, const void* wfrag, const float* bias, void* out,
                         float post, unsigned long long* range_err) {
@@ -685,11 +668,11 @@ static void launch_m16p(hipStream_t st, const Dom& d, int B, const void* in, con
   if (!attr_done[TAIL]) { (void)hipFuncSetAttribute((const void*)k_conv3_m16q<TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); attr_done[TAIL] = true; }
   const int slots = device_cus() * blocks_per_cu((const void*)k_conv3_m16q<TAIL>, lds_bytes, TFL_M16Q_LB);
   int cz = pick_chunk((long long)cxn * cyn * B, na, nb, slots, device_cus(), 0.70f, 0.35f);
-  if (const int e = exp_int("TFL_M16_CZ", 0); e > 0) cz = e;
+  if (const int e = sw::num(Sw::M16_CZ, 0); e > 0) cz = e;
   const int chunks_a = (na + cz - 1) / cz, chunks = chunks_a + (nb + cz - 1) / cz;
   const int n_blocks = cxn * cyn * chunks * B;
   const int grid = ((n_blocks + 7) / 8) * 8;
-  if (getenv("TFL_DEBUG")) {
+  if (sw::present(Sw::DEBUG)) {
     static bool said[2] = {false, false};
     if (!said[TAIL]) {
       said[TAIL] = true;
@@ -701,16 +684,14 @@ static void launch_m16p(hipStream_t st, const Dom& d, int B, const void* in, con
   TFL_TIMED_EXT(TAIL ? "k_conv3_tail" : "k_conv3_mid", st);
 #ifdef TFL_EXPERIMENTS
   // the tail's 1 x 1 x 1 layers on the vector ALUs (TFL_M16_TAIL_MFMA=0) / the un-pipelined kernel (TFL_M16_PIPE=0): k_conv3_m16p
-  const char* etm = getenv("TFL_M16_TAIL_MFMA");       // (read per call: the tests switch it inside one process)
-  const bool tmf = !(etm && atoi(etm) == 0);
-  const char* epp = getenv("TFL_M16_PIPE");
-  if ((epp && atoi(epp) == 0) || (TAIL && !tmf)) {
+  const bool tmf = sw::num(Sw::M16_TAIL_MFMA, 1) != 0;
+  if (sw::num(Sw::M16_PIPE, 1) == 0 || (TAIL && !tmf)) {
     if (TAIL && tmf)
       TFL_LAUNCH_EXT((k_conv3_m16p<TAIL, TAIL>), grid, 256, lds_bytes, st, d, cxn, cyn, cz, chunks_a, chunks, n_blocks, (const uint4*)in,
-                     wp, bias, out, post, range_err, stagger_units("TFL_M16_STAGGER", 0));
+                     wp, bias, out, post, range_err, sw::num(Sw::M16_STAGGER, 0));
     else
       TFL_LAUNCH_EXT((k_conv3_m16p<TAIL, false>), grid, 256, lds_bytes, st, d, cxn, cyn, cz, chunks_a, chunks, n_blocks, (const uint4*)in,
-                     wp, bias, out, post, range_err, stagger_units("TFL_M16_STAGGER", 0));
+                     wp, bias, out, post, range_err, sw::num(Sw::M16_STAGGER, 0));
     return;
   }
 #endif
@@ -725,36 +706,33 @@ static void launch_m16p_in(hipStream_t st, const Dom& d, int B, MIn cin, const v
   if (cxn * cyn * (na + nb) * B <= 0) return;
   const int slots = device_cus() * blocks_per_cu((const void*)k_conv3_m16p_in, 0, TFL_M16PI_LB);
   int cz = pick_chunk((long long)cxn * cyn * B, na, nb, slots, device_cus(), 0.95f, 0.24f);
-  if (const int e = exp_int("TFL_M16_CZ_IN", 0); e > 0) cz = e;
+  if (const int e = sw::num(Sw::M16_CZ_IN, 0); e > 0) cz = e;
   const int chunks_a = (na + cz - 1) / cz, chunks = chunks_a + (nb + cz - 1) / cz;
   const int n_blocks = cxn * cyn * chunks * B;
   const int grid = ((n_blocks + 7) / 8) * 8;
-  if (getenv("TFL_DEBUG")) {
+  if (sw::present(Sw::DEBUG)) {
     static bool said = false;
     if (!said) { said = true; fprintf(stderr, "[tfl] k_conv3_m16p_in: %d block slots, grid %d, chunks of %d planes\n", slots, grid, cz); }
   }
   const uint4* wp = (const uint4*)wfrag + (9 * 64 + 1);     // behind the tile kernel's fragments (conv3_m16_pack_weights)
   TFL_TIMED_EXT("k_conv3_in", st);
   TFL_LAUNCH_EXT(k_conv3_m16p_in, grid, 256, 0, st, d, cxn, cyn, cz, chunks_a, chunks, n_blocks, cin, wp, bias, out, post, range_err,
-                 exp_int("TFL_M16_STAGGER_IN", 0));
+                 sw::num(Sw::M16_STAGGER_IN, 0));
 }
 
 #ifdef TFL_EXPERIMENTS
 #define TFL_M16_EXP_SECTION 2
 #include "conv_mfma16_exp.inc"
 #undef TFL_M16_EXP_SECTION
-// which of the earlier forms the switches of this flavour ask for: TFL_M16_KPACK = 0 (k_conv3_m16z; first layer: the tile kernel) or
-// 2 (first layer only), TFL_M16_TILED bit 0 / 1 = the tile kernel for the mid / tail layer
-static int exp_kpack() { static const int v = getenv("TFL_M16_KPACK") ? atoi(getenv("TFL_M16_KPACK")) : 1; return v; }
-static int exp_tiled() { const char* e = getenv("TFL_M16_TILED"); return e ? atoi(e) : 0; }
 #endif
+// which of the earlier forms the switches of the EXPERIMENTS flavour ask for: TFL_M16_KPACK = 0 (k_conv3_m16z; first layer: the tile
+// kernel) or 2 (first layer only), TFL_M16_TILED bit 0 / 1 = the tile kernel for the mid / tail layer (product library: 1 and 0)
+static int exp_kpack() { return sw::num(Sw::M16_KPACK, 1); }
+static int exp_tiled() { return sw::num(Sw::M16_TILED, 0); }
 
 bool conv3_m16_first_sums_partials() {
-#ifdef TFL_EXPERIMENTS
   if (exp_kpack() == 0 || exp_kpack() == 2) return false;      // the tile kernel reads the reduced sums
-#endif
-  const char* e = getenv("TFL_STATS_CONSUMER");     // A/B switch (read per call: the parity test flips it inside one process): 0 = k_reduce_stats as its own launch
-  return !(e && atoi(e) == 0);
+  return sw::num(Sw::STATS_CONSUMER, 1) != 0;     // A/B switch: 0 = k_reduce_stats as its own launch
 }
 void conv3_m16_first_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const float* pDiv, const float* div, const float* flags,
                            const double* stats, double count, const void* wfrag, const float* bias, float post, void* out_h2,
@@ -780,14 +758,7 @@ bool conv3_m16_first2_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y
   return false;
 #endif
 }
-bool conv3_m16_fuse12_requested() {
-#ifdef TFL_EXPERIMENTS
-  const char* ef = getenv("TFL_M16_FUSE12");
-  return ef && atoi(ef) == 1;
-#else
-  return false;
-#endif
-}
+bool conv3_m16_fuse12_requested() { return sw::num(Sw::M16_FUSE12, 0) == 1; }
 void conv3_m16_mid(hipStream_t st, const Scope& sc, int B, int Z, int Y, int X, const void* in_h2, const void* wfrag, const float* bias, float post,
                    void* out_h2, unsigned long long* range_err) {
 #ifdef TFL_EXPERIMENTS

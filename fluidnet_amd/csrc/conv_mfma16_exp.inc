@@ -960,7 +960,7 @@ static void launch_m16z(hipStream_t st, const Dom& d, int B, const void* in, con
       if (best < 0 || cost < best) { best = cost; cz = c; }
     }
   }
-  if (const char* e = getenv("TFL_M16_CZ")) cz = atoi(e) > 0 ? atoi(e) : cz;
+  if (const int e = sw::num(Sw::M16_CZ, 0); e > 0) cz = e;
   const int chunks_a = (na + cz - 1) / cz, chunks = chunks_a + (nb + cz - 1) / cz;
   const int n_blocks = cxn * cyn * chunks * B;
   const int grid = ((n_blocks + 7) / 8) * 8;
@@ -969,7 +969,7 @@ static void launch_m16z(hipStream_t st, const Dom& d, int B, const void* in, con
   if (attr_dev != dev) {
     (void)hipFuncSetAttribute((const void*)k_conv3_m16z<TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     attr_dev = dev;
-    if (getenv("TFL_DEBUG")) {
+    if (sw::present(Sw::DEBUG)) {
       int nbk = -1;
       (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, (const void*)k_conv3_m16z<TAIL>, 256, lds_bytes);
       fprintf(stderr, "[tfl] k_conv3_m16z<%d>: dynamic LDS %zu B, occupancy %d blocks/CU, grid %d, chunks of %d planes\n", (int)TAIL, lds_bytes, nbk, grid, cz);
@@ -988,19 +988,18 @@ static void launch_m16z(hipStream_t st, const Dom& d, int B, const void* in, con
 // not valid).
 static bool launch_m16p_f2(hipStream_t st, const Dom& d, int B, MIn cin, const void* wfrag1, const float* bias1, float post1,
                            const void* wfrag2, const float* bias2, float post2, void* out, unsigned long long* range_err) {
-  const char* ef = getenv("TFL_M16_FUSE12");           // (read per call: the tests switch it inside one process)
-  if (!(ef && atoi(ef) == 1) || d.nw != d.Z || d.n0 != d.Z) return false;
+  if (sw::num(Sw::M16_FUSE12, 0) != 1 || d.nw != d.Z || d.n0 != d.Z) return false;
   const int cxn = (d.X + kMX - 1) / kMX, cyn = (d.Y + kMY - 1) / kMY;
   if ((long long)cxn * cyn * d.Z * B <= 0) return true;
   const int slots = device_cus() * blocks_per_cu((const void*)k_conv3_m16p_f2, kF2Lds, TFL_M16F2_LB);
   if (slots <= 0) return false;
   // a step carries both layers (~1.7 x the 8 -> 8 layer's) and a chunk has five fill steps: longer chunks than k_conv3_m16p's
   int cz = pick_chunk((long long)cxn * cyn * B, d.Z, 0, slots, device_cus(), 1.10f, 0.55f, kF2Fill + 2, 128);
-  if (const char* e = getenv("TFL_M16_CZ_F2")) cz = atoi(e) > 0 ? atoi(e) : cz;
+  if (const int e = sw::num(Sw::M16_CZ_F2, 0); e > 0) cz = e;
   const int chunks_a = (d.Z + cz - 1) / cz, chunks = chunks_a;
   const int n_blocks = cxn * cyn * chunks * B;
   const int grid = ((n_blocks + 7) / 8) * 8;
-  if (getenv("TFL_DEBUG")) {
+  if (sw::present(Sw::DEBUG)) {
     static bool said = false;
     if (!said) { said = true; fprintf(stderr, "[tfl] k_conv3_m16p_f2: dynamic LDS %zu B, %d block slots, grid %d, chunks of %d planes\n", kF2Lds, slots, grid, cz); }
   }
@@ -1008,7 +1007,7 @@ static bool launch_m16p_f2(hipStream_t st, const Dom& d, int B, MIn cin, const v
   const uint4* w2 = (const uint4*)wfrag2 + (9 * 2 * 64 + 1);
   TFL_TIMED_EXT("k_conv3_in_mid", st);
   TFL_LAUNCH_EXT(k_conv3_m16p_f2, grid, 256, kF2Lds, st, d, cxn, cyn, cz, chunks_a, chunks, n_blocks, cin, w1, bias1, post1, w2, bias2,
-                 post2, out, range_err, stagger_units("TFL_M16_STAGGER_F2", 0));
+                 post2, out, range_err, sw::num(Sw::M16_STAGGER_F2, 0));
   return true;
 }
 
@@ -1031,7 +1030,7 @@ static void launch_m16(hipStream_t st, const Dom& d, int B, const void* in, cons
       if (best < 0 || cost < best) { best = cost; nt = c; }
     }
   }
-  if (const char* e = getenv("TFL_M16_NT")) nt = atoi(e) > 0 ? atoi(e) : nt;
+  if (const int e = sw::num(Sw::M16_NT, 0); e > 0) nt = e;
   if (nt > tz) nt = tz;
   const int n_chunks = tx * ty * ((tz + nt - 1) / nt) * B;
   const int grid = ((n_chunks + 7) / 8) * 8;
@@ -1040,7 +1039,7 @@ static void launch_m16(hipStream_t st, const Dom& d, int B, const void* in, cons
   if (attr_dev != dev) {
     (void)hipFuncSetAttribute((const void*)k_conv3_m16<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     attr_dev = dev;
-    if (getenv("TFL_DEBUG")) {
+    if (sw::present(Sw::DEBUG)) {
       int nb = -1;
       (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_conv3_m16<MODE>, 256, lds_bytes);
       fprintf(stderr, "[tfl] k_conv3_m16<%d>: dynamic LDS %zu B, occupancy %d blocks/CU, grid %d, %d z-tiles per block\n", MODE, lds_bytes, nb, grid, nt);

@@ -260,7 +260,7 @@ static void launch_wino(hipStream_t st, const Dom& d, int B, const float* in, co
   if (attr_dev != cur_dev) {
     (void)hipFuncSetAttribute((const void*)k_conv3_wino<CIN, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     attr_dev = cur_dev;
-    if (getenv("TFL_DEBUG")) {
+    if (sw::present(Sw::DEBUG)) {
       int nb = -1;
       (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_conv3_wino<CIN, TAIL>, 256, lds_bytes);
       fprintf(stderr, "[tfl] k_conv3_wino<%d,%d>: dynamic LDS %zu B, occupancy %d blocks/CU, grid %d\n", CIN, (int)TAIL, lds_bytes, nb, grid);

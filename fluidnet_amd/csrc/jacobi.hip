@@ -183,7 +183,7 @@ __global__ __launch_bounds__(kJLdsThreads) void k_jacobi_lds(int Y, int X, const
 // true = the solve ran (p and resid_sq[b] written); false = shape / settings outside this path (caller iterates launches)
 bool jacobi_solve_lds(hipStream_t st, int B, int Y, int X, const float* flags, const float* div, float* p, float* p_prev,
                       int iters, double* resid_sq) {
-  static const bool off = getenv("TFL_JACOBI_LDS") && atoi(getenv("TFL_JACOBI_LDS")) == 0;
+  const bool off = sw::num(Sw::JACOBI_LDS, 1) == 0;
   const long long N = (long long)Y * X;
   if (off || N > kJLdsMaxCells || N < 1 || iters < 1) return false;
   const size_t lds = sizeof(float) * 2 * (size_t)N;

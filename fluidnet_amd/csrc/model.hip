@@ -839,12 +839,7 @@ long long model_stat_blocks(int B, int Z, int Y, int X) {
 }
 
 bool model_stats_fold_requested() {       // EXPERIMENTS flavour + TFL_STATS_FOLD=1: k_reduce_stats folded into the last block of k_bcs_div_stats
-#ifdef TFL_EXPERIMENTS
-  const char* ef = getenv("TFL_STATS_FOLD");
-  return ef && atoi(ef) == 1;
-#else
-  return false;
-#endif
+  return sw::num(Sw::STATS_FOLD, 0) == 1;
 }
 
 long long model_stat_pairs_per_plane(int B, int Z, int Y, int X, const float* U, const float* flags, const float* Ubc, const float* div) {
@@ -982,7 +977,7 @@ bool model_project(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int
   bc.UBC = UBC; bc.UInvMask = UInvMask; bc.fold = UBC ? no_fold() : f.hand_bc();
   const uintptr_t al = (uintptr_t)pPred | (uintptr_t)flags | (uintptr_t)Uio | (uintptr_t)pOut | (uintptr_t)UBC |
                        (uintptr_t)UInvMask;
-  if (X % 4 == 0 && (al & 15) == 0 && !exp_env("TFL_NO_VEC4")) {
+  if (X % 4 == 0 && (al & 15) == 0 && !sw::present(Sw::NO_VEC4)) {
     const dim3 vb(32, 8, 1), vg((X / 4 + 31) / 32, (Y + 7) / 8, (unsigned)(d.nw * B));
     // the reach maximum rides along where every block of the launch is full (128 x 8 cells: no thread leaves the kernel early)
     const bool acc = is3d && reach_acc && X % 128 == 0 && Y % 8 == 0;

@@ -856,7 +856,7 @@ tfl_model* tfl_model_create_opts(tfl_ctx* c, int is3D, int nlayers, const int32_
   tfl_model* m = build_layers(c, is3D != 0, nlayers, cin, cout, ksize, pool, up, weights, biases, o, stage_table(nlayers), nullptr);
   if (!m) return nullptr;
   // the default topologies run on kernels of their own (TFL_CONV_PATH=direct forces the generic ones)
-  const char* force = getenv("TFL_CONV_PATH");
+  const char* force = tfl::sw::text(tfl::Sw::CONV_PATH);
   if ((force && strcmp(force, "direct") == 0) || m->custom || m->multires || nlayers != 5) return m;
   const int dflt3[5][3] = {{3, 8, 3}, {8, 8, 3}, {8, 8, 3}, {8, 8, 1}, {8, 1, 1}};
   const int dflt2[5][3] = {{3, 16, 3}, {16, 16, 3}, {16, 16, 3}, {16, 16, 3}, {16, 1, 1}};

@@ -82,8 +82,7 @@ int set_const_vals(tfl_ctx* c, const tfl_sim_state* s, const tfl_tensor* U_now, 
 // (the pair kernels of advect_pair3.hip take two of them as arguments). TFL_BC_FOLD=0 keeps every pair in its own launch
 // (A/B switch).
 tfl::BcFoldArg fold_arg(const tfl_bc_plan* p) {
-  const char* e = getenv("TFL_BC_FOLD");       // (read per call: the A/B parity test switches it inside one process)
-  if ((e && atoi(e) == 0) || !p || !p->sparse || !p->boxed || !p->d_fold || p->n_idx == 0) return tfl::no_fold();
+  if (tfl::sw::num(tfl::Sw::BC_FOLD, 1) == 0 || !p || !p->sparse || !p->boxed || !p->d_fold || p->n_idx == 0) return tfl::no_fold();
   return tfl::BcFoldArg{p->d_fold, (unsigned)p->box[2] | ((unsigned)p->box[4] << 16), (unsigned)p->box[3] | ((unsigned)p->box[5] << 16)};
 }
 // What a step asks of an operator call (tfl_ops.hpp): the sparse pair of plan p (null: none) for the kernel that writes the
@@ -244,9 +243,8 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
   // Asked for only when the density's own pair has been applied already (or there is none) and the U pair travels with the
   // same kernel (or there is none); TFL_BUOY_FOLD=0 keeps the force in its own launch (A/B switch).
   {
-    const char* e = getenv("TFL_BUOY_FOLD");
     const bool rho_final = buoyant && (!s->densityBC[0] || (density_done & 1u));
-    if (rho_final && ours && is3D && !(e && atoi(e) == 0) && (!s->UBC || adv.fold.bc.dev)) {
+    if (rho_final && ours && is3D && tfl::sw::num(tfl::Sw::BUOY_FOLD, 1) != 0 && (!s->UBC || adv.fold.bc.dev)) {
       // strength = -gravity * (dt / dx) in float, exactly as tfl_addBuoyancyFrom forms it (tfluids.cc:1190-1192)
       const float bs = prm->dt / tfl::get_dx(c, sc, s->flags);
       adv.fold.buoy = tfl::BuoyFold{s->density[0]->data, -bg[0] * bs, -bg[1] * bs, -bg[2] * bs};
@@ -637,7 +635,7 @@ int copy_owned(tfl_ctx* c, const SlabGeom& g, const tfl_tensor* dst, const tfl_t
 struct Win { int a, b; };
 Win ext(const SlabGeom& g, int below, int above) {
   Win w;
-  static const int widen = tfl::exp_env("TFL_SLAB_WIDEN") ? atoi(tfl::exp_env("TFL_SLAB_WIDEN")) : 0;   // development aid
+  const int widen = tfl::sw::num(tfl::Sw::SLAB_WIDEN, 0);   // development aid
   below += widen; above += widen; w.a = g.o0 - below < 0 ? 0 : g.o0 - below; w.b = g.o1 + above > g.Zl ? g.Zl : g.o1 + above; return w;
 }
 

@@ -14,6 +14,8 @@
 #include <stdint.h>
 #include <cstdlib>
 
+#include "tfl_switches.hpp"
+
 namespace tfl {
 
 enum : int { kFluid = 1, kObstacle = 2, kEmpty = 4, kInflow = 8, kOutflow = 16, kOpen = 32,
@@ -138,24 +140,13 @@ inline bool device_has_8_xcds() {
   }
   return known[dev] > 0;
 }
-inline bool xcd_order_enabled() {
-#ifdef TFL_EXPERIMENTS
-  static const bool on = !(getenv("TFL_XCD_ORDER") && atoi(getenv("TFL_XCD_ORDER")) == 0);
-  return on && device_has_8_xcds();
-#else
-  return device_has_8_xcds();
-#endif
-}
+inline bool xcd_order_enabled() { return sw::num(Sw::XCD_ORDER, 2) != 0 && device_has_8_xcds(); }
 // run length of a gx x gy (x gz) launch: an eighth of a plane per XCD (measured best, or level with one run per XCD, for the
 // scalar advection and the curl / confinement kernels at 128^3 and 256^3: profiles/r05_xcd_order.txt). TFL_XCD_RUN = tiles
 // per run and TFL_XCD_ORDER = 1 (one run per XCD) are the switches of the EXPERIMENTS flavour.
 inline unsigned xcd_run(unsigned gx, unsigned gy) {
-#ifdef TFL_EXPERIMENTS
-  static const int run = getenv("TFL_XCD_RUN") ? atoi(getenv("TFL_XCD_RUN")) : 0;
-  static const int mode = getenv("TFL_XCD_ORDER") ? atoi(getenv("TFL_XCD_ORDER")) : 2;
-  if (run > 0) return (unsigned)run;
-  if (mode == 1) return 0;
-#endif
+  if (const int run = sw::num(Sw::XCD_RUN, 0); run > 0) return (unsigned)run;
+  if (sw::num(Sw::XCD_ORDER, 2) == 1) return 0;
   return gx * gy >= 8 ? gx * gy / 8 : 1;
 }
 

@@ -6,21 +6,11 @@
 #include <cstdlib>
 
 #include "tfl_device.hpp"
+#include "tfl_switches.hpp"
 
 struct tfl_model;
 
 namespace tfl {
-
-// A switch that only the EXPERIMENTS flavour of the library reads (-DTFL_EXPERIMENTS, `make exp`: the earlier and the
-// measured-slower kernel forms, chunk-length / block-order overrides, test hooks); in the product library it is always unset.
-inline const char* exp_env(const char* name) {
-#ifdef TFL_EXPERIMENTS
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
 
 // Where an operator computes and which of its passes run: a value that every windowed operator receives as an argument and
 // hands to its launchers. A public tfl_* operator that honours the tfl_set_* calls forms one from its context at entry

@@ -95,10 +95,9 @@ struct Vec4Launch { bool ok; dim3 blk, grd; };
 inline Vec4Launch vec4_launch(int B, const Dom& d, std::initializer_list<const void*> ptrs) {
   const int Y = d.Y, X = d.X;
   Vec4Launch l; l.ok = false;
-  static const bool disabled = exp_env("TFL_NO_VEC4") != nullptr;
   uintptr_t al = 0;
   for (const void* q : ptrs) al |= (uintptr_t)q;
-  if (disabled || X % 4 != 0 || (al & 15) != 0) return l;
+  if (sw::present(Sw::NO_VEC4) || X % 4 != 0 || (al & 15) != 0) return l;
   const int nx = X / 4, bx = nx <= 8 ? 8 : (nx <= 16 ? 16 : 32), by = 256 / bx;
   l.blk = dim3(bx, by, 1);
   l.grd = dim3((nx + bx - 1) / bx, (Y + by - 1) / by, (unsigned)(d.nw * B));

@@ -995,7 +995,7 @@ static bool launch_vort_pipe(hipStream_t st, const Dom& d, int B, int X, int Y, 
   if (pslots <= 0 || tiles * (na + nb) <= 0) return false;
   if ((long long)d.Z * Y * X * 12 >= (1ll << 32)) return false;      // the kernel addresses an item's array with 32-bit byte offsets (buffer accesses)
   int cz = march_chunk(tiles, na, nb, pslots, kPipeFill, 4);
-  if (const char* e = exp_env("TFL_VORT_CZ")) cz = atoi(e) > 0 ? atoi(e) : cz;
+  if (const int e = sw::num(Sw::VORT_CZ, 0); e > 0) cz = e;
   const int chunks_a = (na + cz - 1) / cz, chunks = chunks_a + (nb + cz - 1) / cz;
   const int n_blocks = (int)(pcx * pcy * chunks * B);
   TFL_TIMED_EXT("k_vort_fused", st);
@@ -1012,8 +1012,7 @@ static bool launch_vort_pipe(hipStream_t st, const Dom& d, int B, int X, int Y, 
 // z-slab rank's 40-plane array of 256^3 on 8 ranks was measured too -- 35.8 us against 40.7, the rank-step 0.293 -> 0.279 ms);
 // where the device cannot hold the pipelined kernel's block, k_vort_fused from 3 M cells (160^3: 69 / 80).
 bool vorticity_confinement_fused_ok(bool is3d, int Z, int Y, int X) {
-  static const int mode = getenv("TFL_VORT_FUSED") ? atoi(getenv("TFL_VORT_FUSED")) : -1;
-  static const int pipe_mode = getenv("TFL_VORT_PIPE") ? atoi(getenv("TFL_VORT_PIPE")) : -1;
+  const int mode = sw::num(Sw::VORT_FUSED, -1), pipe_mode = sw::num(Sw::VORT_PIPE, -1);
   if (!is3d || Z < 3 || mode == 0) return false;
   const long long cells = (long long)Z * Y * X;
   const bool pipe = pipe_mode != 0 && vort_pipe_slots() > 0;
@@ -1038,13 +1037,11 @@ bool vorticity_confinement_fused(hipStream_t st, const Scope& sc, int B, int Z, 
   // the software-pipelined form (one barrier per step; 64 x 16 tiles, 9 steps of fill) wherever the device can hold its block:
   // faster than k_vort_fused at every size measured, 9-step fill and all (profiles/r05_vort_pipe.txt). TFL_VORT_PIPE=0: the
   // three-barrier kernel
-  static const int pipe_mode = getenv("TFL_VORT_PIPE") ? atoi(getenv("TFL_VORT_PIPE")) : -1;
-  if (pipe_mode != 0) {
+  if (sw::num(Sw::VORT_PIPE, -1) != 0) {
 #ifdef TFL_EXPERIMENTS
     // 32 x 16 tiles, two 512-thread blocks per CU (round 6): level with 64 x 16 at 128^3 (34.9 against 34.3 us) and at 256^3
     // (182.6 / 180.5) -- a CU issues the two blocks' steps no faster than the one big block's; kept for A/B only
-    static const int tile = exp_env("TFL_VORT_TILE") ? atoi(exp_env("TFL_VORT_TILE")) : 64;
-    if (tile == 32 && launch_vort_pipe<32, 16>(st, d, B, X, Y, na, nb, Uin, Uout, flags, strength, xcd_order, f)) return true;
+    if (sw::num(Sw::VORT_TILE, 64) == 32 && launch_vort_pipe<32, 16>(st, d, B, X, Y, na, nb, Uin, Uout, flags, strength, xcd_order, f)) return true;
 #endif
     if (launch_vort_pipe<64, 16>(st, d, B, X, Y, na, nb, Uin, Uout, flags, strength, xcd_order, f)) return true;
   }
@@ -1053,7 +1050,7 @@ bool vorticity_confinement_fused(hipStream_t st, const Scope& sc, int B, int Z, 
   const int slots = vort_fused_slots();     // (the dynamic-LDS attribute is a per-device setting: asked once per device)
   if (slots <= 0) return false;             // the caller copies and runs the two-launch form
   int cz = march_chunk((long long)cxn * cyn * B, na, nb, slots, 6, 4);
-  if (const char* e = exp_env("TFL_VORT_CZ")) cz = atoi(e) > 0 ? atoi(e) : cz;
+  if (const int e = sw::num(Sw::VORT_CZ, 0); e > 0) cz = e;
   const int chunks_a = (na + cz - 1) / cz, chunks = chunks_a + (nb + cz - 1) / cz;
   const int n_blocks = cxn * cyn * chunks * B;
   TFL_TIMED_EXT("k_vort_fused", st);

@@ -4,16 +4,29 @@ and reads the switches that select them. A test that forces such a form runs in 
 (TFL_LIBRARY, fluidnet_amd/_lib.py): the library is chosen when it is loaded, once per process."""
 import functools
 import os
+import re
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXP_LIB = os.path.join(ROOT, "fluidnet_amd", "libtfluids_hip_exp.so")
+SWITCH_TABLE = os.path.join(ROOT, "fluidnet_amd", "csrc", "tfl_switches.hpp")
 
-# switches only the EXPERIMENTS flavour reads (tfl_host.hpp exp_env, conv_mfma16_exp.inc, advect_scalar3_march.inc, ...)
-EXPERIMENT_SWITCHES = ("TFL_ADVECT_GATHER", "TFL_SCALAR_GATHER", "TFL_M16_", "TFL_NO_VEC4", "TFL_SCAL3_MARCH", "TFL_SCAL3M_CZ_",
-                       "TFL_STATS_FOLD", "TFL_VEL3_KZ_B", "TFL_VORT_CZ", "TFL_VORT_TILE", "TFL_WF_", "TFL_XCD_", "TFL_SLAB_WIDEN", "TFL_CONV_DEBUG",
-                       "TFL_CONV_TRACE")
+# TFL_* variables the library does not read: the Python hosts and bench.py do (INTEGRATION.md 4e)
+HOST_SIDE = frozenset(("TFL_LIBRARY", "TFL_WALL_PLAN", "TFL_DIST_BACKEND", "TFL_RANKS_SHARE_GPU", "TFL_SLAB_GRAPH"))
+
+
+@functools.lru_cache(maxsize=None)
+def switch_rows():
+    """the rows of the library's switch table: {variable: (id, flavour, when, meaning)}"""
+    rows = re.findall(r'^\s*X\((\w+),\s*"(TFL_[A-Z0-9_]+)",\s*(PRODUCT|EXP),\s*(ONCE|PER_CALL),\s*"([^"]*)"\)', open(SWITCH_TABLE).read(), flags=re.M)
+    assert rows, SWITCH_TABLE
+    return {name: (ident, flavour, when, meaning) for ident, name, flavour, when, meaning in rows}
+
+
+def experiment_switches():
+    """switches only the EXPERIMENTS flavour reads"""
+    return frozenset(name for name, row in switch_rows().items() if row[1] == "EXP")
 
 
 def is_experiments_process():
@@ -21,10 +34,13 @@ def is_experiments_process():
 
 
 def child_env(env, extra=None):
-    """`env` + `extra`; when `extra` holds a switch of the EXPERIMENTS flavour the child loads that library"""
+    """`env` + `extra`; when `extra` holds a switch of the EXPERIMENTS flavour the child loads that library. A TFL_* key that the
+    library's table does not name would be ignored by either library: the test would compare a kernel with itself."""
     e = dict(env)
     e.update(extra or {})
-    if any(k.startswith(EXPERIMENT_SWITCHES) for k in (extra or {})):
+    unknown = [k for k in (extra or {}) if k.startswith("TFL_") and k not in switch_rows() and k not in HOST_SIDE]
+    assert not unknown, "no such switch in fluidnet_amd/csrc/tfl_switches.hpp: %s" % unknown
+    if experiment_switches() & set(extra or {}):
         if not os.path.exists(EXP_LIB):
             import pytest
             pytest.skip("fluidnet_amd/libtfluids_hip_exp.so is not built (make -C fluidnet_amd/csrc exp)")

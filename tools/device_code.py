@@ -36,6 +36,9 @@ def dump_one(job):
     o = os.path.join(d, "_.o")
     flags = makefile_flags(csrc, os.path.splitext(f)[0] + ".o") + (["-DTFL_EXPERIMENTS"] if flavour == "build_exp" else [])
     subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-x", "hip", "-c", "-o", o, f], cwd=csrc)
+    if ".hip_fatbin" not in subprocess.run([LLVM + "llvm-readelf", "-S", o], capture_output=True, text=True, check=True).stdout:
+        os.remove(o)
+        return "%s/%s: no device code" % (flavour, f)       # (a host-only .cpp of SRCS)
     subprocess.check_call([LLVM + "llvm-objcopy", "--dump-section", ".hip_fatbin=" + o + ".fb", o])
     subprocess.check_call([LLVM + "clang-offload-bundler", "--unbundle", "--type=o", "--input=" + o + ".fb",
                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + o + ".co"])
