@@ -6,12 +6,19 @@
 //   -> conv stack -> VelocityUpdate(pPred, UDiv_bc/scale) -> p, U *= scale -> SetWallBcs(U)
 // The reference runs this as ~25 cuDNN / THC / tfluids launches with dense temporaries per node
 // (mask tensors, JoinTable copies, ...). Here the non-conv nodes are three HBM-bound kernels:
-//   k_bcs_div_stats : U, flags -> U_bc (into the caller's U output buffer), div, and the per-sample
-//                     sum(u), sum(u^2) of U_bc accumulated in fp64 (one atomic pair per block)
+//   k_bcs_div_stats : U, flags -> div = VelocityDivergence(U_bc) and the per-sample sum(u), sum(u^2) of U_bc
+//                     as fp64 partial pairs, one per block (U_bc = SetWallBcs(U), formed in registers).
+//                     STORE form (tfl_model_begin, the z-slab step, the training forward, nets whose
+//                     input holds UDiv): U_bc is also written to the caller's U output buffer.
+//                     No-store form (the one-call forward of a net without a UDiv input): it is not --
+//                     nothing but k_project would read it.
 //   k_net_input     : pDiv, div, flags, stats -> the 3 input planes {pDiv/scale, div/scale, occ}
-//   k_project       : pPred, U_bc, flags, stats -> p = pPred*scale, U = SetWallBcs(VelocityUpdate(
-//                     U_bc/scale, pPred) * scale), optionally fused with simulate()'s trailing
-//                     setConstVals + clamp (lib/simulate.lua:321-326)
+//   k_project       : pPred, Uin, flags, stats -> p = pPred*scale, UOut = SetWallBcs(VelocityUpdate(
+//                     Uin/scale, pPred) * scale), optionally fused with simulate()'s trailing
+//                     setConstVals + clamp (lib/simulate.lua:321-326). Uin is U_bc where the STORE form
+//                     left it (Uin == UOut), or the caller's un-masked U (which may also be UOut): the
+//                     kernel's last step zeroes exactly the components SetWallBcs zeroed, whatever was
+//                     loaded for them, and every other component of U_bc is U's own word.
 #include "tfl_device.hpp"
 #include "tfl_fastmath.hpp"
 #include "tfl_host.hpp"
@@ -147,48 +154,6 @@ __device__ __forceinline__ void publish_and_maybe_reduce(const StatTail& tl, dou
   if (tid == 0) *tl.ticket = 0u;      // re-armed for the next launch (which starts behind this one on the stream)
 }
 
-// partials[block*2 + {0,1}] = this block's sum u, sum u^2 of U_bc (fp64). A second tiny kernel
-// (k_reduce_stats) adds the partials of each sample in a fixed order, so the scale is bit-reproducible
-// run to run and independent of how the grid is sharded -- no atomics (8192 same-address fp64 atomics
-// cost 0.2 ms at 128^3, 10x the kernel itself).
-template <bool IS3D, bool FOLD = false>
-__global__ __launch_bounds__(256) void k_bcs_div_stats(Dom d, const float* __restrict__ U, const float* __restrict__ flags,
-                                                       float* __restrict__ Ubc, float* __restrict__ div,
-                                                       double* __restrict__ partials, StatTail tl) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  int b, k; dom_bk(d, b, k);
-  const long long cells = d.sc;
-  const int C = IS3D ? 3 : 2;
-  double s1 = 0.0, s2 = 0.0;
-  if (i < d.X && j < d.Y) {
-    U += b * cells * C; Ubc += b * cells * C; flags += b * cells; div += b * cells;
-    const int o = TFL_AT(d, i, j, k);
-    bool zx, zy, zz;
-    wall_zero_mask<IS3D>(d, flags, i, j, k, o, zx, zy, zz);
-    const float ux = zx ? 0.0f : U[o];
-    const float uy = zy ? 0.0f : U[o + d.sc];
-    const float uz = IS3D ? (zz ? 0.0f : U[o + 2 * d.sc]) : 0.0f;
-    Ubc[o] = ux; Ubc[o + d.sc] = uy; if (IS3D) Ubc[o + 2 * d.sc] = uz;
-    s1 = (double)ux + (double)uy + (double)uz;
-    s2 = (double)ux * ux + (double)uy * uy + (double)uz * uz;
-    float dv = 0.0f;  // velocityDivergenceForward on U_bc, tfluids.cc:1008-1066
-    if (!on_border<IS3D>(d, i, j, k) && (((int)flags[o]) & kFluid)) {
-      dv = ux - u_bc_at<IS3D, 0>(d, U, flags, i + 1, j, k) + uy - u_bc_at<IS3D, 1>(d, U, flags, i, j + 1, k);
-      if (IS3D) dv += (uz - u_bc_at<IS3D, 2>(d, U, flags, i, j, k + 1));
-    }
-    div[o] = dv;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_down(s1, off, 64); s2 += __shfl_down(s2, off, 64); }
-  __shared__ double part[8];
-  const int tid = threadIdx.y * blockDim.x + threadIdx.x;
-  if ((tid & 63) == 0) { part[(tid >> 6) * 2] = s1; part[(tid >> 6) * 2 + 1] = s2; }
-  __syncthreads();
-  const long long blk = blockIdx.x + (long long)gridDim.x * (blockIdx.y + (long long)gridDim.y * ((long long)b * d.Z + k));
-  publish_and_maybe_reduce<FOLD>(tl, partials, blk, (part[0] + part[2]) + (part[4] + part[6]), (part[1] + part[3]) + (part[5] + part[7]), tid);
-}
-
 // k_bcs_div_stats with four x-cells per thread (tfl_vec4.hpp). The wall-BC masks of the cell's +x / +y / +z
 // neighbours (needed for the divergence of U_bc) are rebuilt in registers from the flag rows already
 // loaded for the cell's own mask plus four more rows (the stick test of the +y / +z neighbour looks two rows
@@ -219,191 +184,13 @@ __global__ __launch_bounds__(256) void k_wall_code(Dom d, const float* __restric
   code[o] = (unsigned short)m;
 }
 
-// k_bcs_div_stats_v4 on wall codes: the same loads of U, the same arithmetic and summation order, the same stores -- the flag
-// rows replaced by the code bytes of the cell's row, the row above (y + 1) and the plane above (z + 1)
-template <bool IS3D>
-__global__ __launch_bounds__(256, TFL_LB_BCS) void k_bcs_div_stats_code(Dom d, const float* __restrict__ U, const unsigned short* __restrict__ code,
-                                                                       float* __restrict__ Ubc, float* __restrict__ div,
-                                                                       double* __restrict__ partials, StatTail tl) {
-  const V4Ctx c = v4_ctx(d);
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  int b, k; dom_bk(d, b, k);
-  const bool live = c.i0 < d.X && j < d.Y;
-  const long long cells = d.sc;
-  const int C = IS3D ? 3 : 2;
-  U += b * cells * C; Ubc += b * cells * C; code += b * cells; div += b * cells;
-  const int o = TFL_AT(d, c.i0, j, k);
-  const bool yp = live && j < d.Y - 1, zp = live && IS3D && k < d.Z - 1;
-  // unconditional loads (tfl_vec4.hpp): a lane that must not read takes word 0 and drops it
-  const unsigned long long cc_v = *reinterpret_cast<const unsigned long long*>(code + (live ? o : 0));      // four 16-bit codes
-  const unsigned long long cy_v = *reinterpret_cast<const unsigned long long*>(code + (yp ? o + d.sy : 0));
-  const unsigned long long cz_v = *reinterpret_cast<const unsigned long long*>(code + (zp ? o + d.sz : 0));
-  const unsigned long long cc = live ? cc_v : 0ull, cy = yp ? cy_v : 0ull, cz = zp ? cz_v : 0ull;
-  float u[3][4], uyp[4], uzp[4];
-#pragma unroll
-  for (int a = 0; a < 3; a++) v4_load(U, o + a * d.sc, live && a < C, 0.0f, u[a]);
-  v4_load(U, o + d.sc + d.sy, yp, 0.0f, uyp);
-  v4_load(U, o + 2 * d.sc + d.sz, zp, 0.0f, uzp);
-  const bool need = c.last && live && c.has_r;
-  const int oo = o + 4;
-  const unsigned gcode = code[need ? oo : 0];
-  const float gu = U[need ? oo : 0];
-  double s1 = 0.0, s2 = 0.0;
-  float ubx[5];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const unsigned m = (unsigned)(cc >> (16 * q));
-    if (m & 1u) u[0][q] = 0.0f;
-    if (m & 2u) u[1][q] = 0.0f;
-    if (!IS3D || (m & 4u)) u[2][q] = 0.0f;
-    ubx[q] = u[0][q];
-    if (live) {
-      s1 += (double)u[0][q] + (double)u[1][q] + (double)u[2][q];
-      s2 += (double)u[0][q] * u[0][q] + (double)u[1][q] * u[1][q] + (double)u[2][q] * u[2][q];
-    }
-  }
-  ubx[4] = from_lane_above(ubx[0]);
-  if (c.last) ubx[4] = (need && !(gcode & 1u)) ? gu : 0.0f;
-  float dv[4];
-  const bool row_inner = live && j >= 1 && j <= d.Y - 2 && (!IS3D || (k >= 1 && k <= d.Z - 2));
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const int i = c.i0 + q;
-    dv[q] = 0.0f;
-    if (row_inner && i >= 1 && i <= d.X - 2 && ((unsigned)(cc >> (16 * q)) & 8u)) {   // tfluids.cc:1008-1066 on U_bc
-      const float by = ((unsigned)(cy >> (16 * q)) & 2u) ? 0.0f : uyp[q];
-      float t = u[0][q] - ubx[q + 1] + u[1][q] - by;
-      if (IS3D) {
-        const float bz = ((unsigned)(cz >> (16 * q)) & 4u) ? 0.0f : uzp[q];
-        t += (u[2][q] - bz);
-      }
-      dv[q] = t;
-    }
-  }
-  if (live) {
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-      if (a < C) v4_store(Ubc, o + a * d.sc, u[a]);
-    v4_store(div, o, dv);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_down(s1, off, 64); s2 += __shfl_down(s2, off, 64); }
-  __shared__ double part[8];
-  const int tid = threadIdx.y * blockDim.x + threadIdx.x;
-  if ((tid & 63) == 0) { part[(tid >> 6) * 2] = s1; part[(tid >> 6) * 2 + 1] = s2; }
-  __syncthreads();
-  const long long blk = blockIdx.x + (long long)gridDim.x * (blockIdx.y + (long long)gridDim.y * ((long long)b * d.Z + k));
-  publish_and_maybe_reduce<false>(tl, partials, blk, (part[0] + part[2]) + (part[4] + part[6]), (part[1] + part[3]) + (part[5] + part[7]), tid);
-}
-
-template <bool IS3D, bool FOLD = false>
-__global__ __launch_bounds__(256, TFL_LB_BCS) void k_bcs_div_stats_v4(Dom d, const float* __restrict__ U, const float* __restrict__ flags,
-                                                          float* __restrict__ Ubc, float* __restrict__ div,
-                                                          double* __restrict__ partials, StatTail tl) {
-  const V4Ctx c = v4_ctx(d);
-  const int j = blockIdx.y * blockDim.y + threadIdx.y;
-  int b, k; dom_bk(d, b, k);
-  const bool live = c.i0 < d.X && j < d.Y;
-  const long long cells = d.sc;
-  const int C = IS3D ? 3 : 2;
-  U += b * cells * C; Ubc += b * cells * C; flags += b * cells; div += b * cells;
-  const int o = TFL_AT(d, c.i0, j, k);
-  const bool ym = live && j > 0, yp = live && j < d.Y - 1, yp2 = live && j < d.Y - 2;
-  const bool zm = live && IS3D && k > 0, zp = live && IS3D && k < d.Z - 1, zp2 = live && IS3D && k < d.Z - 2;
-  // flag rows: own (6 wide), y-1, y+1 (6 wide), z-1, z+1 (6 wide); for the +y / +z neighbours' stick tests:
-  // (y+2,z), (y+1,z-1), (y+1,z+1), (y,z+2), (y-1,z+1)
-  float fc[6], fym[4], fyp[6], fzm[4], fzp[6], fyp2[4], fypzm[4], fypzp[4], fzp2[4], fymzp[4];
-  v4_load6<true, true>(c, flags, o, live, 0.0f, fc);
-  v4_load(flags, o - d.sy, ym, 0.0f, fym);
-  v4_load6<true, true>(c, flags, o + d.sy, yp, 0.0f, fyp);
-  v4_load(flags, o - d.sz, zm, 0.0f, fzm);
-  v4_load6<true, true>(c, flags, o + d.sz, zp, 0.0f, fzp);
-  v4_load(flags, o + 2 * d.sy, yp2, 0.0f, fyp2);
-  v4_load(flags, o + d.sy - d.sz, yp && zm, 0.0f, fypzm);
-  v4_load(flags, o + d.sy + d.sz, yp && zp, 0.0f, fypzp);
-  v4_load(flags, o + 2 * d.sz, zp2, 0.0f, fzp2);
-  v4_load(flags, o - d.sy + d.sz, ym && zp, 0.0f, fymzp);
-  float u[3][4], uyp[4], uzp[4];
-#pragma unroll
-  for (int a = 0; a < 3; a++) v4_load(U, o + a * d.sc, live && a < C, 0.0f, u[a]);
-  v4_load(U, o + d.sc + d.sy, yp, 0.0f, uyp);
-  v4_load(U, o + 2 * d.sc + d.sz, zp, 0.0f, uzp);
-  // what the last lane of a row segment needs of cell i0 + 4 (its wall-BC mask and U.x): issued here, with the row loads
-  // (loads unconditional, tfl_vec4.hpp v4_load: every lane reads -- the lanes that need nothing, cell 0 of the field)
-  const bool need = c.last && live && c.has_r;
-  const int oo = o + 4;
-  const float gym = flags[need && ym ? oo - d.sy : 0], gyp = flags[need && yp ? oo + d.sy : 0];
-  const float gzm = flags[need && zm ? oo - d.sz : 0], gzp = flags[need && zp ? oo + d.sz : 0];
-  const float gu = U[need ? oo : 0];
-  // own cells
-  double s1 = 0.0, s2 = 0.0;
-  float ubx[5];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    bool zx, zy, zz;
-    wall_mask_from<IS3D>((int)fc[q + 1], (int)fc[q], (int)fc[q + 2], (int)fym[q], (int)fyp[q + 1], (int)fzm[q], (int)fzp[q + 1],
-                         zx, zy, zz);
-    if (zx) u[0][q] = 0.0f;
-    if (zy) u[1][q] = 0.0f;
-    if (!IS3D || zz) u[2][q] = 0.0f;
-    ubx[q] = u[0][q];
-    if (live) {
-      s1 += (double)u[0][q] + (double)u[1][q] + (double)u[2][q];
-      s2 += (double)u[0][q] * u[0][q] + (double)u[1][q] * u[1][q] + (double)u[2][q] * u[2][q];
-    }
-  }
-  // U_bc.x of cell i0+4: the next lane's first cell, or (segment end) rebuilt from memory
-  ubx[4] = from_lane_above(ubx[0]);
-  {
-    if (c.last) {
-      float v = 0.0f;
-      if (need) {
-        const int f = (int)fc[5];
-        bool zx, zy, zz;
-        wall_mask_from<IS3D>(f, (int)fc[4], 0, ym ? (int)gym : 0, yp ? (int)gyp : 0, zm ? (int)gzm : 0, zp ? (int)gzp : 0, zx, zy, zz);
-        v = zx ? 0.0f : gu;
-      }
-      ubx[4] = v;
-    }
-  }
-  float dv[4];
-  const bool row_inner = live && j >= 1 && j <= d.Y - 2 && (!IS3D || (k >= 1 && k <= d.Z - 2));
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const int i = c.i0 + q;
-    dv[q] = 0.0f;
-    if (row_inner && i >= 1 && i <= d.X - 2 && (((int)fc[q + 1]) & kFluid)) {   // tfluids.cc:1008-1066 on U_bc
-      bool zx, zy, zz;
-      // +y neighbour (i, j+1, k): its -y neighbour is this cell
-      wall_mask_from<IS3D>((int)fyp[q + 1], (int)fyp[q], (int)fyp[q + 2], (int)fc[q + 1], (int)fyp2[q], (int)fypzm[q],
-                           (int)fypzp[q], zx, zy, zz);
-      const float by = zy ? 0.0f : uyp[q];
-      float t = u[0][q] - ubx[q + 1] + u[1][q] - by;
-      if (IS3D) {
-        // +z neighbour (i, j, k+1): its -z neighbour is this cell
-        wall_mask_from<IS3D>((int)fzp[q + 1], (int)fzp[q], (int)fzp[q + 2], (int)fymzp[q], (int)fypzp[q], (int)fc[q + 1],
-                             (int)fzp2[q], zx, zy, zz);
-        const float bz = zz ? 0.0f : uzp[q];
-        t += (u[2][q] - bz);
-      }
-      dv[q] = t;
-    }
-  }
-  if (live) {
-#pragma unroll
-    for (int a = 0; a < 3; a++)
-      if (a < C) v4_store(Ubc, o + a * d.sc, u[a]);
-    v4_store(div, o, dv);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_down(s1, off, 64); s2 += __shfl_down(s2, off, 64); }
-  __shared__ double part[8];
-  const int tid = threadIdx.y * blockDim.x + threadIdx.x;
-  if ((tid & 63) == 0) { part[(tid >> 6) * 2] = s1; part[(tid >> 6) * 2 + 1] = s2; }
-  __syncthreads();
-  const long long blk = blockIdx.x + (long long)gridDim.x * (blockIdx.y + (long long)gridDim.y * ((long long)b * d.Z + k));
-  publish_and_maybe_reduce<FOLD>(tl, partials, blk, (part[0] + part[2]) + (part[4] + part[6]), (part[1] + part[3]) + (part[5] + part[7]), tid);
-}
+// k_bcs_div_stats, k_bcs_div_stats_v4, k_bcs_div_stats_code (TFL_BCS_STORE 1) and their _nostore twins (0)
+#define TFL_BCS_STORE 1
+#include "model_bcs_stats.inc"
+#undef TFL_BCS_STORE
+#define TFL_BCS_STORE 0
+#include "model_bcs_stats.inc"
+#undef TFL_BCS_STORE
 
 // stats[b*2 + 0] = sum u, stats[b*2 + 1] = sum u^2 over all C*Z*Y*X values of U_bc[b]; one block per
 // sample, fixed summation order (strided accumulate, then a shared-memory tree).
@@ -566,8 +353,8 @@ __device__ __forceinline__ void publish_reach(const BcArgs& bc, bool first_threa
 
 template <bool IS3D>
 __global__ __launch_bounds__(256) void k_project(Dom d, const float* __restrict__ pPred, const float* __restrict__ flags,
-                                                 const double* __restrict__ stats, double count,
-                                                 float* __restrict__ Uio, float* __restrict__ pOut, BcArgs bc) {
+                                                 const double* __restrict__ stats, double count, const float* Uin,
+                                                 float* Uio, float* __restrict__ pOut, BcArgs bc) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int j = blockIdx.y * blockDim.y + threadIdx.y;
   int b, k; dom_bk(d, b, k);
@@ -576,11 +363,11 @@ __global__ __launch_bounds__(256) void k_project(Dom d, const float* __restrict_
   const long long cells = d.sc;
   const int C = IS3D ? 3 : 2;
   const float scale = scale_from_stats(stats, b, count);
-  pPred += b * cells; flags += b * cells; pOut += b * cells; Uio += b * cells * C;
+  pPred += b * cells; flags += b * cells; pOut += b * cells; Uio += b * cells * C; Uin += b * cells * C;
   const int o = TFL_AT(d, i, j, k);
   const float pc = pPred[o];
   float u[3];
-  u[0] = Uio[o] / scale; u[1] = Uio[o + d.sc] / scale; u[2] = IS3D ? Uio[o + 2 * d.sc] / scale : 0.0f;
+  u[0] = Uin[o] / scale; u[1] = Uin[o + d.sc] / scale; u[2] = IS3D ? Uin[o + 2 * d.sc] / scale : 0.0f;
   if (!on_border<IS3D>(d, i, j, k)) {  // velocityUpdateForward, tfluids.cc:1072-1156
     const int fc = (int)flags[o];
     const int fn[3] = {(int)flags[o - 1], (int)flags[o - d.sy], IS3D ? (int)flags[o - d.sz] : 0};
@@ -616,12 +403,14 @@ __global__ __launch_bounds__(256) void k_project(Dom d, const float* __restrict_
 
 // k_project with four consecutive x cells per thread (X % 4 == 0, 16-byte aligned rows): every access is
 // a 16-byte vector, the x-1 / x+4 neighbours are single scalar loads. Same per-cell arithmetic (bit-exact).
+// Uin (the velocity read) may be Uio (the velocity written), so neither is __restrict__: a thread reads the words of its own
+// four cells only, and all of them before it writes any.
 __device__ __forceinline__ void unpack4(const float4 v, float* o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
 
 template <bool IS3D, bool CODE = false>
 __global__ __launch_bounds__(256, TFL_LB_PROJECT) void k_project_v4(Dom d, const float* __restrict__ pPred, const float* __restrict__ flags,
-                                                    const double* __restrict__ stats, double count,
-                                                    float* __restrict__ Uio, float* __restrict__ pOut, BcArgs bc) {
+                                                    const double* __restrict__ stats, double count, const float* Uin,
+                                                    float* Uio, float* __restrict__ pOut, BcArgs bc) {
   const int i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
   const int j = blockIdx.y * blockDim.y + threadIdx.y;
   int b, k; dom_bk(d, b, k);
@@ -632,7 +421,7 @@ __global__ __launch_bounds__(256, TFL_LB_PROJECT) void k_project_v4(Dom d, const
   const float scale = scale_from_stats(stats, b, count);
   // the sticky reach word as it stands when the block starts (a uniform load, issued with the kernel's other loads: see the end)
   const float reach_seen = (IS3D && bc.reach_acc) ? *bc.reach_acc : 0.0f;
-  pPred += b * cells; flags += b * cells; pOut += b * cells; Uio += b * cells * C;
+  pPred += b * cells; flags += b * cells; pOut += b * cells; Uio += b * cells * C; Uin += b * cells * C;
   const int o = TFL_AT(d, i0, j, k);
   const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   // every load is unconditional (tfl_vec4.hpp v4_load: a predicated load costs a drained load queue at its join -- 16 in a
@@ -663,7 +452,7 @@ __global__ __launch_bounds__(256, TFL_LB_PROJECT) void k_project_v4(Dom d, const
   const float p_left = i0 > 0 ? p_left_v : 0.0f;
   float u[3][4];
 #pragma unroll
-  for (int c = 0; c < 3; c++) unpack4(ld4(Uio, o + c * d.sc, c < C), u[c]);
+  for (int c = 0; c < 3; c++) unpack4(ld4(Uin, o + c * d.sc, c < C), u[c]);
   float ubc[3][4], umk[3][4];
   bool bc_row = bc.UBC != nullptr;            // does a pair act on this thread's cells, and on which columns
   const float *pb = bc.UBC, *pm = bc.UInvMask;
@@ -860,7 +649,8 @@ void wall_code(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const floa
 }
 
 void model_pre(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* U, const float* flags, float* Ubc,
-               float* div, double* partials, double* stats, int zlo, int zhi, int stages, unsigned* ticket, const unsigned short* code) {
+               float* div, double* partials, double* stats, int zlo, int zhi, int stages, unsigned* ticket, const unsigned short* code,
+               bool store_ubc) {
   const Dom d = make_dom(sc, Z, Y, X);
   const dim3 blk(64, 4, 1), grd = TFL_GRID3(d, B);
   const Vec4Launch v = vec4_launch(B, d, {U, flags, Ubc, div});
@@ -882,7 +672,10 @@ void model_pre(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, 
   if (stages & 1) {
     if (v.ok && code && !fused) {      // round 6: the scene's wall codes instead of its flag words (tfl_wall_plan)
       TFL_TIMED_EXT("k_bcs_div_stats", st);
-      if (is3d) TFL_LAUNCH_EXT((k_bcs_div_stats_code<true>), v.grd, v.blk, 0, st, d, U, code, Ubc, div, partials, tl);
+      if (!store_ubc) {
+        if (is3d) TFL_LAUNCH_EXT((k_bcs_div_stats_code_nostore<true>), v.grd, v.blk, 0, st, d, U, code, Ubc, div, partials, tl);
+        else TFL_LAUNCH_EXT((k_bcs_div_stats_code_nostore<false>), v.grd, v.blk, 0, st, d, U, code, Ubc, div, partials, tl);
+      } else if (is3d) TFL_LAUNCH_EXT((k_bcs_div_stats_code<true>), v.grd, v.blk, 0, st, d, U, code, Ubc, div, partials, tl);
       else TFL_LAUNCH_EXT((k_bcs_div_stats_code<false>), v.grd, v.blk, 0, st, d, U, code, Ubc, div, partials, tl);
     } else if (v.ok) {
       TFL_TIMED_EXT("k_bcs_div_stats", st);
@@ -892,7 +685,10 @@ void model_pre(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, 
         else TFL_LAUNCH_EXT((k_bcs_div_stats_v4<false, true>), v.grd, v.blk, 0, st, d, U, flags, Ubc, div, partials, tl);
       } else
 #endif
-      {
+      if (!store_ubc) {
+        if (is3d) TFL_LAUNCH_EXT((k_bcs_div_stats_v4_nostore<true>), v.grd, v.blk, 0, st, d, U, flags, Ubc, div, partials, tl);
+        else TFL_LAUNCH_EXT((k_bcs_div_stats_v4_nostore<false>), v.grd, v.blk, 0, st, d, U, flags, Ubc, div, partials, tl);
+      } else {
         if (is3d) TFL_LAUNCH_EXT((k_bcs_div_stats_v4<true, false>), v.grd, v.blk, 0, st, d, U, flags, Ubc, div, partials, tl);
         else TFL_LAUNCH_EXT((k_bcs_div_stats_v4<false, false>), v.grd, v.blk, 0, st, d, U, flags, Ubc, div, partials, tl);
       }
@@ -904,7 +700,10 @@ void model_pre(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, 
         else k_bcs_div_stats<false, true><<<grd, blk, 0, st>>>(d, U, flags, Ubc, div, partials, tl);
       } else
 #endif
-      {
+      if (!store_ubc) {
+        if (is3d) k_bcs_div_stats_nostore<true><<<grd, blk, 0, st>>>(d, U, flags, Ubc, div, partials, tl);
+        else k_bcs_div_stats_nostore<false><<<grd, blk, 0, st>>>(d, U, flags, Ubc, div, partials, tl);
+      } else {
         if (is3d) k_bcs_div_stats<true, false><<<grd, blk, 0, st>>>(d, U, flags, Ubc, div, partials, tl);
         else k_bcs_div_stats<false, false><<<grd, blk, 0, st>>>(d, U, flags, Ubc, div, partials, tl);
       }
@@ -963,7 +762,7 @@ void model_skip_channel(hipStream_t st, int B, long long cells, const float* pDi
 }
 
 bool model_project(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* pPred, const float* flags,
-                   const double* stats, double count, float* Uio, float* pOut, const float* UBC, const float* UInvMask,
+                   const double* stats, double count, const float* Uin, float* Uio, float* pOut, const float* UBC, const float* UInvMask,
                    int do_clamp, float lo, float hi, const unsigned long long* range_src, unsigned long long* range_dst,
                    const float* reach_src, float* reach_dst, float* reach_acc, const unsigned short* wall_code, unsigned* reach_tick,
                    Fold& f) {
@@ -975,7 +774,7 @@ bool model_project(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int
   bc.reach_src = reach_dst ? reach_src : nullptr; bc.reach_dst = reach_dst;
   bc.reach_acc = nullptr; bc.wall_code = nullptr; bc.reach_tick = bc.reach_src ? reach_tick : nullptr;
   bc.UBC = UBC; bc.UInvMask = UInvMask; bc.fold = UBC ? no_fold() : f.hand_bc();
-  const uintptr_t al = (uintptr_t)pPred | (uintptr_t)flags | (uintptr_t)Uio | (uintptr_t)pOut | (uintptr_t)UBC |
+  const uintptr_t al = (uintptr_t)pPred | (uintptr_t)flags | (uintptr_t)Uin | (uintptr_t)Uio | (uintptr_t)pOut | (uintptr_t)UBC |
                        (uintptr_t)UInvMask;
   if (X % 4 == 0 && (al & 15) == 0 && !sw::present(Sw::NO_VEC4)) {
     const dim3 vb(32, 8, 1), vg((X / 4 + 31) / 32, (Y + 7) / 8, (unsigned)(d.nw * B));
@@ -985,14 +784,14 @@ bool model_project(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int
     TFL_TIMED_EXT("k_project", st);
     if (wall_code) {
       bc.wall_code = wall_code;
-      if (is3d) TFL_LAUNCH_EXT((k_project_v4<true, true>), vg, vb, 0, st, d, pPred, flags, stats, count, Uio, pOut, bc);
-      else TFL_LAUNCH_EXT((k_project_v4<false, true>), vg, vb, 0, st, d, pPred, flags, stats, count, Uio, pOut, bc);
-    } else if (is3d) TFL_LAUNCH_EXT((k_project_v4<true>), vg, vb, 0, st, d, pPred, flags, stats, count, Uio, pOut, bc);
-    else TFL_LAUNCH_EXT((k_project_v4<false>), vg, vb, 0, st, d, pPred, flags, stats, count, Uio, pOut, bc);
+      if (is3d) TFL_LAUNCH_EXT((k_project_v4<true, true>), vg, vb, 0, st, d, pPred, flags, stats, count, Uin, Uio, pOut, bc);
+      else TFL_LAUNCH_EXT((k_project_v4<false, true>), vg, vb, 0, st, d, pPred, flags, stats, count, Uin, Uio, pOut, bc);
+    } else if (is3d) TFL_LAUNCH_EXT((k_project_v4<true>), vg, vb, 0, st, d, pPred, flags, stats, count, Uin, Uio, pOut, bc);
+    else TFL_LAUNCH_EXT((k_project_v4<false>), vg, vb, 0, st, d, pPred, flags, stats, count, Uin, Uio, pOut, bc);
     return acc;
   }
-  if (is3d) { TFL_TIMED("k_project", st); k_project<true><<<grd, blk, 0, st>>>(d, pPred, flags, stats, count, Uio, pOut, bc); }
-  else { TFL_TIMED("k_project", st); k_project<false><<<grd, blk, 0, st>>>(d, pPred, flags, stats, count, Uio, pOut, bc); }
+  if (is3d) { TFL_TIMED("k_project", st); k_project<true><<<grd, blk, 0, st>>>(d, pPred, flags, stats, count, Uin, Uio, pOut, bc); }
+  else { TFL_TIMED("k_project", st); k_project<false><<<grd, blk, 0, st>>>(d, pPred, flags, stats, count, Uin, Uio, pOut, bc); }
   return false;
 }
 

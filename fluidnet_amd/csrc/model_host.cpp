@@ -759,7 +759,8 @@ int model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tens
   m->stat_pairs_per_plane = tfl::model_stat_pairs_per_plane(flags->B, flags->Z, flags->Y, flags->X, UDiv->data, flags->data, UOut->data, w.div);
   const unsigned short* code = wall_code_of(c, m, flags);
   tfl::model_pre(c->stream, sc, m->is3d, flags->B, flags->Z, flags->Y, flags->X, UDiv->data, flags->data, UOut->data,
-                 w.div, w.partials, stats ? stats : m->d_stats, zlo, zhi, ((stg & 2) ? 1 : 0) | ((stg & 4) ? 2 : 0), m->d_ticket, code);
+                 w.div, w.partials, stats ? stats : m->d_stats, zlo, zhi, ((stg & 2) ? 1 : 0) | ((stg & 4) ? 2 : 0), m->d_ticket, code,
+                 ask.project_reads == nullptr);
   return check_launch(c, "model_begin");
 }
 
@@ -806,8 +807,9 @@ int model_finish(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_ten
   }
   if (stg & 8) {
     const bool pub = ask.reach_via_project;
-    ask.reach_folded = tfl::model_project(a.st, sc, m->is3d, a.B, a.Z, a.Y, a.X, w.pPred, flags->data, a.st_in, a.count, UOut->data,
-                                          pOut->data, UBC ? UBC->data : nullptr, UBC ? UBCInvMask->data : nullptr, doClamp, lo, hi,
+    ask.reach_folded = tfl::model_project(a.st, sc, m->is3d, a.B, a.Z, a.Y, a.X, w.pPred, flags->data, a.st_in, a.count,
+                                          ask.project_reads ? ask.project_reads : UOut->data, UOut->data, pOut->data,
+                                          UBC ? UBC->data : nullptr, UBC ? UBCInvMask->data : nullptr, doClamp, lo, hi,
                                           m->d_range_host ? m->d_range_err : nullptr, m->d_range_host, pub ? c->d_reach : nullptr,
                                           pub ? c->d_reach_host : nullptr, pub ? c->d_reach : nullptr, wall_code_of(c, m, flags),
                                           pub ? c->d_reach_tick : nullptr, ask.fold);
@@ -826,6 +828,20 @@ int model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_te
   // order, the same bits) -- no k_reduce_stats launch between the two kernels (4.3 us of pure latency at 128^3)
   ask.conv1_sums_stats = m && m->path == ConvPath::conv_mfma16 && conv3_m16_first_sums_partials() && !conv3_m16_fuse12_requested() &&
                          !model_stats_fold_requested();
+  // SetWallBcs(UDiv) is an intermediate of this call: where the net's input has no UDiv channel and the input scale is not taken
+  // from a pass over it (opts_stats), only the projection would read it back from UOut -- and that kernel zeroes the very
+  // components the wall BCs zeroed, so it reads UDiv itself and the store is left out (model.hip header).
+  // tfl_model_begin / _finish, the z-slab step and the training forward keep the store: their callers find U_bc in UOut.
+  // So does a call whose UDiv lies inside its own workspace (tfl_simulate_step without a confinement force hands over the
+  // advection's scratch velocity, which shares the step's workspace with this call): the conv stack overwrites it before the
+  // projection runs, and U_bc in UOut is then the only copy.
+  bool keep = !m || !UDiv || !UDiv->data || m->opts.in_UDiv || (m->custom && m->opts.norm_chan == TFL_NORM_UDIV);
+  if (!keep && workspace) {
+    const uintptr_t u0 = (uintptr_t)UDiv->data, u1 = u0 + sizeof(float) * (size_t)UDiv->B * UDiv->C * UDiv->Z * UDiv->Y * UDiv->X;
+    const uintptr_t w0 = (uintptr_t)workspace, w1 = w0 + sizeof(float) * (size_t)(workspace_floats > 0 ? workspace_floats : 0);
+    keep = u0 < w1 && w0 < u1;
+  }
+  ask.project_reads = keep ? nullptr : UDiv->data;
   TRY(model_begin(c, m, UDiv, flags, UOut, workspace, workspace_floats, 0, flags->Z, nullptr, sc, ask));
   const double count = (double)flags->Z * flags->Y * flags->X * (m->is3d ? 3 : 2);
   return model_finish(c, m, pDiv, flags, pOut, UOut, workspace, workspace_floats, nullptr, count, UBC, UBCInvMask, doClamp, lo, hi, sc, ask);
@@ -1120,7 +1136,7 @@ int tfl_model_forward_train(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, co
   std::vector<float*> outs;
   for (size_t l = 0; l < m->layers.size(); l++) outs.push_back(l + 1 < m->layers.size() ? tape + t.out[l] : w.pPred);
   TRY(generic_forward(c, m, w, a, outs.data()));
-  tfl::model_project(a.st, sc, m->is3d, B, Z, Y, X, w.pPred, flags->data, a.st_in, a.count, UOut->data, pOut->data, nullptr, nullptr, 0,
+  tfl::model_project(a.st, sc, m->is3d, B, Z, Y, X, w.pPred, flags->data, a.st_in, a.count, UOut->data, UOut->data, pOut->data, nullptr, nullptr, 0,
                      0.0f, 0.0f, nullptr, nullptr, nullptr, nullptr, nullptr, wall_code_of(c, m, flags), nullptr, ask.fold);
   HIP_TRY(c, hipMemcpyAsync(tape + t.stats, m->d_stats, sizeof(double) * 2 * B, hipMemcpyDeviceToDevice, c->stream));
   return check_launch(c, who);

@@ -226,7 +226,8 @@ bool model_stats_fold_requested();
 long long model_stat_pairs_per_plane(int B, int Z, int Y, int X, const float* U, const float* flags, const float* Ubc, const float* div);   // as model_pre lays them out
 void model_pre(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* U, const float* flags, float* Ubc,
                float* div, double* partials, double* stats, int zlo, int zhi, int stages = 3, unsigned* ticket = nullptr,
-               const unsigned short* wall_code = nullptr);      // wall_code: the flags' tfl_wall_plan (round 6), or null
+               const unsigned short* wall_code = nullptr,       // wall_code: the flags' tfl_wall_plan (round 6), or null
+               bool store_ubc = true);      // false: SetWallBcs(U) is not written to Ubc (div and the sums are the same; model.hip header)
 void wall_code(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* flags, unsigned short* code);
 // (z0 / nz, here and in the two below: the planes [z0, z0 + nz) only; nz < 0 = every plane)
 void model_net_input(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* pDiv, const float* div,
@@ -246,8 +247,10 @@ void model_field_stats_planes(hipStream_t st, int B, int C, int Z, long long yx,
 void model_skip_channel(hipStream_t st, int B, long long cells, const float* pDiv, const double* stats, double count,
                         float* dst, int och, int ch, long long t0 = 0, long long nt = -1);     // cells [t0, t0 + nt) only
 // returns true when the launch also folded max |u_z| of what it wrote into *reach_acc (round 6: k_project_v4 on full blocks)
+// Uin: the velocity it reads -- Uio itself where model_pre stored SetWallBcs(U) there, or the un-masked U model_pre read (the
+// same result, model.hip header); Uio: the velocity it writes
 bool model_project(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* pPred, const float* flags,
-                   const double* stats, double count, float* Uio, float* pOut, const float* UBC, const float* UInvMask,
+                   const double* stats, double count, const float* Uin, float* Uio, float* pOut, const float* UBC, const float* UInvMask,
                    int do_clamp, float lo, float hi, const unsigned long long* range_src, unsigned long long* range_dst,
                    const float* reach_src, float* reach_dst, float* reach_acc, const unsigned short* wall_code, unsigned* reach_tick,
                    Fold& f);

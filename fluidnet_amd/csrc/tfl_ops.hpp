@@ -13,6 +13,8 @@ struct Ask {
   bool two_launch = false;         // vorticityConfinementFrom: the two launches even where the fused kernel would run
   bool gated = true;               // model_begin / model_forward: take the fp16 range gate (a step takes it once, at its entry)
   bool conv1_sums_stats = false;   // model_begin / model_finish (model_forward sets it): the first conv layer sums the partials itself
+  const float* project_reads = nullptr;   // model_forward sets it to UDiv where nothing but the projection would read SetWallBcs(UDiv):
+                                   // model_begin then leaves UOut alone, model_finish's projection reads the velocity here
   bool reach_via_project = false;  // model_finish: the projection (stage 8) publishes the z-slab reach word (tfl_ctx.hpp d_reach) ...
   bool reach_published = false;    // ... out: it was launched so,
   bool reach_folded = false;       // ... out: and folded max|u_z| of the planes it wrote into the word

@@ -402,7 +402,8 @@ int64_t tfl_model_workspace_floats(const tfl_model* model, int B, int Z, int Y, 
  * modified; pOut may alias pDiv and UOut may alias UDiv (simulate.lua:270-272 copies the prediction
  * back into the state, which this makes free). When UBC/UBCInvMask are non-NULL the tail of
  * simulate() -- U = U*UBCInvMask + UBC and, if doClamp, clamp(U, lo, hi) (simulate.lua:321-326) -- is
- * fused into the last kernel. */
+ * fused into the last kernel. UDiv is read again by that last kernel (unless it lies inside `workspace`): it must not be
+ * written by anyone else while the call is in flight on the stream. */
 int tfl_model_forward(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* pDiv, const tfl_tensor* UDiv,
                       const tfl_tensor* flags, const tfl_tensor* pOut, const tfl_tensor* UOut,
                       float* workspace, int64_t workspace_floats, const tfl_tensor* UBC,
