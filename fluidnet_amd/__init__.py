@@ -5,6 +5,7 @@
   fluidnet_amd.model      the `default` projection ConvNet (lib/model.lua) over tfl_model_forward
   fluidnet_amd.stats      host mirror of the rollout of torch/lib/calc_stats.lua (calcStats: divergence norm over time)
   fluidnet_amd.train      ProjectionNet: the net as a torch.nn.Module over tfl_model_forward_train / tfl_model_backward
+  fluidnet_amd.optim      Adam / RMSprop: gradient clip + lib/adam.lua / lib/rmsprop.lua + weight refresh over tfl_optim_step
   fluidnet_amd.criterion  nn.FluidCriterion (torch/lib/modules/fluid_criterion.lua) over tfl_fluidCriterion
   fluidnet_amd.dist       z-slab decomposition across GPUs: halo exchange + 1 all-reduce per step (RCCL)
   fluidnet_amd.csrc/      hand-written HIP kernels for gfx950 + the C ABI (include/tfluids_hip.h)
@@ -17,5 +18,6 @@ from . import criterion  # noqa: F401
 from .criterion import FluidCriterion  # noqa: F401  (nn.FluidCriterion: loss terms and input gradients in one pass)
 from .simulate import calcPUTargets  # noqa: F401  (the training targets by a Jacobi / PCG projection)
 from .train import ProjectionNet  # noqa: F401  (the projection net as an nn.Module: forward with a tape, parameter gradients)
+from . import optim  # noqa: F401  (optim.Adam / optim.RMSprop: clip + update + weight refresh as one device call)
 from . import modules  # noqa: F401  (the tfluids nn.Modules as torch.nn.Modules with autograd)
 from ._lib import TfluidsError  # noqa: F401

@@ -17,6 +17,9 @@ KERNEL_SOURCE = {
     "k_bcs_div_stats": "model.hip", "k_reduce_stats": "model.hip", "k_project": "model.hip", "k_net_input": "model.hip",
     "k_apply_bcs_indexed": "model.hip", "k_bc_scan": "model.hip",
     "k_conv_wgrad": "conv_bwd.hip+tfl_train.hpp", "k_conv_wgrad_finish": "conv_bwd.hip+tfl_train.hpp", "k_scale_add": "conv_bwd.hip",
+    "k_refresh_layers": "weights_refresh.hip+tfl_refresh.hpp", "k_refresh_pack": "weights_refresh.hip+tfl_refresh.hpp",
+    "k_refresh_pack16": "weights_refresh.hip+tfl_refresh.hpp",
+    "k_optim_norm": "optim.hip+tfl_refresh.hpp", "k_optim_update": "optim.hip+tfl_refresh.hpp", "k_optim_advance": "optim.hip",
 }
 # the default conv path can be switched by TFL_CONV_PATH; these are the files behind the same profiler names then
 CONV_SOURCE = {"winograd": "conv_valu.hip", "mfma": "conv_mfma.hip", "direct": "conv.hip", "mfma16": "conv_mfma16.hip"}

@@ -23,6 +23,13 @@ class tfl_model_opts(ctypes.Structure):
                                               "nonlin", "pressure_skip")]
 
 
+class tfl_optim_config(ctypes.Structure):
+    """include/tfluids_hip.h tfl_optim_config"""
+    _fields_ = [("method", ctypes.c_int32)] + \
+               [(n, ctypes.c_double) for n in ("learningRate", "learningRateDecay", "beta1", "beta2", "epsilon", "weightDecay",
+                                               "alpha", "initialMean", "gradNormThreshold")]
+
+
 class tfl_model_graph(ctypes.Structure):
     """include/tfluids_hip.h tfl_model_graph"""
     _PP = ctypes.POINTER(ctypes.POINTER(ctypes.c_float))
@@ -156,6 +163,14 @@ SIGNATURES = {
     "tfl_model_backward_workspace_floats": (_c.c_int64, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "tfl_model_backward": (_c.c_int, [_c.c_void_p, _c.c_void_p, _T, _T, _T, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
                                       _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.c_int]),
+    "tfl_model_set_weights_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p)]),
+    "tfl_optim_create": (_c.c_void_p, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "tfl_optim_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
+                                  _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p)]),
+    "tfl_optim_set_config": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "tfl_optim_steps": (_c.c_int64, [_c.c_void_p, _c.c_void_p]),
+    "tfl_optim_get_state": (_c.c_int64, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "tfl_optim_destroy": (None, [_c.c_void_p, _c.c_void_p]),
     "tfl_set_dx_override": (_c.c_int, [_c.c_void_p, _c.c_float]),
     "tfl_velocityDivergenceBackward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int, _T]),
     "tfl_velocityUpdateBackward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _T, _c.c_int, _T]),

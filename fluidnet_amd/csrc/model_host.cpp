@@ -10,6 +10,7 @@
 
 #include "tfl_abi.hpp"
 #include "tfl_ops.hpp"
+#include "tfl_refresh.hpp"
 #include "tfl_train.hpp"
 
 using tfl::fail; using tfl::check_flags; using tfl::check_vel; using tfl::check_scalar; using tfl::check_launch;
@@ -80,6 +81,12 @@ struct tfl_model {
   int bank_down = 1;          // bank 1's finest resolution inside [split, join) = grid / bank_down (bank i: / 2^(i-1) more, mres)
   int split_c = 0;            // channels entering the split (the mres pyramid's planes)
   int split_down = 1;         // resolution at the split = grid / split_down
+  // tfl_model_set_weights_device: the device tables of its launches (refresh_tables, at creation; null: more than
+  // kRefreshMaxLayers layers) and the words its fp16 launch leaves the post-scales in
+  tfl::RefreshLayer* d_refresh = nullptr;
+  tfl::PackJob* d_jobs = nullptr;
+  int njobs = 0, refresh_elems = 0, job_elems = 0;     // (..._elems: the most destination elements of one table entry)
+  float* d_post16 = nullptr;                           // [4]: post16[0..2], post16_tail
 };
 
 namespace {
@@ -265,6 +272,44 @@ tfl_model* build_layers(tfl_ctx* c, bool is3d, int n, const int32_t* cin, const 
   return m;
 }
 
+// The device tables of tfl_model_set_weights_device, once the model's buffers exist: one RefreshLayer per layer (destinations
+// and the parameters of upload_layer's map) and one PackJob per fp32 buffer of a default topology. False on a HIP failure.
+bool refresh_tables(tfl_model* m) {
+  const int n = (int)m->layers.size();
+  if (n > tfl::kRefreshMaxLayers) return true;       // (the device refresh refuses such a model; everything else works)
+  std::vector<tfl::RefreshLayer> tab;
+  for (const tfl_layer& L : m->layers) {
+    tfl::RefreshLayer r{};
+    r.w = L.w; r.b = L.b; r.wt = L.wt;
+    r.taps = m->is3d ? L.k * L.k * L.k : L.k * L.k;
+    r.S = m->is3d ? L.up * L.up * L.up : L.up * L.up;
+    r.cin = L.cin; r.cout = L.cout; r.cin_ref = L.cin_ref; r.cout_ref = L.cout_ref;
+    r.join_c = L.join_c; r.join_p = L.join_p; r.skip_in = L.skip_in ? 1 : 0;
+    r.cin_t = L.cin - (L.skip_in ? 1 : 0);
+    r.n_w = r.S * r.taps * r.cin * r.cout; r.n_b = r.S * r.cout; r.n_wt = L.wt ? r.taps * r.cout * r.cin_t : 0;
+    m->refresh_elems = std::max(m->refresh_elems, r.n_w + r.n_b + r.n_wt);
+    tab.push_back(r);
+  }
+  if (!upload(m->d_refresh, tab.data(), tab.size() * sizeof(tfl::RefreshLayer))) return false;
+  std::vector<tfl::PackJob> jobs;
+  auto job = [&](float* dst, int kind, int layer, int ci_n, int cnt) { if (dst) jobs.push_back(tfl::PackJob{dst, kind, layer, ci_n, cnt}); };
+  if (default3(m->path)) {
+    for (int l = 0; l < 3; l++) job(m->bfrag[l], tfl::kPackBfrag3, l, m->layers[l].cin_ref, m->layers[l].cin_ref * 9 * 64);
+    job(m->tail_w4, tfl::kPackCopy, 3, 8, 64);
+    job(m->tail_w5, tfl::kPackCopy, 4, 8, 8);
+    // (the fp16 launch writes the tail's post-scale behind the 89 floats; the fp32 paths keep a zero there)
+    job(m->tail_pack, tfl::kPackTail3, 2, 8, m->path == ConvPath::conv_mfma16 ? tfl::kTailPackFloats - 1 : tfl::kTailPackFloats);
+    for (int l = 0; l < 3; l++) job(m->wino[l], tfl::kPackWino3, l, m->layers[l].cin_ref, 9 * 4 * m->layers[l].cin_ref * 8);
+    if (m->path == ConvPath::conv_mfma16 && hipMalloc((void**)&m->d_post16, 4 * sizeof(float)) != hipSuccess) return false;
+  } else if (m->path == ConvPath::conv2d_mfma) {
+    for (int l = 0; l < 4; l++) job(m->bfrag2[l], tfl::kPackBfrag2, l, m->layers[l].cin_ref, 9 * ((m->layers[l].cin_ref + 3) / 4) * 64);
+    job(m->tail_w5, tfl::kPackCopy, 4, 16, 16);
+  }
+  for (const tfl::PackJob& j : jobs) m->job_elems = std::max(m->job_elems, j.n);
+  m->njobs = (int)jobs.size();
+  return jobs.empty() || upload(m->d_jobs, jobs.data(), jobs.size() * sizeof(tfl::PackJob));
+}
+
 // TFL_CONV_PATH -> the form of the 3-D default topology ("direct" never gets here: it keeps the generic kernels)
 ConvPath conv3d_path(const char* force) {
   if (!force || !*force || strcmp(force, "mfma16") == 0) return ConvPath::conv_mfma16;
@@ -278,17 +323,8 @@ ConvPath conv3d_path(const char* force) {
 const char* pack_default3(tfl_model* m, const int32_t* cin, const float* const* weights, const float* const* biases, ConvPath path) {
   m->path = path;
   for (int l = 0; l < 3; l++) {
-    const int ci_n = cin[l];
-    std::vector<float> frag((size_t)ci_n * 9 * 64);
-    for (int c = 0; c < ci_n; c++)
-      for (int kz = 0; kz < 3; kz++)
-        for (int ky = 0; ky < 3; ky++)
-          for (int lane = 0; lane < 64; lane++) {
-            const int k = lane >> 4, n = lane & 15, ph = n >> 3, co = n & 7, kx = k - ph;
-            float v = 0.0f;
-            if (kx >= 0 && kx <= 2) v = weights[l][((((size_t)co * ci_n + c) * 3 + kz) * 3 + ky) * 3 + kx];
-            frag[(((size_t)c * 3 + kz) * 3 + ky) * 64 + lane] = v;
-          }
+    std::vector<float> frag;
+    tfl::pack_bfrag3(weights[l], cin[l], frag);
     if (!upload(m->bfrag[l], frag.data(), frag.size() * sizeof(float))) return "uploading MFMA weight fragments failed";
   }
   if (!upload(m->tail_w4, weights[3], 64 * sizeof(float)) || !upload(m->tail_w5, weights[4], 8 * sizeof(float)))
@@ -312,25 +348,13 @@ const char* pack_default3(tfl_model* m, const int32_t* cin, const float* const* 
     }
   }
   if (path == ConvPath::conv_mfma) return nullptr;
-  std::vector<float> tp(8 + 64 + 8 + 8 + 1 + 1);
-  for (int i = 0; i < 8; i++) tp[i] = biases[2][i];
-  for (int i = 0; i < 64; i++) tp[8 + i] = weights[3][i];
-  for (int i = 0; i < 8; i++) { tp[72 + i] = biases[3][i]; tp[80 + i] = weights[4][i]; }
-  tp[88] = biases[4][0];
-  tp[89] = m->post16_tail;        // conv_mfma16.hip kTailPost4 (0 on the fp32 paths, which do not read it)
+  std::vector<float> tp;
+  tfl::pack_tail3(weights, biases, m->post16_tail, tp);
   if (!upload(m->tail_pack, tp.data(), tp.size() * sizeof(float))) return "uploading tail weights failed";
-  // the three k = 3 layers' weights, Winograd-transformed along x: U = (g0, (g0 + g1 + g2)/2, (g0 - g1 + g2)/2, g2) over the
-  // three x-taps of every (dz, dy, c_in, c_out)
+  // the three k = 3 layers' weights, Winograd-transformed along x
   for (int l = 0; l < 3; l++) {
-    const int ci_n = cin[l];
-    std::vector<float> u((size_t)9 * 4 * ci_n * 8);
-    for (int co = 0; co < 8; co++)
-      for (int c = 0; c < ci_n; c++)
-        for (int zy = 0; zy < 9; zy++) {
-          const float* g = weights[l] + (((size_t)co * ci_n + c) * 9 + zy) * 3;
-          const float uu[4] = {g[0], 0.5f * ((g[0] + g[2]) + g[1]), 0.5f * ((g[0] + g[2]) - g[1]), g[2]};
-          for (int p = 0; p < 4; p++) u[(((size_t)zy * ci_n + c) * 4 + p) * 8 + co] = uu[p];
-        }
+    std::vector<float> u;
+    tfl::pack_wino3(weights[l], cin[l], u);
     if (!upload(m->wino[l], u.data(), u.size() * sizeof(float))) return "uploading transformed weights failed";
   }
   return nullptr;
@@ -340,15 +364,8 @@ const char* pack_default3(tfl_model* m, const int32_t* cin, const float* const* 
 const char* pack_default2(tfl_model* m, const int32_t* cin, const float* const* weights) {
   m->path = ConvPath::conv2d_mfma;
   for (int l = 0; l < 4; l++) {
-    const int ci_n = cin[l], c4n = (ci_n + 3) / 4;
-    // B[k][n] of MFMA (tap, c4): lane = k*16 + n holds w[n][4*c4 + k][dy][dx] (0 for padded channels)
-    std::vector<float> frag((size_t)9 * c4n * 64);
-    for (int tap = 0; tap < 9; tap++)
-      for (int c4 = 0; c4 < c4n; c4++)
-        for (int lane = 0; lane < 64; lane++) {
-          const int k = lane >> 4, n = lane & 15, c = 4 * c4 + k;
-          frag[((size_t)tap * c4n + c4) * 64 + lane] = c < ci_n ? weights[l][((size_t)n * ci_n + c) * 9 + tap] : 0.0f;
-        }
+    std::vector<float> frag;
+    tfl::pack_bfrag2(weights[l], cin[l], frag);
     if (!upload(m->bfrag2[l], frag.data(), frag.size() * sizeof(float))) return "uploading 2-D MFMA weight fragments failed";
   }
   if (!upload(m->tail_w5, weights[4], 16 * sizeof(float))) return "uploading tail weights failed";
@@ -872,8 +889,13 @@ tfl_model* tfl_model_create_opts(tfl_ctx* c, int is3D, int nlayers, const int32_
   tfl_model* m = build_layers(c, is3D != 0, nlayers, cin, cout, ksize, pool, up, weights, biases, o, stage_table(nlayers), nullptr);
   if (!m) return nullptr;
   // the default topologies run on kernels of their own (TFL_CONV_PATH=direct forces the generic ones)
+  auto done = [&]() -> tfl_model* {      // the tables of tfl_model_set_weights_device, now that every buffer exists
+    if (refresh_tables(m)) return m;
+    tfl_model_destroy(c, m);
+    return bad("hipMalloc failed");
+  };
   const char* force = tfl::sw::text(tfl::Sw::CONV_PATH);
-  if ((force && strcmp(force, "direct") == 0) || m->custom || m->multires || nlayers != 5) return m;
+  if ((force && strcmp(force, "direct") == 0) || m->custom || m->multires || nlayers != 5) return done();
   const int dflt3[5][3] = {{3, 8, 3}, {8, 8, 3}, {8, 8, 3}, {8, 8, 1}, {8, 1, 1}};
   const int dflt2[5][3] = {{3, 16, 3}, {16, 16, 3}, {16, 16, 3}, {16, 16, 3}, {16, 1, 1}};
   auto is = [&](const int (&t)[5][3]) {
@@ -884,7 +906,7 @@ tfl_model* tfl_model_create_opts(tfl_ctx* c, int is3D, int nlayers, const int32_
   if (m->is3d && is(dflt3)) err = pack_default3(m, cin, weights, biases, conv3d_path(force));
   if (!m->is3d && is(dflt2)) err = pack_default2(m, cin, weights);
   if (err) { tfl_model_destroy(c, m); return bad(err); }
-  return m;
+  return done();
 }
 
 // Every defineModelGraph configuration (include/tfluids_hip.h tfl_model_create_graph; lib/model.lua:253-392). The trivial
@@ -933,6 +955,7 @@ tfl_model* tfl_model_create_graph(tfl_ctx* c, int is3D, int nconv, const int32_t
   m->path = ConvPath::graph; m->banks = N; m->bank_type = g->bank_type; m->aggregate = g->aggregate;
   m->split = t.split; m->join = t.join; m->nstages = nst;
   m->pool_max = g->pool_type == TFL_POOL_MAX;
+  if (!refresh_tables(m)) { tfl_model_destroy(c, m); return bad("hipMalloc failed"); }
   return m;
 }
 
@@ -952,6 +975,9 @@ void tfl_model_destroy(tfl_ctx* c, tfl_model* m) {
   if (m->tail_w5) (void)hipFree(m->tail_w5);
   if (m->d_stats) (void)hipFree(m->d_stats);
   if (m->d_ticket) (void)hipFree(m->d_ticket);
+  if (m->d_refresh) (void)hipFree(m->d_refresh);
+  if (m->d_jobs) (void)hipFree(m->d_jobs);
+  if (m->d_post16) (void)hipFree(m->d_post16);
   delete m;
 }
 
@@ -1061,6 +1087,20 @@ int train_gate(tfl_ctx* c, const tfl_model* m, const char* who) {
                                      "backward of pooling and of the pixel shuffle is not built", who);
   return TFL_OK;
 }
+// what tfl_model_set_weights_device (and so tfl_optim_step) cannot do, said before anything is launched
+int refresh_gate(tfl_ctx* c, const tfl_model* m, const char* who) {
+  if (!m->d_refresh)
+    return fail(c, TFL_EUNSUPPORTED, "%s: models of more than %d layers take their weights from the host (tfl_model_set_weights)", who,
+                tfl::kRefreshMaxLayers);
+  if (m->path == ConvPath::conv_mfma16) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(c, hipStreamIsCapturing(c->stream, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+      return fail(c, TFL_EUNSUPPORTED, "%s: the split-fp16 MFMA path reads its three post-scales back to the host, which a "
+                                       "capturing stream cannot do (create the model under another TFL_CONV_PATH to capture)", who);
+  }
+  return TFL_OK;
+}
 std::vector<tfl::TrainLayer> train_layers(const tfl_model* m) {
   std::vector<tfl::TrainLayer> v;
   for (const tfl_layer& L : m->layers) v.push_back(tfl::TrainLayer{L.cin, L.cout, L.cin_ref, L.cout_ref, L.k, L.skip_in ? 1 : 0});
@@ -1100,6 +1140,31 @@ int tfl_model_set_weights(tfl_ctx* c, tfl_model* m, const float* const* weights,
   else if (m->path == ConvPath::conv2d_mfma) err = pack_default2(m, cin.data(), weights);
   if (err) return fail(c, TFL_EHIP, "model_set_weights: %s", err);
   return TFL_OK;
+}
+
+int tfl_model_set_weights_device(tfl_ctx* c, tfl_model* m, const float* const* d_weights, const float* const* d_biases) {
+  if (!c) return TFL_EINVAL;
+  const char* who = "model_set_weights_device";
+  if (!m || !d_weights || !d_biases) return fail(c, TFL_EINVAL, "%s: null model or weight table", who);
+  const int n = (int)m->layers.size();
+  for (int l = 0; l < n; l++)
+    if (!d_weights[l] || !d_biases[l]) return fail(c, TFL_EINVAL, "%s: layer %d has no weight or no bias", who, l);
+  TRY(refresh_gate(c, m, who));
+  tfl::RefreshSrc src{};
+  for (int l = 0; l < n; l++) { src.w[l] = d_weights[l]; src.b[l] = d_biases[l]; }
+  tfl::refresh_layers(c->stream, src, m->d_refresh, n, m->refresh_elems);
+  if (m->njobs > 0) tfl::refresh_pack(c->stream, src, m->d_jobs, m->njobs, m->job_elems);
+  if (m->path == ConvPath::conv_mfma16) {
+    tfl::refresh_pack16(c->stream, src, m->wfrag16, m->d_post16, m->tail_pack);
+    TRY(check_launch(c, who));
+    // the one host read: the conv kernels of this path take the three post-scales by value. (m->post16_tail is NOT refreshed: the
+    // kernels read the tail's post-scale from tail_pack[89], which the launch above wrote; the host field is only the value
+    // pack_default3 hands from conv3_m16_pack_tail to pack_tail3 within one host packing, and is recomputed there before use.)
+    HIP_TRY(c, hipMemcpyAsync(m->post16, m->d_post16, 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return TFL_OK;
+  }
+  return check_launch(c, who);
 }
 
 int64_t tfl_model_tape_floats(const tfl_model* m, int B, int Z, int Y, int X) {
@@ -1212,6 +1277,126 @@ int tfl_model_backward(tfl_ctx* c, tfl_model* m, const tfl_tensor* flags, const 
     std::swap(g, g2);
   }
   return check_launch(c, who);
+}
+
+}  // extern "C"
+
+// ---- the optimiser step on the device: state, the hyper-parameters by value, then the refresh above ----------
+struct tfl_optim {
+  tfl_model* model = nullptr;
+  tfl_optim_config cfg{};
+  int ntens = 0;                 // 2 per layer: weight, bias
+  long long total = 0;           // parameters
+  long long* d_off = nullptr;    // [ntens + 1] prefix offsets of the tensors in the flat parameter space
+  float* m = nullptr;            // [total] first moment (RMSprop: the mean square)
+  float* v = nullptr;            // [total] second moment (Adam)
+  long long* d_t = nullptr;      // the step counter
+  double* d_partials = nullptr;  // [kOptimNormBlocks] partial sums of g^2
+};
+
+namespace {
+int optim_config_ok(tfl_ctx* c, const tfl_optim_config* k, const char* who) {
+  if (!k) return fail(c, TFL_EINVAL, "%s: null config", who);
+  if (k->method != TFL_OPTIM_ADAM && k->method != TFL_OPTIM_RMSPROP) return fail(c, TFL_EINVAL, "%s: unknown optimisation method", who);
+  for (double x : {k->learningRate, k->learningRateDecay, k->beta1, k->beta2, k->epsilon, k->weightDecay, k->alpha, k->initialMean, k->gradNormThreshold})
+    if (!std::isfinite(x)) return fail(c, TFL_EINVAL, "%s: a hyper-parameter is not finite", who);
+  return TFL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+tfl_optim* tfl_optim_create(tfl_ctx* c, tfl_model* m, const tfl_optim_config* config) {
+  if (!c) return nullptr;
+  const char* who = "optim_create";
+  if (!m) { fail(c, TFL_EINVAL, "%s: null model", who); return nullptr; }
+  if (optim_config_ok(c, config, who) != TFL_OK) return nullptr;
+  if ((int)m->layers.size() > tfl::kRefreshMaxLayers) { fail(c, TFL_EUNSUPPORTED, "%s: more than %d layers", who, tfl::kRefreshMaxLayers); return nullptr; }
+  tfl_optim* o = new tfl_optim();
+  o->model = m; o->cfg = *config;
+  std::vector<long long> off(1, 0);
+  for (const tfl_layer& L : m->layers) {
+    const long long taps = m->is3d ? L.k * L.k * L.k : L.k * L.k, S = m->is3d ? L.up * L.up * L.up : L.up * L.up;
+    off.push_back(off.back() + (long long)L.cout_ref * S * L.cin_ref * taps);
+    off.push_back(off.back() + (long long)L.cout_ref * S);
+  }
+  o->ntens = (int)off.size() - 1; o->total = off.back();
+  const size_t bytes = sizeof(float) * (size_t)o->total;
+  const bool adam = config->method == TFL_OPTIM_ADAM;
+  bool ok = hipMalloc((void**)&o->d_off, off.size() * sizeof(long long)) == hipSuccess &&
+            hipMemcpy(o->d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMalloc((void**)&o->m, bytes) == hipSuccess && (!adam || hipMalloc((void**)&o->v, bytes) == hipSuccess) &&
+            hipMalloc((void**)&o->d_t, sizeof(long long)) == hipSuccess &&
+            hipMalloc((void**)&o->d_partials, sizeof(double) * tfl::kOptimNormBlocks) == hipSuccess &&
+            hipMemsetAsync(o->d_t, 0, sizeof(long long), c->stream) == hipSuccess &&
+            hipMemsetAsync(o->m, 0, bytes, c->stream) == hipSuccess && (!adam || hipMemsetAsync(o->v, 0, bytes, c->stream) == hipSuccess);
+  if (ok && !adam && config->initialMean != 0.0) tfl::optim_fill(c->stream, o->m, o->total, (float)config->initialMean);
+  if (!ok || check_launch(c, who) != TFL_OK) { if (!ok) fail(c, TFL_EHIP, "%s: hipMalloc failed", who); tfl_optim_destroy(c, o); return nullptr; }
+  return o;
+}
+
+int tfl_optim_set_config(tfl_ctx* c, tfl_optim* o, const tfl_optim_config* config) {
+  if (!c) return TFL_EINVAL;
+  if (!o) return fail(c, TFL_EINVAL, "optim_set_config: null optimiser");
+  TRY(optim_config_ok(c, config, "optim_set_config"));
+  if (config->method != o->cfg.method) return fail(c, TFL_EINVAL, "optim_set_config: the method is fixed at creation");
+  o->cfg = *config;
+  return TFL_OK;
+}
+
+int tfl_optim_step(tfl_ctx* c, tfl_optim* o, float* const* d_weights, float* const* d_biases, float* const* d_gradWeights,
+                   float* const* d_gradBiases) {
+  if (!c) return TFL_EINVAL;
+  const char* who = "optim_step";
+  if (!o || !d_weights || !d_biases || !d_gradWeights || !d_gradBiases) return fail(c, TFL_EINVAL, "%s: null optimiser or parameter table", who);
+  const int n = o->ntens / 2;
+  tfl::OptimPtrs p{};
+  for (int l = 0; l < n; l++) {
+    if (!d_weights[l] || !d_biases[l] || !d_gradWeights[l] || !d_gradBiases[l])
+      return fail(c, TFL_EINVAL, "%s: layer %d lacks a parameter or a gradient array", who, l);
+    p.x[2 * l] = d_weights[l]; p.x[2 * l + 1] = d_biases[l];
+    p.g[2 * l] = d_gradWeights[l]; p.g[2 * l + 1] = d_gradBiases[l];
+  }
+  TRY(refresh_gate(c, o->model, who));
+  const tfl_optim_config& k = o->cfg;
+  const bool adam = k.method == TFL_OPTIM_ADAM;
+  tfl::OptimArgs a{};
+  a.method = adam ? 0 : 1;
+  a.b1 = (float)k.beta1; a.omb1 = (float)(1.0 - k.beta1);
+  a.b2 = (float)(adam ? k.beta2 : k.alpha); a.omb2 = (float)(1.0 - (adam ? k.beta2 : k.alpha));
+  a.eps = (float)k.epsilon; a.wd = (float)k.weightDecay;
+  a.lr = k.learningRate; a.lrd = k.learningRateDecay; a.beta1 = k.beta1; a.beta2 = k.beta2;
+  a.threshold = k.gradNormThreshold > 0.0 ? k.gradNormThreshold : 0.0;
+  tfl::optim_step(c->stream, p, o->d_off, o->ntens, o->total, o->d_partials, o->m, o->v, o->d_t, a);
+  TRY(check_launch(c, who));
+  return tfl_model_set_weights_device(c, o->model, d_weights, d_biases);
+}
+
+int64_t tfl_optim_steps(tfl_ctx* c, tfl_optim* o) {
+  if (!c || !o) return -1;
+  long long t = 0;
+  if (hipMemcpyAsync(&t, o->d_t, sizeof(t), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return -1;
+  if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
+  return (int64_t)t;
+}
+
+int64_t tfl_optim_get_state(tfl_ctx* c, tfl_optim* o, float* d_m, float* d_v) {
+  if (!c || !o) return -1;
+  const size_t bytes = sizeof(float) * (size_t)o->total;
+  if (d_m && hipMemcpyAsync(d_m, o->m, bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return -1;
+  if (d_v && o->v && hipMemcpyAsync(d_v, o->v, bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) return -1;
+  return (int64_t)o->total;
+}
+
+void tfl_optim_destroy(tfl_ctx* c, tfl_optim* o) {
+  (void)c;
+  if (!o) return;
+  if (o->d_off) (void)hipFree(o->d_off);
+  if (o->m) (void)hipFree(o->m);
+  if (o->v) (void)hipFree(o->v);
+  if (o->d_t) (void)hipFree(o->d_t);
+  if (o->d_partials) (void)hipFree(o->d_partials);
+  delete o;
 }
 
 }  // extern "C"

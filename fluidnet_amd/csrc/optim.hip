@@ -1,0 +1,111 @@
+// optim.hip -- the optimiser step of the training closure on the device (tfl_optim_step): the gradient clip of
+// lib/run_epoch.lua:304-312, weight decay, and lib/adam.lua / lib/rmsprop.lua, over the flat parameter space of
+// tfl_refresh.hpp (tensor 2 l = layer l's weight, 2 l + 1 = its bias; the caller's device pointers travel by value).
+// Three launches at the most: k_optim_norm leaves one fp64 partial of sum g^2 per block at a fixed place, k_optim_update adds
+// them in index order (every block the same sum: no atomics, the same bits every call), clips, decays and updates each
+// element in fp32 in the reference's operation order, and k_optim_advance moves the step counter -- a kernel, so that a captured
+// step advances on replay.
+#include <hip/hip_runtime.h>
+
+#include "tfl_host.hpp"
+#include "tfl_refresh.hpp"
+
+namespace tfl {
+namespace {
+
+__global__ __launch_bounds__(kOptimThreads) void k_optim_norm(OptimPtrs p, const long long* __restrict__ off, int ntens, long long total,
+                                                             double* __restrict__ partials) {
+  __shared__ long long s_off[kOptimMaxTensors + 1];
+  __shared__ double red[kOptimThreads];
+  for (int i = threadIdx.x; i <= ntens; i += kOptimThreads) s_off[i] = off[i];
+  __syncthreads();
+  long long lo, hi;
+  optim_chunk(total, gridDim.x, blockIdx.x, &lo, &hi);
+  double s = 0.0;
+  for (long long i = lo + threadIdx.x; i < hi; i += kOptimThreads) {
+    const int t = optim_tensor_of(s_off, ntens, i);
+    const double g = (double)p.g[t][i - s_off[t]];
+    s += g * g;
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = kOptimThreads / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(kOptimThreads) void k_optim_update(OptimPtrs p, const long long* __restrict__ off, int ntens, long long total,
+                                                               const double* __restrict__ partials, int npartials,
+                                                               float* __restrict__ m, float* __restrict__ v,
+                                                               const long long* __restrict__ t_ptr, OptimArgs c) {
+  __shared__ long long s_off[kOptimMaxTensors + 1];
+  __shared__ float s_div, s_step;
+  __shared__ int s_clip;
+  for (int i = threadIdx.x; i <= ntens; i += kOptimThreads) s_off[i] = off[i];
+  if (threadIdx.x == 0) {
+    s_clip = 0; s_div = 1.0f;
+    if (partials) {
+      double sum = 0.0;
+      for (int b = 0; b < npartials; b++) sum += partials[b];
+      const double norm = sqrt(sum);
+      if (norm > c.threshold) { s_clip = 1; s_div = (float)(norm / c.threshold); }
+    }
+    if (c.method == 0) {     // Adam: clr from t before the increment, the bias corrections from the new t, in fp64, rounded once
+      const double t0 = (double)*t_ptr, t1 = t0 + 1.0;
+      const double clr = c.lr / (1.0 + t0 * c.lrd);
+      s_step = (float)-(clr * sqrt(1.0 - pow(c.beta2, t1)) / (1.0 - pow(c.beta1, t1)));
+    } else s_step = (float)-c.lr;
+  }
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * kOptimThreads + threadIdx.x;
+  if (i >= total) return;
+  const int t = optim_tensor_of(s_off, ntens, i);
+  const long long e = i - s_off[t];
+  float x = p.x[t][e], g = p.g[t][e];
+  if (s_clip) g = __fdiv_rn(g, s_div);
+  if (c.wd != 0.0f) g = g + c.wd * x;
+  if (s_clip || c.wd != 0.0f) p.g[t][e] = g;
+  if (c.method == 0) {
+    const float mi = m[i] * c.b1 + c.omb1 * g;
+    const float vi = v[i] * c.b2 + (c.omb2 * g) * g;
+    m[i] = mi; v[i] = vi;
+    x = x + __fdiv_rn(s_step * mi, __fsqrt_rn(vi) + c.eps);
+  } else {
+    const float mi = m[i] * c.b2 + (c.omb2 * g) * g;
+    m[i] = mi;
+    x = x + __fdiv_rn(s_step * g, __fsqrt_rn(mi) + c.eps);
+  }
+  p.x[t][e] = x;
+}
+
+__global__ void k_optim_advance(long long* t) { *t += 1; }
+__global__ __launch_bounds__(kOptimThreads) void k_optim_fill(float* p, long long n, float val) {
+  const long long i = (long long)blockIdx.x * kOptimThreads + threadIdx.x;
+  if (i < n) p[i] = val;
+}
+}  // namespace
+
+void optim_step(hipStream_t st, const OptimPtrs& p, const long long* d_off, int ntens, long long total, double* d_partials, float* m,
+                float* v, long long* d_t, const OptimArgs& c) {
+  const bool clip = c.threshold > 0.0;
+  if (clip) {
+    TFL_TIMED("k_optim_norm", st);
+    hipLaunchKernelGGL(k_optim_norm, dim3(kOptimNormBlocks), dim3(kOptimThreads), 0, st, p, d_off, ntens, total, d_partials);
+  }
+  const unsigned nb = (unsigned)((total + kOptimThreads - 1) / kOptimThreads);
+  {
+    TFL_TIMED("k_optim_update", st);
+    hipLaunchKernelGGL(k_optim_update, dim3(nb), dim3(kOptimThreads), 0, st, p, d_off, ntens, total, clip ? (const double*)d_partials : nullptr,
+                       kOptimNormBlocks, m, v, (const long long*)d_t, c);
+  }
+  TFL_TIMED("k_optim_advance", st);
+  hipLaunchKernelGGL(k_optim_advance, dim3(1), dim3(1), 0, st, d_t);
+}
+void optim_fill(hipStream_t st, float* p, long long n, float val) {
+  if (n < 1) return;
+  hipLaunchKernelGGL(k_optim_fill, dim3((unsigned)((n + kOptimThreads - 1) / kOptimThreads)), dim3(kOptimThreads), 0, st, p, n, val);
+}
+
+}  // namespace tfl

@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "tfl_device.hpp"
+#include "tfl_pack.hpp"
 #include "tfl_switches.hpp"
 
 struct tfl_model;
@@ -363,9 +364,7 @@ bool conv3_m16_first2_fused(hipStream_t st, const Scope& sc, int B, int Z, int Y
                             const double* stats, double count, const void* wfrag1, const float* bias1, float post1,
                             const void* wfrag2, const float* bias2, float post2, void* out_h2, unsigned long long* range_err);
 bool conv3_m16_fuse12_requested();      // EXPERIMENTS flavour + TFL_M16_FUSE12=1 (the default library: always false)
-size_t conv3_m16_frag_halves(int cin);
-float conv3_m16_pack_tail(const float* w4 /* [8][8] (out, in) */, uint16_t* frag_buf_of_a_cin8_layer);
-float conv3_m16_pack_weights(const float* w, int cin, uint16_t* out);
+// (conv3_m16_frag_halves / conv3_m16_pack_tail / conv3_m16_pack_weights, the host packers of wfrag: tfl_pack.hpp)
 
 // backward.hip
 void velocity_divergence_bwd(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const float* flags,
@@ -388,6 +387,18 @@ void conv_wgrad_finish(hipStream_t st, const WgPlan& p, int cin, int cout, int c
                        float* gw, float* gb, int accumulate);
 // dst[b][t] = scale_b * src[b][t] (+ add[b][t]) over `per` floats per batch item; scale_b from the (sum, sum of squares) pairs
 void scale_add(hipStream_t st, int B, long long per, const double* stats, double count, const float* src, const float* add, float* dst);
+
+// weights_refresh.hip: the device-side weight refresh (tfl_model_set_weights_device), one launch each. d_table / d_jobs: the model's
+// device tables (tfl_refresh.hpp); max_elems: the most destination elements of one entry (sizes the grid's x).
+struct RefreshSrc; struct RefreshLayer; struct PackJob; struct OptimPtrs; struct OptimArgs;
+void refresh_layers(hipStream_t st, const RefreshSrc& src, const RefreshLayer* d_table, int nlayers, int max_elems);
+void refresh_pack(hipStream_t st, const RefreshSrc& src, const PackJob* d_jobs, int njobs, int max_elems);
+// the split-fp16 fragments of the 3-D default topology's three k = 3 layers and tail; d_post[4] = their post-scales
+void refresh_pack16(hipStream_t st, const RefreshSrc& src, void* const* wfrag16, float* d_post, float* tail_pack);
+// optim.hip: clip + weight decay + Adam / RMSprop over the flat parameter space (tfl_optim_step): at most three launches
+void optim_step(hipStream_t st, const OptimPtrs& p, const long long* d_off, int ntens, long long total, double* d_partials, float* m,
+                float* v, long long* d_t, const OptimArgs& c);
+void optim_fill(hipStream_t st, float* p, long long n, float val);
 
 // conv2d_mfma.hip (2-D default topology: 16 channels, k = 3; one MFMA = one tap x four input channels)
 void conv2_mfma_first_fused(hipStream_t st, int B, int Y, int X, const float* pDiv, const float* div, const float* flags,

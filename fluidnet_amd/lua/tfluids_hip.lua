@@ -179,6 +179,22 @@ int64_t tfl_model_backward_workspace_floats(const tfl_model* model, int B, int Z
 int tfl_model_backward(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* flags, const tfl_tensor* gradP,
                        const tfl_tensor* gradU, const float* tape, int64_t tape_floats, float* workspace,
                        int64_t workspace_floats, float* const* gradWeights, float* const* gradBiases, int accumulate);
+int tfl_model_set_weights_device(tfl_ctx* ctx, tfl_model* model, const float* const* d_weights, const float* const* d_biases);
+enum { TFL_OPTIM_ADAM = 0, TFL_OPTIM_RMSPROP = 1 };
+typedef struct tfl_optim tfl_optim;
+typedef struct {
+  int32_t method;
+  double learningRate, learningRateDecay, beta1, beta2, epsilon, weightDecay;
+  double alpha, initialMean;
+  double gradNormThreshold;
+} tfl_optim_config;
+tfl_optim* tfl_optim_create(tfl_ctx* ctx, tfl_model* model, const tfl_optim_config* config);
+int tfl_optim_step(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights, float* const* d_biases,
+                   float* const* d_gradWeights, float* const* d_gradBiases);
+int tfl_optim_set_config(tfl_ctx* ctx, tfl_optim* opt, const tfl_optim_config* config);
+int64_t tfl_optim_steps(tfl_ctx* ctx, tfl_optim* opt);
+int64_t tfl_optim_get_state(tfl_ctx* ctx, tfl_optim* opt, float* d_m, float* d_v);
+void tfl_optim_destroy(tfl_ctx* ctx, tfl_optim* opt);
 int tfl_set_dx_override(tfl_ctx* ctx, float dx);
 int tfl_applyBCs(tfl_ctx* ctx, const tfl_tensor* x, const tfl_tensor* bc, const tfl_tensor* invMask,
                  int doClamp, float lo, float hi);
@@ -629,6 +645,69 @@ function Model:backward(flags, gradP, gradU, gradWeights, gradBiases, accumulate
   check(lib.tfl_model_backward(ctx, self.handle, T(flags), gradP and T(gradP) or nil, gradU and T(gradU) or nil,
                                ffi.cast('const float*', torch.data(self.tape)), self.tape:nElement(),
                                ffi.cast('float*', torch.data(self.bwdWork)), self.bwdWork:nElement(), gw, gb, b2i(accumulate == true)))
+end
+
+-- model:setWeightsDevice(weights, biases): the same from CudaTensors where they lie -- every weight form rebuilt by kernels on the
+-- context's stream, no host copy and no synchronisation (the 3-D default model on its fp16 path reads 12 bytes back: header)
+local function devptrs(ts, ctype)
+  local p = ffi.new(ctype .. '[?]', #ts)
+  for i = 1, #ts do
+    assert(ts[i]:isContiguous(), 'parameter tensors must be contiguous')
+    p[i - 1] = ffi.cast(ctype, torch.data(ts[i]))
+  end
+  return p
+end
+function Model:setWeightsDevice(weights, biases)
+  check(lib.tfl_model_set_weights_device(ctx, self.handle, devptrs(weights, 'const float*'), devptrs(biases, 'const float*')))
+end
+
+-- ---- hip.Optim(model, method, config, gradNormThreshold): the closure's clip + optim.adam / optim.rmsprop + weight refresh as
+-- ONE asynchronous call on the CudaTensors of the parameters and their gradients (tfl_optim_*). method: 'adam' | 'rmsprop';
+-- config: the optimState table (learningRate, learningRateDecay, beta1, beta2, epsilon, weightDecay, alpha, initialMean; the
+-- defaults of lib/adam.lua / lib/rmsprop.lua where absent); gradNormThreshold nil or <= 0: no clip.
+--   local opt = hip.Optim(model, mconf.optimizationMethod, mconf.optimState, mconf.gradNormThreshold)
+--   opt:step(weights, biases, gradWeights, gradBiases)      -- tables of CudaTensors, one per convolution
+local Optim = {}
+Optim.__index = Optim
+local function optim_config(method, config, threshold)
+  local c = ffi.new('tfl_optim_config')
+  config = config or {}
+  if method == 'adam' then
+    c.method = lib.TFL_OPTIM_ADAM
+    c.learningRate = config.learningRate or 0.001
+    c.beta1, c.beta2 = config.beta1 or 0.9, config.beta2 or 0.999
+    c.learningRateDecay = config.learningRateDecay or 0
+  elseif method == 'rmsprop' then
+    c.method = lib.TFL_OPTIM_RMSPROP
+    c.learningRate = config.learningRate or 1e-2
+    c.alpha, c.initialMean = config.alpha or 0.99, config.initialMean or 0
+  else
+    error("hip.Optim: optimizationMethod must be 'adam' or 'rmsprop' (optim.sgd is Torch's own)", 3)
+  end
+  c.epsilon, c.weightDecay = config.epsilon or 1e-8, config.weightDecay or 0
+  c.gradNormThreshold = threshold or 0
+  return c
+end
+function M.Optim(model, method, config, gradNormThreshold)
+  local self = setmetatable({model = model, method = method}, Optim)
+  local c = optim_config(method, config, gradNormThreshold)
+  local h = lib.tfl_optim_create(ctx, model.handle, c)
+  if h == nil then error(ffi.string(lib.tfl_last_error(ctx)), 2) end
+  self.handle = ffi.gc(h, function(q) lib.tfl_optim_destroy(ctx, q) end)
+  return self
+end
+function Optim:setConfig(config, gradNormThreshold)
+  check(lib.tfl_optim_set_config(ctx, self.handle, optim_config(self.method, config, gradNormThreshold)))
+end
+function Optim:step(weights, biases, gradWeights, gradBiases)
+  check(lib.tfl_optim_step(ctx, self.handle, devptrs(weights, 'float*'), devptrs(biases, 'float*'), devptrs(gradWeights, 'float*'),
+                           devptrs(gradBiases, 'float*')))
+end
+function Optim:steps() return tonumber(lib.tfl_optim_steps(ctx, self.handle)) end
+-- opt:state(m, v): copies the moments into the CudaTensors m and v (v: Adam only; either may be nil); returns their length
+function Optim:state(m, v)
+  return tonumber(lib.tfl_optim_get_state(ctx, self.handle, m and ffi.cast('float*', torch.data(m)) or nil,
+                                          v and ffi.cast('float*', torch.data(v)) or nil))
 end
 
 -- ---- tfluids.simulate as ONE native call (lib/simulate.lua:175-327 = fluidnet_amd/csrc/simulate.cpp) -----------------

@@ -2,11 +2,10 @@
 closure (model:forward ... model:backward, torch/lib/run_epoch.lua:207-235, 269-293) over tfl_model_forward_train /
 tfl_model_backward; fluidnet_amd.FluidCriterion is the middle. Parameter gradients only: the reference computes a gradInput
 and run_epoch.lua throws it away, so gradients to pDiv, UDiv and flags are not built, and asking for one raises.
-Optimisers are torch.optim's.
+Optimisers: torch.optim's, or the fused device step of fluidnet_amd.optim (clip + Adam / RMSprop + refresh in one call).
 """
 import ctypes
 
-import numpy as np
 import torch
 
 from . import tfluids
@@ -43,8 +42,10 @@ class ProjectionNet(torch.nn.Module):
 
     train(): forward(pDiv, UDiv, flags) -> (p, U) runs tfl_model_forward_train under autograd; .backward() of anything built on
     p and U (FluidCriterion's loss) accumulates the parameters' .grad. eval(): FluidNetModel.forward, the inference path.
-    The native model holds its own re-laid-out copy of the weights: it is refreshed (tfl_model_set_weights) whenever a
-    parameter's version counter has moved since the last push -- every optimiser step moves it -- or by push_parameters().
+    The native model holds its own re-laid-out copy of the weights: it is refreshed on the device, from the parameters where
+    they lie (tfl_model_set_weights_device: no host copy, no synchronisation), whenever a parameter's version counter has moved
+    since the last push -- every torch.optim step moves it -- or by push_parameters(). The host copy `layers` follows lazily:
+    when something reads it, or when a handle is created on a device that has none.
     Accepted wherever simulate() takes a model. Linear models without pooling / upsampling layers can be trained; the others
     run in eval mode only (training raises, naming the reason)."""
 
@@ -58,22 +59,28 @@ class ProjectionNet(torch.nn.Module):
         self.biases = torch.nn.ParameterList([torch.nn.Parameter(torch.from_numpy(b.copy()).to(dev)) for _, b in net.layers])
         self._pushed = self._versions()      # the native model is created from net.layers = these values
         self._pushes = 0                     # times the native model's weights have changed (a backward checks its forward's count)
+        self._host_stale = False             # net.layers is older than the parameters (brought up to date by _host_sync)
         self._bwd_work = None
 
     # -- the FluidNetModel surface simulate() and the z-slab step use ------------------------------------------------
     is3D = property(lambda self: self.net.is3D)
-    layers = property(lambda self: self.net.layers)
+
+    @property
+    def layers(self):
+        self._host_sync()
+        return self.net.layers
+
     opts = property(lambda self: self.net.opts)
     _work = property(lambda self: self.net._work)
     _handles = property(lambda self: self.net._handles)
 
     def _handle(self, lib, ctx, dev):
-        self._sync()
+        self._sync(dev)
         return self.net._handle(lib, ctx, dev)
 
-    def begin(self, *a, **k):
-        self._sync()
-        return self.net.begin(*a, **k)
+    def begin(self, U, *a, **k):
+        self._sync(U.device.index)
+        return self.net.begin(U, *a, **k)
 
     def finish(self, *a, **k):
         return self.net.finish(*a, **k)
@@ -88,55 +95,90 @@ class ProjectionNet(torch.nn.Module):
     def _versions(self):
         return tuple((p._version, p.device) for p in self.parameters())
 
-    def _sync(self):
+    def _sync(self, dev=None):
+        """the native model up to date with the parameters; dev: the device the caller is about to run on -- a handle created
+        there starts from the host copy, so that is brought up to date first"""
         if self._versions() != self._pushed:
-            self.push_parameters()
+            self._push_device()
+        if dev is not None and dev not in self.net._handles:
+            self._host_sync()
 
-    def push_parameters(self):
-        """Copy the parameters into the native model (synchronous). Called by itself when a parameter's version has moved; call
-        it after changing parameter storage behind autograd's back (p.data.copy_ does move the counter; a raw pointer write
-        does not). A z-slab step graph recorded on this model must be re-recorded afterwards."""
-        host = [(w.detach().cpu().contiguous().numpy(), b.detach().cpu().contiguous().numpy())
-                for w, b in zip(self.weights, self.biases)]
-        for (w, b), (w0, b0) in zip(host, self.net.layers):
-            if w.shape != w0.shape or b.shape != b0.shape or w.dtype != np.float32:
+    def _param_arrays(self):
+        for p, (w0, b0) in zip(self.weights, self.net.layers):
+            if tuple(p.shape) != w0.shape or p.dtype != torch.float32 or not p.is_contiguous():
                 raise TfluidsError("parameter shapes / dtype no longer match the model's layers")
-        self.net.layers = host                 # a handle created later (another device) starts from these
-        dev = self.weights[0].device.index
-        for d in [d for d in self.net._handles if d != dev]:      # re-created from net.layers on next use
+        for p, (w0, b0) in zip(self.biases, self.net.layers):
+            if tuple(p.shape) != b0.shape or p.dtype != torch.float32 or not p.is_contiguous():
+                raise TfluidsError("parameter shapes / dtype no longer match the model's layers")
+        return _ptr_array(list(self.weights)), _ptr_array(list(self.biases))
+
+    def _drop_other_handles(self, dev):
+        """the native models on devices other than the parameters' own hold the old weights: destroyed here, re-created from
+        the host copy (brought up to date first: _sync) on next use"""
+        for d in [d for d in self.net._handles if d != dev]:
             lib, ctx = tfluids._context(torch.empty(0, device="cuda:%d" % d))
             lib.tfl_model_destroy(ctx, self.net._handles.pop(d))
+
+    def _push_device(self):
+        """tfl_model_set_weights_device on the current stream: every weight form of the native model rebuilt from the
+        parameters where they lie. (The 3-D default model on its fp16 MFMA path ends with a 12-byte read-back: see the header.)"""
+        ws, bs = self._param_arrays()
+        dev = self.weights[0].device.index
+        self._host_stale = True
+        self._drop_other_handles(dev)
         h = self.net._handles.get(dev)
         if h is not None:
             lib, ctx = tfluids._context(self.weights[0])
-            FP = ctypes.POINTER(ctypes.c_float)
-            n = len(host)
-            ws = (FP * n)(*[w.ctypes.data_as(FP) for w, _ in host])
-            bs = (FP * n)(*[b.ctypes.data_as(FP) for _, b in host])
-            tfluids._call(lib, ctx, lib.tfl_model_set_weights(ctx, h, ws, bs))
+            tfluids._call(lib, ctx, lib.tfl_model_set_weights_device(ctx, h, ws, bs))
         self._pushed = self._versions()
         self._pushes += 1
+
+    def _host_sync(self):
+        """net.layers = the parameters' values (a device-to-host copy: synchronises), if they have changed since it was taken"""
+        if not self._host_stale:
+            return
+        self.net.layers = [(w.detach().cpu().contiguous().numpy(), b.detach().cpu().contiguous().numpy())
+                           for w, b in zip(self.weights, self.biases)]
+        self._host_stale = False
+
+    def _stepped_on_device(self):
+        """fluidnet_amd.optim: a fused step has rewritten the parameters behind autograd's version counters and refreshed the
+        native model on the parameters' device from them itself: no second push is due there, but a backward whose forward saw the
+        old weights is refused, and a native model on any other device is dropped as after a push. (A captured step REPLAYED by
+        its graph does not come through here: see fluidnet_amd.optim.)"""
+        self._drop_other_handles(self.weights[0].device.index)
+        self._pushed = self._versions()
+        self._pushes += 1
+        self._host_stale = True
+
+    def push_parameters(self):
+        """Copy the parameters into the native model and into the host copy, and wait for it (synchronous). Call it after
+        changing parameter storage behind autograd's back (p.data.copy_ does move the counter, and the next forward pushes by
+        itself; a raw pointer write does not). A z-slab step graph recorded on this model must be re-recorded afterwards."""
+        self._push_device()
+        self._host_sync()
+        torch.cuda.current_stream(self.weights[0].device).synchronize()
 
     # -- forward -----------------------------------------------------------------------------------------------------
     def forward(self, pDiv, UDiv=None, flags=None, **kw):
         """forward(pDiv, UDiv, flags) -> (p, U). Also forward([pDiv, UDiv, flags], out=..., UBC=..., ...) -> [p, U]: the call
         shape of FluidNetModel.forward that simulate() uses (inference path, whatever the mode)."""
         if UDiv is None:
-            self._sync()
+            self._sync(pDiv[0].device.index)
             return self.net.forward(pDiv, **kw)
         for name, t in (("pDiv", pDiv), ("UDiv", UDiv), ("flags", flags)):
             if t.requires_grad:
                 raise TfluidsError("ProjectionNet: %s requires grad, but input gradients are not built (parameter gradients "
                                    "only): detach it" % name)
         if not (self.training and torch.is_grad_enabled()):
-            self._sync()
+            self._sync(pDiv.device.index)
             p, U = self.net.forward([pDiv, UDiv, flags])
             return p, U
         return _ForwardTrain.apply(self, pDiv, UDiv, flags, *self.weights, *self.biases)
 
     def forward_train(self, pDiv, UDiv, flags):
         """(p, U, tape) = tfl_model_forward_train: the forward on the shape-generic fp32 kernels and what backward() reads."""
-        self._sync()
+        self._sync(flags.device.index)
         tfluids._dims(UDiv, flags)
         tfluids._check(pDiv.shape == flags.shape and pDiv.is_contiguous(), "Size mismatch")
         tfluids._check((UDiv.size(1) == 3) == self.net.is3D, "model / input dimensionality mismatch")

@@ -467,6 +467,61 @@ int tfl_model_backward(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* flags, 
                        const tfl_tensor* gradU, const float* tape, int64_t tape_floats, float* workspace,
                        int64_t workspace_floats, float* const* gradWeights, float* const* gradBiases, int accumulate);
 
+/* tfl_model_set_weights with DEVICE pointers (cudnn layout, one weight and one bias array per layer, as tfl_model_create takes
+ * them from the host): every weight form the model's path holds is rebuilt by kernels enqueued on the context's stream, into
+ * the buffers it already has -- byte for byte what tfl_model_set_weights produces from the same values. No host read of a
+ * parameter value, no stream synchronisation, capturable; launches that read the old weights were enqueued earlier on the same
+ * stream and finish first. One gather launch covers the generic forms of all layers, one the fp32 forms of a default topology
+ * (MFMA fragments, Winograd transform, tail packs), one the split-fp16 fragments: three launches at the most, none per layer.
+ * The arrays must stay valid until those launches have run. Batch-norm folds are not parameters here and stay as they are.
+ * ONE EXCEPTION: a 3-D default model on the split-fp16 MFMA path (TFL_CONV_PATH unset or "mfma16") hands its three per-layer
+ * post-scales to its conv kernels by value, so on that path only the call ends by reading those three floats back: one 12-byte
+ * copy and the wait for the stream it implies. There it is refused with TFL_EUNSUPPORTED, before anything is launched, while
+ * the stream is capturing. As after tfl_model_set_weights, a tfl_slab_graph recorded with the model must be re-recorded.
+ * Models of more than 32 layers are refused with TFL_EUNSUPPORTED (the pointers travel as kernel arguments). */
+int tfl_model_set_weights_device(tfl_ctx* ctx, tfl_model* model, const float* const* d_weights, const float* const* d_biases);
+
+/* ---- the optimiser step of the training closure: gradient clip (lib/run_epoch.lua:304-312), weight decay, lib/adam.lua or
+ * lib/rmsprop.lua, and the refresh of the native model from the updated parameters, as ONE asynchronous call on device
+ * arrays. (optim.sgd is Torch's own, not in the reference tree, and is not built.) */
+enum { TFL_OPTIM_ADAM = 0, TFL_OPTIM_RMSPROP = 1 };
+typedef struct tfl_optim tfl_optim;
+typedef struct {
+  int32_t method;            /* TFL_OPTIM_ADAM, TFL_OPTIM_RMSPROP */
+  double learningRate, learningRateDecay, beta1, beta2, epsilon, weightDecay;   /* lib/adam.lua:28-34 */
+  double alpha, initialMean;                                                    /* lib/rmsprop.lua:28-32 */
+  double gradNormThreshold;  /* <= 0: no clip (run_epoch.lua:304-312) */
+} tfl_optim_config;
+/* State for the parameters of `model` (one weight and one bias array per layer, cudnn layout): the moments m and v -- RMSprop:
+ * m alone, filled with initialMean -- and the step counter t, all on the device. NULL on error (tfl_last_error).
+ * The optimiser keeps `model` and refreshes it in every step: the model must outlive the optimiser (destroy the optimiser
+ * first; a tfl_optim_step after tfl_model_destroy of its model is undefined). */
+tfl_optim* tfl_optim_create(tfl_ctx* ctx, tfl_model* model, const tfl_optim_config* config);
+/* One step, in place on the DEVICE arrays, fp32 per element in the reference's operation order:
+ *   clip     norm = the L2 norm over all gradients, summed in fp64 in a fixed order (per-block partials at fixed places, added
+ *            in index order, no atomics) and rounded once; if norm > gradNormThreshold every gradient element is divided by
+ *            (float)(norm / gradNormThreshold)
+ *   decay    g += weightDecay x
+ *   Adam     clr = lr / (1 + t lrd) with t before the increment; m = m beta1 + (1 - beta1) g; v = v beta2 + (1 - beta2) g g;
+ *            x -= stepSize m / (sqrt(v) + epsilon), stepSize = clr sqrt(1 - beta2^t) / (1 - beta1^t) formed in fp64 from the
+ *            new t and rounded once
+ *   RMSprop  m = m alpha + (1 - alpha) g g; x -= lr g / (sqrt(m) + epsilon)
+ * The gradient arrays hold the clipped and decayed gradients afterwards. A kernel advances t, so a captured step advances on
+ * replay; the hyper-parameters travel by value with each call (tfl_optim_set_config changes them for the next one). At most
+ * three launches, then tfl_model_set_weights_device from the updated parameters (its launches, its one exception, its limits).
+ * The same inputs and state give the same bits on every call. */
+int tfl_optim_step(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights, float* const* d_biases,
+                   float* const* d_gradWeights, float* const* d_gradBiases);
+/* New hyper-parameters from the next step on; the method and the shapes are fixed (a changed method is TFL_EINVAL). */
+int tfl_optim_set_config(tfl_ctx* ctx, tfl_optim* opt, const tfl_optim_config* config);
+/* The step counter t (reads it back: synchronises the stream; for logging). -1 on error. */
+int64_t tfl_optim_steps(tfl_ctx* ctx, tfl_optim* opt);
+/* The moments, for a checkpoint: copies m into d_m and (Adam) v into d_v -- DEVICE arrays of the returned count of floats, in
+ * parameter order (layer 0's weight, its bias, layer 1's weight, ...); either may be NULL (both NULL: the count alone).
+ * Enqueued on the context's stream, no synchronisation. -1 on error. */
+int64_t tfl_optim_get_state(tfl_ctx* ctx, tfl_optim* opt, float* d_m, float* d_v);
+void tfl_optim_destroy(tfl_ctx* ctx, tfl_optim* opt);
+
 /* A z-slab rank holds only part of the grid, but tfluids.getDx = 1/max(X,Y,Z) (grid.cc:37-40) is a
  * property of the WHOLE grid: dx > 0 overrides the value addBuoyancy / addGravity derive from the
  * local tensor sizes; 0 restores the default. */
