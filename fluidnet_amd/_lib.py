@@ -163,6 +163,9 @@ SIGNATURES = {
     "tfl_model_backward_workspace_floats": (_c.c_int64, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "tfl_model_backward": (_c.c_int, [_c.c_void_p, _c.c_void_p, _T, _T, _T, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_int64,
                                       _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.c_int]),
+    "tfl_model_backward_input_workspace_floats": (_c.c_int64, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "tfl_model_backward_input": (_c.c_int, [_c.c_void_p, _c.c_void_p, _T, _T, _T, _T, _T, _T, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                            _c.c_int64, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.c_int, _T, _T]),
     "tfl_model_set_weights_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p)]),
     "tfl_optim_create": (_c.c_void_p, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "tfl_optim_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),

@@ -178,6 +178,20 @@ void scale_add(hipStream_t st, int B, long long per, const double* stats, double
   k_scale_add<<<dim3((unsigned)((per + 255) / 256), (unsigned)B), 256, 0, st>>>(per, stats, count, src, add, dst);
 }
 
+// the masking of k_conv_wgrad's write-back without the sums: g *= act'(y), plane by plane
+__global__ __launch_bounds__(256) void k_act_mask(long long cells, int cout, int ych, float* __restrict__ g, const float* __restrict__ y, int act) {
+  const int b = blockIdx.z, c = blockIdx.y;
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= cells) return;
+  const long long o = ((long long)b * cout + c) * cells + t;
+  g[o] = act_grad(g[o], y[((long long)b * ych + c) * cells + t], act);
+}
+
+void act_mask(hipStream_t st, int B, int cout, int ych, long long cells, float* g, const float* y, int act) {
+  TFL_TIMED("k_act_mask", st);
+  k_act_mask<<<dim3((unsigned)((cells + 255) / 256), (unsigned)cout, (unsigned)B), 256, 0, st>>>(cells, cout, ych, g, y, act);
+}
+
 bool conv_wgrad_fits(const WgPlan& p) { return p.lds_floats <= 16384; }
 
 bool conv_wgrad(hipStream_t st, bool is3d, const WgPlan& p, int B, int Z, int Y, int X, int cin, int cout, int k, const float* x,

@@ -37,40 +37,7 @@
 
 namespace tfl {
 
-// setWallBcs decision for the cell's own three face components, third_party/tfluids.cc:926-1002, as a pure
-// function of the cell's flag word and its six neighbours' (0 where the neighbour is outside the grid).
-template <bool IS3D>
-__device__ __forceinline__ void wall_mask_from(int fc, int fxm, int fxp, int fym, int fyp, int fzm, int fzp, bool& zx,
-                                               bool& zy, bool& zz) {
-  zx = zy = zz = false;
-  const bool cf = fc & kFluid, co = fc & kObstacle;
-  if (!cf && !co) return;
-  zx = (fxm & kObstacle) || (co && (fxm & kFluid));
-  zy = (fym & kObstacle) || (co && (fym & kFluid));
-  zz = IS3D && ((fzm & kObstacle) || (co && (fzm & kFluid)));
-  if (cf) {
-    if ((fxm & kStick) || (fxp & kStick)) { zy = true; zz = IS3D; }
-    if ((fym & kStick) || (fyp & kStick)) { zx = true; zz = IS3D; }
-    if (IS3D && ((fzm & kStick) || (fzp & kStick))) { zx = true; zy = true; }
-  }
-}
-
-template <bool IS3D>
-__device__ __forceinline__ void wall_zero_mask(const Dom& d, const float* __restrict__ flags, int i, int j, int k, int o,
-                                               bool& zx, bool& zy, bool& zz) {
-  const int fc = (int)flags[o];
-  if (!(fc & (kFluid | kObstacle))) { zx = zy = zz = false; return; }
-  const int fxm = i > 0 ? (int)flags[o - 1] : 0;
-  const int fym = j > 0 ? (int)flags[o - d.sy] : 0;
-  const int fzm = (IS3D && k > 0) ? (int)flags[o - d.sz] : 0;
-  int fxp = 0, fyp = 0, fzp = 0;
-  if (fc & kFluid) {
-    fxp = i < d.X - 1 ? (int)flags[o + 1] : 0;
-    fyp = j < d.Y - 1 ? (int)flags[o + d.sy] : 0;
-    fzp = (IS3D && k < d.Z - 1) ? (int)flags[o + d.sz] : 0;
-  }
-  wall_mask_from<IS3D>(fc, fxm, fxp, fym, fyp, fzm, fzp, zx, zy, zz);
-}
+// (wall_mask_from / wall_zero_mask, the setWallBcs decision of a cell: tfl_device.hpp, shared with input_grad.hip)
 
 // U_bc component AXIS of cell (i,j,k): the input velocity with the wall BCs applied on the fly
 template <bool IS3D, int AXIS>

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "tfl_abi.hpp"
+#include "tfl_input_grad.hpp"
 #include "tfl_ops.hpp"
 #include "tfl_refresh.hpp"
 #include "tfl_train.hpp"
@@ -31,7 +32,10 @@ struct tfl_layer {
   // (ci / join_c) * join_p + ci % join_c -- the concat of the banks
   int cin_ref = 0, cout_ref = 0, join_c = 0, join_p = 0;
   bool skip_in = false;
-  float* wt = nullptr; // device, trainable models, every layer but the first: the data-gradient form [tap][cout][cin] (tfl_train.hpp)
+  float* wt = nullptr; // device, trainable models: the data-gradient form [tap][cout][cin] (tfl_train.hpp); the first layer's has
+                       // gxc input planes of which the first nx are real (relay_first_transposed: tfl_model_backward_input)
+  int nx = 0, gxc = 0; // first layer of a trainable model: the net input's planes without the occupancy channel, and padded
+  float* ws = nullptr; // device, the last layer of a trainable model with the joined skip channel: its gradient's form [tap]
 };
 // The forward a model runs (tfl_model_finish dispatches on it), named after its kernel file; TFL_CONV_PATH at creation picks
 // it for the 3-D `default` topology (3->8 k3, 8->8 k3, 8->8 k3, 8->8 k1, 8->1 k1), and "direct" = generic for both defaults.
@@ -150,8 +154,8 @@ StageTable stage_table(int nst, int banks = 1, int split = 0, int join = 0) {
 
 // A module's cudnn weight [cout*S][cin][taps] (output channel index = o*S + sub) -> [sub][tap][cin_p][cout_p] and its bias
 // [cout*S] -> [sub][cout_p] (tfl_train.hpp relay_layer; the padding holds zeros), uploaded into L -- at creation, and again by
-// tfl_model_set_weights into the same buffers. transposed: also the data-gradient form L.wt (every layer but the first of a
-// model tfl_model_backward takes).
+// tfl_model_set_weights into the same buffers. transposed: also the data-gradient form L.wt (every layer of a model
+// tfl_model_backward takes; the first layer's is read by tfl_model_backward_input alone) and the skip form L.ws.
 bool upload_layer(tfl_layer& L, bool is3d, const float* w, const float* b, bool transposed) {
   const int taps = is3d ? L.k * L.k * L.k : L.k * L.k;
   const int S = is3d ? L.up * L.up * L.up : L.up * L.up;
@@ -163,8 +167,13 @@ bool upload_layer(tfl_layer& L, bool is3d, const float* w, const float* b, bool 
   if (!upload(L.w, relaid.data(), relaid.size() * sizeof(float)) || !upload(L.b, bias_p.data(), bias_p.size() * sizeof(float))) return false;
   if (!transposed) return true;
   std::vector<float> wt;
-  tfl::relay_transposed(taps, L.cin, L.cout, L.cin - (L.skip_in ? 1 : 0), relaid.data(), wt);
-  return upload(L.wt, wt.data(), wt.size() * sizeof(float));
+  if (L.nx > 0) tfl::relay_first_transposed(taps, L.cin, L.cout, L.nx, L.gxc, relaid.data(), wt);
+  else tfl::relay_transposed(taps, L.cin, L.cout, L.cin - (L.skip_in ? 1 : 0), relaid.data(), wt);
+  if (!upload(L.wt, wt.data(), wt.size() * sizeof(float))) return false;
+  if (!L.skip_in) return true;
+  std::vector<float> ws;
+  tfl::relay_skip(taps, L.cin, L.cout, relaid.data(), ws);
+  return upload(L.ws, ws.data(), ws.size() * sizeof(float));
 }
 
 // batch norm after hidden module i, folded in double: scale = w / sqrt(var + eps), shift = b - mean * scale, each rounded once
@@ -266,7 +275,9 @@ tfl_model* build_layers(tfl_ctx* c, bool is3d, int n, const int32_t* cin, const 
   if (!g && !m->multires) {     // a model tfl_model_backward takes: the data-gradient weights and the zero bias of their convolutions
     const std::vector<float> zeros(64, 0.0f);
     bool ok = upload(m->zero_bias, zeros.data(), zeros.size() * sizeof(float));
-    for (int i = 1; i < n && ok; i++) ok = upload_layer(m->layers[i], is3d, weights[i], biases[i], true);
+    m->layers[0].nx = in_c - 1;     // (the occupancy channel sits last and gets no gradient)
+    m->layers[0].gxc = tfl::ig_width(in_c - 1);
+    for (int i = 0; i < n && ok; i++) ok = upload_layer(m->layers[i], is3d, weights[i], biases[i], true);
     if (!ok) return cleanup("uploading weights failed");
   }
   return m;
@@ -285,9 +296,11 @@ bool refresh_tables(tfl_model* m) {
     r.S = m->is3d ? L.up * L.up * L.up : L.up * L.up;
     r.cin = L.cin; r.cout = L.cout; r.cin_ref = L.cin_ref; r.cout_ref = L.cout_ref;
     r.join_c = L.join_c; r.join_p = L.join_p; r.skip_in = L.skip_in ? 1 : 0;
-    r.cin_t = L.cin - (L.skip_in ? 1 : 0);
+    r.cin_t = L.nx > 0 ? L.gxc : L.cin - (L.skip_in ? 1 : 0);
+    r.wt_first = L.nx; r.ws = L.ws;
     r.n_w = r.S * r.taps * r.cin * r.cout; r.n_b = r.S * r.cout; r.n_wt = L.wt ? r.taps * r.cout * r.cin_t : 0;
-    m->refresh_elems = std::max(m->refresh_elems, r.n_w + r.n_b + r.n_wt);
+    r.n_ws = L.ws ? r.taps : 0;
+    m->refresh_elems = std::max(m->refresh_elems, r.n_w + r.n_b + r.n_wt + r.n_ws);
     tab.push_back(r);
   }
   if (!upload(m->d_refresh, tab.data(), tab.size() * sizeof(tfl::RefreshLayer))) return false;
@@ -962,7 +975,7 @@ tfl_model* tfl_model_create_graph(tfl_ctx* c, int is3D, int nconv, const int32_t
 void tfl_model_destroy(tfl_ctx* c, tfl_model* m) {
   (void)c;
   if (!m) return;
-  for (auto& L : m->layers) { if (L.w) (void)hipFree(L.w); if (L.b) (void)hipFree(L.b); if (L.bn) (void)hipFree(L.bn); if (L.wt) (void)hipFree(L.wt); }
+  for (auto& L : m->layers) { if (L.w) (void)hipFree(L.w); if (L.b) (void)hipFree(L.b); if (L.bn) (void)hipFree(L.bn); if (L.wt) (void)hipFree(L.wt); if (L.ws) (void)hipFree(L.ws); }
   if (m->zero_bias) (void)hipFree(m->zero_bias);
   for (int l = 0; l < 3; l++) if (m->bfrag[l]) (void)hipFree(m->bfrag[l]);
   for (int l = 0; l < 3; l++) if (m->wino[l]) (void)hipFree(m->wino[l]);
@@ -1118,6 +1131,132 @@ int check_tape(tfl_ctx* c, const char* who, const tfl::TapeLayout& t, const floa
   if (((uintptr_t)tape & 7) != 0) return fail(c, TFL_EINVAL, "%s: tape must be 8-byte aligned", who);
   return TFL_OK;
 }
+
+// what tfl_model_backward_input takes and gives beyond tfl_model_backward: the forward's inputs and its U, and where the two
+// input gradients go (either may be null)
+struct InputSide { const tfl_tensor *pDiv, *UDiv, *UOut, *gradPDiv, *gradUDiv; };
+tfl::IgChans input_chans(const tfl_model* m) { return tfl::ig_chans(m->is3d, m->opts.in_pDiv, m->opts.in_UDiv, m->opts.in_div); }
+tfl::IgLayout input_layout(const tfl_model* m, int B, int Z, int Y, int X) {
+  return tfl::ig_layout(m->is3d, train_layers(m), input_chans(m), m->opts.pressure_skip != 0,
+                        m->opts.normalize && m->opts.norm_chan == TFL_NORM_DIV, B, Z, Y, X);
+}
+
+// tfl_model_backward (in = null: its launches exactly) and tfl_model_backward_input
+int model_backward(tfl_ctx* c, tfl_model* m, const char* who, const tfl_tensor* flags, const tfl_tensor* gradP, const tfl_tensor* gradU,
+                   const float* tape, int64_t tape_floats, float* workspace, int64_t workspace_floats, float* const* gradWeights,
+                   float* const* gradBiases, int accumulate, const InputSide* in) {
+  TRY(check_flags(c, who, flags));
+  if (!m) return fail(c, TFL_EINVAL, "%s: null model", who);
+  TRY(train_gate(c, m, who));
+  const int is3D = m->is3d ? 1 : 0;
+  if (gradP) TRY(check_scalar(c, who, "gradP", gradP, flags));
+  if (gradU) TRY(check_vel(c, who, "gradU", gradU, flags, is3D));
+  if (!is3D && flags->Z != 1) return fail(c, TFL_EINVAL, "%s: 2D model but zdepth > 1", who);
+  if (in) {
+    TRY(check_scalar(c, who, "pDiv", in->pDiv, flags));
+    TRY(check_vel(c, who, "UDiv", in->UDiv, flags, is3D));
+    TRY(check_vel(c, who, "UOut", in->UOut, flags, is3D));
+    if (in->gradPDiv) TRY(check_scalar(c, who, "gradPDiv", in->gradPDiv, flags));
+    if (in->gradUDiv) TRY(check_vel(c, who, "gradUDiv", in->gradUDiv, flags, is3D));
+  }
+  const int B = flags->B, Z = flags->Z, Y = flags->Y, X = flags->X;
+  if (B > kMaxBatch) return fail(c, TFL_EINVAL, "%s: batch size above %d", who, kMaxBatch);
+  const std::vector<tfl::TrainLayer> tl = train_layers(m);
+  const int nl = (int)tl.size();
+  const tfl::TapeLayout t = tfl::tape_layout(tl, B, Z, Y, X);
+  TRY(check_tape(c, who, t, tape, tape_floats));
+  const tfl::IgLayout ig = in ? input_layout(m, B, Z, Y, X) : tfl::IgLayout{};
+  const tfl::BwdLayout w = in ? ig.bwd : tfl::bwd_layout(m->is3d, tl, B, Z, Y, X);
+  const int64_t need = in ? ig.total : w.total;
+  if (!workspace || workspace_floats < need)
+    return fail(c, TFL_EINVAL, "%s: workspace too small (%lld floats needed)", who, (long long)need);
+  if (((uintptr_t)workspace & 7) != 0) return fail(c, TFL_EINVAL, "%s: workspace must be 8-byte aligned", who);
+  // the parameter gradients: both tables, or (input gradients only) neither
+  const bool params = gradWeights || gradBiases || !in;
+  if (params && (!gradWeights || !gradBiases)) return fail(c, TFL_EINVAL, "%s: null gradient table", who);
+  for (int l = 0; l < nl && params; l++) {
+    if (!gradWeights[l] || !gradBiases[l]) return fail(c, TFL_EINVAL, "%s: layer %d has no gradient buffer", who, l);
+    if (!tfl::conv_wgrad_fits(tfl::wg_plan(m->is3d, tl[l], B, Z, Y, X)))
+      return fail(c, TFL_EUNSUPPORTED, "%s: layer %d (k = %d) does not fit the weight-gradient kernel's tile", who, l, tl[l].k);
+  }
+  hipStream_t st = c->stream;
+  const long long cells = (long long)Z * Y * X;
+  const int C = m->is3d ? 3 : 2;
+  const double* stats = (const double*)(tape + t.stats);
+  const double count = scale_count(m, Z, Y, X);
+  float* g = workspace + w.g0;
+  float* g2 = workspace + w.g1;
+  float* gu = workspace + w.gu;
+  double* partials = (double*)(workspace + w.partials);
+  // g_pPred = scale gradP + velocityUpdateBackward(setWallBcsBackward(scale gradU)): the wall mask only zeroes, so the
+  // scale goes in front of it
+  if (gradU) {
+    tfl::scale_add(st, B, cells * C, stats, count, gradU->data, nullptr, gu);
+    tfl::set_wall_bcs(st, m->is3d, B, Z, Y, X, gu, flags->data);
+    tfl::velocity_update_bwd(st, m->is3d, B, Z, Y, X, flags->data, gu, g);
+    if (gradP) tfl::scale_add(st, B, cells, stats, count, gradP->data, g, g);
+  } else if (gradP) {
+    tfl::scale_add(st, B, cells, stats, count, gradP->data, nullptr, g);
+  } else {
+    HIP_TRY(c, hipMemsetAsync(g, 0, sizeof(float) * (size_t)B * cells, st));
+  }
+  const int act = 1 + m->opts.nonlin;
+  for (int l = nl - 1; l >= 0; l--) {
+    const tfl_layer& L = m->layers[l];
+    const float* x = l == 0 ? tape + t.x : tape + t.out[l - 1];
+    const float* y = l + 1 < nl ? tape + t.out[l] : nullptr;
+    if (params) {
+      const tfl::WgPlan p = tfl::wg_plan(m->is3d, tl[l], B, Z, Y, X);
+      // (the masked gradient is written back wherever a data gradient follows: the first layer's only for the input gradients)
+      if (!tfl::conv_wgrad(st, m->is3d, p, B, Z, Y, X, L.cin, L.cout, L.k, x, g, y, y ? tfl::train_och(tl, l) : 0, act, (l > 0 || in) && y, partials))
+        return fail(c, TFL_EUNSUPPORTED, "%s: no weight-gradient kernel for layer %d (%d output channels)", who, l, L.cout);
+      tfl::conv_wgrad_finish(st, p, L.cin, L.cout, L.cin_ref, L.cout_ref, L.skip_in ? 1 : 0, partials, gradWeights[l], gradBiases[l],
+                             accumulate != 0);
+    } else if (y) {
+      tfl::act_mask(st, B, L.cout, tfl::train_och(tl, l), cells, g, y, act);
+    }
+    // the joined skip channel's gradient: the gradient at pPred against the skip plane's taps, mirrored
+    if (in && L.skip_in && !tfl::conv_direct(st, m->is3d, B, Z, Y, X, L.cout, 1, L.k, 0, g, L.ws, m->zero_bias, workspace + ig.gskip))
+      return fail(c, TFL_EUNSUPPORTED, "%s: no kernel for the skip channel's gradient", who);
+    if (l == 0) break;
+    // g_in = conv(g_pre, W transposed and mirrored); the joined skip channel gets none
+    if (!tfl::conv_direct(st, m->is3d, B, Z, Y, X, L.cout, L.cin - (L.skip_in ? 1 : 0), L.k, 0, g, L.wt, m->zero_bias, g2))
+      return fail(c, TFL_EUNSUPPORTED, "%s: no kernel for %d channels", who, L.cin - (L.skip_in ? 1 : 0));
+    std::swap(g, g2);
+  }
+  if (!in || (!in->gradPDiv && !in->gradUDiv)) return check_launch(c, who);
+  // the first layer's data gradient, then the scale's gradient and the head (input_grad.hip)
+  const tfl_layer& L0 = m->layers[0];
+  if (!tfl::conv_direct(st, m->is3d, B, Z, Y, X, L0.cout, ig.gxc, L0.k, 0, g, L0.wt, m->zero_bias, workspace + ig.gx))
+    return fail(c, TFL_EUNSUPPORTED, "%s: no kernel for %d channels", who, ig.gxc);
+  const tfl::IgChans ch = input_chans(m);
+  const tfl_model_opts& o = m->opts;
+  tfl::IgArgs a{};
+  a.flags = flags->data; a.pDiv = in->pDiv->data; a.UDiv = in->UDiv->data; a.UOut = in->UOut->data;
+  a.gradP = gradP ? gradP->data : nullptr; a.gradU = gradU ? gradU->data : nullptr; a.h = gradU ? gu : nullptr;
+  a.gx = workspace + ig.gx; a.gskip = o.pressure_skip ? workspace + ig.gskip : nullptr;
+  a.x = tape + t.x; a.pPred = tape + t.pPred;
+  a.stats = stats; a.count = count;
+  a.partials = (double*)(workspace + ig.partials); a.gs = (double*)(workspace + ig.gs);
+  a.gradPDiv = in->gradPDiv ? in->gradPDiv->data : nullptr; a.gradUDiv = in->gradUDiv ? in->gradUDiv->data : nullptr;
+  a.gxc = ig.gxc; a.in_c = m->in_c; a.pch = ch.p; a.uch = ch.u; a.dch = ch.d;
+  a.nmode = !o.normalize ? 0 : (o.norm_func == TFL_NORMFUNC_STD ? 1 : 2);
+  a.nchan = o.norm_chan; a.blocks = ig.blocks;
+  if (a.nmode && o.norm_chan == TFL_NORM_DIV) {
+    if (ig.recompute_div) {      // no div channel on the tape to read it back from
+      float* ubc = workspace + ig.ubc;
+      HIP_TRY(c, hipMemcpyAsync(ubc, in->UDiv->data, sizeof(float) * (size_t)B * cells * C, hipMemcpyDeviceToDevice, st));
+      tfl::set_wall_bcs(st, m->is3d, B, Z, Y, X, ubc, flags->data);
+      tfl::velocity_divergence(st, m->is3d, B, Z, Y, X, ubc, flags->data, workspace + ig.div);
+      a.dsrc = workspace + ig.div; a.dstride = cells; a.dscaled = 0;
+    } else {
+      a.dsrc = tape + t.x + (long long)ch.d * cells; a.dstride = (long long)m->in_c * cells; a.dscaled = 1;
+    }
+  }
+  if (a.nmode) tfl::input_grad_sums(st, m->is3d, B, Z, Y, X, a);
+  tfl::input_grad_head(st, m->is3d, B, Z, Y, X, a);
+  return check_launch(c, who);
+}
 }  // namespace
 
 extern "C" {
@@ -1215,68 +1354,22 @@ int64_t tfl_model_backward_workspace_floats(const tfl_model* m, int B, int Z, in
 int tfl_model_backward(tfl_ctx* c, tfl_model* m, const tfl_tensor* flags, const tfl_tensor* gradP, const tfl_tensor* gradU,
                        const float* tape, int64_t tape_floats, float* workspace, int64_t workspace_floats, float* const* gradWeights,
                        float* const* gradBiases, int accumulate) {
-  const char* who = "model_backward";
-  TRY(check_flags(c, who, flags));
-  if (!m) return fail(c, TFL_EINVAL, "%s: null model", who);
-  TRY(train_gate(c, m, who));
-  const int is3D = m->is3d ? 1 : 0;
-  if (gradP) TRY(check_scalar(c, who, "gradP", gradP, flags));
-  if (gradU) TRY(check_vel(c, who, "gradU", gradU, flags, is3D));
-  if (!is3D && flags->Z != 1) return fail(c, TFL_EINVAL, "%s: 2D model but zdepth > 1", who);
-  const int B = flags->B, Z = flags->Z, Y = flags->Y, X = flags->X;
-  if (B > kMaxBatch) return fail(c, TFL_EINVAL, "%s: batch size above %d", who, kMaxBatch);
-  const std::vector<tfl::TrainLayer> tl = train_layers(m);
-  const int nl = (int)tl.size();
-  const tfl::TapeLayout t = tfl::tape_layout(tl, B, Z, Y, X);
-  TRY(check_tape(c, who, t, tape, tape_floats));
-  const tfl::BwdLayout w = tfl::bwd_layout(m->is3d, tl, B, Z, Y, X);
-  if (!workspace || workspace_floats < w.total)
-    return fail(c, TFL_EINVAL, "%s: workspace too small (%lld floats needed)", who, (long long)w.total);
-  if (((uintptr_t)workspace & 7) != 0) return fail(c, TFL_EINVAL, "%s: workspace must be 8-byte aligned", who);
-  if (!gradWeights || !gradBiases) return fail(c, TFL_EINVAL, "%s: null gradient table", who);
-  for (int l = 0; l < nl; l++) {
-    if (!gradWeights[l] || !gradBiases[l]) return fail(c, TFL_EINVAL, "%s: layer %d has no gradient buffer", who, l);
-    if (!tfl::conv_wgrad_fits(tfl::wg_plan(m->is3d, tl[l], B, Z, Y, X)))
-      return fail(c, TFL_EUNSUPPORTED, "%s: layer %d (k = %d) does not fit the weight-gradient kernel's tile", who, l, tl[l].k);
-  }
-  hipStream_t st = c->stream;
-  const long long cells = (long long)Z * Y * X;
-  const int C = m->is3d ? 3 : 2;
-  const double* stats = (const double*)(tape + t.stats);
-  const double count = scale_count(m, Z, Y, X);
-  float* g = workspace + w.g0;
-  float* g2 = workspace + w.g1;
-  float* gu = workspace + w.gu;
-  double* partials = (double*)(workspace + w.partials);
-  // g_pPred = scale gradP + velocityUpdateBackward(setWallBcsBackward(scale gradU)): the wall mask only zeroes, so the
-  // scale goes in front of it
-  if (gradU) {
-    tfl::scale_add(st, B, cells * C, stats, count, gradU->data, nullptr, gu);
-    tfl::set_wall_bcs(st, m->is3d, B, Z, Y, X, gu, flags->data);
-    tfl::velocity_update_bwd(st, m->is3d, B, Z, Y, X, flags->data, gu, g);
-    if (gradP) tfl::scale_add(st, B, cells, stats, count, gradP->data, g, g);
-  } else if (gradP) {
-    tfl::scale_add(st, B, cells, stats, count, gradP->data, nullptr, g);
-  } else {
-    HIP_TRY(c, hipMemsetAsync(g, 0, sizeof(float) * (size_t)B * cells, st));
-  }
-  const int act = 1 + m->opts.nonlin;
-  for (int l = nl - 1; l >= 0; l--) {
-    const tfl_layer& L = m->layers[l];
-    const tfl::WgPlan p = tfl::wg_plan(m->is3d, tl[l], B, Z, Y, X);
-    const float* x = l == 0 ? tape + t.x : tape + t.out[l - 1];
-    const float* y = l + 1 < nl ? tape + t.out[l] : nullptr;
-    if (!tfl::conv_wgrad(st, m->is3d, p, B, Z, Y, X, L.cin, L.cout, L.k, x, g, y, y ? tfl::train_och(tl, l) : 0, act, l > 0 && y, partials))
-      return fail(c, TFL_EUNSUPPORTED, "%s: no weight-gradient kernel for layer %d (%d output channels)", who, l, L.cout);
-    tfl::conv_wgrad_finish(st, p, L.cin, L.cout, L.cin_ref, L.cout_ref, L.skip_in ? 1 : 0, partials, gradWeights[l], gradBiases[l],
-                           accumulate != 0);
-    if (l == 0) break;
-    // g_in = conv(g_pre, W transposed and mirrored); the joined skip channel gets none
-    if (!tfl::conv_direct(st, m->is3d, B, Z, Y, X, L.cout, L.cin - (L.skip_in ? 1 : 0), L.k, 0, g, L.wt, m->zero_bias, g2))
-      return fail(c, TFL_EUNSUPPORTED, "%s: no kernel for %d channels", who, L.cin - (L.skip_in ? 1 : 0));
-    std::swap(g, g2);
-  }
-  return check_launch(c, who);
+  return model_backward(c, m, "model_backward", flags, gradP, gradU, tape, tape_floats, workspace, workspace_floats, gradWeights,
+                        gradBiases, accumulate, nullptr);
+}
+
+int64_t tfl_model_backward_input_workspace_floats(const tfl_model* m, int B, int Z, int Y, int X) {
+  if (!m || m->path == ConvPath::graph || !m->zero_bias || B < 1 || Z < 1 || Y < 1 || X < 1) return -1;
+  return input_layout(m, B, Z, Y, X).total;
+}
+
+int tfl_model_backward_input(tfl_ctx* c, tfl_model* m, const tfl_tensor* flags, const tfl_tensor* pDiv, const tfl_tensor* UDiv,
+                             const tfl_tensor* UOut, const tfl_tensor* gradP, const tfl_tensor* gradU, const float* tape,
+                             int64_t tape_floats, float* workspace, int64_t workspace_floats, float* const* gradWeights,
+                             float* const* gradBiases, int accumulate, const tfl_tensor* gradPDiv, const tfl_tensor* gradUDiv) {
+  const InputSide in{pDiv, UDiv, UOut, gradPDiv, gradUDiv};
+  return model_backward(c, m, "model_backward_input", flags, gradP, gradU, tape, tape_floats, workspace, workspace_floats, gradWeights,
+                        gradBiases, accumulate, &in);
 }
 
 }  // extern "C"

@@ -388,6 +388,35 @@ void conv_wgrad_finish(hipStream_t st, const WgPlan& p, int cin, int cout, int c
 // dst[b][t] = scale_b * src[b][t] (+ add[b][t]) over `per` floats per batch item; scale_b from the (sum, sum of squares) pairs
 void scale_add(hipStream_t st, int B, long long per, const double* stats, double count, const float* src, const float* add, float* dst);
 
+// g[b][c][t] *= act'(y[b][c][t]) over the `cout` planes of g (y has `ych` planes per item): conv_wgrad's write-back alone, for a
+// backward pass that asks for no parameter gradients (tfl_model_backward_input with NULL gradient tables)
+void act_mask(hipStream_t st, int B, int cout, int ych, long long cells, float* g, const float* y, int act);
+
+// input_grad.hip: what tfl_model_backward_input adds behind the first layer's data gradient. Null pointers: gradP /
+// gradU / h (no gradient given), gskip (no joined skip channel), gradPDiv / gradUDiv (not asked for), dsrc (the scale is not
+// taken from the divergence).
+struct IgArgs {
+  const float *flags, *pDiv, *UDiv, *UOut, *gradP, *gradU;
+  const float* h;           // scale keep (.) gradU, [B][C] (tfl_model_backward's velocity-gradient scratch)
+  const float* gx;          // the first layer's data gradient, [B][gxc]
+  const float* gskip;       // the joined skip channel's gradient, [B][1]
+  const float *x, *pPred;   // the tape's net input [B][in_c] and last-layer output
+  const float* dsrc;        // the divergence of U_bc, `dstride` floats per item; dscaled: divided by the scale (the tape's channel)
+  const double* stats; double count;      // the tape's input-scale pair and the count that goes with it
+  double* partials;         // [B][blocks][5]
+  double* gs;               // [B]: the scale's gradient
+  float *gradPDiv, *gradUDiv;
+  long long dstride;
+  int dscaled, gxc, in_c;
+  int pch, uch, dch;        // the first plane of pDiv / U_bc / div in x and gx, -1 = the channel is off
+  int nmode, nchan;         // normaliser: 0 none | 1 std | 2 l2 norm, of 0 UDiv | 1 pDiv | 2 div
+  int blocks;               // blocks per item of the sums launch (tfl_input_grad.hpp ig_sum_blocks)
+};
+// the five dot products of g_s per item into a.partials, then g_s into a.gs: two launches, no atomics
+void input_grad_sums(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const IgArgs& a);
+// gradPDiv / gradUDiv from g_x, g_skip, h and g_s: one gather launch
+void input_grad_head(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const IgArgs& a);
+
 // weights_refresh.hip: the device-side weight refresh (tfl_model_set_weights_device), one launch each. d_table / d_jobs: the model's
 // device tables (tfl_refresh.hpp); max_elems: the most destination elements of one entry (sizes the grid's x).
 struct RefreshSrc; struct RefreshLayer; struct PackJob; struct OptimPtrs; struct OptimArgs;

@@ -27,7 +27,7 @@ namespace tfl {
 constexpr int kRefreshMaxLayers = 32;
 struct RefreshSrc { const float* w[kRefreshMaxLayers]; const float* b[kRefreshMaxLayers]; };
 
-// ---- the generic forms of every layer: w [sub][tap][cin][cout], b [sub][cout], wt [tap][cout][cin_t] ------------------------
+// ---- the generic forms of every layer: w [sub][tap][cin][cout], b [sub][cout], wt [tap][cout][cin_t], ws [tap] ---------------
 // One entry per layer of the model's device table (built at creation): destinations and map parameters (model_host.cpp tfl_layer)
 struct RefreshLayer {
   float *w, *b, *wt;          // wt = null: the layer holds no data-gradient form
@@ -37,6 +37,12 @@ struct RefreshLayer {
   int skip_in;                // the last reference input channel is the joined skip channel, on the last padded plane
   int cin_t;                  // input planes of wt (cin without the skip plane)
   int n_w, n_b, n_wt;         // elements of the three destinations
+  // the input-gradient forms (tfl_model_backward_input). The FIRST layer's wt: cin_t is padded to a width conv_direct has, and
+  // only its first wt_first planes are real (the net input without the occupancy channel; the rest are zeros). The last layer of
+  // a model with the joined skip channel: ws [tap] = the skip plane's taps of output channel 0, mirrored.
+  int wt_first;               // > 0: wt is the first layer's form with this many real planes
+  float* ws;                  // null: no skip form
+  int n_ws;
 };
 // the reference input channel that sits on padded plane cp, or -1 (the inverse of upload_layer's cmap)
 TFL_HD inline int refresh_ci_of_plane(const RefreshLayer& L, int cp) {
@@ -64,9 +70,14 @@ TFL_HD inline int refresh_b_src(const RefreshLayer& L, int d) {
 // element d of wt -> its element of the cudnn weight, or -1: wt[tap][co][ci] = w[taps - 1 - tap][ci][co] (sub-position 0)
 TFL_HD inline long long refresh_wt_src(const RefreshLayer& L, int d) {
   const int cp = d % L.cin_t, co = (d / L.cin_t) % L.cout, t = d / (L.cin_t * L.cout);
+  if (L.wt_first > 0 && cp >= L.wt_first) return -1;
   const int ci = refresh_ci_of_plane(L, cp);
   if (co >= L.cout_ref || ci < 0) return -1;
   return (((long long)co * L.S) * L.cin_ref + ci) * L.taps + (L.taps - 1 - t);
+}
+// element d of ws -> its element of the cudnn weight: ws[tap] = w[taps - 1 - tap][skip plane][0] (sub-position 0)
+TFL_HD inline long long refresh_ws_src(const RefreshLayer& L, int d) {
+  return (long long)(L.cin_ref - 1) * L.taps + (L.taps - 1 - d);
 }
 
 // ---- the fp32 forms of the two default topologies (tfl_pack.hpp pack_bfrag3 / pack_wino3 / pack_tail3 / pack_bfrag2) ---------

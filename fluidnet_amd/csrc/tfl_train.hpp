@@ -42,6 +42,23 @@ inline void relay_transposed(int taps, int cin_p, int cout_p, int cin_t, const f
         wt[((size_t)t * cout_p + co) * cin_t + ci] = relaid[((size_t)(taps - 1 - t) * cin_p + ci) * cout_p + co];
 }
 
+// The first layer's data-gradient form (tfl_model_backward_input): the same map for the first `nx` input planes -- the net input
+// without its occupancy channel, which sits last and needs no gradient -- in a [tap][cout_p][gxc] array, gxc >= nx a width the
+// convolution kernels have; the planes [nx, gxc) hold zeros.
+inline void relay_first_transposed(int taps, int cin_p, int cout_p, int nx, int gxc, const float* relaid, std::vector<float>& wt) {
+  wt.assign((size_t)taps * cout_p * gxc, 0.0f);
+  for (int t = 0; t < taps; t++)
+    for (int co = 0; co < cout_p; co++)
+      for (int ci = 0; ci < nx; ci++)
+        wt[((size_t)t * cout_p + co) * gxc + ci] = relaid[((size_t)(taps - 1 - t) * cin_p + ci) * cout_p + co];
+}
+// The joined skip channel's data-gradient form: the last layer's one output channel against its last input plane, mirrored,
+// ws[tap] = w[taps - 1 - tap][cin_p - 1][0] -- a 1 -> 1 channel convolution of the gradient at pPred.
+inline void relay_skip(int taps, int cin_p, int cout_p, const float* relaid, std::vector<float>& ws) {
+  ws.assign((size_t)taps, 0.0f);
+  for (int t = 0; t < taps; t++) ws[t] = relaid[((size_t)(taps - 1 - t) * cin_p + (cin_p - 1)) * cout_p];
+}
+
 // One layer as the training side sees it: padded and reference channel counts, kernel size, whether its last input plane is
 // the joined pressure-skip channel.
 struct TrainLayer { int cin, cout, cin_ref, cout_ref, k, skip_in; };

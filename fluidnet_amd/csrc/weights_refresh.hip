@@ -1,6 +1,6 @@
 // weights_refresh.hip -- tfl_model_set_weights_device: every weight form a model holds, rebuilt on the device from the caller's
 // cudnn-layout device arrays. At these sizes (7-10 k parameters for the default nets) every launch sits at the launch floor,
-// so the launch count is the cost: ONE gather launch covers w / b / wt of all layers (blockIdx.y = layer, the per-model table
+// so the launch count is the cost: ONE gather launch covers w / b / wt / ws of all layers (blockIdx.y = layer, the per-model table
 // of tfl_refresh.hpp RefreshLayer), ONE covers the fp32 forms of the default topologies (blockIdx.y = packed buffer), ONE
 // the split-fp16 fragments (a block per layer: max |w| in LDS, then the pack). Gathers: a thread owns a destination element and
 // asks tfl_refresh.hpp for its source, so padded elements are rewritten as zeros and nothing is written twice.
@@ -17,7 +17,7 @@ __global__ __launch_bounds__(kRefreshThreads) void k_refresh_layers(RefreshSrc s
   const RefreshLayer L = table[blockIdx.y];
   const float* __restrict__ w = src.w[blockIdx.y];
   const float* __restrict__ b = src.b[blockIdx.y];
-  const int n = L.n_w + L.n_b + L.n_wt;
+  const int n = L.n_w + L.n_b + L.n_wt + L.n_ws;
   for (int d = blockIdx.x * kRefreshThreads + threadIdx.x; d < n; d += gridDim.x * kRefreshThreads) {
     if (d < L.n_w) {
       const long long s = refresh_w_src(L, d);
@@ -25,10 +25,13 @@ __global__ __launch_bounds__(kRefreshThreads) void k_refresh_layers(RefreshSrc s
     } else if (d < L.n_w + L.n_b) {
       const int e = d - L.n_w, s = refresh_b_src(L, e);
       L.b[e] = s >= 0 ? b[s] : 0.0f;
-    } else {
+    } else if (d < L.n_w + L.n_b + L.n_wt) {
       const int e = d - L.n_w - L.n_b;
       const long long s = refresh_wt_src(L, e);
       L.wt[e] = s >= 0 ? w[s] : 0.0f;
+    } else {
+      const int e = d - L.n_w - L.n_b - L.n_wt;
+      L.ws[e] = w[refresh_ws_src(L, e)];
     }
   }
 }

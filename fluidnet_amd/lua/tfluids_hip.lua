@@ -179,6 +179,12 @@ int64_t tfl_model_backward_workspace_floats(const tfl_model* model, int B, int Z
 int tfl_model_backward(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* flags, const tfl_tensor* gradP,
                        const tfl_tensor* gradU, const float* tape, int64_t tape_floats, float* workspace,
                        int64_t workspace_floats, float* const* gradWeights, float* const* gradBiases, int accumulate);
+int64_t tfl_model_backward_input_workspace_floats(const tfl_model* model, int B, int Z, int Y, int X);
+int tfl_model_backward_input(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* flags, const tfl_tensor* pDiv,
+                             const tfl_tensor* UDiv, const tfl_tensor* UOut, const tfl_tensor* gradP, const tfl_tensor* gradU,
+                             const float* tape, int64_t tape_floats, float* workspace, int64_t workspace_floats,
+                             float* const* gradWeights, float* const* gradBiases, int accumulate, const tfl_tensor* gradPDiv,
+                             const tfl_tensor* gradUDiv);
 int tfl_model_set_weights_device(tfl_ctx* ctx, tfl_model* model, const float* const* d_weights, const float* const* d_biases);
 enum { TFL_OPTIM_ADAM = 0, TFL_OPTIM_RMSPROP = 1 };
 typedef struct tfl_optim tfl_optim;
@@ -600,7 +606,8 @@ function Model:cuda() return self end
 function Model:rangeErrors() return tonumber(lib.tfl_model_range_errors(ctx, self.handle)) end
 function Model:rangeFlag() return tonumber(lib.tfl_model_range_flag(ctx, self.handle)) end
 
--- The training side (linear models without pooling / upsampling; parameter gradients only -- include/tfluids_hip.h).
+-- The training side (linear models without pooling / upsampling -- include/tfluids_hip.h): the parameter gradients and, on
+-- request, the gradients to pDiv and UDiv (model:backward's wantGradInput).
 -- model:setWeights(weights, biases): tables of FloatTensors laid out like the convolutions' weight / bias, copied into the
 -- model's own buffers (synchronous; re-record any slab graph built on the model).
 function Model:setWeights(weights, biases)
@@ -627,11 +634,14 @@ function Model:forwardTrain(input)
   check(lib.tfl_model_forward_train(ctx, self.handle, T(pDiv), T(UDiv), T(flags), T(self.p), T(self.U), ws, n,
                                     ffi.cast('float*', torch.data(self.tape)), nt))
   self.output = {self.p, self.U}
+  self.trainInput = {pDiv, UDiv}       -- (what backward's wantGradInput reads again)
   return self.output
 end
--- model:backward(flags, gradP, gradU, gradWeights, gradBiases, accumulate): gradWeights / gradBiases are tables of CudaTensors
--- shaped like the convolutions' weight / bias; gradP or gradU may be nil; accumulate = true adds (accGradParameters)
-function Model:backward(flags, gradP, gradU, gradWeights, gradBiases, accumulate)
+-- model:backward(flags, gradP, gradU, gradWeights, gradBiases, accumulate, wantGradInput): gradWeights / gradBiases are tables of
+-- CudaTensors shaped like the convolutions' weight / bias; gradP or gradU may be nil; accumulate = true adds (accGradParameters).
+-- wantGradInput = true: also returns {gradPDiv, gradUDiv} (tfl_model_backward_input; the tensors given to forwardTrain and its U
+-- must be unchanged since). There is no gradient to flags.
+function Model:backward(flags, gradP, gradU, gradWeights, gradBiases, accumulate, wantGradInput)
   assert(self.tape, 'model:forwardTrain first')
   local n = #gradWeights
   local gw, gb = ffi.new('float*[?]', n), ffi.new('float*[?]', n)
@@ -639,8 +649,21 @@ function Model:backward(flags, gradP, gradU, gradWeights, gradBiases, accumulate
     gw[i - 1], gb[i - 1] = ffi.cast('float*', torch.data(gradWeights[i])), ffi.cast('float*', torch.data(gradBiases[i]))
   end
   local B, Z, Y, X = flags:size(1), flags:size(3), flags:size(4), flags:size(5)
-  local need = tonumber(lib.tfl_model_backward_workspace_floats(self.handle, B, Z, Y, X))
   self.bwdWork = self.bwdWork or flags.new()
+  if wantGradInput then
+    local pDiv, UDiv = self.trainInput[1], self.trainInput[2]
+    local need = tonumber(lib.tfl_model_backward_input_workspace_floats(self.handle, B, Z, Y, X))
+    if self.bwdWork:nElement() < need then self.bwdWork:resize(need) end
+    self.gradPDiv = self.gradPDiv or pDiv.new(); self.gradUDiv = self.gradUDiv or UDiv.new()
+    self.gradPDiv:resizeAs(pDiv); self.gradUDiv:resizeAs(UDiv)
+    check(lib.tfl_model_backward_input(ctx, self.handle, T(flags), T(pDiv), T(UDiv), T(self.U), gradP and T(gradP) or nil,
+                                       gradU and T(gradU) or nil, ffi.cast('const float*', torch.data(self.tape)),
+                                       self.tape:nElement(), ffi.cast('float*', torch.data(self.bwdWork)), self.bwdWork:nElement(),
+                                       gw, gb, b2i(accumulate == true), T(self.gradPDiv), T(self.gradUDiv)))
+    self.gradInput = {self.gradPDiv, self.gradUDiv}
+    return self.gradInput
+  end
+  local need = tonumber(lib.tfl_model_backward_workspace_floats(self.handle, B, Z, Y, X))
   if self.bwdWork:nElement() < need then self.bwdWork:resize(need) end
   check(lib.tfl_model_backward(ctx, self.handle, T(flags), gradP and T(gradP) or nil, gradU and T(gradU) or nil,
                                ffi.cast('const float*', torch.data(self.tape)), self.tape:nElement(),

@@ -1,7 +1,9 @@
 """The projection ConvNet as a torch.nn.Module whose parameters can be fitted: the two ends of the reference's training
 closure (model:forward ... model:backward, torch/lib/run_epoch.lua:207-235, 269-293) over tfl_model_forward_train /
-tfl_model_backward; fluidnet_amd.FluidCriterion is the middle. Parameter gradients only: the reference computes a gradInput
-and run_epoch.lua throws it away, so gradients to pDiv, UDiv and flags are not built, and asking for one raises.
+tfl_model_backward; fluidnet_amd.FluidCriterion is the middle. By default parameter gradients only: the reference computes a
+gradInput and run_epoch.lua throws it away, and asking for a gradient to pDiv, UDiv or flags raises. ProjectionNet(net,
+input_grad=True) also builds the gradients to pDiv and UDiv (tfl_model_backward_input), so that the net can be chained or put
+behind differentiable torch code; there is no gradient to flags.
 Optimisers: torch.optim's, or the fused device step of fluidnet_amd.optim (clip + Adam / RMSprop + refresh in one call).
 """
 import ctypes
@@ -18,23 +20,33 @@ def _ptr_array(tensors):
 
 
 class _ForwardTrain(torch.autograd.Function):
-    """(p, U) = net(pDiv, UDiv, flags) on the exact fp32 kernels, keeping the tape; backward = the parameter gradients."""
+    """(p, U) = net(pDiv, UDiv, flags) on the exact fp32 kernels, keeping the tape; backward = the parameter gradients and,
+    for a module built with input_grad=True, the gradients to pDiv and UDiv where autograd asks for them."""
 
     @staticmethod
     def forward(ctx, module, pDiv, UDiv, flags, *params):
         p, U, tape = module.forward_train(pDiv, UDiv, flags)
         ctx.module, ctx.flags, ctx.tape, ctx.pushes = module, flags, tape, module._pushes
+        if module.input_grad:
+            # (through autograd's own store: an in-place edit of an input or of U before backward trips its version check)
+            ctx.save_for_backward(pDiv, UDiv, U)
         return p, U
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, gradP, gradU):
         # the data gradient reads the native model's weights as they are NOW; the tape was taken with them as they were then
         if ctx.module._pushes != ctx.pushes:
             raise TfluidsError("ProjectionNet: the parameters were pushed to the native model between this forward and its "
                                "backward (an in-place update followed by another forward or push_parameters()): the gradient "
                                "would mix two sets of weights. Run backward before the parameters change")
-        gw, gb = ctx.module.backward(ctx.flags, gradP, gradU, ctx.tape)
-        return (None, None, None, None) + tuple(gw) + tuple(gb)
+        if not ctx.module.input_grad:
+            gw, gb = ctx.module.backward(ctx.flags, gradP, gradU, ctx.tape)
+            return (None, None, None, None) + tuple(gw) + tuple(gb)
+        pDiv, UDiv, U = ctx.saved_tensors
+        gw, gb, gp, gu = ctx.module.backward_input(ctx.flags, pDiv, UDiv, U, gradP, gradU, ctx.tape,
+                                                   want=(ctx.needs_input_grad[1], ctx.needs_input_grad[2]))
+        return (None, gp, gu, None) + tuple(gw) + tuple(gb)
 
 
 class ProjectionNet(torch.nn.Module):
@@ -47,10 +59,13 @@ class ProjectionNet(torch.nn.Module):
     since the last push -- every torch.optim step moves it -- or by push_parameters(). The host copy `layers` follows lazily:
     when something reads it, or when a handle is created on a device that has none.
     Accepted wherever simulate() takes a model. Linear models without pooling / upsampling layers can be trained; the others
-    run in eval mode only (training raises, naming the reason)."""
+    run in eval mode only (training raises, naming the reason).
+    input_grad=True: pDiv and UDiv may require grad, and backward returns their gradients (tfl_model_backward_input) -- two
+    passes can be chained, net(*net(pDiv, UDiv, flags), flags), or torch code put in front. flags never gets a gradient."""
 
-    def __init__(self, net, device="cuda"):
+    def __init__(self, net, device="cuda", input_grad=False):
         super().__init__()
+        self.input_grad = bool(input_grad)
         if not isinstance(net, FluidNetModel):
             raise TfluidsError("ProjectionNet wraps a FluidNetModel")
         self.net = net
@@ -167,9 +182,9 @@ class ProjectionNet(torch.nn.Module):
             self._sync(pDiv[0].device.index)
             return self.net.forward(pDiv, **kw)
         for name, t in (("pDiv", pDiv), ("UDiv", UDiv), ("flags", flags)):
-            if t.requires_grad:
+            if t.requires_grad and not (self.input_grad and name != "flags"):
                 raise TfluidsError("ProjectionNet: %s requires grad, but input gradients are not built (parameter gradients "
-                                   "only): detach it" % name)
+                                   "only) unless the module is created with input_grad=True, and never for flags: detach it" % name)
         if not (self.training and torch.is_grad_enabled()):
             self._sync(pDiv.device.index)
             p, U = self.net.forward([pDiv, UDiv, flags])
@@ -195,14 +210,44 @@ class ProjectionNet(torch.nn.Module):
             ctypes.c_void_p(work.data_ptr()), work.numel(), ctypes.c_void_p(tape.data_ptr()), tape.numel()))
         return p, U, tape
 
+    def _bwd_scratch(self, need, device):
+        if self._bwd_work is None or self._bwd_work.numel() < need or self._bwd_work.device != device:
+            self._bwd_work = torch.empty(max(int(need), 2), dtype=torch.float64, device=device).view(torch.float32)
+        return self._bwd_work
+
+    def backward_input(self, flags, pDiv, UDiv, U, gradP, gradU, tape, out=None, accumulate=False, want=(True, True), params=True):
+        """tfl_model_backward_input: ([gradWeight], [gradBias], gradPDiv, gradUDiv) from gradP / gradU (None = zero) at the
+        model's outputs; pDiv, UDiv: what forward_train was given, U: what it returned. want: which of the two input gradients to
+        build (the other is None). params=False: the input gradients only (the two lists are None). out / accumulate: as backward()."""
+        lib, ctx, h, _ = self.net._prep(flags)
+        B, _, Z, Y, X = flags.shape
+        work = self._bwd_scratch(lib.tfl_model_backward_input_workspace_floats(h, B, Z, Y, X), flags.device)
+        if not params:
+            gw = gb = None
+            tfluids._check(out is None and not accumulate, "params=False builds no parameter gradients")
+        elif out is None:
+            gw, gb = [torch.empty_like(w) for w in self.weights], [torch.empty_like(b) for b in self.biases]
+            tfluids._check(not accumulate, "accumulate needs out=(gradWeights, gradBiases)")
+        else:
+            gw, gb = out
+        gP = None if gradP is None else gradP.contiguous()
+        gU = None if gradU is None else gradU.contiguous()
+        pDiv, UDiv, U = pDiv.contiguous(), UDiv.contiguous(), U.contiguous()
+        gp = torch.empty_like(pDiv) if want[0] else None
+        gu = torch.empty_like(UDiv) if want[1] else None
+        tt = lambda t: None if t is None else tfluids._tt(t)
+        tfluids._call(lib, ctx, lib.tfl_model_backward_input(
+            ctx, h, tfluids._tt(flags), tfluids._tt(pDiv), tfluids._tt(UDiv), tfluids._tt(U), tt(gP), tt(gU),
+            ctypes.c_void_p(tape.data_ptr()), tape.numel(), ctypes.c_void_p(work.data_ptr()), work.numel(),
+            None if gw is None else _ptr_array(gw), None if gb is None else _ptr_array(gb), int(bool(accumulate)), tt(gp), tt(gu)))
+        return gw, gb, gp, gu
+
     def backward(self, flags, gradP, gradU, tape, out=None, accumulate=False):
         """tfl_model_backward: ([gradWeight], [gradBias]) in the parameters' layout from gradP / gradU (None = zero) at the
         model's outputs. out=(gw, gb): write into (accumulate: add onto) these tensors instead of fresh ones."""
         lib, ctx, h, _ = self.net._prep(flags)
         B, _, Z, Y, X = flags.shape
-        need = lib.tfl_model_backward_workspace_floats(h, B, Z, Y, X)
-        if self._bwd_work is None or self._bwd_work.numel() < need or self._bwd_work.device != flags.device:
-            self._bwd_work = torch.empty(max(int(need), 2), dtype=torch.float64, device=flags.device).view(torch.float32)
+        self._bwd_scratch(lib.tfl_model_backward_workspace_floats(h, B, Z, Y, X), flags.device)
         if out is None:
             gw, gb = [torch.empty_like(w) for w in self.weights], [torch.empty_like(b) for b in self.biases]
             tfluids._check(not accumulate, "accumulate needs out=(gradWeights, gradBiases)")

@@ -431,11 +431,13 @@ int tfl_model_finish(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* pDiv, con
  * model:backward (lib/run_epoch.lua:207-235, 269-293); tfl_fluidCriterion is the middle, these are the two ends. For linear
  * models (tfl_model_create[_ex|_opts]) whose layers neither pool nor upsample -- `default`, `yang`, custom layer tables, every
  * tfl_model_opts switch. Graph models and models with pooling / ConvolutionUpsample layers (`tog`) are refused with
- * TFL_EUNSUPPORTED before anything is written. Parameter gradients only: the gradients to pDiv, UDiv and flags are not built
- * (the reference computes a gradInput and run_epoch.lua discards it). */
+ * TFL_EUNSUPPORTED before anything is written. tfl_model_backward gives the parameter gradients (the reference computes a
+ * gradInput and run_epoch.lua discards it); tfl_model_backward_input also gives the gradients to pDiv and UDiv, for training
+ * through the net (an iterated projection, a loss behind a refinement pass, differentiable code in front of it). There is no
+ * gradient to flags. */
 
 /* New weights into an existing model: host pointers laid out as for tfl_model_create. Every re-layout the model's path holds
- * (the [tap][cin][cout] form, the MFMA fragments, the Winograd transform, the tail packs, the data-gradient form) is redone into
+ * (the [tap][cin][cout] form, the MFMA fragments, the Winograd transform, the tail packs, the data-gradient forms) is redone into
  * the buffers it already has, by the code that filled them at creation. Synchronous: waits for the context's stream, copies,
  * and returns with the new weights in place -- what an optimiser step calls; legal between two tfl_simulate_step calls. A
  * tfl_slab_graph recorded with this model holds per-layer constants of the OLD weights by value: the model does not know its
@@ -466,6 +468,33 @@ int64_t tfl_model_backward_workspace_floats(const tfl_model* model, int B, int Z
 int tfl_model_backward(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* flags, const tfl_tensor* gradP,
                        const tfl_tensor* gradU, const float* tape, int64_t tape_floats, float* workspace,
                        int64_t workspace_floats, float* const* gradWeights, float* const* gradBiases, int accumulate);
+/* Scratch floats tfl_model_backward_input needs (-1: the model has no training pass): tfl_model_backward's and, behind them,
+ * the first layer's data gradient, the skip channel's, and the partial sums of the scale's gradient. */
+int64_t tfl_model_backward_input_workspace_floats(const tfl_model* model, int B, int Z, int Y, int X);
+/* tfl_model_backward that also returns the gradients to the net's inputs: gradPDiv [B][1] and gradUDiv [B][C] (device,
+ * overwritten; either may be NULL) from the same gradP / gradU and tape. pDiv and UDiv are the tensors the forward was given,
+ * UOut the U it wrote. gradWeights and gradBiases may BOTH be NULL (input gradients only); where given, the parameter
+ * gradients are bit for bit those of tfl_model_backward on the same tape. The tape is tfl_model_forward_train's, unchanged.
+ * With s the item's input scale, q = 1 / s, U_bc = SetWallBcs(UDiv), d its divergence, h = s SetWallBcs(gradU):
+ *   g_x     the first layer's data gradient (its weights transposed and mirrored), g_skip the joined skip channel's
+ *   g_a     h where velocityUpdate keeps its velocity input, 0 where it overwrites it -- the true derivative (the reference's
+ *           tfluids.VelocityUpdate module passes zero to its velocity input; the net's input gradient does not)
+ *   g_s     sum gradP pPred + q sum gradU UOut - q [sum (g_x[p] + g_skip) q pDiv + sum (g_x[U] + g_a) q U_bc + sum g_x[d] q d],
+ *           one fp64 number per item: the scale depends on the inputs, and for most models that is most of gradUDiv
+ *   gradPDiv = q (g_x[p] + g_skip) [+ g_s ds/dpDiv]
+ *   gradUDiv = SetWallBcs(q (g_x[U] + g_a) + D^T(q g_x[d] [+ g_s ds/dd]) [+ g_s ds/dU_bc])
+ *   ds/dsrc = (src - mean) / ((n - 1) s) for std, src / s for the l2 norm, at the field normalizeInputChan names
+ * gradPDiv is exactly zero for a model with neither the pDiv channel, nor the skip, nor a pDiv normaliser. The sums of g_s run
+ * in a fixed order (fp32 products, fp64 sums, one partial per block at a fixed place, no atomics): the same inputs give the same
+ * bits on every call. Four to five launches more than tfl_model_backward (three more where the scale is taken from the
+ * divergence and the net has no div channel); no host read, no stream synchronisation; capturable. Sizes and shapes are checked
+ * before the first launch: graph models and models with pooling / upsampling layers are TFL_EUNSUPPORTED, a short tape or
+ * workspace TFL_EINVAL, each with nothing written. */
+int tfl_model_backward_input(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* flags, const tfl_tensor* pDiv,
+                             const tfl_tensor* UDiv, const tfl_tensor* UOut, const tfl_tensor* gradP, const tfl_tensor* gradU,
+                             const float* tape, int64_t tape_floats, float* workspace, int64_t workspace_floats,
+                             float* const* gradWeights, float* const* gradBiases, int accumulate, const tfl_tensor* gradPDiv,
+                             const tfl_tensor* gradUDiv);
 
 /* tfl_model_set_weights with DEVICE pointers (cudnn layout, one weight and one bias array per layer, as tfl_model_create takes
  * them from the host): every weight form the model's path holds is rebuilt by kernels enqueued on the context's stream, into
