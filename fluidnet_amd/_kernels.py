@@ -9,7 +9,8 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 KERNEL_SOURCE = {
     "k_conv3_in": "conv_mfma16.hip", "k_conv3_mid": "conv_mfma16.hip", "k_conv3_tail": "conv_mfma16.hip",
     "k_vel_fwd": "advect_vel3.hip+advect_vel3_kernels.hpp", "k_vel_bwd": "advect_vel3.hip+advect_vel3_kernels.hpp",
-    "k_scalar_fwd": "advect_scalar3.hip", "k_scalar_bwd": "advect_scalar3.hip", "k_minmax3": "advect.hip",
+    "k_scalar_fwd": "advect_scalar3.hip+advect_scalar3_sparse.hip", "k_scalar_bwd": "advect_scalar3.hip+advect_scalar3_sparse.hip",
+    "k_scal3_scan": "advect_scalar3_sparse.hip", "k_scal3_lists": "advect_scalar3_sparse.hip", "k_minmax3": "advect.hip",
     "k_curl": "vorticity.hip", "k_confine": "vorticity.hip", "k_vort_fused": "vorticity.hip", "k_stream_copy": "stencil.hip",
     "k_add_buoyancy": "stencil.hip", "k_add_gravity": "stencil.hip",
     "k_divnorm_planes": "divnorm.hip", "k_divnorm_finish": "divnorm.hip",

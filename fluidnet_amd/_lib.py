@@ -100,6 +100,7 @@ SIGNATURES = {
     "tfl_synchronize": (_c.c_int, [_c.c_void_p]),
     "tfl_trace_errors": (_c.c_int64, [_c.c_void_p]),
     "tfl_scal3_zero_blocks": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int64)]),
+    "tfl_scal3_sparse_stats": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int64)]),
     "tfl_profile_begin": (_c.c_int, [_c.c_void_p]),
     "tfl_profile_end": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_int64]),
     "tfl_advectScalar": (_c.c_int, [_c.c_void_p, _c.c_float, _T, _T, _T, _T, _T, _c.c_int,

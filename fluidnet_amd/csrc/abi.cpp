@@ -57,7 +57,7 @@ int advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor* U,
   }
   tfl::advect_scalar(c->stream, sc, is3D != 0, m, flags->B, flags->Z, flags->Y, flags->X, dt, maccormackStrength,
                      sampleOutsideFluid != 0, c->d_trace_err, s->data, U->data, flags->data, fwd_p, bounds_p, mm_p,
-                     sDst->data, ask.fold);
+                     sDst->data, ask.fold, &ask.sparse);
   return check_launch(c, "advectScalar");
 }
 

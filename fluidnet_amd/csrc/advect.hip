@@ -363,14 +363,14 @@ __global__ __launch_bounds__(256) void k_vel_bwd(AdvArgs a, const float* __restr
 // ---- host launchers ----------------------------------------------------------------------------
 template <bool IS3D>
 static void launch_scalar(hipStream_t st, int method, const AdvArgs& a, int B, const float* s, const float* U,
-                          const float* flags, float* fwd, float* bounds, float* mm, float* dst, int stages, Fold& f) {
+                          const float* flags, float* fwd, float* bounds, float* mm, float* dst, int stages, Fold& f, Scal3SparseAsk* sparse) {
   const dim3 blk(64, 4, 1), grd = cell_grid(a.d, B, blk);
   // stages (tfl_set_stages): 1 = the 3^dim min/max grid, 2 = pass A, 4 = pass B; single-pass methods are "pass A"
   const bool pm = stages & 1, pa = stages & 2, pb = stages & 4;
   if (method != kMacCormack && method != kMacCormackOurs && !pa) return;
   // the trace-based methods on a 3-D grid: LDS-tiled fast-path kernels without a min/max grid (advect_scalar3.hip)
   if (IS3D && (method == kEulerOurs || method == kMacCormackOurs) &&
-      advect_scalar3(st, method == kMacCormackOurs, a, B, s, U, flags, fwd, bounds, dst, stages, f))
+      advect_scalar3(st, method == kMacCormackOurs, a, B, s, U, flags, fwd, bounds, dst, stages, f, sparse))
     return;
   switch (method) {
     case kEuler: { TFL_TIMED("k_scalar_fwd", st); k_scalar_fwd<IS3D, kEuler><<<grd, blk, 0, st>>>(a, s, U, flags, dst, nullptr, nullptr, nullptr); break; }
@@ -406,11 +406,11 @@ void minmax3(hipStream_t st, bool is3d, int B, const Dom& d, int outside, const 
 
 void advect_scalar(hipStream_t st, const Scope& sc, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
                    int outside, unsigned long long* err, const float* s, const float* U, const float* flags,
-                   float* fwd, float* bounds, float* mm, float* dst, Fold& f) {
+                   float* fwd, float* bounds, float* mm, float* dst, Fold& f, Scal3SparseAsk* sparse) {
   AdvArgs a; a.d = make_dom(sc, Z, Y, X); a.dt = dt; a.strength = strength; a.outside = outside; a.err = err; a.fast = sc.advect_fast;
   const int stages = sc.passes();
-  if (is3d) launch_scalar<true>(st, method, a, B, s, U, flags, fwd, bounds, mm, dst, stages, f);
-  else launch_scalar<false>(st, method, a, B, s, U, flags, fwd, bounds, mm, dst, stages, f);
+  if (is3d) launch_scalar<true>(st, method, a, B, s, U, flags, fwd, bounds, mm, dst, stages, f, sparse);
+  else launch_scalar<false>(st, method, a, B, s, U, flags, fwd, bounds, mm, dst, stages, f, sparse);
 }
 
 template <bool IS3D>

@@ -66,7 +66,7 @@ namespace {
 #endif
 constexpr int TX = 64, TY = 4;
 constexpr float kFastLen = 0.99f;
-struct SBlock { int L, gx, gy, gz; };      // L < 0: the block is blockIdx of its own 3-D launch
+struct SBlock { int L, gx, gy, gz; bool tile = false; };      // L < 0: the block is blockIdx of its own 3-D launch; tile: (gx, gy, gz) is the tile itself
 // the "not a fluid cell" word of the masked tile: a quiet NaN with a payload no arithmetic produces (hardware NaNs are
 // 0x7fc00000 or carry an input's payload), recognised by its BIT PATTERN -- so a NaN that really sits in the advected
 // field of a fluid cell stays a value, as in the reference
@@ -327,15 +327,18 @@ __device__ __forceinline__ float max3r(float a, float b, float c) { float r; asm
 /* the geometry first: a kernel issues its own per-cell loads between GEOM and STAGE, so that they travel with the tile's */ \
 /* loads instead of costing a memory round trip of their own behind them (round 4) */
 /* (round 6: `sb` = the block's place -- SBlock{-1, ...}: blockIdx as it comes (the kernels below); SBlock{L, gx, gy, gz}: the */ \
-/* L-th block of a gx x gy x gz launch, for the pair kernels of advect_pair3.hip -- and `tile` a pointer to T::N floats of LDS) */
+/* L-th block of a gx x gy x gz launch, for the pair kernels of advect_pair3.hip; SBlock{-1, x, y, z, true}: the tile itself, for the */ \
+/* list-driven kernels of advect_scalar3_sparse.hip -- and `tile` a pointer to T::N floats of LDS) */
 #define TFL_SCAL3_GEOM(H)                                                                          \
   constexpr int PZ = TZ * KZ;                                                                      \
   using T = Tile<PZ, H>;                                                                           \
   const Dom& d = a.d;                                                                              \
   int bx_, by_, bz_;                                                                               \
-  if (sb.L < 0) block_tile(a.ord, bx_, by_, bz_);                                                  \
+  if (sb.tile) { bx_ = sb.gx; by_ = sb.gy; bz_ = sb.gz; }                                          \
+  else if (sb.L < 0) block_tile(a.ord, bx_, by_, bz_);                                             \
   else block_tile_linear(a.ord, (unsigned)sb.L, (unsigned)sb.gx, (unsigned)sb.gy, bx_, by_, bz_);  \
-  int b, k0, kend; group_planes<PZ>(d, bz_, sb.L < 0 ? (int)gridDim.z : sb.gz, b, k0, kend);       \
+  /* (a tile's gz counts plane groups through the batch items: 0 is never the groups of one item, so group_planes divides) */ \
+  int b, k0, kend; group_planes<PZ>(d, bz_, sb.tile ? 0 : (sb.L < 0 ? (int)gridDim.z : sb.gz), b, k0, kend);   \
   const long long cells = (long long)d.sc;                                                         \
   s += b * cells; flags += b * cells; U += b * cells * 3;                                          \
   const int lane = threadIdx.x, ty = threadIdx.y, tz = threadIdx.z;                                \
@@ -579,13 +582,23 @@ int scal3_zskip(const Dom& d) {
 }
 
 bool advect_scalar3(hipStream_t st, bool two_pass, const AdvArgs& a0, int B, const float* s, const float* U, const float* flags,
-                    float* fwd, float* bounds, float* dst, int stages, Fold& f) {
+                    float* fwd, float* bounds, float* dst, int stages, Fold& f, Scal3SparseAsk* sparse) {
   const bool off = sw::present(Sw::ADVECT_GATHER) || sw::present(Sw::SCALAR_GATHER);   // A/B switch: the round-2 gather kernels
   const int tzsel = sw::num(Sw::SCAL3_TZ, 0);   // 0 = per pass and grid size (launch)
   const Dom& d = a0.d;
-  // 24-bit multiplies address the tile and the planes; 32-bit BYTE offsets the cells of the three velocity channels
-  if (off || a0.outside || d.Z < 3 || (long long)d.X * d.Y * 4 >= (1 << 24) || 12ll * d.sc >= (1ll << 32)) return false;
+  if (off || a0.outside || !scal3_shape_ok(d)) return false;
   AdvArgs a = a0; a.zskip = scal3_zskip(d);
+  // tfl_simulate_step's request (advect_scalar3_sparse.hip): the brick scan and lists, then the passes over the lists or, for a
+  // probe, today's two launches. Taken only for the in-place two-pass call on the whole array; anything else runs as before.
+  if (sparse && sparse->run && two_pass && dst == s && (stages & 6) == 6 && scal3_sparse_fits(d)) {
+    scal3_sparse_scan(st, a, B, s, U, f.bc, *sparse);
+    sparse->took = 1;
+    if (sparse->run == 2) {
+      scal3_sparse_passes(st, a, B, dst, U, flags, fwd, bounds, f.hand_bc(), *sparse);
+      sparse->took = 2;
+      return true;
+    }
+  }
 #ifdef TFL_EXPERIMENTS
   // the z-marched kernels (round 5): TFL_SCAL3_MARCH=1 -- bit-identical, one staging pass per plane, and SLOWER than the
   // tile kernels (profiles/r05_advect_experiments.txt: pass A 29.5 vs 25.3 us at 128^3, 176 vs 162 at 256^3; pass B 21.3 vs

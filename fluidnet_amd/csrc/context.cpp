@@ -65,6 +65,40 @@ double get_dx_double(const tfl_ctx* c, const Scope& sc, const tfl_tensor* f) {
   if (sc.dx_cells <= 0 && c && c->dx_override > 0.0f) return (double)c->dx_override;
   return 1.0 / (double)dx_cells(sc, f);
 }
+
+static void scal3_sparse_free(Scal3SparseState* p) {
+  if (p->buf.nz) (void)hipFree(p->buf.nz);
+  if (p->buf.fast) (void)hipFree(p->buf.fast);
+  if (p->buf.lists) (void)hipFree(p->buf.lists);
+  if (p->buf.counts) (void)hipFree(p->buf.counts);
+  if (p->h_mirror) (void)hipHostFree(p->h_mirror);
+  delete p;
+}
+Scal3SparseState* scal3_sparse_state(tfl_ctx* c, const float* key, int B, int Z, int Y, int X, int bricks) {
+  for (Scal3SparseState* p : c->scal3_sparse)
+    if (p->key == key && p->B == B && p->Z == Z && p->Y == Y && p->X == X) return p;
+  if ((int)c->scal3_sparse.size() >= kScal3SparseFields) {      // the oldest field goes (hipFree waits for the kernels that use it)
+    if (c->scal3_last == c->scal3_sparse.front()) c->scal3_last = nullptr;
+    scal3_sparse_free(c->scal3_sparse.front());
+    c->scal3_sparse.erase(c->scal3_sparse.begin());
+  }
+  Scal3SparseState* p = new Scal3SparseState();
+  p->key = key; p->B = B; p->Z = Z; p->Y = Y; p->X = X;
+  const size_t n = (size_t)B * (size_t)bricks;
+  if (hipMalloc((void**)&p->buf.nz, n) != hipSuccess ||
+      hipMalloc((void**)&p->buf.fast, sizeof(unsigned) * B) != hipSuccess || hipMemset(p->buf.fast, 0, sizeof(unsigned) * B) != hipSuccess ||
+      hipMalloc((void**)&p->buf.lists, sizeof(int) * 2 * n) != hipSuccess ||
+      hipMalloc((void**)&p->buf.counts, sizeof(int) * 4 * B) != hipSuccess || hipMemset(p->buf.counts, 0, sizeof(int) * 4 * B) != hipSuccess ||
+      hipHostMalloc((void**)&p->h_mirror, sizeof(unsigned) * 8 * B, hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&p->buf.mirror, p->h_mirror, 0) != hipSuccess) {
+    (void)hipGetLastError();
+    scal3_sparse_free(p);
+    return nullptr;
+  }
+  memset(p->h_mirror, 0, sizeof(unsigned) * 8 * B);      // the scan's number 0: nothing known yet
+  c->scal3_sparse.push_back(p);
+  return p;
+}
 }  // namespace tfl
 
 extern "C" {
@@ -106,6 +140,7 @@ int tfl_get_advect_mode(const tfl_ctx* c) { return c ? (c->advect_fast ? TFL_ADV
 void tfl_destroy(tfl_ctx* c) {
   if (!c) return;
   { std::lock_guard<std::mutex> lock(c->wall_mu); for (tfl_wall_plan* p : c->wall_plans) p->owner = nullptr; c->wall_plans.clear(); }      // the host still owns (and frees) them
+  for (Scal3SparseState* p : c->scal3_sparse) tfl::scal3_sparse_free(p);
   if (c->d_reach) (void)hipFree(c->d_reach);
   if (c->h_reach) (void)hipHostFree(c->h_reach);
   if (c->d_reach_tick) (void)hipFree(c->d_reach_tick);
@@ -215,6 +250,18 @@ int tfl_scal3_zero_blocks(tfl_ctx* c, int64_t* blocks) {
   HIP_TRY(c, hipMemsetAsync(c->d_trace_err + 1, 0, sizeof(v), c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   blocks[0] = (int64_t)v[0]; blocks[1] = (int64_t)v[1];
+  return TFL_OK;
+}
+
+int tfl_scal3_sparse_stats(tfl_ctx* c, int64_t* out) {
+  if (!c || !out) return TFL_EINVAL;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // the last lists kernel has published its counts
+  for (int i = 0; i < 3; i++) { out[i] = (int64_t)c->scal3_counts[i]; c->scal3_counts[i] = 0; }
+  out[3] = out[4] = 0;
+#ifdef TFL_EXPERIMENTS
+  if (const Scal3SparseState* p = c->scal3_last)
+    for (int b = 0; b < p->B; b++) { out[3] += p->h_mirror[8 * b + 3]; out[4] += p->h_mirror[8 * b]; }
+#endif
   return TFL_OK;
 }
 

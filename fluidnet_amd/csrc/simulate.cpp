@@ -125,6 +125,65 @@ LateUbc late_ubc_of(const tfl_sim_state* s) {
   return LateUbc{late, (s->UBC && !late) ? &s->UBC->bc : nullptr, (s->UBC && !late) ? &s->UBC->inv : nullptr};
 }
 
+
+// ---- advectScalar over the list of non-empty bricks: the host policy (advect_scalar3_sparse.hip) -----------------
+// What a step does with the in-place maccormackOurs advection of a 3-D density field: today's two launches (full), the same behind
+// a brick scan (probe), or the scan and the two passes over the lists it builds (lists). All three give the same bits for any
+// state of the field, so the choice is one of time only. It is made from the words the lists kernel of an EARLIER scan left in
+// pinned memory, read without any synchronisation: a stale value can cost time, never bits.
+// mode: TFL_SCAL3_SPARSE (EXPERIMENTS flavour; the product library always runs the policy, 1). known: a scan has published.
+// listed / bricks: |L_B| and the brick count of that scan; fast: it found a velocity word with !(|u dt| <= 0.9), so it listed
+// everything. since_scan: steps on the two full launches since the last scan.
+enum class SparsePlan { full, probe, lists };
+// (profiles/scal3_sparse.md: at 128^3 the lists save 6 us with a fifth of the bricks listed, their passes grow by 0.023 us per listed
+// brick and meet the two full launches at about a third; a probe costs 16 us, 0.4 % of a step when paid every 16th)
+constexpr double kSparseThreshold = 0.25;  // the lists as long as at most this share of the bricks is listed
+constexpr unsigned kSparseProbe = 16;      // above it one step in 16 scans, so that the state can come back
+SparsePlan scal3_sparse_plan(int mode, bool known, unsigned listed, unsigned bricks, bool fast, unsigned since_scan) {
+  if (mode == 0) return SparsePlan::full;
+  if (mode == 2 || !known) return SparsePlan::lists;
+  if (!fast && (double)listed <= kSparseThreshold * (double)bricks) return SparsePlan::lists;
+  return since_scan + 1 >= kSparseProbe ? SparsePlan::probe : SparsePlan::full;
+}
+
+// The request that goes with the advection of density field `rho` (tfl_host.hpp Scal3SparseAsk; run == 0: none) and the field's
+// state. Only for the whole un-cut array -- no z-window, stage mask or origin -- advected in place with a finite strength (the
+// proof's border cells need hs * 0 = 0), on a shape the brick map holds. While the stream is capturing: no request and no state
+// change (a graph replays one decision for ever, and nothing may be allocated), the wall plan's rule.
+tfl::Scal3SparseAsk scal3_sparse_ask(tfl_ctx* c, const tfl_sim_params* prm, const tfl::Scope& sc, const Sizes& z, bool in_place,
+                                     const tfl_tensor* rho, Scal3SparseState** state) {
+  *state = nullptr;
+  tfl::Scal3SparseAsk ask;
+  const int mode = tfl::sw::num(tfl::Sw::SCAL3_SPARSE, 1);
+  if (mode == 0 || !z.is3d || !in_place || sc.windowed() || sc.stages != 0 || sc.origin.total != 0 || !std::isfinite(prm->maccormackStrength)) return ask;
+  if (!tfl::scal3_sparse_fits(tfl::whole_dom(z.Z, z.Y, z.X))) return ask;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(c->stream, &cs) != hipSuccess) { (void)hipGetLastError(); return ask; }
+  if (cs != hipStreamCaptureStatusNone) return ask;
+  Scal3SparseState* st = tfl::scal3_sparse_state(c, rho->data, z.B, z.Z, z.Y, z.X, tfl::scal3_sparse_bricks(z.Z, z.Y, z.X));
+  if (!st) return ask;
+  bool known = true, fast = false;
+  unsigned listed = 0, bricks = 0;
+  const volatile unsigned* m = st->h_mirror;
+  for (int b = 0; b < z.B; b++) { listed += m[8 * b]; bricks += m[8 * b + 1]; fast = fast || m[8 * b + 2] != 0; known = known && m[8 * b + 4] != 0; }
+  const SparsePlan plan = scal3_sparse_plan(mode, known, listed, bricks, fast, st->since_scan);
+  if (plan == SparsePlan::full) { *state = st; return ask; }
+  ask = st->buf;
+  ask.run = plan == SparsePlan::lists ? 2 : 1;
+  ask.took = 0;
+  ask.seq = st->scans + 1;
+  *state = st;
+  return ask;
+}
+// what the operator did of the request (Scal3SparseAsk::took), into the field's state and the EXPERIMENTS flavour's counters
+void scal3_sparse_done(tfl_ctx* c, Scal3SparseState* st, int took) {
+  if (st && took) { st->scans++; st->since_scan = 0; c->scal3_last = st; }
+  else if (st) st->since_scan++;
+#ifdef TFL_EXPERIMENTS
+  c->scal3_counts[0] += took ? 1 : 0; c->scal3_counts[1] += took == 2 ? 1 : 0; c->scal3_counts[2] += took == 2 ? 0 : 1;
+#endif
+}
+
 }  // namespace
 
 extern "C" {
@@ -226,8 +285,12 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
     // the first setConstVals (below) follows the advection directly: the kernel that writes the advected field applies
     // the field's pair itself where it can (step_ask; the sparse launch covers the rest)
     tfl::Ask a = step_ask(s->densityBC[i]);
+    // ... and, where most of the field is +0.0, only over the bricks around the words that are not (scal3_sparse_ask)
+    Scal3SparseState* sparse = nullptr;
+    a.sparse = scal3_sparse_ask(c, prm, sc, z, ours, s->density[i], &sparse);
     rc = tfl::advectScalar(c, prm->dt, s->density[i], s->U, s->flags, &fwd, &bwd, is3D, method, &fwdPos, &bwdPos, 1, 0,
                            prm->maccormackStrength, dst, sc, a);
+    if (ours && z.is3d) scal3_sparse_done(c, sparse, a.sparse.took);
     if (a.fold.bc_took) density_done |= 1u << i;
     if (rc) return rc;
     if (!ours) { rc = tfl_copy(c, s->density[i], &out); if (rc) return rc; }

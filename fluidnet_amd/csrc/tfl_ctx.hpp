@@ -20,6 +20,18 @@ struct tfl_wall_plan {
   struct tfl_ctx* owner = nullptr;            // the context it is registered with (cleared by tfl_destroy: the plan may outlive it)
 };
 
+// What tfl_simulate_step keeps per density field for the passes over the list of non-empty bricks (advect_scalar3_sparse.hip): the
+// device buffers of a Scal3SparseAsk and the pinned words its lists kernel leaves for the policy of later steps. Found again by
+// the field's address and shape; allocated once (context.cpp scal3_sparse_state), never while the stream is capturing.
+struct Scal3SparseState {
+  const float* key = nullptr;
+  int B = 0, Z = 0, Y = 0, X = 0;
+  tfl::Scal3SparseAsk buf;                    // nz, fast, lists, counts, mirror (run / took / seq are per call)
+  unsigned* h_mirror = nullptr;               // pinned, mapped: 8 words per batch item (|L_B|, bricks, fast, |L_A|, the scan's number)
+  unsigned scans = 0;                         // scans launched for this field so far (the next scan's number - 1)
+  unsigned since_scan = 0;                    // steps on the two full launches since the last scan
+};
+
 struct tfl_ctx {
   std::vector<tfl_wall_plan*> wall_plans;     // registered by tfl_wall_plan_create, looked up by tfl_model_begin
   std::mutex wall_mu;                         // (a binding may retire a plan from a finalizer thread while this context steps)
@@ -54,4 +66,14 @@ struct tfl_ctx {
   int wf_skip = 0;                            // > 0: a pipelined PCG sweep timed out on this context: the next wf_skip solves go straight to
                                               // hyperplane sweeps, then the pipelined form is tried again (a transient stall must not latch for good)
   int wf_timeouts = 0;                        // how often that happened (the back-off doubles, one warning per latch)
+  std::vector<Scal3SparseState*> scal3_sparse;   // one per density field tfl_simulate_step has advected over brick lists (at most kScal3SparseFields)
+  Scal3SparseState* scal3_last = nullptr;        // the field of the last scan
+  long long scal3_counts[3] = {0, 0, 0};         // EXPERIMENTS flavour (tfl_scal3_sparse_stats): scans, steps over the lists, steps on the two full launches
 };
+
+namespace tfl {
+constexpr int kScal3SparseFields = 8;      // a step has at most 8 density channels
+// the state of the density field at `key` ([B][1][Z][Y][X], `bricks` bricks per item), created on first use (allocates: never call
+// it while the stream is capturing); null when an allocation fails
+Scal3SparseState* scal3_sparse_state(tfl_ctx* c, const float* key, int B, int Z, int Y, int X, int bricks);
+}  // namespace tfl

@@ -62,6 +62,20 @@ struct Fold {
   BuoyFold hand_buoy() { buoy_took = buoy_took || buoy.rho; return buoy; }
 };
 
+// What tfl_simulate_step asks of the in-place maccormackOurs advectScalar of a 3-D density (advect_scalar3_sparse.hip, DESIGN.md
+// 3.17): find the bricks of 64 x 4 x 4 cells that hold a word other than +0.0, and run the two passes over the bricks around
+// them only. The buffers belong to the context (tfl_ctx.hpp Scal3SparseState: one set per density field, allocated once).
+struct Scal3SparseAsk {
+  int run = 0;                     // 0 = nothing | 1 = scan + lists, then the two full launches (a probe) | 2 = scan + lists + list-driven passes
+  int took = 0;                    // out: what the operator did of it (0: it ran the two full launches and nothing else)
+  unsigned seq = 0;                // the scan's number (> 0), published behind its counts
+  unsigned char* nz = nullptr;     // [B][bricks]: the brick holds a word of s that is not +0.0
+  unsigned* fast = nullptr;        // [B]: some velocity face has !(|U dt| <= 0.9); the lists kernel reads and clears it
+  int* lists = nullptr;            // [2][B][bricks]: the compacted lists L_A, L_B (brick indices, ascending)
+  int* counts = nullptr;           // [B][4]: |L_A|, |L_B|, fast as the lists kernel read it
+  unsigned* mirror = nullptr;      // device address of the pinned mirror, 8 words per item: |L_B|, bricks, fast, |L_A|, seq
+};
+
 // does row (j, k) / cell i of the field lie inside the pair's box
 __device__ __forceinline__ bool fold_row(const BcFold& f, int j, int k) {
   return j >= f.y0 && j <= f.y1 && k >= f.z0 && k <= f.z1;
@@ -129,7 +143,10 @@ struct KernelTimer {
 // advect.hip
 void advect_scalar(hipStream_t st, const Scope& sc, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
                    int outside, unsigned long long* err, const float* s, const float* U, const float* flags,
-                   float* fwd, float* bounds, float* mm, float* dst, Fold& f);
+                   float* fwd, float* bounds, float* mm, float* dst, Fold& f, Scal3SparseAsk* sparse = nullptr);
+// advect_scalar3_sparse.hip
+int scal3_sparse_bricks(int Z, int Y, int X);      // bricks per batch item; 0 = the grid is outside what the brick map holds
+bool scal3_sparse_fits(const Dom& d);              // the whole array, a shape the tile kernels and the brick map take, no forced kernel form
 void advect_vel(hipStream_t st, const Scope& sc, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
                 unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, Fold& f);
 

@@ -51,6 +51,7 @@ int tfl_get_advect_mode(const tfl_ctx* ctx);
 int tfl_synchronize(tfl_ctx* ctx);
 int64_t tfl_trace_errors(tfl_ctx* ctx);
 int tfl_scal3_zero_blocks(tfl_ctx* ctx, int64_t* blocks);
+int tfl_scal3_sparse_stats(tfl_ctx* ctx, int64_t* stats);
 int tfl_profile_begin(tfl_ctx* ctx);
 int tfl_profile_end(tfl_ctx* ctx, char* buf, int64_t cap);
 int tfl_advectScalar(tfl_ctx* ctx, float dt, const tfl_tensor* s, const tfl_tensor* U,

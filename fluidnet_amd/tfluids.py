@@ -537,6 +537,16 @@ def scal3ZeroBlocks(like):
     return int(out[0]), int(out[1])
 
 
+def scal3SparseStats(like):
+    """(scans, steps over the brick lists, steps on the two full launches) of simulate_native's in-place advectScalar since the last
+    call, and (|L_A|, |L_B|) of the last scan. Counted by the EXPERIMENTS flavour of the library only; the product library reports
+    zeros."""
+    lib, ctx = _context(like)
+    out = (ctypes.c_int64 * 5)()
+    _call(lib, ctx, lib.tfl_scal3_sparse_stats(ctx, out))
+    return tuple(int(v) for v in out)
+
+
 class profile:
     """with tfluids.profile(tensor) as prof: ...; prof.kernels -> {name: {"calls": n, "ms": total}}.
     Per-kernel HIP-event timing inside the library (tfl_profile_begin/end)."""

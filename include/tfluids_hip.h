@@ -100,6 +100,11 @@ int64_t tfl_trace_errors(tfl_ctx* ctx);
  * blocks of pass A / pass B of the tiled 3-D advectScalar kernels whose staged tile held nothing but +0.0 and non-fluid cells
  * (they take the short path) since the last call. Synchronises the stream. Diagnostic only. */
 int tfl_scal3_zero_blocks(tfl_ctx* ctx, int64_t* blocks);
+/* EXPERIMENTS flavour of the library only (the product library reports zeros): what tfl_simulate_step did with the in-place
+ * advectScalar of its density fields since the last call -- stats[0] = brick scans launched, stats[1] = steps
+ * whose two passes ran over the lists of non-empty bricks, stats[2] = steps on the two full launches -- and, of the last scan,
+ * stats[3] = |L_A| and stats[4] = |L_B| (bricks of 64 x 4 x 4 cells, summed over the batch). Synchronises the stream. Diagnostic only. */
+int tfl_scal3_sparse_stats(tfl_ctx* ctx, int64_t* stats);
 
 /* Built-in per-kernel timing, the analogue of tfluids.profilePressure (lib/simulate.lua:254-260,
  * 306-318) at kernel granularity: between begin and end every kernel this library launches from the
