@@ -30,6 +30,7 @@ struct WgArgs {
   int Z, Y, X, cin, cout, k, taps, ych, act, wb, is3d;
   int ch, tt, S, ntx, nty;
   long long tiles;
+  int dil;              // tap spacing (a dilated bank's module; read by the DIL instantiations only)
 };
 
 // act'(y) from the saved output: ReLU y > 0, ReLU6 0 < y < 6, sigmoid y (1 - y)
@@ -39,11 +40,13 @@ __device__ __forceinline__ float act_grad(float g, float y, int act) {
   return g * (y * (1.0f - y));
 }
 
-template <int CB>
+// DIL = false: tap spacing 1 as a constant -- the kernel of the linear models, unchanged by the dilated form
+template <int CB, bool DIL>
 __global__ __launch_bounds__(kWgThreads) void k_conv_wgrad(WgArgs a) {
   extern __shared__ float lds[];
   const int tid = threadIdx.x;
-  const WgHalo h = wg_halo(a.is3d != 0, a.k);
+  const int dil = DIL ? a.dil : 1;
+  const WgHalo h = wg_halo(a.is3d != 0, a.k, dil);
   float* xs = lds;                        // [ch][HZ][HY][HX]
   float* gs = lds + a.ch * h.floats;      // [voxel][CB]
   const long long cells = (long long)a.Z * a.Y * a.X;
@@ -53,7 +56,7 @@ __global__ __launch_bounds__(kWgThreads) void k_conv_wgrad(WgArgs a) {
     for (int ci0 = 0; ci0 < a.cin; ci0 += a.ch)
       for (int t0 = 0; t0 < a.taps; t0 += a.tt) {
         const WgChunk ck = wg_chunk(a.ch, a.tt, a.cin, a.taps, ci0, t0);      // (its first chunk carries the bias row and masks g)
-        const WgThread t = wg_thread(tid, ck, h, a.S, ci0, t0, a.k, a.taps, a.is3d != 0, M);
+        const WgThread t = wg_thread(tid, ck, h, a.S, ci0, t0, a.k, a.taps, a.is3d != 0, M, dil);
         const bool mask_now = a.act != 0 && (!a.wb || ck.first);
         double acc64[CB];
 #pragma unroll
@@ -131,7 +134,7 @@ __global__ __launch_bounds__(kWgThreads) void k_conv_wgrad(WgArgs a) {
 // partials y, y + 8, ... in ascending order, lane 0 then adds the eight lanes in order; then the cudnn layout.
 __global__ __launch_bounds__(256) void k_conv_wgrad_finish(const double* __restrict__ partials, int P, int M, int cout, int taps, int cin,
                                                            int cin_ref, int cout_ref, int skip_in, float* __restrict__ gw,
-                                                           float* __restrict__ gb, int accumulate) {
+                                                           float* __restrict__ gb, int accumulate, int join_c, int join_p) {
   __shared__ double sh[8][33];
   const int total = (M + 1) * cout;
   const int o = blockIdx.x * 32 + threadIdx.x;
@@ -149,7 +152,7 @@ __global__ __launch_bounds__(256) void k_conv_wgrad_finish(const double* __restr
     if (co >= cout_ref) return;
     dst = gb + co;
   } else {
-    const long long i = wg_cudnn_index(row, co, taps, cin, cin_ref, cout_ref, skip_in);
+    const long long i = wg_cudnn_index(row, co, taps, cin, cin_ref, cout_ref, skip_in, join_c, join_p);
     if (i < 0) return;
     dst = gw + i;
   }
@@ -202,25 +205,147 @@ bool conv_wgrad(hipStream_t st, bool is3d, const WgPlan& p, int B, int Z, int Y,
   a.x = x; a.g = g; a.y = y; a.partials = partials;
   a.Z = Z; a.Y = Y; a.X = X; a.cin = cin; a.cout = cout; a.k = k; a.taps = p.taps; a.ych = ych; a.act = y ? act : 0; a.wb = wb ? 1 : 0;
   a.is3d = is3d ? 1 : 0;
+  a.dil = p.dil;
   a.ch = p.ch; a.tt = p.tt; a.S = p.S; a.ntx = (X + kWgTX - 1) / kWgTX; a.nty = (Y + kWgTY - 1) / kWgTY; a.tiles = p.tiles;
   const size_t shmem = sizeof(float) * (size_t)p.lds_floats;
   TFL_TIMED("k_conv_wgrad", st);
+#define TFL_WG(N)                                                                                  \
+  case N:                                                                                          \
+    if (p.dil > 1) k_conv_wgrad<N, true><<<p.nblocks, kWgThreads, shmem, st>>>(a);                 \
+    else k_conv_wgrad<N, false><<<p.nblocks, kWgThreads, shmem, st>>>(a);                          \
+    return true;
   switch (p.cb) {
-    case 1: k_conv_wgrad<1><<<p.nblocks, kWgThreads, shmem, st>>>(a); return true;
-    case 2: k_conv_wgrad<2><<<p.nblocks, kWgThreads, shmem, st>>>(a); return true;
-    case 4: k_conv_wgrad<4><<<p.nblocks, kWgThreads, shmem, st>>>(a); return true;
-    case 8: k_conv_wgrad<8><<<p.nblocks, kWgThreads, shmem, st>>>(a); return true;
-    case 16: k_conv_wgrad<16><<<p.nblocks, kWgThreads, shmem, st>>>(a); return true;
+    TFL_WG(1) TFL_WG(2) TFL_WG(4) TFL_WG(8) TFL_WG(16)
     default: return false;
   }
+#undef TFL_WG
 }
 
 void conv_wgrad_finish(hipStream_t st, const WgPlan& p, int cin, int cout, int cin_ref, int cout_ref, int skip_in, const double* partials,
-                       float* gw, float* gb, int accumulate) {
+                       float* gw, float* gb, int accumulate, int join_c, int join_p) {
   const int M = cin * p.taps;
   TFL_TIMED("k_conv_wgrad_finish", st);
   k_conv_wgrad_finish<<<((M + 1) * cout + 31) / 32, dim3(32, 8), 0, st>>>(partials, p.nblocks, M, cout, p.taps, cin, cin_ref, cout_ref,
-                                                                        skip_in, gw, gb, accumulate);
+                                                                        skip_in, gw, gb, accumulate, join_c, join_p);
+}
+
+// ---- the fixed linear maps of a banked model, backwards: streaming kernels, every output element written once
+// by one thread from sums in a fixed order, no atomics ------------------------------------------------------------------------
+struct JoinBwdDst { int n; int sh[kTrainMaxBanks]; float* dst[kTrainMaxBanks]; };
+
+// W consecutive floats of a row, added left to right onto s: one 64- or 128-bit load where the row start is aligned for it
+template <int W>
+__device__ __forceinline__ float row_sum(const float* __restrict__ p, float s) {
+  if (W == 2 && ((uintptr_t)p & 7) == 0) { const float2 v = *reinterpret_cast<const float2*>(p); return (s + v.x) + v.y; }
+  if (W == 4 && ((uintptr_t)p & 15) == 0) { const float4 v = *reinterpret_cast<const float4*>(p); return (((s + v.x) + v.y) + v.z) + v.w; }
+#pragma unroll
+  for (int i = 0; i < W; i++) s += p[i];
+  return s;
+}
+
+// The join's backward, one launch per join: blockIdx.z = bank i, blockIdx.y = (b, c), the block's threads = cells of the bank's
+// own grid. From g [B][och] at the join's resolution [Z][Y][X], bank i gets [B][C] at (grid >> sh_i): its channel slice (concat) or
+// every channel (add); sh = 0 a copy, else the sum over the (2^sh)^dim cells the nearest up-sample replicated the cell over, in
+// fp32, z then y then x (join_bwd_child's order).
+template <bool IS3D>
+__global__ __launch_bounds__(256) void k_join_bwd(int C, int och, int concat, int Z, int Y, int X, JoinBwdDst jd, const float* __restrict__ g) {
+  const int i = blockIdx.z, sh = jd.sh[i];
+  const int Zs = IS3D ? Z >> sh : Z, Ys = Y >> sh, Xs = X >> sh;
+  const long long cs = (long long)Zs * Ys * Xs, t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= cs) return;
+  const int b = blockIdx.y / C, c = blockIdx.y - b * C;
+  const float* __restrict__ gp = g + ((long long)b * och + join_bwd_plane(concat != 0, i, C, c)) * ((long long)Z * Y * X);
+  float* __restrict__ out = jd.dst[i] + (long long)blockIdx.y * cs;
+  if (sh == 0) { out[t] = gp[t]; return; }
+  const int x = (int)(t % Xs), y = (int)((t / Xs) % Ys), z = (int)(t / ((long long)Xs * Ys));
+  const int w = 1 << sh, wz = IS3D ? w : 1;
+  float s = 0.0f;
+  for (int dz = 0; dz < wz; dz++)
+    for (int dy = 0; dy < w; dy++) {
+      const float* __restrict__ row = gp + join_bwd_child(IS3D, sh, z, y, x, (dz * w + dy) * w, Y, X);
+      if (sh == 1) s = row_sum<2>(row, s);
+      else if (sh == 2) s = row_sum<4>(row, s);
+      else for (int dx = 0; dx < w; dx++) s += row[dx];
+    }
+  out[t] = s;
+}
+
+bool join_bwd(hipStream_t st, bool is3d, bool concat, int B, int C, int och, int Z, int Y, int X, int n, const int* sh, float* const* dst,
+              const float* g) {
+  if (n < 1 || n > kTrainMaxBanks) return false;
+  JoinBwdDst jd;
+  jd.n = n;
+  for (int i = 0; i < n; i++) { jd.sh[i] = sh[i]; jd.dst[i] = dst[i]; }
+  const long long cells = train_cells(is3d, sh[0], Z, Y, X);      // (bank 0 is the finest)
+  const dim3 grd((unsigned)((cells + 255) / 256), (unsigned)(B * C), (unsigned)n);
+  TFL_TIMED("k_join_bwd", st);
+  if (is3d) k_join_bwd<true><<<grd, 256, 0, st>>>(C, och, concat ? 1 : 0, Z, Y, X, jd, g);
+  else k_join_bwd<false><<<grd, 256, 0, st>>>(C, och, concat ? 1 : 0, Z, Y, X, jd, g);
+  return true;
+}
+
+// The average-pooling pyramid's backward with accumulate, one launch per level: dst = a + P^T c, P^T = every coarse cell of
+// c [rows][Z/2][Y/2][X/2] over its 2^dim children times 1/2^dim. A thread owns the two x-children of one coarse cell in one fine row
+// (X is even: one 64-bit load and store; the buffers are 8-byte aligned). dst may be a.
+template <bool IS3D>
+__global__ __launch_bounds__(256) void k_pyr_pool_bwd(int Z, int Y, int X, const float* a, const float* __restrict__ c, float* dst) {
+  const int Xh = X >> 1;
+  const long long pairs = (long long)Z * Y * Xh, t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= pairs) return;
+  const int xc = (int)(t % Xh), y = (int)((t / Xh) % Y), z = (int)(t / ((long long)Xh * Y));
+  const long long cells = (long long)Z * Y * X;
+  const float v = c[(long long)blockIdx.y * (cells >> (IS3D ? 3 : 2)) + pyr_bwd_parent(IS3D, z, y, 2 * xc, Y, X)] * (IS3D ? 0.125f : 0.25f);
+  const long long o = (long long)blockIdx.y * cells + ((long long)z * Y + y) * X + 2 * xc;
+  float2 f = *reinterpret_cast<const float2*>(a + o);
+  f.x += v; f.y += v;
+  *reinterpret_cast<float2*>(dst + o) = f;
+}
+
+void pyr_pool_bwd(hipStream_t st, bool is3d, int rows, int Z, int Y, int X, const float* a, const float* c, float* dst) {
+  const long long pairs = (long long)Z * Y * (X / 2);
+  const dim3 grd((unsigned)((pairs + 255) / 256), (unsigned)rows);
+  TFL_TIMED("k_pyr_pool_bwd", st);
+  if (is3d) k_pyr_pool_bwd<true><<<grd, 256, 0, st>>>(Z, Y, X, a, c, dst);
+  else k_pyr_pool_bwd<false><<<grd, 256, 0, st>>>(Z, Y, X, a, c, dst);
+}
+
+// The dilate split's backward: dst = ((src0 + src1) + src2) ... in bank order, fp32; 128-bit where every buffer is aligned for it
+struct BankSumSrc { int n; const float* src[kTrainMaxBanks]; };
+__global__ __launch_bounds__(256) void k_bank_sum(long long count, int vec, BankSumSrc bs, float* __restrict__ dst) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (vec) {
+    if (4 * t + 3 < count) {
+      float4 s = reinterpret_cast<const float4*>(bs.src[0])[t];
+      for (int q = 1; q < bs.n; q++) {
+        const float4 v = reinterpret_cast<const float4*>(bs.src[q])[t];
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+      }
+      reinterpret_cast<float4*>(dst)[t] = s;
+      return;
+    }
+    for (long long e = 4 * t; e < count; e++) {      // (the ragged end: at most three elements, one thread)
+      float s = bs.src[0][e];
+      for (int q = 1; q < bs.n; q++) s += bs.src[q][e];
+      dst[e] = s;
+    }
+    return;
+  }
+  if (t >= count) return;
+  float s = bs.src[0][t];
+  for (int q = 1; q < bs.n; q++) s += bs.src[q][t];
+  dst[t] = s;
+}
+
+bool bank_sum(hipStream_t st, long long count, int n, const float* const* src, float* dst) {
+  if (n < 1 || n > kTrainMaxBanks) return false;
+  BankSumSrc bs;
+  bs.n = n;
+  bool vec = ((uintptr_t)dst & 15) == 0;
+  for (int q = 0; q < n; q++) { bs.src[q] = src[q]; vec = vec && ((uintptr_t)src[q] & 15) == 0; }
+  const long long threads = vec ? (count + 3) / 4 : count;
+  TFL_TIMED("k_bank_sum", st);
+  k_bank_sum<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(count, vec ? 1 : 0, bs, dst);
+  return true;
 }
 
 }  // namespace tfl

@@ -272,11 +272,28 @@ tfl_model* build_layers(tfl_ctx* c, bool is3d, int n, const int32_t* cin, const 
   if (down != 1) return cleanup("the layers do not return to the grid resolution (pool / up factors)");
   if (N > 1 && t.mres) m->multires = true;
   if (m->max_c < 1) m->max_c = 1;
-  if (!g && !m->multires) {     // a model tfl_model_backward takes: the data-gradient weights and the zero bias of their convolutions
+  // A model tfl_model_backward takes: a linear one without pooling / upsampling, or a graph model without batch norm
+  // whose modules neither pool nor upsample and all fit the weight-gradient kernel's tile at their tap spacing. It holds the
+  // data-gradient weights and the zero bias of their convolutions.
+  bool trainable = !g ? !m->multires : !g->batch_norm;
+  for (const tfl_layer& L : m->layers) {
+    if (!g) break;
+    tfl::TrainLayer tl{L.cin, L.cout, L.cin_ref, L.cout_ref, L.k, L.skip_in ? 1 : 0};
+    tl.dil = L.dil;
+    trainable = trainable && L.pool == 1 && L.up == 1 && tfl::conv_wgrad_fits(tfl::wg_plan(is3d, tl, 1, 8, 8, 8));
+    if (L.join_c > 0 && L.cin > 64) trainable = false;      // (no convolution kernel writes its data gradient's planes)
+  }
+  if (trainable) {
     const std::vector<float> zeros(64, 0.0f);
     bool ok = upload(m->zero_bias, zeros.data(), zeros.size() * sizeof(float));
-    m->layers[0].nx = in_c - 1;     // (the occupancy channel sits last and gets no gradient)
-    m->layers[0].gxc = tfl::ig_width(in_c - 1);
+    for (tfl_layer& L : m->layers) {
+      // the stage behind a concat join reads banks x channels planes, which need not be a width the convolution kernels write
+      // (3 x 8): its data gradient is padded like the first layer's, the planes behind the real ones zero
+      if (L.join_c > 0) { L.nx = L.cin; L.gxc = tfl::train_width(L.cin); }
+      if (L.stage != 1) continue;      // (a split at the first stage: every bank's first module reads the net input)
+      L.nx = in_c - 1;                 // (the occupancy channel sits last and gets no gradient)
+      L.gxc = tfl::ig_width(in_c - 1);
+    }
     for (int i = 0; i < n && ok; i++) ok = upload_layer(m->layers[i], is3d, weights[i], biases[i], true);
     if (!ok) return cleanup("uploading weights failed");
   }
@@ -509,7 +526,11 @@ float* graph_layer(hipStream_t st, const tfl_model* m, const tfl_layer& L, int B
 
 // The conv stack of a graph model (lib/model.lua:262-362): trunk stages in the act[] ping-pong, the banks in their own
 // buffers, one k_bank_join launch at the join (none when every bank wrote its own concat slice: dilate + concat).
-int graph_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a) {
+// gt (tfl_model_forward_train): the same launches with the tape as their destinations -- every module's output in its own entry
+// (so no bank writes its slice of the join itself: k_bank_join copies or adds every bank, and for 'add' bank 1 is copied into the
+// join first), the pyramid levels and the join in theirs. Copies are exact: the bits are those of the inference form.
+struct GraphTape { std::vector<float*> out; float* pyr[tfl::kMaxJoinBanks]; float* join; };
+int graph_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a, const GraphTape* gt = nullptr) {
   net_input(m, w, a, 0, -1);
   hipStream_t st = a.st;
   const int B = a.B;
@@ -522,7 +543,7 @@ int graph_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a
   for (int l = 0; l < nl;) {
     const tfl_layer& L0 = m->layers[l];
     if (m->banks > 1 && L0.stage == m->split) {
-      float* join = in == w.act[0] ? w.act[1] : w.act[0];     // (`in` is read by every bank: the join goes elsewhere)
+      float* join = gt ? gt->join : in == w.act[0] ? w.act[1] : w.act[0];     // (`in` is read by every bank: the join goes elsewhere)
       const int N = m->banks, Cp = m->layers[l + (m->join - m->split - 1) * N].cout, och = concat ? Cp * N : Cp;
       // mres: the average-pooling pyramid, one launch per level (model.lua:266-276)
       const float* bin[tfl::kMaxJoinBanks];
@@ -531,8 +552,9 @@ int graph_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a
       for (int i = 1; i < N; i++) {
         bin[i] = in; bZ[i] = bZ[i - 1]; bY[i] = bY[i - 1]; bX[i] = bX[i - 1];
         if (!mres) continue;
-        tfl::avg_pool2(st, m->is3d, B * m->split_c, bZ[i - 1], bY[i - 1], bX[i - 1], bin[i - 1], w.pyr[i]);
-        bin[i] = w.pyr[i];
+        float* level = gt ? gt->pyr[i] : w.pyr[i];
+        tfl::avg_pool2(st, m->is3d, B * m->split_c, bZ[i - 1], bY[i - 1], bX[i - 1], bin[i - 1], level);
+        bin[i] = level;
         if (m->is3d) bZ[i] /= 2;
         bY[i] /= 2; bX[i] /= 2;
       }
@@ -542,16 +564,20 @@ int graph_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a
       for (int i = 0; i < N; i++) {
         const float* x = bin[i];
         int z = bZ[i], y = bY[i], xx = bX[i];
-        const bool direct = i == 0 || (concat && !mres);            // this bank writes its slice of the join itself
+        const bool direct = !gt && (i == 0 || (concat && !mres));            // this bank writes its slice of the join itself
         for (int s = m->split; s < m->join; s++) {
-          const tfl_layer& L = m->layers[l + (s - m->split) * N + i];
+          const int li = l + (s - m->split) * N + i;
+          const tfl_layer& L = m->layers[li];
           const bool last = s + 1 == m->join;
-          x = graph_layer(st, m, L, B, z, y, xx, x, w.bank[i][0], w.bank[i][1], (last && direct) ? join : nullptr, och,
-                          concat ? i * Cp : 0, act);
+          if (gt) x = graph_layer(st, m, L, B, z, y, xx, x, w.bank[i][0], w.bank[i][1], gt->out[li], L.cout, 0, act);
+          else x = graph_layer(st, m, L, B, z, y, xx, x, w.bank[i][0], w.bank[i][1], (last && direct) ? join : nullptr, och,
+                               concat ? i * Cp : 0, act);
           if (!x) return none(L);
         }
         if (i == 0) { jZ = z; jY = y; jX = xx; }
-        if (!direct) { slot[n] = i; sh[n] = mres ? i : 0; src[n] = x; n++; }
+        if (gt && !concat && i == 0) {      // 'add' starts from bank 1
+          HIP_TRY(c, hipMemcpyAsync(join, x, sizeof(float) * (size_t)B * Cp * z * y * xx, hipMemcpyDeviceToDevice, st));
+        } else if (!direct) { slot[n] = i; sh[n] = mres ? i : 0; src[n] = x; n++; }
       }
       if (n > 0 && !tfl::bank_join(st, m->is3d, !concat, B, Cp, jZ, jY, jX, n, slot, sh, src, join, och))
         return fail(c, TFL_EINVAL, "model_finish: bad bank join");
@@ -561,7 +587,7 @@ int graph_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a
     }
     const bool last = l + 1 == nl;
     const bool joins_skip = m->opts.pressure_skip && l + 2 == nl;
-    float* dst = last ? w.pPred : (joins_skip ? (in == w.act[0] ? w.act[1] : w.act[0]) : nullptr);
+    float* dst = last ? w.pPred : gt ? gt->out[l] : (joins_skip ? (in == w.act[0] ? w.act[1] : w.act[0]) : nullptr);
     float* out = graph_layer(st, m, L0, B, Zc, Yc, Xc, in, w.act[0], w.act[1], dst, joins_skip ? L0.cout + 1 : L0.cout, 0,
                              last ? 0 : act);
     if (!out) return none(L0);
@@ -1091,11 +1117,13 @@ int tfl_model_forward(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tf
 
 // ---- the training side: new weights in place, the forward that keeps a tape, the parameter gradients ----
 namespace {
-// Linear models without pooling / upsampling only (they hold the data-gradient weights: build_layers); the rest is refused by name
+// Linear models without pooling / upsampling, and graph models whose modules neither pool nor upsample and that hold no batch
+// norm (they hold the data-gradient weights: build_layers); the rest is refused by name
 int train_gate(tfl_ctx* c, const tfl_model* m, const char* who) {
-  if (m->path == ConvPath::graph)
-    return fail(c, TFL_EUNSUPPORTED, "%s: graph models (banks, batch norm, max pooling: tfl_model_create_graph) have no training pass", who);
-  if (m->multires || !m->zero_bias)
+  if (m->path == ConvPath::graph && !m->zero_bias)
+    return fail(c, TFL_EUNSUPPORTED, "%s: graph models (tfl_model_create_graph) with batch norm, with pooling or ConvolutionUpsample stages, or "
+                                     "with a module the weight-gradient kernel's tile cannot hold have no training pass", who);
+  if (m->path != ConvPath::graph && (m->multires || !m->zero_bias))
     return fail(c, TFL_EUNSUPPORTED, "%s: models with pooling or ConvolutionUpsample layers (`tog`) have no training pass: the "
                                      "backward of pooling and of the pixel shuffle is not built", who);
   return TFL_OK;
@@ -1116,8 +1144,25 @@ int refresh_gate(tfl_ctx* c, const tfl_model* m, const char* who) {
 }
 std::vector<tfl::TrainLayer> train_layers(const tfl_model* m) {
   std::vector<tfl::TrainLayer> v;
-  for (const tfl_layer& L : m->layers) v.push_back(tfl::TrainLayer{L.cin, L.cout, L.cin_ref, L.cout_ref, L.k, L.skip_in ? 1 : 0});
+  const bool mres = m->banks > 1 && m->bank_type == TFL_BANKS_MRES;
+  for (const tfl_layer& L : m->layers) {
+    tfl::TrainLayer t{L.cin, L.cout, L.cin_ref, L.cout_ref, L.k, L.skip_in ? 1 : 0};
+    t.dil = L.dil;
+    t.sh = (mres && L.stage >= m->split && L.stage < m->join) ? L.bank : 0;
+    v.push_back(t);
+  }
   return v;
+}
+static_assert(tfl::kTrainMaxBanks == tfl::kMaxJoinBanks, "tfl_train.hpp and tfl_host.hpp disagree on the most banks");
+// the banked modules of the layer table (n = 1: none)
+tfl::TrainBanks train_banks(const tfl_model* m) {
+  tfl::TrainBanks bk;
+  bk.is3d = m->is3d;
+  if (m->path != ConvPath::graph || m->banks < 2) return bk;
+  bk.n = m->banks; bk.mres = m->bank_type == TFL_BANKS_MRES; bk.concat = m->aggregate == TFL_AGG_CONCAT;
+  bk.nst = m->join - m->split; bk.gxc = m->layers[0].gxc;
+  while (m->layers[bk.l0].stage != m->split) bk.l0++;
+  return bk;
 }
 // the `count` that goes with the model's input-scale pair (opts_stats; tfl_model_forward's own for the default normaliser)
 double scale_count(const tfl_model* m, int Z, int Y, int X) {
@@ -1137,8 +1182,9 @@ int check_tape(tfl_ctx* c, const char* who, const tfl::TapeLayout& t, const floa
 struct InputSide { const tfl_tensor *pDiv, *UDiv, *UOut, *gradPDiv, *gradUDiv; };
 tfl::IgChans input_chans(const tfl_model* m) { return tfl::ig_chans(m->is3d, m->opts.in_pDiv, m->opts.in_UDiv, m->opts.in_div); }
 tfl::IgLayout input_layout(const tfl_model* m, int B, int Z, int Y, int X) {
+  const tfl::TrainBanks bk = train_banks(m);
   return tfl::ig_layout(m->is3d, train_layers(m), input_chans(m), m->opts.pressure_skip != 0,
-                        m->opts.normalize && m->opts.norm_chan == TFL_NORM_DIV, B, Z, Y, X);
+                        m->opts.normalize && m->opts.norm_chan == TFL_NORM_DIV, B, Z, Y, X, &bk);
 }
 
 // tfl_model_backward (in = null: its launches exactly) and tfl_model_backward_input
@@ -1163,10 +1209,12 @@ int model_backward(tfl_ctx* c, tfl_model* m, const char* who, const tfl_tensor* 
   if (B > kMaxBatch) return fail(c, TFL_EINVAL, "%s: batch size above %d", who, kMaxBatch);
   const std::vector<tfl::TrainLayer> tl = train_layers(m);
   const int nl = (int)tl.size();
-  const tfl::TapeLayout t = tfl::tape_layout(tl, B, Z, Y, X);
+  TRY(graph_gate(c, m, flags, who));
+  const tfl::TrainBanks bk = train_banks(m);
+  const tfl::TapeLayout t = tfl::tape_layout(tl, B, Z, Y, X, &bk);
   TRY(check_tape(c, who, t, tape, tape_floats));
   const tfl::IgLayout ig = in ? input_layout(m, B, Z, Y, X) : tfl::IgLayout{};
-  const tfl::BwdLayout w = in ? ig.bwd : tfl::bwd_layout(m->is3d, tl, B, Z, Y, X);
+  const tfl::BwdLayout w = in ? ig.bwd : tfl::bwd_layout(m->is3d, tl, B, Z, Y, X, &bk);
   const int64_t need = in ? ig.total : w.total;
   if (!workspace || workspace_floats < need)
     return fail(c, TFL_EINVAL, "%s: workspace too small (%lld floats needed)", who, (long long)need);
@@ -1201,34 +1249,94 @@ int model_backward(tfl_ctx* c, tfl_model* m, const char* who, const tfl_tensor* 
     HIP_TRY(c, hipMemsetAsync(g, 0, sizeof(float) * (size_t)B * cells, st));
   }
   const int act = 1 + m->opts.nonlin;
-  for (int l = nl - 1; l >= 0; l--) {
+  const bool graph = m->path == ConvPath::graph;
+  const bool want_in = in && (in->gradPDiv || in->gradUDiv);
+  // One module's step on its own grid [Zl][Yl][Xl]: the weight and bias gradient (or the activation mask alone), the joined skip
+  // channel's gradient, and -- gout != null -- the data gradient g_in = conv(g_pre, W transposed and mirrored, at the module's tap
+  // spacing) into gout; the joined skip channel gets none. A first-stage module's is the net input's, gxc wide.
+  auto step = [&](int l, int Zl, int Yl, int Xl, const float* x, const float* y, int ych, float* gl, float* gout) -> int {
     const tfl_layer& L = m->layers[l];
-    const float* x = l == 0 ? tape + t.x : tape + t.out[l - 1];
-    const float* y = l + 1 < nl ? tape + t.out[l] : nullptr;
+    const bool first = L.stage == 1;
     if (params) {
       const tfl::WgPlan p = tfl::wg_plan(m->is3d, tl[l], B, Z, Y, X);
       // (the masked gradient is written back wherever a data gradient follows: the first layer's only for the input gradients)
-      if (!tfl::conv_wgrad(st, m->is3d, p, B, Z, Y, X, L.cin, L.cout, L.k, x, g, y, y ? tfl::train_och(tl, l) : 0, act, (l > 0 || in) && y, partials))
+      if (!tfl::conv_wgrad(st, m->is3d, p, B, Zl, Yl, Xl, L.cin, L.cout, L.k, x, gl, y, y ? ych : 0, act, (!first || in) && y, partials))
         return fail(c, TFL_EUNSUPPORTED, "%s: no weight-gradient kernel for layer %d (%d output channels)", who, l, L.cout);
       tfl::conv_wgrad_finish(st, p, L.cin, L.cout, L.cin_ref, L.cout_ref, L.skip_in ? 1 : 0, partials, gradWeights[l], gradBiases[l],
-                             accumulate != 0);
+                             accumulate != 0, L.join_c, L.join_p);
     } else if (y) {
-      tfl::act_mask(st, B, L.cout, tfl::train_och(tl, l), cells, g, y, act);
+      tfl::act_mask(st, B, L.cout, ych, (long long)Zl * Yl * Xl, gl, y, act);
     }
     // the joined skip channel's gradient: the gradient at pPred against the skip plane's taps, mirrored
-    if (in && L.skip_in && !tfl::conv_direct(st, m->is3d, B, Z, Y, X, L.cout, 1, L.k, 0, g, L.ws, m->zero_bias, workspace + ig.gskip))
+    if (in && L.skip_in && !tfl::conv_direct(st, m->is3d, B, Z, Y, X, L.cout, 1, L.k, 0, gl, L.ws, m->zero_bias, workspace + ig.gskip))
       return fail(c, TFL_EUNSUPPORTED, "%s: no kernel for the skip channel's gradient", who);
-    if (l == 0) break;
-    // g_in = conv(g_pre, W transposed and mirrored); the joined skip channel gets none
-    if (!tfl::conv_direct(st, m->is3d, B, Z, Y, X, L.cout, L.cin - (L.skip_in ? 1 : 0), L.k, 0, g, L.wt, m->zero_bias, g2))
-      return fail(c, TFL_EUNSUPPORTED, "%s: no kernel for %d channels", who, L.cin - (L.skip_in ? 1 : 0));
-    std::swap(g, g2);
+    if (!gout) return TFL_OK;
+    const int gin_c = L.nx > 0 ? L.gxc : L.cin - (L.skip_in ? 1 : 0);      // (nx: the first stage, and the stage behind a concat join)
+    const bool ok = graph ? tfl::conv_direct_graph(st, m->is3d, B, Zl, Yl, Xl, L.cout, gin_c, L.k, 0, gl, L.wt, m->zero_bias, gout, 1, 0, 0, 0,
+                                                   L.dil, nullptr, nullptr)
+                          : tfl::conv_direct(st, m->is3d, B, Zl, Yl, Xl, L.cout, gin_c, L.k, 0, gl, L.wt, m->zero_bias, gout);
+    if (!ok) return fail(c, TFL_EUNSUPPORTED, "%s: no kernel for %d channels", who, gin_c);
+    return TFL_OK;
+  };
+  for (int l = nl - 1; l >= 0;) {
+    if (bk.banked(l)) {
+      // The banks, g = the gradient at the join's output: the join's backward hands every bank its gradient at its
+      // own resolution, each bank walks its modules last stage to first, and the split's backward adds the banks' data gradients
+      // -- mres: through the pyramid pool's transpose, coarsest level first -- into the trunk's next buffer (or, where the split is
+      // the first stage, into the net input's gradient).
+      const int N = bk.n, S = bk.nst, Cp = m->layers[bk.mod(S - 1, 0)].cout;
+      int shs[tfl::kMaxJoinBanks], bZ[tfl::kMaxJoinBanks], bY[tfl::kMaxJoinBanks], bX[tfl::kMaxJoinBanks];
+      float* head[tfl::kMaxJoinBanks];
+      for (int i = 0; i < N; i++) {
+        shs[i] = tl[bk.mod(0, i)].sh; head[i] = workspace + w.gb[i][0];
+        bZ[i] = m->is3d ? Z >> shs[i] : Z; bY[i] = Y >> shs[i]; bX[i] = X >> shs[i];
+      }
+      // (g = the data gradient of the stage behind the join: behind a concat join its planes are padded to a kernel width)
+      const int gch = bk.concat ? m->layers[bk.end()].gxc : Cp;
+      if (!tfl::join_bwd(st, m->is3d, bk.concat, B, Cp, gch, Z, Y, X, N, shs, head, g))
+        return fail(c, TFL_EINVAL, "%s: bad bank join", who);
+      const float* xin = bk.l0 == 0 ? tape + t.x : tape + t.out[bk.l0 - 1];
+      const bool need_split = bk.l0 > 0 || want_in;
+      const float* tail[tfl::kMaxJoinBanks];
+      for (int i = 0; i < N; i++) {
+        float* ga = workspace + w.gb[i][0];
+        float* gb = workspace + w.gb[i][1];
+        for (int s = S - 1; s >= 0; s--) {
+          const int li = bk.mod(s, i);
+          const float* x = s > 0 ? tape + t.out[bk.mod(s - 1, i)] : (bk.mres && i > 0) ? tape + t.pyr[i] : xin;
+          float* gout = (s > 0 || need_split) ? gb : nullptr;
+          TRY(step(li, bZ[i], bY[i], bX[i], x, tape + t.out[li], m->layers[li].cout, ga, gout));
+          if (gout) std::swap(ga, gb);
+        }
+        tail[i] = ga;
+      }
+      if (need_split) {
+        const int planes = bk.l0 == 0 ? ig.gxc : m->layers[bk.l0].cin;
+        float* dest = bk.l0 == 0 ? workspace + ig.gx : g2;
+        if (bk.mres) {
+          const float* coarse = tail[N - 1];
+          for (int i = N - 2; i >= 0; i--) {
+            float* dst = i == 0 ? dest : const_cast<float*>(tail[i]);
+            tfl::pyr_pool_bwd(st, m->is3d, B * planes, bZ[i], bY[i], bX[i], tail[i], coarse, dst);
+            coarse = dst;
+          }
+        } else if (!tfl::bank_sum(st, (long long)B * planes * cells, N, tail, dest)) {
+          return fail(c, TFL_EINVAL, "%s: bad bank split", who);
+        }
+      }
+      std::swap(g, g2);
+      l = bk.l0 - 1;
+      continue;
+    }
+    const float* x = l == 0 ? tape + t.x : (bk.any() && l == bk.end()) ? tape + t.join : tape + t.out[l - 1];
+    const float* y = l + 1 < nl ? tape + t.out[l] : nullptr;
+    float* gout = l > 0 ? g2 : want_in ? workspace + ig.gx : nullptr;
+    TRY(step(l, Z, Y, X, x, y, tfl::train_och(tl, l), g, gout));
+    if (l > 0) std::swap(g, g2);
+    l--;
   }
-  if (!in || (!in->gradPDiv && !in->gradUDiv)) return check_launch(c, who);
-  // the first layer's data gradient, then the scale's gradient and the head (input_grad.hip)
-  const tfl_layer& L0 = m->layers[0];
-  if (!tfl::conv_direct(st, m->is3d, B, Z, Y, X, L0.cout, ig.gxc, L0.k, 0, g, L0.wt, m->zero_bias, workspace + ig.gx))
-    return fail(c, TFL_EUNSUPPORTED, "%s: no kernel for %d channels", who, ig.gxc);
+  if (!want_in) return check_launch(c, who);
+  // behind the first layer's data gradient: the scale's gradient and the head (input_grad.hip)
   const tfl::IgChans ch = input_chans(m);
   const tfl_model_opts& o = m->opts;
   tfl::IgArgs a{};
@@ -1307,8 +1415,9 @@ int tfl_model_set_weights_device(tfl_ctx* c, tfl_model* m, const float* const* d
 }
 
 int64_t tfl_model_tape_floats(const tfl_model* m, int B, int Z, int Y, int X) {
-  if (!m || m->path == ConvPath::graph || !m->zero_bias || B < 1 || Z < 1 || Y < 1 || X < 1) return -1;
-  return tfl::tape_layout(train_layers(m), B, Z, Y, X).total;
+  if (!m || !m->zero_bias || B < 1 || Z < 1 || Y < 1 || X < 1) return -1;
+  const tfl::TrainBanks bk = train_banks(m);
+  return tfl::tape_layout(train_layers(m), B, Z, Y, X, &bk).total;
 }
 
 int tfl_model_forward_train(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
@@ -1326,7 +1435,9 @@ int tfl_model_forward_train(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, co
   const tfl::Scope sc = tfl::scope_of(c);
   if (sc.stages || sc.windowed()) return fail(c, TFL_EINVAL, "%s: clear the z-window / stage mask first", who);
   const int B = flags->B, Z = flags->Z, Y = flags->Y, X = flags->X;
-  const tfl::TapeLayout t = tfl::tape_layout(train_layers(m), B, Z, Y, X);
+  TRY(graph_gate(c, m, flags, who));
+  const tfl::TrainBanks bk = train_banks(m);
+  const tfl::TapeLayout t = tfl::tape_layout(train_layers(m), B, Z, Y, X, &bk);
   TRY(check_tape(c, who, t, tape, tape_floats));
   ModelWs w;
   TRY(model_ws(c, m, flags, workspace, workspace_floats, &w));
@@ -1339,7 +1450,15 @@ int tfl_model_forward_train(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, co
   w.x3 = tape + t.x; w.pPred = tape + t.pPred;
   std::vector<float*> outs;
   for (size_t l = 0; l < m->layers.size(); l++) outs.push_back(l + 1 < m->layers.size() ? tape + t.out[l] : w.pPred);
-  TRY(generic_forward(c, m, w, a, outs.data()));
+  if (m->path == ConvPath::graph) {
+    GraphTape gt{};
+    gt.out = outs;
+    for (int i = 1; i < bk.n && bk.mres; i++) gt.pyr[i] = tape + t.pyr[i];
+    gt.join = bk.any() ? tape + t.join : nullptr;
+    TRY(graph_forward(c, m, w, a, &gt));
+  } else {
+    TRY(generic_forward(c, m, w, a, outs.data()));
+  }
   tfl::model_project(a.st, sc, m->is3d, B, Z, Y, X, w.pPred, flags->data, a.st_in, a.count, UOut->data, UOut->data, pOut->data, nullptr, nullptr, 0,
                      0.0f, 0.0f, nullptr, nullptr, nullptr, nullptr, nullptr, wall_code_of(c, m, flags), nullptr, ask.fold);
   HIP_TRY(c, hipMemcpyAsync(tape + t.stats, m->d_stats, sizeof(double) * 2 * B, hipMemcpyDeviceToDevice, c->stream));
@@ -1347,8 +1466,9 @@ int tfl_model_forward_train(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, co
 }
 
 int64_t tfl_model_backward_workspace_floats(const tfl_model* m, int B, int Z, int Y, int X) {
-  if (!m || m->path == ConvPath::graph || !m->zero_bias || B < 1 || Z < 1 || Y < 1 || X < 1) return -1;
-  return tfl::bwd_layout(m->is3d, train_layers(m), B, Z, Y, X).total;
+  if (!m || !m->zero_bias || B < 1 || Z < 1 || Y < 1 || X < 1) return -1;
+  const tfl::TrainBanks bk = train_banks(m);
+  return tfl::bwd_layout(m->is3d, train_layers(m), B, Z, Y, X, &bk).total;
 }
 
 int tfl_model_backward(tfl_ctx* c, tfl_model* m, const tfl_tensor* flags, const tfl_tensor* gradP, const tfl_tensor* gradU,
@@ -1359,7 +1479,7 @@ int tfl_model_backward(tfl_ctx* c, tfl_model* m, const tfl_tensor* flags, const 
 }
 
 int64_t tfl_model_backward_input_workspace_floats(const tfl_model* m, int B, int Z, int Y, int X) {
-  if (!m || m->path == ConvPath::graph || !m->zero_bias || B < 1 || Z < 1 || Y < 1 || X < 1) return -1;
+  if (!m || !m->zero_bias || B < 1 || Z < 1 || Y < 1 || X < 1) return -1;
   return input_layout(m, B, Z, Y, X).total;
 }
 

@@ -395,19 +395,31 @@ void upsample_nearest_bwd(hipStream_t st, int ratio, long long rows, int Zi, int
 // (tfl_train.hpp wg_plan). conv_wgrad leaves fp64 partials of gradWeight and gradBias per block; g is masked by act'(y) where it
 // is read (y = null: no activation) and, with wb, rewritten masked for the data gradient that follows. conv_wgrad_finish adds
 // the partials in a fixed order and writes (accumulate = 0) or adds onto (1) the cudnn-layout gw [cout_ref][cin_ref][taps] and
-// gb [cout_ref]. false = the layer does not fit the kernel (nothing launched).
+// gb [cout_ref] (join_c, join_p: the plane map of the stage behind a concat join, tfl_train.hpp wg_cudnn_index). false = the layer
+// does not fit the kernel (nothing launched).
 struct WgPlan;
 bool conv_wgrad_fits(const WgPlan& p);
 bool conv_wgrad(hipStream_t st, bool is3d, const WgPlan& p, int B, int Z, int Y, int X, int cin, int cout, int k, const float* x,
                 float* g, const float* y, int ych, int act, bool wb, double* partials);
 void conv_wgrad_finish(hipStream_t st, const WgPlan& p, int cin, int cout, int cin_ref, int cout_ref, int skip_in, const double* partials,
-                       float* gw, float* gb, int accumulate);
+                       float* gw, float* gb, int accumulate, int join_c = 0, int join_p = 0);
 // dst[b][t] = scale_b * src[b][t] (+ add[b][t]) over `per` floats per batch item; scale_b from the (sum, sum of squares) pairs
 void scale_add(hipStream_t st, int B, long long per, const double* stats, double count, const float* src, const float* add, float* dst);
 
 // g[b][c][t] *= act'(y[b][c][t]) over the `cout` planes of g (y has `ych` planes per item): conv_wgrad's write-back alone, for a
 // backward pass that asks for no parameter gradients (tfl_model_backward_input with NULL gradient tables)
 void act_mask(hipStream_t st, int B, int cout, int ych, long long cells, float* g, const float* y, int act);
+
+// conv_bwd.hip: the fixed linear maps of a banked model, backwards; fixed-order fp32 sums, no atomics.
+// join_bwd: from g [B][och] at the join's output [Z][Y][X], bank i's gradient dst[i] [B][C] at (grid >> sh[i]) -- its channel slice
+// (concat) or all channels (add); sh = 0 a copy, else the sum over the block of cells the nearest up-sample replicated.
+bool join_bwd(hipStream_t st, bool is3d, bool concat, int B, int C, int och, int Z, int Y, int X, int n, const int* sh, float* const* dst,
+              const float* g);
+// dst = a + P^T c over `rows` planes, [Z][Y][X] fine (all even in the pooled axes), c at half of it; P = the 2x average pooling.
+// dst may be a; a, c, dst 8-byte aligned.
+void pyr_pool_bwd(hipStream_t st, bool is3d, int rows, int Z, int Y, int X, const float* a, const float* c, float* dst);
+// dst = ((src[0] + src[1]) + src[2]) ... over count floats
+bool bank_sum(hipStream_t st, long long count, int n, const float* const* src, float* dst);
 
 // input_grad.hip: what tfl_model_backward_input adds behind the first layer's data gradient. Null pointers: gradP /
 // gradU / h (no gradient given), gskip (no joined skip channel), gradPDiv / gradUDiv (not asked for), dsrc (the scale is not

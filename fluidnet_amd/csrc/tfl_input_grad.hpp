@@ -51,9 +51,9 @@ TFL_HD inline long long ig_partial_slot(int b, int nblocks, int blk, int t) { re
 //   partials [B][blocks][5] doubles, gs [B] doubles (8-byte aligned)
 struct IgLayout { BwdLayout bwd; int64_t gx, gskip, ubc, div, partials, gs, total; int gxc, blocks; bool recompute_div; };
 inline IgLayout ig_layout(bool is3d, const std::vector<TrainLayer>& L, const IgChans& ch, bool skip, bool norm_from_div, int B, int Z,
-                          int Y, int X) {
+                          int Y, int X, const TrainBanks* bk = nullptr) {
   IgLayout w;
-  w.bwd = bwd_layout(is3d, L, B, Z, Y, X);
+  w.bwd = bwd_layout(is3d, L, B, Z, Y, X, bk);
   const int64_t cells = (int64_t)Z * Y * X, n = (int64_t)B * cells;
   w.gxc = ig_width(ch.nx);
   w.blocks = ig_sum_blocks(cells);

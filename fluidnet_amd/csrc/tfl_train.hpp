@@ -61,8 +61,31 @@ inline void relay_skip(int taps, int cin_p, int cout_p, const float* relaid, std
 
 // One layer as the training side sees it: padded and reference channel counts, kernel size, whether its last input plane is
 // the joined pressure-skip channel.
-struct TrainLayer { int cin, cout, cin_ref, cout_ref, k, skip_in; };
+// A module of a banked model also has its tap spacing `dil` (dilate banks: 2^bank) and the resolution it runs at,
+// grid >> sh per pooled axis (mres banks: sh = bank).
+struct TrainLayer { int cin, cout, cin_ref, cout_ref, k, skip_in; int dil = 1, sh = 0; };
 
+// The banks of a graph model as the training side sees them: modules [l0, l0 + nst * n) of the layer table are banked, module
+// l0 + s * n + i = stage s of bank i. n = 1: a linear model. gxc: the width of the first layer's data gradient (ig_width), which
+// the banks' gradient buffers must hold where the split is the first stage.
+constexpr int kTrainMaxBanks = 8;
+struct TrainBanks {
+  int n = 1;
+  bool is3d = false, mres = false, concat = false;
+  int l0 = 0, nst = 0, gxc = 0;
+  bool any() const { return n > 1; }
+  int mod(int s, int i) const { return l0 + s * n + i; }
+  int end() const { return l0 + nst * n; }
+  bool banked(int l) const { return n > 1 && l >= l0 && l < end(); }
+};
+// cells of one plane at resolution grid >> sh (2-D: z is not pooled); the grid is divisible by 2^sh (graph_gate)
+inline int64_t train_cells(bool is3d, int sh, int Z, int Y, int X) { return (int64_t)(is3d ? Z >> sh : Z) * (Y >> sh) * (X >> sh); }
+
+// the widths the shape-generic convolution kernels write (1, 2, 4 ... 64): c rounded up to one (above 64: none, c itself)
+inline int train_width(int c) {
+  for (int w = 1; w <= 64; w *= 2) if (c <= w) return w;
+  return c;
+}
 inline int train_taps(bool is3d, int k) { return is3d ? k * k * k : k * k; }
 // channel planes of the saved output of layer l (the layer in front of the last also holds the skip channel)
 inline int train_och(const std::vector<TrainLayer>& L, size_t l) { return L[l].cout + ((l + 2 == L.size() && L.back().skip_in) ? 1 : 0); }
@@ -72,15 +95,36 @@ inline int train_och(const std::vector<TrainLayer>& L, size_t l) { return L[l].c
 //   x          the net input, [B][in_c] planes
 //   out[l]     the post-activation output of every layer but the last, [B][och_l] planes (och: train_och)
 //   pPred      the last layer's output, [B][1]
-struct TapeLayout { int64_t stats, x, pPred, total; std::vector<int64_t> out; };
-inline TapeLayout tape_layout(const std::vector<TrainLayer>& L, int B, int Z, int Y, int X) {
+// A banked model (bk): out[l] of a banked module has its cout planes at the module's own resolution (planes[l], sh[l]), and
+// behind the layers' outputs sit
+//   pyr[i]     mres, bank i >= 1: level i of the average-pooling pyramid, [B][cin of the split stage] planes at grid >> i -- bank
+//              i's first input, the x of its first weight gradient. Kept rather than pooled again in the backward: at 1/2^dim of
+//              the level above it costs an eighth (a quarter) of one activation, against one more launch per level and pass.
+//   join       the join's output, [B][join_c] planes at the grid's resolution: the x of the first stage behind the join
+struct TapeLayout {
+  int64_t stats, x, pPred, total;
+  std::vector<int64_t> out;
+  std::vector<int> planes, sh;       // of out[l]
+  int64_t pyr[kTrainMaxBanks] = {0, 0, 0, 0, 0, 0, 0, 0}, join = 0;
+  int pyr_c = 0, join_c = 0;
+};
+inline TapeLayout tape_layout(const std::vector<TrainLayer>& L, int B, int Z, int Y, int X, const TrainBanks* bk = nullptr) {
   TapeLayout t;
-  const int64_t n = (int64_t)B * Z * Y * X;
+  const bool is3d = bk && bk->is3d;
   int64_t off = 0;
   t.stats = off; off += 4 * (int64_t)B;
-  t.x = off; off += n * L[0].cin;
-  for (size_t l = 0; l + 1 < L.size(); l++) { t.out.push_back(off); off += n * train_och(L, l); }
-  t.pPred = off; off += n;
+  t.x = off; off += (int64_t)B * Z * Y * X * L[0].cin;
+  for (size_t l = 0; l + 1 < L.size(); l++) {
+    t.out.push_back(off); t.planes.push_back(train_och(L, l)); t.sh.push_back(L[l].sh);
+    off += (int64_t)B * train_cells(is3d, L[l].sh, Z, Y, X) * train_och(L, l);
+  }
+  if (bk && bk->any()) {
+    t.pyr_c = L[bk->l0].cin;
+    for (int i = 1; i < bk->n && bk->mres; i++) { t.pyr[i] = off; off += (int64_t)B * train_cells(is3d, i, Z, Y, X) * t.pyr_c; }
+    t.join_c = L[bk->mod(bk->nst - 1, 0)].cout * (bk->concat ? bk->n : 1);
+    t.join = off; off += (int64_t)B * Z * Y * X * t.join_c;
+  }
+  t.pPred = off; off += (int64_t)B * Z * Y * X;
   t.total = off;
   return t;
 }
@@ -103,10 +147,11 @@ TFL_HD inline WgChunk wg_chunk(int ch, int tt, int cin, int taps, int ci0, int t
   return c;
 }
 // The LDS tile of x: [channel of the chunk][HZ][HY][HX]
+// (d: the tap spacing of a dilated bank's module, 1 | 2 | 4 ...: the halo radius is d (k / 2) and tap offsets are scaled by d)
 struct WgHalo { int r, rz, HX, HY, HZ, floats; };
-TFL_HD inline WgHalo wg_halo(bool is3d, int k) {
+TFL_HD inline WgHalo wg_halo(bool is3d, int k, int d = 1) {
   WgHalo h;
-  h.r = k / 2; h.rz = is3d ? h.r : 0;
+  h.r = d * (k / 2); h.rz = is3d ? h.r : 0;
   h.HX = kWgTX + 2 * h.r; h.HY = kWgTY + 2 * h.r; h.HZ = 2 * h.rz + 1;
   h.floats = h.HX * h.HY * h.HZ;
   return h;
@@ -114,7 +159,8 @@ TFL_HD inline WgHalo wg_halo(bool is3d, int k) {
 // What thread `tid` of the block does in a chunk: its voxel slice s (active while s < S), its row rr of the chunk -- the bias
 // row or (channel cl of the chunk, tap) --, where its tap starts in the x tile (xoff) and its row of the whole layer (M = the bias)
 struct WgThread { int s, rr, cl, tap, xoff, row; bool active, is_bias; };
-TFL_HD inline WgThread wg_thread(int tid, const WgChunk& c, const WgHalo& h, int S, int ci0, int t0, int k, int taps, bool is3d, int M) {
+TFL_HD inline WgThread wg_thread(int tid, const WgChunk& c, const WgHalo& h, int S, int ci0, int t0, int k, int taps, bool is3d, int M,
+                                   int d = 1) {
   WgThread t;
   t.s = tid / c.R; t.rr = tid - t.s * c.R;
   t.active = t.s < S;
@@ -122,7 +168,7 @@ TFL_HD inline WgThread wg_thread(int tid, const WgChunk& c, const WgHalo& h, int
   t.cl = t.is_bias ? 0 : t.rr / c.ntt;
   t.tap = t.is_bias ? 0 : t0 + (t.rr - t.cl * c.ntt);
   const int dx = t.tap % k, dy = (t.tap / k) % k, dz = is3d ? t.tap / (k * k) : 0;
-  t.xoff = t.cl * h.floats + (dz * h.HY + dy) * h.HX + dx;
+  t.xoff = t.cl * h.floats + (dz * d * h.HY + dy * d) * h.HX + dx * d;
   t.row = t.is_bias ? M : (ci0 + t.cl) * taps + t.tap;
   return t;
 }
@@ -131,12 +177,16 @@ TFL_HD inline int wg_g_slot(int v, int cb, int c) { return v * cb + c; }
 TFL_HD inline int wg_red_slot(const WgThread& t, const WgChunk& c, int s, int cb, int ch) { return (s * c.R + t.rr) * cb + ch; }   // fp64 words
 TFL_HD inline long long wg_partial_slot(int blk, int M, int row, int cout, int co) { return ((long long)blk * (M + 1) + row) * cout + co; }
 
-struct WgPlan { int taps, cb, ch, tt, S, nblocks, halo_floats, lds_floats; int64_t tiles, partial_doubles; };
+// (Z, Y, X: the grid; the plan is that of the module's own resolution, grid >> L.sh)
+struct WgPlan { int taps, cb, ch, tt, S, nblocks, halo_floats, lds_floats; int64_t tiles, partial_doubles; int dil; };
 inline WgPlan wg_plan(bool is3d, const TrainLayer& L, int B, int Z, int Y, int X) {
   WgPlan p;
+  if (is3d) Z >>= L.sh;
+  Y >>= L.sh; X >>= L.sh;
+  p.dil = L.dil;
   p.taps = train_taps(is3d, L.k);
   p.cb = L.cout < 16 ? L.cout : 16;
-  p.halo_floats = wg_halo(is3d, L.k).floats;
+  p.halo_floats = wg_halo(is3d, L.k, L.dil).floats;
   p.tt = p.taps < 255 ? p.taps : 255;
   int ch = 255 / p.tt, fit = kWgLdsFloats / p.halo_floats;
   if (ch > fit) ch = fit;
@@ -161,12 +211,19 @@ inline WgPlan wg_plan(bool is3d, const TrainLayer& L, int B, int Z, int Y, int X
 
 // (row, co) of a layer's weight gradient -> its place in the cudnn layout [cout_ref][cin_ref][taps], or -1 for a padded plane.
 // row = ci * taps + tap over the padded input planes; a joined skip channel sits on the last padded plane and is the last
-// reference channel.
-TFL_HD inline long long wg_cudnn_index(int row, int co, int taps, int cin, int cin_ref, int cout_ref, int skip_in) {
+// reference channel. join_c > 0 (the stage behind a concat join): the banks' slices lie join_p planes apart and hold join_c real
+// channels each, plane ci = reference channel (ci / join_p) * join_c + ci % join_p.
+TFL_HD inline long long wg_cudnn_index(int row, int co, int taps, int cin, int cin_ref, int cout_ref, int skip_in, int join_c = 0,
+                                       int join_p = 0) {
   const int ci = row / taps, tap = row - ci * taps;
   if (co >= cout_ref) return -1;
   int cr;
   if (skip_in && ci == cin - 1) cr = cin_ref - 1;
+  else if (join_c > 0) {
+    const int bank = ci / join_p, c = ci - bank * join_p;
+    if (c >= join_c || bank * join_c + c >= cin_ref - (skip_in ? 1 : 0)) return -1;
+    cr = bank * join_c + c;
+  }
   else if (ci < cin_ref - (skip_in ? 1 : 0)) cr = ci;
   else return -1;
   return ((long long)co * cin_ref + cr) * taps + tap;
@@ -174,9 +231,11 @@ TFL_HD inline long long wg_cudnn_index(int row, int co, int taps, int cin, int c
 
 // The workspace of tfl_model_backward, in floats from its 8-byte aligned start: the fp64 partials of the widest layer, two
 // gradient buffers of `gc` planes (g_out of a layer and its g_in), and the velocity-gradient scratch [B][C].
-struct BwdLayout { int64_t partials, g0, g1, gu, total; int gc; };
-inline BwdLayout bwd_layout(bool is3d, const std::vector<TrainLayer>& L, int B, int Z, int Y, int X) {
-  BwdLayout w;
+// A banked model (bk) has behind them two gradient buffers per bank, gb[i][0 | 1], of `gbc` planes at the bank's resolution: the
+// join's backward fills one, the bank's layers walk the pair, and the split's backward reads the banks' last.
+struct BwdLayout { int64_t partials, g0, g1, gu, total; int gc; int64_t gb[kTrainMaxBanks][2]; int gbc; };
+inline BwdLayout bwd_layout(bool is3d, const std::vector<TrainLayer>& L, int B, int Z, int Y, int X, const TrainBanks* bk = nullptr) {
+  BwdLayout w{};
   const int64_t n = (int64_t)B * Z * Y * X;
   int64_t pd = 0;
   int gc = 1;
@@ -184,6 +243,9 @@ inline BwdLayout bwd_layout(bool is3d, const std::vector<TrainLayer>& L, int B, 
     const WgPlan p = wg_plan(is3d, l, B, Z, Y, X);
     if (p.partial_doubles > pd) pd = p.partial_doubles;
     if (l.cout > gc) gc = l.cout;
+    // (the stage behind a concat join reads all the banks' planes: its data gradient is that wide)
+    // (padded to a width the data-gradient convolution has: 3 x 8 planes come as 32)
+    if (&l != &L[0] && train_width(l.cin - l.skip_in) > gc) gc = train_width(l.cin - l.skip_in);
   }
   w.gc = gc;
   w.partials = 0;
@@ -191,7 +253,35 @@ inline BwdLayout bwd_layout(bool is3d, const std::vector<TrainLayer>& L, int B, 
   w.g1 = w.g0 + n * gc;
   w.gu = w.g1 + n * gc;
   w.total = w.gu + n * (is3d ? 3 : 2);
+  if (bk && bk->any()) {
+    int gbc = bk->l0 == 0 ? (bk->gxc > L[0].cin ? bk->gxc : L[0].cin) : L[bk->l0].cin;
+    for (int l = bk->l0; l < bk->end(); l++) if (L[l].cout > gbc) gbc = L[l].cout;
+    w.gbc = gbc;
+    for (int i = 0; i < bk->n; i++) {
+      int64_t nb = (int64_t)B * train_cells(is3d, L[bk->mod(0, i)].sh, Z, Y, X) * gbc;
+      nb += nb & 1;      // (every buffer stays 8-byte aligned: k_pyr_pool_bwd moves pairs)
+      w.gb[i][0] = w.total; w.gb[i][1] = w.total + nb;
+      w.total += 2 * nb;
+    }
+  }
   return w;
+}
+
+// ---- the index maps of the three bank kernels of conv_bwd.hip (k_join_bwd, k_pyr_pool_bwd, k_bank_sum) -------------------------
+// The join's backward: the gradient of bank i (C planes at grid >> sh) from g at the join's output (och planes at the grid's
+// resolution). concat: the bank's channel slice; add: every bank reads all C channels.
+TFL_HD inline int join_bwd_plane(bool concat, int i, int C, int c) { return concat ? i * C + c : c; }
+// The nearest up-sample by 2^sh replicated coarse cell (z, y, x) over a block of children; child q of its (1 << sh)^dim, in the fixed
+// order the sum takes them (x fastest), as an offset into the fine plane [Z][Y][X].
+TFL_HD inline long long join_bwd_child(bool is3d, int sh, int z, int y, int x, int q, int Y, int X) {
+  const int w = 1 << sh;
+  const int dx = q % w, dy = (q / w) % w, dz = is3d ? q / (w * w) : 0;
+  return ((long long)((is3d ? z * w : z) + dz) * Y + (y * w + dy)) * X + (x * w + dx);
+}
+TFL_HD inline int join_bwd_children(bool is3d, int sh) { return is3d ? 1 << (3 * sh) : 1 << (2 * sh); }
+// The pyramid pool's backward: fine cell (z, y, x) of a [Z][Y][X] plane reads coarse cell (z/2, y/2, x/2) of [Z/2][Y/2][X/2]
+TFL_HD inline long long pyr_bwd_parent(bool is3d, int z, int y, int x, int Y, int X) {
+  return ((long long)(is3d ? z >> 1 : z) * (Y >> 1) + (y >> 1)) * (X >> 1) + (x >> 1);
 }
 
 }  // namespace tfl

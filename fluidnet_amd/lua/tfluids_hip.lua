@@ -607,7 +607,7 @@ function Model:cuda() return self end
 function Model:rangeErrors() return tonumber(lib.tfl_model_range_errors(ctx, self.handle)) end
 function Model:rangeFlag() return tonumber(lib.tfl_model_range_flag(ctx, self.handle)) end
 
--- The training side (linear models without pooling / upsampling -- include/tfluids_hip.h): the parameter gradients and, on
+-- The training side (linear and banked models without batch norm, pooling / upsampling -- include/tfluids_hip.h): the parameter gradients and, on
 -- request, the gradients to pDiv and UDiv (model:backward's wantGradInput).
 -- model:setWeights(weights, biases): tables of FloatTensors laid out like the convolutions' weight / bias, copied into the
 -- model's own buffers (synchronous; re-record any slab graph built on the model).

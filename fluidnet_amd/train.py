@@ -58,8 +58,9 @@ class ProjectionNet(torch.nn.Module):
     they lie (tfl_model_set_weights_device: no host copy, no synchronisation), whenever a parameter's version counter has moved
     since the last push -- every torch.optim step moves it -- or by push_parameters(). The host copy `layers` follows lazily:
     when something reads it, or when a handle is created on a device that has none.
-    Accepted wherever simulate() takes a model. Linear models without pooling / upsampling layers can be trained; the others
-    run in eval mode only (training raises, naming the reason).
+    Accepted wherever simulate() takes a model. Linear models without pooling / upsampling layers can be trained, and so can
+    banked models ('mres' / 'dilate' banks, 'concat' / 'add' joins) without batch norm and without pooling / upsampling stages; the
+    others run in eval mode only (training raises, naming the reason).
     input_grad=True: pDiv and UDiv may require grad, and backward returns their gradients (tfl_model_backward_input) -- two
     passes can be chained, net(*net(pDiv, UDiv, flags), flags), or torch code put in front. flags never gets a gradient."""
 

@@ -435,8 +435,11 @@ int tfl_model_finish(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* pDiv, con
 /* ---- the training side of the projection ConvNet: the reference's closure is model:forward, crit:forward / :backward,
  * model:backward (lib/run_epoch.lua:207-235, 269-293); tfl_fluidCriterion is the middle, these are the two ends. For linear
  * models (tfl_model_create[_ex|_opts]) whose layers neither pool nor upsample -- `default`, `yang`, custom layer tables, every
- * tfl_model_opts switch. Graph models and models with pooling / ConvolutionUpsample layers (`tog`) are refused with
- * TFL_EUNSUPPORTED before anything is written. tfl_model_backward gives the parameter gradients (the reference computes a
+ * tfl_model_opts switch -- and for banked models (tfl_model_create_graph: banksNum 2 .. 8, 'mres' or 'dilate' banks, 'concat' or
+ * 'add' joins, any legal split / join stage) that hold no batch norm and whose modules neither pool nor upsample. Graph models
+ * with batch norm (it needs a training-mode forward), models with pooling / ConvolutionUpsample layers (`tog`, banked or not:
+ * the pixel-shuffle backward is not built) and a module the weight-gradient kernel's tile cannot hold at its tap spacing are
+ * refused with TFL_EUNSUPPORTED before anything is written, and the size queries answer -1 for them. tfl_model_backward gives the parameter gradients (the reference computes a
  * gradInput and run_epoch.lua discards it); tfl_model_backward_input also gives the gradients to pDiv and UDiv, for training
  * through the net (an iterated projection, a loss behind a refinement pass, differentiable code in front of it). There is no
  * gradient to flags. */
@@ -451,7 +454,9 @@ int tfl_model_set_weights(tfl_ctx* ctx, tfl_model* model, const float* const* we
 /* Floats of the tape tfl_model_forward_train fills for a [B][.][Z][Y][X] grid (-1: the model has no training pass). */
 int64_t tfl_model_tape_floats(const tfl_model* model, int B, int Z, int Y, int X);
 /* tfl_model_forward (without its fused UBC / clamp tail) that also keeps what the backward pass reads in `tape` (device,
- * 8-byte aligned): the per-item input scale, the net input, every layer's post-activation output with the joined skip channel.
+ * 8-byte aligned): the per-item input scale, the net input, every layer's post-activation output with the joined skip channel;
+ * for a banked model every module's output at its bank's resolution, the 'mres' pyramid levels and the join's output (its
+ * outputs are tfl_model_forward's of the same model, bit for bit).
  * Always evaluated on the shape-generic fp32 kernels -- the exact fmaf chain, no fp16 and hence no range gate -- whatever
  * path the model was created on: the outputs are those of the same model created under TFL_CONV_PATH=direct, bit for bit.
  * workspace: tfl_model_workspace_floats. A short tape or workspace is TFL_EINVAL with nothing written. */
@@ -466,6 +471,10 @@ int64_t tfl_model_backward_workspace_floats(const tfl_model* model, int B, int Z
  *   g = scale gradP + velocityUpdateBackward(scale setWallBcsBackward(gradU))
  * then per layer from the last to the first g_pre = g (.) act'(y), gradBias = sum g_pre, gradWeight[co][ci][tap] =
  * sum x[ci][pos + tap] g_pre[co][pos], and g = conv(g_pre, W transposed and mirrored) for the layer in front.
+ * A banked model: at the join every bank gets its channel slice ('concat') or all channels ('add') of g, an 'mres' bank the sum
+ * over the block of cells the nearest up-sample replicated; each bank runs the per-layer step on its own grid at its tap
+ * spacing; at the split the banks' gradients are added, 'mres' through the transpose of the 2x average pooling. Fixed-order
+ * sums, no atomics: the same inputs give the same bits.
  * accumulate = 0 overwrites; 1 adds the fresh gradient, rounded to fp32, onto what is there with one fp32 add per element
  * (Torch's accGradParameters). Sums over voxels run in a fixed order (fp32 fmaf inside a 32 x 8 tile, fp64 across tiles and
  * blocks, no atomics): the same inputs give the same bits on every call. No host read, no stream synchronisation; capturable.
