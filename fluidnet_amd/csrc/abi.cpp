@@ -76,7 +76,7 @@ int advectVel(tfl_ctx* c, float dt, const tfl_tensor* U, const tfl_tensor* flags
     fwd_p = fwd->data;
   }
   tfl::advect_vel(c->stream, sc, is3D != 0, m, flags->B, flags->Z, flags->Y, flags->X, dt, maccormackStrength,
-                  c->d_trace_err, U->data, flags->data, fwd_p, UDst->data, ask.fold);
+                  c->d_trace_err, U->data, flags->data, fwd_p, UDst->data, ask.fold, &ask.scan);
   return check_launch(c, "advectVel");
 }
 

@@ -415,13 +415,13 @@ void advect_scalar(hipStream_t st, const Scope& sc, bool is3d, int method, int B
 
 template <bool IS3D>
 static void launch_vel(hipStream_t st, int method, const AdvArgs& a, int B, const float* U, const float* flags,
-                       float* fwd, float* dst, int stages, Fold& f) {
+                       float* fwd, float* dst, int stages, Fold& f, Vel3ScanAsk* scan) {
   const dim3 blk(64, 4, 1), grd = cell_grid(a.d, B, blk);
   const bool pa = stages & 2, pb = stages & 4;   // as in launch_scalar
   if (method != kMacCormack && method != kMacCormackOurs && !pa) return;
   // the trace-based methods on a 3-D grid: LDS-tiled fast-path kernels (advect_vel3.hip)
   if (IS3D && (method == kEulerOurs || method == kMacCormackOurs) &&
-      advect_vel3(st, method == kMacCormackOurs, a, B, U, flags, fwd, dst, stages, f))
+      advect_vel3(st, method == kMacCormackOurs, a, B, U, flags, fwd, dst, stages, f, scan))
     return;
   switch (method) {
     case kEuler: { TFL_TIMED("k_vel_fwd", st); k_vel_fwd<IS3D, false><<<grd, blk, 0, st>>>(a, U, flags, dst); break; }
@@ -438,12 +438,12 @@ static void launch_vel(hipStream_t st, int method, const AdvArgs& a, int B, cons
 }
 
 void advect_vel(hipStream_t st, const Scope& sc, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
-                unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, Fold& f) {
+                unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, Fold& f, Vel3ScanAsk* scan) {
   if (method == kRK2Ours || method == kRK3Ours) method = kMacCormackOurs;  // tfluids.cc:799-802
   AdvArgs a; a.d = make_dom(sc, Z, Y, X); a.dt = dt; a.strength = strength; a.outside = 0; a.err = err; a.fast = sc.advect_fast;
   const int stages = sc.passes();
-  if (is3d) launch_vel<true>(st, method, a, B, U, flags, fwd, dst, stages, f);
-  else launch_vel<false>(st, method, a, B, U, flags, fwd, dst, stages, f);
+  if (is3d) launch_vel<true>(st, method, a, B, U, flags, fwd, dst, stages, f, scan);
+  else launch_vel<false>(st, method, a, B, U, flags, fwd, dst, stages, f, scan);
 }
 
 }  // namespace tfl

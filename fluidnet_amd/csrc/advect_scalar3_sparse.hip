@@ -3,16 +3,31 @@
 // +0.0 has no arithmetic left, but it still loads 32 / 36 B per cell, waits at its barrier and stores +0.0 over +0.0 -- 96-97 % of
 // the blocks of the flagship scene. Here those blocks are never started:
 //
-//   k_scal3_scan    one streaming launch over s and U (16 B/cell). Per BRICK of 64 x 4 x 4 cells, aligned to the array origin (it holds
-//                   whole tiles of every block shape the passes use: PZ = 2 or 4 planes), one byte nz: some word of s in the brick
-//                   is not the bit pattern +0 -- EVERY cell, fluid, obstacle or border; -0.0, denormals, NaN and inf set it. Per
-//                   batch item one word `fast`: set unless every velocity word u of the item satisfies fabsf(u * dt) <= 0.9f, an
-//                   ordered compare (a NaN or inf sets it). A byte store per brick and an atomic OR without a return value.
+//   the scan        per BRICK of 64 x 4 x 4 cells, aligned to the array origin (it holds whole tiles of every block shape the passes
+//                   use: PZ = 2 or 4 planes), one tag nz: some word of s in the brick is not the bit pattern +0 -- EVERY cell, fluid,
+//                   obstacle or border; -0.0, denormals, NaN and inf set it. Per batch item one tag `fast`: set unless every
+//                   velocity word u of the item satisfies fabsf(u * dt) <= 0.9f, an ordered compare (a NaN or inf sets it).
+//                   Two forms write the same tags:
+//     k_vel3_fwd_scan   PASS A OF advectVel with the scan as a by-product (the step runs it first: simulate.cpp). That pass stages
+//                   every word of the same pre-advection U in LDS anyway, and its block (64 x 4 cells x 1 or 2 planes) lies inside
+//                   one brick: per cell it tests the three own-cell velocity words from the tile and the own-cell word of s (one
+//                   more 4-byte load, asked for with the tile's loads), and after its stores a wave takes two ballots and its first
+//                   lane stores at most two tags. The 16 B/cell pass of its own is gone from every step on the lists.
+//     k_scal3_scan  one streaming launch over s and U (16 B/cell), a block per brick: where pass A did not take the request (a
+//                   gather path) and for every density channel after the first.
+//   THE TAGS        are 32-bit words, [B][1 + bricks]: per item `fast`, then one per brick. "Set" means "equals this scan's number":
+//                   the stores are plain and idempotent (every wave of a brick may store the same word), nothing is cleared between
+//                   scans and no atomic is needed. Why a stale tag never equals the current number: the words are zeroed at
+//                   allocation and a scan's number is never 0; a field's scans are numbered 1, 2, 3 ... by the host
+//                   (simulate.cpp scal3_sparse_ask / _done: the number advances whenever a scan was launched with it), so every tag
+//                   in memory is 0 or the number of an EARLIER scan, smaller than the current one. Before the 32-bit number would
+//                   wrap to 0 the host zeroes the words on the stream, ahead of the scan, and starts again from 1: the same
+//                   state as after allocation. (A tag that did compare equal by mistake would list a brick too many: time, not bits.)
 //   k_scal3_lists   one block per batch item, the brick map as one 32-bit word per (y, z) row of bricks in LDS.
 //                   L_B = the bricks within Chebyshev distance 1 of an nz brick, plus the bricks that intersect the box of the
 //                   setConstVals pair pass B folds (the first step of a plume has an all-zero density and a non-empty box);
 //                   L_A = the bricks within distance 1 of L_B; with `fast` set both are every brick. It writes the two lists in
-//                   ascending order, their counts, and clears `fast`. |L_B|, the brick count, fast, |L_A| and the scan's
+//                   ascending order and their counts. |L_B|, the brick count, fast, |L_A| and the scan's
 //                   number go to a mapped pinned mirror for the host's policy (simulate.cpp), as k_project publishes the reach word:
 //                   no copy on the stream. One extra block of pass A writes them, beside the blocks that advect; this kernel itself
 //                   only when no pass over the lists follows (a probe).
@@ -41,7 +56,10 @@
 //       obstacle cell to the bounds of the fluid cells around it).
 //   (6) A listed pass-B tile reads fwd and bounds of its own cells and fwd within +-1 of them: bricks of the 1-ring of L_B, all in
 //       L_A, which pass A has written THIS step. A skipped brick's stale words -- conv activations, the workspace is shared -- are
-//       never read.
+//       never read. With pass A of advectVel in front, bounds live on the planes pass B of advectVel writes afterwards and fwd
+//       behind them (bounds ws[6N, 9N), a three-channel layout per batch item; fwd ws[9N, 10N): simulate.cpp), disjoint from
+//       each other and from that pass A's live temporary ws[0, 3N): the same argument there, and the velocity's temporary is
+//       not written by the scalar passes.
 //   With `fast` set (some |u dt| > 0.9, a NaN, an inf) nothing is skipped.
 // TRACE ERRORS. calcLineTrace's invariant paths (tfl_trace_errors) depend on geometry and velocity only, and a cell of a skipped brick
 // runs no trace, so it counts none here. In the two full launches such a cell traces only when it is fluid with a component of
@@ -60,6 +78,7 @@
 
 #define TFL_SCAL3_NO_ENTRY
 #include "advect_scalar3.hip"      // namespace tfl { namespace { scal3_fwd_body, scal3_bwd_body, Tile, SBlock ... } }
+#include "advect_vel3_kernels.hpp" // namespace tfl { namespace { namespace vel3 { vel3_fwd_body, VTile, VBlock ... } } }
 
 namespace tfl {
 namespace {
@@ -82,8 +101,8 @@ __device__ __forceinline__ unsigned too_fast(float u, float dt) { return __built
 // V4: X % 4 == 0 and 16-byte aligned arrays -- a thread takes four consecutive x cells of one row of the brick (16 rows of 16
 // float4); else one cell of each of the brick's four planes
 template <bool V4>
-__global__ __launch_bounds__(256) void k_scal3_scan(Dom d, Bricks bk, float dt, const float* __restrict__ s, const float* __restrict__ U,
-                                                    unsigned char* __restrict__ nz, unsigned* __restrict__ fast) {
+__global__ __launch_bounds__(256) void k_scal3_scan(Dom d, Bricks bk, float dt, unsigned seq, const float* __restrict__ s, const float* __restrict__ U,
+                                                    unsigned* __restrict__ nz) {
   __shared__ unsigned wave_flags[4];
   const int b = (int)blockIdx.z / bk.nz, iz = (int)blockIdx.z - b * bk.nz, iy = (int)blockIdx.y, ix = (int)blockIdx.x;
   const long long cells = (long long)d.sc;
@@ -122,10 +141,81 @@ __global__ __launch_bounds__(256) void k_scal3_scan(Dom d, Bricks bk, float dt, 
   __syncthreads();
   if (t == 0) {
     const unsigned all = wave_flags[0] | wave_flags[1] | wave_flags[2] | wave_flags[3];
-    nz[((long long)b * bk.nz + iz) * bk.ny * bk.nx + iy * bk.nx + ix] = (unsigned char)(all & 1u);
-    if (all & 2u) atomicOr(fast + b, 1u);      // (the value is not used: an atomic without return)
+    unsigned* tags = nz + (long long)b * (bk.n + 1);
+    if (all & 1u) tags[1 + (iz * bk.ny + iy) * bk.nx + ix] = seq;
+    if (all & 2u) tags[0] = seq;
   }
 }
+
+// ---- the scan as a by-product of pass A of advectVel (advect_vel3_kernels.hpp) ------------------------------------------------------
+// The hook of vel3_fwd_body: a block of that pass (64 x 4 cells x KZ planes from an even plane) lies inside ONE brick -- (vb.x, vb.y,
+// k / 4) -- and its tile holds the own-cell velocity words of every cell it covers. The lane's words of s (one per plane of the
+// block, from a clamped cell: a lane outside the array leaves the body before it looks at them) are asked for before the tile is
+// staged. Per cell the lane's two verdicts are folded into two registers; after the block's last store a wave takes one ballot of
+// each and its first lane stores at most two tags: x0 + lane grows with the lane and the row is the wave's, so lane 0 is inside
+// the array whenever any lane of the wave is. (With the ballots, branches and stores at the top of every plane's iteration the
+// two-plane kernel was 10 us slower at 256^3: profiles/scal3_scan_fold.md.)
+struct ScanHook {
+  static constexpr bool on = true;
+  const float* s;
+  unsigned* nz;
+  unsigned seq;
+  int nx, ny;                                 // bricks per row and rows per plane of bricks: the launch's own gridDim.x, gridDim.y
+  unsigned w0, w1;
+  unsigned long long tags;                    // the item's tags: [0] fast, [1 + brick] nz
+  unsigned brick;
+  unsigned over;                              // the lane's cells so far: some velocity word too fast
+  // (the wave-uniform address, index and number are put into VECTOR registers here, where the stores need them in the end: the
+  // body is short of scalar registers -- see the kernels below -- and has vector registers to spare; timed, it makes no difference)
+  template <int KZ>
+  __device__ __forceinline__ void ask(const Dom& d, int b, int x, int y, int k0, int ix, int iy) {
+    static_assert(KZ == 1 || KZ == 2, "one word of s per plane of the block, both planes in one brick");
+    // (the row is the wave's: a uniform row pointer and the lane's 32-bit offset, as the tile's own row loads)
+    const float* row = s + ((long long)b * d.sc + (long long)y * d.sy);
+    w0 = __builtin_bit_cast(unsigned, vel3::ldg(row + (long long)k0 * d.sz, (unsigned)x * 4u));
+    w1 = KZ == 2 ? __builtin_bit_cast(unsigned, vel3::ldg(row + (long long)min(k0 + 1, d.Z - 1) * d.sz, (unsigned)x * 4u)) : 0u;
+    const int n = nx * ny * ((d.Z + kBrickZ - 1) / kBrickZ);
+    tags = (unsigned long long)(nz + (long long)b * (n + 1));
+    brick = 1u + (unsigned)(((k0 / kBrickZ) * ny + iy) * nx + ix);
+    asm volatile("" : "+v"(tags), "+v"(brick), "+v"(seq));
+  }
+  // per cell: the lane's verdicts only, a few vector instructions beside the body's own; the ballots, branches and stores wait
+  // until the block's results are on their way (finish): nothing of the body waits for them
+  __device__ __forceinline__ void cell(int tz, float u0, float u1, float u2, float dt) {
+    if (tz != 0) w0 |= w1;
+    over |= too_fast(u0, dt) | too_fast(u1, dt) | too_fast(u2, dt);
+  }
+  __device__ __forceinline__ void finish(int lane) const {
+    unsigned* t = reinterpret_cast<unsigned*>(tags);
+    if (__builtin_amdgcn_ballot_w64(w0 != 0u) != 0ull) {
+      if (lane == 0) t[brick] = seq;
+    }
+    if (__builtin_amdgcn_ballot_w64(over != 0u) != 0ull) {
+      if (lane == 0) t[0] = seq;
+    }
+  }
+};
+
+// (depth 1: the plain kernel takes 100 scalar registers, the most that eight waves per SIMD leave a wave, and with the hook the
+// allocator, left alone, takes 102 in the generic trace of the rare slow lanes: seven waves. Capped at 100 it fits in 98 with no
+// spill: 63 VGPRs, 8 waves (the plain kernel: 54, 8). The cap must be a literal, so the four instances are written out)
+template <int KZ, bool FAST>
+__global__ void k_vel3_fwd_scan(AdvArgs a, const float* __restrict__ U, const float* __restrict__ flags, float* __restrict__ out,
+                                const float* __restrict__ s, unsigned* __restrict__ nz, unsigned seq);
+#define TFL_VEL3_FWD_SCAN(KZ, FAST, CAP)                                                                                                  \
+  template <>                                                                                                                              \
+  __global__ __launch_bounds__(256) CAP void k_vel3_fwd_scan<KZ, FAST>(AdvArgs a, const float* __restrict__ U, const float* __restrict__ flags, \
+                                                                       float* __restrict__ out, const float* __restrict__ s,              \
+                                                                       unsigned* __restrict__ nz, unsigned seq) {                          \
+    __shared__ float tile[4 * vel3::VTile<KZ>::LN];                                                                                        \
+    vel3::vel3_fwd_body<KZ, FAST, ScanHook>(vel3::own_block(), tile, a, U, flags, out,                                                     \
+                                            ScanHook{s, nz, seq, (int)gridDim.x, (int)gridDim.y, 0u, 0u, 0ull, 0u, 0u});                       \
+  }
+TFL_VEL3_FWD_SCAN(1, true, __attribute__((amdgpu_num_sgpr(100))))
+TFL_VEL3_FWD_SCAN(1, false, __attribute__((amdgpu_num_sgpr(100))))
+TFL_VEL3_FWD_SCAN(2, true, )
+TFL_VEL3_FWD_SCAN(2, false, )
+#undef TFL_VEL3_FWD_SCAN
 
 constexpr int kListThreads = 1024;
 
@@ -196,13 +286,15 @@ __device__ __forceinline__ void publish_counts(unsigned* mirror, int b, unsigned
 // publish: no pass over the lists follows (a probe), so this kernel writes the mirror itself; else the first list pass does, off the
 // path every later kernel waits on (two round trips to host memory: measured 3-4 us at the end of this one-block kernel)
 __global__ __launch_bounds__(kListThreads) void k_scal3_lists(Bricks bk, int B, BcFoldArg box, unsigned seq, int publish,
-                                                              const unsigned char* __restrict__ nz, unsigned* __restrict__ fast,
+                                                              const unsigned* __restrict__ nz,
                                                               int* __restrict__ lists, int* __restrict__ counts, unsigned* mirror) {
   __shared__ unsigned rows_a[kMaxBrickRows], rows_b[kMaxBrickRows];
   __shared__ int wave_total[kListThreads / 64];
   const int b = (int)blockIdx.x, t = (int)threadIdx.x;
   const unsigned full = bk.nx >= 32 ? ~0u : (1u << bk.nx) - 1u;
-  const bool all = fast[b] != 0u;
+  nz += (long long)b * (bk.n + 1);            // the item's tags: its `fast` tag, then one per brick
+  const bool all = nz[0] == seq;
+  nz++;
   // the bricks of the pair's box (inclusive cell indices, clipped to the array)
   unsigned boxmask = 0u;
   int ey0 = 1, ey1 = 0, ez0 = 1, ez1 = 0;
@@ -216,9 +308,9 @@ __global__ __launch_bounds__(kListThreads) void k_scal3_lists(Bricks bk, int B, 
     }
   }
   for (int r = t; r < bk.rows; r += kListThreads) {
-    const unsigned char* p = nz + ((long long)b * bk.rows + r) * bk.nx;
+    const unsigned* p = nz + (long long)r * bk.nx;
     unsigned w = 0u;
-    for (int ix = 0; ix < bk.nx; ix++) w |= p[ix] ? 1u << ix : 0u;
+    for (int ix = 0; ix < bk.nx; ix++) w |= p[ix] == seq ? 1u << ix : 0u;
     rows_a[r] = w;
   }
   __syncthreads();
@@ -230,7 +322,6 @@ __global__ __launch_bounds__(kListThreads) void k_scal3_lists(Bricks bk, int B, 
   const int nb = compact_rows(rows_b, bk, lists + ((long long)B + b) * bk.n, wave_total, t);
   if (t == 0) {
     counts[4 * b] = na; counts[4 * b + 1] = nb; counts[4 * b + 2] = all ? 1 : 0;
-    fast[b] = 0u;      // for the next scan
     if (publish) publish_counts(mirror, b, seq, (unsigned)nb, (unsigned)bk.n, all ? 1u : 0u, (unsigned)na);
   }
 }
@@ -347,18 +438,35 @@ bool scal3_sparse_fits(const Dom& d) {
   return !forced && whole && scal3_shape_ok(d) && scal3_sparse_bricks(d.Z, d.Y, d.X) > 0;
 }
 
+// (sp.scanned: pass A of advectVel has left this scan's tags already -- vel3_fwd_scan below -- and the lists kernel starts the operator)
 void scal3_sparse_scan(hipStream_t st, const AdvArgs& a, int B, const float* s, const float* U, const BcFoldArg& box, const Scal3SparseAsk& sp) {
   const Dom& d = a.d;
   const Bricks bk = bricks_of(d.Z, d.Y, d.X);
   const dim3 grd((unsigned)bk.nx, (unsigned)bk.ny, (unsigned)(bk.nz * B));
-  {
+  if (!sp.scanned) {
     TFL_TIMED_EXT("k_scal3_scan", st);
-    if (d.X % 4 == 0 && (((uintptr_t)s | (uintptr_t)U) & 15) == 0) TFL_LAUNCH_EXT((k_scal3_scan<true>), grd, 256, 0, st, d, bk, a.dt, s, U, sp.nz, sp.fast);
-    else TFL_LAUNCH_EXT((k_scal3_scan<false>), grd, 256, 0, st, d, bk, a.dt, s, U, sp.nz, sp.fast);
+    if (d.X % 4 == 0 && (((uintptr_t)s | (uintptr_t)U) & 15) == 0) TFL_LAUNCH_EXT((k_scal3_scan<true>), grd, 256, 0, st, d, bk, a.dt, sp.seq, s, U, sp.nz);
+    else TFL_LAUNCH_EXT((k_scal3_scan<false>), grd, 256, 0, st, d, bk, a.dt, sp.seq, s, U, sp.nz);
   }
   TFL_TIMED_EXT("k_scal3_lists", st);
-  TFL_LAUNCH_EXT(k_scal3_lists, (unsigned)B, kListThreads, 0, st, bk, B, box, sp.seq, sp.run == 2 ? 0 : 1, (const unsigned char*)sp.nz, sp.fast, sp.lists,
-                 sp.counts, sp.mirror);
+  TFL_LAUNCH_EXT(k_scal3_lists, (unsigned)B, kListThreads, 0, st, bk, B, box, sp.seq, sp.run == 2 ? 0 : 1, (const unsigned*)sp.nz,
+                 sp.lists, sp.counts, sp.mirror);
+}
+
+// Pass A of advectVel in its scanning form (launched by advect_vel3.hip, which has checked the grid and picked the depth): the
+// launch geometry of the plain k_vel3_fwd<KZ> over the whole array, the same timer name.
+void vel3_fwd_scan(hipStream_t st, int kz, const AdvArgs& a, int B, const float* U, const float* flags, float* out, const Vel3ScanAsk& sc) {
+  const Dom& d = a.d;
+  static_assert(vel3::TX == kBrickX && vel3::TY == kBrickY && kBrickZ % 2 == 0, "a block of either depth lies inside one brick");
+  const int groups = (d.Z + kz - 1) / kz;
+  // (the grid's x and y extents ARE the brick counts the hook indexes the tags with)
+  const dim3 blk(vel3::TX, vel3::TY, 1), grd((d.X + vel3::TX - 1) / vel3::TX, (d.Y + vel3::TY - 1) / vel3::TY, (unsigned)(groups * B));
+  TFL_TIMED_EXT("k_vel_fwd", st);
+#define TFL_VEL3_SCAN(KZ, FAST) \
+  TFL_LAUNCH_EXT((k_vel3_fwd_scan<KZ, FAST>), grd, blk, 0, st, a, U, flags, out, sc.s, sc.nz, sc.seq)
+  if (kz == 1) { if (a.fast) TFL_VEL3_SCAN(1, true); else TFL_VEL3_SCAN(1, false); }
+  else { if (a.fast) TFL_VEL3_SCAN(2, true); else TFL_VEL3_SCAN(2, false); }
+#undef TFL_VEL3_SCAN
 }
 
 void scal3_sparse_passes(hipStream_t st, const AdvArgs& a, int B, float* s, const float* U, const float* flags, float* fwd, float* bounds,

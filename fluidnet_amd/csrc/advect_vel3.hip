@@ -41,16 +41,20 @@ using namespace vel3;
 // kernels: 54 / 72 VGPRs, no SGPR spills in pass A), 2 = two planes per block on one staged tile (3.1 instead of 4.6 staged words
 // per cell and field, at the price of registers -- 63 / 94 VGPRs, SGPR spills): the better one once the staging traffic leaves
 // the caches. Only the one-plane pass B takes the folds' requests `f` (k_vel3_bwd_fold); a deeper launch leaves them untaken.
+// scan (not null: the caller has checked that pass A covers the whole array): pass A in its scanning form, advect_scalar3_sparse.hip.
 template <int KZ>
 void launch(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* U, const float* flags, float* fwd, float* dst,
-            int stages, Fold& f) {
+            int stages, Fold& f, Vel3ScanAsk* scan = nullptr) {
   const Dom& d = a.d;
   const int groups = (d.n0 + KZ - 1) / KZ + (d.nw - d.n0 + KZ - 1) / KZ;      // (KZ = 1: the window's planes, d.nw)
   const dim3 blk(TX, TY, 1), grd((d.X + TX - 1) / TX, (d.Y + TY - 1) / TY, (unsigned)(groups * B));
   const bool pa = stages & 2, pb = stages & 4;
   float* outA = two_pass ? fwd : dst;
   const double hs = (double)a.strength * 0.5;
-  if (pa) {
+  if (pa && scan) {
+    vel3_fwd_scan(st, KZ, a, B, U, flags, outA, *scan);
+    scan->took = true;
+  } else if (pa) {
     TFL_TIMED_EXT("k_vel_fwd", st);
     if (a.fast) TFL_LAUNCH_EXT((k_vel3_fwd<KZ, true>), grd, blk, 0, st, a, U, flags, outA);
     else TFL_LAUNCH_EXT((k_vel3_fwd<KZ, false>), grd, blk, 0, st, a, U, flags, outA);
@@ -80,7 +84,7 @@ void launch(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float*
 }  // namespace
 
 bool advect_vel3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* U, const float* flags, float* fwd,
-                 float* dst, int stages, Fold& f) {
+                 float* dst, int stages, Fold& f, Vel3ScanAsk* scan) {
   const bool off = sw::present(Sw::ADVECT_GATHER);   // A/B switch: the round-2 gather kernels
   const int kz_env = sw::num(Sw::VEL3_KZ, 0);
   const Dom& d = a.d;
@@ -95,11 +99,15 @@ bool advect_vel3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const f
   // one-plane pass B with the force (~320 us) beats the two-plane one plus k_add_buoyancy and two k_apply_bcs_indexed
   // (291 + 94 + 11 us). Pass A stays two-plane. TFL_VEL3_KZ_B=2 keeps the old split.
   const bool b_shallow = deep && two_pass && (stages & 4) && f.buoy.rho && sw::num(Sw::VEL3_KZ_B, 0) != 2;
+  // the scan request of tfl_simulate_step (tfl_host.hpp Vel3ScanAsk): only a pass A over the whole un-cut array at the array's
+  // own origin sees every word once, in blocks that lie inside one brick each; a forced depth still gets THAT depth's kernel
+  const bool whole = d.w0 == 0 && d.n0 == d.Z && d.nw == d.Z && d.zg == 0 && d.Zg == d.Z;
+  Vel3ScanAsk* sc = scan && scan->s && two_pass && (stages & 2) && whole ? scan : nullptr;
   if (deep && b_shallow) {
-    if (stages & 2) launch<2>(st, two_pass, a, B, U, flags, fwd, dst, stages & ~4, f);
+    if (stages & 2) launch<2>(st, two_pass, a, B, U, flags, fwd, dst, stages & ~4, f, sc);
     launch<1>(st, two_pass, a, B, U, flags, fwd, dst, stages & ~2, f);
-  } else if (deep) launch<2>(st, two_pass, a, B, U, flags, fwd, dst, stages, f);
-  else launch<1>(st, two_pass, a, B, U, flags, fwd, dst, stages, f);
+  } else if (deep) launch<2>(st, two_pass, a, B, U, flags, fwd, dst, stages, f, sc);
+  else launch<1>(st, two_pass, a, B, U, flags, fwd, dst, stages, f, sc);
   return true;
 }
 

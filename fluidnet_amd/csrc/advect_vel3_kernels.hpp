@@ -253,16 +253,24 @@ __device__ __forceinline__ void gather8_global(const float* __restrict__ g, cons
 // `for` is removed only after the passes that shape the code around it, and that is what costs the registers (see the top).
 
 // ---- pass A / the single-pass method: SemiLagrangeEulerOursMAC ------------------------------------------------
-template <int KZ, bool FAST>
+// HOOK: a by-product of the pass over the words it stages anyway (advect_scalar3_sparse.hip: the brick scan of advectScalar).
+// ask() runs between the two prologue parts with the lane's clamped cell column (x, y), the block's first plane, batch item and
+// tile (x, y), so loads of its own travel with the tile's; cell() runs once per cell of the array -- fluid, obstacle or border --
+// before the lanes diverge, with the cell's own three velocity words from the tile; finish() once per lane that has cells, after
+// the last plane's stores. NoHook: nothing, the code is what it was without one.
+struct NoHook { static constexpr bool on = false; };
+template <int KZ, bool FAST, class HOOK = NoHook>
 __device__ __forceinline__ void vel3_fwd_body(const VBlock vb, float* __restrict__ tile, const AdvArgs& a, const float* __restrict__ U,
-                                              const float* __restrict__ flags, float* __restrict__ out) {
+                                              const float* __restrict__ flags, float* __restrict__ out, HOOK hook = HOOK()) {
   TFL_VEL3_PRO_A();
+  if constexpr (HOOK::on) hook.template ask<KZ>(d, b, min(x0 + lane, d.X - 1), min(y0 + w, d.Y - 1), k0, vb.x, vb.y);
   TFL_VEL3_PRO_B();
   out += b * cells * 3;
   int tz = 0;
 #pragma unroll 1
   do {
     TFL_VEL3_CELL(tz);
+    if constexpr (HOOK::on) hook.cell(tz, tile[c0], tile[LN + c0], tile[2 * LN + c0], a.dt);
     float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
     unsigned slow = 0;
     const float cf = tile[FL + c0];
@@ -287,6 +295,7 @@ __device__ __forceinline__ void vel3_fwd_body(const VBlock vb, float* __restrict
     }
     if (!(TFL_VEL3_ABL & 4) || a.dt == 12345.0f) { stg(out, o4, v0); stg(out, o4 + sc4, v1); stg(out, o4 + 2u * sc4, v2); }
   } while (KZ > 1 && ++tz < KZ && k0 + tz < kend);
+  if constexpr (HOOK::on) hook.finish(lane);
 }
 template <int KZ, bool FAST>
 __global__ __launch_bounds__(256) void k_vel3_fwd(AdvArgs a, const float* __restrict__ U, const float* __restrict__ flags,

@@ -68,7 +68,6 @@ double get_dx_double(const tfl_ctx* c, const Scope& sc, const tfl_tensor* f) {
 
 static void scal3_sparse_free(Scal3SparseState* p) {
   if (p->buf.nz) (void)hipFree(p->buf.nz);
-  if (p->buf.fast) (void)hipFree(p->buf.fast);
   if (p->buf.lists) (void)hipFree(p->buf.lists);
   if (p->buf.counts) (void)hipFree(p->buf.counts);
   if (p->h_mirror) (void)hipHostFree(p->h_mirror);
@@ -85,8 +84,9 @@ Scal3SparseState* scal3_sparse_state(tfl_ctx* c, const float* key, int B, int Z,
   Scal3SparseState* p = new Scal3SparseState();
   p->key = key; p->B = B; p->Z = Z; p->Y = Y; p->X = X;
   const size_t n = (size_t)B * (size_t)bricks;
-  if (hipMalloc((void**)&p->buf.nz, n) != hipSuccess ||
-      hipMalloc((void**)&p->buf.fast, sizeof(unsigned) * B) != hipSuccess || hipMemset(p->buf.fast, 0, sizeof(unsigned) * B) != hipSuccess ||
+  // (the tags hold scan numbers and are never cleared between scans: zero, the number no scan has, at allocation)
+  p->scans = (unsigned)sw::num(Sw::SCAL3_SEQ0, 0);
+  if (hipMalloc((void**)&p->buf.nz, sizeof(unsigned) * (n + B)) != hipSuccess || hipMemset(p->buf.nz, 0, sizeof(unsigned) * (n + B)) != hipSuccess ||
       hipMalloc((void**)&p->buf.lists, sizeof(int) * 2 * n) != hipSuccess ||
       hipMalloc((void**)&p->buf.counts, sizeof(int) * 4 * B) != hipSuccess || hipMemset(p->buf.counts, 0, sizeof(int) * 4 * B) != hipSuccess ||
       hipHostMalloc((void**)&p->h_mirror, sizeof(unsigned) * 8 * B, hipHostMallocMapped) != hipSuccess ||

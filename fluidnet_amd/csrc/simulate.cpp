@@ -168,15 +168,26 @@ tfl::Scal3SparseAsk scal3_sparse_ask(tfl_ctx* c, const tfl_sim_params* prm, cons
   for (int b = 0; b < z.B; b++) { listed += m[8 * b]; bricks += m[8 * b + 1]; fast = fast || m[8 * b + 2] != 0; known = known && m[8 * b + 4] != 0; }
   const SparsePlan plan = scal3_sparse_plan(mode, known, listed, bricks, fast, st->since_scan);
   if (plan == SparsePlan::full) { *state = st; return ask; }
+  // The scan's number tags the bricks and items it finds set (advect_scalar3_sparse.hip: nothing clears the tags between scans).
+  // Before the number would come back to 0 the tags are cleared on the stream, ahead of the scan, and the count starts again: a
+  // tag in memory is 0 or the number of a scan since the last clear, all below the current one.
+  if (st->scans == 0xffffffffu) {
+    const size_t n = (size_t)z.B * ((size_t)tfl::scal3_sparse_bricks(z.Z, z.Y, z.X) + 1);
+    if (hipMemsetAsync(st->buf.nz, 0, sizeof(unsigned) * n, c->stream) != hipSuccess) { (void)hipGetLastError(); return ask; }
+    st->scans = 0;
+  }
   ask = st->buf;
   ask.run = plan == SparsePlan::lists ? 2 : 1;
   ask.took = 0;
+  ask.scanned = 0;
   ask.seq = st->scans + 1;
   *state = st;
   return ask;
 }
-// what the operator did of the request (Scal3SparseAsk::took), into the field's state and the EXPERIMENTS flavour's counters
-void scal3_sparse_done(tfl_ctx* c, Scal3SparseState* st, int took) {
+// what the operator did of the request (Scal3SparseAsk::took; a scan inside pass A of advectVel has used the number as well), into
+// the field's state and the EXPERIMENTS flavour's counters
+void scal3_sparse_done(tfl_ctx* c, Scal3SparseState* st, int took, bool scanned = false) {
+  if (st && !took && scanned) st->scans++;
   if (st && took) { st->scans++; st->since_scan = 0; c->scal3_last = st; }
   else if (st) st->since_scan++;
 #ifdef TFL_EXPERIMENTS
@@ -278,24 +289,47 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
 
   // ---- advection (simulate.lua:183-200): every density channel with the pre-advection U, then U ----------------
   unsigned density_done = 0;
+  tfl_tensor vfwd = view(ws, (int)z.C), vbwd = view(ws + z.C * z.N, (int)z.C), Uadv = view(ws + 2 * z.C * z.N, (int)z.C);
+  // Where the first channel's advection goes over the brick lists (or probes them: scal3_sparse_ask), PASS A OF advectVel RUNS
+  // FIRST and leaves the brick scan of that channel as a by-product of the words of U it stages anyway (tfl_host.hpp Vel3ScanAsk,
+  // DESIGN.md 3.17): advectVel stage A with the request, the density channels, advectVel stage B. The two operators read the same
+  // pre-advection U and pass A writes nothing but its own temporary, so the results are what they were in the other order. That
+  // temporary (the `fwd` planes, ws[0, 3N)) is now live while the scalar passes run: their temporaries move to planes nothing
+  // writes before stage B. The bounds are laid out as a three-channel field (two planes used of every batch item's three), so
+  // they take all of the `Uadv` planes ws[6N, 9N); the scalar fwd goes behind them, ws[9N, 10N) (|curl| of the confinement,
+  // later in the step; the workspace holds (2C + 4) N); the unused min / max planes go to the unused `bwd` planes ws[3N, 6N).
+  Scal3SparseState* sparse0 = nullptr;
+  tfl::Scal3SparseAsk ask0;
+  if (s->n_density > 0) ask0 = scal3_sparse_ask(c, prm, sc, z, ours, s->density[0], &sparse0);
+  const bool vel_first = ask0.run != 0;      // (only ever in place on the whole un-cut 3-D array, never while capturing)
+  if (vel_first) {
+    tfl::Scope sa = sc;
+    sa.stages = 2;
+    tfl::Ask a = step_ask(nullptr);
+    a.scan.s = s->density[0]->data; a.scan.nz = ask0.nz; a.scan.seq = ask0.seq;
+    rc = tfl::advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vbwd, is3D, method, 1, prm->maccormackStrength, &Uadv, sa, a);
+    if (rc) return rc;
+    ask0.scanned = a.scan.took ? 1 : 0;      // not taken (a gather path): advectScalar runs k_scal3_scan itself
+  }
   for (int i = 0; i < s->n_density; i++) {
     tfl_tensor fwd = view(ws, 1), bwd = view(ws + z.N, 1), fwdPos = view(ws + 2 * z.N, (int)z.C),
                bwdPos = view(ws + (2 + z.C) * z.N, (int)z.C), out = view(ws + (2 + 2 * z.C) * z.N, 1);
+    if (vel_first) { fwd = view(ws + 9 * z.N, 1); bwd = view(ws + 3 * z.N, 1); fwdPos = view(ws + 6 * z.N, 3); bwdPos = view(ws + 3 * z.N, 3); }
     const tfl_tensor* dst = ours ? s->density[i] : &out;       // maccormackOurs runs in place (no copy back)
     // the first setConstVals (below) follows the advection directly: the kernel that writes the advected field applies
     // the field's pair itself where it can (step_ask; the sparse launch covers the rest)
     tfl::Ask a = step_ask(s->densityBC[i]);
     // ... and, where most of the field is +0.0, only over the bricks around the words that are not (scal3_sparse_ask)
-    Scal3SparseState* sparse = nullptr;
-    a.sparse = scal3_sparse_ask(c, prm, sc, z, ours, s->density[i], &sparse);
+    Scal3SparseState* sparse = sparse0;
+    if (i == 0) a.sparse = ask0;
+    else a.sparse = scal3_sparse_ask(c, prm, sc, z, ours, s->density[i], &sparse);
     rc = tfl::advectScalar(c, prm->dt, s->density[i], s->U, s->flags, &fwd, &bwd, is3D, method, &fwdPos, &bwdPos, 1, 0,
                            prm->maccormackStrength, dst, sc, a);
-    if (ours && z.is3d) scal3_sparse_done(c, sparse, a.sparse.took);
+    if (ours && z.is3d) scal3_sparse_done(c, sparse, a.sparse.took, a.sparse.scanned != 0);
     if (a.fold.bc_took) density_done |= 1u << i;
     if (rc) return rc;
     if (!ours) { rc = tfl_copy(c, s->density[i], &out); if (rc) return rc; }
   }
-  tfl_tensor vfwd = view(ws, (int)z.C), vbwd = view(ws + z.C * z.N, (int)z.C), Uadv = view(ws + 2 * z.C * z.N, (int)z.C);
   const bool buoyant = s->n_density > 0 && prm->buoyancyScale > 0.0;
   const double dx = tfl::get_dx_double(c, sc, s->flags);
   float bg[3];
@@ -313,7 +347,9 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
       adv.fold.buoy = tfl::BuoyFold{s->density[0]->data, -bg[0] * bs, -bg[1] * bs, -bg[2] * bs};
     }
   }
-  rc = tfl::advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vbwd, is3D, method, 1, prm->maccormackStrength, &Uadv, sc, adv);
+  tfl::Scope sb = sc;
+  if (vel_first) sb.stages = 4;      // pass A has run, in front of the density channels
+  rc = tfl::advectVel(c, prm->dt, s->U, s->flags, &vfwd, &vbwd, is3D, method, 1, prm->maccormackStrength, &Uadv, sb, adv);
   const bool Uadv_done = adv.fold.bc_took, buoy_folded = adv.fold.buoy_took;
   if (rc) return rc;
   // U:copy(advected) (init.lua:216-218) costs nothing: the velocity stays in the advection's scratch array (`cur`) until an

@@ -124,8 +124,9 @@ static inline dim3 cell_grid(const Dom& d, int B, dim3 blk) {
 
 
 // advect_vel3.hip: advectVel of the trace-based methods on a 3-D grid; false = shape not supported (caller falls back)
+// scan: tfl_simulate_step's request for the brick scan of advectScalar as a by-product of pass A (null: none)
 bool advect_vel3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* U, const float* flags, float* fwd,
-                 float* dst, int stages, Fold& f);
+                 float* dst, int stages, Fold& f, Vel3ScanAsk* scan = nullptr);
 // advect_scalar3.hip: advectScalar of the trace-based methods on a 3-D grid (no min/max grid: `bounds` = two planes)
 // sparse: tfl_simulate_step's request for the passes over the list of non-empty bricks (null or run == 0: none)
 bool advect_scalar3(hipStream_t st, bool two_pass, const AdvArgs& a, int B, const float* s, const float* U, const float* flags,
@@ -139,11 +140,16 @@ inline bool scal3_shape_ok(const Dom& d) {
 // advect_scalar3_sparse.hip: the in-place maccormackOurs advectScalar over a device-built list of the bricks (64 x 4 x 4 cells) around
 // the words of s that are not +0.0.
 // (scal3_sparse_bricks / scal3_sparse_fits, what the step's policy asks first: tfl_host.hpp)
-// k_scal3_scan + k_scal3_lists: the brick flags, the two lists, their counts and the pinned mirror; box = the pair pass B folds
+// k_scal3_scan (unless sp.scanned: pass A of advectVel has left the tags) + k_scal3_lists: the brick tags, the two lists, their counts
+// and the pinned mirror; box = the pair pass B folds
 void scal3_sparse_scan(hipStream_t st, const AdvArgs& a, int B, const float* s, const float* U, const BcFoldArg& box, const Scal3SparseAsk& sp);
 // the two passes over the lists (timer names k_scalar_fwd / k_scalar_bwd); dst == s
 void scal3_sparse_passes(hipStream_t st, const AdvArgs& a, int B, float* s, const float* U, const float* flags, float* fwd, float* bounds,
                          const BcFoldArg& fold, const Scal3SparseAsk& sp);
+
+// pass A of advectVel over the whole array at block depth kz (1 or 2) in its scanning form (timer name k_vel_fwd): the plain
+// kernel's result, and the brick and `fast` tags of scan sc.seq
+void vel3_fwd_scan(hipStream_t st, int kz, const AdvArgs& a, int B, const float* U, const float* flags, float* out, const Vel3ScanAsk& sc);
 
 // 1 = the scalar passes may take the short path of all-zero tiles on this grid (the switch is on and the grid's global extent is
 // inside the bound of the proof); what advect_scalar3 / advect_pair3 put into AdvArgs::zskip

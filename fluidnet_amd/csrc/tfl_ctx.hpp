@@ -26,7 +26,7 @@ struct tfl_wall_plan {
 struct Scal3SparseState {
   const float* key = nullptr;
   int B = 0, Z = 0, Y = 0, X = 0;
-  tfl::Scal3SparseAsk buf;                    // nz, fast, lists, counts, mirror (run / took / seq are per call)
+  tfl::Scal3SparseAsk buf;                    // nz (the tags), lists, counts, mirror (run / took / scanned / seq are per call)
   unsigned* h_mirror = nullptr;               // pinned, mapped: 8 words per batch item (|L_B|, bricks, fast, |L_A|, the scan's number)
   unsigned scans = 0;                         // scans launched for this field so far (the next scan's number - 1)
   unsigned since_scan = 0;                    // steps on the two full launches since the last scan

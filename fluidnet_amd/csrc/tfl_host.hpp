@@ -68,12 +68,23 @@ struct Fold {
 struct Scal3SparseAsk {
   int run = 0;                     // 0 = nothing | 1 = scan + lists, then the two full launches (a probe) | 2 = scan + lists + list-driven passes
   int took = 0;                    // out: what the operator did of it (0: it ran the two full launches and nothing else)
+  int scanned = 0;                 // pass A of advectVel has run this scan already (Vel3ScanAsk::took): the operator starts at the lists kernel
   unsigned seq = 0;                // the scan's number (> 0), published behind its counts
-  unsigned char* nz = nullptr;     // [B][bricks]: the brick holds a word of s that is not +0.0
-  unsigned* fast = nullptr;        // [B]: some velocity face has !(|U dt| <= 0.9); the lists kernel reads and clears it
+  unsigned* nz = nullptr;          // [B][1 + bricks] tags, "set" = equals seq (never cleared between scans). Per item: [0] `fast`, some
+                                   // velocity face has !(|U dt| <= 0.9); [1 + brick] the brick holds a word of s that is not +0.0
   int* lists = nullptr;            // [2][B][bricks]: the compacted lists L_A, L_B (brick indices, ascending)
   int* counts = nullptr;           // [B][4]: |L_A|, |L_B|, fast as the lists kernel read it
   unsigned* mirror = nullptr;      // device address of the pinned mirror, 8 words per item: |L_B|, bricks, fast, |L_A|, seq
+};
+
+// What tfl_simulate_step asks of pass A of advectVel when the advectScalar of density field s follows on the lists: leave that
+// scan's tags (the arrays and the number of the Scal3SparseAsk) as a by-product of the words of U the pass stages anyway. Taken
+// only by the tile kernels on the whole array (advect_vel3.hip); else advectScalar runs its own k_scal3_scan.
+struct Vel3ScanAsk {
+  const float* s = nullptr;        // the density field, [B][1][Z][Y][X]; nullptr: no request
+  unsigned* nz = nullptr;          // Scal3SparseAsk::nz, ::seq
+  unsigned seq = 0;
+  bool took = false;               // out: the scanning form of pass A ran
 };
 
 // does row (j, k) / cell i of the field lie inside the pair's box
@@ -148,7 +159,7 @@ void advect_scalar(hipStream_t st, const Scope& sc, bool is3d, int method, int B
 int scal3_sparse_bricks(int Z, int Y, int X);      // bricks per batch item; 0 = the grid is outside what the brick map holds
 bool scal3_sparse_fits(const Dom& d);              // the whole array, a shape the tile kernels and the brick map take, no forced kernel form
 void advect_vel(hipStream_t st, const Scope& sc, bool is3d, int method, int B, int Z, int Y, int X, float dt, float strength,
-                unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, Fold& f);
+                unsigned long long* err, const float* U, const float* flags, float* fwd, float* dst, Fold& f, Vel3ScanAsk* scan = nullptr);
 
 void minmax3(hipStream_t st, bool is3d, int B, const Dom& d, int outside, const float* s, const float* flags, float* lo3,
              float* hi3);

@@ -11,6 +11,7 @@ namespace tfl {
 struct Ask {
   Fold fold;                       // the setConstVals pair / buoyancy force for the kernel that writes the result, and what was taken
   Scal3SparseAsk sparse;           // advectScalar (tfl_simulate_step sets it): the passes over the list of non-empty bricks (tfl_host.hpp)
+  Vel3ScanAsk scan;                // advectVel (tfl_simulate_step sets it): the brick scan of the advectScalar that follows, inside pass A
   bool two_launch = false;         // vorticityConfinementFrom: the two launches even where the fused kernel would run
   bool gated = true;               // model_begin / model_forward: take the fp16 range gate (a step takes it once, at its entry)
   bool conv1_sums_stats = false;   // model_begin / model_finish (model_forward sets it): the first conv layer sums the partials itself

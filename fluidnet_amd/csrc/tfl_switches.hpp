@@ -54,7 +54,8 @@
   X(SCAL3M_CZ_B,     "TFL_SCAL3M_CZ_B",     EXP,     PER_CALL, ">0 overrides the chosen chunk length of pass B of the z-marched advectScalar") \
   X(SCAL3_MARCH,     "TFL_SCAL3_MARCH",     EXP,     ONCE,     "=1 the z-marched advectScalar kernels (not under a forced TFL_SCAL3_TZ)") \
   X(SCAL3_SPARSE,    "TFL_SCAL3_SPARSE",    EXP,     ONCE,     "advectScalar of tfl_simulate_step over the list of non-empty bricks: 0 = never, 2 = always, 1 or unset = by the host policy (same bits either way)") \
-  X(SCAL3_ZSKIP,     "TFL_SCAL3_ZSKIP",     EXP,     ONCE,     "=0 turns the short path of all-zero advectScalar tiles off: every block traces (same bits either way)") \
+  X(SCAL3_SEQ0,      "TFL_SCAL3_SEQ0",      EXP,     ONCE,     "the number of scans a density field's brick-list state starts from, as a 32-bit word (tests: -3 puts the wrap of the scan's number three scans away; unset = 0)") \
+  X(SCAL3_ZSKIP,   "TFL_SCAL3_ZSKIP",     EXP,     ONCE,     "=0 turns the short path of all-zero advectScalar tiles off: every block traces (same bits either way)") \
   X(SLAB_WIDEN,      "TFL_SLAB_WIDEN",      EXP,     ONCE,     "planes added below and above every phase window of the z-slab step (development aid; unset = 0)") \
   X(STATS_FOLD,      "TFL_STATS_FOLD",      EXP,     PER_CALL, "=1 folds k_reduce_stats into the last block of k_bcs_div_stats (the tests switch it inside one process)") \
   X(VEL3_KZ_B,       "TFL_VEL3_KZ_B",       EXP,     ONCE,     "=2 keeps pass B of advectVel on the two-plane kernel when the buoyancy fold is asked for") \
