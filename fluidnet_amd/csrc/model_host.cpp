@@ -1,6 +1,6 @@
 // model_host.cpp -- the host side of the projection ConvNet behind include/tfluids_hip.h: the tfl_model object (layer table,
 // packed weights, conv path), its creation, its workspace layout, the fp16 range gate, the wall plans, and the forward pass
-// (tfl_model_begin / _finish / _forward) in its six forms. tfl_model's fields are private to this file: simulate.cpp asks
+// (tfl_model_begin / _finish / _forward) in its six forms. tfl_model's fields are private to this file: the native steps ask
 // through model_is_graph / model_grid_factor / model_cone / model_range_counter (tfl_host.hpp, tfl_ops.hpp).
 #include <algorithm>
 #include <cmath>
@@ -792,7 +792,7 @@ void model_slab_stats(hipStream_t st, const tfl_model* m, int B, int Z, long lon
   *count = mode == 0 ? (double)z_total * (double)yx * (udiv ? 3.0 : 1.0) : 2.0;
 }
 
-// (library-internal, C++ linkage: the device word of a model's fp16 range counter, for the z-slab step's collective gate -- simulate.cpp)
+// (library-internal, C++ linkage: the device word of a model's fp16 range counter, for the z-slab step's collective gate -- simulate_slab.cpp)
 const unsigned long long* model_range_counter(const tfl_model* m) { return m ? m->d_range_err : nullptr; }
 
 int model_begin(tfl_ctx* c, tfl_model* m, const tfl_tensor* UDiv, const tfl_tensor* flags, const tfl_tensor* UOut, float* workspace,

@@ -1,5 +1,6 @@
 // tfl_ctx.hpp -- the context object behind the opaque tfl_ctx* of include/tfluids_hip.h (private to the library:
-// context.cpp owns it, simulate.cpp reads the stream and keeps the z-slab reach-check words). It holds resources and what the
+// context.cpp owns it, simulate.cpp and simulate_slab.cpp read the stream, simulate.cpp keeps the brick-list state of
+// advectScalar and simulate_slab.cpp the z-slab reach-check words). It holds resources and what the
 // host's tfl_set_* calls stored. Nothing per call lives here: what a native step asks of an operator call (tfl_ops.hpp Ask)
 // and where that call computes (tfl_host.hpp Scope) travel as arguments.
 #pragma once

@@ -458,7 +458,8 @@ def test_tog_topology_pooling_and_convolution_upsample(oracle, is3d, dims):
 
 
 @pytest.mark.parametrize("which", ["2d_jacobi", "2d_convnet_rgb", "3d_convnet_vort_obstacle", "3d_gravity_rk2", "2d_pcg",
-                                   "3d_buoyancy_any_gravity", "3d_buoyancy_no_vorticity", "3d_buoyancy_jacobi", "3d_buoyancy_fast_mode"])
+                                   "3d_buoyancy_any_gravity", "3d_buoyancy_no_vorticity", "3d_buoyancy_jacobi", "3d_buoyancy_fast_mode",
+                                   "3d_vort_only_convnet", "3d_gravity_only_jacobi"])
 def test_native_simulate_step_equals_python_orchestration(which):
     """tfl_simulate_step (csrc/simulate.cpp: lib/simulate.lua in native code behind one C-ABI call) against
     fluidnet_amd.simulate.simulate() over several steps: identical state, bit for bit."""
@@ -486,6 +487,16 @@ def test_native_simulate_step_equals_python_orchestration(which):
         b = _plume_batch((12, 14, 16), 0.15, 1.0)
         model = FluidNetModel(S.default_3d_layers(seed=5), True)
         mconf = dict(base, simMethod="convnet", advectionMethod="rk2Ours", gravityScale=0.3, buoyancyScale=0, gravity=[0.2, 1.0, -0.3])
+    elif which == "3d_vort_only_convnet":
+        # no buoyancy: the velocity leaves the advection's scratch array through vorticityConfinementFrom with nothing before it
+        # (a grid below the fused kernel's size: the two-launch form)
+        b = _plume_batch((12, 14, 16), 0.15, 1.0)
+        model = FluidNetModel(S.default_3d_layers(seed=5), True)
+        mconf = dict(base, simMethod="convnet", buoyancyScale=0, vorticityConfinementAmp=1.5)
+    elif which == "3d_gravity_only_jacobi":
+        # no buoyancy, no vorticity: gravity in place on the scratch velocity, then the explicit copy into U
+        b = _plume_batch((12, 14, 16), 0.15, 1.0)
+        mconf = dict(base, simMethod="jacobi", maxIter=12, buoyancyScale=0, gravityScale=0.3, gravity=[0.2, 1.0, -0.3])
     elif which.startswith("3d_buoyancy"):
         # round 5: the buoyancy force inside pass B of advectVel (BuoyFold) and the velocity delivered into U by whoever writes
         # every cell next -- a gravity with three components (the generic BUOY mask), no vorticity (the ConvNet projection reads
