@@ -7,6 +7,7 @@
   fluidnet_amd.train      ProjectionNet: the net as a torch.nn.Module over tfl_model_forward_train / tfl_model_backward
   fluidnet_amd.optim      Adam / RMSprop: gradient clip + lib/adam.lua / lib/rmsprop.lua + weight refresh over tfl_optim_step
   fluidnet_amd.criterion  nn.FluidCriterion (torch/lib/modules/fluid_criterion.lua) over tfl_fluidCriterion
+  fluidnet_amd.run_epoch  the training closure of torch/lib/run_epoch.lua (long-term divergence pass included) as one call
   fluidnet_amd.dist       z-slab decomposition across GPUs: halo exchange + 1 all-reduce per step (RCCL)
   fluidnet_amd.csrc/      hand-written HIP kernels for gfx950 + the C ABI (include/tfluids_hip.h)
 """
@@ -16,8 +17,9 @@ from .model import FluidNetModel, load_model  # noqa: F401
 from . import stats  # noqa: F401  (module: stats.calcStats)
 from . import criterion  # noqa: F401
 from .criterion import FluidCriterion  # noqa: F401  (nn.FluidCriterion: loss terms and input gradients in one pass)
-from .simulate import calcPUTargets  # noqa: F401  (the training targets by a Jacobi / PCG projection)
+from .simulate import calcPUTargets, dataAugmentation  # noqa: F401  (the training targets by a Jacobi / PCG projection; the forces added before it)
 from .train import ProjectionNet  # noqa: F401  (the projection net as an nn.Module: forward with a tape, parameter gradients)
 from . import optim  # noqa: F401  (optim.Adam / optim.RMSprop: clip + update + weight refresh as one device call)
+from . import run_epoch  # noqa: F401  (run_epoch.plan_batch / Closure / run_epoch: one call for a training mini-batch)
 from . import modules  # noqa: F401  (the tfluids nn.Modules as torch.nn.Modules with autograd)
 from ._lib import TfluidsError  # noqa: F401

@@ -15,6 +15,7 @@ KERNEL_SOURCE = {
     "k_add_buoyancy": "stencil.hip", "k_add_gravity": "stencil.hip",
     "k_divnorm_planes": "divnorm.hip", "k_divnorm_finish": "divnorm.hip",
     "k_criterion_weight": "criterion.hip", "k_criterion_planes": "criterion.hip", "k_criterion_finish": "criterion.hip",
+    "k_closure_fold": "criterion.hip",
     "k_bcs_div_stats": "model.hip", "k_reduce_stats": "model.hip", "k_project": "model.hip", "k_net_input": "model.hip",
     "k_apply_bcs_indexed": "model.hip", "k_bc_scan": "model.hip",
     "k_conv_wgrad": "conv_bwd.hip+tfl_train.hpp", "k_conv_wgrad_finish": "conv_bwd.hip+tfl_train.hpp", "k_scale_add": "conv_bwd.hip",

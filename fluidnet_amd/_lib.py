@@ -115,6 +115,7 @@ SIGNATURES = {
     "tfl_fluid_criterion_workspace_floats": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32]),
     "tfl_fluidCriterion": (_c.c_int, [_c.c_void_p, _T, _T, _T, _T, _T, _T, _c.c_double, _c.c_double, _c.c_double, _c.c_int, _c.c_int,
                                       _c.c_void_p, _T, _T, _c.c_void_p, _c.c_int64]),
+    "tfl_closure_fold": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double]),
     "tfl_velocityUpdateForward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int]),
     "tfl_vorticityConfinement": (_c.c_int, [_c.c_void_p, _T, _T, _c.c_float, _T, _T, _T, _T,
                                             _c.c_int]),
@@ -171,6 +172,8 @@ SIGNATURES = {
     "tfl_optim_create": (_c.c_void_p, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "tfl_optim_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
                                   _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p)]),
+    "tfl_optim_step_guarded": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
+                                          _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.c_void_p]),
     "tfl_optim_set_config": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "tfl_optim_steps": (_c.c_int64, [_c.c_void_p, _c.c_void_p]),
     "tfl_optim_get_state": (_c.c_int64, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),

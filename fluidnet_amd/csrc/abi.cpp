@@ -325,6 +325,17 @@ int tfl_fluidCriterion(tfl_ctx* c, const tfl_tensor* pPred, const tfl_tensor* UP
   return check_launch(c, op);
 }
 
+int tfl_closure_fold(tfl_ctx* c, const double* loss4, double* sums5, int32_t* guard, int longTerm, double errLimit) {
+  const char* op = "closure_fold";
+  if (!c) return TFL_EINVAL;
+  if (!loss4 || !sums5 || (((uintptr_t)loss4 | (uintptr_t)sums5) & 7) != 0)
+    return fail(c, TFL_EINVAL, "%s: loss4 or sums5 is null or not 8-byte aligned", op);
+  if (!guard || ((uintptr_t)guard & 3) != 0) return fail(c, TFL_EINVAL, "%s: guard is null or not 4-byte aligned", op);
+  if (errLimit != errLimit) return fail(c, TFL_EINVAL, "%s: errLimit is NaN", op);
+  tfl::closure_fold(c->stream, loss4, sums5, guard, longTerm != 0, errLimit);
+  return check_launch(c, op);
+}
+
 int tfl_velocityUpdateForward(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* p,
                               int is3D) {
   TRY(check_flags(c, "velocityUpdateForward", flags));

@@ -316,6 +316,24 @@ __global__ __launch_bounds__(256) void k_criterion_finish(const double* __restri
   }
 }
 
+// run_epoch.lua:216-229, 287-291 without the host read: the epoch's running sums {p, u, div, total, long-term total} take one
+// criterion result, and the guard word is set (and stays set) when the total is NaN or above errLimit. One thread, plain
+// fp64 adds in the order written here.
+__global__ void k_closure_fold(const double* __restrict__ loss4, double* __restrict__ sums5, int* __restrict__ guard, int longTerm,
+                               double errLimit) {
+  const double total = loss4[3];
+  if (longTerm) {
+    sums5[3] = sums5[3] + total;
+    sums5[4] = sums5[4] + total;
+  } else {
+    sums5[0] = sums5[0] + loss4[0];
+    sums5[1] = sums5[1] + loss4[1];
+    sums5[2] = sums5[2] + loss4[2];
+    sums5[3] = sums5[3] + total;
+  }
+  if (total != total || total > errLimit) *guard = 1;
+}
+
 // fluid_criterion.lua:149-157 per cell, one fp32 rounding per Lua call
 __global__ __launch_bounds__(256) void k_criterion_weight(int rad, float bw, float m, float s, int Z, int Y, int X,
                                                           const float* __restrict__ flags, float* __restrict__ w) {
@@ -367,6 +385,11 @@ void criterion_planes(hipStream_t st, bool is3d, int B, int Z, int Y, int X, con
 void criterion_finish(hipStream_t st, long long n, const double* sums, const CriterionFinish& f, double* loss) {
   TFL_TIMED_EXT("k_criterion_finish", st);
   TFL_LAUNCH_EXT(k_criterion_finish, 1, 256, 0, st, sums, n, f, loss);
+}
+
+void closure_fold(hipStream_t st, const double* loss4, double* sums5, int* guard, int longTerm, double errLimit) {
+  TFL_TIMED("k_closure_fold", st);
+  hipLaunchKernelGGL(k_closure_fold, dim3(1), dim3(1), 0, st, loss4, sums5, guard, longTerm, errLimit);
 }
 
 }  // namespace tfl

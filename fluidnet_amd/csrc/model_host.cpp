@@ -1559,8 +1559,14 @@ int tfl_optim_set_config(tfl_ctx* c, tfl_optim* o, const tfl_optim_config* confi
 
 int tfl_optim_step(tfl_ctx* c, tfl_optim* o, float* const* d_weights, float* const* d_biases, float* const* d_gradWeights,
                    float* const* d_gradBiases) {
+  return tfl_optim_step_guarded(c, o, d_weights, d_biases, d_gradWeights, d_gradBiases, nullptr);
+}
+
+int tfl_optim_step_guarded(tfl_ctx* c, tfl_optim* o, float* const* d_weights, float* const* d_biases, float* const* d_gradWeights,
+                           float* const* d_gradBiases, const int32_t* d_guard) {
   if (!c) return TFL_EINVAL;
-  const char* who = "optim_step";
+  const char* who = d_guard ? "optim_step_guarded" : "optim_step";
+  if (((uintptr_t)d_guard & 3) != 0) return fail(c, TFL_EINVAL, "%s: the guard word is not 4-byte aligned", who);
   if (!o || !d_weights || !d_biases || !d_gradWeights || !d_gradBiases) return fail(c, TFL_EINVAL, "%s: null optimiser or parameter table", who);
   const int n = o->ntens / 2;
   tfl::OptimPtrs p{};
@@ -1580,7 +1586,7 @@ int tfl_optim_step(tfl_ctx* c, tfl_optim* o, float* const* d_weights, float* con
   a.eps = (float)k.epsilon; a.wd = (float)k.weightDecay;
   a.lr = k.learningRate; a.lrd = k.learningRateDecay; a.beta1 = k.beta1; a.beta2 = k.beta2;
   a.threshold = k.gradNormThreshold > 0.0 ? k.gradNormThreshold : 0.0;
-  tfl::optim_step(c->stream, p, o->d_off, o->ntens, o->total, o->d_partials, o->m, o->v, o->d_t, a);
+  tfl::optim_step(c->stream, p, o->d_off, o->ntens, o->total, o->d_partials, o->m, o->v, o->d_t, a, d_guard);
   TRY(check_launch(c, who));
   return tfl_model_set_weights_device(c, o->model, d_weights, d_biases);
 }

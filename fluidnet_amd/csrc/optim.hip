@@ -4,7 +4,8 @@
 // Three launches at the most: k_optim_norm leaves one fp64 partial of sum g^2 per block at a fixed place, k_optim_update adds
 // them in index order (every block the same sum: no atomics, the same bits every call), clips, decays and updates each
 // element in fp32 in the reference's operation order, and k_optim_advance moves the step counter -- a kernel, so that a captured
-// step advances on replay.
+// step advances on replay. With a guard word (tfl_optim_step_guarded) the update and the advance read it when they run and,
+// where it is set, write nothing: parameters, moments and the counter stay as they are.
 #include <hip/hip_runtime.h>
 
 #include "tfl_host.hpp"
@@ -39,12 +40,14 @@ __global__ __launch_bounds__(kOptimThreads) void k_optim_norm(OptimPtrs p, const
 __global__ __launch_bounds__(kOptimThreads) void k_optim_update(OptimPtrs p, const long long* __restrict__ off, int ntens, long long total,
                                                                const double* __restrict__ partials, int npartials,
                                                                float* __restrict__ m, float* __restrict__ v,
-                                                               const long long* __restrict__ t_ptr, OptimArgs c) {
+                                                               const long long* __restrict__ t_ptr, OptimArgs c,
+                                                               const int* __restrict__ guard) {
   __shared__ long long s_off[kOptimMaxTensors + 1];
   __shared__ float s_div, s_step;
-  __shared__ int s_clip;
+  __shared__ int s_clip, s_skip;
   for (int i = threadIdx.x; i <= ntens; i += kOptimThreads) s_off[i] = off[i];
   if (threadIdx.x == 0) {
+    s_skip = guard ? *guard : 0;
     s_clip = 0; s_div = 1.0f;
     if (partials) {
       double sum = 0.0;
@@ -60,7 +63,7 @@ __global__ __launch_bounds__(kOptimThreads) void k_optim_update(OptimPtrs p, con
   }
   __syncthreads();
   const long long i = (long long)blockIdx.x * kOptimThreads + threadIdx.x;
-  if (i >= total) return;
+  if (i >= total || s_skip) return;
   const int t = optim_tensor_of(s_off, ntens, i);
   const long long e = i - s_off[t];
   float x = p.x[t][e], g = p.g[t][e];
@@ -80,7 +83,10 @@ __global__ __launch_bounds__(kOptimThreads) void k_optim_update(OptimPtrs p, con
   p.x[t][e] = x;
 }
 
-__global__ void k_optim_advance(long long* t) { *t += 1; }
+__global__ void k_optim_advance(long long* t, const int* __restrict__ guard) {
+  if (guard && *guard) return;
+  *t += 1;
+}
 __global__ __launch_bounds__(kOptimThreads) void k_optim_fill(float* p, long long n, float val) {
   const long long i = (long long)blockIdx.x * kOptimThreads + threadIdx.x;
   if (i < n) p[i] = val;
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(kOptimThreads) void k_optim_fill(float* p, long lon
 }  // namespace
 
 void optim_step(hipStream_t st, const OptimPtrs& p, const long long* d_off, int ntens, long long total, double* d_partials, float* m,
-                float* v, long long* d_t, const OptimArgs& c) {
+                float* v, long long* d_t, const OptimArgs& c, const int* d_guard) {
   const bool clip = c.threshold > 0.0;
   if (clip) {
     TFL_TIMED("k_optim_norm", st);
@@ -98,10 +104,10 @@ void optim_step(hipStream_t st, const OptimPtrs& p, const long long* d_off, int 
   {
     TFL_TIMED("k_optim_update", st);
     hipLaunchKernelGGL(k_optim_update, dim3(nb), dim3(kOptimThreads), 0, st, p, d_off, ntens, total, clip ? (const double*)d_partials : nullptr,
-                       kOptimNormBlocks, m, v, (const long long*)d_t, c);
+                       kOptimNormBlocks, m, v, (const long long*)d_t, c, d_guard);
   }
   TFL_TIMED("k_optim_advance", st);
-  hipLaunchKernelGGL(k_optim_advance, dim3(1), dim3(1), 0, st, d_t);
+  hipLaunchKernelGGL(k_optim_advance, dim3(1), dim3(1), 0, st, d_t, d_guard);
 }
 void optim_fill(hipStream_t st, float* p, long long n, float val) {
   if (n < 1) return;

@@ -214,6 +214,8 @@ struct CriterionFinish { double lambda[3], n[3]; int on[3]; };      // term t = 
 void criterion_weight(hipStream_t st, int B, int Z, int Y, int X, int rad, float bw, float m, float s, const float* flags, float* w);
 void criterion_planes(hipStream_t st, bool is3d, int B, int Z, int Y, int X, const CriterionArgs& a);
 void criterion_finish(hipStream_t st, long long n, const double* sums, const CriterionFinish& f, double* loss);
+// the training closure's loss fold and guard (tfl_closure_fold): one launch of one thread
+void closure_fold(hipStream_t st, const double* loss4, double* sums5, int* guard, int longTerm, double errLimit);
 
 // vorticity.hip
 // stages: bit 0 = pass A (U -> curl, |curl|), bit 1 = pass B (curl, |curl|, flags, U -> U); a z-slab rank runs the two
@@ -466,7 +468,7 @@ void refresh_pack(hipStream_t st, const RefreshSrc& src, const PackJob* d_jobs, 
 void refresh_pack16(hipStream_t st, const RefreshSrc& src, void* const* wfrag16, float* d_post, float* tail_pack);
 // optim.hip: clip + weight decay + Adam / RMSprop over the flat parameter space (tfl_optim_step): at most three launches
 void optim_step(hipStream_t st, const OptimPtrs& p, const long long* d_off, int ntens, long long total, double* d_partials, float* m,
-                float* v, long long* d_t, const OptimArgs& c);
+                float* v, long long* d_t, const OptimArgs& c, const int* d_guard);      // d_guard: NULL, or a device word read at run time (set: nothing is written)
 void optim_fill(hipStream_t st, float* p, long long n, float val);
 
 // conv2d_mfma.hip (2-D default topology: 16 channels, k = 3; one MFMA = one tap x four input channels)

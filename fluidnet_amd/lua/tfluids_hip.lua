@@ -75,6 +75,7 @@ int tfl_fluidCriterion(tfl_ctx* ctx, const tfl_tensor* pPred, const tfl_tensor* 
                        const tfl_tensor* UTarget, const tfl_tensor* flags, const tfl_tensor* weight, double pLambda,
                        double uLambda, double divLambda, int sizeAverage, int is3D, double* loss, const tfl_tensor* gradP,
                        const tfl_tensor* gradU, float* workspace, int64_t workspace_floats);
+int tfl_closure_fold(tfl_ctx* ctx, const double* loss4, double* sums5, int32_t* guard, int longTerm, double errLimit);
 int tfl_velocityUpdateForward(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
                               const tfl_tensor* p, int is3D);
 int tfl_vorticityConfinement(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
@@ -198,6 +199,8 @@ typedef struct {
 tfl_optim* tfl_optim_create(tfl_ctx* ctx, tfl_model* model, const tfl_optim_config* config);
 int tfl_optim_step(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights, float* const* d_biases,
                    float* const* d_gradWeights, float* const* d_gradBiases);
+int tfl_optim_step_guarded(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights, float* const* d_biases,
+                           float* const* d_gradWeights, float* const* d_gradBiases, const int32_t* d_guard);
 int tfl_optim_set_config(tfl_ctx* ctx, tfl_optim* opt, const tfl_optim_config* config);
 int64_t tfl_optim_steps(tfl_ctx* ctx, tfl_optim* opt);
 int64_t tfl_optim_get_state(tfl_ctx* ctx, tfl_optim* opt, float* d_m, float* d_v);

@@ -65,9 +65,11 @@ class _Fused:
             lib, ctx = tfluids._context(self.net.weights[0])
             tfluids._call(lib, ctx, lib.tfl_optim_set_config(ctx, self._opt, ctypes.byref(self._cconfig())))
 
-    def step(self):
+    def step(self, guard=None):
         """clip, decay, update and refresh the native model from the parameters' .grad, in place, on the current stream; the
-        .grad tensors hold the clipped and decayed gradients afterwards"""
+        .grad tensors hold the clipped and decayed gradients afterwards. guard (tfl_optim_step_guarded): an int32 device tensor
+        the update kernels read when they run; where its first word is non-zero the step changes nothing (parameters, moments,
+        gradients and the counter stay; the refresh rebuilds the same weight forms)"""
         net = self.net
         params = list(net.weights) + list(net.biases)
         for p in params:
@@ -76,9 +78,13 @@ class _Fused:
             if p.grad.dtype != torch.float32 or not p.grad.is_contiguous() or not p.is_contiguous() or p.grad.device != p.device:
                 raise TfluidsError("optim.step: parameters and gradients must be contiguous float32 tensors on one device")
         lib, ctx = tfluids._context(net.weights[0])
-        tfluids._call(lib, ctx, lib.tfl_optim_step(
+        if guard is not None and not (torch.is_tensor(guard) and guard.dtype == torch.int32 and guard.numel() >= 1 and
+                                      guard.is_contiguous() and guard.device == self._dev):
+            raise TfluidsError("optim.step: guard must be a contiguous int32 tensor on the parameters' device")
+        tfluids._call(lib, ctx, lib.tfl_optim_step_guarded(
             ctx, self._opt, _ptr_array(list(net.weights)), _ptr_array(list(net.biases)),
-            _ptr_array([p.grad for p in net.weights]), _ptr_array([p.grad for p in net.biases])))
+            _ptr_array([p.grad for p in net.weights]), _ptr_array([p.grad for p in net.biases]),
+            None if guard is None else ctypes.c_void_p(guard.data_ptr())))
         net._stepped_on_device()
 
     def zero_grad(self):

@@ -319,6 +319,32 @@ def calcPUTargets(conf, mconf, batch, model=None):
     tfluids.setWallBcsForward(UTarget, flags)
 
 
+def dataAugmentation(conf, mconf, batch):
+    """tfluids.dataAugmentation, simulate.lua:374-414: buoyancy, gravity and vorticity confinement added to batch["UDiv"] in
+    place (any batch size), before calcPUTargets projects it. As in the reference the buoyancy takes mconf["gravity"] as it is
+    (only buoyancyScale > 0 is read, :392-395), the gravity force takes it times -getDx / 4 * gravityScale."""
+    if mconf.get("trainTargetSource") == "manta":
+        raise TfluidsError("target source is manta, this method should not be called!")
+    # pDiv is just the previous frame's pressure: it is not augmented
+    UDiv, flags = batch["UDiv"], batch["flags"]
+    density = batch.get("density")
+    if density is None:
+        density = batch.get("densityDiv")
+    # external forces: buoyancy
+    if density is not None and (mconf.get("buoyancyScale") or 0) > 0:
+        tfluids._check(mconf.get("gravity") is not None, "dataAugmentation: buoyancy needs mconf.gravity")
+        tfluids._check(torch.is_tensor(density), "density while training should be a tensor")
+        tfluids.addBuoyancy(UDiv, flags, density, _gravity(mconf), mconf["dt"])
+    # external forces: gravity
+    if (mconf.get("gravityScale") or 0) > 0:
+        tfluids._check(mconf.get("gravity") is not None, "dataAugmentation: gravity needs mconf.gravity")
+        s = _f32((-tfluids.getDx(flags) / 4) * mconf["gravityScale"])      # gravity:mul(...) on a float tensor
+        tfluids.addGravity(UDiv, flags, [_f32(v) * s for v in _gravity(mconf)], mconf["dt"])
+    # external forces: vorticity confinement
+    if (mconf.get("vorticityConfinementAmp") or 0) > 0:
+        tfluids.vorticityConfinement(UDiv, flags, tfluids.getDx(flags) * mconf["vorticityConfinementAmp"])
+
+
 _dead_plans = []      # plans whose tensors have died, waiting for a safe moment
 _WALL_PLANS = os.environ.get("TFL_WALL_PLAN", "1") != "0"
 

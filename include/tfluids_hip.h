@@ -184,6 +184,15 @@ int tfl_fluidCriterion(tfl_ctx* ctx, const tfl_tensor* pPred, const tfl_tensor* 
                        double uLambda, double divLambda, int sizeAverage, int is3D, double* loss, const tfl_tensor* gradP,
                        const tfl_tensor* gradU, float* workspace, int64_t workspace_floats);
 
+/* The loss bookkeeping of the training closure (lib/run_epoch.lua:216-229, 287-291) without its host read. loss4: what
+ * tfl_fluidCriterion wrote; sums5 (DEVICE memory, 5 doubles, zeroed by the caller at the start of an epoch) = the running sums
+ * {pLoss, uLoss, divLoss, total, long-term total}; guard: one DEVICE word, zeroed by the caller.
+ *   longTerm == 0 (the main pass):  sums5[0] += loss4[0]; sums5[1] += loss4[1]; sums5[2] += loss4[2]; sums5[3] += loss4[3]
+ *   longTerm != 0:                  sums5[3] += loss4[3]; sums5[4] += loss4[3]
+ * plain fp64 adds in this order, then *guard = 1 if loss4[3] is NaN or > errLimit (the reference: 1e9); a set guard is never
+ * cleared here. One launch of one thread on the context's stream; no host read, no synchronisation: capturable. */
+int tfl_closure_fold(tfl_ctx* ctx, const double* loss4, double* sums5, int32_t* guard, int longTerm, double errLimit);
+
 /* init.lua:346 -> third_party/tfluids.cc:1072-1156 | tfluids.cu:1111-1195 (in place on U). */
 int tfl_velocityUpdateForward(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
                               const tfl_tensor* p, int is3D);
@@ -555,6 +564,13 @@ tfl_optim* tfl_optim_create(tfl_ctx* ctx, tfl_model* model, const tfl_optim_conf
  * The same inputs and state give the same bits on every call. */
 int tfl_optim_step(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights, float* const* d_biases,
                    float* const* d_gradWeights, float* const* d_gradBiases);
+/* tfl_optim_step whose update kernels read *d_guard (a DEVICE word: tfl_closure_fold's) when they RUN: where it is non-zero they
+ * write nothing -- parameters, moments, gradients and the step counter stay as they are -- and the refresh that follows rebuilds
+ * the native model's weight forms from the unchanged parameters, i.e. the same forms. The clip's norm launch and the refresh
+ * run either way, so the call is the same sequence of launches whatever the word holds and can be captured. d_guard == NULL is
+ * tfl_optim_step itself. */
+int tfl_optim_step_guarded(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights, float* const* d_biases,
+                           float* const* d_gradWeights, float* const* d_gradBiases, const int32_t* d_guard);
 /* New hyper-parameters from the next step on; the method and the shapes are fixed (a changed method is TFL_EINVAL). */
 int tfl_optim_set_config(tfl_ctx* ctx, tfl_optim* opt, const tfl_optim_config* config);
 /* The step counter t (reads it back: synchronises the stream; for logging). -1 on error. */
