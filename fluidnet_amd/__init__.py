@@ -8,7 +8,8 @@
   fluidnet_amd.optim      Adam / RMSprop: gradient clip + lib/adam.lua / lib/rmsprop.lua + weight refresh over tfl_optim_step
   fluidnet_amd.criterion  nn.FluidCriterion (torch/lib/modules/fluid_criterion.lua) over tfl_fluidCriterion
   fluidnet_amd.run_epoch  the training closure of torch/lib/run_epoch.lua (long-term divergence pass included) as one call
-  fluidnet_amd.dist       z-slab decomposition across GPUs: halo exchange + 1 all-reduce per step (RCCL)
+  fluidnet_amd.dist       z-slab decomposition across GPUs: halo exchange + 1 all-reduce per step (RCCL); the transports that
+                          data-parallel training (optim.step(comm=...), run_epoch.Closure(comm=...)) reduces its gradients over
   fluidnet_amd.csrc/      hand-written HIP kernels for gfx950 + the C ABI (include/tfluids_hip.h)
 """
 from . import tfluids  # noqa: F401
@@ -21,5 +22,6 @@ from .simulate import calcPUTargets, dataAugmentation  # noqa: F401  (the traini
 from .train import ProjectionNet  # noqa: F401  (the projection net as an nn.Module: forward with a tape, parameter gradients)
 from . import optim  # noqa: F401  (optim.Adam / optim.RMSprop: clip + update + weight refresh as one device call)
 from . import run_epoch  # noqa: F401  (run_epoch.plan_batch / Closure / run_epoch: one call for a training mini-batch)
+from . import dist  # noqa: F401  (transports: DistComm / RcclComm / ThreadComm; the z-slab step; run_virtual_closures)
 from . import modules  # noqa: F401  (the tfluids nn.Modules as torch.nn.Modules with autograd)
 from ._lib import TfluidsError  # noqa: F401

@@ -178,6 +178,13 @@ SIGNATURES = {
     "tfl_optim_steps": (_c.c_int64, [_c.c_void_p, _c.c_void_p]),
     "tfl_optim_get_state": (_c.c_int64, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "tfl_optim_destroy": (None, [_c.c_void_p, _c.c_void_p]),
+    "tfl_optim_reduce_doubles": (_c.c_int64, [_c.c_void_p, _c.c_void_p]),
+    "tfl_optim_step_reduced": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
+                                          _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p), _c.c_void_p, _c.POINTER(tfl_comm),
+                                          _c.c_int32, _c.c_void_p, _c.c_int64]),
+    "tfl_optim_reduced_guard": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "tfl_optim_sync_parameters": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
+                                             _c.POINTER(tfl_comm), _c.c_int32, _c.c_void_p, _c.c_int64]),
     "tfl_set_dx_override": (_c.c_int, [_c.c_void_p, _c.c_float]),
     "tfl_velocityDivergenceBackward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int, _T]),
     "tfl_velocityUpdateBackward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _T, _c.c_int, _T]),

@@ -6,6 +6,10 @@
 // element in fp32 in the reference's operation order, and k_optim_advance moves the step counter -- a kernel, so that a captured
 // step advances on replay. With a guard word (tfl_optim_step_guarded) the update and the advance read it when they run and,
 // where it is set, write nothing: parameters, moments and the counter stay as they are.
+// The data-parallel step (tfl_optim_step_reduced) puts three things around that: k_optim_pack widens the gradients and the guard
+// into the caller's fp64 reduce buffer, the transport sums it over the ranks, and k_optim_unpack_norm -- k_optim_norm with the
+// average in front: (float)(sum / world), one division, one rounding -- writes the averaged gradients back and leaves the same
+// partials at the same places (k_optim_unpack where there is no clip). Every output element has one writer.
 #include <hip/hip_runtime.h>
 
 #include "tfl_host.hpp"
@@ -83,6 +87,74 @@ __global__ __launch_bounds__(kOptimThreads) void k_optim_update(OptimPtrs p, con
   p.x[t][e] = x;
 }
 
+// flat element i < total -> slot i of the reduce buffer (what: 0 the gradient, 1 the parameter, 2 zero); slot total = the guard
+// as 0 / 1; the reserved slots behind it = 0. One thread per slot.
+__global__ __launch_bounds__(kOptimThreads) void k_optim_pack(OptimPtrs p, const long long* __restrict__ off, int ntens, long long total,
+                                                             const int* __restrict__ guard, double* __restrict__ out, int what) {
+  __shared__ long long s_off[kOptimMaxTensors + 1];
+  for (int i = threadIdx.x; i <= ntens; i += kOptimThreads) s_off[i] = off[i];
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * kOptimThreads + threadIdx.x;
+  if (i >= total + kOptimReduceTail) return;
+  double val = 0.0;
+  if (i < total) {
+    if (what != 2) {
+      const int t = optim_tensor_of(s_off, ntens, i);
+      val = (double)(what == 0 ? p.g[t][i - s_off[t]] : p.x[t][i - s_off[t]]);
+    }
+  } else if (i == total) val = (guard && *guard != 0) ? 1.0 : 0.0;
+  out[i] = val;
+}
+
+// k_optim_norm over the averaged gradients, which it writes first: the chunks, the tree and the places of the partials are
+// k_optim_norm's, so the sum the update forms is the one it would form from these gradient floats. A set reduced guard
+// (r[total] != 0) keeps the gradient arrays as they are.
+__global__ __launch_bounds__(kOptimThreads) void k_optim_unpack_norm(OptimPtrs p, const long long* __restrict__ off, int ntens, long long total,
+                                                                    const double* __restrict__ r, double world,
+                                                                    double* __restrict__ partials, int* __restrict__ rguard) {
+  __shared__ long long s_off[kOptimMaxTensors + 1];
+  __shared__ double red[kOptimThreads];
+  for (int i = threadIdx.x; i <= ntens; i += kOptimThreads) s_off[i] = off[i];
+  __syncthreads();
+  const bool skip = r[total] != 0.0;
+  long long lo, hi;
+  optim_chunk(total, gridDim.x, blockIdx.x, &lo, &hi);
+  double s = 0.0;
+  for (long long i = lo + threadIdx.x; i < hi; i += kOptimThreads) {
+    const int t = optim_tensor_of(s_off, ntens, i);
+    const float gf = (float)(r[i] / world);
+    if (!skip) p.g[t][i - s_off[t]] = gf;
+    const double g = (double)gf;
+    s += g * g;
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = kOptimThreads / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+  if (threadIdx.x == 0 && blockIdx.x == 0) *rguard = skip ? 1 : 0;
+}
+
+// slot i -> flat element i of the gradients (to_params: of the parameters), one thread each; rguard (NULL: none, nothing skips)
+// receives the reduced guard
+__global__ __launch_bounds__(kOptimThreads) void k_optim_unpack(OptimPtrs p, const long long* __restrict__ off, int ntens, long long total,
+                                                               const double* __restrict__ r, double world, int* __restrict__ rguard,
+                                                               int to_params) {
+  __shared__ long long s_off[kOptimMaxTensors + 1];
+  for (int i = threadIdx.x; i <= ntens; i += kOptimThreads) s_off[i] = off[i];
+  __syncthreads();
+  const bool skip = rguard && r[total] != 0.0;
+  const long long i = (long long)blockIdx.x * kOptimThreads + threadIdx.x;
+  if (i == 0 && rguard) *rguard = skip ? 1 : 0;
+  if (i >= total || skip) return;
+  const int t = optim_tensor_of(s_off, ntens, i);
+  const float val = (float)(r[i] / world);
+  if (to_params) p.x[t][i - s_off[t]] = val;
+  else p.g[t][i - s_off[t]] = val;
+}
+
 __global__ void k_optim_advance(long long* t, const int* __restrict__ guard) {
   if (guard && *guard) return;
   *t += 1;
@@ -94,9 +166,9 @@ __global__ __launch_bounds__(kOptimThreads) void k_optim_fill(float* p, long lon
 }  // namespace
 
 void optim_step(hipStream_t st, const OptimPtrs& p, const long long* d_off, int ntens, long long total, double* d_partials, float* m,
-                float* v, long long* d_t, const OptimArgs& c, const int* d_guard) {
+                float* v, long long* d_t, const OptimArgs& c, const int* d_guard, bool norm_done) {
   const bool clip = c.threshold > 0.0;
-  if (clip) {
+  if (clip && !norm_done) {
     TFL_TIMED("k_optim_norm", st);
     hipLaunchKernelGGL(k_optim_norm, dim3(kOptimNormBlocks), dim3(kOptimThreads), 0, st, p, d_off, ntens, total, d_partials);
   }
@@ -108,6 +180,25 @@ void optim_step(hipStream_t st, const OptimPtrs& p, const long long* d_off, int 
   }
   TFL_TIMED("k_optim_advance", st);
   hipLaunchKernelGGL(k_optim_advance, dim3(1), dim3(1), 0, st, d_t, d_guard);
+}
+void optim_pack(hipStream_t st, const OptimPtrs& p, const long long* d_off, int ntens, long long total, const int* d_guard,
+                double* d_reduce, int what) {
+  TFL_TIMED("k_optim_pack", st);
+  const unsigned nb = (unsigned)((total + kOptimReduceTail + kOptimThreads - 1) / kOptimThreads);
+  hipLaunchKernelGGL(k_optim_pack, dim3(nb), dim3(kOptimThreads), 0, st, p, d_off, ntens, total, d_guard, d_reduce, what);
+}
+void optim_unpack(hipStream_t st, const OptimPtrs& p, const long long* d_off, int ntens, long long total, const double* d_reduce,
+                  int world, double* d_partials, int* d_rguard, bool to_params) {
+  if (d_partials) {
+    TFL_TIMED("k_optim_unpack_norm", st);
+    hipLaunchKernelGGL(k_optim_unpack_norm, dim3(kOptimNormBlocks), dim3(kOptimThreads), 0, st, p, d_off, ntens, total, d_reduce,
+                       (double)world, d_partials, d_rguard);
+    return;
+  }
+  TFL_TIMED("k_optim_unpack", st);
+  const unsigned nb = (unsigned)((total + kOptimThreads - 1) / kOptimThreads);
+  hipLaunchKernelGGL(k_optim_unpack, dim3(nb), dim3(kOptimThreads), 0, st, p, d_off, ntens, total, d_reduce, (double)world, d_rguard,
+                     to_params ? 1 : 0);
 }
 void optim_fill(hipStream_t st, float* p, long long n, float val) {
   if (n < 1) return;

@@ -468,7 +468,16 @@ void refresh_pack(hipStream_t st, const RefreshSrc& src, const PackJob* d_jobs, 
 void refresh_pack16(hipStream_t st, const RefreshSrc& src, void* const* wfrag16, float* d_post, float* tail_pack);
 // optim.hip: clip + weight decay + Adam / RMSprop over the flat parameter space (tfl_optim_step): at most three launches
 void optim_step(hipStream_t st, const OptimPtrs& p, const long long* d_off, int ntens, long long total, double* d_partials, float* m,
-                float* v, long long* d_t, const OptimArgs& c, const int* d_guard);      // d_guard: NULL, or a device word read at run time (set: nothing is written)
+                float* v, long long* d_t, const OptimArgs& c, const int* d_guard,       // d_guard: NULL, or a device word read at run time (set: nothing is written)
+                bool norm_done = false);      // the partials are already in place (optim_unpack left them): no norm launch
+// the data-parallel step's two launches around the all-reduce (tfl_optim_step_reduced). pack: slot i of d_reduce [total +
+// kOptimReduceTail] = flat element i (what: 0 the gradients, 1 the parameters, 2 zeros), slot total = (*d_guard != 0).
+// unpack: flat element i = (float)(d_reduce[i] / world) into the gradients (to_params: the parameters), *d_rguard (may be NULL:
+// nothing skips) = d_reduce[total] != 0, which where set leaves the arrays alone; d_partials non-NULL: also k_optim_norm's partials
+void optim_pack(hipStream_t st, const OptimPtrs& p, const long long* d_off, int ntens, long long total, const int* d_guard,
+                double* d_reduce, int what);
+void optim_unpack(hipStream_t st, const OptimPtrs& p, const long long* d_off, int ntens, long long total, const double* d_reduce,
+                  int world, double* d_partials, int* d_rguard, bool to_params);
 void optim_fill(hipStream_t st, float* p, long long n, float val);
 
 // conv2d_mfma.hip (2-D default topology: 16 channels, k = 3; one MFMA = one tap x four input channels)

@@ -215,6 +215,8 @@ TFL_HD inline M16Src m16_tail_src(int d) {
 // ---- the optimiser's flat parameter space: tensor 2 l = layer l's weight, 2 l + 1 = its bias, off[] their prefix offsets -----
 constexpr int kOptimMaxTensors = 2 * kRefreshMaxLayers;
 constexpr int kOptimNormBlocks = 64, kOptimThreads = 256;
+// the reduce buffer of the data-parallel step: slot i = flat element i, slot total = the guard, then reserved slots (zeros)
+constexpr int kOptimReduceTail = 8;
 struct OptimPtrs { float* x[kOptimMaxTensors]; float* g[kOptimMaxTensors]; };
 // the hyper-parameters of one step, by value: fp32 where the reference hands Torch a scalar for an fp32 tensor operation
 // (1 - beta formed in double first), fp64 where it computes in Lua numbers. method 0 = Adam, 1 = RMSprop (b2 / omb2 = alpha / 1 - alpha)

@@ -562,3 +562,92 @@ def run_virtual_ranks(sims, steps):
     torch.cuda.synchronize(dev)
     if errs:
         raise errs[0]
+
+
+class _TurnBarrier:
+    """A Hub's barrier for virtual ranks that share ONE library context: a rank holds `turn` whenever it runs and gives it up
+    only while it waits here, so between two barriers the ranks run one after the other, in no fixed order, never side by side.
+    (The context of tfluids._context is one per device and not made for two threads at once; the z-slab ranks above avoid that
+    with a context each, which a training closure -- many calls through the shared one -- cannot.)"""
+
+    def __init__(self, barrier, turn, timeout_s):
+        self.barrier, self.turn, self.timeout_s = barrier, turn, timeout_s
+
+    def wait(self):
+        self.turn.release()
+        try:
+            return self.barrier.wait(self.timeout_s)      # a rank that never arrives breaks the barrier for all after timeout_s
+        finally:
+            self.turn.acquire()
+
+    def abort(self):
+        self.barrier.abort()
+
+
+def run_virtual(hub, works, timeout_s=120.0):
+    """One thread per rank of a ThreadComm.Hub, works[r]() in rank r's; returns their results in rank order. The ranks take
+    turns (see _TurnBarrier). An exception in one rank aborts the hub's barrier, so the others leave their collectives with an
+    error instead of waiting; the threads are joined with a time limit, and the first error, by rank, is raised."""
+    if len(works) != hub.world:
+        raise TfluidsError("run_virtual: %d callables for a hub of %d ranks" % (len(works), hub.world))
+    dev = torch.cuda.current_device()
+    turn = threading.Lock()
+    plain = hub.barrier
+    hub.barrier = _TurnBarrier(plain, turn, timeout_s)
+    out, errs = [None] * hub.world, [None] * hub.world
+
+    def run(r):
+        with turn:
+            try:
+                torch.cuda.set_device(dev)
+                out[r] = works[r]()
+            except Exception as e:   # noqa: BLE001
+                errs[r] = e
+                plain.abort()
+
+    ts = [threading.Thread(target=run, args=(r,), daemon=True) for r in range(hub.world)]
+    try:
+        for t in ts:
+            t.start()
+        for t in ts:
+            t.join(timeout_s)
+        if any(t.is_alive() for t in ts):
+            plain.abort()
+            for t in ts:
+                t.join(5.0)
+            raise TfluidsError("run_virtual: a rank did not finish within %.0f s" % timeout_s)
+    finally:
+        hub.barrier = plain
+        if plain.broken:
+            hub.barrier = threading.Barrier(hub.world)      # (a broken barrier stays broken: the hub gets a fresh one)
+    torch.cuda.synchronize(dev)
+    first = [e for e in errs if e is not None and not isinstance(e, threading.BrokenBarrierError)] or [e for e in errs if e is not None]
+    if first:
+        raise first[0]
+    return out
+
+
+def run_virtual_closures(closures, batches_per_rank, steps=None, rngs=None, training=True, timeout_s=120.0):
+    """Data-parallel training on VIRTUAL ranks: closures[r] (run_epoch.Closure with a ThreadComm of one Hub as its comm) runs
+    run_epoch over batches_per_rank[r] -- its first `steps` batches where given -- in a thread of its own, modelled on
+    run_virtual_ranks. rngs[r]: rank r's plan rng (None: run_epoch's default). Returns run_epoch's result of every rank, in rank
+    order; an error in one rank (a NaN batch, say: every rank raises the same) ends all of them and is raised here."""
+    from . import run_epoch as _re
+    if not closures or any(getattr(c, "comm", None) is None or not isinstance(c.comm, ThreadComm) for c in closures):
+        raise TfluidsError("run_virtual_closures: every closure needs a ThreadComm as its comm")
+    hub = closures[0].comm.hub
+    if any(c.comm.hub is not hub for c in closures) or sorted(c.comm.rank for c in closures) != list(range(hub.world)):
+        raise TfluidsError("run_virtual_closures: the closures' comms must be the ranks 0 .. world - 1 of one hub")
+    order = sorted(range(len(closures)), key=lambda i: closures[i].comm.rank)
+
+    def work(i):
+        batches = list(batches_per_rank[i])
+        if steps is not None:
+            batches = batches[:int(steps)]
+        return lambda: _re.run_epoch(closures[i], batches, None if rngs is None else rngs[i], training)
+
+    res = run_virtual(hub, [work(i) for i in order], timeout_s)
+    back = [None] * len(closures)
+    for r, i in enumerate(order):
+        back[i] = res[r]
+    return back

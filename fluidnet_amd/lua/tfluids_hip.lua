@@ -308,6 +308,13 @@ tfl_rccl_comm* tfl_rccl_comm_wrap(tfl_ctx* ctx, void* nccl_comm, int rank, int w
 const tfl_comm* tfl_rccl_comm_callbacks(tfl_rccl_comm* comm);
 int tfl_rccl_comm_set_inline(tfl_rccl_comm* comm, int on);
 void tfl_rccl_comm_destroy(tfl_ctx* ctx, tfl_rccl_comm* comm);
+int64_t tfl_optim_reduce_doubles(tfl_ctx* ctx, tfl_optim* opt);
+int tfl_optim_step_reduced(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights, float* const* d_biases,
+                           float* const* d_gradWeights, float* const* d_gradBiases, const int32_t* d_guard,
+                           const tfl_comm* comm, int32_t world, double* d_reduce, int64_t reduce_doubles);
+int tfl_optim_reduced_guard(tfl_ctx* ctx, tfl_optim* opt, int32_t* d_out);
+int tfl_optim_sync_parameters(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights, float* const* d_biases,
+                              const tfl_comm* comm, int32_t rank, double* d_reduce, int64_t reduce_doubles);
 ]]
 -- END generated cdef
 
@@ -735,6 +742,17 @@ function Optim:steps() return tonumber(lib.tfl_optim_steps(ctx, self.handle)) en
 function Optim:state(m, v)
   return tonumber(lib.tfl_optim_get_state(ctx, self.handle, m and ffi.cast('float*', torch.data(m)) or nil,
                                           v and ffi.cast('float*', torch.data(v)) or nil))
+end
+-- hip.optimStepReduced(opt, weights, biases, gradWeights, gradBiases, guard, callbacks, world, reduce): the data-parallel step
+-- (tfl_optim_step_reduced): the gradients averaged over `world` ranks by ONE all-reduce inside the step. guard: an IntTensor on
+-- the device or nil; callbacks: a const tfl_comm* (lib.tfl_rccl_comm_callbacks(comm), as hip.Slab keeps it) or nil = the guarded
+-- step; reduce: a CudaDoubleTensor of at least hip.optimReduceDoubles(opt) elements, the caller's and kept between steps.
+function M.optimReduceDoubles(opt) return tonumber(lib.tfl_optim_reduce_doubles(ctx, opt.handle)) end
+function M.optimStepReduced(opt, weights, biases, gradWeights, gradBiases, guard, callbacks, world, reduce)
+  check(lib.tfl_optim_step_reduced(ctx, opt.handle, devptrs(weights, 'float*'), devptrs(biases, 'float*'), devptrs(gradWeights, 'float*'),
+                                   devptrs(gradBiases, 'float*'), guard and ffi.cast('const int32_t*', torch.data(guard)) or nil,
+                                   callbacks, world or 1, reduce and ffi.cast('double*', torch.data(reduce)) or nil,
+                                   reduce and reduce:nElement() or 0))
 end
 
 -- ---- tfluids.simulate as ONE native call (lib/simulate.lua:175-327 = fluidnet_amd/csrc/simulate.cpp) -----------------

@@ -12,6 +12,12 @@ net.push_parameters() before using the net on another device.
     net = ProjectionNet(model).train()
     opt = fluidnet_amd.optim.from_mconf(net, mconf)        # or Adam(net, learningRate=..., gradNormThreshold=1)
     loss.backward(); opt.step(); opt.zero_grad()
+
+Data parallel (tfl_optim_step_reduced): N ranks, each with its own net, optimiser and mini-batch, and a transport of
+fluidnet_amd.dist between them. opt.step(guard, comm) averages the gradients over the ranks inside the step -- one all-reduce of
+P + 1 doubles, g = float(sum of the ranks' g in fp64 / N) -- so that every rank takes the step of the N-fold batch and all end
+with the same bits; opt.sync_parameters(comm) first gives every rank rank 0's parameters. A guard set on one rank holds the
+step back on all of them (opt.reduced_guard()).
 """
 import ctypes
 
@@ -29,6 +35,16 @@ _DEFAULTS = {
 }
 
 
+def comm_world(comm):
+    """the number of ranks behind a transport of fluidnet_amd.dist (ThreadComm keeps it on its hub)"""
+    world = getattr(comm, "world", None)
+    if world is None and getattr(comm, "hub", None) is not None:
+        world = comm.hub.world
+    if world is None or int(world) < 1:
+        raise TfluidsError("optim: the transport does not say how many ranks it joins (comm.world)")
+    return int(world)
+
+
 class _Fused:
     method = None
 
@@ -38,6 +54,7 @@ class _Fused:
         self.net = net
         self.config = dict(_DEFAULTS[self.method])
         self._opt = None
+        self._reduce = None      # the fp64 reduce buffer of the data-parallel step, as the float tensor a transport binds
         self.set_config(gradNormThreshold=gradNormThreshold, **config)
         p = net.weights[0]
         self._lib, ctx = tfluids._context(p)
@@ -65,11 +82,37 @@ class _Fused:
             lib, ctx = tfluids._context(self.net.weights[0])
             tfluids._call(lib, ctx, lib.tfl_optim_set_config(ctx, self._opt, ctypes.byref(self._cconfig())))
 
-    def step(self, guard=None):
+    def _reduce_for(self, comm):
+        """(pointer, doubles) of the reduce buffer, with comm bound to it: dist._CommBase resolves the pointers its callbacks
+        receive inside the tensor it is bound to"""
+        if not hasattr(comm, "struct"):
+            raise TfluidsError("optim: comm must be a transport of fluidnet_amd.dist (DistComm, RcclComm, ThreadComm)")
+        lib, ctx = tfluids._context(self.net.weights[0])
+        if self._reduce is None:
+            n = int(lib.tfl_optim_reduce_doubles(ctx, self._opt))
+            if n < 1:
+                raise TfluidsError("tfl_optim_reduce_doubles failed")
+            self._reduce = torch.zeros(2 * n, dtype=torch.float32, device=self._dev)
+        comm.bind(self._reduce)
+        comm.error = None
+        return ctypes.c_void_p(self._reduce.data_ptr()), self._reduce.numel() // 2
+
+    @staticmethod
+    def _comm_call(lib, ctx, comm, rc):
+        if rc != 0:
+            if comm.error is not None:
+                raise comm.error
+            raise TfluidsError(lib.tfl_last_error(ctx).decode())
+
+    def step(self, guard=None, comm=None):
         """clip, decay, update and refresh the native model from the parameters' .grad, in place, on the current stream; the
         .grad tensors hold the clipped and decayed gradients afterwards. guard (tfl_optim_step_guarded): an int32 device tensor
         the update kernels read when they run; where its first word is non-zero the step changes nothing (parameters, moments,
-        gradients and the counter stay; the refresh rebuilds the same weight forms)"""
+        gradients and the counter stay; the refresh rebuilds the same weight forms).
+        comm (tfl_optim_step_reduced): a DistComm, RcclComm or ThreadComm; every rank of its world calls step() together. The
+        gradients are summed over the ranks in fp64 by ONE all-reduce and divided by the world size, rounded once; the guards
+        travel with them, and a guard set on any rank holds every rank's step back (reduced_guard()). The .grad tensors hold the
+        averaged (clipped, decayed) gradients afterwards -- under a set reduced guard, the local ones still."""
         net = self.net
         params = list(net.weights) + list(net.biases)
         for p in params:
@@ -81,10 +124,38 @@ class _Fused:
         if guard is not None and not (torch.is_tensor(guard) and guard.dtype == torch.int32 and guard.numel() >= 1 and
                                       guard.is_contiguous() and guard.device == self._dev):
             raise TfluidsError("optim.step: guard must be a contiguous int32 tensor on the parameters' device")
-        tfluids._call(lib, ctx, lib.tfl_optim_step_guarded(
-            ctx, self._opt, _ptr_array(list(net.weights)), _ptr_array(list(net.biases)),
-            _ptr_array([p.grad for p in net.weights]), _ptr_array([p.grad for p in net.biases]),
-            None if guard is None else ctypes.c_void_p(guard.data_ptr())))
+        args = (ctx, self._opt, _ptr_array(list(net.weights)), _ptr_array(list(net.biases)),
+                _ptr_array([p.grad for p in net.weights]), _ptr_array([p.grad for p in net.biases]),
+                None if guard is None else ctypes.c_void_p(guard.data_ptr()))
+        if comm is None:
+            tfluids._call(lib, ctx, lib.tfl_optim_step_guarded(*args))
+        else:
+            buf, n = self._reduce_for(comm)
+            self._comm_call(lib, ctx, comm, lib.tfl_optim_step_reduced(*args, ctypes.byref(comm.struct), comm_world(comm), buf, n))
+        net._stepped_on_device()
+
+    def reduced_guard(self, out=None):
+        """the guard word the last step(comm=...) acted on -- non-zero: some rank's guard was set and no rank stepped -- as an
+        int32 device tensor [1] (out: written in place). A copy enqueued on the current stream; nothing waits."""
+        if out is None:
+            out = torch.empty(1, dtype=torch.int32, device=self._dev)
+        if not (torch.is_tensor(out) and out.dtype == torch.int32 and out.numel() >= 1 and out.is_contiguous() and out.device == self._dev):
+            raise TfluidsError("optim.reduced_guard: out must be a contiguous int32 tensor on the parameters' device")
+        lib, ctx = tfluids._context(self.net.weights[0])
+        tfluids._call(lib, ctx, lib.tfl_optim_reduced_guard(ctx, self._opt, ctypes.c_void_p(out.data_ptr())))
+        return out
+
+    def sync_parameters(self, comm):
+        """rank 0's parameters into the parameters of every rank of comm's world, bit for bit (tfl_optim_sync_parameters: one
+        all-reduce), and the native model refreshed from them. Collective. The moments and the step counter stay."""
+        net = self.net
+        for p in net.parameters():
+            if not p.is_contiguous() or p.dtype != torch.float32:
+                raise TfluidsError("optim.sync_parameters: parameters must be contiguous float32 tensors")
+        lib, ctx = tfluids._context(net.weights[0])
+        buf, n = self._reduce_for(comm)
+        self._comm_call(lib, ctx, comm, lib.tfl_optim_sync_parameters(
+            ctx, self._opt, _ptr_array(list(net.weights)), _ptr_array(list(net.biases)), ctypes.byref(comm.struct), int(comm.rank), buf, n))
         net._stepped_on_device()
 
     def zero_grad(self):

@@ -17,6 +17,11 @@ step reads that word when it runs (tfl_optim_step_guarded: a set guard leaves pa
 What still waits for the device inside a call: tfluids.normalizePressureMean (its component labelling polls a counter), i.e.
 every configuration with lossPLambda > 0 or with non-manta targets and the long-term pass on; the PCG target source; and a
 torch.optim optimiser (below). Without those a call enqueues launches only and can be captured into a graph.
+
+Data parallel: Closure(..., comm=a transport of fluidnet_amd.dist) on every rank, each with its own net, optimiser and batches.
+Both passes of a batch accumulate into the rank's own gradients; the step at the end is the reduced step (optim.step(guard,
+comm): one all-reduce of the gradients and the guard), so N ranks with B items each take the step of the mean over N B items.
+closure.sync_parameters() first makes the ranks' parameters rank 0's; run_epoch() then returns the means over all ranks' batches.
 """
 import ctypes
 
@@ -121,19 +126,32 @@ class Closure:
     [1], sticky) live on the device; .loss and .loss_long_term hold the last call's two criterion results (float64 [4] each).
     The criterion's lambdas and net.training are back as they were when the call returns or raises.
     training=False: the same forwards and losses, no backward, no step. (The reference's evaluation epochs still run the
-    long-term pass's backward, :292-293, into gradients nobody reads; that stray backward is dropped here.)"""
+    long-term pass's backward, :292-293, into gradients nobody reads; that stray backward is dropped here.)
 
-    def __init__(self, net, criterion, optimiser, conf, mconf, errLimit=ERR_LIMIT):
+    comm: a DistComm, RcclComm or ThreadComm (fluidnet_amd.dist) joining the ranks of a data-parallel world; every rank calls the
+    closure together. Step 5 becomes the reduced step: the gradients both passes left in this rank's .grad are averaged over
+    the ranks inside it, and .guard_all (int32 [1]) receives the guard it acted on -- set on every rank once any rank's .guard is
+    set, from which batch on no rank steps. Needs a fluidnet_amd.optim optimiser: a torch.optim one is refused. The ranks may
+    draw different plans (the long-term pass on one and not on another: launches only, nothing collective in it).
+    Without a comm, .guard_all is .guard. (training=False under a comm runs nothing collective: .guard_all follows the local
+    guard.)"""
+
+    def __init__(self, net, criterion, optimiser, conf, mconf, errLimit=ERR_LIMIT, comm=None):
         if not isinstance(net, ProjectionNet):
             raise TfluidsError("run_epoch.Closure trains a ProjectionNet")
         self.net, self.criterion, self.optimiser, self.conf, self.mconf = net, criterion, optimiser, conf, mconf
         self.fused = isinstance(optimiser, _optim._Fused)
         if self.fused and optimiser.net is not net:
             raise TfluidsError("run_epoch.Closure: the optimiser steps another net")
+        if comm is not None and not self.fused:
+            raise TfluidsError("run_epoch.Closure: a comm needs a fluidnet_amd.optim optimiser -- the gradient all-reduce lives "
+                               "inside its fused step (tfl_optim_step_reduced), and a torch.optim step has no place for it")
+        self.comm = comm
         self.errLimit = float(errLimit)
         dev = net.weights[0].device
         self.sums = torch.zeros(5, dtype=torch.float64, device=dev)
         self.guard = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.guard_all = self.guard if comm is None else torch.zeros(1, dtype=torch.int32, device=dev)
         self.loss = torch.zeros(4, dtype=torch.float64, device=dev)
         self.loss_long_term = torch.zeros(4, dtype=torch.float64, device=dev)
         self.first_bad = None      # the batch index at which a poll first saw the guard set (host side: check())
@@ -142,12 +160,20 @@ class Closure:
         """a new epoch: the sums and the guard back to zero (on the stream, no synchronisation)"""
         self.sums.zero_()
         self.guard.zero_()
+        self.guard_all.zero_()
         self.first_bad = None
+
+    def sync_parameters(self):
+        """rank 0's parameters to every rank of the comm's world, bit for bit, and the native models refreshed from them
+        (optim.sync_parameters: one all-reduce). Collective; call it before the first batch."""
+        if self.comm is None:
+            raise TfluidsError("run_epoch.Closure.sync_parameters: the closure has no comm")
+        self.optimiser.sync_parameters(self.comm)
 
     def check(self, index=None):
         """reads the guard (synchronises) and raises as run_epoch.lua:216-222 when it is set; index: the batch this poll
         belongs to, named in the message and kept as .first_bad"""
-        if self.first_bad is None and int(self.guard.item()) != 0:
+        if self.first_bad is None and int(self.guard_all.item()) != 0:
             self.first_bad = -1 if index is None else int(index)
         self._raise_if_bad()
 
@@ -240,8 +266,13 @@ class Closure:
             crit.pLambda, crit.uLambda, crit.divLambda = lambdas
             net.train(was_training)
         if not training:
+            if self.comm is not None:
+                self.guard_all.copy_(self.guard)
             return
-        if self.fused:
+        if self.comm is not None:
+            self.optimiser.step(guard=self.guard, comm=self.comm)
+            self.optimiser.reduced_guard(out=self.guard_all)
+        elif self.fused:
             self.optimiser.step(guard=self.guard)
         else:
             self.check()
@@ -255,7 +286,13 @@ def run_epoch(closure, batches, rng=None, training=True):
     device ONCE, after the last batch: per batch only an asynchronous copy of the guard word into pinned host memory is
     enqueued, and the final read looks through those copies for the first batch at which the guard was set -- then it raises
     TfluidsError('criterion error is NaN or > 1e9 ...') naming that batch. (From that batch on the guarded step has left the
-    parameters alone.)"""
+    parameters alone.)
+
+    With closure.comm (data parallel) every rank calls run_epoch together. The poll copies closure.guard_all, the guard the
+    reduced step acted on, so every rank names the same first bad batch. After the last batch the five sums and the batch count
+    go through ONE all-reduce: the means are over all ranks' batches and `nbatches` is their total, the same on every rank.
+    Every rank must supply EQUALLY MANY batches (each batch is one collective step; a rank that runs out early leaves the others
+    waiting in theirs) -- this is not checked. The ranks may draw different plans."""
     rng = RandomStateRng() if rng is None else rng
     closure.reset()
     chunk, polls, n = 1024, [], 0
@@ -264,16 +301,31 @@ def run_epoch(closure, batches, rng=None, training=True):
         closure(batch, plan, training)
         if n % chunk == 0:
             polls.append(torch.zeros(chunk, dtype=torch.int32).pin_memory())
-        polls[-1][n % chunk:n % chunk + 1].copy_(closure.guard, non_blocking=True)
+        polls[-1][n % chunk:n % chunk + 1].copy_(closure.guard_all, non_blocking=True)
         n += 1
     if n == 0:
         raise TfluidsError("No batches to train / eval on!")
-    sums = closure.sums.cpu().numpy()      # the one read: it waits for the stream, so every guard copy has landed too
+    total = n
+    comm = getattr(closure, "comm", None)
+    if comm is not None:      # sums and count of every rank: one all-reduce of six doubles, then the one read
+        buf = torch.zeros(16, dtype=torch.float32, device=closure.sums.device)
+        all6 = buf.view(torch.float64)
+        all6[:5].copy_(closure.sums)
+        all6[5].fill_(float(n))
+        lib, ctx = tfluids._context(buf)      # (the transport's calls are ordered on the context's stream)
+        comm.bind(buf)
+        comm.error = None
+        if comm.struct.allreduce_sum(comm.struct.user, ctypes.c_void_p(buf.data_ptr()), 6) != 0:
+            raise comm.error if comm.error is not None else TfluidsError(lib.tfl_last_error(ctx).decode() or "comm callback failed (allreduce_sum)")
+        all6 = all6.cpu().numpy()
+        sums, total = all6[:5], int(round(float(all6[5])))
+    else:
+        sums = closure.sums.cpu().numpy()      # the one read: it waits for the stream, so every guard copy has landed too
     for i in range(n):
         if int(polls[i // chunk][i % chunk]) != 0:
             closure.first_bad = i
             break
     closure._raise_if_bad()
-    out = {name: float(sums[j] / n) for name, j in zip(_SUMS, (3, 0, 1, 2, 4))}
-    out["nbatches"] = n
+    out = {name: float(sums[j] / total) for name, j in zip(_SUMS, (3, 0, 1, 2, 4))}
+    out["nbatches"] = total
     return out

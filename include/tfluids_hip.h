@@ -904,6 +904,40 @@ const tfl_comm* tfl_rccl_comm_callbacks(tfl_rccl_comm* comm);
 int tfl_rccl_comm_set_inline(tfl_rccl_comm* comm, int on);
 void tfl_rccl_comm_destroy(tfl_ctx* ctx, tfl_rccl_comm* comm);
 
+/* ---- data-parallel training: the optimiser step with ONE gradient all-reduce inside (csrc/optim.hip) -------
+ * N ranks hold equal parameters and moments and each the gradient of its own mini-batch; the step averages the gradients over
+ * the ranks and then updates, so every rank takes the step of the N-fold batch and ends with the same bits.
+ * The reduce buffer is the CALLER's: tfl_optim_reduce_doubles() device doubles = P + 8, P the parameter count of
+ * tfl_optim_get_state: slot i < P belongs to parameter element i in that call's order, slot P to the guard, the rest is reserved
+ * (written as zeros). A transport that resolves pointers inside a bound array (fluidnet_amd/dist.py) is bound to it. */
+int64_t tfl_optim_reduce_doubles(tfl_ctx* ctx, tfl_optim* opt);
+/* comm == NULL: tfl_optim_step_guarded itself (same launches, same bits; world, d_reduce and reduce_doubles are not read).
+ * With a comm (any world >= 1, a world of one included):
+ *   pack     d_reduce[i] = (double) g[i]; d_reduce[P] = (*d_guard != 0), 0 for a NULL guard              (one launch)
+ *   reduce   ONE comm->allreduce_sum(user, d_reduce, P + 1), ordered on the context's stream; a failing callback is
+ *            TFL_EINVAL with "comm callback failed"
+ *   unpack   g[i] = (float)(d_reduce[i] / (double) world): one fp64 division, one rounding -- the whole definition of the
+ *            average; the REDUCED guard (d_reduce[P] != 0) goes into a word of the optimiser's (tfl_optim_reduced_guard).
+ *            With a clip this is the clip's norm launch (the same fp64 partials at the same places as tfl_optim_step's, so the
+ *            step that follows has the bits of tfl_optim_step_guarded on the averaged gradients); without, a launch of its own
+ *   update   tfl_optim_step_guarded's update, counter and refresh launches, reading the reduced guard
+ * i.e. at most two launches more than the guarded step of the same configuration, and one collective. Where the reduced guard
+ * is set NOTHING is written on any rank: parameters, moments, counter and the gradient arrays (which keep the rank's local
+ * gradients) stay. Otherwise the gradient arrays hold the averaged, clipped and decayed gradients afterwards. The reduced
+ * guard is not sticky: a local guard is (tfl_closure_fold), which keeps the reduced one set from that step on.
+ * No host read and no synchronisation: with a comm whose `capturable` is set the call can be captured into a graph. */
+int tfl_optim_step_reduced(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights, float* const* d_biases,
+                           float* const* d_gradWeights, float* const* d_gradBiases, const int32_t* d_guard,
+                           const tfl_comm* comm, int32_t world, double* d_reduce, int64_t reduce_doubles);
+/* Enqueues a copy of the last tfl_optim_step_reduced's reduced guard word (0 before the first) into the DEVICE word d_out. */
+int tfl_optim_reduced_guard(tfl_ctx* ctx, tfl_optim* opt, int32_t* d_out);
+/* Rank 0's parameters to every rank: d_reduce = the parameters on rank 0 and zeros elsewhere, ONE allreduce_sum of P doubles
+ * (x + 0 is exact, so the values arrive bit for bit), unpacked into the parameter arrays of every rank; then
+ * tfl_model_set_weights_device from them (its launches, its one exception, its limits). Moments and counter are not touched:
+ * call it before the first step, or where they are equal anyway. comm == NULL: the refresh alone. */
+int tfl_optim_sync_parameters(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights, float* const* d_biases,
+                              const tfl_comm* comm, int32_t rank, double* d_reduce, int64_t reduce_doubles);
+
 #ifdef __cplusplus
 }
 #endif
