@@ -8,6 +8,8 @@
   fluidnet_amd.optim      Adam / RMSprop: gradient clip + lib/adam.lua / lib/rmsprop.lua + weight refresh over tfl_optim_step
   fluidnet_amd.criterion  nn.FluidCriterion (torch/lib/modules/fluid_criterion.lua) over tfl_fluidCriterion
   fluidnet_amd.run_epoch  the training closure of torch/lib/run_epoch.lua (long-term divergence pass included) as one call
+  fluidnet_amd.data       torch/lib/data_binary.lua: the data set in a resident frame store (tfl_frames_*), mini-batches by one launch
+  fluidnet_amd.train_loop the loop of torch/fluid_net_train.lua: fit() -- epochs, last / best model files, log, resume
   fluidnet_amd.dist       z-slab decomposition across GPUs: halo exchange + 1 all-reduce per step (RCCL); the transports that
                           data-parallel training (optim.step(comm=...), run_epoch.Closure(comm=...)) reduces its gradients over
   fluidnet_amd.csrc/      hand-written HIP kernels for gfx950 + the C ABI (include/tfluids_hip.h)
@@ -23,5 +25,7 @@ from .train import ProjectionNet  # noqa: F401  (the projection net as an nn.Mod
 from . import optim  # noqa: F401  (optim.Adam / optim.RMSprop: clip + update + weight refresh as one device call)
 from . import run_epoch  # noqa: F401  (run_epoch.plan_batch / Closure / run_epoch: one call for a training mini-batch)
 from . import dist  # noqa: F401  (transports: DistComm / RcclComm / ThreadComm; the z-slab step; run_virtual_closures)
+from . import data  # noqa: F401  (data.DataBinary: the training set in a resident frame store, one launch per mini-batch)
+from . import train_loop  # noqa: F401  (train_loop.fit: epochs, best / last model files, log, resume)
 from . import modules  # noqa: F401  (the tfluids nn.Modules as torch.nn.Modules with autograd)
 from ._lib import TfluidsError  # noqa: F401

@@ -185,6 +185,12 @@ SIGNATURES = {
     "tfl_optim_reduced_guard": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "tfl_optim_sync_parameters": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_void_p),
                                              _c.POINTER(tfl_comm), _c.c_int32, _c.c_void_p, _c.c_int64]),
+    "tfl_optim_set_state": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64]),
+    "tfl_frames_create": (_c.c_void_p, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64]),
+    "tfl_frames_destroy": (None, [_c.c_void_p, _c.c_void_p]),
+    "tfl_frames_record_floats": (_c.c_int64, [_c.c_void_p]),
+    "tfl_frames_put": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "tfl_frames_gather": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.POINTER(_c.c_int32), _T, _T, _T, _T, _T, _T, _T]),
     "tfl_set_dx_override": (_c.c_int, [_c.c_void_p, _c.c_float]),
     "tfl_velocityDivergenceBackward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int, _T]),
     "tfl_velocityUpdateBackward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _T, _c.c_int, _T]),

@@ -1683,6 +1683,18 @@ int64_t tfl_optim_get_state(tfl_ctx* c, tfl_optim* o, float* d_m, float* d_v) {
   return (int64_t)o->total;
 }
 
+int tfl_optim_set_state(tfl_ctx* c, tfl_optim* o, const float* d_m, const float* d_v, int64_t steps) {
+  if (!c) return TFL_EINVAL;
+  const char* who = "optim_set_state";
+  if (!o) return fail(c, TFL_EINVAL, "%s: null optimiser", who);
+  if (steps < 0) return fail(c, TFL_EINVAL, "%s: a step count of %lld", who, (long long)steps);
+  const size_t bytes = sizeof(float) * (size_t)o->total;
+  if (d_m) HIP_TRY(c, hipMemcpyAsync(o->m, d_m, bytes, hipMemcpyDeviceToDevice, c->stream));
+  if (d_v && o->v) HIP_TRY(c, hipMemcpyAsync(o->v, d_v, bytes, hipMemcpyDeviceToDevice, c->stream));
+  tfl::optim_set_steps(c->stream, o->d_t, (long long)steps);
+  return check_launch(c, who);
+}
+
 void tfl_optim_destroy(tfl_ctx* c, tfl_optim* o) {
   (void)c;
   if (!o) return;

@@ -159,6 +159,8 @@ __global__ void k_optim_advance(long long* t, const int* __restrict__ guard) {
   if (guard && *guard) return;
   *t += 1;
 }
+// the counter of a restored checkpoint (tfl_optim_set_state): the value travels by value, so the call stays asynchronous
+__global__ void k_optim_set_steps(long long* t, long long steps) { *t = steps; }
 __global__ __launch_bounds__(kOptimThreads) void k_optim_fill(float* p, long long n, float val) {
   const long long i = (long long)blockIdx.x * kOptimThreads + threadIdx.x;
   if (i < n) p[i] = val;
@@ -199,6 +201,9 @@ void optim_unpack(hipStream_t st, const OptimPtrs& p, const long long* d_off, in
   const unsigned nb = (unsigned)((total + kOptimThreads - 1) / kOptimThreads);
   hipLaunchKernelGGL(k_optim_unpack, dim3(nb), dim3(kOptimThreads), 0, st, p, d_off, ntens, total, d_reduce, (double)world, d_rguard,
                      to_params ? 1 : 0);
+}
+void optim_set_steps(hipStream_t st, long long* d_t, long long steps) {
+  hipLaunchKernelGGL(k_optim_set_steps, dim3(1), dim3(1), 0, st, d_t, steps);
 }
 void optim_fill(hipStream_t st, float* p, long long n, float val) {
   if (n < 1) return;

@@ -479,6 +479,7 @@ void optim_pack(hipStream_t st, const OptimPtrs& p, const long long* d_off, int 
 void optim_unpack(hipStream_t st, const OptimPtrs& p, const long long* d_off, int ntens, long long total, const double* d_reduce,
                   int world, double* d_partials, int* d_rguard, bool to_params);
 void optim_fill(hipStream_t st, float* p, long long n, float val);
+void optim_set_steps(hipStream_t st, long long* d_t, long long steps);      // *d_t = steps, by a launch (tfl_optim_set_state)
 
 // conv2d_mfma.hip (2-D default topology: 16 channels, k = 3; one MFMA = one tap x four input channels)
 void conv2_mfma_first_fused(hipStream_t st, int B, int Y, int X, const float* pDiv, const float* div, const float* flags,

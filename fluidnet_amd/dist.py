@@ -18,6 +18,7 @@ a slab only ever talks to ranks r-1 and r+1, each over its own link, so every ex
 per neighbour -- no ring, no all-to-all.
 """
 import ctypes
+import itertools
 import threading
 
 import torch
@@ -641,9 +642,11 @@ def run_virtual_closures(closures, batches_per_rank, steps=None, rngs=None, trai
     order = sorted(range(len(closures)), key=lambda i: closures[i].comm.rank)
 
     def work(i):
-        batches = list(batches_per_rank[i])
+        # iterated inside the rank's thread, one batch at a time: a generator over one set of batch buffers
+        # (data.DataBinary.batches) yields a batch that is valid only until the next one is asked for
+        batches = batches_per_rank[i]
         if steps is not None:
-            batches = batches[:int(steps)]
+            batches = itertools.islice(batches, int(steps))
         return lambda: _re.run_epoch(closures[i], batches, None if rngs is None else rngs[i], training)
 
     res = run_virtual(hub, [work(i) for i in order], timeout_s)

@@ -315,6 +315,16 @@ int tfl_optim_step_reduced(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights
 int tfl_optim_reduced_guard(tfl_ctx* ctx, tfl_optim* opt, int32_t* d_out);
 int tfl_optim_sync_parameters(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights, float* const* d_biases,
                               const tfl_comm* comm, int32_t rank, double* d_reduce, int64_t reduce_doubles);
+int tfl_optim_set_state(tfl_ctx* ctx, tfl_optim* opt, const float* d_m, const float* d_v, int64_t steps);
+typedef struct tfl_frames tfl_frames;
+tfl_frames* tfl_frames_create(tfl_ctx* ctx, int is3D, int Z, int Y, int X, int64_t capacity, int64_t device_frames);
+void tfl_frames_destroy(tfl_ctx* ctx, tfl_frames* frames);
+int64_t tfl_frames_record_floats(const tfl_frames* frames);
+int tfl_frames_put(tfl_ctx* ctx, tfl_frames* frames, int64_t slot, const float* h_record);
+int tfl_frames_gather(tfl_ctx* ctx, tfl_frames* frames, int n, const int32_t* h_slots,
+                      const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
+                      const tfl_tensor* densityDiv, const tfl_tensor* pTarget, const tfl_tensor* UTarget,
+                      const tfl_tensor* densityTarget);
 ]]
 -- END generated cdef
 

@@ -7,8 +7,10 @@ SetWallBcs) runs inside libtfluids_hip.so (tfl_model_forward); this class only o
 host copy, the device handle and the scratch tensor.
 """
 import ctypes
+import json
 import math
 import os
+import re
 
 import numpy as np
 import torch
@@ -178,10 +180,51 @@ class FluidNetModel:
 
     @classmethod
     def from_npz(cls, path):
+        """w0, b0, w1, b1, ... (cudnn layout) from an .npz. A file written by save_npz also holds `model_json`: is3D, pool / up,
+        the forward options and the graph, so that a custom or banked model comes back as it was; a file without it is a
+        linear model with the default options, its dimensionality read from the weights' rank."""
         z = np.load(path)
-        n = len([k for k in z.files if k.startswith("w")])
+        n = len([k for k in z.files if re.fullmatch(r"w\d+", k)])
         layers = [(z["w%d" % i], z["b%d" % i]) for i in range(n)]
-        return cls(layers, is3D=layers[0][0].ndim == 5)
+        if "model_json" not in z.files:
+            return cls(layers, is3D=layers[0][0].ndim == 5)
+        d = json.loads(str(z["model_json"]))
+        graph = d.get("graph")
+        if graph is not None and graph.get("bn") is not None:
+            graph["bn"] = [{k: (None if v is None else float(v) if k == "eps" else np.asarray(v, np.float32)) for k, v in m.items()}
+                           for m in graph["bn"]]
+        return cls(layers, bool(d["is3D"]), pool=d.get("pool"), up=d.get("up"), opts=d.get("opts"), graph=graph)
+
+    @staticmethod
+    def npz_meta(path):
+        """the caller's `meta` of a file written by save_npz (None where there is none)"""
+        z = np.load(path)
+        return json.loads(str(z["model_json"])).get("meta") if "model_json" in z.files else None
+
+    def save_npz(self, path, meta=None, extra=None):
+        """The counterpart of from_npz: weights and biases under the keys it reads, plus one JSON string `model_json` = {is3D,
+        pool, up, opts, graph (batch-norm statistics included), meta}. meta: anything json can hold, kept for the caller
+        (npz_meta). extra: further arrays under keys of their own (a checkpoint's optimiser moments; not w<i> / b<i>).
+        Written to `path` exactly (no .npz is appended), through a temporary file beside it."""
+        graph = None
+        if self.graph is not None:
+            graph = dict(self.graph)
+            if graph.get("bn") is not None:
+                graph["bn"] = [{k: (None if v is None else float(v) if k == "eps" else [float(x) for x in np.asarray(v, np.float32).ravel()])
+                                for k, v in m.items()} for m in graph["bn"]]
+        d = dict(is3D=self.is3D, pool=self.pool, up=self.up, opts=self.opts, graph=graph, meta=meta)
+        arrays = {}
+        for i, (w, b) in enumerate(self.layers):
+            arrays["w%d" % i], arrays["b%d" % i] = w, b
+        for k, v in (extra or {}).items():
+            if re.fullmatch(r"[wb]\d+", k) or k == "model_json":
+                raise TfluidsError("save_npz: extra key %r collides with the model's own" % (k,))
+            arrays[k] = np.asarray(v)
+        arrays["model_json"] = np.array(json.dumps(d, default=lambda o: o.tolist()))      # (numpy scalars / arrays in opts or meta)
+        tmp = path + ".tmp"
+        with open(tmp, "wb") as f:
+            np.savez(f, **arrays)
+        os.replace(tmp, path)
 
     @classmethod
     def default_3d(cls, seed=1, scale=0.35):

@@ -190,6 +190,30 @@ class _Fused:
             return out
         return split(m), (split(v) if v is not None else None)
 
+    def load_state(self, m, v, steps):
+        """the inverse of state() and .steps (tfl_optim_set_state), for resuming from a checkpoint: m, v as state() returns them
+        (lists of tensors or arrays in its order, or one flat tensor each; v is ignored for RMSprop), and the step counter.
+        Enqueued on the current stream; nothing waits."""
+        lib, ctx = tfluids._context(self.net.weights[0])
+        n = int(lib.tfl_optim_get_state(ctx, self._opt, None, None))
+
+        def flat(x, name):
+            if x is None:
+                return None
+            parts = [x] if torch.is_tensor(x) or not isinstance(x, (list, tuple)) else list(x)
+            t = torch.cat([torch.as_tensor(p, dtype=torch.float32).reshape(-1).to(self._dev) for p in parts]).contiguous()
+            if t.numel() != n:
+                raise TfluidsError("optim.load_state: %s holds %d floats, the optimiser's state %d" % (name, t.numel(), n))
+            return t
+        fm, fv = flat(m, "m"), (flat(v, "v") if self.method == ADAM else None)
+        if self.method == ADAM and (fm is None) != (fv is None):
+            raise TfluidsError("optim.load_state: Adam restores m and v together")
+        tfluids._call(lib, ctx, lib.tfl_optim_set_state(ctx, self._opt, None if fm is None else ctypes.c_void_p(fm.data_ptr()),
+                                                        None if fv is None else ctypes.c_void_p(fv.data_ptr()), int(steps)))
+        for t in (fm, fv):      # the copies read these on the stream: keep the caching allocator from handing them out before
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(self._dev))
+
     def close(self):
         if self._opt:
             lib, ctx = tfluids._context(self.net.weights[0])

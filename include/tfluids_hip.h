@@ -938,6 +938,46 @@ int tfl_optim_reduced_guard(tfl_ctx* ctx, tfl_optim* opt, int32_t* d_out);
 int tfl_optim_sync_parameters(tfl_ctx* ctx, tfl_optim* opt, float* const* d_weights, float* const* d_biases,
                               const tfl_comm* comm, int32_t rank, double* d_reduce, int64_t reduce_doubles);
 
+/* The inverse of tfl_optim_get_state, for resuming from a checkpoint: m from d_m and (Adam) v from d_v -- DEVICE arrays of
+ * tfl_optim_get_state's count of floats in its order; either may be NULL and is then left as it is -- and the step counter set
+ * to `steps` (>= 0). The counter lives on the device and is written by a launch that takes the value as an argument: the
+ * call is enqueued on the context's stream and waits for nothing. The arrays must stay valid until the copies have run. */
+int tfl_optim_set_state(tfl_ctx* ctx, tfl_optim* opt, const float* d_m, const float* d_v, int64_t steps);
+
+/* ---- the resident frame store of the training loop and its one-launch mini-batch gather (csrc/frames.hip) ----
+ * The data set of lib/data_binary.lua, kept where the training step runs. A store holds `capacity` slots of one record each:
+ * 2 C + 5 fp32 planes of Z Y X cells (C = 3 in 3-D, 2 in 2-D) in the order
+ *     pDiv, UDiv[C], flags, densityDiv, p, U[C], density
+ * i.e. the divergent frame, the flags ONCE (the two files of a frame carry equal flags, data_binary.lua:77; the int32 words as
+ * floats, as loadMantaFile delivers them) and the target frame. Every plane is padded to a multiple of 4 floats, so each plane
+ * of each slot starts on 16 bytes: a record is tfl_frames_record_floats() = (2 C + 5) * ((Z Y X + 3) & ~3) floats, and plane k
+ * starts at float k * ((Z Y X + 3) & ~3) of it (the padding floats are never read back).
+ * Slots [0, device_frames) are ONE device allocation; slots [device_frames, capacity) are ONE pinned, device-mapped host
+ * allocation that the gather kernel reads through its device address. device_frames may be 0 or capacity. A slot that was
+ * never put holds undefined floats. NULL on error (tfl_last_error). */
+typedef struct tfl_frames tfl_frames;
+tfl_frames* tfl_frames_create(tfl_ctx* ctx, int is3D, int Z, int Y, int X, int64_t capacity, int64_t device_frames);
+void tfl_frames_destroy(tfl_ctx* ctx, tfl_frames* frames);
+int64_t tfl_frames_record_floats(const tfl_frames* frames);
+/* One record from HOST memory into a slot. NOT a hot path: ingest happens once per data set, one call per frame. A device slot
+ * is one host-to-device copy enqueued on the context's stream: h_record must stay valid and unchanged until the stream has
+ * passed it. A host slot first waits for the stream -- a gather enqueued earlier may still be reading the slot -- and is then a
+ * memcpy, done when the call returns. */
+int tfl_frames_put(tfl_ctx* ctx, tfl_frames* frames, int64_t slot, const float* h_record);
+/* One mini-batch: item i < n of every output tensor = the planes of slot h_slots[i], wherever the slot lies -- ONE launch
+ * (k_frames_gather) for up to 128 items, one more per further 128. The outputs are contiguous [B][1 or C][Z][Y][X] device tensors
+ * with n <= B; any of them may be NULL and is then skipped; items [n, B) are not touched. pTarget / UTarget / densityTarget
+ * receive the record's p / U / density. A slot may appear more than once.
+ * h_slots is a HOST array, read during the call only: the indices are validated here (range; n against every B; shapes; the
+ * outputs are memory of the context's device), before anything is launched -- a refused call has written nothing -- and then
+ * travel to the kernel BY VALUE. So there is no host read of device memory and no synchronisation, and a call captured into a
+ * graph replays the slots it was recorded with (re-record, or call eagerly, for other slots).
+ * The copy is bit-exact: NaN payloads, -0 and denormals arrive as they were put. */
+int tfl_frames_gather(tfl_ctx* ctx, tfl_frames* frames, int n, const int32_t* h_slots,
+                      const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
+                      const tfl_tensor* densityDiv, const tfl_tensor* pTarget, const tfl_tensor* UTarget,
+                      const tfl_tensor* densityTarget);
+
 #ifdef __cplusplus
 }
 #endif
