@@ -581,11 +581,11 @@ __global__ __launch_bounds__(512) void k_vort_fused(Dom d, int cols_x, int cols_
 //   cell, 0 where p lies on the border shell: each c(p) was evaluated by up to two cells, from two ring reads, an add, a
 //   multiply and a border select each time. The staging threads now evaluate it ONCE per staged cell (same expression: same
 //   bits), border zero included, and the curl of a cell is 12 ring reads and 12 flops.
-//     step t:  C ring[(t - 1) & 3] <- centred velocities of plane t - 1: c_x, c_y from the plane's own loads (registers since
+//     step t:  C ring (4 planes)   <- centred velocities of plane t - 1: c_x, c_y from the plane's own loads (registers since
 //                                     step t - 1), c_z from u_z of planes t - 1 (carried) and t (loaded during step t - 1)
-//              curl, |curl| of plane zc = t - 3  from C planes t - 4, t - 3, t - 2        -> Cv[zc % 3], Cn[zc & 3]
-//              force of plane zf = t - 5          from Cn planes t - 6, t - 5, t - 4, Cv plane t - 5   -> Fe[zf & 1], registers
-//              plane zo = t - 6 out               from Fe[zo & 1] (x / y neighbours), the thread's own force of planes zo and
+//              curl, |curl| of plane zc = t - 3  from C planes t - 4, t - 3, t - 2        -> Cv (3 planes), Cn (4 planes)
+//              force of plane zf = t - 5          from Cn planes t - 6, t - 5, t - 4, Cv plane t - 5   -> Fe (2 planes), registers
+//              plane zo = t - 6 out               from Fe plane zo (x / y neighbours), the thread's own force of planes zo and
 //                                                 zo - 1 (registers), its own velocities and flags (loaded at the top of the step)
 //   Nothing a step writes is read in the same step, and what step t + 1 overwrites (C plane t - 4, Cn plane t - 6, Cv plane
 //   t - 5, Fe plane t - 6) was last read before step t's barrier.
@@ -593,6 +593,10 @@ __global__ __launch_bounds__(512) void k_vort_fused(Dom d, int cols_x, int cols_
 // (k_vort_fused: 1.91), curl cells 1.24 (1.44); the second rounds of the staging / the curl tile and the edge forces go to
 // DIFFERENT waves (9-15 / 0-3 / 4-5). Pipeline fill: 9 steps per chunk (6). Per-cell arithmetic is k_curl / k_confine's,
 // operation for operation: bit-equal to the two-launch form (tests/test_hip_parity.py).
+// Static schedule (profiles/vort_pipe_static.md): a chunk of n >= 4 planes runs 5 fill steps, n - 4 steady steps and 4 drain steps,
+// each an instance of the step with exactly its stages as a compile-time set (one basic block, no guard inside); the ring slots
+// are numbered by the plane relative to the chunk and rotated, not rebuilt from z. Shorter chunks take the guarded step.
+// tests/test_hip_vort_pipe_static.py holds every chunk length around the bound to the two-launch form and the oracle, bit for bit.
 namespace {
 // k_vort_pipe's global accesses are BUFFER loads / stores: resource (the batch item's array) + the lane's 32-bit byte offset, fixed
 // for the whole march, + the plane's byte offset in a scalar register. Written as pointers, the loop optimiser turns "moving
@@ -625,6 +629,9 @@ struct PipeGeo {
   static_assert(QN <= 2 * NT && PCN <= 2 * NT && NT % 64 == 0, "two rounds cover the tiles");
 };
 constexpr int kPipeFill = 9;
+// the stages of a step of k_vort_pipe, and the shortest chunk whose steps all have a compile-time stage set (see the kernel)
+enum : int { kStStage = 1, kStLoad = 2, kStCurl = 4, kStForce = 8, kStAsk = 16, kStOut = 32, kStAll = 63, kStGuarded = -1 };
+constexpr int kPipeStatic = 4;
 }  // namespace
 
 template <int BX, int BY>
@@ -634,10 +641,8 @@ __global__ __launch_bounds__(BX * BY) void k_vort_pipe(Dom d, int cols_x, int co
   using G = PipeGeo<BX, BY>;
   constexpr int PBX = G::PBX, PBY = G::PBY, NT = G::NT, PCX = G::PCX, PCN = G::PCN, QX = G::QX, QN = G::QN, PEX = G::PEX, PEY = G::PEY;
   extern __shared__ float lds[];
-  float* Cr = lds;                    // [4][3][QN]   centred velocities, planes z & 3
-  float* Cn = Cr + 4 * 3 * QN;        // [4][PCN]     |curl|, planes z & 3
-  float* Cv = Cn + 4 * PCN;           // [3][3][PCN]  curl, planes z % 3
-  float* Fe = Cv + 3 * 3 * PCN;       // [2][2][PEY][PEX] force.x / force.y, planes z & 1
+  // lds: Cr [4][3][QN] centred velocities | Cn [4][PCN] |curl| | Cv [3][3][PCN] curl | Fe [2][2][PEY][PEX] force.x / force.y; which
+  // plane a slot holds: the ring-slot variables below
   const int blk = xcd_order ? (int)xcd_contiguous(blockIdx.x, (unsigned)n_blocks) : (int)blockIdx.x;
   if (blk >= n_blocks) return;
   int tq = blk;
@@ -741,14 +746,30 @@ __global__ __launch_bounds__(BX * BY) void k_vort_pipe(Dom d, int cols_x, int co
   float fn[3] = {0.0f, 0.0f, 0.0f}, fzc = 0.0f, un[3] = {0.0f, 0.0f, 0.0f};
   v3 fcar = mk3(0.0f, 0.0f, 0.0f);    // the thread's force of plane t - 6 (computed in step t - 1)
   float fzcar = 0.0f;                 // force.z of plane t - 7
-  int cv3 = ((t0 - 3) % 3 + 3) % 3;   // (zc % 3) of this step's curl plane, kept as a counter
-  // one step; STEADY = every stage is active (no block-uniform guards: ONE basic block, so that the scheduler can run the
-  // stages' ring reads and arithmetic against each other)
-  auto step = [&](int t, auto steady_tag) {
-    constexpr bool STEADY = decltype(steady_tag)::value;
-    // ---- out stage, part 1: ask for the flags and the velocities of plane zo = t - 6 now ----
+  // ring slots as pointers into lds, numbered by the plane RELATIVE to the chunk (the rings are private to the block) and
+  // ROTATED at the end of a step instead of rebuilt from t: the slot a step writes is the one whose plane the previous step read
+  // last. Names: the Cr slots of planes t - 1 (written) and t - 4, t - 3, t - 2 (read: zc - 1, zc, zc + 1); the Cn slots of planes
+  // t - 3 (written) and t - 4, t - 5, t - 6 (read: zf + 1, zf, zf - 1); the Cv slots of planes t - 3 (written), t - 4 and t - 5
+  // (read); the Fe slots of planes t - 5 (written) and t - 6 (read). At t = za + 1 plane za has Cr slot 0: the prologue fills 1, 2, 3
+  constexpr int oCn = 4 * 3 * QN, oCv = oCn + 4 * PCN, oFe = oCv + 3 * 3 * PCN;
+  float *crW = lds, *crM = lds + 3 * QN, *cr0 = lds + 2 * 3 * QN, *crP = lds + 3 * 3 * QN;
+  float *cnW = lds + oCn, *cnP = lds + oCn + PCN, *cn0s = lds + oCn + 2 * PCN, *cnM = lds + oCn + 3 * PCN;
+  float *cvW = lds + oCv, *cvX = lds + oCv + 3 * PCN, *cvR = lds + oCv + 2 * 3 * PCN;
+  float *feW = lds + oFe, *feR = lds + oFe + 2 * PEY * PEX;
+  // one step. MASK = the stages that run, a compile-time set: the step is ONE basic block with no block-uniform guard inside, so
+  // that the scheduler can run its stages' ring reads and arithmetic against each other -- the steady steps (every stage) and each
+  // fill and drain step with exactly its own. MASK = kStGuarded: the stages behind runtime guards (chunks too short for the table)
+  auto step = [&](int t, auto mask_tag) __attribute__((always_inline)) {
+    constexpr int MASK = decltype(mask_tag)::value;
+    constexpr bool RT = MASK == kStGuarded;
+    const bool on_stage = RT ? t <= zb + 2 : (MASK & kStStage) != 0;                     // block-uniform, all six
+    const bool on_load = RT ? t <= zb + 1 : (MASK & kStLoad) != 0;
+    const bool on_curl = RT ? t <= zb + 3 : (MASK & kStCurl) != 0;                       // (t >= za + 1 always)
+    const bool on_force = RT ? (t >= za + 4 && t <= zb + 4) : (MASK & kStForce) != 0;
+    const bool on_ask = RT ? (t >= za + 5 && t <= zb + 4) : (MASK & kStAsk) != 0;
+    const bool out_act = RT ? (t >= za + 6 && t <= zb + 5) : (MASK & kStOut) != 0;
+    // ---- out stage, part 1: the flags and the velocities of plane zo = t - 6, asked for a step ago ----
     const int zo = t - 6;
-    const bool out_act = STEADY || (zo >= za && zo < zb);         // block-uniform
     const bool out_live = out_xy && out_act;
     const bool out_inner = out_live && f_in && zo >= 1 && zo <= d.Z - 2;
     float pfc = 0.0f, pnx = 0.0f, pny = 0.0f, pnz = 0.0f, pu0 = 0.0f, pu1 = 0.0f, pu2 = 0.0f;
@@ -756,36 +777,36 @@ __global__ __launch_bounds__(BX * BY) void k_vort_pipe(Dom d, int cols_x, int co
     // the cell's own flag of the plane before (fzc: carried). This step asks for plane zo + 1's.
     if (out_act) { pfc = out_inner ? fn[0] : 0.0f; pnx = out_inner ? fn[1] : 0.0f; pny = out_inner ? fn[2] : 0.0f; pnz = out_inner ? fzc : 0.0f; }
     pu0 = un[0]; pu1 = un[1]; pu2 = un[2];
-    if (STEADY || (zo + 1 >= za && zo + 1 < zb)) {      // block-uniform
+    if (on_ask) {
       fzc = fn[0];
       const unsigned pz = (unsigned)min(max(zo + 1, 0), d.Z - 1) * sz4;      // (scalar)
       fn[0] = ldb(rF, o_safe4, pz); fn[1] = ldb(rF, o_safe_x4, pz); fn[2] = ldb(rF, o_safe_y4, pz);
       un[0] = ldb(rU, o_xy4, pz); un[1] = ldb(rU, o_xy4, pz + sc4); un[2] = ldb(rU, o_xy4, pz + 2u * sc4);
     }
     // ---- centred velocities of plane t - 1 -> ring; then ask for plane t + 1 ----
-    if (STEADY || t <= zb + 2) {        // block-uniform
+    if (on_stage) {
       const bool zsh = t - 1 <= 0 || t - 1 >= d.Z - 1;
-      float* dst = Cr + ((t - 1) & 3) * 3 * QN;
+      float* dst = crW;
 #pragma unroll
       for (int r = 0; r < 2; r++) {
         if (r == 1 && !two_st) continue;
         const float cxn = 0.5f * (nl[r][0] + nl[r][1]), cyn = 0.5f * (nl[r][2] + nl[r][3]);     // plane t: next step's
         const float czp = 0.5f * (uzp[r] + nl[r][4]);
         const bool z0 = zsh || st_sh[r];
-        if (STEADY || t > t0) { dst[st_it[r]] = z0 ? 0.0f : cxp[r]; dst[QN + st_it[r]] = z0 ? 0.0f : cyp[r]; dst[2 * QN + st_it[r]] = z0 ? 0.0f : czp; }
+        dst[st_it[r]] = z0 ? 0.0f : cxp[r]; dst[QN + st_it[r]] = z0 ? 0.0f : cyp[r]; dst[2 * QN + st_it[r]] = z0 ? 0.0f : czp;
         cxp[r] = cxn; cyp[r] = cyn; uzp[r] = nl[r][4];
       }
-      if (STEADY || t <= zb + 1) load_plane(t + 1);
+      if (on_load) load_plane(t + 1);
     }
     // ---- curl, |curl| of plane zc = t - 3 from C planes t - 4, t - 3, t - 2 ----
     const int zc = t - 3;
-    if (STEADY || (zc >= za - 2 && zc <= zb)) {       // block-uniform
+    if (on_curl) {
       const bool z_in = zc >= 1 && zc <= d.Z - 2;
-      const float* P0 = Cr + (zc & 3) * 3 * QN;
-      const float* Pp = Cr + ((zc + 1) & 3) * 3 * QN;
-      const float* Pm = Cr + ((zc - 1) & 3) * 3 * QN;
-      float* cvw = Cv + cv3 * 3 * PCN;
-      float* cnw = Cn + (zc & 3) * PCN;
+      const float* P0 = cr0;
+      const float* Pp = crP;
+      const float* Pm = crM;
+      float* cvw = cvW;
+      float* cnw = cnW;
 #pragma unroll
       for (int r = 0; r < 2; r++) {
         if (r == 1 && wave * 64 >= kC1) continue;              // waves 4-15 have no cell in the second round
@@ -813,14 +834,13 @@ __global__ __launch_bounds__(BX * BY) void k_vort_pipe(Dom d, int cols_x, int co
     // ---- force of plane zf = t - 5 from Cn planes t - 6, t - 5, t - 4 and Cv plane t - 5 ----
     const int zf = t - 5;
     v3 f0 = mk3(0.0f, 0.0f, 0.0f);
-    if (STEADY || (zf >= za - 1 && zf <= zb - 1)) {   // block-uniform
+    if (on_force) {
       const bool z_in = zf >= 1 && zf <= d.Z - 2;
-      const float* cn0 = Cn + (zf & 3) * PCN;
-      const float* cnp = Cn + ((zf + 1) & 3) * PCN;
-      const float* cnm = Cn + ((zf - 1) & 3) * PCN;
-      const int cvf = cv3 >= 2 ? cv3 - 2 : cv3 + 1;          // (zc - 2) % 3
-      const float* cv = Cv + cvf * 3 * PCN;
-      float* fe = Fe + (zf & 1) * 2 * PEY * PEX;
+      const float* cn0 = cn0s;
+      const float* cnp = cnP;
+      const float* cnm = cnM;
+      const float* cv = cvR;
+      float* fe = feW;
       f0 = force(f_it, z_in && f_in, cn0, cnp, cnm, cv);
       fe[(ty + 1) * PEX + tx + 1] = f0.x;
       fe[(PEY + ty + 1) * PEX + tx + 1] = f0.y;
@@ -831,7 +851,7 @@ __global__ __launch_bounds__(BX * BY) void k_vort_pipe(Dom d, int cols_x, int co
     }
     // ---- plane zo = t - 6 out: AddForceField (tfluids.cc:1312-1339); every cell of the plane is written ----
     if (out_act) {
-      const float* fe = Fe + (zo & 1) * 2 * PEY * PEX;
+      const float* fe = feR;
       float u0 = pu0, u1 = pu1, u2 = pu2;
       const int fc = (int)pfc;            // (all zero when !out_inner: nothing is added)
       const bool cf = fc & kFluid, ce = fc & kEmpty;
@@ -857,13 +877,14 @@ __global__ __launch_bounds__(BX * BY) void k_vort_pipe(Dom d, int cols_x, int co
         stb(wU, o_xy4, po, u0); stb(wU, o_xy4, po + sc4, u1); stb(wU, o_xy4, po + 2u * sc4, u2);
       }
     }
-    // ---- rotate the registers that travel with the planes ----
+    // ---- rotate the registers that travel with the planes, and the ring slots ----
     fzcar = fcar.z; fcar = f0;
-    cv3 = cv3 == 2 ? 0 : cv3 + 1;
+    { float* const s = crM; crM = cr0; cr0 = crP; crP = crW; crW = s; }
+    { float* const s = cnM; cnM = cn0s; cn0s = cnP; cnP = cnW; cnW = s; }
+    { float* const s = cvR; cvR = cvX; cvX = cvW; cvW = s; }
+    { float* const s = feR; feR = feW; feW = s; }
     __syncthreads();
   };
-  // every stage is active for t in [za + 6, zb + 1]
-  const int ts = min(max(za + 6, t0), t1 + 1), te = min(zb + 1, t1);
 #ifdef TFL_VORT_TIMING
   long long tk[40]; int nk = 0;
   tk[nk++] = wall_clock64();
@@ -892,7 +913,7 @@ __global__ __launch_bounds__(BX * BY) void k_vort_pipe(Dom d, int cols_x, int co
     for (int q = 0; q < 3; q++) {
       const int pz = t0 + q;
       const bool zsh = pz <= 0 || pz >= d.Z - 1;
-      float* dst = Cr + (pz & 3) * 3 * QN;
+      float* dst = lds + (q + 1) * 3 * QN;      // (the Cr slots of planes za - 3, za - 2, za - 1: crM, cr0, crP of step za + 1)
 #pragma unroll
       for (int r = 0; r < 2; r++) {
         if (r == 1 && !two_st) continue;
@@ -907,17 +928,31 @@ __global__ __launch_bounds__(BX * BY) void k_vort_pipe(Dom d, int cols_x, int co
       if (r == 1 && !two_st) continue;
       cxp[r] = 0.5f * (pl[3][r][0] + pl[3][r][1]); cyp[r] = 0.5f * (pl[3][r][2] + pl[3][r][3]); uzp[r] = pl[3][r][4];
     }
-    cv3 = (cv3 + 4) % 3;
     __syncthreads();
   }
   TFL_VT();
-  int t = za + 1;
+  // the steps t = za + 1 .. zb + 5. Staging runs for t <= zb + 2, the load-ahead for t <= zb + 1, curl for t <= zb + 3, force for
+  // za + 4 <= t <= zb + 4, the out-ask for za + 5 <= t <= zb + 4, out for za + 6 <= t. With n = zb - za planes: the five fill steps
+  // t <= za + 5 run every stage that has begun iff za + 5 <= zb + 1, and the four drain steps t >= zb + 2 every stage that has
+  // not ended iff zb + 2 >= za + 6 -- both n >= 4: then no step is a fill and a drain step at once, and each has its own instance.
+  // A shorter chunk (the last one of a ragged z range, or an override) takes the guarded step. Block-uniform.
+  if (zb - za >= kPipeStatic) {
+    using Fill3 = std::integral_constant<int, kStStage | kStLoad | kStCurl>;
+    step(za + 1, Fill3{}); TFL_VT();
+    step(za + 2, Fill3{}); TFL_VT();
+    step(za + 3, Fill3{}); TFL_VT();
+    step(za + 4, std::integral_constant<int, kStStage | kStLoad | kStCurl | kStForce>{}); TFL_VT();
+    step(za + 5, std::integral_constant<int, kStStage | kStLoad | kStCurl | kStForce | kStAsk>{}); TFL_VT();
 #pragma unroll 1
-  for (; t < ts; t++) { step(t, std::false_type{}); TFL_VT(); }
+    for (int t = za + 6; t <= zb + 1; t++) { step(t, std::integral_constant<int, kStAll>{}); TFL_VT(); }
+    step(zb + 2, std::integral_constant<int, kStAll & ~kStLoad>{}); TFL_VT();
+    step(zb + 3, std::integral_constant<int, kStCurl | kStForce | kStAsk | kStOut>{}); TFL_VT();
+    step(zb + 4, std::integral_constant<int, kStForce | kStAsk | kStOut>{}); TFL_VT();
+    step(zb + 5, std::integral_constant<int, kStOut>{}); TFL_VT();
+  } else {
 #pragma unroll 1
-  for (; t <= te; t++) { step(t, std::true_type{}); TFL_VT(); }
-#pragma unroll 1
-  for (; t <= t1; t++) { step(t, std::false_type{}); TFL_VT(); }
+    for (int t = za + 1; t <= t1; t++) { step(t, std::integral_constant<int, kStGuarded>{}); TFL_VT(); }
+  }
 #ifdef TFL_VORT_TIMING
   if (tid == 0 && (blk == 0 || blk == n_blocks / 2 + 3)) {
     for (int q = 1; q < nk; q++) printf("vt blk %d step %d (t-za %d) %lld\n", blk, q - 1, q - 1, tk[q] - tk[q - 1]);     // (step 0 = the prologue)
