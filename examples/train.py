@@ -36,7 +36,7 @@ def default_mconf(modelType, longTerm):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--dataDir", required=True)
+    ap.add_argument("--dataDir", required=True, help="holds <dataset>/{tr,te}/...; examples/gen_data.py generates such a set")
     ap.add_argument("--dataset", required=True)
     ap.add_argument("--out", required=True, help="conf.modelDirname: the prefix of the files written")
     ap.add_argument("--modelType", default="default", choices=("default", "yang"))

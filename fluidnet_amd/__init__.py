@@ -9,6 +9,7 @@
   fluidnet_amd.criterion  nn.FluidCriterion (torch/lib/modules/fluid_criterion.lua) over tfl_fluidCriterion
   fluidnet_amd.run_epoch  the training closure of torch/lib/run_epoch.lua (long-term divergence pass included) as one call
   fluidnet_amd.data       torch/lib/data_binary.lua: the data set in a resident frame store (tfl_frames_*), mini-batches by one launch
+  fluidnet_amd.datagen    training sets generated on the device: random scenes, PCG frame pairs, into a frame store or onto the disk
   fluidnet_amd.train_loop the loop of torch/fluid_net_train.lua: fit() -- epochs, last / best model files, log, resume
   fluidnet_amd.dist       z-slab decomposition across GPUs: halo exchange + 1 all-reduce per step (RCCL); the transports that
                           data-parallel training (optim.step(comm=...), run_epoch.Closure(comm=...)) reduces its gradients over
@@ -26,6 +27,7 @@ from . import optim  # noqa: F401  (optim.Adam / optim.RMSprop: clip + update + 
 from . import run_epoch  # noqa: F401  (run_epoch.plan_batch / Closure / run_epoch: one call for a training mini-batch)
 from . import dist  # noqa: F401  (transports: DistComm / RcclComm / ThreadComm; the z-slab step; run_virtual_closures)
 from . import data  # noqa: F401  (data.DataBinary: the training set in a resident frame store, one launch per mini-batch)
+from . import datagen  # noqa: F401  (datagen.plan_run / init_state / generate: the producer of what fit() reads)
 from . import train_loop  # noqa: F401  (train_loop.fit: epochs, best / last model files, log, resume)
 from . import modules  # noqa: F401  (the tfluids nn.Modules as torch.nn.Modules with autograd)
 from ._lib import TfluidsError  # noqa: F401

@@ -24,7 +24,9 @@ KERNEL_SOURCE = {
     "k_optim_norm": "optim.hip+tfl_refresh.hpp", "k_optim_update": "optim.hip+tfl_refresh.hpp", "k_optim_advance": "optim.hip",
     "k_optim_pack": "optim.hip+tfl_refresh.hpp", "k_optim_unpack": "optim.hip+tfl_refresh.hpp",
     "k_optim_unpack_norm": "optim.hip+tfl_refresh.hpp",
-    "k_frames_gather": "frames.hip+tfl_frames.hpp",
+    "k_frames_gather": "frames.hip+tfl_frames.hpp", "k_frames_scatter": "frames.hip+tfl_frames.hpp",
+    "k_scene_flags": "datagen.hip+tfl_datagen.hpp", "k_noise_potential": "datagen.hip+tfl_datagen.hpp",
+    "k_curl_mac": "datagen.hip+tfl_datagen.hpp",
 }
 # the default conv path can be switched by TFL_CONV_PATH; these are the files behind the same profiler names then
 CONV_SOURCE = {"winograd": "conv_valu.hip", "mfma": "conv_mfma.hip", "direct": "conv.hip", "mfma16": "conv_mfma16.hip"}

@@ -64,6 +64,11 @@ class tfl_sim_state(_c.Structure):
                 ("UBC", _c.c_void_p), ("densityBC", _c.c_void_p * 8), ("model", _c.c_void_p)]
 
 
+class tfl_scene_prim(_c.Structure):
+    """include/tfluids_hip.h tfl_scene_prim."""
+    _fields_ = [("kind", _c.c_int32), ("a", _c.c_float * 3), ("b", _c.c_float * 3), ("val", _c.c_float)]
+
+
 class tfl_slab(_c.Structure):
     """include/tfluids_hip.h tfl_slab."""
     _fields_ = [("z_total", _c.c_int32), ("z_first", _c.c_int32), ("own_lo", _c.c_int32), ("own_hi", _c.c_int32),
@@ -191,6 +196,11 @@ SIGNATURES = {
     "tfl_frames_record_floats": (_c.c_int64, [_c.c_void_p]),
     "tfl_frames_put": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p]),
     "tfl_frames_gather": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.POINTER(_c.c_int32), _T, _T, _T, _T, _T, _T, _T]),
+    "tfl_frames_put_device": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.POINTER(_c.c_int32), _T, _T, _T, _T, _T, _T, _T]),
+    "tfl_scene_flags": (_c.c_int, [_c.c_void_p, _c.POINTER(tfl_scene_prim), _c.c_int, _c.POINTER(tfl_scene_prim), _c.c_int, _c.c_int,
+                                   _T, _T]),
+    "tfl_noise_potential": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _T]),
+    "tfl_curl_mac": (_c.c_int, [_c.c_void_p, _T, _c.c_float, _c.c_int, _T]),
     "tfl_set_dx_override": (_c.c_int, [_c.c_void_p, _c.c_float]),
     "tfl_velocityDivergenceBackward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int, _T]),
     "tfl_velocityUpdateBackward": (_c.c_int, [_c.c_void_p, _T, _T, _T, _T, _c.c_int, _T]),
@@ -214,6 +224,8 @@ SIGNATURES = {
     "tfl_simulate_workspace_floats": (_c.c_int64, [_c.c_void_p, _c.POINTER(tfl_sim_params), _c.POINTER(tfl_sim_state)]),
     "tfl_simulate_step": (_c.c_int, [_c.c_void_p, _c.POINTER(tfl_sim_params), _c.POINTER(tfl_sim_state), _c.c_void_p,
                                      _c.c_int64]),
+    "tfl_simulate_project": (_c.c_int, [_c.c_void_p, _c.POINTER(tfl_sim_params), _c.POINTER(tfl_sim_state), _c.c_void_p,
+                                        _c.c_int64]),
     "tfl_applyBCsIndexedMulti": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_T), _c.POINTER(_T), _c.POINTER(_T),
                                             _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_int64)]),
     "tfl_applyBCs": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int, _c.c_float, _c.c_float]),

@@ -143,7 +143,7 @@ struct Step {
   // array and writes the other since round 5) or the ConvNet projection (UDiv = cur, UOut = U); a copy only where none does.
   const tfl_tensor* cur = nullptr;     // where the velocity of the step currently lives
 
-  int validate();                      // every refusal, before anything is enqueued; the methods, the views, the forces
+  int validate(const char* who = "simulate_step");      // every refusal, before anything is enqueued, under the entry's name; the methods, the views, the forces
   int advect();                        // [advectVel pass A,] the density channels, advectVel, the first setConstVals
   int forces();                        // buoyancy (unless folded), gravity, confinement, the velocity into U where nobody delivered it
   int project_net();                   // the second setConstVals, the ConvNet projection, the last setConstVals
@@ -154,7 +154,7 @@ struct Step {
   tfl_tensor view(tfl::WsRegion r, int C) const { tfl_tensor t = *s->flags; t.data = ws + r.off; t.C = C; return t; }
 };
 
-int Step::validate() {
+int Step::validate(const char* who) {
   if (s->n_density < 0 || s->n_density > 8) return TFL_EINVAL;
   z = sizes_of(s);
   is3D = z.is3d ? 1 : 0;
@@ -167,13 +167,13 @@ int Step::validate() {
   const bool net = s->model && proj == tfl::StepProj::convnet;
   // an earlier step's projection left the fp16 range of the default 3-D conv path (no sync: the word the projection kernel
   // wrote to pinned memory): refuse to step on from a clamped pressure, before anything of this step has been written
-  if (net && tfl_model_range_flag(c, s->model) > 0) return range_refusal(c, "simulate_step");
+  if (net && tfl_model_range_flag(c, s->model) > 0) return range_refusal(c, who);
   // a banked / batch-norm / max-pool model refuses a grid its pyramid and pooling cannot halve evenly: here, before the
   // advection writes anything (tfl_model_begin would refuse the same grid half-way through the step)
   if (net && tfl::model_is_graph(s->model)) {
     const int f = tfl::model_grid_factor(s->model);
     if ((z.is3d && z.Z % f) || z.Y % f || z.X % f) {
-      c->err = "simulate_step: the grid is not divisible by the model's downsampling factor " + std::to_string(f) + " (banks x pooling)";
+      c->err = std::string(who) + ": the grid is not divisible by the model's downsampling factor " + std::to_string(f) + " (banks x pooling)";
       return TFL_EINVAL;
     }
   }
@@ -408,6 +408,21 @@ int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state
   TRY(S.advect());
   TRY(S.forces());
   if (prm->outputDiv) return TFL_OK;
+  return S.proj == tfl::StepProj::convnet ? S.project_net() : S.project_solver();
+}
+
+// The projection phase alone, behind an outputDiv step. That step has delivered the velocity into U (forces(): `cur` is copied
+// where no force wrote U) and applied no pair since the first setConstVals (fold_forces is off under outputDiv), so the phase
+// starts from cur = U with nothing folded: the second setConstVals runs as its own launch, where the full ConvNet step may
+// have let the last force's kernel apply the U pair -- the same values in the same cells -- and the ConvNet projection reads
+// and writes U in place, as fluidnet_amd/simulate.py's does.
+int tfl_simulate_project(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state* s, float* ws, int64_t ws_floats) {
+  if (!c || !prm || !s || !s->p || !s->U || !s->flags) return TFL_EINVAL;
+  Step S{c, prm, s, ws, ws_floats};
+  TRY(S.validate("simulate_project"));
+  if (S.proj == tfl::StepProj::unknown) { c->err = "simulate_project: mconf.simMethod is not a valid option"; return TFL_EINVAL; }
+  if (S.proj == tfl::StepProj::convnet && !s->model) { c->err = "simulate_project: simMethod convnet needs a model"; return TFL_EINVAL; }
+  S.cur = s->U;
   return S.proj == tfl::StepProj::convnet ? S.project_net() : S.project_solver();
 }
 

@@ -96,4 +96,20 @@ TFL_HD inline FramesSplit frames_split(long long cells, int mis, long long v) {
   return s;
 }
 
+// ---- the scatter: device tensors into slots (tfl_frames_put_device, k_frames_scatter) -----------------------------------------
+// The gather's map run backwards, on the same launch geometry (grid x = frames_blocks_x, y = plane of the record, z = item;
+// thread `tid` of block `bx` owns the vectors frames_vec(bx, k, tid) < plane / 4 of the SLOT's plane). Plane pl of the record is
+// fed by channel ch of input tensor t (frames_plane_dst); a NULL tensor leaves its planes as they are. The slot side starts on
+// 16 bytes and is padded, so every vector is ONE 128-bit store, the padding floats included (as zero); the tensor side is
+// where the alignment varies: the four floats of vector v are read as frames_split says -- the kinds name loads here -- and the
+// vector that holds the plane's last cells reads n < 4 scalars and fills the rest with zero.
+TFL_HD inline long long frames_scatter_src_offset(const FramesLayout& L, long long item, int t, int ch) {
+  return frames_dst_offset(L, item, frames_out_channels(L.C, t), ch);
+}
+TFL_HD inline long long frames_scatter_dst_offset(const FramesLayout& L, long long local_slot, int pl) { return frames_src_offset(L, local_slot, pl); }
+// how a thread reads vector v of a tensor plane that starts `mis` floats behind a 16-byte boundary (v < plane / 4, so n >= 1)
+TFL_HD inline FramesSplit frames_scatter_split(long long cells, int mis, long long v) { return frames_split(cells, mis, v); }
+// float e of vector v of a slot's plane: a cell (read from the tensor) or padding (written as zero)
+TFL_HD inline bool frames_scatter_is_cell(long long cells, long long v, int e) { return 4 * v + e < cells; }
+
 }  // namespace tfl

@@ -144,10 +144,7 @@ class FrameStore:
             torch.cuda.current_stream(self.device).synchronize()
             self._pending = []
 
-    def gather(self, slots, tensors):
-        """tfl_frames_gather: item i of every tensor in `tensors` (a dict by output name -- pDiv, UDiv, flags, densityDiv,
-        pTarget, UTarget, densityTarget; missing or None: skipped) = slot slots[i]. One launch per 128 items, on the current
-        stream; nothing waits. A call captured into a graph replays the slots it was recorded with."""
+    def _tensor_args(self, who, tensors):
         args = []
         for name in _OUTPUTS:
             t = tensors.get(name)
@@ -155,15 +152,33 @@ class FrameStore:
                 args.append(None)
                 continue
             if not (torch.is_tensor(t) and t.dim() == 5 and t.dtype == torch.float32 and t.is_contiguous()):
-                raise TfluidsError("frames gather: %s must be a contiguous float32 [B, C, Z, Y, X] tensor" % name)
+                raise TfluidsError("frames %s: %s must be a contiguous float32 [B, C, Z, Y, X] tensor" % (who, name))
             if t.device != self.device:
-                raise TfluidsError("frames gather: %s is on %s, the store on %s (a CPU tensor? there is no CPU path)"
-                                   % (name, t.device, self.device))
+                raise TfluidsError("frames %s: %s is on %s, the store on %s (a CPU tensor? there is no CPU path)"
+                                   % (who, name, t.device, self.device))
             args.append(tfluids._tt(t))
+        return args
+
+    def gather(self, slots, tensors):
+        """tfl_frames_gather: item i of every tensor in `tensors` (a dict by output name -- pDiv, UDiv, flags, densityDiv,
+        pTarget, UTarget, densityTarget; missing or None: skipped) = slot slots[i]. One launch per 128 items, on the current
+        stream; nothing waits. A call captured into a graph replays the slots it was recorded with."""
+        args = self._tensor_args("gather", tensors)
         slots = [int(s) for s in slots]
         lib, ctx = tfluids._context(self._anchor)
         idx = (ctypes.c_int32 * max(len(slots), 1))(*slots)
         tfluids._call(lib, ctx, lib.tfl_frames_gather(ctx, self._h, len(slots), idx, *args))
+
+    def put_device(self, slots, tensors):
+        """tfl_frames_put_device, the gather's mirror: item i of every tensor in `tensors` (a dict by the gather's names; missing
+        or None: the planes it feeds keep what they hold) into slot slots[i], HBM and host-mapped slots alike. One launch per 128
+        items on the current stream, no host round trip, nothing waits; a slot may appear only once per call. A record can be
+        filled in two calls: pDiv / UDiv / flags / densityDiv first, pTarget / UTarget / densityTarget later."""
+        args = self._tensor_args("put_device", tensors)
+        slots = [int(s) for s in slots]
+        lib, ctx = tfluids._context(self._anchor)
+        idx = (ctypes.c_int32 * max(len(slots), 1))(*slots)
+        tfluids._call(lib, ctx, lib.tfl_frames_put_device(ctx, self._h, len(slots), idx, *args))
 
     def close(self):
         if self._h:
@@ -178,6 +193,24 @@ class FrameStore:
             self.close()
         except Exception:      # noqa: BLE001
             pass
+
+
+def max_target_divergence(store, is3D, dims, first, n, chunk=16):
+    """data_binary.lua:122-127 on store slots [first, first + n): the SIGNED maximum of velocityDivergence(U target, flags)
+    (the loader's filter, and the generator's: fluidnet_amd.datagen)"""
+    dims = tuple(dims)
+    c = min(chunk, n)
+    U = torch.empty((c, 3 if is3D else 2) + dims, device=store.device)
+    flags = torch.empty((c, 1) + dims, device=store.device)
+    div = torch.empty_like(flags)
+    worst = None
+    for i in range(0, n, c):
+        m = min(c, n - i)
+        store.gather(range(first + i, first + i + m), dict(UTarget=U, flags=flags))
+        tfluids.velocityDivergenceForward(U[:m], flags[:m], div[:m])
+        cur = div[:m].max()
+        worst = cur if worst is None else torch.maximum(worst, cur)
+    return float(worst.item())
 
 
 class DataBinary:
@@ -231,20 +264,34 @@ class DataBinary:
         self.samples = np.asarray(samples, np.int64).reshape(-1, 2)
         self.capacity, self.device_frames = self.store.capacity, self.store.device_frames
 
+    @classmethod
+    def from_store(cls, store, runs, is3D, dims):
+        """The same surface over a store that was filled on the device (datagen.generate: FrameStore.put_device), without a file
+        read. runs: [(name, ntimesteps)] in slot order -- run r's frames lie in the slots behind those of runs 0 .. r - 1, sample i
+        in slot i as after __init__. Nothing is checked or filtered here: the generator has applied the divergence threshold.
+        The store stays the caller's: the data set reads it and does not copy it, it must outlive the data set's last batch, and
+        close() closes THAT store (FrameStore.close may be called twice) -- a caller that goes on using the store does not call it."""
+        dims = tuple(int(v) for v in dims)
+        if bool(is3D) != store.is3D or dims != tuple(store.dims):
+            raise TfluidsError("from_store: is3D / dims %s %s differ from the store's %s %s" % (bool(is3D), dims, store.is3D, store.dims))
+        self = cls.__new__(cls)
+        self.dataDir = self.dataset = self.prefix = None
+        self.store, self.device = store, store.device
+        self.is3D, (self.zdim, self.ydim, self.xdim) = bool(is3D), dims
+        self.runs, samples = [], []
+        for name, n in runs:
+            samples.extend((len(self.runs), f) for f in range(int(n)))
+            self.runs.append(dict(dir=str(name), ntimesteps=int(n), xdim=self.xdim, ydim=self.ydim, zdim=self.zdim, is3D=self.is3D))
+        if not self.runs or not samples:
+            raise TfluidsError("from_store: no runs")
+        if len(samples) > store.capacity:
+            raise TfluidsError("from_store: %d samples, the store holds %d slots" % (len(samples), store.capacity))
+        self.samples = np.asarray(samples, np.int64).reshape(-1, 2)
+        self.capacity, self.device_frames = store.capacity, store.device_frames
+        return self
+
     def _max_target_divergence(self, first, n, chunk=16):
-        """data_binary.lua:122-127: the SIGNED maximum of velocityDivergence(U target, flags) over slots [first, first + n)"""
-        c = min(chunk, n)
-        U = torch.empty(c, 3 if self.is3D else 2, self.zdim, self.ydim, self.xdim, device=self.device)
-        flags = torch.empty(c, 1, self.zdim, self.ydim, self.xdim, device=self.device)
-        div = torch.empty_like(flags)
-        worst = None
-        for i in range(0, n, c):
-            m = min(c, n - i)
-            self.store.gather(range(first + i, first + i + m), dict(UTarget=U, flags=flags))
-            tfluids.velocityDivergenceForward(U[:m], flags[:m], div[:m])
-            cur = div[:m].max()
-            worst = cur if worst is None else torch.maximum(worst, cur)
-        return float(worst.item())
+        return max_target_divergence(self.store, self.is3D, (self.zdim, self.ydim, self.xdim), first, n, chunk)
 
     def close(self):
         if self.store is not None:

@@ -249,6 +249,8 @@ typedef struct tfl_sim_state {
 int64_t tfl_simulate_workspace_floats(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state);
 int tfl_simulate_step(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state, float* workspace,
                       int64_t workspace_floats);
+int tfl_simulate_project(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state, float* workspace,
+                         int64_t workspace_floats);
 int tfl_packPlanes(tfl_ctx* ctx, int n, const tfl_tensor* const* fields, int zlo, int zhi, float* buf,
                    int unpack);
 int tfl_set_z_window(tfl_ctx* ctx, int a0, int a1, int b0, int b1);
@@ -325,6 +327,20 @@ int tfl_frames_gather(tfl_ctx* ctx, tfl_frames* frames, int n, const int32_t* h_
                       const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
                       const tfl_tensor* densityDiv, const tfl_tensor* pTarget, const tfl_tensor* UTarget,
                       const tfl_tensor* densityTarget);
+int tfl_frames_put_device(tfl_ctx* ctx, tfl_frames* frames, int n, const int32_t* h_slots,
+                          const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
+                          const tfl_tensor* densityDiv, const tfl_tensor* pTarget, const tfl_tensor* UTarget,
+                          const tfl_tensor* densityTarget);
+typedef struct tfl_scene_prim {
+  int32_t kind;
+  float a[3];
+  float b[3];
+  float val;
+} tfl_scene_prim;
+int tfl_scene_flags(tfl_ctx* ctx, const tfl_scene_prim* obstacles, int n_obstacles, const tfl_scene_prim* blobs, int n_blobs,
+                    int is3D, const tfl_tensor* flags, const tfl_tensor* density);
+int tfl_noise_potential(tfl_ctx* ctx, uint32_t seed, uint32_t run, const tfl_tensor* psi);
+int tfl_curl_mac(tfl_ctx* ctx, const tfl_tensor* psi, float amp, int is3D, const tfl_tensor* U);
 ]]
 -- END generated cdef
 

@@ -494,6 +494,20 @@ def simulate_native(conf, mconf, batch, model, outputDiv=False):
     del keep
 
 
+def project(conf, mconf, batch, model=None):
+    """The second half of the step as its own call (tfl_simulate_project): the projection phase of simulate() -- [setWallBcs,]
+    setConstVals, the ConvNet | Jacobi | PCG projection, setConstVals, the clamp -- on a batch whose UDiv holds the post-force
+    velocity, i.e. what simulate(..., outputDiv=True) leaves. simulate(outputDiv=True) followed by project() leaves the bits
+    of one simulate(); between the two the divergent state can be read (the data-set generator stores it)."""
+    U = batch["UDiv"]
+    lib, ctx = tfluids._context(U)
+    prm, st, keep = _native_args(lib, ctx, mconf, batch, model, False)
+    nws = int(lib.tfl_simulate_workspace_floats(ctx, ctypes.byref(prm), ctypes.byref(st)))
+    ws = tfluids.getTempStorage(U, [(nws,)])[0]
+    tfluids._call(lib, ctx, lib.tfl_simulate_project(ctx, ctypes.byref(prm), ctypes.byref(st), ctypes.c_void_p(ws.data_ptr()), nws))
+    del keep
+
+
 class GraphedSimulate:
     """simulate() captured once into a HIP graph and replayed: one host call per step instead of ~25
     kernel launches + Python dispatch. The reference's 2-D path is launch-bound (~70

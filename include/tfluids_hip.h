@@ -673,6 +673,16 @@ typedef struct tfl_sim_state {
 int64_t tfl_simulate_workspace_floats(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state);
 int tfl_simulate_step(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state, float* workspace,
                       int64_t workspace_floats);
+/* The second half of the step as its own entry: the projection phase of tfl_simulate_step alone (simulate.lua:247-326: [setWallBcs,]
+ * setConstVals, the ConvNet | Jacobi | PCG projection, setConstVals, U:clamp) on a state whose U already holds the post-force
+ * velocity and whose p holds the previous pressure -- what a tfl_simulate_step call with params->outputDiv = 1 leaves.
+ * Contract: an outputDiv = 1 step followed by tfl_simulate_project (same params but for outputDiv, which this entry does not read;
+ * same state) leaves the bits of ONE tfl_simulate_step with outputDiv = 0 -- for pcg, jacobi and convnet, in 2-D and 3-D, with and
+ * without BC pairs and density. Between the two calls the host may read the divergent state (the data-set generator stores it:
+ * fluidnet_amd/datagen.py) but must not write it. The workspace is the step's: tfl_simulate_workspace_floats, same alignment.
+ * tfl_simulate_step itself is not changed by this entry. */
+int tfl_simulate_project(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state, float* workspace,
+                         int64_t workspace_floats);
 
 /* ---- z-slab decomposition across the GPUs of a node (BASELINE config 5; no counterpart in the reference, which is
  * single-GPU). A rank holds planes [z_first, z_first + Zlocal) of a z_total-deep grid: the planes it OWNS,
@@ -977,6 +987,49 @@ int tfl_frames_gather(tfl_ctx* ctx, tfl_frames* frames, int n, const int32_t* h_
                       const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
                       const tfl_tensor* densityDiv, const tfl_tensor* pTarget, const tfl_tensor* UTarget,
                       const tfl_tensor* densityTarget);
+/* The mirror of tfl_frames_gather: item i < n of every non-NULL tensor is written into the plane(s) it feeds of slot h_slots[i],
+ * device slots and host-mapped slots alike -- ONE launch (k_frames_scatter) per 128 items, 128-bit stores on the slot side. The
+ * planes of a NULL tensor keep what they held, so a record can be filled in two calls: the divergent half (pDiv, UDiv, flags,
+ * densityDiv) first, the target half (pTarget, UTarget, densityTarget -> the record's p, U, density) later. The padding floats of
+ * a written plane are written as zero. The inputs are contiguous [B][1 or C][Z][Y][X] device tensors with n <= B.
+ * Validation is tfl_frames_gather's (range; n against every B; shapes; device memory of the context's device), before anything is
+ * launched -- a refused call has written nothing -- and a slot index that appears twice in one call is refused as well. The
+ * indices travel BY VALUE: no host read of device memory, no synchronisation, and the call can be captured into a graph, which
+ * then replays the slots it was recorded with. The write is ordered on the context's stream like any kernel: a gather
+ * enqueued behind it reads the new planes. Bit-exact: NaN payloads, -0 and denormals arrive as they were. */
+int tfl_frames_put_device(tfl_ctx* ctx, tfl_frames* frames, int n, const int32_t* h_slots,
+                          const tfl_tensor* pDiv, const tfl_tensor* UDiv, const tfl_tensor* flags,
+                          const tfl_tensor* densityDiv, const tfl_tensor* pTarget, const tfl_tensor* UTarget,
+                          const tfl_tensor* densityTarget);
+
+/* ---- the scene kernels of the data-set generator (csrc/datagen.hip, csrc/tfl_datagen.hpp) ---------------------
+ * No counterpart in the reference, whose sets come from a Mantaflow scene script outside its tree: these build this project's
+ * own random scenes. Every value is a function of the arguments alone, in fp32 / uint32 arithmetic of one stated order
+ * (tfl_datagen.hpp), so a numpy restatement gives the same bits.
+ *
+ * One primitive in cell units, tested at the cell centres (i + 0.5, j + 0.5, k + 0.5), x first:
+ *   kind 0, sphere: a = centre, b[0] = radius: inside where ((dx dx + dy dy) + dz dz) <= r r (2-D: no dz term)
+ *   kind 1, box:    a = lo, b = hi: inside where lo <= centre <= hi on every axis (2-D: x and y)
+ * val is the density of a blob; the obstacle table does not read it. */
+typedef struct tfl_scene_prim {
+  int32_t kind;
+  float a[3];
+  float b[3];
+  float val;
+} tfl_scene_prim;
+/* flags ([B][1][Z][Y][X], every item alike) = emptyDomain(bnd = 1) with every cell whose centre lies in one of the n_obstacles
+ * <= 32 primitives made an obstacle; density (same shape, or NULL) = the val of the LAST of the n_blobs <= 32 blobs that holds
+ * the cell's centre, +0 outside all of them and in every non-fluid cell. One launch (k_scene_flags). */
+int tfl_scene_flags(tfl_ctx* ctx, const tfl_scene_prim* obstacles, int n_obstacles, const tfl_scene_prim* blobs, int n_blobs,
+                    int is3D, const tfl_tensor* flags, const tfl_tensor* density);
+/* White noise into psi ([B][1][Z][Y][X] in 2-D, [B][3][Z][Y][X] in 3-D): the value of cell t of channel c of item b is
+ * (int(h >> 8) - 2^23) * 2^-23 with h = mix(mix(mix(mix(seed + 0x9e3779b9) ^ (run + b)) ^ c) ^ t), mix a lowbias32-style uint32
+ * mixer (tfl_datagen.hpp noise_mix): independent of the launch geometry, a multiple of 2^-23 in [-1, 1). (k_noise_potential) */
+int tfl_noise_potential(tfl_ctx* ctx, uint32_t seed, uint32_t run, const tfl_tensor* psi);
+/* U = amp * the MAC-staggered discrete curl of the edge-located potential psi (2-D: u = d_y psi, v = -(d_x psi); 3-D: the three
+ * components d_y psi_z - d_z psi_y, d_z psi_x - d_x psi_z, d_x psi_y - d_y psi_x; d_a f = f(+1 along a) - f, the neighbour index
+ * clamped at the grid's end). Its discrete MAC divergence is zero but for rounding. psi and U must not alias. (k_curl_mac) */
+int tfl_curl_mac(tfl_ctx* ctx, const tfl_tensor* psi, float amp, int is3D, const tfl_tensor* U);
 
 #ifdef __cplusplus
 }
