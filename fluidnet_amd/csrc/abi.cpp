@@ -1,7 +1,7 @@
 // abi.cpp -- the fluid operators of the C ABI of libtfluids_hip.so (include/tfluids_hip.h): argument validation that
 // mirrors torch/tfluids/init.lua's asserts, then kernel launches on the context's stream. The operators a native step calls
 // come first in their tfl:: forms (tfl_ops.hpp), then every public tfl_* operator. The context is context.cpp's, the
-// projection ConvNet model_host.cpp's.
+// projection ConvNet model_build.cpp's, model_host.cpp's, model_train.cpp's and optim_host.cpp's (tfl_model.hpp).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>

@@ -1,5 +1,5 @@
-// tfl_abi.hpp -- what the .cpp files behind include/tfluids_hip.h share (context.cpp, abi.cpp, model_host.cpp, simulate.cpp,
-// simulate_slab.cpp; private to them -- of the .hip files only frames.hip, which holds its entries' host side, includes it): the batch limit, the error return, the argument checks that mirror
+// tfl_abi.hpp -- what the .cpp files behind include/tfluids_hip.h share (context.cpp, abi.cpp, model_build.cpp, model_host.cpp,
+// model_train.cpp, optim_host.cpp, simulate.cpp, simulate_slab.cpp; private to them -- of the .hip files only frames.hip, which holds its entries' host side, includes it): the batch limit, the error return, the argument checks that mirror
 // torch/tfluids/init.lua's asserts, and the two early-return macros. The checks are inline: every operator runs several per call,
 // and as calls into another translation unit they measured 0.1 - 0.5 % on the benchmark's step. fail() is context.cpp's.
 // (What only the two native steps share is tfl_step.hpp, inline for the same reason.)

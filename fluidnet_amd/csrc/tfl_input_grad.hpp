@@ -1,7 +1,7 @@
 // tfl_input_grad.hpp -- the host arithmetic of tfl_model_backward_input: where the net input's fields sit among
 // its channel planes, the width of the first layer's data gradient, and the workspace layout behind tfl_model_backward's own.
 // Plain C++ without a HIP call, so that a stand-alone host program can walk all of it under a sanitizer
-// (tests/input_grad_layout_host.cpp); model_host.cpp and input_grad.hip include it.
+// (tests/input_grad_layout_host.cpp); model_build.cpp, model_train.cpp and input_grad.hip include it.
 #pragma once
 #include <cstdint>
 #include <vector>

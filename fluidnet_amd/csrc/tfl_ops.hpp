@@ -1,7 +1,7 @@
 // tfl_ops.hpp -- library-internal (C++ linkage) forms of the operators that the native steps call (simulate.cpp: the un-cut
 // step; simulate_slab.cpp: the z-slab rank-step): each takes
 // the public tfl_* operator's arguments plus where it computes and which passes run (tfl_host.hpp Scope) and a request (Ask).
-// The public operator (abi.cpp, model_host.cpp) passes scope_of(its context) and an empty Ask; a native step passes scopes of its own.
+// The public operator (abi.cpp, model_host.cpp, model_train.cpp) passes scope_of(its context) and an empty Ask; a native step passes scopes of its own.
 #pragma once
 #include "../../include/tfluids_hip.h"
 #include "tfl_host.hpp"

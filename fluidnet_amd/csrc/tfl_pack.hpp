@@ -1,7 +1,7 @@
 // tfl_pack.hpp -- the host packers of the projection ConvNet's own weight forms: the split-fp16 A fragments of conv_mfma16.hip
 // (conv3_m16_pack_weights / _pack_tail, with the integer float -> half conversion they round with) and the fp32 forms of the
 // two default topologies (the MFMA B fragments, the Winograd transform, the tail pack). Plain C++ without a HIP call:
-// model_host.cpp packs with them at creation and in tfl_model_set_weights, and a stand-alone host program holds the device
+// model_build.cpp packs with them at creation and in tfl_model_set_weights, and a stand-alone host program holds the device
 // refresh maps (tfl_refresh.hpp) to them byte for byte (tests/refresh_layout_host.cpp).
 #pragma once
 #include <cmath>
@@ -153,7 +153,7 @@ inline float conv3_m16_pack_weights(const float* w, int cin, uint16_t* out) {
   return ldexpf(1.0f, -(11 + e));
 }
 
-// ---- the fp32 forms of the two default topologies (model_host.cpp pack_default3 / pack_default2 upload them) --------------
+// ---- the fp32 forms of the two default topologies (model_build.cpp pack_default3 / pack_default2 upload them) --------------
 // 3-D default, one k = 3 layer: the per-lane B fragments of conv_mfma.hip, [c][kz][ky][64 lanes]
 inline void pack_bfrag3(const float* w, int ci_n, std::vector<float>& frag) {
   frag.assign((size_t)ci_n * 9 * 64, 0.0f);

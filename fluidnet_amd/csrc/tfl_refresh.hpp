@@ -28,7 +28,7 @@ constexpr int kRefreshMaxLayers = 32;
 struct RefreshSrc { const float* w[kRefreshMaxLayers]; const float* b[kRefreshMaxLayers]; };
 
 // ---- the generic forms of every layer: w [sub][tap][cin][cout], b [sub][cout], wt [tap][cout][cin_t], ws [tap] ---------------
-// One entry per layer of the model's device table (built at creation): destinations and map parameters (model_host.cpp tfl_layer)
+// One entry per layer of the model's device table (built at creation): destinations and map parameters (tfl_model.hpp tfl_layer)
 struct RefreshLayer {
   float *w, *b, *wt;          // wt = null: the layer holds no data-gradient form
   int S, taps, cin, cout;     // sub-positions (ConvolutionUpsample), taps, padded channel counts

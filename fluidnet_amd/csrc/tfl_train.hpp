@@ -1,7 +1,7 @@
 // tfl_train.hpp -- the host arithmetic of the training side of the projection ConvNet (tfl_model_set_weights, _forward_train,
 // _backward): weight re-layouts, the tape and workspace layouts with their size checks, the chunking of the weight-gradient
 // kernel and the map from its (row, co) results back to the cudnn layout. Plain C++ without a HIP call, so that a stand-alone
-// host program can run all of it under a sanitizer (tests/train_layout_host.cpp); model_host.cpp and conv_bwd.hip include it.
+// host program can run all of it under a sanitizer (tests/train_layout_host.cpp); tfl_model.hpp (for model_build.cpp and model_train.cpp) and conv_bwd.hip include it.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -17,7 +17,7 @@
 
 using namespace tfl;
 
-// a banked model as model_host.cpp's train_layers / train_banks describe it: `pre` trunk stages, `nst` banked stages of n banks,
+// a banked model as model_train.cpp's train_layers / train_banks describe it: `pre` trunk stages, `nst` banked stages of n banks,
 // `post` trunk stages (the last one the 1-channel output); c channels, kernel size k in the banked stages
 struct Model { std::vector<TrainLayer> L; TrainBanks bk; };
 static Model make(bool is3d, int n, bool mres, bool concat, int pre, int nst, int post, int in_c, int c, int k, bool skip) {
@@ -209,7 +209,7 @@ static void check_join_weight_map(int n, int join_c, int join_p, int cout_ref, i
       hit[(size_t)i]++;
       const int cr = (int)((i / taps) % cin_ref), plane = row / taps;
       CHECK(i / ((long long)taps * cin_ref) == co && i % taps == row % taps);
-      CHECK(plane == (cr / join_c) * join_p + cr % join_c);        // (model_host.cpp upload_layer's cmap)
+      CHECK(plane == (cr / join_c) * join_p + cr % join_c);        // (model_build.cpp upload_layer's cmap)
     }
   for (int h : hit) CHECK(h == 1);
 }

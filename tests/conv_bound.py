@@ -64,7 +64,7 @@ def topology(layers):
 
 
 def conv_path(model, env_path=None):
-    """The forward tfl_model_create picks for `model` (model_host.cpp ConvPath) with TFL_CONV_PATH = env_path (None = unset)."""
+    """The forward tfl_model_create picks for `model` (tfl_model.hpp ConvPath) with TFL_CONV_PATH = env_path (None = unset)."""
     custom = S.model_opts(model.opts) != S.model_opts(None)
     if model.graph is not None or custom or any(v > 1 for v in model.pool + model.up):
         return "fp32"
@@ -240,7 +240,7 @@ class BoundEval:
         return ap(a, 2), ap(e, 2) + gamma(2 ** self.dim - 1) * ap(a.abs() + e, 2)
 
     def bn(self, v, d):
-        # model_host.cpp bn_fold: sc = w / sqrt(var + eps), sh = b - mean sc in fp64, each rounded to fp32 once; y = fmaf(v, sc, sh)
+        # model_build.cpp bn_fold: sc = w / sqrt(var + eps), sh = b - mean sc in fp64, each rounded to fp32 once; y = fmaf(v, sc, sh)
         a, e = v
         sh_ = (1, -1) + (1,) * self.dim
         wt = np.ones_like(d["running_mean"], np.float64) if d.get("weight") is None else np.asarray(d["weight"], np.float64)

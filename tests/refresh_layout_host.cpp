@@ -27,7 +27,7 @@ template <class T> static bool same_bytes(const std::vector<T>& a, const std::ve
   return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
 }
 
-// ---- the generic forms: one layer as model_host.cpp build_layers lays it out ------------------------------------------------
+// ---- the generic forms: one layer as model_build.cpp build_layers lays it out -----------------------------------------------
 static RefreshLayer layer_of(bool is3d, int k, int up, int cin_ref, int cout_ref, int cin_p, int cout_p, int join_c, int join_p, bool skip_in,
                              bool transposed) {
   RefreshLayer L{};
@@ -43,7 +43,7 @@ static void check_layer(const RefreshLayer& L) {
   std::vector<float> w((size_t)L.cout_ref * L.S * L.cin_ref * L.taps), b((size_t)L.cout_ref * L.S);
   for (float& v : w) v = rnd();
   for (float& v : b) v = rnd();
-  auto cmap = [&](int ci) {      // model_host.cpp upload_layer
+  auto cmap = [&](int ci) {      // model_build.cpp upload_layer
     return (L.skip_in && ci == L.cin_ref - 1) ? L.cin - 1 : L.join_c > 0 ? (ci / L.join_c) * L.join_p + ci % L.join_c : ci;
   };
   std::vector<float> relaid, bias_p, wt;
