@@ -434,23 +434,27 @@ int tfl_solveLinearSystemPCG(tfl_ctx* c, const tfl_tensor* p, const tfl_tensor* 
   char msg[256] = {0};
   // the pipelined sweeps need every sub-box resident at once: when something else holds part of the GPU they time out (~1 s)
   // and the solve is repeated with one launch per hyperplane -- remembered per context, so that only the FIRST solve pays
-  int rc = tfl::pcg_solve(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, p->data, flags->data, div->data,
-                          pc, tol, maxIter, verbose, workspace, residual, msg, sizeof(msg), c->wf_skip == 0);
+  const tfl::PcgProblem q{is3D != 0, flags->B, flags->Z, flags->Y, flags->X, p->data, flags->data, div->data, pc, tol, maxIter, verbose};
+  auto solve = [&](bool allow_wavefronts) {
+    return tfl::pcg_solve(c->stream, q, workspace, residual, msg, sizeof(msg), allow_wavefronts);
+  };
+  tfl::PcgResult rc = solve(c->wf_skip == 0);
   if (c->wf_skip > 0) c->wf_skip--;
-  if (rc == -5) {
+  if (rc == tfl::PcgResult::wavefront_timeout) {
     // back off for 16, 32, ... 1024 solves, then try the pipelined sweeps again; say so once per latch
     c->wf_timeouts++;
     c->wf_skip = 16 << (c->wf_timeouts < 7 ? c->wf_timeouts - 1 : 6);
     fprintf(stderr, "[tfl] solveLinearSystemPCG: a pipelined triangular sweep timed out (something else holds part of the GPU?); "
                     "this solve and the next %d on this context use hyperplane sweeps (slower), then the pipelined form is retried\n", c->wf_skip);
+    rc = solve(false);
   }
-  if (rc == -5)
-    rc = tfl::pcg_solve(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, p->data, flags->data, div->data,
-                        pc, tol, maxIter, verbose, workspace, residual, msg, sizeof(msg), false);
-  if (rc == -1 || rc == -3) return fail(c, TFL_EINVAL, "%s", msg);
-  if (rc == -2) return fail(c, TFL_EINVAL, "%s", msg);
-  if (rc != 0) return fail(c, TFL_EHIP, "%s", msg);
-  return check_launch(c, "solveLinearSystemPCG");
+  switch (rc) {
+    case tfl::PcgResult::ok: return check_launch(c, "solveLinearSystemPCG");
+    case tfl::PcgResult::bad_flags:
+    case tfl::PcgResult::nan_residual:
+    case tfl::PcgResult::too_many_components: return fail(c, TFL_EINVAL, "%s", msg);
+    default: return fail(c, TFL_EHIP, "%s", msg);
+  }
 }
 
 int64_t tfl_normalize_workspace_floats(int32_t Z, int32_t Y, int32_t X) { return tfl::npm_workspace_floats(Z, Y, X); }
@@ -465,9 +469,9 @@ int tfl_normalizePressureMean(tfl_ctx* c, const tfl_tensor* p, const tfl_tensor*
     return fail(c, TFL_EINVAL, "normalizePressureMean: workspace too small (tfl_normalize_workspace_floats)");
   if ((long long)flags->Z * flags->Y * flags->X >= (1ll << 31)) return fail(c, TFL_EINVAL, "normalizePressureMean: grid too large for 32-bit cell indices");
   char msg[256] = {0};
-  const int rc = tfl::normalize_pressure_mean(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, p->data,
-                                              flags->data, workspace, msg, sizeof(msg));
-  if (rc != 0) return fail(c, TFL_EHIP, "%s", msg);
+  const tfl::PcgResult rc = tfl::normalize_pressure_mean(c->stream, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, p->data,
+                                                         flags->data, workspace, msg, sizeof(msg));
+  if (rc != tfl::PcgResult::ok) return fail(c, TFL_EHIP, "%s", msg);
   return check_launch(c, "normalizePressureMean");
 }
 

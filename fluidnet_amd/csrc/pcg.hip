@@ -23,8 +23,14 @@
 //     iteration run as PIPELINED WAVEFRONTS on 3-D grids -- two launches instead of ~760 at 128^3 (k_wf_sweep below). 2-D grids keep the
 //     launch-per-hyperplane sweeps; 3-D grids with more than 240 sub-boxes run the wavefronts one range of slabs per launch.
 // Dot products are two-stage fp64 reductions with a fixed order (bit-reproducible run to run).
+//
+// The file: the kernels; then the host code. The caller's workspace is laid out by ONE table (tfl_pcg_ws.hpp: pcg_ws / npm_ws,
+// which also size it), pcg_solve is the struct `Solve` -- the views of that table and the phases item / read_components /
+// component / begin / factor / build_wavefront_operands / precondition / iteration / run_chunks / write_back -- and
+// label_components is shared with normalize_pressure_mean. Results are named (PcgResult, tfl_host.hpp).
 #include "tfl_device.hpp"
 #include "tfl_host.hpp"
+#include "tfl_pcg_ws.hpp"
 #include "tfl_vec4.hpp"
 
 #include <algorithm>
@@ -33,27 +39,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <limits>
+#include <optional>
 #include <type_traits>
 #include <vector>
 
 namespace tfl {
 
 namespace {
-
-constexpr int kRedBlocks = 512;    // partial sums per dot product
-constexpr int kMaxComponents = 4096;
-
-// Device-resident solver state of one component solve.
-struct PcgState {
-  double rr1, rr0;         // current / previous ||r||^2
-  double num, prev_num;    // r.z of this / the previous iteration (preconditioned form)
-  double den;              // s.A s
-  float alpha, beta;
-  float tol2;
-  int iter, max_iter, done, first, bad;   // bad: a NaN residual was seen
-  int pending;                            // an update's r.r partials have not been folded into rr1 yet
-  double sum_x;
-};
 
 __device__ __forceinline__ float clamp_to_epsilon(float v) {   // generic/tfluids.cu:1203-1214
   const float eps = 1.17549435e-38f;
@@ -385,61 +377,20 @@ __global__ __launch_bounds__(256) void k_ilu_backward(const PcgState* __restrict
 //   forward    q = (((r + q_z) + q_y) + q_x) * cc          (q = y * c of the reference's forward solve)
 //   backward   z = q + ((z_x + z_y) + z_z) * cc
 // (the reference divides by R(m,m) / d(m) where this multiplies by reciprocals: inside the solver's tolerance).
-#ifndef TFL_WF_PLANES
-#define TFL_WF_PLANES 8
-#endif
-#ifndef TFL_WF_DEPTH
-#define TFL_WF_DEPTH 16
-#endif
-// kWfDepth: steps the operands are prefetched ahead; kWfHelperAhead: exchange intervals the helper wave prefetches the
-// predecessors' pairs ahead (a block can only run that far + the memory round trip behind its predecessor)
-#ifndef TFL_WF_LAG
-#define TFL_WF_LAG 2
-#endif
-#ifndef TFL_WF_HELPER_AHEAD
-#define TFL_WF_HELPER_AHEAD 4
-#endif
-constexpr int kWfRows = 64, kWfPlanes = TFL_WF_PLANES, kWfLag = TFL_WF_LAG, kWfDepth = TFL_WF_DEPTH, kWfHelperAhead = TFL_WF_HELPER_AHEAD, kWfMaxBlocks = 240;
-static_assert(kWfDepth % 4 == 0 && (kWfLag == 1 || kWfLag == 2 || kWfLag == 4), "operands in groups of four steps");
-static_assert(kWfHelperAhead >= 1 && (kWfDepth / kWfLag) % kWfHelperAhead == 0, "the helper's rotating slots repeat with the unrolled loop");
-static_assert(kWfPlanes * kWfLag <= 64, "one helper lane per (plane, step of the interval)");
+// The shape constants (kWfRows, kWfPlanes, kWfLag, kWfDepth, kWfHelperAhead, kWfGuard), WfGeom / wf_geom and the sizes of the
+// skewed and hand-off arrays are plain data shared with the host's workspace table: tfl_pcg_ws.hpp.
 
-struct WfGeom {
-  int X, Y, Z, ns, nb, NT;     // strips, slabs, steps per sub-box (a multiple of kWfDepth)
-  long long sub;               // cells of one sub-box in the skewed arrays = kWfPlanes * NT * kWfRows
-  int b_lo, b_cnt;             // the slabs [b_lo, b_lo + b_cnt) this launch works on (all strips of them)
-};
 // the sub-box of a workgroup: blocks of one launch are numbered strip-major over the launch's slabs
 __device__ __forceinline__ int wf_block(const WfGeom& g, int& sidx, int& bidx) {
   sidx = (int)blockIdx.x / g.b_cnt;
   bidx = g.b_lo + ((int)blockIdx.x - sidx * g.b_cnt);
   return sidx * g.nb + bidx;
 }
-inline WfGeom wf_geom(int Z, int Y, int X) {
-  WfGeom g;
-  g.X = X; g.Y = Y; g.Z = Z;
-  g.ns = (Y - 2 + kWfRows - 1) / kWfRows; g.nb = (Z - 2 + kWfPlanes - 1) / kWfPlanes;
-  g.NT = (((X - 2) + (kWfRows - 1) + kWfLag * (kWfPlanes - 1)) + kWfDepth - 1) / kWfDepth * kWfDepth;
-  g.sub = (long long)kWfPlanes * g.NT * kWfRows;
-  g.b_lo = 0; g.b_cnt = g.nb;
-  return g;
-}
 inline bool wf_usable(bool is3d, int Z, int Y, int X) {
   if (!is3d || X < 3 || Y < 3 || Z < 3) return false;
   const bool off = sw::present(Sw::PCG_HYPERPLANES);     // A/B switch: the one-launch-per-hyperplane sweeps
   const WfGeom g = wf_geom(Z, Y, X);
   return !off && g.ns <= kWfMaxBlocks;      // (grids with more sub-boxes than fit the GPU at once run slab range by slab range)
-}
-// floats of: cc, r, q, z (skewed) | the slab hand-off pairs [block][t / 4][row][t % 4] | the strip hand-off pairs
-// [block][plane][t] | the error word
-// (floats, including kWfGuard pairs of padding at either end: the helper wave reads up to kWfLag * (kWfPlanes - 1) resp. 63 steps
-// past a block's rows without clamping)
-constexpr long long kWfGuard = 4 * kWfRows * (kWfLag * (kWfPlanes - 1) / 4 + 2);        // pairs; >= 64 too
-inline long long wf_handoff_k(const WfGeom& g) { return 2ll * g.ns * g.nb * g.NT * kWfRows + 4 * kWfGuard; }
-inline long long wf_handoff_s(const WfGeom& g) { return 2ll * g.ns * g.nb * kWfPlanes * g.NT + 4 * kWfGuard; }
-inline long long wf_floats(int Z, int Y, int X) {
-  const WfGeom g = wf_geom(Z, Y, X);
-  return 4 * g.sub * g.ns * g.nb + wf_handoff_k(g) + wf_handoff_s(g) + 64;
 }
 __device__ __forceinline__ long long wf_at(const WfGeom& g, int i, int j, int k) {
   const int s = (j - 1) / kWfRows, l = (j - 1) % kWfRows, b = (k - 1) / kWfPlanes, w = (k - 1) % kWfPlanes;
@@ -762,269 +713,361 @@ __global__ __launch_bounds__(256) void k_npm_sub(Dom d, const int* __restrict__ 
   p[o] = p[o] - (float)(sum_at[l] / (double)size_at[l]);
 }
 
+// ---- host code ------------------------------------------------------------------------------------------------------------
 inline int cdiv(long long a, int b) { return (int)((a + b - 1) / b); }
+
+template <class T>
+T* view(float* workspace, WsRegion r) { return reinterpret_cast<T*>(workspace + r.off); }
+
+// the caller's message buffer; a failed HIP call reads "<operator>: <what>: <the runtime's text>"
+struct Report {
+  const char* who;
+  char* msg;
+  size_t len;
+  bool ok(hipError_t e, const char* what) const {
+    if (e == hipSuccess) return true;
+    snprintf(msg, len, "%s: %s: %s", who, what, hipGetErrorString(e));
+    return false;
+  }
+};
+#define HIP_TRY(call, what) do { if (!er.ok(call, what)) return PcgResult::hip_error; } while (0)
+#define PCG_TRY(call) do { const PcgResult rc_ = (call); if (rc_ != PcgResult::ok) return rc_; } while (0)
+
+// a "k_cc" scope, or none
+struct CcTimer {
+  std::optional<KernelTimer> t;
+  CcTimer(bool on, hipStream_t st) { if (on) t.emplace("k_cc", st); }
+};
+
+// counters: [0] changed, [1] count, [2] border fluid
+PcgResult clear_component_counts(hipStream_t st, const Report& er, int* counters, int* size_at, long long n) {
+  HIP_TRY(hipMemsetAsync(counters, 0, 3 * sizeof(int), st), "memset");
+  HIP_TRY(hipMemsetAsync(size_at, 0, sizeof(int) * (size_t)n, st), "memset");
+  return PcgResult::ok;
+}
+
+// label[o] = the smallest cell index of o's fluid component (-1: no fluid): init, then hook + compress until a round changes
+// nothing. h_cnt: the counters as the last round left them. timed: with "k_cc" scopes of its own (init | each round), as
+// pcg_solve has them; normalize_pressure_mean keeps ONE scope around everything it launches for an item instead.
+PcgResult label_components(hipStream_t st, const Report& er, const Dom& d, bool is3d, const float* fl, int* label, int* counters,
+                           int h_cnt[3], bool timed) {
+  const int gcell = cdiv(d.sc, 256);
+  { CcTimer t(timed, st); k_cc_init<<<gcell, 256, 0, st>>>(d, is3d, fl, label, counters + 2); }
+  for (int round = 0;; round++) {
+    HIP_TRY(hipMemsetAsync(counters, 0, sizeof(int), st), "memset");
+    { CcTimer t(timed, st);
+      k_cc_hook<<<gcell, 256, 0, st>>>(d, is3d, label, counters);
+      k_cc_compress<<<gcell, 256, 0, st>>>(d, label); }
+    HIP_TRY(hipMemcpyAsync(h_cnt, counters, 3 * sizeof(int), hipMemcpyDeviceToHost, st), "memcpy");
+    HIP_TRY(hipStreamSynchronize(st), "sync");
+    if (!h_cnt[0]) return PcgResult::ok;
+    if (round > 100000) { snprintf(er.msg, er.len, "%s: component labelling did not converge", er.who); return PcgResult::hip_error; }
+  }
+}
+
+// One call of pcg_solve: the problem, the views of its workspace (tfl_pcg_ws.hpp), and what one phase hands to the next.
+struct Solve {
+  hipStream_t st;
+  const PcgProblem& q;
+  Report er;
+  Dom d;
+  long long n;
+  // the workspace
+  double *partials, *p_den, *p_rr;     // r.r of the set-up, r.z, the sum of x | s.w | r.r of the update
+  PcgState* S;
+  int *label, *size_at, *roots, *counters;
+  float *x, *r, *z, *s, *w, *dg, *y;
+  // pipelined wavefront sweeps (3-D): the skewed arrays (cc, r, q, z), the two hand-off arrays of {value, tag} pairs, an error word
+  bool wf;
+  WfGeom wg;
+  float *cs = nullptr, *rsk = nullptr, *qsk = nullptr, *zsk = nullptr;
+  float2 *wf_hk = nullptr, *wf_hs = nullptr;
+  int* wferr = nullptr;
+  size_t wf_clear_bytes = 0;
+  int wf_slabs = 1;                    // slabs per launch
+  int epoch = 0;                       // tag of the next sweep; the skewed arrays are zeroed with it
+  long long* wf_trace = nullptr;       // TFL_WF_TRACE
+  // launch sizes: per cell, per hyperplane, per interior cell; the hyperplanes h = i + j + k of the interior
+  int gcell, gwave, ginner = 0, hmin, hmax;
+  // the item and the component at hand
+  int b = 0, cidx = 0, root = 0, size = 0, pc = 0;
+  const float *fl = nullptr, *dv = nullptr;
+  float* pb = nullptr;
+  float max_res = -std::numeric_limits<float>::infinity();
+
+  Solve(hipStream_t st, const PcgProblem& q, float* workspace, char* msg, size_t msg_len, bool allow_wavefronts);
+  ~Solve() { if (wf_trace) (void)hipFree(wf_trace); }      // every exit frees it
+  PcgResult item(int b);
+  PcgResult read_components(int h_cnt[3], std::vector<int>& h_roots, std::vector<int>& h_sizes);
+  PcgResult component(int cidx, int root, int size);
+  void begin();
+  void factor();
+  PcgResult build_wavefront_operands();
+  template <bool IS3D, bool IC> void hyperplane_sweeps();
+  void precondition();
+  void iteration();
+  PcgResult wavefront_error();
+  PcgResult run_chunks();
+  void write_back();
+  void print_trace();
+};
+
+Solve::Solve(hipStream_t st_, const PcgProblem& q_, float* workspace, char* msg, size_t msg_len, bool allow_wavefronts)
+    : st(st_), q(q_), er{"solveLinearSystemPCG", msg, msg_len}, d(whole_dom(q_.Z, q_.Y, q_.X)), n(d.sc) {
+  wf = allow_wavefronts && wf_usable(q.is3d, q.Z, q.Y, q.X);
+  const PcgWs t = pcg_ws(q.Z, q.Y, q.X, wf);
+  partials = view<double>(workspace, t.partials); p_den = view<double>(workspace, t.p_den); p_rr = view<double>(workspace, t.p_rr);
+  S = view<PcgState>(workspace, t.state);
+  label = view<int>(workspace, t.label); size_at = view<int>(workspace, t.size_at);
+  x = view<float>(workspace, t.x); r = view<float>(workspace, t.r); z = view<float>(workspace, t.z); s = view<float>(workspace, t.s);
+  w = view<float>(workspace, t.w); dg = view<float>(workspace, t.dg); y = view<float>(workspace, t.y);
+  roots = view<int>(workspace, t.roots); counters = view<int>(workspace, t.counters);
+  wg = t.geom;
+  if (wf) {
+    float* wfb = workspace + pcg_wf_pad(workspace, t);      // 16-byte aligned (float4 rows, {value, tag} pairs)
+    cs = view<float>(wfb, t.wf_cc); rsk = view<float>(wfb, t.wf_r); qsk = view<float>(wfb, t.wf_q); zsk = view<float>(wfb, t.wf_z);
+    wf_hk = view<float2>(wfb, t.wf_hk) + kWfGuard; wf_hs = view<float2>(wfb, t.wf_hs) + kWfGuard;
+    wferr = view<int>(wfb, t.wf_err);
+    wf_clear_bytes = sizeof(float) * (size_t)t.wf_clear.floats;
+    // every sub-box of a launch must be resident (they wait for each other): at most wf_cap of them per launch
+    const int wf_cap = sw::present(Sw::WF_MAX_BLOCKS) ? std::max(1, sw::num(Sw::WF_MAX_BLOCKS, 0)) : kWfMaxBlocks;     // (tests: small launches)
+    wf_slabs = std::max(1, std::min(wf_cap, kWfMaxBlocks) / std::max(wg.ns, 1));
+    ginner = cdiv((long long)(q.X - 2) * (q.Y - 2) * (q.Z - 2), 256);
+    // development aid: TFL_WF_TRACE=1 prints when every sub-box of the last forward / backward sweep started and finished
+    if (sw::present(Sw::WF_TRACE) && q.precond && hipMalloc(&wf_trace, sizeof(long long) * 4 * wg.ns * wg.nb) != hipSuccess) wf_trace = nullptr;
+  }
+  gcell = cdiv(n, 256);
+  gwave = cdiv((long long)(q.Y - 2) * (q.is3d ? q.Z - 2 : 1), 256);
+  hmin = q.is3d ? 3 : 2; hmax = (q.X - 2) + (q.Y - 2) + (q.is3d ? q.Z - 2 : 0);
+}
+
+// one batch element: its components, then one CG solve per component
+PcgResult Solve::item(int b_) {
+  b = b_;
+  fl = q.flags + (long long)b * n; dv = q.div + (long long)b * n; pb = q.p + (long long)b * n;
+  int h_cnt[3] = {0, 0, 0};
+  PCG_TRY(clear_component_counts(st, er, counters, size_at, n));
+  PCG_TRY(label_components(st, er, d, q.is3d, fl, label, counters, h_cnt, true));
+  if (h_cnt[2] > 0) {   // generic/tfluids.cu:1083-1091 raises for a fluid cell on the border
+    snprintf(er.msg, er.len, "solveLinearSystemPCG: Non fluid cell found in a connected component or fluid cell found on the "
+             "domain border (%d fluid border cells)", h_cnt[2]);
+    return PcgResult::bad_flags;
+  }
+  std::vector<int> h_roots, h_sizes;
+  PCG_TRY(read_components(h_cnt, h_roots, h_sizes));
+  for (size_t c = 0; c < h_roots.size(); c++) PCG_TRY(component((int)c, h_roots[c], h_sizes[c]));
+  return PcgResult::ok;
+}
+
+// the components' count, their roots in scan order of the first cell (= the reference's numbering) and their sizes
+PcgResult Solve::read_components(int h_cnt[3], std::vector<int>& h_roots, std::vector<int>& h_sizes) {
+  { TFL_TIMED("k_cc", st); k_cc_count<<<gcell, 256, 0, st>>>(d, label, size_at, roots, counters + 1); }
+  HIP_TRY(hipMemcpyAsync(h_cnt, counters, 3 * sizeof(int), hipMemcpyDeviceToHost, st), "memcpy");
+  HIP_TRY(hipStreamSynchronize(st), "sync");
+  const int ncomp = h_cnt[1];
+  if (ncomp > kMaxComponents) {
+    snprintf(er.msg, er.len, "solveLinearSystemPCG: %d fluid components (the solver handles %d)", ncomp, kMaxComponents);
+    return PcgResult::too_many_components;
+  }
+  h_roots.resize(ncomp); h_sizes.resize(ncomp);
+  if (!ncomp) return PcgResult::ok;
+  HIP_TRY(hipMemcpy(h_roots.data(), roots, sizeof(int) * ncomp, hipMemcpyDeviceToHost), "memcpy roots");
+  std::sort(h_roots.begin(), h_roots.end());
+  for (int c = 0; c < ncomp; c++)
+    HIP_TRY(hipMemcpy(&h_sizes[c], size_at + h_roots[c], sizeof(int), hipMemcpyDeviceToHost), "memcpy size");
+  return PcgResult::ok;
+}
+
+PcgResult Solve::component(int cidx_, int root_, int size_) {
+  cidx = cidx_; root = root_; size = size_;
+  if (size == 1) {   // :1375-1383: no valid solution, pressure stays 0
+    if (q.verbose) printf("PCG batch %d component %d has size 1, skipping.\n", b + 1, cidx + 1);
+    return PcgResult::ok;
+  }
+  pc = q.precond;
+  if (size < 5) pc = 0;   // :1390-1393
+  if (q.verbose) printf("PCG batch %d component %d has size %d.\nPCG: %d component %d using precond type %s\n", b + 1, cidx + 1,
+                        size, b + 1, cidx + 1, pc == 0 ? "none" : (pc == 1 ? "ilu0" : "ic0"));
+  // z is only ever written on the component; its other cells must read as 0 in s = z and r.z
+  if (pc) HIP_TRY(hipMemsetAsync(z, 0, sizeof(float) * (size_t)n, st), "memset z");
+  begin();
+  if (pc) {
+    TFL_TIMED("k_pcg_precond", st);
+    factor();
+    if (wf) PCG_TRY(build_wavefront_operands());
+  }
+  PCG_TRY(run_chunks());
+  write_back();
+  return PcgResult::ok;
+}
+
+void Solve::begin() {
+  TFL_TIMED("k_pcg", st);
+  k_pcg_setup<<<kRedBlocks, 256, 0, st>>>(n, label, root, dv, x, r, s, partials);
+  k_pcg_begin<<<1, 256, 0, st>>>(S, partials, q.tol, q.max_iter);
+}
+
+// the diagonal of ILU(0) / IC(0): one launch per hyperplane
+void Solve::factor() {
+  for (int h = hmin; h <= hmax; h++) {
+    if (q.is3d) k_ilu_factor<true><<<gwave, 256, 0, st>>>(d, h, fl, label, root, dg);
+    else k_ilu_factor<false><<<gwave, 256, 0, st>>>(d, h, fl, label, root, dg);
+  }
+}
+
+// the skewed arrays and both hand-off arrays zeroed (with them the tags: epoch starts over), cc from the factor's diagonal
+PcgResult Solve::build_wavefront_operands() {
+  HIP_TRY(hipMemsetAsync(cs, 0, wf_clear_bytes, st), "memset skewed arrays");
+  epoch = 0;
+  if (pc == 2) k_wf_build<true><<<ginner, 256, 0, st>>>(wg, d, label, root, dg, cs);
+  else k_wf_build<false><<<ginner, 256, 0, st>>>(wg, d, label, root, dg, cs);
+  return PcgResult::ok;
+}
+
+// M^-1 r with one launch per hyperplane and sweep
+template <bool IS3D, bool IC>
+void Solve::hyperplane_sweeps() {
+  for (int h = hmin; h <= hmax; h++) k_ilu_forward<IS3D, IC><<<gwave, 256, 0, st>>>(S, d, h, fl, label, root, dg, r, y);
+  for (int h = hmax; h >= hmin; h--) k_ilu_backward<IS3D, IC><<<gwave, 256, 0, st>>>(S, d, h, fl, label, root, dg, y, z);
+}
+
+// z = M^-1 r
+void Solve::precondition() {
+  TFL_TIMED("k_pcg_precond", st);
+  if (!wf) {
+    if (q.is3d) { if (pc == 2) hyperplane_sweeps<true, true>(); else hyperplane_sweeps<true, false>(); }
+    else { if (pc == 2) hyperplane_sweeps<false, true>(); else hyperplane_sweeps<false, false>(); }
+    return;
+  }
+  // as two launches (pipelined wavefronts)
+  const int nblk = wg.ns * wg.nb;
+  k_wf_skew<true><<<ginner, 256, 0, st>>>(S, wg, d, r, rsk);
+  // every sub-box of a launch must be resident (they wait for each other): at most wf_cap of them per launch,
+  // all strips of a range of slabs, the ranges in sweep order -- a later launch finds its predecessors' pairs
+  // waiting under the same tag
+  ++epoch;
+  for (int b0 = 0; b0 < wg.nb; b0 += wf_slabs) {
+    WfGeom c = wg; c.b_lo = b0; c.b_cnt = std::min(wf_slabs, wg.nb - b0);
+    k_wf_sweep<1><<<wg.ns * c.b_cnt, (kWfPlanes + 2) * 64, 0, st>>>(S, c, WfArrays{cs, rsk, qsk, wf_hk, wf_hs, wferr, wf_trace}, epoch);
+  }
+  ++epoch;
+  for (int b1 = wg.nb; b1 > 0; b1 -= wf_slabs) {
+    WfGeom c = wg; c.b_lo = std::max(b1 - wf_slabs, 0); c.b_cnt = b1 - c.b_lo;
+    k_wf_sweep<-1><<<wg.ns * c.b_cnt, (kWfPlanes + 2) * 64, 0, st>>>(S, c, WfArrays{cs, qsk, zsk, wf_hk, wf_hs, wferr, wf_trace ? wf_trace + 2 * nblk : nullptr}, epoch);
+  }
+  k_wf_skew<false><<<ginner, 256, 0, st>>>(S, wg, d, z, zsk);
+}
+
+// one CG iteration, enqueued: every kernel returns at once when the state says `done`
+void Solve::iteration() {
+  k_pcg_top<<<1, 256, 0, st>>>(S, p_rr, 1);
+  if (pc) precondition();
+  TFL_TIMED("k_pcg", st);
+  if (pc) k_pcg_dot<<<kRedBlocks, 256, 0, st>>>(S, n, r, z, partials);
+  k_pcg_dir<<<kRedBlocks, 256, 0, st>>>(S, n, partials, pc ? 1 : 0, pc ? z : r, s);
+  if (q.is3d) k_pcg_apply<true><<<kRedBlocks, 256, 0, st>>>(S, d, fl, label, root, s, w, p_den);
+  else k_pcg_apply<false><<<kRedBlocks, 256, 0, st>>>(S, d, fl, label, root, s, w, p_den);
+  k_pcg_update<<<kRedBlocks, 256, 0, st>>>(S, n, p_den, s, w, x, r, p_rr);
+}
+
+// the error word of the pipelined sweeps, read after a chunk
+PcgResult Solve::wavefront_error() {
+  int e = 0;
+  HIP_TRY(hipMemcpy(&e, wferr, sizeof(int), hipMemcpyDeviceToHost), "memcpy");
+  if (sw::present(Sw::WF_TEST_TIMEOUT)) e = 1;     // tests: exercise the caller's fallback
+  // (its sub-boxes wait for each other, so all of them must be resident at once: not the case when something else holds
+  // part of the GPU. The caller repeats the solve with one launch per hyperplane.)
+  if (!e) return PcgResult::ok;
+  snprintf(er.msg, er.len, "solveLinearSystemPCG: a block of the pipelined triangular solve never saw its predecessor");
+  return PcgResult::wavefront_timeout;
+}
+
+// the iterations of one component: a chunk enqueued, then the state read back
+PcgResult Solve::run_chunks() {
+  PcgState hs;
+  const int chunk = q.verbose ? 1 : (pc ? (wf ? 16 : 4) : 32);
+  for (;;) {
+    for (int it = 0; it < chunk; it++) iteration();
+    { TFL_TIMED("k_pcg", st); k_pcg_top<<<1, 256, 0, st>>>(S, p_rr, 0); }     // fold the last update's residual for the host
+    HIP_TRY(hipMemcpyAsync(&hs, S, sizeof(PcgState), hipMemcpyDeviceToHost, st), "memcpy state");
+    HIP_TRY(hipStreamSynchronize(st), "sync");
+    if (q.verbose && !hs.done)
+      printf("PCG batch %d comp %d iter %d: residual %g (tol %g)\n", b + 1, cidx + 1, hs.iter, std::sqrt(hs.rr1), (double)q.tol);
+    if (wf && pc) PCG_TRY(wavefront_error());
+    if (hs.bad) { snprintf(er.msg, er.len, "solveLinearSystemPCG: ERROR: r_norm_sq1 is nan!"); return PcgResult::nan_residual; }
+    // the loop ends when the NEXT top-of-loop test fails
+    if (hs.done || !((float)hs.rr1 > q.tol * q.tol) || hs.iter > q.max_iter) break;
+  }
+  max_res = std::max(max_res, (float)std::sqrt((float)hs.rr1));
+  return PcgResult::ok;
+}
+
+// p = x - mean of x on the component
+void Solve::write_back() {
+  TFL_TIMED("k_pcg", st);
+  k_pcg_sum<<<kRedBlocks, 256, 0, st>>>(n, x, partials);
+  k_pcg_sum_end<<<1, 256, 0, st>>>(S, partials);
+  k_pcg_write<<<kRedBlocks, 256, 0, st>>>(S, n, label, root, size, x, pb);
+}
+
+void Solve::print_trace() {
+  if (!wf_trace) return;
+  const int nblk = wg.ns * wg.nb;
+  std::vector<long long> t(4 * nblk);
+  if (hipMemcpy(t.data(), wf_trace, sizeof(long long) * 4 * nblk, hipMemcpyDeviceToHost) != hipSuccess) return;
+  long long t0 = t[0];
+  for (int i = 0; i < 4 * nblk; i++) if (t[i] && t[i] < t0) t0 = t[i];
+  for (int dir = 0; dir < 2; dir++)
+    for (int b2 = 0; b2 < nblk; b2++)
+      fprintf(stderr, "[tfl] wf %s strip %d slab %2d: start %8.2f us  end %8.2f us\n", dir ? "bwd" : "fwd", b2 / wg.nb, b2 % wg.nb,
+              (t[dir * 2 * nblk + 2 * b2] - t0) * 0.01, (t[dir * 2 * nblk + 2 * b2 + 1] - t0) * 0.01);
+}
 
 }  // namespace
 
-long long pcg_workspace_floats(int Z, int Y, int X) {
-  const long long n = (long long)Z * Y * X;
-  // label, size_at (int32) + x, r, z, s, w, dg, y (fp32) + roots + partials/state (fp64, kept 8-byte aligned first)
-  return 2 * (3 * kRedBlocks + 64) + 9 * n + kMaxComponents + 64 + (wf_usable(Z > 1, Z, Y, X) ? wf_floats(Z, Y, X) + 4 : 0);
+long long pcg_workspace_floats(int Z, int Y, int X) { return pcg_ws(Z, Y, X, wf_usable(Z > 1, Z, Y, X)).total; }
+
+// Solves every component of every batch element. Anything but PcgResult::ok comes with `msg` filled; wavefront_timeout (the
+// pipelined triangular solves timed out) only with allow_wavefronts: repeat without.
+PcgResult pcg_solve(hipStream_t st, const PcgProblem& q, float* workspace, float* residual, char* msg, size_t msg_len,
+                    bool allow_wavefronts) {
+  Solve v(st, q, workspace, msg, msg_len, allow_wavefronts);
+  const Report& er = v.er;
+  HIP_TRY(hipMemsetAsync(q.p, 0, sizeof(float) * (size_t)q.B * v.n, st), "memset p");   // :1341
+  for (int b = 0; b < q.B; b++) PCG_TRY(v.item(b));
+  v.print_trace();
+  if (residual) *residual = v.max_res;
+  return PcgResult::ok;
 }
 
-// Solves every component of every batch element. Returns 0, or a negative code with `msg` filled:
-// -1 invalid flags (fluid on the border), -2 NaN residual, -3 too many components, -4 HIP error, -5 the pipelined
-// triangular solves timed out (only with allow_wavefronts: repeat without).
-int pcg_solve(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* p, const float* flags, const float* div,
-              int precond /*0 none, 1 ilu0, 2 ic0*/, float tol, int max_iter, int verbose, float* workspace, float* residual,
-              char* msg, size_t msg_len, bool allow_wavefronts) {
+long long npm_workspace_floats(int Z, int Y, int X) { return npm_ws(Z, Y, X).total; }
+
+// normalizePressureMean for every batch element.
+PcgResult normalize_pressure_mean(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* p, const float* flags,
+                                  float* workspace, char* msg, size_t msg_len) {
   const Dom d = whole_dom(Z, Y, X);
   const long long n = d.sc;
-  double* partials = reinterpret_cast<double*>(workspace);
-  double* p_den = partials + kRedBlocks;      // s.w
-  double* p_rr = partials + 2 * kRedBlocks;   // r.r of the update
-  PcgState* S = reinterpret_cast<PcgState*>(partials + 3 * kRedBlocks);
-  float* base = workspace + 2 * (3 * kRedBlocks + 64);
-  int* label = reinterpret_cast<int*>(base);
-  int* size_at = reinterpret_cast<int*>(base + n);
-  float* x = base + 2 * n; float* r = base + 3 * n; float* z = base + 4 * n; float* s = base + 5 * n;
-  float* w = base + 6 * n; float* dg = base + 7 * n; float* y = base + 8 * n;
-  int* roots = reinterpret_cast<int*>(base + 9 * n);
-  int* counters = roots + kMaxComponents;   // [0] changed, [1] count, [2] border fluid
-  // pipelined wavefront sweeps (3-D): the skewed arrays (cc, r, q, z), the two hand-off arrays of {value, tag} pairs, an error word
-  const bool wf = allow_wavefronts && wf_usable(is3d, Z, Y, X);
-  const WfGeom wg = wf_geom(Z > 2 ? Z : 3, Y > 2 ? Y : 3, X > 2 ? X : 3);
-  float* wfbase = base + 9 * n + kMaxComponents + 64;
-  wfbase += (4 - (((uintptr_t)wfbase >> 2) & 3)) & 3;                  // 16-byte aligned (float4 rows, {value, tag} pairs)
-  float* cs = wfbase;
-  const long long wtot = wg.sub * wg.ns * wg.nb;
-  float* rsk = wf ? cs + wtot : nullptr;
-  float* qsk = wf ? cs + 2 * wtot : nullptr;
-  float* zsk = wf ? cs + 3 * wtot : nullptr;
-  float2* wf_hk = wf ? reinterpret_cast<float2*>(cs + 4 * wtot) + kWfGuard : nullptr;       // 16-byte aligned: wtot is a multiple of 1024
-  float2* wf_hs = wf ? reinterpret_cast<float2*>(cs + 4 * wtot + wf_handoff_k(wg)) + kWfGuard : nullptr;
-  int* wferr = wf ? reinterpret_cast<int*>(cs + 4 * wtot + wf_handoff_k(wg) + wf_handoff_s(wg)) : nullptr;
-  int epoch = 0;                                // tag of the next sweep; the skewed arrays are zeroed with it
-  const int wf_cap = sw::present(Sw::WF_MAX_BLOCKS) ? std::max(1, sw::num(Sw::WF_MAX_BLOCKS, 0)) : kWfMaxBlocks;     // (tests: small launches)
-  const int wf_slabs = std::max(1, std::min(wf_cap, kWfMaxBlocks) / std::max(wg.ns, 1));      // slabs per launch
-  // development aid: TFL_WF_TRACE=1 prints when every sub-box of the last forward / backward sweep started and finished
-  const bool wf_trace_on = sw::present(Sw::WF_TRACE);
-  long long* wf_trace = nullptr;
-  if (wf && wf_trace_on && precond && hipMalloc(&wf_trace, sizeof(long long) * 4 * wg.ns * wg.nb) != hipSuccess) wf_trace = nullptr;
-  struct TraceGuard { long long*& p; ~TraceGuard() { if (p) { (void)hipFree(p); p = nullptr; } } } trace_guard{wf_trace};   // every exit frees it
-  auto hip_ok = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    snprintf(msg, msg_len, "solveLinearSystemPCG: %s: %s", what, hipGetErrorString(e));
-    return false;
-  };
-  if (!hip_ok(hipMemsetAsync(p, 0, sizeof(float) * (size_t)B * n, st), "memset p")) return -4;   // :1341
-  const int gcell = cdiv(n, 256);
-  float max_res = -std::numeric_limits<float>::infinity();
-  const int nlev = (X - 2) + (Y - 2) + (is3d ? Z - 2 : 0);        // hyperplanes h = hmin .. hmin + nlev - dims
-  const int hmin = is3d ? 3 : 2, hmax = (X - 2) + (Y - 2) + (is3d ? Z - 2 : 0);
-  (void)nlev;
-  const int gwave = cdiv((long long)(Y - 2) * (is3d ? Z - 2 : 1), 256);
-  for (int b = 0; b < B; b++) {
-    const float* fl = flags + (long long)b * n;
-    const float* dv = div + (long long)b * n;
-    float* pb = p + (long long)b * n;
-    // ---- components -----------------------------------------------------------------------------------
-    int h_cnt[3] = {0, 0, 0};
-    if (!hip_ok(hipMemsetAsync(counters, 0, 3 * sizeof(int), st), "memset")) return -4;
-    if (!hip_ok(hipMemsetAsync(size_at, 0, sizeof(int) * (size_t)n, st), "memset")) return -4;
-    { TFL_TIMED("k_cc", st); k_cc_init<<<gcell, 256, 0, st>>>(d, is3d, fl, label, counters + 2); }
-    for (int round = 0;; round++) {
-      if (!hip_ok(hipMemsetAsync(counters, 0, sizeof(int), st), "memset")) return -4;
-      { TFL_TIMED("k_cc", st);
-        k_cc_hook<<<gcell, 256, 0, st>>>(d, is3d, label, counters);
-        k_cc_compress<<<gcell, 256, 0, st>>>(d, label); }
-      if (!hip_ok(hipMemcpyAsync(h_cnt, counters, 3 * sizeof(int), hipMemcpyDeviceToHost, st), "memcpy")) return -4;
-      if (!hip_ok(hipStreamSynchronize(st), "sync")) return -4;
-      if (!h_cnt[0]) break;
-      if (round > 100000) { snprintf(msg, msg_len, "solveLinearSystemPCG: component labelling did not converge"); return -4; }
-    }
-    if (h_cnt[2] > 0) {   // generic/tfluids.cu:1083-1091 raises for a fluid cell on the border
-      snprintf(msg, msg_len, "solveLinearSystemPCG: Non fluid cell found in a connected component or fluid cell found on the "
-               "domain border (%d fluid border cells)", h_cnt[2]);
-      return -1;
-    }
-    { TFL_TIMED("k_cc", st); k_cc_count<<<gcell, 256, 0, st>>>(d, label, size_at, roots, counters + 1); }
-    if (!hip_ok(hipMemcpyAsync(h_cnt, counters, 3 * sizeof(int), hipMemcpyDeviceToHost, st), "memcpy")) return -4;
-    if (!hip_ok(hipStreamSynchronize(st), "sync")) return -4;
-    const int ncomp = h_cnt[1];
-    if (ncomp > kMaxComponents) {
-      snprintf(msg, msg_len, "solveLinearSystemPCG: %d fluid components (the solver handles %d)", ncomp, kMaxComponents);
-      return -3;
-    }
-    std::vector<int> h_roots(ncomp), h_sizes(ncomp);
-    if (ncomp) {
-      if (!hip_ok(hipMemcpy(h_roots.data(), roots, sizeof(int) * ncomp, hipMemcpyDeviceToHost), "memcpy roots")) return -4;
-      std::sort(h_roots.begin(), h_roots.end());   // scan order of the first cell = the reference's numbering
-      for (int cidx = 0; cidx < ncomp; cidx++)
-        if (!hip_ok(hipMemcpy(&h_sizes[cidx], size_at + h_roots[cidx], sizeof(int), hipMemcpyDeviceToHost), "memcpy size")) return -4;
-    }
-    // ---- one CG solve per component -------------------------------------------------------------------
-    for (int cidx = 0; cidx < ncomp; cidx++) {
-      const int root = h_roots[cidx], size = h_sizes[cidx];
-      if (size == 1) {   // :1375-1383: no valid solution, pressure stays 0
-        if (verbose) printf("PCG batch %d component %d has size 1, skipping.\n", b + 1, cidx + 1);
-        continue;
-      }
-      int pc = precond;
-      if (size < 5) pc = 0;   // :1390-1393
-      if (verbose) printf("PCG batch %d component %d has size %d.\nPCG: %d component %d using precond type %s\n", b + 1, cidx + 1,
-                          size, b + 1, cidx + 1, pc == 0 ? "none" : (pc == 1 ? "ilu0" : "ic0"));
-      // z is only ever written on the component; its other cells must read as 0 in s = z and r.z
-      if (pc && !hip_ok(hipMemsetAsync(z, 0, sizeof(float) * (size_t)n, st), "memset z")) return -4;
-      { TFL_TIMED("k_pcg", st);
-        k_pcg_setup<<<kRedBlocks, 256, 0, st>>>(n, label, root, dv, x, r, s, partials);
-        k_pcg_begin<<<1, 256, 0, st>>>(S, partials, tol, max_iter); }
-      if (pc) {
-        TFL_TIMED("k_pcg_precond", st);
-        for (int h = hmin; h <= hmax; h++) {
-          if (is3d) k_ilu_factor<true><<<gwave, 256, 0, st>>>(d, h, fl, label, root, dg);
-          else k_ilu_factor<false><<<gwave, 256, 0, st>>>(d, h, fl, label, root, dg);
-        }
-        if (wf) {
-          const long long tot = wg.sub * wg.ns * wg.nb;
-          if (!hip_ok(hipMemsetAsync(cs, 0, sizeof(float) * (size_t)(tot * 4 + wf_handoff_k(wg) + wf_handoff_s(wg) + 16), st), "memset skewed arrays")) return -4;
-          epoch = 0;
-          const int gb = cdiv((long long)(X - 2) * (Y - 2) * (Z - 2), 256);
-          if (pc == 2) k_wf_build<true><<<gb, 256, 0, st>>>(wg, d, label, root, dg, cs);
-          else k_wf_build<false><<<gb, 256, 0, st>>>(wg, d, label, root, dg, cs);
-        }
-      }
-      PcgState hs;
-      const int chunk = verbose ? 1 : (pc ? (wf ? 16 : 4) : 32);
-      for (;;) {
-        for (int it = 0; it < chunk; it++) {
-          k_pcg_top<<<1, 256, 0, st>>>(S, p_rr, 1);
-          const float* dir_src = r;
-          if (pc && wf) {
-            // M^-1 r as two launches (pipelined wavefronts)
-            const int nblk = wg.ns * wg.nb;
-            const int gb = cdiv((long long)(X - 2) * (Y - 2) * (Z - 2), 256);
-            { TFL_TIMED("k_pcg_precond", st);
-              k_wf_skew<true><<<gb, 256, 0, st>>>(S, wg, d, r, rsk);
-              // every sub-box of a launch must be resident (they wait for each other): at most wf_cap of them per launch,
-              // all strips of a range of slabs, the ranges in sweep order -- a later launch finds its predecessors' pairs
-              // waiting under the same tag
-              ++epoch;
-              for (int b0 = 0; b0 < wg.nb; b0 += wf_slabs) {
-                WfGeom c = wg; c.b_lo = b0; c.b_cnt = std::min(wf_slabs, wg.nb - b0);
-                k_wf_sweep<1><<<wg.ns * c.b_cnt, (kWfPlanes + 2) * 64, 0, st>>>(S, c, WfArrays{cs, rsk, qsk, wf_hk, wf_hs, wferr, wf_trace}, epoch);
-              }
-              ++epoch;
-              for (int b1 = wg.nb; b1 > 0; b1 -= wf_slabs) {
-                WfGeom c = wg; c.b_lo = std::max(b1 - wf_slabs, 0); c.b_cnt = b1 - c.b_lo;
-                k_wf_sweep<-1><<<wg.ns * c.b_cnt, (kWfPlanes + 2) * 64, 0, st>>>(S, c, WfArrays{cs, qsk, zsk, wf_hk, wf_hs, wferr, wf_trace ? wf_trace + 2 * nblk : nullptr}, epoch);
-              }
-              k_wf_skew<false><<<gb, 256, 0, st>>>(S, wg, d, z, zsk); }
-            dir_src = z;
-          } else if (pc) {
-            TFL_TIMED("k_pcg_precond", st);
-            for (int h = hmin; h <= hmax; h++) {
-              if (is3d) { if (pc == 2) k_ilu_forward<true, true><<<gwave, 256, 0, st>>>(S, d, h, fl, label, root, dg, r, y);
-                          else k_ilu_forward<true, false><<<gwave, 256, 0, st>>>(S, d, h, fl, label, root, dg, r, y); }
-              else { if (pc == 2) k_ilu_forward<false, true><<<gwave, 256, 0, st>>>(S, d, h, fl, label, root, dg, r, y);
-                     else k_ilu_forward<false, false><<<gwave, 256, 0, st>>>(S, d, h, fl, label, root, dg, r, y); }
-            }
-            for (int h = hmax; h >= hmin; h--) {
-              if (is3d) { if (pc == 2) k_ilu_backward<true, true><<<gwave, 256, 0, st>>>(S, d, h, fl, label, root, dg, y, z);
-                          else k_ilu_backward<true, false><<<gwave, 256, 0, st>>>(S, d, h, fl, label, root, dg, y, z); }
-              else { if (pc == 2) k_ilu_backward<false, true><<<gwave, 256, 0, st>>>(S, d, h, fl, label, root, dg, y, z);
-                     else k_ilu_backward<false, false><<<gwave, 256, 0, st>>>(S, d, h, fl, label, root, dg, y, z); }
-            }
-            dir_src = z;
-          }
-          TFL_TIMED("k_pcg", st);
-          if (pc) k_pcg_dot<<<kRedBlocks, 256, 0, st>>>(S, n, r, z, partials);
-          k_pcg_dir<<<kRedBlocks, 256, 0, st>>>(S, n, partials, pc ? 1 : 0, dir_src, s);
-          if (is3d) k_pcg_apply<true><<<kRedBlocks, 256, 0, st>>>(S, d, fl, label, root, s, w, p_den);
-          else k_pcg_apply<false><<<kRedBlocks, 256, 0, st>>>(S, d, fl, label, root, s, w, p_den);
-          k_pcg_update<<<kRedBlocks, 256, 0, st>>>(S, n, p_den, s, w, x, r, p_rr);
-        }
-        { TFL_TIMED("k_pcg", st); k_pcg_top<<<1, 256, 0, st>>>(S, p_rr, 0); }     // fold the last update's residual for the host
-        if (!hip_ok(hipMemcpyAsync(&hs, S, sizeof(PcgState), hipMemcpyDeviceToHost, st), "memcpy state")) return -4;
-        if (!hip_ok(hipStreamSynchronize(st), "sync")) return -4;
-        if (verbose && !hs.done)
-          printf("PCG batch %d comp %d iter %d: residual %g (tol %g)\n", b + 1, cidx + 1, hs.iter, std::sqrt(hs.rr1), (double)tol);
-        if (wf && pc) {
-          int e = 0;
-          if (!hip_ok(hipMemcpy(&e, wferr, sizeof(int), hipMemcpyDeviceToHost), "memcpy")) return -4;
-          if (sw::present(Sw::WF_TEST_TIMEOUT)) e = 1;     // tests: exercise the caller's fallback
-          // (its sub-boxes wait for each other, so all of them must be resident at once: not the case when something else holds
-          // part of the GPU. The caller repeats the solve with one launch per hyperplane.)
-          if (e) { snprintf(msg, msg_len, "solveLinearSystemPCG: a block of the pipelined triangular solve never saw its predecessor"); return -5; }
-        }
-        if (hs.bad) { snprintf(msg, msg_len, "solveLinearSystemPCG: ERROR: r_norm_sq1 is nan!"); return -2; }
-        // the loop ends when the NEXT top-of-loop test fails
-        if (hs.done || !((float)hs.rr1 > tol * tol) || hs.iter > max_iter) break;
-      }
-      max_res = std::max(max_res, (float)std::sqrt((float)hs.rr1));
-      { TFL_TIMED("k_pcg", st);
-        k_pcg_sum<<<kRedBlocks, 256, 0, st>>>(n, x, partials);
-        k_pcg_sum_end<<<1, 256, 0, st>>>(S, partials);
-        k_pcg_write<<<kRedBlocks, 256, 0, st>>>(S, n, label, root, size, x, pb); }
-    }
-  }
-  if (wf_trace) {
-    const int nblk = wg.ns * wg.nb;
-    std::vector<long long> t(4 * nblk);
-    if (hipMemcpy(t.data(), wf_trace, sizeof(long long) * 4 * nblk, hipMemcpyDeviceToHost) == hipSuccess) {
-      long long t0 = t[0];
-      for (int i = 0; i < 4 * nblk; i++) if (t[i] && t[i] < t0) t0 = t[i];
-      for (int dir = 0; dir < 2; dir++)
-        for (int b2 = 0; b2 < nblk; b2++)
-          fprintf(stderr, "[tfl] wf %s strip %d slab %2d: start %8.2f us  end %8.2f us\n", dir ? "bwd" : "fwd", b2 / wg.nb, b2 % wg.nb,
-                  (t[dir * 2 * nblk + 2 * b2] - t0) * 0.01, (t[dir * 2 * nblk + 2 * b2 + 1] - t0) * 0.01);
-    }
-  }
-  if (residual) *residual = max_res;
-  return 0;
-}
-
-long long npm_workspace_floats(int Z, int Y, int X) { return 4ll * Z * Y * X + 16 + kMaxComponents; }
-
-// normalizePressureMean for every batch element. workspace: sum_at (fp64, first for alignment), label, size_at, counters.
-int normalize_pressure_mean(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* p, const float* flags,
-                            float* workspace, char* msg, size_t msg_len) {
-  const Dom d = whole_dom(Z, Y, X);
-  const long long n = d.sc;
-  double* sum_at = reinterpret_cast<double*>(workspace);
-  int* label = reinterpret_cast<int*>(workspace + 2 * n);
-  int* size_at = reinterpret_cast<int*>(workspace + 3 * n);
-  int* counters = reinterpret_cast<int*>(workspace + 4 * n);    // [0] changed, [1] count, [2] border fluid, [3..] roots sink
-  auto hip_ok = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    snprintf(msg, msg_len, "normalizePressureMean: %s: %s", what, hipGetErrorString(e));
-    return false;
-  };
+  const NpmWs t = npm_ws(Z, Y, X);
+  double* sum_at = view<double>(workspace, t.sum_at);
+  int* label = view<int>(workspace, t.label);
+  int* size_at = view<int>(workspace, t.size_at);
+  int* counters = view<int>(workspace, t.counters);
+  const Report er{"normalizePressureMean", msg, msg_len};
   const int gcell = cdiv(n, 256);
   for (int b = 0; b < B; b++) {
     const float* fl = flags + (long long)b * n;
     float* pb = p + (long long)b * n;
     int h_cnt[3] = {0, 0, 0};
-    if (!hip_ok(hipMemsetAsync(counters, 0, 3 * sizeof(int), st), "memset")) return -4;
-    if (!hip_ok(hipMemsetAsync(size_at, 0, sizeof(int) * (size_t)n, st), "memset")) return -4;
-    if (!hip_ok(hipMemsetAsync(sum_at, 0, sizeof(double) * (size_t)n, st), "memset")) return -4;
+    PCG_TRY(clear_component_counts(st, er, counters, size_at, n));
+    HIP_TRY(hipMemsetAsync(sum_at, 0, sizeof(double) * (size_t)n, st), "memset");
     TFL_TIMED("k_cc", st);
-    k_cc_init<<<gcell, 256, 0, st>>>(d, is3d, fl, label, counters + 2);
-    for (int round = 0;; round++) {
-      if (!hip_ok(hipMemsetAsync(counters, 0, sizeof(int), st), "memset")) return -4;
-      k_cc_hook<<<gcell, 256, 0, st>>>(d, is3d, label, counters);
-      k_cc_compress<<<gcell, 256, 0, st>>>(d, label);
-      if (!hip_ok(hipMemcpyAsync(h_cnt, counters, 3 * sizeof(int), hipMemcpyDeviceToHost, st), "memcpy")) return -4;
-      if (!hip_ok(hipStreamSynchronize(st), "sync")) return -4;
-      if (!h_cnt[0]) break;
-      if (round > 100000) { snprintf(msg, msg_len, "normalizePressureMean: component labelling did not converge"); return -4; }
-    }
+    PCG_TRY(label_components(st, er, d, is3d, fl, label, counters, h_cnt, false));
     // sizes only (the roots list is not needed: means are looked up through the label)
-    k_cc_count<<<gcell, 256, 0, st>>>(d, label, size_at, counters + 3, counters + 1);
+    k_cc_count<<<gcell, 256, 0, st>>>(d, label, size_at, view<int>(workspace, t.roots), counters + 1);
     k_npm_sum<<<gcell, 256, 0, st>>>(d, label, pb, sum_at);
     k_npm_sub<<<gcell, 256, 0, st>>>(d, label, size_at, sum_at, pb);
   }
-  return 0;
+  return PcgResult::ok;
 }
 
 }  // namespace tfl

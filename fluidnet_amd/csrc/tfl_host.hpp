@@ -243,13 +243,25 @@ bool jacobi_solve_lds(hipStream_t st, int B, int Y, int X, const float* flags, c
                       int iters, double* resid_sq);
 
 // pcg.hip
-long long pcg_workspace_floats(int Z, int Y, int X);
-int pcg_solve(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* p, const float* flags, const float* div,
-              int precond, float tol, int max_iter, int verbose, float* workspace, float* residual, char* msg, size_t msg_len, bool allow_wavefronts = true);
+// bad_flags: fluid on the domain's border; wavefront_timeout: the pipelined triangular solves never saw a predecessor (only
+// with allow_wavefronts: the caller repeats the solve without)
+enum class PcgResult { ok, bad_flags, nan_residual, too_many_components, hip_error, wavefront_timeout };
+struct PcgProblem {
+  bool is3d;
+  int B, Z, Y, X;
+  float* p;
+  const float *flags, *div;
+  int precond;      // 0 none, 1 ilu0, 2 ic0
+  float tol;
+  int max_iter, verbose;
+};
+long long pcg_workspace_floats(int Z, int Y, int X);     // the total of pcg_ws (tfl_pcg_ws.hpp)
+PcgResult pcg_solve(hipStream_t st, const PcgProblem& q, float* workspace, float* residual, char* msg, size_t msg_len,
+                    bool allow_wavefronts);
 
-long long npm_workspace_floats(int Z, int Y, int X);
-int normalize_pressure_mean(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* p, const float* flags,
-                            float* workspace, char* msg, size_t msg_len);
+long long npm_workspace_floats(int Z, int Y, int X);     // the total of npm_ws
+PcgResult normalize_pressure_mean(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* p, const float* flags,
+                                  float* workspace, char* msg, size_t msg_len);
 
 // model.hip
 long long model_stat_blocks(int B, int Z, int Y, int X);
