@@ -31,12 +31,13 @@ def main():
     ap.add_argument("--save-every", type=int, default=4)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--models", nargs="*", default=[], help="binvox files stamped into 3-D scenes as obstacles")
+    ap.add_argument("--pcgPrecond", default="ic0", choices=("none", "ilu0", "ic0", "mg"), help="preconditioner of the PCG solves")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     is3D = a.dim == 3
     res = a.res or (64 if is3D else 128)
     models = [io.loadVoxelData(fn)["data"] for fn in a.models]
-    gconf = datagen.default_gconf(is3D, (res if is3D else 1, res, res), steps=a.steps, saveEvery=a.save_every, models=models)
+    gconf = datagen.default_gconf(is3D, (res if is3D else 1, res, res), steps=a.steps, saveEvery=a.save_every, models=models, pcgPrecond=a.pcgPrecond)
     out = os.path.join(a.out, a.dataset)
     first = 0
     for prefix, nruns in (("tr", a.runs_tr), ("te", a.runs_te)):

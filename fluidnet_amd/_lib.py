@@ -211,6 +211,8 @@ SIGNATURES = {
     "tfl_normalize_workspace_floats": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32]),
     "tfl_normalizePressureMean": (_c.c_int, [_c.c_void_p, _T, _T, _c.c_int, _c.c_void_p, _c.c_int64]),
     "tfl_pcg_workspace_floats": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32]),
+    "tfl_pcg_workspace_floats_for": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_char_p]),
+    "tfl_pcg_last_iterations": (_c.c_int64, [_c.c_void_p]),
     "tfl_solveLinearSystemPCG": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int, _c.c_char_p, _c.c_float, _c.c_int, _c.c_int,
                                             _c.c_void_p, _c.c_int64, _c.c_void_p]),
     "tfl_getDx": (_c.c_double, [_c.c_void_p, _T]),

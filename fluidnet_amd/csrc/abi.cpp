@@ -416,6 +416,16 @@ int tfl_signedDistanceField(tfl_ctx* c, const tfl_tensor* flags, int searchRad, 
 
 int64_t tfl_pcg_workspace_floats(int32_t Z, int32_t Y, int32_t X) { return tfl::pcg_workspace_floats(Z, Y, X); }
 
+// "none" 0 | "ilu0" 1 | "ic0" 2 | "mg" 3; NULL = "ic0"; -1: not a preconditioner
+static int pcg_precond_of(const char* precondType) {
+  const std::string pt = precondType ? precondType : "ic0";
+  return pt == "none" ? 0 : pt == "ilu0" ? 1 : pt == "ic0" ? 2 : pt == "mg" ? 3 : -1;
+}
+int64_t tfl_pcg_workspace_floats_for(int32_t Z, int32_t Y, int32_t X, const char* precondType) {
+  return tfl::pcg_workspace_floats_for(Z, Y, X, pcg_precond_of(precondType));
+}
+int64_t tfl_pcg_last_iterations(tfl_ctx* c) { return c ? c->pcg_last_iterations : -1; }
+
 int tfl_solveLinearSystemPCG(tfl_ctx* c, const tfl_tensor* p, const tfl_tensor* flags, const tfl_tensor* div, int is3D,
                              const char* precondType, float tol, int maxIter, int verbose, float* workspace,
                              int64_t workspace_floats, float* residual) {
@@ -423,20 +433,20 @@ int tfl_solveLinearSystemPCG(tfl_ctx* c, const tfl_tensor* p, const tfl_tensor* 
   TRY(check_scalar(c, "solveLinearSystemPCG", "p", p, flags));
   TRY(check_scalar(c, "solveLinearSystemPCG", "div", div, flags));
   if (!is3D && flags->Z != 1) return fail(c, TFL_EINVAL, "solveLinearSystemPCG: d > 1 for a 2D domain");
-  int pc = -1;
-  const std::string pt = precondType ? precondType : "ic0";
-  if (pt == "none") pc = 0; else if (pt == "ilu0") pc = 1; else if (pt == "ic0") pc = 2;
+  const int pc = pcg_precond_of(precondType);
   if (pc < 0) return fail(c, TFL_EINVAL, "solveLinearSystemPCG: precondType is not supported.");
   if (!workspace || ((uintptr_t)workspace & 7) != 0) return fail(c, TFL_EINVAL, "solveLinearSystemPCG: workspace must be 8-byte aligned");
-  if (workspace_floats < tfl::pcg_workspace_floats(flags->Z, flags->Y, flags->X))
-    return fail(c, TFL_EINVAL, "solveLinearSystemPCG: workspace too small (tfl_pcg_workspace_floats)");
+  if (workspace_floats < tfl::pcg_workspace_floats_for(flags->Z, flags->Y, flags->X, pc))
+    return fail(c, TFL_EINVAL, "%s", pc == 3 ? "solveLinearSystemPCG: workspace too small (tfl_pcg_workspace_floats_for)"
+                                       : "solveLinearSystemPCG: workspace too small (tfl_pcg_workspace_floats)");
   if ((long long)flags->Z * flags->Y * flags->X >= (1ll << 31)) return fail(c, TFL_EINVAL, "solveLinearSystemPCG: grid too large for 32-bit cell indices");
   char msg[256] = {0};
   // the pipelined sweeps need every sub-box resident at once: when something else holds part of the GPU they time out (~1 s)
   // and the solve is repeated with one launch per hyperplane -- remembered per context, so that only the FIRST solve pays
   const tfl::PcgProblem q{is3D != 0, flags->B, flags->Z, flags->Y, flags->X, p->data, flags->data, div->data, pc, tol, maxIter, verbose};
+  long long iterations = 0;
   auto solve = [&](bool allow_wavefronts) {
-    return tfl::pcg_solve(c->stream, q, workspace, residual, msg, sizeof(msg), allow_wavefronts);
+    return tfl::pcg_solve(c->stream, q, workspace, residual, msg, sizeof(msg), allow_wavefronts, &iterations);
   };
   tfl::PcgResult rc = solve(c->wf_skip == 0);
   if (c->wf_skip > 0) c->wf_skip--;
@@ -449,7 +459,7 @@ int tfl_solveLinearSystemPCG(tfl_ctx* c, const tfl_tensor* p, const tfl_tensor* 
     rc = solve(false);
   }
   switch (rc) {
-    case tfl::PcgResult::ok: return check_launch(c, "solveLinearSystemPCG");
+    case tfl::PcgResult::ok: c->pcg_last_iterations = iterations; return check_launch(c, "solveLinearSystemPCG");
     case tfl::PcgResult::bad_flags:
     case tfl::PcgResult::nan_residual:
     case tfl::PcgResult::too_many_components: return fail(c, TFL_EINVAL, "%s", msg);

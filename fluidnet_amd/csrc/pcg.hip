@@ -26,10 +26,13 @@
 //
 // The file: the kernels; then the host code. The caller's workspace is laid out by ONE table (tfl_pcg_ws.hpp: pcg_ws / npm_ws,
 // which also size it), pcg_solve is the struct `Solve` -- the views of that table and the phases item / read_components /
-// component / begin / factor / build_wavefront_operands / precondition / iteration / run_chunks / write_back -- and
-// label_components is shared with normalize_pressure_mean. Results are named (PcgResult, tfl_host.hpp).
+// component / begin / factor / build_wavefront_operands / build_levels / precondition / vcycle / iteration / run_chunks /
+// write_back -- and label_components is shared with normalize_pressure_mean. Results are named (PcgResult, tfl_host.hpp).
+// precondType = "mg" (pc == 3) is one multigrid V-cycle per application: its kernels are pcg_mg.hip, its scheme tfl_pcg_mg.hpp;
+// the wavefront machinery is not set up under it.
 #include "tfl_device.hpp"
 #include "tfl_host.hpp"
+#include "tfl_pcg_mg.hpp"
 #include "tfl_pcg_ws.hpp"
 #include "tfl_vec4.hpp"
 
@@ -787,6 +790,12 @@ struct Solve {
   int wf_slabs = 1;                    // slabs per launch
   int epoch = 0;                       // tag of the next sweep; the skewed arrays are zeroed with it
   long long* wf_trace = nullptr;       // TFL_WF_TRACE
+  // the multigrid hierarchy (pc == 3): its levels' geometry and arrays
+  bool mg;
+  MgDev mgd{};
+  int* mg_open = nullptr;              // device word: the component has a cell next to an empty one (its matrix is regular)
+  bool mg_closed = false;              // ... read back at set-up: the component at hand is closed, its cycle runs on r minus its mean
+  long long iterations = 0;            // the sum over the component solves of the iteration counter at exit
   // launch sizes: per cell, per hyperplane, per interior cell; the hyperplanes h = i + j + k of the interior
   int gcell, gwave, ginner = 0, hmin, hmax;
   // the item and the component at hand
@@ -803,6 +812,8 @@ struct Solve {
   void begin();
   void factor();
   PcgResult build_wavefront_operands();
+  PcgResult build_levels();
+  void vcycle();
   template <bool IS3D, bool IC> void hyperplane_sweeps();
   void precondition();
   void iteration();
@@ -814,8 +825,9 @@ struct Solve {
 
 Solve::Solve(hipStream_t st_, const PcgProblem& q_, float* workspace, char* msg, size_t msg_len, bool allow_wavefronts)
     : st(st_), q(q_), er{"solveLinearSystemPCG", msg, msg_len}, d(whole_dom(q_.Z, q_.Y, q_.X)), n(d.sc) {
-  wf = allow_wavefronts && wf_usable(q.is3d, q.Z, q.Y, q.X);
-  const PcgWs t = pcg_ws(q.Z, q.Y, q.X, wf);
+  mg = q.precond == 3;
+  wf = !mg && allow_wavefronts && wf_usable(q.is3d, q.Z, q.Y, q.X);
+  const PcgWs t = pcg_ws(q.Z, q.Y, q.X, wf, mg, q.is3d);
   partials = view<double>(workspace, t.partials); p_den = view<double>(workspace, t.p_den); p_rr = view<double>(workspace, t.p_rr);
   S = view<PcgState>(workspace, t.state);
   label = view<int>(workspace, t.label); size_at = view<int>(workspace, t.size_at);
@@ -835,6 +847,21 @@ Solve::Solve(hipStream_t st_, const PcgProblem& q_, float* workspace, char* msg,
     ginner = cdiv((long long)(q.X - 2) * (q.Y - 2) * (q.Z - 2), 256);
     // development aid: TFL_WF_TRACE=1 prints when every sub-box of the last forward / backward sweep started and finished
     if (sw::present(Sw::WF_TRACE) && q.precond && hipMalloc(&wf_trace, sizeof(long long) * 4 * wg.ns * wg.nb) != hipSuccess) wf_trace = nullptr;
+  }
+  if (mg) {
+    const MgLevels ml = mg_levels(q.Z, q.Y, q.X, q.is3d);
+    mgd.count = ml.count; mgd.first_block_level = ml.first_block_level;
+    // level 0: z is the CG's, diag lives in dg, the second iterate in y and the cycle's right-hand side in w (all idle under mg,
+    // w while the preconditioner runs)
+    mgd.lv[0] = MgLv{ml.lv[0], (int)ml.lv[0].n, dg, view<float>(workspace, t.mg_invd0), view<float>(workspace, t.mg_cx0),
+                     view<float>(workspace, t.mg_cy0), view<float>(workspace, t.mg_cz0), w, y, z};
+    mg_open = counters + kPcgMgOpenWord;
+    for (int l = 1; l < ml.count; l++) {
+      const long long o = ml.lv[l].off;
+      mgd.lv[l] = MgLv{ml.lv[l], (int)ml.lv[l].n, view<float>(workspace, t.mg_c_diag) + o, view<float>(workspace, t.mg_c_invd) + o,
+                       view<float>(workspace, t.mg_c_cx) + o, view<float>(workspace, t.mg_c_cy) + o, view<float>(workspace, t.mg_c_cz) + o,
+                       view<float>(workspace, t.mg_c_r) + o, view<float>(workspace, t.mg_c_za) + o, view<float>(workspace, t.mg_c_zb) + o};
+    }
   }
   gcell = cdiv(n, 256);
   gwave = cdiv((long long)(q.Y - 2) * (q.is3d ? q.Z - 2 : 1), 256);
@@ -887,13 +914,14 @@ PcgResult Solve::component(int cidx_, int root_, int size_) {
   pc = q.precond;
   if (size < 5) pc = 0;   // :1390-1393
   if (q.verbose) printf("PCG batch %d component %d has size %d.\nPCG: %d component %d using precond type %s\n", b + 1, cidx + 1,
-                        size, b + 1, cidx + 1, pc == 0 ? "none" : (pc == 1 ? "ilu0" : "ic0"));
+                        size, b + 1, cidx + 1, pc == 0 ? "none" : (pc == 1 ? "ilu0" : (pc == 2 ? "ic0" : "mg")));
   // z is only ever written on the component; its other cells must read as 0 in s = z and r.z
   if (pc) HIP_TRY(hipMemsetAsync(z, 0, sizeof(float) * (size_t)n, st), "memset z");
   begin();
   if (pc) {
     TFL_TIMED("k_pcg_precond", st);
-    factor();
+    if (pc == 3) PCG_TRY(build_levels());
+    else factor();
     if (wf) PCG_TRY(build_wavefront_operands());
   }
   PCG_TRY(run_chunks());
@@ -924,6 +952,21 @@ PcgResult Solve::build_wavefront_operands() {
   return PcgResult::ok;
 }
 
+// the multigrid hierarchy of the component: level 0 from the flags and the label, then one launch per coarser level
+// (one word read back: whether the component is closed decides what the cycle launches)
+PcgResult Solve::build_levels() {
+  mg_build_levels(st, d, q.is3d, mgd, fl, label, root, mg_open);
+  int h_open = 0;
+  HIP_TRY(hipMemcpyAsync(&h_open, mg_open, sizeof(int), hipMemcpyDeviceToHost, st), "memcpy");
+  HIP_TRY(hipStreamSynchronize(st), "sync");
+  mg_closed = h_open == 0;
+  mgd.lv[0].r = mg_closed ? w : r;     // closed: the right-hand side of the cycle is formed in the idle w
+  return PcgResult::ok;
+}
+
+// z = M^-1 r, one V-cycle
+void Solve::vcycle() { mg_vcycle(st, q.is3d, mgd, S, mg_closed, r, partials, size); }
+
 // M^-1 r with one launch per hyperplane and sweep
 template <bool IS3D, bool IC>
 void Solve::hyperplane_sweeps() {
@@ -934,6 +977,7 @@ void Solve::hyperplane_sweeps() {
 // z = M^-1 r
 void Solve::precondition() {
   TFL_TIMED("k_pcg_precond", st);
+  if (pc == 3) { vcycle(); return; }
   if (!wf) {
     if (q.is3d) { if (pc == 2) hyperplane_sweeps<true, true>(); else hyperplane_sweeps<true, false>(); }
     else { if (pc == 2) hyperplane_sweeps<false, true>(); else hyperplane_sweeps<false, false>(); }
@@ -985,7 +1029,7 @@ PcgResult Solve::wavefront_error() {
 // the iterations of one component: a chunk enqueued, then the state read back
 PcgResult Solve::run_chunks() {
   PcgState hs;
-  const int chunk = q.verbose ? 1 : (pc ? (wf ? 16 : 4) : 32);
+  const int chunk = q.verbose ? 1 : (pc ? (wf ? 16 : (pc == 3 ? 8 : 4)) : 32);
   for (;;) {
     for (int it = 0; it < chunk; it++) iteration();
     { TFL_TIMED("k_pcg", st); k_pcg_top<<<1, 256, 0, st>>>(S, p_rr, 0); }     // fold the last update's residual for the host
@@ -999,6 +1043,7 @@ PcgResult Solve::run_chunks() {
     if (hs.done || !((float)hs.rr1 > q.tol * q.tol) || hs.iter > q.max_iter) break;
   }
   max_res = std::max(max_res, (float)std::sqrt((float)hs.rr1));
+  iterations += hs.iter;
   return PcgResult::ok;
 }
 
@@ -1026,17 +1071,22 @@ void Solve::print_trace() {
 }  // namespace
 
 long long pcg_workspace_floats(int Z, int Y, int X) { return pcg_ws(Z, Y, X, wf_usable(Z > 1, Z, Y, X)).total; }
+long long pcg_workspace_floats_for(int Z, int Y, int X, int precond) {
+  if (precond >= 0 && precond <= 2) return pcg_workspace_floats(Z, Y, X);
+  return precond == 3 ? pcg_ws(Z, Y, X, false, true, Z > 1).total : -1;
+}
 
 // Solves every component of every batch element. Anything but PcgResult::ok comes with `msg` filled; wavefront_timeout (the
 // pipelined triangular solves timed out) only with allow_wavefronts: repeat without.
 PcgResult pcg_solve(hipStream_t st, const PcgProblem& q, float* workspace, float* residual, char* msg, size_t msg_len,
-                    bool allow_wavefronts) {
+                    bool allow_wavefronts, long long* iterations) {
   Solve v(st, q, workspace, msg, msg_len, allow_wavefronts);
   const Report& er = v.er;
   HIP_TRY(hipMemsetAsync(q.p, 0, sizeof(float) * (size_t)q.B * v.n, st), "memset p");   // :1341
   for (int b = 0; b < q.B; b++) PCG_TRY(v.item(b));
   v.print_trace();
   if (residual) *residual = v.max_res;
+  if (iterations) *iterations = v.iterations;
   return PcgResult::ok;
 }
 

@@ -98,8 +98,14 @@ tfl::StepProj proj_of(const tfl_sim_params* p) {
        : !std::strcmp(m, "pcg") ? tfl::StepProj::pcg : tfl::StepProj::unknown;
 }
 // the workspace table of a step (tfl_step_ws.hpp), and the floats the step needs: the table's, or the model's own workspace
-tfl::StepWs step_ws_of(const Sizes& z, tfl::StepProj proj) {
-  return tfl::step_ws(z.B, z.Z, z.Y, z.X, (int)z.C, proj, proj == tfl::StepProj::pcg ? tfl_pcg_workspace_floats(z.Z, z.Y, z.X) : 0);
+// (the PCG region is sized for params->pcgPrecond; a name the solver does not know gets the common size and is refused there)
+tfl::StepWs step_ws_of(const tfl_sim_params* prm, const Sizes& z, tfl::StepProj proj) {
+  long long pcg = 0;
+  if (proj == tfl::StepProj::pcg) {
+    pcg = tfl_pcg_workspace_floats_for(z.Z, z.Y, z.X, prm->pcgPrecond && prm->pcgPrecond[0] ? prm->pcgPrecond : "ic0");
+    if (pcg < 0) pcg = tfl_pcg_workspace_floats(z.Z, z.Y, z.X);
+  }
+  return tfl::step_ws(z.B, z.Z, z.Y, z.X, (int)z.C, proj, pcg);
 }
 long long step_ws_floats(const tfl_sim_state* s, const Sizes& z, tfl::StepProj proj, const tfl::StepWs& W) {
   if (proj != tfl::StepProj::convnet || !s->model) return W.total;
@@ -159,7 +165,7 @@ int Step::validate(const char* who) {
   z = sizes_of(s);
   is3D = z.is3d ? 1 : 0;
   proj = proj_of(prm);
-  const tfl::StepWs W = step_ws_of(z, proj);
+  const tfl::StepWs W = step_ws_of(prm, z, proj);
   if (!ws || ((uintptr_t)ws & 15) != 0 || ws_floats < step_ws_floats(s, z, proj, W)) return TFL_EINVAL;
   method = (prm->advectionMethod && prm->advectionMethod[0]) ? prm->advectionMethod : "maccormackOurs";
   ours = std::strcmp(method, "maccormackOurs") == 0;
@@ -398,7 +404,7 @@ int64_t tfl_simulate_workspace_floats(tfl_ctx* c, const tfl_sim_params* prm, con
   if (!c || !prm || !s || !s->flags || !s->U) return 0;
   const Sizes z = sizes_of(s);
   const tfl::StepProj proj = proj_of(prm);
-  return step_ws_floats(s, z, proj, step_ws_of(z, proj));
+  return step_ws_floats(s, z, proj, step_ws_of(prm, z, proj));
 }
 
 int tfl_simulate_step(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state* s, float* ws, int64_t ws_floats) {

@@ -67,6 +67,7 @@ struct tfl_ctx {
   int wf_skip = 0;                            // > 0: a pipelined PCG sweep timed out on this context: the next wf_skip solves go straight to
                                               // hyperplane sweeps, then the pipelined form is tried again (a transient stall must not latch for good)
   int wf_timeouts = 0;                        // how often that happened (the back-off doubles, one warning per latch)
+  long long pcg_last_iterations = -1;         // tfl_pcg_last_iterations: CG iterations of the last tfl_solveLinearSystemPCG, summed over its component solves
   std::vector<Scal3SparseState*> scal3_sparse;   // one per density field tfl_simulate_step has advected over brick lists (at most kScal3SparseFields)
   Scal3SparseState* scal3_last = nullptr;        // the field of the last scan
   long long scal3_counts[3] = {0, 0, 0};         // EXPERIMENTS flavour (tfl_scal3_sparse_stats): scans, steps over the lists, steps on the two full launches

@@ -251,13 +251,24 @@ struct PcgProblem {
   int B, Z, Y, X;
   float* p;
   const float *flags, *div;
-  int precond;      // 0 none, 1 ilu0, 2 ic0
+  int precond;      // 0 none, 1 ilu0, 2 ic0, 3 mg
   float tol;
   int max_iter, verbose;
 };
-long long pcg_workspace_floats(int Z, int Y, int X);     // the total of pcg_ws (tfl_pcg_ws.hpp)
+long long pcg_workspace_floats(int Z, int Y, int X);     // the total of pcg_ws (tfl_pcg_ws.hpp) for none / ilu0 / ic0
+long long pcg_workspace_floats_for(int Z, int Y, int X, int precond);     // ... for PcgProblem::precond; -1: no such preconditioner
+// iterations: the sum over the component solves of the iteration counter at exit (may be null)
 PcgResult pcg_solve(hipStream_t st, const PcgProblem& q, float* workspace, float* residual, char* msg, size_t msg_len,
-                    bool allow_wavefronts);
+                    bool allow_wavefronts, long long* iterations = nullptr);
+
+// pcg_mg.hip: the multigrid preconditioner (tfl_pcg_mg.hpp). Set-up once per component (*open = 1: a cell of the component has an
+// empty neighbour, the matrix is regular); one V-cycle per application, r -> zb of level 0, every kernel of it returning at once
+// when S->done. closed: the cycle runs on r minus its mean, written to the r array of level 0; else r of level 0 is r itself.
+// partials: kRedBlocks doubles.
+struct MgDev;
+struct PcgState;
+void mg_build_levels(hipStream_t st, const Dom& d, bool is3d, const MgDev& h, const float* flags, const int* label, int root, int* open);
+void mg_vcycle(hipStream_t st, bool is3d, const MgDev& h, const PcgState* S, bool closed, const float* r, double* partials, int size);
 
 long long npm_workspace_floats(int Z, int Y, int X);     // the total of npm_ws
 PcgResult normalize_pressure_mean(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* p, const float* flags,

@@ -9,6 +9,7 @@
 
 #include <cstdint>
 
+#include "tfl_pcg_mg.hpp"       // mg_levels: the hierarchy of precondType = "mg"
 #include "tfl_step_ws.hpp"      // WsRegion
 
 namespace tfl {
@@ -86,7 +87,8 @@ struct PcgWs {
   WsRegion label, size_at;           // int32 per cell
   WsRegion x, r, z, s, w, dg, y;     // fp32 per cell
   WsRegion roots;                    // int32, kMaxComponents
-  WsRegion counters;                 // int32: [0] changed, [1] count, [2] border fluid
+  WsRegion counters;                 // int32, 64 words: [0] changed, [1] count, [2] border fluid (label_components);
+                                     // [kPcgMgOpenWord] the multigrid set-up's "open component" word
   // The pipelined wavefront sweeps (3-D; every floats = 0 and geom zeroed without them). These regions need 16 bytes (float4
   // rows, {value, tag} pairs) where the workspace promises 8: the offsets below are those of a workspace that happens to be
   // 16-byte aligned, pcg_wf_pad() gives the 0..3 floats to add to each of them for the array at hand, and kPcgWfSlack floats
@@ -97,11 +99,19 @@ struct PcgWs {
                                      // pairs of block 0 begin 2 * kWfGuard floats in
   WsRegion wf_err;                   // the error word
   WsRegion wf_clear;                 // what the per-solve memset clears: from cc to behind the error word
+  // The multigrid hierarchy (precondType = "mg"; every floats = 0 without it), appended behind everything above. Level 0 keeps its
+  // diag in dg and its second iterate in y (idle under mg) and adds invd, cx, cy, cz (n each); the coarser levels are stacked:
+  // level l >= 1 begins mg_levels().lv[l].off floats into each of the eight mg_c_* arrays (mg_levels().coarse_cells each).
+  WsRegion mg_invd0, mg_cx0, mg_cy0, mg_cz0;
+  WsRegion mg_c_diag, mg_c_invd, mg_c_cx, mg_c_cy, mg_c_cz, mg_c_r, mg_c_za, mg_c_zb;
   long long total;                   // floats the table needs
 };
 constexpr long long kPcgWfSlack = 4;
+// the word of the counters' slot that pcg_mg.hip's set-up owns: 1 when a cell of the component at hand has an empty neighbour
+constexpr int kPcgCounterWords = 64, kPcgLabelWords = 3, kPcgMgOpenWord = 8;
+static_assert(kPcgMgOpenWord >= kPcgLabelWords && kPcgMgOpenWord < kPcgCounterWords, "the open word lies in the counters' slot, behind label_components' words");
 
-inline PcgWs pcg_ws(int Z, int Y, int X, bool wavefronts) {
+inline PcgWs pcg_ws(int Z, int Y, int X, bool wavefronts, bool mg = false, bool mg_is3d = false) {
   const long long n = (long long)Z * Y * X;
   PcgWs t{};
   long long at = 0;
@@ -111,7 +121,7 @@ inline PcgWs pcg_ws(int Z, int Y, int X, bool wavefronts) {
   t.label = take(n); t.size_at = take(n);
   t.x = take(n); t.r = take(n); t.z = take(n); t.s = take(n); t.w = take(n); t.dg = take(n); t.y = take(n);
   t.roots = take(kMaxComponents);
-  t.counters = take(64);
+  t.counters = take(kPcgCounterWords);
   if (wavefronts) {
     t.geom = wf_geom(Z, Y, X);
     const long long wtot = t.geom.sub * t.geom.ns * t.geom.nb;
@@ -120,6 +130,12 @@ inline PcgWs pcg_ws(int Z, int Y, int X, bool wavefronts) {
     t.wf_err = {at, 1};
     t.wf_clear = {t.wf_cc.off, at + kWfClearTail - t.wf_cc.off};
     at += kWfErrFloats + kPcgWfSlack;
+  }
+  if (mg) {
+    const long long cc = mg_levels(Z, Y, X, mg_is3d).coarse_cells;
+    t.mg_invd0 = take(n); t.mg_cx0 = take(n); t.mg_cy0 = take(n); t.mg_cz0 = take(n);
+    t.mg_c_diag = take(cc); t.mg_c_invd = take(cc); t.mg_c_cx = take(cc); t.mg_c_cy = take(cc); t.mg_c_cz = take(cc);
+    t.mg_c_r = take(cc); t.mg_c_za = take(cc); t.mg_c_zb = take(cc);
   }
   t.total = at;
   return t;

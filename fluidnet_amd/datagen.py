@@ -47,6 +47,7 @@ def default_gconf(is3D=False, dims=None, **over):
     saveEvery are the paper's recipe (256 steps, every 4th saved)."""
     g = dict(is3D=bool(is3D), dims=tuple(dims) if dims is not None else ((64, 64, 64) if is3D else (1, 128, 128)),
              steps=256, saveEvery=4, dt=0.1, advectionMethod="maccormack", maccormackStrength=0.6, maxIter=100,
+             pcgPrecond="ic0",          # the preconditioner of every PCG solve of a run: 'none' | 'ilu0' | 'ic0' | 'mg' (tfluids.solveLinearSystemPCG)
              maxSpheres=3, maxBoxes=3, maxBlobs=3, maxEmitters=2, maxModels=1, models=(),
              # emitterSpeed: 0 (default): an emitter is a densityBC pair only. > 0: it also carries a UBC pair of that share of the
              # speed cap. A velocity imposed AFTER the projection leaves divergence on the emitter's surface, so such runs exceed
@@ -234,14 +235,14 @@ def plan_run(gconf, seed, run, attempt=0):
                 emitters=emitters, voxels=None if voxels is None else voxels.astype(np.uint8), noise_radius=radius,
                 noise_passes=passes, speed=speed, gravity=gravity, buoyancyScale=buoyancy, vorticityConfinementAmp=vort,
                 dt=float(gconf["dt"]), advectionMethod=gconf["advectionMethod"], maccormackStrength=float(gconf["maccormackStrength"]),
-                maxIter=int(gconf["maxIter"]))
+                maxIter=int(gconf["maxIter"]), pcgPrecond=str(gconf.get("pcgPrecond") or "ic0"))
 
 
 def mconf_of(plan):
     """the mconf every step of the plan's run is simulated with"""
     return dict(dt=plan["dt"], advectionMethod=plan["advectionMethod"], maccormackStrength=plan["maccormackStrength"],
                 buoyancyScale=plan["buoyancyScale"], gravityScale=0, vorticityConfinementAmp=plan["vorticityConfinementAmp"],
-                gravity=list(plan["gravity"]), simMethod="pcg", maxIter=plan["maxIter"])
+                gravity=list(plan["gravity"]), simMethod="pcg", maxIter=plan["maxIter"], pcgPrecond=plan.get("pcgPrecond") or "ic0")
 
 
 def noise_seed(plan):
@@ -339,7 +340,7 @@ def init_state(plan, device):
     div = torch.empty_like(flags)
     tfluids.setWallBcsForward(U, flags)
     tfluids.velocityDivergenceForward(U, flags, div)
-    tfluids.solveLinearSystemPCG(p, flags, div, is3D, 1e-4, plan["maxIter"], "ic0")
+    tfluids.solveLinearSystemPCG(p, flags, div, is3D, 1e-4, plan["maxIter"], plan.get("pcgPrecond") or "ic0")
     tfluids.velocityUpdateForward(U, flags, p)
     p.zero_()
     batch = dict(pDiv=p, UDiv=U, flags=flags, density=density, div=div)

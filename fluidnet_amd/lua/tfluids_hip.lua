@@ -96,6 +96,8 @@ int tfl_rectangularBlur(tfl_ctx* ctx, const tfl_tensor* src, int blurRad, int is
                         const tfl_tensor* tmp);
 int tfl_signedDistanceField(tfl_ctx* ctx, const tfl_tensor* flags, int searchRad, int is3D, const tfl_tensor* dst);
 int64_t tfl_pcg_workspace_floats(int32_t Z, int32_t Y, int32_t X);
+int64_t tfl_pcg_workspace_floats_for(int32_t Z, int32_t Y, int32_t X, const char* precondType);
+int64_t tfl_pcg_last_iterations(tfl_ctx* ctx);
 int tfl_solveLinearSystemPCG(tfl_ctx* ctx, const tfl_tensor* p, const tfl_tensor* flags, const tfl_tensor* div,
                              int is3D, const char* precondType, float tol, int maxIter, int verbose,
                              float* workspace, int64_t workspace_floats, float* residual);
@@ -446,11 +448,18 @@ end
 -- init.lua:674-676: p.tfluids.solveLinearSystemPCG(tfluids._tmpPCG, p, flags, div, is3D, precondType, tol, maxIter,
 -- verbose) -> residual. The reference's cache table of cuSPARSE temporaries is ignored: the workspace is ours.
 function ops.solveLinearSystemPCG(tmpPCG, p, flags, div, is3D, precondType, tol, maxIter, verbose)
-  local ws, n = workspace(p, lib.tfl_pcg_workspace_floats(flags:size(3), flags:size(4), flags:size(5)))
+  -- sized for the preconditioner ('mg' adds its hierarchy); a name that is none gets the common size and is refused by the call
+  local need = lib.tfl_pcg_workspace_floats_for(flags:size(3), flags:size(4), flags:size(5), precondType)
+  if need < 0 then need = lib.tfl_pcg_workspace_floats(flags:size(3), flags:size(4), flags:size(5)) end
+  local ws, n = workspace(p, need)
   local res = ffi.new('float[1]')
   check(lib.tfl_solveLinearSystemPCG(ctx, T(p), T(flags), T(div), b2i(is3D), precondType, tol, maxIter,
                                      b2i(verbose), ws, n, res))
   return res[0]
+end
+-- CG iterations of the last solveLinearSystemPCG, summed over its component solves (-1 before any solve)
+function ops.pcgLastIterations()
+  return tonumber(lib.tfl_pcg_last_iterations(ctx))
 end
 
 -- ---- tfluids.normalizePressureMean on the device (init.lua:747-764 copies to the host and back) ---------------------

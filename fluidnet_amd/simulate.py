@@ -273,7 +273,8 @@ def simulate(conf, mconf, batch, model, outputDiv=False):
     elif simMethod == "pcg":
         # simulate.lua:281-286: tol 1e-4, maxIter (default 100), 'ic0' -- the default here too (pipelined wavefront
         # sweeps, pcg.hip); mconf.pcgPrecond = 'none' | 'ilu0' | 'ic0' overrides ('none' is ~1.7x faster per solve at
-        # 128^3 on this machine but needs ~3x the iterations, which matters under a small maxIter).
+        # 128^3 on this machine but needs ~3x the iterations, which matters under a small maxIter); 'mg' (not in the reference)
+        # is one multigrid V-cycle per iteration (pcg_mg.hip), no sweeps; what it took on the grids measured: profiles/pcg_mg.md.
         div = batch.get("div")
         if div is None or div.shape != p.shape:
             div = torch.empty_like(p)

@@ -458,8 +458,9 @@ def signedDistanceField(flags, searchRad, is3D, dst):
 
 def solveLinearSystemPCG(p, flags, div, is3D, tol=None, maxIter=None, precondType=None, verbose=None):
     """init.lua:645-677: the baseline (P)CG pressure solve, A p = div per connected fluid component.
-    precondType 'none' | 'ilu0' | 'ic0' (default 'ic0'), tol default 1e-6, maxIter default 1000.
-    Returns the max residual over the solved systems (host sync, as in the reference)."""
+    precondType 'none' | 'ilu0' | 'ic0' | 'mg' (default 'ic0'; 'mg' is not in the reference: one multigrid V-cycle per
+    iteration, csrc/pcg_mg.hip), tol default 1e-6, maxIter default 1000.
+    Returns the max residual over the solved systems (host sync, as in the reference); pcgLastIterations() has the iterations."""
     _check(p.dim() == 5 and flags.dim() == 5 and div.dim() == 5, "Dimension mismatch")
     _check(flags.size(1) == 1, "flags is not scalar")
     bsz, _, d, h, w = flags.shape
@@ -473,13 +474,22 @@ def solveLinearSystemPCG(p, flags, div, is3D, tol=None, maxIter=None, precondTyp
     maxIter = 1000 if maxIter is None else maxIter
     _check(p.is_contiguous() and flags.is_contiguous() and div.is_contiguous(), "Input is not contiguous")
     lib, ctx = _context(p)
-    nws = int(lib.tfl_pcg_workspace_floats(d, h, w))
+    nws = int(lib.tfl_pcg_workspace_floats_for(d, h, w, str(precondType).encode()))
+    if nws < 0:         # not a preconditioner: the library refuses the call below
+        nws = int(lib.tfl_pcg_workspace_floats(d, h, w))
     ws = getTempStorage(p, [(nws,)])[0]
     res = ctypes.c_float(0.0)
     _call(lib, ctx, lib.tfl_solveLinearSystemPCG(ctx, _tt(p), _tt(flags), _tt(div), int(bool(is3D)),
                                                  str(precondType).encode(), float(tol), int(maxIter), int(verbose),
                                                  ctypes.c_void_p(ws.data_ptr()), nws, ctypes.byref(res)))
     return res.value
+
+
+def pcgLastIterations(like):
+    """CG iterations of the last solveLinearSystemPCG on the device of tensor `like` (its context), summed over the component
+    solves; -1 before any solve."""
+    lib, ctx = _context(like)
+    return int(lib.tfl_pcg_last_iterations(ctx))
 
 
 def normalizePressureMean(p, flags, is3D):

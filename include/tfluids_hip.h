@@ -255,15 +255,23 @@ int tfl_signedDistanceField(tfl_ctx* ctx, const tfl_tensor* flags, int searchRad
  * component (generic/find_connected_fluid_components.cc) of every batch element is solved by (P)CG from x = 0 with
  * the Laplacian of setupLaplacian (generic/tfluids.cu:904-1093), the component's mean is removed and the result
  * scattered into p; components of one cell are skipped, of fewer than five use no preconditioner.
- * precondType: "none" | "ilu0" | "ic0" (init.lua default "ic0"); tol (default 1e-6) on ||r||; maxIter (default
+ * precondType: "none" | "ilu0" | "ic0" | "mg" (init.lua default "ic0"); tol (default 1e-6) on ||r||; maxIter (default
  * 1000); *residual = max over the solves of the final ||r|| (-inf if there was nothing to solve).
  * The reference keeps its temporaries in the tfluids._tmpPCG table; here the caller passes a workspace of
- * tfl_pcg_workspace_floats(Z, Y, X) floats (8-byte aligned). Synchronises the stream (as the reference does after
+ * tfl_pcg_workspace_floats_for(Z, Y, X, precondType) floats (8-byte aligned; tfl_pcg_workspace_floats(Z, Y, X) is that number
+ * for "none" | "ilu0" | "ic0", the _for form returns -1 for a name that is no preconditioner). Synchronises the stream (as the reference does after
  * every dot product). On 3-D grids the IC(0) / ILU(0) triangular solves run as pipelined wavefronts whose sub-boxes wait
  * for each other (all of them must be resident on the GPU at once); if one times out (~1 s: something else holds part of
  * the GPU) the solve is repeated with one launch per hyperplane. TFL_PCG_HYPERPLANES=1 in the environment selects that
- * schedule from the start. Returns TFL_EINVAL for a fluid cell on the domain border (the reference raises). */
+ * schedule from the start. "mg" is not in the reference: one symmetric V-cycle of aggregation multigrid per CG iteration
+ * (damped Jacobi, piecewise-constant prolongation, Galerkin coarse operators, matrix-free from the flags) in which no block
+ * waits for another one, so it has no such fallback; deterministic. Iterations and times measured so far: profiles/pcg_mg.md.
+ * tfl_pcg_last_iterations: the CG iterations of the last tfl_solveLinearSystemPCG on this context that returned TFL_OK, summed
+ * over its component solves (the iteration counter of each at exit); -1 before any solve.
+ * Returns TFL_EINVAL for a fluid cell on the domain border (the reference raises). */
 int64_t tfl_pcg_workspace_floats(int32_t Z, int32_t Y, int32_t X);
+int64_t tfl_pcg_workspace_floats_for(int32_t Z, int32_t Y, int32_t X, const char* precondType);
+int64_t tfl_pcg_last_iterations(tfl_ctx* ctx);
 int tfl_solveLinearSystemPCG(tfl_ctx* ctx, const tfl_tensor* p, const tfl_tensor* flags, const tfl_tensor* div,
                              int is3D, const char* precondType, float tol, int maxIter, int verbose,
                              float* workspace, int64_t workspace_floats, float* residual);
@@ -653,7 +661,7 @@ typedef struct tfl_sim_params {      /* mconf of lib/simulate.lua (defaults of l
   double vorticityConfinementAmp;    /* 0 = off */
   const char* simMethod;             /* NULL | "convnet" | "jacobi" | "pcg" */
   int32_t maxIter;                   /* jacobi / pcg; <= 0 -> 100 */
-  const char* pcgPrecond;            /* NULL = "ic0" like simulate.lua:283; "none" | "ilu0" | "ic0". The unpreconditioned
+  const char* pcgPrecond;            /* NULL = "ic0" like simulate.lua:283; "none" | "ilu0" | "ic0" | "mg". The unpreconditioned
                                         solve is ~1.7x faster per call at 128^3 here (slower at 256^3) and takes ~3x the iterations */
   int32_t outputDiv;                 /* 1: return before the projection (simulate.lua:241-245) */
 } tfl_sim_params;

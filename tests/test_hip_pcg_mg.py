@@ -1,0 +1,262 @@
+"""precondType = 'mg' of solveLinearSystemPCG (fluidnet_amd/csrc/pcg_mg.hip; DESIGN.md, the multigrid preconditioner) on the
+device: converged solves against the oracle's 'ic0' solution with the assertions of test_hip_parity.py's PCG test; the iterates
+of the ladder per cell against the fp64 restatement of tests/pcg_mg_ref64.py (bound C_ITERATE, derived there); iteration counts
+through pcgLastIterations; the component rules; determinism; the workspace sizes; the step (simulate, simulate_native, project)
+and the data-set generator with pcgPrecond = 'mg'."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import pcg_mg_ref64 as M
+import pcg_ref64 as R
+import scenes
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+@pytest.fixture(scope="module")
+def hip():
+    from hip_adapter import HipTfluids
+    return HipTfluids(DEV)
+
+
+def _last_iterations():
+    import torch
+    from fluidnet_amd import tfluids
+    return tfluids.pcgLastIterations(torch.empty(1, device=DEV))
+
+
+# ---- 1. converged solves ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dims,seed,split,B,tol", [((1, 24, 28), 3, False, 1, 1e-5), ((9, 11, 13), 4, False, 2, 1e-5),
+                                                  ((1, 30, 34), 5, True, 1, 1e-5), ((8, 10, 16), 6, True, 1, 1e-5),
+                                                  ((24, 20, 36), 8, False, 1, 1e-4), ((1, 96, 128), 9, True, 1, 1e-4),
+                                                  ((36, 134, 22), 10, True, 1, 1e-4)])
+def test_mg_converges_to_the_oracles_ic0_solution(hip, oracle, dims, seed, split, B, tol):
+    """the seven cases and the assertions of test_hip_pcg_matches_the_oracle_and_the_reference_properties, with 'mg' on the
+    device against 'ic0' in the oracle"""
+    sc, f, U, div = scenes.pcg_problem(oracle, dims, seed, split=split, B=B, vel_cells=2.0 if tol < 5e-5 else 0.3)
+    pa = np.random.RandomState(2).rand(*div.shape).astype(np.float32)
+    pb = pa.copy()
+    ra = hip.solveLinearSystemPCG(pa, f, div, sc["is3d"], tol, 1000, "mg")
+    its = _last_iterations()
+    rb = oracle.solveLinearSystemPCG(pb, f, div, sc["is3d"], tol, 1000, "ic0")
+    scale = max(np.abs(pb).max(), 1e-6)
+    print("MGCONV %s tol %g: residual %.3e (oracle ic0 %.3e), iterations %d, max|p - p_ic0| %.3e, scale %.3e"
+          % (dims, tol, ra, rb, its, np.abs(pa - pb).max(), scale))
+    assert ra < 2 * tol and rb < 2 * tol and np.isfinite(pa).all(), (ra, rb)
+    assert np.abs(pa - pb).max() < max(5e-5 * scale, 50 * tol), (np.abs(pa - pb).max(), scale)
+    assert np.all(pa[f != 1.0] == 0.0)
+    Un = U.copy()
+    hip.velocityUpdateForward(Un, f, pa)
+    d2 = np.zeros_like(div)
+    hip.velocityDivergenceForward(Un, f, d2)
+    assert np.abs(d2).max() < max(3e-5 * max(1.0, np.abs(div).max()), 2 * tol), np.abs(d2).max()
+
+
+# ---- 2. iterates ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(M.CASES))
+def test_mg_iterates_against_the_fp64_restatement(hip, oracle, name):
+    """rungs maxIter = 0, 1, 3 with a tolerance that never fires: every cell within C_ITERATE max|p64| of its component, the
+    returned residual within C_RESIDUAL relative, exact zeros outside the solved components"""
+    f, div, is3d = M.case(name)
+    ref = M.reference(name)
+    for k in M.RUNGS:
+        p = np.random.RandomState(3).rand(*div.shape).astype(np.float32)
+        res = hip.solveLinearSystemPCG(p, f, div, is3d, R.TOL_NEVER, k, "mg")
+        err, zero = R.worst_error(p, ref["p"][k], ref)
+        dres = abs(float(res) - ref["res"][k]) / ref["res"][k]
+        print("MGIT %-18s rung %d err %.2e (bound %.1e) residual %.2e" % (name, k, err, M.C_ITERATE, dres))
+        assert np.isfinite(p).all() and zero, (name, k)
+        assert err <= M.C_ITERATE, (name, k, err)
+        assert dres <= M.C_RESIDUAL, (name, k, float(res), ref["res"][k])
+        assert _last_iterations() == (k + 1) * sum(1 for s in ref["sizes"] for n in s if n > 1)
+
+
+# ---- 3. iteration counts ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [n for n in sorted(M.CASES)])
+def test_mg_iteration_counts(hip, oracle, name):
+    """on the cases of 500 cells or more: no more iterations than 'ic0' at tol 1e-5, and the restatement's count within 2"""
+    assert M.cells(name) >= 500
+    f, div, is3d = M.case(name)
+    its = {}
+    for pc in ("mg", "ic0"):
+        p = np.zeros_like(div)
+        hip.solveLinearSystemPCG(p, f, div, is3d, 1e-5, 1000, pc)
+        its[pc] = _last_iterations()
+    want = M.iterations(name, "mg")
+    print("MGCOUNT %-18s mg %d ic0 %d restatement mg %d ic0 %d" % (name, its["mg"], its["ic0"], want, M.iterations(name, "ic0")))
+    assert its["mg"] <= its["ic0"], its
+    assert abs(its["mg"] - want) <= 2, (its, want)
+
+
+# ---- 4. component rules -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["pockets_flat_20x22", "pockets_9x14x12"])
+def test_small_components_take_the_unpreconditioned_path(hip, oracle, name):
+    """a one-cell component is untouched (p = 0 there), pockets of 2 - 4 cells carry the bits of 'none'; the large component
+    differs from 'none' (it is preconditioned)"""
+    f, div, is3d = R.case(name)
+    ref = R.reference(name, "none")
+    got = {}
+    for pc in ("mg", "none"):
+        p = np.random.RandomState(4).rand(*div.shape).astype(np.float32)
+        hip.solveLinearSystemPCG(p, f, div, is3d, R.TOL_NEVER, 3, pc)
+        got[pc] = p
+    sizes, comp = ref["sizes"][0], ref["comp"][0]
+    assert 1 in sizes and 3 in sizes and max(sizes) >= 5
+    for c, size in enumerate(sizes):
+        m = comp == c
+        a, b = got["mg"][0, 0][m], got["none"][0, 0][m]
+        if size == 1:
+            assert np.all(a == 0.0)
+        elif size < 5:
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and np.any(a != 0.0), (c, size)
+        else:
+            assert not np.array_equal(a, b), (c, size)
+
+
+def test_batch_items_with_their_own_flags(hip, oracle):
+    """B = 2 with other flags in item 1 (a wall: two components): item 1 solved alone gives the bits it has in the batch"""
+    f, div, is3d = M.case("batch_9x11x13")
+    assert not np.array_equal(f[0], f[1])
+    p = np.zeros_like(div)
+    hip.solveLinearSystemPCG(p, f, div, is3d, 1e-5, 1000, "mg")
+    both = _last_iterations()
+    p1 = np.zeros_like(div[1:2])
+    hip.solveLinearSystemPCG(p1, np.ascontiguousarray(f[1:2]), np.ascontiguousarray(div[1:2]), is3d, 1e-5, 1000, "mg")
+    assert np.array_equal(p1.view(np.uint32), p[1:2].view(np.uint32)) and 0 < _last_iterations() < both
+
+
+# ---- 5. determinism ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["flat_odd_33x47", "odd_12x17x20"])
+def test_mg_is_deterministic(hip, oracle, name):
+    """two solves give the same bits, and so does one behind an 'ic0' solve in the same workspace"""
+    f, div, is3d = M.case(name)
+    out = []
+    for pc in ("mg", "mg", "ic0", "mg"):
+        p = np.zeros_like(div)
+        res = hip.solveLinearSystemPCG(p, f, div, is3d, 1e-5, 1000, pc)
+        out.append((pc, p, res, _last_iterations()))
+    first = out[0]
+    for pc, p, res, its in out[1:]:
+        if pc == "mg":
+            assert np.array_equal(p.view(np.uint32), first[1].view(np.uint32)) and res == first[2] and its == first[3]
+
+
+# ---- 6. sizes ---------------------------------------------------------------------------------------------------------------
+def test_workspace_sizes_and_the_refusal_of_the_old_size():
+    import torch
+    from fluidnet_amd import tfluids
+    like = torch.empty(1, device=DEV)
+    lib, ctx = tfluids._context(like)
+    for dims in ((1, 24, 28), (1, 33, 47), (9, 11, 13), (36, 134, 22), (64, 64, 64)):
+        old = int(lib.tfl_pcg_workspace_floats(*dims))
+        for pc in (b"none", b"ilu0", b"ic0", None):
+            assert int(lib.tfl_pcg_workspace_floats_for(*dims, pc)) == old
+        assert int(lib.tfl_pcg_workspace_floats_for(*dims, b"jacobi")) == -1
+        assert int(lib.tfl_pcg_workspace_floats_for(*dims, b"mg")) > 0
+    dims = (1, 24, 28)
+    old, new = int(lib.tfl_pcg_workspace_floats(*dims)), int(lib.tfl_pcg_workspace_floats_for(*dims, b"mg"))
+    assert old < new
+    f = torch.from_numpy(np.ascontiguousarray(M.case("flat_24x28")[0])).to(DEV)
+    div = torch.from_numpy(np.ascontiguousarray(M.case("flat_24x28")[1])).to(DEV)
+    p = torch.zeros_like(div)
+    ws = torch.empty(new, device=DEV)
+    res = ctypes.c_float(0.0)
+
+    def call(pc, nws):
+        return lib.tfl_solveLinearSystemPCG(ctx, tfluids._tt(p), tfluids._tt(f), tfluids._tt(div), 0, pc, 1e-5, 1000, 0,
+                                            ctypes.c_void_p(ws.data_ptr()), nws, ctypes.byref(res))
+    assert call(b"mg", old) != 0 and "tfl_pcg_workspace_floats_for" in lib.tfl_last_error(ctx).decode()
+    assert float(p.abs().max()) == 0.0
+    assert call(b"mg", new) == 0 and call(b"ic0", old) == 0
+    assert call(b"mgx", new) != 0 and lib.tfl_last_error(ctx).decode() == "solveLinearSystemPCG: precondType is not supported."
+    with pytest.raises(tfluids.TfluidsError, match="precondType is not supported"):
+        tfluids.solveLinearSystemPCG(p, f, div, False, 1e-5, 10, "multigrid")
+
+
+# ---- 7. the step ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dims,rad,usc", [((1, 32, 32), 0.1, 3.0), ((12, 16, 20), 0.15, 1.0)])
+def test_the_step_with_mg(oracle, dims, rad, usc):
+    """simulate() and simulate_native() with simMethod = 'pcg', pcgPrecond = 'mg' leave the same bits; both are within the
+    step-level PCG tolerance of test_hip_simulate.py (rel-L2 2e-4) of the 'ic0' step; an outputDiv step followed by project()
+    equals one full step. (The top face is open, as in test_hip_simulate.py's PCG steps: a regular system, the open-component
+    path. Closed components at step level: test_the_generator_with_mg.)"""
+    import torch
+    from fluidnet_amd.simulate import project, simulate, simulate_native
+    from test_hip_simulate import _plume_batch, _to_dev
+    b = _plume_batch(dims, rad, usc, obstacles_seed=5)
+    Y = dims[1]
+    top = b["flags"][:, :, 1:-1, Y - 2, 1:-1] if dims[0] > 1 else b["flags"][:, :, :, Y - 2, 1:-1]
+    top[...] = 4.0                                     # open top: a well-posed system
+    base = dict(dt=0.1, advectionMethod="maccormackOurs", maccormackStrength=0.75, buoyancyScale=1.0, gravityScale=0,
+                vorticityConfinementAmp=0.5, simMethod="pcg", maxIter=400)
+    mg, ic = dict(base, pcgPrecond="mg"), dict(base, pcgPrecond="ic0")
+    dev = torch.device(DEV)
+    ta, tn, ti, tp = (_to_dev(b, dev) for _ in range(4))
+    for _ in range(3):
+        simulate(None, mg, ta, None)
+        simulate_native(None, mg, tn, None)
+        simulate(None, ic, ti, None)
+        simulate(None, mg, tp, None, outputDiv=True)
+        project(None, mg, tp)
+    for k in ("pDiv", "UDiv", "density"):
+        assert torch.equal(ta[k], tn[k]), k
+        assert torch.equal(ta[k], tp[k]), k
+    for k in ("UDiv", "density"):
+        r = scenes.rel_l2(ta[k].cpu().numpy(), ti[k].cpu().numpy())
+        print("MGSTEP %s %s rel-L2 against the ic0 step %.3e" % (dims, k, r))
+        assert np.isfinite(ta[k].cpu().numpy()).all() and r <= 2e-4, (k, r)
+
+
+# ---- 8. the generator -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("is3D,dims", [(False, (1, 32, 32)), (True, (12, 16, 20))], ids=["2d", "3d"])
+def test_the_generator_with_mg(is3D, dims):
+    """the plans of test_hip_datagen.py (2 runs x 6 frames): with pcgPrecond = 'mg' no run is dropped under data.DIV_THRESHOLD;
+    the default is 'ic0' and a configuration that does not name a preconditioner produces the same bits as one that names 'ic0'.
+    (Both of those run this code: that the default still produces the bits it produced before 'mg' existed rests on the
+    untouched tests/test_hip_datagen.py, which holds generate() to the two-call restatement bit for bit. The generator's scenes
+    are closed boxes: this is the test that takes the closed-component path -- the mean of r removed -- through whole steps.)"""
+    import torch
+    import datagen_ref as G
+    from fluidnet_amd import data, datagen
+    from fluidnet_amd.data import FrameStore
+    from test_hip_datagen import KEYS, _gather_all
+    g = G.gen_gconf(is3D, dims)
+    assert g["pcgPrecond"] == "ic0" and g["divThreshold"] == data.DIV_THRESHOLD
+    plan = datagen.plan_run(g, G.GEN_SEED, 0)
+    assert plan["pcgPrecond"] == "ic0" and datagen.mconf_of(plan)["pcgPrecond"] == "ic0"
+    gm = dict(g, pcgPrecond="mg")
+    assert datagen.mconf_of(datagen.plan_run(gm, G.GEN_SEED, 0))["pcgPrecond"] == "mg"
+    bare = {k: v for k, v in g.items() if k != "pcgPrecond"}
+    stores = [FrameStore(DEV, is3D, *dims, 12, 6) for _ in range(3)]
+    try:
+        res = datagen.generate(gm, "tr", G.GEN_RUNS, G.GEN_SEED, store=stores[0], device=DEV)
+        print("MGGEN %s max div per run: %s" % (dims, ["%.3e" % r["max_div"] for r in res["report"]]))
+        assert res["runs"] == [("000000", 6), ("000001", 6)] and [r["kept"] for r in res["report"]] == [True, True]
+        assert all(r["attempt"] == 0 and r["max_div"] <= data.DIV_THRESHOLD for r in res["report"])
+        datagen.generate(g, "tr", G.GEN_RUNS, G.GEN_SEED, store=stores[1], device=DEV)
+        datagen.generate(bare, "tr", G.GEN_RUNS, G.GEN_SEED, store=stores[2], device=DEV)
+        with_mg, named, unnamed = (_gather_all(s, is3D, dims, 12) for s in stores)
+        for key in KEYS:
+            assert torch.equal(named[key], unnamed[key]), key
+        assert not torch.equal(with_mg["pTarget"], named["pTarget"])
+    finally:
+        for s in stores:
+            s.close()
+
+
+def test_experiments_flavour_runs_this_file_green():
+    """the second library flavour (libtfluids_hip_exp.so) carries the same kernels: this file in a child process against it"""
+    import os
+    import subprocess
+    import sys
+    import flavours
+    if flavours.is_experiments_process():
+        return
+    assert os.path.exists(flavours.EXP_LIB), "fluidnet_amd/libtfluids_hip_exp.so is not built (make -C fluidnet_amd/csrc exp)"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"], cwd=root,
+                         env=dict(os.environ, TFL_LIBRARY=flavours.EXP_LIB), capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and " passed" in out.stdout and "failed" not in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]

@@ -12,7 +12,8 @@ and one whole run of the paper's recipe (256 steps, every 4th saved; scene set-u
 Protocol of profiles/data_gather.md: one process, the forms alternated round by round, a round = `calls` calls between two
 device events after a synchronise, FIVE rounds, the median of the rounds, min .. max beside it. Nothing is asserted but that the
 forms agree bit for bit.
-usage: python tools/datagen_bench.py [--out profiles/datagen.md] [--calls 20]"""
+--pcgPrecond names the preconditioner of every PCG solve (default 'ic0'; profiles/pcg_mg.md has the 'mg' rows).
+usage: python tools/datagen_bench.py [--out profiles/datagen.md] [--calls 20] [--pcgPrecond ic0]"""
 import argparse
 import json
 import os
@@ -56,8 +57,8 @@ def _timed(forms, calls, before=None):
     return out
 
 
-def measure(is3D, dims, calls):
-    g = datagen.default_gconf(is3D, dims)
+def measure(is3D, dims, calls, precond="ic0"):
+    g = datagen.default_gconf(is3D, dims, pcgPrecond=precond)
     plan = datagen.plan_run(g, SEED, 0)
     mconf = datagen.mconf_of(plan)
     batch = datagen.init_state(plan, DEV)
@@ -135,12 +136,12 @@ def measure(is3D, dims, calls):
                           buoyancyScale=plan["buoyancyScale"], vorticityConfinementAmp=plan["vorticityConfinementAmp"]))
 
 
-def report(results, path, oracle_lines):
+def report(results, path, oracle_lines, precond="ic0"):
     f3 = lambda r, t, k: "%.1f (%.1f .. %.1f)" % (r[t][k], r[t + "_min_max"][k][0], r[t + "_min_max"][k][1])
     lines = ["# The data-set generator (tools/datagen_bench.py)", "",
-             "%s, HIP %s. %d rounds, the forms alternated round by round, device events around a round after a synchronise; medians "
+             "%s, HIP %s. pcgPrecond = '%s'. %d rounds, the forms alternated round by round, device events around a round after a synchronise; medians "
              "of the rounds, min .. max beside them. Every figure below comes from this one run on the device named here."
-             % (torch.cuda.get_device_name(0), torch.version.hip, ROUNDS), "",
+             % (torch.cuda.get_device_name(0), torch.version.hip, precond, ROUNDS), "",
              "## One saved frame pair into the store", "",
              "| shape | record bytes | put_device, HBM slot us | put_device, host-mapped slot us | host route us | memcpy D2D us | put_device / D2D | host route / put_device |",
              "|---|---|---|---|---|---|---|---|"]
@@ -164,7 +165,7 @@ def report(results, path, oracle_lines):
                                                             s["generator_step"] - s["two_call_step"]))
     lines += ["", "generator step: `simulate(outputDiv=True)`, the half-put of the divergent frame, `simulate.project`, the half-put of the "
               "target frame. two-call: the same without the puts. plain: one `simulate()`. All three start every round from the same "
-              "snapshot and leave equal bits (checked in the run). Almost all of a step is the PCG solve (maxIter 100, IC(0), a host "
+              "snapshot and leave equal bits (checked in the run). Almost all of a step is the PCG solve (maxIter 100, the preconditioner named above, a host "
               "read of the residual per solve), which the three forms share; where `two-call - plain` is smaller than the forms' own "
               "min .. max it is not a cost that this run can show. Where it is larger, no measurement here says where it goes. What "
               "the two-call form does more than the plain step, and so the supposed cause: a second host entry per step (`project` "
@@ -183,11 +184,11 @@ def report(results, path, oracle_lines):
         f.write("\n".join(lines) + "\n")
 
 
-def device_figures_of_the_test_plans():
+def device_figures_of_the_test_plans(precond="ic0"):
     """max div(U target) of the runs tests/test_hip_datagen.py generates, on the device (the CPU figures are in the test's output)"""
     out = []
     for is3D, dims in ((False, (1, 32, 32)), (True, (12, 16, 20))):
-        g = datagen.default_gconf(is3D, dims, steps=12, saveEvery=2)
+        g = datagen.default_gconf(is3D, dims, steps=12, saveEvery=2, pcgPrecond=precond)
         store = FrameStore(DEV, is3D, *dims, 12, 12)
         try:
             res = datagen.generate(g, "tr", 2, SEED, store=store, device=DEV)
@@ -199,23 +200,28 @@ def device_figures_of_the_test_plans():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "datagen.md"))
+    ap.add_argument("--out", default=None, help="default profiles/datagen.md with 'ic0'; required with another preconditioner")
     ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--pcgPrecond", default="ic0", choices=("none", "ilu0", "ic0", "mg"))
     a = ap.parse_args()
+    if a.out is None:
+        if a.pcgPrecond != "ic0":
+            ap.error("--out is required with --pcgPrecond %s: profiles/datagen.md is the record of the 'ic0' run" % a.pcgPrecond)
+        a.out = os.path.join(ROOT, "profiles", "datagen.md")
     if not torch.cuda.is_available():
         raise SystemExit("datagen_bench needs an MI355X: nothing is measured without one")
     results = []
     for is3D, dims in ((False, (1, 128, 128)), (True, (64, 64, 64))):
-        r = measure(is3D, dims, a.calls)
+        r = measure(is3D, dims, a.calls, a.pcgPrecond)
         print(json.dumps(r), flush=True)
         results.append(r)
     oracle_lines = ["`tests/test_hip_datagen.py` generates 2 runs x 6 saved frames (seed %d, 12 steps, every 2nd saved) at 1x32x32 and 12x16x20 and "
                     "requires that no run is dropped by `data.DIV_THRESHOLD` = %g. The signed maximum of div(U target) per run on the device, "
                     "in this run (the CPU figures of the same plans, from the oracle's operators, are printed by "
                     "`pytest tests/test_datagen_cpu.py -s` and are not repeated by this tool):" % (SEED, data.DIV_THRESHOLD), ""]
-    for dims, divs, kept in device_figures_of_the_test_plans():
+    for dims, divs, kept in device_figures_of_the_test_plans(a.pcgPrecond):
         oracle_lines.append("* %s: %s, %s" % ("x".join(str(d) for d in dims), ", ".join("%.3e" % d for d in divs), "all kept" if kept else "A RUN WAS DROPPED"))
-    report(results, a.out, oracle_lines)
+    report(results, a.out, oracle_lines, a.pcgPrecond)
 
 
 if __name__ == "__main__":
