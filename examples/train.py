@@ -50,6 +50,9 @@ def main():
     ap.add_argument("--no-long-term", action="store_true", help="longTermDivLambda = 0: no rollout pass")
     ap.add_argument("--no-eval", action="store_true", help="evaluateDuringTraining = false: no test set is loaded")
     ap.add_argument("--resume", default=None, help="a _lastEpoch.npz to continue from")
+    ap.add_argument("--pcgBatched", action="store_true",
+                    help="mconf.pcgBatched: where trainTargetSource = 'pcg', calcPUTargets solves all batch items in the same "
+                         "launches ('mg'); without --resume only, a resumed run keeps its saved mconf")
     a = ap.parse_args()
     conf = dict(dataDir=a.dataDir, dataset=a.dataset, ignoreFrames=a.ignoreFrames, batchSize=a.batchSize, maxEpochs=a.epochs,
                 modelDirname=a.out, evaluateDuringTraining=not a.no_eval, maxSamplesPerEpoch=a.maxSamplesPerEpoch, seed=a.seed,
@@ -59,6 +62,8 @@ def main():
     print("==> loaded %d training samples (%s, %d x %d x %d), %d of %d frames in HBM"
           % (tr.nsamples(), "3D" if tr.is3D else "2D", tr.zdim, tr.ydim, tr.xdim, tr.device_frames, tr.capacity))
     mconf = None if a.resume else default_mconf(a.modelType, not a.no_long_term)
+    if mconf is not None and a.pcgBatched:
+        mconf["pcgBatched"] = True
     out = fit(conf, mconf, tr, te, resume=a.resume)
     print("==> %d epochs run, now at epoch %d: trLoss %.4e teLoss %.4e, bestPerf %.4e"
           % (out["epochs"], out["mconf"]["epoch"], (out["trPerf"] or {}).get("aveLoss", float("nan")),

@@ -215,6 +215,9 @@ SIGNATURES = {
     "tfl_pcg_last_iterations": (_c.c_int64, [_c.c_void_p]),
     "tfl_solveLinearSystemPCG": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int, _c.c_char_p, _c.c_float, _c.c_int, _c.c_int,
                                             _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "tfl_pcg_batched_workspace_floats": (_c.c_int64, [_c.c_int32, _c.c_int32, _c.c_int32, _c.c_int32, _c.c_char_p]),
+    "tfl_solveLinearSystemPCGBatched": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int, _c.c_char_p, _c.c_float, _c.c_int,
+                                                   _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p]),
     "tfl_getDx": (_c.c_double, [_c.c_void_p, _T]),
     "tfl_copy": (_c.c_int, [_c.c_void_p, _T, _T]),
     "tfl_stream_copy": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64]),

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "tfl_abi.hpp"
 #include "tfl_advect.hpp"
@@ -465,6 +466,45 @@ int tfl_solveLinearSystemPCG(tfl_ctx* c, const tfl_tensor* p, const tfl_tensor* 
     case tfl::PcgResult::too_many_components: return fail(c, TFL_EINVAL, "%s", msg);
     default: return fail(c, TFL_EHIP, "%s", msg);
   }
+}
+
+int64_t tfl_pcg_batched_workspace_floats(int32_t B, int32_t Z, int32_t Y, int32_t X, const char* precondType) {
+  const int pc = precondType ? pcg_precond_of(precondType) : -1;
+  return B > 0 ? tfl::pcg_batched_workspace_floats(B, Z, Y, X, pc) : -1;
+}
+
+int tfl_solveLinearSystemPCGBatched(tfl_ctx* c, const tfl_tensor* p, const tfl_tensor* flags, const tfl_tensor* div, int is3D,
+                                    const char* precondType, float tol, int maxIter, float* workspace, int64_t workspace_floats,
+                                    float* residuals, int64_t* iterations) {
+  const char* who = "solveLinearSystemPCGBatched";
+  TRY(check_flags(c, who, flags));
+  TRY(check_scalar(c, who, "p", p, flags));
+  TRY(check_scalar(c, who, "div", div, flags));
+  if (!is3D && flags->Z != 1) return fail(c, TFL_EINVAL, "%s: d > 1 for a 2D domain", who);
+  const int pc = precondType ? pcg_precond_of(precondType) : -1;
+  if (pc < 0) return fail(c, TFL_EINVAL, "%s: precondType is not supported.", who);
+  if (pc == 1 || pc == 2)
+    return fail(c, TFL_EUNSUPPORTED, "%s: precondType '%s' does not batch (its wavefront sweeps wait for each other): 'mg' or 'none'", who,
+                precondType);
+  if (!workspace || ((uintptr_t)workspace & 7) != 0) return fail(c, TFL_EINVAL, "%s: workspace must be 8-byte aligned", who);
+  if (workspace_floats < tfl::pcg_batched_workspace_floats(flags->B, flags->Z, flags->Y, flags->X, pc))
+    return fail(c, TFL_EINVAL, "%s: workspace too small (tfl_pcg_batched_workspace_floats)", who);
+  if ((long long)flags->Z * flags->Y * flags->X >= (1ll << 31)) return fail(c, TFL_EINVAL, "%s: grid too large for 32-bit cell indices", who);
+  if (flags->B > 65535) return fail(c, TFL_EINVAL, "%s: more than 65535 batch items (the item is a launch's y index)", who);
+  char msg[256] = {0};
+  const tfl::PcgProblem q{is3D != 0, flags->B, flags->Z, flags->Y, flags->X, p->data, flags->data, div->data, pc, tol, maxIter, 0};
+  std::vector<long long> its(flags->B, 0);
+  long long total = 0;
+  switch (tfl::pcg_solve_batched(c->stream, q, workspace, residuals, its.data(), &total, msg, sizeof(msg))) {
+    case tfl::PcgResult::ok: break;
+    case tfl::PcgResult::bad_flags:
+    case tfl::PcgResult::nan_residual:
+    case tfl::PcgResult::too_many_components: return fail(c, TFL_EINVAL, "%s", msg);
+    default: return fail(c, TFL_EHIP, "%s", msg);
+  }
+  if (iterations) for (int b = 0; b < flags->B; b++) iterations[b] = its[b];
+  c->pcg_last_iterations = total;
+  return check_launch(c, who);
 }
 
 int64_t tfl_normalize_workspace_floats(int32_t Z, int32_t Y, int32_t X) { return tfl::npm_workspace_floats(Z, Y, X); }

@@ -29,7 +29,9 @@
 // component / begin / factor / build_wavefront_operands / build_levels / precondition / vcycle / iteration / run_chunks /
 // write_back -- and label_components is shared with normalize_pressure_mean. Results are named (PcgResult, tfl_host.hpp).
 // precondType = "mg" (pc == 3) is one multigrid V-cycle per application: its kernels are pcg_mg.hip, its scheme tfl_pcg_mg.hpp;
-// the wavefront machinery is not set up under it.
+// the wavefront machinery is not set up under it. The bodies of the k_cc_* / k_pcg_* kernels are __device__ functions (d_*):
+// pcg_batched.inc, included at the end of the unnamed namespace, runs them once more with the batch item in blockIdx.y
+// (solveLinearSystemPCGBatched, BatchedSolve).
 #include "tfl_device.hpp"
 #include "tfl_host.hpp"
 #include "tfl_pcg_mg.hpp"
@@ -60,7 +62,7 @@ __device__ __forceinline__ bool cell_fluid(const float* __restrict__ flags, int 
 __device__ __forceinline__ bool cell_obstacle(const float* __restrict__ flags, int o) { return (((int)flags[o]) & kObstacle) != 0; }
 
 // ---- connected components -------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_cc_init(Dom d, bool is3d, const float* __restrict__ flags, int* __restrict__ label,
+__device__ __forceinline__ void d_cc_init(Dom d, bool is3d, const float* __restrict__ flags, int* __restrict__ label,
                                                  int* __restrict__ border_fluid) {
   const int o = blockIdx.x * 256 + threadIdx.x;
   if (o >= d.sc) return;
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(256) void k_cc_init(Dom d, bool is3d, const float* 
 }
 
 // hook: a cell that sees a smaller label next door pulls its own label AND its current root down to it
-__global__ __launch_bounds__(256) void k_cc_hook(Dom d, bool is3d, int* __restrict__ label, int* __restrict__ changed) {
+__device__ __forceinline__ void d_cc_hook(Dom d, bool is3d, int* __restrict__ label, int* __restrict__ changed) {
   const int o = blockIdx.x * 256 + threadIdx.x;
   if (o >= d.sc) return;
   const int l = label[o];
@@ -94,7 +96,7 @@ __global__ __launch_bounds__(256) void k_cc_hook(Dom d, bool is3d, int* __restri
   }
 }
 // compress: point every cell at the root of its tree
-__global__ __launch_bounds__(256) void k_cc_compress(Dom d, int* __restrict__ label) {
+__device__ __forceinline__ void d_cc_compress(Dom d, int* __restrict__ label) {
   const int o = blockIdx.x * 256 + threadIdx.x;
   if (o >= d.sc) return;
   int l = label[o];
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(256) void k_cc_compress(Dom d, int* __restrict__ la
   label[o] = l;
 }
 // roots[0..count) = the cells that name a component; size_at[root] = cells in it
-__global__ __launch_bounds__(256) void k_cc_count(Dom d, const int* __restrict__ label, int* __restrict__ size_at,
+__device__ __forceinline__ void d_cc_count(Dom d, const int* __restrict__ label, int* __restrict__ size_at,
                                                   int* __restrict__ roots, int* __restrict__ count) {
   const int o = blockIdx.x * 256 + threadIdx.x;
   if (o >= d.sc) return;
@@ -140,7 +142,7 @@ __device__ __forceinline__ double reduce_partials(const double* __restrict__ par
 
 // ---- CG pieces ------------------------------------------------------------------------------------------
 // x = 0, r = rhs on the component (0 elsewhere), partial r.r
-__global__ __launch_bounds__(256) void k_pcg_setup(long long n, const int* __restrict__ label, int root,
+__device__ __forceinline__ void d_pcg_setup(long long n, const int* __restrict__ label, int root,
                                                    const float* __restrict__ div, float* __restrict__ x,
                                                    float* __restrict__ r, float* __restrict__ s, double* __restrict__ partials) {
   double acc = 0.0;
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(256) void k_pcg_setup(long long n, const int* __res
   }
   block_partial(acc, partials);
 }
-__global__ __launch_bounds__(256) void k_pcg_begin(PcgState* __restrict__ S, const double* __restrict__ partials, float tol,
+__device__ __forceinline__ void d_pcg_begin(PcgState* __restrict__ S, const double* __restrict__ partials, float tol,
                                                    int max_iter) {
   const double rr = reduce_partials(partials);
   if (threadIdx.x == 0) {
@@ -174,7 +176,7 @@ __device__ __forceinline__ void pcg_fold_residual(PcgState* __restrict__ S, doub
   if (rr != rr) { S->bad = 1; S->done = 1; }
 }
 // end of the previous iteration (if one is pending), then the loop condition and iter++
-__global__ __launch_bounds__(256) void k_pcg_top(PcgState* __restrict__ S, const double* __restrict__ p_rr, int test) {
+__device__ __forceinline__ void d_pcg_top(PcgState* __restrict__ S, const double* __restrict__ p_rr, int test) {
   if (S->done) return;
   const int pending = S->pending;
   double rr = 0.0;
@@ -186,7 +188,7 @@ __global__ __launch_bounds__(256) void k_pcg_top(PcgState* __restrict__ S, const
   S->iter++;
 }
 // partial a.b over the grid (vectors are 0 off the component)
-__global__ __launch_bounds__(256) void k_pcg_dot(const PcgState* __restrict__ S, long long n, const float* __restrict__ a,
+__device__ __forceinline__ void d_pcg_dot(const PcgState* __restrict__ S, long long n, const float* __restrict__ a,
                                                  const float* __restrict__ b, double* __restrict__ partials) {
   if (S->done) return;
   double acc = 0.0;
@@ -195,7 +197,7 @@ __global__ __launch_bounds__(256) void k_pcg_dot(const PcgState* __restrict__ S,
 }
 // beta (num = r.z from `p_num` when preconditioned, else r.r), then s = z + beta * s
 // (iteration 1: s = z; the reference's scal-then-axpy order: (beta*s) + z)
-__global__ __launch_bounds__(256) void k_pcg_dir(PcgState* __restrict__ S, long long n, const double* __restrict__ p_num, int precond,
+__device__ __forceinline__ void d_pcg_dir(PcgState* __restrict__ S, long long n, const double* __restrict__ p_num, int precond,
                                                  const float* __restrict__ z, float* __restrict__ s) {
   if (S->done) return;
   const bool first = S->first != 0;
@@ -209,7 +211,7 @@ __global__ __launch_bounds__(256) void k_pcg_dir(PcgState* __restrict__ S, long 
 }
 // w = A s on the component, partial s.w
 template <bool IS3D>
-__global__ __launch_bounds__(256) void k_pcg_apply(const PcgState* __restrict__ S, Dom d, const float* __restrict__ flags,
+__device__ __forceinline__ void d_pcg_apply(const PcgState* __restrict__ S, Dom d, const float* __restrict__ flags,
                                                    const int* __restrict__ label, int root, const float* __restrict__ s,
                                                    float* __restrict__ w, double* __restrict__ partials) {
   if (S->done) return;
@@ -246,7 +248,7 @@ __global__ __launch_bounds__(256) void k_pcg_apply(const PcgState* __restrict__ 
   block_partial(acc, partials);
 }
 // alpha = num / s.w (from `p_den`), then x += alpha s; r -= alpha w; partial r.r
-__global__ __launch_bounds__(256) void k_pcg_update(PcgState* __restrict__ S, long long n, const double* __restrict__ p_den,
+__device__ __forceinline__ void d_pcg_update(PcgState* __restrict__ S, long long n, const double* __restrict__ p_den,
                                                     const float* __restrict__ s, const float* __restrict__ w, float* __restrict__ x,
                                                     float* __restrict__ r, double* __restrict__ p_rr) {
   if (S->done) return;
@@ -264,20 +266,57 @@ __global__ __launch_bounds__(256) void k_pcg_update(PcgState* __restrict__ S, lo
   block_partial(acc, p_rr);
 }
 // sum of x over the component (for the mean), then p = x - mean on the component
-__global__ __launch_bounds__(256) void k_pcg_sum(long long n, const float* __restrict__ x, double* __restrict__ partials) {
+__device__ __forceinline__ void d_pcg_sum(long long n, const float* __restrict__ x, double* __restrict__ partials) {
   double acc = 0.0;
   for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < n; o += (long long)gridDim.x * 256) acc += (double)x[o];
   block_partial(acc, partials);
 }
-__global__ __launch_bounds__(256) void k_pcg_sum_end(PcgState* __restrict__ S, const double* __restrict__ partials) {
+__device__ __forceinline__ void d_pcg_sum_end(PcgState* __restrict__ S, const double* __restrict__ partials) {
   const double v = reduce_partials(partials);
   if (threadIdx.x == 0) S->sum_x = v;
 }
-__global__ __launch_bounds__(256) void k_pcg_write(const PcgState* __restrict__ S, long long n, const int* __restrict__ label,
+__device__ __forceinline__ void d_pcg_write(const PcgState* __restrict__ S, long long n, const int* __restrict__ label,
                                                    int root, int size, const float* __restrict__ x, float* __restrict__ p) {
   const float mean = (float)(S->sum_x / (double)size);
   for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < n; o += (long long)gridDim.x * 256)
     if (label[o] == root) p[o] = x[o] - mean;      // copyPressureFromSystem, generic/tfluids.cu:1216-1240
+}
+
+// The bodies above (d_*) as the kernels of ONE system. pcg_batched.inc launches the same bodies with the batch item in blockIdx.y.
+__global__ __launch_bounds__(256) void k_cc_init(Dom d, bool is3d, const float* __restrict__ flags, int* __restrict__ label,
+                                                 int* __restrict__ border_fluid) { d_cc_init(d, is3d, flags, label, border_fluid); }
+__global__ __launch_bounds__(256) void k_cc_hook(Dom d, bool is3d, int* __restrict__ label, int* __restrict__ changed) {
+  d_cc_hook(d, is3d, label, changed);
+}
+__global__ __launch_bounds__(256) void k_cc_compress(Dom d, int* __restrict__ label) { d_cc_compress(d, label); }
+__global__ __launch_bounds__(256) void k_cc_count(Dom d, const int* __restrict__ label, int* __restrict__ size_at,
+                                                  int* __restrict__ roots, int* __restrict__ count) { d_cc_count(d, label, size_at, roots, count); }
+__global__ __launch_bounds__(256) void k_pcg_setup(long long n, const int* __restrict__ label, int root,
+                                                   const float* __restrict__ div, float* __restrict__ x,
+                                                   float* __restrict__ r, float* __restrict__ s, double* __restrict__ partials) {
+  d_pcg_setup(n, label, root, div, x, r, s, partials);
+}
+__global__ __launch_bounds__(256) void k_pcg_begin(PcgState* __restrict__ S, const double* __restrict__ partials, float tol,
+                                                   int max_iter) { d_pcg_begin(S, partials, tol, max_iter); }
+__global__ __launch_bounds__(256) void k_pcg_top(PcgState* __restrict__ S, const double* __restrict__ p_rr, int test) { d_pcg_top(S, p_rr, test); }
+__global__ __launch_bounds__(256) void k_pcg_dot(const PcgState* __restrict__ S, long long n, const float* __restrict__ a,
+                                                 const float* __restrict__ b, double* __restrict__ partials) { d_pcg_dot(S, n, a, b, partials); }
+__global__ __launch_bounds__(256) void k_pcg_dir(PcgState* __restrict__ S, long long n, const double* __restrict__ p_num, int precond,
+                                                 const float* __restrict__ z, float* __restrict__ s) { d_pcg_dir(S, n, p_num, precond, z, s); }
+template <bool IS3D>
+__global__ __launch_bounds__(256) void k_pcg_apply(const PcgState* __restrict__ S, Dom d, const float* __restrict__ flags,
+                                                   const int* __restrict__ label, int root, const float* __restrict__ s,
+                                                   float* __restrict__ w, double* __restrict__ partials) {
+  d_pcg_apply<IS3D>(S, d, flags, label, root, s, w, partials);
+}
+__global__ __launch_bounds__(256) void k_pcg_update(PcgState* __restrict__ S, long long n, const double* __restrict__ p_den,
+                                                    const float* __restrict__ s, const float* __restrict__ w, float* __restrict__ x,
+                                                    float* __restrict__ r, double* __restrict__ p_rr) { d_pcg_update(S, n, p_den, s, w, x, r, p_rr); }
+__global__ __launch_bounds__(256) void k_pcg_sum(long long n, const float* __restrict__ x, double* __restrict__ partials) { d_pcg_sum(n, x, partials); }
+__global__ __launch_bounds__(256) void k_pcg_sum_end(PcgState* __restrict__ S, const double* __restrict__ partials) { d_pcg_sum_end(S, partials); }
+__global__ __launch_bounds__(256) void k_pcg_write(const PcgState* __restrict__ S, long long n, const int* __restrict__ label,
+                                                   int root, int size, const float* __restrict__ x, float* __restrict__ p) {
+  d_pcg_write(S, n, label, root, size, x, p);
 }
 
 // ---- ILU(0) / IC(0) on the 5/7-point pattern: wavefront sweeps over hyperplanes h = i + j + k -------------
@@ -1068,6 +1107,8 @@ void Solve::print_trace() {
               (t[dir * 2 * nblk + 2 * b2] - t0) * 0.01, (t[dir * 2 * nblk + 2 * b2 + 1] - t0) * 0.01);
 }
 
+#include "pcg_batched.inc"      // solveLinearSystemPCGBatched: the kernels above with the batch item in blockIdx.y, and its host code
+
 }  // namespace
 
 long long pcg_workspace_floats(int Z, int Y, int X) { return pcg_ws(Z, Y, X, wf_usable(Z > 1, Z, Y, X)).total; }
@@ -1087,6 +1128,29 @@ PcgResult pcg_solve(hipStream_t st, const PcgProblem& q, float* workspace, float
   v.print_trace();
   if (residual) *residual = v.max_res;
   if (iterations) *iterations = v.iterations;
+  return PcgResult::ok;
+}
+
+long long pcg_batched_workspace_floats(int B, int Z, int Y, int X, int precond) {
+  return (precond == 0 || precond == 3) ? pcg_batched_ws(B, Z, Y, X, precond == 3, Z > 1).total : -1;
+}
+
+// Every item's systems in the same launches, round by round (pcg_batched.inc). Anything but PcgResult::ok comes with `msg` filled.
+PcgResult pcg_solve_batched(hipStream_t st, const PcgProblem& q, float* workspace, float* residuals, long long* iterations,
+                            long long* total, char* msg, size_t msg_len) {
+  BatchedSolve v(st, q, workspace, msg, msg_len);
+  const Report& er = v.er;
+  HIP_TRY(hipMemsetAsync(q.p, 0, sizeof(float) * (size_t)q.B * v.n, st), "memset p");   // :1341
+  PCG_TRY(v.label_items());
+  PCG_TRY(v.read_components());
+  for (int c = 0; c < v.maxc; c++) PCG_TRY(v.round(c));
+  long long sum = 0;
+  for (int b = 0; b < q.B; b++) {
+    if (residuals) residuals[b] = v.max_res[b];
+    if (iterations) iterations[b] = v.iters[b];
+    sum += v.iters[b];
+  }
+  if (total) *total = sum;
   return PcgResult::ok;
 }
 

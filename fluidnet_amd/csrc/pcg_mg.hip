@@ -168,7 +168,7 @@ __device__ __forceinline__ void mg_galerkin(const MgLv& F, const MgLv& C, int t,
 // level 0 from the flags and the component's label: diag as k_pcg_apply forms it (0 off the component)
 // *open = 1 when a cell of the component has an empty neighbour (every thread that sees one stores the same word)
 template <bool IS3D>
-__global__ __launch_bounds__(256) void k_mg_level0(Dom d, const float* __restrict__ flags, const int* __restrict__ label, int root, MgLv L,
+__device__ __forceinline__ void d_mg_level0(Dom d, const float* __restrict__ flags, const int* __restrict__ label, int root, MgLv L,
                                                    int* __restrict__ open) {
   for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < d.sc; o += (long long)gridDim.x * 256) {
     const bool in = label[o] == root;       // (a component's cell is never on the border: all six neighbours exist)
@@ -193,20 +193,57 @@ __global__ __launch_bounds__(256) void k_mg_level0(Dom d, const float* __restric
   }
 }
 template <bool IS3D>
+__global__ __launch_bounds__(256) void k_mg_level0(Dom d, const float* __restrict__ flags, const int* __restrict__ label, int root, MgLv L,
+                                                   int* __restrict__ open) { d_mg_level0<IS3D>(d, flags, label, root, L, open); }
+template <bool IS3D>
 __global__ __launch_bounds__(256) void k_mg_galerkin(MgLv F, MgLv C) {
   mg_galerkin<IS3D>(F, C, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
 
+// ---- the batch view (solveLinearSystemPCGBatched) ---------------------------------------------------------------------------
+// The kernels below (k_*_b) run the same device functions with the batch item in blockIdx.y: item b's arrays lie b * stride floats
+// behind item 0's, and what the host decides per component above (is there a system, is it preconditioned, is it closed) is
+// read from the item's record. Level 0's right-hand side is the idle w (r0) when the component is closed, else the CG's r.
+__device__ __forceinline__ MgLv mg_at(const MgLv& L, long long off, float* r0 = nullptr) {
+  return MgLv{L.g, L.n, L.diag + off, L.invd + off, L.cx + off, L.cy + off, L.cz + off, r0 ? r0 : L.r + off, L.za + off, L.zb + off};
+}
+struct MgItem { bool run; long long off; const PcgState* S; int size; bool closed; };
+// set-up kernels run for every mg system of the round; per-application kernels only until its CG is done
+__device__ __forceinline__ MgItem mg_item(const PcgBatch& bt, bool setup) {
+  const int b = blockIdx.y;
+  const PcgItemRec& rc = bt.rec[b];
+  MgItem it;
+  it.off = (long long)b * bt.stride; it.S = pcg_state_of(bt, b); it.size = rc.size; it.closed = rc.open == 0;
+  it.run = rc.active && rc.pc == 3 && (setup || !it.S->done);
+  return it;
+}
+// the level-0 right-hand side of item `it`: w0 is item 0's w, null for any other level
+__device__ __forceinline__ float* mg_rhs0(const MgItem& it, float* w0) { return (w0 && it.closed) ? w0 + it.off : nullptr; }
+
+template <bool IS3D>
+__global__ __launch_bounds__(256) void k_mg_level0_b(PcgBatch bt, Dom d, const float* __restrict__ flags, const int* __restrict__ label, MgLv L) {
+  const MgItem it = mg_item(bt, true);
+  if (!it.run) return;
+  PcgItemRec& rc = bt.rec[blockIdx.y];
+  d_mg_level0<IS3D>(d, flags + (long long)blockIdx.y * d.sc, label + it.off, rc.root, mg_at(L, it.off), &rc.open);
+}
+template <bool IS3D>
+__global__ __launch_bounds__(256) void k_mg_galerkin_b(PcgBatch bt, MgLv F, MgLv C) {
+  const MgItem it = mg_item(bt, true);
+  if (!it.run) return;
+  mg_galerkin<IS3D>(mg_at(F, it.off), mg_at(C, it.off), blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
+}
+
 // ---- one application ------------------------------------------------------------------------------------------------------
 // the partial sums of r over the grid (r is 0 off the component)
-__global__ __launch_bounds__(256) void k_mg_rsum(const PcgState* __restrict__ S, int n, const float* __restrict__ r, double* __restrict__ partials) {
+__device__ __forceinline__ void d_mg_rsum(const PcgState* __restrict__ S, int n, const float* __restrict__ r, double* __restrict__ partials) {
   if (S->done) return;
   double acc = 0.0;
   for (int o = blockIdx.x * 256 + threadIdx.x; o < n; o += gridDim.x * 256) acc += (double)r[o];
   mg_block_partial(acc, partials);
 }
 // the first sweep of level 0 of a closed component: the cycle's right-hand side L.r = r - mean of r, and z = omega L.r / diag
-__global__ __launch_bounds__(256) void k_mg_first0(const PcgState* __restrict__ S, MgLv L, const float* __restrict__ r,
+__device__ __forceinline__ void d_mg_first0(const PcgState* __restrict__ S, MgLv L, const float* __restrict__ r,
                                                    const double* __restrict__ partials, int size, float* __restrict__ zout) {
   if (S->done) return;
   const double sum = mg_reduce_partials(partials);
@@ -217,6 +254,13 @@ __global__ __launch_bounds__(256) void k_mg_first0(const PcgState* __restrict__ 
     L.r[o] = v;
     zout[o] = (kMgOmega * invd) * v;
   }
+}
+__global__ __launch_bounds__(256) void k_mg_rsum(const PcgState* __restrict__ S, int n, const float* __restrict__ r, double* __restrict__ partials) {
+  d_mg_rsum(S, n, r, partials);
+}
+__global__ __launch_bounds__(256) void k_mg_first0(const PcgState* __restrict__ S, MgLv L, const float* __restrict__ r,
+                                                   const double* __restrict__ partials, int size, float* __restrict__ zout) {
+  d_mg_first0(S, L, r, partials, size, zout);
 }
 __global__ __launch_bounds__(256) void k_mg_first(const PcgState* __restrict__ S, MgLv L, float* __restrict__ zout) {
   if (S->done) return;
@@ -249,24 +293,68 @@ __device__ __forceinline__ void mg_block_smooth_from_zero(const MgLv& L, int swe
 }
 // the levels first .. count - 1 of the cycle in one block: r of level `first` from level first - 1, down, the coarsest level, up;
 // z of level `first` ends in its zb. Every operation reads what the one before wrote to global memory: a barrier between them.
+// The hierarchy is h's, `off` floats on (the batch item); r0: level 0's right-hand side when it is not h's (a closed item).
 template <bool IS3D>
-__global__ __launch_bounds__(kMgBlockThreads) void k_mg_coarse(const PcgState* __restrict__ S, MgDev h, int first) {
-  if (S->done) return;
+__device__ __forceinline__ void mg_coarse(const MgDev& h, int first, long long off, float* r0) {
   const int last = h.count - 1;
+  auto lv = [&](int l) { return mg_at(h.lv[l], off, l == 0 ? r0 : nullptr); };
   for (int l = first; l <= last; l++) {
-    mg_restrict<IS3D>(h.lv[l - 1], h.lv[l], threadIdx.x, kMgBlockThreads);
+    const MgLv L = lv(l);
+    mg_restrict<IS3D>(lv(l - 1), L, threadIdx.x, kMgBlockThreads);
     __syncthreads();
-    mg_block_smooth_from_zero<IS3D>(h.lv[l], l == last ? kMgNuCoarse : kMgNu);
+    mg_block_smooth_from_zero<IS3D>(L, l == last ? kMgNuCoarse : kMgNu);
   }
   for (int l = last - 1; l >= first; l--) {
-    const MgLv& L = h.lv[l];
-    mg_sweep<IS3D, true>(L, L.zb, L.za, h.lv[l + 1].zb, h.lv[l + 1].g, threadIdx.x, kMgBlockThreads);
+    const MgLv L = lv(l);
+    mg_sweep<IS3D, true>(L, L.zb, L.za, h.lv[l + 1].zb + off, h.lv[l + 1].g, threadIdx.x, kMgBlockThreads);
     __syncthreads();
     for (int s = 1; s < kMgNu; s++) {
       mg_sweep<IS3D, false>(L, (s & 1) ? L.za : L.zb, (s & 1) ? L.zb : L.za, nullptr, L.g, threadIdx.x, kMgBlockThreads);
       __syncthreads();
     }
   }
+}
+template <bool IS3D>
+__global__ __launch_bounds__(kMgBlockThreads) void k_mg_coarse(const PcgState* __restrict__ S, MgDev h, int first) {
+  if (S->done) return;
+  mg_coarse<IS3D>(h, first, 0, nullptr);
+}
+
+// the batch forms: one item per blockIdx.y. w0: item 0's w on level 0, null on the other levels (mg_rhs0)
+__global__ __launch_bounds__(256) void k_mg_rsum_b(PcgBatch bt, int n, const float* __restrict__ r, double* __restrict__ partials) {
+  const MgItem it = mg_item(bt, false);
+  if (!it.run || !it.closed) return;
+  d_mg_rsum(it.S, n, r + it.off, reinterpret_cast<double*>(reinterpret_cast<float*>(partials) + it.off));
+}
+// the first sweep of a level; on level 0 of a closed item the one that forms the right-hand side
+__global__ __launch_bounds__(256) void k_mg_first_b(PcgBatch bt, MgLv L0, float* w0, const float* __restrict__ r,
+                                                    const double* __restrict__ partials, float* __restrict__ zout) {
+  const MgItem it = mg_item(bt, false);
+  if (!it.run) return;
+  float* r0 = mg_rhs0(it, w0);
+  const MgLv L = mg_at(L0, it.off, r0);
+  if (r0) d_mg_first0(it.S, L, r + it.off, reinterpret_cast<const double*>(reinterpret_cast<const float*>(partials) + it.off), it.size, zout + it.off);
+  else mg_first(L, zout + it.off, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
+}
+template <bool IS3D, bool PROLONG>
+__global__ __launch_bounds__(256) void k_mg_sweep_b(PcgBatch bt, MgLv L, float* w0, const float* __restrict__ zin,
+                                                    float* __restrict__ zout, const float* __restrict__ zc, MgLevelGeom cg) {
+  const MgItem it = mg_item(bt, false);
+  if (!it.run) return;
+  mg_sweep<IS3D, PROLONG>(mg_at(L, it.off, mg_rhs0(it, w0)), zin + it.off, zout + it.off, PROLONG ? zc + it.off : nullptr, cg,
+                          blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
+}
+template <bool IS3D>
+__global__ __launch_bounds__(256) void k_mg_restrict_b(PcgBatch bt, MgLv F, float* w0, MgLv C) {
+  const MgItem it = mg_item(bt, false);
+  if (!it.run) return;
+  mg_restrict<IS3D>(mg_at(F, it.off, mg_rhs0(it, w0)), mg_at(C, it.off), blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
+}
+template <bool IS3D>
+__global__ __launch_bounds__(kMgBlockThreads) void k_mg_coarse_b(PcgBatch bt, MgDev h, float* w0, int first) {
+  const MgItem it = mg_item(bt, false);
+  if (!it.run) return;
+  mg_coarse<IS3D>(h, first, it.off, mg_rhs0(it, w0));
 }
 
 inline int mg_grid(long long n) { return (int)((n + 255) / 256); }
@@ -313,7 +401,51 @@ void vcycle(hipStream_t st, const MgDev& h, const PcgState* S, const MgRhs* rhs)
   }
 }
 
+// ---- the same schedule for a batch: what the host decides above per component (rhs or not) the kernels read per item ---------
+template <bool IS3D>
+void build_levels_b(hipStream_t st, int B, const PcgBatch& bt, const Dom& d, const MgDev& h, const float* flags, const int* label) {
+  k_mg_level0_b<IS3D><<<dim3(mg_grid(d.sc), B), 256, 0, st>>>(bt, d, flags, label, h.lv[0]);
+  for (int l = 1; l < h.count; l++) k_mg_galerkin_b<IS3D><<<dim3(mg_grid(h.lv[l].n), B), 256, 0, st>>>(bt, h.lv[l - 1], h.lv[l]);
+}
+template <bool IS3D>
+void vcycle_b(hipStream_t st, int B, const PcgBatch& bt, const MgDev& h, float* w, const float* r, double* partials) {
+  auto grid = [B](const MgLv& L) { return dim3(mg_grid(L.n), B); };
+  auto w0 = [w](int l) { return l == 0 ? w : nullptr; };
+  k_mg_rsum_b<<<dim3(kRedBlocks, B), 256, 0, st>>>(bt, h.lv[0].n, r, partials);
+  const int last = h.count - 1, fb = h.first_block_level;
+  const int wide = std::min(fb, h.count);
+  for (int l = 0; l < wide; l++) {
+    const MgLv& L = h.lv[l];
+    if (l > 0) k_mg_restrict_b<IS3D><<<grid(L), 256, 0, st>>>(bt, h.lv[l - 1], w0(l - 1), L);
+    const int sweeps = l == last ? kMgNuCoarse : kMgNu;
+    float* a = (sweeps & 1) ? L.zb : L.za;
+    float* b = (sweeps & 1) ? L.za : L.zb;
+    k_mg_first_b<<<grid(L), 256, 0, st>>>(bt, L, w0(l), r, partials, a);
+    for (int s = 1; s < sweeps; s++) {
+      k_mg_sweep_b<IS3D, false><<<grid(L), 256, 0, st>>>(bt, L, w0(l), a, b, nullptr, L.g);
+      std::swap(a, b);
+    }
+  }
+  if (fb < h.count) k_mg_coarse_b<IS3D><<<dim3(1, B), kMgBlockThreads, 0, st>>>(bt, h, w, fb);
+  for (int l = std::min(wide, last) - 1; l >= 0; l--) {
+    const MgLv& L = h.lv[l];
+    k_mg_sweep_b<IS3D, true><<<grid(L), 256, 0, st>>>(bt, L, w0(l), L.zb, L.za, h.lv[l + 1].zb, h.lv[l + 1].g);
+    for (int s = 1; s < kMgNu; s++)
+      k_mg_sweep_b<IS3D, false><<<grid(L), 256, 0, st>>>(bt, L, w0(l), (s & 1) ? L.za : L.zb, (s & 1) ? L.zb : L.za, nullptr, L.g);
+  }
+}
+
 }  // namespace
+
+void mg_build_levels_batched(hipStream_t st, bool is3d, int B, const PcgBatch& bt, const Dom& d, const MgDev& h, const float* flags,
+                             const int* label) {
+  if (is3d) build_levels_b<true>(st, B, bt, d, h, flags, label);
+  else build_levels_b<false>(st, B, bt, d, h, flags, label);
+}
+void mg_vcycle_batched(hipStream_t st, bool is3d, int B, const PcgBatch& bt, const MgDev& h, float* w, const float* r, double* partials) {
+  if (is3d) vcycle_b<true>(st, B, bt, h, w, r, partials);
+  else vcycle_b<false>(st, B, bt, h, w, r, partials);
+}
 
 void mg_build_levels(hipStream_t st, const Dom& d, bool is3d, const MgDev& h, const float* flags, const int* label, int root, int* open) {
   if (is3d) build_levels<true>(st, d, h, flags, label, root, open);

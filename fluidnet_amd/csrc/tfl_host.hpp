@@ -269,6 +269,17 @@ struct MgDev;
 struct PcgState;
 void mg_build_levels(hipStream_t st, const Dom& d, bool is3d, const MgDev& h, const float* flags, const int* label, int root, int* open);
 void mg_vcycle(hipStream_t st, bool is3d, const MgDev& h, const PcgState* S, bool closed, const float* r, double* partials, int size);
+// The same for a batch (pcg_batched.inc): h, label, w, r and partials are item 0's, item b's lie b * bt.stride floats on; flags is
+// the caller's tensor. Root, size, "is there an mg system" and "closed" come from the items' records (tfl_pcg_ws.hpp), on the device.
+struct PcgBatch;
+void mg_build_levels_batched(hipStream_t st, bool is3d, int B, const PcgBatch& bt, const Dom& d, const MgDev& h, const float* flags,
+                             const int* label);
+void mg_vcycle_batched(hipStream_t st, bool is3d, int B, const PcgBatch& bt, const MgDev& h, float* w, const float* r, double* partials);
+// solveLinearSystemPCGBatched: every item's systems advance in the same launches; item b gets the bits pcg_solve gives it alone.
+// q.precond is 0 or 3, q.verbose is not read. residuals / iterations: B entries each, may be null. total: the sum of iterations.
+long long pcg_batched_workspace_floats(int B, int Z, int Y, int X, int precond);     // -1: not 0 / 3
+PcgResult pcg_solve_batched(hipStream_t st, const PcgProblem& q, float* workspace, float* residuals, long long* iterations,
+                            long long* total, char* msg, size_t msg_len);
 
 long long npm_workspace_floats(int Z, int Y, int X);     // the total of npm_ws
 PcgResult normalize_pressure_mean(hipStream_t st, bool is3d, int B, int Z, int Y, int X, float* p, const float* flags,

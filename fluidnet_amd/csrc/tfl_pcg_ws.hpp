@@ -5,6 +5,8 @@
 // share: the solver's device state and the geometry of the pipelined wavefront sweeps with their compile-time shape.
 // Held by a stand-alone host program (tests/pcg_ws_host.cpp: every offset against the expression pcg_solve used to write out,
 // the totals, disjointness, alignment, the cleared span and the guard pairs). Plain C++ without a HIP header.
+// pcg_batched_ws is the table of solveLinearSystemPCGBatched: B of pcg_ws's blocks and the per-item tables (held by
+// tests/pcg_batched_ws_host.cpp).
 #pragma once
 
 #include <cstdint>
@@ -143,6 +145,56 @@ inline PcgWs pcg_ws(int Z, int Y, int X, bool wavefronts, bool mg = false, bool 
 // the run-time round-up of the wavefront block: floats to add to every wf_* offset so that it sits on 16 bytes in `workspace`
 inline long long pcg_wf_pad(const float* workspace, const PcgWs& t) {
   return (4 - ((((uintptr_t)workspace >> 2) + (uintptr_t)t.wf_cc.off) & 3)) & 3;
+}
+
+// ---- solveLinearSystemPCGBatched (pcg_batched.inc) -----------------------------------------------------------------------------
+// What a batched kernel reads of the system its item is on in this round: written on the device (k_pcgb_round, k_mg_level0_b),
+// never by the host.
+struct PcgItemRec {
+  int root, size;      // the component at hand
+  int pc;              // its preconditioner: 0 none (also: fewer than 5 cells), 3 mg
+  int open;            // mg set-up: a cell of the component has an empty neighbour (0: closed, the cycle runs on r minus its mean)
+  int active;          // 0: the item has no system in this round (no such component, or one of size 1)
+  int pad[3];
+};
+constexpr long long kPcgRecFloats = sizeof(PcgItemRec) / sizeof(float);
+constexpr int kPcgCcWords = 4;     // per item: [0] changed, [1] count, [2] border fluid, [3] spare
+// The batch as a kernel sees it: item b's record, its state slot, and its arrays b * stride floats behind item 0's.
+struct PcgBatch {
+  PcgItemRec* rec;
+  PcgState* S;         // slot 0; the slots are kPcgStateFloats apart
+  long long stride;
+};
+TFL_MG_HD inline PcgState* pcg_state_of(const PcgBatch& bt, int b) {
+  return reinterpret_cast<PcgState*>(reinterpret_cast<float*>(bt.S) + (long long)b * kPcgStateFloats);
+}
+
+// B copies of the per-item block (pcg_ws without wavefront regions; its state slot and its counters stay idle) at one even stride,
+// then tables of B: the solver states (one read per chunk), the records, the labelling words (one read per round) and the
+// components (root, size) in scan order, kMaxComponents pairs per item.
+struct PcgBatchedWs {
+  PcgWs item;          // offsets inside an item's block
+  long long stride;    // floats from one item's block to the next: even, so every fp64 region stays on 8 bytes
+  WsRegion items;
+  WsRegion states;     // B slots of kPcgStateFloats
+  WsRegion recs;       // B PcgItemRec
+  WsRegion cc;         // B * kPcgCcWords int32
+  WsRegion comps;      // B * kMaxComponents * 2 int32
+  long long total;
+};
+inline PcgBatchedWs pcg_batched_ws(int B, int Z, int Y, int X, bool mg, bool is3d) {
+  PcgBatchedWs t{};
+  t.item = pcg_ws(Z, Y, X, false, mg, is3d);
+  t.stride = (t.item.total + 1) & ~1ll;
+  long long at = 0;
+  auto take = [&at](long long floats) { const WsRegion r{at, floats}; at += floats; return r; };
+  t.items = take(B * t.stride);
+  t.states = take(B * kPcgStateFloats);
+  t.recs = take(B * kPcgRecFloats);
+  t.cc = take((long long)B * kPcgCcWords);
+  t.comps = take((long long)B * kMaxComponents * 2);
+  t.total = at;
+  return t;
 }
 
 // ---- normalizePressureMean --------------------------------------------------------------------------------------------------

@@ -101,6 +101,10 @@ int64_t tfl_pcg_last_iterations(tfl_ctx* ctx);
 int tfl_solveLinearSystemPCG(tfl_ctx* ctx, const tfl_tensor* p, const tfl_tensor* flags, const tfl_tensor* div,
                              int is3D, const char* precondType, float tol, int maxIter, int verbose,
                              float* workspace, int64_t workspace_floats, float* residual);
+int64_t tfl_pcg_batched_workspace_floats(int32_t B, int32_t Z, int32_t Y, int32_t X, const char* precondType);
+int tfl_solveLinearSystemPCGBatched(tfl_ctx* ctx, const tfl_tensor* p, const tfl_tensor* flags, const tfl_tensor* div,
+                                    int is3D, const char* precondType, float tol, int maxIter, float* workspace,
+                                    int64_t workspace_floats, float* residuals, int64_t* iterations);
 int64_t tfl_normalize_workspace_floats(int32_t Z, int32_t Y, int32_t X);
 int tfl_normalizePressureMean(tfl_ctx* ctx, const tfl_tensor* p, const tfl_tensor* flags, int is3D, float* workspace,
                               int64_t workspace_floats);

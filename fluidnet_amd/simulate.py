@@ -308,7 +308,11 @@ def calcPUTargets(conf, mconf, batch, model=None):
         div = torch.empty_like(flags)
         batch["div"] = div
     tfluids.velocityDivergenceForward(UDiv, flags, div)
-    if source == "pcg":
+    if source == "pcg" and mconf.get("pcgBatched"):
+        # every batch item in the same launches (not in the reference): 'mg' unless mconf.pcgPrecond says 'none'
+        tfluids.solveLinearSystemPCGBatched(pTarget, flags, div, is3D, 1e-4, mconf.get("maxIter") or 100,
+                                            mconf.get("pcgPrecond") or "mg")
+    elif source == "pcg":
         tfluids.solveLinearSystemPCG(pTarget, flags, div, is3D, 1e-4, mconf.get("maxIter") or 100, "ic0")
     elif source == "jacobi":
         tfluids.solveLinearSystemJacobi(pTarget, flags, div, is3D, 0, mconf.get("maxIter") or 50, residual=False)

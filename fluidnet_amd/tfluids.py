@@ -8,6 +8,7 @@ stream, like the reference's CUDA path. The work is done by libtfluids_hip.so th
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -483,6 +484,37 @@ def solveLinearSystemPCG(p, flags, div, is3D, tol=None, maxIter=None, precondTyp
                                                  str(precondType).encode(), float(tol), int(maxIter), int(verbose),
                                                  ctypes.c_void_p(ws.data_ptr()), nws, ctypes.byref(res)))
     return res.value
+
+
+def solveLinearSystemPCGBatched(p, flags, div, is3D, tol=None, maxIter=None, precondType="mg"):
+    """solveLinearSystemPCG with every batch item advancing in the same launches (csrc/pcg_batched.inc; not in the reference):
+    item b gets, bit for bit, what solveLinearSystemPCG gives it alone. precondType 'mg' (default) | 'none'; 'ic0' / 'ilu0'
+    do not batch and are refused. tol default 1e-6, maxIter default 1000.
+    Returns (residuals, iterations): numpy arrays of length B, the final residual (-inf: nothing to solve) and the CG
+    iterations of every item (one host sync); pcgLastIterations() has their sum."""
+    _check(p.dim() == 5 and flags.dim() == 5 and div.dim() == 5, "Dimension mismatch")
+    _check(flags.size(1) == 1, "flags is not scalar")
+    bsz, _, d, h, w = flags.shape
+    _check(p.shape == flags.shape, "size mismatch")
+    _check(div.shape == flags.shape, "size mismatch")
+    if not is3D:
+        _check(d == 1, "d > 1 for a 2D domain")
+    precondType = precondType or "mg"
+    tol = 1e-6 if tol is None else tol
+    maxIter = 1000 if maxIter is None else maxIter
+    _check(p.is_contiguous() and flags.is_contiguous() and div.is_contiguous(), "Input is not contiguous")
+    lib, ctx = _context(p)
+    nws = int(lib.tfl_pcg_batched_workspace_floats(bsz, d, h, w, str(precondType).encode()))
+    if nws < 0:         # not a preconditioner that batches: the library refuses the call below by name
+        nws = int(lib.tfl_pcg_batched_workspace_floats(bsz, d, h, w, b"none"))
+    ws = getTempStorage(p, [(nws,)])[0]
+    res = np.zeros(bsz, dtype=np.float32)
+    its = np.zeros(bsz, dtype=np.int64)
+    _call(lib, ctx, lib.tfl_solveLinearSystemPCGBatched(ctx, _tt(p), _tt(flags), _tt(div), int(bool(is3D)),
+                                                        str(precondType).encode(), float(tol), int(maxIter),
+                                                        ctypes.c_void_p(ws.data_ptr()), nws,
+                                                        res.ctypes.data_as(ctypes.c_void_p), its.ctypes.data_as(ctypes.c_void_p)))
+    return res, its
 
 
 def pcgLastIterations(like):

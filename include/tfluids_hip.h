@@ -276,6 +276,22 @@ int tfl_solveLinearSystemPCG(tfl_ctx* ctx, const tfl_tensor* p, const tfl_tensor
                              int is3D, const char* precondType, float tol, int maxIter, int verbose,
                              float* workspace, int64_t workspace_floats, float* residual);
 
+/* tfl_solveLinearSystemPCG with every batch element advancing in the SAME launches (not in the reference): the c-th connected
+ * component of every element is solved at once, for c = 0 .. the largest component count - 1, so a CG iteration of the batch
+ * is as many launches as a CG iteration of one element and the host waits for the stream once per chunk of iterations, not
+ * once per element and component. For every element b, p[b], residuals[b] and iterations[b] are bit for bit what
+ * tfl_solveLinearSystemPCG gives for that element alone with the same precondType, tol and maxIter (residuals[b] = -inf where
+ * nothing was solved); tfl_pcg_last_iterations afterwards is the sum of iterations[]. residuals / iterations: host arrays
+ * of B entries, either may be NULL. precondType: "mg" | "none"; "ilu0" and "ic0" are refused with TFL_EUNSUPPORTED (their
+ * wavefront sweeps wait for each other and do not batch), any other name with TFL_EINVAL. workspace:
+ * tfl_pcg_batched_workspace_floats(B, Z, Y, X, precondType) floats, 8-byte aligned (-1 for any name but "mg" | "none").
+ * p is zeroed first; a fluid cell on the border of any element is refused with TFL_EINVAL before any CG launch (the message
+ * names the first such element, counted from 0). Synchronises the stream. */
+int64_t tfl_pcg_batched_workspace_floats(int32_t B, int32_t Z, int32_t Y, int32_t X, const char* precondType);
+int tfl_solveLinearSystemPCGBatched(tfl_ctx* ctx, const tfl_tensor* p, const tfl_tensor* flags, const tfl_tensor* div,
+                                    int is3D, const char* precondType, float tol, int maxIter, float* workspace,
+                                    int64_t workspace_floats, float* residuals, int64_t* iterations);
+
 /* init.lua:747-764 `tfluids.normalizePressureMean(p, flags, is3D)` -> tfluids_<Real>Main_normalizePressureMean,
  * generic/tfluids.cc:845-925 (CPU only in the reference: CUDA tensors are copied to the host and back): subtracts
  * from p, per batch element, the mean of p over each connected component of fluid cells (non-fluid cells untouched).

@@ -9,7 +9,11 @@ falling through, the write-back; 'none' shows what of it is not the precondition
 are the launch sequence of the host code (pcg.hip Solve::iteration / precondition, pcg_mg.hip vcycle) worked out for the grid, with
 the shape constants read from tfl_pcg_mg.hpp and tfl_pcg_ws.hpp: per iteration 5 launches of CG itself (4 without a
 preconditioner), per chunk one more, per component solve 2 (set-up) + 3 (write-back), for a single closed component.
-usage: python tools/pcg_bench.py [--out FILE.md] [--grids 2d128,2d256,3d64,3d128]"""
+--batched B[,B...] measures solveLinearSystemPCGBatched instead (profiles/pcg_batched.md keeps that table): the closed scene of
+the generator's plans 0 .. B - 1 as one batch; per repetition, in turn, the batched 'mg' solve, one call of solveLinearSystemPCG
+with 'mg' and one with 'ic0' on the same batch (that entry solves the items one after the other), each synchronised; then, at
+the largest B, one calcPUTargets call (trainTargetSource = 'pcg', tol 1e-4, maxIter 100) with and without mconf.pcgBatched.
+usage: python tools/pcg_bench.py [--out FILE.md] [--grids 2d128,2d256,3d64,3d128] [--batched 1,4,16]"""
 import argparse
 import json
 import os
@@ -77,9 +81,9 @@ def sweep_launches(dims, is3D):
     return 2 + 2 * -(-nb // max(1, WF_MAX_BLOCKS // ns)), planes + 1
 
 
-def scene(is3D, dims, open_face):
+def scene(is3D, dims, open_face, run=0, with_velocity=False):
     g = datagen.default_gconf(is3D, dims)
-    plan = datagen.plan_run(g, SEED, 0)
+    plan = datagen.plan_run(g, SEED, run)
     mconf = datagen.mconf_of(plan)
     batch = datagen.init_state(plan, DEV)
     for _ in range(8):
@@ -94,6 +98,8 @@ def scene(is3D, dims, open_face):
     tfluids.setWallBcsForward(U, flags)
     div = torch.empty_like(batch["pDiv"])
     tfluids.velocityDivergenceForward(U, flags, div)
+    if with_velocity:
+        return flags, div, batch["UDiv"].clone()
     return flags, div
 
 
@@ -128,13 +134,97 @@ def measure(key):
     return rows
 
 
+def _timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def measure_batched(key, sizes):
+    """rows of the batched table for one grid: per B the three solves in turn, REPS times after a warm round; then calcPUTargets"""
+    from fluidnet_amd.simulate import calcPUTargets
+    is3D, dims = GRIDS[key]
+    items = [scene(is3D, dims, False, run=b, with_velocity=True) for b in range(max(sizes))]
+    rows = []
+    for B in sizes:
+        flags, div = (torch.cat([it[i] for it in items[:B]]).contiguous() for i in (0, 1))
+        pb, pm, pi = (torch.zeros_like(div) for _ in range(3))
+        forms = (("batched mg", lambda: tfluids.solveLinearSystemPCGBatched(pb, flags, div, is3D, TOL, MAX_ITER, "mg")[1].sum()),
+                 ("sequential mg", lambda: (tfluids.solveLinearSystemPCG(pm, flags, div, is3D, TOL, MAX_ITER, "mg"), tfluids.pcgLastIterations(pm))[1]),
+                 ("sequential ic0", lambda: (tfluids.solveLinearSystemPCG(pi, flags, div, is3D, TOL, MAX_ITER, "ic0"), tfluids.pcgLastIterations(pi))[1]))
+        ts, its = {n: [] for n, _ in forms}, {}
+        for rep in range(REPS + 1):                       # the first round warms every form up
+            for n, fn in forms:
+                t, its[n] = _timed(fn)
+                if rep:
+                    ts[n].append(t)
+        row = dict(grid=key, B=B, same_bits=bool(torch.equal(pb, pm)), iterations={n: int(v) for n, v in its.items()},
+                   ms={n: float(np.median(v)) for n, v in ts.items()}, ms_min={n: min(v) for n, v in ts.items()},
+                   ms_max={n: max(v) for n, v in ts.items()})
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    B = max(sizes)
+    flags = torch.cat([it[0] for it in items[:B]]).contiguous()
+    U0 = torch.cat([it[2] for it in items[:B]]).contiguous()
+    base = dict(trainTargetSource="pcg", maxIter=100)
+    batch = dict(flags=flags, UDiv=U0.clone(), pTarget=torch.zeros_like(flags), UTarget=torch.zeros_like(U0))
+    ts = {"pcgBatched": [], "as it is": []}
+    for rep in range(REPS + 1):
+        for n, mconf in (("pcgBatched", dict(base, pcgBatched=True)), ("as it is", base)):
+            batch["UDiv"].copy_(U0)
+            t, _ = _timed(lambda: calcPUTargets(None, mconf, batch))
+            if rep:
+                ts[n].append(t)
+    row = dict(grid=key, B=B, calcPUTargets_ms={n: float(np.median(v)) for n, v in ts.items()},
+               calcPUTargets_ms_min={n: min(v) for n, v in ts.items()}, calcPUTargets_ms_max={n: max(v) for n, v in ts.items()})
+    rows.append(row)
+    print(json.dumps(row), flush=True)
+    return rows
+
+
+def batched_table(rows):
+    lines = ["%s, HIP %s. tol %g, maxIter %d (calcPUTargets: maxIter 100); ms: median of %d after a warm round, the forms in turn "
+             "(min .. max). Iterations: summed over the items." % (torch.cuda.get_device_name(0), torch.version.hip, TOL, MAX_ITER, REPS), "",
+             "| grid | B | batched mg ms | sequential mg ms | sequential ic0 ms | sequential mg / batched | sequential ic0 / batched | iterations mg | iterations ic0 | same bits as sequential mg |",
+             "|---|---|---|---|---|---|---|---|---|---|"]
+    f = lambda r, n: "%.2f (%.2f .. %.2f)" % (r["ms"][n], r["ms_min"][n], r["ms_max"][n])
+    for r in rows:
+        if "ms" in r:
+            b = r["ms"]["batched mg"]
+            lines.append("| %s | %d | %s | %s | %s | %.2f | %.2f | %d | %d | %s |" % (
+                r["grid"], r["B"], f(r, "batched mg"), f(r, "sequential mg"), f(r, "sequential ic0"), r["ms"]["sequential mg"] / b,
+                r["ms"]["sequential ic0"] / b, r["iterations"]["batched mg"], r["iterations"]["sequential ic0"], "yes" if r["same_bits"] else "NO"))
+    lines += ["", "| grid | B | calcPUTargets with pcgBatched ms | calcPUTargets as it is ('ic0') ms | ratio |", "|---|---|---|---|---|"]
+    for r in rows:
+        if "calcPUTargets_ms" in r:
+            m, lo, hi = r["calcPUTargets_ms"], r["calcPUTargets_ms_min"], r["calcPUTargets_ms_max"]
+            lines.append("| %s | %d | %.2f (%.2f .. %.2f) | %.2f (%.2f .. %.2f) | %.2f |" % (
+                r["grid"], r["B"], m["pcgBatched"], lo["pcgBatched"], hi["pcgBatched"], m["as it is"], lo["as it is"], hi["as it is"],
+                m["as it is"] / m["pcgBatched"]))
+    return "\n".join(lines) + "\n"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--grids", default="2d128,2d256,3d64,3d128")
+    ap.add_argument("--batched", default=None, help="batch sizes, e.g. 1,4,16: measure solveLinearSystemPCGBatched instead")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("pcg_bench needs an MI355X: nothing is measured without one")
+    if a.batched:
+        rows = []
+        for key in a.grids.split(","):
+            rows += measure_batched(key, [int(b) for b in a.batched.split(",")])
+        text = batched_table(rows)
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text)
+        return
     rows = []
     for key in a.grids.split(","):
         rows += measure(key)
