@@ -15,12 +15,20 @@ SEED = 11
 BATCHES = {"flat": (1, 24, 28), "vol": (9, 11, 13)}
 
 
+def open_patch(f, dims, is3d):
+    """turns the fluid cells of a patch (two rows near the top in y, all of x but three cells at either end, the middle plane in
+    3-D) into empty cells, in place: their fluid neighbours get a Dirichlet condition, the component is open"""
+    Z, Y, X = dims
+    patch = f[:, :, (Z // 2 if is3d else 0), Y - 4:Y - 2, 3:X - 3]
+    patch[patch == 1.0] = 4.0
+
+
 def build_item(tf, dims, kind, seed=SEED, vel_cells=2.0):
     """(flags, U0, div, is3d) of one item: U0 is the velocity before its wall BCs, div the divergence after them.
       box      scenes.pcg_problem as it is: one closed component
       split    split=True: two large components and one of a single cell
       pockets  pcg_ref64._add_pockets: walled pockets of 2, 3 and 4 cells (each with an empty cell in its wall) and a single cell
-      open     a patch of empty cells inside the fluid: the component is open (a regular matrix)"""
+      open     open_patch: a patch of empty cells inside the fluid: the component is open (a regular matrix)"""
     import scenes
     assert kind in KINDS
     sc, f, U, div = scenes.pcg_problem(tf, dims, seed, vel_cells=vel_cells, split=kind == "split")
@@ -29,9 +37,7 @@ def build_item(tf, dims, kind, seed=SEED, vel_cells=2.0):
         if kind == "pockets":
             R._add_pockets(f, is3d)
         else:
-            Z, Y, X = dims
-            patch = f[:, :, (Z // 2 if is3d else 0), Y - 4:Y - 2, 3:X - 3]
-            patch[patch == 1.0] = 4.0
+            open_patch(f, dims, is3d)
         U = sc["U"].copy()
         tf.setWallBcsForward(U, f)
         div = np.zeros_like(sc["p"])

@@ -24,7 +24,10 @@ fp32 costs is measured on the restatement itself: solve(dtype=float32) (vectors,
 products accumulated in fp64 as on the device) against solve(dtype=float64) on CASES at RUNGS, worst cell per component relative
 to max|p64| of the component. The largest ratio is 7.19e-7 (flat_split_30x34, rung 1; per case and rung in profiles/pcg_mg.md);
 C_ITERATE is 4 x that, rounded up to two digits (2.9e-6): the margin covers the device's different order in the reductions that feed
-alpha. The mutants of MUTANTS move the first rung by more than 100 x C_ITERATE (tests/test_pcg_mg_ref_cpu.py)."""
+alpha. The mutants of MUTANTS move the first rung by more than 100 x C_ITERATE (tests/test_pcg_mg_ref_cpu.py).
+
+WIDE_CASES (below) are the grids on which the device runs coarse levels one launch per operation; they have bounds of their own,
+one per rung, by the same rule, and mutants that live on one coarse level (LEVEL_MUTANTS)."""
 import functools
 
 import numpy as np
@@ -56,6 +59,64 @@ EXTRA_CASES = {"split_10x14x20": dict(dims=(10, 14, 20), seed=6, split=True)}
 RATIO_CASES = tuple(n for n in sorted(CASES) if n != "split_8x10x16") + ("split_10x14x20",)
 
 
+# ---- the levels that run one launch per operation ----------------------------------------------------------------------------
+# Levels of more than BLOCK_CELLS cells run one launch per operation (k_mg_restrict / k_mg_first / k_mg_sweep), all smaller ones
+# inside one launch of k_mg_coarse; the host picks from the grid size alone. In every case of CASES level 1 has at most 17 x 24
+# cells: level 0 is the only level that runs as launches. WIDE_SHAPES are the smallest grids that reach the other schedules;
+# `levels` = (level count, first level k_mg_coarse owns: == count when it owns none), held by tests/test_pcg_mg_ref_cpu.py.
+# Each shape is a case twice, closed (the box as scenes.pcg_problem builds it: the mean of r removed, k_mg_rsum / k_mg_first0) and
+# open (NAME_open: pcg_batched_cases.open_patch, the cycle straight from CG's r with k_mg_first).
+BLOCK_CELLS = 4096                                # kMgBlockCells
+WIDE_SHAPES = {
+    # level 1 = 66 x 68 as launches. (Not seed 11: its obstacles wall off a closed pocket of two cells, which CG solves exactly in
+    # one iteration -- r = 0 in any precision -- so that the solve does not run k + 1 iterations on every component.)
+    "wide2_flat_132x136": dict(dims=(1, 132, 136), seed=19, split=True, levels=(7, 2)),
+    # levels 1 (130 x 132) and 2 (65 x 66 = 4290) as launches: prolongation launch to launch, a stacked offset > 0
+    "wide3_flat_260x264": dict(dims=(1, 260, 264), seed=12, levels=(8, 3)),
+    "wide3_flat_odd_259x263": dict(dims=(1, 259, 263), seed=13, levels=(8, 3)),           # 259 x 263, 130 x 132, 65 x 66: odd
+    "wide2_24x36x40": dict(dims=(24, 36, 40), seed=14, split=True, levels=(4, 2)),        # level 1 = 12 x 18 x 20 = 4320
+    "thin_flat_8x2100": dict(dims=(1, 8, 2100), seed=15, levels=(2, 2)),                  # no level for k_mg_coarse: the coarsest
+    "thin_6x6x1000": dict(dims=(6, 6, 1000), seed=16, levels=(2, 2)),                     # level's sweeps as launches
+    "one_level_flat_4x60": dict(dims=(1, 4, 60), seed=17, levels=(1, 1)),                 # NU_C sweeps of level 0, nothing else
+    "one_level_4x12x14": dict(dims=(4, 12, 14), seed=18, levels=(1, 1)),
+}
+WIDE_CASES = {}
+for _n, _c in WIDE_SHAPES.items():
+    WIDE_CASES[_n] = {k: v for k, v in _c.items() if k != "levels"}
+    WIDE_CASES[_n + "_open"] = dict(WIDE_CASES[_n], open=True)
+COUNT_CASES = tuple(n for n in sorted(WIDE_CASES) if n.startswith(("wide", "thin")))       # iteration counts at COUNT_TOL
+COUNT_TOL = 1e-4
+# The bounds of the device test on WIDE_CASES, one per rung, by C_ITERATE's rule: 4 x the worst fp32-restatement-against-fp64-
+# restatement ratio over WIDE_CASES at that rung (worst cell per component relative to max|p64| of the component), rounded up to
+# two digits. Per case and rung: profiles/pcg_mg.md. tests/test_pcg_mg_ref_cpu.py pins each constant to the measurement.
+FP32_WORST_WIDE = {0: 5.327e-7, 1: 3.177e-6, 3: 6.585e-6}       # measured, by rung: wide3_flat_260x264 at each
+C_ITERATE_WIDE = {0: 2.2e-6, 1: 1.3e-5, 3: 2.7e-5}
+# The returned residual: C_RESIDUAL at the rungs where the fp32 restatement stays under C_RESIDUAL / 2 on every case of WIDE_CASES
+# (rungs 0 and 1), elsewhere 4 x the fp32 restatement's worst relative error at that rung, rounded up to two digits (rung 3:
+# 1.452e-5 on one_level_flat_4x60_open, whose residual has fallen from 2.1 to 1.7e-3 by then; 1.17e-5 on wide3_flat_260x264).
+FP32_RES_WIDE = {0: 4.824e-7, 1: 2.081e-6, 3: 1.452e-5}
+C_RESIDUAL_WIDE = {0: C_RESIDUAL, 1: C_RESIDUAL, 3: 5.9e-5}
+
+
+def four_times_rounded_up(worst):
+    """4 x worst rounded up to two significant digits: the rule C_ITERATE and the bounds of WIDE_CASES follow"""
+    import decimal
+    d = decimal.Decimal(repr(4.0 * worst))
+    return float(d.quantize(decimal.Decimal((0, (1,), d.adjusted() - 1)), rounding=decimal.ROUND_CEILING))
+
+
+# Mutants local to one coarse level (the three of MUTANTS change every level at once). One that names a level a case does not
+# have is the identity there: mutant_applies.
+LEVEL_MUTANTS = ("coarsest_one_sweep_short", "alpha_one_into_level1", "level1_one_post_sweep", "level2_one_post_sweep")
+
+
+def mutant_applies(mutant, count):
+    """whether a mutant of LEVEL_MUTANTS changes the cycle of a hierarchy of `count` levels"""
+    # a prolongation into level l, and post-smoothing on it, exist when level l is not the last one
+    return {"coarsest_one_sweep_short": True, "alpha_one_into_level1": count >= 3, "level1_one_post_sweep": count >= 3,
+            "level2_one_post_sweep": count >= 4}[mutant]
+
+
 def mg_levels(Z, Y, X, is3d):
     """[(Z, Y, X)] per level, level 0 first (tfl_pcg_mg.hpp mg_levels)"""
     lv = [(Z, Y, X)]
@@ -65,6 +126,16 @@ def mg_levels(Z, Y, X, is3d):
             break
         lv.append(((z + 1) // 2 if is3d else z, (y + 1) // 2, (x + 1) // 2))
     return lv
+
+
+def first_block_level(levels):
+    """the first level k_mg_coarse owns (tfl_pcg_mg.hpp MgLevels::first_block_level): >= 1, == len(levels) when it owns none"""
+    fb = len(levels)
+    for l in range(len(levels) - 1, 0, -1):
+        if levels[l][0] * levels[l][1] * levels[l][2] > BLOCK_CELLS:
+            break
+        fb = l
+    return fb
 
 
 def _blocks(a, cshape, is3d):
@@ -148,7 +219,7 @@ class MgComponent(R._Component):
     def _cycle(self, l, r):
         lv = self.lv[l]
         if l == len(self.lv) - 1:
-            return self._smooth(lv, r, None, NU_C)
+            return self._smooth(lv, r, None, NU_C - 1 if self.mutate == "coarsest_one_sweep_short" else NU_C)
         z = self._smooth(lv, r, None, NU)
         cl = self.lv[l + 1]
         res = _blocks(r - self._apply(lv, z), cl.diag.shape, self.is3d)
@@ -161,8 +232,12 @@ class MgComponent(R._Component):
         for ax in ((0, 1, 2) if self.is3d else (1, 2)):
             up = np.repeat(up, 2, axis=ax)
         up = up[:z.shape[0], :z.shape[1], :z.shape[2]]
-        z = z + self.dtype(ALPHA) * up * lv.active
-        return z if self.mutate == "no_post_smoothing" else self._smooth(lv, r, z, NU)
+        alpha = 1.0 if (self.mutate == "alpha_one_into_level1" and l == 1) else ALPHA
+        z = z + self.dtype(alpha) * up * lv.active
+        if self.mutate == "no_post_smoothing":
+            return z
+        short = self.mutate == "level%d_one_post_sweep" % l and l >= 1
+        return self._smooth(lv, r, z, NU - 1 if short else NU)
 
     def cycle(self, r):
         """the bare V-cycle on flat grid-shaped vectors"""
@@ -255,11 +330,15 @@ def iterations_to(flags, div, is3d, precond, tol, max_iter=1000, dtype=np.float6
 def build_case(tf, name):
     """(flags, div, is3d); tf = any object with setWallBcsForward / velocityDivergenceForward (the oracle)"""
     import scenes
-    c = CASES[name] if name in CASES else EXTRA_CASES[name]
+    from pcg_batched_cases import open_patch
+    c = next(t[name] for t in (CASES, EXTRA_CASES, WIDE_CASES) if name in t)
     kw = {k: c[k] for k in ("B",) if k in c}
     sc, f, U, div = scenes.pcg_problem(tf, c["dims"], c["seed"], vel_cells=2.0, split=c.get("split", False), **kw)
-    if c.get("item_wall"):                      # item 1 alone gets a wall across y: other flags per item, two large components
-        f[1, :, :, f.shape[3] // 2, :] = 2.0
+    if c.get("item_wall") or c.get("open"):
+        if c.get("item_wall"):                  # item 1 alone gets a wall across y: other flags per item, two large components
+            f[1, :, :, f.shape[3] // 2, :] = 2.0
+        if c.get("open"):                       # a patch of empty cells: the component around it is open
+            open_patch(f, c["dims"], sc["is3d"])
         U = sc["U"].copy()
         tf.setWallBcsForward(U, f)
         div = np.zeros_like(sc["p"])

@@ -23,8 +23,13 @@ static char g_case[160];
 
 static bool same(WsRegion a, WsRegion b) { return a.off == b.off && a.floats == b.floats; }
 
-static void check_levels(int Z, int Y, int X, bool is3d) {
+// want_count / want_fb: the level count and first_block_level a shape is in the list for (-1: not stated)
+static void check_levels(int Z, int Y, int X, bool is3d, int want_count = -1, int want_fb = -1) {
   const MgLevels m = mg_levels(Z, Y, X, is3d);
+  if (want_count >= 0) CHECK(m.count == want_count);
+  if (want_fb >= 0) CHECK(m.first_block_level == want_fb);
+  // no level small enough for k_mg_coarse: first_block_level == count, and only then
+  CHECK((m.first_block_level == m.count) == (m.count == 1 || m.lv[m.count - 1].n > kMgBlockCells));
   CHECK(m.count >= 1 && m.count <= kMgMaxLevels);
   CHECK(m.lv[0].Z == Z && m.lv[0].Y == Y && m.lv[0].X == X && m.lv[0].n == (long long)Z * Y * X);
   long long stacked = 0;
@@ -122,6 +127,20 @@ int main() {
     std::snprintf(g_case, sizeof(g_case), "mg %d x %d x %d", s[0], s[1], s[2]);
     check_levels(s[0], s[1], s[2], is3d);
     check_ws(s[0], s[1], s[2], is3d);
+  }
+  // the shapes whose coarse levels run one launch per operation (tests/pcg_mg_ref64.py WIDE_SHAPES): {Z, Y, X, count, first_block_level}.
+  // Levels 1 and 2 as launches (a stacked offset > 0), even and odd; the thin grids, where no level is small enough for
+  // k_mg_coarse (first_block_level == count); one level only.
+  const int wide[][5] = {{1, 132, 136, 7, 2}, {1, 260, 264, 8, 3}, {1, 259, 263, 8, 3}, {24, 36, 40, 4, 2},
+                         {1, 8, 2100, 2, 2}, {6, 6, 1000, 2, 2}, {1, 4, 60, 1, 1}, {4, 12, 14, 1, 1}};
+  for (const auto& s : wide) {
+    const bool is3d = s[0] > 1;
+    std::snprintf(g_case, sizeof(g_case), "mg wide %d x %d x %d", s[0], s[1], s[2]);
+    check_levels(s[0], s[1], s[2], is3d, s[3], s[4]);
+    check_ws(s[0], s[1], s[2], is3d);
+    const MgLevels m = mg_levels(s[0], s[1], s[2], is3d);
+    if (s[4] == 3) CHECK(m.lv[2].off == m.lv[1].n && m.lv[2].n > kMgBlockCells);
+    if (s[3] == 2 && s[4] == 2) CHECK(m.lv[1].n > kMgBlockCells);              // the thin shapes: the coarsest level as launches
   }
   // a 3-D call on a grid one plane thick pools z as well and must still fit the size of the 2-D table (what the library sizes for Z = 1)
   CHECK(pcg_ws(1, 40, 40, false, true, true).total <= pcg_ws(1, 40, 40, false, true, false).total);

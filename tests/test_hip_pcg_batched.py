@@ -89,13 +89,26 @@ def test_every_item_gets_the_bits_of_the_sequential_solver(oracle, name, pc, tol
 
 
 # ---- 2. coarse levels that run one launch per operation -------------------------------------------------------------------------
-@pytest.mark.parametrize("dims", [(1, 132, 136), (24, 36, 40)])
+# dims: (the kinds of the two items, level count, first level of k_mg_coarse_b)
+WIDE = {(1, 132, 136): (("box", "split"), 7, 2), (24, 36, 40): (("box", "split"), 4, 2),
+        (1, 260, 264): (("box", "open"), 8, 3), (1, 8, 2100): (("box", "open"), 2, 2), (6, 6, 1000): (("box", "open"), 2, 2),
+        (1, 4, 60): (("box", "open"), 1, 1), (4, 12, 14): (("box", "open"), 1, 1)}
+
+
+@pytest.mark.parametrize("dims", list(WIDE))
 def test_wide_coarse_levels(oracle, dims):
-    """level 1 of these grids has more than kMgBlockCells = 4096 cells (66 x 68; 12 x 18 x 20): restriction, smoothing and
-    prolongation of a level below level 0 as batched launches of their own"""
+    """level 1 of the first two grids has more than kMgBlockCells = 4096 cells (66 x 68; 12 x 18 x 20): restriction, smoothing and
+    prolongation of a level below level 0 as batched launches of their own. The others (pcg_mg_ref64.WIDE_SHAPES) with a closed
+    and an open item, so that the launches of a level run with and without w as level 0's right-hand side: two levels below level 0
+    as launches (260 x 264), no level for k_mg_coarse_b (the thin grids: first block level == level count), one level only"""
+    kinds, count, first_block = WIDE[dims]
     levels = M.mg_levels(*dims, dims[0] > 1)
-    assert levels[1][0] * levels[1][1] * levels[1][2] > 4096
-    f, _, div, is3d = C.build_batch(oracle, dims, ("box", "split"), vel_cells=0.3)
+    cells = [z * y * x for z, y, x in levels]
+    fb = M.first_block_level(levels)
+    assert (len(levels), fb) == (count, first_block)
+    assert all(n > M.BLOCK_CELLS for n in cells[1:fb]) and all(n <= M.BLOCK_CELLS for n in cells[fb:])
+    assert count == 1 or cells[1] > 4096
+    f, _, div, is3d = C.build_batch(oracle, dims, kinds, vel_cells=0.3)
     want = _sequential(f, div, is3d, 1e-4, 1000, "mg")
     _assert_same(_batched(f, div, is3d, 1e-4, 1000, "mg"), want, "wide %s" % (dims,))
     assert (want[1] < 2e-4).all(), want[1]

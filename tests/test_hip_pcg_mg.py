@@ -1,6 +1,7 @@
 """precondType = 'mg' of solveLinearSystemPCG (fluidnet_amd/csrc/pcg_mg.hip; DESIGN.md, the multigrid preconditioner) on the
 device: converged solves against the oracle's 'ic0' solution with the assertions of test_hip_parity.py's PCG test; the iterates
-of the ladder per cell against the fp64 restatement of tests/pcg_mg_ref64.py (bound C_ITERATE, derived there); iteration counts
+of the ladder per cell against the fp64 restatement of tests/pcg_mg_ref64.py (bound C_ITERATE, derived there), on the small cases
+and on those whose coarse levels run one launch per operation (WIDE_CASES, one bound per rung); iteration counts
 through pcgLastIterations; the component rules; determinism; the workspace sizes; the step (simulate, simulate_native, project)
 and the data-set generator with pcgPrecond = 'mg'."""
 import ctypes
@@ -74,6 +75,27 @@ def test_mg_iterates_against_the_fp64_restatement(hip, oracle, name):
         assert _last_iterations() == (k + 1) * sum(1 for s in ref["sizes"] for n in s if n > 1)
 
 
+@pytest.mark.parametrize("name", sorted(M.WIDE_CASES))
+def test_mg_wide_levels_against_the_fp64_restatement(hip, oracle, name):
+    """the same on the grids whose coarse levels run one launch per operation (pcg_mg_ref64.WIDE_SHAPES: a level >= 1 as launches,
+    prolongation launch to launch at a stacked offset, no level for k_mg_coarse, one level only), each closed and open, with the
+    per-rung bounds C_ITERATE_WIDE / C_RESIDUAL_WIDE derived there from the fp32 restatement"""
+    f, div, is3d = M.case(name)
+    ref = M.reference(name)
+    for k in M.RUNGS:
+        p = np.random.RandomState(3).rand(*div.shape).astype(np.float32)
+        res = hip.solveLinearSystemPCG(p, f, div, is3d, R.TOL_NEVER, k, "mg")
+        its = _last_iterations()
+        err, zero = R.worst_error(p, ref["p"][k], ref)
+        dres = abs(float(res) - ref["res"][k]) / ref["res"][k]
+        print("MGIT %-28s rung %d err %.2e (bound %.1e) residual %.2e (bound %.1e)"
+              % (name, k, err, M.C_ITERATE_WIDE[k], dres, M.C_RESIDUAL_WIDE[k]))
+        assert np.isfinite(p).all() and zero, (name, k)
+        assert err <= M.C_ITERATE_WIDE[k], (name, k, err)
+        assert dres <= M.C_RESIDUAL_WIDE[k], (name, k, float(res), ref["res"][k])
+        assert its == (k + 1) * sum(1 for s in ref["sizes"] for n in s if n > 1)
+
+
 # ---- 3. iteration counts ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", [n for n in sorted(M.CASES)])
 def test_mg_iteration_counts(hip, oracle, name):
@@ -89,6 +111,20 @@ def test_mg_iteration_counts(hip, oracle, name):
     print("MGCOUNT %-18s mg %d ic0 %d restatement mg %d ic0 %d" % (name, its["mg"], its["ic0"], want, M.iterations(name, "ic0")))
     assert its["mg"] <= its["ic0"], its
     assert abs(its["mg"] - want) <= 2, (its, want)
+
+
+@pytest.mark.parametrize("name", M.COUNT_CASES)
+def test_mg_iteration_counts_on_wide_levels(hip, oracle, name):
+    """the wide and the thin cases, closed and open, at tol 1e-4 (the tolerance of the large converged cases above): the
+    restatement's count within 2. A coarse level that is wrong but still symmetric and positive costs iterations and nothing else."""
+    f, div, is3d = M.case(name)
+    p = np.zeros_like(div)
+    res = hip.solveLinearSystemPCG(p, f, div, is3d, M.COUNT_TOL, 1000, "mg")
+    its = _last_iterations()
+    want = M.iterations(name, "mg", M.COUNT_TOL)
+    print("MGCOUNT %-28s tol %g: mg %d restatement %d, residual %.3e" % (name, M.COUNT_TOL, its, want, res))
+    assert res <= M.COUNT_TOL and np.isfinite(p).all(), res
+    assert abs(its - want) <= 2, (its, want)
 
 
 # ---- 4. component rules -----------------------------------------------------------------------------------------------------
@@ -129,7 +165,7 @@ def test_batch_items_with_their_own_flags(hip, oracle):
 
 
 # ---- 5. determinism ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["flat_odd_33x47", "odd_12x17x20"])
+@pytest.mark.parametrize("name", ["flat_odd_33x47", "odd_12x17x20", "wide2_24x36x40", "wide2_flat_132x136_open"])
 def test_mg_is_deterministic(hip, oracle, name):
     """two solves give the same bits, and so does one behind an 'ic0' solve in the same workspace"""
     f, div, is3d = M.case(name)
