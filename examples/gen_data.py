@@ -7,7 +7,7 @@ divergence-free noise velocity, random gravity direction, buoyancy and vorticity
 every --save-every-th step one frame pair. The scenes are this project's own; they are NOT the reference's Mantaflow scenes.
 
   python examples/gen_data.py --out data/datasets --dataset my_set --dim 2 --res 128 --runs-tr 320 --runs-te 320 \\
-        [--steps 256] [--save-every 4] [--seed 1] [--models a.binvox b.binvox]
+        [--steps 256] [--save-every 4] [--seed 1] [--models a.binvox b.binvox] [--pcgPrecond mg --batchRuns 16]
   python examples/train.py --dataDir data/datasets --dataset my_set --out /tmp/fit/model
 """
 import argparse
@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--models", nargs="*", default=[], help="binvox files stamped into 3-D scenes as obstacles")
     ap.add_argument("--pcgPrecond", default="ic0", choices=("none", "ilu0", "ic0", "mg"), help="preconditioner of the PCG solves")
+    ap.add_argument("--batchRuns", type=int, default=1, help="runs stepped at a time as the items of one batch (1 .. 32; the same set either "
+                    "way). It pays where a step is launch-bound: small grids with --pcgPrecond mg | none")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     is3D = a.dim == 3
@@ -44,7 +46,7 @@ def main():
         if nruns <= 0:
             continue
         # the test set's runs carry on from the training set's numbers: no scene appears in both
-        res_ = datagen.generate(gconf, prefix, nruns, a.seed, out_dir=out, device=a.device, first_run=first)
+        res_ = datagen.generate(gconf, prefix, nruns, a.seed, out_dir=out, device=a.device, first_run=first, batch_runs=a.batchRuns)
         first += nruns
         again = [r for r in res_["report"] if not r["kept"]]
         print("==> %s: %d runs of %d frame pairs in %s; worst max(div) kept %.3e; %d attempts regenerated"

@@ -57,6 +57,12 @@ class tfl_sim_params(_c.Structure):
                 ("pcgPrecond", _c.c_char_p), ("outputDiv", _c.c_int32)]
 
 
+class tfl_sim_item(_c.Structure):
+    """include/tfluids_hip.h tfl_sim_item (the force fields of tfl_sim_params, for one batch item)."""
+    _fields_ = [("gravity", _c.c_float * 3), ("buoyancyScale", _c.c_double), ("gravityScale", _c.c_double),
+                ("vorticityConfinementAmp", _c.c_double)]
+
+
 class tfl_sim_state(_c.Structure):
     """include/tfluids_hip.h tfl_sim_state."""
     _fields_ = [("p", _c.POINTER(tfl_tensor)), ("U", _c.POINTER(tfl_tensor)), ("flags", _c.POINTER(tfl_tensor)),
@@ -129,6 +135,12 @@ SIGNATURES = {
                                    _c.c_int]),
     "tfl_addBuoyancyFrom": (_c.c_int, [_c.c_void_p, _T, _T, _T, _T, _F3, _c.c_float, _c.c_int]),
     "tfl_addGravity": (_c.c_int, [_c.c_void_p, _T, _T, _F3, _c.c_float, _c.c_int, _c.c_void_p]),
+    "tfl_addBuoyancyItems": (_c.c_int, [_c.c_void_p, _T, _T, _T, _T, _c.POINTER(_c.c_float), _c.POINTER(_c.c_int32), _c.c_int32,
+                                        _c.c_float, _c.c_int]),
+    "tfl_addGravityItems": (_c.c_int, [_c.c_void_p, _T, _T, _c.POINTER(_c.c_float), _c.POINTER(_c.c_int32), _c.c_int32, _c.c_float,
+                                       _c.c_int]),
+    "tfl_vorticityConfinementItems": (_c.c_int, [_c.c_void_p, _T, _T, _c.POINTER(_c.c_float), _c.POINTER(_c.c_int32), _c.c_int32,
+                                                 _T, _T, _c.c_int]),
     "tfl_emptyDomain": (_c.c_int, [_c.c_void_p, _T, _c.c_int, _c.c_int]),
     "tfl_flagsToOccupancy": (_c.c_int, [_c.c_void_p, _T, _T]),
     "tfl_rectangularBlur": (_c.c_int, [_c.c_void_p, _T, _c.c_int, _c.c_int, _T, _T]),
@@ -231,6 +243,11 @@ SIGNATURES = {
                                      _c.c_int64]),
     "tfl_simulate_project": (_c.c_int, [_c.c_void_p, _c.POINTER(tfl_sim_params), _c.POINTER(tfl_sim_state), _c.c_void_p,
                                         _c.c_int64]),
+    "tfl_simulate_items_workspace_floats": (_c.c_int64, [_c.c_void_p, _c.POINTER(tfl_sim_params), _c.POINTER(tfl_sim_state)]),
+    "tfl_simulate_step_items": (_c.c_int, [_c.c_void_p, _c.POINTER(tfl_sim_params), _c.POINTER(tfl_sim_item), _c.c_int32,
+                                           _c.POINTER(tfl_sim_state), _c.c_void_p, _c.c_int64]),
+    "tfl_simulate_project_items": (_c.c_int, [_c.c_void_p, _c.POINTER(tfl_sim_params), _c.POINTER(tfl_sim_item), _c.c_int32,
+                                              _c.POINTER(tfl_sim_state), _c.c_void_p, _c.c_int64]),
     "tfl_applyBCsIndexedMulti": (_c.c_int, [_c.c_void_p, _c.c_int, _c.POINTER(_T), _c.POINTER(_T), _c.POINTER(_T),
                                             _c.POINTER(_c.c_void_p), _c.POINTER(_c.c_int64)]),
     "tfl_applyBCs": (_c.c_int, [_c.c_void_p, _T, _T, _T, _c.c_int, _c.c_float, _c.c_float]),

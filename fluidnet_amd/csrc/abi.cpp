@@ -192,9 +192,93 @@ int addGravity(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const f
                    gravity[0] * k, gravity[1] * k, gravity[2] * k);
   return check_launch(c, "addGravity");
 }
+
+// ---- the per-item force operators --------------------------------------------------------------------------
+// what every one of them refuses, by name, before anything is enqueued
+static int check_items(tfl_ctx* c, const char* op, const tfl_tensor* flags, const void* table, int n_items, const Scope& sc) {
+  if (!table) return fail(c, TFL_EINVAL, "%s: the per-item table is null", op);
+  if (n_items > TFL_MAX_ITEMS) return fail(c, TFL_EINVAL, "%s: %d items, at most %d fit the kernel arguments", op, n_items, TFL_MAX_ITEMS);
+  if (n_items != flags->B) return fail(c, TFL_EINVAL, "%s: n_items = %d, the batch holds %d", op, n_items, flags->B);
+  if (sc.windowed() || sc.stages != 0) return fail(c, TFL_EUNSUPPORTED, "%s: a z-window or stage mask is set on the context", op);
+  return TFL_OK;
+}
+static bool item_on(const int32_t* on, int b) { return !on || on[b] != 0; }
+
+int addBuoyancyItems(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* density,
+                     const float* gravity, const int32_t* on, int n_items, float dt, int is3D, const Scope& sc) {
+  const char* op = "addBuoyancyItems";
+  TRY(check_flags(c, op, flags));
+  TRY(check_vel(c, op, "U", U, flags, is3D));
+  if (USrc) TRY(check_vel(c, op, "USrc", USrc, flags, is3D));
+  TRY(check_scalar(c, op, "density", density, flags));
+  TRY(check_items(c, op, flags, gravity, n_items, sc));
+  const float k = dt / get_dx(c, sc, flags);  // strength = -gravity * (dt / dx), as addBuoyancyFrom forms it
+  tfl::ItemVec t{};
+  for (int b = 0; b < n_items; b++) {
+    if (!item_on(on, b)) continue;
+    t.on |= 1u << b;
+    t.x[b] = -gravity[3 * b] * k; t.y[b] = -gravity[3 * b + 1] * k; t.z[b] = -gravity[3 * b + 2] * k;
+  }
+  tfl::add_buoyancy_items(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, USrc ? USrc->data : U->data, U->data, flags->data,
+                          density->data, t);
+  return check_launch(c, op);
+}
+
+int addGravityItems(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const float* gravity, const int32_t* on, int n_items,
+                    float dt, int is3D, const Scope& sc) {
+  const char* op = "addGravityItems";
+  TRY(check_flags(c, op, flags));
+  TRY(check_vel(c, op, "U", U, flags, is3D));
+  TRY(check_items(c, op, flags, gravity, n_items, sc));
+  const float k = dt / get_dx(c, sc, flags);  // force = gravity * (dt / dx), as addGravity forms it
+  tfl::ItemVec t{};
+  for (int b = 0; b < n_items; b++) {
+    if (!item_on(on, b)) continue;
+    t.on |= 1u << b;
+    t.x[b] = gravity[3 * b] * k; t.y[b] = gravity[3 * b + 1] * k; t.z[b] = gravity[3 * b + 2] * k;
+  }
+  tfl::add_gravity_items(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, t);
+  return check_launch(c, op);
+}
+
+int vorticityConfinementItems(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const float* strength, const int32_t* on,
+                              int n_items, const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D, const Scope& sc) {
+  const char* op = "vorticityConfinementItems";
+  TRY(check_flags(c, op, flags));
+  TRY(check_vel(c, op, "U", U, flags, is3D));
+  if (!curl || !curl->data || curl->C != 3 || !same_dims(curl, flags))
+    return fail(c, TFL_EINVAL, "%s: curl must be a 3-channel grid of the flags size", op);
+  TRY(check_scalar(c, op, "curlNorm", curlNorm, flags));
+  TRY(check_items(c, op, flags, strength, n_items, sc));
+  tfl::ItemAmp t{};
+  for (int b = 0; b < n_items; b++) {
+    if (!item_on(on, b)) continue;
+    t.on |= 1u << b;
+    t.s[b] = strength[b];
+  }
+  tfl::vorticity_confinement_items(c->stream, sc, is3D != 0, flags->B, flags->Z, flags->Y, flags->X, U->data, flags->data, t,
+                                   curl->data, curlNorm->data);
+  return check_launch(c, op);
+}
 }  // namespace tfl
 
 extern "C" {
+
+int tfl_addBuoyancyItems(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* density,
+                         const float* gravity, const int32_t* on, int32_t n_items, float dt, int is3D) {
+  if (!c) return TFL_EINVAL;
+  return tfl::addBuoyancyItems(c, USrc, U, flags, density, gravity, on, n_items, dt, is3D, tfl::scope_of(c));
+}
+int tfl_addGravityItems(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const float* gravity, const int32_t* on,
+                        int32_t n_items, float dt, int is3D) {
+  if (!c) return TFL_EINVAL;
+  return tfl::addGravityItems(c, U, flags, gravity, on, n_items, dt, is3D, tfl::scope_of(c));
+}
+int tfl_vorticityConfinementItems(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const float* strength,
+                                  const int32_t* on, int32_t n_items, const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D) {
+  if (!c) return TFL_EINVAL;
+  return tfl::vorticityConfinementItems(c, U, flags, strength, on, n_items, curl, curlNorm, is3D, tfl::scope_of(c));
+}
 
 int tfl_advectScalar(tfl_ctx* c, float dt, const tfl_tensor* s, const tfl_tensor* U, const tfl_tensor* flags,
                      const tfl_tensor* fwd, const tfl_tensor* bwd, int is3D, const char* method,

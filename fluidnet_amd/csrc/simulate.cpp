@@ -97,15 +97,22 @@ tfl::StepProj proj_of(const tfl_sim_params* p) {
   return !std::strcmp(m, "convnet") ? tfl::StepProj::convnet : !std::strcmp(m, "jacobi") ? tfl::StepProj::jacobi
        : !std::strcmp(m, "pcg") ? tfl::StepProj::pcg : tfl::StepProj::unknown;
 }
+// the preconditioners tfl_solveLinearSystemPCGBatched takes: the step on items (tfl_simulate_step_items) solves all items at once
+bool pcg_batches(const tfl_sim_params* prm) {
+  return prm->pcgPrecond && (!std::strcmp(prm->pcgPrecond, "mg") || !std::strcmp(prm->pcgPrecond, "none"));
+}
 // the workspace table of a step (tfl_step_ws.hpp), and the floats the step needs: the table's, or the model's own workspace
 // (the PCG region is sized for params->pcgPrecond; a name the solver does not know gets the common size and is refused there)
-tfl::StepWs step_ws_of(const tfl_sim_params* prm, const Sizes& z, tfl::StepProj proj) {
+// items: the table of the step on items, whose PCG region holds the batched solver's workspace where that solver runs
+tfl::StepWs step_ws_of(const tfl_sim_params* prm, const Sizes& z, tfl::StepProj proj, bool items = false) {
   long long pcg = 0;
   if (proj == tfl::StepProj::pcg) {
     pcg = tfl_pcg_workspace_floats_for(z.Z, z.Y, z.X, prm->pcgPrecond && prm->pcgPrecond[0] ? prm->pcgPrecond : "ic0");
     if (pcg < 0) pcg = tfl_pcg_workspace_floats(z.Z, z.Y, z.X);
   }
-  return tfl::step_ws(z.B, z.Z, z.Y, z.X, (int)z.C, proj, pcg);
+  if (!items) return tfl::step_ws(z.B, z.Z, z.Y, z.X, (int)z.C, proj, pcg);
+  const long long batched = proj == tfl::StepProj::pcg && pcg_batches(prm) ? tfl_pcg_batched_workspace_floats(z.B, z.Z, z.Y, z.X, prm->pcgPrecond) : -1;
+  return tfl::step_items_ws(z.B, z.Z, z.Y, z.X, (int)z.C, proj, pcg, batched);
 }
 long long step_ws_floats(const tfl_sim_state* s, const Sizes& z, tfl::StepProj proj, const tfl::StepWs& W) {
   if (proj != tfl::StepProj::convnet || !s->model) return W.total;
@@ -148,6 +155,17 @@ struct Step {
   // confinement (tfl_vorticityConfinementFrom: the fused kernel cannot run in place anyway, the two-launch form reads one
   // array and writes the other since round 5) or the ConvNet projection (UDiv = cur, UOut = U); a copy only where none does.
   const tfl_tensor* cur = nullptr;     // where the velocity of the step currently lives
+  // The step on batch items (tfl_simulate_step_items): every item has forces of its own. The advection and the
+  // solver projection are the phases above, batch-wide; the forces run as the per-item operators, one launch per force (a force
+  // runs where ANY item has it), and PCG as the batched solver where the preconditioner batches. `buoyant`, `gravity_on` and
+  // `vort` stay off, so the advection folds no force.
+  const tfl_sim_item* items = nullptr; // [z.B], set by validate_items
+  bool on_items = false;               // the workspace table is the items step's
+  bool pcg_batched = false;            // PCG runs tfl_solveLinearSystemPCGBatched
+  tfl_sim_item own_items[TFL_MAX_ITEMS];   // items == NULL: params' forces for every item
+
+  int validate_items(const tfl_sim_item* it, int n_items, const char* who);   // the items step's refusals, then validate()
+  int forces_items();                  // the per-item forces, the velocity into U
 
   int validate(const char* who = "simulate_step");      // every refusal, before anything is enqueued, under the entry's name; the methods, the views, the forces
   int advect();                        // [advectVel pass A,] the density channels, advectVel, the first setConstVals
@@ -165,7 +183,7 @@ int Step::validate(const char* who) {
   z = sizes_of(s);
   is3D = z.is3d ? 1 : 0;
   proj = proj_of(prm);
-  const tfl::StepWs W = step_ws_of(prm, z, proj);
+  const tfl::StepWs W = step_ws_of(prm, z, proj, on_items);
   if (!ws || ((uintptr_t)ws & 15) != 0 || ws_floats < step_ws_floats(s, z, proj, W)) return TFL_EINVAL;
   method = (prm->advectionMethod && prm->advectionMethod[0]) ? prm->advectionMethod : "maccormackOurs";
   ours = std::strcmp(method, "maccormackOurs") == 0;
@@ -336,14 +354,105 @@ int Step::project_solver() {
     // IC(0) / ILU(0) solves run as pipelined wavefronts (pcg.hip, two launches per application); the preconditioned
     // solve takes ~1.7x the time of the unpreconditioned one at 128^3 on this machine and 0.7x at 256^3 (a third of the
     // iterations, each with two latency-bound sweeps): pcgPrecond = "none" trades that for more iterations within maxIter.
-    TRY(tfl_solveLinearSystemPCG(c, s->p, s->flags, &div, is3D, prm->pcgPrecond && prm->pcgPrecond[0] ? prm->pcgPrecond : "ic0",
-                                 1e-4f, max_iter, 0, pws, ws_floats - (pws - ws), &res));
+    if (pcg_batched) {    // (the step on items: every item in the launches of one, each with the bits it gets alone)
+      TRY(tfl_solveLinearSystemPCGBatched(c, s->p, s->flags, &div, is3D, prm->pcgPrecond, 1e-4f, max_iter, pws, ws_floats - (pws - ws), nullptr, nullptr));
+    } else {
+      TRY(tfl_solveLinearSystemPCG(c, s->p, s->flags, &div, is3D, prm->pcgPrecond && prm->pcgPrecond[0] ? prm->pcgPrecond : "ic0",
+                                   1e-4f, max_iter, 0, pws, ws_floats - (pws - ws), &res));
+    }
   } else {
     return TFL_EINVAL;   // mconf.simMethod is not a valid option
   }
   TRY(tfl_velocityUpdateForward(c, s->U, s->flags, s->p, is3D));
   TRY(set_const_vals(c, s, s->U, true, Unchanged{false, false, true}));
   return tfl_applyBCs(c, s->U, nullptr, nullptr, 1, -1e6f, 1e6f);
+}
+
+// ---- the step on batch items ---------------------------------------------------------------------------------------------------
+// Every refusal of the items entries, by name, before anything is enqueued; then the step's own validate() on the items table.
+int Step::validate_items(const tfl_sim_item* it, int n_items, const char* who) {
+  auto refuse = [&](int code, const std::string& why) { c->err = std::string(who) + ": " + why; return code; };
+  if (!s->flags->data || !s->U->data || !s->p->data) return refuse(TFL_EINVAL, "a state tensor is null");
+  z = sizes_of(s);
+  if (n_items > TFL_MAX_ITEMS || z.B > TFL_MAX_ITEMS)
+    return refuse(TFL_EINVAL, std::to_string(std::max(n_items, z.B)) + " items, at most " + std::to_string(TFL_MAX_ITEMS) + " fit the force kernels' arguments");
+  if (n_items != z.B) return refuse(TFL_EINVAL, "n_items = " + std::to_string(n_items) + ", the batch holds " + std::to_string(z.B));
+  proj = proj_of(prm);
+  if (proj == tfl::StepProj::convnet)
+    return refuse(TFL_EUNSUPPORTED, "simMethod convnet is not stepped on items (the training rollouts share one mconf: tfl_simulate_step)");
+  if (proj == tfl::StepProj::unknown) return refuse(TFL_EINVAL, "mconf.simMethod is not a valid option");
+  const char* pc = prm->pcgPrecond && prm->pcgPrecond[0] ? prm->pcgPrecond : "ic0";
+  if (proj == tfl::StepProj::pcg && tfl_pcg_workspace_floats_for(z.Z, z.Y, z.X, pc) < 0)
+    return refuse(TFL_EINVAL, std::string("pcgPrecond '") + pc + "' is not a preconditioner");
+  const tfl::Scope here = tfl::scope_of(c);
+  if (here.windowed() || here.stages != 0) return refuse(TFL_EUNSUPPORTED, "a z-window or stage mask is set on the context");
+  if (s->n_density < 0 || s->n_density > 8) return refuse(TFL_EINVAL, "0 to 8 density channels");
+  if (!it) {
+    for (int b = 0; b < z.B; b++) {
+      tfl_sim_item& o = own_items[b];
+      for (int a = 0; a < 3; a++) o.gravity[a] = prm->gravity[a];
+      o.buoyancyScale = prm->buoyancyScale; o.gravityScale = prm->gravityScale; o.vorticityConfinementAmp = prm->vorticityConfinementAmp;
+    }
+    it = own_items;
+  }
+  for (int b = 0; b < z.B; b++) {
+    const tfl_sim_item& o = it[b];
+    if (!std::isfinite(o.gravity[0]) || !std::isfinite(o.gravity[1]) || !std::isfinite(o.gravity[2]) || !std::isfinite(o.buoyancyScale) ||
+        !std::isfinite(o.gravityScale) || !std::isfinite(o.vorticityConfinementAmp))
+      return refuse(TFL_EINVAL, "a force field of item " + std::to_string(b) + " is not finite");
+  }
+  items = it;
+  on_items = true;
+  pcg_batched = proj == tfl::StepProj::pcg && pcg_batches(prm);
+  const long long need = step_ws_of(prm, z, proj, true).total;
+  if (!ws || ((uintptr_t)ws & 15) != 0) return refuse(TFL_EINVAL, "the workspace is null or not 16-byte aligned");
+  if (ws_floats < need)
+    return refuse(TFL_EINVAL, "the workspace holds " + std::to_string((long long)ws_floats) + " floats, the step needs " + std::to_string(need) +
+                                  " (tfl_simulate_items_workspace_floats)");
+  TRY(validate(who));
+  buoyant = gravity_on = vort = vfused = false;      // params' own force fields are not read: the items carry them
+  return TFL_OK;
+}
+
+// forces (simulate.lua:204-239), each as ONE launch (the confinement: its two) for the whole batch. An item takes a force where the
+// single-item step would: buoyancyScale > 0 with a density, gravityScale > 0, vorticityConfinementAmp > 0, with the strengths
+// formed by the functions that step uses. The velocity reaches U through addBuoyancyItems where any item is buoyant (it writes
+// every cell of U: the items without the force are copied), else by a copy; gravity and the confinement then run in place on U,
+// and leave the items without them alone.
+int Step::forces_items() {
+  const int B = z.B;
+  float g[3 * TFL_MAX_ITEMS], amp[TFL_MAX_ITEMS];
+  int32_t on[TFL_MAX_ITEMS];
+  auto fill = [&](auto scale_of, bool extra) {
+    bool any = false;
+    for (int b = 0; b < B; b++) {
+      tfl_sim_params q = *prm;
+      for (int a = 0; a < 3; a++) q.gravity[a] = items[b].gravity[a];
+      const double scale = scale_of(items[b]);
+      on[b] = extra && scale > 0.0;
+      any = any || on[b];
+      scaled_gravity(&q, dx, scale, g + 3 * b);
+    }
+    return any;
+  };
+  if (fill([](const tfl_sim_item& o) { return o.buoyancyScale; }, s->n_density > 0)) {
+    TRY(tfl::addBuoyancyItems(c, cur, s->U, s->flags, s->density[0], g, on, B, prm->dt, is3D, sc));
+    cur = s->U;
+  }
+  if (cur != s->U) {
+    TRY(tfl_copy(c, s->U, cur));
+    cur = s->U;
+  }
+  if (fill([](const tfl_sim_item& o) { return o.gravityScale; }, true))
+    TRY(tfl::addGravityItems(c, s->U, s->flags, g, on, B, prm->dt, is3D, sc));
+  bool any_vort = false;
+  for (int b = 0; b < B; b++) {
+    on[b] = items[b].vorticityConfinementAmp > 0.0;
+    any_vort = any_vort || on[b];
+    amp[b] = (float)(dx * items[b].vorticityConfinementAmp);
+  }
+  if (any_vort) TRY(tfl::vorticityConfinementItems(c, s->U, s->flags, amp, on, B, &curl, &cnorm, is3D, sc));
+  return TFL_OK;
 }
 
 }  // namespace
@@ -430,6 +539,34 @@ int tfl_simulate_project(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_st
   if (S.proj == tfl::StepProj::convnet && !s->model) { c->err = "simulate_project: simMethod convnet needs a model"; return TFL_EINVAL; }
   S.cur = s->U;
   return S.proj == tfl::StepProj::convnet ? S.project_net() : S.project_solver();
+}
+
+int64_t tfl_simulate_items_workspace_floats(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_state* s) {
+  if (!c || !prm || !s || !s->flags || !s->U) return 0;
+  const Sizes z = sizes_of(s);
+  return step_ws_of(prm, z, proj_of(prm), true).total;
+}
+
+int tfl_simulate_step_items(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_item* items, int32_t n_items, const tfl_sim_state* s,
+                            float* ws, int64_t ws_floats) {
+  if (!c || !prm || !s || !s->p || !s->U || !s->flags) return TFL_EINVAL;
+  Step S{c, prm, s, ws, ws_floats};
+  TRY(S.validate_items(items, n_items, "simulate_step_items"));
+  TRY(S.advect());
+  TRY(S.forces_items());
+  if (prm->outputDiv) return TFL_OK;
+  return S.project_solver();
+}
+
+// the projection phase alone, behind an outputDiv items step (which has delivered the velocity into U and applied no pair since
+// the first setConstVals): tfl_simulate_project's contract, on items
+int tfl_simulate_project_items(tfl_ctx* c, const tfl_sim_params* prm, const tfl_sim_item* items, int32_t n_items, const tfl_sim_state* s,
+                               float* ws, int64_t ws_floats) {
+  if (!c || !prm || !s || !s->p || !s->U || !s->flags) return TFL_EINVAL;
+  Step S{c, prm, s, ws, ws_floats};
+  TRY(S.validate_items(items, n_items, "simulate_project_items"));
+  S.cur = s->U;
+  return S.project_solver();
 }
 
 }  // extern "C"

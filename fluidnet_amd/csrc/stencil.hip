@@ -96,11 +96,19 @@ __global__ __launch_bounds__(256) void k_velocity_update(Dom d, float* __restric
   }
 }
 
+// The per-item form of the force kernels (Tab = one ItemVec, tfl_host.hpp): the block's item b is block-uniform, so its strengths
+// are scalar loads from the argument segment; an item whose bit of `on` is clear has no force.
+
 // third_party/tfluids.cc:1162-1233; (sx,sy,sz) = -gravity * dt / dx computed on the host
-template <bool IS3D>
+template <bool IS3D, class... Tab>
 __global__ __launch_bounds__(256) void k_add_buoyancy(Dom d, float* __restrict__ U, const float* __restrict__ flags,
-                                                      const float* __restrict__ rho, float sx, float sy, float sz) {
+                                                      const float* __restrict__ rho, float sx, float sy, float sz, Tab... tab) {
   TFL_STENCIL_INDEX();
+  if constexpr (sizeof...(Tab) != 0) {
+    const ItemVec& t = items_of(tab...);
+    if (!((t.on >> b) & 1u)) return;      // the item's words are not touched
+    sx = t.x[b]; sy = t.y[b]; sz = t.z[b];
+  }
   if (on_border<IS3D>(d, i, j, k)) return;
   U += b * cells * C; flags += b * cells; rho += b * cells;
   if (!(((int)flags[o]) & kFluid)) return;
@@ -112,17 +120,24 @@ __global__ __launch_bounds__(256) void k_add_buoyancy(Dom d, float* __restrict__
 
 // The same, four consecutive x cells per thread (X % 4 == 0, 16-byte aligned rows): every access is a
 // 16-byte vector; the x-1 neighbour of the first cell is one extra scalar load. Identical arithmetic per cell.
-template <bool IS3D>
+template <bool IS3D, class... Tab>
 __global__ __launch_bounds__(256) void k_add_buoyancy_v4(Dom d, const float* __restrict__ Usrc, float* __restrict__ U,
                                                          const float* __restrict__ flags, const float* __restrict__ rho,
-                                                         float sx, float sy, float sz, BcFoldArg folda) {
+                                                         float sx, float sy, float sz, BcFoldArg folda, Tab... tab) {
   // U = Usrc + buoyancy. Usrc == U: the reference's in-place op. Usrc != U (tfl_addBuoyancyFrom): every cell is
   // written, which folds the `U:copy(advected)` that precedes it in simulate() into this pass.
   const int i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
   const int j = blockIdx.y * blockDim.y + threadIdx.y;
   int b, k; dom_bk(d, b, k);
   if (i0 >= d.X || j >= d.Y) return;
-  const bool inner = !(j < 1 || j > d.Y - 2 || (IS3D && (k < 1 || k > d.Z - 2)));
+  bool inner = !(j < 1 || j > d.Y - 2 || (IS3D && (k < 1 || k > d.Z - 2)));
+  if constexpr (sizeof...(Tab) != 0) {
+    const ItemVec& t = items_of(tab...);
+    // an item without the force is a grid of border rows: not touched in place, copied otherwise
+    const bool on = (t.on >> b) & 1u;
+    inner = inner && on;
+    sx = on ? t.x[b] : 0.0f; sy = on ? t.y[b] : 0.0f; sz = on ? t.z[b] : 0.0f;
+  }
   if (!inner && Usrc == U) return;
   const long long cells = d.sc;
   const int C = IS3D ? 3 : 2;
@@ -181,10 +196,15 @@ __global__ __launch_bounds__(256) void k_add_buoyancy_v4(Dom d, const float* __r
 }
 
 // third_party/tfluids.cc:1239-1306
-template <bool IS3D>
+template <bool IS3D, class... Tab>
 __global__ __launch_bounds__(256) void k_add_gravity(Dom d, float* __restrict__ U, const float* __restrict__ flags,
-                                                     float fx, float fy, float fz) {
+                                                     float fx, float fy, float fz, Tab... tab) {
   TFL_STENCIL_INDEX();
+  if constexpr (sizeof...(Tab) != 0) {
+    const ItemVec& t = items_of(tab...);
+    if (!((t.on >> b) & 1u)) return;      // the item's words are not touched
+    fx = t.x[b]; fy = t.y[b]; fz = t.z[b];
+  }
   if (on_border<IS3D>(d, i, j, k)) return;
   U += b * cells * C; flags += b * cells;
   const int fc = (int)flags[o];
@@ -360,6 +380,34 @@ void add_buoyancy(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int 
 void add_gravity(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags, float fx,
                  float fy, float fz) {
   TFL_LAUNCH(make_dom(sc, Z, Y, X), k_add_gravity, U, flags, fx, fy, fz);
+}
+// The per-item forms: the same launches with the table (no pair is folded)
+#define TFL_LAUNCH_ITEMS(dom, kern, ...)                             \
+  do {                                                               \
+    const Dom d = dom;                                               \
+    const dim3 blk(64, 4, 1), grd = cgrid(d, B, blk);                \
+    TFL_TIMED(#kern "_items", st);                                   \
+    if (is3d) kern<true><<<grd, blk, 0, st>>>(d, __VA_ARGS__); \
+    else kern<false><<<grd, blk, 0, st>>>(d, __VA_ARGS__);     \
+  } while (0)
+void add_buoyancy_items(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* Usrc, float* U, const float* flags,
+                        const float* density, const ItemVec& t) {
+  const bool vec = (X % 4 == 0) && ((((uintptr_t)U | (uintptr_t)Usrc | (uintptr_t)flags | (uintptr_t)density) & 15) == 0) &&
+                   !sw::present(Sw::NO_VEC4);
+  if (vec) {
+    const Dom d = make_dom(sc, Z, Y, X);
+    const dim3 blk(32, 8, 1), grd((X / 4 + 31) / 32, (Y + 7) / 8, (unsigned)(d.nw * B));
+    TFL_TIMED("k_add_buoyancy_items", st);
+    if (is3d) k_add_buoyancy_v4<true><<<grd, blk, 0, st>>>(d, Usrc, U, flags, density, 0.0f, 0.0f, 0.0f, no_fold(), t);
+    else k_add_buoyancy_v4<false><<<grd, blk, 0, st>>>(d, Usrc, U, flags, density, 0.0f, 0.0f, 0.0f, no_fold(), t);
+    return;
+  }
+  if (Usrc != U)   // the one-cell-per-thread kernel skips the cells it does not change
+    (void)hipMemcpyAsync(U, Usrc, sizeof(float) * (size_t)B * (is3d ? 3 : 2) * Z * Y * X, hipMemcpyDeviceToDevice, st);
+  TFL_LAUNCH_ITEMS(make_dom(sc, Z, Y, X), k_add_buoyancy, U, flags, density, 0.0f, 0.0f, 0.0f, t);
+}
+void add_gravity_items(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags, const ItemVec& t) {
+  TFL_LAUNCH_ITEMS(make_dom(sc, Z, Y, X), k_add_gravity, U, flags, 0.0f, 0.0f, 0.0f, t);
 }
 // ---- rectangularBlur / signedDistanceField (generic/tfluids.cc:642-821): criterion-side helpers, not on the step ----------
 // One thread per line; the running sum is sequential along the line in the reference's order (bit-exact). Lines of a pass:

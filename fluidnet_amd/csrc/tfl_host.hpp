@@ -62,6 +62,19 @@ struct Fold {
   BuoyFold hand_buoy() { buoy_took = buoy_took || buoy.rho; return buoy; }
 };
 
+// The forces of the `Items` operators (tfl_addBuoyancyItems, tfl_addGravityItems, tfl_vorticityConfinementItems):
+// every batch item has its own strengths. The table travels BY VALUE in the kernel arguments and is indexed by the block's item,
+// which is block-uniform: the reads are scalar loads from the argument segment. Bit b of `on`: item b has the force; a block of
+// an item without it returns (in place) or copies (source != destination) and never reads the item's entries.
+constexpr int kMaxItems = 32;
+struct ItemVec { float x[kMaxItems], y[kMaxItems], z[kMaxItems]; unsigned on; };
+struct ItemAmp { float s[kMaxItems]; unsigned on; };
+// The force kernels are written once, template <bool IS3D, class... Tab>, with the table as a trailing argument PACK: empty for the
+// operators of the reference, whose instantiations so keep their argument segment and their instruction streams (an empty struct
+// would take a byte of it and move the hidden arguments; profiles/datagen_batched.md holds the disassembly diff), one ItemVec /
+// ItemAmp for the `Items` operators. items_of(tab...) is that one table.
+template <class T> __host__ __device__ inline const T& items_of(const T& t) { return t; }
+
 // What tfl_simulate_step asks of the in-place maccormackOurs advectScalar of a 3-D density (advect_scalar3_sparse.hip, DESIGN.md
 // 3.17): find the bricks of 64 x 4 x 4 cells that hold a word other than +0.0, and run the two passes over the bricks around
 // them only. The buffers belong to the context (tfl_ctx.hpp Scal3SparseState: one set per density field, allocated once).
@@ -180,6 +193,10 @@ void add_buoyancy(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int 
                   const float* density, float sx, float sy, float sz, Fold& f);
 void add_gravity(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags, float fx,
                  float fy, float fz);
+// the same two with per-item strengths (no pair is folded; Usrc != U: the items without the force are copied)
+void add_buoyancy_items(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, const float* Usrc, float* U, const float* flags,
+                        const float* density, const ItemVec& t);
+void add_gravity_items(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags, const ItemVec& t);
 void empty_domain(hipStream_t st, bool is3d, int bnd, int B, int Z, int Y, int X, float* flags);
 void flags_to_occupancy(hipStream_t st, long long numel, const float* flags, float* occ);
 void rectangular_blur(hipStream_t st, bool is3d, int B, int C, int Z, int Y, int X, int rad, const float* src, float* dst,
@@ -224,6 +241,11 @@ void closure_fold(hipStream_t st, const double* loss4, double* sums5, int* guard
 // not possible here, nothing launched, the caller copies Usrc into U and calls again without it)
 bool vorticity_confinement(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags,
                            float strength, float* curl, float* curl_norm, int stages, const float* Usrc, Fold& f);
+
+// the two launches in place with per-item strengths: k_curl and k_confine skip the items without the force (their words of U are
+// not touched, their curl / |curl| planes not written)
+void vorticity_confinement_items(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags,
+                                 const ItemAmp& t, float* curl, float* curl_norm);
 
 // U_out = U_in + confinement(U_in), 3-D, one fused launch without curl arrays (U_out != U_in); false = not supported here
 bool vorticity_confinement_fused_ok(bool is3d, int Z, int Y, int X);   // does the native step use the fused kernel for this grid

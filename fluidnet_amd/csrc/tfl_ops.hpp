@@ -39,6 +39,13 @@ int advectVel(tfl_ctx* c, float dt, const tfl_tensor* U, const tfl_tensor* flags
 int addBuoyancyFrom(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* density,
                     const float gravity[3], float dt, int is3D, const Scope& sc, Ask& ask);
 int addGravity(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const float gravity[3], float dt, int is3D, const Scope& sc);
+// the per-item forms (tfl_addBuoyancyItems ...; include/tfluids_hip.h): whole array only, the scope gives dx
+int addBuoyancyItems(tfl_ctx* c, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags, const tfl_tensor* density,
+                     const float* gravity, const int32_t* on, int n_items, float dt, int is3D, const Scope& sc);
+int addGravityItems(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const float* gravity, const int32_t* on, int n_items,
+                    float dt, int is3D, const Scope& sc);
+int vorticityConfinementItems(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, const float* strength, const int32_t* on,
+                              int n_items, const tfl_tensor* curl, const tfl_tensor* curlNorm, int is3D, const Scope& sc);
 int vorticityConfinement(tfl_ctx* c, const tfl_tensor* U, const tfl_tensor* flags, float strength, const tfl_tensor* centered,
                          const tfl_tensor* curl, const tfl_tensor* curlNorm, const tfl_tensor* force, int is3D, const Scope& sc,
                          Ask& ask);

@@ -70,4 +70,12 @@ inline StepWs step_ws(int B, int Z, int Y, int X, int C, StepProj proj, long lon
   return w;
 }
 
+// The table of the step on batch items (tfl_simulate_step_items): the step's own, region for region -- the items are the batch,
+// and no offset above moves -- with the PCG region sized for the solver that step runs: the batched one's table
+// (tfl_pcg_ws.hpp pcg_batched_ws(B, ...).total: B item blocks and the per-item tables) where the preconditioner batches,
+// batched_floats >= 0, else the sequential solver's as above. Held by tests/step_items_ws_host.cpp.
+inline StepWs step_items_ws(int B, int Z, int Y, int X, int C, StepProj proj, long long pcg_floats, long long batched_floats) {
+  return step_ws(B, Z, Y, X, C, proj, batched_floats >= 0 ? batched_floats : pcg_floats);
+}
+
 }  // namespace tfl

@@ -36,12 +36,17 @@ __device__ __forceinline__ float centred_c(const Dom& d, const float* __restrict
   return 0.5f * (U[a] + U[a + step]);
 }
 
-template <bool IS3D>
+// The per-item form of the two-launch kernels (Tab = one ItemAmp, tfl_host.hpp): the block's item b is block-uniform, so its strength
+// is a scalar load from the argument segment. An item whose bit of `on` is clear has no force: both passes skip it -- its curl
+// planes are not written, its words of U not touched (the per-item form of pass B runs in place only).
+
+template <bool IS3D, class... Tab>
 __global__ __launch_bounds__(256) void k_curl(Dom d, const float* __restrict__ U, float* __restrict__ curl,
-                                              float* __restrict__ cnorm) {
+                                              float* __restrict__ cnorm, Tab... tab) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int j = blockIdx.y * blockDim.y + threadIdx.y;
   int b, k; dom_bk(d, b, k);
+  if constexpr (sizeof...(Tab) != 0) { if (!((items_of(tab...).on >> b) & 1u)) return; }
   if (i >= d.X || j >= d.Y) return;
   const long long cells = d.sc;
   U += b * cells * (IS3D ? 3 : 2); curl += b * cells * 3; cnorm += b * cells;
@@ -77,13 +82,14 @@ __device__ __forceinline__ v3 force_at(const Dom& d, const float* __restrict__ c
              ((g.x * w.y) - (g.y * w.x)) * strength);
 }
 
-template <bool IS3D>
+template <bool IS3D, class... Tab>
 __global__ __launch_bounds__(256) void k_confine(Dom d, float* __restrict__ U, const float* __restrict__ flags,
                                                  const float* __restrict__ curl, const float* __restrict__ cn,
-                                                 float strength) {
+                                                 float strength, Tab... tab) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const int j = blockIdx.y * blockDim.y + threadIdx.y;
   int b, k; dom_bk(d, b, k);
+  if constexpr (sizeof...(Tab) != 0) { const ItemAmp& t = items_of(tab...); if (!((t.on >> b) & 1u)) return; strength = t.s[b]; }
   if (i >= d.X || j >= d.Y) return;
   if (on_border<IS3D>(d, i, j, k)) return;
   const long long cells = d.sc;
@@ -106,13 +112,14 @@ __global__ __launch_bounds__(256) void k_confine(Dom d, float* __restrict__ U, c
 // ---- four x-cells per thread (tfl_vec4.hpp): same per-cell arithmetic, 16-byte accesses -----------------
 // k_curl_v4: 16 row loads per 4 cells instead of 24 dword loads per cell. Tap (i+-1, j+-1, k+-1) of a
 // non-border cell is on the border shell iff its moved coordinate is 0 or N-1 -> contributes 0.
-template <bool IS3D>
+template <bool IS3D, class... Tab>
 __global__ __launch_bounds__(256, TFL_LB_CURL) void k_curl_v4(Dom d, const float* __restrict__ U, float* __restrict__ curl,
-                                                 float* __restrict__ cnorm, BlockOrder ord) {
+                                                 float* __restrict__ cnorm, BlockOrder ord, Tab... tab) {
   int bx_, by_, bz_; block_tile(ord, bx_, by_, bz_);
   const V4Ctx c = v4_ctx(d, bx_);
   const int j = by_ * blockDim.y + threadIdx.y;
   int b, k; dom_bk_of(d, bz_, b, k);
+  if constexpr (sizeof...(Tab) != 0) { if (!((items_of(tab...).on >> b) & 1u)) return; }
   const bool live = c.i0 < d.X && j < d.Y;
   const long long cells = d.sc;
   U += b * cells * (IS3D ? 3 : 2); curl += b * cells * 3; cnorm += b * cells;
@@ -203,10 +210,10 @@ __device__ __forceinline__ void force_row(const Dom& d, float strength, int i0, 
 // k_confine_v4: the force of the thread's own four cells, of the four cells one row down (y-1) and one plane
 // down (z-1) are evaluated in registers from 10 |curl| rows + 7 curl rows; force.x of cell i0-1 comes from the
 // previous lane. U is rewritten in full rows (unchanged cells get their own value back).
-template <bool IS3D>
+template <bool IS3D, class... Tab>
 __global__ __launch_bounds__(256, TFL_LB_CONFINE) void k_confine_v4(Dom d, const float* Usrc, float* U, const float* __restrict__ flags,
                                                     const float* __restrict__ curl, const float* __restrict__ cn,
-                                                    float strength, BcFoldArg folda, BlockOrder ord) {
+                                                    float strength, BcFoldArg folda, BlockOrder ord, Tab... tab) {
   // U = Usrc + confinement force. Usrc == U: the reference's in-place operator; Usrc != U (round 5, tfl_vorticityConfinementFrom
   // on grids below the fused kernel's size): every cell of the window is written, which moves the velocity out of the
   // advection's scratch array for free
@@ -214,6 +221,7 @@ __global__ __launch_bounds__(256, TFL_LB_CONFINE) void k_confine_v4(Dom d, const
   const V4Ctx c = v4_ctx(d, bx_);
   const int j = by_ * blockDim.y + threadIdx.y;
   int b, k; dom_bk_of(d, bz_, b, k);
+  if constexpr (sizeof...(Tab) != 0) { const ItemAmp& t = items_of(tab...); if (!((t.on >> b) & 1u)) return; strength = t.s[b]; }      // (the whole block: b is block-uniform)
   const bool fold_blk = fold_block(folda, (int)(by_ * blockDim.y), (int)(by_ * blockDim.y + blockDim.y - 1), k, k);
   const bool live = c.i0 < d.X && j < d.Y;
   const long long cells = d.sc;
@@ -1121,6 +1129,31 @@ bool vorticity_confinement(hipStream_t st, const Scope& sc, bool is3d, int B, in
     if (pb) { TFL_TIMED("k_confine", st); k_confine<false><<<grd, blk, 0, st>>>(d, U, flags, curl, curl_norm, strength); }
   }
   return true;
+}
+
+void vorticity_confinement_items(hipStream_t st, const Scope& sc, bool is3d, int B, int Z, int Y, int X, float* U, const float* flags,
+                                 const ItemAmp& t, float* curl, float* curl_norm) {
+  const Dom d = make_dom(sc, Z, Y, X);
+  const dim3 blk(64, 4, 1), grd((X + 63) / 64, (Y + 3) / 4, (unsigned)(d.nw * B));
+  const Vec4Launch v = vec4_launch(B, d, {U, flags, curl, curl_norm});
+  if (v.ok) {
+    const BlockOrder ord = make_block_order(v.grd.x, v.grd.y, v.grd.z, is3d && xcd_order_enabled(), xcd_run(v.grd.x, v.grd.y));
+    if (is3d) {
+      { TFL_TIMED("k_curl_items", st); k_curl_v4<true><<<v.grd, v.blk, 0, st>>>(d, U, curl, curl_norm, ord, t); }
+      { TFL_TIMED("k_confine_items", st); k_confine_v4<true><<<v.grd, v.blk, 0, st>>>(d, U, U, flags, curl, curl_norm, 0.0f, no_fold(), ord, t); }
+    } else {
+      { TFL_TIMED("k_curl_items", st); k_curl_v4<false><<<v.grd, v.blk, 0, st>>>(d, U, curl, curl_norm, ord, t); }
+      { TFL_TIMED("k_confine_items", st); k_confine_v4<false><<<v.grd, v.blk, 0, st>>>(d, U, U, flags, curl, curl_norm, 0.0f, no_fold(), ord, t); }
+    }
+    return;
+  }
+  if (is3d) {
+    { TFL_TIMED("k_curl_items", st); k_curl<true><<<grd, blk, 0, st>>>(d, U, curl, curl_norm, t); }
+    { TFL_TIMED("k_confine_items", st); k_confine<true><<<grd, blk, 0, st>>>(d, U, flags, curl, curl_norm, 0.0f, t); }
+  } else {
+    { TFL_TIMED("k_curl_items", st); k_curl<false><<<grd, blk, 0, st>>>(d, U, curl, curl_norm, t); }
+    { TFL_TIMED("k_confine_items", st); k_confine<false><<<grd, blk, 0, st>>>(d, U, flags, curl, curl_norm, 0.0f, t); }
+  }
 }
 
 }  // namespace tfl

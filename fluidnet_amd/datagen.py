@@ -18,7 +18,9 @@ produced as an outputDiv step, put_device of the divergent half, simulate.projec
 one full simulate() per step (tfl_simulate_project's contract).
 
 plan_run is host code without a GPU; its draw order is part of the format of a (seed, run) pair (see plan_run). Runs are
-stepped one at a time, never as batch items: PCG's iteration count is a property of the whole batch.
+stepped one at a time by default; generate(..., batch_runs=R) steps R of them as the items of one batch (simulate_items: per-item
+forces, and with pcgPrecond 'mg' | 'none' one batched PCG solve in which every item keeps the iterations and the bits it has
+alone) and holds the values of the set generated one run at a time.
 """
 import ctypes
 import os
@@ -31,7 +33,7 @@ from . import data as _data
 from . import io as _io
 from . import tfluids
 from ._lib import TfluidsError, tfl_scene_prim
-from .simulate import project, simulate
+from .simulate import project, project_items, simulate, simulate_items
 
 MAX_PRIMS = 32            # tfl_datagen.hpp kSceneMaxPrims
 SPHERE, BOX = 0, 1
@@ -394,8 +396,122 @@ def _write_run(store, is3D, dims, first, n, out_dir, prefix, run):
         _io.saveMantaFile(fn_div, h["pDiv"], h["UDiv"], h["flags"], h["densityDiv"])
 
 
-def generate(gconf, prefix, nruns, seed, out_dir=None, store=None, device="cuda", first_run=0):
+# ---- R runs at a time, as the items of one batch ------------------------------------------------------------------
+MAX_BATCH_RUNS = 32       # TFL_MAX_ITEMS: the per-item forces travel in the kernel arguments (and 32 slots x 2 halves fit one put)
+
+
+def schedule_waves(first_run, nruns, batch_runs, run_wave, div_threshold, keep=None):
+    """The order in which generate(batch_runs=R) works through its runs; host code, no GPU. A pending list of (run, attempt) starts
+    as (first_run + i, 0); a wave is its next <= batch_runs entries; run_wave(wave) -> the max_div of every entry. An entry above
+    div_threshold (None: no filter) appends (run, attempt + 1) to the list -- a retried run lands in a later wave -- and after
+    MAX_ATTEMPTS the serial generator's error is raised. keep(j, run): called behind its wave for every entry j of it that is kept
+    (the disk sink reads the wave's slots before the next wave reuses them).
+    -> (runs kept, report, warnings), each in the order the serial generator produces them: by run, then attempt."""
+    pending = [(int(first_run) + i, 0) for i in range(int(nruns))]
+    report, notes = [], []
+    while pending:
+        wave, pending = pending[:batch_runs], pending[batch_runs:]
+        divs = run_wave(wave)
+        assert len(divs) == len(wave)
+        for j, ((run, attempt), max_div) in enumerate(zip(wave, divs)):
+            kept = div_threshold is None or max_div <= float(div_threshold)
+            report.append(dict(run=run, attempt=attempt, max_div=max_div, kept=kept))
+            if kept:
+                if keep is not None:
+                    keep(j, run)
+                continue
+            if attempt + 1 >= MAX_ATTEMPTS:
+                raise TfluidsError("generate: run %d exceeded the divergence threshold %d times" % (run, MAX_ATTEMPTS))
+            notes.append((run, attempt, "generated run %d (attempt %d) has max(div) = %g above the threshold %g: generating it again"
+                          % (run, attempt, max_div, float(div_threshold))))
+            pending.append((run, attempt + 1))
+    report.sort(key=lambda r: (r["run"], r["attempt"]))
+    return [r["run"] for r in report if r["kept"]], report, [n[2] for n in sorted(notes)]
+
+
+def join_states(states):
+    """B = 1 batches of one shape (init_state) as one [B]-wide batch. A BC pair is the identity (mask 1, value 0) for the items
+    without one and is left out where no item has it."""
+    batch = {k: torch.cat([st[k] for st in states], 0) for k in ("pDiv", "UDiv", "flags", "density", "div")}
+    for bc, mask in (("UBC", "UBCInvMask"), ("densityBC", "densityBCInvMask")):
+        if any(bc in st for st in states):
+            like = next(st[bc] for st in states if bc in st)
+            batch[bc] = torch.cat([st[bc] if bc in st else torch.zeros_like(like) for st in states], 0)
+            batch[mask] = torch.cat([st[mask] if mask in st else torch.ones_like(like) for st in states], 0)
+    return batch
+
+
+def init_wave(plans, device):
+    """The S_0 of every plan (init_state, one run at a time as in the serial generator: its cost, the host read included, is per
+    run) joined into one batch, and the forces of every item. -> (batch, mconf, item_forces); mconf's shared fields (dt, the
+    method, the strength, maxIter, pcgPrecond) are equal over the plans by construction."""
+    batch = join_states([init_state(p, device) for p in plans])
+    mconfs = [mconf_of(p) for p in plans]
+    shared = ("dt", "advectionMethod", "maccormackStrength", "simMethod", "maxIter", "pcgPrecond")
+    assert all(m[k] == mconfs[0][k] for m in mconfs for k in shared)
+    forces = [{k: m[k] for k in ("gravity", "buoyancyScale", "gravityScale", "vorticityConfinementAmp")} for m in mconfs]
+    return batch, mconfs[0], forces
+
+
+def wave_frames(plans, gconf, store, first_slots, device):
+    """run_frames for a wave: the runs of `plans` as the items of one batch, item j into slots [first_slots[j], + frames). Per
+    step an outputDiv items step and project_items; around a saved step ONE put per half for all items. -> frames written per run."""
+    batch, mconf, forces = init_wave(plans, device)
+    every, n = int(gconf["saveEvery"]), 0
+    for k in range(int(gconf["steps"])):
+        save = k % every == 0
+        simulate_items(None, mconf, batch, forces, outputDiv=True)
+        if save:
+            store.put_device([f + n for f in first_slots], dict(pDiv=batch["pDiv"], UDiv=batch["UDiv"], flags=batch["flags"],
+                                                                densityDiv=batch["density"]))
+        project_items(None, mconf, batch, forces)
+        if save:
+            store.put_device([f + n for f in first_slots], dict(pTarget=batch["pDiv"], UTarget=batch["UDiv"],
+                                                                densityTarget=batch["density"]))
+            n += 1
+    return n
+
+
+def _generate_waves(gconf, prefix, nruns, seed, out_dir, store, device, first_run, batch_runs):
+    is3D, dims = bool(gconf["is3D"]), tuple(gconf["dims"])
+    frames = len(saved_steps(gconf))
+    own = store is None
+    if own:
+        store = _data.FrameStore(device, is3D, *dims, batch_runs * frames, batch_runs * frames)
+    elif store.is3D != is3D or tuple(store.dims) != dims or store.capacity < nruns * frames:
+        raise TfluidsError("generate: the store (%s, %d slots) does not hold %d runs of %d frames of %s"
+                           % (store.dims, store.capacity, nruns, frames, dims))
+    firsts = {}
+
+    def run_wave(wave):
+        plans = [plan_run(gconf, seed, run, attempt) for run, attempt in wave]
+        firsts.clear()
+        firsts.update({j: (j if own else run - first_run) * frames for j, (run, _) in enumerate(wave)})
+        n = wave_frames(plans, gconf, store, [firsts[j] for j in range(len(wave))], store.device)
+        assert n == frames
+        return [_data.max_target_divergence(store, is3D, dims, firsts[j], n) for j in range(len(wave))]
+
+    def keep(j, run):
+        if out_dir is not None:
+            _write_run(store, is3D, dims, firsts[j], frames, out_dir, prefix, run)
+
+    try:
+        kept, report, notes = schedule_waves(first_run, nruns, batch_runs, run_wave, gconf.get("divThreshold"), keep)
+        for note in notes:
+            warnings.warn(note)
+        runs = [("%06d" % run, frames) for run in kept]
+        dataset = None if own else _data.DataBinary.from_store(store, runs, is3D, dims)
+    finally:
+        if own:
+            store.close()
+    return dict(runs=runs, report=report, data=dataset)
+
+
+def generate(gconf, prefix, nruns, seed, out_dir=None, store=None, device="cuda", first_run=0, batch_runs=1):
     """nruns runs (numbers first_run ...) of gconf's scenes under `seed`, saved_steps(gconf) frame pairs each.
+    batch_runs = R > 1 (at most MAX_BATCH_RUNS): R runs are stepped at a time as the items of one batch (schedule_waves,
+    wave_frames) -- the same frames in the same slots and files, the same runs and report as one run at a time, which stays the
+    default; it pays where a step is launch-bound (profiles/datagen_batched.md). The scratch store then holds R runs.
     store: a data.FrameStore of the right shape with room for nruns * frames records (None with out_dir: a scratch store of ONE
     run is used); run i's frames go to slots [i * frames, (i + 1) * frames), straight from the simulation's tensors.
     out_dir: <dataDir>/<dataset>; the frames are also written as <out_dir>/<prefix>/<run %06d>/<frame %06d>[_divergent].bin.
@@ -404,6 +520,11 @@ def generate(gconf, prefix, nruns, seed, out_dir=None, store=None, device="cuda"
     -> {"runs": [(name, frames)], "report": [{run, attempt, max_div, kept}], "data": DataBinary.from_store(...) or None}"""
     if out_dir is None and store is None:
         raise TfluidsError("generate: neither a store nor an out_dir to write to")
+    batch_runs = int(batch_runs)
+    if batch_runs < 1 or batch_runs > MAX_BATCH_RUNS:
+        raise TfluidsError("generate: batch_runs = %d, 1 to %d runs are stepped at a time" % (batch_runs, MAX_BATCH_RUNS))
+    if batch_runs > 1:
+        return _generate_waves(gconf, prefix, nruns, seed, out_dir, store, device, first_run, batch_runs)
     is3D, dims = bool(gconf["is3D"]), tuple(gconf["dims"])
     frames = len(saved_steps(gconf))
     own = store is None

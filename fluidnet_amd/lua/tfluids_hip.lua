@@ -90,6 +90,13 @@ int tfl_addBuoyancyFrom(tfl_ctx* ctx, const tfl_tensor* USrc, const tfl_tensor* 
                         const tfl_tensor* density, const float gravity[3], float dt, int is3D);
 int tfl_addGravity(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
                    const float gravity[3], float dt, int is3D, float* forceTmp);
+int tfl_addBuoyancyItems(tfl_ctx* ctx, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags,
+                         const tfl_tensor* density, const float* gravity, const int32_t* on, int32_t n_items, float dt, int is3D);
+int tfl_addGravityItems(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags, const float* gravity, const int32_t* on,
+                        int32_t n_items, float dt, int is3D);
+int tfl_vorticityConfinementItems(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags, const float* strength,
+                                  const int32_t* on, int32_t n_items, const tfl_tensor* curl, const tfl_tensor* curlNorm,
+                                  int is3D);
 int tfl_emptyDomain(tfl_ctx* ctx, const tfl_tensor* flags, int is3D, int bnd);
 int tfl_flagsToOccupancy(tfl_ctx* ctx, const tfl_tensor* flags, const tfl_tensor* occupancy);
 int tfl_rectangularBlur(tfl_ctx* ctx, const tfl_tensor* src, int blurRad, int is3D, const tfl_tensor* dst,
@@ -257,6 +264,17 @@ int tfl_simulate_step(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_
                       int64_t workspace_floats);
 int tfl_simulate_project(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state, float* workspace,
                          int64_t workspace_floats);
+typedef struct tfl_sim_item {
+  float gravity[3];
+  double buoyancyScale;
+  double gravityScale;
+  double vorticityConfinementAmp;
+} tfl_sim_item;
+int64_t tfl_simulate_items_workspace_floats(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state);
+int tfl_simulate_step_items(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_item* items, int32_t n_items,
+                            const tfl_sim_state* state, float* workspace, int64_t workspace_floats);
+int tfl_simulate_project_items(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_item* items, int32_t n_items,
+                               const tfl_sim_state* state, float* workspace, int64_t workspace_floats);
 int tfl_packPlanes(tfl_ctx* ctx, int n, const tfl_tensor* const* fields, int zlo, int zhi, float* buf,
                    int unpack);
 int tfl_set_z_window(tfl_ctx* ctx, int a0, int a1, int b0, int b1);

@@ -513,6 +513,52 @@ def project(conf, mconf, batch, model=None):
     del keep
 
 
+def _item_array(mconf, item_forces):
+    """tfl_sim_item[n] of item_forces (None: NULL, every item takes mconf's forces): dicts with any of gravity, buoyancyScale,
+    gravityScale, vorticityConfinementAmp; a missing key takes mconf's value."""
+    from ._lib import tfl_sim_item
+    if item_forces is None:
+        return None
+    arr = (tfl_sim_item * max(len(item_forces), 1))()      # (a count that is not the batch's is refused by the library, by name)
+    for b, f in enumerate(item_forces):
+        unknown = set(f) - {"gravity", "buoyancyScale", "gravityScale", "vorticityConfinementAmp"}
+        if unknown:
+            raise TfluidsError("item_forces[%d]: unknown key(s) %s" % (b, sorted(unknown)))
+        m = dict(mconf, **f)
+        for i, v in enumerate(_gravity(m)):
+            arr[b].gravity[i] = v
+        arr[b].buoyancyScale = float(m.get("buoyancyScale", 0) or 0)
+        arr[b].gravityScale = float(m.get("gravityScale", 0) or 0)
+        arr[b].vorticityConfinementAmp = float(m.get("vorticityConfinementAmp", 0) or 0)
+    return arr
+
+
+def _items_call(entry, mconf, batch, item_forces, outputDiv):
+    U = batch["UDiv"]
+    lib, ctx = tfluids._context(U)
+    prm, st, keep = _native_args(lib, ctx, mconf, batch, None, outputDiv)
+    n = int(U.size(0))
+    items = _item_array(mconf, item_forces)
+    nws = int(lib.tfl_simulate_items_workspace_floats(ctx, ctypes.byref(prm), ctypes.byref(st)))
+    ws = tfluids.getTempStorage(U, [(max(nws, 1),)])[0]
+    tfluids._call(lib, ctx, getattr(lib, entry)(ctx, ctypes.byref(prm), items, n if item_forces is None else len(item_forces), ctypes.byref(st),
+                                                ctypes.c_void_p(ws.data_ptr()), nws))
+    del keep
+
+
+def simulate_items(conf, mconf, batch, item_forces, outputDiv=False):
+    """One step of a batch whose items have forces of their own (tfl_simulate_step_items): item b ends with the
+    values simulate_native gives a batch holding item b alone, under mconf with item_forces[b]'s gravity / buoyancyScale /
+    gravityScale / vorticityConfinementAmp (missing keys: mconf's; item_forces None: mconf's forces for every item). simMethod
+    'pcg' | 'jacobi'; with pcgPrecond 'mg' | 'none' all items are solved in the launches of one."""
+    _items_call("tfl_simulate_step_items", mconf, batch, item_forces, outputDiv)
+
+
+def project_items(conf, mconf, batch, item_forces):
+    """project() of a batch stepped with simulate_items(..., outputDiv=True): together the values of one simulate_items()."""
+    _items_call("tfl_simulate_project_items", mconf, batch, item_forces, False)
+
+
 class GraphedSimulate:
     """simulate() captured once into a HIP graph and replayed: one host call per step instead of ~25
     kernel launches + Python dispatch. The reference's 2-D path is launch-bound (~70

@@ -386,6 +386,58 @@ def addGravity(U, flags, gravity, dt):
                                        int(is3D), None))
 
 
+def _item_tables(n, rows, width, on, name):
+    """(float array [n * width], int32 array [n] or None) of a per-item table for the `Items` operators"""
+    _check(len(rows) == n, "%s: one entry per batch item (%d given, the batch holds %d)" % (name, len(rows), n))
+    flat = []
+    for r in rows:
+        r = [r] if width == 1 else (r.tolist() if torch.is_tensor(r) else list(r))
+        _check(len(r) == width, "%s: every entry holds %d number(s)" % (name, width))
+        flat += [float(v) for v in r]
+    arr = (ctypes.c_float * max(len(flat), 1))(*flat)
+    if on is None:
+        return arr, None
+    _check(len(on) == n, "%s: `on` holds one word per batch item" % name)
+    return arr, (ctypes.c_int32 * max(n, 1))(*[int(bool(v)) for v in on])
+
+
+def addBuoyancyItems(U, flags, density, gravities, dt, on=None, USrc=None):
+    """addBuoyancy with a gravity vector PER BATCH ITEM, in one launch (tfl_addBuoyancyItems; not in the reference): item b gets
+    what addBuoyancy gives it alone with gravities[b]. on: one truth value per item (None: all); an item that is off is not
+    touched, bit for bit -- or, with USrc (another tensor than U), copied like every other cell U = USrc + buoyancy writes."""
+    _, _, _, _, is3D = _dims(U, flags)
+    _check(density.dim() == 5 and density.shape == flags.shape, "Size mismatch")
+    _check(density.is_contiguous(), "Input is not contiguous")
+    _check(isinstance(dt, (int, float)), "time step must be a number")
+    g, o = _item_tables(len(gravities), gravities, 3, on, "addBuoyancyItems")
+    lib, ctx = _context(U)
+    src = None
+    if USrc is not None and USrc.data_ptr() != U.data_ptr():
+        _check(USrc.shape == U.shape and USrc.is_contiguous(), "Size mismatch")
+        src = _tt(USrc)
+    _call(lib, ctx, lib.tfl_addBuoyancyItems(ctx, src, _tt(U), _tt(flags), _tt(density), g, o, len(gravities), float(dt), int(is3D)))
+
+
+def addGravityItems(U, flags, gravities, dt, on=None):
+    """addGravity with a gravity vector per batch item, in one launch (tfl_addGravityItems); an item that is off is not touched."""
+    _, _, _, _, is3D = _dims(U, flags)
+    _check(isinstance(dt, (int, float)), "time step must be a number")
+    g, o = _item_tables(len(gravities), gravities, 3, on, "addGravityItems")
+    lib, ctx = _context(U)
+    _call(lib, ctx, lib.tfl_addGravityItems(ctx, _tt(U), _tt(flags), g, o, len(gravities), float(dt), int(is3D)))
+
+
+def vorticityConfinementItems(U, flags, strengths, on=None):
+    """vorticityConfinement with a strength per batch item, in its two launches (tfl_vorticityConfinementItems); an item that is
+    off is skipped by both and not touched."""
+    bsz, d, h, w, is3D = _dims(U, flags)
+    st, o = _item_tables(len(strengths), strengths, 1, on, "vorticityConfinementItems")
+    curl, curlNorm = getTempStorage(U, [(bsz, 3, d, h, w), (bsz, 1, d, h, w)])
+    lib, ctx = _context(U)
+    _call(lib, ctx, lib.tfl_vorticityConfinementItems(ctx, _tt(U), _tt(flags), st, o, len(strengths), _tt(curl), _tt(curlNorm),
+                                                      int(is3D)))
+
+
 def emptyDomain(flags, is3D, bnd=None):
     """init.lua:545-553."""
     bnd = bnd or 1

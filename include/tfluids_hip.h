@@ -232,6 +232,26 @@ int tfl_addBuoyancyFrom(tfl_ctx* ctx, const tfl_tensor* USrc, const tfl_tensor* 
 int tfl_addGravity(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags,
                    const float gravity[3], float dt, int is3D, float* forceTmp);
 
+/* The three force operators with PER-ITEM strengths (not in the reference; what tfl_simulate_step_items runs): batch item b gets
+ * the force of the single-item operator called on item b alone with the b-th entry, in ONE launch per operator for the whole
+ * batch (vorticityConfinement: its two). n_items must equal flags->B and be at most TFL_MAX_ITEMS: the strengths travel by value
+ * in the kernel arguments. on: n_items words, non-zero = the item has the force (NULL: every item has). An item without it is
+ * not touched, bit for bit (the operator is not run with a zero strength: x + 0 * f would turn -0 into +0 and a NaN force into
+ * NaN) -- with one exception: tfl_addBuoyancyItems with USrc != U (USrc NULL or == U: in place) writes every cell of U like
+ * tfl_addBuoyancyFrom, and copies such an item. gravity: n_items x 3 floats in HOST memory, each row what tfl_addBuoyancy /
+ * tfl_addGravity take; strength: n_items floats in host memory, each what tfl_vorticityConfinement takes. The per-cell arithmetic
+ * is the single-item kernels', operation for operation. tfl_vorticityConfinementItems always runs the two launches (curl, then the
+ * force, which equal the fused forms bit for bit); curl (3 channels) / curlNorm are scratch of the flags' size. A z-window or
+ * stage mask set on the context is refused by name. */
+#define TFL_MAX_ITEMS 32
+int tfl_addBuoyancyItems(tfl_ctx* ctx, const tfl_tensor* USrc, const tfl_tensor* U, const tfl_tensor* flags,
+                         const tfl_tensor* density, const float* gravity, const int32_t* on, int32_t n_items, float dt, int is3D);
+int tfl_addGravityItems(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags, const float* gravity, const int32_t* on,
+                        int32_t n_items, float dt, int is3D);
+int tfl_vorticityConfinementItems(tfl_ctx* ctx, const tfl_tensor* U, const tfl_tensor* flags, const float* strength,
+                                  const int32_t* on, int32_t n_items, const tfl_tensor* curl, const tfl_tensor* curlNorm,
+                                  int is3D);
+
 /* init.lua:552 -> generic/tfluids.cc:136-167 | generic/tfluids.cu:314-353. */
 int tfl_emptyDomain(tfl_ctx* ctx, const tfl_tensor* flags, int is3D, int bnd);
 
@@ -707,6 +727,32 @@ int tfl_simulate_step(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_
  * tfl_simulate_step itself is not changed by this entry. */
 int tfl_simulate_project(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state, float* workspace,
                          int64_t workspace_floats);
+
+/* The step on batch items with forces of their own (not in the reference): what the data-set generator steps R
+ * runs at a time with. Contract: item b of the state ends with the VALUES of tfl_simulate_step (or of an outputDiv step followed
+ * by tfl_simulate_project) on a B = 1 state that holds item b alone -- its slices of p, U, flags, density and of the BC tensors --
+ * with params whose four force fields are items[b]'s. items == NULL: every item takes params' own forces. Values, not bits, in
+ * one respect: the sign of a zero (a dense BC pair, or a pair folded into a producing kernel, computes x * 1 + 0 on the cells of
+ * an item whose pair is the identity, which turns -0 into +0; DESIGN.md 3.25 lists the paths).
+ * simMethod "pcg" | "jacobi"; "convnet" is refused by name with TFL_EUNSUPPORTED. pcgPrecond "mg" | "none" solve all items in the
+ * launches of one (tfl_solveLinearSystemPCGBatched, tol 1e-4); "ic0" | "ilu0" | NULL run tfl_solveLinearSystemPCG, serial over the
+ * items. tfl_pcg_last_iterations afterwards: the sum over the items. Every advection method, 0..8 density channels and BC plans
+ * over [B]-wide tensors are taken as in tfl_simulate_step. n_items must equal state->flags->B and be at most TFL_MAX_ITEMS.
+ * Refused by name before anything is enqueued: a wrong n_items, more than TFL_MAX_ITEMS items, a workspace shorter than
+ * tfl_simulate_items_workspace_floats or not 16-byte aligned, "convnet", an unknown simMethod / pcgPrecond, a force field that is
+ * not finite, a z-window or stage mask set on the context. tfl_simulate_project_items is the projection phase alone, as
+ * tfl_simulate_project is of tfl_simulate_step: an outputDiv items step + project items = one items step. */
+typedef struct tfl_sim_item {        /* the force fields of tfl_sim_params, for one batch item */
+  float gravity[3];
+  double buoyancyScale;
+  double gravityScale;
+  double vorticityConfinementAmp;
+} tfl_sim_item;
+int64_t tfl_simulate_items_workspace_floats(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_state* state);
+int tfl_simulate_step_items(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_item* items, int32_t n_items,
+                            const tfl_sim_state* state, float* workspace, int64_t workspace_floats);
+int tfl_simulate_project_items(tfl_ctx* ctx, const tfl_sim_params* params, const tfl_sim_item* items, int32_t n_items,
+                               const tfl_sim_state* state, float* workspace, int64_t workspace_floats);
 
 /* ---- z-slab decomposition across the GPUs of a node (BASELINE config 5; no counterpart in the reference, which is
  * single-GPU). A rank holds planes [z_first, z_first + Zlocal) of a z_total-deep grid: the planes it OWNS,

@@ -13,7 +13,12 @@ Protocol of profiles/data_gather.md: one process, the forms alternated round by 
 device events after a synchronise, FIVE rounds, the median of the rounds, min .. max beside it. Nothing is asserted but that the
 forms agree bit for bit.
 --pcgPrecond names the preconditioner of every PCG solve (default 'ic0'; profiles/pcg_mg.md has the 'mg' rows).
-usage: python tools/datagen_bench.py [--out profiles/datagen.md] [--calls 20] [--pcgPrecond ic0]"""
+--batchRuns R[,R...] measures the generator's batched form instead (generate(batch_runs=R)) and prints one JSON
+line per shape: per R the time of one generator step of a wave of R runs (the plans 0 .. R - 1 of the seed, after 8 steps; R = 1:
+the serial generator's step, averaged over the plans 0 .. 3) per run, and the runs per minute of the paper's recipe by the wall
+clock (generate() of max(R, 4) runs, scene set-up and divergence check included). Nothing is written: profiles/datagen_batched.md
+is put together from these lines and those of the same tool at the parent commit, taken in the same session.
+usage: python tools/datagen_bench.py [--out profiles/datagen.md] [--calls 20] [--pcgPrecond ic0] [--batchRuns 1,4,16]"""
 import argparse
 import json
 import os
@@ -136,6 +141,73 @@ def measure(is3D, dims, calls, precond="ic0"):
                           buoyancyScale=plan["buoyancyScale"], vorticityConfinementAmp=plan["vorticityConfinementAmp"]))
 
 
+def measure_batched(is3D, dims, calls, precond, batch_runs, steps=256):
+    """per R: us of one generator step per run (median of ROUNDS, min .. max), and runs per minute of generate()"""
+    g = datagen.default_gconf(is3D, dims, pcgPrecond=precond, divThreshold=None, steps=steps)
+    frames = len(datagen.saved_steps(g))
+    out = dict(shape="%s %s" % ("3-D" if is3D else "2-D", "x".join(str(d) for d in dims)), pcgPrecond=precond, calls_per_round=calls, R={})
+    for R in batch_runs:
+        plans = [datagen.plan_run(g, SEED, r) for r in range(max(R, 4) if R == 1 else R)]
+        store = FrameStore(DEV, is3D, *dims, max(R, 4), max(R, 4))
+        try:
+            if R == 1:
+                runs = []
+                for plan in plans:
+                    mconf, batch = datagen.mconf_of(plan), datagen.init_state(plan, DEV)
+                    for _ in range(8):
+                        simulate(None, mconf, batch, None)
+                    runs.append((mconf, batch, {k: batch[k].clone() for k in ("pDiv", "UDiv", "density")}))
+
+                def restore():
+                    for _, batch, snap in runs:
+                        for k, v in snap.items():
+                            batch[k].copy_(v)
+
+                def step():      # one generator step of each of the four runs
+                    for mconf, batch, _ in runs:
+                        simulate(None, mconf, batch, None, outputDiv=True)
+                        store.put_device([0], dict(pDiv=batch["pDiv"], UDiv=batch["UDiv"], flags=batch["flags"], densityDiv=batch["density"]))
+                        project(None, mconf, batch)
+                        store.put_device([0], dict(pTarget=batch["pDiv"], UTarget=batch["UDiv"], densityTarget=batch["density"]))
+                per = len(runs)
+            else:
+                from fluidnet_amd.simulate import project_items, simulate_items
+                batch, mconf, forces = datagen.init_wave(plans, DEV)
+                for _ in range(8):
+                    simulate_items(None, mconf, batch, forces)
+                snap = {k: batch[k].clone() for k in ("pDiv", "UDiv", "density")}
+                slots = list(range(R))
+
+                def restore():
+                    for k, v in snap.items():
+                        batch[k].copy_(v)
+
+                def step():
+                    simulate_items(None, mconf, batch, forces, outputDiv=True)
+                    store.put_device(slots, dict(pDiv=batch["pDiv"], UDiv=batch["UDiv"], flags=batch["flags"], densityDiv=batch["density"]))
+                    project_items(None, mconf, batch, forces)
+                    store.put_device(slots, dict(pTarget=batch["pDiv"], UTarget=batch["UDiv"], densityTarget=batch["density"]))
+                per = R
+            t = _timed([("step", step)], max(calls // 2, 4), before=restore)["step"]
+        finally:
+            torch.cuda.synchronize()
+            store.close()
+        nruns = max(R, 4)
+        big = FrameStore(DEV, is3D, *dims, nruns * frames, nruns * frames)
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = datagen.generate(g, "tr", nruns, SEED, store=big, device=DEV, **({} if R == 1 else dict(batch_runs=R)))
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+        finally:
+            big.close()
+        out["R"][str(R)] = dict(step_us_per_run=float(np.median(t)) / per, step_us_per_run_min_max=[min(t) / per, max(t) / per],
+                                wave_step_us=float(np.median(t)), runs=nruns, seconds=wall, runs_per_minute=60.0 * nruns / wall,
+                                worst_max_div=max(r["max_div"] for r in res["report"]))
+    return out
+
+
 def report(results, path, oracle_lines, precond="ic0"):
     f3 = lambda r, t, k: "%.1f (%.1f .. %.1f)" % (r[t][k], r[t + "_min_max"][k][0], r[t + "_min_max"][k][1])
     lines = ["# The data-set generator (tools/datagen_bench.py)", "",
@@ -203,7 +275,15 @@ def main():
     ap.add_argument("--out", default=None, help="default profiles/datagen.md with 'ic0'; required with another preconditioner")
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--pcgPrecond", default="ic0", choices=("none", "ilu0", "ic0", "mg"))
+    ap.add_argument("--batchRuns", default=None, help="R[,R...]: measure generate(batch_runs=R) instead (1 = the serial generator); prints JSON lines")
+    ap.add_argument("--steps", type=int, default=256, help="with --batchRuns: steps per run of the wall-clock figure")
     a = ap.parse_args()
+    if a.batchRuns is not None:
+        if not torch.cuda.is_available():
+            raise SystemExit("datagen_bench needs an MI355X: nothing is measured without one")
+        for is3D, dims in ((False, (1, 128, 128)), (True, (64, 64, 64))):
+            print(json.dumps(measure_batched(is3D, dims, a.calls, a.pcgPrecond, [int(v) for v in a.batchRuns.split(",")], a.steps)), flush=True)
+        return
     if a.out is None:
         if a.pcgPrecond != "ic0":
             ap.error("--out is required with --pcgPrecond %s: profiles/datagen.md is the record of the 'ic0' run" % a.pcgPrecond)
