@@ -8,7 +8,7 @@ NNNNNN_divergent.bin (manta's scenes/_trainingData.py): both sets are loaded onc
 model so far; FluidNetModel.from_npz loads it) and <out>_log.txt.
 
   python examples/train.py --dataDir data/datasets --dataset output_current_model_sphere --out /tmp/fit/model \\
-        [--modelType default|yang] [--epochs 10] [--batchSize 16] [--resume /tmp/fit/model_lastEpoch.npz]
+        [--modelType default|yang|tog] [--epochs 10] [--batchSize 16] [--resume /tmp/fit/model_lastEpoch.npz]
 """
 import argparse
 import os
@@ -39,7 +39,7 @@ def main():
     ap.add_argument("--dataDir", required=True, help="holds <dataset>/{tr,te}/...; examples/gen_data.py generates such a set")
     ap.add_argument("--dataset", required=True)
     ap.add_argument("--out", required=True, help="conf.modelDirname: the prefix of the files written")
-    ap.add_argument("--modelType", default="default", choices=("default", "yang"))
+    ap.add_argument("--modelType", default="default", choices=("default", "yang", "tog"))
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--batchSize", type=int, default=16)
     ap.add_argument("--ignoreFrames", type=int, default=0)

@@ -176,6 +176,7 @@ SIGNATURES = {
                                     _c.c_void_p, _c.c_double, _T, _T, _c.c_int, _c.c_float, _c.c_float]),
     "tfl_model_set_weights": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.POINTER(_c.POINTER(_c.c_float)),
                                          _c.POINTER(_c.POINTER(_c.c_float))]),
+    "tfl_model_enable_multires_training": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
     "tfl_model_tape_floats": (_c.c_int64, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "tfl_model_forward_train": (_c.c_int, [_c.c_void_p, _c.c_void_p, _T, _T, _T, _T, _T, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                            _c.c_int64]),

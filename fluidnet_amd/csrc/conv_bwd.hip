@@ -31,6 +31,8 @@ struct WgArgs {
   int ch, tt, S, ntx, nty;
   long long tiles;
   int dil;              // tap spacing (a dilated bank's module; read by the DIL instantiations only)
+  int up, gch;          // (the UP instantiations only) an upsample layer's inner convolution: g and y have gch planes at up times
+                        // the resolution, column cv = sub * gch + co reads plane co at up_fine_cell(sub, z, y, x); cout = subs * gch
 };
 
 // act'(y) from the saved output: ReLU y > 0, ReLU6 0 < y < 6, sigmoid y (1 - y)
@@ -41,7 +43,9 @@ __device__ __forceinline__ float act_grad(float g, float y, int act) {
 }
 
 // DIL = false: tap spacing 1 as a constant -- the kernel of the linear models, unchanged by the dilated form
-template <int CB, bool DIL>
+// UP = true: the strided read of g and y of an upsample layer: the mask is taken behind the shuffle, the masked
+// value written back to the fine cell it was read from (every fine cell belongs to one (cell, sub-position): written once)
+template <int CB, bool DIL, bool UP = false>
 __global__ __launch_bounds__(kWgThreads) void k_conv_wgrad(WgArgs a) {
   extern __shared__ float lds[];
   const int tid = threadIdx.x;
@@ -52,7 +56,10 @@ __global__ __launch_bounds__(kWgThreads) void k_conv_wgrad(WgArgs a) {
   const long long cells = (long long)a.Z * a.Y * a.X;
   const int M = a.cin * a.taps;
   const int vx = tid % kWgTX, vy = tid / kWgTX;      // the voxel this thread stages g for
-  for (int co0 = 0; co0 < a.cout; co0 += CB)
+  for (int co0 = 0; co0 < a.cout; co0 += CB) {
+    const int sub = UP ? co0 / a.gch : 0, cp0 = UP ? co0 - sub * a.gch : co0;      // (sub-position, first plane of g)
+    const int gch = UP ? a.gch : a.cout;
+    const long long gcells = UP ? cells * (a.cout / a.gch) : cells;
     for (int ci0 = 0; ci0 < a.cin; ci0 += a.ch)
       for (int t0 = 0; t0 < a.taps; t0 += a.tt) {
         const WgChunk ck = wg_chunk(a.ch, a.tt, a.cin, a.taps, ci0, t0);      // (its first chunk carries the bias row and masks g)
@@ -77,15 +84,15 @@ __global__ __launch_bounds__(kWgThreads) void k_conv_wgrad(WgArgs a) {
           {
             const int gx = x0 + vx, gy = y0 + vy;
             const bool ok = gx < a.X && gy < a.Y;
-            const long long o = ((long long)z * a.Y + gy) * a.X + gx;
+            const long long o = UP ? (ok ? up_fine_cell(a.is3d != 0, a.up, sub, z, gy, gx, a.Y, a.X) : 0) : ((long long)z * a.Y + gy) * a.X + gx;
 #pragma unroll
             for (int c = 0; c < CB; c++) {
               float v = 0.0f;
               if (ok) {
-                float* gp = a.g + ((long long)b * a.cout + co0 + c) * cells + o;
+                float* gp = a.g + ((long long)b * gch + cp0 + c) * gcells + o;
                 v = *gp;
                 if (mask_now) {
-                  v = act_grad(v, a.y[((long long)b * a.ych + co0 + c) * cells + o], a.act);
+                  v = act_grad(v, a.y[((long long)b * a.ych + cp0 + c) * gcells + o], a.act);
                   if (a.wb) *gp = v;
                 }
               }
@@ -128,13 +135,14 @@ __global__ __launch_bounds__(kWgThreads) void k_conv_wgrad(WgArgs a) {
           for (int c = 0; c < CB; c++) a.partials[wg_partial_slot((int)blockIdx.x, M, t.row, a.cout, co0 + c)] = acc64[c];
         }
       }
+  }
 }
 
 // The blocks' partials of 32 (row, co) results per block of 32 x 8 threads, in fp64 and in a fixed order: lane y adds the
 // partials y, y + 8, ... in ascending order, lane 0 then adds the eight lanes in order; then the cudnn layout.
 __global__ __launch_bounds__(256) void k_conv_wgrad_finish(const double* __restrict__ partials, int P, int M, int cout, int taps, int cin,
                                                            int cin_ref, int cout_ref, int skip_in, float* __restrict__ gw,
-                                                           float* __restrict__ gb, int accumulate, int join_c, int join_p) {
+                                                           float* __restrict__ gb, int accumulate, int join_c, int join_p, int subs) {
   __shared__ double sh[8][33];
   const int total = (M + 1) * cout;
   const int o = blockIdx.x * 32 + threadIdx.x;
@@ -148,7 +156,11 @@ __global__ __launch_bounds__(256) void k_conv_wgrad_finish(const double* __restr
   const int row = o / cout, co = o - row * cout;
   const float f = (float)s;
   float* dst;
-  if (row == M) {
+  if (subs > 1) {      // an upsample layer's inner convolution: cout = subs * its padded output channels
+    const long long i = wg_cudnn_index_up(row == M ? -1 : row, co, cout / subs, subs, taps, cin, cin_ref, cout_ref);
+    if (i < 0) return;
+    dst = (row == M ? gb : gw) + i;
+  } else if (row == M) {
     if (co >= cout_ref) return;
     dst = gb + co;
   } else {
@@ -206,12 +218,18 @@ bool conv_wgrad(hipStream_t st, bool is3d, const WgPlan& p, int B, int Z, int Y,
   a.Z = Z; a.Y = Y; a.X = X; a.cin = cin; a.cout = cout; a.k = k; a.taps = p.taps; a.ych = ych; a.act = y ? act : 0; a.wb = wb ? 1 : 0;
   a.is3d = is3d ? 1 : 0;
   a.dil = p.dil;
+  a.up = p.up; a.gch = cout;
+  if (p.up > 1) {
+    if (p.dil > 1 || p.vcout != cout * p.subs || cout % p.cb) return false;
+    a.cout = p.vcout;
+  }
   a.ch = p.ch; a.tt = p.tt; a.S = p.S; a.ntx = (X + kWgTX - 1) / kWgTX; a.nty = (Y + kWgTY - 1) / kWgTY; a.tiles = p.tiles;
   const size_t shmem = sizeof(float) * (size_t)p.lds_floats;
   TFL_TIMED("k_conv_wgrad", st);
 #define TFL_WG(N)                                                                                  \
   case N:                                                                                          \
-    if (p.dil > 1) k_conv_wgrad<N, true><<<p.nblocks, kWgThreads, shmem, st>>>(a);                 \
+    if (p.up > 1) k_conv_wgrad<N, false, true><<<p.nblocks, kWgThreads, shmem, st>>>(a);           \
+    else if (p.dil > 1) k_conv_wgrad<N, true><<<p.nblocks, kWgThreads, shmem, st>>>(a);            \
     else k_conv_wgrad<N, false><<<p.nblocks, kWgThreads, shmem, st>>>(a);                          \
     return true;
   switch (p.cb) {
@@ -224,9 +242,10 @@ bool conv_wgrad(hipStream_t st, bool is3d, const WgPlan& p, int B, int Z, int Y,
 void conv_wgrad_finish(hipStream_t st, const WgPlan& p, int cin, int cout, int cin_ref, int cout_ref, int skip_in, const double* partials,
                        float* gw, float* gb, int accumulate, int join_c, int join_p) {
   const int M = cin * p.taps;
+  if (p.up > 1) cout = p.vcout;
   TFL_TIMED("k_conv_wgrad_finish", st);
   k_conv_wgrad_finish<<<((M + 1) * cout + 31) / 32, dim3(32, 8), 0, st>>>(partials, p.nblocks, M, cout, p.taps, cin, cin_ref, cout_ref,
-                                                                        skip_in, gw, gb, accumulate, join_c, join_p);
+                                                                        skip_in, gw, gb, accumulate, join_c, join_p, p.up > 1 ? p.subs : 1);
 }
 
 // ---- the fixed linear maps of a banked model, backwards: streaming kernels, every output element written once

@@ -78,6 +78,24 @@ StageTable stage_table(int nst, int banks = 1, int split = 0, int join = 0) {
 // [cout*S] -> [sub][cout_p] (tfl_train.hpp relay_layer; the padding holds zeros), uploaded into L -- at creation, and again by
 // tfl_model_set_weights into the same buffers. transposed: also the data-gradient form L.wt (every layer of a model
 // tfl_model_backward takes; the first layer's is read by tfl_model_backward_input alone) and the skip form L.ws.
+// the data-gradient form of a layer from its re-laid weight [sub][tap][cin][cout]: one slice per sub-position (an upsample layer of a
+// model enabled for training has several; the first layer, which has its own form, never upsamples)
+bool transposed_form(const tfl_layer& L, bool is3d, const std::vector<float>& relaid, std::vector<float>& wt) {
+  const int taps = layer_taps(is3d, L), S = layer_subs(is3d, L);
+  if (L.nx > 0) {
+    if (S != 1) return false;
+    tfl::relay_first_transposed(taps, L.cin, L.cout, L.nx, L.gxc, relaid.data(), wt);
+    return true;
+  }
+  wt.clear();
+  std::vector<float> one;
+  for (int sub = 0; sub < S; sub++) {
+    tfl::relay_transposed(taps, L.cin, L.cout, L.cin - (L.skip_in ? 1 : 0), relaid.data() + (size_t)sub * taps * L.cin * L.cout, one);
+    wt.insert(wt.end(), one.begin(), one.end());
+  }
+  return true;
+}
+
 bool upload_layer(tfl_layer& L, bool is3d, const float* w, const float* b, bool transposed) {
   const int taps = layer_taps(is3d, L), S = layer_subs(is3d, L);
   auto cmap = [&](int ci) {
@@ -88,9 +106,7 @@ bool upload_layer(tfl_layer& L, bool is3d, const float* w, const float* b, bool 
   if (!upload(L.w, relaid.data(), relaid.size() * sizeof(float)) || !upload(L.b, bias_p.data(), bias_p.size() * sizeof(float))) return false;
   if (!transposed) return true;
   std::vector<float> wt;
-  if (L.nx > 0) tfl::relay_first_transposed(taps, L.cin, L.cout, L.nx, L.gxc, relaid.data(), wt);
-  else tfl::relay_transposed(taps, L.cin, L.cout, L.cin - (L.skip_in ? 1 : 0), relaid.data(), wt);
-  if (!upload(L.wt, wt.data(), wt.size() * sizeof(float))) return false;
+  if (!transposed_form(L, is3d, relaid, wt) || !upload(L.wt, wt.data(), wt.size() * sizeof(float))) return false;
   if (!L.skip_in) return true;
   std::vector<float> ws;
   tfl::relay_skip(taps, L.cin, L.cout, relaid.data(), ws);
@@ -234,7 +250,7 @@ bool refresh_tables(tfl_model* m) {
     r.join_c = L.join_c; r.join_p = L.join_p; r.skip_in = L.skip_in ? 1 : 0;
     r.cin_t = L.nx > 0 ? L.gxc : L.cin - (L.skip_in ? 1 : 0);
     r.wt_first = L.nx; r.ws = L.ws;
-    r.n_w = r.S * r.taps * r.cin * r.cout; r.n_b = r.S * r.cout; r.n_wt = L.wt ? r.taps * r.cout * r.cin_t : 0;
+    r.n_w = r.S * r.taps * r.cin * r.cout; r.n_b = r.S * r.cout; r.n_wt = L.wt ? r.S * r.taps * r.cout * r.cin_t : 0;
     r.n_ws = L.ws ? r.taps : 0;
     m->refresh_elems = std::max(m->refresh_elems, r.n_w + r.n_b + r.n_wt + r.n_ws);
     tab.push_back(r);
@@ -442,6 +458,44 @@ tfl_model* tfl_model_create_graph(tfl_ctx* c, int is3D, int nconv, const int32_t
   m->pool_max = g->pool_type == TFL_POOL_MAX;
   if (!refresh_tables(m)) { tfl_model_destroy(c, m); return bad("hipMalloc failed"); }
   return m;
+}
+
+// The training-side forms of a linear model with pooling / upsampling layers, built from the weights the model
+// holds on the device. Every refusal comes before anything is allocated or written.
+int tfl_model_enable_multires_training(tfl_ctx* c, tfl_model* m) {
+  if (!c) return TFL_EINVAL;
+  const char* who = "model_enable_multires_training";
+  if (!m) return fail(c, TFL_EINVAL, "%s: null model", who);
+  if (m->zero_bias) return TFL_OK;      // (a model with a training pass already)
+  if (m->path == ConvPath::graph)
+    return fail(c, TFL_EUNSUPPORTED, "%s: graph models (tfl_model_create_graph: banks, max pooling, batch norm) with pooling or "
+                                     "ConvolutionUpsample stages stay without a training pass", who);
+  const int n = (int)m->layers.size();
+  if (n > tfl::kRefreshMaxLayers)
+    return fail(c, TFL_EUNSUPPORTED, "%s: models of more than %d layers have no training pass with pooling or ConvolutionUpsample layers",
+                who, tfl::kRefreshMaxLayers);
+  for (int l = 0; l < n; l++) {
+    const tfl_layer& L = m->layers[l];
+    if (!tfl::conv_wgrad_fits(tfl::wg_plan(m->is3d, tfl::model::train_layer(L), 1, 8, 8, 8)))
+      return fail(c, TFL_EUNSUPPORTED, "%s: layer %d (k = %d, %d input channels) does not fit the weight-gradient kernel's tile", who, l, L.k, L.cin);
+    if (L.up > 1 && (l == 0 || tfl::train_width(L.cin) != L.cin))
+      return fail(c, TFL_EUNSUPPORTED, "%s: layer %d: no data-gradient kernel for an upsample layer of %d input channels", who, l, L.cin);
+  }
+  // every launch that reads or writes the weights is done before they are read back
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  tfl_layer& F = m->layers[0];
+  F.nx = m->in_c - 1; F.gxc = tfl::ig_width(m->in_c - 1);      // (build_layers: the first layer's form)
+  for (tfl_layer& L : m->layers) {
+    std::vector<float> relaid((size_t)layer_subs(m->is3d, L) * layer_taps(m->is3d, L) * L.cin * L.cout), wt;
+    HIP_TRY(c, hipMemcpy(relaid.data(), L.w, relaid.size() * sizeof(float), hipMemcpyDeviceToHost));
+    if (!transposed_form(L, m->is3d, relaid, wt) || !upload(L.wt, wt.data(), wt.size() * sizeof(float)))
+      return fail(c, TFL_EHIP, "%s: uploading the data-gradient weights failed", who);
+  }
+  if (!refresh_tables(m)) return fail(c, TFL_EHIP, "%s: hipMalloc failed", who);
+  // (last: the model counts as trainable only once everything else is in place)
+  const std::vector<float> zeros(64, 0.0f);
+  if (!upload(m->zero_bias, zeros.data(), zeros.size() * sizeof(float))) return fail(c, TFL_EHIP, "%s: hipMalloc failed", who);
+  return TFL_OK;
 }
 
 void tfl_model_destroy(tfl_ctx* c, tfl_model* m) {

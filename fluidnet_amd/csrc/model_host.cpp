@@ -268,8 +268,9 @@ void forward_mfma2d(const tfl_model* m, const ModelWs& w, const Fwd& a) {
 // Every other linear model, layer by layer on the shape-generic kernels. The planes of every launch: the whole grid, or (a
 // z-window [za, zb) on a 3-D model: a z-slab rank's owned planes) the cone of the planes the velocity update reads, layer by
 // layer (model_cone).
-// outs (tfl_model_forward_train): where each layer's output goes instead of the act[] ping-pong -- the tape.
-int tfl::model::generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a, float* const* outs) {
+// outs (tfl_model_forward_train): where each layer's output goes instead of the act[] ping-pong -- the tape; pooled_to: the same
+// for the pooled output of a pooling layer.
+int tfl::model::generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a, float* const* outs, float* const* pooled_to) {
   hipStream_t st = a.st;
   const int B = a.B, Z = a.Z, Y = a.Y, X = a.X;
   const bool windowed = a.sc.windowed();
@@ -321,7 +322,7 @@ int tfl::model::generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w
     Yc *= L.up; Xc *= L.up;
     in = out;
     if (L.pool > 1) {
-      float* pooled = in == w.act[0] ? w.act[1] : w.act[0];
+      float* pooled = (pooled_to && pooled_to[l]) ? pooled_to[l] : in == w.act[0] ? w.act[1] : w.act[0];
       if (windowed) span(cone.layer[l].pool_lo, cone.layer[l].pool_hi, 2 * cone.layer[l].conv_d, Zc / 2, z0, nz);
       else { z0 = 0; nz = -1; }
       tfl::avg_pool2(st, m->is3d, B * L.cout, Zc, Yc, Xc, in, pooled, z0, nz);

@@ -14,13 +14,14 @@ using tfl::fail; using tfl::check_flags; using tfl::check_vel; using tfl::check_
 using namespace tfl::model;
 
 namespace {
-// Linear models without pooling / upsampling, and graph models whose modules neither pool nor upsample and that hold no batch
-// norm (they hold the data-gradient weights: build_layers); the rest is refused by name
+// Linear models without pooling / upsampling, linear models with them once tfl_model_enable_multires_training has built their
+// training-side forms, and graph models whose modules neither pool nor upsample and that hold no batch norm
+// (they all hold the data-gradient weights and the zero bias: build_layers); the rest is refused by name
 int train_gate(tfl_ctx* c, const tfl_model* m, const char* who) {
   if (m->path == ConvPath::graph && !m->zero_bias)
     return fail(c, TFL_EUNSUPPORTED, "%s: graph models (tfl_model_create_graph) with batch norm, with pooling or ConvolutionUpsample stages, or "
                                      "with a module the weight-gradient kernel's tile cannot hold have no training pass", who);
-  if (m->path != ConvPath::graph && (m->multires || !m->zero_bias))
+  if (m->path != ConvPath::graph && !m->zero_bias)
     return fail(c, TFL_EUNSUPPORTED, "%s: models with pooling or ConvolutionUpsample layers (`tog`) have no training pass: the "
                                      "backward of pooling and of the pixel shuffle is not built", who);
   return TFL_OK;
@@ -30,12 +31,26 @@ bool trainable_at(const tfl_model* m, int B, int Z, int Y, int X) { return m && 
 std::vector<tfl::TrainLayer> train_layers(const tfl_model* m) {
   std::vector<tfl::TrainLayer> v;
   const bool mres = m->banks > 1 && m->bank_type == TFL_BANKS_MRES;
+  int sh = 0;      // a linear model with pooling / upsampling layers: the shift of the current activations
   for (const tfl_layer& L : m->layers) {
     tfl::TrainLayer t = train_layer(L);
     t.sh = (mres && L.stage >= m->split && L.stage < m->join) ? L.bank : 0;
+    if (multires_trainable(m)) {
+      t.sh = sh;
+      sh += (L.pool > 1 ? 1 : 0) - (L.up > 1 ? 1 : 0);
+    }
     v.push_back(t);
   }
   return v;
+}
+// a linear model with pooling / upsampling layers takes grids its coarsest level divides (generic_forward's own refusal, said
+// before anything is enqueued)
+int multires_gate(tfl_ctx* c, const tfl_model* m, const tfl_tensor* flags, const char* who) {
+  if (!multires_trainable(m)) return TFL_OK;
+  const int f = m->max_down;
+  if ((m->is3d && flags->Z % f) || flags->Y % f || flags->X % f)
+    return fail(c, TFL_EINVAL, "%s: grid %dx%dx%d is not divisible by the model's pooling factor %d", who, flags->Z, flags->Y, flags->X, f);
+  return TFL_OK;
 }
 static_assert(tfl::kTrainMaxBanks == tfl::kMaxJoinBanks, "tfl_train.hpp and tfl_host.hpp disagree on the most banks");
 // the banked modules of the layer table (n = 1: none)
@@ -93,6 +108,7 @@ struct Backward {
   int module(int l, int Zl, int Yl, int Xl, const float* x, const float* y, int ych, float* gl, float* gout);
   int banks(float* g, float* g2);
   int trunk();             // every module from the last to the first, the banks where they sit
+  int trunk_multires();    // the same for a linear model whose resolution changes from layer to layer
   int input_head();        // behind the first layer's data gradient: the gradients to pDiv and UDiv
 };
 
@@ -115,6 +131,7 @@ int Backward::validate() {
   if (B > kMaxBatch) return fail(c, TFL_EINVAL, "%s: batch size above %d", who, kMaxBatch);
   tl = train_layers(m);
   TRY(graph_gate(c, m, flags, who));
+  TRY(multires_gate(c, m, flags, who));
   bk = train_banks(m);
   t = tfl::tape_layout(tl, B, Z, Y, X, &bk);
   TRY(check_buffer(c, who, "tape", tape, tape_floats, t.total));
@@ -256,6 +273,46 @@ int Backward::trunk() {
   return TFL_OK;
 }
 
+// A linear model with pooling / upsampling layers. Layer l's convolution runs on grid >> sh_l; g arrives at the
+// resolution of what the next layer read. A pooling layer first takes it back through the pool, masked by its own activation in
+// the same pass (pool_bwd_mask, into the other buffer); an upsample layer's weight gradient reads g where the shuffle put it and
+// its data gradient adds the sub-positions inside one launch (up_dgrad). Neither the skip channel nor banks exist here.
+int Backward::trunk_multires() {
+  float* g = ws + w.g0;
+  float* g2 = ws + w.g1;
+  const int nl = (int)tl.size();
+  for (int l = nl - 1; l >= 0; l--) {
+    const tfl_layer& L = m->layers[l];
+    const tfl::TrainLayer& T = tl[l];
+    const int Zi = m->is3d ? Z >> T.sh : Z, Yi = Y >> T.sh, Xi = X >> T.sh;                 // the convolution's grid
+    const int Zo = m->is3d ? Zi * T.up : Zi, Yo = Yi * T.up, Xo = Xi * T.up;                // its output's, behind the shuffle
+    const float* x = l == 0 ? tape + t.x : tl[l - 1].pool > 1 ? tape + t.pooled[l - 1] : tape + t.out[l - 1];
+    const float* y = l + 1 < nl ? tape + t.out[l] : nullptr;
+    if (T.pool > 1) {
+      tfl::pool_bwd_mask(st, m->is3d, B * L.cout, Zo, Yo, Xo, y, g, g2, act);
+      std::swap(g, g2);
+      y = nullptr;      // (g is masked already)
+    }
+    const bool dgrad = l > 0 || want_in;
+    if (params) {
+      const tfl::WgPlan p = tfl::wg_plan(m->is3d, T, B, Z, Y, X);
+      if (!tfl::conv_wgrad(st, m->is3d, p, B, Zi, Yi, Xi, L.cin, L.cout, L.k, x, g, y, y ? L.cout : 0, act, dgrad && y, partials))
+        return fail(c, TFL_EUNSUPPORTED, "%s: no weight-gradient kernel for layer %d (%d output channels)", who, l, L.cout);
+      tfl::conv_wgrad_finish(st, p, L.cin, L.cout, L.cin_ref, L.cout_ref, 0, partials, gradWeights[l], gradBiases[l], accumulate != 0, 0, 0);
+    } else if (y) {
+      tfl::act_mask(st, B, L.cout, L.cout, (long long)Zo * Yo * Xo, g, y, act);
+    }
+    if (!dgrad) break;
+    float* gout = l > 0 ? g2 : ws + ig.gx;
+    const int gin_c = L.nx > 0 ? L.gxc : L.cin;
+    const bool ok = T.up > 1 ? tfl::up_dgrad(st, m->is3d, B, Zi, Yi, Xi, T.up, L.cout, gin_c, L.k, g, L.wt, gout)
+                             : tfl::conv_direct(st, m->is3d, B, Zi, Yi, Xi, L.cout, gin_c, L.k, 0, g, L.wt, m->zero_bias, gout);
+    if (!ok) return fail(c, TFL_EUNSUPPORTED, "%s: no kernel for %d channels", who, gin_c);
+    std::swap(g, g2);
+  }
+  return TFL_OK;
+}
+
 // behind the first layer's data gradient: the scale's gradient and the head (input_grad.hip)
 int Backward::input_head() {
   const tfl::IgChans ch = input_chans(m);
@@ -293,7 +350,7 @@ int model_backward(tfl_ctx* c, tfl_model* m, const char* who, const tfl_tensor* 
   Backward b{c, m, who, flags, gradP, gradU, tape, tape_floats, workspace, workspace_floats, gradWeights, gradBiases, accumulate, in};
   TRY(b.validate());
   TRY(b.head_gradient());
-  TRY(b.trunk());
+  TRY(multires_trainable(m) ? b.trunk_multires() : b.trunk());
   if (b.want_in) TRY(b.input_head());
   return check_launch(c, who);
 }
@@ -323,6 +380,7 @@ int tfl_model_forward_train(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, co
   if (sc.stages || sc.windowed()) return fail(c, TFL_EINVAL, "%s: clear the z-window / stage mask first", who);
   const int B = flags->B, Z = flags->Z, Y = flags->Y, X = flags->X;
   TRY(graph_gate(c, m, flags, who));
+  TRY(multires_gate(c, m, flags, who));
   const tfl::TrainBanks bk = train_banks(m);
   const tfl::TapeLayout t = tfl::tape_layout(train_layers(m), B, Z, Y, X, &bk);
   TRY(check_buffer(c, who, "tape", tape, tape_floats, t.total));
@@ -335,8 +393,11 @@ int tfl_model_forward_train(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, co
   Fwd a{c->stream, B, Z, Y, X, pDiv->data, UOut->data, flags->data, m->d_stats, (double)Z * Y * X * (m->is3d ? 3 : 2), sc, false};
   if (m->custom) TRY(opts_stats(c, m, w, a));
   w.x3 = tape + t.x; w.pPred = tape + t.pPred;
-  std::vector<float*> outs;
-  for (size_t l = 0; l < m->layers.size(); l++) outs.push_back(l + 1 < m->layers.size() ? tape + t.out[l] : w.pPred);
+  std::vector<float*> outs, pooled;
+  for (size_t l = 0; l < m->layers.size(); l++) {
+    outs.push_back(l + 1 < m->layers.size() ? tape + t.out[l] : w.pPred);
+    pooled.push_back(m->layers[l].pool > 1 && l < t.pooled.size() && t.pooled[l] > 0 ? tape + t.pooled[l] : nullptr);
+  }
   if (m->path == ConvPath::graph) {
     GraphTape gt{};
     gt.out = outs;
@@ -344,7 +405,7 @@ int tfl_model_forward_train(tfl_ctx* c, tfl_model* m, const tfl_tensor* pDiv, co
     gt.join = bk.any() ? tape + t.join : nullptr;
     TRY(graph_forward(c, m, w, a, &gt));
   } else {
-    TRY(generic_forward(c, m, w, a, outs.data()));
+    TRY(generic_forward(c, m, w, a, outs.data(), pooled.data()));
   }
   tfl::model_project(a.st, sc, m->is3d, B, Z, Y, X, w.pPred, flags->data, a.st_in, a.count, UOut->data, UOut->data, pOut->data, nullptr, nullptr, 0,
                      0.0f, 0.0f, nullptr, nullptr, nullptr, nullptr, nullptr, wall_code_of(c, m, flags), nullptr, ask.fold);

@@ -479,6 +479,15 @@ void scale_add(hipStream_t st, int B, long long per, const double* stats, double
 // backward pass that asks for no parameter gradients (tfl_model_backward_input with NULL gradient tables)
 void act_mask(hipStream_t st, int B, int cout, int ych, long long cells, float* g, const float* y, int act);
 
+// multires_bwd.hip: the backward of pooling and of the pixel shuffle in a linear model; no atomics.
+// pool_bwd_mask: dst[row][fine] = act'(y[row][fine]) gc[row][fine >> 1] / 2^dim over `rows` = B * C planes [Z][Y][X] (gc at half
+// the resolution; Y, X and in 3-D Z even). act as conv_wgrad's.
+void pool_bwd_mask(hipStream_t st, bool is3d, int rows, int Z, int Y, int X, const float* y, const float* gc, float* dst, int act);
+// up_dgrad: the data gradient of an upsample layer, gin [B][cin_t] on the layer's input grid [Z][Y][X] from g [B][gch] at `up`
+// times the resolution and wt [sub][tap][gch][cin_t]; false = no kernel for cin_t planes (nothing launched)
+bool up_dgrad(hipStream_t st, bool is3d, int B, int Z, int Y, int X, int up, int gch, int cin_t, int ksz, const float* g, const float* wt,
+              float* gin);
+
 // conv_bwd.hip: the fixed linear maps of a banked model, backwards; fixed-order fp32 sums, no atomics.
 // join_bwd: from g [B][och] at the join's output [Z][Y][X], bank i's gradient dst[i] [B][C] at (grid >> sh[i]) -- its channel slice
 // (concat) or all channels (add); sh = 0 a copy, else the sum over the block of cells the nearest up-sample replicated.

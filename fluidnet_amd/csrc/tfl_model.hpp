@@ -28,7 +28,8 @@ struct tfl_layer {
   int cin_ref = 0, cout_ref = 0, join_c = 0, join_p = 0;
   bool skip_in = false;
   float* wt = nullptr; // device, trainable models: the data-gradient form [tap][cout][cin] (tfl_train.hpp); the first layer's has
-                       // gxc input planes of which the first nx are real (relay_first_transposed: tfl_model_backward_input)
+                       // gxc input planes of which the first nx are real (relay_first_transposed: tfl_model_backward_input);
+                       // an upsample layer's (tfl_model_enable_multires_training) is [sub][tap][cout][cin], one per sub-position
   int nx = 0, gxc = 0; // first layer of a trainable model: the net input's planes without the occupancy channel, and padded
   float* ws = nullptr; // device, the last layer of a trainable model with the joined skip channel: its gradient's form [tap]
 };
@@ -99,6 +100,7 @@ inline int layer_subs(bool is3d, const tfl_layer& L) { return is3d ? L.up * L.up
 inline TrainLayer train_layer(const tfl_layer& L) {
   TrainLayer t{L.cin, L.cout, L.cin_ref, L.cout_ref, L.k, L.skip_in ? 1 : 0};
   t.dil = L.dil;
+  t.pool = L.pool; t.up = L.up;
   return t;
 }
 // a caller's float buffer (`what`: workspace, tape): there, long enough and 8-byte aligned -- or the refusal, under the entry's name
@@ -111,6 +113,8 @@ inline int check_buffer(tfl_ctx* c, const char* who, const char* what, const flo
 // -- model_build.cpp --
 // what tfl_model_set_weights_device (and so tfl_optim_step) cannot do, said before anything is launched
 int refresh_gate(tfl_ctx* c, const tfl_model* m, const char* who);
+// a linear model with pooling / upsampling layers that tfl_model_enable_multires_training has given its training-side forms
+inline bool multires_trainable(const tfl_model* m) { return m->path != ConvPath::graph && m->multires && m->zero_bias; }
 // the elements of every layer's cudnn weight and bias, {weight, bias} per layer in layer order (the optimiser's flat space)
 std::vector<long long> param_counts(const tfl_model* m);
 
@@ -138,7 +142,9 @@ int opts_stats(tfl_ctx* c, const tfl_model* m, const ModelWs& w, Fwd& a);
 // The two shape-generic forwards; tfl_model_forward_train hands them the tape as their destinations (gt / outs).
 struct GraphTape { std::vector<float*> out; float* pyr[kMaxJoinBanks]; float* join; };
 int graph_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a, const GraphTape* gt = nullptr);
-int generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a, float* const* outs = nullptr);
+// (pooled: where a pooling layer's pooled output goes, per layer; null entries and a null table: the act[] ping-pong)
+int generic_forward(tfl_ctx* c, const tfl_model* m, const ModelWs& w, const Fwd& a, float* const* outs = nullptr,
+                    float* const* pooled = nullptr);
 
 }  // namespace model
 }  // namespace tfl

@@ -67,13 +67,14 @@ TFL_HD inline int refresh_b_src(const RefreshLayer& L, int d) {
   const int co = d % L.cout, sub = d / L.cout;
   return co < L.cout_ref ? co * L.S + sub : -1;
 }
-// element d of wt -> its element of the cudnn weight, or -1: wt[tap][co][ci] = w[taps - 1 - tap][ci][co] (sub-position 0)
+// element d of wt -> its element of the cudnn weight, or -1: wt[sub][tap][co][ci] = w[sub][taps - 1 - tap][ci][co] (n_wt covers
+// sub-position 0 alone, or -- an upsample layer of a model enabled for training -- all S)
 TFL_HD inline long long refresh_wt_src(const RefreshLayer& L, int d) {
-  const int cp = d % L.cin_t, co = (d / L.cin_t) % L.cout, t = d / (L.cin_t * L.cout);
+  const int cp = d % L.cin_t, co = (d / L.cin_t) % L.cout, t = (d / (L.cin_t * L.cout)) % L.taps, sub = d / (L.cin_t * L.cout * L.taps);
   if (L.wt_first > 0 && cp >= L.wt_first) return -1;
   const int ci = refresh_ci_of_plane(L, cp);
   if (co >= L.cout_ref || ci < 0) return -1;
-  return (((long long)co * L.S) * L.cin_ref + ci) * L.taps + (L.taps - 1 - t);
+  return (((long long)co * L.S + sub) * L.cin_ref + ci) * L.taps + (L.taps - 1 - t);
 }
 // element d of ws -> its element of the cudnn weight: ws[tap] = w[taps - 1 - tap][skip plane][0] (sub-position 0)
 TFL_HD inline long long refresh_ws_src(const RefreshLayer& L, int d) {

@@ -63,7 +63,17 @@ inline void relay_skip(int taps, int cin_p, int cout_p, const float* relaid, std
 // the joined pressure-skip channel.
 // A module of a banked model also has its tap spacing `dil` (dilate banks: 2^bank) and the resolution it runs at,
 // grid >> sh per pooled axis (mres banks: sh = bank).
-struct TrainLayer { int cin, cout, cin_ref, cout_ref, k, skip_in; int dil = 1, sh = 0; };
+// A layer of a linear model that changes the resolution has `pool` = 2 (2x average pooling behind its
+// activation) or `up` = 2 (ConvolutionUpsample: up^dim sub-position convolutions whose outputs are pixel-shuffled); its
+// convolution runs at grid >> sh, its output out[l] lies at grid >> train_out_sh, and what the next layer reads at one more
+// shift where it pools.
+struct TrainLayer { int cin, cout, cin_ref, cout_ref, k, skip_in; int dil = 1, sh = 0; int pool = 1, up = 1; };
+inline int train_subs(bool is3d, const TrainLayer& L) { return is3d ? L.up * L.up * L.up : L.up * L.up; }
+inline int train_out_sh(const TrainLayer& L) { return L.sh - (L.up > 1 ? 1 : 0); }
+inline bool train_multires(const std::vector<TrainLayer>& L) {
+  for (const TrainLayer& l : L) if (l.pool > 1 || l.up > 1) return true;
+  return false;
+}
 
 // The banks of a graph model as the training side sees them: modules [l0, l0 + nst * n) of the layer table are banked, module
 // l0 + s * n + i = stage s of bank i. n = 1: a linear model. gxc: the width of the first layer's data gradient (ig_width), which
@@ -101,9 +111,15 @@ inline int train_och(const std::vector<TrainLayer>& L, size_t l) { return L[l].c
 //              i's first input, the x of its first weight gradient. Kept rather than pooled again in the backward: at 1/2^dim of
 //              the level above it costs an eighth (a quarter) of one activation, against one more launch per level and pass.
 //   join       the join's output, [B][join_c] planes at the grid's resolution: the x of the first stage behind the join
+// A linear model with pooling / upsampling layers: out[l] is the post-activation output at the convolution's output resolution
+// (an upsample layer's: behind the shuffle) -- what the activation mask reads --, and a pooling layer also keeps
+//   pooled[l]  its pooled output, [B][cout] planes at half that resolution: the x of the next layer's weight gradient. Kept
+//              rather than pooled again in the backward, for the reason the pyramid is kept: 1/2^dim of one activation against
+//              one more launch per pooling layer and pass.
 struct TapeLayout {
   int64_t stats, x, pPred, total;
   std::vector<int64_t> out;
+  std::vector<int64_t> pooled;       // (0: the layer does not pool)
   std::vector<int> planes, sh;       // of out[l]
   int64_t pyr[kTrainMaxBanks] = {0, 0, 0, 0, 0, 0, 0, 0}, join = 0;
   int pyr_c = 0, join_c = 0;
@@ -115,8 +131,11 @@ inline TapeLayout tape_layout(const std::vector<TrainLayer>& L, int B, int Z, in
   t.stats = off; off += 4 * (int64_t)B;
   t.x = off; off += (int64_t)B * Z * Y * X * L[0].cin;
   for (size_t l = 0; l + 1 < L.size(); l++) {
-    t.out.push_back(off); t.planes.push_back(train_och(L, l)); t.sh.push_back(L[l].sh);
-    off += (int64_t)B * train_cells(is3d, L[l].sh, Z, Y, X) * train_och(L, l);
+    const int osh = train_out_sh(L[l]);
+    t.out.push_back(off); t.planes.push_back(train_och(L, l)); t.sh.push_back(osh);
+    off += (int64_t)B * train_cells(is3d, osh, Z, Y, X) * train_och(L, l);
+    t.pooled.push_back(L[l].pool > 1 ? off : 0);
+    if (L[l].pool > 1) off += (int64_t)B * train_cells(is3d, osh + 1, Z, Y, X) * L[l].cout;
   }
   if (bk && bk->any()) {
     t.pyr_c = L[bk->l0].cin;
@@ -178,12 +197,15 @@ TFL_HD inline int wg_red_slot(const WgThread& t, const WgChunk& c, int s, int cb
 TFL_HD inline long long wg_partial_slot(int blk, int M, int row, int cout, int co) { return ((long long)blk * (M + 1) + row) * cout + co; }
 
 // (Z, Y, X: the grid; the plan is that of the module's own resolution, grid >> L.sh)
-struct WgPlan { int taps, cb, ch, tt, S, nblocks, halo_floats, lds_floats; int64_t tiles, partial_doubles; int dil; };
+// An upsample layer is its inner convolution: subs * cout output channels on the layer's input grid, channel sub * cout + co
+// = output channel co at sub-position sub (vcout of them; cb divides cout, so a register block never straddles two sub-positions)
+struct WgPlan { int taps, cb, ch, tt, S, nblocks, halo_floats, lds_floats; int64_t tiles, partial_doubles; int dil; int up, subs, vcout; };
 inline WgPlan wg_plan(bool is3d, const TrainLayer& L, int B, int Z, int Y, int X) {
   WgPlan p;
   if (is3d) Z >>= L.sh;
   Y >>= L.sh; X >>= L.sh;
   p.dil = L.dil;
+  p.up = L.up; p.subs = train_subs(is3d, L); p.vcout = L.cout * p.subs;
   p.taps = train_taps(is3d, L.k);
   p.cb = L.cout < 16 ? L.cout : 16;
   p.halo_floats = wg_halo(is3d, L.k, L.dil).floats;
@@ -199,7 +221,7 @@ inline WgPlan wg_plan(bool is3d, const TrainLayer& L, int B, int Z, int Y, int X
   if (p.S > 1 && p.lds_floats < 2 * kWgThreads * p.cb) p.lds_floats = 2 * kWgThreads * p.cb;
   p.tiles = (int64_t)B * Z * ((Y + kWgTY - 1) / kWgTY) * ((X + kWgTX - 1) / kWgTX);
   // blocks: one per tile up to the count that keeps the partials of this layer near 16 MB
-  const int64_t per_block = (L.cin * (int64_t)p.taps + 1) * L.cout;
+  const int64_t per_block = (L.cin * (int64_t)p.taps + 1) * p.vcout;
   int64_t nb = (16ll << 20) / (8 * per_block);
   if (nb > 1024) nb = 1024;
   if (nb < 8) nb = 8;
@@ -229,8 +251,26 @@ TFL_HD inline long long wg_cudnn_index(int row, int co, int taps, int cin, int c
   return ((long long)co * cin_ref + cr) * taps + tap;
 }
 
+// The same for an upsample layer's inner convolution: column cv = sub * cout + co of the kernel -> output channel co * subs + sub of
+// the cudnn layout [cout_ref * subs][cin_ref][taps] (tfl_refresh.hpp refresh_w_src, the other way round), or -1 for a padded
+// plane; row < 0: the bias, [cout_ref * subs].
+TFL_HD inline long long wg_cudnn_index_up(int row, int cv, int cout, int subs, int taps, int cin, int cin_ref, int cout_ref) {
+  const int sub = cv / cout, co = cv - sub * cout;
+  if (co >= cout_ref) return -1;
+  if (row < 0) return (long long)co * subs + sub;
+  return wg_cudnn_index(row, co * subs + sub, taps, cin, cin_ref, cout_ref * subs, 0);
+}
+// The fine cell that sub-position `sub` of conv-grid cell (z, y, x) is shuffled to, as an offset into a plane at up times the
+// resolution [uz Z][up Y][up X] (uz = up in 3-D, 1 in 2-D): the forward's ConvUp (conv.hip), sub = (sz * up + sy) * up + sx.
+TFL_HD inline long long up_fine_cell(bool is3d, int up, int sub, int z, int y, int x, int Y, int X) {
+  const int sx = sub % up, sy = (sub / up) % up, sz = is3d ? sub / (up * up) : 0;
+  return ((long long)((is3d ? z * up : z) + sz) * (Y * up) + (y * up + sy)) * ((long long)X * up) + (x * up + sx);
+}
+
 // The workspace of tfl_model_backward, in floats from its 8-byte aligned start: the fp64 partials of the widest layer, two
 // gradient buffers of `gc` planes (g_out of a layer and its g_in), and the velocity-gradient scratch [B][C].
+// A linear model with pooling / upsampling layers walks grids of several resolutions: its two buffers hold the
+// largest gradient any layer has at its own resolution, which is less than gc planes of the full grid.
 // A banked model (bk) has behind them two gradient buffers per bank, gb[i][0 | 1], of `gbc` planes at the bank's resolution: the
 // join's backward fills one, the bank's layers walk the pair, and the split's backward reads the banks' last.
 struct BwdLayout { int64_t partials, g0, g1, gu, total; int gc; int64_t gb[kTrainMaxBanks][2]; int gbc; };
@@ -248,10 +288,23 @@ inline BwdLayout bwd_layout(bool is3d, const std::vector<TrainLayer>& L, int B, 
     if (&l != &L[0] && train_width(l.cin - l.skip_in) > gc) gc = train_width(l.cin - l.skip_in);
   }
   w.gc = gc;
+  // (a linear model with pooling / upsampling layers: the widest layer at its own resolution -- its gradient at the convolution's
+  // output and its data gradient at the convolution's input --, rounded to 16 bytes for k_pool_bwd_mask's stores)
+  int64_t gn = n * gc;
+  if (train_multires(L)) {
+    gn = n;
+    for (const TrainLayer& l : L) {
+      const int64_t go = (int64_t)B * train_cells(is3d, train_out_sh(l), Z, Y, X) * l.cout;
+      const int64_t gi = &l != &L[0] ? (int64_t)B * train_cells(is3d, l.sh, Z, Y, X) * train_width(l.cin - l.skip_in) : 0;
+      if (go > gn) gn = go;
+      if (gi > gn) gn = gi;
+    }
+    gn = (gn + 3) & ~(int64_t)3;
+  }
   w.partials = 0;
   w.g0 = 2 * pd;
-  w.g1 = w.g0 + n * gc;
-  w.gu = w.g1 + n * gc;
+  w.g1 = w.g0 + gn;
+  w.gu = w.g1 + gn;
   w.total = w.gu + n * (is3d ? 3 : 2);
   if (bk && bk->any()) {
     int gbc = bk->l0 == 0 ? (bk->gxc > L[0].cin ? bk->gxc : L[0].cin) : L[bk->l0].cin;

@@ -186,6 +186,7 @@ int tfl_model_finish(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* pDiv, con
                      int64_t workspace_floats, const double* stats, double count, const tfl_tensor* UBC,
                      const tfl_tensor* UBCInvMask, int doClamp, float lo, float hi);
 int tfl_model_set_weights(tfl_ctx* ctx, tfl_model* model, const float* const* weights, const float* const* biases);
+int tfl_model_enable_multires_training(tfl_ctx* ctx, tfl_model* model);
 int64_t tfl_model_tape_floats(const tfl_model* model, int B, int Z, int Y, int X);
 int tfl_model_forward_train(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* pDiv, const tfl_tensor* UDiv,
                             const tfl_tensor* flags, const tfl_tensor* pOut, const tfl_tensor* UOut, float* workspace,
@@ -562,7 +563,10 @@ end
 -- with it the graph is walked as a whole (graph_walk: banks, dilation, pooling, batch norm; tfl_model_create_graph).
 -- Without it, a graph holding batch-norm, dilated, pooling, upsampling or bank-join nodes is refused: the flat walk below
 -- would drop them.
-function M.Model(gmodule, mconf)
+-- opts (optional): {train = true} gives a linear model with pooling / ConvolutionUpsample layers (`tog`) its training pass at
+-- creation (tfl_model_enable_multires_training); a model that trains anyway is left as it is, a graph model (banks, max
+-- pooling, batch norm) with such stages raises the library's refusal.
+function M.Model(gmodule, mconf, opts_)
   if mconf == nil then
     for _, node in ipairs(gmodule.forwardnodes) do
       local tn = node.data.module and torch.type(node.data.module) or ''
@@ -650,6 +654,7 @@ function M.Model(gmodule, mconf)
   end
   if self.handle == nil then error(ffi.string(lib.tfl_last_error(ctx)), 2) end
   ffi.gc(self.handle, function(h) lib.tfl_model_destroy(ctx, h) end)
+  if opts_ and opts_.train then check(lib.tfl_model_enable_multires_training(ctx, self.handle)) end
   return self
 end
 
@@ -674,7 +679,8 @@ function Model:cuda() return self end
 function Model:rangeErrors() return tonumber(lib.tfl_model_range_errors(ctx, self.handle)) end
 function Model:rangeFlag() return tonumber(lib.tfl_model_range_flag(ctx, self.handle)) end
 
--- The training side (linear and banked models without batch norm, pooling / upsampling -- include/tfluids_hip.h): the parameter gradients and, on
+-- The training side (linear and banked models without batch norm, pooling / upsampling -- include/tfluids_hip.h; a linear model
+-- with pooling / upsampling layers once it is created with {train = true}): the parameter gradients and, on
 -- request, the gradients to pDiv and UDiv (model:backward's wantGradInput).
 -- model:setWeights(weights, biases): tables of FloatTensors laid out like the convolutions' weight / bias, copied into the
 -- model's own buffers (synchronous; re-record any slab graph built on the model).
@@ -696,7 +702,7 @@ function Model:forwardTrain(input)
   local B, Z, Y, X = flags:size(1), flags:size(3), flags:size(4), flags:size(5)
   local ws, n = workspace(pDiv, lib.tfl_model_workspace_floats(self.handle, B, Z, Y, X))
   local nt = tonumber(lib.tfl_model_tape_floats(self.handle, B, Z, Y, X))
-  if nt < 0 then error('this model has no training pass (graph model, pooling or upsampling layers)', 2) end
+  if nt < 0 then error('this model has no training pass (graph model; pooling or upsampling layers without {train = true})', 2) end
   self.tape = self.tape or pDiv.new()
   self.tape:resize(nt)
   check(lib.tfl_model_forward_train(ctx, self.handle, T(pDiv), T(UDiv), T(flags), T(self.p), T(self.U), ws, n,

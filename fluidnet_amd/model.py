@@ -302,6 +302,12 @@ class FluidNetModel:
                                                ctypes.byref(copts), ctypes.byref(cg))
             if not h:
                 raise TfluidsError(lib.tfl_last_error(ctx).decode())
+            if getattr(self, "_multires_training", False):
+                # ProjectionNet(multires=True): the training-side forms of a linear model with pooling / upsampling layers
+                if lib.tfl_model_enable_multires_training(ctx, h) != 0:
+                    why = lib.tfl_last_error(ctx).decode()
+                    lib.tfl_model_destroy(ctx, h)
+                    raise TfluidsError(why)
             self._handles[dev] = h
         return h
 

@@ -60,16 +60,25 @@ class ProjectionNet(torch.nn.Module):
     when something reads it, or when a handle is created on a device that has none.
     Accepted wherever simulate() takes a model. Linear models without pooling / upsampling layers can be trained, and so can
     banked models ('mres' / 'dilate' banks, 'concat' / 'add' joins) without batch norm and without pooling / upsampling stages; the
-    others run in eval mode only (training raises, naming the reason).
+    others run in eval mode only (training raises, naming the reason) -- unless they are linear and the module is created with
+    multires=True (below).
+    multires=True: a linear model with 2x average pooling / ConvolutionUpsample layers (`tog`, custom layer tables) gets its
+    training pass when its native model is created (tfl_model_enable_multires_training). Nothing changes for a model that can be
+    trained anyway; a model the call does not take (banked `tog`, max pooling, batch norm) raises the library's refusal.
     input_grad=True: pDiv and UDiv may require grad, and backward returns their gradients (tfl_model_backward_input) -- two
     passes can be chained, net(*net(pDiv, UDiv, flags), flags), or torch code put in front. flags never gets a gradient."""
 
-    def __init__(self, net, device="cuda", input_grad=False):
+    def __init__(self, net, device="cuda", input_grad=False, multires=False):
         super().__init__()
         self.input_grad = bool(input_grad)
+        self.multires = bool(multires)
         if not isinstance(net, FluidNetModel):
             raise TfluidsError("ProjectionNet wraps a FluidNetModel")
         self.net = net
+        if self.multires:
+            if net._handles and not getattr(net, "_multires_training", False):
+                raise TfluidsError("ProjectionNet(multires=True): this FluidNetModel has a native model already; wrap a fresh one")
+            net._multires_training = True
         dev = torch.device(device)
         self.weights = torch.nn.ParameterList([torch.nn.Parameter(torch.from_numpy(w.copy()).to(dev)) for w, _ in net.layers])
         self.biases = torch.nn.ParameterList([torch.nn.Parameter(torch.from_numpy(b.copy()).to(dev)) for _, b in net.layers])

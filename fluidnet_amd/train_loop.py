@@ -69,6 +69,15 @@ def _log_line(trPerf, tePerf):
     return "\t".join("%.8e" % p[k] for p in (trPerf, tePerf) for k in _PERF)
 
 
+def _module_for(model, device):
+    """the ProjectionNet fit() makes by itself: a linear model with pooling / upsampling layers (`tog`) opts in to its training
+    pass (ProjectionNet(multires=True)); every other model is wrapped as it always was"""
+    g = model.graph      # (a graph of one bank, average pooling and no batch norm is a linear model: tfl_model_create_graph)
+    linear = g is None or (g["banksNum"] == 1 and not g["addBatchNorm"] and g["poolType"] == "avg")
+    multires = linear and any(v > 1 for v in list(model.pool) + list(model.up))
+    return ProjectionNet(model, device=device, multires=multires)
+
+
 def fit(conf, mconf, tr, te=None, net=None, comm=None, resume=None):
     """Train on `tr` (a data.DataBinary) until mconf["epoch"] reaches conf["maxEpochs"]. Per epoch: the learning-rate
     multipliers of run_epoch.lua:39-48, run_epoch on tr, run_epoch(training=False) on te when evaluateDuringTraining (else tePerf =
@@ -99,7 +108,7 @@ def fit(conf, mconf, tr, te=None, net=None, comm=None, resume=None):
         r = meta["rng"]
         rs.set_state((r["kind"], np.asarray(arrays["rng_keys"], np.uint32), int(r["pos"]), int(r["has_gauss"]), float(r["cached_gaussian"])))
         if net is None:
-            net = ProjectionNet(model, device=tr.device)
+            net = _module_for(model, tr.device)
         else:
             with torch.no_grad():
                 for p, (w, b) in zip(zip(net.weights, net.biases), model.layers):
@@ -108,7 +117,7 @@ def fit(conf, mconf, tr, te=None, net=None, comm=None, resume=None):
     elif mconf is None:
         raise TfluidsError("fit: no mconf and nothing to resume from")
     if net is None:
-        net = ProjectionNet(FluidNetModel.from_mconf(mconf, tr.is3D, seed=int(conf.get("modelSeed", 1))), device=tr.device)
+        net = _module_for(FluidNetModel.from_mconf(mconf, tr.is3D, seed=int(conf.get("modelSeed", 1))), tr.device)
     if net.is3D != tr.is3D:
         raise TfluidsError("Mixing 3D model with 2D data or vice-versa!")
     net.train()

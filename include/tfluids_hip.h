@@ -490,9 +490,11 @@ int tfl_model_finish(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* pDiv, con
  * models (tfl_model_create[_ex|_opts]) whose layers neither pool nor upsample -- `default`, `yang`, custom layer tables, every
  * tfl_model_opts switch -- and for banked models (tfl_model_create_graph: banksNum 2 .. 8, 'mres' or 'dilate' banks, 'concat' or
  * 'add' joins, any legal split / join stage) that hold no batch norm and whose modules neither pool nor upsample. Graph models
- * with batch norm (it needs a training-mode forward), models with pooling / ConvolutionUpsample layers (`tog`, banked or not:
- * the pixel-shuffle backward is not built) and a module the weight-gradient kernel's tile cannot hold at its tap spacing are
- * refused with TFL_EUNSUPPORTED before anything is written, and the size queries answer -1 for them. tfl_model_backward gives the parameter gradients (the reference computes a
+ * with batch norm (it needs a training-mode forward), models with pooling / ConvolutionUpsample layers (`tog`, banked or not)
+ * and a module the weight-gradient kernel's tile cannot hold at its tap spacing are refused with TFL_EUNSUPPORTED before
+ * anything is written, and the size queries answer -1 for them -- a LINEAR model with pooling / ConvolutionUpsample layers
+ * until tfl_model_enable_multires_training (below) has been called on it, from then on it trains like the others.
+ * tfl_model_backward gives the parameter gradients (the reference computes a
  * gradInput and run_epoch.lua discards it); tfl_model_backward_input also gives the gradients to pDiv and UDiv, for training
  * through the net (an iterated projection, a loss behind a refinement pass, differentiable code in front of it). There is no
  * gradient to flags. */
@@ -504,6 +506,19 @@ int tfl_model_finish(tfl_ctx* ctx, tfl_model* model, const tfl_tensor* pDiv, con
  * tfl_slab_graph recorded with this model holds per-layer constants of the OLD weights by value: the model does not know its
  * graphs, so the caller destroys and re-records them after this call. */
 int tfl_model_set_weights(tfl_ctx* ctx, tfl_model* model, const float* const* weights, const float* const* biases);
+/* Opt-in: gives a linear model (tfl_model_create[_ex|_opts]) with 2x average pooling and / or ConvolutionUpsample layers -- the
+ * `tog` layer tables, custom ones -- its training pass. Builds, from the weights the model holds, the data-gradient form of every
+ * layer (an upsample layer's for each of its up^dim sub-positions), the first layer's padded form and the zero bias; afterwards
+ * the three size queries, tfl_model_forward_train, tfl_model_backward, tfl_model_backward_input, tfl_model_set_weights[_device]
+ * and the tfl_optim_* entries take the model as they take `default`. The tape then also keeps every pooling layer's pooled
+ * output; in the backward a pooling layer's gradient goes back through the pool and its activation mask in one pass,
+ * g_pre[fine] = act'(y[fine]) g[fine >> 1] / 2^dim, an upsample layer's weight gradient reads the gradient where the pixel
+ * shuffle put it (the mask is taken behind the shuffle) and its data gradient adds the sub-positions' transposed convolutions in
+ * one launch, in a fixed order. Until the call nothing changes: the model is refused as before. A model that has a training
+ * pass already: TFL_OK, nothing done. Refused with TFL_EUNSUPPORTED, by name and before anything is allocated or written: graph
+ * models (tfl_model_create_graph with banks, max pooling or batch norm), a layer the weight-gradient kernel's tile cannot hold,
+ * more than 32 layers. Synchronous (waits for the context's stream and reads the weights back once); not capturable. */
+int tfl_model_enable_multires_training(tfl_ctx* ctx, tfl_model* model);
 /* Floats of the tape tfl_model_forward_train fills for a [B][.][Z][Y][X] grid (-1: the model has no training pass). */
 int64_t tfl_model_tape_floats(const tfl_model* model, int B, int Z, int Y, int X);
 /* tfl_model_forward (without its fused UBC / clamp tail) that also keeps what the backward pass reads in `tape` (device,
