@@ -373,11 +373,13 @@ int64_t tfl_simulate_slab_workspace_floats(tfl_ctx* c, const tfl_sim_params* prm
 }
 
 int tfl_slab_drain(tfl_ctx* c, const tfl_sim_state* s, tfl_slab* sl, const tfl_comm* comm, float* ws, int64_t ws_floats) {
-  if (!c || !s || !sl || !comm || !ws) return TFL_EINVAL;
+  if (!c) return TFL_EINVAL;
+  if (!s || !sl || !comm || !ws) { c->err = "slab_drain: null state, slab, comm or workspace"; return TFL_EINVAL; }
   SlabGeom g;
   int rc = slab_geom(c, s, sl, &g);
   if (rc) return rc;
-  if (ws_floats < slab_ws(g, s, nullptr, nullptr)) return TFL_EINVAL;
+  // (the step's own test: a workspace the step would refuse cannot hold its messages)
+  if (((uintptr_t)ws & 15) != 0 || ws_floats < slab_ws(g, s, nullptr, nullptr)) { c->err = "slab_drain: workspace too small or misaligned"; return TFL_EINVAL; }
   Msg m[4];
   slab_messages(g, s, s->U, s->flags, m);
   msg_layout(g, m, 4, ws);

@@ -67,6 +67,35 @@ enum {
 
 typedef struct tfl_ctx tfl_ctx;
 
+/* ---- scratch memory: `workspace` and `tape` arguments ----------------------------------------------------------------------
+ * Every `float* workspace, int64_t workspace_floats` pair (and the `tape` of the training entries) is device memory the caller
+ * owns and the entry sizes with the tfl_*_workspace_floats / tfl_model_tape_floats query next to it. For all of them:
+ *   contents   undefined on entry. No entry reads a word it has not written in the same call: results, residuals, iteration
+ *              counts and error counters do not depend on what the array held before -- zeros, NaN, the leftovers of another
+ *              operator or of the same entry on another scene or grid size. The entries add in a fixed order, so that means
+ *              the same bits, with one exception: tfl_normalizePressureMean adds each component's cells with fp64 atomics,
+ *              in whatever order the waves arrive. Its sum can differ in the last bits of a double from one call to the next
+ *              (leftovers or not); the mean is rounded to fp32 before it is subtracted, so the pressure comes out different
+ *              only when the mean lies within ~1e-16 (relative) of an fp32 rounding boundary.
+ *              No region carries state from one call to the next, with two exceptions stated where they apply: the tape
+ *              (written by tfl_model_forward_train, read by the two backward entries) and the message buffers at the head of
+ *              the z-slab step's workspace while slab->in_flight is not 0 (the p / U halos in flight between two steps; a
+ *              first step, with in_flight = 0, takes the whole array undefined, and the compute region behind the buffers is
+ *              dead between steps).
+ *   size       exactly the query's value is enough, and no word outside [workspace, workspace + workspace_floats) is written
+ *              (the helper wave of the PCG wavefront sweeps READS without clamping, inside the guard pairs the query counts).
+ *              A shorter array is TFL_EINVAL before anything is enqueued or written.
+ *   alignment  8 bytes: tfl_solveLinearSystemPCG[Batched], tfl_normalizePressureMean, tfl_velocityDivergenceNorm,
+ *              tfl_fluidCriterion, tfl_model_forward / _forward_train / _backward / _backward_input and the tape (regions
+ *              that need 16 bytes are rounded up inside the array at run time, paid for by slack the query counts); such an
+ *              array at 8 mod 16 gives the bits of one at 0 mod 16. 16 bytes: tfl_simulate_step / _project,
+ *              tfl_simulate_step_items / _project_items, tfl_simulate_step_slab, tfl_slab_drain and tfl_slab_divergence_norm
+ *              (and with them tfl_model_begin / _finish as the z-slab step calls them, inside its workspace); anything less
+ *              is TFL_EINVAL with nothing written. Operators that take their temporaries as tfl_tensor arguments (advection,
+ *              vorticity confinement, Jacobi, blur) fall under the first two rules; for alignment each temporary is a tensor
+ *              like the operator's others.
+ * Held by tests/test_hip_scratch_history.py for the entries of tests/scratch_cases.py. */
+
 /* ---- context ------------------------------------------------------------------------------ */
 /* Replaces THCState (device + current stream). `device` is a HIP device ordinal. */
 tfl_ctx* tfl_create(int device);
